@@ -620,6 +620,32 @@ def _drop_notes(x):
     return {k: _drop_notes(v) for k, v in x.items() if k != "note"} if isinstance(x, dict) else x
 
 
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: all files together
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """--dump-outputs: each array (name -> tensor or ndarray) as out_dir/<name>.npy, float32 or float64.  When they hold more than
+    `max_bytes` in all, the small ones are written whole and every large one is cut to a fixed sample of its rows (sorted, drawn by
+    numpy's default_rng(seed)), written beside it as <name>_rows.npy (float64): the same arguments give the same rows, so two builds
+    compare file for file.  -> {name: shape written}."""
+    arrays = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in arrays.items()}
+    arrays = {k: (v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > max_bytes:
+        large = [k for k, a in arrays.items() if a.ndim > 0 and a.nbytes > max_bytes // 16]
+        share = (max_bytes - sum(a.nbytes for k, a in arrays.items() if k not in large)) // max(1, len(large))
+        for k in large:
+            a = arrays[k]
+            n = a.shape[0]
+            keep = min(n, share // (a.nbytes // n + 8))   # (+ 8: the row's index in <name>_rows.npy)
+            rows = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+            arrays[k], arrays[k + "_rows"] = a[rows], rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return {k: a.shape for k, a in arrays.items()}
+
+
 HEADLINE_BUDGET = 6000   # bytes; tests/test_host_cpu.py holds the line below 8 000 on canned numbers
 
 
@@ -747,7 +773,13 @@ def main():
         ap.add_argument(f"--{leg}", choices=["on", "off"], default=None, help=what + " (N = 1 only)")
     ap.add_argument("--dump", default=None, help="write the last dense step's outputs (scalars, gradient rows, rewards) to this .npz "
                                                  "(rank 0): tests compare runs at different N")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the headline's last timed step computed (rank 0's scalars, poses_grad, "
+                         "quats_grad, rewards; with --mode both also the culled path's as culled_<name>) as DIR/<name>.npy, at most 64 MB "
+                         "in all (a fixed, seeded sample of rows beyond that).  The inputs are seeded: the same arguments give the same inputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1: the timed region is exactly K steps")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started plainly: this process has not touched the GPU (importing torch does not) and never will — it starts the ranks as
         # children, relays their output and exits with their status
@@ -1118,6 +1150,12 @@ def main():
 
     if rank == 0 and args.dump:
         np.savez(args.dump, scalars=out[0].cpu().numpy(), pg=out[1].cpu().numpy(), qg=out[2].cpu().numpy(), rewards=out[3].cpu().numpy())
+    if rank == 0 and args.dump_outputs:
+        names = ("scalars", "poses_grad", "quats_grad", "rewards")
+        arrays = dict(zip(names, out))
+        if args.mode == "both":
+            arrays.update(("culled_" + k, v) for k, v in zip(names, out_c))
+        dump_outputs(args.dump_outputs, arrays)
     if rank == 0:
         # dominant kernel: pass 1, the one launch that evaluates every pair.  VALU-issue roofline (module docstring).
         mix = isa_mix()

@@ -69,6 +69,35 @@ def test_profile_age_flags_a_stale_counter_file():
     assert pmc["file"].startswith("profiles/r") and pmc["traffic"] > 1e6 and 0.05 < pmc["kernel_ms"] < 0.2
 
 
+def test_dump_outputs_writes_float_npy_within_the_cap(tmp_path):
+    """--dump-outputs: one DIR/<name>.npy per output in float32 / float64; under the cap every array whole, over it the small arrays
+    whole and the large ones cut to the same seeded rows on every run (listed in <name>_rows.npy), the files together within the cap."""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(5)
+    arrays = {"scalars": torch.tensor([0.5, 2.0, -4.0, 0.0]), "poses_grad": rng.random((64, 3)).astype(np.float32),
+              "rewards": rng.random(1_000_000).astype(np.float32), "culled_rewards": rng.random(1_000_000).astype(np.float32),
+              "counts": np.arange(10, dtype=np.int64)}
+    whole = bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    assert set(whole) == set(arrays)
+    for k, v in arrays.items():
+        a = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, np.asarray(v, np.float64)), k
+    cap = 2_000_000
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays, max_bytes=cap)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in files) <= cap   # (128: the .npy header)
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    rows = np.load(tmp_path / "a" / "rewards_rows.npy")
+    assert rows.dtype == np.float64 and len(rows) > 80_000 and (np.diff(rows) > 0).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "rewards.npy"), arrays["rewards"][rows.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "a" / "scalars.npy"), arrays["scalars"].numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "poses_grad.npy"), arrays["poses_grad"])
+
+
 _FAKE_RANK = textwrap.dedent("""
     import json, os, sys
     rank = int(os.environ["RANK"]); world = int(os.environ["WORLD_SIZE"])

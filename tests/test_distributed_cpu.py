@@ -20,6 +20,13 @@ def _free_port():
         return s.getsockname()[1]
 
 
+def _cpu_barrier():
+    """dist.barrier() first asks torch for the machine's accelerator, which starts the HIP runtime, and so opens the GPU, in every
+    rank even on a gloo group: on a GPU machine these CPU-only ranks would each hold the GPU.  An all-reduce of a CPU tensor
+    synchronises the ranks just the same without touching it."""
+    dist.all_reduce(torch.zeros(1))
+
+
 def _worker(rank, world, port, n_pts, n_wps, out_dir):
     sys.path.insert(0, REPO)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
@@ -60,7 +67,7 @@ def _worker(rank, world, port, n_pts, n_wps, out_dir):
         assert torch.equal(gathered, torch.cat([pg, qg], dim=1))
     np.savez(os.path.join(out_dir, f"rank{rank}.npz"), rewards=rewards.numpy(), pg=pg.numpy(), qg=qg.numpy(),
              bounds=np.array([lo, hi]), gathered=np.zeros(0) if gathered is None else gathered.numpy())
-    dist.barrier()
+    _cpu_barrier()
     dist.destroy_process_group()
 
 
@@ -165,7 +172,7 @@ def _worker_points(rank, world, port, n_pts, n_wps, out_dir):
     pg, qg = oracle.traj_backward_final(poses, quats, partial[8:].reshape(n_wps, 40), -vis * vis / partial[2], prec="f64")
     np.savez(os.path.join(out_dir, f"rank{rank}.npz"), rewards=rewards, bounds=np.array([lo, hi]), pg=pg, qg=qg, vis=vis, gmin=gmin32, gmax=gmax32,
              gmin64=gmin, gmax64=gmax, n_all=partial[2])
-    dist.barrier()
+    _cpu_barrier()
     dist.destroy_process_group()
 
 

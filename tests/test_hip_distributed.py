@@ -184,15 +184,33 @@ _BENCH_COMMON = ["--points", "200000", "--steps", "2", "--warmup", "1", "--cpu-w
 
 
 @pytest.fixture(scope="module")
-def bench_one_rank(tmp_path_factory):
+def bench_one_rank_dir(tmp_path_factory):
     import json
     d = tmp_path_factory.mktemp("bench")
-    out = _run([sys.executable, "bench.py", "--gpus", "1", "--wps-per-gpu", "64", "--dump", str(d / "n1.npz")] + _BENCH_COMMON, {})
+    out = _run([sys.executable, "bench.py", "--gpus", "1", "--wps-per-gpu", "64", "--dump", str(d / "n1.npz"),
+                "--dump-outputs", str(d / "outputs")] + _BENCH_COMMON, {})
     last = out.strip().splitlines()[-1]
     assert len(last) < 8000      # the driver keeps an 8 KB tail of stdout: the headline must fit it whole
     line = json.loads(last)
     assert line["n_gpus"] == 1 and line["roofline"]["bound"] == "valu" and 0.0 < line["roofline"]["frac"] <= 1.0
-    return np.load(d / "n1.npz")
+    assert line["steps"] == 2
+    return d
+
+
+@pytest.fixture(scope="module")
+def bench_one_rank(bench_one_rank_dir):
+    return np.load(bench_one_rank_dir / "n1.npz")
+
+
+def test_bench_dump_outputs_are_the_timed_step(bench_one_rank_dir, bench_one_rank):
+    """--dump-outputs DIR: the last timed step's outputs, one float32 .npy each, whole at this size: the arrays --dump holds."""
+    d = bench_one_rank_dir / "outputs"
+    assert sorted(os.listdir(d)) == ["poses_grad.npy", "quats_grad.npy", "rewards.npy", "scalars.npy"]
+    a = bench_one_rank
+    for name, key in (("scalars", "scalars"), ("poses_grad", "pg"), ("quats_grad", "qg"), ("rewards", "rewards")):
+        x = np.load(d / f"{name}.npy")
+        assert x.dtype == np.float32 and np.array_equal(x, a[key]), name
+    assert a["rewards"].shape == (200_000,) and a["pg"].shape == (64, 3) and np.isfinite(a["scalars"]).all()
 
 
 def test_bench_step_two_ranks_equal_one_rank(bench_one_rank, tmp_path):
