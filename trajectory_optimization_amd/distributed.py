@@ -8,8 +8,8 @@ One process per GPU; the cloud is replicated (12 MB at 1 M points), the evaluate
 into contiguous per-rank ranges.  The only data-path collective is ONE all-reduce (sum, f32, N floats) of
 the partial log-odds vector per forward — `torch.distributed` backend "nccl" is RCCL over xGMI on ROCm;
 the per-waypoint min/max normalisation is rank-local by construction.  In the backward every rank
-produces the gradient rows of its own waypoints and a (W,7)-float all-reduce assembles them so that a
-replicated optimiser steps identically everywhere.
+produces the gradient rows of its own waypoints and one all-reduce of 7 floats per evaluated waypoint assembles them so
+that a replicated optimiser steps identically everywhere (ops.WaypointShardStep).
 
 PointShard.  Every rank packs N / R of the points and evaluates ALL waypoints on them.  A point's log-odds sum is then complete
 on its own rank (rewards never travel); what the ranks exchange is per WAYPOINT: after pass 1 the extrema (one element-wise MAX
@@ -40,7 +40,7 @@ class WaypointShard:
         self.group = process_group
         self.world_size = dist.get_world_size(process_group)
         self.rank = dist.get_rank(process_group)
-        self._always = bool(force_collectives)
+        self.collective = self.world_size > 1 or bool(force_collectives)   # does this shard issue its collectives?
         self.compact = bool(compact)
 
     def bounds(self, n_wps, rank=None):
@@ -58,7 +58,7 @@ class WaypointShard:
         return self._allreduce(t, dist.ReduceOp.MAX)
 
     def _allreduce(self, t, op):
-        if self.world_size > 1 or self._always:
+        if self.collective:
             if t.is_cuda and dist.get_backend(self.group) == "gloo":
                 # rehearsal setups (several ranks on one GPU, gloo): stage through the host; RCCL reduces in place
                 h = t.detach().cpu()
@@ -72,7 +72,7 @@ class WaypointShard:
     def allreduce_sum_async(self, t):
         """Starts the in-place sum of `t` and returns a handle whose wait() makes the CURRENT stream wait for it (RCCL
         runs the collective on its own stream): kernels enqueued in between that do not touch `t` overlap with it."""
-        if (self.world_size > 1 or self._always) and not (t.is_cuda and dist.get_backend(self.group) == "gloo"):
+        if self.collective and not (t.is_cuda and dist.get_backend(self.group) == "gloo"):
             return dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
         self.allreduce_sum(t)  # single rank, or the host-staged rehearsal path: nothing left in flight
 
@@ -84,7 +84,7 @@ class WaypointShard:
     def allgather_rows(self, t):
         """Concatenate every rank's (rows, k) block in rank order (equal row counts): the per-waypoint gradient
         rows of a contiguous shard -> the whole trajectory's, on every rank."""
-        if self.world_size == 1 and not self._always:
+        if not self.collective:
             return t
         staged = t.is_cuda and dist.get_backend(self.group) == "gloo"
         src = t.detach().cpu() if staged else t.contiguous()

@@ -182,73 +182,53 @@ class _PoseLoss(torch.autograd.Function):
         return tg, qg, None, None
 
 
-def _local_forward(model, ps, qs, occ):
-    """tohip_traj_forward for this rank's waypoints -> (lo_sum, rewards pre-filled with 0.5, workspace, its generation)."""
-    ws = model._workspace(ps.shape[0])
-    half = torch.empty(model._cloud.n, dtype=torch.float32, device=ps.device)
-    lo_sum, _ = ops.traj_forward(model._cloud, ps, qs, model._cam, ws, model._rig, flags=model._flags, occ=occ, rewards_half=half)
-    return lo_sum, half, ws, ws.generation
-
-
-def _local_backward(model, ctx_ws, ctx_gen, ps, qs, occ, lo_sum, **kw):
-    """tohip_traj_backward reads the state the step's forward left in the workspace.  If another forward has used the
-    workspace since (model() called again before backward()), that state is rebuilt first — same inputs, same bits."""
-    if ctx_ws.generation != ctx_gen:
-        ops.traj_forward(model._cloud, ps, qs, model._cam, ctx_ws, model._rig, flags=model._flags, occ=occ)
-    return ops.traj_backward(model._cloud, ps.shape[0], model._cam, ctx_ws, lo_sum, rig=model._rig, flags=model._flags, occ=occ, **kw)
-
-
 class _TrajRewards(torch.autograd.Function):
-    """rewards(poses, quats) for the evaluated waypoints.  With a process group the waypoints are sharded
-    over the ranks; the only data-path collective is the all-reduce of the log-odds vector."""
+    """rewards(poses, quats) for the evaluated waypoints (ops.WaypointShardStep: with a process group the waypoints are sharded
+    over the ranks; the only data-path collective is the all-reduce of the log-odds vector)."""
 
     @staticmethod
     def forward(ctx, poses, quats, model):
-        p = poses.detach().contiguous()
-        q = quats.detach().contiguous()
-        sh = model._shard
-        lo, hi = sh.bounds(p.shape[0])
-        ps, qs = p[lo:hi].clone(), q[lo:hi].clone()  # own copies: the step's inputs, whatever happens to the Parameters
-        occ = None
-        if hi > lo and model._occlusion is not None:
-            # occlusion masks are piecewise constant in the poses: computed per forward, not differentiated
-            occ = model._occlusion_rows(ps, qs)
-        ws, gen, half = None, 0, None
-        if hi > lo:
-            lo_sum, half, ws, gen = _local_forward(model, ps, qs, occ)
-        else:
-            lo_sum = torch.zeros(model._cloud.npad, device=p.device)
-        lo_sum = ops.allreduce_log_odds(sh, model._cloud, model._workspace(max(hi - lo, 1)), lo_sum, local=hi > lo)
-        rewards, _ = ops.traj_reward(model._cloud, lo_sum, model._cam, model._workspace(max(hi - lo, 1)), rewards=half,
-                                     prefilled=half is not None)
-        ctx.model, ctx.range, ctx.n_wps, ctx.occ, ctx.ws, ctx.gen = model, (lo, hi), p.shape[0], occ, ws, gen
+        p, q = poses.detach().contiguous(), quats.detach().contiguous()
+        st = model._waypoint_step(p.shape[0])
+        ps, qs = p[st.lo:st.hi].clone(), q[st.lo:st.hi].clone()  # own copies: the step's inputs, whatever happens to the Parameters
+        # occlusion masks are piecewise constant in the poses: computed per forward, not differentiated
+        occ = model._occlusion_rows(ps, qs) if st.hi > st.lo and model._occlusion is not None else None
+        lo_sum, rewards, _ = st.forward(ps, qs, occ)
+        ctx.step, ctx.occ, ctx.gen = st, occ, st.ws.generation
         ctx.save_for_backward(ps, qs, lo_sum)
         return rewards
 
     @staticmethod
     def backward(ctx, grad_rewards):
         ps, qs, lo_sum = ctx.saved_tensors
-        m = ctx.model
-        lo, hi = ctx.range
-        # every rank fills the rows of its own waypoints; ONE (W,7) all-reduce assembles positions and quaternions
-        grads = torch.zeros((ctx.n_wps, 7), dtype=torch.float32, device=lo_sum.device)
-        if hi > lo:
-            g = grad_rewards.to(torch.float32).contiguous()
-            pg, qg = _local_backward(m, ctx.ws, ctx.gen, ps, qs, ctx.occ, lo_sum, grad_rewards=g)
-            grads[lo:hi, :3], grads[lo:hi, 3:] = pg, qg
-        grads = m._shard.allreduce_sum(grads)
-        return grads[:, :3].contiguous(), grads[:, 3:].contiguous(), None
+        st = ctx.step
+        upstream = dict(grad_rewards=grad_rewards.to(torch.float32).contiguous()) if st.hi > st.lo else None
+        pg, qg = st.backward(ps, qs, ctx.occ, ctx.gen, lo_sum, upstream)
+        return pg.contiguous(), qg.contiguous(), None
 
 
-def _assemble_grads(model, step_w, W, lo, hi, pg, qg, g_loss, g_terms, reg_sum, reg_terms, dev):
-    """(W,3) / (W,4) gradients from this rank's evaluated rows [lo, hi) (pg, qg: None when the visibility term carries no
-    gradient), all-reduced over the shard, plus the regularisers' share (identical on every rank, so added after the all-reduce).
-    g_terms = (g_l2, g_length, g_smooth): upstream gradients of the single entries of model.loss, or all None."""
-    grads = torch.zeros((W, 7), dtype=torch.float32, device=dev)
-    if pg is not None:
-        rows = slice(lo * step_w, (hi - 1) * step_w + 1, step_w)
-        grads[rows, :3], grads[rows, 3:] = pg, qg
-    grads = model._shard.allreduce_sum(grads)
+def _regularizers(model, p_all, scalars):
+    """criterion()'s terms on the device after the visibility step that left `scalars` -> (terms[8]: vis, l2, length, smooth, total,
+    ...; reg_sum (W,3): the gradient of the regularisers' sum; reg_terms (3,W,3): the gradient of each)."""
+    W, dev = p_all.shape[0], p_all.device
+    terms = torch.empty(8, dtype=torch.float32, device=dev)
+    reg_sum = torch.empty((W, 3), dtype=torch.float32, device=dev)
+    reg_terms = torch.empty((3, W, 3), dtype=torch.float32, device=dev)
+    args = (ptr(p_all), ptr(model.poses0), W, float(model.smoothness_weight), float(model.traj_length_weight), float(model.eps),
+            ptr(scalars), ptr(terms), ptr(reg_sum), 0, None, ptr(reg_terms))
+    with torch.cuda.device(dev):
+        check(_lib.lib().tohip_traj_regularizers(*args, stream_ptr()), "tohip_traj_regularizers")
+    return terms, reg_sum, reg_terms
+
+
+def _assemble_grads(step_w, W, pg_e, qg_e, g_loss, g_terms, reg_sum, reg_terms):
+    """(W,3) / (W,4) gradients: the evaluated rows pg_e, qg_e (every step_w-th waypoint; None when the visibility term carries no
+    gradient) plus the regularisers' share.  g_terms = (g_l2, g_length, g_smooth): upstream gradients of the single entries of
+    model.loss, or all None."""
+    grads = torch.zeros((W, 7), dtype=torch.float32, device=reg_sum.device)
+    if pg_e is not None:
+        rows = slice(0, (pg_e.shape[0] - 1) * step_w + 1, step_w)
+        grads[rows, :3], grads[rows, 3:] = pg_e, qg_e
     pg_all, qg_all = grads[:, :3], grads[:, 3:]
     if all(g is None for g in g_terms):
         if g_loss is not None:
@@ -282,118 +262,64 @@ class _TrajLoss(torch.autograd.Function):
     """ModelTraj.forward in one autograd node: (poses, quats) -> (loss, rewards, vis, l2, length, smooth), for a sharded and / or
     occlusion-aware model (the plain single-GPU model goes through _TrajLossPlan below: one library call per direction).
 
-    Same launches as optimizer.optimize_trajectory's step — visibility forward, [all-reduce], reward, criterion
-    regularisers with their analytic gradients — instead of the ~60 small torch kernels and as many autograd nodes
-    the op-by-op criterion costs.  Every output stays differentiable, as in the reference: `loss.backward()` takes the
-    fused visibility-loss path; a loss built on model.rewards or on single entries of model.loss back-propagates
-    through the general dL/d rewards path and the per-term regulariser gradients."""
+    The model's visibility step, then criterion's regularisers with their analytic gradients — instead of the ~60 small torch
+    kernels and as many autograd nodes the op-by-op criterion costs.  Every output stays differentiable, as in the reference.
+
+    Waypoint placement (ops.WaypointShardStep: visibility forward, [all-reduce], reward): `loss.backward()` takes the fused
+    visibility-loss path; a loss built on model.rewards or on single entries of model.loss back-propagates through the general
+    dL/d rewards path and the per-term regulariser gradients.
+
+    Point placement (ops.PointShardStep: this rank's part of the cloud, every waypoint, two small collectives inside the
+    forward): the forward has the gradient of the visibility loss in hand when it returns (the sums are taken with unit upstream
+    gradient), so the backward issues no kernel and no collective: it scales.  Loss, loss terms and gradients are identical on
+    every rank; `rewards` are this rank's rows.  A loss built on model.rewards would need the other ranks' upstream gradients per
+    point: not supported (raises)."""
 
     @staticmethod
     def forward(ctx, poses, quats, model, step_w):
-        L = _lib.lib()
-        dev = poses.device
-        p_all, q_all = poses.detach().contiguous(), quats.detach().contiguous()
-        W = p_all.shape[0]
-        p_eval = p_all[::step_w].contiguous() if step_w > 1 else p_all
-        q_eval = q_all[::step_w].contiguous() if step_w > 1 else q_all
-        sh = model._shard
-        lo, hi = sh.bounds(p_eval.shape[0])
-        ps, qs = p_eval[lo:hi].clone(), q_eval[lo:hi].clone()  # own copies: the step's inputs, whatever happens to the Parameters
-        occ = None
-        if hi > lo and model._occlusion is not None:
-            occ = model._occlusion_rows(ps, qs)
-        ws, gen, half = None, 0, None
-        if hi > lo:
-            lo_sum, half, ws, gen = _local_forward(model, ps, qs, occ)
+        W = poses.shape[0]
+        n_eval = (W + step_w - 1) // step_w
+        if model._shard.kind == "points":
+            if not (poses.is_contiguous() and quats.is_contiguous() and poses.dtype == torch.float32 and quats.dtype == torch.float32):
+                raise RuntimeError("ModelTraj: poses / quats must be contiguous float32 tensors")
+            p_all = poses.detach()
+            st = model._point_step(n_eval)
+            rewards, scalars, pg_e, qg_e = st.step(p_all, quats.detach(), flags_extra=((step_w - 1) & 0xffff) << 8)   # every step_w-th waypoint, read in place
+            model._mean_reward = scalars[0].clone()   # of ALL points, identical on every rank (model.mean_reward)
+            rewards, saved = rewards.clone(), (pg_e.clone(), qg_e.clone())   # the step's buffers are the next step's
         else:
-            lo_sum = torch.zeros(model._cloud.npad, device=dev)
-        lo_sum = ops.allreduce_log_odds(sh, model._cloud, model._workspace(max(hi - lo, 1)), lo_sum, local=hi > lo)
-        rewards, scalars = ops.traj_reward(model._cloud, lo_sum, model._cam, model._workspace(max(hi - lo, 1)), rewards=half,
-                                           prefilled=half is not None)
-        terms = torch.empty(8, dtype=torch.float32, device=dev)
-        reg_sum = torch.empty((W, 3), dtype=torch.float32, device=dev)
-        reg_terms = torch.empty((3, W, 3), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            check(L.tohip_traj_regularizers(ptr(p_all), ptr(model.poses0), W, float(model.smoothness_weight),
-                                            float(model.traj_length_weight), float(model.eps), ptr(scalars), ptr(terms),
-                                            ptr(reg_sum), 0, None, ptr(reg_terms), stream_ptr()), "tohip_traj_regularizers")
-        ctx.model, ctx.range, ctx.step_w, ctx.W, ctx.occ, ctx.ws, ctx.gen = model, (lo, hi), step_w, W, occ, ws, gen
+            p_all, q_all = poses.detach().contiguous(), quats.detach().contiguous()
+            st = model._waypoint_step(n_eval)
+            p_eval = p_all[::step_w].contiguous() if step_w > 1 else p_all
+            q_eval = q_all[::step_w].contiguous() if step_w > 1 else q_all
+            ps, qs = p_eval[st.lo:st.hi].clone(), q_eval[st.lo:st.hi].clone()  # own copies: the step's inputs, whatever happens to the Parameters
+            occ = model._occlusion_rows(ps, qs) if st.hi > st.lo and model._occlusion is not None else None
+            lo_sum, rewards, scalars = st.forward(ps, qs, occ)
+            ctx.occ, ctx.gen = occ, st.ws.generation
+            saved = (ps, qs, lo_sum, scalars)
+        terms, reg_sum, reg_terms = _regularizers(model, p_all, scalars)
+        ctx.step, ctx.step_w, ctx.W = st, step_w, W
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(ps, qs, lo_sum, scalars, reg_sum, reg_terms)
+        ctx.save_for_backward(reg_sum, reg_terms, *saved)
         vis, l2, length, smooth, total = terms[:5].unbind()
         return total, rewards, vis, l2, length, smooth
 
     @staticmethod
     def backward(ctx, g_loss, g_rewards, g_vis, g_l2, g_length, g_smooth):
-        ps, qs, lo_sum, scalars, reg_sum, reg_terms = ctx.saved_tensors
-        m = ctx.model
-        lo, hi = ctx.range
-        g_loss = _f32(g_loss)
-        pg = qg = None
-        kw = _vis_upstream(g_loss, _f32(g_vis), g_rewards, scalars) if hi > lo else None
-        if kw is not None:
-            pg, qg = _local_backward(m, ctx.ws, ctx.gen, ps, qs, ctx.occ, lo_sum, **kw)
-        pg_all, qg_all = _assemble_grads(m, ctx.step_w, ctx.W, lo, hi, pg, qg, g_loss, (g_l2, g_length, g_smooth), reg_sum, reg_terms,
-                                         lo_sum.device)
-        return pg_all, qg_all, None, None
-
-
-class _TrajLossPoints(torch.autograd.Function):
-    """ModelTraj.forward of a POINT-sharded model (distributed.PointShard): this rank's part of the cloud, every waypoint, two
-    small collectives inside the forward (the waypoints' extrema after pass 1; 40 sums per waypoint and the reward sum after
-    the gradient sums) — ops.PointShardStep.  The forward has the gradient of the visibility loss in hand when it returns (the
-    sums are taken with unit upstream gradient), so the backward issues no kernel and no collective: it scales.  Loss, loss terms
-    and gradients are identical on every rank; `rewards` are this rank's rows.  A loss built on model.rewards would need the
-    other ranks' upstream gradients per point: not supported (raises)."""
-
-    @staticmethod
-    def forward(ctx, poses, quats, model, step_w):
-        L = _lib.lib()
-        dev = poses.device
-        if not (poses.is_contiguous() and quats.is_contiguous() and poses.dtype == torch.float32 and quats.dtype == torch.float32):
-            raise RuntimeError("ModelTraj: poses / quats must be contiguous float32 tensors")
-        p_all, q_all = poses.detach(), quats.detach()
-        W = p_all.shape[0]
-        n_eval = (W + step_w - 1) // step_w
-        st = model._point_step(n_eval)
-        rewards, scalars, pg_e, qg_e = st.step(p_all, q_all, flags_extra=((step_w - 1) & 0xffff) << 8)   # every step_w-th waypoint, read in place
-        model._mean_reward = scalars[0].clone()   # of ALL points, identical on every rank (model.mean_reward)
-        terms = torch.empty(8, dtype=torch.float32, device=dev)
-        reg_sum = torch.empty((W, 3), dtype=torch.float32, device=dev)
-        reg_terms = torch.empty((3, W, 3), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            check(L.tohip_traj_regularizers(ptr(p_all), ptr(model.poses0), W, float(model.smoothness_weight),
-                                            float(model.traj_length_weight), float(model.eps), ptr(scalars), ptr(terms),
-                                            ptr(reg_sum), 0, None, ptr(reg_terms), stream_ptr()), "tohip_traj_regularizers")
-        ctx.step_w, ctx.W, ctx.n_eval = step_w, W, n_eval
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(pg_e.clone(), qg_e.clone(), reg_sum, reg_terms)
-        vis, l2, length, smooth, total = terms[:5].unbind()
-        return total, rewards.clone(), vis, l2, length, smooth
-
-    @staticmethod
-    def backward(ctx, g_loss, g_rewards, g_vis, g_l2, g_length, g_smooth):
-        if g_rewards is not None:
-            raise NotImplementedError("ModelTraj(shard=PointShard()): the rewards are rank-local; a loss built on model.rewards is not "
-                                      "supported with point sharding (use WaypointShard, or model.loss / the returned loss)")
-        pg_e, qg_e, reg_sum, reg_terms = ctx.saved_tensors
+        st = ctx.step
+        reg_sum, reg_terms, *saved = ctx.saved_tensors
         g_loss, g_vis = _f32(g_loss), _f32(g_vis)
-        c_vis = g_vis if g_loss is None else (g_loss if g_vis is None else g_loss + g_vis)
-        dev = pg_e.device
-        pg = torch.zeros((ctx.W, 3), dtype=torch.float32, device=dev)
-        qg = torch.zeros((ctx.W, 4), dtype=torch.float32, device=dev)
-        if c_vis is not None:
-            rows = slice(0, (ctx.n_eval - 1) * ctx.step_w + 1, ctx.step_w)
-            pg[rows], qg[rows] = c_vis * pg_e, c_vis * qg_e
-        g_terms = (g_l2, g_length, g_smooth)
-        if all(g is None for g in g_terms):
-            if g_loss is not None:
-                pg = pg + g_loss * reg_sum
+        if isinstance(st, ops.PointShardStep):
+            if g_rewards is not None:
+                raise NotImplementedError("ModelTraj(shard=PointShard()): the rewards are rank-local; a loss built on model.rewards is not "
+                                          "supported with point sharding (use WaypointShard, or model.loss / the returned loss)")
+            c_vis = g_vis if g_loss is None else (g_loss if g_vis is None else g_loss + g_vis)
+            pg_e, qg_e = (None, None) if c_vis is None else (c_vis * saved[0], c_vis * saved[1])
         else:
-            for k, g in enumerate(g_terms):
-                c = g_loss if g is None else (g.to(torch.float32) if g_loss is None else g_loss + g.to(torch.float32))
-                if c is not None:
-                    pg = pg + c * reg_terms[k]
+            ps, qs, lo_sum, scalars = saved
+            upstream = _vis_upstream(g_loss, g_vis, g_rewards, scalars) if st.hi > st.lo else None
+            pg_e, qg_e = st.backward(ps, qs, ctx.occ, ctx.gen, lo_sum, upstream)
+        pg, qg = _assemble_grads(ctx.step_w, ctx.W, pg_e, qg_e, g_loss, (g_l2, g_length, g_smooth), reg_sum, reg_terms)
         return pg, qg, None, None
 
 
@@ -662,8 +588,7 @@ class _TrajLossPlan(torch.autograd.Function):
         if kw is not None:
             pg, qg = ops.traj_backward(m._cloud, plan.n_eval, m._cam, plan.ws, plan.lo_sum, rig=m._rig, flags=m._flags, **kw)
             plan.sums_stale = True   # the pair sums in the workspace are now scaled by THIS upstream gradient
-        pg_all, qg_all = _assemble_grads(m, plan.step_w, plan.W, 0, plan.n_eval, pg, qg, g_loss, (g_l2, g_length, g_smooth), plan.reg_sum,
-                                         plan.reg_terms, plan.dev)
+        pg_all, qg_all = _assemble_grads(plan.step_w, plan.W, pg, qg, g_loss, (g_l2, g_length, g_smooth), plan.reg_sum, plan.reg_terms)
         return pg_all, qg_all, None
 
 
@@ -749,16 +674,18 @@ class ModelPose(nn.Module):
 
 
 class _NoShard:
-    """Single-process placement: every waypoint is local, no collective."""
-    world_size, rank = 1, 0
+    """Single-process placement: every waypoint is local, no collective (distributed.WaypointShard's surface)."""
+    kind, world_size, rank, collective, compact = "waypoints", 1, 0, False, False
 
     @staticmethod
-    def bounds(n):
+    def bounds(n, rank=None):
         return 0, n
 
     @staticmethod
     def allreduce_sum(t):
         return t
+
+    allreduce_max = allreduce_sum
 
 
 class ModelTraj(nn.Module):
@@ -802,7 +729,7 @@ class ModelTraj(nn.Module):
         if cloud is not None:
             if not isinstance(cloud, ops.PackedCloud) or not cloud.sorted:
                 raise ValueError("cloud= must be an ops.PackedCloud in Morton order (sort=True) or a ModelTraj")
-            if shard is not None and getattr(shard, "kind", "waypoints") == "points":
+            if shard is not None and shard.kind == "points":
                 raise ValueError("a shared packed cloud holds the whole cloud: not available with PointShard")
             if cloud.device != (self.device if self.device.index is not None else torch.device(self.device.type, torch.cuda.current_device())):
                 raise ValueError(f"the packed cloud lives on {cloud.device}, the model on {self.device}")
@@ -814,7 +741,7 @@ class ModelTraj(nn.Module):
                 if tuple(pt.shape) != tuple(cloud.points.shape) or not torch.equal(pt.to(cloud.points.device), cloud.points):
                     raise ValueError("cloud= does not hold these points")
             self.points = cloud.points
-        elif shard is not None and getattr(shard, "kind", "waypoints") == "points":
+        elif shard is not None and shard.kind == "points":
             # point sharding: this rank keeps its own rows of the cloud (the whole cloud is handed in, or — n_points_global — the
             # rows already); model.rewards are those rows' rewards
             pts = torch.as_tensor(points, dtype=torch.float32)
@@ -992,6 +919,15 @@ class ModelTraj(nn.Module):
                                                                          self._shard, rig=self._rig, flags=self._flags)
         return st
 
+    def _waypoint_step(self, n_eval):
+        """The waypoint-placed step (ops.WaypointShardStep) for n_eval evaluated waypoints."""
+        st = self._ws_cache.get(("waypoints", n_eval))
+        if st is None:
+            lo, hi = self._shard.bounds(n_eval)
+            st = self._ws_cache[("waypoints", n_eval)] = ops.WaypointShardStep(self._cloud, n_eval, self._cam, self._workspace(max(hi - lo, 1)),
+                                                                               self._shard, rig=self._rig, flags=self._flags)
+        return st
+
     def _plan(self, step_w):
         """The library-side description of this model for the one-call forward / backward (rebuilt when something it froze
         has changed: the weights of criterion, the mode, the initial trajectory, the number of waypoints)."""
@@ -1019,20 +955,18 @@ class ModelTraj(nn.Module):
         t0 = time()
         N_wps = len(self.poses)
         wps_step = self._wps_step(vis_wps_dist)
-        if self._n_global is not None:
-            if not (N_wps >= 3 and type(self).criterion is ModelTraj.criterion):
-                raise NotImplementedError("ModelTraj(shard=PointShard()) supports the reference's criterion on >= 3 waypoints")
-            loss, self.rewards, vis, l2, length, smooth = _TrajLossPoints.apply(self.poses, self.quats, self, wps_step)
-            self.loss = {'vis': vis, 'length': length, 'l2': l2, 'smooth': smooth}
-            return loss
-        if self.fused_loss and N_wps >= 3 and type(self).criterion is ModelTraj.criterion:
-            if self._occlusion is None and self._shard.world_size == 1 and not getattr(self._shard, "_always", False):
+        points = self._shard.kind == "points"
+        fused = N_wps >= 3 and type(self).criterion is ModelTraj.criterion
+        if points and not fused:
+            raise NotImplementedError("ModelTraj(shard=PointShard()) supports the reference's criterion on >= 3 waypoints")
+        if fused and (self.fused_loss or points):
+            if points or self._shard.collective or self._occlusion is not None:
+                loss, self.rewards, vis, l2, length, smooth = _TrajLoss.apply(self.poses, self.quats, self, wps_step)
+            else:
                 plan = self._plan(wps_step)
                 loss, self.rewards, vis, l2, length, smooth = _TrajLossPlan.apply(self.poses, self.quats, plan)
                 if type(loss) is _Loss and loss.requires_grad:
                     loss.__dict__["_tohip_fast"] = _FastBackward(plan, plan.ws.generation, loss.grad_fn, (self.poses, self.quats))
-            else:
-                loss, self.rewards, vis, l2, length, smooth = _TrajLoss.apply(self.poses, self.quats, self, wps_step)
             self.loss = {'vis': vis, 'length': length, 'l2': l2, 'smooth': smooth}
             if debug:
                 torch.cuda.synchronize(self.device)

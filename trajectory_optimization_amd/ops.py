@@ -312,12 +312,93 @@ class PointShardStep:
         return self.rewards, self.scalars, self.pg, self.qg
 
 
+class WaypointShardStep:
+    """One waypoint-sharded visibility step (distributed.WaypointShard, or one process with every waypoint): this rank's range
+    [lo, hi) = shard.bounds(n_wps) of the evaluated waypoints over the whole cloud, ONE all-reduce of the log-odds vector between
+    forward and reward, ONE (n_wps, 7) all-reduce of the gradient rows.  Every rank issues both in that order, a rank that owns no
+    waypoint included.  `ws` serves max(hi - lo, 1) waypoints.
+
+    step() is the launch-only loop's step over buffers allocated once (as PointShardStep.step: gradients for dL/d loss_vis = 1);
+    forward() / backward() are an autograd node's two halves, with fresh outputs per call."""
+
+    def __init__(self, cloud, n_wps, cam, ws, shard, rig=None, flags=0):
+        self.cloud, self.n_wps, self.cam, self.ws, self.shard, self.rig, self.flags = cloud, int(n_wps), cam, ws, shard, rig, int(flags)
+        self.lo, self.hi = shard.bounds(self.n_wps)
+        n_loc = max(self.hi - self.lo, 1)
+        f32 = dict(dtype=torch.float32, device=cloud.device)
+        self.lo_sum, self.minmax = torch.empty(cloud.npad, **f32), torch.empty((n_loc * (rig.n_cams if rig is not None else 1), 2), **f32)
+        self.rewards, self.scalars = torch.empty(cloud.n, **f32), torch.zeros(4, **f32)
+        self.pg_loc, self.qg_loc = torch.empty((n_loc, 3), **f32), torch.empty((n_loc, 4), **f32)
+        self.g = torch.zeros((self.n_wps, 7), **f32)   # rows outside this rank's range stay zero
+        self.pg, self.qg = torch.empty((self.n_wps, 3), **f32), torch.empty((self.n_wps, 4), **f32)
+        self.gout = torch.ones(1, **f32)
+        self.rig_ref = rig.ref() if rig is not None else _NULL_RIG
+
+    def step(self, poses, quats, flags_extra=0, occ=None):
+        """poses / quats: the whole trajectory, read in place; flags_extra: TOHIP_TRAJ_STRIDE bits (the evaluated waypoints are every
+        s-th row, this rank's first at row lo * s).  occ: the occlusion rows of this rank's waypoints.  -> (rewards, scalars,
+        poses_grad (n_wps,3), quats_grad (n_wps,4)), the same on every rank."""
+        L, c, ws, local = _lib.lib(), self.cloud, self.ws, self.hi > self.lo
+        at = self.lo * (((int(flags_extra) >> 8) & 0xffff) + 1)
+        with torch.cuda.device(c.device):
+            s = stream_ptr()
+            if local:
+                check(L.tohip_traj_forward(ptr(c.blob), c.n, ptr(poses[at:]), ptr(quats[at:]), self.hi - self.lo, self.cam.ref(), self.rig_ref,
+                                           self.flags | int(flags_extra), ptr(occ), ptr(self.lo_sum), ptr(self.minmax), ptr(self.rewards),
+                                           ptr(ws.buf), ws.bytes, s), "forward")
+                ws.generation += 1
+            else:
+                self.lo_sum.zero_()
+            allreduce_log_odds(self.shard, c, ws, self.lo_sum, local=local)
+            if local:
+                # rewards, their mean and the loss scalars share the backward's first launch
+                check(L.tohip_traj_reward_backward(ptr(c.blob), c.n, self.hi - self.lo, self.cam.ref(), self.rig_ref, self.flags, ptr(occ),
+                                                   ptr(self.lo_sum), self.cam.eps, 1, ptr(self.rewards), ptr(self.scalars), ptr(self.gout),
+                                                   ptr(self.pg_loc), ptr(self.qg_loc), ptr(ws.buf), ws.bytes, s), "reward + backward")
+                self.g[self.lo:self.hi, :3], self.g[self.lo:self.hi, 3:] = self.pg_loc, self.qg_loc
+            else:
+                check(L.tohip_traj_reward(ptr(c.blob), ptr(self.lo_sum), c.n, self.cam.eps, 0, ptr(self.rewards), ptr(self.scalars),
+                                          ptr(ws.buf), ws.bytes, s), "reward")
+            self.shard.allreduce_sum(self.g)
+            self.pg.copy_(self.g[:, :3])
+            self.qg.copy_(self.g[:, 3:])
+            self.g.zero_()   # the other ranks' rows must be zero again before the next sum
+        return self.rewards, self.scalars, self.pg, self.qg
+
+    def forward(self, ps, qs, occ=None):
+        """ps / qs: this rank's evaluated waypoints (rows lo:hi, contiguous).  -> (lo_sum, rewards, scalars); the step's state stays
+        in the workspace for backward(), which needs ws.generation as it is now."""
+        c = self.cloud
+        if self.hi > self.lo:
+            half = torch.empty(c.n, dtype=torch.float32, device=c.device)
+            lo_sum, _ = traj_forward(c, ps, qs, self.cam, self.ws, self.rig, flags=self.flags, occ=occ, rewards_half=half)
+        else:
+            half, lo_sum = None, torch.zeros(c.npad, dtype=torch.float32, device=c.device)
+        allreduce_log_odds(self.shard, c, self.ws, lo_sum, local=half is not None)
+        rewards, scalars = traj_reward(c, lo_sum, self.cam, self.ws, rewards=half, prefilled=half is not None)
+        return lo_sum, rewards, scalars
+
+    def backward(self, ps, qs, occ, gen, lo_sum, upstream):
+        """-> the all-reduced gradient rows (n_wps,3), (n_wps,4) of the forward that left the workspace at generation `gen`.
+        upstream: traj_backward's upstream keyword arguments, or None when no gradient reaches this rank's visibility term (the
+        all-reduce is joined all the same).  If another forward has used the workspace since, that state is rebuilt first — same
+        inputs, same bits."""
+        g = torch.zeros((self.n_wps, 7), dtype=torch.float32, device=lo_sum.device)
+        if upstream is not None and self.hi > self.lo:
+            if self.ws.generation != gen:
+                traj_forward(self.cloud, ps, qs, self.cam, self.ws, self.rig, flags=self.flags, occ=occ)
+            g[self.lo:self.hi, :3], g[self.lo:self.hi, 3:] = traj_backward(self.cloud, ps.shape[0], self.cam, self.ws, lo_sum, rig=self.rig,
+                                                                         flags=self.flags, occ=occ, **upstream)
+        g = self.shard.allreduce_sum(g)
+        return g[:, :3], g[:, 3:]
+
+
 def allreduce_log_odds(shard, cloud, ws, lo_sum, local=True):
     """The one data-path collective of a waypoint-sharded step: the sum of the ranks' partial log-odds vectors, in
     place.  With shard.compact only the slots some rank's forward listed as candidates travel (tohip_traj_candidate_flags ...
     tohip_slots_pack): the vector is exactly zero elsewhere on every rank.  local=False: this rank ran no forward over `ws` (it
     holds no waypoint): its vector is zero and it lists nothing."""
-    if not getattr(shard, "compact", False) or shard.world_size == 1 and not shard._always:
+    if not (shard.compact and shard.collective):
         return shard.allreduce_sum(lo_sum)
     L = _lib.lib()
     dev = cloud.device

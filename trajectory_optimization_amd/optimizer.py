@@ -122,14 +122,12 @@ def optimize_trajectory(model, n_opt_steps=10, lr_pose=0.1, lr_quat=0.0, rewards
     A step is ONE library call and FIVE launches (tohip_traj_opt_step): the waypoint selection is a stride of the first launch's
     reads, the regularisers and Adam's constants are one block more of the THIRD launch (the sparse kernel's: nothing launched
     before it may read them), the parameter update and the early-stop bookkeeping are the tail of the last launch's blocks.  A waypoint-sharded or occlusion-aware model has a collective or a hull
-    pass inside the step and goes through the separate calls (forward | all-reduce | reward + backward | tohip_traj_step_tail).
+    pass inside the step and goes through the separate calls (forward | all-reduce | reward + backward | step tail).
     (A HIP-graph replay of the step was measured slower than issuing its launches — a replay costs 10-16 us of host time by
     itself, five launches 17 us, and the GPU side is the same — so there is no graph variant.)"""
     if n_opt_steps <= 0:   # nothing to run: the model keeps its rewards and loss terms
         return TrajOptResult(0, False, [], 0.0, 0.0)
-    if getattr(model, "_n_global", None) is not None:
-        return _optimize_trajectory_points(model, n_opt_steps, lr_pose, lr_quat, rewards_th, smoothness_th, vis_wps_dist, betas, adam_eps)
-    if model._shard.world_size > 1 or getattr(model._shard, "_always", False) or model._occlusion is not None:
+    if model._shard.kind == "points" or model._shard.collective or model._occlusion is not None:
         return _optimize_trajectory_split(model, n_opt_steps, lr_pose, lr_quat, rewards_th, smoothness_th, vis_wps_dist, betas, adam_eps)
     run = _OptRun([model], n_opt_steps, lr_pose, lr_quat, rewards_th, smoothness_th, vis_wps_dist, betas, adam_eps)
     run.run(n_opt_steps)
@@ -137,16 +135,17 @@ def optimize_trajectory(model, n_opt_steps=10, lr_pose=0.1, lr_quat=0.0, rewards
 
 
 @torch.no_grad()
-def _optimize_trajectory_points(model, n_opt_steps, lr_pose, lr_quat, rewards_th, smoothness_th, vis_wps_dist, betas, adam_eps):
-    """optimize_trajectory of a POINT-sharded model (distributed.PointShard): per step the point-sharded visibility step
-    (ops.PointShardStep: this rank's points, every waypoint, two small collectives) and the replicated O(W) remainder
-    (tohip_traj_step_tail) — every rank holds the same gradients, so every rank takes the same step."""
+def _optimize_trajectory_split(model, n_opt_steps, lr_pose, lr_quat, rewards_th, smoothness_th, vis_wps_dist, betas, adam_eps):
+    """optimize_trajectory with a collective (a sharded model) or a hull pass (occlusion rows) inside the step: per step the model's
+    visibility step (ops.WaypointShardStep or ops.PointShardStep: gradients identical on every rank) and the replicated O(W)
+    remainder in one launch — scatter, regularisers, both Adam updates, early stop — so every rank takes the same step."""
     L = _lib.lib()
     dev = model.device
     W = model.poses.shape[0]
     step_w = model._wps_step(vis_wps_dist)
     n_eval = (W + step_w - 1) // step_w
-    st = model._point_step(n_eval)
+    points = model._shard.kind == "points"
+    st = model._point_step(n_eval) if points else model._waypoint_step(n_eval)
     f32 = dict(dtype=torch.float32, device=dev)
     pg, qg = torch.zeros((W, 3), **f32), torch.zeros((W, 4), **f32)
     loss_terms = torch.zeros((n_opt_steps + 1, 8), **f32)
@@ -154,10 +153,15 @@ def _optimize_trajectory_points(model, n_opt_steps, lr_pose, lr_quat, rewards_th
     mp, vp = torch.zeros((W, 3), **f32), torch.zeros((W, 3), **f32)
     mq, vq = torch.zeros((W, 4), **f32), torch.zeros((W, 4), **f32)
     poses, quats = model.poses.data, model.quats.data
+    # the evaluated waypoints are every step_w-th row of the Parameters, read in place (TOHIP_TRAJ_STRIDE in the flags: no gather)
     stride = ((step_w - 1) & 0xffff) << 8
     with torch.cuda.device(dev):
         for _ in range(n_opt_steps):
-            rewards, scalars, pg_e, qg_e = st.step(poses, quats, flags_extra=stride)
+            kw = {}
+            if model._occlusion is not None and st.hi > st.lo:   # (waypoint placement: PointShard refuses occlusion)
+                own = slice(st.lo * step_w, (st.hi - 1) * step_w + 1, step_w)
+                kw["occ"] = model._occlusion_rows(poses[own].contiguous(), quats[own].contiguous())
+            _, scalars, pg_e, qg_e = st.step(poses, quats, flags_extra=stride, **kw)
             check(L.tohip_traj_step_tail(ptr(poses), ptr(quats), ptr(model.poses0), W, ptr(pg_e), ptr(qg_e), n_eval, step_w,
                                          ptr(pg), ptr(qg), ptr(mp), ptr(vp), ptr(mq), ptr(vq), float(model.smoothness_weight),
                                          float(model.traj_length_weight), float(model.eps), float(lr_pose), float(lr_quat),
@@ -168,92 +172,11 @@ def _optimize_trajectory_points(model, n_opt_steps, lr_pose, lr_quat, rewards_th
     stt = state.cpu()  # the run's only host synchronisation
     steps = int(stt[3].item())
     lt_host = loss_terms[:max(steps, 1)].cpu()
-    model.rewards = st.rewards
-    model._mean_reward = st.scalars[0].clone()
+    model.rewards = st.rewards.clone()   # (the step's buffer is the next run's)
+    if points:
+        model._mean_reward = st.scalars[0].clone()
     model.loss = {"vis": lt_host[-1, 0], "l2": lt_host[-1, 1], "length": lt_host[-1, 2], "smooth": lt_host[-1, 3]}
     return TrajOptResult(steps, bool(stt[2].item() != 0), lt_host[:, 4].tolist(), float(stt[4]), float(stt[5]))
-
-
-@torch.no_grad()
-def _optimize_trajectory_split(model, n_opt_steps, lr_pose, lr_quat, rewards_th, smoothness_th, vis_wps_dist, betas, adam_eps):
-    """optimize_trajectory with a collective (waypoint sharding) or a hull pass (occlusion rows) inside the step."""
-    L = _lib.lib()
-    dev = model.device
-    cloud, cam, rig = model._cloud, model._cam, model._rig
-    W = model.poses.shape[0]
-    step_w = model._wps_step(vis_wps_dist)
-    n_eval = (W + step_w - 1) // step_w
-    # waypoint sharding (one process per GPU): this rank evaluates rows [lo_e, hi_e) of the evaluated waypoints; the
-    # log-odds vector and the (n_eval, 7) gradient rows are all-reduced, everything else is replicated
-    lo_e, hi_e = model._shard.bounds(n_eval)
-    n_loc = hi_e - lo_e
-    ws = model._workspace(max(n_loc, 1))
-    f32 = dict(dtype=torch.float32, device=dev)
-    g_e = torch.zeros((n_eval, 7), **f32)  # rows outside this rank's range stay zero
-    pg_e, qg_e = torch.empty((n_eval, 3), **f32), torch.empty((n_eval, 4), **f32)
-    pg_loc, qg_loc = torch.empty((max(n_loc, 1), 3), **f32), torch.empty((max(n_loc, 1), 4), **f32)
-    pg, qg = torch.zeros((W, 3), **f32), torch.zeros((W, 4), **f32)
-    lo_sum = torch.empty(cloud.npad, **f32)
-    minmax = torch.empty((max(n_loc, 1) * (rig.n_cams if rig else 1), 2), **f32)
-    rewards, scalars = torch.empty(cloud.n, **f32), torch.zeros(4, **f32)
-    loss_terms = torch.zeros((n_opt_steps + 1, 8), **f32)
-    state = torch.zeros(8, **f32)
-    gout = torch.ones(1, **f32)
-    mp, vp = torch.zeros((W, 3), **f32), torch.zeros((W, 3), **f32)
-    mq, vq = torch.zeros((W, 4), **f32), torch.zeros((W, 4), **f32)
-    poses, quats = model.poses.data, model.quats.data
-    rig_ref = rig.ref() if rig is not None else ops._NULL_RIG
-    occluded = model._occlusion is not None
-    # this rank's evaluated waypoints are rows lo_e * step_w, (lo_e + 1) * step_w, ... of the Parameters: read in place
-    # (TOHIP_TRAJ_STRIDE in the flags: no gather launch)
-    flags_fwd = int(model._flags) | (((step_w - 1) & 0xffff) << 8)
-    p_at, q_at = poses[lo_e * step_w:], quats[lo_e * step_w:]
-
-    def iteration():
-        s = stream_ptr()
-        occ = None
-        if occluded and n_loc > 0:
-            occ = model._occlusion_rows(poses[lo_e * step_w:(hi_e - 1) * step_w + 1:step_w].contiguous(),
-                                        quats[lo_e * step_w:(hi_e - 1) * step_w + 1:step_w].contiguous())
-        if n_loc > 0:
-            check(L.tohip_traj_forward(ptr(cloud.blob), cloud.n, ptr(p_at), ptr(q_at), n_loc, cam.ref(), rig_ref,
-                                       flags_fwd, ptr(occ), ptr(lo_sum), ptr(minmax), ptr(rewards), ptr(ws.buf), ws.bytes, s),
-                  "forward")
-            ws.generation += 1
-        else:
-            lo_sum.zero_()
-        ops.allreduce_log_odds(model._shard, cloud, ws, lo_sum, local=n_loc > 0)
-        if n_loc > 0:
-            # rewards, their mean and the loss scalars share the backward's first launch
-            check(L.tohip_traj_reward_backward(ptr(cloud.blob), cloud.n, n_loc, cam.ref(), rig_ref, model._flags, ptr(occ), ptr(lo_sum),
-                                               cam.eps, 1, ptr(rewards), ptr(scalars), ptr(gout), ptr(pg_loc), ptr(qg_loc), ptr(ws.buf),
-                                               ws.bytes, s), "reward + backward")
-        else:
-            check(L.tohip_traj_reward(ptr(cloud.blob), ptr(lo_sum), cloud.n, cam.eps, 0, ptr(rewards), ptr(scalars), ptr(ws.buf), ws.bytes, s),
-                  "reward")
-        # assemble every rank's gradient rows: ONE (n_eval, 7) all-reduce, then the replicated remainder of the step
-        if n_loc > 0:
-            g_e[lo_e:hi_e, :3], g_e[lo_e:hi_e, 3:] = pg_loc, qg_loc
-        model._shard.allreduce_sum(g_e)
-        pg_e.copy_(g_e[:, :3])
-        qg_e.copy_(g_e[:, 3:])
-        g_e.zero_()  # the other ranks' rows must be zero again before the next sum
-        # the O(W) remainder of the step in one launch: scatter, regularisers, both Adam updates, early stop
-        check(L.tohip_traj_step_tail(ptr(poses), ptr(quats), ptr(model.poses0), W, ptr(pg_e), ptr(qg_e), n_eval, step_w,
-                                     ptr(pg), ptr(qg), ptr(mp), ptr(vp), ptr(mq), ptr(vq), float(model.smoothness_weight),
-                                     float(model.traj_length_weight), float(model.eps), float(lr_pose), float(lr_quat),
-                                     betas[0], betas[1], adam_eps, float(rewards_th), float(smoothness_th), ptr(scalars),
-                                     ptr(loss_terms), ptr(state), s), "step tail")
-
-    with torch.cuda.device(dev):
-        for _ in range(n_opt_steps):
-            iteration()
-    st = state.cpu()  # the run's only host synchronisation
-    steps = int(st[3].item())
-    lt_host = loss_terms[:max(steps, 1)].cpu()
-    model.rewards = rewards
-    model.loss = {"vis": lt_host[-1, 0], "l2": lt_host[-1, 1], "length": lt_host[-1, 2], "smooth": lt_host[-1, 3]}
-    return TrajOptResult(steps, bool(st[2].item() != 0), lt_host[:, 4].tolist(), float(st[4]), float(st[5]))
 
 
 @torch.no_grad()
