@@ -267,7 +267,7 @@ def test_sample_hull_by_sequential_insertion_on_many_shapes(dev, kind):
 def test_a_build_that_runs_out_of_faces_is_retried_cleanly(dev):
     """A cloud most of whose points are visible needs more faces than the recommended workspace holds: the build returns TOHIP_ENOSPC
     and ops retries with 4x the bytes.  The host only learns of the overflow from its next readback — up to two batches of rounds are
-    enqueued behind the failing one; they must not walk the half-built round (r06: a memory fault found by tools/stress_hpr_repeat.py,
+    enqueued behind the failing one; they must not walk the half-built round (r06: a memory fault found by repeated builds,
     on exactly this path, when the workspace held another build's bytes).  Three builds into poisoned memory: no fault, Qhull's set."""
     from oracle import oracle
     from trajectory_optimization_amd import _lib, ops

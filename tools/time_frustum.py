@@ -1,4 +1,4 @@
-"""tohip_frustum_cull at 1 M and 2 M points: microseconds per call (HIP events around back-to-back calls).  TOHIP_FRUSTUM_OWN_PREFIX=0: with the scan launch."""
+"""tohip_frustum_cull at 1 M and 2 M points: microseconds per call (HIP events around back-to-back calls)."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,7 +1,7 @@
 """PointCloud2 -> xyz at 1 M and 16 M points (16-byte xyz + intensity points), without and with 1 % NaN rows, ONE workspace per size carried
 through the sequence dense, NaN, dense (the adaptive mode's hint flips twice; the first call after a flip runs in the "wrong" mode and must be
 exact all the same): microseconds per call (HIP events around back-to-back calls through the C ABI) and GB/s on the algorithmic bytes (16 B read +
-12 B written per finite point).  TOHIP_PC2_ADAPTIVE=0: always count | scan | write."""
+12 B written per finite point)."""
 import os, sys
 import numpy as np
 import torch

@@ -209,8 +209,7 @@ extern "C" int tohip_pack_cloud(const float* xyz, int64_t n, int sort, void* pac
         size_t tmp = pl.tmp_bytes;
         // by the 21 most significant bits (7 per axis: cells of 1/128 of the box's longest side; the stable sort keeps the caller's
         // order inside a cell): a radix pass less than all 30 bits, and a 256-point tile spans several cells either way
-        // (TOHIP_PACK_SORT_LOW_BIT: an experiment knob, clamped to the bits the sort's plan was sized for — begin_bit < end_bit = 30)
-        static const int low_bit = [] { const char* ev = getenv("TOHIP_PACK_SORT_LOW_BIT"); const int v = ev ? atoi(ev) : 9; return v < 0 ? 0 : (v > 29 ? 29 : v); }();
+        constexpr int low_bit = 9;
         e = sort_pairs(ws + pl.off_tmp, tmp, keys, keys2, vals, vals2, (int)n, low_bit, 30, st);
         if (e != hipSuccess) return (int)e;
         order = vals2;  // radix sort is stable: equal cells keep the caller's order (deterministic)
@@ -386,8 +385,7 @@ extern "C" int tohip_frustum_cull(const float* cam_3xN, int64_t n, const tohip_c
     k_frustum_count<<<ntiles, TO_BLOCK, 0, st>>>(cam_3xN, n, f, dist_mask, fov_mask, tile_count, keep);
     TO_HIP_CHECK_LAUNCH();
     const int wblocks = (ntiles + TO_WAVES_PER_BLOCK - 1) / TO_WAVES_PER_BLOCK;
-    static const int own_prefix = getenv("TOHIP_FRUSTUM_OWN_PREFIX") ? atoi(getenv("TOHIP_FRUSTUM_OWN_PREFIX")) : 1;   // experiments: 0 = always scan
-    if (own_prefix && ntiles <= 2048 && (kept_idx || kept_count)) {   // two launches: every wave of the write pass finds its own offset
+    if (ntiles <= 2048 && (kept_idx || kept_count)) {   // two launches: every wave of the write pass finds its own offset
         k_frustum_write<<<wblocks, TO_BLOCK, 0, st>>>(n, keep, nullptr, tile_count, kept_count, kept_idx);
         TO_HIP_CHECK_LAUNCH();
         return TOHIP_OK;

@@ -14,8 +14,8 @@
 //                faces its apex sees; a hashed total order breaks overlaps
 //            (3) a candidate is accepted iff it owns every face its apex sees and no better candidate
 //                owns a face across its horizon -> accepted regions are pairwise non-adjacent, so the
-//                insertions commute and equal the sequential result (r06: decided inside step (2)'s walk —
-//                k_owner_claim's `verdict` — the k_accept launch is the careful path's)
+//                insertions commute and equal the sequential result (r06: decided inside step (2)'s walk,
+//                k_owner_claim — the k_accept launch is the careful path's)
 //            (4) one new triangle per horizon edge, linked to its two siblings by rotating around the
 //                shared horizon vertex; (5) points of deleted faces move to a new face or retire
 //   end      no point is outside any face; hull vertices = vertices of the live faces
@@ -23,7 +23,6 @@
 // Predicates are plain f64 (coordinate differences of f32 inputs are exact; products are rounded):
 // like Qhull's own, they are not exact on nearly coplanar quadruples — DESIGN.md §6.
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -103,8 +102,6 @@ struct Bufs {
     int m1;
     int fcap;
     int nseg;
-    int hbits;             // bits of the apex height in a candidate's rank (make_prio)
-    int early_out;         // k_owner_claim: candidates beaten by a neighbouring candidate do not walk
     int share_edges;       // k_owner_claim: regions that share a horizon edge convexly are accepted together (convex_across)
     int origin;            // 1: the last slot of a segment is the appended origin; 0: it repeats the segment's first point and never takes part
     int sub;               // > 1 while only every sub-th point (in Morton order) takes part: the first rounds of a large build
@@ -189,7 +186,7 @@ __host__ inline size_t carve(Bufs* b, char* base, int64_t n_points, int64_t nseg
         if (tmp32 > tmp) tmp = tmp32;
     }
     p = take(tmp); if (b) { b->sort_tmp = p; b->sort_tmp_bytes = tmp; }
-    if (b) { b->m1 = (int)m1; b->fcap = fcap; b->nseg = (int)nseg; b->sub = 1; b->origin = 1; b->hbits = 0; b->early_out = 0; b->share_edges = 0; b->serial = 0; b->key32 = 1; }
+    if (b) { b->m1 = (int)m1; b->fcap = fcap; b->nseg = (int)nseg; b->sub = 1; b->origin = 1; b->share_edges = 0; b->serial = 0; b->key32 = 1; }
     return o;
 }
 
@@ -211,14 +208,15 @@ __device__ __forceinline__ unsigned hash32(unsigned x) {
     x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
     return x;
 }
-// Rank of candidate face f in round `round` (smaller = better): the top `hbits` bits of its apex's HEIGHT above the face
+// Rank of candidate face f in round `round` (smaller = better): the top kHBits bits of its apex's HEIGHT above the face
 // (float: exponent first — higher apexes first, they bury more of the others), then a hash salted per round, then the id.
-// hbits = 0: the hashed total order alone.
-__device__ __forceinline__ unsigned long long make_prio(int f, int round, float height, int hbits) {
+// 9 = exponent + one mantissa bit: apexes more than ~1.4x higher go first, the hash decides among the rest.  Measured at
+// 1 M points: 0 bits (hash only) 177 rounds / 10.7 ms, 6: 116 / 7.0, 9: 106 / 6.2, 12: 120 / 6.7, 16: 129 / 7.2
+constexpr int kHBits = 9;
+__device__ __forceinline__ unsigned long long make_prio(int f, int round, float height) {
     const unsigned h = hash32((unsigned)f * 0x9E3779B9u + (unsigned)round);
-    if (hbits <= 0) return ((unsigned long long)h << 32) | (unsigned)f;
-    const unsigned hb = (__float_as_uint(height) & 0x7fffffffu) >> (31 - hbits);
-    const unsigned inv = ((1u << hbits) - 1u) - hb;
+    const unsigned hb = (__float_as_uint(height) & 0x7fffffffu) >> (31 - kHBits);
+    const unsigned inv = ((1u << kHBits) - 1u) - hb;
     return ((unsigned long long)inv << 48) | ((unsigned long long)(h & 0xffffu) << 32) | (unsigned)f;
 }
 
@@ -845,7 +843,7 @@ __device__ __forceinline__ bool convex_across(const Bufs& b, int cg, int k, doub
     const double d = nx * tx + ny * ty + nz * tz;
     return d < 0.0 && d * d > (kConvexTol * kConvexTol) * (nx * nx + ny * ny + nz * nz) * (tx * tx + ty * ty + tz * tz);
 }
-// verdict != 0 (r06, the fast path): the walk also DECIDES who is accepted, so the round needs no k_accept launch.  k_accept's rule —
+// The fast path's walk (r06) also DECIDES who is accepted, so the round needs no k_accept launch.  k_accept's rule —
 // a candidate stays accepted iff it owns every face its apex sees and no better candidate owns a face across its horizon — is
 // settled where ownership changes hands: a walk that meets a face it sees in better hands, or a better owner across its horizon,
 // fails itself; a walk that robs a face, or finds a worse owner across its horizon, fails that one; an incomplete walk fails itself.
@@ -853,10 +851,10 @@ __device__ __forceinline__ bool convex_across(const Bufs& b, int cg, int k, doub
 // and looks are atomics at the memory side: of two candidates that take adjacent faces at the same time at least one sees the
 // other, whichever order the CASes land in.  The verdict is what k_accept computed from the final ownership: the accepted bit
 // (fflags bit 1) of the candidates nobody failed.  Block 0 does k_accept's housekeeping.
-__global__ void __launch_bounds__(TO_BLOCK) k_owner_claim(Bufs b, int round, int par, int verdict) {
+__global__ void __launch_bounds__(TO_BLOCK) k_owner_claim(Bufs b, int round, int par) {
     __shared__ int fr[TO_WAVES_PER_BLOCK][2][kClaimFront];
     if (b.ctrl[kCtrlError] != 0) return;   // (see round_dead)
-    if (verdict && blockIdx.x == 0) {
+    if (blockIdx.x == 0) {
         // nothing has been inserted yet this round: the staged count is the face count; it is published here for the
         // kernels that run while k_new_faces raises the staged one.  The next round's lists start empty.
         if (threadIdx.x == 0) { b.ctrl[kCtrlNFaces] = min(b.ctrl[kCtrlNFaces + 8], b.fcap); b.ctrl[kCtrlAccepted] = 0; }
@@ -887,7 +885,7 @@ __global__ void __launch_bounds__(TO_BLOCK) k_owner_claim(Bufs b, int round, int
     for (int c = (blockIdx.x / kSubLists) * TO_WAVES_PER_BLOCK + wid; c < ncand; c += wstep) {
         const int o = cand[c];
         const unsigned long long ax = b.fmax[o];
-        const int n0 = (b.early_out && lane < 3) ? b.fn[3 * o + lane] : kNone;   // for the look at the neighbours below: requested with the apex
+        const int n0 = lane < 3 ? b.fn[3 * o + lane] : kNone;   // for the look at the neighbours below: requested with the apex
         if (ax == 0ull) {  // a candidate without a point outside its face (never seen): not a candidate
             if (lane == 0) { b.fowner[o] = kNone; atomicAnd(&b.fflags[o], ~2); }
             continue;
@@ -901,7 +899,7 @@ __global__ void __launch_bounds__(TO_BLOCK) k_owner_claim(Bufs b, int round, int
         {
             // A candidate whose own face is seen by the apex of a BETTER candidate next door has lost before it starts: that
             // neighbour's walk takes this face at its first level.  Not walking keeps its claims off the faces that worse
-            // candidates need (experiments: TOHIP_HULL_EARLY_OUT=0 switches it off)
+            // candidates need
             bool doomed = false;
             if (n0 >= 0) {
                 const int n = n0;
@@ -914,7 +912,7 @@ __global__ void __launch_bounds__(TO_BLOCK) k_owner_claim(Bufs b, int round, int
                 }
             }
             if (__any(doomed)) {
-                if (verdict && lane == 0) atomicAnd(&b.fflags[o], ~2);
+                if (lane == 0) atomicAnd(&b.fflags[o], ~2);
                 continue;
             }
         }
@@ -945,16 +943,14 @@ __global__ void __launch_bounds__(TO_BLOCK) k_owner_claim(Bufs b, int round, int
                         }
                     } else if (sees) {
                         fail_me = co != o;                     // a face my apex sees, in better hands
-                    } else if (co >= 0 && co != o && verdict) { // across my horizon, in other hands: unless the two fit, the worse one loses
+                    } else if (co >= 0 && co != o) {   // across my horizon, in other hands: unless the two fit, the worse one loses
                         if (!b.share_edges || !convex_across(b, cg, t % 3, px, py, pz, co)) {
                             if (b.fprio[co] < po) fail_me = true; else fail_other = co;
                         }
                     }
                 }
-                if (verdict) {
-                    if (fail_other >= 0) atomicAnd(&b.fflags[fail_other], ~2);
-                    failed = failed || __any(fail_me);
-                }
+                if (fail_other >= 0) atomicAnd(&b.fflags[fail_other], ~2);
+                failed = failed || __any(fail_me);
                 const unsigned long long bal = __ballot(mine);
                 const int cnt = __popcll(bal), rank = __popcll(bal & ((1ull << lane) - 1ull));
                 if (logn + cnt > kClaimLog) flush();
@@ -969,23 +965,23 @@ __global__ void __launch_bounds__(TO_BLOCK) k_owner_claim(Bufs b, int round, int
             cur ^= 1;
         }
         if (ncur > 0) failed = true;                  // the claim budget ran out with a frontier left
-        if (verdict && failed && lane == 0) atomicAnd(&b.fflags[o], ~2);
+        if (failed && lane == 0) atomicAnd(&b.fflags[o], ~2);
     }
     flush();
 }
 
-// The same walk for rounds with TENS OF THOUSANDS of candidates (a batch of views: up to 150 k per round), four or eight candidates
-// to a wave (r06; eight is the default).  There a wave's walk is a chain of dependent accesses (neighbour -> owner and plane -> CAS, ~4.5 us per candidate) on
+// The same walk for rounds with TENS OF THOUSANDS of candidates (a batch of views: up to 150 k per round), eight candidates to a
+// wave (r06).  There a wave's walk is a chain of dependent accesses (neighbour -> owner and plane -> CAS, ~4.5 us per candidate) on
 // the 10-20 lanes its region's edges fill, every wave of the chip holds one, and the launch is as long as the 18 candidates a wave
-// walks one after the other (80 us per round for 128 views).  Regions are small in such rounds, so each QUARTER (or eighth) of a wave
-// takes a candidate of its own: sixteen (eight) (face, edge) pairs per step, a frontier of at most 32 faces per level — a walk that outgrows it is
-// incomplete: the candidate fails itself and comes back in a later round — four chains in flight per wave.  The four walks are
-// independent but move in lock-step through one instruction stream: every ballot is the whole wave's, a quarter reads its bits of
-// it.  Same claims, same log, same verdict rule as k_owner_claim (verdict = 1 always: this kernel is the fast path's).
+// walks one after the other (80 us per round for 128 views).  Regions are small in such rounds, so each EIGHTH of a wave takes a
+// candidate of its own: eight (face, edge) pairs per step, a frontier of at most 32 faces per level — a walk that outgrows it is
+// incomplete: the candidate fails itself and comes back in a later round — eight chains in flight per wave (measured: 12.0-12.1 ms
+// for 128 views; sixteen lanes each: 12.3-12.4; a wave each: 13.9-14.0).  The eight walks are independent but move in lock-step
+// through one instruction stream: every ballot is the whole wave's, a group reads its bits of it.  Same claims, same log, same
+// verdict rule as k_owner_claim.
 constexpr int kSubFront = 32;
-template <int SL>   // lanes per candidate: 16 (four to a wave) or 8 (eight)
 __global__ void __launch_bounds__(TO_BLOCK) k_owner_claim_sub(Bufs b, int round, int par) {
-    constexpr int NG = 64 / SL;
+    constexpr int SL = 8, NG = 64 / SL;   // lanes per candidate, candidates per wave
     __shared__ int fr[TO_WAVES_PER_BLOCK][NG][2][kSubFront];
     __shared__ int lg[TO_WAVES_PER_BLOCK][kClaimLog];
     __shared__ int lgc[TO_WAVES_PER_BLOCK][kClaimLog];
@@ -1003,7 +999,7 @@ __global__ void __launch_bounds__(TO_BLOCK) k_owner_claim_sub(Bufs b, int round,
     int* own_n = ocnt(b, par, sl);
     const int ncand = min(*ccnt(b, par, sl), cap);
     const int cstep = (gridDim.x / kSubLists) * TO_WAVES_PER_BLOCK * NG;
-    int c = ((blockIdx.x / kSubLists) * TO_WAVES_PER_BLOCK + wid) * NG + grp;   // this quarter's next candidate
+    int c = ((blockIdx.x / kSubLists) * TO_WAVES_PER_BLOCK + wid) * NG + grp;   // this group's next candidate
     int logn = 0;
     auto flush = [&]() {  // wave-uniform
         if (logn == 0) return;
@@ -1016,13 +1012,13 @@ __global__ void __launch_bounds__(TO_BLOCK) k_owner_claim_sub(Bufs b, int round,
         }
         logn = 0;
     };
-    // a quarter's walk (the same values in its sixteen lanes)
+    // a group's walk (the same values in its eight lanes)
     bool active = false, failed = false;
     int o = kNone, cur = 0, ncur = 0, nnext = 0, claimed = 0, base = 0;
     unsigned long long po = 0ull;
     double px = 0.0, py = 0.0, pz = 0.0;
     while (true) {
-        // ---- quarters without a walk take their next candidate (one try per turn)
+        // ---- groups without a walk take their next candidate (one try per turn)
         const bool fetch = !active && c < ncand;
         if (!__any(active || fetch)) break;
         {
@@ -1032,7 +1028,7 @@ __global__ void __launch_bounds__(TO_BLOCK) k_owner_claim_sub(Bufs b, int round,
             if (fetch) {
                 oc = cand[c];
                 ax = b.fmax[oc];
-                const int n0 = (b.early_out && gl < 3) ? b.fn[3 * oc + gl] : kNone;
+                const int n0 = gl < 3 ? b.fn[3 * oc + gl] : kNone;
                 if (ax == 0ull) {   // (never seen: a candidate without a point outside its face)
                     if (gl == 0) { b.fowner[oc] = kNone; atomicAnd(&b.fflags[oc], ~2); }
                 } else if (__hip_atomic_load(&b.fowner[oc], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == oc) {
@@ -1050,7 +1046,7 @@ __global__ void __launch_bounds__(TO_BLOCK) k_owner_claim_sub(Bufs b, int round,
                 }
                 c += cstep;
             }
-            const bool gd = (__ballot(doomed) & gm) != 0ull;   // (the whole wave's ballot; this quarter's bits)
+            const bool gd = (__ballot(doomed) & gm) != 0ull;   // (the whole wave's ballot; this group's bits)
             if (fetch && ok) {
                 if (gd) { if (gl == 0) atomicAnd(&b.fflags[oc], ~2); }
                 else {
@@ -1059,7 +1055,7 @@ __global__ void __launch_bounds__(TO_BLOCK) k_owner_claim_sub(Bufs b, int round,
                 }
             }
         }
-        // ---- one step of every walking quarter: sixteen (face, edge) pairs of its current level
+        // ---- one step of every walking group: eight (face, edge) pairs of its current level
         const int t = base + gl;
         bool mine = false, fail_me = false;
         int n = kNone, fail_other = kNone;
@@ -1097,7 +1093,7 @@ __global__ void __launch_bounds__(TO_BLOCK) k_owner_claim_sub(Bufs b, int round,
             nnext += cnt;
             failed = failed || (balf & gm) != 0ull;
             base += SL;
-            if (base >= 3 * ncur) {   // the level is done (the same in all lanes of the quarter)
+            if (base >= 3 * ncur) {   // the level is done (the same in all lanes of the group)
                 claimed += nnext;
                 if (nnext > kSubFront) failed = true;
                 ncur = nnext < kSubFront ? nnext : kSubFront;
@@ -1196,8 +1192,8 @@ __global__ void __launch_bounds__(TO_BLOCK) k_new_faces(Bufs b, int par) {
     // An error (face capacity, a claimed-face list that ran full, inconsistent topology) ends the build — but the host only learns of
     // it from its next readback, up to two batches of rounds later, and a round cut short by the capacity leaves horizon edges without
     // faces, links unset and `newface` words stale: walking that structure reads owners out of records nobody wrote (r06: a memory
-    // fault in tools/stress_hpr_repeat.py, on the build that runs out of faces and is retried).  So every round kernel leaves at
-    // once when the error word is set: the rounds behind the failing one do nothing (round_dead).
+    // fault on the build that runs out of faces and is retried; test_a_build_that_runs_out_of_faces_is_retried_cleanly).  So every
+    // round kernel leaves at once when the error word is set: the rounds behind the failing one do nothing (round_dead).
     if (b.ctrl[kCtrlError] != 0 || b.ctrl[kCtrlOverflow] != 0) return;
     const ListWalk w = list_walk(b, par, blockIdx.x, gridDim.x);
     for (int it = 0; it < w.loops; ++it) {
@@ -1371,16 +1367,6 @@ __global__ void __launch_bounds__(TO_BLOCK) k_link_reassign(Bufs b, int par, int
     if ((int)blockIdx.x < link_blocks) link_faces(b, par, blockIdx.x, link_blocks);
     else reassign_points(b, tab, blockIdx.x - link_blocks, gridDim.x - link_blocks);
 }
-// (experiments, TOHIP_HULL_SPLIT_LINK=1: the two halves as launches of their own, so that a profile shows which one the round waits for)
-__global__ void __launch_bounds__(TO_BLOCK) k_link_only(Bufs b, int par) {
-    if (b.ctrl[kCtrlError] != 0) return;
-    link_faces(b, par, blockIdx.x, gridDim.x);
-}
-__global__ void __launch_bounds__(TO_BLOCK) k_reassign_only(Bufs b) {
-    __shared__ FaceMaxTable tab;
-    if (b.ctrl[kCtrlError] != 0) return;
-    reassign_points(b, tab, blockIdx.x, gridDim.x);
-}
 
 // End of a round = start of the next: apexes of the faces created this round (point loop), then per listed face: the accepted
 // regions' faces die and the round's ownership is cleared; the candidates that are still alive and the new faces with points
@@ -1412,7 +1398,7 @@ __global__ void __launch_bounds__(TO_BLOCK) k_round_tail(Bufs b, int par, int ne
                 b.fowner[f1] = cand ? f1 : kNone;
                 b.fflags[f1] = alive | (cand ? 2 : 0);
                 if (from_cand) b.nfhead[f1] = 0;
-                if (cand && from_cand) b.fprio[f1] = make_prio(f1, next_round, apex_dist(b.fmax[f1]) * b.frec[f1].inv_norm, b.hbits);
+                if (cand && from_cand) b.fprio[f1] = make_prio(f1, next_round, apex_dist(b.fmax[f1]) * b.frec[f1].inv_norm);
             }
             c1 = cand && from_cand;  // a candidate enters through its own entry, not through a claim's
         }
@@ -1422,7 +1408,7 @@ __global__ void __launch_bounds__(TO_BLOCK) k_round_tail(Bufs b, int par, int ne
             c2 = f2 < nf && (b.fflags[f2] & 1) && b.fmax[f2] != 0ull;
             if (c2) {
                 b.fowner[f2] = f2; b.fflags[f2] = 3;
-                b.fprio[f2] = make_prio(f2, next_round, apex_dist(b.fmax[f2]) * b.frec[f2].inv_norm, b.hbits);
+                b.fprio[f2] = make_prio(f2, next_round, apex_dist(b.fmax[f2]) * b.frec[f2].inv_norm);
             }
         }
         const int slot = block_alloc(next_n, (c1 ? 1 : 0) + (c2 ? 1 : 0));
@@ -1469,7 +1455,7 @@ __device__ __forceinline__ bool is_sample(const Bufs& b, int lo, int hi, int j) 
     return b.serial ? ((j - lo) % sample_stride(b, lo, hi) == 0) : (j % b.sub == 0);
 }
 
-__host__ __device__ inline size_t sample_hull_lds_bytes(int KL) {
+__host__ __device__ constexpr size_t sample_hull_lds_bytes(int KL) {
     // per face: plane 6 doubles, inv_norm, 3 vertices, 3 neighbours, a mark, a flag byte; per vertex (<= KL / 2 + 4): 3 doubles + position
     const size_t nv = (size_t)KL / 2 + 8;
     return sizeof(double) * 6 * KL + sizeof(double) * 3 * nv + sizeof(unsigned long long) * 24 + sizeof(float) * KL +
@@ -1563,13 +1549,6 @@ __global__ void __launch_bounds__(kSerialThreads) k_sample_hull(Bufs b, int KL, 
             if (cf[p] >= 0) hgt[p] = (float)best * s_inv[cf[p]];
         }
     }
-#ifdef TOHIP_SH_STAMPS   // diagnostic build (tools/hpr_sample_stamps.sh): where an insertion's time goes, in shader clocks and 100 MHz ticks
-    unsigned long long st_acc[6] = {0, 0, 0, 0, 0, 0}, st_t = clock64();
-    const unsigned long long st_w0 = wall_clock64();
-#define SH_STAMP(i) { const unsigned long long st_n = clock64(); st_acc[i] += st_n - st_t; st_t = st_n; }
-#else
-#define SH_STAMP(i)
-#endif
     int nf = 4, nv = 4, created = 0;
     // Two block barriers per insertion: (1) after every wave has put its best point forward, (2) after the topology.  Face ids are
     // never reused, so a dead face keeps its mark (nobody's neighbour, nobody's conflict face: never looked at again) and nothing
@@ -1586,9 +1565,7 @@ __global__ void __launch_bounds__(kSerialThreads) k_sample_hull(Bufs b, int KL, 
             }
         key = wave_max63_u64(key);
         if (lane == 63) s_red[wid] = key;
-        SH_STAMP(0)
         __syncthreads();
-        SH_STAMP(1)
         key = 0ull;
         for (int w = 0; w < kSerialThreads / 64; ++w) key = s_red[w] > key ? s_red[w] : key;
         if (key == 0ull) break;   // nobody outside: the sample's hull is complete (block-uniform)
@@ -1668,9 +1645,7 @@ __global__ void __launch_bounds__(kSerialThreads) k_sample_hull(Bufs b, int KL, 
                 }
             }
         }
-        SH_STAMP(2)
         __syncthreads();
-        SH_STAMP(3)
         const int H = s_misc[1];
         if (H < 0 || s_misc[2]) break;   // (block-uniform)
         const double ax = __longlong_as_double((long long)s_red[16]), ay = __longlong_as_double((long long)s_red[17]),
@@ -1708,15 +1683,7 @@ __global__ void __launch_bounds__(kSerialThreads) k_sample_hull(Bufs b, int KL, 
                 if ((test >> p) & 1u) { cf[p] = bf[p]; hgt[p] = bf[p] >= 0 ? (float)best[p] * s_inv[bf[p]] : 0.f; }
         }
         nf += H; nv += 1; created += H;
-        SH_STAMP(4)
     }
-#ifdef TOHIP_SH_STAMPS
-    if (sg == 0 && lane == 0) {   // per wave: [phase 1 | barrier 1 wait | topology (or nothing) | barrier 2 wait | phase 3], insertions, wall ticks
-        unsigned long long* o = b.keys + 16 * wid;
-        for (int i = 0; i < 5; ++i) o[i] = st_acc[i];
-        o[5] = (unsigned long long)nv - 4; o[6] = wall_clock64() - st_w0; o[7] = (unsigned long long)nf;
-    }
-#endif
     __syncthreads();
     __syncthreads();
     if (s_misc[2] && t == 0) atomicOr(&b.ctrl[kCtrlError], kErrTopology);
@@ -1870,7 +1837,7 @@ __global__ void __launch_bounds__(TO_BLOCK) k_rebuild_candidates(Bufs b, int par
         const bool alive = f < nf && (b.fflags[f] & 1);
         const bool cand = alive && b.fmax[f] != 0ull;
         if (alive) { b.fowner[f] = cand ? f : kNone; b.fflags[f] = 1 | (cand ? 2 : 0); b.nfhead[f] = 0; }
-        if (cand) b.fprio[f] = make_prio(f, next_round, apex_dist(b.fmax[f]) * b.frec[f].inv_norm, b.hbits);
+        if (cand) b.fprio[f] = make_prio(f, next_round, apex_dist(b.fmax[f]) * b.frec[f].inv_norm);
         const int slot = block_alloc(next_n, cand ? 1 : 0);
         if (cand) {
             if (slot < cap) next[slot] = f;
@@ -2014,24 +1981,20 @@ inline int nblocks(int64_t n, int cap = 2048) {
 // Builds the hull of pts (n,3) [+ origin]; leaves vflag set.  Synchronises the stream.
 // b.seg_off must already be on the device (k_single_segment for one hull).
 static int build(const Bufs& b_in, const float* pts, int with_origin, int64_t max_seg_points, hipStream_t st, int* rounds_out) {
+    // The other schedules, for the GPU tests that check them against the default one in child processes:
+    //   TOHIP_HULL_CAREFUL        every round with ownership propagated to convergence (k_owner_prop + k_accept)
+    //   TOHIP_HULL_SERIAL=0       the sample's rounds instead of its hull by sequential insertion (k_sample_hull), as until r05
+    //   TOHIP_HULL_SHARE_EDGES=0  adjacent regions exclude each other, as until r05
+    static const bool always_careful = getenv("TOHIP_HULL_CAREFUL") != nullptr;
+    static const bool serial_sample = !getenv("TOHIP_HULL_SERIAL") || atoi(getenv("TOHIP_HULL_SERIAL")) != 0;
+    static const int share_edges = getenv("TOHIP_HULL_SHARE_EDGES") ? atoi(getenv("TOHIP_HULL_SHARE_EDGES")) : 1;
     Bufs b = b_in;  // local copy: the two live-point buffers swap roles at every compaction
     b.origin = with_origin ? 1 : 0;
-    {
-        // 9 = exponent + one mantissa bit: apexes more than ~1.4x higher go first, the hash decides among the rest.  Measured
-        // (tools/hpr_sweep.sh): 0 bits (hash only) 177 rounds / 10.7 ms at 1 M points, 6: 116 / 7.0, 9: 106 / 6.2, 12: 120 / 6.7, 16: 129 / 7.2
-        static const int hb = getenv("TOHIP_HULL_HBITS") ? atoi(getenv("TOHIP_HULL_HBITS")) : 9;  // experiments
-        b.hbits = hb < 0 ? 0 : (hb > 16 ? 16 : hb);
-        static const int eo = getenv("TOHIP_HULL_EARLY_OUT") ? atoi(getenv("TOHIP_HULL_EARLY_OUT")) : 1;  // experiments
-        b.early_out = eo;
-        static const int se = getenv("TOHIP_HULL_SHARE_EDGES") ? atoi(getenv("TOHIP_HULL_SHARE_EDGES")) : 1;    // experiments: 0 = adjacent regions exclude each other (r05)
-        b.share_edges = se;
-    }
+    b.share_edges = share_edges;
     {
         // large segments: the first rounds on a sample (see k_assign_all)
-        static const int force_sub = getenv("TOHIP_HULL_SUB") ? atoi(getenv("TOHIP_HULL_SUB")) : 0;  // experiments: 1 = off
         const int64_t avg = b.m1 / b.nseg;
         b.sub = (avg >= 32768 && b.nseg <= 65535) ? (int)std::min<int64_t>(128, std::max<int64_t>(2, avg / 1024)) : 1;
-        if (force_sub > 0) b.sub = force_sub;
     }
     hipError_t e = hipMemsetAsync(b.ctrl, 0, sizeof(int) * kCtrlTotal, st);
     if (e != hipSuccess) return (int)e;
@@ -2074,40 +2037,15 @@ static int build(const Bufs& b_in, const float* pts, int with_origin, int64_t ma
     }
     TO_HIP_CHECK_LAUNCH();
     // Large segments: the sample's hull by sequential insertion, one block per segment out of LDS (k_sample_hull) instead of the
-    // first ~20-25 rounds; then the join below, immediately.  TOHIP_HULL_SERIAL=0: the sample's rounds as until r05 (experiments);
-    // TOHIP_HULL_SERIAL_IDS: face ids per segment (LDS: 92 bytes each), TOHIP_HULL_SERIAL_FACES: stop after that many created.
-    int serial_ids = 0;
-    if (b.sub > 1) {
-        static const int want = getenv("TOHIP_HULL_SERIAL") ? atoi(getenv("TOHIP_HULL_SERIAL")) : 1;
-        // measured (tools/hpr_serial_sweep.sh, r06): an insertion costs ~5 us here, a round ~45 us for one hull and ~160 us for 128 —
-        // one hull is best served by 192-448 ids (flat), a batch by 768-896
-        static const int ids_env = getenv("TOHIP_HULL_SERIAL_IDS") ? atoi(getenv("TOHIP_HULL_SERIAL_IDS")) : 0;
-        const int ids = std::max(64, std::min(1536, (ids_env > 0 ? ids_env : (b.nseg == 1 ? 192 : 512)) / 2 * 2));   // (with regions sharing edges and the polled report, r06: one hull 2.19 / 2.19 / 2.17 / 2.23 / 2.26 / 2.39 ms at 64 / 128 / 192 / 256 / 320 / 448, the sample's rounds instead 2.22; 128 views 9.0 / 8.8 / 8.7 / 8.9 / 9.2 ms at 256 / 384 / 512 / 768 / 1024)
-        if (want && (int64_t)4 * b.nseg + (int64_t)b.nseg * (ids - 4) <= (int64_t)b.fcap) {
-            static int lds_ok_for = 0;   // the dynamic-LDS limit of the kernel is raised once per size
-            const size_t lds = sample_hull_lds_bytes(ids);
-            if (lds_ok_for != ids) {
-                if (hipFuncSetAttribute((const void*)k_sample_hull, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) lds_ok_for = ids;
-                else (void)hipGetLastError();
-            }
-            if (lds_ok_for == ids) serial_ids = ids;
-        }
-    }
-    if (serial_ids) {
-        static const int faces_env = getenv("TOHIP_HULL_SERIAL_FACES") ? atoi(getenv("TOHIP_HULL_SERIAL_FACES")) : 0;
-        const int target = faces_env > 0 ? faces_env : serial_ids;   // (the loop also stops when an insertion no longer fits the ids)
+    // first ~20-25 rounds; then the join below, immediately.  Face ids per segment (LDS: 92 bytes each), and the insertions stop
+    // after as many faces created (or when one no longer fits the ids).  Measured (r06): an insertion costs ~5 us here, a round ~45 us
+    // for one hull and ~160 us for 128; one hull 2.19 / 2.19 / 2.17 / 2.23 / 2.26 / 2.39 ms at 64 / 128 / 192 / 256 / 320 / 448 ids,
+    // the sample's rounds instead 2.22; 128 views 9.0 / 8.8 / 8.7 / 8.9 / 9.2 ms at 256 / 384 / 512 / 768 / 1024.
+    static_assert(sample_hull_lds_bytes(512) <= 65536, "both sizes fit the default limit of dynamic LDS");
+    const int serial_ids = b.nseg == 1 ? 192 : 512;
+    if (b.sub > 1 && serial_sample && (int64_t)4 * b.nseg + (int64_t)b.nseg * (serial_ids - 4) <= (int64_t)b.fcap) {
         b.serial = 1;
-        k_sample_hull<<<b.nseg, kSerialThreads, sample_hull_lds_bytes(serial_ids), st>>>(b, serial_ids, target);
-#ifdef TOHIP_SH_STAMPS
-        {
-            unsigned long long hst[16 * 8];
-            (void)hipStreamSynchronize(st);
-            (void)hipMemcpy(hst, b.keys, sizeof(hst), hipMemcpyDeviceToHost);
-            for (int w = 0; w < 8; ++w)
-                fprintf(stderr, "sample hull wave %d: phase1 %llu  wait1 %llu  topology %llu  wait2 %llu  phase3 %llu clocks; %llu insertions, %llu faces, %.1f us wall\n", w,
-                        hst[16 * w], hst[16 * w + 1], hst[16 * w + 2], hst[16 * w + 3], hst[16 * w + 4], hst[16 * w + 5], hst[16 * w + 7], hst[16 * w + 6] * 0.01);
-        }
-#endif
+        k_sample_hull<<<b.nseg, kSerialThreads, sample_hull_lds_bytes(serial_ids), st>>>(b, serial_ids, serial_ids);
     } else {
         if (b.sub > 1) k_live_stride<<<nblocks((b.m1 + b.sub - 1) / b.sub), TO_BLOCK, 0, st>>>(b);
         k_assign0<<<nblocks(b.m1, 1024), TO_BLOCK, 0, st>>>(b);
@@ -2156,9 +2094,7 @@ static int build(const Bufs& b_in, const float* pts, int with_origin, int64_t ma
         wslot ^= 1; ++inflight;
         return er;
     };
-    double host_enqueue_us = 0.0, host_wait_us = 0.0;  // for the trace: where the host's time goes
     auto collect = [&]() -> hipError_t {
-        const auto t0 = std::chrono::steady_clock::now();
         hipError_t er = hipSuccess;
         const volatile int* seqp = pin.rec[rslot] + kRepSeq;
         // poll; every so often ask the stream whether it is still working (a fault, or a report that never ran, must not hang the host)
@@ -2173,7 +2109,6 @@ static int build(const Bufs& b_in, const float* pts, int with_origin, int64_t ma
             }
             __builtin_ia32_pause();
         }
-        host_wait_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
         h = pin.rec[rslot];
         rslot ^= 1; --inflight;
         return er;
@@ -2188,25 +2123,17 @@ static int build(const Bufs& b_in, const float* pts, int with_origin, int64_t ma
     int nf = h[kCtrlNFaces + 8];
     const int max_rounds = 100000;
     int round = 0 /* rounds enqueued */, ncand = candidates(0), live_bound = (b.m1 + b.sub - 1) / b.sub;
-    static const bool batch_env = getenv("TOHIP_HULL_BATCH") != nullptr;
-    static const int batch = batch_env ? std::max(1, atoi(getenv("TOHIP_HULL_BATCH"))) : 3;  // experiments: rounds per readback (1 M points: 2.38 / 2.29 / 2.26 / 2.29 / 2.30 / 2.37 ms at 1 / 2 / 3 / 4 / 6 / 8)
-    static const bool always_careful = getenv("TOHIP_HULL_CAREFUL") != nullptr;                   // experiments: the slow path only
-    static const int compact_every = getenv("TOHIP_HULL_COMPACT") ? atoi(getenv("TOHIP_HULL_COMPACT")) : 2;
-    static const bool trace = getenv("TOHIP_HULL_TRACE") != nullptr;   // experiments: the build's progress, one line per readback
-    static const int fused_verdict = getenv("TOHIP_HULL_FUSED_ACCEPT") ? atoi(getenv("TOHIP_HULL_FUSED_ACCEPT")) : 1;   // experiments: 0 = a k_accept launch per round
-    static const int sub_claim = getenv("TOHIP_HULL_SUB_CLAIM") ? atoi(getenv("TOHIP_HULL_SUB_CLAIM")) : 4;   // experiments: candidates per wave from which the quarter-wave walk takes over (0 = never)
-    static const int sub_lanes = getenv("TOHIP_HULL_SUB_LANES") ? atoi(getenv("TOHIP_HULL_SUB_LANES")) : 8;   // eight candidates to a wave (measured: 12.0-12.1 ms for 128 views; 16 lanes each: 12.3-12.4; a wave each: 13.9-14.0)
-    static const int reassign_cap = getenv("TOHIP_HULL_REASSIGN_CAP") ? std::max(64, atoi(getenv("TOHIP_HULL_REASSIGN_CAP"))) : 1024;   // experiments: blocks of the point kernel
-    static const int grid_scale = getenv("TOHIP_HULL_GRID_SCALE") ? std::max(1, atoi(getenv("TOHIP_HULL_GRID_SCALE"))) : 4;   // experiments (1 M points: 2.97 / 2.89 / 2.85 / 2.84 ms at 1 / 2 / 4 / 8)
-    static const int split_link = getenv("TOHIP_HULL_SPLIT_LINK") ? atoi(getenv("TOHIP_HULL_SPLIT_LINK")) : 0;   // experiments
-    static const int join_faces = getenv("TOHIP_HULL_JOIN_FACES") ? atoi(getenv("TOHIP_HULL_JOIN_FACES")) : 192;  // experiments
+    constexpr int batch = 3;          // rounds per readback (1 M points: 2.38 / 2.29 / 2.26 / 2.29 / 2.30 / 2.37 ms at 1 / 2 / 3 / 4 / 6 / 8)
+    constexpr int compact_every = 2;  // readbacks between two compactions of the live list
+    constexpr int sub_claim = 4;      // candidates per wave from which eight walks to a wave take over (k_owner_claim_sub)
 
     // `careful`: ownership propagated to convergence with the host checking (after a batch that accepted nobody)
-    auto enqueue_rounds_inner = [&](int nrounds, bool careful) -> int {
+    auto enqueue_rounds = [&](int nrounds, bool careful) -> int {
         // grids: a wave per candidate; a thread per listed face (a candidate claims a handful of faces; lists grow within a batch)
         // (`ncand` is what a readback said two batches ago, and while a hull grows its candidates multiply by ~1.25 per round: the
-        // grids are cut for `grid_scale` times as many — a wave that finds no candidate leaves, one that finds three walks them in turn)
-        const int64_t nc_grid = (int64_t)ncand * grid_scale;
+        // grids are cut for four times as many — a wave that finds no candidate leaves, one that finds three walks them in turn;
+        // 1 M points: 2.97 / 2.89 / 2.85 / 2.84 ms at 1 / 2 / 4 / 8 times)
+        const int64_t nc_grid = (int64_t)ncand * 4;
         const int ga = kSubLists * (int)std::min<int64_t>(32, std::max<int64_t>(1, cdiv(nc_grid, kSubLists * TO_WAVES_PER_BLOCK)));
         const int gl = kSubLists * (int)std::min<int64_t>(16, std::max<int64_t>(1, cdiv(nc_grid * 16, kSubLists * TO_BLOCK)));
         for (int r = 0; r < nrounds; ++r, ++round) {
@@ -2214,11 +2141,11 @@ static int build(const Bufs& b_in, const float* pts, int with_origin, int64_t ma
             if (!careful) {
                 // Fast path: a wave per candidate walks and claims its region (one launch, no readback).  Incomplete
                 // ownership is safe — a candidate is accepted only if it owns every face its apex sees (k_accept).
-                // many candidates (a batch of views): four to a wave (k_owner_claim_sub); else a wave each
-                if (fused_verdict && sub_claim && (int64_t)ncand >= (int64_t)sub_claim * ga * TO_WAVES_PER_BLOCK)
-                    { if (sub_lanes == 8) k_owner_claim_sub<8><<<ga, TO_BLOCK, 0, st>>>(b, round, par); else k_owner_claim_sub<16><<<ga, TO_BLOCK, 0, st>>>(b, round, par); }
+                // many candidates (a batch of views): eight to a wave (k_owner_claim_sub); else a wave each
+                if ((int64_t)ncand >= (int64_t)sub_claim * ga * TO_WAVES_PER_BLOCK)
+                    k_owner_claim_sub<<<ga, TO_BLOCK, 0, st>>>(b, round, par);
                 else
-                    k_owner_claim<<<ga, TO_BLOCK, 0, st>>>(b, round, par, fused_verdict);
+                    k_owner_claim<<<ga, TO_BLOCK, 0, st>>>(b, round, par);
                 TO_HIP_CHECK_LAUNCH();
             } else {
                 while (true) {
@@ -2235,26 +2162,15 @@ static int build(const Bufs& b_in, const float* pts, int with_origin, int64_t ma
                 k_owned_list<<<kSubLists * (int)std::min<int64_t>(16, std::max<int64_t>(1, cdiv(nf, kSubLists * TO_BLOCK))), TO_BLOCK, 0, st>>>(b, par);
                 TO_HIP_CHECK_LAUNCH();
             }
-            const int gr = nblocks(live_bound, reassign_cap);
-            if (careful || !fused_verdict) k_accept<<<gl, TO_BLOCK, 0, st>>>(b, round, par);   // (the fast path's walk has given its verdict)
+            const int gr = nblocks(live_bound, 1024);
+            if (careful) k_accept<<<gl, TO_BLOCK, 0, st>>>(b, round, par);   // (the fast path's walk has given its verdict)
             k_new_faces<<<gl, TO_BLOCK, 0, st>>>(b, par);
-            if (split_link) {
-                k_link_only<<<gl, TO_BLOCK, 0, st>>>(b, par); k_reassign_only<<<gr, TO_BLOCK, 0, st>>>(b);
-                if (split_link == 2) k_reassign_only<<<gr, TO_BLOCK, 0, st>>>(b);   // (experiments: the second pass moves nobody — what the scan alone costs)
-            }
-            else k_link_reassign<<<gl + gr, TO_BLOCK, 0, st>>>(b, par, gl);
+            k_link_reassign<<<gl + gr, TO_BLOCK, 0, st>>>(b, par, gl);
             const int gt = gl;   // (a list walk: the apexes of the new faces come with their maxima since r06, no pass over the live points)
             k_round_tail<<<gt, TO_BLOCK, 0, st>>>(b, par, round + 1);
             TO_HIP_CHECK_LAUNCH();
         }
         return TOHIP_OK;
-    };
-
-    auto enqueue_rounds = [&](int nrounds, bool careful) -> int {
-        const auto t0 = std::chrono::steady_clock::now();
-        const int rc = enqueue_rounds_inner(nrounds, careful);
-        host_enqueue_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-        return rc;
     };
     int rounds_seen = 0;                 // rounds covered by the last collected readback
     int round_of[2] = {0, 0};            // rounds enqueued when each in-flight readback was posted
@@ -2265,7 +2181,7 @@ static int build(const Bufs& b_in, const float* pts, int with_origin, int64_t ma
     const int ahead = always_careful ? 1 : 2;
     auto drain = [&](int rc) { while (inflight > 0) (void)collect(); return rc; };
     // the sample's rounds end when its hulls have a few hundred faces each (faces created ~ 3x faces alive), are complete, or late
-    const int64_t switch_faces = (int64_t)join_faces * b.nseg;
+    const int64_t switch_faces = (int64_t)192 * b.nseg;
     auto join_all_points = [&]() -> int {
         hipError_t ej = hipMemsetAsync(b.seg_cnt, 0, sizeof(int) * (size_t)b.nseg, st);
         if (ej != hipSuccess) return (int)ej;
@@ -2308,7 +2224,6 @@ static int build(const Bufs& b_in, const float* pts, int with_origin, int64_t ma
             if (e != hipSuccess) return drain((int)e);
             if (h[kCtrlError]) return (h[kCtrlError] & kErrCapacity) ? TOHIP_ENOSPC : TOHIP_ENOTCONV;
             ncand = candidates(round & 1);
-            if (trace) fprintf(stderr, "hull: all points joined after round %d: faces %d live %d candidates %d\n", round, nf, h[kCtrlNLive], ncand);
             stalled = false;
             live_bound = std::max(1, h[kCtrlNLive]);   // the join compacted the list: this readback holds its length
             batches_since_compaction = 0;
@@ -2321,7 +2236,7 @@ static int build(const Bufs& b_in, const float* pts, int with_origin, int64_t ma
                 // nothing (up to eight such rounds at four per readback: 0.1 ms of a build) -> two per readback from here on
                 // ... and with tens of thousands of candidates (a batch of views) a round is hundreds of microseconds: the host is
                 // ahead anyway, and one round per readback wastes the fewest at the end (128 views: 9.5 ms at 4, 9.0 at 2, 8.9 at 1)
-                const int per = batch_env ? batch : (ncand >= 16384 ? 1 : (ncand <= 512 ? 2 : batch));
+                const int per = ncand >= 16384 ? 1 : (ncand <= 512 ? 2 : batch);
                 const int rc = enqueue_rounds(always_careful ? 1 : per, always_careful);
                 if (rc != TOHIP_OK) return drain(rc);
                 round_of[wslot] = round;
@@ -2330,7 +2245,6 @@ static int build(const Bufs& b_in, const float* pts, int with_origin, int64_t ma
             }
         } else if (inflight == 0) {
             // every enqueued round has reported and the last one accepted nobody: one round with converged ownership
-            if (trace) fprintf(stderr, "hull: careful round %d (candidates %d)\n", round, ncand);
             const int rc = enqueue_rounds(1, true);
             if (rc != TOHIP_OK) return drain(rc);
             round_of[wslot] = round;
@@ -2342,14 +2256,9 @@ static int build(const Bufs& b_in, const float* pts, int with_origin, int64_t ma
         e = collect();
         if (e != hipSuccess) return drain((int)e);
         rounds_seen = posted_at;
-        if (h[kCtrlError]) {
-            if (trace) fprintf(stderr, "hull: error bits %d at round %d\n", h[kCtrlError], posted_at);
-            return drain((h[kCtrlError] & kErrCapacity) ? TOHIP_ENOSPC : TOHIP_ENOTCONV);
-        }
+        if (h[kCtrlError]) return drain((h[kCtrlError] & kErrCapacity) ? TOHIP_ENOSPC : TOHIP_ENOTCONV);
         nf = h[kCtrlNFaces + 8] < b.fcap ? h[kCtrlNFaces + 8] : b.fcap;
         ncand = candidates(posted_at & 1);
-        if (trace) fprintf(stderr, "hull: round %d faces %d live %d candidates %d accepted(last) %d\n", posted_at, nf, h[kCtrlNLive], ncand,
-                           h[kCtrlAccepted]);
         if (ncand == 0) {  // no face has a point outside it: the hull is complete (rounds still in flight are no-ops) ...
             if (b.sub > 1) continue;  // ... of the sample: time for the other points
             break;
@@ -2379,10 +2288,10 @@ static int build(const Bufs& b_in, const float* pts, int with_origin, int64_t ma
     }
     if (round >= max_rounds && ncand > 0) return drain(TOHIP_ENOTCONV);
     round = rounds_seen;
-    if (trace) fprintf(stderr, "hull: %d rounds; host: %.0f us enqueueing rounds, %.0f us waiting for readbacks\n", round, host_enqueue_us, host_wait_us);
     if (rounds_out) *rounds_out = round;
     k_mark_vertices<<<nblocks(nf), TO_BLOCK, 0, st>>>(b);
-    TO_HIP_CHECK_LAUNCH();
+    e = hipGetLastError();   // (a report may be in flight into the shared mapped records: drain before leaving)
+    if (e != hipSuccess) return drain((int)e);
     while (inflight > 0) {  // the mapped records are this thread's next build's too
         e = collect();
         if (e != hipSuccess) return (int)e;

@@ -177,8 +177,7 @@ extern "C" int tohip_pointcloud2_to_xyz(const uint8_t* data, int64_t n_points, i
         layout |= datatype == 8 ? TO_PC2_F64_ALIGNED : TO_PC2_F32_ALIGNED;
     if ((layout & TO_PC2_F32_ALIGNED) && point_step == 16 && !((uintptr_t)data & 15)) layout |= TO_PC2_VEC16;
     // large messages only: below ~2 M points the call is its three launches' boundaries either way
-    static const int adapt_env = getenv("TOHIP_PC2_ADAPTIVE") ? atoi(getenv("TOHIP_PC2_ADAPTIVE")) : 1;   // experiments: 0 = always two passes
-    Pc2Mode* mode = (adapt_env && n_points >= (int64_t)2 << 20) ? (Pc2Mode*)((char*)workspace + 2 * sg + 128) : nullptr;
+    Pc2Mode* mode = n_points >= (int64_t)2 << 20 ? (Pc2Mode*)((char*)workspace + 2 * sg + 128) : nullptr;
     k_pc2_count<<<ntiles, TO_BLOCK, 0, st>>>(data, n_points, point_step, x_off, y_off, z_off, datatype, layout,
                                               remove_nans, tile_count, mode, out_xyz);
     TO_HIP_CHECK_LAUNCH();

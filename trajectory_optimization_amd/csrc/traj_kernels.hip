@@ -734,7 +734,7 @@ k_traj_pass1_cull(CloudView cv, const WayRec* __restrict__ rec, int V, EvalK k, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// sparse: blocks of NW waves (4 by default: up to four blocks to a CU, 1 024 resident; 16 behind TOHIP_SPARSE_WAVES for comparison)
+// sparse: blocks of NW = 4 waves (up to four blocks to a CU, 1 024 resident; kSparseWaves)
 // take the candidate (slot, trajectory) bits pass 1 set (6-8 % of the slots on the BASELINE workloads; 15-37 % once an optimisation
 // has moved the trajectory or in an indoor cloud).  Every wave holds the slot's 256 points (four consecutive points per lane, as
 // two packed pairs); the slot's flagged waypoints of a trajectory, in ascending order, are dealt by rank & 15 into SIXTEEN partial
@@ -796,7 +796,7 @@ struct __attribute__((aligned(16))) StagedWay {
 };
 static_assert(sizeof(StagedWay) == 80, "StagedWay is 20 floats");
 
-// NW = waves of the block (16 or 4); SFW = flag words held (TO_SP_MAXW, or 8 where one trajectory of at most TO_SP_STAGE virtual
+// NW = waves of the block (kSparseWaves); SFW = flag words held (TO_SP_MAXW, or 8 where one trajectory of at most TO_SP_STAGE virtual
 // waypoints is all there is: 36 KB instead of 44, four 4-wave blocks to a CU)
 template <int NW, int SFW>
 struct SparseLds {
@@ -1056,7 +1056,7 @@ __device__ __forceinline__ void sparse_walk(const SparseArgs& a, int b, int nb, 
 }
 
 template <int MODE, bool OCC, int NW, int SFW>
-__global__ void __launch_bounds__(NW * 64, (NW == 16 || SFW == 8) ? 4 : 3) k_traj_sparse(SparseArgs a, OptStep os) {   // (4 waves per SIMD: 128 registers; 3 where the LDS allows no more)
+__global__ void __launch_bounds__(NW * 64, SFW == 8 ? 4 : 3) k_traj_sparse(SparseArgs a, OptStep os) {   // (4 waves per SIMD: 128 registers; 3 where the LDS allows no more)
     __shared__ SparseLds<NW, SFW> L;
     // The step's prologue (opt_step.hpp: a trajectory's regularisers with their gradient, the step's Adam constants) needs the
     // positions only and is wanted by the finish kernel: it rides HERE, as one block per trajectory behind the candidates' blocks —
@@ -1974,7 +1974,6 @@ inline TrajPlan make_plan(int64_t n, int64_t V, int64_t W, int64_t n_traj = 1) {
 
 // dense pass 1: as many persistent blocks as are resident at once (never more than one per (point block, waypoint) pair)
 inline int dense_blocks(int nblk, int V, bool occ) {
-    static const int forced = [] { const char* e = getenv("TOHIP_DENSE_BLOCKS"); return e ? atoi(e) : 0; }();  // experiments
     static int per_cu[2] = {0, 0}, cus = 0;
     if (cus == 0) {
         int dev = 0;
@@ -1991,7 +1990,7 @@ inline int dense_blocks(int nblk, int V, bool occ) {
         if (per_cu[0] < 1) per_cu[0] = 1;
         if (per_cu[1] < 1) per_cu[1] = 1;
     }
-    int64_t nb = forced > 0 ? forced : (int64_t)per_cu[occ ? 1 : 0] * cus;
+    int64_t nb = (int64_t)per_cu[occ ? 1 : 0] * cus;
     const int64_t total = (int64_t)nblk * V;
     if (nb > total) nb = total;
     return (int)nb;
@@ -2099,16 +2098,9 @@ inline int launch_probe_pass1(const TrajStep& s, const float* poses, const float
             // blocks of four waves, up to eight to a row: a waypoint's reachable slots are evaluated by 32 waves on up to eight CUs.
             // (Two 16-wave blocks to a row kept a heavy row — 800 reachable slots in a 10 m room, 100 on the slab — on the eight
             // SIMDs of two CUs: 17 us of instruction issue there while the light rows' CUs idled.)
-            static const int cull_waves = [] { const char* e = getenv("TOHIP_CULL_WAVES"); return e && atoi(e) == 16 ? 16 : 4; }();
-            if (cull_waves == 16) {
-                const dim3 grid(V <= 256 ? 2 : 1, V);
-                if (occ) k_traj_pass1_cull<true, 16><<<grid, 1024, 0, s.st>>>(s.cv, s.rec, V, s.k, s.part, s.ext, s.cbits, s.pl.fv_words, s.live, s.occ, s.occw, oi);
-                else k_traj_pass1_cull<false, 16><<<grid, 1024, 0, s.st>>>(s.cv, s.rec, V, s.k, s.part, s.ext, s.cbits, s.pl.fv_words, s.live, s.occ, s.occw, oi);
-            } else {
-                const dim3 grid(std::max(1, std::min(8, 1024 / V)), V);
-                if (occ) k_traj_pass1_cull<true, 4><<<grid, 256, 0, s.st>>>(s.cv, s.rec, V, s.k, s.part, s.ext, s.cbits, s.pl.fv_words, s.live, s.occ, s.occw, oi);
-                else k_traj_pass1_cull<false, 4><<<grid, 256, 0, s.st>>>(s.cv, s.rec, V, s.k, s.part, s.ext, s.cbits, s.pl.fv_words, s.live, s.occ, s.occw, oi);
-            }
+            const dim3 grid(std::max(1, std::min(8, 1024 / V)), V);
+            if (occ) k_traj_pass1_cull<true, 4><<<grid, 256, 0, s.st>>>(s.cv, s.rec, V, s.k, s.part, s.ext, s.cbits, s.pl.fv_words, s.live, s.occ, s.occw, oi);
+            else k_traj_pass1_cull<false, 4><<<grid, 256, 0, s.st>>>(s.cv, s.rec, V, s.k, s.part, s.ext, s.cbits, s.pl.fv_words, s.live, s.occ, s.occw, oi);
         } else {
             const int nblk8 = (int)(s.pl.npad / (TO_BLOCK * TO_PD));
             const int nb = dense_blocks(nblk8, V, occ);
@@ -2135,11 +2127,8 @@ inline SparseArgs sparse_args(const TrajStep& s, float* lo_sum) {
 // of its own; a dense cloud lists every slot and the blocks loop
 // 4-wave blocks, four to a CU (all resident): a candidate slot is a chain of dependent accesses of ~9 us whatever the block's
 // shape, and a 16-wave block holds a whole CU for it — 1 441 candidates (the BASELINE trajectory after a hundred optimiser steps)
-// were 5.6 rounds of 256 such blocks, 28 us.  Sixteen-wave blocks remain for experiments (TOHIP_SPARSE_WAVES=16).
-inline int sparse_waves() {
-    static const int nw = [] { const char* e = getenv("TOHIP_SPARSE_WAVES"); const int v = e ? atoi(e) : 0; return v == 16 ? 16 : 4; }();
-    return nw;
-}
+// were 5.6 rounds of 256 such blocks, 28 us.
+constexpr int kSparseWaves = 4;
 // one 16-wave block per CU, all resident: the pairs are dealt to the grid's waves
 inline int pair_blocks() {
     static const int cus = [] {
@@ -2158,28 +2147,28 @@ inline bool sparse_small_flags(const TrajStep& s) {
     if (s.n_traj == 1) return s.V <= 8 * 64;
     return s.max_traj_v > 0 && s.max_traj_v <= 7 * 64;
 }
-inline int sparse_blocks(const TrajStep& s, int nw) {
-    // as many blocks as are RESIDENT at once — four 4-wave blocks to a CU with the small flag array, three with the large one, two of
-    // sixteen waves — shared evenly by the trajectories: a block walks its trajectory's candidates q, q + S, ..., and a block that
+inline int sparse_blocks(const TrajStep& s) {
+    // as many blocks as are RESIDENT at once — four 4-wave blocks to a CU with the small flag array, three with the large one —
+    // shared evenly by the trajectories: a block walks its trajectory's candidates q, q + S, ..., and a block that
     // waits for a CU starts its walk when the others are half way through theirs (r04 launched 1 024 blocks of which 768 were
     // resident for eight trajectories: 72 us where 55 do)
-    const int64_t resident = (int64_t)pair_blocks() * (nw == 16 ? 2 : (sparse_small_flags(s) ? 4 : 3));
+    const int64_t resident = (int64_t)pair_blocks() * (sparse_small_flags(s) ? 4 : 3);
     const int64_t per_traj = std::max<int64_t>(1, std::min<int64_t>(s.pl.nslots, resident / s.n_traj));
     return (int)(per_traj * s.n_traj);
 }
 
-template <int MODE, bool OCC, int NW>
-inline void launch_sparse_nw(const TrajStep& s, const SparseArgs& a) {
-    const int grid = sparse_blocks(s, NW) + (s.opt.mode ? s.opt.n_traj : 0);   // (+ the step's prologue blocks)
+template <int MODE, bool OCC>
+inline void launch_sparse_occ(const TrajStep& s, const SparseArgs& a) {
+    constexpr int NW = kSparseWaves;
+    const int grid = sparse_blocks(s) + (s.opt.mode ? s.opt.n_traj : 0);   // (+ the step's prologue blocks)
     if (sparse_small_flags(s)) k_traj_sparse<MODE, OCC, NW, 8><<<grid, NW * 64, 0, s.st>>>(a, s.opt);
     else k_traj_sparse<MODE, OCC, NW, TO_SP_MAXW><<<grid, NW * 64, 0, s.st>>>(a, s.opt);
 }
 
 template <int MODE>
 inline int launch_sparse(const TrajStep& s, const SparseArgs& a) {
-    const bool w16 = sparse_waves() == 16;
-    if (s.occ) { if (w16) launch_sparse_nw<MODE, true, 16>(s, a); else launch_sparse_nw<MODE, true, 4>(s, a); }
-    else { if (w16) launch_sparse_nw<MODE, false, 16>(s, a); else launch_sparse_nw<MODE, false, 4>(s, a); }
+    if (s.occ) launch_sparse_occ<MODE, true>(s, a);
+    else launch_sparse_occ<MODE, false>(s, a);
     TO_HIP_CHECK_LAUNCH();
     return TOHIP_OK;
 }
