@@ -36,26 +36,36 @@ def pc_to_voxel(pc, resolution=0.15, x=(0, 90), y=(-50, 50), z=(-4.5, 5.5)):
     return voxel
 
 
-def voxel_grid(points, leaf=0.1, field=2, lim_min=-2.5, lim_max=2.5):
+def _voxel_runs(points, leaf, field, lim_min, lim_max):
+    """The filtered points in stable voxel-key order and their runs -> (qs, heads, ends), or the input when the grid overflows."""
     p = np.asarray(points, np.float32)
     keep = np.isfinite(p).all(1)
     if field is not None and field >= 0:
         keep &= ~((p[:, field] > np.float32(lim_max)) | (p[:, field] < np.float32(lim_min)))
     q = p[keep]
     if len(q) == 0:
-        return np.zeros((0, 3), np.float32)
-    inv = np.float32(1.0) / np.float32(leaf)
+        return np.zeros((0, 3), np.float32), None
+    inv = np.float32(1.0) / np.broadcast_to(np.asarray(leaf, np.float32), (3,))   # a scalar leaf or one per axis
     cell = np.floor(q * inv).astype(np.int64)
     mn = cell.min(0)
     div = cell.max(0) - mn + 1
     if int(div[0]) * int(div[1]) * int(div[2]) > 2**31 - 1:   # pcl::VoxelGrid: "Leaf size is too small ...": output = input
-        return p.copy()
+        return p.copy(), None
     ijk = cell - mn
     key = ijk[:, 0] + ijk[:, 1] * div[0] + ijk[:, 2] * div[0] * div[1]
     order = np.argsort(key, kind="stable")
     ks, qs = key[order], q[order]
     heads = np.flatnonzero(np.r_[True, ks[1:] != ks[:-1]])
     ends = np.r_[heads[1:], len(ks)]
+    return qs, (heads, ends)
+
+
+def voxel_grid_loop(points, leaf=0.1, field=2, lim_min=-2.5, lim_max=2.5):
+    """The definition: one voxel at a time, its points added one by one in f32 (slow: a Python loop over every point)."""
+    qs, runs = _voxel_runs(points, leaf, field, lim_min, lim_max)
+    if runs is None:
+        return qs
+    heads, ends = runs
     out = np.empty((len(heads), 3), np.float32)
     for v, (a, b) in enumerate(zip(heads, ends)):  # sequential float32 accumulation like PCL's accumulator
         s = np.zeros(3, np.float32)
@@ -63,3 +73,19 @@ def voxel_grid(points, leaf=0.1, field=2, lim_min=-2.5, lim_max=2.5):
             s = s + r
         out[v] = s / np.float32(b - a)
     return out
+
+
+def voxel_grid(points, leaf=0.1, field=2, lim_min=-2.5, lim_max=2.5):
+    """voxel_grid_loop with the loop turned inside out: step r adds the r-th point of every voxel that has one.  Each voxel still
+    sums its points in the same order in f32, so the result is bitwise the loop's (tests/test_ingest.py checks it)."""
+    qs, runs = _voxel_runs(points, leaf, field, lim_min, lim_max)
+    if runs is None:
+        return qs
+    heads, ends = runs
+    cnt = ends - heads
+    s = np.zeros((len(heads), 3), np.float32)
+    live = np.arange(len(heads))
+    for r in range(int(cnt.max())):
+        live = live[cnt[live] > r]
+        s[live] = s[live] + qs[heads[live] + r]
+    return s / cnt.astype(np.float32)[:, None]

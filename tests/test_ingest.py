@@ -86,6 +86,7 @@ def test_hip_pc_to_voxel(dev):
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,leaf", [(1, 0.1), (5000, 0.5), (200_000, 0.1), (1_000_000, 0.2)])
 def test_hip_voxel_grid_vs_oracle(dev, n, leaf):
+    """Bitwise at every size: the kernel and the oracle take each voxel's points in the same (stable) order and add them in f32."""
     from oracle import ingest_oracle
     from trajectory_optimization_amd import pointcloud_utils as pcu
     rng = np.random.default_rng(n)
@@ -93,17 +94,27 @@ def test_hip_voxel_grid_vs_oracle(dev, n, leaf):
     if n > 10:
         p[rng.integers(0, n, n // 50)] = np.nan
     out = pcu.voxel_grid_filter(torch.from_numpy(p).to(dev), leaf, "z", -2.5, 2.5).cpu().numpy()
-    ref = ingest_oracle.voxel_grid(p, leaf, 2, -2.5, 2.5) if n <= 200_000 else None
-    if ref is not None:
-        assert out.shape == ref.shape
-        np.testing.assert_allclose(out, ref, rtol=1e-6, atol=1e-6)
-    else:  # full size: properties
-        kept = p[np.isfinite(p).all(1) & (p[:, 2] <= 2.5) & (p[:, 2] >= -2.5)]
-        cells = np.floor(kept * (np.float32(1.0) / np.float32(leaf))).astype(np.int64)
-        assert len(out) == len(np.unique(cells, axis=0))
-        np.testing.assert_allclose(out.astype(np.float64).mean(0) * 0 + np.sort(out[:, 2])[[0, -1]].clip(-2.5, 2.5).sum() * 0, 0)
+    ref = ingest_oracle.voxel_grid(p, leaf, 2, -2.5, 2.5)
+    assert out.shape == ref.shape
+    assert np.array_equal(out.view(np.uint32), ref.view(np.uint32))
     none = pcu.voxel_grid_filter(torch.from_numpy(p).to(dev), leaf, "z", 100.0, 200.0)
     assert none.shape[0] == 0
+
+
+@pytest.mark.parametrize("leaf,field", [(0.5, 2), ((0.1, 0.25, 0.4), 0), (0.3, None), (0.05, 1)])
+def test_oracle_voxel_grid_fast_form_is_the_loop(leaf, field):
+    """voxel_grid (one step per rank within a voxel) against voxel_grid_loop (one point at a time): bitwise, including a voxel with
+    hundreds of points where any change of summation order shows."""
+    from oracle import ingest_oracle
+    rng = np.random.default_rng(9)
+    p = (rng.random((4000, 3)) * np.array([6, 4, 3]) - np.array([3, 2, 1.5])).astype(np.float32)
+    p[:600] = rng.uniform(0.26, 0.49, (600, 3)).astype(np.float32)   # one crowded voxel at leaf 0.5 / 0.3 / (0.1, 0.25, 0.4)
+    p[rng.integers(0, 4000, 40), rng.integers(0, 3, 40)] = np.nan
+    rng.shuffle(p)
+    fast = ingest_oracle.voxel_grid(p, leaf, field, -1.0, 1.2)
+    loop = ingest_oracle.voxel_grid_loop(p, leaf, field, -1.0, 1.2)
+    assert fast.dtype == loop.dtype == np.float32 and fast.shape == loop.shape and len(fast) > 50
+    assert np.array_equal(fast.view(np.uint32), loop.view(np.uint32))
 
 
 def test_oracle_voxel_grid_leaf_too_small():
