@@ -37,9 +37,11 @@
 extern "C" {
 #endif
 
-/* 12 (r05): + tohip_render_points_blend / tohip_render_blend_workspace_bytes; + TOHIP_TRAJ_OPT_LAST_OUTPUTS; tohip_voxel_grid reports
+/* 13: + tohip_pose_workspace_bytes_multi / tohip_pose_forward_backward_multi / tohip_pose_opt_step_multi (several poses of one
+ * camera over one cloud per pass).
+ * 12 (r05): + tohip_render_points_blend / tohip_render_blend_workspace_bytes; + TOHIP_TRAJ_OPT_LAST_OUTPUTS; tohip_voxel_grid reports
  * PCL's "leaf size too small" case as *out_count = -1.  (11: r04) */
-#define TOHIP_ABI_VERSION 12
+#define TOHIP_ABI_VERSION 13
 
 #define TOHIP_OK 0
 #define TOHIP_EINVAL (-1)   /* bad size / null pointer */
@@ -384,6 +386,43 @@ int tohip_pose_opt_step(const void *packed, int64_t n_points, float *trans, floa
                         float *exp_avg_t, float *exp_avg_sq_t, float *exp_avg_q, float *exp_avg_sq_q, float lr_pose, float lr_quat,
                         float beta1, float beta2, float adam_eps, int32_t step, float *loss_log, void *workspace,
                         size_t workspace_bytes, void *stream);
+
+/* ---- several poses of one camera over one cloud (many starts, candidate views) ------------------
+ * B = n_poses poses in rows of trans (B,3) / quat (B,4); every pass over the cloud evaluates a tile of them on the points it holds
+ * in registers.  Each pose's sums are taken in the order of the single-pose pass on the same grid: scalars, gradients,
+ * observations and Adam updates are bit for bit those of B single-pose calls.  occlusion_mask (N, caller's order, may be NULL)
+ * multiplies every pose's observations. */
+size_t tohip_pose_workspace_bytes_multi(int64_t n_points, int64_t n_poses);
+/* observations (B,N) in the caller's point order, or NULL: nothing is written.  scalars (B,4) as tohip_pose_forward's per pose.
+ * trans_grad (B,3) / quat_grad (B,4) = gout[b] x d loss_b / d (trans_b, raw quat_b); gout = device pointer to B floats, NULL = 1.
+ * Both gradient pointers NULL: the forward-only pass (scoring candidate views); one of them NULL alone is an error.
+ * Two launches. */
+int tohip_pose_forward_backward_multi(const void *packed, int64_t n_points, const float *trans, const float *quat, int64_t n_poses,
+                                      const tohip_camera *cam_host, const float *occlusion_mask, float *observations, float *scalars,
+                                      const float *gout, float *trans_grad, float *quat_grad, void *workspace,
+                                      size_t workspace_bytes, void *stream);
+/* One step of B independent PoseOpt loops (tohip_pose_opt_step per pose): Adam with two groups per pose (trans @ lr_pose,
+ * quat @ lr_quat), shared betas / eps, its own moments per pose.  Filled once, passed by pointer in HOST memory. */
+typedef struct tohip_pose_opt {
+    const void *packed;        /* tohip_pack_cloud blob */
+    int64_t n_points;
+    int32_t n_poses;           /* B */
+    int32_t n_steps;           /* rows of loss_log per pose */
+    tohip_camera cam;
+    const float *occlusion_mask;   /* N, caller's order, may be NULL: shared by every pose */
+    float *trans, *quat;       /* (B,3), (B,4): the parameters, updated in place */
+    float lr_pose, lr_quat, beta1, beta2, adam_eps;
+    float *exp_avg_t, *exp_avg_sq_t;   /* (B,3) */
+    float *exp_avg_q, *exp_avg_sq_q;   /* (B,4) */
+    float *scalars;            /* (B,4): the step's sum and loss per pose */
+    float *trans_grad, *quat_grad;     /* (B,3), (B,4), may be NULL: the step's gradients */
+    float *loss_log;           /* (B, n_steps): loss_log[b n_steps + step - 1] = pose b's loss of this step (before the update) */
+    void *workspace;           /* tohip_pose_workspace_bytes_multi(n_points, n_poses) */
+    size_t workspace_bytes;
+} tohip_pose_opt;
+/* step = 1, 2, ... n_steps, in order.  observations (B,N) or NULL: pass it on the step that should leave them (the last).
+ * Two launches; nothing synchronises. */
+int tohip_pose_opt_step_multi(const tohip_pose_opt *opt_host, int32_t step, float *observations, void *stream);
 
 /* ---- element-wise helpers of model.py (forward values) ---------------------------------------- */
 /* to_camera_frame (model.py:50-57; normalize=1) / ego_to_cam_torch (pc_processor.py:63-70;

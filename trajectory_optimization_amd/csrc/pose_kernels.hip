@@ -210,7 +210,9 @@ struct PoseFinish {
     float* loss_log;           // adam: loss_log[step - 1] = the loss of this step
 };
 
-__global__ void __launch_bounds__(1024) k_pose_finish(PoseFinish f) {
+// k_pose_finish's body, shared with k_pose_finish_multi (one block per pose there): the order of every f64 add depends only on
+// f.nparts and blockDim.x, so a pose of a batch gets the bits it gets alone
+__device__ __forceinline__ void pose_finish_body(const PoseFinish& f) {
     __shared__ double stot[16];
     __shared__ double sred[1024 / 16][16];
     __shared__ WayRec srec;
@@ -262,6 +264,178 @@ __global__ void __launch_bounds__(1024) k_pose_finish(PoseFinish f) {
             for (int i = 0; i < 4; ++i) adam_apply(const_cast<float*>(f.quat), o[3 + i], f.mq, f.vq, i, f.beta1, f.beta2, f.adam_eps, cq);
         }
     }
+}
+
+__global__ void __launch_bounds__(1024) k_pose_finish(PoseFinish f) { pose_finish_body(f); }
+
+// ---------------------------------------------------------------------------------------------
+// Several poses of one camera over one cloud (optimizer.optimize_poses: many starts; scoring candidate views).
+//
+// Grid nb x T: nb is the single-pose pass's grid for this cloud, T = ceil(B / TO_POSE_TILE) tiles of poses.  Block (c0, tile)
+// walks the chunks c0, c0 + nb, ... exactly as k_pose_stream's block c0 does (same eight points per lane, same prefetch) and
+// evaluates the tile's poses on each chunk while its points sit in registers: the points are read once per tile instead of once
+// per pose.  Per pose a lane adds in the single-pose order, then the same DPP tree and the same f64 order over the waves, so the
+// (pose, block) row of partials is bitwise the row k_pose_stream writes for that pose alone.  Each pose carries 1 + 12 packed
+// accumulators (25 VGPRs): TO_POSE_TILE is set from the register report.
+#ifndef TO_POSE_TILE   // (-DTO_POSE_TILE=n: a diagnostic build for comparing tile sizes, tools/time_pose_multi.py)
+#define TO_POSE_TILE 2
+#endif
+
+struct PoseMultiArgs {
+    CloudView cv;
+    const float* trans;   // (B,3)
+    const float* quat;    // (B,4)
+    int n_poses;
+    EvalK k;
+    const float* mask;    // caller's order, may be NULL: shared by every pose
+    float* obs;           // (B,N) caller's order, may be NULL: nothing written
+    double* part;         // (B, nb, 16): pose b's rows are part[(b nb + block) 16 + j]
+};
+
+template <bool GRAD>
+__global__ void __launch_bounds__(TO_BLOCK) k_pose_stream_multi(PoseMultiArgs a) {
+    __shared__ WayRec srec[TO_POSE_TILE];
+    __shared__ WayCold scold[TO_POSE_TILE];
+    __shared__ float swave[TO_POSE_TILE][TO_WAVES_PER_BLOCK][16];
+    const int b0 = (int)blockIdx.y * TO_POSE_TILE;
+    const int np = a.n_poses - b0 < TO_POSE_TILE ? a.n_poses - b0 : TO_POSE_TILE;   // poses of this tile (the last may hold fewer)
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    // the tile's camera records, one thread per pose (prep_wayrec as k_pose_stream's pose_record)
+    if (t < np) prep_wayrec(0, a.trans + 3 * (b0 + t), a.quat + 4 * (b0 + t), 1, nullptr, nullptr, a.k, &srec[t], &scold[t], nullptr, 1);
+    __syncthreads();
+    // every record's first line as scalars (a packed instruction takes one scalar operand); a tile's missing poses copy its last
+    WayRec r[TO_POSE_TILE];
+#pragma unroll
+    for (int p = 0; p < TO_POSE_TILE; ++p) {
+        const float* src = reinterpret_cast<const float*>(&srec[p < np ? p : np - 1]);
+        float* dst = reinterpret_cast<float*>(&r[p]);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) dst[i] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, src[i])));
+    }
+    const EvalK& k = a.k;
+    const bool ident = a.cv.hdr[0] == 0;
+    const int64_t n = a.cv.n, npad = a.cv.npad;
+    float asum[TO_POSE_TILE];
+    f2 acc[TO_POSE_TILE][12];
+#pragma unroll
+    for (int p = 0; p < TO_POSE_TILE; ++p) {
+        asum[p] = 0.f;
+#pragma unroll
+        for (int j = 0; j < 12; ++j) acc[p][j] = pk_splat(0.f);
+    }
+    const int64_t nchunks = npad / TO_POSE_CHUNK;
+    float nx[TO_POSE_PTS], ny[TO_POSE_PTS], nz[TO_POSE_PTS];
+    if ((int64_t)blockIdx.x < nchunks) load_points<TO_POSE_PTS>(a.cv.soa, npad, (int64_t)blockIdx.x * TO_POSE_CHUNK + (int64_t)t * TO_POSE_PTS, nx, ny, nz);
+    for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int64_t base = c * TO_POSE_CHUNK + (int64_t)t * TO_POSE_PTS;
+        float x[TO_POSE_PTS], y[TO_POSE_PTS], z[TO_POSE_PTS];
+#pragma unroll
+        for (int i = 0; i < TO_POSE_PTS; ++i) { x[i] = nx[i]; y[i] = ny[i]; z[i] = nz[i]; }
+        if (c + gridDim.x < nchunks) load_points<TO_POSE_PTS>(a.cv.soa, npad, (c + gridDim.x) * TO_POSE_CHUNK + (int64_t)t * TO_POSE_PTS, nx, ny, nz);
+        if (base >= n) continue;   // pads only
+        const bool whole = base + TO_POSE_PTS <= n && ident;
+        int o[TO_POSE_PTS];
+        if (!ident) {
+            const int4 p0 = *reinterpret_cast<const int4*>(a.cv.perm + base), p1 = *reinterpret_cast<const int4*>(a.cv.perm + base + 4);
+            o[0] = p0.x; o[1] = p0.y; o[2] = p0.z; o[3] = p0.w; o[4] = p1.x; o[5] = p1.y; o[6] = p1.z; o[7] = p1.w;
+        } else {
+#pragma unroll
+            for (int i = 0; i < TO_POSE_PTS; ++i) o[i] = (int)(base + i);
+        }
+        float w[TO_POSE_PTS];   // the occlusion mask (shared by the poses), 0 for pads
+#pragma unroll
+        for (int i = 0; i < TO_POSE_PTS; ++i) w[i] = base + i < n ? 1.0f : 0.f;
+        if (a.mask != nullptr) {
+            if (whole && ((((uintptr_t)a.mask) & 15) == 0)) {
+                const float4 m0 = *reinterpret_cast<const float4*>(a.mask + base), m1 = *reinterpret_cast<const float4*>(a.mask + base + 4);
+                w[0] = m0.x; w[1] = m0.y; w[2] = m0.z; w[3] = m0.w; w[4] = m1.x; w[5] = m1.y; w[6] = m1.z; w[7] = m1.w;
+            } else {
+#pragma unroll
+                for (int i = 0; i < TO_POSE_PTS; ++i)
+                    if (base + i < n) w[i] = a.mask[o[i]];
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < TO_POSE_TILE; ++p) {
+            if (p >= np) continue;   // uniform: the last tile's missing poses
+            float ob[TO_POSE_PTS];
+#pragma unroll
+            for (int i = 0; i < TO_POSE_PTS; i += 2) {
+                VisGrad2 vg;
+                const f2 pv = vis_p_pk_grad(r[p], k, f2{x[i], x[i + 1]}, f2{y[i], y[i + 1]}, f2{z[i], z[i + 1]}, vg);
+                const f2 obs2 = f2{w[i], w[i + 1]} * pv;
+                ob[i] = obs2.x; ob[i + 1] = obs2.y;
+                asum[p] += obs2.x;
+                asum[p] += obs2.y;
+                if (GRAD) {
+                    f2 g[3];
+                    dvis_dy_pk(r[p], k, pv, vg, g);
+                    const f2 wg = f2{w[i], w[i + 1]};
+                    const f2 w0 = wg * g[0], w1 = wg * g[1], w2 = wg * g[2];
+                    f2* ac = acc[p];
+                    ac[0] = ac[0] + w0; ac[1] = ac[1] + w1; ac[2] = ac[2] + w2;
+                    ac[3] = pk_fma(vg.y0, w0, ac[3]); ac[4] = pk_fma(vg.y0, w1, ac[4]); ac[5] = pk_fma(vg.y0, w2, ac[5]);
+                    ac[6] = pk_fma(vg.y1, w0, ac[6]); ac[7] = pk_fma(vg.y1, w1, ac[7]); ac[8] = pk_fma(vg.y1, w2, ac[8]);
+                    ac[9] = pk_fma(vg.y2, w0, ac[9]); ac[10] = pk_fma(vg.y2, w1, ac[10]); ac[11] = pk_fma(vg.y2, w2, ac[11]);
+                }
+            }
+            if (a.obs != nullptr) {
+                float* orow = a.obs + (int64_t)(b0 + p) * n;
+                if (whole && ((((uintptr_t)orow) & 15) == 0)) {
+                    __builtin_nontemporal_store(f4v{ob[0], ob[1], ob[2], ob[3]}, reinterpret_cast<f4v*>(orow + base));
+                    __builtin_nontemporal_store(f4v{ob[4], ob[5], ob[6], ob[7]}, reinterpret_cast<f4v*>(orow + base + 4));
+                } else {
+#pragma unroll
+                    for (int i = 0; i < TO_POSE_PTS; ++i)
+                        if (base + i < n) orow[o[i]] = ob[i];
+                }
+            }
+        }
+    }
+    // per pose and wave one DPP tree per sum (valid in lane 63), then the block's four waves in order, in f64 (k_pose_stream's)
+#pragma unroll
+    for (int p = 0; p < TO_POSE_TILE; ++p) {
+        if (p >= np) continue;
+        float sums[TO_POSE_NSUM];
+        sums[0] = wave_sum63(asum[p]);
+        if (GRAD) {
+#pragma unroll
+            for (int j = 0; j < 12; ++j) sums[1 + j] = wave_sum63(acc[p][j].x + acc[p][j].y);
+        }
+        if (lane == 63) {
+#pragma unroll
+            for (int j = 0; j < (GRAD ? TO_POSE_NSUM : 1); ++j) swave[p][wave][j] = sums[j];
+        }
+    }
+    __syncthreads();
+    const int p = t >> 4, j = t & 15;
+    if (p < np && j < (GRAD ? TO_POSE_NSUM : 1)) {
+        double s = 0.0;
+#pragma unroll
+        for (int wv = 0; wv < TO_WAVES_PER_BLOCK; ++wv) s += (double)swave[p][wv][j];
+        a.part[((int64_t)(b0 + p) * gridDim.x + blockIdx.x) * 16 + j] = s;
+    }
+}
+static_assert(TO_POSE_TILE * 16 <= TO_BLOCK, "one thread per (pose, sum) writes the partial rows");
+
+// k_pose_finish for pose b = blockIdx.x of a batch: f's pointers are pose 0's; the per-pose rows follow (part: f.nparts rows of 16
+// per pose, trans / grads / moments 3 or 4 floats, scalars 4, gout 1, loss_log n_steps)
+__global__ void __launch_bounds__(1024) k_pose_finish_multi(PoseFinish f, int n_steps) {
+    const int64_t b = blockIdx.x;
+    PoseFinish g = f;
+    g.part = f.part + b * f.nparts * 16;
+    g.trans = f.trans + 3 * b;
+    g.quat = f.quat + 4 * b;
+    if (f.scalars_out) g.scalars_out = f.scalars_out + 4 * b;
+    if (f.gout) g.gout = f.gout + b;
+    if (f.trans_grad) g.trans_grad = f.trans_grad + 3 * b;
+    if (f.quat_grad) g.quat_grad = f.quat_grad + 4 * b;
+    if (f.adam) {
+        g.mt = f.mt + 3 * b; g.vt = f.vt + 3 * b;
+        g.mq = f.mq + 4 * b; g.vq = f.vq + 4 * b;
+        g.loss_log = f.loss_log + b * n_steps;
+    }
+    pose_finish_body(g);
 }
 
 __global__ void __launch_bounds__(TO_BLOCK)
@@ -497,6 +671,42 @@ inline int pose_launch(PoseCall& c) {
     TO_HIP_CHECK_LAUNCH();
     return TOHIP_OK;
 }
+
+// the multi-pose workspace: the (B, nb, 16) partial rows first, nb <= min(chunks, TO_POSE_MAXBLOCKS), then a single-pose
+// workspace's worth (n_poses = 1 never needs less than tohip_pose_workspace_bytes)
+inline size_t pose_multi_bytes(int64_t n, int64_t n_poses) {
+    int64_t rows = tohip_padded_points(n) / TO_POSE_CHUNK;
+    if (rows > TO_POSE_MAXBLOCKS) rows = TO_POSE_MAXBLOCKS;
+    return align_up((size_t)n_poses * (size_t)rows * 16 * sizeof(double), 256) + pose_plan().total;
+}
+
+// B poses per launch pair: the stream pass on the single-pose grid x tiles, then one finish block per pose
+template <bool GRAD>
+inline int pose_multi_launch(const PoseMultiArgs& a, PoseFinish f, int n_steps, hipStream_t st) {
+    const int nb = pose_stream_blocks<true, GRAD>(a.cv.npad);   // the single-pose pass's grid: the same chunks per block
+    const int tiles = (a.n_poses + TO_POSE_TILE - 1) / TO_POSE_TILE;
+    k_pose_stream_multi<GRAD><<<dim3(nb, tiles), TO_BLOCK, 0, st>>>(a);
+    TO_HIP_CHECK_LAUNCH();
+    f.nparts = nb;
+    f.grad = GRAD ? 1 : 0;
+    k_pose_finish_multi<<<a.n_poses, nb > 64 ? 1024 : TO_BLOCK, 0, st>>>(f, n_steps);   // k_pose_finish's block size rule
+    TO_HIP_CHECK_LAUNCH();
+    return TOHIP_OK;
+}
+
+inline int pose_multi_init(PoseMultiArgs& a, PoseFinish& f, const void* packed, int64_t n, const float* trans, const float* quat,
+                           int64_t n_poses, const tohip_camera* cam, const float* mask, float* obs, void* workspace, size_t workspace_bytes) {
+    if (!packed || !trans || !quat || !cam || !workspace || n <= 0 || n_poses <= 0 || n > INT32_MAX) return TOHIP_EINVAL;
+    if ((n_poses + TO_POSE_TILE - 1) / TO_POSE_TILE > 65535 || n_poses > INT32_MAX) return TOHIP_EINVAL;   // the grid's y extent
+    if (workspace_bytes < pose_multi_bytes(n, n_poses)) return TOHIP_ENOSPC;
+    a.cv = cloud_view(packed, n);
+    a.trans = trans; a.quat = quat; a.n_poses = (int)n_poses; a.k = make_evalk(cam); a.mask = mask; a.obs = obs;
+    a.part = (double*)workspace;
+    f.part = a.part; f.nparts = 0; f.trans = trans; f.quat = quat; f.k = a.k; f.eps = cam->eps;
+    f.scalars_out = nullptr; f.scalars_in = nullptr; f.gout = nullptr; f.coef_mode = 2; f.grad = 0; f.trans_grad = nullptr; f.quat_grad = nullptr;
+    f.adam = 0; f.mt = f.vt = f.mq = f.vq = nullptr; f.lr_pose = f.lr_quat = f.beta1 = f.beta2 = f.adam_eps = 0.f; f.step = 0; f.loss_log = nullptr;
+    return TOHIP_OK;
+}
 }  // namespace
 
 extern "C" size_t tohip_pose_workspace_bytes(int64_t n_points) {
@@ -560,6 +770,42 @@ extern "C" int tohip_pose_opt_step(const void* packed, int64_t n, float* trans, 
     c.f.adam = 1; c.f.mt = exp_avg_t; c.f.vt = exp_avg_sq_t; c.f.mq = exp_avg_q; c.f.vq = exp_avg_sq_q;
     c.f.lr_pose = lr_pose; c.f.lr_quat = lr_quat; c.f.beta1 = beta1; c.f.beta2 = beta2; c.f.adam_eps = adam_eps; c.f.step = step; c.f.loss_log = loss_log;
     return pose_launch<true, true>(c);
+}
+
+extern "C" size_t tohip_pose_workspace_bytes_multi(int64_t n_points, int64_t n_poses) {
+    if (n_points < 0 || n_poses <= 0) return 0;
+    return pose_multi_bytes(n_points, n_poses);
+}
+
+extern "C" int tohip_pose_forward_backward_multi(const void* packed, int64_t n, const float* trans, const float* quat, int64_t n_poses,
+                                                 const tohip_camera* cam, const float* mask, float* obs, float* scalars, const float* gout,
+                                                 float* trans_grad, float* quat_grad, void* workspace, size_t workspace_bytes, void* stream_) {
+    if (!scalars || (trans_grad == nullptr) != (quat_grad == nullptr)) return TOHIP_EINVAL;
+    PoseMultiArgs a;
+    PoseFinish f;
+    const int rc = pose_multi_init(a, f, packed, n, trans, quat, n_poses, cam, mask, obs, workspace, workspace_bytes);
+    if (rc != TOHIP_OK) return rc;
+    f.scalars_out = scalars;
+    if (!trans_grad) return pose_multi_launch<false>(a, f, 0, (hipStream_t)stream_);   // scoring: no gradient sums
+    f.gout = gout; f.trans_grad = trans_grad; f.quat_grad = quat_grad;
+    return pose_multi_launch<true>(a, f, 0, (hipStream_t)stream_);
+}
+
+extern "C" int tohip_pose_opt_step_multi(const tohip_pose_opt* o, int32_t step, float* obs, void* stream_) {
+    if (!o || !o->scalars || !o->exp_avg_t || !o->exp_avg_sq_t || !o->exp_avg_q || !o->exp_avg_sq_q || !o->loss_log || step < 1 ||
+        step > o->n_steps)
+        return TOHIP_EINVAL;
+    PoseMultiArgs a;
+    PoseFinish f;
+    const int rc = pose_multi_init(a, f, o->packed, o->n_points, o->trans, o->quat, o->n_poses, &o->cam, o->occlusion_mask, obs,
+                                   o->workspace, o->workspace_bytes);
+    if (rc != TOHIP_OK) return rc;
+    f.scalars_out = o->scalars;
+    f.trans_grad = o->trans_grad; f.quat_grad = o->quat_grad;
+    f.adam = 1; f.mt = o->exp_avg_t; f.vt = o->exp_avg_sq_t; f.mq = o->exp_avg_q; f.vq = o->exp_avg_sq_q;
+    f.lr_pose = o->lr_pose; f.lr_quat = o->lr_quat; f.beta1 = o->beta1; f.beta2 = o->beta2; f.adam_eps = o->adam_eps; f.step = step;
+    f.loss_log = o->loss_log;
+    return pose_multi_launch<true>(a, f, o->n_steps, (hipStream_t)stream_);
 }
 
 extern "C" int tohip_to_camera_frame(const float* xyz, int64_t n, const float* quat, const float* trans, int normalize,

@@ -604,16 +604,35 @@ class ModelPose(nn.Module):
                  intrins: torch.tensor,  # pinhole matrix K, shape (3, 3)
                  img_width, img_height,
                  min_dist=1.0, max_dist=5.0,
-                 device=torch.device('cuda:0'), *, fast_adam=False):
+                 device=torch.device('cuda:0'), *, cloud=None, fast_adam=False):
         super().__init__()
         assert trans0.size() == torch.Size([1, 3])
         assert q0.size() == torch.Size([1, 4])
         assert intrins.size() == torch.Size([3, 3])
 
         self.device = torch.device(device)
-        # the reference keeps the caller's dtype (model.py:80) and then fails in get_fov_mask's matmul
-        # for anything but float32; float32 is the contract here
-        self.points = torch.as_tensor(points, dtype=torch.float32).to(self.device)
+        # One packed cloud for several poses (many starts of one camera, optimizer.optimize_poses): `points` may be an
+        # ops.PackedCloud, or `cloud=` names one (or a ModelPose whose cloud to share).  The pose path keeps the caller's order, so
+        # only an unsorted cloud (sort=False) will do: another order would change the sums.
+        if isinstance(points, ops.PackedCloud):
+            cloud, points = points, None
+        if isinstance(cloud, ModelPose):
+            cloud = cloud._cloud
+        if cloud is not None:
+            if not isinstance(cloud, ops.PackedCloud) or cloud.sorted:
+                raise ValueError("cloud= must be an ops.PackedCloud in the caller's order (sort=False) or a ModelPose")
+            if cloud.device != (self.device if self.device.index is not None else torch.device(self.device.type, torch.cuda.current_device())):
+                raise ValueError(f"the packed cloud lives on {cloud.device}, the model on {self.device}")
+            if points is not None and not (torch.is_tensor(points) and points.data_ptr() == cloud.points.data_ptr() and
+                                           tuple(points.shape) == tuple(cloud.points.shape) and points.stride() == cloud.points.stride()):
+                pt = torch.as_tensor(points, dtype=torch.float32)
+                if tuple(pt.shape) != tuple(cloud.points.shape) or not torch.equal(pt.to(cloud.points.device), cloud.points):
+                    raise ValueError("cloud= does not hold these points")
+            self.points = cloud.points
+        else:
+            # the reference keeps the caller's dtype (model.py:80) and then fails in get_fov_mask's matmul
+            # for anything but float32; float32 is the contract here
+            self.points = torch.as_tensor(points, dtype=torch.float32).to(self.device)
         self.rewards = None
         self.observations = None
         self.lo_sum = 0.0
@@ -629,7 +648,8 @@ class ModelPose(nn.Module):
         self.pc_clip_limits = [min_dist, max_dist]  # near / far range of the distance mask, metres
 
         self.to(self.device)
-        self._cloud = ops.PackedCloud(self.points, sort=False)   # nothing culls here: the caller's order, masks and observations in place
+        # nothing culls here: the caller's order, masks and observations in place
+        self._cloud = cloud if cloud is not None else ops.PackedCloud(self.points, sort=False)
         self._cam = ops.Camera(self.K, self.img_width, self.img_height, min_dist, max_dist, self.eps)
         self._ws = ops.PoseWorkspace(self._cloud)
         self._occlusion_mask, self._occlusion_key = None, None
@@ -641,17 +661,27 @@ class ModelPose(nn.Module):
         if fast_adam:          # fast_adam=True here, optimizer.accelerate_torch_adam(True) or accelerate_torch_adam(opt) (nothing is hooked otherwise)
             accelerate_torch_adam(True)
 
+    @classmethod
+    def sharing_cloud_of(cls, other, trans0, q0, **kw):
+        """A model of another start over `other`'s cloud: same packed cloud (not packed again), camera and device; keyword
+        arguments as the constructor's."""
+        kw.setdefault("device", other.device)
+        kw.setdefault("min_dist", other.pc_clip_limits[0])
+        kw.setdefault("max_dist", other.pc_clip_limits[1])
+        return cls(other._cloud, trans0, q0, other.K, other.img_width, other.img_height, **kw)
+
+    def _hpr_mask(self):
+        """HPR of the WORLD-frame cloud seen from the world origin (model.py:114): pose independent, so it is computed once per
+        cloud and cached; a replaced or edited cloud gets a new mask."""
+        key = (self.points.data_ptr(), self.points._version, tuple(self.points.shape))
+        if self._occlusion_mask is None or self._occlusion_key != key:
+            self._occlusion_mask = hidden_pts_removal(self.points.detach(), device=self.device)[1].contiguous()
+            self._occlusion_key = key
+        return self._occlusion_mask
+
     def forward(self, debug=False, hpr=False):
         t0 = time()
-        mask = None
-        if hpr:
-            # HPR of the WORLD-frame cloud seen from the world origin (model.py:114): pose independent,
-            # so it is computed once per cloud
-            key = (self.points.data_ptr(), self.points._version, tuple(self.points.shape))
-            if self._occlusion_mask is None or self._occlusion_key != key:   # a replaced or edited cloud gets a new mask
-                self._occlusion_mask = hidden_pts_removal(self.points.detach(), device=self.device)[1].contiguous()
-                self._occlusion_key = key
-            mask = self._occlusion_mask
+        mask = self._hpr_mask() if hpr else None
         fused = self.fused_loss and type(self).criterion is ModelPose.criterion
         if fused:
             loss, self.observations, scalars = _PoseLoss.apply(self.trans, self.quat, self, mask)

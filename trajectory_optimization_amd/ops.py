@@ -433,8 +433,15 @@ def traj_step_stats(cloud, ws):
 
 
 class PoseWorkspace:
-    def __init__(self, cloud):
-        self.bytes = _lib.lib().tohip_pose_workspace_bytes(cloud.n)
+    """Scratch of the ModelPose kernels.  The default is the single-pose calls' size; n_poses > 1, or multi=True, sizes it for the
+    multi-pose calls (pose_forward_backward_multi) over up to n_poses poses — which serves the single-pose calls too."""
+
+    def __init__(self, cloud, n_poses=1, multi=False):
+        L = _lib.lib()
+        if int(n_poses) < 1:
+            raise ValueError(f"n_poses must be at least 1, got {n_poses}")
+        self.n_poses, self.multi = int(n_poses), bool(multi) or int(n_poses) > 1
+        self.bytes = L.tohip_pose_workspace_bytes_multi(cloud.n, self.n_poses) if self.multi else L.tohip_pose_workspace_bytes(cloud.n)
         self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=cloud.device)
 
 
@@ -459,6 +466,34 @@ def pose_forward_backward(cloud, trans, quat, cam, ws, mask=None, gout=None):
     with torch.cuda.device(dev):
         check(_lib.lib().tohip_pose_forward_backward(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), cam.ref(), ptr(mask), ptr(obs), ptr(scalars),
                                                      ptr(gout), ptr(tg), ptr(qg), ptr(ws.buf), ws.bytes, stream_ptr()), "tohip_pose_forward_backward")
+    return obs, scalars, tg, qg
+
+
+def pose_forward_backward_multi(cloud, trans, quat, cam, ws, mask=None, observations=False, grad=True):
+    """B poses of one camera over one cloud in one pass (tohip_pose_forward_backward_multi): trans (B,3), quat (B,4) contiguous f32,
+    ws a PoseWorkspace(cloud, n_poses >= B).  Each pose's results are bitwise those of pose_forward_backward (grad) or pose_forward.
+    -> (observations (B,N) or None, scalars (B,4: sum, loss, -, -), trans_grad (B,3) or None, quat_grad (B,4) or None);
+    grad=False runs the forward-only pass (scoring candidate views)."""
+    dev = cloud.device
+    B = trans.shape[0] if trans.dim() == 2 else 0
+    if B == 0 or tuple(trans.shape) != (B, 3) or tuple(quat.shape) != (B, 4):
+        raise ValueError(f"trans / quat must be (B,3) / (B,4) with B > 0, got {tuple(trans.shape)} / {tuple(quat.shape)}")
+    for name, t in (("trans", trans), ("quat", quat), ("mask", mask)):   # the kernels read raw f32 rows on the cloud's device
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev):
+            raise ValueError(f"{name} must be a contiguous float32 tensor on {dev}")
+    if mask is not None and tuple(mask.shape) != (cloud.n,):
+        raise ValueError(f"mask must have {cloud.n} entries, got {tuple(mask.shape)}")
+    if not ws.multi or ws.n_poses < B:
+        raise ValueError(f"ws must be a PoseWorkspace(cloud, n_poses >= {B}) sized for the multi-pose calls (multi=True)")
+    f32 = dict(dtype=torch.float32, device=dev)
+    obs = torch.empty((B, cloud.n), **f32) if observations else None
+    scalars = torch.empty((B, 4), **f32)
+    tg = torch.empty((B, 3), **f32) if grad else None
+    qg = torch.empty((B, 4), **f32) if grad else None
+    with torch.cuda.device(dev):
+        check(_lib.lib().tohip_pose_forward_backward_multi(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), B, cam.ref(), ptr(mask), ptr(obs),
+                                                           ptr(scalars), None, ptr(tg), ptr(qg), ptr(ws.buf), ws.bytes, stream_ptr()),
+              "tohip_pose_forward_backward_multi")
     return obs, scalars, tg, qg
 
 

@@ -256,6 +256,72 @@ def optimize_pose(model, n_opt_steps=100, lr_pose=0.1, lr_quat=0.1, hpr=False, b
     return PoseOptResult(losses[:n_opt_steps].cpu().tolist())  # the run's only host synchronisation
 
 
+@torch.no_grad()
+def optimize_poses(models, n_opt_steps=100, lr_pose=0.1, lr_quat=0.1, hpr=False, betas=(0.9, 0.999), adam_eps=1e-8):
+    """`optimize_pose` for several poses of ONE camera over the SAME cloud at once (many starts; scoring candidate views): every
+    step is one library call and two launches for all of them (tohip_pose_opt_step_multi) — one pass over the cloud evaluates a
+    tile of poses on the points it holds, then one finish block per pose runs its loss, gradient and both Adam updates.  Each model
+    ends up bit for bit where its own `optimize_pose` run would have put it (trans, quat, losses, observations).  Models: ModelPose
+    on the same points with the same camera (K, image size, clip limits), eps and device.  -> [PoseOptResult].
+    Each model.observations is row b of one (B, N) tensor: any one of them keeps all B x N floats alive (clone a row to keep it
+    alone)."""
+    models = list(models)
+    if not models:
+        raise ValueError("optimize_poses: no models")
+    m0 = models[0]
+    for m in models[1:]:
+        if m.device != m0.device or float(m.eps) != float(m0.eps):
+            raise ValueError("optimize_poses: the models must live on one device and share eps")
+        if bytes(m._cam.c) != bytes(m0._cam.c):
+            raise ValueError("optimize_poses: the models must share the camera (K, image size, clip limits)")
+        # what the kernels read is the packed cloud: the same object, or one of equal size over equal rows (the shapes are compared
+        # first — a model on a slice of the same tensor shares its data pointer)
+        c, c0 = m._cloud, m0._cloud
+        if c is not c0 and (c.n != c0.n or tuple(c.points.shape) != tuple(c0.points.shape) or not torch.equal(c.points, c0.points)):
+            raise ValueError("optimize_poses: the models must be built on the same points")
+    if n_opt_steps <= 0:   # nothing to run: the models keep what they have
+        return []
+    if len(models) == 1:   # the single-pose pass carries no tile of accumulators: its own path
+        return [optimize_pose(m0, n_opt_steps, lr_pose, lr_quat, hpr, betas, adam_eps)]
+    L = _lib.lib()
+    dev, cloud, B = m0.device, m0._cloud, len(models)
+    f32 = dict(dtype=torch.float32, device=dev)
+    mask = m0._hpr_mask() if hpr else None   # pose independent: built once for the batch
+    trans = torch.cat([m.trans.data for m in models]).contiguous()
+    quat = torch.cat([m.quat.data for m in models]).contiguous()
+    obs, scalars = torch.empty((B, cloud.n), **f32), torch.zeros((B, 4), **f32)
+    tg, qg = torch.empty((B, 3), **f32), torch.empty((B, 4), **f32)
+    moments = [torch.zeros((B, 3), **f32), torch.zeros((B, 3), **f32), torch.zeros((B, 4), **f32), torch.zeros((B, 4), **f32)]
+    losses = torch.empty((B, n_opt_steps), **f32)
+    ws = ops.PoseWorkspace(cloud, B)
+    c = _lib.PoseOpt()
+    c.packed, c.n_points, c.n_poses, c.n_steps = cloud.blob.data_ptr(), cloud.n, B, n_opt_steps
+    c.cam = m0._cam.c
+    c.occlusion_mask = mask.data_ptr() if mask is not None else None
+    c.trans, c.quat = trans.data_ptr(), quat.data_ptr()
+    c.lr_pose, c.lr_quat, c.beta1, c.beta2, c.adam_eps = float(lr_pose), float(lr_quat), float(betas[0]), float(betas[1]), float(adam_eps)
+    c.exp_avg_t, c.exp_avg_sq_t, c.exp_avg_q, c.exp_avg_sq_q = (t.data_ptr() for t in moments)
+    c.scalars, c.trans_grad, c.quat_grad, c.loss_log = scalars.data_ptr(), tg.data_ptr(), qg.data_ptr(), losses.data_ptr()
+    c.workspace, c.workspace_bytes = ws.buf.data_ptr(), ws.bytes
+    ref, fn = ctypes.byref(c), L.tohip_pose_opt_step_multi
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    with torch.cuda.device(idx):
+        stream = torch._C._cuda_getCurrentRawStream(idx)
+        for i in range(n_opt_steps):
+            # the observations are what the last step leaves (optimize_pose writes them every step; the bits are the same)
+            rc = fn(ref, i + 1, obs.data_ptr() if i + 1 == n_opt_steps else None, stream)
+            if rc:
+                check(rc, "tohip_pose_opt_step_multi")
+        for b, m in enumerate(models):
+            m.trans.data.copy_(trans[b:b + 1])
+            m.quat.data.copy_(quat[b:b + 1])
+            torch.autograd.graph.increment_version(m.trans)
+            torch.autograd.graph.increment_version(m.quat)
+            m.observations = obs[b]
+    lt = losses.cpu()   # the run's only host synchronisation
+    return [PoseOptResult(lt[b].tolist()) for b in range(B)]
+
+
 def _adam_update(L, entries, arr):
     """One launch for all the listed (group, param, state, grad) entries (at most ADAM_MAX_GROUPS per launch)."""
     k = 0
