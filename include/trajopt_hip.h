@@ -37,11 +37,13 @@
 extern "C" {
 #endif
 
-/* 13: + tohip_pose_workspace_bytes_multi / tohip_pose_forward_backward_multi / tohip_pose_opt_step_multi (several poses of one
+/* 14: + tohip_pose_forward_bits / _backward_bits / _forward_backward_bits / _opt_step_bits / _forward_backward_multi_bits (per-pose
+ * occlusion bit rows); tohip_pose_opt gains occlusion_bits at its end.
+ * 13: + tohip_pose_workspace_bytes_multi / tohip_pose_forward_backward_multi / tohip_pose_opt_step_multi (several poses of one
  * camera over one cloud per pass).
  * 12 (r05): + tohip_render_points_blend / tohip_render_blend_workspace_bytes; + TOHIP_TRAJ_OPT_LAST_OUTPUTS; tohip_voxel_grid reports
  * PCL's "leaf size too small" case as *out_count = -1.  (11: r04) */
-#define TOHIP_ABI_VERSION 13
+#define TOHIP_ABI_VERSION 14
 
 #define TOHIP_OK 0
 #define TOHIP_EINVAL (-1)   /* bad size / null pointer */
@@ -387,6 +389,27 @@ int tohip_pose_opt_step(const void *packed, int64_t n_points, float *trans, floa
                         float beta1, float beta2, float adam_eps, int32_t step, float *loss_log, void *workspace,
                         size_t workspace_bytes, void *stream);
 
+/* The same four calls with an occlusion BIT ROW in place of the float mask: occlusion_bits (non-NULL, Npad/32 words) holds bit i = 1
+ * when the packed point i is NOT occluded from this pose — the layout of tohip_traj_forward's rows (a ModelPose cloud is packed with
+ * sort = 0, so packed order is the caller's order).  Each bit becomes the weight 1.0f or 0.0f and the arithmetic after it is the float
+ * mask's: the results are bitwise those of the float calls given the row unpacked to zeros and ones in the caller's order.  Pads
+ * carry no weight whatever their bits.  4 B per point less to read than a float mask. */
+int tohip_pose_forward_bits(const void *packed, int64_t n_points, const float *trans, const float *quat, const tohip_camera *cam_host,
+                            const uint32_t *occlusion_bits, float *observations, float *scalars, void *workspace, size_t workspace_bytes,
+                            void *stream);
+int tohip_pose_backward_bits(const void *packed, int64_t n_points, const float *trans, const float *quat, const tohip_camera *cam_host,
+                             const uint32_t *occlusion_bits, const float *grad_obs, const float *scalars, const float *gout,
+                             float *trans_grad, float *quat_grad, void *workspace, size_t workspace_bytes, void *stream);
+int tohip_pose_forward_backward_bits(const void *packed, int64_t n_points, const float *trans, const float *quat,
+                                     const tohip_camera *cam_host, const uint32_t *occlusion_bits, float *observations, float *scalars,
+                                     const float *gout, float *trans_grad, float *quat_grad, void *workspace, size_t workspace_bytes,
+                                     void *stream);
+int tohip_pose_opt_step_bits(const void *packed, int64_t n_points, float *trans, float *quat, const tohip_camera *cam_host,
+                             const uint32_t *occlusion_bits, float *observations, float *scalars, float *trans_grad, float *quat_grad,
+                             float *exp_avg_t, float *exp_avg_sq_t, float *exp_avg_q, float *exp_avg_sq_q, float lr_pose, float lr_quat,
+                             float beta1, float beta2, float adam_eps, int32_t step, float *loss_log, void *workspace,
+                             size_t workspace_bytes, void *stream);
+
 /* ---- several poses of one camera over one cloud (many starts, candidate views) ------------------
  * B = n_poses poses in rows of trans (B,3) / quat (B,4); every pass over the cloud evaluates a tile of them on the points it holds
  * in registers.  Each pose's sums are taken in the order of the single-pose pass on the same grid: scalars, gradients,
@@ -401,6 +424,12 @@ int tohip_pose_forward_backward_multi(const void *packed, int64_t n_points, cons
                                       const tohip_camera *cam_host, const float *occlusion_mask, float *observations, float *scalars,
                                       const float *gout, float *trans_grad, float *quat_grad, void *workspace,
                                       size_t workspace_bytes, void *stream);
+/* The same with one occlusion bit row PER POSE: occlusion_bits (B, Npad/32), row b for pose b (layout of tohip_pose_forward_bits);
+ * pose b's results are bitwise those of tohip_pose_forward_backward_bits with row b — and of the float call given row b unpacked. */
+int tohip_pose_forward_backward_multi_bits(const void *packed, int64_t n_points, const float *trans, const float *quat, int64_t n_poses,
+                                           const tohip_camera *cam_host, const uint32_t *occlusion_bits, float *observations,
+                                           float *scalars, const float *gout, float *trans_grad, float *quat_grad, void *workspace,
+                                           size_t workspace_bytes, void *stream);
 /* One step of B independent PoseOpt loops (tohip_pose_opt_step per pose): Adam with two groups per pose (trans @ lr_pose,
  * quat @ lr_quat), shared betas / eps, its own moments per pose.  Filled once, passed by pointer in HOST memory. */
 typedef struct tohip_pose_opt {
@@ -419,6 +448,9 @@ typedef struct tohip_pose_opt {
     float *loss_log;           /* (B, n_steps): loss_log[b n_steps + step - 1] = pose b's loss of this step (before the update) */
     void *workspace;           /* tohip_pose_workspace_bytes_multi(n_points, n_poses) */
     size_t workspace_bytes;
+    const uint32_t *occlusion_bits;   /* (B, Npad/32) or NULL: each pose's own occlusion bit row (tohip_pose_forward_backward_multi_bits);
+                                         giving occlusion_mask too is an error (TOHIP_EINVAL).  A refresh may replace the pointer between
+                                         steps. */
 } tohip_pose_opt;
 /* step = 1, 2, ... n_steps, in order.  observations (B,N) or NULL: pass it on the step that should leave them (the last).
  * Two launches; nothing synchronises. */

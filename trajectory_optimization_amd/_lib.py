@@ -54,7 +54,8 @@ class PoseOpt(ctypes.Structure):
     _fields_ = [("packed", c_vp), ("n_points", c_i64), ("n_poses", c_i32), ("n_steps", c_i32), ("cam", Camera), ("occlusion_mask", c_vp),
                 ("trans", c_vp), ("quat", c_vp), ("lr_pose", c_f), ("lr_quat", c_f), ("beta1", c_f), ("beta2", c_f), ("adam_eps", c_f),
                 ("exp_avg_t", c_vp), ("exp_avg_sq_t", c_vp), ("exp_avg_q", c_vp), ("exp_avg_sq_q", c_vp), ("scalars", c_vp),
-                ("trans_grad", c_vp), ("quat_grad", c_vp), ("loss_log", c_vp), ("workspace", c_vp), ("workspace_bytes", c_sz)]
+                ("trans_grad", c_vp), ("quat_grad", c_vp), ("loss_log", c_vp), ("workspace", c_vp), ("workspace_bytes", c_sz),
+                ("occlusion_bits", c_vp)]
 
 
 class AdamGroup(ctypes.Structure):
@@ -121,6 +122,15 @@ SIGNATURES = {
                                                     c_vp, c_sz, c_vp]),
     "tohip_pose_opt_step": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, ctypes.POINTER(Camera), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                             c_vp, c_f, c_f, c_f, c_f, c_f, c_i32, c_vp, c_vp, c_sz, c_vp]),
+    "tohip_pose_forward_bits": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, ctypes.POINTER(Camera), c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "tohip_pose_backward_bits": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, ctypes.POINTER(Camera), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
+                                                 c_vp]),
+    "tohip_pose_forward_backward_bits": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, ctypes.POINTER(Camera), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                         c_vp, c_sz, c_vp]),
+    "tohip_pose_opt_step_bits": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, ctypes.POINTER(Camera), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                 c_vp, c_vp, c_f, c_f, c_f, c_f, c_f, c_i32, c_vp, c_vp, c_sz, c_vp]),
+    "tohip_pose_forward_backward_multi_bits": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, ctypes.POINTER(Camera), c_vp, c_vp, c_vp, c_vp,
+                                                               c_vp, c_vp, c_vp, c_sz, c_vp]),
     "tohip_pose_workspace_bytes_multi": (c_sz, [c_i64, c_i64]),
     "tohip_pose_forward_backward_multi": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, ctypes.POINTER(Camera), c_vp, c_vp, c_vp, c_vp,
                                                           c_vp, c_vp, c_vp, c_sz, c_vp]),
@@ -231,7 +241,7 @@ def lib():
     return _lib
 
 
-ABI_VERSION = 13  # TOHIP_ABI_VERSION of include/trajopt_hip.h (tests/test_host_cpu.py checks the two agree)
+ABI_VERSION = 14  # TOHIP_ABI_VERSION of include/trajopt_hip.h (tests/test_host_cpu.py checks the two agree)
 ENOSPC = -2  # TOHIP_ENOSPC
 ENAN = -4    # TOHIP_ENAN
 

@@ -62,7 +62,10 @@ struct PoseArgs {
     const float* trans;
     const float* quat;
     EvalK k;
-    const float* mask;       // caller's order, may be NULL
+    union {                      // (one slot: the float kernels' arguments stay what they were)
+        const float* mask;       // caller's order, may be NULL
+        const uint32_t* bits;    // OCC: the occlusion bit row (Npad/32 words, bit i = packed point i)
+    };
     const float* grad_obs;   // caller's order, may be NULL: dL/d observations (general upstream); NULL: unit weights
     float* obs;              // caller's order (FWD)
     double* part;            // gridDim.x x 16 doubles
@@ -74,7 +77,16 @@ __device__ __forceinline__ void pose_record(const PoseArgs& a, WayRec* srec, Way
     __syncthreads();
 }
 
-template <bool FWD, bool GRAD>
+// the weights of a lane's eight points from an occlusion bit row: they are one aligned byte of a word (base is a multiple of 8);
+// w = bit ? 1 : 0, pads 0 — the values a float mask of zeros and ones gives, so everything after is the float path's arithmetic
+__device__ __forceinline__ void occ_weights(uint32_t word, int64_t base, int64_t n, float (&w)[TO_POSE_PTS]) {
+    const uint32_t byte = word >> (uint32_t)(base & 31);
+#pragma unroll
+    for (int i = 0; i < TO_POSE_PTS; ++i) w[i] = (base + i < n && ((byte >> i) & 1u)) ? 1.0f : 0.f;
+}
+
+// OCC: the mask is the bit row a.bits (packed order) instead of a.mask
+template <bool FWD, bool GRAD, bool OCC>
 __global__ void __launch_bounds__(TO_BLOCK) k_pose_stream(PoseArgs a) {
     __shared__ WayRec srec;
     __shared__ WayCold scold;
@@ -119,7 +131,9 @@ __global__ void __launch_bounds__(TO_BLOCK) k_pose_stream(PoseArgs a) {
         float w[TO_POSE_PTS];   // what multiplies p in the observation (the occlusion mask), 0 for pads
 #pragma unroll
         for (int i = 0; i < TO_POSE_PTS; ++i) w[i] = base + i < n ? 1.0f : 0.f;
-        if (a.mask != nullptr) {
+        if (OCC) {
+            occ_weights(a.bits[base >> 5], base, n, w);
+        } else if (a.mask != nullptr) {
             if (whole && ((((uintptr_t)a.mask) & 15) == 0)) {
                 const float4 m0 = *reinterpret_cast<const float4*>(a.mask + base), m1 = *reinterpret_cast<const float4*>(a.mask + base + 4);
                 w[0] = m0.x; w[1] = m0.y; w[2] = m0.z; w[3] = m0.w; w[4] = m1.x; w[5] = m1.y; w[6] = m1.z; w[7] = m1.w;
@@ -287,12 +301,16 @@ struct PoseMultiArgs {
     const float* quat;    // (B,4)
     int n_poses;
     EvalK k;
-    const float* mask;    // caller's order, may be NULL: shared by every pose
+    union {
+        const float* mask;    // caller's order, may be NULL: shared by every pose
+        const uint32_t* bits; // OCC: (B, Npad/32) occlusion bit rows, one per pose (packed order)
+    };
     float* obs;           // (B,N) caller's order, may be NULL: nothing written
     double* part;         // (B, nb, 16): pose b's rows are part[(b nb + block) 16 + j]
 };
 
-template <bool GRAD>
+// OCC: pose b's mask is its own bit row a.bits + b Npad/32 (the tile's words are read once per chunk, next to the points)
+template <bool GRAD, bool OCC>
 __global__ void __launch_bounds__(TO_BLOCK) k_pose_stream_multi(PoseMultiArgs a) {
     __shared__ WayRec srec[TO_POSE_TILE];
     __shared__ WayCold scold[TO_POSE_TILE];
@@ -345,7 +363,11 @@ __global__ void __launch_bounds__(TO_BLOCK) k_pose_stream_multi(PoseMultiArgs a)
         float w[TO_POSE_PTS];   // the occlusion mask (shared by the poses), 0 for pads
 #pragma unroll
         for (int i = 0; i < TO_POSE_PTS; ++i) w[i] = base + i < n ? 1.0f : 0.f;
-        if (a.mask != nullptr) {
+        uint32_t occw[TO_POSE_TILE];   // OCC: each pose's word of this lane's points
+        if (OCC) {
+#pragma unroll
+            for (int p = 0; p < TO_POSE_TILE; ++p) occw[p] = p < np ? a.bits[(int64_t)(b0 + p) * (npad >> 5) + (base >> 5)] : 0u;
+        } else if (a.mask != nullptr) {
             if (whole && ((((uintptr_t)a.mask) & 15) == 0)) {
                 const float4 m0 = *reinterpret_cast<const float4*>(a.mask + base), m1 = *reinterpret_cast<const float4*>(a.mask + base + 4);
                 w[0] = m0.x; w[1] = m0.y; w[2] = m0.z; w[3] = m0.w; w[4] = m1.x; w[5] = m1.y; w[6] = m1.z; w[7] = m1.w;
@@ -358,6 +380,7 @@ __global__ void __launch_bounds__(TO_BLOCK) k_pose_stream_multi(PoseMultiArgs a)
 #pragma unroll
         for (int p = 0; p < TO_POSE_TILE; ++p) {
             if (p >= np) continue;   // uniform: the last tile's missing poses
+            if (OCC) occ_weights(occw[p], base, n, w);
             float ob[TO_POSE_PTS];
 #pragma unroll
             for (int i = 0; i < TO_POSE_PTS; i += 2) {
@@ -625,12 +648,12 @@ inline int pose_blocks(int64_t n) {
 // blocks of the streaming pass: one per 2048-point chunk while they are all resident at once (occupancy x CUs), else that many
 // persistent ones striding over the chunks
 template <bool FWD, bool GRAD>
-inline int pose_stream_blocks(int64_t npad) {
+inline int pose_stream_blocks(int64_t npad) {   // (the OCC variants run on the same grid: the same chunks per block, the same sums)
     static const int resident = [] {
         int dev = 0, cus = 256, per = 4;
         hipDeviceProp_t prop;
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_pose_stream<FWD, GRAD>, TO_BLOCK, 0) != hipSuccess || per <= 0) per = 2;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_pose_stream<FWD, GRAD, false>, TO_BLOCK, 0) != hipSuccess || per <= 0) per = 2;
         if (per > 2) per = 2;   // two blocks to a CU keep the chip's HBM pipes full with the next chunk's loads in flight (12 MB), and
                                 // the finish has a quarter of the partials to add
         const int r = per * cus;
@@ -642,17 +665,21 @@ inline int pose_stream_blocks(int64_t npad) {
 
 struct PoseCall {
     hipStream_t st;
+    bool occ;   // a.bits holds an occlusion bit row (else a.mask a float mask or NULL)
     PoseArgs a;
     PoseFinish f;
 };
 inline int pose_call_init(PoseCall& c, const void* packed, int64_t n, const float* trans, const float* quat, const tohip_camera* cam,
-                          const float* mask, void* workspace, size_t workspace_bytes, void* stream_) {
-    if (!packed || !trans || !quat || !cam || !workspace || n <= 0) return TOHIP_EINVAL;
+                          const float* mask, const uint32_t* bits, void* workspace, size_t workspace_bytes, void* stream_) {
+    if (!packed || !trans || !quat || !cam || !workspace || n <= 0 || (mask && bits)) return TOHIP_EINVAL;
     const PosePlan pl = pose_plan();
     if (workspace_bytes < pl.total) return TOHIP_ENOSPC;
     c.st = (hipStream_t)stream_;
     c.a.cv = cloud_view(packed, n);
-    c.a.trans = trans; c.a.quat = quat; c.a.k = make_evalk(cam); c.a.mask = mask; c.a.grad_obs = nullptr; c.a.obs = nullptr;
+    c.a.trans = trans; c.a.quat = quat; c.a.k = make_evalk(cam); c.occ = bits != nullptr;
+    if (c.occ) c.a.bits = bits;
+    else c.a.mask = mask;
+    c.a.grad_obs = nullptr; c.a.obs = nullptr;
     c.a.part = (double*)((char*)workspace + pl.off_part);
     PoseFinish& f = c.f;
     f.part = c.a.part; f.nparts = 0; f.trans = trans; f.quat = quat; f.k = c.a.k; f.eps = cam->eps;
@@ -663,7 +690,8 @@ inline int pose_call_init(PoseCall& c, const void* packed, int64_t n, const floa
 template <bool FWD, bool GRAD>
 inline int pose_launch(PoseCall& c) {
     const int nb = pose_stream_blocks<FWD, GRAD>(c.a.cv.npad);
-    k_pose_stream<FWD, GRAD><<<nb, TO_BLOCK, 0, c.st>>>(c.a);
+    if (c.occ) k_pose_stream<FWD, GRAD, true><<<nb, TO_BLOCK, 0, c.st>>>(c.a);
+    else k_pose_stream<FWD, GRAD, false><<<nb, TO_BLOCK, 0, c.st>>>(c.a);
     TO_HIP_CHECK_LAUNCH();
     c.f.nparts = nb;
     c.f.grad = GRAD ? 1 : 0;
@@ -682,10 +710,11 @@ inline size_t pose_multi_bytes(int64_t n, int64_t n_poses) {
 
 // B poses per launch pair: the stream pass on the single-pose grid x tiles, then one finish block per pose
 template <bool GRAD>
-inline int pose_multi_launch(const PoseMultiArgs& a, PoseFinish f, int n_steps, hipStream_t st) {
+inline int pose_multi_launch(const PoseMultiArgs& a, bool occ, PoseFinish f, int n_steps, hipStream_t st) {
     const int nb = pose_stream_blocks<true, GRAD>(a.cv.npad);   // the single-pose pass's grid: the same chunks per block
     const int tiles = (a.n_poses + TO_POSE_TILE - 1) / TO_POSE_TILE;
-    k_pose_stream_multi<GRAD><<<dim3(nb, tiles), TO_BLOCK, 0, st>>>(a);
+    if (occ) k_pose_stream_multi<GRAD, true><<<dim3(nb, tiles), TO_BLOCK, 0, st>>>(a);
+    else k_pose_stream_multi<GRAD, false><<<dim3(nb, tiles), TO_BLOCK, 0, st>>>(a);
     TO_HIP_CHECK_LAUNCH();
     f.nparts = nb;
     f.grad = GRAD ? 1 : 0;
@@ -695,12 +724,15 @@ inline int pose_multi_launch(const PoseMultiArgs& a, PoseFinish f, int n_steps, 
 }
 
 inline int pose_multi_init(PoseMultiArgs& a, PoseFinish& f, const void* packed, int64_t n, const float* trans, const float* quat,
-                           int64_t n_poses, const tohip_camera* cam, const float* mask, float* obs, void* workspace, size_t workspace_bytes) {
-    if (!packed || !trans || !quat || !cam || !workspace || n <= 0 || n_poses <= 0 || n > INT32_MAX) return TOHIP_EINVAL;
+                           int64_t n_poses, const tohip_camera* cam, const float* mask, const uint32_t* bits, float* obs, void* workspace,
+                           size_t workspace_bytes) {
+    if (!packed || !trans || !quat || !cam || !workspace || n <= 0 || n_poses <= 0 || n > INT32_MAX || (mask && bits)) return TOHIP_EINVAL;
     if ((n_poses + TO_POSE_TILE - 1) / TO_POSE_TILE > 65535 || n_poses > INT32_MAX) return TOHIP_EINVAL;   // the grid's y extent
     if (workspace_bytes < pose_multi_bytes(n, n_poses)) return TOHIP_ENOSPC;
     a.cv = cloud_view(packed, n);
-    a.trans = trans; a.quat = quat; a.n_poses = (int)n_poses; a.k = make_evalk(cam); a.mask = mask; a.obs = obs;
+    a.trans = trans; a.quat = quat; a.n_poses = (int)n_poses; a.k = make_evalk(cam); a.obs = obs;
+    if (bits) a.bits = bits;
+    else a.mask = mask;
     a.part = (double*)workspace;
     f.part = a.part; f.nparts = 0; f.trans = trans; f.quat = quat; f.k = a.k; f.eps = cam->eps;
     f.scalars_out = nullptr; f.scalars_in = nullptr; f.gout = nullptr; f.coef_mode = 2; f.grad = 0; f.trans_grad = nullptr; f.quat_grad = nullptr;
@@ -714,25 +746,25 @@ extern "C" size_t tohip_pose_workspace_bytes(int64_t n_points) {
     return pose_plan().total;
 }
 
-extern "C" int tohip_pose_forward(const void* packed, int64_t n, const float* trans, const float* quat,
-                                  const tohip_camera* cam, const float* mask, float* obs, float* scalars,
-                                  void* workspace, size_t workspace_bytes, void* stream_) {
+namespace {
+// the bodies of the exported calls, with the mask given as floats (caller's order) or as an occlusion bit row (packed order)
+int pose_forward_impl(const void* packed, int64_t n, const float* trans, const float* quat, const tohip_camera* cam, const float* mask,
+                      const uint32_t* bits, float* obs, float* scalars, void* workspace, size_t workspace_bytes, void* stream_) {
     if (!obs || !scalars) return TOHIP_EINVAL;
     PoseCall c;
-    const int rc = pose_call_init(c, packed, n, trans, quat, cam, mask, workspace, workspace_bytes, stream_);
+    const int rc = pose_call_init(c, packed, n, trans, quat, cam, mask, bits, workspace, workspace_bytes, stream_);
     if (rc != TOHIP_OK) return rc;
     c.a.obs = obs;
     c.f.scalars_out = scalars;
     return pose_launch<true, false>(c);
 }
 
-extern "C" int tohip_pose_backward(const void* packed, int64_t n, const float* trans, const float* quat,
-                                   const tohip_camera* cam, const float* mask, const float* grad_obs,
-                                   const float* scalars, const float* gout, float* trans_grad, float* quat_grad,
-                                   void* workspace, size_t workspace_bytes, void* stream_) {
+int pose_backward_impl(const void* packed, int64_t n, const float* trans, const float* quat, const tohip_camera* cam, const float* mask,
+                       const uint32_t* bits, const float* grad_obs, const float* scalars, const float* gout, float* trans_grad,
+                       float* quat_grad, void* workspace, size_t workspace_bytes, void* stream_) {
     if (!trans_grad || !quat_grad || (!grad_obs && (!scalars || !gout))) return TOHIP_EINVAL;
     PoseCall c;
-    const int rc = pose_call_init(c, packed, n, trans, quat, cam, mask, workspace, workspace_bytes, stream_);
+    const int rc = pose_call_init(c, packed, n, trans, quat, cam, mask, bits, workspace, workspace_bytes, stream_);
     if (rc != TOHIP_OK) return rc;
     c.a.grad_obs = grad_obs;
     c.f.coef_mode = grad_obs ? 0 : 1;
@@ -741,12 +773,12 @@ extern "C" int tohip_pose_backward(const void* packed, int64_t n, const float* t
     return pose_launch<false, true>(c);
 }
 
-extern "C" int tohip_pose_forward_backward(const void* packed, int64_t n, const float* trans, const float* quat,
-                                           const tohip_camera* cam, const float* mask, float* obs, float* scalars, const float* gout,
-                                           float* trans_grad, float* quat_grad, void* workspace, size_t workspace_bytes, void* stream_) {
+int pose_forward_backward_impl(const void* packed, int64_t n, const float* trans, const float* quat, const tohip_camera* cam,
+                               const float* mask, const uint32_t* bits, float* obs, float* scalars, const float* gout, float* trans_grad,
+                               float* quat_grad, void* workspace, size_t workspace_bytes, void* stream_) {
     if (!obs || !scalars || !trans_grad || !quat_grad) return TOHIP_EINVAL;
     PoseCall c;
-    const int rc = pose_call_init(c, packed, n, trans, quat, cam, mask, workspace, workspace_bytes, stream_);
+    const int rc = pose_call_init(c, packed, n, trans, quat, cam, mask, bits, workspace, workspace_bytes, stream_);
     if (rc != TOHIP_OK) return rc;
     c.a.obs = obs;
     c.f.scalars_out = scalars;
@@ -755,13 +787,13 @@ extern "C" int tohip_pose_forward_backward(const void* packed, int64_t n, const 
     return pose_launch<true, true>(c);
 }
 
-extern "C" int tohip_pose_opt_step(const void* packed, int64_t n, float* trans, float* quat, const tohip_camera* cam, const float* mask,
-                                   float* obs, float* scalars, float* trans_grad, float* quat_grad, float* exp_avg_t, float* exp_avg_sq_t,
-                                   float* exp_avg_q, float* exp_avg_sq_q, float lr_pose, float lr_quat, float beta1, float beta2,
-                                   float adam_eps, int32_t step, float* loss_log, void* workspace, size_t workspace_bytes, void* stream_) {
+int pose_opt_step_impl(const void* packed, int64_t n, float* trans, float* quat, const tohip_camera* cam, const float* mask,
+                       const uint32_t* bits, float* obs, float* scalars, float* trans_grad, float* quat_grad, float* exp_avg_t,
+                       float* exp_avg_sq_t, float* exp_avg_q, float* exp_avg_sq_q, float lr_pose, float lr_quat, float beta1, float beta2,
+                       float adam_eps, int32_t step, float* loss_log, void* workspace, size_t workspace_bytes, void* stream_) {
     if (!obs || !scalars || !exp_avg_t || !exp_avg_sq_t || !exp_avg_q || !exp_avg_sq_q || !loss_log || step < 1) return TOHIP_EINVAL;
     PoseCall c;
-    const int rc = pose_call_init(c, packed, n, trans, quat, cam, mask, workspace, workspace_bytes, stream_);
+    const int rc = pose_call_init(c, packed, n, trans, quat, cam, mask, bits, workspace, workspace_bytes, stream_);
     if (rc != TOHIP_OK) return rc;
     c.a.obs = obs;
     c.f.scalars_out = scalars;
@@ -772,6 +804,88 @@ extern "C" int tohip_pose_opt_step(const void* packed, int64_t n, float* trans, 
     return pose_launch<true, true>(c);
 }
 
+int pose_forward_backward_multi_impl(const void* packed, int64_t n, const float* trans, const float* quat, int64_t n_poses,
+                                     const tohip_camera* cam, const float* mask, const uint32_t* bits, float* obs, float* scalars,
+                                     const float* gout, float* trans_grad, float* quat_grad, void* workspace, size_t workspace_bytes,
+                                     void* stream_) {
+    if (!scalars || (trans_grad == nullptr) != (quat_grad == nullptr)) return TOHIP_EINVAL;
+    PoseMultiArgs a;
+    PoseFinish f;
+    const int rc = pose_multi_init(a, f, packed, n, trans, quat, n_poses, cam, mask, bits, obs, workspace, workspace_bytes);
+    if (rc != TOHIP_OK) return rc;
+    f.scalars_out = scalars;
+    if (!trans_grad) return pose_multi_launch<false>(a, bits != nullptr, f, 0, (hipStream_t)stream_);   // scoring: no gradient sums
+    f.gout = gout; f.trans_grad = trans_grad; f.quat_grad = quat_grad;
+    return pose_multi_launch<true>(a, bits != nullptr, f, 0, (hipStream_t)stream_);
+}
+}  // namespace
+
+extern "C" int tohip_pose_forward(const void* packed, int64_t n, const float* trans, const float* quat,
+                                  const tohip_camera* cam, const float* mask, float* obs, float* scalars,
+                                  void* workspace, size_t workspace_bytes, void* stream_) {
+    return pose_forward_impl(packed, n, trans, quat, cam, mask, nullptr, obs, scalars, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int tohip_pose_forward_bits(const void* packed, int64_t n, const float* trans, const float* quat,
+                                       const tohip_camera* cam, const uint32_t* occlusion_bits, float* obs, float* scalars,
+                                       void* workspace, size_t workspace_bytes, void* stream_) {
+    if (!occlusion_bits) return TOHIP_EINVAL;
+    return pose_forward_impl(packed, n, trans, quat, cam, nullptr, occlusion_bits, obs, scalars, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int tohip_pose_backward(const void* packed, int64_t n, const float* trans, const float* quat,
+                                   const tohip_camera* cam, const float* mask, const float* grad_obs,
+                                   const float* scalars, const float* gout, float* trans_grad, float* quat_grad,
+                                   void* workspace, size_t workspace_bytes, void* stream_) {
+    return pose_backward_impl(packed, n, trans, quat, cam, mask, nullptr, grad_obs, scalars, gout, trans_grad, quat_grad, workspace,
+                              workspace_bytes, stream_);
+}
+
+extern "C" int tohip_pose_backward_bits(const void* packed, int64_t n, const float* trans, const float* quat,
+                                        const tohip_camera* cam, const uint32_t* occlusion_bits, const float* grad_obs,
+                                        const float* scalars, const float* gout, float* trans_grad, float* quat_grad,
+                                        void* workspace, size_t workspace_bytes, void* stream_) {
+    if (!occlusion_bits) return TOHIP_EINVAL;
+    return pose_backward_impl(packed, n, trans, quat, cam, nullptr, occlusion_bits, grad_obs, scalars, gout, trans_grad, quat_grad,
+                              workspace, workspace_bytes, stream_);
+}
+
+extern "C" int tohip_pose_forward_backward(const void* packed, int64_t n, const float* trans, const float* quat,
+                                           const tohip_camera* cam, const float* mask, float* obs, float* scalars, const float* gout,
+                                           float* trans_grad, float* quat_grad, void* workspace, size_t workspace_bytes, void* stream_) {
+    return pose_forward_backward_impl(packed, n, trans, quat, cam, mask, nullptr, obs, scalars, gout, trans_grad, quat_grad, workspace,
+                                      workspace_bytes, stream_);
+}
+
+extern "C" int tohip_pose_forward_backward_bits(const void* packed, int64_t n, const float* trans, const float* quat,
+                                                const tohip_camera* cam, const uint32_t* occlusion_bits, float* obs, float* scalars,
+                                                const float* gout, float* trans_grad, float* quat_grad, void* workspace,
+                                                size_t workspace_bytes, void* stream_) {
+    if (!occlusion_bits) return TOHIP_EINVAL;
+    return pose_forward_backward_impl(packed, n, trans, quat, cam, nullptr, occlusion_bits, obs, scalars, gout, trans_grad, quat_grad,
+                                      workspace, workspace_bytes, stream_);
+}
+
+extern "C" int tohip_pose_opt_step(const void* packed, int64_t n, float* trans, float* quat, const tohip_camera* cam, const float* mask,
+                                   float* obs, float* scalars, float* trans_grad, float* quat_grad, float* exp_avg_t, float* exp_avg_sq_t,
+                                   float* exp_avg_q, float* exp_avg_sq_q, float lr_pose, float lr_quat, float beta1, float beta2,
+                                   float adam_eps, int32_t step, float* loss_log, void* workspace, size_t workspace_bytes, void* stream_) {
+    return pose_opt_step_impl(packed, n, trans, quat, cam, mask, nullptr, obs, scalars, trans_grad, quat_grad, exp_avg_t, exp_avg_sq_t,
+                              exp_avg_q, exp_avg_sq_q, lr_pose, lr_quat, beta1, beta2, adam_eps, step, loss_log, workspace,
+                              workspace_bytes, stream_);
+}
+
+extern "C" int tohip_pose_opt_step_bits(const void* packed, int64_t n, float* trans, float* quat, const tohip_camera* cam,
+                                        const uint32_t* occlusion_bits, float* obs, float* scalars, float* trans_grad, float* quat_grad,
+                                        float* exp_avg_t, float* exp_avg_sq_t, float* exp_avg_q, float* exp_avg_sq_q, float lr_pose,
+                                        float lr_quat, float beta1, float beta2, float adam_eps, int32_t step, float* loss_log,
+                                        void* workspace, size_t workspace_bytes, void* stream_) {
+    if (!occlusion_bits) return TOHIP_EINVAL;
+    return pose_opt_step_impl(packed, n, trans, quat, cam, nullptr, occlusion_bits, obs, scalars, trans_grad, quat_grad, exp_avg_t,
+                              exp_avg_sq_t, exp_avg_q, exp_avg_sq_q, lr_pose, lr_quat, beta1, beta2, adam_eps, step, loss_log, workspace,
+                              workspace_bytes, stream_);
+}
+
 extern "C" size_t tohip_pose_workspace_bytes_multi(int64_t n_points, int64_t n_poses) {
     if (n_points < 0 || n_poses <= 0) return 0;
     return pose_multi_bytes(n_points, n_poses);
@@ -780,32 +894,34 @@ extern "C" size_t tohip_pose_workspace_bytes_multi(int64_t n_points, int64_t n_p
 extern "C" int tohip_pose_forward_backward_multi(const void* packed, int64_t n, const float* trans, const float* quat, int64_t n_poses,
                                                  const tohip_camera* cam, const float* mask, float* obs, float* scalars, const float* gout,
                                                  float* trans_grad, float* quat_grad, void* workspace, size_t workspace_bytes, void* stream_) {
-    if (!scalars || (trans_grad == nullptr) != (quat_grad == nullptr)) return TOHIP_EINVAL;
-    PoseMultiArgs a;
-    PoseFinish f;
-    const int rc = pose_multi_init(a, f, packed, n, trans, quat, n_poses, cam, mask, obs, workspace, workspace_bytes);
-    if (rc != TOHIP_OK) return rc;
-    f.scalars_out = scalars;
-    if (!trans_grad) return pose_multi_launch<false>(a, f, 0, (hipStream_t)stream_);   // scoring: no gradient sums
-    f.gout = gout; f.trans_grad = trans_grad; f.quat_grad = quat_grad;
-    return pose_multi_launch<true>(a, f, 0, (hipStream_t)stream_);
+    return pose_forward_backward_multi_impl(packed, n, trans, quat, n_poses, cam, mask, nullptr, obs, scalars, gout, trans_grad, quat_grad,
+                                            workspace, workspace_bytes, stream_);
+}
+
+extern "C" int tohip_pose_forward_backward_multi_bits(const void* packed, int64_t n, const float* trans, const float* quat,
+                                                      int64_t n_poses, const tohip_camera* cam, const uint32_t* occlusion_bits, float* obs,
+                                                      float* scalars, const float* gout, float* trans_grad, float* quat_grad,
+                                                      void* workspace, size_t workspace_bytes, void* stream_) {
+    if (!occlusion_bits) return TOHIP_EINVAL;
+    return pose_forward_backward_multi_impl(packed, n, trans, quat, n_poses, cam, nullptr, occlusion_bits, obs, scalars, gout, trans_grad,
+                                            quat_grad, workspace, workspace_bytes, stream_);
 }
 
 extern "C" int tohip_pose_opt_step_multi(const tohip_pose_opt* o, int32_t step, float* obs, void* stream_) {
     if (!o || !o->scalars || !o->exp_avg_t || !o->exp_avg_sq_t || !o->exp_avg_q || !o->exp_avg_sq_q || !o->loss_log || step < 1 ||
-        step > o->n_steps)
+        step > o->n_steps || (o->occlusion_mask && o->occlusion_bits))
         return TOHIP_EINVAL;
     PoseMultiArgs a;
     PoseFinish f;
-    const int rc = pose_multi_init(a, f, o->packed, o->n_points, o->trans, o->quat, o->n_poses, &o->cam, o->occlusion_mask, obs,
-                                   o->workspace, o->workspace_bytes);
+    const int rc = pose_multi_init(a, f, o->packed, o->n_points, o->trans, o->quat, o->n_poses, &o->cam, o->occlusion_mask, o->occlusion_bits,
+                                   obs, o->workspace, o->workspace_bytes);
     if (rc != TOHIP_OK) return rc;
     f.scalars_out = o->scalars;
     f.trans_grad = o->trans_grad; f.quat_grad = o->quat_grad;
     f.adam = 1; f.mt = o->exp_avg_t; f.vt = o->exp_avg_sq_t; f.mq = o->exp_avg_q; f.vq = o->exp_avg_sq_q;
     f.lr_pose = o->lr_pose; f.lr_quat = o->lr_quat; f.beta1 = o->beta1; f.beta2 = o->beta2; f.adam_eps = o->adam_eps; f.step = step;
     f.loss_log = o->loss_log;
-    return pose_multi_launch<true>(a, f, o->n_steps, (hipStream_t)stream_);
+    return pose_multi_launch<true>(a, o->occlusion_bits != nullptr, f, o->n_steps, (hipStream_t)stream_);
 }
 
 extern "C" int tohip_to_camera_frame(const float* xyz, int64_t n, const float* quat, const float* trans, int normalize,

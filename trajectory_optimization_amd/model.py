@@ -122,11 +122,11 @@ def mean_angle_calc(traj_wps, eps=1e-6):
 
 class _PoseObservations(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, trans, quat, model, mask):
+    def forward(ctx, trans, quat, model, mask, occ):
         t = trans.detach().contiguous()
         q = quat.detach().contiguous()
-        obs, _ = ops.pose_forward(model._cloud, t, q, model._cam, model._ws, mask)
-        ctx.model, ctx.mask = model, mask
+        obs, _ = ops.pose_forward(model._cloud, t, q, model._cam, model._ws, mask, occ=occ)
+        ctx.model, ctx.mask, ctx.occ = model, mask, occ
         ctx.save_for_backward(t, q)
         return obs
 
@@ -134,18 +134,18 @@ class _PoseObservations(torch.autograd.Function):
     def backward(ctx, grad_obs):
         t, q = ctx.saved_tensors
         m = ctx.model
-        tg, qg = ops.pose_backward(m._cloud, t, q, m._cam, m._ws, ctx.mask, grad_obs=grad_obs.contiguous())
-        return tg, qg, None, None
+        tg, qg = ops.pose_backward(m._cloud, t, q, m._cam, m._ws, ctx.mask, grad_obs=grad_obs.contiguous(), occ=ctx.occ)
+        return tg, qg, None, None, None
 
 
 class _PoseLoss(torch.autograd.Function):
     """ModelPose.forward in one autograd node: (trans, quat) -> (loss, observations).  The pass over the cloud that writes the
     observations also takes the gradient sums of the fused loss (they do not depend on its value; tohip_pose_forward_backward), so
     `loss.backward()` is a multiplication of seven numbers; a loss built on model.observations goes through the general
-    dL/d observations pass."""
+    dL/d observations pass.  mask: a float mask (the reference's world-frame HPR) or None; occ: the pose's occlusion bit row or None."""
 
     @staticmethod
-    def forward(ctx, trans, quat, model, mask):
+    def forward(ctx, trans, quat, model, mask, occ):
         if not (trans.is_contiguous() and quat.is_contiguous() and trans.dtype == torch.float32 and quat.dtype == torch.float32):
             raise RuntimeError("ModelPose: trans / quat must be contiguous float32 tensors")
         plan = model._plan
@@ -154,11 +154,11 @@ class _PoseLoss(torch.autograd.Function):
         want_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         if want_grad:
             grads = torch.empty(8, **plan.f32)   # d loss / d trans [0:3], d loss / d quat [4:8]
-            plan.forward_backward(trans, quat, mask, obs, scalars, grads)
+            plan.forward_backward(trans, quat, mask, obs, scalars, grads, occ)
         else:
             grads = None
-            plan.forward(trans, quat, mask, obs, scalars)
-        ctx.model, ctx.mask, ctx.grads = model, mask, grads
+            plan.forward(trans, quat, mask, obs, scalars, occ)
+        ctx.model, ctx.mask, ctx.occ, ctx.grads = model, mask, occ, grads
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(trans, quat, scalars)   # by reference: an in-place edit before backward() raises, as for torch's ops
         loss = scalars[1]
@@ -171,15 +171,15 @@ class _PoseLoss(torch.autograd.Function):
         t, q, scalars = ctx.saved_tensors
         m = ctx.model
         if g_loss is None and g_obs is None:
-            return None, None, None, None
+            return None, None, None, None, None
         if g_obs is None:
             g = g_loss.to(torch.float32) * ctx.grads
-            return g[0:3].reshape(1, 3), g[4:8].reshape(1, 4), None, None
+            return g[0:3].reshape(1, 3), g[4:8].reshape(1, 4), None, None, None
         g = g_obs.to(torch.float32)
         if g_loss is not None:
             g = g - g_loss.to(torch.float32) * scalars[1] * scalars[1]  # d loss / d observation_n = -loss^2
-        tg, qg = ops.pose_backward(m._cloud, t, q, m._cam, m._ws, ctx.mask, grad_obs=g.contiguous())
-        return tg, qg, None, None
+        tg, qg = ops.pose_backward(m._cloud, t, q, m._cam, m._ws, ctx.mask, grad_obs=g.contiguous(), occ=ctx.occ)
+        return tg, qg, None, None, None
 
 
 class _TrajRewards(torch.autograd.Function):
@@ -489,6 +489,8 @@ class _PosePlan:
     def __init__(self, model):
         L = _lib.lib()
         self.fwd, self.bwd, self.fwdbwd = L.tohip_pose_forward, L.tohip_pose_backward, L.tohip_pose_forward_backward
+        # the same calls with an occlusion bit row in the mask's place
+        self.fwd_occ, self.bwd_occ, self.fwdbwd_occ = L.tohip_pose_forward_bits, L.tohip_pose_backward_bits, L.tohip_pose_forward_backward_bits
         self.blob, self.n = model._cloud.blob.data_ptr(), model._cloud.n
         self.cam = model._cam.ref()
         self.ws, self.wsb = model._ws.buf.data_ptr(), model._ws.bytes
@@ -505,24 +507,27 @@ class _PosePlan:
         with torch.cuda.device(idx):
             return fn(*args, self.ws, self.wsb, torch._C._cuda_getCurrentRawStream(idx))
 
-    def forward(self, t, q, mask, obs, scalars):
-        rc = self._call(self.fwd, self.blob, self.n, t.data_ptr(), q.data_ptr(), self.cam, mask.data_ptr() if mask is not None else None,
+    def forward(self, t, q, mask, obs, scalars, occ=None):
+        fn, m = (self.fwd_occ, occ) if occ is not None else (self.fwd, mask)
+        rc = self._call(fn, self.blob, self.n, t.data_ptr(), q.data_ptr(), self.cam, m.data_ptr() if m is not None else None,
                         obs.data_ptr(), scalars.data_ptr())
         if rc:
-            check(rc, "tohip_pose_forward")
+            check(rc, "tohip_pose_forward_bits" if occ is not None else "tohip_pose_forward")
 
-    def forward_backward(self, t, q, mask, obs, scalars, grads):
+    def forward_backward(self, t, q, mask, obs, scalars, grads, occ=None):
         gp = grads.data_ptr()
-        rc = self._call(self.fwdbwd, self.blob, self.n, t.data_ptr(), q.data_ptr(), self.cam, mask.data_ptr() if mask is not None else None,
+        fn, m = (self.fwdbwd_occ, occ) if occ is not None else (self.fwdbwd, mask)
+        rc = self._call(fn, self.blob, self.n, t.data_ptr(), q.data_ptr(), self.cam, m.data_ptr() if m is not None else None,
                         obs.data_ptr(), scalars.data_ptr(), None, gp, gp + 16)
         if rc:
-            check(rc, "tohip_pose_forward_backward")
+            check(rc, "tohip_pose_forward_backward_bits" if occ is not None else "tohip_pose_forward_backward")
 
-    def backward(self, t, q, mask, scalars, gout, tg, qg):
-        rc = self._call(self.bwd, self.blob, self.n, t.data_ptr(), q.data_ptr(), self.cam, mask.data_ptr() if mask is not None else None, None,
+    def backward(self, t, q, mask, scalars, gout, tg, qg, occ=None):
+        fn, m = (self.bwd_occ, occ) if occ is not None else (self.bwd, mask)
+        rc = self._call(fn, self.blob, self.n, t.data_ptr(), q.data_ptr(), self.cam, m.data_ptr() if m is not None else None, None,
                         scalars.data_ptr(), gout.data_ptr(), tg.data_ptr(), qg.data_ptr())
         if rc:
-            check(rc, "tohip_pose_backward")
+            check(rc, "tohip_pose_backward_bits" if occ is not None else "tohip_pose_backward")
 
 
 def _plain_grad(p):
@@ -595,7 +600,15 @@ class _TrajLossPlan(torch.autograd.Function):
 # ------------------------------------------------------------------------------ models
 
 class ModelPose(nn.Module):
-    """Single camera pose optimisation model (/root/reference/src/model.py:65-127)."""
+    """Single camera pose optimisation model (/root/reference/src/model.py:65-127).
+
+    Extra keyword arguments (absent from the reference): `occlusion='hpr'|'zbuffer'` hides from the pose the points its own camera
+    does not see — ModelTraj's per-waypoint rows for this one pose: the cloud in the camera frame (normalised quaternion), the hard
+    frustum cull with `occlusion_limits`, then HPR from the camera centre (or the z-buffer splat), as in
+    /root/reference/src/pc_processor.py:158-187; observations[n] = dist_mask * fov_mask * bit[n].  The row carries no gradient and is
+    rebuilt on every `occlusion_refresh_every`-th forward (ModelTraj's policy).  forward(hpr=True) keeps the reference's world-frame
+    HPR from the world origin (model.py:112-115) and cannot be combined with `occlusion`.
+    """
 
     def __init__(self,
                  points: torch.tensor,   # the cloud, (N, 3), world frame
@@ -604,7 +617,8 @@ class ModelPose(nn.Module):
                  intrins: torch.tensor,  # pinhole matrix K, shape (3, 3)
                  img_width, img_height,
                  min_dist=1.0, max_dist=5.0,
-                 device=torch.device('cuda:0'), *, cloud=None, fast_adam=False):
+                 device=torch.device('cuda:0'), *, cloud=None, fast_adam=False, occlusion=None, occlusion_limits=(1.0, 15.0),
+                 occlusion_refresh_every=1):
         super().__init__()
         assert trans0.size() == torch.Size([1, 3])
         assert q0.size() == torch.Size([1, 4])
@@ -653,6 +667,15 @@ class ModelPose(nn.Module):
         self._cam = ops.Camera(self.K, self.img_width, self.img_height, min_dist, max_dist, self.eps)
         self._ws = ops.PoseWorkspace(self._cloud)
         self._occlusion_mask, self._occlusion_key = None, None
+        if occlusion not in (None, "hpr", "zbuffer"):
+            raise ValueError("occlusion must be None, 'hpr' or 'zbuffer'")
+        self._occlusion, self._occlusion_limits = occlusion, occlusion_limits
+        # The pose's occlusion row is piecewise constant in the pose and carries no gradient; building it (a hard cull and a convex
+        # hull, or a z-buffer) costs many plain steps.  Rebuilt on the first forward and on every occlusion_refresh_every-th one after
+        # (k = 1: every forward), reused in between; refresh_occlusion() forces a rebuild at the next forward.
+        self.occlusion_refresh_every = max(1, int(occlusion_refresh_every))
+        self._occ_cache = None    # (row (1, npad/32) int32, forwards since it was built)
+        self.occlusion_rebuilds = 0   # full rebuilds: bookkeeping for tools and tests
         self.fused_loss = True  # forward() as one autograd node; False (or an overridden criterion): observations node + torch ops
         self.fast_backward = True   # a plain `loss.backward()` on what forward() returned runs on the calling thread
         self._plan = _PosePlan(self)
@@ -668,7 +691,38 @@ class ModelPose(nn.Module):
         kw.setdefault("device", other.device)
         kw.setdefault("min_dist", other.pc_clip_limits[0])
         kw.setdefault("max_dist", other.pc_clip_limits[1])
+        kw.setdefault("occlusion", other._occlusion)
+        kw.setdefault("occlusion_limits", other._occlusion_limits)
+        kw.setdefault("occlusion_refresh_every", other.occlusion_refresh_every)
         return cls(other._cloud, trans0, q0, other.K, other.img_width, other.img_height, **kw)
+
+    def refresh_occlusion(self):
+        """The next forward rebuilds the occlusion row whatever occlusion_refresh_every says."""
+        self._occ_cache = None
+
+    def _occlusion_row(self):
+        """The pose's occlusion bit row for this forward: rebuilt from the current pose on every occlusion_refresh_every-th call,
+        reused otherwise."""
+        c = self._occ_cache
+        if c is None or c[1] >= self.occlusion_refresh_every:
+            row = self._build_occlusion_rows(self.trans.detach().contiguous(), self.quat.detach().contiguous())
+            self.occlusion_rebuilds += 1
+            self._occ_cache = (row, 1)
+            return row
+        self._occ_cache = (c[0], c[1] + 1)
+        return c[0]
+
+    def _adopt_occlusion_row(self, row, age, rebuilds):
+        """What a launch-only loop (optimizer.optimize_pose / optimize_poses) leaves in the cache: its last row, the number of steps
+        that used it, and its rebuilds counted — so the model's next forwards continue the loop's schedule as if its steps had been
+        forwards of the model."""
+        self._occ_cache = (row, age)
+        self.occlusion_rebuilds += rebuilds
+
+    def _build_occlusion_rows(self, trans, quat):
+        """(B, npad/32) occlusion bit rows of B poses of this camera over this cloud, in one batched pass (B = 1 for the model's own)."""
+        return ops.occlusion_bits(self._cloud, self.points, trans, quat, self._cam, self._occlusion_limits[0], self._occlusion_limits[1],
+                                  self._occlusion)
 
     def _hpr_mask(self):
         """HPR of the WORLD-frame cloud seen from the world origin (model.py:114): pose independent, so it is computed once per
@@ -681,14 +735,17 @@ class ModelPose(nn.Module):
 
     def forward(self, debug=False, hpr=False):
         t0 = time()
+        if hpr and self._occlusion is not None:
+            raise ValueError("hpr=True (the reference's world-frame mask) and occlusion= (the pose's own) exclude each other")
         mask = self._hpr_mask() if hpr else None
+        occ = self._occlusion_row() if self._occlusion is not None else None
         fused = self.fused_loss and type(self).criterion is ModelPose.criterion
         if fused:
-            loss, self.observations, scalars = _PoseLoss.apply(self.trans, self.quat, self, mask)
+            loss, self.observations, scalars = _PoseLoss.apply(self.trans, self.quat, self, mask, occ)
             if type(loss) is _Loss and loss.requires_grad:
                 loss.__dict__["_tohip_fast"] = _FastBackwardPose(self._plan, loss.grad_fn, (self.trans, self.quat), loss.grad_fn.grads)
         else:
-            self.observations = _PoseObservations.apply(self.trans, self.quat, self, mask)
+            self.observations = _PoseObservations.apply(self.trans, self.quat, self, mask, occ)
         if debug:
             torch.cuda.synchronize(self.device)
             print(f'Visibility estimation took: {1000 * (time() - t0)} msec')

@@ -445,35 +445,58 @@ class PoseWorkspace:
         self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=cloud.device)
 
 
-def pose_forward(cloud, trans, quat, cam, ws, mask=None):
+def _occ_row(cloud, occ, rows=1, mask=None):
+    """An occlusion bit row argument of the pose calls: (rows, npad/32) or (npad/32,) int32 words on the cloud's device (what
+    occlusion_bits returns).  A float mask besides it is an error (the C ABI's TOHIP_EINVAL)."""
+    if mask is not None:
+        raise ValueError("give a float mask or occlusion bit rows, not both")
+    words = cloud.npad // 32
+    if occ.dtype != torch.int32 or not occ.is_contiguous() or occ.device != cloud.device or occ.numel() != rows * words:
+        raise ValueError(f"occ must be a contiguous int32 tensor of {rows} x {words} words on {cloud.device} (ops.occlusion_bits' rows)")
+    return occ
+
+
+def pose_forward(cloud, trans, quat, cam, ws, mask=None, occ=None):
+    """occ: the pose's occlusion bit row (1, npad/32) instead of a float mask (tohip_pose_forward_bits)."""
     obs = torch.empty(cloud.n, dtype=torch.float32, device=cloud.device)
     scalars = torch.zeros(4, dtype=torch.float32, device=cloud.device)
     with torch.cuda.device(cloud.device):
-        check(_lib.lib().tohip_pose_forward(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), cam.ref(), ptr(mask),
-                                            ptr(obs), ptr(scalars), ptr(ws.buf), ws.bytes, stream_ptr()),
-              "tohip_pose_forward")
+        if occ is not None:
+            check(_lib.lib().tohip_pose_forward_bits(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), cam.ref(), ptr(_occ_row(cloud, occ, mask=mask)),
+                                                     ptr(obs), ptr(scalars), ptr(ws.buf), ws.bytes, stream_ptr()), "tohip_pose_forward_bits")
+        else:
+            check(_lib.lib().tohip_pose_forward(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), cam.ref(), ptr(mask),
+                                                ptr(obs), ptr(scalars), ptr(ws.buf), ws.bytes, stream_ptr()),
+                  "tohip_pose_forward")
     return obs, scalars
 
 
-def pose_forward_backward(cloud, trans, quat, cam, ws, mask=None, gout=None):
+def pose_forward_backward(cloud, trans, quat, cam, ws, mask=None, gout=None, occ=None):
     """ModelPose.forward and the backward of its fused loss in ONE pass over the cloud (tohip_pose_forward_backward).
-    -> (observations (N,), scalars (4: sum, loss, -, -), trans_grad (1,3), quat_grad (1,4)); gradients are gout x d loss / d (.)."""
+    -> (observations (N,), scalars (4: sum, loss, -, -), trans_grad (1,3), quat_grad (1,4)); gradients are gout x d loss / d (.).
+    occ: the pose's occlusion bit row instead of a float mask (tohip_pose_forward_backward_bits)."""
     dev = cloud.device
     obs = torch.empty(cloud.n, dtype=torch.float32, device=dev)
     scalars = torch.empty(4, dtype=torch.float32, device=dev)
     tg = torch.empty((1, 3), dtype=torch.float32, device=dev)
     qg = torch.empty((1, 4), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        check(_lib.lib().tohip_pose_forward_backward(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), cam.ref(), ptr(mask), ptr(obs), ptr(scalars),
-                                                     ptr(gout), ptr(tg), ptr(qg), ptr(ws.buf), ws.bytes, stream_ptr()), "tohip_pose_forward_backward")
+        if occ is not None:
+            check(_lib.lib().tohip_pose_forward_backward_bits(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), cam.ref(), ptr(_occ_row(cloud, occ, mask=mask)),
+                                                              ptr(obs), ptr(scalars), ptr(gout), ptr(tg), ptr(qg), ptr(ws.buf), ws.bytes, stream_ptr()),
+                  "tohip_pose_forward_backward_bits")
+        else:
+            check(_lib.lib().tohip_pose_forward_backward(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), cam.ref(), ptr(mask), ptr(obs), ptr(scalars),
+                                                         ptr(gout), ptr(tg), ptr(qg), ptr(ws.buf), ws.bytes, stream_ptr()), "tohip_pose_forward_backward")
     return obs, scalars, tg, qg
 
 
-def pose_forward_backward_multi(cloud, trans, quat, cam, ws, mask=None, observations=False, grad=True):
+def pose_forward_backward_multi(cloud, trans, quat, cam, ws, mask=None, observations=False, grad=True, occ=None):
     """B poses of one camera over one cloud in one pass (tohip_pose_forward_backward_multi): trans (B,3), quat (B,4) contiguous f32,
     ws a PoseWorkspace(cloud, n_poses >= B).  Each pose's results are bitwise those of pose_forward_backward (grad) or pose_forward.
     -> (observations (B,N) or None, scalars (B,4: sum, loss, -, -), trans_grad (B,3) or None, quat_grad (B,4) or None);
-    grad=False runs the forward-only pass (scoring candidate views)."""
+    grad=False runs the forward-only pass (scoring candidate views).  occ: (B, npad/32) int32, each pose's own occlusion bit row
+    (ops.occlusion_bits of the B poses; tohip_pose_forward_backward_multi_bits) instead of one float mask for all."""
     dev = cloud.device
     B = trans.shape[0] if trans.dim() == 2 else 0
     if B == 0 or tuple(trans.shape) != (B, 3) or tuple(quat.shape) != (B, 4):
@@ -483,6 +506,8 @@ def pose_forward_backward_multi(cloud, trans, quat, cam, ws, mask=None, observat
             raise ValueError(f"{name} must be a contiguous float32 tensor on {dev}")
     if mask is not None and tuple(mask.shape) != (cloud.n,):
         raise ValueError(f"mask must have {cloud.n} entries, got {tuple(mask.shape)}")
+    if occ is not None:
+        _occ_row(cloud, occ, B, mask=mask)
     if not ws.multi or ws.n_poses < B:
         raise ValueError(f"ws must be a PoseWorkspace(cloud, n_poses >= {B}) sized for the multi-pose calls (multi=True)")
     f32 = dict(dtype=torch.float32, device=dev)
@@ -491,20 +516,40 @@ def pose_forward_backward_multi(cloud, trans, quat, cam, ws, mask=None, observat
     tg = torch.empty((B, 3), **f32) if grad else None
     qg = torch.empty((B, 4), **f32) if grad else None
     with torch.cuda.device(dev):
-        check(_lib.lib().tohip_pose_forward_backward_multi(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), B, cam.ref(), ptr(mask), ptr(obs),
-                                                           ptr(scalars), None, ptr(tg), ptr(qg), ptr(ws.buf), ws.bytes, stream_ptr()),
-              "tohip_pose_forward_backward_multi")
+        if occ is not None:
+            check(_lib.lib().tohip_pose_forward_backward_multi_bits(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), B, cam.ref(), ptr(occ),
+                                                                    ptr(obs), ptr(scalars), None, ptr(tg), ptr(qg), ptr(ws.buf), ws.bytes,
+                                                                    stream_ptr()), "tohip_pose_forward_backward_multi_bits")
+        else:
+            check(_lib.lib().tohip_pose_forward_backward_multi(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), B, cam.ref(), ptr(mask), ptr(obs),
+                                                               ptr(scalars), None, ptr(tg), ptr(qg), ptr(ws.buf), ws.bytes, stream_ptr()),
+                  "tohip_pose_forward_backward_multi")
     return obs, scalars, tg, qg
 
 
-def pose_backward(cloud, trans, quat, cam, ws, mask=None, grad_obs=None, scalars=None, gout=None):
+def pose_backward(cloud, trans, quat, cam, ws, mask=None, grad_obs=None, scalars=None, gout=None, occ=None):
+    """occ: the pose's occlusion bit row instead of a float mask (tohip_pose_backward_bits)."""
     tg = torch.empty((1, 3), dtype=torch.float32, device=cloud.device)
     qg = torch.empty((1, 4), dtype=torch.float32, device=cloud.device)
     with torch.cuda.device(cloud.device):
-        check(_lib.lib().tohip_pose_backward(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), cam.ref(), ptr(mask),
-                                             ptr(grad_obs), ptr(scalars), ptr(gout), ptr(tg), ptr(qg), ptr(ws.buf),
-                                             ws.bytes, stream_ptr()), "tohip_pose_backward")
+        if occ is not None:
+            check(_lib.lib().tohip_pose_backward_bits(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), cam.ref(), ptr(_occ_row(cloud, occ, mask=mask)),
+                                                      ptr(grad_obs), ptr(scalars), ptr(gout), ptr(tg), ptr(qg), ptr(ws.buf), ws.bytes,
+                                                      stream_ptr()), "tohip_pose_backward_bits")
+        else:
+            check(_lib.lib().tohip_pose_backward(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), cam.ref(), ptr(mask),
+                                                 ptr(grad_obs), ptr(scalars), ptr(gout), ptr(tg), ptr(qg), ptr(ws.buf),
+                                                 ws.bytes, stream_ptr()), "tohip_pose_backward")
     return tg, qg
+
+
+def unpack_occlusion_rows(cloud, rows):
+    """(W, npad/32) occlusion bit rows -> (W, N) float32 masks of zeros and ones in the CALLER'S point order (1 = not occluded): what
+    the float-mask calls take for the same weights.  For tests and inspection (plain torch ops)."""
+    r = rows.reshape(-1, cloud.npad // 32)
+    bits = (r[:, :, None] >> torch.arange(32, dtype=torch.int32, device=r.device)) & 1
+    packed = bits.reshape(r.shape[0], -1)[:, :cloud.n].to(torch.float32)
+    return packed[:, cloud.inv_perm.long()].contiguous()
 
 
 HPR_BATCH_POINTS = 32_000_000  # points per batched hull pass (workspace ~0.12 KB per point)

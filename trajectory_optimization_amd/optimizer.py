@@ -216,17 +216,31 @@ class PoseOptResult:
         self.losses = losses
 
 
+def _occlusion_schedule(model, hpr, what):
+    """The occlusion refresh period of a ModelPose run (0: no per-pose rows); hpr=True with occlusion= is refused as in forward()."""
+    if model._occlusion is None:
+        return 0
+    if hpr:
+        raise ValueError(f"{what}: hpr=True (the reference's world-frame mask) and occlusion= (each pose's own) exclude each other")
+    return model.occlusion_refresh_every
+
+
 @torch.no_grad()
 def optimize_pose(model, n_opt_steps=100, lr_pose=0.1, lr_quat=0.1, hpr=False, betas=(0.9, 0.999), adam_eps=1e-8):
     """The reference's PoseOpt loop (/root/reference/src/pose_optimization.py:93-97,124-141): n_opt_steps of
     `loss = model(hpr); loss.backward(); Adam(trans @ lr_pose, quat @ lr_quat).step()` on a ModelPose, in place, as
     launches only — two per step (tohip_pose_opt_step: ONE pass over the cloud for observations, loss and gradient sums, then a
     one-block finish with both Adam updates and the loss log) — with one host synchronisation when the run ends.  model.trans / model.quat hold the optimised pose (the
-    reference normalises the quaternion only when publishing, :102), model.observations the last observations."""
+    reference normalises the quaternion only when publishing, :102), model.observations the last observations.
+    A model with occlusion= gets its row rebuilt from the pose on the device before steps 1, k + 1, 2k + 1, ... (k =
+    model.occlusion_refresh_every: the schedule of a fresh model's forwards); the steps in between are launches only, and each
+    refresh adds the hull pass's own host synchronisation.  The model's row cache is left as n_opt_steps forwards would leave it
+    (the last row, the steps since it was built, the rebuilds counted in occlusion_rebuilds)."""
     L = _lib.lib()
     dev = model.device
     cloud, cam, ws = model._cloud, model._cam, model._ws
     f32 = dict(dtype=torch.float32, device=dev)
+    every = _occlusion_schedule(model, hpr, "optimize_pose")
     mask = None
     if hpr:
         model(hpr=True)  # builds (and caches) the world-frame occlusion mask of model.py:114
@@ -237,22 +251,27 @@ def optimize_pose(model, n_opt_steps=100, lr_pose=0.1, lr_quat=0.1, hpr=False, b
     mq, vq = torch.zeros(4, **f32), torch.zeros(4, **f32)
     losses = torch.empty(max(n_opt_steps, 1), **f32)
     trans, quat = model.trans.data, model.quat.data
-    fn = L.tohip_pose_opt_step
-    args = (cloud.blob.data_ptr(), cloud.n, trans.data_ptr(), quat.data_ptr(), cam.ref(), mask.data_ptr() if mask is not None else None,
-            obs.data_ptr(), scalars.data_ptr(), tg.data_ptr(), qg.data_ptr(), mt.data_ptr(), vt.data_ptr(), mq.data_ptr(), vq.data_ptr(),
+    fn = L.tohip_pose_opt_step_bits if every else L.tohip_pose_opt_step
+    rest = (obs.data_ptr(), scalars.data_ptr(), tg.data_ptr(), qg.data_ptr(), mt.data_ptr(), vt.data_ptr(), mq.data_ptr(), vq.data_ptr(),
             float(lr_pose), float(lr_quat), float(betas[0]), float(betas[1]), float(adam_eps))
+    args = (cloud.blob.data_ptr(), cloud.n, trans.data_ptr(), quat.data_ptr(), cam.ref(), mask.data_ptr() if mask is not None else None) + rest
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     with torch.cuda.device(idx):
         stream = torch._C._cuda_getCurrentRawStream(idx)
         for i in range(n_opt_steps):
+            if every and i % every == 0:   # the pose's occlusion row from the pose the device holds now (queued after the last step)
+                row = model._build_occlusion_rows(trans, quat)
+                args = (cloud.blob.data_ptr(), cloud.n, trans.data_ptr(), quat.data_ptr(), cam.ref(), row.data_ptr()) + rest
             # one pass over the cloud (observations, their sum, the gradient sums) and its one-block finish (loss, gradient, both
             # Adam updates, the loss log): two launches per step
             rc = fn(*args, i + 1, losses.data_ptr(), ws.buf.data_ptr(), ws.bytes, stream)
             if rc:
-                check(rc, "tohip_pose_opt_step")
+                check(rc, "tohip_pose_opt_step_bits" if every else "tohip_pose_opt_step")
     torch.autograd.graph.increment_version(model.trans)
     torch.autograd.graph.increment_version(model.quat)
     model.observations = obs
+    if every and n_opt_steps > 0:   # the cache holds the last row and its age: the next forward continues the schedule
+        model._adopt_occlusion_row(row, n_opt_steps - (n_opt_steps - 1) // every * every, (n_opt_steps + every - 1) // every)
     return PoseOptResult(losses[:n_opt_steps].cpu().tolist())  # the run's only host synchronisation
 
 
@@ -262,7 +281,9 @@ def optimize_poses(models, n_opt_steps=100, lr_pose=0.1, lr_quat=0.1, hpr=False,
     step is one library call and two launches for all of them (tohip_pose_opt_step_multi) — one pass over the cloud evaluates a
     tile of poses on the points it holds, then one finish block per pose runs its loss, gradient and both Adam updates.  Each model
     ends up bit for bit where its own `optimize_pose` run would have put it (trans, quat, losses, observations).  Models: ModelPose
-    on the same points with the same camera (K, image size, clip limits), eps and device.  -> [PoseOptResult].
+    on the same points with the same camera (K, image size, clip limits), eps, device and occlusion settings.  -> [PoseOptResult].
+    With occlusion= every pose has its own row: all B are rebuilt in ONE batched hull pass (ops.occlusion_bits) on optimize_pose's
+    schedule, and the pass reads pose b's row for pose b (tohip_pose_opt.occlusion_bits).
     Each model.observations is row b of one (B, N) tensor: any one of them keeps all B x N floats alive (clone a row to keep it
     alone)."""
     models = list(models)
@@ -274,11 +295,15 @@ def optimize_poses(models, n_opt_steps=100, lr_pose=0.1, lr_quat=0.1, hpr=False,
             raise ValueError("optimize_poses: the models must live on one device and share eps")
         if bytes(m._cam.c) != bytes(m0._cam.c):
             raise ValueError("optimize_poses: the models must share the camera (K, image size, clip limits)")
+        if (m._occlusion != m0._occlusion or tuple(m._occlusion_limits) != tuple(m0._occlusion_limits) or
+                m.occlusion_refresh_every != m0.occlusion_refresh_every):
+            raise ValueError("optimize_poses: the models must share occlusion, occlusion_limits and occlusion_refresh_every")
         # what the kernels read is the packed cloud: the same object, or one of equal size over equal rows (the shapes are compared
         # first — a model on a slice of the same tensor shares its data pointer)
         c, c0 = m._cloud, m0._cloud
         if c is not c0 and (c.n != c0.n or tuple(c.points.shape) != tuple(c0.points.shape) or not torch.equal(c.points, c0.points)):
             raise ValueError("optimize_poses: the models must be built on the same points")
+    every = _occlusion_schedule(m0, hpr, "optimize_poses")
     if n_opt_steps <= 0:   # nothing to run: the models keep what they have
         return []
     if len(models) == 1:   # the single-pose pass carries no tile of accumulators: its own path
@@ -298,6 +323,7 @@ def optimize_poses(models, n_opt_steps=100, lr_pose=0.1, lr_quat=0.1, hpr=False,
     c.packed, c.n_points, c.n_poses, c.n_steps = cloud.blob.data_ptr(), cloud.n, B, n_opt_steps
     c.cam = m0._cam.c
     c.occlusion_mask = mask.data_ptr() if mask is not None else None
+    c.occlusion_bits = None
     c.trans, c.quat = trans.data_ptr(), quat.data_ptr()
     c.lr_pose, c.lr_quat, c.beta1, c.beta2, c.adam_eps = float(lr_pose), float(lr_quat), float(betas[0]), float(betas[1]), float(adam_eps)
     c.exp_avg_t, c.exp_avg_sq_t, c.exp_avg_q, c.exp_avg_sq_q = (t.data_ptr() for t in moments)
@@ -305,9 +331,13 @@ def optimize_poses(models, n_opt_steps=100, lr_pose=0.1, lr_quat=0.1, hpr=False,
     c.workspace, c.workspace_bytes = ws.buf.data_ptr(), ws.bytes
     ref, fn = ctypes.byref(c), L.tohip_pose_opt_step_multi
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    rows = None
     with torch.cuda.device(idx):
         stream = torch._C._cuda_getCurrentRawStream(idx)
         for i in range(n_opt_steps):
+            if every and i % every == 0:   # every pose's row, from the poses the device holds now, in one batched pass
+                rows = m0._build_occlusion_rows(trans, quat)
+                c.occlusion_bits = rows.data_ptr()
             # the observations are what the last step leaves (optimize_pose writes them every step; the bits are the same)
             rc = fn(ref, i + 1, obs.data_ptr() if i + 1 == n_opt_steps else None, stream)
             if rc:
@@ -318,6 +348,9 @@ def optimize_poses(models, n_opt_steps=100, lr_pose=0.1, lr_quat=0.1, hpr=False,
             torch.autograd.graph.increment_version(m.trans)
             torch.autograd.graph.increment_version(m.quat)
             m.observations = obs[b]
+            if every:   # each model's cache holds its own last row and its age (optimize_pose's bookkeeping)
+                m._adopt_occlusion_row(rows[b:b + 1].clone(), n_opt_steps - (n_opt_steps - 1) // every * every,
+                                       (n_opt_steps + every - 1) // every)
     lt = losses.cpu()   # the run's only host synchronisation
     return [PoseOptResult(lt[b].tolist()) for b in range(B)]
 
