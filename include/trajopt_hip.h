@@ -37,13 +37,16 @@
 extern "C" {
 #endif
 
-/* 14: + tohip_pose_forward_bits / _backward_bits / _forward_backward_bits / _opt_step_bits / _forward_backward_multi_bits (per-pose
+/* 15: + tohip_clearance / tohip_clearance_workspace_bytes / tohip_traj_clearance_scratch_bytes / tohip_traj_step_tail_clearance /
+ * tohip_traj_regularizers_clearance (the clearance term); tohip_traj_loss and tohip_traj_opt gain clearance_radius,
+ * clearance_weight, clearance_scratch(_bytes) at their ends (zero = off).
+ * 14: + tohip_pose_forward_bits / _backward_bits / _forward_backward_bits / _opt_step_bits / _forward_backward_multi_bits (per-pose
  * occlusion bit rows); tohip_pose_opt gains occlusion_bits at its end.
  * 13: + tohip_pose_workspace_bytes_multi / tohip_pose_forward_backward_multi / tohip_pose_opt_step_multi (several poses of one
  * camera over one cloud per pass).
  * 12 (r05): + tohip_render_points_blend / tohip_render_blend_workspace_bytes; + TOHIP_TRAJ_OPT_LAST_OUTPUTS; tohip_voxel_grid reports
  * PCL's "leaf size too small" case as *out_count = -1.  (11: r04) */
-#define TOHIP_ABI_VERSION 14
+#define TOHIP_ABI_VERSION 15
 
 #define TOHIP_OK 0
 #define TOHIP_EINVAL (-1)   /* bad size / null pointer */
@@ -290,6 +293,13 @@ typedef struct tohip_traj_loss {
     size_t scratch_bytes;
     float *reg_terms;        /* NULL, or (3, W, 3) floats: the gradients of l2, length and smooth separately (callers that
                                 differentiate a single entry of model.loss) */
+    /* the clearance term (tohip_clearance); clearance_weight = 0: off (model() is then exactly the four-term criterion).  On:
+       model() launches the query first (five launches), loss_terms[5] = clearance and total includes it; loss.backward() adds
+       gout x its gradient rows to the regularisers' before the visibility rows: vis + gout (regularisers + clearance) */
+    float clearance_radius;
+    float clearance_weight;
+    void *clearance_scratch;  /* tohip_traj_clearance_scratch_bytes(W, 1): its gradient rows (W,3) f32 at offset 0, then the terms */
+    size_t clearance_scratch_bytes;
 } tohip_traj_loss;
 size_t tohip_traj_loss_scratch_bytes(int64_t n_points, int64_t n_wps, int32_t wps_step, int32_t n_cams);
 /* byte offsets into `scratch` of: [0] poses_e (n_eval,3)  [1] quats_e (n_eval,4)  [2] lo_sum (Npad, packed order)
@@ -350,6 +360,14 @@ typedef struct tohip_traj_opt {
     size_t workspace_bytes;
     void *scratch;             /* tohip_traj_opt_scratch_bytes(n_wps, n_traj) */
     size_t scratch_bytes;
+    /* the clearance term (tohip_clearance) of every trajectory; clearance_weight = 0: off — the step's launches, grids and outputs
+       are then exactly those without these fields.  On: a SIXTH launch, first, queries every waypoint (n_traj W waves); the sparse
+       launch's prologue blocks sum the terms, the finish epilogue's full gradient is vis + (regularisers + clearance) and the loss
+       log row gets [5] = clearance (total includes it) */
+    float clearance_radius;
+    float clearance_weight;
+    void *clearance_scratch;   /* tohip_traj_clearance_scratch_bytes(n_wps, n_traj) */
+    size_t clearance_scratch_bytes;
 } tohip_traj_opt;
 size_t tohip_traj_opt_scratch_bytes(int64_t n_wps, int64_t n_traj);
 /* step_index = 0, 1, ... n_steps - 1, in order.  A trajectory that has stopped (state[2]) stays put; its rewards are still
@@ -559,6 +577,13 @@ int tohip_traj_regularizers(const float *poses, const float *poses0, int64_t n_w
 /* state (may be NULL): when given, loss_terms is the base of an (n_steps, 8) log and the row written is
  * state[3] = steps taken so far — the launch then carries no per-step host value and can be replayed from a
  * hipGraph.  Same convention for tohip_adam_step (step <= 0: step index = state[3] + 1) and tohip_early_stop. */
+/* The same with the clearance term: clearance_terms (W doubles) as tohip_clearance left them in its workspace for these positions,
+ * with weight clearance_weight; loss_terms[5] = clearance and loss_terms[4] = the five-term total, rounded once (as
+ * tohip_traj_opt_step and tohip_traj_loss_forward write it).  grad_poses / grad_terms: the regularisers' gradients only. */
+int tohip_traj_regularizers_clearance(const float *poses, const float *poses0, int64_t n_wps, float smoothness_weight,
+                                      float traj_length_weight, float eps, const float *scalars, float *loss_terms,
+                                      float *grad_poses, int accumulate, const float *state, float *grad_terms,
+                                      float clearance_weight, const double *clearance_terms, void *stream);
 /* rows r*step of a (.., cols) array <-> a compact (n_rows, cols) array: the every-wps_step-th waypoint selection
  * of model.py:217 (scatter = 0: gather src[r*step] -> dst[r]; 1: scatter src[r] -> dst[r*step]). */
 int tohip_rows_strided(const float *src, int64_t n_rows, int cols, int step, int scatter, float *dst, void *stream);
@@ -604,11 +629,38 @@ int tohip_traj_step_tail_multi(float *poses, float *quats, const float *poses0, 
                                float *exp_avg_sq_q, float smoothness_weight, float traj_length_weight, float eps, float lr_pose,
                                float lr_quat, float beta1, float beta2, float adam_eps, float rewards_th, float smoothness_th,
                                const float *scalars, float *loss_terms, int64_t loss_terms_stride, float *state, void *stream);
+/* tohip_traj_step_tail_multi with the clearance term: clearance_grad (n_traj W, 3) and clearance_terms (n_traj W doubles) as
+ * tohip_clearance left them for these positions (its grad rows and its workspace) with weight clearance_weight.  The full gradient is
+ * vis + (regularisers + clearance), as in tohip_traj_opt_step; the loss row gets [5] = clearance and total includes it. */
+int tohip_traj_step_tail_clearance(float *poses, float *quats, const float *poses0, int64_t n_wps, int64_t n_traj,
+                                   const float *poses_grad_eval, const float *quats_grad_eval, int64_t n_eval, int step,
+                                   float *poses_grad, float *quats_grad, float *exp_avg_p, float *exp_avg_sq_p, float *exp_avg_q,
+                                   float *exp_avg_sq_q, float smoothness_weight, float traj_length_weight, float eps, float lr_pose,
+                                   float lr_quat, float beta1, float beta2, float adam_eps, float rewards_th, float smoothness_th,
+                                   const float *scalars, float *loss_terms, int64_t loss_terms_stride, float *state,
+                                   float clearance_weight, const float *clearance_grad, const double *clearance_terms, void *stream);
 int tohip_gather_waypoints_multi(const float *poses, const float *quats, int64_t n_wps, int64_t n_traj, int64_t n_eval, int step,
                                  float *poses_e, float *quats_e, void *stream);
 /* poses_e[r] = poses[r*step], quats_e[r] = quats[r*step] for r < n_eval, in one launch. */
 int tohip_gather_waypoints(const float *poses, const float *quats, int64_t n_eval, int step, float *poses_e, float *quats_e,
                            void *stream);
+
+/* ---- clearance: how far each waypoint is from the cloud (clearance_kernels.hip) -------------------------------------------
+ * For query positions t_w (n_queries, 3) over a packed cloud (sorted or not): d2_w = the smallest fl((dx*dx + dy*dy) + dz*dz),
+ * dx = fl(t_w.x - x_i.x) ... in f32 without contraction, over the rows with three finite coordinates; ties go to the lowest caller
+ * row.  idx[w] = that row, or -1 when no point has d2 < fl(r*r) (or t_w has a non-finite coordinate); d[w] = (float)sqrt((double)
+ * d2_w), +inf when idx[w] = -1.  The term: clearance = weight x sum_w (r - d_w)^2 over the waypoints with idx >= 0, summed in f64
+ * in w order and rounded to f32 (value: one device float, may be NULL); its gradient -2 weight (r - d_w)(t_w - x_idx) / d_w in f64,
+ * rounded to f32, zero when idx = -1 or d_w = 0, into grad (n_queries, 3; may be NULL), overwritten or (accumulate != 0) added to.
+ * workspace: tohip_clearance_workspace_bytes(n_queries); it holds the per-query (r - d_w)^2 (f64, query order) after the call.
+ * radius > 0 and weight >= 0, both finite.  One block of 16 waves per query prunes the 256-point tile spheres; no atomics: the results do
+ * not depend on the launch.  One launch (two with value). */
+size_t tohip_clearance_workspace_bytes(int64_t n_queries);
+int tohip_clearance(const void *packed, int64_t n_points, const float *queries, int64_t n_queries, float radius, float weight, float *d,
+                    int32_t *idx, float *value, float *grad, int accumulate, void *workspace, size_t workspace_bytes, void *stream);
+/* bytes of tohip_traj_loss.clearance_scratch / tohip_traj_opt.clearance_scratch: gradient rows (n_traj W, 3) f32 at offset 0, then
+ * the per-waypoint terms */
+size_t tohip_traj_clearance_scratch_bytes(int64_t n_wps, int64_t n_traj);
 
 /* ---- input formats (pointcloud_utils.py, launch/voxels_filtering.launch) --------------------------------
  * PointCloud2 payload -> (N,3) f32 with non-finite rows removed, in message order

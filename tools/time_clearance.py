@@ -1,0 +1,143 @@
+"""The clearance term's cost and effect (clearance_kernels.hip), in one process:
+
+  query     tohip_clearance alone (one launch: d, idx, gradient rows) over 1 M points x 128 waypoints and 16 M points x 1 024
+            queries, event-timed over back-to-back calls (what the GPU takes per call; rocprofv3 --kernel-trace --stats gives the
+            kernel alone)
+  step      optimize_trajectory per step at 1 M points x 128 waypoints, default mode, without and with the term, the two variants
+            alternating: whole runs at two step counts, the difference over the extra steps = one step
+  sample    the bundled sample (tests/golden/bundled.npz) under examples/trajectory_optimization_sample.py's settings (400 steps,
+            lr 0.1 / 0.02, thresholds 1.1 / 0.9) through optimize_trajectory, without and with the term: the smallest distance from
+            a waypoint to the cloud at the end
+
+    python tools/time_clearance.py [--reps 5] [--steps 20,120] [--radius 0.5] [--weight 5] [--json out.json]
+    python tools/time_clearance.py --only-query        # under rocprofv3 --kernel-trace --stats
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+from trajectory_optimization_amd import _lib, ops, synth, tools  # noqa: E402
+from trajectory_optimization_amd._lib import check, ptr, stream_ptr  # noqa: E402
+from trajectory_optimization_amd.model import ModelTraj  # noqa: E402
+from trajectory_optimization_amd.optimizer import optimize_trajectory  # noqa: E402
+
+K, IW, IH = synth.K_INTRINS, synth.IMG_WIDTH, synth.IMG_HEIGHT
+
+
+def time_query(cloud, q, radius, reps, calls=200):
+    L = _lib.lib()
+    dev = q.device
+    n = q.shape[0]
+    d = torch.empty(n, dtype=torch.float32, device=dev)
+    idx = torch.empty(n, dtype=torch.int32, device=dev)
+    g = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    wsb = L.tohip_clearance_workspace_bytes(n)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    args = (cloud.blob.data_ptr(), cloud.n, q.data_ptr(), n, float(radius), 1.0, d.data_ptr(), idx.data_ptr(), None, g.data_ptr(), 0,
+            ws.data_ptr(), wsb)
+    st = stream_ptr()
+    check(L.tohip_clearance(*args, st), "tohip_clearance")
+    best = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(calls):
+            L.tohip_clearance(*args, st)
+        b.record()
+        b.synchronize()
+        best.append(1000.0 * a.elapsed_time(b) / calls)
+    hit = int((idx >= 0).sum())
+    return {"us_per_call_min": min(best), "us_per_call_median": float(np.median(best)), "queries_with_a_point": hit, "queries": n}
+
+
+def query_case(n_points, n_queries, radius, reps, dev):
+    pts = torch.from_numpy(synth.make_cloud(n_points, seed=1)).to(dev)
+    cloud = ops.PackedCloud(pts)
+    rng = np.random.default_rng(2)
+    q = torch.from_numpy(rng.uniform((-18, -18, -1.5), (18, 18, 1.5), (n_queries, 3)).astype(np.float32)).to(dev)
+    out = time_query(cloud, q, radius, reps)
+    out.update(points=n_points)
+    return out
+
+
+def run_ms(model_factory, steps):
+    m = model_factory()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    optimize_trajectory(m, steps, 0.05, 0.01, 1e9, 1e9, 0.5)   # thresholds out of reach: every step is taken
+    torch.cuda.synchronize()
+    return 1000.0 * (time.perf_counter() - t0)
+
+
+def step_case(radius, weight, steps, reps, dev):
+    pts = torch.from_numpy(synth.make_cloud(1_000_000, seed=1))
+    p, q = synth.make_path(128, optical=True, jitter_seed=1)
+    base = ModelTraj(pts, torch.from_numpy(p), torch.from_numpy(q), torch.from_numpy(K), IW, IH, device=dev)
+    variants = {"without": {}, "with": dict(clearance_radius=radius, clearance_weight=weight)}
+
+    def factory(kw):
+        return lambda: ModelTraj.sharing_cloud_of(base, torch.from_numpy(p), torch.from_numpy(q), **kw)
+    for kw in variants.values():   # warm-up: plans, workspaces, code objects
+        run_ms(factory(kw), 3)
+    per = {k: [] for k in variants}
+    for _ in range(reps):
+        for k, kw in variants.items():   # alternating
+            lo, hi = run_ms(factory(kw), steps[0]), run_ms(factory(kw), steps[1])
+            per[k].append((hi - lo) / (steps[1] - steps[0]))
+    out = {f"{k}_ms_per_step_min": min(v) for k, v in per.items()}
+    out.update({f"{k}_ms_per_step_median": float(np.median(v)) for k, v in per.items()})
+    out["overhead_median_pct"] = 100.0 * (out["with_ms_per_step_median"] / out["without_ms_per_step_median"] - 1.0)
+    return out
+
+
+def sample_case(radius, weight, dev):
+    d = np.load(os.path.join(REPO, "tests", "golden", "bundled.npz"))
+    pts, poses = d["pts"], d["poses"]
+    quats = np.tile(np.array([[1.0, 0.0, 0.0, 0.0]], dtype=np.float32), (len(poses), 1))
+    Kt, iw, ih = tools.load_intrinsics(device=dev)
+    out = {}
+    for name, kw in (("without", {}), ("with", dict(clearance_radius=radius, clearance_weight=weight))):
+        m = ModelTraj(torch.from_numpy(pts), torch.from_numpy(poses), torch.from_numpy(quats), Kt, iw, ih, smoothness_weight=14.0,
+                      traj_length_weight=0.02, device=dev, **kw)
+        d0, _ = tools.trajectory_clearance(m, m.poses.data, 100.0)
+        res = optimize_trajectory(m, 400, 0.1, 0.02, 1.1, 0.9)
+        d1, _ = tools.trajectory_clearance(m, m.poses.data, 100.0)
+        out[name] = {"steps": res.steps_taken, "min_clearance_start_m": float(d0.min()), "min_clearance_end_m": float(d1.min()),
+                     "waypoints_within_radius_end": int((d1 < radius).sum())}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--steps", default="20,120")
+    ap.add_argument("--radius", type=float, default=0.5)
+    ap.add_argument("--weight", type=float, default=5.0)
+    ap.add_argument("--only-query", action="store_true")
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    res = {"query_1m_x_128": query_case(1_000_000, 128, a.radius, a.reps, dev)}
+    print(json.dumps(res), flush=True)
+    res["query_16m_x_1024"] = query_case(16_000_000, 1024, a.radius, a.reps, dev)
+    print(json.dumps(res["query_16m_x_1024"]), flush=True)
+    if not a.only_query:
+        steps = tuple(int(s) for s in a.steps.split(","))
+        res["step_1m_x_128"] = step_case(a.radius, a.weight, steps, a.reps, dev)
+        print(json.dumps(res["step_1m_x_128"]), flush=True)
+        res["sample"] = sample_case(a.radius, a.weight, dev)
+        print(json.dumps(res["sample"]), flush=True)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

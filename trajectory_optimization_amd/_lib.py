@@ -34,7 +34,9 @@ class TrajLoss(ctypes.Structure):
     """struct tohip_traj_loss (include/trajopt_hip.h)."""
     _fields_ = [("packed", c_vp), ("n_points", c_i64), ("n_wps", c_i64), ("wps_step", c_i32), ("flags", c_i32), ("cam", Camera),
                 ("rig", Rig), ("poses0", c_vp), ("smoothness_weight", c_f), ("traj_length_weight", c_f), ("workspace", c_vp),
-                ("workspace_bytes", c_sz), ("scratch", c_vp), ("scratch_bytes", c_sz), ("reg_terms", c_vp)]
+                ("workspace_bytes", c_sz), ("scratch", c_vp), ("scratch_bytes", c_sz), ("reg_terms", c_vp),
+                # ABI 15: the clearance term (zero = off), after every earlier field
+                ("clearance_radius", c_f), ("clearance_weight", c_f), ("clearance_scratch", c_vp), ("clearance_scratch_bytes", c_sz)]
 
 
 class TrajOpt(ctypes.Structure):
@@ -46,7 +48,9 @@ class TrajOpt(ctypes.Structure):
                 ("exp_avg_p", c_vp), ("exp_avg_sq_p", c_vp), ("exp_avg_q", c_vp), ("exp_avg_sq_q", c_vp), ("poses_grad", c_vp),
                 ("quats_grad", c_vp), ("poses_grad_eval", c_vp), ("quats_grad_eval", c_vp), ("lo_sum", c_vp), ("minmax", c_vp),
                 ("rewards", c_vp), ("scalars", c_vp), ("loss_log", c_vp), ("state_log", c_vp), ("workspace", c_vp),
-                ("workspace_bytes", c_sz), ("scratch", c_vp), ("scratch_bytes", c_sz)]
+                ("workspace_bytes", c_sz), ("scratch", c_vp), ("scratch_bytes", c_sz),
+                # ABI 15: the clearance term (zero = off), after every earlier field
+                ("clearance_radius", c_f), ("clearance_weight", c_f), ("clearance_scratch", c_vp), ("clearance_scratch_bytes", c_sz)]
 
 
 class PoseOpt(ctypes.Structure):
@@ -158,8 +162,16 @@ SIGNATURES = {
                                                    c_vp]),
     "tohip_traj_regularizers": (ctypes.c_int, [c_vp, c_vp, c_i64, c_f, c_f, c_f, c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_vp,
                                                 c_vp]),
+    "tohip_traj_regularizers_clearance": (ctypes.c_int, [c_vp, c_vp, c_i64, c_f, c_f, c_f, c_vp, c_vp, c_vp, ctypes.c_int, c_vp,
+                                                          c_vp, c_f, c_vp, c_vp]),
     "tohip_traj_step_tail": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                                              c_vp, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp, c_vp, c_vp]),
+    "tohip_traj_step_tail_clearance": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, ctypes.c_int, c_vp, c_vp,
+                                                       c_vp, c_vp, c_vp, c_vp, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_vp,
+                                                       c_vp, c_i64, c_vp, c_f, c_vp, c_vp, c_vp]),
+    "tohip_clearance_workspace_bytes": (c_sz, [c_i64]),
+    "tohip_clearance": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_f, c_f, c_vp, c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_sz, c_vp]),
+    "tohip_traj_clearance_scratch_bytes": (c_sz, [c_i64, c_i64]),
     "tohip_gather_waypoints": (ctypes.c_int, [c_vp, c_vp, c_i64, ctypes.c_int, c_vp, c_vp, c_vp]),
     "tohip_rows_strided": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
     "tohip_adam_step": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_f, c_f, c_f, c_i32, c_vp, c_vp]),
@@ -241,7 +253,7 @@ def lib():
     return _lib
 
 
-ABI_VERSION = 14  # TOHIP_ABI_VERSION of include/trajopt_hip.h (tests/test_host_cpu.py checks the two agree)
+ABI_VERSION = 15  # TOHIP_ABI_VERSION of include/trajopt_hip.h (tests/test_host_cpu.py checks the two agree)
 ENOSPC = -2  # TOHIP_ENOSPC
 ENAN = -4    # TOHIP_ENAN
 

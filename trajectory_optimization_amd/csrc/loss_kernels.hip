@@ -16,6 +16,8 @@
 //   tohip_traj_loss_backward   one launch: the per-waypoint finish of the visibility gradient (scaled by dL/d loss, read on the
 //                              device); every block also writes its waypoint's rows of the full (W,3) / (W,4) gradients —
 //                              visibility row + dL/d loss x the regularisers' gradient (opt_step.hpp, mode 2)
+//   clearance_weight != 0         the clearance query of every waypoint is launched first by the forward (clearance_kernels.hip);
+//                              its rows join the regularisers' gradient and its value the loss terms ([5], and the total)
 #include "common.hpp"
 #include "opt_step.hpp"
 
@@ -47,6 +49,9 @@ inline LossLayout loss_layout(int64_t n, int64_t W, int step, int n_cams) {
 
 inline bool loss_plan_ok(const tohip_traj_loss* p, LossLayout* l, int* C) {
     if (!p || !p->packed || !p->poses0 || !p->workspace || !p->scratch || p->n_points <= 0 || p->n_wps < 3 || p->wps_step < 1) return false;
+    if (p->clearance_weight != 0.f && (!clearance_args_ok(p->clearance_radius, p->clearance_weight) || !p->clearance_scratch ||
+                                       p->clearance_scratch_bytes < clearance_scratch_bytes(p->n_wps) || p->n_points > INT32_MAX))
+        return false;
     *C = (p->rig.n_cams > 0 && p->rig.rig_quats) ? p->rig.n_cams : 1;
     *l = loss_layout(p->n_points, p->n_wps, p->wps_step, *C);
     return true;
@@ -62,6 +67,11 @@ inline void loss_opt(OptStep& a, const tohip_traj_loss* p, const LossLayout& l) 
     a.reg_terms = p->reg_terms;
     a.W = (int)p->n_wps; a.n_eval = (int)l.n_eval; a.step = p->wps_step; a.n_traj = 1;
     a.smooth_w = p->smoothness_weight; a.length_w = p->traj_length_weight; a.eps = p->cam.eps;
+    if (p->clearance_weight != 0.f) {   // the clearance term: its rows join the regularisers' (opt_step.hpp)
+        a.clr = clearance_scratch_grad(p->clearance_scratch);
+        a.clr_term = clearance_scratch_term(p->clearance_scratch, p->n_wps);
+        a.clr_w = p->clearance_weight;
+    }
 }
 
 }  // namespace
@@ -100,6 +110,11 @@ extern "C" int tohip_traj_loss_forward(const tohip_traj_loss* p, const float* po
     s.opt.poses = const_cast<float*>(poses);
     s.opt.loss_log = loss_terms;
     s.opt_scalars = scal;
+    if (s.opt.clr) {   // one launch more, first: the clearance query of every waypoint (the prologue block sums its terms)
+        rc = clearance_launch(p->packed, p->n_points, poses, p->n_wps, p->clearance_radius, p->clearance_weight, nullptr, nullptr,
+                              const_cast<double*>(s.opt.clr_term), const_cast<float*>(s.opt.clr), 0, st);
+        if (rc != TOHIP_OK) return rc;
+    }
     return traj_fused_forward(s, poses, quats, lo, mm, rewards);
 }
 

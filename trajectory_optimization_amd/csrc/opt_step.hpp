@@ -27,7 +27,16 @@
 // others add zeros — the sums are the same bits whatever launch the block rides in.
 struct RegOut {
     double l2, length, smooth;   // the three terms (model.py:249-258)
+    double clr = 0.0;            // the clearance term (clearance_kernels.hip) when has_clr
+    bool has_clr = false;
 };
+
+// the clearance term's value: weight x the sum of n per-waypoint terms (r - d)^2 in waypoint order, f64 (one thread)
+__device__ __forceinline__ double clearance_sum(const double* __restrict__ term, int64_t n, float weight) {
+    double s = 0.0;
+    for (int64_t i = 0; i < n; ++i) s += term[i];
+    return (double)weight * s;
+}
 
 // grad_poses (W,3), may be NULL: the regularisers' gradient (ADDED to its content when accumulate != 0); grad_terms, may be
 // NULL: (3, W, 3) = d l2, d length, d smooth separately.  Returns the terms in every thread.
@@ -135,10 +144,15 @@ regularizers_eval(const float* __restrict__ poses, const float* __restrict__ pos
     return o;
 }
 
-// loss_terms[0..4] = vis, l2, length, smooth, total
+// loss_terms[0..4] = vis, l2, length, smooth, total; with the clearance term also [5] = clearance (and total includes it)
 __device__ __forceinline__ void write_loss_terms(float* __restrict__ loss_terms, double vis, const RegOut& o) {
     loss_terms[0] = (float)vis; loss_terms[1] = (float)o.l2; loss_terms[2] = (float)o.length; loss_terms[3] = (float)o.smooth;
-    loss_terms[4] = (float)(vis + o.l2 + o.length + o.smooth);
+    if (!o.has_clr) {
+        loss_terms[4] = (float)(vis + o.l2 + o.length + o.smooth);
+        return;
+    }
+    loss_terms[4] = (float)(vis + o.l2 + o.length + o.smooth + o.clr);
+    loss_terms[5] = (float)o.clr;
 }
 
 // ---- torch.optim.Adam (defaults betas=(0.9,0.999), eps=1e-8, no weight decay / amsgrad) --------------------------------------
@@ -190,7 +204,18 @@ struct __attribute__((aligned(64))) OptPro {
     double l2, length, smooth;
     float ss_p, ss_q, sqrt_bc2;   // Adam: lr_pose / bc1, lr_quat / bc1, sqrt(bc2) of step (state row)[3] + 1
     float pad;
+    double clr;                   // the clearance term (valid when has_clr)
+    int has_clr;
 };
+static_assert(sizeof(OptPro) == 64, "OptPro is one 64-byte record");
+
+// the terms a loss row is written from
+__device__ __forceinline__ RegOut regout_of(const OptPro& p) {
+    RegOut o;
+    o.l2 = p.l2; o.length = p.length; o.smooth = p.smooth;
+    o.clr = p.clr; o.has_clr = p.has_clr != 0;
+    return o;
+}
 
 struct OptStep {
     int mode;                  // 0: off   1: an optimisation step (regularisers, Adam, early stop)   2: model() / loss.backward() (loss_kernels.hip)
@@ -206,6 +231,9 @@ struct OptStep {
     const float* state_in;     // mode 1: trajectory b's state row of this step at + b * state_stride
     float* state_out;          //   ... and of the next one
     const float* gout;         // mode 2: dL/d loss (device)
+    const float* clr;          // NULL: no clearance term; else (n_traj * W, 3) its gradient rows (clearance_kernels.hip, launched first)
+    const double* clr_term;    //   ... and the per-waypoint terms (r - d)^2 the prologue sums
+    float clr_w;               //   ... and its weight
     int64_t log_stride, state_stride;
     int W, n_eval, step, n_traj;
     float smooth_w, length_w, eps, lr_pose, lr_quat, beta1, beta2, adam_eps, rewards_th, smoothness_th;
@@ -234,6 +262,8 @@ __device__ __forceinline__ void opt_prologue_block(const OptStep& a, int b, doub
                                        a.mode == 2 ? a.reg_terms : nullptr, lds, sh);
     if (threadIdx.x == 0) {
         a.pro[b].l2 = o.l2; a.pro[b].length = o.length; a.pro[b].smooth = o.smooth;
+        a.pro[b].has_clr = a.clr != nullptr;
+        a.pro[b].clr = a.clr ? clearance_sum(a.clr_term + (int64_t)b * a.W, a.W, a.clr_w) : 0.0;
         if (a.mode == 1 && adam_thread == 0) adam();
         if (a.mode != 1 || adam_thread == 0) { a.pro[b].ss_p = p.ss_p; a.pro[b].ss_q = p.ss_q; a.pro[b].sqrt_bc2 = p.sqrt_bc2; a.pro[b].pad = 0.f; }
     }
@@ -259,7 +289,7 @@ __device__ __forceinline__ OptElem opt_elem_load(const OptStep& a, int b, int r,
     if (j >= a.W || jj >= a.step) return o;
     const int64_t row = (int64_t)b * a.W + j;
     o.at = k < 3 ? row * 3 + k : row * 4 + (k - 3);
-    if (k < 3) o.reg = a.reg[o.at];
+    if (k < 3) o.reg = a.clr ? a.reg[o.at] + a.clr[o.at] : a.reg[o.at];   // vis + (regularisers + clearance)
     if (a.mode == 1) {
         o.m = (k < 3 ? a.mp : a.mq)[o.at];
         o.v = (k < 3 ? a.vp : a.vq)[o.at];
@@ -292,8 +322,6 @@ __device__ __forceinline__ void opt_update_element(const OptStep& a, int b, int 
 __device__ __forceinline__ void opt_commit(const OptStep& a, int b, const float* scalars, const OptPro& p) {
     const float* in = a.state_in + (int64_t)b * a.state_stride;
     float* out = a.state_out + (int64_t)b * a.state_stride;
-    RegOut o;
-    o.l2 = p.l2; o.length = p.length; o.smooth = p.smooth;
-    if (in[2] == 0.f) write_loss_terms(a.loss_log + (int64_t)b * a.log_stride + 8 * (int)in[3], (double)scalars[1], o);
+    if (in[2] == 0.f) write_loss_terms(a.loss_log + (int64_t)b * a.log_stride + 8 * (int)in[3], (double)scalars[1], regout_of(p));
     early_stop_next(in, out, scalars[0], (float)p.smooth, a.rewards_th, a.smoothness_th);
 }

@@ -1207,10 +1207,7 @@ __global__ void __launch_bounds__(TO_SP_THREADS) k_traj_pairs(SparseArgs a, OptS
             float sc[4];
             reward_scalars_from_a(a.acc, a.cv.n, a.shift, os.eps, sc);
             scalars_out[0] = sc[0]; scalars_out[1] = sc[1]; scalars_out[2] = sc[2]; scalars_out[3] = sc[3];
-            const OptPro p = os.pro[0];
-            RegOut o;
-            o.l2 = p.l2; o.length = p.length; o.smooth = p.smooth;
-            write_loss_terms(os.loss_log, (double)sc[1], o);
+            write_loss_terms(os.loss_log, (double)sc[1], regout_of(os.pro[0]));
         }
         return;
     }
@@ -2417,6 +2414,10 @@ extern "C" int tohip_traj_opt_step(const tohip_traj_opt* o, int32_t step_index, 
     const int64_t W = o->n_wps, B = o->n_traj, n_eval = (W + o->wps_step - 1) / o->wps_step;
     const OptLayout l = opt_layout(W, B);
     if (o->scratch_bytes < l.total) return TOHIP_ENOSPC;
+    const bool clr = o->clearance_weight != 0.f;   // zero-initialised: the step without the clearance term
+    if (clr && (!clearance_args_ok(o->clearance_radius, o->clearance_weight) || !o->clearance_scratch || o->n_points > INT32_MAX))
+        return TOHIP_EINVAL;
+    if (clr && o->clearance_scratch_bytes < clearance_scratch_bytes(W * B)) return TOHIP_ENOSPC;
     const tohip_rig* rig = (o->rig.n_cams > 0 && o->rig.rig_quats) ? &o->rig : nullptr;
     TrajStep s;
     int rc = traj_step_init(s, o->packed, o->n_points, B * n_eval, B, o->traj_offsets, &o->cam, rig, o->flags & TOHIP_TRAJ_DENSE, nullptr, o->workspace,
@@ -2444,6 +2445,14 @@ extern "C" int tohip_traj_opt_step(const tohip_traj_opt* o, int32_t step_index, 
     a.smooth_w = o->smoothness_weight; a.length_w = o->traj_length_weight; a.eps = o->cam.eps;
     a.lr_pose = o->lr_pose; a.lr_quat = o->lr_quat; a.beta1 = o->beta1; a.beta2 = o->beta2; a.adam_eps = o->adam_eps;
     a.rewards_th = o->rewards_th; a.smoothness_th = o->smoothness_th;
+    if (clr) {   // a sixth launch, first: the clearance rows of every waypoint (the prologue sums the terms, the epilogue adds the rows)
+        a.clr = clearance_scratch_grad(o->clearance_scratch);
+        a.clr_term = clearance_scratch_term(o->clearance_scratch, W * B);
+        a.clr_w = o->clearance_weight;
+        rc = clearance_launch(o->packed, o->n_points, o->poses, W * B, o->clearance_radius, o->clearance_weight, nullptr, nullptr,
+                              const_cast<double*>(a.clr_term), const_cast<float*>(a.clr), 0, s.st);
+        if (rc != TOHIP_OK) return rc;
+    }
     rc = traj_fused_forward(s, o->poses, o->quats, o->lo_sum, o->minmax, o->rewards);
     if (rc != TOHIP_OK) return rc;
     return launch_finish(s, finish_post(s, 2, nullptr, nullptr, o->scalars, o->cam.eps), o->poses_grad_eval, o->quats_grad_eval);

@@ -2,6 +2,7 @@
 //
 // Build:  hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fPIC -shared trajopt_hip.hip -o libtrajopt_hip.so
 // (-ffp-contract=off: every FMA in the kernels is an explicit fmaf(); see common.hpp.)
+#include "clearance_kernels.hip"
 #include "traj_kernels.hip"
 #include "pose_kernels.hip"
 #include "hard_kernels.hip"

@@ -207,9 +207,10 @@ class _TrajRewards(torch.autograd.Function):
         return pg.contiguous(), qg.contiguous(), None
 
 
-def _regularizers(model, p_all, scalars):
+def _regularizers(model, p_all, scalars, clr_terms=None):
     """criterion()'s terms on the device after the visibility step that left `scalars` -> (terms[8]: vis, l2, length, smooth, total,
-    ...; reg_sum (W,3): the gradient of the regularisers' sum; reg_terms (3,W,3): the gradient of each)."""
+    ...; reg_sum (W,3): the gradient of the regularisers' sum; reg_terms (3,W,3): the gradient of each).  clr_terms (W float64, the
+    clearance query's per-waypoint terms): terms[5] = clearance, and the total is the five-term sum rounded once, as on every path."""
     W, dev = p_all.shape[0], p_all.device
     terms = torch.empty(8, dtype=torch.float32, device=dev)
     reg_sum = torch.empty((W, 3), dtype=torch.float32, device=dev)
@@ -217,7 +218,11 @@ def _regularizers(model, p_all, scalars):
     args = (ptr(p_all), ptr(model.poses0), W, float(model.smoothness_weight), float(model.traj_length_weight), float(model.eps),
             ptr(scalars), ptr(terms), ptr(reg_sum), 0, None, ptr(reg_terms))
     with torch.cuda.device(dev):
-        check(_lib.lib().tohip_traj_regularizers(*args, stream_ptr()), "tohip_traj_regularizers")
+        if clr_terms is None:
+            check(_lib.lib().tohip_traj_regularizers(*args, stream_ptr()), "tohip_traj_regularizers")
+        else:
+            check(_lib.lib().tohip_traj_regularizers_clearance(*args, float(model.clearance_weight), ptr(clr_terms), stream_ptr()),
+                  "tohip_traj_regularizers_clearance")
     return terms, reg_sum, reg_terms
 
 
@@ -239,6 +244,39 @@ def _assemble_grads(step_w, W, pg_e, qg_e, g_loss, g_terms, reg_sum, reg_terms):
             if c is not None:
                 pg_all = pg_all + c * reg_terms[k]
     return pg_all.contiguous(), qg_all.contiguous()
+
+
+def _assemble_grads_clr(step_w, W, pg_e, qg_e, g_loss, g_terms, g_clr, reg_sum, reg_terms, clr_rows):
+    """_assemble_grads with the clearance term's rows (None: the term is off).  dL/d loss alone: vis + g_loss (regularisers +
+    clearance), the order of the one-call step (tohip_traj_opt_step)."""
+    if clr_rows is None:
+        return _assemble_grads(step_w, W, pg_e, qg_e, g_loss, g_terms, reg_sum, reg_terms)
+    if g_clr is None and all(g is None for g in g_terms):
+        return _assemble_grads(step_w, W, pg_e, qg_e, g_loss, g_terms, reg_sum + clr_rows, reg_terms)
+    pg, qg = _assemble_grads(step_w, W, pg_e, qg_e, g_loss, g_terms, reg_sum, reg_terms)
+    g_clr = _f32(g_clr)
+    c = g_loss if g_clr is None else (g_clr if g_loss is None else g_loss + g_clr)
+    if c is not None:
+        pg = pg + c * clr_rows
+    return pg.contiguous(), qg
+
+
+class _Clearance(torch.autograd.Function):
+    """The clearance term of the op-by-op criterion: poses (W,3) -> weight x sum (r - d)^2 (clearance_kernels.hip; its analytic
+    gradient rows are taken by the same launch)."""
+
+    @staticmethod
+    def forward(ctx, poses, model):
+        rows = torch.empty((poses.shape[0], 3), dtype=torch.float32, device=poses.device)
+        _, _, value = ops.clearance(model._cloud, poses.detach(), model.clearance_radius, model.clearance_weight, grad=rows,
+                                    want_value=True)
+        ctx.save_for_backward(rows)
+        return value
+
+    @staticmethod
+    def backward(ctx, g):
+        rows, = ctx.saved_tensors
+        return (g.to(torch.float32) * rows).contiguous(), None
 
 
 def _vis_upstream(g_loss, g_vis, g_rewards, scalars):
@@ -297,17 +335,24 @@ class _TrajLoss(torch.autograd.Function):
             lo_sum, rewards, scalars = st.forward(ps, qs, occ)
             ctx.occ, ctx.gen = occ, st.ws.generation
             saved = (ps, qs, lo_sum, scalars)
-        terms, reg_sum, reg_terms = _regularizers(model, p_all, scalars)
+        clr_rows = clr_terms = None
+        if model._clearance_on:   # every rank: all W waypoints, the whole cloud
+            clr_rows = torch.empty((W, 3), dtype=torch.float32, device=p_all.device)
+            clr_terms = torch.empty(_lib.lib().tohip_clearance_workspace_bytes(W) // 8, dtype=torch.float64, device=p_all.device)
+            ops.clearance(model._cloud, p_all, model.clearance_radius, model.clearance_weight, grad=clr_rows, terms=clr_terms)
+        terms, reg_sum, reg_terms = _regularizers(model, p_all, scalars, clr_terms)
         ctx.step, ctx.step_w, ctx.W = st, step_w, W
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(reg_sum, reg_terms, *saved)
-        vis, l2, length, smooth, total = terms[:5].unbind()
-        return total, rewards, vis, l2, length, smooth
+        vis, l2, length, smooth, total, clr = terms[:6].unbind()   # (clr: [5], written when the clearance term is on)
+        ctx.has_clr = clr_rows is not None
+        ctx.save_for_backward(reg_sum, reg_terms, *((clr_rows,) if ctx.has_clr else ()), *saved)
+        return total, rewards, vis, l2, length, smooth, clr
 
     @staticmethod
-    def backward(ctx, g_loss, g_rewards, g_vis, g_l2, g_length, g_smooth):
+    def backward(ctx, g_loss, g_rewards, g_vis, g_l2, g_length, g_smooth, g_clr):
         st = ctx.step
         reg_sum, reg_terms, *saved = ctx.saved_tensors
+        clr_rows = saved.pop(0) if ctx.has_clr else None
         g_loss, g_vis = _f32(g_loss), _f32(g_vis)
         if isinstance(st, ops.PointShardStep):
             if g_rewards is not None:
@@ -319,7 +364,8 @@ class _TrajLoss(torch.autograd.Function):
             ps, qs, lo_sum, scalars = saved
             upstream = _vis_upstream(g_loss, g_vis, g_rewards, scalars) if st.hi > st.lo else None
             pg_e, qg_e = st.backward(ps, qs, ctx.occ, ctx.gen, lo_sum, upstream)
-        pg, qg = _assemble_grads(ctx.step_w, ctx.W, pg_e, qg_e, g_loss, (g_l2, g_length, g_smooth), reg_sum, reg_terms)
+        pg, qg = _assemble_grads_clr(ctx.step_w, ctx.W, pg_e, qg_e, g_loss, (g_l2, g_length, g_smooth), g_clr, reg_sum, reg_terms,
+                                     clr_rows)
         return pg, qg, None, None
 
 
@@ -357,6 +403,13 @@ class _LossPlan:
         c.workspace, c.workspace_bytes = self.ws.buf.data_ptr(), self.ws.bytes
         c.scratch, c.scratch_bytes = self.scratch.data_ptr(), nbytes
         c.reg_terms = self.reg_terms.data_ptr()
+        self.clr_rows = None
+        if model._clearance_on:   # the clearance term: its gradient rows (W,3) lead the plan's clearance scratch
+            cb = L.tohip_traj_clearance_scratch_bytes(W, 1)
+            self.clr_scratch = torch.empty(cb, dtype=torch.uint8, device=dev)
+            self.clr_rows = self.clr_scratch[:12 * W].view(torch.float32).view(W, 3)
+            c.clearance_radius, c.clearance_weight = float(model.clearance_radius), float(model.clearance_weight)
+            c.clearance_scratch, c.clearance_scratch_bytes = self.clr_scratch.data_ptr(), cb
         self.c, self.ref = c, ctypes.byref(c)
         self.model = model
         self.fwd, self.bwd, self.refresh = L.tohip_traj_loss_forward, L.tohip_traj_loss_backward, L.tohip_traj_loss_refresh
@@ -567,18 +620,18 @@ class _TrajLossPlan(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         ctx.inputs, ctx.versions = (poses, quats), (poses._version, quats._version)
         ctx.save_for_backward(plan.one)   # nothing of it is needed: a second backward() without retain_graph raises like torch's ops
-        vis, l2, length, smooth, total = terms[:5].unbind()
+        vis, l2, length, smooth, total, clr = terms[:6].unbind()   # (clr: [5], written when the clearance term is on)
         if plan.model.fast_backward:
             total = total.as_subclass(_Loss)   # made here: an alias made outside would be one more autograd node
-        return total, rewards, vis, l2, length, smooth
+        return total, rewards, vis, l2, length, smooth, clr
 
     @staticmethod
-    def backward(ctx, g_loss, g_rewards, g_vis, g_l2, g_length, g_smooth):
+    def backward(ctx, g_loss, g_rewards, g_vis, g_l2, g_length, g_smooth, g_clr):
         plan = ctx.plan
         ctx.saved_tensors
         if plan.ws.generation != ctx.gen:   # model() ran again since: rebuild this step's state (rewards / loss terms to spare vectors)
             ctx.gen = plan.rebuild(ctx.inputs[0], ctx.inputs[1], ctx.versions)
-        if g_rewards is None and g_vis is None and g_l2 is None and g_length is None and g_smooth is None:
+        if g_rewards is None and g_vis is None and g_l2 is None and g_length is None and g_smooth is None and g_clr is None:
             if g_loss is None:
                 return None, None, None
             if g_loss.dtype != torch.float32 or g_loss.device != plan.dev:
@@ -593,7 +646,8 @@ class _TrajLossPlan(torch.autograd.Function):
         if kw is not None:
             pg, qg = ops.traj_backward(m._cloud, plan.n_eval, m._cam, plan.ws, plan.lo_sum, rig=m._rig, flags=m._flags, **kw)
             plan.sums_stale = True   # the pair sums in the workspace are now scaled by THIS upstream gradient
-        pg_all, qg_all = _assemble_grads(plan.step_w, plan.W, pg, qg, g_loss, (g_l2, g_length, g_smooth), plan.reg_sum, plan.reg_terms)
+        pg_all, qg_all = _assemble_grads_clr(plan.step_w, plan.W, pg, qg, g_loss, (g_l2, g_length, g_smooth), g_clr, plan.reg_sum,
+                                             plan.reg_terms, plan.clr_rows)
         return pg_all, qg_all, None
 
 
@@ -798,8 +852,14 @@ class ModelTraj(nn.Module):
                  smoothness_weight=14.0, traj_length_weight=0.02,
                  device=torch.device('cuda'),
                  *, rig=None, shard=None, dense=False, occlusion=None, occlusion_limits=(1.0, 15.0), occlusion_refresh_every=1,
-                 occlusion_refresh_tol=None, occlusion_check_every=5, n_points_global=None, cloud=None, fast_adam=False):
+                 occlusion_refresh_tol=None, occlusion_check_every=5, n_points_global=None, cloud=None, fast_adam=False,
+                 clearance_radius=None, clearance_weight=0.0):
         super().__init__()
+        # the clearance term (clearance_kernels.hip): weight x sum over ALL waypoints of (r - d)^2, d = the distance to the nearest
+        # cloud point within r — it keeps the path off the cloud; weight 0 (the default): off, the reference's criterion as it is
+        self._clr_points_shard = shard is not None and shard.kind == "points"
+        self._clr = (None, 0.0)
+        self.set_clearance(clearance_radius, clearance_weight)
         assert wps_poses.dim() == wps_quats.dim()
         assert wps_poses.size()[1] == 3
         assert wps_quats.size()[1] == 4
@@ -902,6 +962,34 @@ class ModelTraj(nn.Module):
             tag_parameter(p)   # torch.optim.Adam.step() MAY update them with one launch — once the caller opts in:
         if fast_adam:          # fast_adam=True here, optimizer.accelerate_torch_adam(True) or accelerate_torch_adam(opt) (nothing is hooked otherwise)
             accelerate_torch_adam(True)
+
+    def set_clearance(self, radius, weight):
+        """The clearance term's settings (both checked together: radius > 0 when weight > 0, both finite; ValueError otherwise).
+        Weight 0 switches the term off.  The next forward / optimiser run uses them."""
+        r, w = ops.check_clearance(radius, weight)
+        if w > 0.0 and self._clr_points_shard:
+            raise ValueError("the clearance term needs the whole cloud on every rank: not available with PointShard")
+        self._clr = (r if w > 0.0 else radius, w)
+
+    @property
+    def clearance_radius(self):
+        return self._clr[0]
+
+    @clearance_radius.setter
+    def clearance_radius(self, radius):
+        self.set_clearance(radius, self._clr[1])
+
+    @property
+    def clearance_weight(self):
+        return self._clr[1]
+
+    @clearance_weight.setter
+    def clearance_weight(self, weight):
+        self.set_clearance(self._clr[0], weight)
+
+    @property
+    def _clearance_on(self):
+        return self._clr[1] > 0.0
 
     @classmethod
     def sharing_cloud_of(cls, other, wps_poses, wps_quats, **kw):
@@ -1019,7 +1107,7 @@ class ModelTraj(nn.Module):
         """The library-side description of this model for the one-call forward / backward (rebuilt when something it froze
         has changed: the weights of criterion, the mode, the initial trajectory, the number of waypoints)."""
         key = (step_w, float(self.smoothness_weight), float(self.traj_length_weight), self._flags, self.poses0.data_ptr(),
-               self.poses.shape[0])
+               self.poses.shape[0], self._clearance_on, self.clearance_radius, self.clearance_weight)
         if self._plan_key != key:
             self._plan_obj, self._plan_key = _LossPlan(self, step_w), key
         return self._plan_obj
@@ -1048,13 +1136,15 @@ class ModelTraj(nn.Module):
             raise NotImplementedError("ModelTraj(shard=PointShard()) supports the reference's criterion on >= 3 waypoints")
         if fused and (self.fused_loss or points):
             if points or self._shard.collective or self._occlusion is not None:
-                loss, self.rewards, vis, l2, length, smooth = _TrajLoss.apply(self.poses, self.quats, self, wps_step)
+                loss, self.rewards, vis, l2, length, smooth, clr = _TrajLoss.apply(self.poses, self.quats, self, wps_step)
             else:
                 plan = self._plan(wps_step)
-                loss, self.rewards, vis, l2, length, smooth = _TrajLossPlan.apply(self.poses, self.quats, plan)
+                loss, self.rewards, vis, l2, length, smooth, clr = _TrajLossPlan.apply(self.poses, self.quats, plan)
                 if type(loss) is _Loss and loss.requires_grad:
                     loss.__dict__["_tohip_fast"] = _FastBackward(plan, plan.ws.generation, loss.grad_fn, (self.poses, self.quats))
             self.loss = {'vis': vis, 'length': length, 'l2': l2, 'smooth': smooth}
+            if self._clearance_on:
+                self.loss['clearance'] = clr
             if debug:
                 torch.cuda.synchronize(self.device)
                 print(f'Trajectory evaluation took {1000 * (time() - t0)} msec')
@@ -1087,4 +1177,9 @@ class ModelTraj(nn.Module):
             self._length0 = length_calc(self.poses0)
         self.loss['length'] = self.traj_length_weight * torch.abs(length_calc(self.poses) - self._length0)
 
-        return self.loss['vis'] + self.loss['l2'] + self.loss['length'] + self.loss['smooth']
+        total = self.loss['vis'] + self.loss['l2'] + self.loss['length'] + self.loss['smooth']
+        if self._clearance_on:
+            # keep the waypoints off the cloud (the term's query and gradient rows: one launch)
+            self.loss['clearance'] = _Clearance.apply(self.poses, self)
+            total = total + self.loss['clearance']
+        return total

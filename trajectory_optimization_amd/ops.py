@@ -422,6 +422,41 @@ def allreduce_log_odds(shard, cloud, ws, lo_sum, local=True):
     return lo_sum
 
 
+def check_clearance(radius, weight):
+    """The clearance term's settings: radius > 0 and weight >= 0, both finite (ValueError otherwise)."""
+    r, w = float(radius) if radius is not None else float("nan"), float(weight)
+    if not (np.isfinite(w) and w >= 0.0):
+        raise ValueError(f"clearance_weight must be a finite number >= 0, got {weight!r}")
+    if w > 0.0 and not (np.isfinite(r) and r > 0.0):
+        raise ValueError(f"clearance_radius must be a finite number > 0 when clearance_weight > 0, got {radius!r}")
+    return r, w
+
+
+def clearance(cloud, positions, radius, weight=0.0, grad=None, accumulate=False, want_value=False, terms=None):
+    """tohip_clearance: each position's nearest cloud point within `radius` -> (d (n,) f32, +inf when none; idx (n,) int32 caller rows,
+    -1 when none[, value: 0-d f32 = weight x sum (radius - d)^2]).  grad (n, 3) f32, optional: the term's gradient rows, overwritten
+    (accumulate=False) or added to.  terms (optional): a float64 tensor of n entries that receives the per-position (radius - d)^2."""
+    _require_cuda(positions, "positions")
+    q = positions.detach().to(torch.float32).contiguous()
+    if q.dim() != 2 or q.shape[1] != 3 or q.shape[0] == 0:
+        raise ValueError(f"positions must be (n,3) with n>0, got {tuple(q.shape)}")
+    r, w = check_clearance(radius, weight)
+    L = _lib.lib()
+    n, dev = q.shape[0], q.device
+    d = torch.empty(n, dtype=torch.float32, device=dev)
+    idx = torch.empty(n, dtype=torch.int32, device=dev)
+    value = torch.empty((), dtype=torch.float32, device=dev) if want_value else None
+    wsb = L.tohip_clearance_workspace_bytes(n)
+    if terms is None:
+        terms = torch.empty(wsb // 8, dtype=torch.float64, device=dev)
+    if grad is not None and not (grad.is_contiguous() and grad.dtype == torch.float32 and tuple(grad.shape) == (n, 3)):
+        raise ValueError("grad must be a contiguous (n,3) float32 tensor")
+    with torch.cuda.device(dev):
+        check(L.tohip_clearance(cloud.blob.data_ptr(), cloud.n, ptr(q), n, r, w, ptr(d), ptr(idx), ptr(value), ptr(grad),
+                                int(bool(accumulate)), ptr(terms), terms.numel() * 8, stream_ptr()), "tohip_clearance")
+    return (d, idx, value) if want_value else (d, idx)
+
+
 def traj_step_stats(cloud, ws):
     """What the last forward over `ws` found -> dict(flagged_pairs, candidate_slots, slots, virtual_waypoints, flagged_fraction,
     evaluated_pairs: those the last culled pass 1 evaluated)."""

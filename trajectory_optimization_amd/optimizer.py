@@ -78,6 +78,12 @@ class _OptRun:
         c.loss_log, c.state_log = self.loss_log.data_ptr(), self.state_log.data_ptr()
         c.workspace, c.workspace_bytes = self.ws.buf.data_ptr(), self.ws.bytes
         c.scratch, c.scratch_bytes = self.scratch.data_ptr(), nbytes
+        self.clearance = m0._clearance_on
+        if self.clearance:   # the clearance term: one launch more per step, first (its rows join the regularisers')
+            cb = L.tohip_traj_clearance_scratch_bytes(W, B)
+            self.clr_scratch = torch.empty(cb, dtype=torch.uint8, device=dev)
+            c.clearance_radius, c.clearance_weight = float(m0.clearance_radius), float(m0.clearance_weight)
+            c.clearance_scratch, c.clearance_scratch_bytes = self.clr_scratch.data_ptr(), cb
         self.c, self.ref, self.fn = c, ctypes.byref(c), L.tohip_traj_opt_step
 
     def run(self, n):
@@ -109,6 +115,8 @@ class _OptRun:
                 row = lt[b, steps - 1]
                 m.rewards = self.rewards[b]
                 m.loss = {"vis": row[0], "l2": row[1], "length": row[2], "smooth": row[3]}
+                if self.clearance:
+                    m.loss["clearance"] = row[5]
             out.append(TrajOptResult(steps, bool(st[b, 2].item() != 0), lt[b, :steps, 4].tolist(), float(st[b, 4]), float(st[b, 5])))
         return out
 
@@ -155,6 +163,10 @@ def _optimize_trajectory_split(model, n_opt_steps, lr_pose, lr_quat, rewards_th,
     poses, quats = model.poses.data, model.quats.data
     # the evaluated waypoints are every step_w-th row of the Parameters, read in place (TOHIP_TRAJ_STRIDE in the flags: no gather)
     stride = ((step_w - 1) & 0xffff) << 8
+    clr = model._clearance_on
+    if clr:   # the clearance term: the query's gradient rows and per-waypoint terms, consumed by the step tail
+        clr_rows = torch.empty((W, 3), **f32)
+        clr_terms = torch.empty(L.tohip_clearance_workspace_bytes(W) // 8, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         for _ in range(n_opt_steps):
             kw = {}
@@ -162,6 +174,15 @@ def _optimize_trajectory_split(model, n_opt_steps, lr_pose, lr_quat, rewards_th,
                 own = slice(st.lo * step_w, (st.hi - 1) * step_w + 1, step_w)
                 kw["occ"] = model._occlusion_rows(poses[own].contiguous(), quats[own].contiguous())
             _, scalars, pg_e, qg_e = st.step(poses, quats, flags_extra=stride, **kw)
+            if clr:
+                ops.clearance(model._cloud, poses, model.clearance_radius, model.clearance_weight, grad=clr_rows, terms=clr_terms)
+                check(L.tohip_traj_step_tail_clearance(ptr(poses), ptr(quats), ptr(model.poses0), W, 1, ptr(pg_e), ptr(qg_e), n_eval, step_w,
+                                                       ptr(pg), ptr(qg), ptr(mp), ptr(vp), ptr(mq), ptr(vq), float(model.smoothness_weight),
+                                                       float(model.traj_length_weight), float(model.eps), float(lr_pose), float(lr_quat),
+                                                       betas[0], betas[1], adam_eps, float(rewards_th), float(smoothness_th), ptr(scalars),
+                                                       ptr(loss_terms), 0, ptr(state), float(model.clearance_weight), ptr(clr_rows),
+                                                       ptr(clr_terms), stream_ptr()), "step tail")
+                continue
             check(L.tohip_traj_step_tail(ptr(poses), ptr(quats), ptr(model.poses0), W, ptr(pg_e), ptr(qg_e), n_eval, step_w,
                                          ptr(pg), ptr(qg), ptr(mp), ptr(vp), ptr(mq), ptr(vq), float(model.smoothness_weight),
                                          float(model.traj_length_weight), float(model.eps), float(lr_pose), float(lr_quat),
@@ -176,6 +197,8 @@ def _optimize_trajectory_split(model, n_opt_steps, lr_pose, lr_quat, rewards_th,
     if points:
         model._mean_reward = st.scalars[0].clone()
     model.loss = {"vis": lt_host[-1, 0], "l2": lt_host[-1, 1], "length": lt_host[-1, 2], "smooth": lt_host[-1, 3]}
+    if clr:
+        model.loss["clearance"] = lt_host[-1, 5]
     return TrajOptResult(steps, bool(stt[2].item() != 0), lt_host[:, 4].tolist(), float(stt[4]), float(stt[5]))
 
 
@@ -196,8 +219,10 @@ def optimize_trajectories(models, n_opt_steps=10, lr_pose=0.1, lr_quat=0.0, rewa
         if (m.poses.shape[0] != W or m._wps_step(vis_wps_dist) != step_w or m._cloud.n != cloud.n or m._flags != m0._flags or
                 (m._rig is None) != (rig is None) or m._shard.world_size > 1 or m._occlusion is not None or
                 bytes(m._cam.c) != bytes(cam.c) or m.smoothness_weight != m0.smoothness_weight or
-                m.traj_length_weight != m0.traj_length_weight):
-            raise ValueError("optimize_trajectories: the models must share the cloud, camera, rig, mode, waypoint count and step")
+                m.traj_length_weight != m0.traj_length_weight or m._clearance_on != m0._clearance_on or
+                (m0._clearance_on and (m.clearance_radius != m0.clearance_radius or m.clearance_weight != m0.clearance_weight))):
+            raise ValueError("optimize_trajectories: the models must share the cloud, camera, rig, mode, waypoint count, step and "
+                             "clearance settings")
         if m is not m0 and m.points.data_ptr() != m0.points.data_ptr() and not torch.equal(m.points, m0.points):
             raise ValueError("optimize_trajectories: the models must be built on the same points")
         if m is not m0 and (m.device != m0.device or float(m.eps) != float(m0.eps)):

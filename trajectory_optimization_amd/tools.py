@@ -174,3 +174,19 @@ def xy_yaw_gradient(poses_grad, quats, quats_grad):
     w, x, y, z = q.unbind(-1)
     dq = 0.5 * torch.stack([-z, -y, x, w], dim=-1)
     return torch.cat([gp[..., :2], (gq * dq).sum(-1, keepdim=True)], dim=-1)
+
+
+def trajectory_clearance(points_or_packed_cloud, poses, radius):
+    """How far each waypoint is from the cloud: (d, idx) on the device — d (W,) f32 the distance to the nearest point within
+    `radius` (+inf when none), idx (W,) int32 that point's row in the caller's order (-1 when none; ties go to the lowest row).
+    The query behind ModelTraj's clearance term (clearance_kernels.hip); `points_or_packed_cloud`: (N,3) points on the device, an
+    ops.PackedCloud (sorted or not) or a ModelTraj (its cloud)."""
+    cloud = points_or_packed_cloud
+    if hasattr(cloud, "_cloud") and isinstance(cloud._cloud, ops.PackedCloud):
+        cloud = cloud._cloud
+    if not isinstance(cloud, ops.PackedCloud):
+        cloud = ops.PackedCloud(torch.as_tensor(cloud, dtype=torch.float32))
+    poses = torch.as_tensor(poses, dtype=torch.float32)
+    if poses.device != cloud.device:
+        poses = poses.to(cloud.device)
+    return ops.clearance(cloud, poses, radius)
