@@ -111,19 +111,19 @@ def test_model_refuses_bad_settings_without_a_gpu():
 def test_single_regulariser_gradient_with_the_term_on():
     """A gradient that reaches one regulariser entry alone (no dL/d loss, no dL/d clearance) with the term on: only that term's rows."""
     import torch
-    from trajectory_optimization_amd.model import _assemble_grads_clr
+    from trajectory_optimization_amd.model import _assemble_grads
     W = 5
     reg_sum = torch.full((W, 3), 7.0)
     reg_terms = torch.stack([torch.full((W, 3), float(k + 1)) for k in range(3)])
     clr = torch.ones((W, 3))
     for k in range(3):
         g_terms = tuple(torch.tensor(2.0) if j == k else None for j in range(3))
-        pg, qg = _assemble_grads_clr(1, W, None, None, None, g_terms, None, reg_sum, reg_terms, clr)
+        pg, qg = _assemble_grads(1, W, None, None, None, g_terms, reg_sum, reg_terms, clr, None)
         assert torch.equal(pg, 2.0 * reg_terms[k]) and torch.equal(qg, torch.zeros((W, 4)))
     # dL/d clearance alone, and with dL/d loss
-    pg, _ = _assemble_grads_clr(1, W, None, None, None, (None, None, None), torch.tensor(3.0), reg_sum, reg_terms, clr)
+    pg, _ = _assemble_grads(1, W, None, None, None, (None, None, None), reg_sum, reg_terms, clr, torch.tensor(3.0))
     assert torch.equal(pg, 3.0 * clr)
-    pg, _ = _assemble_grads_clr(1, W, None, None, torch.tensor(1.0), (None, None, None), None, reg_sum, reg_terms, clr)
+    pg, _ = _assemble_grads(1, W, None, None, torch.tensor(1.0), (None, None, None), reg_sum, reg_terms, clr, None)
     assert torch.equal(pg, reg_sum + clr)
 
 

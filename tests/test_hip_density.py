@@ -134,7 +134,7 @@ def test_culling_beyond_one_word_block_of_slots():
     # and as two trajectories in one pass (candidate bits of two rows of 184 words)
     toff = torch.tensor([0, 2, w], dtype=torch.int32, device=dev)
     wsm = ops.TrajWorkspace(cloud, w, 2)
-    m = ops.traj_forward_backward_multi(cloud, p, q, toff, cam, wsm, torch.ones(2, device=dev), flags=0)
+    m = ops.traj_forward_backward(cloud, p, q, cam, wsm, torch.ones(2, device=dev), flags=0, traj_offsets=toff)
     one0 = ops.traj_forward_backward(cloud, p[:2].contiguous(), q[:2].contiguous(), cam, ops.TrajWorkspace(cloud, 2), gout, flags=0)
     one1 = ops.traj_forward_backward(cloud, p[2:].contiguous(), q[2:].contiguous(), cam, ops.TrajWorkspace(cloud, w - 2), gout, flags=0)
     assert torch.equal(m[0][0], one0[0]) and torch.equal(m[0][1], one1[0])          # rewards per trajectory

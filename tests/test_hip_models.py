@@ -705,12 +705,12 @@ def test_several_trajectories_in_one_pass_equal_separate_calls(dev, dense, lens)
     B, W = len(lens), sum(lens)
     ws = ops.TrajWorkspace(cloud, W * 2, B)
     half = torch.empty((B, cloud.n), device=dev)
-    lo, mm = ops.traj_forward_multi(cloud, p_all, q_all, toff, cam, ws, rig=rg, flags=flags, rewards_half=half)
-    rew, sc = ops.traj_reward_multi(cloud, lo, cam, ws, rewards=half, prefilled=True)
+    lo, mm = ops.traj_forward(cloud, p_all, q_all, cam, ws, rig=rg, flags=flags, rewards_half=half, traj_offsets=toff)
+    rew, sc = ops.traj_reward(cloud, lo, cam, ws, rewards=half, prefilled=True)
     gout = torch.tensor([1.0, 0.5, 2.0], device=dev)
-    pg, qg = ops.traj_backward_multi(cloud, W, B, cam, ws, lo, scalars=sc, gout=gout, rig=rg, flags=flags)
+    pg, qg = ops.traj_backward(cloud, W, cam, ws, lo, scalars=sc, gout=gout, rig=rg, flags=flags, n_traj=B)
     g = torch.rand((B, cloud.n), generator=torch.Generator().manual_seed(3)).to(dev) - 0.3
-    pg2, qg2 = ops.traj_backward_multi(cloud, W, B, cam, ws, lo, grad_rewards=g, rig=rg, flags=flags)
+    pg2, qg2 = ops.traj_backward(cloud, W, cam, ws, lo, grad_rewards=g, rig=rg, flags=flags, n_traj=B)
     assert float(rew.max()) > 0.5
     o = 0
     for b, w in enumerate(lens):

@@ -521,7 +521,7 @@ def test_fused_step_of_several_trajectories_equals_single_calls(dev):
     toff = torch.tensor(np.concatenate([[0], np.cumsum(lens)]), dtype=torch.int32, device=dev)
     gout = torch.tensor([1.0, 0.5, 2.0], device=dev)
     ws = ops.TrajWorkspace(cloud, sum(lens), len(lens))
-    rew, sc, pg, qg, lo, mm = ops.traj_forward_backward_multi(cloud, P, Q, toff, cam, ws, gout)
+    rew, sc, pg, qg, lo, mm = ops.traj_forward_backward(cloud, P, Q, cam, ws, gout, traj_offsets=toff)
     o = 0
     for b, n in enumerate(lens):
         ws1 = ops.TrajWorkspace(cloud, n)

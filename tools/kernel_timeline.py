@@ -81,7 +81,7 @@ def main():
     for it in range(16):
         L.tohip_stamps_clear()
         if n_traj > 1:
-            ops.traj_forward_backward_multi(cloud, p, q, toff, cam, ws, gout, flags=flags)
+            ops.traj_forward_backward(cloud, p, q, cam, ws, gout, flags=flags, traj_offsets=toff)
         else:
             ops.traj_forward_backward(cloud, p, q, cam, ws, gout, flags=flags)
         torch.cuda.synchronize()

@@ -55,9 +55,9 @@ for it in range(int(sys.argv[1]) if len(sys.argv) > 1 else 60):
         toff = torch.tensor([0, cut, w], dtype=torch.int32, device=dev)
         V = w * cams
         wsm = ops.TrajWorkspace(cloud, V, 2)
-        lom, mmm = ops.traj_forward_multi(cloud, p, q, toff, cam, wsm, rg)
-        rewm, scm = ops.traj_reward_multi(cloud, lom, cam, wsm)
-        pgm, qgm = ops.traj_backward_multi(cloud, w, 2, cam, wsm, lom, scalars=scm, gout=torch.ones(2, device=dev), rig=rg)
+        lom, mmm = ops.traj_forward(cloud, p, q, cam, wsm, rg, traj_offsets=toff)
+        rewm, scm = ops.traj_reward(cloud, lom, cam, wsm)
+        pgm, qgm = ops.traj_backward(cloud, w, cam, wsm, lom, scalars=scm, gout=torch.ones(2, device=dev), rig=rg, n_traj=2)
         for k, (lo_, hi_) in enumerate(((0, cut), (cut, w))):
             s = one(cloud, p[lo_:hi_].contiguous(), q[lo_:hi_].contiguous(), cam, rg, 0, None, g)
             ok &= same(s[0], lom[k, :cloud.n]) and same(s[2], rewm[k]) and same(s[3], scm[k, :2]) and same(s[4], pgm[lo_:hi_]) and same(s[5], qgm[lo_:hi_])

@@ -285,5 +285,20 @@ def stream_ptr():
     return c_vp(torch.cuda.current_stream().cuda_stream)
 
 
+def device_index(device):
+    """A HIP device's index ('cuda' alone: the current device's), resolved once where a plan is built."""
+    device = torch.device(device)
+    return device.index if device.index is not None else torch.cuda.current_device()
+
+
+def on_device(index, fn, *args):
+    """fn(*args, stream) with `stream` the raw current stream of device `index`.  torch.cuda.device(index) is entered only when
+    `index` is not the current device: the host-bound paths, whose device is current, pay no context manager."""
+    if torch._C._cuda_getDevice() == index:
+        return fn(*args, torch._C._cuda_getCurrentRawStream(index))
+    with torch.cuda.device(index):
+        return fn(*args, torch._C._cuda_getCurrentRawStream(index))
+
+
 def ptr(t):
     return c_vp(t.data_ptr()) if t is not None else c_vp(0)

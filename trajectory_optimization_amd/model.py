@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from . import _lib, ops
 from ._lib import check, ptr, stream_ptr
-from .optimizer import accelerate_torch_adam, tag_parameter
+from .optimizer import _refresh_age, accelerate_torch_adam, tag_parameter
 from .tools import hidden_pts_removal
 
 
@@ -217,19 +217,22 @@ def _regularizers(model, p_all, scalars, clr_terms=None):
     reg_terms = torch.empty((3, W, 3), dtype=torch.float32, device=dev)
     args = (ptr(p_all), ptr(model.poses0), W, float(model.smoothness_weight), float(model.traj_length_weight), float(model.eps),
             ptr(scalars), ptr(terms), ptr(reg_sum), 0, None, ptr(reg_terms))
+    if clr_terms is None:
+        name, extra = "tohip_traj_regularizers", ()
+    else:
+        name, extra = "tohip_traj_regularizers_clearance", (float(model.clearance_weight), ptr(clr_terms))
     with torch.cuda.device(dev):
-        if clr_terms is None:
-            check(_lib.lib().tohip_traj_regularizers(*args, stream_ptr()), "tohip_traj_regularizers")
-        else:
-            check(_lib.lib().tohip_traj_regularizers_clearance(*args, float(model.clearance_weight), ptr(clr_terms), stream_ptr()),
-                  "tohip_traj_regularizers_clearance")
+        check(getattr(_lib.lib(), name)(*args, *extra, stream_ptr()), name)
     return terms, reg_sum, reg_terms
 
 
-def _assemble_grads(step_w, W, pg_e, qg_e, g_loss, g_terms, reg_sum, reg_terms):
+def _assemble_grads(step_w, W, pg_e, qg_e, g_loss, g_terms, reg_sum, reg_terms, clr_rows=None, g_clr=None):
     """(W,3) / (W,4) gradients: the evaluated rows pg_e, qg_e (every step_w-th waypoint; None when the visibility term carries no
     gradient) plus the regularisers' share.  g_terms = (g_l2, g_length, g_smooth): upstream gradients of the single entries of
-    model.loss, or all None."""
+    model.loss, or all None.  clr_rows: the clearance term's gradient rows (None: the term is off), g_clr the upstream gradient of
+    its entry.  dL/d loss alone: vis + g_loss (regularisers + clearance), the order of the one-call step (tohip_traj_opt_step)."""
+    if clr_rows is not None and g_clr is None and all(g is None for g in g_terms):
+        reg_sum, clr_rows = reg_sum + clr_rows, None
     grads = torch.zeros((W, 7), dtype=torch.float32, device=reg_sum.device)
     if pg_e is not None:
         rows = slice(0, (pg_e.shape[0] - 1) * step_w + 1, step_w)
@@ -243,22 +246,11 @@ def _assemble_grads(step_w, W, pg_e, qg_e, g_loss, g_terms, reg_sum, reg_terms):
             c = g_loss if g is None else (g.to(torch.float32) if g_loss is None else g_loss + g.to(torch.float32))
             if c is not None:
                 pg_all = pg_all + c * reg_terms[k]
+    if clr_rows is not None:
+        c = g_loss if g_clr is None else (g_clr.to(torch.float32) if g_loss is None else g_loss + g_clr.to(torch.float32))
+        if c is not None:
+            pg_all = pg_all + c * clr_rows
     return pg_all.contiguous(), qg_all.contiguous()
-
-
-def _assemble_grads_clr(step_w, W, pg_e, qg_e, g_loss, g_terms, g_clr, reg_sum, reg_terms, clr_rows):
-    """_assemble_grads with the clearance term's rows (None: the term is off).  dL/d loss alone: vis + g_loss (regularisers +
-    clearance), the order of the one-call step (tohip_traj_opt_step)."""
-    if clr_rows is None:
-        return _assemble_grads(step_w, W, pg_e, qg_e, g_loss, g_terms, reg_sum, reg_terms)
-    if g_clr is None and all(g is None for g in g_terms):
-        return _assemble_grads(step_w, W, pg_e, qg_e, g_loss, g_terms, reg_sum + clr_rows, reg_terms)
-    pg, qg = _assemble_grads(step_w, W, pg_e, qg_e, g_loss, g_terms, reg_sum, reg_terms)
-    g_clr = _f32(g_clr)
-    c = g_loss if g_clr is None else (g_clr if g_loss is None else g_loss + g_clr)
-    if c is not None:
-        pg = pg + c * clr_rows
-    return pg.contiguous(), qg
 
 
 class _Clearance(torch.autograd.Function):
@@ -364,8 +356,7 @@ class _TrajLoss(torch.autograd.Function):
             ps, qs, lo_sum, scalars = saved
             upstream = _vis_upstream(g_loss, g_vis, g_rewards, scalars) if st.hi > st.lo else None
             pg_e, qg_e = st.backward(ps, qs, ctx.occ, ctx.gen, lo_sum, upstream)
-        pg, qg = _assemble_grads_clr(ctx.step_w, ctx.W, pg_e, qg_e, g_loss, (g_l2, g_length, g_smooth), g_clr, reg_sum, reg_terms,
-                                     clr_rows)
+        pg, qg = _assemble_grads(ctx.step_w, ctx.W, pg_e, qg_e, g_loss, (g_l2, g_length, g_smooth), reg_sum, reg_terms, clr_rows, g_clr)
         return pg, qg, None, None
 
 
@@ -414,22 +405,15 @@ class _LossPlan:
         self.model = model
         self.fwd, self.bwd, self.refresh = L.tohip_traj_loss_forward, L.tohip_traj_loss_backward, L.tohip_traj_loss_refresh
         self.sums_stale = False   # True: a general backward (tohip_traj_backward) has overwritten the unit-gradient pair sums
-        self.dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
+        self.dev_index = _lib.device_index(dev)
         self.dev = dev
         self.f32 = dict(dtype=torch.float32, device=dev)
         self.one = torch.ones((), **self.f32)   # dL/d loss of a plain loss.backward()
 
     def forward(self, poses, quats, rewards, terms):
-        idx = self.dev_index
         self.ws.generation += 1
         self.sums_stale = False
-        if torch.cuda.current_device() == idx:
-            rc = self.fwd(self.ref, poses.data_ptr(), quats.data_ptr(), rewards.data_ptr(), terms.data_ptr(),
-                          torch._C._cuda_getCurrentRawStream(idx))
-        else:
-            with torch.cuda.device(idx):
-                rc = self.fwd(self.ref, poses.data_ptr(), quats.data_ptr(), rewards.data_ptr(), terms.data_ptr(),
-                              torch._C._cuda_getCurrentRawStream(idx))
+        rc = _lib.on_device(self.dev_index, self.fwd, self.ref, poses.data_ptr(), quats.data_ptr(), rewards.data_ptr(), terms.data_ptr())
         if rc:
             check(rc, "tohip_traj_loss_forward")
         return self.ws.generation
@@ -443,30 +427,16 @@ class _LossPlan:
         return self.forward(poses, quats, torch.empty(self.n, **self.f32), torch.empty(8, **self.f32))
 
     def backward(self, gout, pg, qg):
-        idx = self.dev_index
-        with torch.cuda.device(idx) if torch.cuda.current_device() != idx else _NOOP:
-            stream = torch._C._cuda_getCurrentRawStream(idx)
-            if self.sums_stale:
-                # a backward through model.rewards / single loss terms of this step ran before: it left ITS sums (scaled by its
-                # upstream gradient) where this one expects the unit-gradient ones — take them again (same pairs, same bits)
-                rc = self.refresh(self.ref, stream)
-                if rc:
-                    check(rc, "tohip_traj_loss_refresh")
-                self.sums_stale = False
-            rc = self.bwd(self.ref, gout.data_ptr(), pg.data_ptr(), qg.data_ptr(), stream)
+        if self.sums_stale:
+            # a backward through model.rewards / single loss terms of this step ran before: it left ITS sums (scaled by its
+            # upstream gradient) where this one expects the unit-gradient ones — take them again (same pairs, same bits)
+            rc = _lib.on_device(self.dev_index, self.refresh, self.ref)
+            if rc:
+                check(rc, "tohip_traj_loss_refresh")
+            self.sums_stale = False
+        rc = _lib.on_device(self.dev_index, self.bwd, self.ref, gout.data_ptr(), pg.data_ptr(), qg.data_ptr())
         if rc:
             check(rc, "tohip_traj_loss_backward")
-
-
-class _Noop:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
-_NOOP = _Noop()
 
 
 class _FastBackward:
@@ -548,37 +518,31 @@ class _PosePlan:
         self.cam = model._cam.ref()
         self.ws, self.wsb = model._ws.buf.data_ptr(), model._ws.bytes
         dev = model.device
-        self.dev, self.dev_index = dev, (dev.index if dev.index is not None else torch.cuda.current_device())
+        self.dev, self.dev_index = dev, _lib.device_index(dev)
         self.f32 = dict(dtype=torch.float32, device=dev)
         self.one = torch.ones(1, **self.f32)
         self.model = model
 
-    def _call(self, fn, *args):
-        idx = self.dev_index
-        if torch.cuda.current_device() == idx:
-            return fn(*args, self.ws, self.wsb, torch._C._cuda_getCurrentRawStream(idx))
-        with torch.cuda.device(idx):
-            return fn(*args, self.ws, self.wsb, torch._C._cuda_getCurrentRawStream(idx))
-
     def forward(self, t, q, mask, obs, scalars, occ=None):
         fn, m = (self.fwd_occ, occ) if occ is not None else (self.fwd, mask)
-        rc = self._call(fn, self.blob, self.n, t.data_ptr(), q.data_ptr(), self.cam, m.data_ptr() if m is not None else None,
-                        obs.data_ptr(), scalars.data_ptr())
+        rc = _lib.on_device(self.dev_index, fn, self.blob, self.n, t.data_ptr(), q.data_ptr(), self.cam,
+                            m.data_ptr() if m is not None else None, obs.data_ptr(), scalars.data_ptr(), self.ws, self.wsb)
         if rc:
             check(rc, "tohip_pose_forward_bits" if occ is not None else "tohip_pose_forward")
 
     def forward_backward(self, t, q, mask, obs, scalars, grads, occ=None):
         gp = grads.data_ptr()
         fn, m = (self.fwdbwd_occ, occ) if occ is not None else (self.fwdbwd, mask)
-        rc = self._call(fn, self.blob, self.n, t.data_ptr(), q.data_ptr(), self.cam, m.data_ptr() if m is not None else None,
-                        obs.data_ptr(), scalars.data_ptr(), None, gp, gp + 16)
+        rc = _lib.on_device(self.dev_index, fn, self.blob, self.n, t.data_ptr(), q.data_ptr(), self.cam,
+                            m.data_ptr() if m is not None else None, obs.data_ptr(), scalars.data_ptr(), None, gp, gp + 16, self.ws, self.wsb)
         if rc:
             check(rc, "tohip_pose_forward_backward_bits" if occ is not None else "tohip_pose_forward_backward")
 
     def backward(self, t, q, mask, scalars, gout, tg, qg, occ=None):
         fn, m = (self.bwd_occ, occ) if occ is not None else (self.bwd, mask)
-        rc = self._call(fn, self.blob, self.n, t.data_ptr(), q.data_ptr(), self.cam, m.data_ptr() if m is not None else None, None,
-                        scalars.data_ptr(), gout.data_ptr(), tg.data_ptr(), qg.data_ptr())
+        rc = _lib.on_device(self.dev_index, fn, self.blob, self.n, t.data_ptr(), q.data_ptr(), self.cam,
+                            m.data_ptr() if m is not None else None, None, scalars.data_ptr(), gout.data_ptr(), tg.data_ptr(),
+                            qg.data_ptr(), self.ws, self.wsb)
         if rc:
             check(rc, "tohip_pose_backward_bits" if occ is not None else "tohip_pose_backward")
 
@@ -646,12 +610,37 @@ class _TrajLossPlan(torch.autograd.Function):
         if kw is not None:
             pg, qg = ops.traj_backward(m._cloud, plan.n_eval, m._cam, plan.ws, plan.lo_sum, rig=m._rig, flags=m._flags, **kw)
             plan.sums_stale = True   # the pair sums in the workspace are now scaled by THIS upstream gradient
-        pg_all, qg_all = _assemble_grads_clr(plan.step_w, plan.W, pg, qg, g_loss, (g_l2, g_length, g_smooth), g_clr, plan.reg_sum,
-                                             plan.reg_terms, plan.clr_rows)
+        pg_all, qg_all = _assemble_grads(plan.step_w, plan.W, pg, qg, g_loss, (g_l2, g_length, g_smooth), plan.reg_sum, plan.reg_terms,
+                                         plan.clr_rows, g_clr)
         return pg_all, qg_all, None
 
 
 # ------------------------------------------------------------------------------ models
+
+def _adopt_cloud(points, cloud, device, sort, model_cls):
+    """The packed cloud a model's constructor adopts: `points` may be an ops.PackedCloud, or `cloud=` names one (or a model of
+    `model_cls` whose cloud to share), packed with sort=`sort` on `device`.  -> (the cloud, its points), or (None, points) when there
+    is none to adopt."""
+    if isinstance(points, ops.PackedCloud):
+        cloud, points = points, None
+    if isinstance(cloud, model_cls):
+        cloud = cloud._cloud
+    if cloud is None:
+        return None, points
+    if not isinstance(cloud, ops.PackedCloud) or cloud.sorted != sort:
+        order = "Morton order (sort=True)" if sort else "the caller's order (sort=False)"
+        raise ValueError(f"cloud= must be an ops.PackedCloud in {order} or a {model_cls.__name__}")
+    if cloud.device != torch.device(device.type, _lib.device_index(device)):
+        raise ValueError(f"the packed cloud lives on {cloud.device}, the model on {device}")
+    if points is not None and not (torch.is_tensor(points) and points.data_ptr() == cloud.points.data_ptr() and
+                                   tuple(points.shape) == tuple(cloud.points.shape) and points.stride() == cloud.points.stride()):
+        # a different tensor object: it must hold the packed cloud's rows (an equal-sized OTHER cloud would silently be replaced by
+        # cloud.points otherwise); the comparison is one pass over the rows, paid only by callers who hand both
+        pt = torch.as_tensor(points, dtype=torch.float32)
+        if tuple(pt.shape) != tuple(cloud.points.shape) or not torch.equal(pt.to(cloud.points.device), cloud.points):
+            raise ValueError("cloud= does not hold these points")
+    return cloud, cloud.points
+
 
 class ModelPose(nn.Module):
     """Single camera pose optimisation model (/root/reference/src/model.py:65-127).
@@ -679,28 +668,12 @@ class ModelPose(nn.Module):
         assert intrins.size() == torch.Size([3, 3])
 
         self.device = torch.device(device)
-        # One packed cloud for several poses (many starts of one camera, optimizer.optimize_poses): `points` may be an
-        # ops.PackedCloud, or `cloud=` names one (or a ModelPose whose cloud to share).  The pose path keeps the caller's order, so
-        # only an unsorted cloud (sort=False) will do: another order would change the sums.
-        if isinstance(points, ops.PackedCloud):
-            cloud, points = points, None
-        if isinstance(cloud, ModelPose):
-            cloud = cloud._cloud
-        if cloud is not None:
-            if not isinstance(cloud, ops.PackedCloud) or cloud.sorted:
-                raise ValueError("cloud= must be an ops.PackedCloud in the caller's order (sort=False) or a ModelPose")
-            if cloud.device != (self.device if self.device.index is not None else torch.device(self.device.type, torch.cuda.current_device())):
-                raise ValueError(f"the packed cloud lives on {cloud.device}, the model on {self.device}")
-            if points is not None and not (torch.is_tensor(points) and points.data_ptr() == cloud.points.data_ptr() and
-                                           tuple(points.shape) == tuple(cloud.points.shape) and points.stride() == cloud.points.stride()):
-                pt = torch.as_tensor(points, dtype=torch.float32)
-                if tuple(pt.shape) != tuple(cloud.points.shape) or not torch.equal(pt.to(cloud.points.device), cloud.points):
-                    raise ValueError("cloud= does not hold these points")
-            self.points = cloud.points
-        else:
-            # the reference keeps the caller's dtype (model.py:80) and then fails in get_fov_mask's matmul
-            # for anything but float32; float32 is the contract here
-            self.points = torch.as_tensor(points, dtype=torch.float32).to(self.device)
+        # One packed cloud for several poses (many starts of one camera, optimizer.optimize_poses).  The pose path keeps the caller's
+        # order, so only an unsorted cloud (sort=False) will do: another order would change the sums.
+        cloud, points = _adopt_cloud(points, cloud, self.device, False, ModelPose)
+        # the reference keeps the caller's dtype (model.py:80) and then fails in get_fov_mask's matmul
+        # for anything but float32; float32 is the contract here
+        self.points = points if cloud is not None else torch.as_tensor(points, dtype=torch.float32).to(self.device)
         self.rewards = None
         self.observations = None
         self.lo_sum = 0.0
@@ -758,13 +731,14 @@ class ModelPose(nn.Module):
         """The pose's occlusion bit row for this forward: rebuilt from the current pose on every occlusion_refresh_every-th call,
         reused otherwise."""
         c = self._occ_cache
-        if c is None or c[1] >= self.occlusion_refresh_every:
+        age = _refresh_age(c[1] if c is not None else None, self.occlusion_refresh_every)
+        if age == 1:
             row = self._build_occlusion_rows(self.trans.detach().contiguous(), self.quat.detach().contiguous())
             self.occlusion_rebuilds += 1
-            self._occ_cache = (row, 1)
-            return row
-        self._occ_cache = (c[0], c[1] + 1)
-        return c[0]
+        else:
+            row = c[0]
+        self._occ_cache = (row, age)
+        return row
 
     def _adopt_occlusion_row(self, row, age, rebuilds):
         """What a launch-only loop (optimizer.optimize_pose / optimize_poses) leaves in the cache: its last row, the number of steps
@@ -868,26 +842,12 @@ class ModelTraj(nn.Module):
         self._n_global = None
         # One packed cloud for many models: the reference builds a model per (cloud, path) message pair over the same map
         # (/root/reference/src/trajectory_optimization.py:129-136); packing — bounding box, Morton sort, tile bounds — costs several
-        # optimiser steps and 20 B/point.  `points` may be an ops.PackedCloud, or `cloud=` names one (or a ModelTraj whose cloud to share).
-        if isinstance(points, ops.PackedCloud):
-            cloud, points = points, None
-        if isinstance(cloud, ModelTraj):
-            cloud = cloud._cloud
+        # optimiser steps and 20 B/point.
+        cloud, points = _adopt_cloud(points, cloud, self.device, True, ModelTraj)
         if cloud is not None:
-            if not isinstance(cloud, ops.PackedCloud) or not cloud.sorted:
-                raise ValueError("cloud= must be an ops.PackedCloud in Morton order (sort=True) or a ModelTraj")
             if shard is not None and shard.kind == "points":
                 raise ValueError("a shared packed cloud holds the whole cloud: not available with PointShard")
-            if cloud.device != (self.device if self.device.index is not None else torch.device(self.device.type, torch.cuda.current_device())):
-                raise ValueError(f"the packed cloud lives on {cloud.device}, the model on {self.device}")
-            if points is not None and not (torch.is_tensor(points) and points.data_ptr() == cloud.points.data_ptr() and
-                                           tuple(points.shape) == tuple(cloud.points.shape) and points.stride() == cloud.points.stride()):
-                # a different tensor object: it must hold the packed cloud's rows (an equal-sized OTHER cloud would silently be
-                # replaced by cloud.points otherwise); the comparison is one pass over the rows, paid only by callers who hand both
-                pt = torch.as_tensor(points, dtype=torch.float32)
-                if tuple(pt.shape) != tuple(cloud.points.shape) or not torch.equal(pt.to(cloud.points.device), cloud.points):
-                    raise ValueError("cloud= does not hold these points")
-            self.points = cloud.points
+            self.points = points
         elif shard is not None and shard.kind == "points":
             # point sharding: this rank keeps its own rows of the cloud (the whole cloud is handed in, or — n_points_global — the
             # rows already); model.rewards are those rows' rewards
@@ -1036,15 +996,17 @@ class ModelTraj(nn.Module):
         moved (see the constructor); reused otherwise."""
         key = (tuple(ps.shape), tuple(qs.shape))
         c = self._occ_cache
-        if c is None or c[1] != key or c[2] >= self.occlusion_refresh_every or (self.occlusion_refresh_tol is not None and self._occ_built is None):
+        kept = c is not None and c[1] == key and (self.occlusion_refresh_tol is None or self._occ_built is not None)
+        age = _refresh_age(c[2] if kept else None, self.occlusion_refresh_every)
+        if age == 1:
             rows = self._build_occlusion_rows(ps, qs)
             self._occ_cache = (rows, key, 1)
             self.occlusion_rebuilds[0] += 1
             if self.occlusion_refresh_tol is not None:
                 self._occ_built = (ps.clone(), torch.nn.functional.normalize(qs, dim=1))
             return rows
-        rows, age = c[0], c[2]
-        if self.occlusion_refresh_tol is not None and age % self.occlusion_check_every == 0:
+        rows = c[0]
+        if self.occlusion_refresh_tol is not None and c[2] % self.occlusion_check_every == 0:
             tol_p, tol_q = self.occlusion_refresh_tol
             bp, bq = self._occ_built
             qn = torch.nn.functional.normalize(qs, dim=1)
@@ -1059,7 +1021,7 @@ class ModelTraj(nn.Module):
                 rows[vidx] = new
                 bp[idx], bq[idx] = ps[idx], qn[idx]
                 self.occlusion_rebuilds[1] += int(idx.numel())
-        self._occ_cache = (rows, key, age + 1)
+        self._occ_cache = (rows, key, age)
         return rows
 
     def _build_occlusion_rows(self, ps, qs):

@@ -105,47 +105,54 @@ class TrajWorkspace:
 DENSE = 1  # TOHIP_TRAJ_DENSE
 
 
-def traj_forward(cloud, poses, quats, cam, ws, rig=None, flags=0, occ=None, lo_sum=None, minmax=None, rewards_half=None):
+def traj_forward(cloud, poses, quats, cam, ws, rig=None, flags=0, occ=None, lo_sum=None, minmax=None, rewards_half=None,
+                 traj_offsets=None):
     """-> (lo_sum[npad] in packed order (first N valid), minmax[V,2]) for the given waypoints (this rank's shard).
     Leaves the step's state in `ws` for traj_backward.  rewards_half: optional (N,) f32 tensor filled with 0.5 on the way
-    (hand it to traj_reward as `rewards=` with prefilled=True)."""
+    (hand it to traj_reward as `rewards=` with prefilled=True).
+    traj_offsets: several trajectories over one cloud in one pass — `poses` (W,3) / `quats` (W,4) hold their waypoints end to end,
+    `traj_offsets` (B+1 int32 on the device) where each starts; lo_sum is then (B, npad) and ws = TrajWorkspace(cloud, V, B)."""
     W = poses.shape[0]
     C = rig.n_cams if rig is not None else 1
-    if lo_sum is None:
-        lo_sum = torch.empty(cloud.npad, dtype=torch.float32, device=cloud.device)
+    B = traj_offsets.numel() - 1 if traj_offsets is not None else 1
+    if lo_sum is None:   # one trajectory: (npad,); the trajectories of traj_offsets: (B, npad)
+        lo_sum = torch.empty((B, cloud.npad) if traj_offsets is not None else cloud.npad, dtype=torch.float32, device=cloud.device)
     if minmax is None:
         minmax = torch.empty((W * C, 2), dtype=torch.float32, device=cloud.device)
     ws.generation += 1
     with torch.cuda.device(cloud.device):
-        check(_lib.lib().tohip_traj_forward(ptr(cloud.blob), cloud.n, ptr(poses), ptr(quats), W, cam.ref(),
-                                            rig.ref() if rig is not None else _NULL_RIG, int(flags), ptr(occ), ptr(lo_sum), ptr(minmax),
-                                            ptr(rewards_half), ptr(ws.buf), ws.bytes, stream_ptr()), "tohip_traj_forward")
+        check(_lib.lib().tohip_traj_forward_multi(ptr(cloud.blob), cloud.n, ptr(poses), ptr(quats), W, ptr(traj_offsets), B, cam.ref(),
+                                                  rig.ref() if rig is not None else _NULL_RIG, int(flags), ptr(occ), ptr(lo_sum), ptr(minmax),
+                                                  ptr(rewards_half), ptr(ws.buf), ws.bytes, stream_ptr()), "tohip_traj_forward_multi")
     return lo_sum, minmax
 
 
 def traj_reward(cloud, lo_sum, cam, ws, rewards=None, scalars=None, prefilled=False):
     """-> (rewards[N], scalars[4] = mean, loss_vis, dloss/dreward, -).  prefilled: `rewards` holds 0.5 everywhere (traj_forward's
-    rewards_half): only the others are stored."""
+    rewards_half): only the others are stored.  A (B, npad) lo_sum (traj_forward with traj_offsets): rewards (B,N), scalars (B,4)."""
+    lead = tuple(lo_sum.shape[:-1])
     if rewards is None:
-        rewards = torch.empty(cloud.n, dtype=torch.float32, device=cloud.device)
+        rewards = torch.empty((*lead, cloud.n), dtype=torch.float32, device=cloud.device)
     if scalars is None:
-        scalars = torch.empty(4, dtype=torch.float32, device=cloud.device)  # all four written by the kernel
+        scalars = torch.empty((*lead, 4), dtype=torch.float32, device=cloud.device)  # all four written by the kernel
     with torch.cuda.device(cloud.device):
-        check(_lib.lib().tohip_traj_reward(ptr(cloud.blob), ptr(lo_sum), cloud.n, cam.eps, int(bool(prefilled)), ptr(rewards), ptr(scalars),
-                                           ptr(ws.buf), ws.bytes, stream_ptr()), "tohip_traj_reward")
+        check(_lib.lib().tohip_traj_reward_multi(ptr(cloud.blob), ptr(lo_sum), cloud.n, lead[0] if lead else 1, cam.eps,
+                                                 int(bool(prefilled)), ptr(rewards), ptr(scalars), ptr(ws.buf), ws.bytes, stream_ptr()),
+              "tohip_traj_reward_multi")
     return rewards, scalars
 
 
-def traj_backward(cloud, n_wps, cam, ws, lo_sum, grad_rewards=None, scalars=None, gout=None, rig=None, flags=0, occ=None):
+def traj_backward(cloud, n_wps, cam, ws, lo_sum, grad_rewards=None, scalars=None, gout=None, rig=None, flags=0, occ=None, n_traj=1):
     """Gradients of the step whose traj_forward last used `ws` (same cloud, n_wps, rig, flags, occ).
-    lo_sum: the (all-reduced) log-odds vector in packed order, as returned by traj_forward."""
+    lo_sum: the (all-reduced) log-odds vector in packed order, as returned by traj_forward.  n_traj: the number of trajectories of
+    traj_forward's traj_offsets (gout: (B,) dL/d loss_vis per trajectory); the gradients are (n_wps,3), (n_wps,4) of all of them."""
     pg = torch.empty((n_wps, 3), dtype=torch.float32, device=cloud.device)
     qg = torch.empty((n_wps, 4), dtype=torch.float32, device=cloud.device)
     with torch.cuda.device(cloud.device):
-        check(_lib.lib().tohip_traj_backward(ptr(cloud.blob), cloud.n, n_wps, cam.ref(),
-                                             rig.ref() if rig is not None else _NULL_RIG, int(flags), ptr(occ), ptr(lo_sum),
-                                             ptr(grad_rewards), ptr(scalars), ptr(gout), ptr(pg), ptr(qg), ptr(ws.buf), ws.bytes,
-                                             stream_ptr()), "tohip_traj_backward")
+        check(_lib.lib().tohip_traj_backward_multi(ptr(cloud.blob), cloud.n, n_wps, n_traj, cam.ref(),
+                                                   rig.ref() if rig is not None else _NULL_RIG, int(flags), ptr(occ), ptr(lo_sum),
+                                                   ptr(grad_rewards), ptr(scalars), ptr(gout), ptr(pg), ptr(qg), ptr(ws.buf), ws.bytes,
+                                                   stream_ptr()), "tohip_traj_backward_multi")
     return pg, qg
 
 
@@ -165,110 +172,33 @@ def traj_reward_backward(cloud, n_wps, cam, ws, lo_sum, gout, rewards=None, pref
     return rewards, scalars, pg, qg
 
 
-def traj_forward_backward(cloud, poses, quats, cam, ws, gout, rig=None, flags=0, occ=None, lo_sum=None, minmax=None, rewards=None):
+def traj_forward_backward(cloud, poses, quats, cam, ws, gout, rig=None, flags=0, occ=None, lo_sum=None, minmax=None, rewards=None,
+                          traj_offsets=None):
     """The whole step of the fused visibility loss when no collective sits between forward and backward (tohip_traj_forward_backward,
-    five launches).  -> (rewards[N], scalars[4], poses_grad (W,3), quats_grad (W,4), lo_sum[npad] packed order, minmax[V,2])."""
+    five launches).  -> (rewards[N], scalars[4], poses_grad (W,3), quats_grad (W,4), lo_sum[npad] packed order, minmax[V,2]).
+    traj_offsets: B trajectories laid end to end (traj_forward's layout; gout: (B,) dL/d loss_vis each): rewards (B,N),
+    scalars (B,4), lo_sum (B,npad)."""
     W = poses.shape[0]
     C = rig.n_cams if rig is not None else 1
+    B = traj_offsets.numel() - 1 if traj_offsets is not None else 1
+    lead = (B,) if traj_offsets is not None else ()   # the per-trajectory outputs' leading shape
     dev = cloud.device
     if lo_sum is None:
-        lo_sum = torch.empty(cloud.npad, dtype=torch.float32, device=dev)
+        lo_sum = torch.empty((*lead, cloud.npad), dtype=torch.float32, device=dev)
     if minmax is None:
         minmax = torch.empty((W * C, 2), dtype=torch.float32, device=dev)
     if rewards is None:
-        rewards = torch.empty(cloud.n, dtype=torch.float32, device=dev)
-    scalars = torch.empty(4, dtype=torch.float32, device=dev)
-    pg = torch.empty((W, 3), dtype=torch.float32, device=dev)
-    qg = torch.empty((W, 4), dtype=torch.float32, device=dev)
-    ws.generation += 1
-    with torch.cuda.device(dev):
-        check(_lib.lib().tohip_traj_forward_backward(ptr(cloud.blob), cloud.n, ptr(poses), ptr(quats), W, cam.ref(),
-                                                     rig.ref() if rig is not None else _NULL_RIG, int(flags), ptr(occ), ptr(lo_sum), ptr(minmax),
-                                                     ptr(rewards), ptr(scalars), ptr(gout), ptr(pg), ptr(qg), ptr(ws.buf), ws.bytes, stream_ptr()),
-              "tohip_traj_forward_backward")
-    return rewards, scalars, pg, qg, lo_sum, minmax
-
-
-def traj_forward_backward_multi(cloud, poses, quats, traj_offsets, cam, ws, gout, rig=None, flags=0, lo_sum=None, minmax=None, rewards=None):
-    """traj_forward_backward for B trajectories laid end to end (traj_forward_multi's layout; gout: (B,) dL/d loss_vis each).
-    -> (rewards (B,N), scalars (B,4), poses_grad (W,3), quats_grad (W,4), lo_sum (B,npad), minmax (V,2))."""
-    W, B = poses.shape[0], traj_offsets.numel() - 1
-    C = rig.n_cams if rig is not None else 1
-    dev = cloud.device
-    if lo_sum is None:
-        lo_sum = torch.empty((B, cloud.npad), dtype=torch.float32, device=dev)
-    if minmax is None:
-        minmax = torch.empty((W * C, 2), dtype=torch.float32, device=dev)
-    if rewards is None:
-        rewards = torch.empty((B, cloud.n), dtype=torch.float32, device=dev)
-    scalars = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        rewards = torch.empty((*lead, cloud.n), dtype=torch.float32, device=dev)
+    scalars = torch.empty((*lead, 4), dtype=torch.float32, device=dev)
     pg = torch.empty((W, 3), dtype=torch.float32, device=dev)
     qg = torch.empty((W, 4), dtype=torch.float32, device=dev)
     ws.generation += 1
     with torch.cuda.device(dev):
         check(_lib.lib().tohip_traj_forward_backward_multi(ptr(cloud.blob), cloud.n, ptr(poses), ptr(quats), W, ptr(traj_offsets), B, cam.ref(),
-                                                           rig.ref() if rig is not None else _NULL_RIG, int(flags), None, ptr(lo_sum), ptr(minmax),
-                                                           ptr(rewards), ptr(scalars), ptr(gout), ptr(pg), ptr(qg), ptr(ws.buf), ws.bytes,
-                                                           stream_ptr()), "tohip_traj_forward_backward_multi")
+                                                           rig.ref() if rig is not None else _NULL_RIG, int(flags), ptr(occ), ptr(lo_sum),
+                                                           ptr(minmax), ptr(rewards), ptr(scalars), ptr(gout), ptr(pg), ptr(qg), ptr(ws.buf),
+                                                           ws.bytes, stream_ptr()), "tohip_traj_forward_backward_multi")
     return rewards, scalars, pg, qg, lo_sum, minmax
-
-
-def traj_reward_backward_multi(cloud, n_wps, n_traj, cam, ws, lo_sum, gout, rewards=None, prefilled=False, rig=None, flags=0):
-    """-> (rewards (B,N), scalars (B,4), poses_grad (W,3), quats_grad (W,4)) of B trajectories (traj_forward_multi's lo_sum)."""
-    if rewards is None:
-        rewards = torch.empty((n_traj, cloud.n), dtype=torch.float32, device=cloud.device)
-    scalars = torch.empty((n_traj, 4), dtype=torch.float32, device=cloud.device)
-    pg = torch.empty((n_wps, 3), dtype=torch.float32, device=cloud.device)
-    qg = torch.empty((n_wps, 4), dtype=torch.float32, device=cloud.device)
-    with torch.cuda.device(cloud.device):
-        check(_lib.lib().tohip_traj_reward_backward_multi(ptr(cloud.blob), cloud.n, n_wps, n_traj, cam.ref(),
-                                                          rig.ref() if rig is not None else _NULL_RIG, int(flags), None, ptr(lo_sum),
-                                                          cam.eps, int(bool(prefilled)), ptr(rewards), ptr(scalars), ptr(gout), ptr(pg),
-                                                          ptr(qg), ptr(ws.buf), ws.bytes, stream_ptr()),
-              "tohip_traj_reward_backward_multi")
-    return rewards, scalars, pg, qg
-
-
-def traj_forward_multi(cloud, poses, quats, traj_offsets, cam, ws, rig=None, flags=0, lo_sum=None, minmax=None, rewards_half=None):
-    """Several trajectories over one cloud in one pass: `poses` (W,3) / `quats` (W,4) hold their waypoints end to end,
-    `traj_offsets` (B+1 int32 on the device) where each starts.  -> (lo_sum (B, npad), minmax (V, 2)); ws = TrajWorkspace(cloud, V, B)."""
-    W, B = poses.shape[0], traj_offsets.numel() - 1
-    C = rig.n_cams if rig is not None else 1
-    if lo_sum is None:
-        lo_sum = torch.empty((B, cloud.npad), dtype=torch.float32, device=cloud.device)
-    if minmax is None:
-        minmax = torch.empty((W * C, 2), dtype=torch.float32, device=cloud.device)
-    ws.generation += 1
-    with torch.cuda.device(cloud.device):
-        check(_lib.lib().tohip_traj_forward_multi(ptr(cloud.blob), cloud.n, ptr(poses), ptr(quats), W, ptr(traj_offsets), B, cam.ref(),
-                                                  rig.ref() if rig is not None else _NULL_RIG, int(flags), None, ptr(lo_sum), ptr(minmax),
-                                                  ptr(rewards_half), ptr(ws.buf), ws.bytes, stream_ptr()), "tohip_traj_forward_multi")
-    return lo_sum, minmax
-
-
-def traj_reward_multi(cloud, lo_sum, cam, ws, rewards=None, scalars=None, prefilled=False):
-    """-> (rewards (B, N), scalars (B, 4)) for the B log-odds vectors of traj_forward_multi."""
-    B = lo_sum.shape[0]
-    if rewards is None:
-        rewards = torch.empty((B, cloud.n), dtype=torch.float32, device=cloud.device)
-    if scalars is None:
-        scalars = torch.empty((B, 4), dtype=torch.float32, device=cloud.device)
-    with torch.cuda.device(cloud.device):
-        check(_lib.lib().tohip_traj_reward_multi(ptr(cloud.blob), ptr(lo_sum), cloud.n, B, cam.eps, int(bool(prefilled)), ptr(rewards),
-                                                 ptr(scalars), ptr(ws.buf), ws.bytes, stream_ptr()), "tohip_traj_reward_multi")
-    return rewards, scalars
-
-
-def traj_backward_multi(cloud, n_wps, n_traj, cam, ws, lo_sum, grad_rewards=None, scalars=None, gout=None, rig=None, flags=0):
-    """Gradients (W,3), (W,4) of all trajectories' waypoints; gout: (B,) dL/d loss_vis per trajectory."""
-    pg = torch.empty((n_wps, 3), dtype=torch.float32, device=cloud.device)
-    qg = torch.empty((n_wps, 4), dtype=torch.float32, device=cloud.device)
-    with torch.cuda.device(cloud.device):
-        check(_lib.lib().tohip_traj_backward_multi(ptr(cloud.blob), cloud.n, n_wps, n_traj, cam.ref(),
-                                                   rig.ref() if rig is not None else _NULL_RIG, int(flags), None, ptr(lo_sum),
-                                                   ptr(grad_rewards), ptr(scalars), ptr(gout), ptr(pg), ptr(qg), ptr(ws.buf), ws.bytes,
-                                                   stream_ptr()), "tohip_traj_backward_multi")
-    return pg, qg
 
 
 class PointShardStep:

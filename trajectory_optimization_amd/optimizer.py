@@ -33,6 +33,7 @@ class _OptRun:
         L = _lib.lib()
         m0 = models[0]
         self.models, self.B, self.dev, self.n_steps = models, len(models), m0.device, max(int(n_opt_steps), 1)
+        self.dev_index = _lib.device_index(self.dev)
         B, dev = self.B, self.dev
         cloud, rig = m0._cloud, m0._rig
         W = self.W = m0.poses.shape[0]
@@ -87,19 +88,19 @@ class _OptRun:
         self.c, self.ref, self.fn = c, ctypes.byref(c), L.tohip_traj_opt_step
 
     def run(self, n):
-        idx = self.dev.index if self.dev.index is not None else torch.cuda.current_device()
         if n != self.n_steps:   # a run cut short has no "last step" to leave the rewards: every step writes them
             self.c.flags &= ~LAST_OUTPUTS
-        with torch.cuda.device(idx):
-            stream = torch._C._cuda_getCurrentRawStream(idx)
-            for i in range(n):
-                rc = self.fn(self.ref, i, stream)
-                if rc:
-                    check(rc, "tohip_traj_opt_step")
-                self.ws.generation += 1
+        _lib.on_device(self.dev_index, self._steps, n)
         for m in self.models:   # the Parameters (or their copies) were written through raw pointers
             torch.autograd.graph.increment_version(m.poses)
             torch.autograd.graph.increment_version(m.quats)
+
+    def _steps(self, n, stream):
+        for i in range(n):
+            rc = self.fn(self.ref, i, stream)
+            if rc:
+                check(rc, "tohip_traj_opt_step")
+            self.ws.generation += 1
 
     def results(self, n):
         """The run's only host synchronisation: the final state rows and the loss logs."""
@@ -163,31 +164,28 @@ def _optimize_trajectory_split(model, n_opt_steps, lr_pose, lr_quat, rewards_th,
     poses, quats = model.poses.data, model.quats.data
     # the evaluated waypoints are every step_w-th row of the Parameters, read in place (TOHIP_TRAJ_STRIDE in the flags: no gather)
     stride = ((step_w - 1) & 0xffff) << 8
+    # the step tail reads the visibility step's own buffers (st.scalars, st.pg, st.qg: what st.step returns), one trajectory
+    tail_args = (ptr(poses), ptr(quats), ptr(model.poses0), W, 1, ptr(st.pg), ptr(st.qg), n_eval, step_w, ptr(pg), ptr(qg), ptr(mp),
+                 ptr(vp), ptr(mq), ptr(vq), float(model.smoothness_weight), float(model.traj_length_weight), float(model.eps),
+                 float(lr_pose), float(lr_quat), betas[0], betas[1], adam_eps, float(rewards_th), float(smoothness_th), ptr(st.scalars),
+                 ptr(loss_terms), 0, ptr(state))
     clr = model._clearance_on
     if clr:   # the clearance term: the query's gradient rows and per-waypoint terms, consumed by the step tail
         clr_rows = torch.empty((W, 3), **f32)
         clr_terms = torch.empty(L.tohip_clearance_workspace_bytes(W) // 8, dtype=torch.float64, device=dev)
+        tail, tail_args = L.tohip_traj_step_tail_clearance, tail_args + (float(model.clearance_weight), ptr(clr_rows), ptr(clr_terms))
+    else:
+        tail = L.tohip_traj_step_tail_multi
     with torch.cuda.device(dev):
         for _ in range(n_opt_steps):
             kw = {}
             if model._occlusion is not None and st.hi > st.lo:   # (waypoint placement: PointShard refuses occlusion)
                 own = slice(st.lo * step_w, (st.hi - 1) * step_w + 1, step_w)
                 kw["occ"] = model._occlusion_rows(poses[own].contiguous(), quats[own].contiguous())
-            _, scalars, pg_e, qg_e = st.step(poses, quats, flags_extra=stride, **kw)
+            st.step(poses, quats, flags_extra=stride, **kw)
             if clr:
                 ops.clearance(model._cloud, poses, model.clearance_radius, model.clearance_weight, grad=clr_rows, terms=clr_terms)
-                check(L.tohip_traj_step_tail_clearance(ptr(poses), ptr(quats), ptr(model.poses0), W, 1, ptr(pg_e), ptr(qg_e), n_eval, step_w,
-                                                       ptr(pg), ptr(qg), ptr(mp), ptr(vp), ptr(mq), ptr(vq), float(model.smoothness_weight),
-                                                       float(model.traj_length_weight), float(model.eps), float(lr_pose), float(lr_quat),
-                                                       betas[0], betas[1], adam_eps, float(rewards_th), float(smoothness_th), ptr(scalars),
-                                                       ptr(loss_terms), 0, ptr(state), float(model.clearance_weight), ptr(clr_rows),
-                                                       ptr(clr_terms), stream_ptr()), "step tail")
-                continue
-            check(L.tohip_traj_step_tail(ptr(poses), ptr(quats), ptr(model.poses0), W, ptr(pg_e), ptr(qg_e), n_eval, step_w,
-                                         ptr(pg), ptr(qg), ptr(mp), ptr(vp), ptr(mq), ptr(vq), float(model.smoothness_weight),
-                                         float(model.traj_length_weight), float(model.eps), float(lr_pose), float(lr_quat),
-                                         betas[0], betas[1], adam_eps, float(rewards_th), float(smoothness_th), ptr(scalars),
-                                         ptr(loss_terms), ptr(state), stream_ptr()), "step tail")
+            check(tail(*tail_args, stream_ptr()), "step tail")
     torch.autograd.graph.increment_version(model.poses)
     torch.autograd.graph.increment_version(model.quats)
     stt = state.cpu()  # the run's only host synchronisation
@@ -241,6 +239,13 @@ class PoseOptResult:
         self.losses = losses
 
 
+def _refresh_age(age, every):
+    """The fixed refresh schedule of occlusion rows: a row is rebuilt on every `every`-th forward — when there is none (age None)
+    or the cached one has served `every` forwards — and reused in between.  -> the row's age after this forward: 1 when this
+    forward rebuilds it.  The models' row caches and the launch-only loops below all step it."""
+    return 1 if age is None or age >= every else age + 1
+
+
 def _occlusion_schedule(model, hpr, what):
     """The occlusion refresh period of a ModelPose run (0: no per-pose rows); hpr=True with occlusion= is refused as in forward()."""
     if model._occlusion is None:
@@ -280,23 +285,29 @@ def optimize_pose(model, n_opt_steps=100, lr_pose=0.1, lr_quat=0.1, hpr=False, b
     rest = (obs.data_ptr(), scalars.data_ptr(), tg.data_ptr(), qg.data_ptr(), mt.data_ptr(), vt.data_ptr(), mq.data_ptr(), vq.data_ptr(),
             float(lr_pose), float(lr_quat), float(betas[0]), float(betas[1]), float(adam_eps))
     args = (cloud.blob.data_ptr(), cloud.n, trans.data_ptr(), quat.data_ptr(), cam.ref(), mask.data_ptr() if mask is not None else None) + rest
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    with torch.cuda.device(idx):
-        stream = torch._C._cuda_getCurrentRawStream(idx)
+
+    def steps(stream):
+        """-> (the last occlusion row, its age, rows built): what the model's cache adopts."""
+        args_i, row, age, rebuilds = args, None, None, 0
         for i in range(n_opt_steps):
-            if every and i % every == 0:   # the pose's occlusion row from the pose the device holds now (queued after the last step)
-                row = model._build_occlusion_rows(trans, quat)
-                args = (cloud.blob.data_ptr(), cloud.n, trans.data_ptr(), quat.data_ptr(), cam.ref(), row.data_ptr()) + rest
+            if every:
+                age = _refresh_age(age, every)
+                if age == 1:   # the pose's occlusion row from the pose the device holds now (queued after the last step)
+                    row, rebuilds = model._build_occlusion_rows(trans, quat), rebuilds + 1
+                    args_i = args[:5] + (row.data_ptr(),) + rest
             # one pass over the cloud (observations, their sum, the gradient sums) and its one-block finish (loss, gradient, both
             # Adam updates, the loss log): two launches per step
-            rc = fn(*args, i + 1, losses.data_ptr(), ws.buf.data_ptr(), ws.bytes, stream)
+            rc = fn(*args_i, i + 1, losses.data_ptr(), ws.buf.data_ptr(), ws.bytes, stream)
             if rc:
                 check(rc, "tohip_pose_opt_step_bits" if every else "tohip_pose_opt_step")
+        return row, age, rebuilds
+
+    row, age, rebuilds = _lib.on_device(_lib.device_index(dev), steps)
     torch.autograd.graph.increment_version(model.trans)
     torch.autograd.graph.increment_version(model.quat)
     model.observations = obs
     if every and n_opt_steps > 0:   # the cache holds the last row and its age: the next forward continues the schedule
-        model._adopt_occlusion_row(row, n_opt_steps - (n_opt_steps - 1) // every * every, (n_opt_steps + every - 1) // every)
+        model._adopt_occlusion_row(row, age, rebuilds)
     return PoseOptResult(losses[:n_opt_steps].cpu().tolist())  # the run's only host synchronisation
 
 
@@ -355,14 +366,15 @@ def optimize_poses(models, n_opt_steps=100, lr_pose=0.1, lr_quat=0.1, hpr=False,
     c.scalars, c.trans_grad, c.quat_grad, c.loss_log = scalars.data_ptr(), tg.data_ptr(), qg.data_ptr(), losses.data_ptr()
     c.workspace, c.workspace_bytes = ws.buf.data_ptr(), ws.bytes
     ref, fn = ctypes.byref(c), L.tohip_pose_opt_step_multi
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    rows = None
-    with torch.cuda.device(idx):
-        stream = torch._C._cuda_getCurrentRawStream(idx)
+
+    def steps(stream):
+        rows, age, rebuilds = None, None, 0
         for i in range(n_opt_steps):
-            if every and i % every == 0:   # every pose's row, from the poses the device holds now, in one batched pass
-                rows = m0._build_occlusion_rows(trans, quat)
-                c.occlusion_bits = rows.data_ptr()
+            if every:
+                age = _refresh_age(age, every)
+                if age == 1:   # every pose's row, from the poses the device holds now, in one batched pass
+                    rows, rebuilds = m0._build_occlusion_rows(trans, quat), rebuilds + 1
+                    c.occlusion_bits = rows.data_ptr()
             # the observations are what the last step leaves (optimize_pose writes them every step; the bits are the same)
             rc = fn(ref, i + 1, obs.data_ptr() if i + 1 == n_opt_steps else None, stream)
             if rc:
@@ -374,8 +386,9 @@ def optimize_poses(models, n_opt_steps=100, lr_pose=0.1, lr_quat=0.1, hpr=False,
             torch.autograd.graph.increment_version(m.quat)
             m.observations = obs[b]
             if every:   # each model's cache holds its own last row and its age (optimize_pose's bookkeeping)
-                m._adopt_occlusion_row(rows[b:b + 1].clone(), n_opt_steps - (n_opt_steps - 1) // every * every,
-                                       (n_opt_steps + every - 1) // every)
+                m._adopt_occlusion_row(rows[b:b + 1].clone(), age, rebuilds)
+
+    _lib.on_device(_lib.device_index(dev), steps)
     lt = losses.cpu()   # the run's only host synchronisation
     return [PoseOptResult(lt[b].tolist()) for b in range(B)]
 
@@ -393,12 +406,7 @@ def _adam_update(L, entries, arr):
         if dev is not None and p.device != dev:
             raise RuntimeError("one optimizer step over parameters of several devices is not supported")
         dev = p.device
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    if torch.cuda.current_device() == idx:
-        rc = L.tohip_adam_step_multi(arr, k, torch._C._cuda_getCurrentRawStream(idx))
-    else:
-        with torch.cuda.device(idx):
-            rc = L.tohip_adam_step_multi(arr, k, torch._C._cuda_getCurrentRawStream(idx))
+    rc = _lib.on_device(dev.index, L.tohip_adam_step_multi, arr, k)   # (a tensor's device always has its index)
     if rc:
         check(rc, "tohip_adam_step_multi")
     for _, q, _, _ in entries:   # the kernel wrote through raw pointers: autograd's in-place guards must still see an update
