@@ -516,7 +516,8 @@ int tohip_cull_waypoints_packed(const float *xyz, int64_t n_points, const float 
                                 int normalize, const tohip_camera *cam_host, float min_dist, float max_dist, int32_t *kept_idx,
                                 float *kept_pts, int32_t *kept_count, int64_t *seg_off, void *workspace, size_t workspace_bytes,
                                 void *stream);
-/* gather rows: out[i,:] = xyz[idx[i],:] for i < *count (device), xyz (N,3) or (3,N) by in_layout. */
+/* gather rows: out[i,:] = xyz[idx[i],:] for i < min(*count, capacity) (count: device), xyz (N,3) or (3,N) by in_layout.  out_xyz
+ * holds capacity rows; a count above capacity writes the first capacity rows and nothing beyond them. */
 int tohip_gather_points(const float *xyz, int64_t n_points, int in_layout, const int32_t *idx, const int32_t *count,
                         int64_t capacity, float *out_xyz, void *stream);
 
@@ -588,7 +589,8 @@ int tohip_traj_regularizers_clearance(const float *poses, const float *poses0, i
  * of model.py:217 (scatter = 0: gather src[r*step] -> dst[r]; 1: scatter src[r] -> dst[r*step]). */
 int tohip_rows_strided(const float *src, int64_t n_rows, int cols, int step, int scatter, float *dst, void *stream);
 /* torch.optim.Adam update of one parameter group (defaults of trajectory_optimization.py:91-94); step is the
- * 1-based iteration; a no-op once state[2] != 0 (early stop reached).  state may be NULL. */
+ * 1-based iteration; a no-op once state[2] != 0 (early stop reached).  state may be NULL.  0 < n <= 2^31 - 1, as in
+ * tohip_adam_step_multi. */
 int tohip_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr, float beta1,
                     float beta2, float eps, int32_t step, const float *state, void *stream);
 /* The same update for up to TOHIP_ADAM_MAX_GROUPS parameter tensors in ONE launch (the reference's optimiser holds two:

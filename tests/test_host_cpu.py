@@ -25,6 +25,25 @@ def test_library_exports_every_declared_symbol():
     assert int(re.search(r'#define TOHIP_ABI_VERSION (\d+)', header).group(1)) == _lib.ABI_VERSION == _lib.lib().tohip_abi_version()
 
 
+def test_every_declared_entry_point_is_called_somewhere():
+    """Every tohip_* function the header declares is called by the tests, the package, bench.py (as `.<name>` on the library
+    handle) or the C host example: an export nothing calls has never run."""
+    header = open(os.path.join(REPO, "include", "trajopt_hip.h")).read()
+    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    header = re.sub(r"//[^\n]*", " ", header)
+    declared = set(re.findall(r"\b(tohip_\w+)\s*\(", header))
+    assert declared, "no declarations found"
+    sources = []
+    for d in ("tests", "trajectory_optimization_amd"):
+        for root, _, files in os.walk(os.path.join(REPO, d)):
+            sources += [os.path.join(root, f) for f in files if f.endswith(".py") and f != "_lib.py"]
+    sources.append(os.path.join(REPO, "bench.py"))
+    py = "\n".join(open(f).read() for f in sources)
+    used = set(re.findall(r"\.(tohip_\w+)\b", py))
+    used |= set(re.findall(r"\b(tohip_\w+)\s*\(", open(os.path.join(REPO, "examples", "c_host.cpp")).read()))
+    assert not declared - used, f"declared in include/trajopt_hip.h but never called: {sorted(declared - used)}"
+
+
 def test_sizes_and_argument_errors_without_gpu():
     from trajectory_optimization_amd import _lib
     L = _lib.lib()

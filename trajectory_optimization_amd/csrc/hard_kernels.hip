@@ -585,11 +585,11 @@ extern "C" int tohip_cull_waypoints_packed(const float* xyz, int64_t n, const fl
                                workspace, workspace_bytes, stream_);
 }
 
-// out[i,:] = xyz[idx[i],:]  for i < *count
+// out[i,:] = xyz[idx[i],:]  for i < min(*count, capacity): a device count above the output's capacity writes capacity rows
 __global__ void __launch_bounds__(TO_BLOCK)
 k_gather_points(const float* __restrict__ xyz, int64_t n, int in_layout, const int32_t* __restrict__ idx,
-                const int32_t* __restrict__ count, float* __restrict__ out) {
-    const int m = *count;
+                const int32_t* __restrict__ count, int64_t capacity, float* __restrict__ out) {
+    const int64_t m = min((int64_t)*count, capacity);
     const int64_t stride = (int64_t)gridDim.x * TO_BLOCK;
     for (int64_t i = (int64_t)blockIdx.x * TO_BLOCK + threadIdx.x; i < m; i += stride) {
         const int64_t s = idx[i];
@@ -607,7 +607,7 @@ extern "C" int tohip_gather_points(const float* xyz, int64_t n, int in_layout, c
     if (capacity == 0) return TOHIP_OK;
     int64_t nb = (capacity + TO_BLOCK - 1) / TO_BLOCK;
     if (nb > 2048) nb = 2048;
-    k_gather_points<<<(int)nb, TO_BLOCK, 0, (hipStream_t)stream_>>>(xyz, n, in_layout, idx, count, out);
+    k_gather_points<<<(int)nb, TO_BLOCK, 0, (hipStream_t)stream_>>>(xyz, n, in_layout, idx, count, capacity, out);
     TO_HIP_CHECK_LAUNCH();
     return TOHIP_OK;
 }

@@ -282,7 +282,7 @@ extern "C" int tohip_rows_strided(const float* src, int64_t n_rows, int cols, in
 
 extern "C" int tohip_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                                float beta1, float beta2, float eps, int32_t step, const float* state, void* stream_) {
-    if (!param || !grad || !exp_avg || !exp_avg_sq || n <= 0 || (step < 1 && !state)) return TOHIP_EINVAL;
+    if (!param || !grad || !exp_avg || !exp_avg_sq || n <= 0 || n > 0x7fffffff || (step < 1 && !state)) return TOHIP_EINVAL;
     k_adam<<<(int)((n + 255) / 256), 256, 0, (hipStream_t)stream_>>>(param, grad, exp_avg, exp_avg_sq, (int)n, lr, beta1, beta2,
                                                                       eps, step, state);
     TO_HIP_CHECK_LAUNCH();
