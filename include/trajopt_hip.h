@@ -210,6 +210,35 @@ int tohip_traj_reward_backward_multi(const void *packed, int64_t n_points, int64
                                      float *scalars, const float *gout, float *poses_grad, float *quats_grad, void *workspace,
                                      size_t workspace_bytes, void *stream);
 
+/* ---- a per-point log-odds prior (prior_kernels.hip) -------------------------------------------------------------------------
+ * What is already known of the map, as OctoMap accumulates it: rewards become r_i = sigmoid(lo_sum_i + prior_i), lo_sum the
+ * forward's sum over the evaluated waypoints as before (the forward does not change), the prior added last in one f32 add.  A zero
+ * prior gives the bits of the calls without one.  prior >= 0 and finite (the integer reward sum is exact for r in [1/2, 1) only).
+ * tohip_traj_prior_build turns an (N,) f32 prior in the CALLER'S order into prior_buf (tohip_traj_prior_bytes(N) device bytes): the
+ * prior and sigmoid(prior) in packed order and the fixed-point sums the reward kernel starts from.  *status (device int32) is 0, or
+ * has bit 0 set for a negative (or NaN) entry and bit 1 for a non-finite one; prior_buf is then not to be used.  Two launches.
+ * The _prior variants take the argument lists of tohip_traj_reward, tohip_traj_reward_backward and tohip_traj_backward plus
+ * prior_buf (built for the same cloud and N); prior_buf = NULL is the call without a prior.  With a prior: one trajectory, and
+ * prefilled must be 0 (every reward is stored).
+ * tohip_traj_coverage: out[0..N) (caller's order) = prior + lo_sum (lo_sum in packed order, as the forward writes it; prior_buf may
+ * be NULL: lo_sum alone), values above clamp_max set to clamp_max (OctoMap's upper clamping threshold; +inf: none; >= 0) — the fused
+ * log-odds map that is the next plan's prior.  One launch. */
+size_t tohip_traj_prior_bytes(int64_t n_points);
+int tohip_traj_prior_build(const void *packed, int64_t n_points, const float *prior, void *prior_buf, size_t prior_buf_bytes,
+                           int32_t *status, void *stream);
+int tohip_traj_reward_prior(const void *packed, const float *lo_sum, int64_t n_points, float eps, int prefilled, float *rewards,
+                            float *scalars, void *workspace, size_t workspace_bytes, const void *prior_buf, void *stream);
+int tohip_traj_reward_backward_prior(const void *packed, int64_t n_points, int64_t n_wps, const tohip_camera *cam_host,
+                                     const tohip_rig *rig_host, int flags, const uint32_t *occlusion_bits, const float *lo_sum,
+                                     float eps, int prefilled, float *rewards, float *scalars, const float *gout, float *poses_grad,
+                                     float *quats_grad, void *workspace, size_t workspace_bytes, const void *prior_buf, void *stream);
+int tohip_traj_backward_prior(const void *packed, int64_t n_points, int64_t n_wps, const tohip_camera *cam_host,
+                              const tohip_rig *rig_host, int flags, const uint32_t *occlusion_bits, const float *lo_sum,
+                              const float *grad_rewards, const float *scalars, const float *gout, float *poses_grad, float *quats_grad,
+                              void *workspace, size_t workspace_bytes, const void *prior_buf, void *stream);
+int tohip_traj_coverage(const void *packed, int64_t n_points, const float *lo_sum, const void *prior_buf, float clamp_max, float *out,
+                        void *stream);
+
 /* The whole step when NO collective sits between forward and backward (one GPU, or every rank holding all waypoints):
  * tohip_traj_forward + tohip_traj_reward + tohip_traj_backward of the fused visibility loss in FIVE launches — records + probe,
  * pass 1, the sparse kernel (flags, log-odds, rewards, their sum; a block per candidate slot), the gradient sums of the flagged

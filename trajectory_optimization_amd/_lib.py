@@ -89,7 +89,15 @@ SIGNATURES = {
                                                          c_vp, c_vp, c_f, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "tohip_traj_reward_backward": (ctypes.c_int, [c_vp, c_i64, c_i64, ctypes.POINTER(Camera), ctypes.POINTER(Rig), ctypes.c_int,
                                                    c_vp, c_vp, c_f, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
-    "tohip_traj_step_tail_multi": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, ctypes.c_int, c_vp, c_vp, c_vp, c_vp,
+    "tohip_traj_prior_bytes": (c_sz, [c_i64]),
+    "tohip_traj_prior_build": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "tohip_traj_reward_prior": (ctypes.c_int, [c_vp, c_vp, c_i64, c_f, ctypes.c_int, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "tohip_traj_reward_backward_prior": (ctypes.c_int, [c_vp, c_i64, c_i64, ctypes.POINTER(Camera), ctypes.POINTER(Rig), ctypes.c_int,
+                                                         c_vp, c_vp, c_f, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "tohip_traj_backward_prior": (ctypes.c_int, [c_vp, c_i64, c_i64, ctypes.POINTER(Camera), ctypes.POINTER(Rig), ctypes.c_int, c_vp,
+                                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "tohip_traj_coverage": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_f, c_vp, c_vp]),
+    "tohip_traj_step_tail_multi": (ctypes.c_int,[c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, ctypes.c_int, c_vp, c_vp, c_vp, c_vp,
                                                    c_vp, c_vp, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp, c_i64, c_vp,
                                                    c_vp]),
     "tohip_gather_waypoints_multi": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, ctypes.c_int, c_vp, c_vp, c_vp]),

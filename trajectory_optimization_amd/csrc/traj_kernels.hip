@@ -1089,8 +1089,10 @@ __global__ void __launch_bounds__(NW * 64, SFW == 8 ? 4 : 3) k_traj_sparse(Spars
 //   (they are linear in it; k_traj_finish scales them once the mean of the rewards is known).
 // UNIT: the upstream gradient is the unit one AND this step's fused sparse kernel has left r (1 - r) of the slot's points in
 // a.unit: four loads instead of four sigmoids per lane and pair (a slot's points meet dozens of waypoints).
-template <bool OCC, bool UNIT>
-__device__ __forceinline__ void pair_sums(const SparseArgs& a, int slot, int v, int lane) {
+// PRIOR: r = sigmoid(lo_sum + prior) with the per-point log-odds prior (packed order, prior_kernels.hip) added last, one f32 add.
+template <bool OCC, bool UNIT, bool PRIOR = false>
+__device__ __forceinline__ void pair_sums(const SparseArgs& a, int slot, int v, int lane, const float* __restrict__ prior = nullptr) {
+    static_assert(!(UNIT && PRIOR), "a prior step has no fused forward: r (1 - r) comes from the log-odds");
     const EvalK& k = a.k;
     const WayRec& r = a.rec[v];
     const int tr = a.toff ? r.seg : 0;
@@ -1106,7 +1108,11 @@ __device__ __forceinline__ void pair_sums(const SparseArgs& a, int slot, int v, 
     load_norm(a.ext[v], av, pmax, M, invM);
     if (!(M > 0.f) || !(invM < INFINITY)) invM = __builtin_nanf("");   // degenerate: nothing is active (NaN compares false)
     const float coef = (!UNIT && a.scalars) ? a.scalars[4 * tr + 2] * a.gout[tr] : 1.0f;
-    const float lo[4] = {l4.x, l4.y, l4.z, l4.w};
+    float lo[4] = {l4.x, l4.y, l4.z, l4.w};
+    if constexpr (PRIOR) {
+        const float4 p4 = *reinterpret_cast<const float4*>(prior + base);
+        lo[0] += p4.x; lo[1] += p4.y; lo[2] += p4.z; lo[3] += p4.w;
+    }
     const int o[4] = {o4.x, o4.y, o4.z, o4.w};
     float gn[4];   // dL/d lo_sum_n
 #pragma unroll
@@ -1164,8 +1170,8 @@ __device__ __forceinline__ void pair_sums(const SparseArgs& a, int slot, int v, 
 }
 
 // block b of nb (TO_SP_THREADS threads each): wave gw = wave * nb + b of 16 nb takes the pairs gw, gw + 16 nb, ...
-template <bool OCC, bool UNIT>
-__device__ __forceinline__ void pair_walk(const SparseArgs& a, int b, int nb) {
+template <bool OCC, bool UNIT, bool PRIOR = false>
+__device__ __forceinline__ void pair_walk(const SparseArgs& a, int b, int nb, const float* __restrict__ prior = nullptr) {
     const int lane = threadIdx.x & 63;
     TO_STAMP(TO_STAMP_PAIRS, 0);
     // wave-major numbering: the step's pairs rarely divide by the grid's waves, and the waves that take one pair more should be ONE per
@@ -1191,7 +1197,7 @@ __device__ __forceinline__ void pair_walk(const SparseArgs& a, int b, int nb) {
     for (int p = gw; p < P; p += GW) {
         const int2 cur = next;
         if (p + GW < P) next = entry(p + GW);
-        pair_sums<OCC, UNIT>(a, __builtin_amdgcn_readfirstlane(cur.x), __builtin_amdgcn_readfirstlane(cur.y), lane);
+        pair_sums<OCC, UNIT, PRIOR>(a, __builtin_amdgcn_readfirstlane(cur.x), __builtin_amdgcn_readfirstlane(cur.y), lane, prior);
     }
     TO_STAMP(TO_STAMP_PAIRS, 2);
     TO_STAMP_LAST(TO_STAMP_PAIRS, 3);   // the block's last wave
@@ -1225,9 +1231,20 @@ __global__ void __launch_bounds__(TO_SP_THREADS) k_traj_pairs(SparseArgs a, OptS
 // arrival completes the count has the total (integer addition commutes: no dependence on the order), writes the scalars and
 // clears the accumulator for the next launch.
 // block bx of nbx of trajectory `traj` (its own log-odds vector, rewards vector, accumulator and scalars); blockDim.x = 1024
+// PRIOR (one trajectory, never prefilled): r = sigmoid(lo_sum + prior), every reward stored.  The block's integer sum starts from
+// its share of sum fixed(sigmoid(prior)) (the prior build's base for block bx of this very partition) and adds fixed(r) -
+// fixed(sigmoid(prior)) over the points the waypoints touched (lo_sum != 0): the untouched ones' reward IS sigmoid(prior), read
+// from the build's vector.  The block's total is then the sum of its points' fixed(r), as without a prior: never negative.
+struct PriorView {
+    const long long* base;   // TO_REWARD_BLOCKS entries: block bx's sum of fixed(sigmoid(prior)) over its points
+    const float* prior;      // npad, packed order (0 at the pads)
+    const float* sig;        // npad, packed order: sigmoid(prior), the expression below with lo_sum = 0
+};
+template <bool PRIOR = false>
 __device__ __forceinline__ void reward_block(const float* __restrict__ lo_sum, const int* __restrict__ perm, int64_t n, int64_t npad, float eps,
                                              int shift, int prefilled, float* __restrict__ rewards, RewardAcc* __restrict__ acc,
-                                             float* __restrict__ scalars, int bx, int nbx, int traj, long long* lds) {
+                                             float* __restrict__ scalars, int bx, int nbx, int traj, long long* lds,
+                                             PriorView pv = PriorView{nullptr, nullptr, nullptr}) {
     lo_sum += (int64_t)traj * npad;
     rewards += (int64_t)traj * n;
     acc += traj;
@@ -1238,8 +1255,33 @@ __device__ __forceinline__ void reward_block(const float* __restrict__ lo_sum, c
     const int64_t stride = (int64_t)nbx * TO_SP_THREADS * 4;
     for (int64_t i0 = ((int64_t)bx * TO_SP_THREADS + threadIdx.x) * 4; i0 < n; i0 += stride) {
         const float4 lo4 = *reinterpret_cast<const float4*>(lo_sum + i0);   // npad is a multiple of 2048: aligned, in bounds
-        const float lo[4] = {lo4.x, lo4.y, lo4.z, lo4.w};
         const bool all0 = (lo4.x == 0.f) & (lo4.y == 0.f) & (lo4.z == 0.f) & (lo4.w == 0.f);
+        if constexpr (PRIOR) {
+            const float4 sg4 = *reinterpret_cast<const float4*>(pv.sig + i0);
+            const int4 o4 = *reinterpret_cast<const int4*>(perm + i0);
+            const float sg[4] = {sg4.x, sg4.y, sg4.z, sg4.w};
+            const int o[4] = {o4.x, o4.y, o4.z, o4.w};
+            float lt[4] = {lo4.x, lo4.y, lo4.z, lo4.w};
+            if (!all0) {
+                const float4 p4 = *reinterpret_cast<const float4*>(pv.prior + i0);
+                lt[0] += p4.x; lt[1] += p4.y; lt[2] += p4.z; lt[3] += p4.w;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (i0 + j < n) {
+                    float r = sg[j];
+                    if (!all0) {
+                        r = to_rcp(1.0f + to_exp(-lt[j]));
+                        if (lt[j] != lt[j]) r = lt[j];
+                    }
+                    rewards[o[j]] = r;
+                    if (r != r) anynan = true;
+                    else if (!all0) s += reward_fixed(r, shift) - reward_fixed(sg[j], shift);
+                }
+            }
+            continue;
+        }
+        const float lo[4] = {lo4.x, lo4.y, lo4.z, lo4.w};
         if (all0 && prefilled) {   // sigmoid(0) evaluated as below is exactly 0.5
             s += half * min((int64_t)4, n - i0);
             continue;
@@ -1266,6 +1308,7 @@ __device__ __forceinline__ void reward_block(const float* __restrict__ lo_sum, c
     long long tot = 0;
     bool nan_ = false;
     for (int w = 0; w < TO_SP_WAVES; ++w) { tot += lds[w]; nan_ |= lds[TO_SP_WAVES + w] != 0ll; }
+    if constexpr (PRIOR) tot += pv.base[bx];
     const unsigned long long word = (1ull << 56) | (nan_ ? (1ull << 48) : 0ull) | ((unsigned long long)tot & 0xffffffffffffull);
     const unsigned long long old = __hip_atomic_fetch_add(&acc->b.word, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if ((int)(old >> 56) != nbx - 1) return;
@@ -1283,6 +1326,14 @@ k_traj_reward(const float* __restrict__ lo_sum, const int* __restrict__ perm, in
     reward_block(lo_sum, perm, n, npad, eps, shift, prefilled, rewards, acc, scalars, blockIdx.x, gridDim.x, blockIdx.y, lds);
 }
 
+// the same with a log-odds prior: r = sigmoid(lo_sum + prior), one trajectory, every reward stored
+__global__ void __launch_bounds__(TO_SP_THREADS)
+k_traj_reward_prior(const float* __restrict__ lo_sum, const int* __restrict__ perm, int64_t n, int64_t npad, float eps, int shift,
+                    float* __restrict__ rewards, RewardAcc* __restrict__ acc, float* __restrict__ scalars, PriorView pv) {
+    __shared__ long long lds[2 * TO_SP_WAVES];
+    reward_block<true>(lo_sum, perm, n, npad, eps, shift, 0, rewards, acc, scalars, blockIdx.x, gridDim.x, 0, lds, pv);
+}
+
 // rewards + mean + loss (the first nbx * n_traj blocks) and the gradient sums with unit upstream gradient (the other blocks:
 // k_traj_pairs' waves) in ONE launch: both need the complete log-odds vector and nothing of each other.
 template <bool OCC>
@@ -1296,6 +1347,24 @@ k_traj_reward_bwd(const float* __restrict__ lo_sum, int64_t n, float eps, int pr
         return;
     }
     pair_walk<OCC, false>(a, (int)blockIdx.x - R, (int)gridDim.x - R);   // (the rewards of this very launch: no r (1 - r) left by a fused forward)
+}
+
+// the two kernels of a split step's backward with a log-odds prior (one trajectory): k_traj_reward_bwd's launch, and k_traj_pairs'
+// without the one-call step's extra block
+template <bool OCC>
+__global__ void __launch_bounds__(TO_SP_THREADS)
+k_traj_reward_bwd_prior(const float* __restrict__ lo_sum, int64_t n, float eps, float* __restrict__ rewards, float* __restrict__ scalars,
+                        int nbx, SparseArgs a, PriorView pv) {
+    __shared__ long long lds[2 * TO_SP_WAVES];
+    if ((int)blockIdx.x < nbx) {
+        reward_block<true>(lo_sum, a.cv.perm, n, a.cv.npad, eps, a.shift, 0, rewards, a.acc, scalars, blockIdx.x, nbx, 0, lds, pv);
+        return;
+    }
+    pair_walk<OCC, false, true>(a, (int)blockIdx.x - nbx, (int)gridDim.x - nbx, pv.prior);
+}
+template <bool OCC>
+__global__ void __launch_bounds__(TO_SP_THREADS) k_traj_pairs_prior(SparseArgs a, const float* __restrict__ prior) {
+    pair_walk<OCC, false, true>(a, (int)blockIdx.x, (int)gridDim.x, prior);
 }
 
 // thread per body waypoint: rig composition, dL/dt = -R sum dL/dc, dL/dR = sum y (x) dL/dc,
@@ -2277,12 +2346,33 @@ struct FusedReward { float eps; int prefilled; float* rewards; float* scalars; }
 int traj_backward_impl(const void* packed, int64_t n, int64_t W, int64_t n_traj, const tohip_camera* cam,
                        const tohip_rig* rig, int flags, const uint32_t* occlusion_bits, float* lo_sum,
                        const float* grad_rewards, const float* scalars, const float* gout, float* poses_grad,
-                       float* quats_grad, void* workspace, size_t workspace_bytes, void* stream_, const FusedReward* fused) {
+                       float* quats_grad, void* workspace, size_t workspace_bytes, void* stream_, const FusedReward* fused,
+                       const PriorView* prior = nullptr) {
     if (!lo_sum || !poses_grad || !quats_grad || (!grad_rewards && (!scalars || !gout))) return TOHIP_EINVAL;
+    if (prior && (n_traj != 1 || (fused && fused->prefilled))) return TOHIP_EINVAL;   // (a prior step writes every reward)
     TrajStep s;
     int rc = traj_step_init(s, packed, n, W, n_traj, nullptr, cam, rig, flags, occlusion_bits, workspace, workspace_bytes, stream_, false);
     if (rc != TOHIP_OK) return rc;
     SparseArgs a = sparse_args(s, lo_sum);
+    if (prior) {
+        TO_PROF(TOHIP_PROF_BWD, s.st);
+        if (fused) {
+            const int nbx = reward_blocks(n);
+            const int blocks = nbx + pair_blocks();
+            if (s.occ) k_traj_reward_bwd_prior<true><<<blocks, TO_SP_THREADS, 0, s.st>>>(lo_sum, n, fused->eps, fused->rewards, fused->scalars, nbx, a, *prior);
+            else k_traj_reward_bwd_prior<false><<<blocks, TO_SP_THREADS, 0, s.st>>>(lo_sum, n, fused->eps, fused->rewards, fused->scalars, nbx, a, *prior);
+        } else {
+            a.grad_rewards = grad_rewards;
+            a.scalars = grad_rewards ? nullptr : scalars;
+            a.gout = grad_rewards ? nullptr : gout;
+            a.unit = nullptr;
+            if (s.occ) k_traj_pairs_prior<true><<<pair_blocks(), TO_SP_THREADS, 0, s.st>>>(a, prior->prior);
+            else k_traj_pairs_prior<false><<<pair_blocks(), TO_SP_THREADS, 0, s.st>>>(a, prior->prior);
+        }
+        TO_HIP_CHECK_LAUNCH();
+        return fused ? launch_finish(s, finish_post(s, 1, scalars, gout, nullptr, fused->eps), poses_grad, quats_grad)
+                     : launch_finish(s, finish_post(s, 0, nullptr, nullptr, nullptr, 0.f), poses_grad, quats_grad);
+    }
     if (fused) {
         TO_PROF(TOHIP_PROF_BWD, s.st);
         const int nbx = reward_blocks(n);

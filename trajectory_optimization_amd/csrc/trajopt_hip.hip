@@ -4,6 +4,7 @@
 // (-ffp-contract=off: every FMA in the kernels is an explicit fmaf(); see common.hpp.)
 #include "clearance_kernels.hip"
 #include "traj_kernels.hip"
+#include "prior_kernels.hip"
 #include "pose_kernels.hip"
 #include "hard_kernels.hip"
 #include "hull_kernels.hip"

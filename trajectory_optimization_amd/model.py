@@ -193,8 +193,8 @@ class _TrajRewards(torch.autograd.Function):
         ps, qs = p[st.lo:st.hi].clone(), q[st.lo:st.hi].clone()  # own copies: the step's inputs, whatever happens to the Parameters
         # occlusion masks are piecewise constant in the poses: computed per forward, not differentiated
         occ = model._occlusion_rows(ps, qs) if st.hi > st.lo and model._occlusion is not None else None
-        lo_sum, rewards, _ = st.forward(ps, qs, occ)
-        ctx.step, ctx.occ, ctx.gen = st, occ, st.ws.generation
+        lo_sum, rewards, _ = st.forward(ps, qs, occ, prior=model._prior)
+        ctx.step, ctx.occ, ctx.gen, ctx.prior = st, occ, st.ws.generation, model._prior
         ctx.save_for_backward(ps, qs, lo_sum)
         return rewards
 
@@ -203,7 +203,7 @@ class _TrajRewards(torch.autograd.Function):
         ps, qs, lo_sum = ctx.saved_tensors
         st = ctx.step
         upstream = dict(grad_rewards=grad_rewards.to(torch.float32).contiguous()) if st.hi > st.lo else None
-        pg, qg = st.backward(ps, qs, ctx.occ, ctx.gen, lo_sum, upstream)
+        pg, qg = st.backward(ps, qs, ctx.occ, ctx.gen, lo_sum, upstream, prior=ctx.prior)
         return pg.contiguous(), qg.contiguous(), None
 
 
@@ -324,8 +324,11 @@ class _TrajLoss(torch.autograd.Function):
             q_eval = q_all[::step_w].contiguous() if step_w > 1 else q_all
             ps, qs = p_eval[st.lo:st.hi].clone(), q_eval[st.lo:st.hi].clone()  # own copies: the step's inputs, whatever happens to the Parameters
             occ = model._occlusion_rows(ps, qs) if st.hi > st.lo and model._occlusion is not None else None
-            lo_sum, rewards, scalars = st.forward(ps, qs, occ)
-            ctx.occ, ctx.gen = occ, st.ws.generation
+            lo_sum, rewards, scalars = st.forward(ps, qs, occ, prior=model._prior)
+            ctx.occ, ctx.gen, ctx.prior = occ, st.ws.generation, model._prior
+            # a prior model that would take the one-call plan without its prior keeps the plan's gradient arithmetic (unit sums
+            # scaled once per waypoint): a zero prior changes no bit
+            ctx.unit_sums = not (model._shard.collective or model._occlusion is not None)
             saved = (ps, qs, lo_sum, scalars)
         clr_rows = clr_terms = None
         if model._clearance_on:   # every rank: all W waypoints, the whole cloud
@@ -355,7 +358,7 @@ class _TrajLoss(torch.autograd.Function):
         else:
             ps, qs, lo_sum, scalars = saved
             upstream = _vis_upstream(g_loss, g_vis, g_rewards, scalars) if st.hi > st.lo else None
-            pg_e, qg_e = st.backward(ps, qs, ctx.occ, ctx.gen, lo_sum, upstream)
+            pg_e, qg_e = st.backward(ps, qs, ctx.occ, ctx.gen, lo_sum, upstream, prior=ctx.prior, unit_sums=ctx.unit_sums)
         pg, qg = _assemble_grads(ctx.step_w, ctx.W, pg_e, qg_e, g_loss, (g_l2, g_length, g_smooth), reg_sum, reg_terms, clr_rows, g_clr)
         return pg, qg, None, None
 
@@ -813,7 +816,9 @@ class ModelTraj(nn.Module):
     `occlusion='hpr'|'zbuffer'` makes the reward occlusion-aware per waypoint — the reference's TODO
     (/root/reference/src/tools.py:61-62, /root/reference/src/model.py:210): each waypoint's camera-frame cloud goes
     through the hard pipeline of /root/reference/src/pc_processor.py:171-178 (frustum cull with `occlusion_limits`,
-    then HPR from the camera centre) and the points it hides get p = 0 for that waypoint.
+    then HPR from the camera centre) and the points it hides get p = 0 for that waypoint;
+    `prior_log_odds=` an (N,) tensor of what is already known of the map (OctoMap's accumulated log-odds, >= 0, in the caller's point
+    order): rewards become sigmoid(lo_sum + prior) — see the prior_log_odds property and coverage_log_odds().
     """
 
     def __init__(self,
@@ -827,7 +832,7 @@ class ModelTraj(nn.Module):
                  device=torch.device('cuda'),
                  *, rig=None, shard=None, dense=False, occlusion=None, occlusion_limits=(1.0, 15.0), occlusion_refresh_every=1,
                  occlusion_refresh_tol=None, occlusion_check_every=5, n_points_global=None, cloud=None, fast_adam=False,
-                 clearance_radius=None, clearance_weight=0.0):
+                 clearance_radius=None, clearance_weight=0.0, prior_log_odds=None):
         super().__init__()
         # the clearance term (clearance_kernels.hip): weight x sum over ALL waypoints of (r - d)^2, d = the distance to the nearest
         # cloud point within r — it keeps the path off the cloud; weight 0 (the default): off, the reference's criterion as it is
@@ -895,6 +900,8 @@ class ModelTraj(nn.Module):
         if occlusion not in (None, "hpr", "zbuffer"):
             raise ValueError("occlusion must be None, 'hpr' or 'zbuffer'")
         self._occlusion, self._occlusion_limits = occlusion, occlusion_limits
+        self._prior = None   # ops.LogOddsPrior (the property below)
+        self.prior_log_odds = prior_log_odds
         # The occlusion masks are piecewise constant in the poses (a point is hidden from a waypoint or it is not) and carry no
         # gradient; building them — a hard cull and a convex hull (or a z-buffer) per waypoint — costs hundreds of plain steps.
         # occlusion_refresh_every = k: they are rebuilt on every k-th forward of the model (k = 1: every forward, the bits of a
@@ -950,6 +957,47 @@ class ModelTraj(nn.Module):
     @property
     def _clearance_on(self):
         return self._clr[1] > 0.0
+
+    @property
+    def prior_log_odds(self):
+        """The per-point log-odds prior (N,) f32 in the caller's order, or None.  Rewards are sigmoid(lo_sum + prior): lo_sum the sum
+        over the evaluated waypoints as without it, the prior added last (a zero prior gives the bits of the model without one).
+        Setting it checks the value (finite, >= 0, one entry per point, on the model's device: ValueError otherwise) and the next
+        forward / optimiser run uses it; None returns the model to the path without a prior.  A prior model goes through the
+        separate visibility calls (as an occlusion-aware one); not available with PointShard or optimize_trajectories."""
+        return self._prior.values if self._prior is not None else None
+
+    @prior_log_odds.setter
+    def prior_log_odds(self, prior):
+        if prior is None:
+            self._prior = None
+            return
+        if self._shard.kind == "points":
+            raise ValueError("prior_log_odds needs the whole cloud on every rank: not available with PointShard")
+        self._prior = ops.LogOddsPrior(self._cloud, prior)   # (checks it: ops.check_prior)
+
+    @torch.no_grad()
+    def coverage_log_odds(self, upto=None, clamp_max=None, vis_wps_dist=0.5):
+        """The fused log-odds map (N,) f32 in the caller's order: prior + lo_sum, lo_sum from the model's evaluated waypoints (every
+        wps_step-th, as forward(vis_wps_dist) selects them) with index < upto (all when None) at their current poses, with their
+        current occlusion rows when the model has them.  clamp_max: OctoMap's upper clamping threshold (>= 0; None: none).  Forward
+        only.  This is the next plan's prior_log_odds: the coverage of the path flown so far, or of another robot's plan."""
+        if self._shard.kind == "points":
+            raise ValueError("coverage_log_odds needs the whole cloud: not available with PointShard")
+        W = self.poses.shape[0]
+        upto = W if upto is None else int(upto)
+        if not 0 <= upto <= W:
+            raise ValueError(f"upto must be in [0, {W}], got {upto}")
+        step_w = self._wps_step(vis_wps_dist)
+        ps = self.poses.detach()[0:upto:step_w].contiguous()
+        qs = self.quats.detach()[0:upto:step_w].contiguous()
+        cloud = self._cloud
+        if ps.shape[0] > 0:
+            occ = self._build_occlusion_rows(ps, qs) if self._occlusion is not None else None
+            lo_sum, _ = ops.traj_forward(cloud, ps, qs, self._cam, self._workspace(ps.shape[0]), self._rig, flags=self._flags, occ=occ)
+        else:
+            lo_sum = torch.zeros(cloud.npad, dtype=torch.float32, device=cloud.device)
+        return ops.traj_coverage(cloud, lo_sum, self._prior, clamp_max)
 
     @classmethod
     def sharing_cloud_of(cls, other, wps_poses, wps_quats, **kw):
@@ -1097,7 +1145,7 @@ class ModelTraj(nn.Module):
         if points and not fused:
             raise NotImplementedError("ModelTraj(shard=PointShard()) supports the reference's criterion on >= 3 waypoints")
         if fused and (self.fused_loss or points):
-            if points or self._shard.collective or self._occlusion is not None:
+            if points or self._shard.collective or self._occlusion is not None or self._prior is not None:
                 loss, self.rewards, vis, l2, length, smooth, clr = _TrajLoss.apply(self.poses, self.quats, self, wps_step)
             else:
                 plan = self._plan(wps_step)

@@ -127,14 +127,20 @@ def traj_forward(cloud, poses, quats, cam, ws, rig=None, flags=0, occ=None, lo_s
     return lo_sum, minmax
 
 
-def traj_reward(cloud, lo_sum, cam, ws, rewards=None, scalars=None, prefilled=False):
+def traj_reward(cloud, lo_sum, cam, ws, rewards=None, scalars=None, prefilled=False, prior=None):
     """-> (rewards[N], scalars[4] = mean, loss_vis, dloss/dreward, -).  prefilled: `rewards` holds 0.5 everywhere (traj_forward's
-    rewards_half): only the others are stored.  A (B, npad) lo_sum (traj_forward with traj_offsets): rewards (B,N), scalars (B,4)."""
+    rewards_half): only the others are stored.  A (B, npad) lo_sum (traj_forward with traj_offsets): rewards (B,N), scalars (B,4).
+    prior: a LogOddsPrior over the cloud (one trajectory, not prefilled): rewards = sigmoid(lo_sum + prior)."""
     lead = tuple(lo_sum.shape[:-1])
     if rewards is None:
         rewards = torch.empty((*lead, cloud.n), dtype=torch.float32, device=cloud.device)
     if scalars is None:
         scalars = torch.empty((*lead, 4), dtype=torch.float32, device=cloud.device)  # all four written by the kernel
+    if prior is not None:
+        with torch.cuda.device(cloud.device):
+            check(_lib.lib().tohip_traj_reward_prior(ptr(cloud.blob), ptr(lo_sum), cloud.n, cam.eps, int(bool(prefilled)), ptr(rewards),
+                                                     ptr(scalars), ptr(ws.buf), ws.bytes, ptr(prior.buf), stream_ptr()), "tohip_traj_reward_prior")
+        return rewards, scalars
     with torch.cuda.device(cloud.device):
         check(_lib.lib().tohip_traj_reward_multi(ptr(cloud.blob), ptr(lo_sum), cloud.n, lead[0] if lead else 1, cam.eps,
                                                  int(bool(prefilled)), ptr(rewards), ptr(scalars), ptr(ws.buf), ws.bytes, stream_ptr()),
@@ -142,12 +148,20 @@ def traj_reward(cloud, lo_sum, cam, ws, rewards=None, scalars=None, prefilled=Fa
     return rewards, scalars
 
 
-def traj_backward(cloud, n_wps, cam, ws, lo_sum, grad_rewards=None, scalars=None, gout=None, rig=None, flags=0, occ=None, n_traj=1):
+def traj_backward(cloud, n_wps, cam, ws, lo_sum, grad_rewards=None, scalars=None, gout=None, rig=None, flags=0, occ=None, n_traj=1,
+                  prior=None):
     """Gradients of the step whose traj_forward last used `ws` (same cloud, n_wps, rig, flags, occ).
     lo_sum: the (all-reduced) log-odds vector in packed order, as returned by traj_forward.  n_traj: the number of trajectories of
-    traj_forward's traj_offsets (gout: (B,) dL/d loss_vis per trajectory); the gradients are (n_wps,3), (n_wps,4) of all of them."""
+    traj_forward's traj_offsets (gout: (B,) dL/d loss_vis per trajectory); the gradients are (n_wps,3), (n_wps,4) of all of them.
+    prior: the LogOddsPrior the rewards were taken with (one trajectory): d reward / d lo_sum = r (1 - r) at lo_sum + prior."""
     pg = torch.empty((n_wps, 3), dtype=torch.float32, device=cloud.device)
     qg = torch.empty((n_wps, 4), dtype=torch.float32, device=cloud.device)
+    if prior is not None:
+        with torch.cuda.device(cloud.device):
+            check(_lib.lib().tohip_traj_backward_prior(ptr(cloud.blob), cloud.n, n_wps, cam.ref(), rig.ref() if rig is not None else _NULL_RIG,
+                                                       int(flags), ptr(occ), ptr(lo_sum), ptr(grad_rewards), ptr(scalars), ptr(gout), ptr(pg),
+                                                       ptr(qg), ptr(ws.buf), ws.bytes, ptr(prior.buf), stream_ptr()), "tohip_traj_backward_prior")
+        return pg, qg
     with torch.cuda.device(cloud.device):
         check(_lib.lib().tohip_traj_backward_multi(ptr(cloud.blob), cloud.n, n_wps, n_traj, cam.ref(),
                                                    rig.ref() if rig is not None else _NULL_RIG, int(flags), ptr(occ), ptr(lo_sum),
@@ -156,14 +170,21 @@ def traj_backward(cloud, n_wps, cam, ws, lo_sum, grad_rewards=None, scalars=None
     return pg, qg
 
 
-def traj_reward_backward(cloud, n_wps, cam, ws, lo_sum, gout, rewards=None, prefilled=False, rig=None, flags=0, occ=None):
+def traj_reward_backward(cloud, n_wps, cam, ws, lo_sum, gout, rewards=None, prefilled=False, rig=None, flags=0, occ=None, prior=None):
     """traj_reward + traj_backward of the fused visibility loss in two launches instead of three.
-    -> (rewards[N], scalars[4], poses_grad (n_wps,3), quats_grad (n_wps,4))."""
+    -> (rewards[N], scalars[4], poses_grad (n_wps,3), quats_grad (n_wps,4)).  prior: as traj_reward's (not prefilled)."""
     if rewards is None:
         rewards = torch.empty(cloud.n, dtype=torch.float32, device=cloud.device)
     scalars = torch.empty(4, dtype=torch.float32, device=cloud.device)
     pg = torch.empty((n_wps, 3), dtype=torch.float32, device=cloud.device)
     qg = torch.empty((n_wps, 4), dtype=torch.float32, device=cloud.device)
+    if prior is not None:
+        with torch.cuda.device(cloud.device):
+            check(_lib.lib().tohip_traj_reward_backward_prior(ptr(cloud.blob), cloud.n, n_wps, cam.ref(), rig.ref() if rig is not None else _NULL_RIG,
+                                                              int(flags), ptr(occ), ptr(lo_sum), cam.eps, int(bool(prefilled)), ptr(rewards),
+                                                              ptr(scalars), ptr(gout), ptr(pg), ptr(qg), ptr(ws.buf), ws.bytes, ptr(prior.buf),
+                                                              stream_ptr()), "tohip_traj_reward_backward_prior")
+        return rewards, scalars, pg, qg
     with torch.cuda.device(cloud.device):
         check(_lib.lib().tohip_traj_reward_backward(ptr(cloud.blob), cloud.n, n_wps, cam.ref(), rig.ref() if rig is not None else _NULL_RIG,
                                                     int(flags), ptr(occ), ptr(lo_sum), cam.eps, int(bool(prefilled)), ptr(rewards),
@@ -264,23 +285,35 @@ class WaypointShardStep:
         self.gout = torch.ones(1, **f32)
         self.rig_ref = rig.ref() if rig is not None else _NULL_RIG
 
-    def step(self, poses, quats, flags_extra=0, occ=None):
+    def step(self, poses, quats, flags_extra=0, occ=None, prior=None):
         """poses / quats: the whole trajectory, read in place; flags_extra: TOHIP_TRAJ_STRIDE bits (the evaluated waypoints are every
-        s-th row, this rank's first at row lo * s).  occ: the occlusion rows of this rank's waypoints.  -> (rewards, scalars,
-        poses_grad (n_wps,3), quats_grad (n_wps,4)), the same on every rank."""
+        s-th row, this rank's first at row lo * s).  occ: the occlusion rows of this rank's waypoints.  prior: a LogOddsPrior (the same
+        on every rank; added after the all-reduce).  -> (rewards, scalars, poses_grad (n_wps,3), quats_grad (n_wps,4)), the same on
+        every rank."""
         L, c, ws, local = _lib.lib(), self.cloud, self.ws, self.hi > self.lo
         at = self.lo * (((int(flags_extra) >> 8) & 0xffff) + 1)
         with torch.cuda.device(c.device):
             s = stream_ptr()
             if local:
+                # (with a prior every reward is stored: no 1/2 prefill)
                 check(L.tohip_traj_forward(ptr(c.blob), c.n, ptr(poses[at:]), ptr(quats[at:]), self.hi - self.lo, self.cam.ref(), self.rig_ref,
-                                           self.flags | int(flags_extra), ptr(occ), ptr(self.lo_sum), ptr(self.minmax), ptr(self.rewards),
-                                           ptr(ws.buf), ws.bytes, s), "forward")
+                                           self.flags | int(flags_extra), ptr(occ), ptr(self.lo_sum), ptr(self.minmax),
+                                           ptr(self.rewards if prior is None else None), ptr(ws.buf), ws.bytes, s), "forward")
                 ws.generation += 1
             else:
                 self.lo_sum.zero_()
             allreduce_log_odds(self.shard, c, ws, self.lo_sum, local=local)
-            if local:
+            if prior is not None:
+                if local:
+                    check(L.tohip_traj_reward_backward_prior(ptr(c.blob), c.n, self.hi - self.lo, self.cam.ref(), self.rig_ref, self.flags, ptr(occ),
+                                                             ptr(self.lo_sum), self.cam.eps, 0, ptr(self.rewards), ptr(self.scalars), ptr(self.gout),
+                                                             ptr(self.pg_loc), ptr(self.qg_loc), ptr(ws.buf), ws.bytes, ptr(prior.buf), s),
+                          "reward + backward (prior)")
+                    self.g[self.lo:self.hi, :3], self.g[self.lo:self.hi, 3:] = self.pg_loc, self.qg_loc
+                else:
+                    check(L.tohip_traj_reward_prior(ptr(c.blob), ptr(self.lo_sum), c.n, self.cam.eps, 0, ptr(self.rewards), ptr(self.scalars),
+                                                    ptr(ws.buf), ws.bytes, ptr(prior.buf), s), "reward (prior)")
+            elif local:
                 # rewards, their mean and the loss scalars share the backward's first launch
                 check(L.tohip_traj_reward_backward(ptr(c.blob), c.n, self.hi - self.lo, self.cam.ref(), self.rig_ref, self.flags, ptr(occ),
                                                    ptr(self.lo_sum), self.cam.eps, 1, ptr(self.rewards), ptr(self.scalars), ptr(self.gout),
@@ -295,30 +328,39 @@ class WaypointShardStep:
             self.g.zero_()   # the other ranks' rows must be zero again before the next sum
         return self.rewards, self.scalars, self.pg, self.qg
 
-    def forward(self, ps, qs, occ=None):
+    def forward(self, ps, qs, occ=None, prior=None):
         """ps / qs: this rank's evaluated waypoints (rows lo:hi, contiguous).  -> (lo_sum, rewards, scalars); the step's state stays
-        in the workspace for backward(), which needs ws.generation as it is now."""
+        in the workspace for backward(), which needs ws.generation as it is now.  prior: a LogOddsPrior, added to the all-reduced
+        log-odds where the rewards are taken (every reward stored: no 1/2 prefill)."""
         c = self.cloud
-        if self.hi > self.lo:
-            half = torch.empty(c.n, dtype=torch.float32, device=c.device)
+        local = self.hi > self.lo
+        half = torch.empty(c.n, dtype=torch.float32, device=c.device) if local and prior is None else None
+        if local:
             lo_sum, _ = traj_forward(c, ps, qs, self.cam, self.ws, self.rig, flags=self.flags, occ=occ, rewards_half=half)
         else:
-            half, lo_sum = None, torch.zeros(c.npad, dtype=torch.float32, device=c.device)
-        allreduce_log_odds(self.shard, c, self.ws, lo_sum, local=half is not None)
-        rewards, scalars = traj_reward(c, lo_sum, self.cam, self.ws, rewards=half, prefilled=half is not None)
+            lo_sum = torch.zeros(c.npad, dtype=torch.float32, device=c.device)
+        allreduce_log_odds(self.shard, c, self.ws, lo_sum, local=local)
+        rewards, scalars = traj_reward(c, lo_sum, self.cam, self.ws, rewards=half, prefilled=half is not None, prior=prior)
         return lo_sum, rewards, scalars
 
-    def backward(self, ps, qs, occ, gen, lo_sum, upstream):
+    def backward(self, ps, qs, occ, gen, lo_sum, upstream, prior=None, unit_sums=False):
         """-> the all-reduced gradient rows (n_wps,3), (n_wps,4) of the forward that left the workspace at generation `gen`.
         upstream: traj_backward's upstream keyword arguments, or None when no gradient reaches this rank's visibility term (the
         all-reduce is joined all the same).  If another forward has used the workspace since, that state is rebuilt first — same
-        inputs, same bits."""
+        inputs, same bits.  prior: the forward's LogOddsPrior.  unit_sums (with a prior and the fused visibility loss's upstream): the
+        sums are taken with unit dL/d reward and scaled once per waypoint (traj_reward_backward, the rewards taken again) — the
+        arithmetic of the one-call step, whose bits a prior model without collective or occlusion rows keeps for a zero prior."""
         g = torch.zeros((self.n_wps, 7), dtype=torch.float32, device=lo_sum.device)
         if upstream is not None and self.hi > self.lo:
             if self.ws.generation != gen:
                 traj_forward(self.cloud, ps, qs, self.cam, self.ws, self.rig, flags=self.flags, occ=occ)
-            g[self.lo:self.hi, :3], g[self.lo:self.hi, 3:] = traj_backward(self.cloud, ps.shape[0], self.cam, self.ws, lo_sum, rig=self.rig,
-                                                                         flags=self.flags, occ=occ, **upstream)
+            if prior is not None and unit_sums and "gout" in upstream:
+                _, _, pg, qg = traj_reward_backward(self.cloud, ps.shape[0], self.cam, self.ws, lo_sum, upstream["gout"], rig=self.rig,
+                                                    flags=self.flags, occ=occ, prior=prior)
+            else:
+                pg, qg = traj_backward(self.cloud, ps.shape[0], self.cam, self.ws, lo_sum, rig=self.rig, flags=self.flags, occ=occ,
+                                       prior=prior, **upstream)
+            g[self.lo:self.hi, :3], g[self.lo:self.hi, 3:] = pg, qg
         g = self.shard.allreduce_sum(g)
         return g[:, :3], g[:, 3:]
 
@@ -360,6 +402,55 @@ def check_clearance(radius, weight):
     if w > 0.0 and not (np.isfinite(r) and r > 0.0):
         raise ValueError(f"clearance_radius must be a finite number > 0 when clearance_weight > 0, got {radius!r}")
     return r, w
+
+
+def check_prior(prior, n, device=None):
+    """A log-odds prior for n points: an (n,) floating tensor, finite and >= 0 (on `device` when one is given) -> it as a contiguous
+    float32 tensor; ValueError otherwise.  >= 0 is the model's own range (p is clipped at 1/2), where the integer reward sum is exact."""
+    if not torch.is_tensor(prior) or not (prior.is_floating_point()):
+        raise ValueError(f"prior_log_odds must be a floating-point tensor, got {type(prior).__name__}"
+                         f"{'' if not torch.is_tensor(prior) else ' of ' + str(prior.dtype)}")
+    if prior.dim() != 1 or prior.shape[0] != n:
+        raise ValueError(f"prior_log_odds must have shape ({n},) (one entry per point), got {tuple(prior.shape)}")
+    dev = torch.device(device) if device is not None else None
+    if dev is not None and (prior.device.type != dev.type or (dev.index is not None and prior.device.index != dev.index)):
+        raise ValueError(f"prior_log_odds lives on {prior.device}, the model on {device}")
+    p = prior.detach().to(torch.float32).contiguous()
+    if not bool(torch.isfinite(p).all()):
+        raise ValueError("prior_log_odds must be finite (NaN or inf found)")
+    if not bool((p >= 0).all()):
+        raise ValueError("prior_log_odds must be >= 0 (a negative entry found): the prior is log-odds of coverage, p >= 1/2")
+    return p
+
+
+class LogOddsPrior:
+    """A per-point log-odds prior over a packed cloud, in the kernels' form (tohip_traj_prior_build: the prior and sigmoid(prior) in
+    packed order, the fixed-point sums the reward starts from).  `values`: the (N,) f32 prior in the caller's order."""
+
+    def __init__(self, cloud, values):
+        L = _lib.lib()
+        self.values = check_prior(values, cloud.n, cloud.device)
+        self.bytes = L.tohip_traj_prior_bytes(cloud.n)
+        self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=cloud.device)
+        status = torch.empty(1, dtype=torch.int32, device=cloud.device)
+        with torch.cuda.device(cloud.device):
+            check(L.tohip_traj_prior_build(ptr(cloud.blob), cloud.n, ptr(self.values), ptr(self.buf), self.bytes, ptr(status), stream_ptr()),
+                  "tohip_traj_prior_build")
+        if int(status.item()) != 0:   # (check_prior has seen the values already: the kernel's own word, read once per prior)
+            raise ValueError("prior_log_odds must be finite and >= 0")
+
+
+def traj_coverage(cloud, lo_sum, prior=None, clamp_max=None):
+    """The fused log-odds map (N,) f32 in the caller's order: prior + lo_sum (lo_sum in packed order as traj_forward writes it;
+    prior a LogOddsPrior or None), clamped to clamp_max when one is given (OctoMap's upper clamping threshold, >= 0)."""
+    c = float("inf") if clamp_max is None else float(clamp_max)
+    if not c >= 0.0:
+        raise ValueError(f"clamp_max must be a number >= 0 or None, got {clamp_max!r}")
+    out = torch.empty(cloud.n, dtype=torch.float32, device=cloud.device)
+    with torch.cuda.device(cloud.device):
+        check(_lib.lib().tohip_traj_coverage(ptr(cloud.blob), cloud.n, ptr(lo_sum), ptr(prior.buf) if prior is not None else None, c,
+                                             ptr(out), stream_ptr()), "tohip_traj_coverage")
+    return out
 
 
 def clearance(cloud, positions, radius, weight=0.0, grad=None, accumulate=False, want_value=False, terms=None):

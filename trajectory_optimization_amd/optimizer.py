@@ -131,12 +131,13 @@ def optimize_trajectory(model, n_opt_steps=10, lr_pose=0.1, lr_quat=0.0, rewards
     A step is ONE library call and FIVE launches (tohip_traj_opt_step): the waypoint selection is a stride of the first launch's
     reads, the regularisers and Adam's constants are one block more of the THIRD launch (the sparse kernel's: nothing launched
     before it may read them), the parameter update and the early-stop bookkeeping are the tail of the last launch's blocks.  A waypoint-sharded or occlusion-aware model has a collective or a hull
-    pass inside the step and goes through the separate calls (forward | all-reduce | reward + backward | step tail).
+    pass inside the step, and a model with a log-odds prior (prior_log_odds) a reward of its own: they go through the separate calls
+    (forward | all-reduce | reward + backward | step tail).
     (A HIP-graph replay of the step was measured slower than issuing its launches — a replay costs 10-16 us of host time by
     itself, five launches 17 us, and the GPU side is the same — so there is no graph variant.)"""
     if n_opt_steps <= 0:   # nothing to run: the model keeps its rewards and loss terms
         return TrajOptResult(0, False, [], 0.0, 0.0)
-    if model._shard.kind == "points" or model._shard.collective or model._occlusion is not None:
+    if model._shard.kind == "points" or model._shard.collective or model._occlusion is not None or model._prior is not None:
         return _optimize_trajectory_split(model, n_opt_steps, lr_pose, lr_quat, rewards_th, smoothness_th, vis_wps_dist, betas, adam_eps)
     run = _OptRun([model], n_opt_steps, lr_pose, lr_quat, rewards_th, smoothness_th, vis_wps_dist, betas, adam_eps)
     run.run(n_opt_steps)
@@ -178,7 +179,7 @@ def _optimize_trajectory_split(model, n_opt_steps, lr_pose, lr_quat, rewards_th,
         tail = L.tohip_traj_step_tail_multi
     with torch.cuda.device(dev):
         for _ in range(n_opt_steps):
-            kw = {}
+            kw = {} if model._prior is None else {"prior": model._prior}   # (waypoint placement: PointShard refuses a prior)
             if model._occlusion is not None and st.hi > st.lo:   # (waypoint placement: PointShard refuses occlusion)
                 own = slice(st.lo * step_w, (st.hi - 1) * step_w + 1, step_w)
                 kw["occ"] = model._occlusion_rows(poses[own].contiguous(), quats[own].contiguous())
@@ -208,8 +209,11 @@ def optimize_trajectories(models, n_opt_steps=10, lr_pose=0.1, lr_quat=0.0, rewa
     waypoints, each trajectory keeps its own log-odds vector, rewards, loss terms, Adam moments and early-stop state (a
     trajectory that has stopped stays put while the others go on).  Each model ends up exactly — bit for bit — where its own
     `optimize_trajectory` run would have put it.  Models: ModelTraj built on the same points with the same camera, rig and
-    mode, equal numbers of waypoints and the same waypoint step; no sharding, no occlusion.  -> [TrajOptResult]."""
+    mode, equal numbers of waypoints and the same waypoint step; no sharding, no occlusion, no prior_log_odds.  -> [TrajOptResult]."""
     m0 = models[0]
+    if any(m._prior is not None for m in models):
+        raise ValueError("optimize_trajectories: a model with a log-odds prior (prior_log_odds) is not supported; run "
+                         "optimize_trajectory on it")
     cloud, cam, rig = m0._cloud, m0._cam, m0._rig
     W = m0.poses.shape[0]
     step_w = m0._wps_step(vis_wps_dist)

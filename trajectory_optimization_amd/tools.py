@@ -190,3 +190,20 @@ def trajectory_clearance(points_or_packed_cloud, poses, radius):
     if poses.device != cloud.device:
         poses = poses.to(cloud.device)
     return ops.clearance(cloud, poses, radius)
+
+
+def fuse_log_odds(*maps, clamp_max=None):
+    """OctoMap's fusion of independent log-odds maps of one cloud (ModelTraj.coverage_log_odds of two robots' plans, or a map and a
+    new plan's): their sum, clamped to clamp_max (its upper threshold; None: none) -> (N,) f32, a valid prior_log_odds when each map
+    is one.  Maps of the same cloud in the same point order."""
+    if not maps:
+        raise ValueError("fuse_log_odds: no map given")
+    out = torch.as_tensor(maps[0], dtype=torch.float32).clone()
+    for m in maps[1:]:
+        m = torch.as_tensor(m, dtype=torch.float32, device=out.device)
+        if m.shape != out.shape:
+            raise ValueError(f"fuse_log_odds: maps of {tuple(out.shape)} and {tuple(m.shape)} points")
+        out += m
+    if clamp_max is not None:
+        out.clamp_(max=float(clamp_max))
+    return out
