@@ -125,7 +125,9 @@ class _PoseObservations(torch.autograd.Function):
     def forward(ctx, trans, quat, model, mask, occ):
         t = trans.detach().contiguous()
         q = quat.detach().contiguous()
-        obs, _ = ops.pose_forward(model._cloud, t, q, model._cam, model._ws, mask, occ=occ)
+        plan = model._plan
+        obs = torch.empty(plan.n, **plan.f32)
+        plan.forward(t, q, mask, occ, obs, torch.empty(4, **plan.f32))
         ctx.model, ctx.mask, ctx.occ = model, mask, occ
         ctx.save_for_backward(t, q)
         return obs
@@ -133,8 +135,7 @@ class _PoseObservations(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_obs):
         t, q = ctx.saved_tensors
-        m = ctx.model
-        tg, qg = ops.pose_backward(m._cloud, t, q, m._cam, m._ws, ctx.mask, grad_obs=grad_obs.contiguous(), occ=ctx.occ)
+        tg, qg = ctx.model._plan.backward(t, q, ctx.mask, ctx.occ, grad_obs.contiguous())
         return tg, qg, None, None, None
 
 
@@ -154,10 +155,10 @@ class _PoseLoss(torch.autograd.Function):
         want_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         if want_grad:
             grads = torch.empty(8, **plan.f32)   # d loss / d trans [0:3], d loss / d quat [4:8]
-            plan.forward_backward(trans, quat, mask, obs, scalars, grads, occ)
+            plan.forward_backward(trans, quat, mask, occ, obs, scalars, grads)
         else:
             grads = None
-            plan.forward(trans, quat, mask, obs, scalars, occ)
+            plan.forward(trans, quat, mask, occ, obs, scalars)
         ctx.model, ctx.mask, ctx.occ, ctx.grads = model, mask, occ, grads
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(trans, quat, scalars)   # by reference: an in-place edit before backward() raises, as for torch's ops
@@ -169,7 +170,6 @@ class _PoseLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, g_obs, _g_scalars):
         t, q, scalars = ctx.saved_tensors
-        m = ctx.model
         if g_loss is None and g_obs is None:
             return None, None, None, None, None
         if g_obs is None:
@@ -178,7 +178,7 @@ class _PoseLoss(torch.autograd.Function):
         g = g_obs.to(torch.float32)
         if g_loss is not None:
             g = g - g_loss.to(torch.float32) * scalars[1] * scalars[1]  # d loss / d observation_n = -loss^2
-        tg, qg = ops.pose_backward(m._cloud, t, q, m._cam, m._ws, ctx.mask, grad_obs=g.contiguous(), occ=ctx.occ)
+        tg, qg = ctx.model._plan.backward(t, q, ctx.mask, ctx.occ, g.contiguous())
         return tg, qg, None, None, None
 
 
@@ -192,7 +192,7 @@ class _TrajRewards(torch.autograd.Function):
         st = model._waypoint_step(p.shape[0])
         ps, qs = p[st.lo:st.hi].clone(), q[st.lo:st.hi].clone()  # own copies: the step's inputs, whatever happens to the Parameters
         # occlusion masks are piecewise constant in the poses: computed per forward, not differentiated
-        occ = model._occlusion_rows(ps, qs) if st.hi > st.lo and model._occlusion is not None else None
+        occ = model._own_occlusion_rows(st, p, q)
         lo_sum, rewards, _ = st.forward(ps, qs, occ, prior=model._prior)
         ctx.step, ctx.occ, ctx.gen, ctx.prior = st, occ, st.ws.generation, model._prior
         ctx.save_for_backward(ps, qs, lo_sum)
@@ -217,12 +217,11 @@ def _regularizers(model, p_all, scalars, clr_terms=None):
     reg_terms = torch.empty((3, W, 3), dtype=torch.float32, device=dev)
     args = (ptr(p_all), ptr(model.poses0), W, float(model.smoothness_weight), float(model.traj_length_weight), float(model.eps),
             ptr(scalars), ptr(terms), ptr(reg_sum), 0, None, ptr(reg_terms))
-    if clr_terms is None:
-        name, extra = "tohip_traj_regularizers", ()
-    else:
-        name, extra = "tohip_traj_regularizers_clearance", (float(model.clearance_weight), ptr(clr_terms))
+    L = _lib.lib()
+    fn, extra = ((L.tohip_traj_regularizers, ()) if clr_terms is None else
+                 (L.tohip_traj_regularizers_clearance, (float(model.clearance_weight), ptr(clr_terms))))
     with torch.cuda.device(dev):
-        check(getattr(_lib.lib(), name)(*args, *extra, stream_ptr()), name)
+        check(fn(*args, *extra, stream_ptr()), fn.__name__)
     return terms, reg_sum, reg_terms
 
 
@@ -323,12 +322,12 @@ class _TrajLoss(torch.autograd.Function):
             p_eval = p_all[::step_w].contiguous() if step_w > 1 else p_all
             q_eval = q_all[::step_w].contiguous() if step_w > 1 else q_all
             ps, qs = p_eval[st.lo:st.hi].clone(), q_eval[st.lo:st.hi].clone()  # own copies: the step's inputs, whatever happens to the Parameters
-            occ = model._occlusion_rows(ps, qs) if st.hi > st.lo and model._occlusion is not None else None
+            occ = model._own_occlusion_rows(st, p_eval, q_eval)
             lo_sum, rewards, scalars = st.forward(ps, qs, occ, prior=model._prior)
             ctx.occ, ctx.gen, ctx.prior = occ, st.ws.generation, model._prior
             # a prior model that would take the one-call plan without its prior keeps the plan's gradient arithmetic (unit sums
             # scaled once per waypoint): a zero prior changes no bit
-            ctx.unit_sums = not (model._shard.collective or model._occlusion is not None)
+            ctx.unit_sums = not model._needs_split_step(prior=False)
             saved = (ps, qs, lo_sum, scalars)
         clr_rows = clr_terms = None
         if model._clearance_on:   # every rank: all W waypoints, the whole cloud
@@ -509,47 +508,6 @@ class _FastBackwardPose(_FastBackward):
         return g[0:3].reshape(1, 3).clone(), g[4:8].reshape(1, 4).clone()
 
 
-class _PosePlan:
-    """ModelPose's two library calls with everything constant converted once (the loop is host-bound)."""
-
-    def __init__(self, model):
-        L = _lib.lib()
-        self.fwd, self.bwd, self.fwdbwd = L.tohip_pose_forward, L.tohip_pose_backward, L.tohip_pose_forward_backward
-        # the same calls with an occlusion bit row in the mask's place
-        self.fwd_occ, self.bwd_occ, self.fwdbwd_occ = L.tohip_pose_forward_bits, L.tohip_pose_backward_bits, L.tohip_pose_forward_backward_bits
-        self.blob, self.n = model._cloud.blob.data_ptr(), model._cloud.n
-        self.cam = model._cam.ref()
-        self.ws, self.wsb = model._ws.buf.data_ptr(), model._ws.bytes
-        dev = model.device
-        self.dev, self.dev_index = dev, _lib.device_index(dev)
-        self.f32 = dict(dtype=torch.float32, device=dev)
-        self.one = torch.ones(1, **self.f32)
-        self.model = model
-
-    def forward(self, t, q, mask, obs, scalars, occ=None):
-        fn, m = (self.fwd_occ, occ) if occ is not None else (self.fwd, mask)
-        rc = _lib.on_device(self.dev_index, fn, self.blob, self.n, t.data_ptr(), q.data_ptr(), self.cam,
-                            m.data_ptr() if m is not None else None, obs.data_ptr(), scalars.data_ptr(), self.ws, self.wsb)
-        if rc:
-            check(rc, "tohip_pose_forward_bits" if occ is not None else "tohip_pose_forward")
-
-    def forward_backward(self, t, q, mask, obs, scalars, grads, occ=None):
-        gp = grads.data_ptr()
-        fn, m = (self.fwdbwd_occ, occ) if occ is not None else (self.fwdbwd, mask)
-        rc = _lib.on_device(self.dev_index, fn, self.blob, self.n, t.data_ptr(), q.data_ptr(), self.cam,
-                            m.data_ptr() if m is not None else None, obs.data_ptr(), scalars.data_ptr(), None, gp, gp + 16, self.ws, self.wsb)
-        if rc:
-            check(rc, "tohip_pose_forward_backward_bits" if occ is not None else "tohip_pose_forward_backward")
-
-    def backward(self, t, q, mask, scalars, gout, tg, qg, occ=None):
-        fn, m = (self.bwd_occ, occ) if occ is not None else (self.bwd, mask)
-        rc = _lib.on_device(self.dev_index, fn, self.blob, self.n, t.data_ptr(), q.data_ptr(), self.cam,
-                            m.data_ptr() if m is not None else None, None, scalars.data_ptr(), gout.data_ptr(), tg.data_ptr(),
-                            qg.data_ptr(), self.ws, self.wsb)
-        if rc:
-            check(rc, "tohip_pose_backward_bits" if occ is not None else "tohip_pose_backward")
-
-
 def _plain_grad(p):
     g = p.grad
     return g.dtype == torch.float32 and g.device == p.device and g.shape == p.shape and not g.requires_grad and not g.is_sparse
@@ -708,7 +666,7 @@ class ModelPose(nn.Module):
         self.occlusion_rebuilds = 0   # full rebuilds: bookkeeping for tools and tests
         self.fused_loss = True  # forward() as one autograd node; False (or an overridden criterion): observations node + torch ops
         self.fast_backward = True   # a plain `loss.backward()` on what forward() returned runs on the calling thread
-        self._plan = _PosePlan(self)
+        self._plan = ops.PosePlan(self._cloud, self._cam, self._ws)
         for p in (self.trans, self.quat):
             tag_parameter(p)   # torch.optim.Adam.step() MAY update them with one launch — once the caller opts in:
         if fast_adam:          # fast_adam=True here, optimizer.accelerate_torch_adam(True) or accelerate_torch_adam(opt) (nothing is hooked otherwise)
@@ -1072,6 +1030,14 @@ class ModelTraj(nn.Module):
         self._occ_cache = (rows, key, age)
         return rows
 
+    def _own_occlusion_rows(self, st, poses, quats, step_w=1):
+        """The occlusion rows of the waypoints the waypoint-placed step `st` owns — rows lo .. hi-1 of the evaluated waypoints, which
+        are every step_w-th row of poses / quats — or None: no occlusion, or no waypoint on this rank."""
+        if self._occlusion is None or st.hi <= st.lo:
+            return None
+        own = slice(st.lo * step_w, (st.hi - 1) * step_w + 1, step_w)
+        return self._occlusion_rows(poses[own].contiguous(), quats[own].contiguous())
+
     def _build_occlusion_rows(self, ps, qs):
         if self._rig is not None:
             qn = qs / qs.norm(dim=1, keepdim=True).clamp_min(1e-12)
@@ -1088,6 +1054,12 @@ class ModelTraj(nn.Module):
             ps, qs = vt.contiguous(), vq.contiguous()
         return ops.occlusion_bits(self._cloud, self.points, ps, qs, self._cam, self._occlusion_limits[0],
                                   self._occlusion_limits[1], self._occlusion)
+
+    def _needs_split_step(self, prior=True):
+        """Whether the visibility step goes through the separate calls (ops.WaypointShardStep / PointShardStep) instead of the
+        one-call library step: point sharding, a collective, occlusion rows or (prior=True) a log-odds prior."""
+        return (self._shard.kind == "points" or self._shard.collective or self._occlusion is not None or
+                (prior and self._prior is not None))
 
     def _workspace(self, n_local_wps):
         v = n_local_wps * (self._rig.n_cams if self._rig is not None else 1)
@@ -1145,7 +1117,7 @@ class ModelTraj(nn.Module):
         if points and not fused:
             raise NotImplementedError("ModelTraj(shard=PointShard()) supports the reference's criterion on >= 3 waypoints")
         if fused and (self.fused_loss or points):
-            if points or self._shard.collective or self._occlusion is not None or self._prior is not None:
+            if self._needs_split_step():
                 loss, self.rewards, vis, l2, length, smooth, clr = _TrajLoss.apply(self.poses, self.quats, self, wps_step)
             else:
                 plan = self._plan(wps_step)

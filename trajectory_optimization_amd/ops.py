@@ -105,6 +105,31 @@ class TrajWorkspace:
 DENSE = 1  # TOHIP_TRAJ_DENSE
 
 
+def _rig_ref(rig):
+    return rig.ref() if rig is not None else _NULL_RIG
+
+
+# The two launches the wrappers below share with WaypointShardStep.step (which hands in buffers allocated once); the caller has made
+# the cloud's device current.  Here and in the wrappers a prior selects the _prior twin of an entry, which takes the same arguments
+# and prior_buf after them.
+
+def _forward(c, poses, quats, W, traj_offsets, B, cam, rig_ref, flags, occ, lo_sum, minmax, rewards_half, ws, stream):
+    ws.generation += 1
+    check(_lib.lib().tohip_traj_forward_multi(ptr(c.blob), c.n, ptr(poses), ptr(quats), W, ptr(traj_offsets), B, cam.ref(), rig_ref, flags,
+                                              ptr(occ), ptr(lo_sum), ptr(minmax), ptr(rewards_half), ptr(ws.buf), ws.bytes, stream),
+          "tohip_traj_forward_multi")
+
+
+def _reward_backward(c, W, cam, rig_ref, flags, occ, lo_sum, prefilled, rewards, scalars, gout, pg, qg, ws, prior, stream):
+    L = _lib.lib()
+    args = (ptr(c.blob), c.n, W, cam.ref(), rig_ref, flags, ptr(occ), ptr(lo_sum), cam.eps, prefilled, ptr(rewards), ptr(scalars), ptr(gout),
+            ptr(pg), ptr(qg), ptr(ws.buf), ws.bytes)
+    if prior is None:
+        check(L.tohip_traj_reward_backward(*args, stream), "tohip_traj_reward_backward")
+    else:
+        check(L.tohip_traj_reward_backward_prior(*args, ptr(prior.buf), stream), "tohip_traj_reward_backward_prior")
+
+
 def traj_forward(cloud, poses, quats, cam, ws, rig=None, flags=0, occ=None, lo_sum=None, minmax=None, rewards_half=None,
                  traj_offsets=None):
     """-> (lo_sum[npad] in packed order (first N valid), minmax[V,2]) for the given waypoints (this rank's shard).
@@ -119,11 +144,8 @@ def traj_forward(cloud, poses, quats, cam, ws, rig=None, flags=0, occ=None, lo_s
         lo_sum = torch.empty((B, cloud.npad) if traj_offsets is not None else cloud.npad, dtype=torch.float32, device=cloud.device)
     if minmax is None:
         minmax = torch.empty((W * C, 2), dtype=torch.float32, device=cloud.device)
-    ws.generation += 1
     with torch.cuda.device(cloud.device):
-        check(_lib.lib().tohip_traj_forward_multi(ptr(cloud.blob), cloud.n, ptr(poses), ptr(quats), W, ptr(traj_offsets), B, cam.ref(),
-                                                  rig.ref() if rig is not None else _NULL_RIG, int(flags), ptr(occ), ptr(lo_sum), ptr(minmax),
-                                                  ptr(rewards_half), ptr(ws.buf), ws.bytes, stream_ptr()), "tohip_traj_forward_multi")
+        _forward(cloud, poses, quats, W, traj_offsets, B, cam, _rig_ref(rig), int(flags), occ, lo_sum, minmax, rewards_half, ws, stream_ptr())
     return lo_sum, minmax
 
 
@@ -136,15 +158,13 @@ def traj_reward(cloud, lo_sum, cam, ws, rewards=None, scalars=None, prefilled=Fa
         rewards = torch.empty((*lead, cloud.n), dtype=torch.float32, device=cloud.device)
     if scalars is None:
         scalars = torch.empty((*lead, 4), dtype=torch.float32, device=cloud.device)  # all four written by the kernel
-    if prior is not None:
-        with torch.cuda.device(cloud.device):
-            check(_lib.lib().tohip_traj_reward_prior(ptr(cloud.blob), ptr(lo_sum), cloud.n, cam.eps, int(bool(prefilled)), ptr(rewards),
-                                                     ptr(scalars), ptr(ws.buf), ws.bytes, ptr(prior.buf), stream_ptr()), "tohip_traj_reward_prior")
-        return rewards, scalars
+    L, args = _lib.lib(), (ptr(cloud.blob), ptr(lo_sum), cloud.n)
+    rest = (cam.eps, int(bool(prefilled)), ptr(rewards), ptr(scalars), ptr(ws.buf), ws.bytes)
     with torch.cuda.device(cloud.device):
-        check(_lib.lib().tohip_traj_reward_multi(ptr(cloud.blob), ptr(lo_sum), cloud.n, lead[0] if lead else 1, cam.eps,
-                                                 int(bool(prefilled)), ptr(rewards), ptr(scalars), ptr(ws.buf), ws.bytes, stream_ptr()),
-              "tohip_traj_reward_multi")
+        if prior is None:
+            check(L.tohip_traj_reward_multi(*args, lead[0] if lead else 1, *rest, stream_ptr()), "tohip_traj_reward_multi")
+        else:
+            check(L.tohip_traj_reward_prior(*args, *rest, ptr(prior.buf), stream_ptr()), "tohip_traj_reward_prior")
     return rewards, scalars
 
 
@@ -156,17 +176,14 @@ def traj_backward(cloud, n_wps, cam, ws, lo_sum, grad_rewards=None, scalars=None
     prior: the LogOddsPrior the rewards were taken with (one trajectory): d reward / d lo_sum = r (1 - r) at lo_sum + prior."""
     pg = torch.empty((n_wps, 3), dtype=torch.float32, device=cloud.device)
     qg = torch.empty((n_wps, 4), dtype=torch.float32, device=cloud.device)
-    if prior is not None:
-        with torch.cuda.device(cloud.device):
-            check(_lib.lib().tohip_traj_backward_prior(ptr(cloud.blob), cloud.n, n_wps, cam.ref(), rig.ref() if rig is not None else _NULL_RIG,
-                                                       int(flags), ptr(occ), ptr(lo_sum), ptr(grad_rewards), ptr(scalars), ptr(gout), ptr(pg),
-                                                       ptr(qg), ptr(ws.buf), ws.bytes, ptr(prior.buf), stream_ptr()), "tohip_traj_backward_prior")
-        return pg, qg
+    L, args = _lib.lib(), (ptr(cloud.blob), cloud.n, n_wps)
+    rest = (cam.ref(), _rig_ref(rig), int(flags), ptr(occ), ptr(lo_sum), ptr(grad_rewards), ptr(scalars), ptr(gout), ptr(pg), ptr(qg),
+            ptr(ws.buf), ws.bytes)
     with torch.cuda.device(cloud.device):
-        check(_lib.lib().tohip_traj_backward_multi(ptr(cloud.blob), cloud.n, n_wps, n_traj, cam.ref(),
-                                                   rig.ref() if rig is not None else _NULL_RIG, int(flags), ptr(occ), ptr(lo_sum),
-                                                   ptr(grad_rewards), ptr(scalars), ptr(gout), ptr(pg), ptr(qg), ptr(ws.buf), ws.bytes,
-                                                   stream_ptr()), "tohip_traj_backward_multi")
+        if prior is None:
+            check(L.tohip_traj_backward_multi(*args, n_traj, *rest, stream_ptr()), "tohip_traj_backward_multi")
+        else:
+            check(L.tohip_traj_backward_prior(*args, *rest, ptr(prior.buf), stream_ptr()), "tohip_traj_backward_prior")
     return pg, qg
 
 
@@ -178,18 +195,9 @@ def traj_reward_backward(cloud, n_wps, cam, ws, lo_sum, gout, rewards=None, pref
     scalars = torch.empty(4, dtype=torch.float32, device=cloud.device)
     pg = torch.empty((n_wps, 3), dtype=torch.float32, device=cloud.device)
     qg = torch.empty((n_wps, 4), dtype=torch.float32, device=cloud.device)
-    if prior is not None:
-        with torch.cuda.device(cloud.device):
-            check(_lib.lib().tohip_traj_reward_backward_prior(ptr(cloud.blob), cloud.n, n_wps, cam.ref(), rig.ref() if rig is not None else _NULL_RIG,
-                                                              int(flags), ptr(occ), ptr(lo_sum), cam.eps, int(bool(prefilled)), ptr(rewards),
-                                                              ptr(scalars), ptr(gout), ptr(pg), ptr(qg), ptr(ws.buf), ws.bytes, ptr(prior.buf),
-                                                              stream_ptr()), "tohip_traj_reward_backward_prior")
-        return rewards, scalars, pg, qg
     with torch.cuda.device(cloud.device):
-        check(_lib.lib().tohip_traj_reward_backward(ptr(cloud.blob), cloud.n, n_wps, cam.ref(), rig.ref() if rig is not None else _NULL_RIG,
-                                                    int(flags), ptr(occ), ptr(lo_sum), cam.eps, int(bool(prefilled)), ptr(rewards),
-                                                    ptr(scalars), ptr(gout), ptr(pg), ptr(qg), ptr(ws.buf), ws.bytes, stream_ptr()),
-              "tohip_traj_reward_backward")
+        _reward_backward(cloud, n_wps, cam, _rig_ref(rig), int(flags), occ, lo_sum, int(bool(prefilled)), rewards, scalars, gout, pg, qg, ws,
+                         prior, stream_ptr())
     return rewards, scalars, pg, qg
 
 
@@ -216,9 +224,9 @@ def traj_forward_backward(cloud, poses, quats, cam, ws, gout, rig=None, flags=0,
     ws.generation += 1
     with torch.cuda.device(dev):
         check(_lib.lib().tohip_traj_forward_backward_multi(ptr(cloud.blob), cloud.n, ptr(poses), ptr(quats), W, ptr(traj_offsets), B, cam.ref(),
-                                                           rig.ref() if rig is not None else _NULL_RIG, int(flags), ptr(occ), ptr(lo_sum),
-                                                           ptr(minmax), ptr(rewards), ptr(scalars), ptr(gout), ptr(pg), ptr(qg), ptr(ws.buf),
-                                                           ws.bytes, stream_ptr()), "tohip_traj_forward_backward_multi")
+                                                           _rig_ref(rig), int(flags), ptr(occ), ptr(lo_sum), ptr(minmax), ptr(rewards),
+                                                           ptr(scalars), ptr(gout), ptr(pg), ptr(qg), ptr(ws.buf), ws.bytes, stream_ptr()),
+              "tohip_traj_forward_backward_multi")
     return rewards, scalars, pg, qg, lo_sum, minmax
 
 
@@ -243,7 +251,7 @@ class PointShardStep:
         check(L.tohip_traj_extrema_view(cloud.n, V, ptr(ws.buf), ws.bytes, ctypes.byref(words), ctypes.byref(n_words)), "tohip_traj_extrema_view")
         off = words.value - ws.buf.data_ptr()
         self.extrema = ws.buf[off:off + 4 * n_words.value].view(torch.int32)   # the workspace's own words: reduced in place
-        self.rig_ref = rig.ref() if rig is not None else _NULL_RIG
+        self.rig_ref = _rig_ref(rig)
 
     def step(self, poses, quats, flags_extra=0):
         """flags_extra: TOHIP_TRAJ_STRIDE bits (the evaluated waypoints as every step-th row of poses / quats, read in place)."""
@@ -283,45 +291,31 @@ class WaypointShardStep:
         self.g = torch.zeros((self.n_wps, 7), **f32)   # rows outside this rank's range stay zero
         self.pg, self.qg = torch.empty((self.n_wps, 3), **f32), torch.empty((self.n_wps, 4), **f32)
         self.gout = torch.ones(1, **f32)
-        self.rig_ref = rig.ref() if rig is not None else _NULL_RIG
+        self.rig_ref = _rig_ref(rig)
 
     def step(self, poses, quats, flags_extra=0, occ=None, prior=None):
         """poses / quats: the whole trajectory, read in place; flags_extra: TOHIP_TRAJ_STRIDE bits (the evaluated waypoints are every
         s-th row, this rank's first at row lo * s).  occ: the occlusion rows of this rank's waypoints.  prior: a LogOddsPrior (the same
         on every rank; added after the all-reduce).  -> (rewards, scalars, poses_grad (n_wps,3), quats_grad (n_wps,4)), the same on
         every rank."""
-        L, c, ws, local = _lib.lib(), self.cloud, self.ws, self.hi > self.lo
+        c, ws, n_loc = self.cloud, self.ws, self.hi - self.lo
         at = self.lo * (((int(flags_extra) >> 8) & 0xffff) + 1)
         with torch.cuda.device(c.device):
             s = stream_ptr()
-            if local:
+            if n_loc:
                 # (with a prior every reward is stored: no 1/2 prefill)
-                check(L.tohip_traj_forward(ptr(c.blob), c.n, ptr(poses[at:]), ptr(quats[at:]), self.hi - self.lo, self.cam.ref(), self.rig_ref,
-                                           self.flags | int(flags_extra), ptr(occ), ptr(self.lo_sum), ptr(self.minmax),
-                                           ptr(self.rewards if prior is None else None), ptr(ws.buf), ws.bytes, s), "forward")
-                ws.generation += 1
+                _forward(c, poses[at:], quats[at:], n_loc, None, 1, self.cam, self.rig_ref, self.flags | int(flags_extra), occ, self.lo_sum,
+                         self.minmax, self.rewards if prior is None else None, ws, s)
             else:
                 self.lo_sum.zero_()
-            allreduce_log_odds(self.shard, c, ws, self.lo_sum, local=local)
-            if prior is not None:
-                if local:
-                    check(L.tohip_traj_reward_backward_prior(ptr(c.blob), c.n, self.hi - self.lo, self.cam.ref(), self.rig_ref, self.flags, ptr(occ),
-                                                             ptr(self.lo_sum), self.cam.eps, 0, ptr(self.rewards), ptr(self.scalars), ptr(self.gout),
-                                                             ptr(self.pg_loc), ptr(self.qg_loc), ptr(ws.buf), ws.bytes, ptr(prior.buf), s),
-                          "reward + backward (prior)")
-                    self.g[self.lo:self.hi, :3], self.g[self.lo:self.hi, 3:] = self.pg_loc, self.qg_loc
-                else:
-                    check(L.tohip_traj_reward_prior(ptr(c.blob), ptr(self.lo_sum), c.n, self.cam.eps, 0, ptr(self.rewards), ptr(self.scalars),
-                                                    ptr(ws.buf), ws.bytes, ptr(prior.buf), s), "reward (prior)")
-            elif local:
+            allreduce_log_odds(self.shard, c, ws, self.lo_sum, local=n_loc > 0)
+            if n_loc:
                 # rewards, their mean and the loss scalars share the backward's first launch
-                check(L.tohip_traj_reward_backward(ptr(c.blob), c.n, self.hi - self.lo, self.cam.ref(), self.rig_ref, self.flags, ptr(occ),
-                                                   ptr(self.lo_sum), self.cam.eps, 1, ptr(self.rewards), ptr(self.scalars), ptr(self.gout),
-                                                   ptr(self.pg_loc), ptr(self.qg_loc), ptr(ws.buf), ws.bytes, s), "reward + backward")
+                _reward_backward(c, n_loc, self.cam, self.rig_ref, self.flags, occ, self.lo_sum, int(prior is None), self.rewards, self.scalars,
+                                 self.gout, self.pg_loc, self.qg_loc, ws, prior, s)
                 self.g[self.lo:self.hi, :3], self.g[self.lo:self.hi, 3:] = self.pg_loc, self.qg_loc
             else:
-                check(L.tohip_traj_reward(ptr(c.blob), ptr(self.lo_sum), c.n, self.cam.eps, 0, ptr(self.rewards), ptr(self.scalars),
-                                          ptr(ws.buf), ws.bytes, s), "reward")
+                traj_reward(c, self.lo_sum, self.cam, ws, self.rewards, self.scalars, prior=prior)
             self.shard.allreduce_sum(self.g)
             self.pg.copy_(self.g[:, :3])
             self.qg.copy_(self.g[:, 3:])
@@ -512,18 +506,58 @@ def _occ_row(cloud, occ, rows=1, mask=None):
     return occ
 
 
+class PosePlan:
+    """The pose visibility calls over one cloud, camera and workspace, with everything constant converted once (ModelPose's loop is
+    host-bound): ModelPose's autograd nodes and the pose_* wrappers below go through it.  Each call takes a float mask or, in its
+    place, occlusion bit rows `occ` (the _bits twin then runs).  Nothing is checked here: the wrappers check their arguments."""
+
+    def __init__(self, cloud, cam, ws):
+        self.L = _lib.lib()
+        self.blob, self.n = cloud.blob.data_ptr(), cloud.n
+        self.cam = cam.ref()
+        self.ws, self.wsb = ws.buf.data_ptr(), ws.bytes
+        self.dev_index = _lib.device_index(cloud.device)
+        self.f32 = dict(dtype=torch.float32, device=cloud.device)
+
+    def forward(self, t, q, mask, occ, obs, scalars):
+        fn, m = (self.L.tohip_pose_forward_bits, occ) if occ is not None else (self.L.tohip_pose_forward, mask)
+        rc = _lib.on_device(self.dev_index, fn, self.blob, self.n, t.data_ptr(), q.data_ptr(), self.cam,
+                            m.data_ptr() if m is not None else None, obs.data_ptr(), scalars.data_ptr(), self.ws, self.wsb)
+        if rc:
+            check(rc, fn.__name__)
+
+    def forward_backward(self, t, q, mask, occ, obs, scalars, grads, gout=None):
+        """grads: 8 floats, d loss / d trans at [0:3] and d loss / d quat at [4:8] (times gout when one is given)."""
+        fn, m = (self.L.tohip_pose_forward_backward_bits, occ) if occ is not None else (self.L.tohip_pose_forward_backward, mask)
+        gp = grads.data_ptr()
+        rc = _lib.on_device(self.dev_index, fn, self.blob, self.n, t.data_ptr(), q.data_ptr(), self.cam, m.data_ptr() if m is not None else None,
+                            obs.data_ptr(), scalars.data_ptr(), gout.data_ptr() if gout is not None else None, gp, gp + 16, self.ws, self.wsb)
+        if rc:
+            check(rc, fn.__name__)
+
+    def backward(self, t, q, mask, occ, grad_obs=None, scalars=None, gout=None):
+        """-> fresh (trans_grad (1,3), quat_grad (1,4))."""
+        fn, m = (self.L.tohip_pose_backward_bits, occ) if occ is not None else (self.L.tohip_pose_backward, mask)
+        tg, qg = torch.empty((1, 3), **self.f32), torch.empty((1, 4), **self.f32)
+        rc = _lib.on_device(self.dev_index, fn, self.blob, self.n, t.data_ptr(), q.data_ptr(), self.cam, m.data_ptr() if m is not None else None,
+                            ptr(grad_obs), ptr(scalars), ptr(gout), tg.data_ptr(), qg.data_ptr(), self.ws, self.wsb)
+        if rc:
+            check(rc, fn.__name__)
+        return tg, qg
+
+    def forward_backward_multi(self, t, q, B, mask, occ, obs, scalars, tg, qg):
+        fn, m = (self.L.tohip_pose_forward_backward_multi_bits, occ) if occ is not None else (self.L.tohip_pose_forward_backward_multi, mask)
+        rc = _lib.on_device(self.dev_index, fn, self.blob, self.n, t.data_ptr(), q.data_ptr(), B, self.cam, ptr(m), ptr(obs), ptr(scalars),
+                            None, ptr(tg), ptr(qg), self.ws, self.wsb)
+        if rc:
+            check(rc, fn.__name__)
+
+
 def pose_forward(cloud, trans, quat, cam, ws, mask=None, occ=None):
     """occ: the pose's occlusion bit row (1, npad/32) instead of a float mask (tohip_pose_forward_bits)."""
     obs = torch.empty(cloud.n, dtype=torch.float32, device=cloud.device)
     scalars = torch.zeros(4, dtype=torch.float32, device=cloud.device)
-    with torch.cuda.device(cloud.device):
-        if occ is not None:
-            check(_lib.lib().tohip_pose_forward_bits(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), cam.ref(), ptr(_occ_row(cloud, occ, mask=mask)),
-                                                     ptr(obs), ptr(scalars), ptr(ws.buf), ws.bytes, stream_ptr()), "tohip_pose_forward_bits")
-        else:
-            check(_lib.lib().tohip_pose_forward(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), cam.ref(), ptr(mask),
-                                                ptr(obs), ptr(scalars), ptr(ws.buf), ws.bytes, stream_ptr()),
-                  "tohip_pose_forward")
+    PosePlan(cloud, cam, ws).forward(trans, quat, mask, occ if occ is None else _occ_row(cloud, occ, mask=mask), obs, scalars)
     return obs, scalars
 
 
@@ -531,20 +565,11 @@ def pose_forward_backward(cloud, trans, quat, cam, ws, mask=None, gout=None, occ
     """ModelPose.forward and the backward of its fused loss in ONE pass over the cloud (tohip_pose_forward_backward).
     -> (observations (N,), scalars (4: sum, loss, -, -), trans_grad (1,3), quat_grad (1,4)); gradients are gout x d loss / d (.).
     occ: the pose's occlusion bit row instead of a float mask (tohip_pose_forward_backward_bits)."""
-    dev = cloud.device
-    obs = torch.empty(cloud.n, dtype=torch.float32, device=dev)
-    scalars = torch.empty(4, dtype=torch.float32, device=dev)
-    tg = torch.empty((1, 3), dtype=torch.float32, device=dev)
-    qg = torch.empty((1, 4), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        if occ is not None:
-            check(_lib.lib().tohip_pose_forward_backward_bits(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), cam.ref(), ptr(_occ_row(cloud, occ, mask=mask)),
-                                                              ptr(obs), ptr(scalars), ptr(gout), ptr(tg), ptr(qg), ptr(ws.buf), ws.bytes, stream_ptr()),
-                  "tohip_pose_forward_backward_bits")
-        else:
-            check(_lib.lib().tohip_pose_forward_backward(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), cam.ref(), ptr(mask), ptr(obs), ptr(scalars),
-                                                         ptr(gout), ptr(tg), ptr(qg), ptr(ws.buf), ws.bytes, stream_ptr()), "tohip_pose_forward_backward")
-    return obs, scalars, tg, qg
+    f32 = dict(dtype=torch.float32, device=cloud.device)
+    obs, scalars, grads = torch.empty(cloud.n, **f32), torch.empty(4, **f32), torch.empty(8, **f32)
+    PosePlan(cloud, cam, ws).forward_backward(trans, quat, mask, occ if occ is None else _occ_row(cloud, occ, mask=mask), obs, scalars, grads,
+                                              gout)
+    return obs, scalars, grads[0:3].view(1, 3), grads[4:8].view(1, 4)
 
 
 def pose_forward_backward_multi(cloud, trans, quat, cam, ws, mask=None, observations=False, grad=True, occ=None):
@@ -571,32 +596,13 @@ def pose_forward_backward_multi(cloud, trans, quat, cam, ws, mask=None, observat
     scalars = torch.empty((B, 4), **f32)
     tg = torch.empty((B, 3), **f32) if grad else None
     qg = torch.empty((B, 4), **f32) if grad else None
-    with torch.cuda.device(dev):
-        if occ is not None:
-            check(_lib.lib().tohip_pose_forward_backward_multi_bits(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), B, cam.ref(), ptr(occ),
-                                                                    ptr(obs), ptr(scalars), None, ptr(tg), ptr(qg), ptr(ws.buf), ws.bytes,
-                                                                    stream_ptr()), "tohip_pose_forward_backward_multi_bits")
-        else:
-            check(_lib.lib().tohip_pose_forward_backward_multi(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), B, cam.ref(), ptr(mask), ptr(obs),
-                                                               ptr(scalars), None, ptr(tg), ptr(qg), ptr(ws.buf), ws.bytes, stream_ptr()),
-                  "tohip_pose_forward_backward_multi")
+    PosePlan(cloud, cam, ws).forward_backward_multi(trans, quat, B, mask, occ, obs, scalars, tg, qg)
     return obs, scalars, tg, qg
 
 
 def pose_backward(cloud, trans, quat, cam, ws, mask=None, grad_obs=None, scalars=None, gout=None, occ=None):
     """occ: the pose's occlusion bit row instead of a float mask (tohip_pose_backward_bits)."""
-    tg = torch.empty((1, 3), dtype=torch.float32, device=cloud.device)
-    qg = torch.empty((1, 4), dtype=torch.float32, device=cloud.device)
-    with torch.cuda.device(cloud.device):
-        if occ is not None:
-            check(_lib.lib().tohip_pose_backward_bits(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), cam.ref(), ptr(_occ_row(cloud, occ, mask=mask)),
-                                                      ptr(grad_obs), ptr(scalars), ptr(gout), ptr(tg), ptr(qg), ptr(ws.buf), ws.bytes,
-                                                      stream_ptr()), "tohip_pose_backward_bits")
-        else:
-            check(_lib.lib().tohip_pose_backward(ptr(cloud.blob), cloud.n, ptr(trans), ptr(quat), cam.ref(), ptr(mask),
-                                                 ptr(grad_obs), ptr(scalars), ptr(gout), ptr(tg), ptr(qg), ptr(ws.buf),
-                                                 ws.bytes, stream_ptr()), "tohip_pose_backward")
-    return tg, qg
+    return PosePlan(cloud, cam, ws).backward(trans, quat, mask, occ if occ is None else _occ_row(cloud, occ, mask=mask), grad_obs, scalars, gout)
 
 
 def unpack_occlusion_rows(cloud, rows):
@@ -717,24 +723,13 @@ def _occlusion_rows_chunk(cloud, points, poses, quats, cam, min_dist, max_dist, 
 
 def _hpr_batched_mask(points, seg_offsets, mask_out):
     """tohip_hidden_pts_removal_batched for its mask only (mask_out: n_total f32, 1 = visible), over cached scratch -> status (B,) int32."""
-    L = _lib.lib()
     n, dev = points.shape[0], points.device
     B = len(seg_offsets) - 1
-    c_offs = (ctypes.c_int64 * (B + 1))(*[int(o) for o in seg_offsets])
     idx = _scratch(dev, "hidx", 4 * max(n, 1))[:4 * max(n, 1)].view(torch.int32)
     voff = torch.empty(B + 1, dtype=torch.int32, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
-    wsb = L.tohip_hpr_batched_workspace_bytes(n, B)
-    for _ in range(4):
-        ws = _scratch(dev, "hull", wsb)
-        with torch.cuda.device(dev):
-            rc = L.tohip_hidden_pts_removal_batched(ptr(points), c_offs, B, 2.0, ptr(idx), ptr(voff), ptr(mask_out), ptr(status), ptr(ws), ws.numel(),
-                                                    stream_ptr())
-        if rc != _lib.ENOSPC:
-            check(rc, "tohip_hidden_pts_removal_batched")
-            return status
-        wsb *= 4   # most of a cloud's points on its hull: every extra byte goes to faces
-    raise _lib.HipError("hull workspace: still out of face capacity at 64x the recommended size")
+    _hpr_batched(points, seg_offsets, 2.0, idx, voff, mask_out, status, scratch=True)
+    return status
 
 
 def cull_waypoints(points, poses, quats, cam, min_dist, max_dist, normalize=True, scratch=False, packed=False):
@@ -869,13 +864,14 @@ def spherical_flip(points, param=2):
     return out, rad
 
 
-def _with_hull_workspace(wsb, dev, call):
-    """Run call(ws, wsb) with the recommended hull workspace; a cloud whose hull needs more faces than that holds
-    (TOHIP_ENOSPC: most of its points are hull vertices) is retried with 4x the bytes — every extra byte goes to faces."""
+def _with_hull_workspace(wsb, dev, call, scratch=False):
+    """Run call(ws) over a hull workspace of the recommended wsb bytes — a fresh tensor, or (scratch) the cached _scratch buffer of at
+    least that many (call passes ws.numel() as its size); a cloud whose hull needs more faces than that holds (TOHIP_ENOSPC: most of
+    its points are hull vertices) is retried with 4x the bytes — every extra byte goes to faces."""
     for _ in range(4):
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        ws = _scratch(dev, "hull", wsb) if scratch else torch.empty(wsb, dtype=torch.uint8, device=dev)
         try:
-            return call(ws, wsb)
+            return call(ws)
         except _lib.HipError as e:
             if e.code != _lib.ENOSPC:
                 raise
@@ -893,12 +889,25 @@ def hidden_pts_removal(points, param=2):
     idx = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     cnt = torch.zeros(1, dtype=torch.int32, device=dev)
     mask = torch.empty(n, dtype=torch.float32, device=dev)
-    def call(ws, wsb):
+    def call(ws):
         with torch.cuda.device(dev):
-            check(_lib.lib().tohip_hidden_pts_removal(ptr(pts), n, float(param), ptr(idx), ptr(cnt), ptr(mask), ptr(ws), wsb,
+            check(_lib.lib().tohip_hidden_pts_removal(ptr(pts), n, float(param), ptr(idx), ptr(cnt), ptr(mask), ptr(ws), ws.numel(),
                                                       stream_ptr()), "tohip_hidden_pts_removal")
     _with_hull_workspace(_lib.lib().tohip_hpr_workspace_bytes(n), dev, call)
     return idx[:int(cnt.item())], mask
+
+
+def _hpr_batched(points, seg_offsets, param, idx, voff, mask, status, scratch=False):
+    """tohip_hidden_pts_removal_batched of the segments `seg_offsets` (B+1 host ints) of `points` into the given outputs, with the hull
+    workspace's retry rule (scratch: over the cached buffer)."""
+    L, dev, B = _lib.lib(), points.device, len(seg_offsets) - 1
+    c_offs = (ctypes.c_int64 * (B + 1))(*[int(o) for o in seg_offsets])
+
+    def call(ws):
+        with torch.cuda.device(dev):
+            check(L.tohip_hidden_pts_removal_batched(ptr(points), c_offs, B, float(param), ptr(idx), ptr(voff), ptr(mask), ptr(status), ptr(ws),
+                                                     ws.numel(), stream_ptr()), "tohip_hidden_pts_removal_batched")
+    _with_hull_workspace(L.tohip_hpr_batched_workspace_bytes(points.shape[0], B), dev, call, scratch)
 
 
 def hidden_pts_removal_batched(points, seg_offsets, param=2):
@@ -913,17 +922,11 @@ def hidden_pts_removal_batched(points, seg_offsets, param=2):
     B = len(offs) - 1
     if B < 1 or offs[0] != 0 or offs[-1] != n:
         raise ValueError("seg_offsets must run from 0 to len(points)")
-    c_offs = (ctypes.c_int64 * (B + 1))(*offs)
     idx = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     voff = torch.empty(B + 1, dtype=torch.int32, device=dev)
     mask = torch.empty(n, dtype=torch.float32, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    def call(ws, wsb):
-        with torch.cuda.device(dev):
-            check(L.tohip_hidden_pts_removal_batched(ptr(pts), c_offs, B, float(param), ptr(idx), ptr(voff), ptr(mask),
-                                                     ptr(status), ptr(ws), wsb, stream_ptr()), "tohip_hidden_pts_removal_batched")
-    _with_hull_workspace(L.tohip_hpr_batched_workspace_bytes(n, B), dev, call)
+    _hpr_batched(pts, offs, param, idx, voff, mask, status)
     voff_h = voff.cpu().to(torch.int64)
     return idx[:int(voff_h[-1])], voff_h, mask, status
 
@@ -937,10 +940,10 @@ def hull_vertices_with_origin(points, with_origin=True, return_rounds=False):
     idx = torch.empty(n + 1, dtype=torch.int32, device=dev)
     cnt = torch.zeros(1, dtype=torch.int32, device=dev)
     rounds = ctypes.c_int32(0)
-    def call(ws, wsb):
+    def call(ws):
         with torch.cuda.device(dev):
             check(_lib.lib().tohip_convex_hull_vertices(ptr(pts), n, int(with_origin), ptr(idx), ptr(cnt),
-                                                        ctypes.byref(rounds), ptr(ws), wsb, stream_ptr()),
+                                                        ctypes.byref(rounds), ptr(ws), ws.numel(), stream_ptr()),
                   "tohip_convex_hull_vertices")
     _with_hull_workspace(_lib.lib().tohip_hpr_workspace_bytes(n), dev, call)
     out = idx[:int(cnt.item())]

@@ -137,7 +137,7 @@ def optimize_trajectory(model, n_opt_steps=10, lr_pose=0.1, lr_quat=0.0, rewards
     itself, five launches 17 us, and the GPU side is the same — so there is no graph variant.)"""
     if n_opt_steps <= 0:   # nothing to run: the model keeps its rewards and loss terms
         return TrajOptResult(0, False, [], 0.0, 0.0)
-    if model._shard.kind == "points" or model._shard.collective or model._occlusion is not None or model._prior is not None:
+    if model._needs_split_step():
         return _optimize_trajectory_split(model, n_opt_steps, lr_pose, lr_quat, rewards_th, smoothness_th, vis_wps_dist, betas, adam_eps)
     run = _OptRun([model], n_opt_steps, lr_pose, lr_quat, rewards_th, smoothness_th, vis_wps_dist, betas, adam_eps)
     run.run(n_opt_steps)
@@ -179,11 +179,10 @@ def _optimize_trajectory_split(model, n_opt_steps, lr_pose, lr_quat, rewards_th,
         tail = L.tohip_traj_step_tail_multi
     with torch.cuda.device(dev):
         for _ in range(n_opt_steps):
-            kw = {} if model._prior is None else {"prior": model._prior}   # (waypoint placement: PointShard refuses a prior)
-            if model._occlusion is not None and st.hi > st.lo:   # (waypoint placement: PointShard refuses occlusion)
-                own = slice(st.lo * step_w, (st.hi - 1) * step_w + 1, step_w)
-                kw["occ"] = model._occlusion_rows(poses[own].contiguous(), quats[own].contiguous())
-            st.step(poses, quats, flags_extra=stride, **kw)
+            if points:   # (PointShard refuses occlusion and a prior)
+                st.step(poses, quats, flags_extra=stride)
+            else:
+                st.step(poses, quats, flags_extra=stride, occ=model._own_occlusion_rows(st, poses, quats, step_w), prior=model._prior)
             if clr:
                 ops.clearance(model._cloud, poses, model.clearance_radius, model.clearance_weight, grad=clr_rows, terms=clr_terms)
             check(tail(*tail_args, stream_ptr()), "step tail")
