@@ -538,6 +538,73 @@ def gen_full():
          rewards_above_half=np.int64((r > 0.5).sum()), vis_poses_grad=m.poses.grad, vis_quats_grad=m.quats.grad)
 
 
+def gen_baseline():
+    """The reference itself on the benchmark's own workloads (BASELINE.json configs 1 and 2, bench.py's inputs: synth.make_cloud(N,
+    seed=0), synth.make_path(W, optical=True), clip 1-5 m), the cloud by recipe + checksum.  Wall time and the process's peak RSS
+    after each stage (torch CPU, 8 threads, 8 vCPUs; the peak is cumulative):
+      traj_config1_100k_32         100 k x 32, forward only: loss, every 97th reward, their f64 sum, the count above 1/2
+                                   0.8 s, 1.8 GB; 3.2 KiB
+      traj_full_1m_128_dropin      1 M x 128 through the reference's own loop body, loss = m() (vis_wps_dist = 0.5: every 3rd
+                                   waypoint) and loss.backward(): the total loss, its four terms, every 997th reward, the sum, the
+                                   count above 1/2, the gradients of the total loss; and of the same loop body's loss['vis'] alone
+                                   11.7 s, 10.4 GB; 9.9 KiB
+      traj_full_1m_128             1 M x 128, vis_wps_dist = 0, loss['vis'].backward() (bench.py's step): the same samples, the
+                                   visibility gradients                                                   24.1 s, 48.5 GB; 8.6 KiB
+    python tests/golden/make_golden.py baseline"""
+    import resource
+    import time
+
+    def room(n, w):
+        pts = synth.make_cloud(n, seed=0)
+        poses, quats = synth.make_path(w, optical=True)
+        common = dict(recipe=np.asarray("room"), n=n, seed=0, extent=np.asarray((40.0, 40.0, 4.0)), poses=poses, quats=quats,
+                      min_dist=np.float64(1.0), max_dist=np.float64(5.0), points_checksum=np.float64(pts.astype(np.float64).sum()))
+        m = ref_model.ModelTraj(points=torch.from_numpy(pts), wps_poses=torch.from_numpy(poses), wps_quats=torch.from_numpy(quats),
+                                intrins=K, img_width=IMG_W, img_height=IMG_H, device=CPU, min_dist=1.0, max_dist=5.0)
+        return m, common
+
+    def samples(r, every):
+        r = r.detach().numpy()
+        return {f"rewards_every_{every}th": r[::every].copy(), "rewards_sum": np.float64(r.astype(np.float64).sum()),
+                "rewards_above_half": np.int64((r > 0.5).sum())}
+
+    def report(name, t0):
+        peak = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 2 ** 20
+        print(f"   {name}: {time.perf_counter() - t0:.1f} s, peak RSS {peak:.1f} GB")
+
+    t0 = time.perf_counter()
+    m, common = room(100_000, 32)
+    m(vis_wps_dist=0.0)
+    save("traj_config1_100k_32", **common, loss_vis=m.loss["vis"], **samples(m.rewards, 97))
+    report("traj_config1_100k_32", t0)
+
+    t0 = time.perf_counter()
+    m, common = room(1_000_000, 128)
+    loss = m()   # trajectory_optimization.py's loop body at the default vis_wps_dist = 0.5
+    loss.backward()
+    wps_step = int(0.5 / (m.poses0[1:] - m.poses0[:-1]).norm(dim=1).mean()) + 1   # the step forward() took (model.py:214-215)
+    # the same loop body's visibility term alone: the reference's f32 regulariser gradient (arccos of nearly straight segments) is
+    # far from its f64 value here, so the visibility part of the total cannot be recovered from the total to 1e-5
+    m2, _ = room(1_000_000, 128)
+    m2()
+    m2.loss["vis"].backward()
+    assert m2.loss["vis"].item() == m.loss["vis"].item()
+    save("traj_full_1m_128_dropin", **common, vis_wps_dist=np.float64(0.5), wps_step=np.int64(wps_step), loss=loss,
+         loss_vis=m.loss["vis"], loss_l2=m.loss["l2"], loss_length=m.loss["length"], loss_smooth=m.loss["smooth"],
+         **samples(m.rewards, 997), poses_grad=m.poses.grad, quats_grad=m.quats.grad, vis_poses_grad=m2.poses.grad,
+         vis_quats_grad=m2.quats.grad)
+    report(f"traj_full_1m_128_dropin (every waypoint with index a multiple of {wps_step})", t0)
+    del m, m2, loss
+
+    t0 = time.perf_counter()
+    m, common = room(1_000_000, 128)
+    m(vis_wps_dist=0.0)
+    m.loss["vis"].backward()
+    save("traj_full_1m_128", **common, loss_vis=m.loss["vis"], **samples(m.rewards, 997), vis_poses_grad=m.poses.grad,
+         vis_quats_grad=m.quats.grad)
+    report("traj_full_1m_128", t0)
+
+
 def gen_timing():
     """Not a fixture: wall time of the reference itself (torch CPU, this container) on the bench workload's shape, for
     the record kept in profiles/r01_reference_cpu_timing.txt.  python tests/golden/make_golden.py timing"""

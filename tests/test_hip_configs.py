@@ -41,8 +41,14 @@ def test_config1_100k_x32_forward_only(dev):
 
 def test_config3_1m_x1024_sharded_over_8(dev):
     """configs[3]: 1M points x 1024 waypoints as 8 shards of 128 (what 8 ranks compute before the all-reduce):
-    the shards' log-odds add up to the single-device result; rewards match the oracle on a waypoint subsample."""
+    the shards' log-odds add up to the single-device result; rewards match the oracle on a waypoint subsample, and all 1 M of
+    them — from the summed shard log-odds — match the f64 oracle over all 1024 waypoints.  A rank's real work, the backward of
+    its 128 waypoints behind the summed log-odds, is checked for two shards against the f64 oracle under the conditional 1e-5
+    bar (a waypoint with a point within MARGIN of a threshold is excused only within what the band is worth; the excused set is
+    asserted exactly)."""
+    import warnings
     from oracle import oracle
+    from test_hip_conditioning import BASELINE_EXCLUDED_WAYPOINTS, MARGIN, _margins
     ops, pts, poses, quats, cloud, cam, _ = _setup(dev, 1_000_000, 1024)
     p, q = torch.from_numpy(poses).to(dev), torch.from_numpy(quats).to(dev)
     ws1 = ops.TrajWorkspace(cloud, 1024)
@@ -63,6 +69,41 @@ def test_config3_1m_x1024_sharded_over_8(dev):
     r_s, _ = ops.traj_reward(cloud, lo_s, cam, ws)
     f = oracle.traj_forward(pts, poses[sel], quats[sel], K, IW, IH, prec="f64")
     np.testing.assert_allclose(r_s.cpu().numpy(), f["rewards"], rtol=1e-5, atol=0)
+    # every reward of the 1024-waypoint trajectory (the summed shards' log-odds) against the f64 oracle, computed once
+    rew_all = rew.cpu().numpy()
+    f_all = oracle.traj_forward(pts, poses, quats, K, IW, IH, prec="f64")
+    np.testing.assert_allclose(rew_all, f_all["rewards"], rtol=1e-5, atol=0)
+    assert abs(sc[1].item() - f_all["loss_vis"]) <= 5e-6 * f_all["loss_vis"]
+    # a rank's backward: its shard's forward again (the workspace then holds that step), the reward of the summed log-odds, and the
+    # backward of its 128 waypoints behind it
+    gout = torch.ones(1, device=dev)
+    for s in (0, 5):
+        rows = slice(128 * s, 128 * (s + 1))
+        ops.traj_forward(cloud, p[rows].contiguous(), q[rows].contiguous(), cam, ws)
+        rew_s, sc_s = ops.traj_reward(cloud, total, cam, ws)
+        assert torch.equal(rew_s, rew) and torch.equal(sc_s, sc)
+        pg, qg = ops.traj_backward(cloud, 128, cam, ws, total, scalars=sc_s, gout=gout)
+        pg, qg = pg.cpu().numpy().astype(np.float64), qg.cpu().numpy().astype(np.float64)
+        kw = dict(min_dist=1.0, max_dist=5.0, prec="f64")
+        ref = oracle.traj_backward(pts, poses[rows], quats[rows], K, IW, IH, f_all, **kw)
+        keep = _margins(pts, poses[rows], quats[rows], (1.0, 5.0)) > MARGIN
+        assert np.flatnonzero(~keep).tolist() == BASELINE_EXCLUDED_WAYPOINTS[f"config3_shard{s}"]
+        band = None
+        if not keep.all():   # what the points inside the band are worth: the activity threshold moved by -/+ 2 MARGIN
+            lo_b = oracle.traj_backward(pts, poses[rows], quats[rows], K, IW, IH, f_all, act_shift=-2 * MARGIN, **kw)
+            hi_b = oracle.traj_backward(pts, poses[rows], quats[rows], K, IW, IH, f_all, act_shift=2 * MARGIN, **kw)
+            band = [np.abs(a - b).max(axis=1) for a, b in zip(lo_b, hi_b)]
+        worst = worst_ex = 0.0
+        for k, (g, r) in enumerate(((pg, ref[0]), (qg, ref[1]))):
+            den = np.abs(r).max()
+            err = np.abs(g - r).max(axis=1)
+            assert (err[keep] < 1e-5 * den).all(), (s, k, (err[keep] / den).max())
+            worst = max(worst, float((err[keep] / den).max()))
+            for v in np.flatnonzero(~keep):
+                assert band[k][v] > 0 and err[v] <= 1.05 * band[k][v] + 1e-5 * den, (s, k, v, err[v] / den, band[k][v] / den)
+                worst_ex = max(worst_ex, float(err[v] / den))
+        warnings.warn(f"config 3 shard {s} backward vs the f64 oracle over 1024 waypoints: {int(keep.sum())} waypoints within 1e-5 (worst "
+                      f"{worst:.1e} of the largest row), {int((~keep).sum())} excused within the band (worst {worst_ex:.1e})")
 
 
 def test_config4_five_cameras_1m_x256(dev):

@@ -87,6 +87,70 @@ def test_full_size_against_the_reference(prec):
     assert rep["excluded_waypoints"] == [] and rep["kept"] == len(d["poses"]) == 16   # all 16 waypoints hold the plain bar
 
 
+def _reward_samples(rewards, d, every):
+    """The reward samples a `baseline` fixture keeps (every `every`-th, the f64 sum, the count above 1/2) against `rewards`."""
+    np.testing.assert_allclose(rewards[::every], d[f"rewards_every_{every}th"], rtol=2e-5, atol=0)
+    assert abs(float(rewards.astype(np.float64).sum()) - float(d["rewards_sum"])) <= 1e-6 * float(d["rewards_sum"])
+    assert abs(int((rewards > 0.5).sum()) - int(d["rewards_above_half"])) <= 2   # (a point exactly on p_hat = 1/2 may fall either way)
+
+
+@pytest.mark.parametrize("name,every", [("traj_full_1m_128", 997), ("traj_config1_100k_32", 97)])
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_benchmark_workloads_against_the_reference(name, every, prec):
+    """The reference ITSELF on the benchmark's own workloads (make_golden.py baseline): BASELINE config 2 (1 M x 128, what bench.py
+    times, fwd + bwd) and config 1 (100 k x 32, forward only): loss, the reward samples, and config 2's gradients under the
+    conditional 1e-5 bar with the excluded set asserted exactly."""
+    from conftest import conditional_gradient_report, load_reference_case
+    from test_hip_conditioning import BASELINE_EXCLUDED_WAYPOINTS, MARGIN
+    d = load_reference_case(name)
+    fwd = oracle.traj_forward(d["points"], d["poses"], d["quats"], K, IW, IH, d["clip"][0], d["clip"][1], prec=prec)
+    assert abs(fwd["loss_vis"] - float(d["loss_vis"])) <= 2e-6 * float(d["loss_vis"])
+    _reward_samples(fwd["rewards"], d, every)
+    if "vis_poses_grad" not in d:
+        return
+    pg, qg = oracle.traj_backward(d["points"], d["poses"], d["quats"], K, IW, IH, fwd, min_dist=d["clip"][0], max_dist=d["clip"][1], prec=prec)
+    rep = conditional_gradient_report(d, pg, qg, MARGIN)
+    assert rep["excluded_waypoints"] == BASELINE_EXCLUDED_WAYPOINTS[name]
+    assert rep["kept"] == len(d["poses"]) - len(BASELINE_EXCLUDED_WAYPOINTS[name])
+
+
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_dropin_loop_at_size_against_the_reference(prec):
+    """The reference's own loop body at 1 M x 128 (make_golden.py baseline: loss = m() at vis_wps_dist = 0.5, every 3rd waypoint
+    evaluated, then loss.backward()).  The oracle's visibility term on the evaluated waypoints: loss, reward samples and the
+    visibility gradient under the conditional 1e-5 bar.  The totals with the f64 regularisers: the loss and each term to 1e-5, the
+    quaternion gradient (no regulariser reaches it) to 1e-5, and the position gradient rows that only the regularisers reach.
+    The reference's f32 smoothness gradient is NOT pinned at 1e-5: segments of this path are so nearly straight (1 + cos of the
+    angle down to 1.5e-7) that its f32 arccos' derivative is rounding noise there."""
+    from conftest import conditional_gradient_report, load_reference_case
+    from test_hip_conditioning import BASELINE_EXCLUDED_WAYPOINTS, MARGIN, dropin_visibility_case, regularisers_f64
+    d = load_reference_case("traj_full_1m_128_dropin")
+    v, idx = dropin_visibility_case(d)
+    assert int(d["wps_step"]) == 3 and len(idx) == 43
+    fwd = oracle.traj_forward(v["points"], v["poses"], v["quats"], K, IW, IH, d["clip"][0], d["clip"][1], prec=prec)
+    assert abs(fwd["loss_vis"] - float(d["loss_vis"])) <= 2e-6 * float(d["loss_vis"])
+    _reward_samples(fwd["rewards"], d, 997)
+    pg, qg = oracle.traj_backward(v["points"], v["poses"], v["quats"], K, IW, IH, fwd, min_dist=d["clip"][0], max_dist=d["clip"][1], prec=prec)
+    rep = conditional_gradient_report(v, pg, qg, MARGIN)
+    name = "traj_full_1m_128_dropin"
+    assert rep["excluded_waypoints"] == BASELINE_EXCLUDED_WAYPOINTS[name] and rep["kept"] == len(idx) - len(BASELINE_EXCLUDED_WAYPOINTS[name])
+    off = np.setdiff1d(np.arange(len(d["poses"])), idx)
+    # the visibility term reaches the evaluated waypoints only
+    assert np.all(d["vis_poses_grad"][off] == 0) and np.all(d["vis_quats_grad"][off] == 0) and np.all(d["quats_grad"][off] == 0)
+    l2, length, smooth, reg = regularisers_f64(d["poses"])
+    for term, val in (("vis", fwd["loss_vis"]), ("l2", l2), ("length", length), ("smooth", smooth)):
+        assert abs(val - float(d["loss_" + term])) <= 1e-5 * max(1.0, abs(float(d["loss_" + term]))), term
+    assert abs(fwd["loss_vis"] + l2 + length + smooth - float(d["loss"])) <= 1e-5 * float(d["loss"])
+    # quaternions: the total IS the visibility gradient (no regulariser reaches them)
+    qt = np.zeros((len(d["poses"]), 4))
+    qt[idx] = qg
+    assert rel_inf(qt, d["quats_grad"]) < 1e-5
+    # positions: the reference's total minus its own visibility part is its regulariser gradient — within 1e-2 of the f64 one,
+    # no better (the nearly straight segments above)
+    ref_reg = d["poses_grad"].astype(np.float64) - d["vis_poses_grad"]
+    assert rel_inf(ref_reg, reg) < 1e-2
+
+
 STRESS_FIXTURES = ["traj_stress_23_4", "traj_stress_31_83", "traj_stress_31_101", "traj_stress_23_134"]
 
 
