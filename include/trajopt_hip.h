@@ -37,7 +37,10 @@
 extern "C" {
 #endif
 
-/* 15: + tohip_clearance / tohip_clearance_workspace_bytes / tohip_traj_clearance_scratch_bytes / tohip_traj_step_tail_clearance /
+/* (still 15) + tohip_team_step_tail / tohip_team_loss / tohip_team_member_gains / tohip_team_state_bytes /
+ * tohip_team_member_gains_bytes (team coverage): new symbols only — no struct and no existing signature changes, so a caller built
+ * against the earlier header of 15 works unchanged and the number stays.
+ * 15: + tohip_clearance / tohip_clearance_workspace_bytes / tohip_traj_clearance_scratch_bytes / tohip_traj_step_tail_clearance /
  * tohip_traj_regularizers_clearance (the clearance term); tohip_traj_loss and tohip_traj_opt gain clearance_radius,
  * clearance_weight, clearance_scratch(_bytes) at their ends (zero = off).
  * 14: + tohip_pose_forward_bits / _backward_bits / _forward_backward_bits / _opt_step_bits / _forward_backward_multi_bits (per-pose
@@ -743,6 +746,56 @@ size_t tohip_zbuffer_batched_workspace_bytes(int32_t width, int32_t height, int6
 int tohip_zbuffer_visible_batched(const float *verts, int64_t n_stride, const int32_t *count, int64_t n_clouds, const float *K9_host,
                                   int32_t width, int32_t height, float radius, float znear, float zfar, float *visible,
                                   void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- team coverage: B robots over one cloud behind ONE reward ------------------------
+ * The team's visibility term is the entries above over the members' evaluated waypoints laid end to end as one trajectory
+ * (n_traj = 1; tohip_gather_waypoints_multi when n_wps is not a multiple of the waypoint step).  The entries below are what stays
+ * per member behind that one reward.  Members: n_members equal-length trajectories laid end to end (poses (B n_wps, 3), ...).
+ *
+ * tohip_team_state_bytes: the per-step state of a run of n_steps, zero-filled once by the caller:
+ *   [state (n_steps + 1, B, 8) f32: tohip_traj_opt's state row per member — [0] the team's first mean reward, [1] the member's first
+ *    smooth term, [2] stopped, [3] steps taken, [4] visibility gain, [5] the member's smooth gain]
+ *   [terms (n_steps + 1, B, 4) f64: l2, length, smooth, - of every member at the positions step i starts from]
+ * Row 0 of `terms` is tohip_team_loss's member_terms64 (call it on the starting positions before the first step).
+ *
+ * tohip_team_step_tail: step `step_index` (0-based, in order) of a run of n_steps, ONE launch, block b = member b: what
+ * tohip_traj_step_tail_multi / _clearance do per trajectory — the same device functions, the same bits for one member — with two
+ * differences: `scalars` is ONE row, the team's, and the early stop is the team's: visibility gain = mean reward / the team's
+ * first; smooth gain per member; the team stops at the first step where the visibility gain > rewards_th and EVERY member's smooth
+ * gain > smoothness_th, all members together.  Loss rows (member b's at loss_log + b * loss_log_stride, n_steps rows of 8):
+ * [0] vis [1] l2 [2] length [3] smooth [5] clearance of the member, [4] the TEAM total = vis, then l2, length, smooth [, clearance]
+ * of every member in member order, one running f64 sum rounded once.  clearance_grad / clearance_terms: both NULL (no clearance
+ * term) or the query's rows (B n_wps, 3) and per-waypoint terms (B n_wps). */
+#define TOHIP_TEAM_MAX_MEMBERS 256
+size_t tohip_team_state_bytes(int64_t n_members, int64_t n_steps);
+int tohip_team_step_tail(float *poses, float *quats, const float *poses0, int64_t n_wps, int64_t n_members,
+                         const float *poses_grad_eval, const float *quats_grad_eval, int64_t n_eval, int step, float *poses_grad,
+                         float *quats_grad, float *exp_avg_p, float *exp_avg_sq_p, float *exp_avg_q, float *exp_avg_sq_q,
+                         float smoothness_weight, float traj_length_weight, float eps, float lr_pose, float lr_quat, float beta1,
+                         float beta2, float adam_eps, float rewards_th, float smoothness_th, const float *scalars, float *loss_log,
+                         int64_t loss_log_stride, void *team_state, size_t team_state_bytes, int32_t n_steps, int32_t step_index,
+                         float clearance_weight, const float *clearance_grad, const double *clearance_terms, void *stream);
+
+/* tohip_team_loss: criterion's terms of every member in ONE launch (block b = member b) — member_terms (B, 8): [0] vis (scalars[1];
+ * 0 when scalars is NULL) [1] l2 [2] length [3] smooth [5] clearance — with, each optional (NULL): member_terms64 (B, 4) f64 l2,
+ * length, smooth, -; total (1): the team total as above (needs scalars); grad_poses (B n_wps, 3): the regularisers' gradient rows
+ * (overwritten); grad_terms (B, 3, n_wps, 3): d l2, d length, d smooth of each member.  clearance_terms: NULL or (B n_wps). */
+int tohip_team_loss(const float *poses, const float *poses0, int64_t n_wps, int64_t n_members, float smoothness_weight,
+                    float traj_length_weight, float eps, const float *scalars, float clearance_weight, const double *clearance_terms,
+                    float *member_terms, double *member_terms64, float *total, float *grad_poses, float *grad_terms, void *stream);
+
+/* tohip_team_member_gains: what each member adds.  lo_members (B, npad): the per-member log-odds rows tohip_traj_forward_multi
+ * (n_traj = B) leaves, packed order; prior_buf: NULL or the team's prior.  sums (DEVICE int64, tohip_team_member_gains_bytes =
+ * 8 (1 + 2 B) bytes, zeroed by the call): [0] the fixed-point sum of sigmoid(S + prior), [1 + b] of sigmoid(S - lo_b + prior),
+ * [1 + B + b] the points with lo_b > 0; S = the members' rows summed in member order in f32; fixed point: x 2^(47 - ceil(log2 N)),
+ * the reward kernel's.  gain_b = (sums[0] - sums[1 + b]) / 2^shift / N.  Integer sums: the same bits every run.  B <= 16.
+ * `packed` is the cloud the rows belong to (it fixes N's padding; the kernel itself reads the rows only).
+ * A member whose row is NaN (a waypoint that sees nothing at all: max p == min p, NaN rewards in the reference) counts as absent:
+ * its log-odds are taken as 0, its gain and count are 0. */
+#define TOHIP_TEAM_MAX_GAINS 16
+size_t tohip_team_member_gains_bytes(int64_t n_members);
+int tohip_team_member_gains(const void *packed, int64_t n_points, const float *lo_members, int64_t n_members, const void *prior_buf,
+                            int64_t *sums, size_t sums_bytes, void *stream);
 
 /* ---- optional per-kernel timing (bench.py's roofline leg) -----------------------------------------
  * When enabled, every launch of the big kernels is bracketed by hipEventRecord on its own stream.

@@ -177,6 +177,13 @@ SIGNATURES = {
     "tohip_traj_step_tail_clearance": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, ctypes.c_int, c_vp, c_vp,
                                                        c_vp, c_vp, c_vp, c_vp, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_vp,
                                                        c_vp, c_i64, c_vp, c_f, c_vp, c_vp, c_vp]),
+    "tohip_team_state_bytes": (c_sz, [c_i64, c_i64]),
+    "tohip_team_step_tail": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                             c_vp, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp, c_i64, c_vp, c_sz, c_i32,
+                                             c_i32, c_f, c_vp, c_vp, c_vp]),
+    "tohip_team_loss": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_f, c_f, c_f, c_vp, c_f, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "tohip_team_member_gains_bytes": (c_sz, [c_i64]),
+    "tohip_team_member_gains": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
     "tohip_clearance_workspace_bytes": (c_sz, [c_i64]),
     "tohip_clearance": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_f, c_f, c_vp, c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_sz, c_vp]),
     "tohip_traj_clearance_scratch_bytes": (c_sz, [c_i64, c_i64]),

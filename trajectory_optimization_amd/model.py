@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from . import _lib, ops
 from ._lib import check, ptr, stream_ptr
-from .optimizer import _refresh_age, accelerate_torch_adam, tag_parameter
+from .optimizer import _refresh_age, accelerate_torch_adam, check_team, tag_parameter
 from .tools import hidden_pts_removal
 
 
@@ -1165,3 +1165,130 @@ class ModelTraj(nn.Module):
             self.loss['clearance'] = _Clearance.apply(self.poses, self)
             total = total + self.loss['clearance']
         return total
+
+
+# ------------------------------------------------------------------------------ team coverage
+
+class _TeamLoss(torch.autograd.Function):
+    """TeamTraj.forward in one autograd node: (every member's poses, every member's quats) -> (team total, rewards, member terms).
+    The visibility step is a plain trajectory's over the members' evaluated waypoints laid end to end (the separate calls a prior
+    model takes, n_traj = 1); criterion's terms of all members and their gradient rows are one launch (tohip_team_loss).  The total,
+    the rewards and vis are differentiable; the member terms (B, 8) are not.  `loss.backward()` takes the fused visibility loss's
+    unit sums (the arithmetic of the optimiser's step); any other upstream takes the kernels a ModelTraj on the same rows takes for it
+    (with a prior the unit sums for loss['vis'] as well, the general dL/d rewards path otherwise)."""
+
+    @staticmethod
+    def forward(ctx, team, step_w, *params):
+        B, m0 = team.B, team.models[0]
+        P, Q = [p.detach() for p in params[:B]], [q.detach() for q in params[B:]]
+        W = P[0].shape[0]
+        n_eval = (W + step_w - 1) // step_w
+        p_all = torch.cat(P).contiguous()
+        ps, qs = torch.cat([p[::step_w] for p in P]).contiguous(), torch.cat([q[::step_w] for q in Q]).contiguous()   # E: own copies
+        st = m0._waypoint_step(B * n_eval)
+        lo_sum, rewards, scalars = st.forward(ps, qs, None, prior=team._prior)
+        clr_rows = clr_terms = None
+        if m0._clearance_on:
+            clr_rows = torch.empty((B * W, 3), dtype=torch.float32, device=p_all.device)
+            clr_terms = torch.empty(_lib.lib().tohip_clearance_workspace_bytes(B * W) // 8, dtype=torch.float64, device=p_all.device)
+            ops.clearance(m0._cloud, p_all, m0.clearance_radius, m0.clearance_weight, grad=clr_rows, terms=clr_terms)
+        terms, total, reg = ops.team_loss(p_all, team._poses0, B, m0.smoothness_weight, m0.traj_length_weight, m0.eps, scalars,
+                                          m0.clearance_weight, clr_terms)
+        ctx.team, ctx.step, ctx.gen, ctx.step_w, ctx.W, ctx.n_eval, ctx.has_clr = team, st, st.ws.generation, step_w, W, n_eval, clr_rows is not None
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(terms)
+        ctx.save_for_backward(ps, qs, lo_sum, scalars, reg, *((clr_rows,) if ctx.has_clr else ()))
+        return total.reshape(()), rewards, scalars[1].clone(), terms
+
+    @staticmethod
+    def backward(ctx, g_loss, g_rewards, g_vis, _g_terms):
+        team, st, W, n_eval = ctx.team, ctx.step, ctx.W, ctx.n_eval
+        B, m0 = team.B, team.models[0]
+        ps, qs, lo_sum, scalars, reg, *rest = ctx.saved_tensors
+        clr_rows = rest[0] if ctx.has_clr else None
+        g_loss = _f32(g_loss)
+        upstream = _vis_upstream(g_loss, _f32(g_vis), g_rewards, scalars)
+        pg = qg = None
+        if upstream is not None:   # unit sums scaled once per waypoint for loss.backward(), and for loss['vis'] where a prior model takes them
+            pg, qg = st.backward(ps, qs, None, ctx.gen, lo_sum, upstream, prior=team._prior,
+                                 unit_sums=team._prior is not None or g_vis is None)
+        grads_p, grads_q = [], []
+        for b in range(B):
+            e, w = slice(b * n_eval, (b + 1) * n_eval), slice(b * W, (b + 1) * W)
+            gp, gq = _assemble_grads(ctx.step_w, W, pg[e] if pg is not None else None, qg[e] if qg is not None else None, g_loss,
+                                     (None, None, None), reg[w], None, clr_rows[w] if clr_rows is not None else None, None)
+            grads_p.append(gp)
+            grads_q.append(gq)
+        return (None, None, *grads_p, *grads_q)
+
+
+class TeamTraj(nn.Module):
+    """Several ModelTraj over ONE map as one model (team coverage): its parameters are the members' poses / quats, its
+    reward is the team's — sigmoid(one log-odds sum over every member's evaluated waypoints + the prior) — so a point counts once
+    whichever robot sees it, and the members divide the scene.  forward() returns the team total: 1 / (mean reward + eps) once, plus
+    every member's own l2, length, smooth (and clearance).  Members: as optimizer.optimize_team's (same points, camera, rig, mode, eps,
+    weights, waypoint count and step; no sharding, no occlusion; at most one prior, the first model's).  optimizer.optimize_team is
+    the launch-only loop over the same arithmetic."""
+
+    def __init__(self, models):
+        super().__init__()
+        models = list(models)
+        self._prior = check_team(models, 0.5, "TeamTraj")
+        self.models = nn.ModuleList(models)
+        self.B = len(models)
+        self._poses0 = torch.cat([m.poses0 for m in models]).contiguous()
+        self._checked = {0.5}
+        self.rewards = None
+        self.loss = {"vis": float("inf")}
+
+    def _step(self, vis_wps_dist):
+        if vis_wps_dist not in self._checked:   # (the members' waypoint steps may differ at another distance)
+            check_team(self.models, vis_wps_dist, "TeamTraj")
+            self._checked.add(vis_wps_dist)
+        return self.models[0]._wps_step(vis_wps_dist)
+
+    def forward(self, vis_wps_dist=0.5):
+        step_w = self._step(vis_wps_dist)
+        total, self.rewards, vis, terms = _TeamLoss.apply(self, step_w, *[m.poses for m in self.models], *[m.quats for m in self.models])
+        self.loss = {"vis": vis, "l2": list(terms[:, 1].unbind()), "length": list(terms[:, 2].unbind()),
+                     "smooth": list(terms[:, 3].unbind())}
+        if self.models[0]._clearance_on:
+            self.loss["clearance"] = list(terms[:, 5].unbind())
+        return total
+
+    def mean_reward(self):
+        """mean(rewards) of the team after the last forward (0-d tensor), or None before it."""
+        return torch.mean(self.rewards.detach()) if self.rewards is not None else None
+
+    def _evaluated(self, step_w):
+        ps = torch.cat([m.poses.detach()[::step_w] for m in self.models]).contiguous()
+        qs = torch.cat([m.quats.detach()[::step_w] for m in self.models]).contiguous()
+        return ps, qs
+
+    @torch.no_grad()
+    def coverage_log_odds(self, clamp_max=None, vis_wps_dist=0.5):
+        """The team's fused log-odds map (N,) f32 in the caller's order: prior + the one sum over every member's evaluated waypoints at
+        their current poses — the next plan's prior_log_odds.  clamp_max: OctoMap's upper clamping threshold (>= 0; None: none)."""
+        m0 = self.models[0]
+        ps, qs = self._evaluated(self._step(vis_wps_dist))
+        lo_sum, _ = ops.traj_forward(m0._cloud, ps, qs, m0._cam, m0._workspace(ps.shape[0]), m0._rig, flags=m0._flags)
+        return ops.traj_coverage(m0._cloud, lo_sum, self._prior, clamp_max)
+
+    @torch.no_grad()
+    def member_gains(self, vis_wps_dist=0.5):
+        """What each member adds, at the current poses -> (gain (B,) float64: the team's mean reward minus the mean reward of the team
+        without member b; count (B,) int64: the points member b sees at all, log-odds > 0), on the host.  One forward that keeps a
+        log-odds row per member, one pass over those rows (tohip_team_member_gains).  A member that sees nothing at all (far from the
+        cloud: its row is NaN, as the reference's rewards are for such a waypoint) counts as absent: gain 0 and count 0 exactly, and
+        the others' gains are those of the team without it.  At most 16 members."""
+        if self.B > 16:   # TOHIP_TEAM_MAX_GAINS: the pass keeps one accumulator pair per member in registers
+            raise ValueError(f"TeamTraj.member_gains: at most 16 members ({self.B} given)")
+        m0 = self.models[0]
+        ps, qs = self._evaluated(self._step(vis_wps_dist))
+        n_eval, C = ps.shape[0] // self.B, (m0._rig.n_cams if m0._rig is not None else 1)
+        ws = m0._ws_cache.get(("team", self.B, n_eval))
+        if ws is None:
+            ws = m0._ws_cache[("team", self.B, n_eval)] = ops.TrajWorkspace(m0._cloud, self.B * n_eval * C, self.B)
+        toff = (torch.arange(self.B + 1, dtype=torch.int32) * n_eval).to(m0.device)
+        lo, _ = ops.traj_forward(m0._cloud, ps, qs, m0._cam, ws, m0._rig, flags=m0._flags, traj_offsets=toff)
+        return ops.team_member_gains(m0._cloud, lo, self._prior)

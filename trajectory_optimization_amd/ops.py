@@ -341,14 +341,14 @@ class WaypointShardStep:
         """-> the all-reduced gradient rows (n_wps,3), (n_wps,4) of the forward that left the workspace at generation `gen`.
         upstream: traj_backward's upstream keyword arguments, or None when no gradient reaches this rank's visibility term (the
         all-reduce is joined all the same).  If another forward has used the workspace since, that state is rebuilt first — same
-        inputs, same bits.  prior: the forward's LogOddsPrior.  unit_sums (with a prior and the fused visibility loss's upstream): the
+        inputs, same bits.  prior: the forward's LogOddsPrior or None.  unit_sums (with the fused visibility loss's upstream): the
         sums are taken with unit dL/d reward and scaled once per waypoint (traj_reward_backward, the rewards taken again) — the
         arithmetic of the one-call step, whose bits a prior model without collective or occlusion rows keeps for a zero prior."""
         g = torch.zeros((self.n_wps, 7), dtype=torch.float32, device=lo_sum.device)
         if upstream is not None and self.hi > self.lo:
             if self.ws.generation != gen:
                 traj_forward(self.cloud, ps, qs, self.cam, self.ws, self.rig, flags=self.flags, occ=occ)
-            if prior is not None and unit_sums and "gout" in upstream:
+            if unit_sums and "gout" in upstream:
                 _, _, pg, qg = traj_reward_backward(self.cloud, ps.shape[0], self.cam, self.ws, lo_sum, upstream["gout"], rig=self.rig,
                                                     flags=self.flags, occ=occ, prior=prior)
             else:
@@ -445,6 +445,38 @@ def traj_coverage(cloud, lo_sum, prior=None, clamp_max=None):
         check(_lib.lib().tohip_traj_coverage(ptr(cloud.blob), cloud.n, ptr(lo_sum), ptr(prior.buf) if prior is not None else None, c,
                                              ptr(out), stream_ptr()), "tohip_traj_coverage")
     return out
+
+
+def team_loss(poses, poses0, n_members, smoothness_weight, traj_length_weight, eps, scalars, clearance_weight=0.0, clr_terms=None):
+    """tohip_team_loss: criterion's terms of every member (poses / poses0: the members' (B W, 3) rows end to end) behind the team's
+    `scalars` -> (member_terms (B, 8): [0] vis [1] l2 [2] length [3] smooth [5] clearance; total (1): the team total; reg (B W, 3): the
+    regularisers' gradient rows).  clr_terms: the clearance query's per-waypoint terms of all B W waypoints (float64), or None."""
+    dev, W = poses.device, poses.shape[0] // n_members
+    terms = torch.empty((n_members, 8), dtype=torch.float32, device=dev)
+    total = torch.empty(1, dtype=torch.float32, device=dev)
+    reg = torch.empty((n_members * W, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().tohip_team_loss(ptr(poses), ptr(poses0), W, n_members, float(smoothness_weight), float(traj_length_weight), float(eps),
+                                         ptr(scalars), float(clearance_weight), ptr(clr_terms), ptr(terms), None, ptr(total), ptr(reg), None,
+                                         stream_ptr()), "tohip_team_loss")
+    return terms, total, reg
+
+
+def team_member_gains(cloud, lo_members, prior=None):
+    """tohip_team_member_gains over the (B, npad) per-member log-odds rows traj_forward leaves with traj_offsets -> (gain (B,) f64:
+    the team's mean reward minus the team's without member b; count (B,) int64: the points with lo_b > 0), on the host.  Integer
+    sums on the device: the same bits every run."""
+    L = _lib.lib()
+    B = lo_members.shape[0]
+    nbytes = L.tohip_team_member_gains_bytes(B)
+    sums = torch.empty(nbytes // 8, dtype=torch.int64, device=cloud.device)
+    with torch.cuda.device(cloud.device):
+        check(L.tohip_team_member_gains(ptr(cloud.blob), cloud.n, ptr(lo_members), B, ptr(prior.buf) if prior is not None else None, ptr(sums),
+                                        nbytes, stream_ptr()), "tohip_team_member_gains")
+    h = sums.cpu()
+    shift = 47 - (cloud.n - 1).bit_length()   # the reward kernel's fixed point: 2^shift per unit, N 2^shift <= 2^47
+    gain = (h[0] - h[1:1 + B]).to(torch.float64) / float(2 ** shift) / cloud.n
+    return gain, h[1 + B:1 + 2 * B].clone()
 
 
 def clearance(cloud, positions, radius, weight=0.0, grad=None, accumulate=False, want_value=False, terms=None):

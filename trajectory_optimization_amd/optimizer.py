@@ -200,6 +200,37 @@ def _optimize_trajectory_split(model, n_opt_steps, lr_pose, lr_quat, rewards_th,
     return TrajOptResult(steps, bool(stt[2].item() != 0), lt_host[:, 4].tolist(), float(stt[4]), float(stt[5]))
 
 
+def _check_same_setup(models, vis_wps_dist, what):
+    """What a run over several ModelTraj at once demands of them — built on the same points with the same camera, rig, mode, eps,
+    weights and clearance settings, equal numbers of waypoints and the same waypoint step, no sharding, no occlusion rows — or a
+    ValueError that names what differs.  Host checks only (equal tensors are compared where the objects differ)."""
+    m0 = models[0]
+    cloud, cam, rig = m0._cloud, m0._cam, m0._rig
+    W = m0.poses.shape[0]
+    step_w = m0._wps_step(vis_wps_dist)
+    for m in models:
+        if m._shard.world_size > 1:
+            raise ValueError(f"{what}: a sharded model (WaypointShard / PointShard) is not supported")
+        if m._occlusion is not None:
+            raise ValueError(f"{what}: a model with occlusion rows (occlusion=) is not supported")
+        if m.poses.shape[0] != W:
+            raise ValueError(f"{what}: the models must have equal numbers of waypoints ({m.poses.shape[0]} and {W})")
+        if m._wps_step(vis_wps_dist) != step_w:
+            raise ValueError(f"{what}: the models must share the waypoint step ({m._wps_step(vis_wps_dist)} and {step_w} at "
+                             f"vis_wps_dist={vis_wps_dist})")
+        if m._cloud.n != cloud.n or (m is not m0 and m.points.data_ptr() != m0.points.data_ptr() and not torch.equal(m.points, m0.points)):
+            raise ValueError(f"{what}: the models must be built on the same points")
+        if (m._flags != m0._flags or (m._rig is None) != (rig is None) or bytes(m._cam.c) != bytes(cam.c) or
+                m.smoothness_weight != m0.smoothness_weight or m.traj_length_weight != m0.traj_length_weight or
+                m._clearance_on != m0._clearance_on or
+                (m0._clearance_on and (m.clearance_radius != m0.clearance_radius or m.clearance_weight != m0.clearance_weight))):
+            raise ValueError(f"{what}: the models must share the camera, rig, mode, weights and clearance settings")
+        if m is not m0 and (m.device != m0.device or float(m.eps) != float(m0.eps)):
+            raise ValueError(f"{what}: the models must live on one device and share eps")
+        if m is not m0 and rig is not None and (m._rig.n_cams != rig.n_cams or not torch.equal(m._rig.q, rig.q) or not torch.equal(m._rig.t, rig.t)):
+            raise ValueError(f"{what}: the models must share the camera rig (extrinsics differ)")
+
+
 @torch.no_grad()
 def optimize_trajectories(models, n_opt_steps=10, lr_pose=0.1, lr_quat=0.0, rewards_th=1.2, smoothness_th=0.9,
                           vis_wps_dist=0.5, betas=(0.9, 0.999), adam_eps=1e-8):
@@ -209,32 +240,136 @@ def optimize_trajectories(models, n_opt_steps=10, lr_pose=0.1, lr_quat=0.0, rewa
     trajectory that has stopped stays put while the others go on).  Each model ends up exactly — bit for bit — where its own
     `optimize_trajectory` run would have put it.  Models: ModelTraj built on the same points with the same camera, rig and
     mode, equal numbers of waypoints and the same waypoint step; no sharding, no occlusion, no prior_log_odds.  -> [TrajOptResult]."""
-    m0 = models[0]
     if any(m._prior is not None for m in models):
         raise ValueError("optimize_trajectories: a model with a log-odds prior (prior_log_odds) is not supported; run "
                          "optimize_trajectory on it")
-    cloud, cam, rig = m0._cloud, m0._cam, m0._rig
-    W = m0.poses.shape[0]
-    step_w = m0._wps_step(vis_wps_dist)
-    for m in models:
-        if (m.poses.shape[0] != W or m._wps_step(vis_wps_dist) != step_w or m._cloud.n != cloud.n or m._flags != m0._flags or
-                (m._rig is None) != (rig is None) or m._shard.world_size > 1 or m._occlusion is not None or
-                bytes(m._cam.c) != bytes(cam.c) or m.smoothness_weight != m0.smoothness_weight or
-                m.traj_length_weight != m0.traj_length_weight or m._clearance_on != m0._clearance_on or
-                (m0._clearance_on and (m.clearance_radius != m0.clearance_radius or m.clearance_weight != m0.clearance_weight))):
-            raise ValueError("optimize_trajectories: the models must share the cloud, camera, rig, mode, waypoint count, step and "
-                             "clearance settings")
-        if m is not m0 and m.points.data_ptr() != m0.points.data_ptr() and not torch.equal(m.points, m0.points):
-            raise ValueError("optimize_trajectories: the models must be built on the same points")
-        if m is not m0 and (m.device != m0.device or float(m.eps) != float(m0.eps)):
-            raise ValueError("optimize_trajectories: the models must live on one device and share eps")
-        if m is not m0 and rig is not None and (m._rig.n_cams != rig.n_cams or not torch.equal(m._rig.q, rig.q) or not torch.equal(m._rig.t, rig.t)):
-            raise ValueError("optimize_trajectories: the models must share the camera rig (extrinsics differ)")
+    _check_same_setup(models, vis_wps_dist, "optimize_trajectories")
     if n_opt_steps <= 0:   # nothing to run: the models keep their rewards and loss terms
         return [TrajOptResult(0, False, [], 0.0, 0.0) for _ in models]
     run = _OptRun(list(models), n_opt_steps, lr_pose, lr_quat, rewards_th, smoothness_th, vis_wps_dist, betas, adam_eps)
     run.run(n_opt_steps)
     return run.results(n_opt_steps)
+
+
+class TeamOptResult:
+    """optimize_team's result: steps_taken and stopped (the team's), losses (the TEAM total of every step taken), visibility_gain (the
+    team's mean reward over its first), smoothness_gains (per member) and member_losses (per member, the last step's own terms:
+    l2, length, smooth[, clearance]); loss_log: a (B, steps_taken, 8) float32 array, every member's row of every step taken
+    ([0] vis [1] l2 [2] length [3] smooth [4] the team total [5] clearance), or None when nothing ran; poses_grad (B, W, 3) /
+    quats_grad (B, W, 4): the full gradients of the last step launched (device tensors), or None."""
+
+    def __init__(self, steps_taken, stopped, losses, vis_gain, smooth_gains, member_losses, loss_log=None, poses_grad=None, quats_grad=None):
+        self.poses_grad, self.quats_grad = poses_grad, quats_grad
+        self.steps_taken, self.stopped, self.losses = steps_taken, stopped, losses
+        self.visibility_gain, self.smoothness_gains, self.member_losses, self.loss_log = vis_gain, smooth_gains, member_losses, loss_log
+
+
+def check_team(models, vis_wps_dist, what):
+    """A team's members (team coverage): what _check_same_setup demands, no point-sharded member, and at most one
+    log-odds prior — the first model's; the others have none or the same tensor.  -> the team's ops.LogOddsPrior or None."""
+    models = list(models)
+    if not models:
+        raise ValueError(f"{what}: no models")
+    for m in models:
+        if m._shard.kind == "points":
+            raise ValueError(f"{what}: a sharded model (WaypointShard / PointShard) is not supported")
+    _check_same_setup(models, vis_wps_dist, what)
+    prior = models[0]._prior
+    for m in models[1:]:
+        q = m._prior
+        if q is None or q is prior:
+            continue
+        if prior is None or not (q.values.data_ptr() == prior.values.data_ptr() or torch.equal(q.values, prior.values)):
+            raise ValueError(f"{what}: the team has ONE log-odds prior, the first model's: the other members must have none or the same "
+                             "tensor (two different priors given)")
+    return prior
+
+
+@torch.no_grad()
+def optimize_team(models, n_opt_steps=10, lr_pose=0.1, lr_quat=0.0, rewards_th=1.2, smoothness_th=0.9, vis_wps_dist=0.5,
+                  betas=(0.9, 0.999), adam_eps=1e-8):
+    """Several robots over ONE map, optimised in the same steps and rewarded ONCE for a point whichever of them sees it (DESIGN.md
+    10, team coverage).  The team's log-odds are one sum over all members' evaluated waypoints, rewards = sigmoid(that + prior); a
+    member's visibility gradient takes r (1 - r) from the team's reward; regularisers, clearance, Adam and its moments stay per
+    member; the early stop is the team's (visibility gain of the team's mean reward, every member's smooth gain).  Launches only, one
+    host synchronisation at the end.  Members: as optimize_trajectories', and at most one prior (the first model's).  Every model
+    ends with poses / quats updated in place, model.loss = its own terms and the team's vis, model.rewards = the team's rewards (one
+    tensor, shared).  A team of one is optimize_trajectory on the separate-calls path, bit for bit.  -> TeamOptResult."""
+    models = list(models)
+    prior = check_team(models, vis_wps_dist, "optimize_team")
+    B, m0 = len(models), models[0]
+    if n_opt_steps <= 0:   # nothing to run: the models keep their rewards and loss terms
+        return TeamOptResult(0, False, [], 0.0, [0.0] * B, [])
+    L = _lib.lib()
+    dev, cloud = m0.device, m0._cloud
+    n = int(n_opt_steps)
+    W = m0.poses.shape[0]
+    step_w = m0._wps_step(vis_wps_dist)
+    n_eval = (W + step_w - 1) // step_w
+    f32 = dict(dtype=torch.float32, device=dev)
+    if B == 1:   # the Parameters themselves are updated in place
+        poses, quats, poses0 = m0.poses.data, m0.quats.data, m0.poses0.contiguous()
+    else:
+        poses = torch.cat([m.poses.data for m in models]).contiguous()
+        quats = torch.cat([m.quats.data for m in models]).contiguous()
+        poses0 = torch.cat([m.poses0 for m in models]).contiguous()
+    if not (poses.is_contiguous() and quats.is_contiguous() and poses.dtype == torch.float32 and quats.dtype == torch.float32):
+        raise RuntimeError("optimize_team: poses / quats must be contiguous float32 tensors")
+    # the team's visibility step: the members' evaluated waypoints as ONE trajectory of B n_eval rows through the separate calls
+    st = m0._waypoint_step(B * n_eval)
+    # every step_w-th row of the concatenation lands on each member's rows only when W is a multiple of the step: a gather otherwise
+    strided = B == 1 or W % step_w == 0
+    stride = ((step_w - 1) & 0xffff) << 8 if strided else 0
+    src_p, src_q = (poses, quats) if strided else (torch.empty((B * n_eval, 3), **f32), torch.empty((B * n_eval, 4), **f32))
+    pg, qg = torch.zeros((B * W, 3), **f32), torch.zeros((B * W, 4), **f32)
+    moments = [torch.zeros((B * W, 3), **f32), torch.zeros((B * W, 3), **f32), torch.zeros((B * W, 4), **f32), torch.zeros((B * W, 4), **f32)]
+    loss_log = torch.zeros((B, n, 8), **f32)
+    sb = L.tohip_team_state_bytes(B, n)
+    team_state = torch.zeros(sb, dtype=torch.uint8, device=dev)
+    state = team_state[:sb // 2].view(torch.float32).view(n + 1, B, 8)
+    terms64 = team_state[sb // 2:].view(torch.float64).view(n + 1, B, 4)
+    member_terms = torch.empty((B, 8), **f32)
+    weights = (float(m0.smoothness_weight), float(m0.traj_length_weight), float(m0.eps))
+    clr = m0._clearance_on
+    clr_w, clr_rows, clr_terms = 0.0, None, None
+    if clr:   # the clearance query of all members' waypoints: one launch per step, before the tail
+        clr_w = float(m0.clearance_weight)
+        clr_rows = torch.empty((B * W, 3), **f32)
+        clr_terms = torch.empty(L.tohip_clearance_workspace_bytes(B * W) // 8, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        # every member's terms at the start: row 0 of the state's terms (a step's blocks read the others' from the row before)
+        check(L.tohip_team_loss(ptr(poses), ptr(poses0), W, B, *weights, None, 0.0, None, ptr(member_terms), ptr(terms64), None, None, None,
+                                stream_ptr()), "tohip_team_loss")
+        for i in range(n):
+            if not strided:
+                check(L.tohip_gather_waypoints_multi(ptr(poses), ptr(quats), W, B, n_eval, step_w, ptr(src_p), ptr(src_q), stream_ptr()),
+                      "tohip_gather_waypoints_multi")
+            st.step(src_p, src_q, flags_extra=stride, prior=prior)
+            if clr:
+                ops.clearance(cloud, poses, m0.clearance_radius, m0.clearance_weight, grad=clr_rows, terms=clr_terms)
+            check(L.tohip_team_step_tail(ptr(poses), ptr(quats), ptr(poses0), W, B, ptr(st.pg), ptr(st.qg), n_eval, step_w, ptr(pg), ptr(qg),
+                                         *(ptr(t) for t in moments), *weights, float(lr_pose), float(lr_quat), betas[0], betas[1], adam_eps,
+                                         float(rewards_th), float(smoothness_th), ptr(st.scalars), ptr(loss_log), n * 8, ptr(team_state), sb,
+                                         n, i, clr_w, ptr(clr_rows), ptr(clr_terms), stream_ptr()), "tohip_team_step_tail")
+    stt = state[n].cpu()   # the run's only host synchronisation
+    lt = loss_log.cpu()
+    steps = int(stt[0, 3].item())
+    rewards = st.rewards.clone()   # (the step's buffer is the next run's)
+    member_losses = []
+    for b, m in enumerate(models):
+        if B > 1:
+            m.poses.data.copy_(poses[b * W:(b + 1) * W])
+            m.quats.data.copy_(quats[b * W:(b + 1) * W])
+        torch.autograd.graph.increment_version(m.poses)
+        torch.autograd.graph.increment_version(m.quats)
+        row = lt[b, max(steps, 1) - 1]
+        m.rewards = rewards
+        m.loss = {"vis": row[0], "l2": row[1], "length": row[2], "smooth": row[3]}
+        if clr:
+            m.loss["clearance"] = row[5]
+        member_losses.append({k: float(v) for k, v in m.loss.items() if k != "vis"})
+    return TeamOptResult(steps, bool(stt[0, 2].item() != 0), lt[0, :max(steps, 1), 4].tolist(), float(stt[0, 4]),
+                         [float(x) for x in stt[:, 5]], member_losses, lt[:, :steps].numpy(), pg.view(B, W, 3), qg.view(B, W, 4))
 
 
 class PoseOptResult:
