@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_team_step_tail / tohip_team_loss / tohip_team_member_gains / tohip_team_state_bytes /
+/* (still 15) + tohip_views_bytes / tohip_views_append / tohip_views_select / tohip_views_row (greedy view selection): new symbols only.
+ * (still 15) + tohip_team_step_tail / tohip_team_loss / tohip_team_member_gains / tohip_team_state_bytes /
  * tohip_team_member_gains_bytes (team coverage): new symbols only — no struct and no existing signature changes, so a caller built
  * against the earlier header of 15 works unchanged and the number stays.
  * 15: + tohip_clearance / tohip_clearance_workspace_bytes / tohip_traj_clearance_scratch_bytes / tohip_traj_step_tail_clearance /
@@ -796,6 +797,46 @@ int tohip_team_loss(const float *poses, const float *poses0, int64_t n_wps, int6
 size_t tohip_team_member_gains_bytes(int64_t n_members);
 int tohip_team_member_gains(const void *packed, int64_t n_points, const float *lo_members, int64_t n_members, const void *prior_buf,
                             int64_t *sums, size_t sums_bytes, void *stream);
+
+/* ---- greedy view selection: the best k of M candidate views (views_kernels.hip) --------------------------------
+ * A candidate view's log-odds row is the row tohip_traj_forward_multi writes for it taken as a trajectory of one body waypoint
+ * (n_traj = M, traj_offsets = 0..M; a rig's C virtual waypoints summed into the one row).  The rows are kept as one CSR structure in
+ * `views` (tohip_views_bytes(n_points, n_candidates, nnz_capacity) device bytes, caller-owned; its first 256 bytes — the header — zero-filled once before the first use): per candidate its
+ * (packed index u32, log-odds f32) pairs with log-odds > 0, pads excluded, in ascending index order.  Layout, every section aligned
+ * to 256 bytes: [header 32 x int64: [0] entries stored [1] entries needed by everything appended so far [2] status — bit 0: the
+ * capacity does not hold them, bit 1: an append that did not continue the set [3] candidates appended [4] selection stopped]
+ * [offsets (M + 1) int64] [absent M int32] [gain sums M int64] [chosen M int32] [segment counts 256 x ceil(Npad / 8192) int32]
+ * [idx capacity u32] [val capacity f32].  Every call takes the three sizes the buffer was sized with.
+ *
+ * tohip_views_append: rows first .. first + n_rows - 1 of the set from lo_rows (n_rows, Npad) — one chunk of the forward's output,
+ * n_rows <= TOHIP_VIEWS_MAX_CHUNK; chunks in order, first = 0 starts the set anew.  A row that holds a NaN (a view that sees nothing
+ * at all: max p == min p) makes its candidate ABSENT: no entries, absent[c] = 1, never chosen.  Three launches (count per segment, a
+ * one-block scan with the capacity check, ordered write).  A chunk that does not fit writes no entry and no offset: the status and
+ * the needed count are all that change, and every later append and select is a no-op on the status.  needed_host = NULL: launches
+ * only (read the header when convenient).  Non-NULL: the call SYNCHRONISES the stream, stores the entries needed by everything
+ * appended so far and returns TOHIP_ENOSPC when the capacity does not hold them — size a new buffer with that count and append again
+ * from first = 0.
+ *
+ * tohip_views_select: k greedy rounds, two launches each, nothing synchronises.  With F(x) = sum_i reward_fixed(r_i) of the rewards
+ * tohip_traj_reward / _prior give for lo_sum = x (prior_buf: NULL or tohip_traj_prior_build's, same cloud), S = 0 and in round j
+ * G_c = F(S + lo_c) - F(S) over candidate c's entries for every c neither chosen nor absent; c* = argmax G_c, ties to the lowest
+ * index; the selection ends without choosing when no candidate is left, G_c* <= 0 or G_c* / 2^shift / N < min_gain (f64; shift =
+ * 47 - ceil(log2 N)); else order[j] = c*, gain_fixed[j] = G_c*, S += lo_c* (f32), *n_selected = j + 1.  S: Npad floats, packed order
+ * (zeroed by the call; pads stay 0) — what tohip_traj_coverage and tohip_traj_reward(_prior) take.  order / gain_fixed: k entries.
+ * Integer sums: the same result in every run.  The call uses the sums and flags inside `views`: one selection at a time per set.
+ *
+ * tohip_views_row: candidate c's list scattered back into row (Npad floats: zero where nothing is stored, pads included; NaN at
+ * every point for an absent candidate) — for tests and for looking.  Two launches. */
+#define TOHIP_VIEWS_MAX_CHUNK 256
+#define TOHIP_VIEWS_MAX_CANDIDATES 65536
+size_t tohip_views_bytes(int64_t n_points, int64_t n_candidates, int64_t nnz_capacity);
+int tohip_views_append(void *views, size_t views_bytes, int64_t n_points, int64_t n_candidates, int64_t nnz_capacity,
+                       const float *lo_rows, int64_t first, int64_t n_rows, int64_t *needed_host, void *stream);
+int tohip_views_select(void *views, size_t views_bytes, int64_t n_points, int64_t n_candidates, int64_t nnz_capacity,
+                       const void *prior_buf, int64_t k, double min_gain, float *S, int32_t *order, int64_t *gain_fixed,
+                       int32_t *n_selected, void *stream);
+int tohip_views_row(const void *views, size_t views_bytes, int64_t n_points, int64_t n_candidates, int64_t nnz_capacity,
+                    int64_t candidate, float *row, void *stream);
 
 /* ---- optional per-kernel timing (bench.py's roofline leg) -----------------------------------------
  * When enabled, every launch of the big kernels is bracketed by hipEventRecord on its own stream.

@@ -184,6 +184,10 @@ SIGNATURES = {
     "tohip_team_loss": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_f, c_f, c_f, c_vp, c_f, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "tohip_team_member_gains_bytes": (c_sz, [c_i64]),
     "tohip_team_member_gains": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "tohip_views_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "tohip_views_append": (ctypes.c_int, [c_vp, c_sz, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, ctypes.POINTER(c_i64), c_vp]),
+    "tohip_views_select": (ctypes.c_int, [c_vp, c_sz, c_i64, c_i64, c_i64, c_vp, c_i64, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "tohip_views_row": (ctypes.c_int, [c_vp, c_sz, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp]),
     "tohip_clearance_workspace_bytes": (c_sz, [c_i64]),
     "tohip_clearance": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_f, c_f, c_vp, c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_sz, c_vp]),
     "tohip_traj_clearance_scratch_bytes": (c_sz, [c_i64, c_i64]),

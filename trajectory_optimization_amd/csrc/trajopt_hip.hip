@@ -10,6 +10,7 @@
 #include "hull_kernels.hip"
 #include "optim_kernels.hip"
 #include "team_kernels.hip"
+#include "views_kernels.hip"
 #include "loss_kernels.hip"
 #include "ingest_kernels.hip"
 #include "render_kernels.hip"

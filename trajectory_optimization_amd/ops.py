@@ -462,6 +462,165 @@ def team_loss(poses, poses0, n_members, smoothness_weight, traj_length_weight, e
     return terms, total, reg
 
 
+VIEWS_MAX_CHUNK = 256          # TOHIP_VIEWS_MAX_CHUNK
+VIEWS_MAX_CANDIDATES = 65536   # TOHIP_VIEWS_MAX_CANDIDATES
+VIEWS_CHUNK_BYTES = 1 << 30    # the dense (chunk, npad) f32 rows a ViewSet compacts at a time: 256 candidates at 1 M points
+
+
+def check_views(cand_poses, cand_quats, k, min_gain=0.0, chunk=None):
+    """The arguments of a view selection: cand_poses (M,3) and cand_quats (M,4) floating tensors with the same M in
+    [1, VIEWS_MAX_CANDIDATES], finite; 1 <= k (an int); min_gain a finite number >= 0; chunk None or an int in [1, VIEWS_MAX_CHUNK]
+    -> (M, k clipped to M, min_gain); ValueError otherwise."""
+    for name, t, w in (("cand_poses", cand_poses, 3), ("cand_quats", cand_quats, 4)):
+        if not torch.is_tensor(t) or not t.is_floating_point():
+            raise ValueError(f"{name} must be a floating-point tensor, got {type(t).__name__}"
+                             f"{'' if not torch.is_tensor(t) else ' of ' + str(t.dtype)}")
+        if t.dim() != 2 or t.shape[1] != w or t.shape[0] == 0:
+            raise ValueError(f"{name} must have shape (M,{w}) with M >= 1, got {tuple(t.shape)}")
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError(f"{name} must be finite (NaN or inf found)")
+    M = cand_poses.shape[0]
+    if cand_quats.shape[0] != M:
+        raise ValueError(f"cand_poses holds {M} candidates, cand_quats {cand_quats.shape[0]}")
+    if M > VIEWS_MAX_CANDIDATES:
+        raise ValueError(f"at most {VIEWS_MAX_CANDIDATES} candidate views, got {M}")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError(f"k must be an integer >= 1, got {k!r}")
+    try:
+        g = float(min_gain)
+    except (TypeError, ValueError):
+        g = float("nan")
+    if not (np.isfinite(g) and g >= 0.0):
+        raise ValueError(f"min_gain must be a finite number >= 0, got {min_gain!r}")
+    if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or not 1 <= chunk <= VIEWS_MAX_CHUNK):
+        raise ValueError(f"chunk must be None or an integer in [1, {VIEWS_MAX_CHUNK}], got {chunk!r}")
+    return M, min(int(k), M), g
+
+
+def views_layout(npad, n_candidates, nnz_capacity):
+    """Byte offsets of a view set's sections (include/trajopt_hip.h, tohip_views_bytes): every section aligned to 256 bytes."""
+    up = lambda v: (v + 255) // 256 * 256
+    M, nseg = n_candidates, (npad + 8191) // 8192
+    out, o = {"header": 0}, 256
+    for name, nbytes in (("offsets", 8 * (M + 1)), ("absent", 4 * M), ("gain", 8 * M), ("chosen", 4 * M),
+                         ("segments", 4 * VIEWS_MAX_CHUNK * nseg), ("idx", 4 * nnz_capacity), ("val", 4 * nnz_capacity)):
+        out[name] = o
+        o += up(nbytes)
+    out["total"] = o
+    return out
+
+
+class ViewSet:
+    """M candidate views over one packed cloud as sparse log-odds rows (tohip_views_append): per candidate the (packed index,
+    log-odds) pairs of the row traj_forward gives it as a trajectory of its own with one body waypoint, ascending, zeros and pads
+    left out.  Owns the CSR buffers; `append` runs the forward in chunks of `chunk` candidates (default: as many as keep the dense
+    chunk, chunk x npad x 4 bytes, within VIEWS_CHUNK_BYTES; at most VIEWS_MAX_CHUNK) and compacts each.  nnz_capacity: entries the
+    buffers hold (default 1 % of M x N); a set that outgrows it stores nothing more and says so in `status()`."""
+
+    def __init__(self, cloud, cam, n_candidates, rig=None, flags=0, nnz_capacity=None, chunk=None):
+        L = _lib.lib()
+        self.cloud, self.cam, self.rig, self.flags = cloud, cam, rig, int(flags)
+        self.n_candidates = int(n_candidates)
+        self.capacity = int(nnz_capacity) if nnz_capacity is not None else max(4096, self.n_candidates * cloud.n // 100)
+        self.chunk = int(chunk) if chunk is not None else max(1, min(VIEWS_MAX_CHUNK, VIEWS_CHUNK_BYTES // (4 * cloud.npad)))
+        self.bytes = L.tohip_views_bytes(cloud.n, self.n_candidates, self.capacity)
+        if self.bytes == 0 or not 1 <= self.chunk <= VIEWS_MAX_CHUNK:
+            raise ValueError(f"a view set of {n_candidates} candidates x {self.capacity} entries in chunks of {self.chunk} is out of range")
+        self.layout = views_layout(cloud.npad, self.n_candidates, self.capacity)
+        assert self.layout["total"] == self.bytes
+        self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=cloud.device)
+        self.buf[:256].zero_()   # the header: an empty set until the first append
+        self.appended = 0
+        self._ws, self._dense = {}, None
+
+    def _sizes(self):
+        return ptr(self.buf), self.bytes, self.cloud.n, self.n_candidates, self.capacity
+
+    def _section(self, name, count, dtype):
+        o = self.layout[name]
+        return self.buf[o:o + count * torch.empty(0, dtype=dtype).element_size()].view(dtype)
+
+    def append(self, poses, quats, occ=None):
+        """The next candidates: poses (n,3), quats (n,4) wxyz on the cloud's device; occ: their occlusion bit rows (n C, npad/32), one
+        per virtual waypoint, or None.  Launches only."""
+        c, C = self.cloud, self.rig.n_cams if self.rig is not None else 1
+        n = poses.shape[0]
+        if self.appended + n > self.n_candidates:
+            raise ValueError(f"the view set holds {self.n_candidates} candidates: {self.appended} appended, {n} more given")
+        if self._dense is None:
+            self._dense = torch.empty((self.chunk, c.npad), dtype=torch.float32, device=c.device)
+        L = _lib.lib()
+        for w0 in range(0, n, self.chunk):
+            t = min(self.chunk, n - w0)
+            ws = self._ws.get(t)
+            if ws is None:   # a workspace per chunk size: its layout depends on the number of trajectories
+                ws = self._ws[t] = (TrajWorkspace(c, t * C, t), torch.arange(t + 1, dtype=torch.int32, device=c.device))
+            ps, qs = poses[w0:w0 + t].contiguous(), quats[w0:w0 + t].contiguous()
+            rows = occ[w0 * C:(w0 + t) * C].contiguous() if occ is not None else None
+            lo = self._dense[:t]
+            traj_forward(c, ps, qs, self.cam, ws[0], self.rig, flags=self.flags, occ=rows, lo_sum=lo, traj_offsets=ws[1])
+            with torch.cuda.device(c.device):
+                check(L.tohip_views_append(*self._sizes(), ptr(lo), self.appended, t, None, stream_ptr()), "tohip_views_append")
+            self.appended += t
+
+    def header(self):
+        """The header's first five words on the device: entries stored, entries needed, status, candidates appended, stopped."""
+        return self.buf[:40].view(torch.int64)
+
+    def status(self):
+        """-> (entries stored, entries needed by everything appended, fits) — one device-to-host read."""
+        h = self.header().cpu()
+        if int(h[2]) & 2:
+            raise RuntimeError("the view set's chunks were not appended in order")
+        return int(h[0]), int(h[1]), int(h[2]) == 0
+
+    @property
+    def nnz(self):
+        return self.status()[0]
+
+    @property
+    def absent(self):
+        """(M,) bool on the device: the candidates whose row is NaN (a view that sees nothing at all); never chosen."""
+        return self._section("absent", self.n_candidates, torch.int32)[:self.appended] != 0
+
+    @property
+    def offsets(self):
+        return self._section("offsets", self.n_candidates + 1, torch.int64)[:self.appended + 1]
+
+    def entries(self):
+        """-> (idx int32, val f32) views of the stored entries (the first nnz of the capacity), candidate after candidate."""
+        nnz = self.nnz
+        return self._section("idx", self.capacity, torch.int32)[:nnz], self._section("val", self.capacity, torch.float32)[:nnz]
+
+    def row(self, c):
+        """Candidate c's list scattered back to a dense (npad,) f32 row in packed order (zeros where nothing is stored, pads
+        included; NaN at every point of an absent candidate)."""
+        if not 0 <= int(c) < self.appended:
+            raise IndexError(f"candidate {c} of {self.appended}")
+        row = torch.empty(self.cloud.npad, dtype=torch.float32, device=self.cloud.device)
+        with torch.cuda.device(self.cloud.device):
+            check(_lib.lib().tohip_views_row(*self._sizes(), int(c), ptr(row), stream_ptr()), "tohip_views_row")
+        return row
+
+
+def views_select(viewset, k, prior=None, min_gain=0.0):
+    """tohip_views_select: k greedy rounds over a complete ViewSet -> (order (k,) int32, gain_fixed (k,) int64, n_selected (1,) int32,
+    S (npad,) f32 in packed order), all on the device, nothing synchronised; the first n_selected entries of order / gain_fixed count.
+    prior: a LogOddsPrior over the set's cloud or None."""
+    if viewset.appended != viewset.n_candidates:
+        raise ValueError(f"the view set holds {viewset.appended} of its {viewset.n_candidates} candidates: append the rest first")
+    c = viewset.cloud
+    k = int(k)
+    order = torch.zeros(k, dtype=torch.int32, device=c.device)
+    gain = torch.zeros(k, dtype=torch.int64, device=c.device)
+    n_sel = torch.empty(1, dtype=torch.int32, device=c.device)
+    S = torch.empty(c.npad, dtype=torch.float32, device=c.device)
+    with torch.cuda.device(c.device):
+        check(_lib.lib().tohip_views_select(*viewset._sizes(), ptr(prior.buf) if prior is not None else None, k, float(min_gain), ptr(S),
+                                            ptr(order), ptr(gain), ptr(n_sel), stream_ptr()), "tohip_views_select")
+    return order, gain, n_sel, S
+
+
 def team_member_gains(cloud, lo_members, prior=None):
     """tohip_team_member_gains over the (B, npad) per-member log-odds rows traj_forward leaves with traj_offsets -> (gain (B,) f64:
     the team's mean reward minus the team's without member b; count (B,) int64: the points with lo_b > 0), on the host.  Integer

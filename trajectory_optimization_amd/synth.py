@@ -65,6 +65,27 @@ def make_path(n_wps, optical=True, jitter_seed=None, scale=1.0):
     return pos.astype(np.float32), q.astype(np.float32)
 
 
+def candidate_grid(xs, ys, z, n_headings):
+    """Candidate views for a view selection: positions xs x ys at height z, n_headings headings 2 pi j / n_headings + 0.1 at each;
+    quaternion r_z(heading) (x) Q_OPTICAL (the camera looks along the heading); candidate index = (ix * len(ys) + iy) * n_headings + j.
+    -> (poses (M,3) f32, wxyz quats (M,4) f32)."""
+    poses, quats = [], []
+    for x in xs:
+        for y in ys:
+            for j in range(n_headings):
+                a = 2.0 * np.pi * j / n_headings + 0.1
+                poses.append([x, y, z])
+                quats.append(quat_mul(np.array([np.cos(a / 2), 0.0, 0.0, np.sin(a / 2)]), Q_OPTICAL))
+    return np.asarray(poses, dtype=np.float32), np.asarray(quats, dtype=np.float32)
+
+
+def bundled_candidate_grid(points, path, g=6, n_headings=4):
+    """The candidate grid over a scanned cloud: x in linspace(min_x + 3, max_x - 3, g), y likewise, z = the mean z of `path`."""
+    lo, hi = points.min(axis=0).astype(np.float64), points.max(axis=0).astype(np.float64)
+    return candidate_grid(np.linspace(lo[0] + 3, hi[0] - 3, g), np.linspace(lo[1] + 3, hi[1] - 3, g),
+                          float(np.asarray(path)[:, 2].astype(np.float64).mean()), n_headings)
+
+
 def camera_rig(n_cams=5):
     """Fixed extrinsics of a multi-camera rig: yaw offsets 0, +-72, +-144 deg
     about the body z axis, shared K (BASELINE.json config 5). Returns wxyz

@@ -207,3 +207,126 @@ def fuse_log_odds(*maps, clamp_max=None):
     if clamp_max is not None:
         out.clamp_(max=float(clamp_max))
     return out
+
+
+class ViewSelection:
+    """What select_views returns: order (n_selected,) int64 and gains (n_selected,) f64 on the host (gain j = what view order[j] added
+    to the mean reward when it was chosen), poses / quats (the chosen rows in selection order), rewards (N,) and mean_reward of the
+    chosen views together (with the prior), coverage_log_odds (N,) in the caller's order (prior + the chosen views' log-odds: the next
+    plan's prior), nnz (entries the candidates' sparse rows hold), absent (M,) bool (the candidates that see nothing at all),
+    gain_fixed (n_selected,) int64 (the integer sums behind `gains`) and log_odds (npad,) the chosen views' summed log-odds in the
+    packed order."""
+    __slots__ = ("order", "gains", "gain_fixed", "poses", "quats", "rewards", "mean_reward", "coverage_log_odds", "nnz", "absent", "log_odds")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    @property
+    def n_selected(self):
+        return int(self.order.shape[0])
+
+
+def _views_setup(model_or_cloud, prior_log_odds, occlusion, kw):
+    """select_views' first argument resolved -> dict(cloud, cam, rig, flags, prior, occlusion, limits); cloud / prior may still be
+    what the caller gave (points / a tensor): they are packed after every check has passed."""
+    m = model_or_cloud
+    if hasattr(m, "_cloud") and hasattr(m, "_shard"):   # a ModelTraj: its own settings, nothing to override
+        if m._shard.kind == "points" or m._shard.world_size > 1 or m._shard.collective:
+            raise ValueError("select_views: a sharded model (WaypointShard / PointShard) is not supported")
+        if kw:
+            raise ValueError(f"select_views: {sorted(kw)} belong to the call with points; a ModelTraj brings its own camera and rig")
+        if occlusion is not None and occlusion != m._occlusion:
+            raise ValueError(f"select_views: occlusion={occlusion!r} given, the model has {m._occlusion!r}")
+        prior = m._prior if prior_log_odds is None else prior_log_odds
+        return dict(cloud=m._cloud, cam=m._cam, rig=m._rig, flags=m._flags, prior=prior, occlusion=m._occlusion,
+                    limits=m._occlusion_limits)
+    if occlusion not in (None, "hpr", "zbuffer"):
+        raise ValueError("occlusion must be None, 'hpr' or 'zbuffer'")
+    allowed = {"intrins", "img_width", "img_height", "min_dist", "max_dist", "rig", "dense", "occlusion_limits"}
+    if set(kw) - allowed:
+        raise ValueError(f"select_views: unknown keyword(s) {sorted(set(kw) - allowed)}")
+    missing = [k for k in ("intrins", "img_width", "img_height") if k not in kw]
+    if missing:
+        raise ValueError(f"select_views: with points or a PackedCloud the camera is needed: {missing} missing")
+    if isinstance(m, ops.PackedCloud):
+        if not m.sorted:
+            raise ValueError("select_views: the PackedCloud must be in Morton order (sort=True), as ModelTraj's")
+        n = m.n
+    else:
+        if not torch.is_tensor(m) or m.dim() != 2 or m.shape[1] != 3 or m.shape[0] == 0:
+            raise ValueError(f"select_views: points must be an (N,3) tensor with N > 0, a PackedCloud or a ModelTraj, got "
+                             f"{tuple(m.shape) if torch.is_tensor(m) else type(m).__name__}")
+        n = m.shape[0]
+    if prior_log_odds is not None:
+        ops.check_prior(prior_log_odds, n)
+    cam = ops.Camera(kw["intrins"], kw["img_width"], kw["img_height"], kw.get("min_dist", 1.0), kw.get("max_dist", 5.0))
+    return dict(cloud=m, cam=cam, rig=kw.get("rig"), flags=ops.DENSE if kw.get("dense") else 0, prior=prior_log_odds, occlusion=occlusion,
+                limits=kw.get("occlusion_limits", (1.0, 15.0)))
+
+
+def select_views(model_or_cloud, cand_poses, cand_quats, k, prior_log_odds=None, min_gain=0.0, occlusion=None, clamp_max=None, chunk=None,
+                 **camera):
+    """Greedy view selection: out of the M candidate views cand_poses (M,3) / cand_quats (M,4) wxyz, choose up to k
+    that together cover the most, against what prior_log_odds (N,) already holds.  Round after round the view that adds the most to
+    the mean reward sigmoid(S + prior) is chosen (S: the log-odds of the views chosen so far; ties go to the lowest index) until k
+    are chosen, none is left, the best adds nothing or adds less than min_gain to the mean reward.  The objective is monotone
+    submodular: the greedy choice is within (1 - 1/e) of the best set of that size.
+
+    model_or_cloud: a ModelTraj — its cloud, camera, rig, dense mode, prior and occlusion setting score the candidates exactly as
+    that model rewards them (prior_log_odds overrides its prior) — or (N,3) points / an ops.PackedCloud with the keywords intrins,
+    img_width, img_height[, min_dist, max_dist, rig=(quats, trans), dense, occlusion_limits] as the models take them.
+    occlusion='hpr'|'zbuffer': every candidate's occlusion rows are built chunk by chunk (ops.occlusion_bits).  clamp_max: OctoMap's
+    upper clamping threshold for coverage_log_odds.  chunk: candidates per forward (None: ops.ViewSet's default).
+    -> ViewSelection.  One host synchronisation at the end (the hull pass's own with occlusion; one more run when the candidates'
+    rows outgrow the first capacity guess, 1 % of M x N)."""
+    cfg = _views_setup(model_or_cloud, prior_log_odds, occlusion, camera)
+    M, k, min_gain = ops.check_views(cand_poses, cand_quats, k, min_gain, chunk)
+    if clamp_max is not None and not float(clamp_max) >= 0.0:
+        raise ValueError(f"clamp_max must be a number >= 0 or None, got {clamp_max!r}")
+    cloud = cfg["cloud"]
+    if not isinstance(cloud, ops.PackedCloud):
+        cloud = ops.PackedCloud(torch.as_tensor(cloud, dtype=torch.float32))
+    dev = cloud.device
+    prior = cfg["prior"]
+    if prior is not None and not isinstance(prior, ops.LogOddsPrior):
+        prior = ops.LogOddsPrior(cloud, prior)   # (checks it: ops.check_prior)
+    rig = cfg["rig"]
+    if rig is not None and not isinstance(rig, ops.CameraRig):
+        rig = ops.CameraRig(rig[0], rig[1], dev)
+    ps = cand_poses.detach().to(device=dev, dtype=torch.float32).contiguous()
+    qs = cand_quats.detach().to(device=dev, dtype=torch.float32).contiguous()
+    occ_of = None
+    if cfg["occlusion"] is not None:
+        from .model import ModelTraj   # (model imports this module)
+        shim = types.SimpleNamespace(_rig=rig, _cloud=cloud, points=cloud.points, _cam=cfg["cam"], _occlusion_limits=cfg["limits"],
+                                     _occlusion=cfg["occlusion"])
+        occ_of = lambda p, q: ModelTraj._build_occlusion_rows(shim, p, q)
+    capacity = None
+    for attempt in range(2):
+        vs = ops.ViewSet(cloud, cfg["cam"], M, rig=rig, flags=cfg["flags"], nnz_capacity=capacity, chunk=chunk)
+        for w0 in range(0, M, vs.chunk):
+            p, q = ps[w0:w0 + vs.chunk], qs[w0:w0 + vs.chunk]
+            vs.append(p, q, occ_of(p, q) if occ_of is not None else None)
+        order, gain, n_sel, S = ops.views_select(vs, k, prior, min_gain)
+        ws = ops.TrajWorkspace(cloud, 1)
+        rewards, scalars = ops.traj_reward(cloud, S, cfg["cam"], ws, prior=prior)
+        coverage = ops.traj_coverage(cloud, S, prior, clamp_max)
+        absent = vs.absent
+        # the one synchronisation: everything small in one copy
+        h = torch.cat([vs.header(), n_sel.long(), order.long(), gain]).cpu()
+        if int(h[2]) & 2:
+            raise RuntimeError("select_views: the view set's chunks were not appended in order")
+        if int(h[2]) == 0:
+            break
+        if attempt == 1:
+            raise RuntimeError(f"select_views: the candidates' rows need {int(h[1])} entries, more than the reported {capacity}")
+        capacity = int(h[1])
+    n = int(h[5])
+    sel = h[6:6 + n].clone()
+    gfix = h[6 + k:6 + k + n].clone()
+    shift = 47 - (cloud.n - 1).bit_length()   # the reward kernel's fixed point
+    idx = sel.to(dev)
+    return ViewSelection(order=sel, gain_fixed=gfix, gains=gfix.to(torch.float64) / float(2 ** shift) / cloud.n, poses=ps[idx], quats=qs[idx],
+                         rewards=rewards, mean_reward=float(scalars[0]), coverage_log_odds=coverage, nnz=int(h[0]), absent=absent.cpu(),
+                         log_odds=S)
