@@ -37,7 +37,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_views_bytes / tohip_views_append / tohip_views_select / tohip_views_row (greedy view selection): new symbols only.
+/* (still 15) + tohip_covmap_bytes / tohip_covmap_init / tohip_covmap_integrate / tohip_covmap_lookup / tohip_covmap_merge /
+ * tohip_covmap_rehash / tohip_covmap_export / tohip_covmap_read_header (the voxel-keyed log-odds map): new symbols only.
+ * (still 15) + tohip_views_bytes / tohip_views_append / tohip_views_select / tohip_views_row (greedy view selection): new symbols only.
  * (still 15) + tohip_team_step_tail / tohip_team_loss / tohip_team_member_gains / tohip_team_state_bytes /
  * tohip_team_member_gains_bytes (team coverage): new symbols only — no struct and no existing signature changes, so a caller built
  * against the earlier header of 15 works unchanged and the number stays.
@@ -837,6 +839,57 @@ int tohip_views_select(void *views, size_t views_bytes, int64_t n_points, int64_
                        int32_t *n_selected, void *stream);
 int tohip_views_row(const void *views, size_t views_bytes, int64_t n_points, int64_t n_candidates, int64_t nnz_capacity,
                     int64_t candidate, float *row, void *stream);
+
+/* ---- a voxel-keyed log-odds map: coverage carried across changing clouds (covmap_kernels.hip) --------------------
+ * What tohip_traj_coverage returns is indexed by the rows of one cloud.  This map keys it by position: a hash table of voxels on the
+ * device that a coverage row is folded into and that ANY later cloud reads its prior from (tohip_traj_prior_build takes the result).
+ *
+ * Key of a point: per axis i = (int) floorf((x - origin) / resolution), in f32 throughout (correctly rounded division); the three
+ * indices + 2^20, 21 bits each, packed x | y | z from the high end into a uint64; all ones marks an empty slot.  A point with a
+ * non-finite coordinate or an index outside [-2^20, 2^20) is SKIPPED: counted, stored nowhere, read back as 0.
+ *
+ * Buffer (tohip_covmap_bytes(capacity) = 256 + 16 x capacity device bytes, caller-owned, 16-byte aligned; capacity a power of two in
+ * [16, 2^32]): [header 256 B][capacity slots of 16 B: uint64 key | f32 value | uint32 pending].  Header, int64 words: [0] voxels
+ * held [1] capacity [2] status of the last integrate / merge / rehash — bit 0: it would have left the table more than half full,
+ * bit 1: a probe gave up (the table filled up while the call ran), bit 2: a merge of maps whose origin or resolution differ
+ * [3] voxels the map holds after that call, or would have to hold (with bit 1 a lower bound: size for [0] + n_points instead)
+ * [4] points that call skipped [5] rows it skipped for their log-odds (negative or non-finite) [6], [7] scratch; then five f32 at
+ * byte 64: origin x, y, z, resolution, clamp_max.  tohip_covmap_init writes all of it (one launch): an empty map.
+ *
+ * tohip_covmap_integrate: points (n, 3) f32 rows and log_odds (n) f32 in the same order.  The observation of a voxel is the MAXIMUM
+ * over the call's points that fall into it; then, one f32 operation per voxel, value = min(max(old, obs), clamp_max)
+ * (TOHIP_COVMAP_MAX: a fused row, prior + lo_sum — idempotent) or min(old + obs, clamp_max) (TOHIP_COVMAP_ADD: an independent
+ * observation); a voxel not seen before starts from 0 and is created even when its observation is 0.  fold != 0: runs of equal keys
+ * in consecutive rows are reduced inside the wave before the table is touched (what the host layer passes: up to 4 x faster on rows
+ * sorted by voxel, at most 0.02 ms slower at 1 M unsorted rows — DESIGN.md 10, Measured); 0: every row probes.  Same map either way.  The result — values, count, skipped counts — is the same in every run and under any permutation of the rows;
+ * only the slot a key lands in may differ.  A call that would leave the table more than half full changes NOTHING but words 2..5:
+ * the status and the needed count.  Allocate a map of capacity >= 2 x needed, tohip_covmap_rehash the old one into it and call again.
+ * header_host = NULL: launches only.  Non-NULL (8 int64 on the host): the call SYNCHRONISES the stream, stores header words 0..7 and
+ * returns TOHIP_ENOSPC when status bits 0 / 1 are set (TOHIP_EINVAL for bit 2).  Three launches.
+ *
+ * tohip_covmap_lookup: out[i] = the value of point i's voxel; 0 for a voxel the map does not hold and for a skipped point.  One
+ * launch, nothing synchronises, the map is not written.
+ * tohip_covmap_merge: every voxel of `other` integrated as one observation with the same two rules (same capacity rule and
+ * header_host as integrate).  tohip_covmap_rehash: the same with TOHIP_COVMAP_MAX — into an empty map, a copy: the growth of a table.
+ * tohip_covmap_export: the live voxels in no particular order (sort by key for a reproducible one): keys[v] (the packed key as
+ * int64), values[v], centres[3 v ..] = origin + (index + 1/2) x resolution; at most out_capacity are written (size with word [0]).
+ * tohip_covmap_read_header: SYNCHRONISES; words_host: 8 int64, geometry_host: 5 floats or NULL. */
+#define TOHIP_COVMAP_MAX 0
+#define TOHIP_COVMAP_ADD 1
+size_t tohip_covmap_bytes(int64_t capacity);
+int tohip_covmap_init(void *map, size_t map_bytes, int64_t capacity, const float *origin_host, float resolution, float clamp_max,
+                      void *stream);
+int tohip_covmap_integrate(void *map, size_t map_bytes, int64_t capacity, const float *points, const float *log_odds, int64_t n_points,
+                           int mode, int fold, int64_t *header_host, void *stream);
+int tohip_covmap_lookup(const void *map, size_t map_bytes, int64_t capacity, const float *points, int64_t n_points, float *out,
+                        void *stream);
+int tohip_covmap_merge(void *map, size_t map_bytes, int64_t capacity, const void *other, size_t other_bytes, int64_t other_capacity,
+                       int mode, int64_t *header_host, void *stream);
+int tohip_covmap_rehash(void *map, size_t map_bytes, int64_t capacity, const void *old_map, size_t old_bytes, int64_t old_capacity,
+                        int64_t *header_host, void *stream);
+int tohip_covmap_export(void *map, size_t map_bytes, int64_t capacity, int64_t out_capacity, int64_t *keys, float *values,
+                        float *centres, void *stream);
+int tohip_covmap_read_header(const void *map, int64_t *words_host, float *geometry_host, void *stream);
 
 /* ---- optional per-kernel timing (bench.py's roofline leg) -----------------------------------------
  * When enabled, every launch of the big kernels is bracketed by hipEventRecord on its own stream.

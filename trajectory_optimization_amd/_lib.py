@@ -188,6 +188,14 @@ SIGNATURES = {
     "tohip_views_append": (ctypes.c_int, [c_vp, c_sz, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, ctypes.POINTER(c_i64), c_vp]),
     "tohip_views_select": (ctypes.c_int, [c_vp, c_sz, c_i64, c_i64, c_i64, c_vp, c_i64, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "tohip_views_row": (ctypes.c_int, [c_vp, c_sz, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp]),
+    "tohip_covmap_bytes": (c_sz, [c_i64]),
+    "tohip_covmap_init": (ctypes.c_int, [c_vp, c_sz, c_i64, ctypes.POINTER(c_f), c_f, c_f, c_vp]),
+    "tohip_covmap_integrate": (ctypes.c_int, [c_vp, c_sz, c_i64, c_vp, c_vp, c_i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_i64), c_vp]),
+    "tohip_covmap_lookup": (ctypes.c_int, [c_vp, c_sz, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "tohip_covmap_merge": (ctypes.c_int, [c_vp, c_sz, c_i64, c_vp, c_sz, c_i64, ctypes.c_int, ctypes.POINTER(c_i64), c_vp]),
+    "tohip_covmap_rehash": (ctypes.c_int, [c_vp, c_sz, c_i64, c_vp, c_sz, c_i64, ctypes.POINTER(c_i64), c_vp]),
+    "tohip_covmap_export": (ctypes.c_int, [c_vp, c_sz, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "tohip_covmap_read_header": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_f), c_vp]),
     "tohip_clearance_workspace_bytes": (c_sz, [c_i64]),
     "tohip_clearance": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_f, c_f, c_vp, c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_sz, c_vp]),
     "tohip_traj_clearance_scratch_bytes": (c_sz, [c_i64, c_i64]),

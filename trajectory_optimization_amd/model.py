@@ -776,7 +776,8 @@ class ModelTraj(nn.Module):
     through the hard pipeline of /root/reference/src/pc_processor.py:171-178 (frustum cull with `occlusion_limits`,
     then HPR from the camera centre) and the points it hides get p = 0 for that waypoint;
     `prior_log_odds=` an (N,) tensor of what is already known of the map (OctoMap's accumulated log-odds, >= 0, in the caller's point
-    order): rewards become sigmoid(lo_sum + prior) — see the prior_log_odds property and coverage_log_odds().
+    order): rewards become sigmoid(lo_sum + prior) — see the prior_log_odds property and coverage_log_odds().  An ops.CoverageMap is
+    accepted in its place: the prior is its lookup over this cloud (commit_coverage folds a plan back into it).
     """
 
     def __init__(self,
@@ -932,7 +933,8 @@ class ModelTraj(nn.Module):
             return
         if self._shard.kind == "points":
             raise ValueError("prior_log_odds needs the whole cloud on every rank: not available with PointShard")
-        self._prior = ops.LogOddsPrior(self._cloud, prior)   # (checks it: ops.check_prior)
+        # (a CoverageMap: its lookup over this cloud; checks the result: ops.check_prior)
+        self._prior = ops.LogOddsPrior(self._cloud, ops.resolve_prior(prior, self._cloud))
 
     @torch.no_grad()
     def coverage_log_odds(self, upto=None, clamp_max=None, vis_wps_dist=0.5):
@@ -956,6 +958,14 @@ class ModelTraj(nn.Module):
         else:
             lo_sum = torch.zeros(cloud.npad, dtype=torch.float32, device=cloud.device)
         return ops.traj_coverage(cloud, lo_sum, self._prior, clamp_max)
+
+    def commit_coverage(self, coverage_map, upto=None, vis_wps_dist=0.5):
+        """Fold what this plan has seen into an ops.CoverageMap: coverage_log_odds(upto, the map's clamp_max, vis_wps_dist) integrated
+        over this model's points with mode 'max' (the row holds the prior, which a model built with prior_log_odds=map read from that
+        map).  Any later cloud reads it back: ModelTraj(other_points, ..., prior_log_odds=coverage_map).  -> the map."""
+        if self._shard.kind == "points" or self._shard.world_size > 1 or self._shard.collective:
+            raise ValueError("commit_coverage: a sharded model (WaypointShard / PointShard) is not supported")
+        return coverage_map.integrate(self, self.coverage_log_odds(upto, clamp_max=coverage_map.clamp_max, vis_wps_dist=vis_wps_dist), mode="max")
 
     @classmethod
     def sharing_cloud_of(cls, other, wps_poses, wps_quats, **kw):
@@ -1273,6 +1283,12 @@ class TeamTraj(nn.Module):
         ps, qs = self._evaluated(self._step(vis_wps_dist))
         lo_sum, _ = ops.traj_forward(m0._cloud, ps, qs, m0._cam, m0._workspace(ps.shape[0]), m0._rig, flags=m0._flags)
         return ops.traj_coverage(m0._cloud, lo_sum, self._prior, clamp_max)
+
+    def commit_coverage(self, coverage_map, vis_wps_dist=0.5):
+        """ModelTraj.commit_coverage for the team: its coverage_log_odds (the map's clamp_max) integrated over the shared cloud with
+        mode 'max'.  -> the map."""
+        return coverage_map.integrate(self.models[0], self.coverage_log_odds(clamp_max=coverage_map.clamp_max, vis_wps_dist=vis_wps_dist),
+                                      mode="max")
 
     @torch.no_grad()
     def member_gains(self, vis_wps_dist=0.5):

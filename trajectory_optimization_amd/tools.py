@@ -209,6 +209,14 @@ def fuse_log_odds(*maps, clamp_max=None):
     return out
 
 
+def coverage_map(origin=(0.0, 0.0, 0.0), resolution=0.1, clamp_max=None, capacity=None, device=torch.device('cuda')):
+    """An empty ops.CoverageMap: the voxel-keyed log-odds map that carries coverage from one cloud to the next.
+    resolution: the voxel edge in metres — by default the leaf of the reference's VoxelGrid filter
+    (/root/reference/launch/voxels_filtering.launch, voxel_grid_filter's default), so a filtered cloud has about one point per voxel.
+    clamp_max: OctoMap's upper clamping threshold (None: none).  model.commit_coverage(map) writes, prior_log_odds=map reads."""
+    return ops.CoverageMap(origin, resolution, clamp_max=clamp_max, capacity=capacity, device=device)
+
+
 class ViewSelection:
     """What select_views returns: order (n_selected,) int64 and gains (n_selected,) f64 on the host (gain j = what view order[j] added
     to the mean reward when it was chosen), poses / quats (the chosen rows in selection order), rewards (N,) and mean_reward of the
@@ -238,7 +246,7 @@ def _views_setup(model_or_cloud, prior_log_odds, occlusion, kw):
             raise ValueError(f"select_views: {sorted(kw)} belong to the call with points; a ModelTraj brings its own camera and rig")
         if occlusion is not None and occlusion != m._occlusion:
             raise ValueError(f"select_views: occlusion={occlusion!r} given, the model has {m._occlusion!r}")
-        prior = m._prior if prior_log_odds is None else prior_log_odds
+        prior = m._prior if prior_log_odds is None else ops.resolve_prior(prior_log_odds, m._cloud)
         return dict(cloud=m._cloud, cam=m._cam, rig=m._rig, flags=m._flags, prior=prior, occlusion=m._occlusion,
                     limits=m._occlusion_limits)
     if occlusion not in (None, "hpr", "zbuffer"):
@@ -259,6 +267,7 @@ def _views_setup(model_or_cloud, prior_log_odds, occlusion, kw):
                              f"{tuple(m.shape) if torch.is_tensor(m) else type(m).__name__}")
         n = m.shape[0]
     if prior_log_odds is not None:
+        prior_log_odds = ops.resolve_prior(prior_log_odds, m)   # (a CoverageMap: its lookup over these points)
         ops.check_prior(prior_log_odds, n)
     cam = ops.Camera(kw["intrins"], kw["img_width"], kw["img_height"], kw.get("min_dist", 1.0), kw.get("max_dist", 5.0))
     return dict(cloud=m, cam=cam, rig=kw.get("rig"), flags=ops.DENSE if kw.get("dense") else 0, prior=prior_log_odds, occlusion=occlusion,
@@ -268,7 +277,7 @@ def _views_setup(model_or_cloud, prior_log_odds, occlusion, kw):
 def select_views(model_or_cloud, cand_poses, cand_quats, k, prior_log_odds=None, min_gain=0.0, occlusion=None, clamp_max=None, chunk=None,
                  **camera):
     """Greedy view selection: out of the M candidate views cand_poses (M,3) / cand_quats (M,4) wxyz, choose up to k
-    that together cover the most, against what prior_log_odds (N,) already holds.  Round after round the view that adds the most to
+    that together cover the most, against what prior_log_odds (N,) — or an ops.CoverageMap, looked up over the cloud — already holds.  Round after round the view that adds the most to
     the mean reward sigmoid(S + prior) is chosen (S: the log-odds of the views chosen so far; ties go to the lowest index) until k
     are chosen, none is left, the best adds nothing or adds less than min_gain to the mean reward.  The objective is monotone
     submodular: the greedy choice is within (1 - 1/e) of the best set of that size.
