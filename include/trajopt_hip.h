@@ -762,7 +762,8 @@ int tohip_zbuffer_visible_batched(const float *verts, int64_t n_stride, const in
  * Row 0 of `terms` is tohip_team_loss's member_terms64 (call it on the starting positions before the first step).
  *
  * tohip_team_step_tail: step `step_index` (0-based, in order) of a run of n_steps, ONE launch, block b = member b: what
- * tohip_traj_step_tail_multi / _clearance do per trajectory — the same device functions, the same bits for one member — with two
+ * tohip_traj_step_tail_multi / _clearance do per trajectory — both kernels run ONE block of device code (opt_step.hpp:
+ * tail_gradients, tail_adam), so a member's gradients, moments and parameters are a trajectory's bits for any B — with two
  * differences: `scalars` is ONE row, the team's, and the early stop is the team's: visibility gain = mean reward / the team's
  * first; smooth gain per member; the team stops at the first step where the visibility gain > rewards_th and EVERY member's smooth
  * gain > smoothness_th, all members together.  Loss rows (member b's at loss_log + b * loss_log_stride, n_steps rows of 8):

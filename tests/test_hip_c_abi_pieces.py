@@ -433,6 +433,65 @@ def test_step_tail_equals_its_pieces(dev, step):
     assert A["state"][3].item() == 9 and not torch.equal(A["poses"], poses0)
 
 
+# (W, step, n_eval): the smallest legal W, no interior angle to spare | the last row is evaluated | W no multiple of the step, the
+# trailing rows 7..9 carry the regularisers only | one element more than a block's stride: every strided loop takes a second trip
+TAIL_SHAPES = [(3, 1, 3), (9, 2, 5), (10, 3, 3), (257, 1, 257)]
+
+
+@pytest.mark.parametrize("clearance", [False, True])
+@pytest.mark.parametrize("W,step,n_eval", TAIL_SHAPES)
+def test_team_tail_members_are_trajectory_tails(dev, W, step, n_eval, clearance):
+    """The block the two tails share: tohip_team_step_tail with B = 3 against tohip_traj_step_tail_multi (_clearance) with n_traj = 3
+    on copies of the same random inputs, the same scalars row for every member, thresholds out of reach, two consecutive steps:
+    poses, quats, full gradients, all four moments and the loss log's columns 0..3 (5 with clearance) are equal to the bit.
+    Column 4 is left out: the team's total is the team's by design."""
+    L = _L()
+    B, n_steps = 3, 2
+    sw, lw, eps, lr_p, lr_q, th, clr_w = 28.0, 0.05, 1e-6, 0.12, 0.05, 1e9, 0.7
+    rng = np.random.default_rng(1000 * W + step)
+    poses0 = _rand_f32(rng, (B * W, 3), dev)
+    clr_rows = _rand_f32(rng, (B * W, 3), dev) * 0.01 if clearance else None
+    clr_terms = torch.from_numpy(rng.random(B * W)).to(dev) if clearance else None   # f64, (r - d)^2 >= 0
+    start = dict(poses=poses0 + 0.05 * _rand_f32(rng, (B * W, 3), dev), quats=_rand_f32(rng, (B * W, 4), dev))
+
+    def fresh():
+        d = {k: v.clone() for k, v in start.items()}
+        d.update(pg=_sentinel_f32((B * W, 3), dev), qg=_sentinel_f32((B * W, 4), dev), log=torch.zeros((B, n_steps, 8), device=dev))
+        for k, cols in (("mp", 3), ("vp", 3), ("mq", 4), ("vq", 4)):
+            d[k] = torch.zeros((B * W, cols), device=dev)
+        return d
+
+    def head(d, pge, qge):
+        return (_p(d["poses"]), _p(d["quats"]), _p(poses0), W, B, _p(pge), _p(qge), n_eval, step, _p(d["pg"]), _p(d["qg"]), _p(d["mp"]),
+                _p(d["vp"]), _p(d["mq"]), _p(d["vq"]), sw, lw, eps, lr_p, lr_q, B1, B2, AEPS, th, th)
+
+    T, M = fresh(), fresh()
+    sb = L.tohip_team_state_bytes(B, n_steps)
+    team_state = torch.zeros(sb, dtype=torch.uint8, device=dev)
+    terms64 = team_state[sb // 2:].view(torch.float64).view(n_steps + 1, B, 4)
+    _ok(L.tohip_team_loss(_p(T["poses"]), _p(poses0), W, B, sw, lw, eps, None, 0.0, None, _p(torch.empty((B, 8), device=dev)), _p(terms64),
+                          None, None, None, _s()), "team_loss")
+    state = torch.zeros((B, 8), device=dev)
+    for i in range(n_steps):
+        pge, qge = _rand_f32(rng, (B * n_eval, 3), dev) * 0.01, _rand_f32(rng, (B * n_eval, 4), dev) * 0.01
+        row = torch.tensor([0.5 + 0.01 * i, 1.7 - 0.01 * i, -0.1, 0.0], device=dev)
+        rows = row.repeat(B, 1).contiguous()
+        _ok(L.tohip_team_step_tail(*head(T, pge, qge), _p(row), _p(T["log"]), n_steps * 8, _p(team_state), sb, n_steps, i, clr_w,
+                                   _p(clr_rows), _p(clr_terms), _s()), "team_step_tail")
+        if clearance:
+            _ok(L.tohip_traj_step_tail_clearance(*head(M, pge, qge), _p(rows), _p(M["log"]), n_steps * 8, _p(state), clr_w, _p(clr_rows),
+                                                 _p(clr_terms), _s()), "traj_step_tail_clearance")
+        else:
+            _ok(L.tohip_traj_step_tail_multi(*head(M, pge, qge), _p(rows), _p(M["log"]), n_steps * 8, _p(state), _s()), "traj_step_tail_multi")
+        torch.cuda.synchronize()
+        for k in ("poses", "quats", "pg", "qg", "mp", "vp", "mq", "vq"):
+            assert torch.equal(T[k], M[k]), (k, "step", i + 1)
+        cols = [0, 1, 2, 3, 5] if clearance else [0, 1, 2, 3]
+        assert torch.equal(T["log"][:, :, cols], M["log"][:, :, cols]), ("loss log", "step", i + 1)
+    assert (state[:, 3] == n_steps).all() and (state[:, 2] == 0).all()   # both steps were taken, by every trajectory
+    assert not torch.equal(T["poses"], start["poses"]) and bool((T["log"][:, n_steps - 1, 3] != 0).all())
+
+
 @pytest.mark.parametrize("masked", [False, True])
 def test_pose_opt_step_equals_its_pieces(dev, masked):
     """INTEGRATION.md's piecewise pose step: tohip_pose_forward_backward + tohip_adam_step (trans, lr_pose) + tohip_adam_step (quat,

@@ -15,6 +15,8 @@
 //              first waypoint also writes the loss log and the next row of the early-stop state
 // The state of step i is ROW i of a log (n_steps + 1 rows of 8 floats per trajectory, row 0 zero): every block reads row i,
 // one block writes row i + 1 — no block waits for another inside the launch.
+// The separate-calls path (a collective, a hull pass or a prior inside the step; a team) has a launch of its own for the remainder:
+// its block — TailArgs, tail_gradients, tail_adam — is here too, one copy for a trajectory and for a team member.
 //   state row: [0] reward0 (mean reward of the first step)   [1] smooth0 (smooth loss of the first step)
 //              [2] stopped (0/1)   [3] steps taken   [4] last visibility gain   [5] last smooth gain
 #pragma once
@@ -195,6 +197,90 @@ __device__ __forceinline__ void early_stop_next(const float* __restrict__ in, fl
         if (vg > rewards_th && sg > smoothness_th) s[2] = 1.f;
     }
     for (int i = 0; i < TO_OPT_STATE; ++i) out[i] = s[i];
+}
+
+// ---- the step tail of the separate-calls path: ONE launch, block b = trajectory (or team member) b ----------------------------
+// What k_traj_step_tail (optim_kernels.hip) and k_team_step_tail (team_kernels.hip) share: the arguments, their check, and the
+// two device functions below — a member's bits are a trajectory's because both kernels run this code, not a copy of it.
+struct TailArgs {
+    // per block b: poses / poses0 / moments / full gradients at row b * W, the evaluated rows at row b * n_eval
+    float *poses, *quats;
+    const float* poses0;
+    const float *pg_eval, *qg_eval;  // (n_eval, 3), (n_eval, 4): rows r -> waypoint r * step
+    float *pg, *qg;                  // (W, 3), (W, 4): full gradients (outputs)
+    float *mp, *vp, *mq, *vq;        // Adam moments
+    const float* scalars;            // (mean reward, loss_vis, ...): a row per trajectory, or the team's one
+    float* loss_log;                 // block b's (n_steps, 8) log at + b * log_stride, row = steps taken
+    int64_t log_stride;
+    int W, n_eval, step;
+    float smooth_w, length_w, eps, lr_pose, lr_quat, beta1, beta2, adam_eps, rewards_th, smoothness_th;
+    const float* clr;                // NULL, or the clearance term's gradient rows (n_blocks W, 3) ...
+    const double* clr_term;          //   ... its per-waypoint terms (n_blocks W) ...
+    float clr_w;                     //   ... and its weight
+};
+
+inline void tail_args_fill(TailArgs& a, float* poses, float* quats, const float* poses0, int64_t W, const float* poses_grad_eval,
+                           const float* quats_grad_eval, int64_t n_eval, int step, float* poses_grad, float* quats_grad, float* exp_avg_p,
+                           float* exp_avg_sq_p, float* exp_avg_q, float* exp_avg_sq_q, float smoothness_weight, float traj_length_weight,
+                           float eps, float lr_pose, float lr_quat, float beta1, float beta2, float adam_eps, float rewards_th,
+                           float smoothness_th, const float* scalars, float* loss_log, int64_t loss_log_stride, float clearance_weight,
+                           const float* clearance_grad, const double* clearance_terms) {
+    a.poses = poses; a.quats = quats; a.poses0 = poses0; a.pg_eval = poses_grad_eval; a.qg_eval = quats_grad_eval;
+    a.pg = poses_grad; a.qg = quats_grad; a.mp = exp_avg_p; a.vp = exp_avg_sq_p; a.mq = exp_avg_q; a.vq = exp_avg_sq_q;
+    a.scalars = scalars; a.loss_log = loss_log; a.log_stride = loss_log_stride; a.W = (int)W; a.n_eval = (int)n_eval; a.step = step;
+    a.smooth_w = smoothness_weight; a.length_w = traj_length_weight; a.eps = eps; a.lr_pose = lr_pose; a.lr_quat = lr_quat;
+    a.beta1 = beta1; a.beta2 = beta2; a.adam_eps = adam_eps; a.rewards_th = rewards_th; a.smoothness_th = smoothness_th;
+    a.clr = clearance_grad; a.clr_term = clearance_terms; a.clr_w = clearance_grad ? clearance_weight : 0.f;
+}
+
+// what every tail entry point refuses (sizes as the caller gave them); the clearance rows and terms come together or not at all
+inline bool tail_args_ok(const TailArgs& a, int64_t W, int64_t n_eval, int64_t n_blocks) {
+    return a.poses && a.quats && a.poses0 && a.pg_eval && a.qg_eval && a.pg && a.qg && a.mp && a.vp && a.mq && a.vq && a.scalars &&
+           a.loss_log && W >= 3 && n_eval > 0 && a.step > 0 && (n_eval - 1) * a.step < W && n_blocks > 0 &&
+           (a.clr != nullptr) == (a.clr_term != nullptr) && (!a.clr || (std::isfinite(a.clr_w) && a.clr_w >= 0.f));
+}
+
+// element i of the evaluated rows (n_eval, cols) scattered to rows r * step of a (W, cols) array, zero in between
+__device__ __forceinline__ float tail_scattered(const float* __restrict__ rows, int i, int cols, int step, int n_eval) {
+    const int j = i / cols, k = i - cols * j, r = j / step;
+    return (j == r * step && r < n_eval) ? rows[cols * r + k] : 0.f;
+}
+
+// the arguments with every row pointer moved to block b's own rows (scalars, loss_log and clr_term stay: theirs is the kernel's to place)
+__device__ __forceinline__ TailArgs tail_block(TailArgs a, int64_t b) {
+    a.poses += b * a.W * 3; a.quats += b * a.W * 4; a.poses0 += b * a.W * 3;
+    a.pg_eval += b * a.n_eval * 3; a.qg_eval += b * a.n_eval * 4;
+    a.pg += b * a.W * 3; a.qg += b * a.W * 4;
+    a.mp += b * a.W * 3; a.vp += b * a.W * 3; a.mq += b * a.W * 4; a.vq += b * a.W * 4;
+    if (a.clr) a.clr += b * a.W * 3;
+    return a;
+}
+
+// A block's full gradients (r = tail_block's): the visibility rows scattered into pg / qg, the regularisers on top — vis + reg, or
+// with the clearance term the regularisers' rows first and then vis + (reg + clearance), the order of the one-call step.  Every
+// gradient is complete (and the block synchronised) on return, before any parameter moves: the regularisers read their
+// neighbours' positions.
+__device__ __forceinline__ RegOut tail_gradients(const TailArgs& r, double* lds, double* sh) {
+    const int t = threadIdx.x;
+    if (!r.clr)
+        for (int i = t; i < r.W * 3; i += TO_BLOCK) r.pg[i] = tail_scattered(r.pg_eval, i, 3, r.step, r.n_eval);
+    for (int i = t; i < r.W * 4; i += TO_BLOCK) r.qg[i] = tail_scattered(r.qg_eval, i, 4, r.step, r.n_eval);
+    __syncthreads();
+    const RegOut o = regularizers_eval(r.poses, r.poses0, r.W, r.smooth_w, r.length_w, r.eps, r.pg, r.clr ? 0 : 1, nullptr, lds, sh);
+    __syncthreads();
+    if (r.clr) {
+        for (int i = t; i < r.W * 3; i += TO_BLOCK) r.pg[i] = tail_scattered(r.pg_eval, i, 3, r.step, r.n_eval) + (r.pg[i] + r.clr[i]);
+        __syncthreads();
+    }
+    return o;
+}
+
+// both Adam updates of a block's rows; step_idx: 1-based
+__device__ __forceinline__ void tail_adam(const TailArgs& r, int step_idx) {
+    for (int i = threadIdx.x; i < r.W * 3; i += TO_BLOCK)
+        adam_element(r.poses, r.pg[i], r.mp, r.vp, i, r.lr_pose, r.beta1, r.beta2, r.adam_eps, step_idx);
+    for (int i = threadIdx.x; i < r.W * 4; i += TO_BLOCK)
+        adam_element(r.quats, r.qg[i], r.mq, r.vq, i, r.lr_quat, r.beta1, r.beta2, r.adam_eps, step_idx);
 }
 
 // ---- one optimisation step's constants, shared by the prologue and the epilogue ----------------------------------------------

@@ -6,24 +6,15 @@
 //   Adam (two parameter groups)       /root/reference/src/trajectory_optimization.py:91-94 (torch.optim.Adam defaults)
 //   early stop                        /root/reference/src/trajectory_optimization.py:100-124
 //
-// Everything here is a single small block: W is tens to a few thousand waypoints.
+// Everything here is a single small block: W is tens to a few thousand waypoints.  The step tail's own block — scatter,
+// regularisers, clearance merge, Adam — is opt_step.hpp's (tail_gradients, tail_adam), shared with team_kernels.hip's tail; its
+// argument check and struct fill (tail_args_ok, tail_args_fill) stand behind every tail entry point of both files.
 #include "common.hpp"
 #include "opt_step.hpp"
 
 // loss_terms[0..4] = vis, l2, length, smooth, total.  grad_poses (W,3) receives the regularisers' gradient (ADDED to what the
 // visibility backward wrote when accumulate != 0).  state (may be NULL): the loss row written is state[3] (steps taken so far).
-__device__ __forceinline__ void
-regularizers_block(const float* __restrict__ poses, const float* __restrict__ poses0, int W, float smooth_w,
-                   float length_w, float eps, const float* __restrict__ scalars /* [1] = loss_vis */,
-                   float* __restrict__ loss_terms, float* __restrict__ grad_poses, int accumulate,
-                   const float* __restrict__ state, float* __restrict__ grad_terms, double* lds, double* sh,
-                   bool has_clr = false, double clr = 0.0) {
-    if (state) loss_terms += 8 * (int)state[3];
-    RegOut o = regularizers_eval(poses, poses0, W, smooth_w, length_w, eps, grad_poses, accumulate, grad_terms, lds, sh);
-    o.has_clr = has_clr; o.clr = clr;
-    if (threadIdx.x == 0) write_loss_terms(loss_terms, (double)scalars[1], o);
-}
-
+// clr_terms (may be NULL): the clearance query's per-waypoint terms; the loss row then gets [5] = clearance and the five-term total.
 __global__ void __launch_bounds__(TO_BLOCK)
 k_traj_regularizers(const float* __restrict__ poses, const float* __restrict__ poses0, int W, float smooth_w,
                     float length_w, float eps, const float* __restrict__ scalars, float* __restrict__ loss_terms,
@@ -31,10 +22,10 @@ k_traj_regularizers(const float* __restrict__ poses, const float* __restrict__ p
                     float* __restrict__ grad_terms, const double* __restrict__ clr_terms, float clr_w) {
     __shared__ double lds[TO_BLOCK / 64];
     __shared__ double sh[4];
-    // clr_terms (may be NULL): the clearance query's per-waypoint terms; the loss row then gets [5] = clearance and the five-term total
-    const double clr = clr_terms && threadIdx.x == 0 ? clearance_sum(clr_terms, W, clr_w) : 0.0;
-    regularizers_block(poses, poses0, W, smooth_w, length_w, eps, scalars, loss_terms, grad_poses, accumulate, state,
-                       grad_terms, lds, sh, clr_terms != nullptr, clr);
+    RegOut o = regularizers_eval(poses, poses0, W, smooth_w, length_w, eps, grad_poses, accumulate, grad_terms, lds, sh);
+    if (threadIdx.x != 0) return;
+    if (clr_terms) { o.has_clr = true; o.clr = clearance_sum(clr_terms, W, clr_w); }
+    write_loss_terms(state ? loss_terms + 8 * (int)state[3] : loss_terms, (double)scalars[1], o);
 }
 
 // scatter the gradient rows of the evaluated waypoints (every wps_step-th) into full (W,3)/(W,4) arrays
@@ -74,77 +65,30 @@ __global__ void k_early_stop(const float* __restrict__ scalars /* [0] = mean rew
     if (threadIdx.x == 0 && blockIdx.x == 0) early_stop_rule(scalars, loss_terms, rewards_th, smoothness_th, state, row_from_state);
 }
 
-// One block does the whole O(W) remainder of an optimisation step (optimizer.optimize_trajectory): scatter of the
-// evaluated waypoints' visibility gradients into full (W,3)/(W,4) arrays, criterion regularisers + their gradient on top,
-// the two Adam updates, the early-stop rule — five launches and two memsets otherwise.  Every gradient is complete
-// before any parameter moves (the regularisers read their neighbours' positions).
-struct StepTail {
-    float *poses, *quats;
-    const float* poses0;
-    const float *pg_eval, *qg_eval;  // (n_eval, 3), (n_eval, 4): rows r -> waypoint r * step
-    float *pg, *qg;                  // (W, 3), (W, 4): full gradients (outputs)
-    float *mp, *vp, *mq, *vq;        // Adam moments
-    const float* scalars;
-    float* loss_terms;               // (n_steps, 8) log, row = state[3]
-    float* state;
-    int W, n_eval, step;
-    float smooth_w, length_w, eps, lr_pose, lr_quat, beta1, beta2, adam_eps, rewards_th, smoothness_th;
-    int64_t log_stride;              // floats between two trajectories' loss logs (several trajectories: one block each)
-    const float* clr;                // NULL, or the clearance term's gradient rows (n_traj W, 3) ...
-    const double* clr_term;          //   ... its per-waypoint terms (n_traj W) ...
-    float clr_w;                     //   ... and its weight
+// One block does the whole O(W) remainder of an optimisation step (optimizer.optimize_trajectory's separate-calls path): scatter of
+// the evaluated waypoints' visibility gradients into full (W,3)/(W,4) arrays, criterion regularisers + their gradient on top, the
+// two Adam updates (opt_step.hpp: tail_gradients, tail_adam — the block a team member runs too), then what is the trajectory's
+// alone: its loss row, and the early-stop rule on its state in place — five launches and two memsets otherwise.
+// Block b = trajectory b: equal-length trajectories laid end to end, each with its own state, scalars and log.
+struct StepTail : TailArgs {
+    float* state;   // (n_traj, 8), updated in place
 };
 
 __global__ void __launch_bounds__(TO_BLOCK) k_traj_step_tail(StepTail a) {
-    __shared__ double lds[TO_BLOCK];
+    __shared__ double lds[TO_BLOCK / 64];
     __shared__ double sh[4];
-    const int t = threadIdx.x;
-    {   // block b = trajectory b: equal-length trajectories laid end to end, each with its own state, scalars and log
-        const int64_t b = blockIdx.x;
-        a.poses += b * a.W * 3; a.quats += b * a.W * 4; a.poses0 += b * a.W * 3;
-        a.pg_eval += b * a.n_eval * 3; a.qg_eval += b * a.n_eval * 4;
-        a.pg += b * a.W * 3; a.qg += b * a.W * 4;
-        a.mp += b * a.W * 3; a.vp += b * a.W * 3; a.mq += b * a.W * 4; a.vq += b * a.W * 4;
-        a.scalars += b * 4; a.state += b * 8; a.loss_terms += b * a.log_stride;
-    }
-    if (!a.clr) {
-        for (int i = t; i < a.W * 3; i += TO_BLOCK) {
-            const int j = i / 3, k = i - 3 * j, r = j / a.step;
-            a.pg[i] = (j == r * a.step && r < a.n_eval) ? a.pg_eval[3 * r + k] : 0.f;
-        }
-    }
-    for (int i = t; i < a.W * 4; i += TO_BLOCK) {
-        const int j = i >> 2, k = i & 3, r = j / a.step;
-        a.qg[i] = (j == r * a.step && r < a.n_eval) ? a.qg_eval[4 * r + k] : 0.f;
-    }
+    const int64_t b = blockIdx.x;
+    const float* scalars = a.scalars + b * 4;
+    float* state = a.state + b * 8;
+    float* loss_log = a.loss_log + b * a.log_stride;
+    const TailArgs r = tail_block(a, b);
+    RegOut o = tail_gradients(r, lds, sh);
+    if (state[2] == 0.f) tail_adam(r, (int)state[3] + 1);   // not stopped yet (uniform)
     __syncthreads();
-    if (!a.clr) {
-        regularizers_block(a.poses, a.poses0, a.W, a.smooth_w, a.length_w, a.eps, a.scalars, a.loss_terms, a.pg, 1, a.state,
-                           nullptr, lds, sh);
-    } else {
-        // the clearance term: the regularisers' rows first (pg = reg), then vis + (reg + clearance) — the order of the one-call step
-        const int64_t b = blockIdx.x;
-        const double clr = t == 0 ? clearance_sum(a.clr_term + b * a.W, a.W, a.clr_w) : 0.0;
-        regularizers_block(a.poses, a.poses0, a.W, a.smooth_w, a.length_w, a.eps, a.scalars, a.loss_terms, a.pg, 0, a.state,
-                           nullptr, lds, sh, true, clr);
-        __syncthreads();
-        const float* cg = a.clr + b * a.W * 3;
-        for (int i = t; i < a.W * 3; i += TO_BLOCK) {
-            const int j = i / 3, k = i - 3 * j, r = j / a.step;
-            const float vis = (j == r * a.step && r < a.n_eval) ? a.pg_eval[3 * r + k] : 0.f;
-            a.pg[i] = vis + (a.pg[i] + cg[i]);
-        }
-    }
-    __syncthreads();
-    if (a.state[2] == 0.f) {  // not stopped yet (uniform)
-        const int step_idx = (int)a.state[3] + 1;
-        for (int i = t; i < a.W * 3; i += TO_BLOCK)
-            adam_element(a.poses, a.pg[i], a.mp, a.vp, i, a.lr_pose, a.beta1, a.beta2, a.adam_eps, step_idx);
-        for (int i = t; i < a.W * 4; i += TO_BLOCK)
-            adam_element(a.quats, a.qg[i], a.mq, a.vq, i, a.lr_quat, a.beta1, a.beta2, a.adam_eps, step_idx);
-    }
-    __syncthreads();
-    if (t == 0) early_stop_rule(a.scalars, a.loss_terms, a.rewards_th, a.smoothness_th, a.state, 1);
+    if (threadIdx.x != 0) return;
+    if (a.clr) { o.has_clr = true; o.clr = clearance_sum(a.clr_term + b * a.W, a.W, a.clr_w); }
+    write_loss_terms(loss_log + 8 * (int)state[3], (double)scalars[1], o);
+    early_stop_rule(scalars, loss_log, a.rewards_th, a.smoothness_th, state, 1);
 }
 
 // poses_e[r] = poses[r * step], quats_e[r] = quats[r * step] in one launch (model.py:217's waypoint selection)
@@ -183,6 +127,26 @@ extern "C" int tohip_gather_waypoints(const float* poses, const float* quats, in
     return TOHIP_OK;
 }
 
+// the one check, struct fill and launch behind tohip_traj_step_tail, _multi and _clearance (clearance_grad NULL: no clearance term)
+static int traj_step_tail_launch(float* poses, float* quats, const float* poses0, int64_t W, int64_t n_traj,
+                                 const float* poses_grad_eval, const float* quats_grad_eval, int64_t n_eval, int step,
+                                 float* poses_grad, float* quats_grad, float* exp_avg_p, float* exp_avg_sq_p, float* exp_avg_q,
+                                 float* exp_avg_sq_q, float smoothness_weight, float traj_length_weight, float eps,
+                                 float lr_pose, float lr_quat, float beta1, float beta2, float adam_eps, float rewards_th,
+                                 float smoothness_th, const float* scalars, float* loss_terms, int64_t loss_terms_stride,
+                                 float* state, float clearance_weight, const float* clearance_grad,
+                                 const double* clearance_terms, void* stream_) {
+    StepTail a;
+    tail_args_fill(a, poses, quats, poses0, W, poses_grad_eval, quats_grad_eval, n_eval, step, poses_grad, quats_grad, exp_avg_p, exp_avg_sq_p,
+                   exp_avg_q, exp_avg_sq_q, smoothness_weight, traj_length_weight, eps, lr_pose, lr_quat, beta1, beta2, adam_eps, rewards_th,
+                   smoothness_th, scalars, loss_terms, loss_terms_stride, clearance_weight, clearance_grad, clearance_terms);
+    a.state = state;
+    if (!tail_args_ok(a, W, n_eval, n_traj) || !state) return TOHIP_EINVAL;
+    k_traj_step_tail<<<(int)n_traj, TO_BLOCK, 0, (hipStream_t)stream_>>>(a);
+    TO_HIP_CHECK_LAUNCH();
+    return TOHIP_OK;
+}
+
 extern "C" int tohip_traj_step_tail_multi(float* poses, float* quats, const float* poses0, int64_t W, int64_t n_traj,
                                           const float* poses_grad_eval, const float* quats_grad_eval, int64_t n_eval, int step,
                                           float* poses_grad, float* quats_grad, float* exp_avg_p, float* exp_avg_sq_p, float* exp_avg_q,
@@ -190,21 +154,9 @@ extern "C" int tohip_traj_step_tail_multi(float* poses, float* quats, const floa
                                           float lr_pose, float lr_quat, float beta1, float beta2, float adam_eps, float rewards_th,
                                           float smoothness_th, const float* scalars, float* loss_terms, int64_t loss_terms_stride,
                                           float* state, void* stream_) {
-    if (!poses || !quats || !poses0 || !poses_grad_eval || !quats_grad_eval || !poses_grad || !quats_grad || !exp_avg_p ||
-        !exp_avg_sq_p || !exp_avg_q || !exp_avg_sq_q || !scalars || !loss_terms || !state || W < 3 || n_eval <= 0 || step <= 0 ||
-        (n_eval - 1) * step >= W || n_traj <= 0)
-        return TOHIP_EINVAL;
-    StepTail a;
-    a.poses = poses; a.quats = quats; a.poses0 = poses0; a.pg_eval = poses_grad_eval; a.qg_eval = quats_grad_eval;
-    a.pg = poses_grad; a.qg = quats_grad; a.mp = exp_avg_p; a.vp = exp_avg_sq_p; a.mq = exp_avg_q; a.vq = exp_avg_sq_q;
-    a.scalars = scalars; a.loss_terms = loss_terms; a.state = state; a.W = (int)W; a.n_eval = (int)n_eval; a.step = step;
-    a.smooth_w = smoothness_weight; a.length_w = traj_length_weight; a.eps = eps; a.lr_pose = lr_pose; a.lr_quat = lr_quat;
-    a.beta1 = beta1; a.beta2 = beta2; a.adam_eps = adam_eps; a.rewards_th = rewards_th; a.smoothness_th = smoothness_th;
-    a.log_stride = loss_terms_stride;
-    a.clr = nullptr; a.clr_term = nullptr; a.clr_w = 0.f;
-    k_traj_step_tail<<<(int)n_traj, TO_BLOCK, 0, (hipStream_t)stream_>>>(a);
-    TO_HIP_CHECK_LAUNCH();
-    return TOHIP_OK;
+    return traj_step_tail_launch(poses, quats, poses0, W, n_traj, poses_grad_eval, quats_grad_eval, n_eval, step, poses_grad, quats_grad,
+                                 exp_avg_p, exp_avg_sq_p, exp_avg_q, exp_avg_sq_q, smoothness_weight, traj_length_weight, eps, lr_pose, lr_quat,
+                                 beta1, beta2, adam_eps, rewards_th, smoothness_th, scalars, loss_terms, loss_terms_stride, state, 0.f, nullptr, nullptr, stream_);
 }
 
 extern "C" int tohip_traj_step_tail_clearance(float* poses, float* quats, const float* poses0, int64_t W, int64_t n_traj,
@@ -215,22 +167,11 @@ extern "C" int tohip_traj_step_tail_clearance(float* poses, float* quats, const 
                                               float smoothness_th, const float* scalars, float* loss_terms, int64_t loss_terms_stride,
                                               float* state, float clearance_weight, const float* clearance_grad,
                                               const double* clearance_terms, void* stream_) {
-    if (!poses || !quats || !poses0 || !poses_grad_eval || !quats_grad_eval || !poses_grad || !quats_grad || !exp_avg_p ||
-        !exp_avg_sq_p || !exp_avg_q || !exp_avg_sq_q || !scalars || !loss_terms || !state || W < 3 || n_eval <= 0 || step <= 0 ||
-        (n_eval - 1) * step >= W || n_traj <= 0 || !clearance_grad || !clearance_terms || !std::isfinite(clearance_weight) ||
-        !(clearance_weight >= 0.f))
-        return TOHIP_EINVAL;
-    StepTail a;
-    a.poses = poses; a.quats = quats; a.poses0 = poses0; a.pg_eval = poses_grad_eval; a.qg_eval = quats_grad_eval;
-    a.pg = poses_grad; a.qg = quats_grad; a.mp = exp_avg_p; a.vp = exp_avg_sq_p; a.mq = exp_avg_q; a.vq = exp_avg_sq_q;
-    a.scalars = scalars; a.loss_terms = loss_terms; a.state = state; a.W = (int)W; a.n_eval = (int)n_eval; a.step = step;
-    a.smooth_w = smoothness_weight; a.length_w = traj_length_weight; a.eps = eps; a.lr_pose = lr_pose; a.lr_quat = lr_quat;
-    a.beta1 = beta1; a.beta2 = beta2; a.adam_eps = adam_eps; a.rewards_th = rewards_th; a.smoothness_th = smoothness_th;
-    a.log_stride = loss_terms_stride;
-    a.clr = clearance_grad; a.clr_term = clearance_terms; a.clr_w = clearance_weight;
-    k_traj_step_tail<<<(int)n_traj, TO_BLOCK, 0, (hipStream_t)stream_>>>(a);
-    TO_HIP_CHECK_LAUNCH();
-    return TOHIP_OK;
+    if (!clearance_grad || !clearance_terms) return TOHIP_EINVAL;
+    return traj_step_tail_launch(poses, quats, poses0, W, n_traj, poses_grad_eval, quats_grad_eval, n_eval, step, poses_grad, quats_grad,
+                                 exp_avg_p, exp_avg_sq_p, exp_avg_q, exp_avg_sq_q, smoothness_weight, traj_length_weight, eps, lr_pose, lr_quat,
+                                 beta1, beta2, adam_eps, rewards_th, smoothness_th, scalars, loss_terms, loss_terms_stride, state, clearance_weight, clearance_grad,
+                                 clearance_terms, stream_);
 }
 
 extern "C" int tohip_traj_step_tail(float* poses, float* quats, const float* poses0, int64_t W, const float* poses_grad_eval,
@@ -239,35 +180,39 @@ extern "C" int tohip_traj_step_tail(float* poses, float* quats, const float* pos
                                     float smoothness_weight, float traj_length_weight, float eps, float lr_pose, float lr_quat,
                                     float beta1, float beta2, float adam_eps, float rewards_th, float smoothness_th,
                                     const float* scalars, float* loss_terms, float* state, void* stream_) {
-    return tohip_traj_step_tail_multi(poses, quats, poses0, W, 1, poses_grad_eval, quats_grad_eval, n_eval, step, poses_grad, quats_grad,
-                                      exp_avg_p, exp_avg_sq_p, exp_avg_q, exp_avg_sq_q, smoothness_weight, traj_length_weight, eps, lr_pose,
-                                      lr_quat, beta1, beta2, adam_eps, rewards_th, smoothness_th, scalars, loss_terms, 0, state, stream_);
+    return traj_step_tail_launch(poses, quats, poses0, W, 1, poses_grad_eval, quats_grad_eval, n_eval, step, poses_grad, quats_grad,
+                                 exp_avg_p, exp_avg_sq_p, exp_avg_q, exp_avg_sq_q, smoothness_weight, traj_length_weight, eps, lr_pose, lr_quat,
+                                 beta1, beta2, adam_eps, rewards_th, smoothness_th, scalars, loss_terms, 0, state, 0.f, nullptr, nullptr, stream_);
+}
+
+// the one launch behind tohip_traj_regularizers and _clearance (clearance_terms NULL: no clearance term)
+static int traj_regularizers_launch(const float* poses, const float* poses0, int64_t W, float smoothness_weight, float traj_length_weight,
+                                    float eps, const float* scalars, float* loss_terms, float* grad_poses, int accumulate,
+                                    const float* state, float* grad_terms, float clearance_weight, const double* clearance_terms,
+                                    void* stream_) {
+    if (!poses || !poses0 || !scalars || !loss_terms || W < 3) return TOHIP_EINVAL;
+    k_traj_regularizers<<<1, TO_BLOCK, 0, (hipStream_t)stream_>>>(poses, poses0, (int)W, smoothness_weight, traj_length_weight, eps, scalars,
+                                                                  loss_terms, grad_poses, accumulate, state, grad_terms, clearance_terms,
+                                                                  clearance_weight);
+    TO_HIP_CHECK_LAUNCH();
+    return TOHIP_OK;
 }
 
 extern "C" int tohip_traj_regularizers(const float* poses, const float* poses0, int64_t W, float smoothness_weight,
                                        float traj_length_weight, float eps, const float* scalars, float* loss_terms,
                                        float* grad_poses, int accumulate, const float* state, float* grad_terms,
                                        void* stream_) {
-    if (!poses || !poses0 || !scalars || !loss_terms || W < 3) return TOHIP_EINVAL;
-    k_traj_regularizers<<<1, TO_BLOCK, 0, (hipStream_t)stream_>>>(poses, poses0, (int)W, smoothness_weight,
-                                                                  traj_length_weight, eps, scalars, loss_terms, grad_poses,
-                                                                  accumulate, state, grad_terms, nullptr, 0.f);
-    TO_HIP_CHECK_LAUNCH();
-    return TOHIP_OK;
+    return traj_regularizers_launch(poses, poses0, W, smoothness_weight, traj_length_weight, eps, scalars, loss_terms, grad_poses, accumulate,
+                                    state, grad_terms, 0.f, nullptr, stream_);
 }
 
 extern "C" int tohip_traj_regularizers_clearance(const float* poses, const float* poses0, int64_t W, float smoothness_weight,
                                                  float traj_length_weight, float eps, const float* scalars, float* loss_terms,
                                                  float* grad_poses, int accumulate, const float* state, float* grad_terms,
                                                  float clearance_weight, const double* clearance_terms, void* stream_) {
-    if (!poses || !poses0 || !scalars || !loss_terms || W < 3 || !clearance_terms || !std::isfinite(clearance_weight) ||
-        !(clearance_weight >= 0.f))
-        return TOHIP_EINVAL;
-    k_traj_regularizers<<<1, TO_BLOCK, 0, (hipStream_t)stream_>>>(poses, poses0, (int)W, smoothness_weight,
-                                                                  traj_length_weight, eps, scalars, loss_terms, grad_poses,
-                                                                  accumulate, state, grad_terms, clearance_terms, clearance_weight);
-    TO_HIP_CHECK_LAUNCH();
-    return TOHIP_OK;
+    if (!clearance_terms || !std::isfinite(clearance_weight) || !(clearance_weight >= 0.f)) return TOHIP_EINVAL;
+    return traj_regularizers_launch(poses, poses0, W, smoothness_weight, traj_length_weight, eps, scalars, loss_terms, grad_poses, accumulate,
+                                    state, grad_terms, clearance_weight, clearance_terms, stream_);
 }
 
 extern "C" int tohip_rows_strided(const float* src, int64_t n_rows, int cols, int step, int scatter, float* dst,

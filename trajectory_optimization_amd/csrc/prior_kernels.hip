@@ -53,7 +53,7 @@ k_prior_build(const float* __restrict__ prior_in, const int* __restrict__ perm, 
                 p[j] = prior_in[o[j]];
                 if (!(p[j] >= 0.f)) bad |= TO_PRIOR_NEG;   // (a NaN as well)
                 if (!(p[j] < INFINITY)) bad |= TO_PRIOR_NONFINITE;
-                g[j] = to_rcp(1.0f + to_exp(-(0.0f + p[j])));   // == reward_block<true>'s r at lo_sum = 0
+                g[j] = reward_sigmoid(0.0f + p[j]);   // reward_block<true>'s r at lo_sum = 0
                 s += reward_fixed(g[j], shift);
             }
         }

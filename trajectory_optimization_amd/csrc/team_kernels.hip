@@ -3,8 +3,9 @@
 // The team's visibility term is the existing forward / reward / backward over the members' evaluated waypoints laid end to end as one
 // trajectory (n_traj = 1).  What is per member behind that one reward lives here:
 //
-//   k_team_step_tail     block b = member b: what k_traj_step_tail does for a trajectory (scatter of the visibility rows, regularisers
-//                        and clearance rows, Adam) read against ONE scalars row, and the TEAM's early-stop rule
+//   k_team_step_tail     block b = member b: the block k_traj_step_tail runs for a trajectory (opt_step.hpp's tail_gradients and tail_adam:
+//                        scatter of the visibility rows, regularisers and clearance rows, Adam) against ONE scalars row; its own are the
+//                        team total, the TEAM's early-stop rule and the terms of the positions it leaves
 //   k_team_loss          block b = member b: criterion's terms and the regularisers' gradient rows of every member, and the team total
 //   k_team_member_gains  one pass over the members' log-odds rows: what each member adds to the team's mean reward
 //
@@ -23,24 +24,12 @@
 
 namespace {
 
-struct TeamTail {
-    float *poses, *quats;
-    const float* poses0;
-    const float *pg_eval, *qg_eval;  // (B n_eval, 3 / 4): the team's visibility rows, member b's at b * n_eval
-    float *pg, *qg;                  // (B W, 3 / 4): full gradients (outputs)
-    float *mp, *vp, *mq, *vq;        // Adam moments
-    const float* scalars;            // the TEAM's (mean reward, loss_vis, ...): one row
-    float* loss_log;                 // member b's (n_steps, 8) log at + b * log_stride, row = steps taken
+struct TeamTail : TailArgs {     // (scalars: the TEAM's one row; pg_eval / qg_eval: the team's visibility rows, member b's at b * n_eval)
     const float* state_in;           // (B, 8): this step's rows
     float* state_out;                //   ... and the next step's
     const double* terms_in;          // (B, 4): every member's l2, length, smooth at its current positions
     double* terms_out;               //   ... and at the positions this step leaves
-    int W, n_eval, step, B;
-    float smooth_w, length_w, eps, lr_pose, lr_quat, beta1, beta2, adam_eps, rewards_th, smoothness_th;
-    int64_t log_stride;
-    const float* clr;                // NULL, or the clearance term's gradient rows (B W, 3) ...
-    const double* clr_term;          //   ... its per-waypoint terms (B W) ...
-    float clr_w;                     //   ... and its weight
+    int B;
 };
 
 __global__ void __launch_bounds__(TO_BLOCK) k_team_step_tail(TeamTail a) {
@@ -49,39 +38,11 @@ __global__ void __launch_bounds__(TO_BLOCK) k_team_step_tail(TeamTail a) {
     __shared__ double clrs[TO_BLOCK];   // every member's clearance term (B <= TO_BLOCK)
     const int t = threadIdx.x;
     const int64_t b = blockIdx.x;
-    float* poses = a.poses + b * a.W * 3;
-    float* quats = a.quats + b * a.W * 4;
-    const float* poses0 = a.poses0 + b * a.W * 3;
-    const float* pg_eval = a.pg_eval + b * a.n_eval * 3;
-    const float* qg_eval = a.qg_eval + b * a.n_eval * 4;
-    float* pg = a.pg + b * a.W * 3;
-    float* qg = a.qg + b * a.W * 4;
     const float* in = a.state_in + b * TO_OPT_STATE;
-    if (!a.clr) {
-        for (int i = t; i < a.W * 3; i += TO_BLOCK) {
-            const int j = i / 3, k = i - 3 * j, r = j / a.step;
-            pg[i] = (j == r * a.step && r < a.n_eval) ? pg_eval[3 * r + k] : 0.f;
-        }
-    } else if (t < a.B) {
-        clrs[t] = clearance_sum(a.clr_term + (int64_t)t * a.W, a.W, a.clr_w);   // thread m: member m's, each the one-thread sum
-    }
-    for (int i = t; i < a.W * 4; i += TO_BLOCK) {
-        const int j = i >> 2, k = i & 3, r = j / a.step;
-        qg[i] = (j == r * a.step && r < a.n_eval) ? qg_eval[4 * r + k] : 0.f;
-    }
-    __syncthreads();
-    // the member's own terms and rows: vis + regularisers, or with the clearance term vis + (regularisers + clearance)
-    const RegOut o = regularizers_eval(poses, poses0, a.W, a.smooth_w, a.length_w, a.eps, pg, a.clr ? 0 : 1, nullptr, lds, sh);
-    __syncthreads();
-    if (a.clr) {
-        const float* cg = a.clr + b * a.W * 3;
-        for (int i = t; i < a.W * 3; i += TO_BLOCK) {
-            const int j = i / 3, k = i - 3 * j, r = j / a.step;
-            const float vis = (j == r * a.step && r < a.n_eval) ? pg_eval[3 * r + k] : 0.f;
-            pg[i] = vis + (pg[i] + cg[i]);
-        }
-        __syncthreads();
-    }
+    if (a.clr && t < a.B) clrs[t] = clearance_sum(a.clr_term + (int64_t)t * a.W, a.W, a.clr_w);   // thread m: member m's, each the one-thread sum
+    // the member's own terms and rows: the trajectory tail's block (its first barrier also publishes clrs)
+    const TailArgs r = tail_block(a, b);
+    const RegOut o = tail_gradients(r, lds, sh);
     const bool stopped = in[2] != 0.f;   // before this step (uniform, and the same in every block)
     if (t == 0) {
         // the team total: vis, then every member's l2, length, smooth [, clearance], members ascending — one running f64 sum, rounded
@@ -112,18 +73,10 @@ __global__ void __launch_bounds__(TO_BLOCK) k_team_step_tail(TeamTail a) {
         early_stop_next(in, a.state_out + b * TO_OPT_STATE, a.scalars[0], (float)a.terms_in[b * 4 + 2], a.rewards_th,
                         others ? a.smoothness_th : INFINITY);
     }
-    if (!stopped) {
-        const int step_idx = (int)in[3] + 1;
-        float* mp = a.mp + b * a.W * 3; float* vp = a.vp + b * a.W * 3;
-        float* mq = a.mq + b * a.W * 4; float* vq = a.vq + b * a.W * 4;
-        for (int i = t; i < a.W * 3; i += TO_BLOCK)
-            adam_element(poses, pg[i], mp, vp, i, a.lr_pose, a.beta1, a.beta2, a.adam_eps, step_idx);
-        for (int i = t; i < a.W * 4; i += TO_BLOCK)
-            adam_element(quats, qg[i], mq, vq, i, a.lr_quat, a.beta1, a.beta2, a.adam_eps, step_idx);
-    }
+    if (!stopped) tail_adam(r, (int)in[3] + 1);
     __syncthreads();
     // the terms of the positions this step leaves: what the next step's blocks read of this member
-    const RegOut nx = regularizers_eval(poses, poses0, a.W, a.smooth_w, a.length_w, a.eps, nullptr, 0, nullptr, lds, sh);
+    const RegOut nx = regularizers_eval(r.poses, r.poses0, a.W, a.smooth_w, a.length_w, a.eps, nullptr, 0, nullptr, lds, sh);
     if (t == 0) {
         double* p = a.terms_out + b * 4;
         p[0] = nx.l2; p[1] = nx.length; p[2] = nx.smooth; p[3] = 0.0;
@@ -210,8 +163,7 @@ k_team_member_gains(const float* __restrict__ lo, int64_t n, int64_t npad, int B
         for (int j = 0; j < 4; ++j) {
             if (i0 + j >= n) continue;
             const float lt = prior ? S[j] + p[j] : S[j];
-            const float r = to_rcp(1.0f + to_exp(-lt));   // the reward kernel's expression (reward_block)
-            const long long fr = reward_fixed(r, shift);
+            const long long fr = reward_fixed(reward_sigmoid(lt), shift);
             team += fr;
 #pragma unroll
             for (int m = 0; m < NB; ++m) {
@@ -220,8 +172,7 @@ k_team_member_gains(const float* __restrict__ lo, int64_t n, int64_t npad, int B
                     if (lm > 0.f) count[m] += 1;
                     if (lm == 0.f) { without[m] += fr; continue; }   // S - 0 is S: the same reward, to the bit
                     const float lw = prior ? (S[j] - lm) + p[j] : S[j] - lm;
-                    const float rw = to_rcp(1.0f + to_exp(-lw));
-                    without[m] += reward_fixed(rw, shift);
+                    without[m] += reward_fixed(reward_sigmoid(lw), shift);
                 }
             }
         }
@@ -264,28 +215,21 @@ extern "C" int tohip_team_step_tail(float* poses, float* quats, const float* pos
                                     float* loss_log, int64_t loss_log_stride, void* team_state, size_t team_state_bytes_, int32_t n_steps,
                                     int32_t step_index, float clearance_weight, const float* clearance_grad,
                                     const double* clearance_terms, void* stream_) {
-    if (!poses || !quats || !poses0 || !poses_grad_eval || !quats_grad_eval || !poses_grad || !quats_grad || !exp_avg_p ||
-        !exp_avg_sq_p || !exp_avg_q || !exp_avg_sq_q || !scalars || !loss_log || !team_state || W < 3 || W > (1 << 24) || n_eval <= 0 ||
-        step <= 0 || (n_eval - 1) * step >= W || n_members <= 0 || n_members > TOHIP_TEAM_MAX_MEMBERS || n_steps <= 0 || step_index < 0 ||
-        step_index >= n_steps || (n_members > 1 && loss_log_stride < 8 * (int64_t)n_steps) ||
-        (clearance_grad != nullptr) != (clearance_terms != nullptr) ||
-        (clearance_grad && (!std::isfinite(clearance_weight) || !(clearance_weight >= 0.f))))
+    TeamTail a;
+    tail_args_fill(a, poses, quats, poses0, W, poses_grad_eval, quats_grad_eval, n_eval, step, poses_grad, quats_grad, exp_avg_p, exp_avg_sq_p,
+                   exp_avg_q, exp_avg_sq_q, smoothness_weight, traj_length_weight, eps, lr_pose, lr_quat, beta1, beta2, adam_eps, rewards_th,
+                   smoothness_th, scalars, loss_log, loss_log_stride, clearance_weight, clearance_grad, clearance_terms);
+    if (!tail_args_ok(a, W, n_eval, n_members) || !team_state || W > (1 << 24) || n_members > TOHIP_TEAM_MAX_MEMBERS || n_steps <= 0 ||
+        step_index < 0 || step_index >= n_steps || (n_members > 1 && loss_log_stride < 8 * (int64_t)n_steps))
         return TOHIP_EINVAL;
     if (team_state_bytes_ < team_state_bytes(n_members, n_steps)) return TOHIP_ENOSPC;
-    TeamTail a;
-    a.poses = poses; a.quats = quats; a.poses0 = poses0; a.pg_eval = poses_grad_eval; a.qg_eval = quats_grad_eval;
-    a.pg = poses_grad; a.qg = quats_grad; a.mp = exp_avg_p; a.vp = exp_avg_sq_p; a.mq = exp_avg_q; a.vq = exp_avg_sq_q;
-    a.scalars = scalars; a.loss_log = loss_log; a.log_stride = loss_log_stride;
     float* state = (float*)team_state;
     double* terms = (double*)((char*)team_state + (size_t)32 * n_members * (n_steps + 1));
     a.state_in = state + (int64_t)step_index * n_members * TO_OPT_STATE;
     a.state_out = state + (int64_t)(step_index + 1) * n_members * TO_OPT_STATE;
     a.terms_in = terms + (int64_t)step_index * n_members * 4;
     a.terms_out = terms + (int64_t)(step_index + 1) * n_members * 4;
-    a.W = (int)W; a.n_eval = (int)n_eval; a.step = step; a.B = (int)n_members;
-    a.smooth_w = smoothness_weight; a.length_w = traj_length_weight; a.eps = eps; a.lr_pose = lr_pose; a.lr_quat = lr_quat;
-    a.beta1 = beta1; a.beta2 = beta2; a.adam_eps = adam_eps; a.rewards_th = rewards_th; a.smoothness_th = smoothness_th;
-    a.clr = clearance_grad; a.clr_term = clearance_terms; a.clr_w = clearance_grad ? clearance_weight : 0.f;
+    a.B = (int)n_members;
     k_team_step_tail<<<(int)n_members, TO_BLOCK, 0, (hipStream_t)stream_>>>(a);
     TO_HIP_CHECK_LAUNCH();
     return TOHIP_OK;

@@ -126,6 +126,8 @@ __host__ __device__ inline int reward_shift(int64_t n) {
     return 47 - lg;   // n * 2^shift <= 2^47: the sum stays below bit 48
 }
 __device__ __forceinline__ long long reward_fixed(float r, int shift) { return __double2ll_rn(ldexp((double)r, shift)); }
+// THE reward of a log-odds sum x: every kernel that takes a reward (or its fixed-point value: the exact integer gains) calls this
+__device__ __forceinline__ float reward_sigmoid(float x) { return to_rcp(1.0f + to_exp(-x)); }
 // scalars[0] = mean(rewards), [1] = loss_vis = 1/(mean+eps) (model.py:246), [2] = d loss_vis / d reward_n, [3] reserved
 __device__ __forceinline__ void reward_scalars(long long total, bool anynan, int64_t n, int shift, float eps, float out[4]) {
     const float mean = anynan ? __builtin_nanf("") : (float)(ldexp((double)total, -shift) / (double)n);
@@ -975,7 +977,7 @@ __device__ __forceinline__ void sparse_slot(const SparseArgs& a, int slot, int t
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float ex = to_exp(-lo[j]);
-                float rw = to_rcp(1.0f + ex);   // == k_traj_reward's value of rewards[perm[i]]
+                float rw = reward_sigmoid(lo[j]);   // k_traj_reward's value of rewards[perm[i]] (the exponential is the one above)
                 float om = rw * ex;             // 1 - r = e / (1 + e): taken from the exponential, not from r (see pair_sums)
                 if (lo[j] != lo[j]) { rw = lo[j]; om = lo[j]; }
                 un[j] = base + j < a.cv.n ? 1.0f * rw * om : 0.f;   // the pair kernel's d reward / d lo_sum of this point, bit for bit
@@ -1271,7 +1273,7 @@ __device__ __forceinline__ void reward_block(const float* __restrict__ lo_sum, c
                 if (i0 + j < n) {
                     float r = sg[j];
                     if (!all0) {
-                        r = to_rcp(1.0f + to_exp(-lt[j]));
+                        r = reward_sigmoid(lt[j]);
                         if (lt[j] != lt[j]) r = lt[j];
                     }
                     rewards[o[j]] = r;
@@ -1291,7 +1293,7 @@ __device__ __forceinline__ void reward_block(const float* __restrict__ lo_sum, c
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (i0 + j < n) {
-                float r = to_rcp(1.0f + to_exp(-lo[j]));
+                float r = reward_sigmoid(lo[j]);
                 if (lo[j] != lo[j]) r = lo[j];  // a degenerate waypoint (max == min) makes the reference's rewards NaN: propagate
                 if (!prefilled || lo[j] != 0.f) rewards[o[j]] = r;
                 if (r != r) anynan = true;

@@ -187,7 +187,7 @@ k_views_write(const float* __restrict__ lo, int64_t n, int64_t npad, int nseg, c
 // the reward of one packed point as k_traj_reward / k_traj_reward_prior take it (reward_block), in fixed point
 __device__ __forceinline__ long long views_fixed(float lo, float p, bool prior, int shift) {
     const float lt = prior ? lo + p : lo;
-    return reward_fixed(to_rcp(1.0f + to_exp(-lt)), shift);
+    return reward_fixed(reward_sigmoid(lt), shift);
 }
 
 __device__ __forceinline__ void views_flush(long long acc, int c, long long* __restrict__ gain) {

@@ -144,60 +144,104 @@ def optimize_trajectory(model, n_opt_steps=10, lr_pose=0.1, lr_quat=0.0, rewards
     return run.results(n_opt_steps)[0]
 
 
+class _TailRun:
+    """One run of the separate-calls path as its two users see it (_optimize_trajectory_split: one model; optimize_team: B members):
+    equal-length trajectories laid end to end, every per-step buffer allocated once, and per step the caller's visibility step
+    over the evaluated waypoints (`st`: what its step() leaves in st.pg / st.qg / st.scalars is what the tail reads), the clearance
+    query when the term is on, the caller's tail entry — launches only.  `tail_args`: the arguments every tail entry starts with
+    (tohip_traj_step_tail_multi / _clearance, tohip_team_step_tail), `clr_args`: the three the clearance term adds."""
+
+    def __init__(self, models, st, n_opt_steps, lr_pose, lr_quat, rewards_th, smoothness_th, vis_wps_dist, betas, adam_eps, what):
+        L = _lib.lib()
+        m0 = models[0]
+        self.models, self.B, self.dev, self.n, self.cloud = models, len(models), m0.device, int(n_opt_steps), m0._cloud
+        B, n, dev = self.B, self.n, self.dev
+        W = self.W = m0.poses.shape[0]
+        step_w = self.step_w = m0._wps_step(vis_wps_dist)
+        n_eval = self.n_eval = (W + step_w - 1) // step_w
+        f32 = dict(dtype=torch.float32, device=dev)
+        if B == 1:   # the Parameters themselves are updated in place
+            self.poses, self.quats, self.poses0 = m0.poses.data, m0.quats.data, m0.poses0.contiguous()
+        else:
+            self.poses = torch.cat([m.poses.data for m in models]).contiguous()
+            self.quats = torch.cat([m.quats.data for m in models]).contiguous()
+            self.poses0 = torch.cat([m.poses0 for m in models]).contiguous()
+        poses, quats = self.poses, self.quats
+        if not (poses.is_contiguous() and quats.is_contiguous() and poses.dtype == torch.float32 and quats.dtype == torch.float32):
+            raise RuntimeError(f"{what}: poses / quats must be contiguous float32 tensors")
+        # the evaluated waypoints are every step_w-th row of the Parameters, read in place (TOHIP_TRAJ_STRIDE in the flags: no gather);
+        # over a concatenation that lands on each member's rows only when W is a multiple of the step: a gather otherwise
+        self.strided = B == 1 or W % step_w == 0
+        self.stride = ((step_w - 1) & 0xffff) << 8 if self.strided else 0
+        self.src = (poses, quats) if self.strided else (torch.empty((B * n_eval, 3), **f32), torch.empty((B * n_eval, 4), **f32))
+        self.pg, self.qg = torch.zeros((B * W, 3), **f32), torch.zeros((B * W, 4), **f32)
+        self.moments = [torch.zeros((B * W, 3), **f32), torch.zeros((B * W, 3), **f32), torch.zeros((B * W, 4), **f32), torch.zeros((B * W, 4), **f32)]
+        self.loss_log = torch.zeros((B, n + 1, 8), **f32)   # (a stopped trajectory's later steps rewrite the row after its last)
+        self.clr, self.clr_args = m0._clearance_on, (0.0, None, None)
+        if self.clr:   # the clearance query of all B W waypoints: its gradient rows and per-waypoint terms, consumed by the tail
+            self.clr_rows = torch.empty((B * W, 3), **f32)
+            self.clr_terms = torch.empty(L.tohip_clearance_workspace_bytes(B * W) // 8, dtype=torch.float64, device=dev)
+            self.clr_args = (float(m0.clearance_weight), ptr(self.clr_rows), ptr(self.clr_terms))
+        self.st, self.weights = st, (float(m0.smoothness_weight), float(m0.traj_length_weight), float(m0.eps))
+        self.tail_args = (ptr(poses), ptr(quats), ptr(self.poses0), W, B, ptr(st.pg), ptr(st.qg), n_eval, step_w, ptr(self.pg), ptr(self.qg),
+                          *(ptr(t) for t in self.moments), *self.weights, float(lr_pose), float(lr_quat), betas[0], betas[1], adam_eps,
+                          float(rewards_th), float(smoothness_th), ptr(st.scalars), ptr(self.loss_log), (n + 1) * 8)
+
+    def run(self, vis_step, tail, what):
+        """n steps: vis_step(poses_src, quats_src, flags_extra) is the caller's visibility step, tail(i) its tail entry's return code."""
+        L, m0 = _lib.lib(), self.models[0]
+        with torch.cuda.device(self.dev):
+            for i in range(self.n):
+                if not self.strided:
+                    check(L.tohip_gather_waypoints_multi(ptr(self.poses), ptr(self.quats), self.W, self.B, self.n_eval, self.step_w,
+                                                         ptr(self.src[0]), ptr(self.src[1]), stream_ptr()), "tohip_gather_waypoints_multi")
+                vis_step(*self.src, self.stride)
+                if self.clr:
+                    ops.clearance(self.cloud, self.poses, m0.clearance_radius, m0.clearance_weight, grad=self.clr_rows, terms=self.clr_terms)
+                check(tail(i), what)
+
+    def finish(self, steps):
+        """Every model's Parameters, rewards (one tensor, shared) and loss terms after `steps` steps -> the loss logs on the host."""
+        lt = self.loss_log.cpu()
+        rewards = self.st.rewards.clone()   # (the step's buffer is the next run's)
+        for b, m in enumerate(self.models):
+            if self.B > 1:
+                m.poses.data.copy_(self.poses[b * self.W:(b + 1) * self.W])
+                m.quats.data.copy_(self.quats[b * self.W:(b + 1) * self.W])
+            torch.autograd.graph.increment_version(m.poses)
+            torch.autograd.graph.increment_version(m.quats)
+            row = lt[b, max(steps, 1) - 1]
+            m.rewards = rewards
+            m.loss = {"vis": row[0], "l2": row[1], "length": row[2], "smooth": row[3]}
+            if self.clr:
+                m.loss["clearance"] = row[5]
+        return lt
+
+
 @torch.no_grad()
 def _optimize_trajectory_split(model, n_opt_steps, lr_pose, lr_quat, rewards_th, smoothness_th, vis_wps_dist, betas, adam_eps):
     """optimize_trajectory with a collective (a sharded model) or a hull pass (occlusion rows) inside the step: per step the model's
     visibility step (ops.WaypointShardStep or ops.PointShardStep: gradients identical on every rank) and the replicated O(W)
     remainder in one launch — scatter, regularisers, both Adam updates, early stop — so every rank takes the same step."""
     L = _lib.lib()
-    dev = model.device
     W = model.poses.shape[0]
     step_w = model._wps_step(vis_wps_dist)
     n_eval = (W + step_w - 1) // step_w
     points = model._shard.kind == "points"
     st = model._point_step(n_eval) if points else model._waypoint_step(n_eval)
-    f32 = dict(dtype=torch.float32, device=dev)
-    pg, qg = torch.zeros((W, 3), **f32), torch.zeros((W, 4), **f32)
-    loss_terms = torch.zeros((n_opt_steps + 1, 8), **f32)
-    state = torch.zeros(8, **f32)
-    mp, vp = torch.zeros((W, 3), **f32), torch.zeros((W, 3), **f32)
-    mq, vq = torch.zeros((W, 4), **f32), torch.zeros((W, 4), **f32)
-    poses, quats = model.poses.data, model.quats.data
-    # the evaluated waypoints are every step_w-th row of the Parameters, read in place (TOHIP_TRAJ_STRIDE in the flags: no gather)
-    stride = ((step_w - 1) & 0xffff) << 8
-    # the step tail reads the visibility step's own buffers (st.scalars, st.pg, st.qg: what st.step returns), one trajectory
-    tail_args = (ptr(poses), ptr(quats), ptr(model.poses0), W, 1, ptr(st.pg), ptr(st.qg), n_eval, step_w, ptr(pg), ptr(qg), ptr(mp),
-                 ptr(vp), ptr(mq), ptr(vq), float(model.smoothness_weight), float(model.traj_length_weight), float(model.eps),
-                 float(lr_pose), float(lr_quat), betas[0], betas[1], adam_eps, float(rewards_th), float(smoothness_th), ptr(st.scalars),
-                 ptr(loss_terms), 0, ptr(state))
-    clr = model._clearance_on
-    if clr:   # the clearance term: the query's gradient rows and per-waypoint terms, consumed by the step tail
-        clr_rows = torch.empty((W, 3), **f32)
-        clr_terms = torch.empty(L.tohip_clearance_workspace_bytes(W) // 8, dtype=torch.float64, device=dev)
-        tail, tail_args = L.tohip_traj_step_tail_clearance, tail_args + (float(model.clearance_weight), ptr(clr_rows), ptr(clr_terms))
-    else:
-        tail = L.tohip_traj_step_tail_multi
-    with torch.cuda.device(dev):
-        for _ in range(n_opt_steps):
-            if points:   # (PointShard refuses occlusion and a prior)
-                st.step(poses, quats, flags_extra=stride)
-            else:
-                st.step(poses, quats, flags_extra=stride, occ=model._own_occlusion_rows(st, poses, quats, step_w), prior=model._prior)
-            if clr:
-                ops.clearance(model._cloud, poses, model.clearance_radius, model.clearance_weight, grad=clr_rows, terms=clr_terms)
-            check(tail(*tail_args, stream_ptr()), "step tail")
-    torch.autograd.graph.increment_version(model.poses)
-    torch.autograd.graph.increment_version(model.quats)
+    run = _TailRun([model], st, n_opt_steps, lr_pose, lr_quat, rewards_th, smoothness_th, vis_wps_dist, betas, adam_eps, "optimize_trajectory")
+    state = torch.zeros(8, dtype=torch.float32, device=model.device)
+    def vis_step(p, q, stride):   # (PointShard refuses occlusion and a prior)
+        kw = {} if points else dict(occ=model._own_occlusion_rows(st, p, q, step_w), prior=model._prior)
+        st.step(p, q, flags_extra=stride, **kw)
+    tail, rest = (L.tohip_traj_step_tail_clearance, run.clr_args) if run.clr else (L.tohip_traj_step_tail_multi, ())
+    run.run(vis_step, lambda i: tail(*run.tail_args, ptr(state), *rest, stream_ptr()), "step tail")
     stt = state.cpu()  # the run's only host synchronisation
     steps = int(stt[3].item())
-    lt_host = loss_terms[:max(steps, 1)].cpu()
-    model.rewards = st.rewards.clone()   # (the step's buffer is the next run's)
+    lt = run.finish(steps)
     if points:
         model._mean_reward = st.scalars[0].clone()
-    model.loss = {"vis": lt_host[-1, 0], "l2": lt_host[-1, 1], "length": lt_host[-1, 2], "smooth": lt_host[-1, 3]}
-    if clr:
-        model.loss["clearance"] = lt_host[-1, 5]
-    return TrajOptResult(steps, bool(stt[2].item() != 0), lt_host[:, 4].tolist(), float(stt[4]), float(stt[5]))
+    return TrajOptResult(steps, bool(stt[2].item() != 0), lt[0, :max(steps, 1), 4].tolist(), float(stt[4]), float(stt[5]))
 
 
 def _check_same_setup(models, vis_wps_dist, what):
@@ -301,75 +345,29 @@ def optimize_team(models, n_opt_steps=10, lr_pose=0.1, lr_quat=0.0, rewards_th=1
     if n_opt_steps <= 0:   # nothing to run: the models keep their rewards and loss terms
         return TeamOptResult(0, False, [], 0.0, [0.0] * B, [])
     L = _lib.lib()
-    dev, cloud = m0.device, m0._cloud
     n = int(n_opt_steps)
     W = m0.poses.shape[0]
     step_w = m0._wps_step(vis_wps_dist)
-    n_eval = (W + step_w - 1) // step_w
-    f32 = dict(dtype=torch.float32, device=dev)
-    if B == 1:   # the Parameters themselves are updated in place
-        poses, quats, poses0 = m0.poses.data, m0.quats.data, m0.poses0.contiguous()
-    else:
-        poses = torch.cat([m.poses.data for m in models]).contiguous()
-        quats = torch.cat([m.quats.data for m in models]).contiguous()
-        poses0 = torch.cat([m.poses0 for m in models]).contiguous()
-    if not (poses.is_contiguous() and quats.is_contiguous() and poses.dtype == torch.float32 and quats.dtype == torch.float32):
-        raise RuntimeError("optimize_team: poses / quats must be contiguous float32 tensors")
     # the team's visibility step: the members' evaluated waypoints as ONE trajectory of B n_eval rows through the separate calls
-    st = m0._waypoint_step(B * n_eval)
-    # every step_w-th row of the concatenation lands on each member's rows only when W is a multiple of the step: a gather otherwise
-    strided = B == 1 or W % step_w == 0
-    stride = ((step_w - 1) & 0xffff) << 8 if strided else 0
-    src_p, src_q = (poses, quats) if strided else (torch.empty((B * n_eval, 3), **f32), torch.empty((B * n_eval, 4), **f32))
-    pg, qg = torch.zeros((B * W, 3), **f32), torch.zeros((B * W, 4), **f32)
-    moments = [torch.zeros((B * W, 3), **f32), torch.zeros((B * W, 3), **f32), torch.zeros((B * W, 4), **f32), torch.zeros((B * W, 4), **f32)]
-    loss_log = torch.zeros((B, n, 8), **f32)
+    st = m0._waypoint_step(B * ((W + step_w - 1) // step_w))
+    run = _TailRun(models, st, n, lr_pose, lr_quat, rewards_th, smoothness_th, vis_wps_dist, betas, adam_eps, "optimize_team")
     sb = L.tohip_team_state_bytes(B, n)
-    team_state = torch.zeros(sb, dtype=torch.uint8, device=dev)
+    team_state = torch.zeros(sb, dtype=torch.uint8, device=m0.device)
     state = team_state[:sb // 2].view(torch.float32).view(n + 1, B, 8)
     terms64 = team_state[sb // 2:].view(torch.float64).view(n + 1, B, 4)
-    member_terms = torch.empty((B, 8), **f32)
-    weights = (float(m0.smoothness_weight), float(m0.traj_length_weight), float(m0.eps))
-    clr = m0._clearance_on
-    clr_w, clr_rows, clr_terms = 0.0, None, None
-    if clr:   # the clearance query of all members' waypoints: one launch per step, before the tail
-        clr_w = float(m0.clearance_weight)
-        clr_rows = torch.empty((B * W, 3), **f32)
-        clr_terms = torch.empty(L.tohip_clearance_workspace_bytes(B * W) // 8, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
+    member_terms = torch.empty((B, 8), dtype=torch.float32, device=m0.device)
+    with torch.cuda.device(m0.device):
         # every member's terms at the start: row 0 of the state's terms (a step's blocks read the others' from the row before)
-        check(L.tohip_team_loss(ptr(poses), ptr(poses0), W, B, *weights, None, 0.0, None, ptr(member_terms), ptr(terms64), None, None, None,
-                                stream_ptr()), "tohip_team_loss")
-        for i in range(n):
-            if not strided:
-                check(L.tohip_gather_waypoints_multi(ptr(poses), ptr(quats), W, B, n_eval, step_w, ptr(src_p), ptr(src_q), stream_ptr()),
-                      "tohip_gather_waypoints_multi")
-            st.step(src_p, src_q, flags_extra=stride, prior=prior)
-            if clr:
-                ops.clearance(cloud, poses, m0.clearance_radius, m0.clearance_weight, grad=clr_rows, terms=clr_terms)
-            check(L.tohip_team_step_tail(ptr(poses), ptr(quats), ptr(poses0), W, B, ptr(st.pg), ptr(st.qg), n_eval, step_w, ptr(pg), ptr(qg),
-                                         *(ptr(t) for t in moments), *weights, float(lr_pose), float(lr_quat), betas[0], betas[1], adam_eps,
-                                         float(rewards_th), float(smoothness_th), ptr(st.scalars), ptr(loss_log), n * 8, ptr(team_state), sb,
-                                         n, i, clr_w, ptr(clr_rows), ptr(clr_terms), stream_ptr()), "tohip_team_step_tail")
+        check(L.tohip_team_loss(ptr(run.poses), ptr(run.poses0), W, B, *run.weights, None, 0.0, None, ptr(member_terms), ptr(terms64), None,
+                                None, None, stream_ptr()), "tohip_team_loss")
+    run.run(lambda p, q, stride: st.step(p, q, flags_extra=stride, prior=prior),
+            lambda i: L.tohip_team_step_tail(*run.tail_args, ptr(team_state), sb, n, i, *run.clr_args, stream_ptr()), "tohip_team_step_tail")
     stt = state[n].cpu()   # the run's only host synchronisation
-    lt = loss_log.cpu()
     steps = int(stt[0, 3].item())
-    rewards = st.rewards.clone()   # (the step's buffer is the next run's)
-    member_losses = []
-    for b, m in enumerate(models):
-        if B > 1:
-            m.poses.data.copy_(poses[b * W:(b + 1) * W])
-            m.quats.data.copy_(quats[b * W:(b + 1) * W])
-        torch.autograd.graph.increment_version(m.poses)
-        torch.autograd.graph.increment_version(m.quats)
-        row = lt[b, max(steps, 1) - 1]
-        m.rewards = rewards
-        m.loss = {"vis": row[0], "l2": row[1], "length": row[2], "smooth": row[3]}
-        if clr:
-            m.loss["clearance"] = row[5]
-        member_losses.append({k: float(v) for k, v in m.loss.items() if k != "vis"})
+    lt = run.finish(steps)
+    member_losses = [{k: float(v) for k, v in m.loss.items() if k != "vis"} for m in models]
     return TeamOptResult(steps, bool(stt[0, 2].item() != 0), lt[0, :max(steps, 1), 4].tolist(), float(stt[0, 4]),
-                         [float(x) for x in stt[:, 5]], member_losses, lt[:, :steps].numpy(), pg.view(B, W, 3), qg.view(B, W, 4))
+                         [float(x) for x in stt[:, 5]], member_losses, lt[:, :steps].numpy(), run.pg.view(B, W, 3), run.qg.view(B, W, 4))
 
 
 class PoseOptResult:
