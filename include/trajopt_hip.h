@@ -37,7 +37,10 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_covmap_bytes / tohip_covmap_init / tohip_covmap_integrate / tohip_covmap_lookup / tohip_covmap_merge /
+/* (still 15) + tohip_clearance_segments / tohip_clearance_segments_workspace_bytes / tohip_traj_clearance_segments_scratch_bytes and
+ * the flag bit TOHIP_TRAJ_CLEARANCE_SEGMENTS (the swept clearance term: the hinge on each segment's distance): new symbols and one
+ * flag bit that was refused before — no struct and no existing signature changes.
+ * (still 15) + tohip_covmap_bytes / tohip_covmap_init / tohip_covmap_integrate / tohip_covmap_lookup / tohip_covmap_merge /
  * tohip_covmap_rehash / tohip_covmap_export / tohip_covmap_read_header (the voxel-keyed log-odds map): new symbols only.
  * (still 15) + tohip_views_bytes / tohip_views_append / tohip_views_select / tohip_views_row (greedy view selection): new symbols only.
  * (still 15) + tohip_team_step_tail / tohip_team_loss / tohip_team_member_gains / tohip_team_state_bytes /
@@ -122,6 +125,11 @@ size_t tohip_traj_workspace_bytes(int64_t n_points, int64_t n_virtual);
  * overwrites unread — 64 MB of stores per step for eight trajectories over 1 M points
  * (/root/reference/src/trajectory_optimization.py:147-157 publishes model.rewards once, after the loop). */
 #define TOHIP_TRAJ_OPT_LAST_OUTPUTS 2
+/* tohip_traj_loss.flags and tohip_traj_opt.flags only: with clearance_weight > 0 the clearance term is the SWEPT one — the hinge on
+ * each segment's distance to the cloud (tohip_clearance_segments) in place of each waypoint's; its launches come first, as the point
+ * query's do, and clearance_scratch is then tohip_traj_clearance_segments_scratch_bytes.  Without the bit, or with weight 0, every
+ * launch is the one without it. */
+#define TOHIP_TRAJ_CLEARANCE_SEGMENTS 4
 
 /* Forward over the W evaluated waypoints (caller has applied wps_step, model.py:214-217):
  * to_camera_frame -> get_dist_mask * get_fov_mask -> per-waypoint (p-min)/max -> clip -> log-odds,
@@ -333,7 +341,8 @@ typedef struct tohip_traj_loss {
        gout x its gradient rows to the regularisers' before the visibility rows: vis + gout (regularisers + clearance) */
     float clearance_radius;
     float clearance_weight;
-    void *clearance_scratch;  /* tohip_traj_clearance_scratch_bytes(W, 1): its gradient rows (W,3) f32 at offset 0, then the terms */
+    void *clearance_scratch;  /* tohip_traj_clearance_scratch_bytes(W, 1): its gradient rows (W,3) f32 at offset 0, then the terms
+                                 (TOHIP_TRAJ_CLEARANCE_SEGMENTS: tohip_traj_clearance_segments_scratch_bytes(W, 1), the same offsets) */
     size_t clearance_scratch_bytes;
 } tohip_traj_loss;
 size_t tohip_traj_loss_scratch_bytes(int64_t n_points, int64_t n_wps, int32_t wps_step, int32_t n_cams);
@@ -369,7 +378,7 @@ typedef struct tohip_traj_opt {
     int64_t n_points;
     int64_t n_wps;             /* W: waypoints of ONE trajectory */
     int32_t wps_step;          /* every wps_step-th waypoint is evaluated for visibility */
-    int32_t flags;             /* TOHIP_TRAJ_DENSE, TOHIP_TRAJ_OPT_LAST_OUTPUTS or 0 */
+    int32_t flags;             /* TOHIP_TRAJ_DENSE, TOHIP_TRAJ_OPT_LAST_OUTPUTS, TOHIP_TRAJ_CLEARANCE_SEGMENTS or 0 */
     int32_t n_traj;            /* trajectories laid end to end: rows b * W .. b * W + W - 1 of every per-waypoint array */
     int32_t n_steps;           /* rows of the logs below */
     const int32_t *traj_offsets; /* n_traj + 1 device int32: b * ceil(W / wps_step) (NULL when n_traj == 1) */
@@ -401,7 +410,8 @@ typedef struct tohip_traj_opt {
        log row gets [5] = clearance (total includes it) */
     float clearance_radius;
     float clearance_weight;
-    void *clearance_scratch;   /* tohip_traj_clearance_scratch_bytes(n_wps, n_traj) */
+    void *clearance_scratch;   /* tohip_traj_clearance_scratch_bytes(n_wps, n_traj) (TOHIP_TRAJ_CLEARANCE_SEGMENTS:
+                                  tohip_traj_clearance_segments_scratch_bytes(n_wps, n_traj); two launches first instead of one) */
     size_t clearance_scratch_bytes;
 } tohip_traj_opt;
 size_t tohip_traj_opt_scratch_bytes(int64_t n_wps, int64_t n_traj);
@@ -698,6 +708,30 @@ int tohip_clearance(const void *packed, int64_t n_points, const float *queries, 
 /* bytes of tohip_traj_loss.clearance_scratch / tohip_traj_opt.clearance_scratch: gradient rows (n_traj W, 3) f32 at offset 0, then
  * the per-waypoint terms */
 size_t tohip_traj_clearance_scratch_bytes(int64_t n_wps, int64_t n_traj);
+
+/* The swept term: the same hinge on each SEGMENT's distance to the cloud, so that the straight line between two waypoints stays off
+ * it as well.  poses (n_traj n_wps, 3): n_traj trajectories of n_wps >= 2 waypoints laid end to end; segment (b, w), w < n_wps - 1,
+ * joins a = waypoint w and b = waypoint w + 1 of trajectory b — never two trajectories.  In f32 without contraction: e = fl(b - a),
+ * ee = fl(fl(ex ex + ey ey) + ez ez), inv = fl(1 / ee) when ee > 0, else 0; per point x with three finite coordinates u = fl(x - a),
+ * s = fmin(fmax(fl(fl(fl(ux ex + uy ey) + uz ez) inv), 0), 1) (a NaN becomes 0), q = fl(u - fl(s e)), d2 = fl(fl(qx qx + qy qy) + qz qz).
+ * idx = the argmin of d2 over d2 < fl(r r), ties to the lowest caller row; -1 when there is none or an end is not finite (a = b is
+ * tohip_clearance's query bit for bit).  d = (float)sqrt((double)d2), +inf when idx = -1; s = where along the segment the closest
+ * point c lies (0 = a, 1 = b), recomputed in f64 from the f32 coordinates (0 when idx = -1).  d, idx, s: (n_traj (n_wps - 1)).
+ * The term: weight x sum over the segments of (r - d)^2, per trajectory, f64 in order, rounded to f32 (value: n_traj device floats,
+ * may be NULL).  Its gradient, with n = (c - x) / |c - x|: g_a = -2 weight (r - d)(1 - s) n, g_b = -2 weight (r - d) s n in f64
+ * (zero when idx = -1 or |c - x| = 0); grad (n_traj n_wps, 3; may be NULL; overwritten) row w = (float)(g_b of segment w - 1 + g_a
+ * of segment w).  workspace: tohip_clearance_segments_workspace_bytes(n_wps, n_traj); after the call it holds (n_traj n_wps) doubles
+ * at offset 0 — the segment's (r - d)^2 at its first waypoint's row, 0 at a trajectory's last — which is what
+ * tohip_traj_step_tail_clearance, tohip_traj_regularizers_clearance and the team calls take as clearance_terms (with grad as
+ * clearance_grad), then the per-segment g_a, g_b.  radius > 0 and weight >= 0, both finite.  One block of 16 waves per segment and one
+ * thread per waypoint; no atomics: the results do not depend on the launch.  Two launches (three with value). */
+size_t tohip_clearance_segments_workspace_bytes(int64_t n_wps, int64_t n_traj);
+int tohip_clearance_segments(const void *packed, int64_t n_points, const float *poses, int64_t n_wps, int64_t n_traj, float radius,
+                             float weight, float *d, int32_t *idx, float *s, float *value, float *grad, void *workspace,
+                             size_t workspace_bytes, void *stream);
+/* bytes of clearance_scratch with TOHIP_TRAJ_CLEARANCE_SEGMENTS: tohip_traj_clearance_scratch_bytes' rows and terms at the same
+ * offsets, then the per-segment g_a, g_b */
+size_t tohip_traj_clearance_segments_scratch_bytes(int64_t n_wps, int64_t n_traj);
 
 /* ---- input formats (pointcloud_utils.py, launch/voxels_filtering.launch) --------------------------------
  * PointCloud2 payload -> (N,3) f32 with non-finite rows removed, in message order

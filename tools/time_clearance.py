@@ -11,6 +11,9 @@
 
     python tools/time_clearance.py [--reps 5] [--steps 20,120] [--radius 0.5] [--weight 5] [--json out.json]
     python tools/time_clearance.py --only-query        # under rocprofv3 --kernel-trace --stats
+    python tools/time_clearance.py --path              # the queries are the waypoints of a path (synth.make_path), not random positions
+    python tools/time_clearance.py --segments          # clearance_mode='segments': tohip_clearance_segments over the segments of that
+                                                       # path (k_clearance_seg + k_clearance_seg_rows), and the step / sample with the mode
 """
 import argparse
 import json
@@ -57,12 +60,42 @@ def time_query(cloud, q, radius, reps, calls=200):
     return {"us_per_call_min": min(best), "us_per_call_median": float(np.median(best)), "queries_with_a_point": hit, "queries": n}
 
 
-def query_case(n_points, n_queries, radius, reps, dev):
+def time_segments(cloud, p, radius, reps, calls=200):
+    L = _lib.lib()
+    dev = p.device
+    n = p.shape[0]
+    d = torch.empty(n - 1, dtype=torch.float32, device=dev)
+    idx = torch.empty(n - 1, dtype=torch.int32, device=dev)
+    s = torch.empty(n - 1, dtype=torch.float32, device=dev)
+    g = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    wsb = L.tohip_clearance_segments_workspace_bytes(n, 1)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    args = (cloud.blob.data_ptr(), cloud.n, p.data_ptr(), n, 1, float(radius), 1.0, d.data_ptr(), idx.data_ptr(), s.data_ptr(), None,
+            g.data_ptr(), ws.data_ptr(), wsb)
+    st = stream_ptr()
+    check(L.tohip_clearance_segments(*args, st), "tohip_clearance_segments")
+    best = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(calls):
+            L.tohip_clearance_segments(*args, st)
+        b.record()
+        b.synchronize()
+        best.append(1000.0 * a.elapsed_time(b) / calls)
+    hit = int((idx >= 0).sum())
+    return {"us_per_call_min": min(best), "us_per_call_median": float(np.median(best)), "segments_with_a_point": hit, "segments": n - 1}
+
+
+def query_case(n_points, n_queries, radius, reps, dev, path=False, segments=False):
     pts = torch.from_numpy(synth.make_cloud(n_points, seed=1)).to(dev)
     cloud = ops.PackedCloud(pts)
     rng = np.random.default_rng(2)
-    q = torch.from_numpy(rng.uniform((-18, -18, -1.5), (18, 18, 1.5), (n_queries, 3)).astype(np.float32)).to(dev)
-    out = time_query(cloud, q, radius, reps)
+    if path or segments:
+        q = torch.from_numpy(synth.make_path(n_queries, optical=True, jitter_seed=1)[0]).to(dev)
+    else:
+        q = torch.from_numpy(rng.uniform((-18, -18, -1.5), (18, 18, 1.5), (n_queries, 3)).astype(np.float32)).to(dev)
+    out = time_segments(cloud, q, radius, reps) if segments else time_query(cloud, q, radius, reps)
     out.update(points=n_points)
     return out
 
@@ -76,11 +109,11 @@ def run_ms(model_factory, steps):
     return 1000.0 * (time.perf_counter() - t0)
 
 
-def step_case(radius, weight, steps, reps, dev):
+def step_case(radius, weight, steps, reps, dev, mode="waypoints"):
     pts = torch.from_numpy(synth.make_cloud(1_000_000, seed=1))
     p, q = synth.make_path(128, optical=True, jitter_seed=1)
     base = ModelTraj(pts, torch.from_numpy(p), torch.from_numpy(q), torch.from_numpy(K), IW, IH, device=dev)
-    variants = {"without": {}, "with": dict(clearance_radius=radius, clearance_weight=weight)}
+    variants = {"without": {}, "with": dict(clearance_radius=radius, clearance_weight=weight, clearance_mode=mode)}
 
     def factory(kw):
         return lambda: ModelTraj.sharing_cloud_of(base, torch.from_numpy(p), torch.from_numpy(q), **kw)
@@ -97,20 +130,21 @@ def step_case(radius, weight, steps, reps, dev):
     return out
 
 
-def sample_case(radius, weight, dev):
+def sample_case(radius, weight, dev, mode="waypoints"):
     d = np.load(os.path.join(REPO, "tests", "golden", "bundled.npz"))
     pts, poses = d["pts"], d["poses"]
     quats = np.tile(np.array([[1.0, 0.0, 0.0, 0.0]], dtype=np.float32), (len(poses), 1))
     Kt, iw, ih = tools.load_intrinsics(device=dev)
     out = {}
-    for name, kw in (("without", {}), ("with", dict(clearance_radius=radius, clearance_weight=weight))):
+    for name, kw in (("without", {}), ("with", dict(clearance_radius=radius, clearance_weight=weight, clearance_mode=mode))):
         m = ModelTraj(torch.from_numpy(pts), torch.from_numpy(poses), torch.from_numpy(quats), Kt, iw, ih, smoothness_weight=14.0,
                       traj_length_weight=0.02, device=dev, **kw)
         d0, _ = tools.trajectory_clearance(m, m.poses.data, 100.0)
         res = optimize_trajectory(m, 400, 0.1, 0.02, 1.1, 0.9)
         d1, _ = tools.trajectory_clearance(m, m.poses.data, 100.0)
         out[name] = {"steps": res.steps_taken, "min_clearance_start_m": float(d0.min()), "min_clearance_end_m": float(d1.min()),
-                     "waypoints_within_radius_end": int((d1 < radius).sum())}
+                     "waypoints_within_radius_end": int((d1 < radius).sum()),
+                     "min_segment_clearance_end_m": float(tools.trajectory_clearance(m, m.poses.data, 100.0, segments=True)[0].min())}
     return out
 
 
@@ -121,18 +155,21 @@ def main():
     ap.add_argument("--radius", type=float, default=0.5)
     ap.add_argument("--weight", type=float, default=5.0)
     ap.add_argument("--only-query", action="store_true")
+    ap.add_argument("--path", action="store_true", help="the queries are the waypoints of a path instead of random positions")
+    ap.add_argument("--segments", action="store_true", help="clearance_mode='segments' throughout (the query over that path's segments)")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    res = {"query_1m_x_128": query_case(1_000_000, 128, a.radius, a.reps, dev)}
+    mode = "segments" if a.segments else "waypoints"
+    res = {"query_1m_x_128": query_case(1_000_000, 128, a.radius, a.reps, dev, a.path, a.segments)}
     print(json.dumps(res), flush=True)
-    res["query_16m_x_1024"] = query_case(16_000_000, 1024, a.radius, a.reps, dev)
+    res["query_16m_x_1024"] = query_case(16_000_000, 1024, a.radius, a.reps, dev, a.path, a.segments)
     print(json.dumps(res["query_16m_x_1024"]), flush=True)
     if not a.only_query:
         steps = tuple(int(s) for s in a.steps.split(","))
-        res["step_1m_x_128"] = step_case(a.radius, a.weight, steps, a.reps, dev)
+        res["step_1m_x_128"] = step_case(a.radius, a.weight, steps, a.reps, dev, mode)
         print(json.dumps(res["step_1m_x_128"]), flush=True)
-        res["sample"] = sample_case(a.radius, a.weight, dev)
+        res["sample"] = sample_case(a.radius, a.weight, dev, mode)
         print(json.dumps(res["sample"]), flush=True)
     if a.json:
         with open(a.json, "w") as f:

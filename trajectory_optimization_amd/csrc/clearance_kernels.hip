@@ -131,6 +131,157 @@ __global__ void __launch_bounds__(TO_CLR_WAVES * 64) k_clearance(ClrArgs a) {
         for (int k = 0; k < 3; ++k) a.grad[3 * w + k] = a.accumulate ? a.grad[3 * w + k] + g[k] : g[k];
 }
 
+// ---- the swept term: the same hinge on each SEGMENT's distance to its nearest cloud point ('segments' mode) --------------------
+// For consecutive waypoints a = t_w, b = t_{w+1} of ONE trajectory (never across two trajectories laid end to end), all f32 without
+// contraction:  e = fl(b - a), ee = fl(fl(ex ex + ey ey) + ez ez), inv = fl(1 / ee) (0 when ee is not > 0);  per finite point x:
+// u = fl(x - a), s = fmin(fmax(fl(fl(fl(ux ex + uy ey) + uz ez) inv), 0), 1) (a NaN becomes 0), q = fl(u - fl(s e)),
+// d2 = fl(fl(qx qx + qy qy) + qz qz).  The winner is the argmin of d2 over d2 < fl(r r), ties to the lowest caller row (-1: none, or
+// an endpoint that is not finite); a = b is the point query above, bit for bit.  One thread finishes in f64: d = sqrt((double)d2),
+// s* and the closest point c recomputed in f64 from the f32 coordinates, n = (c - x) / |c - x|, term = (r - d)^2,
+// g_a = -2 weight (r - d)(1 - s*) n, g_b = -2 weight (r - d) s* n (the envelope theorem: s* is a minimiser or sits on its clamp),
+// both zero when |c - x| = 0.  The per-segment parts go to scratch; k_clearance_seg_rows adds them per waypoint.
+// The same block shape as k_clearance; the prune measures the sphere's centre against the segment (same clamp, plain f32).
+struct ClrSegArgs {
+    CloudView cv;
+    const float* p;        // (n_traj W, 3) waypoint positions, trajectories end to end
+    int W;                 // waypoints of one trajectory (>= 2): segment blockIdx.x = (b, w), b = blockIdx.x / (W - 1)
+    float r, weight;
+    float* d;              // may be NULL: (n_traj (W - 1)) distance, +inf when no point is within r
+    int* idx;              // may be NULL: (n_traj (W - 1)) caller row of the nearest point, -1 when none
+    float* s;              // may be NULL: (n_traj (W - 1)) where along the segment the closest point lies (0 = a, 1 = b; 0 when idx = -1)
+    double* term;          // (n_traj W) per-waypoint terms: entry b W + w = (r - d)^2 of segment (b, w)
+    double* part;          // (n_traj (W - 1), 6) g_a, g_b of every segment in f64
+};
+
+__global__ void __launch_bounds__(TO_CLR_WAVES * 64) k_clearance_seg(ClrSegArgs a) {
+    __shared__ unsigned long long sbest[TO_CLR_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t seg = blockIdx.x;
+    const int64_t row = seg / (a.W - 1) * a.W + seg % (a.W - 1);   // the waypoint row of the segment's first end
+    const float ax = a.p[3 * row], ay = a.p[3 * row + 1], az = a.p[3 * row + 2];
+    const float bx = a.p[3 * row + 3], by = a.p[3 * row + 4], bz = a.p[3 * row + 5];
+    const float r2 = __fmul_rn(a.r, a.r);
+    unsigned long long best = ~0ull;
+    if (clr_finite3(ax, ay, az) && clr_finite3(bx, by, bz)) {
+        const int64_t npad = a.cv.npad, n = a.cv.n;
+        const int ntiles = (int)(npad / 256);
+        const float* X = a.cv.soa;
+        const float* Y = X + npad;
+        const float* Z = Y + npad;
+        const float ex = __fsub_rn(bx, ax), ey = __fsub_rn(by, ay), ez = __fsub_rn(bz, az);
+        const float ee = __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez));
+        const float inv = ee > 0.f ? __fdiv_rn(1.f, ee) : 0.f;
+        const float ta = fmaxf(fmaxf(fmaxf(fabsf(ax), fabsf(ay)), fabsf(az)), fmaxf(fmaxf(fabsf(bx), fabsf(by)), fabsf(bz)));
+        float rad = a.r;
+        auto cand = [&](float x, float y, float z, int64_t s, int prow) {
+            if (s >= n || prow < 0 || !clr_finite3(x, y, z)) return;
+            const float ux = __fsub_rn(x, ax), uy = __fsub_rn(y, ay), uz = __fsub_rn(z, az);
+            const float dot = __fadd_rn(__fadd_rn(__fmul_rn(ux, ex), __fmul_rn(uy, ey)), __fmul_rn(uz, ez));
+            const float t = fminf(fmaxf(__fmul_rn(dot, inv), 0.f), 1.f);   // fmaxf(NaN, 0) = 0
+            const float qx = __fsub_rn(ux, __fmul_rn(t, ex)), qy = __fsub_rn(uy, __fmul_rn(t, ey)), qz = __fsub_rn(uz, __fmul_rn(t, ez));
+            const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(qx, qx), __fmul_rn(qy, qy)), __fmul_rn(qz, qz));
+            if (d2 < r2) {
+                const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)prow;
+                best = key < best ? key : best;
+            }
+        };
+        for (int base = 64 * wave; base < ntiles; base += 64 * TO_CLR_WAVES) {
+            const int tile = base + lane;
+            bool keep = false;
+            if (tile < ntiles) {
+                const float4 b = a.cv.bounds[tile];
+                if (!(clr_finite3(b.x, b.y, b.z) && isfinite(b.w))) {
+                    keep = true;
+                } else {
+                    const float ux = b.x - ax, uy = b.y - ay, uz = b.z - az;
+                    const float t = fminf(fmaxf((ux * ex + uy * ey + uz * ez) * inv, 0.f), 1.f);
+                    const float qx = ux - t * ex, qy = uy - t * ey, qz = uz - t * ez;
+                    const float dc = sqrtf(qx * qx + qy * qy + qz * qz);
+                    const float amax = fmaxf(ta, fmaxf(fmaxf(fabsf(b.x), fabsf(b.y)), fabsf(b.z)));
+                    // |c - segment| - R > rad, with room for the rounding of dc, of the sphere and of each point's d2; (a dc that is
+                    // not a number — an overflow — keeps the tile)
+                    keep = !(dc > (b.w + rad) * 1.0001f + 1e-5f * amax + 1e-6f);
+                }
+            }
+            unsigned long long kept = __ballot(keep);
+            if (!kept) continue;
+            while (kept) {
+                const int k = __ffsll((long long)kept) - 1;
+                kept &= kept - 1;
+                const int64_t p0 = (int64_t)(base + k) * 256 + 4 * lane;
+                const float4 x4 = *(const float4*)(X + p0), y4 = *(const float4*)(Y + p0), z4 = *(const float4*)(Z + p0);
+                const int4 i4 = *(const int4*)(a.cv.perm + p0);
+                cand(x4.x, y4.x, z4.x, p0, i4.x);
+                cand(x4.y, y4.y, z4.y, p0 + 1, i4.y);
+                cand(x4.z, y4.z, z4.z, p0 + 2, i4.z);
+                cand(x4.w, y4.w, z4.w, p0 + 3, i4.w);
+            }
+            best = clr_wave_min(best);   // uniform from here: the search radius shrinks to the best distance so far
+            if (best != ~0ull) rad = sqrtf(__uint_as_float((unsigned)(best >> 32)));
+        }
+        best = clr_wave_min(best);
+    }
+    if (lane == 0) sbest[wave] = best;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int k = 0; k < TO_CLR_WAVES; ++k) best = sbest[k] < best ? sbest[k] : best;
+    float dout = INFINITY, sout = 0.f;
+    int iout = -1;
+    double term = 0.0, g[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (best != ~0ull) {
+        const float d2 = __uint_as_float((unsigned)(best >> 32));
+        iout = (int)(unsigned)(best & 0xffffffffull);
+        const double d = sqrt((double)d2);
+        dout = (float)d;
+        const double h = (double)a.r - d;
+        term = h * h;
+        const int64_t slot = a.cv.inv[iout];
+        const float* P = a.cv.soa;
+        const double a3[3] = {(double)ax, (double)ay, (double)az}, b3[3] = {(double)bx, (double)by, (double)bz};
+        double e3[3], u3[3], v3[3], ee = 0.0, dot = 0.0, vv = 0.0;
+        for (int k = 0; k < 3; ++k) {
+            e3[k] = b3[k] - a3[k];
+            u3[k] = (double)P[k * a.cv.npad + slot] - a3[k];
+            ee += e3[k] * e3[k];
+            dot += u3[k] * e3[k];
+        }
+        const double t = ee > 0.0 ? fmin(fmax(dot / ee, 0.0), 1.0) : 0.0;
+        sout = (float)t;
+        for (int k = 0; k < 3; ++k) {
+            v3[k] = t * e3[k] - u3[k];   // c - x
+            vv += v3[k] * v3[k];
+        }
+        if (vv > 0.0) {
+            const double c = -2.0 * (double)a.weight * h / sqrt(vv);
+            for (int k = 0; k < 3; ++k) {
+                g[k] = c * (1.0 - t) * v3[k];
+                g[3 + k] = c * t * v3[k];
+            }
+        }
+    }
+    if (a.d) a.d[seg] = dout;
+    if (a.idx) a.idx[seg] = iout;
+    if (a.s) a.s[seg] = sout;
+    a.term[row] = term;
+    for (int k = 0; k < 6; ++k) a.part[6 * seg + k] = g[k];
+}
+
+// one thread per waypoint row: gradient row w = (float)(g_b of segment w - 1 + g_a of segment w), added in f64 in that order and
+// rounded once; the last waypoint of a trajectory starts no segment: its term is 0
+__global__ void __launch_bounds__(256) k_clearance_seg_rows(const double* __restrict__ part, int W, int64_t n_rows, double* __restrict__ term,
+                                                             float* __restrict__ grad) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= n_rows) return;
+    const int w = (int)(row % W);
+    const int64_t seg = row / W * (W - 1) + w;
+    if (w == W - 1) term[row] = 0.0;
+    if (!grad) return;
+    for (int k = 0; k < 3; ++k) {
+        const double gb = w > 0 ? part[6 * (seg - 1) + 3 + k] : 0.0, ga = w < W - 1 ? part[6 * seg + k] : 0.0;
+        grad[3 * row + k] = (float)(gb + ga);
+    }
+}
+
 // value = weight * sum of the n_seg terms of segment blockIdx.x (in order, f64), rounded to f32 — one thread per segment
 __global__ void k_clearance_value(const double* __restrict__ term, int64_t n_seg, float weight, float* __restrict__ value) {
     if (threadIdx.x == 0) value[blockIdx.x] = (float)clearance_sum(term + (int64_t)blockIdx.x * n_seg, n_seg, weight);
@@ -175,6 +326,71 @@ extern "C" int tohip_clearance(const void* packed, int64_t n_points, const float
     int rc = clearance_launch(packed, n_points, queries, n_queries, radius, weight, d, idx, term, grad, accumulate, st);
     if (rc != TOHIP_OK || !value) return rc;
     k_clearance_value<<<1, 64, 0, st>>>(term, n_queries, weight, value);
+    TO_HIP_CHECK_LAUNCH();
+    return TOHIP_OK;
+}
+
+// ---- 'segments' mode: the entry points -------------------------------------------------------------------------------------------
+static inline size_t clearance_seg_part_bytes(int64_t W, int64_t n_traj) { return align_up((size_t)(n_traj * (W - 1)) * 48, 256); }
+
+// the two launches behind every path that carries the swept term: the segment query, then the per-waypoint rows and terms
+static inline int clearance_seg_launch(const void* packed, int64_t n_points, const float* poses, int64_t W, int64_t n_traj, float r,
+                                       float weight, float* d, int* idx, float* s, double* term, double* part, float* grad, hipStream_t st) {
+    ClrSegArgs a;
+    a.cv = cloud_view(packed, n_points);
+    a.p = poses; a.W = (int)W; a.r = r; a.weight = weight;
+    a.d = d; a.idx = idx; a.s = s; a.term = term; a.part = part;
+    k_clearance_seg<<<(unsigned)(n_traj * (W - 1)), TO_CLR_WAVES * 64, 0, st>>>(a);
+    TO_HIP_CHECK_LAUNCH();
+    const int64_t rows = n_traj * W;
+    k_clearance_seg_rows<<<(unsigned)((rows + 255) / 256), 256, 0, st>>>(part, (int)W, rows, term, grad);
+    TO_HIP_CHECK_LAUNCH();
+    return TOHIP_OK;
+}
+
+// the scratch of a plan / run that carries the swept term: clearance_scratch_bytes' rows and terms at their offsets, then the
+// per-segment parts
+static inline size_t clearance_seg_scratch_bytes(int64_t W, int64_t n_traj) {
+    return clearance_scratch_bytes(W * n_traj) + clearance_seg_part_bytes(W, n_traj);
+}
+static inline double* clearance_seg_scratch_part(void* s, int64_t nq) { return (double*)((char*)s + clearance_scratch_bytes(nq)); }
+
+// the query of a plan / run in either mode into its clearance scratch (segments: TOHIP_TRAJ_CLEARANCE_SEGMENTS in its flags)
+static inline int clearance_scratch_launch(const void* packed, int64_t n_points, const float* poses, int64_t W, int64_t n_traj, float r,
+                                           float weight, bool segments, void* scratch, hipStream_t st) {
+    float* rows = clearance_scratch_grad(scratch);
+    double* term = clearance_scratch_term(scratch, W * n_traj);
+    if (!segments) return clearance_launch(packed, n_points, poses, W * n_traj, r, weight, nullptr, nullptr, term, rows, 0, st);
+    return clearance_seg_launch(packed, n_points, poses, W, n_traj, r, weight, nullptr, nullptr, nullptr, term,
+                                clearance_seg_scratch_part(scratch, W * n_traj), rows, st);
+}
+
+static inline bool clearance_seg_counts_ok(int64_t n_wps, int64_t n_traj) {
+    return n_wps >= 2 && n_traj >= 1 && n_wps <= (int64_t)INT32_MAX && n_traj <= (int64_t)INT32_MAX / n_wps;
+}
+
+extern "C" size_t tohip_clearance_segments_workspace_bytes(int64_t n_wps, int64_t n_traj) {
+    if (!clearance_seg_counts_ok(n_wps, n_traj)) return 0;
+    return align_up((size_t)(n_wps * n_traj) * 8, 256) + clearance_seg_part_bytes(n_wps, n_traj);
+}
+
+extern "C" size_t tohip_traj_clearance_segments_scratch_bytes(int64_t n_wps, int64_t n_traj) {
+    return clearance_seg_counts_ok(n_wps, n_traj) ? clearance_seg_scratch_bytes(n_wps, n_traj) : 0;
+}
+
+extern "C" int tohip_clearance_segments(const void* packed, int64_t n_points, const float* poses, int64_t n_wps, int64_t n_traj, float radius,
+                                        float weight, float* d, int32_t* idx, float* s, float* value, float* grad, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+    if (!packed || !poses || !d || !idx || !s || !workspace || n_points <= 0 || n_points > INT32_MAX || !clearance_seg_counts_ok(n_wps, n_traj) ||
+        !clearance_args_ok(radius, weight))
+        return TOHIP_EINVAL;
+    if (workspace_bytes < tohip_clearance_segments_workspace_bytes(n_wps, n_traj)) return TOHIP_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    double* term = (double*)workspace;
+    double* part = (double*)((char*)workspace + align_up((size_t)(n_wps * n_traj) * 8, 256));
+    int rc = clearance_seg_launch(packed, n_points, poses, n_wps, n_traj, radius, weight, d, idx, s, term, part, grad, st);
+    if (rc != TOHIP_OK || !value) return rc;
+    k_clearance_value<<<(unsigned)n_traj, 64, 0, st>>>(term, n_wps, weight, value);
     TO_HIP_CHECK_LAUNCH();
     return TOHIP_OK;
 }

@@ -259,8 +259,12 @@ class _Clearance(torch.autograd.Function):
     @staticmethod
     def forward(ctx, poses, model):
         rows = torch.empty((poses.shape[0], 3), dtype=torch.float32, device=poses.device)
-        _, _, value = ops.clearance(model._cloud, poses.detach(), model.clearance_radius, model.clearance_weight, grad=rows,
-                                    want_value=True)
+        if model.clearance_mode == "segments":
+            value = ops.clearance_segments(model._cloud, poses.detach(), model.clearance_radius, model.clearance_weight, grad=rows,
+                                           want_value=True)[3].reshape(())
+        else:
+            _, _, value = ops.clearance(model._cloud, poses.detach(), model.clearance_radius, model.clearance_weight, grad=rows,
+                                        want_value=True)
         ctx.save_for_backward(rows)
         return value
 
@@ -332,8 +336,8 @@ class _TrajLoss(torch.autograd.Function):
         clr_rows = clr_terms = None
         if model._clearance_on:   # every rank: all W waypoints, the whole cloud
             clr_rows = torch.empty((W, 3), dtype=torch.float32, device=p_all.device)
-            clr_terms = torch.empty(_lib.lib().tohip_clearance_workspace_bytes(W) // 8, dtype=torch.float64, device=p_all.device)
-            ops.clearance(model._cloud, p_all, model.clearance_radius, model.clearance_weight, grad=clr_rows, terms=clr_terms)
+            clr_terms = ops.clearance_terms(W, 1, model.clearance_mode, p_all.device)
+            ops.clearance_rows(model._cloud, p_all, model.clearance_radius, model.clearance_weight, model.clearance_mode, 1, clr_rows, clr_terms)
         terms, reg_sum, reg_terms = _regularizers(model, p_all, scalars, clr_terms)
         ctx.step, ctx.step_w, ctx.W = st, step_w, W
         ctx.set_materialize_grads(False)
@@ -398,7 +402,11 @@ class _LossPlan:
         c.reg_terms = self.reg_terms.data_ptr()
         self.clr_rows = None
         if model._clearance_on:   # the clearance term: its gradient rows (W,3) lead the plan's clearance scratch
-            cb = L.tohip_traj_clearance_scratch_bytes(W, 1)
+            if model.clearance_mode == "segments":   # the swept term: the flag bit and the larger scratch (rows and terms where they were)
+                c.flags |= ops.CLEARANCE_SEGMENTS
+                cb = L.tohip_traj_clearance_segments_scratch_bytes(W, 1)
+            else:
+                cb = L.tohip_traj_clearance_scratch_bytes(W, 1)
             self.clr_scratch = torch.empty(cb, dtype=torch.uint8, device=dev)
             self.clr_rows = self.clr_scratch[:12 * W].view(torch.float32).view(W, 3)
             c.clearance_radius, c.clearance_weight = float(model.clearance_radius), float(model.clearance_weight)
@@ -791,13 +799,16 @@ class ModelTraj(nn.Module):
                  device=torch.device('cuda'),
                  *, rig=None, shard=None, dense=False, occlusion=None, occlusion_limits=(1.0, 15.0), occlusion_refresh_every=1,
                  occlusion_refresh_tol=None, occlusion_check_every=5, n_points_global=None, cloud=None, fast_adam=False,
-                 clearance_radius=None, clearance_weight=0.0, prior_log_odds=None):
+                 clearance_radius=None, clearance_weight=0.0, prior_log_odds=None, clearance_mode='waypoints'):
         super().__init__()
         # the clearance term (clearance_kernels.hip): weight x sum over ALL waypoints of (r - d)^2, d = the distance to the nearest
-        # cloud point within r — it keeps the path off the cloud; weight 0 (the default): off, the reference's criterion as it is
+        # cloud point within r — it keeps the path off the cloud; weight 0 (the default): off, the reference's criterion as it is.
+        # clearance_mode 'segments': d = the distance from each SEGMENT between consecutive waypoints to its nearest point, so the
+        # straight line driven between two waypoints stays off the cloud as well
         self._clr_points_shard = shard is not None and shard.kind == "points"
         self._clr = (None, 0.0)
-        self.set_clearance(clearance_radius, clearance_weight)
+        self._clr_mode = "waypoints"
+        self.set_clearance(clearance_radius, clearance_weight, clearance_mode)
         assert wps_poses.dim() == wps_quats.dim()
         assert wps_poses.size()[1] == 3
         assert wps_quats.size()[1] == 4
@@ -889,13 +900,23 @@ class ModelTraj(nn.Module):
         if fast_adam:          # fast_adam=True here, optimizer.accelerate_torch_adam(True) or accelerate_torch_adam(opt) (nothing is hooked otherwise)
             accelerate_torch_adam(True)
 
-    def set_clearance(self, radius, weight):
-        """The clearance term's settings (both checked together: radius > 0 when weight > 0, both finite; ValueError otherwise).
-        Weight 0 switches the term off.  The next forward / optimiser run uses them."""
+    def set_clearance(self, radius, weight, mode=None):
+        """The clearance term's settings (checked together: radius > 0 when weight > 0, both finite, mode 'waypoints' or 'segments' —
+        None keeps the current one; ValueError otherwise).  Weight 0 switches the term off.  The next forward / optimiser run uses
+        them."""
         r, w = ops.check_clearance(radius, weight)
+        mode = ops.check_clearance_mode(self._clr_mode if mode is None else mode)
         if w > 0.0 and self._clr_points_shard:
             raise ValueError("the clearance term needs the whole cloud on every rank: not available with PointShard")
-        self._clr = (r if w > 0.0 else radius, w)
+        self._clr, self._clr_mode = (r if w > 0.0 else radius, w), mode
+
+    @property
+    def clearance_mode(self):
+        return self._clr_mode
+
+    @clearance_mode.setter
+    def clearance_mode(self, mode):
+        self.set_clearance(self._clr[0], self._clr[1], mode)
 
     @property
     def clearance_radius(self):
@@ -1099,7 +1120,7 @@ class ModelTraj(nn.Module):
         """The library-side description of this model for the one-call forward / backward (rebuilt when something it froze
         has changed: the weights of criterion, the mode, the initial trajectory, the number of waypoints)."""
         key = (step_w, float(self.smoothness_weight), float(self.traj_length_weight), self._flags, self.poses0.data_ptr(),
-               self.poses.shape[0], self._clearance_on, self.clearance_radius, self.clearance_weight)
+               self.poses.shape[0], self._clearance_on, self.clearance_radius, self.clearance_weight, self.clearance_mode)
         if self._plan_key != key:
             self._plan_obj, self._plan_key = _LossPlan(self, step_w), key
         return self._plan_obj
@@ -1171,7 +1192,7 @@ class ModelTraj(nn.Module):
 
         total = self.loss['vis'] + self.loss['l2'] + self.loss['length'] + self.loss['smooth']
         if self._clearance_on:
-            # keep the waypoints off the cloud (the term's query and gradient rows: one launch)
+            # keep the waypoints (clearance_mode 'segments': the segments between them) off the cloud — the term's query and gradient rows
             self.loss['clearance'] = _Clearance.apply(self.poses, self)
             total = total + self.loss['clearance']
         return total
@@ -1200,8 +1221,8 @@ class _TeamLoss(torch.autograd.Function):
         clr_rows = clr_terms = None
         if m0._clearance_on:
             clr_rows = torch.empty((B * W, 3), dtype=torch.float32, device=p_all.device)
-            clr_terms = torch.empty(_lib.lib().tohip_clearance_workspace_bytes(B * W) // 8, dtype=torch.float64, device=p_all.device)
-            ops.clearance(m0._cloud, p_all, m0.clearance_radius, m0.clearance_weight, grad=clr_rows, terms=clr_terms)
+            clr_terms = ops.clearance_terms(W, B, m0.clearance_mode, p_all.device)
+            ops.clearance_rows(m0._cloud, p_all, m0.clearance_radius, m0.clearance_weight, m0.clearance_mode, B, clr_rows, clr_terms)
         terms, total, reg = ops.team_loss(p_all, team._poses0, B, m0.smoothness_weight, m0.traj_length_weight, m0.eps, scalars,
                                           m0.clearance_weight, clr_terms)
         ctx.team, ctx.step, ctx.gen, ctx.step_w, ctx.W, ctx.n_eval, ctx.has_clr = team, st, st.ws.generation, step_w, W, n_eval, clr_rows is not None

@@ -398,6 +398,17 @@ def check_clearance(radius, weight):
     return r, w
 
 
+CLEARANCE_MODES = ("waypoints", "segments")
+CLEARANCE_SEGMENTS = 4   # TOHIP_TRAJ_CLEARANCE_SEGMENTS: the flag bit of tohip_traj_loss / tohip_traj_opt
+
+
+def check_clearance_mode(mode):
+    """The clearance term's mode: 'waypoints' (each waypoint's distance) or 'segments' (each segment's); ValueError otherwise."""
+    if mode not in CLEARANCE_MODES:
+        raise ValueError(f"clearance_mode must be one of {CLEARANCE_MODES}, got {mode!r}")
+    return mode
+
+
 def check_prior(prior, n, device=None, name="prior_log_odds"):
     """A log-odds prior for n points: an (n,) floating tensor, finite and >= 0 (on `device` when one is given) -> it as a contiguous
     float32 tensor; ValueError otherwise.  >= 0 is the model's own range (p is clipped at 1/2), where the integer reward sum is exact.
@@ -876,6 +887,54 @@ def clearance(cloud, positions, radius, weight=0.0, grad=None, accumulate=False,
         check(L.tohip_clearance(cloud.blob.data_ptr(), cloud.n, ptr(q), n, r, w, ptr(d), ptr(idx), ptr(value), ptr(grad),
                                 int(bool(accumulate)), ptr(terms), terms.numel() * 8, stream_ptr()), "tohip_clearance")
     return (d, idx, value) if want_value else (d, idx)
+
+
+def clearance_segments(cloud, poses, radius, weight=0.0, n_traj=1, grad=None, want_value=False, terms=None):
+    """tohip_clearance_segments: the nearest cloud point within `radius` of every segment between consecutive waypoints of each of the
+    n_traj equal-length trajectories laid end to end in `poses` (n_traj W, 3), W >= 2 -> (d (n_traj (W-1),) f32, +inf when none; idx
+    int32 caller rows, -1 when none; s f32: where along the segment the closest point lies, 0 = its first end[, value (n_traj,) f32 =
+    weight x sum (radius - d)^2 per trajectory]).  grad (n_traj W, 3) f32, optional: the term's per-waypoint gradient rows,
+    overwritten.  terms (optional): a float64 tensor of tohip_clearance_segments_workspace_bytes / 8 entries; its first n_traj W
+    receive the per-waypoint terms ((radius - d)^2 of the segment a waypoint starts, 0 for a trajectory's last)."""
+    _require_cuda(poses, "poses")
+    q = poses.detach().to(torch.float32).contiguous()
+    B = int(n_traj)
+    if q.dim() != 2 or q.shape[1] != 3 or B < 1 or q.shape[0] % B or q.shape[0] // B < 2:
+        raise ValueError(f"poses must be (n_traj W, 3) with W >= 2, got {tuple(q.shape)} for n_traj={n_traj}")
+    r, w = check_clearance(radius, weight)
+    L = _lib.lib()
+    n, dev = q.shape[0], q.device
+    W = n // B
+    d = torch.empty(n - B, dtype=torch.float32, device=dev)
+    idx = torch.empty(n - B, dtype=torch.int32, device=dev)
+    s = torch.empty(n - B, dtype=torch.float32, device=dev)
+    value = torch.empty(B, dtype=torch.float32, device=dev) if want_value else None
+    if terms is None:
+        terms = clearance_terms(W, B, "segments", dev)
+    if grad is not None and not (grad.is_contiguous() and grad.dtype == torch.float32 and tuple(grad.shape) == (n, 3)):
+        raise ValueError("grad must be a contiguous (n_traj W, 3) float32 tensor")
+    with torch.cuda.device(dev):
+        check(L.tohip_clearance_segments(cloud.blob.data_ptr(), cloud.n, ptr(q), W, B, r, w, ptr(d), ptr(idx), ptr(s), ptr(value), ptr(grad),
+                                         ptr(terms), terms.numel() * 8, stream_ptr()), "tohip_clearance_segments")
+    return (d, idx, s, value) if want_value else (d, idx, s)
+
+
+def clearance_terms(n_wps, n_traj, mode, device):
+    """The float64 buffer the clearance query of `mode` fills for n_traj trajectories of n_wps waypoints: the per-waypoint terms lead
+    it in either mode (what the step tails, the regularisers' kernel and the team calls read)."""
+    L = _lib.lib()
+    nbytes = (L.tohip_clearance_segments_workspace_bytes(n_wps, n_traj) if mode == "segments" else
+              L.tohip_clearance_workspace_bytes(n_wps * n_traj))
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def clearance_rows(cloud, poses, radius, weight, mode, n_traj, grad, terms):
+    """The clearance term of `mode` for n_traj trajectories laid end to end: its per-waypoint gradient rows into `grad` and terms into
+    `terms` (clearance_terms) — one launch for 'waypoints', two for 'segments'."""
+    if mode == "segments":
+        clearance_segments(cloud, poses, radius, weight, n_traj=n_traj, grad=grad, terms=terms)
+    else:
+        clearance(cloud, poses, radius, weight, grad=grad, terms=terms)
 
 
 def traj_step_stats(cloud, ws):

@@ -81,7 +81,11 @@ class _OptRun:
         c.scratch, c.scratch_bytes = self.scratch.data_ptr(), nbytes
         self.clearance = m0._clearance_on
         if self.clearance:   # the clearance term: one launch more per step, first (its rows join the regularisers')
-            cb = L.tohip_traj_clearance_scratch_bytes(W, B)
+            if m0.clearance_mode == "segments":   # the swept term: the segment query and its per-waypoint combine, two launches
+                c.flags |= ops.CLEARANCE_SEGMENTS
+                cb = L.tohip_traj_clearance_segments_scratch_bytes(W, B)
+            else:
+                cb = L.tohip_traj_clearance_scratch_bytes(W, B)
             self.clr_scratch = torch.empty(cb, dtype=torch.uint8, device=dev)
             c.clearance_radius, c.clearance_weight = float(m0.clearance_radius), float(m0.clearance_weight)
             c.clearance_scratch, c.clearance_scratch_bytes = self.clr_scratch.data_ptr(), cb
@@ -180,7 +184,7 @@ class _TailRun:
         self.clr, self.clr_args = m0._clearance_on, (0.0, None, None)
         if self.clr:   # the clearance query of all B W waypoints: its gradient rows and per-waypoint terms, consumed by the tail
             self.clr_rows = torch.empty((B * W, 3), **f32)
-            self.clr_terms = torch.empty(L.tohip_clearance_workspace_bytes(B * W) // 8, dtype=torch.float64, device=dev)
+            self.clr_terms = ops.clearance_terms(W, B, m0.clearance_mode, dev)
             self.clr_args = (float(m0.clearance_weight), ptr(self.clr_rows), ptr(self.clr_terms))
         self.st, self.weights = st, (float(m0.smoothness_weight), float(m0.traj_length_weight), float(m0.eps))
         self.tail_args = (ptr(poses), ptr(quats), ptr(self.poses0), W, B, ptr(st.pg), ptr(st.qg), n_eval, step_w, ptr(self.pg), ptr(self.qg),
@@ -197,7 +201,8 @@ class _TailRun:
                                                          ptr(self.src[0]), ptr(self.src[1]), stream_ptr()), "tohip_gather_waypoints_multi")
                 vis_step(*self.src, self.stride)
                 if self.clr:
-                    ops.clearance(self.cloud, self.poses, m0.clearance_radius, m0.clearance_weight, grad=self.clr_rows, terms=self.clr_terms)
+                    ops.clearance_rows(self.cloud, self.poses, m0.clearance_radius, m0.clearance_weight, m0.clearance_mode, self.B,
+                                       self.clr_rows, self.clr_terms)
                 check(tail(i), what)
 
     def finish(self, steps):
@@ -267,7 +272,8 @@ def _check_same_setup(models, vis_wps_dist, what):
         if (m._flags != m0._flags or (m._rig is None) != (rig is None) or bytes(m._cam.c) != bytes(cam.c) or
                 m.smoothness_weight != m0.smoothness_weight or m.traj_length_weight != m0.traj_length_weight or
                 m._clearance_on != m0._clearance_on or
-                (m0._clearance_on and (m.clearance_radius != m0.clearance_radius or m.clearance_weight != m0.clearance_weight))):
+                (m0._clearance_on and (m.clearance_radius != m0.clearance_radius or m.clearance_weight != m0.clearance_weight or
+                                       m.clearance_mode != m0.clearance_mode))):
             raise ValueError(f"{what}: the models must share the camera, rig, mode, weights and clearance settings")
         if m is not m0 and (m.device != m0.device or float(m.eps) != float(m0.eps)):
             raise ValueError(f"{what}: the models must live on one device and share eps")
