@@ -37,7 +37,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_clearance_segments / tohip_clearance_segments_workspace_bytes / tohip_traj_clearance_segments_scratch_bytes and
+/* (still 15) + tohip_clearance_edges / tohip_tour_bytes / tohip_tour_plan (a collision-checked tour through chosen views): new symbols
+ * only.
+ * (still 15) + tohip_clearance_segments / tohip_clearance_segments_workspace_bytes / tohip_traj_clearance_segments_scratch_bytes and
  * the flag bit TOHIP_TRAJ_CLEARANCE_SEGMENTS (the swept clearance term: the hinge on each segment's distance): new symbols and one
  * flag bit that was refused before — no struct and no existing signature changes.
  * (still 15) + tohip_covmap_bytes / tohip_covmap_init / tohip_covmap_integrate / tohip_covmap_lookup / tohip_covmap_merge /
@@ -732,6 +734,39 @@ int tohip_clearance_segments(const void *packed, int64_t n_points, const float *
 /* bytes of clearance_scratch with TOHIP_TRAJ_CLEARANCE_SEGMENTS: tohip_traj_clearance_scratch_bytes' rows and terms at the same
  * offsets, then the per-segment g_a, g_b */
 size_t tohip_traj_clearance_segments_scratch_bytes(int64_t n_wps, int64_t n_traj);
+
+/* The same segment query for n_edges UNRELATED segments: edge e joins a[e] and b[e] (two (n_edges, 3) device arrays).  d, idx, s
+ * (n_edges each; any of them may be NULL) are bit for bit what tohip_clearance_segments writes for a trajectory of the two waypoints
+ * a[e], b[e] — the definition above — without the term and its gradient.  One wave per edge, four edges to a block (the 16-wave block
+ * per segment above is sized for the hundred segments of a path, this for the tens of thousands of pairs of a node set); a sorted or
+ * an unsorted packed cloud; no atomics: the results do not depend on the launch.  radius > 0 and finite.  One launch. */
+int tohip_clearance_edges(const void *packed, int64_t n_points, const float *a, const float *b, int64_t n_edges, float radius, float *d,
+                          int32_t *idx, float *s, void *stream);
+
+/* ---- a collision-checked tour through chosen views (tour_kernels.hip) ----------------------------------------------
+ * nodes (n, 3) f32 on the device, 2 <= n <= TOHIP_TOUR_MAX_NODES; node 0 is where the tour starts.  Edge (i, j), i < j, has the index
+ * e = i n - i (i + 1) / 2 + (j - i - 1) (the upper triangle, row-major) and is OPEN iff both ends are finite and edge_idx[e] == -1 —
+ * edge_idx: the idx of tohip_clearance_edges for a = node i, b = node j (n (n - 1) / 2 int32), or NULL: every edge between finite nodes
+ * — and its length fits.  Lengths are integers in units of 2^-20 m: in f64 without contraction dx = (double)x_i - (double)x_j ...,
+ * w_ij = llrint(sqrt((dx dx + dy dy) + dz dz) 2^20); an edge with w_ij > 2^40 is closed.
+ * Closure: D (n, n) int64 = w_ij on open edges, 0 on the diagonal, INF = 2^62 elsewhere; nxt (n, n) int32 = j on open edges, -1
+ * elsewhere; Floyd-Warshall with k ascending: when D[i][k] + D[k][j] < D[i][j] strictly and both terms are below INF, D[i][j] = the
+ * sum and nxt[i][j] = nxt[i][k] (one launch per k, one thread per (i, j): row and column k do not change during iteration k, so the
+ * sweep is the serial loop).  R = {j : D[0][j] < INF}, m = |R|.  Start order: t[0] = 0, then repeatedly the unvisited j in R with the
+ * smallest D[t[last]][j], ties to the lowest j; its length (with closed != 0: back to node 0 included) is nn_length_fixed.
+ * 2-opt, best improvement, position 0 fixed: for 1 <= i < j <= m - 1 reversing t[i..j] changes the length by D[t[i-1]][t[j]] +
+ * D[t[i]][t[j+1]] - D[t[i-1]][t[i]] - D[t[j]][t[j+1]] (closed: t[m] = t[0]; open and j = m - 1: the two terms that name t[m] are
+ * dropped); the move with the most negative change is applied, ties to the lowest i and then the lowest j, until no change is
+ * negative (converged = 1) or max_moves moves are done (converged says whether a negative change is left).
+ * buf (tohip_tour_bytes(n) device bytes, caller-owned, 256-byte aligned), every section aligned to 256 bytes: [header 32 x int64:
+ * [0] m [1] moves [2] converged [3] length_fixed [4] nn_length_fixed [5] status — bit 0: node 0 has a non-finite coordinate (m = 1)]
+ * [order n int32: the first m count, -1 behind them] [unreachable n uint8] [D n x n int64] [nxt n x n int32].  The walk from u to v
+ * is u, nxt[u][v], nxt[nxt[u][v]][v], ..., v.  n + 2 launches, nothing synchronises; integers throughout: the same bits in every run.
+ * tohip_tour_bytes: 0 for an n out of range. */
+#define TOHIP_TOUR_MAX_NODES 256
+size_t tohip_tour_bytes(int64_t n);
+int tohip_tour_plan(const float *nodes, int64_t n, const int32_t *edge_idx, int closed, int64_t max_moves, void *buf, size_t bytes,
+                    void *stream);
 
 /* ---- input formats (pointcloud_utils.py, launch/voxels_filtering.launch) --------------------------------
  * PointCloud2 payload -> (N,3) f32 with non-finite rows removed, in message order

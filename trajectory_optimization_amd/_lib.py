@@ -202,6 +202,9 @@ SIGNATURES = {
     "tohip_clearance_segments_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "tohip_clearance_segments": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_f, c_f, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "tohip_traj_clearance_segments_scratch_bytes": (c_sz, [c_i64, c_i64]),
+    "tohip_clearance_edges": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_f, c_vp, c_vp, c_vp, c_vp]),
+    "tohip_tour_bytes": (c_sz, [c_i64]),
+    "tohip_tour_plan": (ctypes.c_int, [c_vp, c_i64, c_vp, ctypes.c_int, c_i64, c_vp, c_sz, c_vp]),
     "tohip_gather_waypoints": (ctypes.c_int, [c_vp, c_vp, c_i64, ctypes.c_int, c_vp, c_vp, c_vp]),
     "tohip_rows_strided": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
     "tohip_adam_step": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_f, c_f, c_f, c_i32, c_vp, c_vp]),

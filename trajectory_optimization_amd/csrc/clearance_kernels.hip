@@ -394,3 +394,125 @@ extern "C" int tohip_clearance_segments(const void* packed, int64_t n_points, co
     TO_HIP_CHECK_LAUNCH();
     return TOHIP_OK;
 }
+
+// ---- arbitrary segments, one WAVE each: the edge stage of tools.plan_tour (tour_kernels.hip) -----------------------------------
+// tohip_clearance_segments with n_wps = 2 answers E unrelated segments with E blocks of 16 waves; all pairs of 257 nodes are 32 896 of
+// them, far more than the chip has room for at once, so the 16 waves of a block buy no latency and cost a block-wide fold each.  Here
+// a wave owns an edge (TO_EDGE_WAVES edges to a block, no LDS, no barrier): its lanes stride over ALL the tile spheres with
+// k_clearance_seg's inequality, it scans the kept tiles of each group of 64 four points per lane and shrinks the radius after each
+// group.  The key, the per-point arithmetic and the f64 finish are k_clearance_seg's, so (d, idx, s) are its bits for the same two
+// ends: the prune only ever drops tiles that hold no point within the current radius, whatever the order the tiles are met in.
+#define TO_EDGE_WAVES 4
+
+struct ClrEdgeArgs {
+    CloudView cv;
+    const float* a;        // (E, 3) first ends
+    const float* b;        // (E, 3) second ends
+    int64_t E;
+    float r;
+    float* d;              // may be NULL: (E) distance, +inf when no point is within r
+    int* idx;              // may be NULL: (E) caller row of the nearest point, -1 when none
+    float* s;              // may be NULL: (E) where along the edge the closest point lies
+};
+
+__global__ void __launch_bounds__(TO_EDGE_WAVES * 64) k_clearance_edge(ClrEdgeArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t e = (int64_t)blockIdx.x * TO_EDGE_WAVES + (threadIdx.x >> 6);
+    if (e >= a.E) return;   // (wave-uniform)
+    const float ax = a.a[3 * e], ay = a.a[3 * e + 1], az = a.a[3 * e + 2];
+    const float bx = a.b[3 * e], by = a.b[3 * e + 1], bz = a.b[3 * e + 2];
+    const float r2 = __fmul_rn(a.r, a.r);
+    unsigned long long best = ~0ull;
+    if (clr_finite3(ax, ay, az) && clr_finite3(bx, by, bz)) {
+        const int64_t npad = a.cv.npad, n = a.cv.n;
+        const int ntiles = (int)(npad / 256);
+        const float* X = a.cv.soa;
+        const float* Y = X + npad;
+        const float* Z = Y + npad;
+        const float ex = __fsub_rn(bx, ax), ey = __fsub_rn(by, ay), ez = __fsub_rn(bz, az);
+        const float ee = __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez));
+        const float inv = ee > 0.f ? __fdiv_rn(1.f, ee) : 0.f;
+        const float ta = fmaxf(fmaxf(fmaxf(fabsf(ax), fabsf(ay)), fabsf(az)), fmaxf(fmaxf(fabsf(bx), fabsf(by)), fabsf(bz)));
+        float rad = a.r;
+        auto cand = [&](float x, float y, float z, int64_t s, int prow) {
+            if (s >= n || prow < 0 || !clr_finite3(x, y, z)) return;
+            const float ux = __fsub_rn(x, ax), uy = __fsub_rn(y, ay), uz = __fsub_rn(z, az);
+            const float dot = __fadd_rn(__fadd_rn(__fmul_rn(ux, ex), __fmul_rn(uy, ey)), __fmul_rn(uz, ez));
+            const float t = fminf(fmaxf(__fmul_rn(dot, inv), 0.f), 1.f);   // fmaxf(NaN, 0) = 0
+            const float qx = __fsub_rn(ux, __fmul_rn(t, ex)), qy = __fsub_rn(uy, __fmul_rn(t, ey)), qz = __fsub_rn(uz, __fmul_rn(t, ez));
+            const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(qx, qx), __fmul_rn(qy, qy)), __fmul_rn(qz, qz));
+            if (d2 < r2) {
+                const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)prow;
+                best = key < best ? key : best;
+            }
+        };
+        for (int base = 0; base < ntiles; base += 64) {
+            const int tile = base + lane;
+            bool keep = false;
+            if (tile < ntiles) {
+                const float4 b = a.cv.bounds[tile];
+                if (!(clr_finite3(b.x, b.y, b.z) && isfinite(b.w))) {
+                    keep = true;
+                } else {
+                    const float ux = b.x - ax, uy = b.y - ay, uz = b.z - az;
+                    const float t = fminf(fmaxf((ux * ex + uy * ey + uz * ez) * inv, 0.f), 1.f);
+                    const float qx = ux - t * ex, qy = uy - t * ey, qz = uz - t * ez;
+                    const float dc = sqrtf(qx * qx + qy * qy + qz * qz);
+                    const float amax = fmaxf(ta, fmaxf(fmaxf(fabsf(b.x), fabsf(b.y)), fabsf(b.z)));
+                    keep = !(dc > (b.w + rad) * 1.0001f + 1e-5f * amax + 1e-6f);   // k_clearance_seg's inequality
+                }
+            }
+            unsigned long long kept = __ballot(keep);
+            if (!kept) continue;
+            while (kept) {
+                const int k = __ffsll((long long)kept) - 1;
+                kept &= kept - 1;
+                const int64_t p0 = (int64_t)(base + k) * 256 + 4 * lane;   // base + k < ntiles: only lanes with tile < ntiles vote
+                const float4 x4 = *(const float4*)(X + p0), y4 = *(const float4*)(Y + p0), z4 = *(const float4*)(Z + p0);
+                const int4 i4 = *(const int4*)(a.cv.perm + p0);
+                cand(x4.x, y4.x, z4.x, p0, i4.x);
+                cand(x4.y, y4.y, z4.y, p0 + 1, i4.y);
+                cand(x4.z, y4.z, z4.z, p0 + 2, i4.z);
+                cand(x4.w, y4.w, z4.w, p0 + 3, i4.w);
+            }
+            best = clr_wave_min(best);   // uniform from here: the search radius shrinks to the best distance so far
+            if (best != ~0ull) rad = sqrtf(__uint_as_float((unsigned)(best >> 32)));
+        }
+        best = clr_wave_min(best);
+    }
+    if (lane != 0) return;
+    float dout = INFINITY, sout = 0.f;
+    int iout = -1;
+    if (best != ~0ull) {   // k_clearance_seg's finish, without the term and the gradient
+        const float d2 = __uint_as_float((unsigned)(best >> 32));
+        iout = (int)(unsigned)(best & 0xffffffffull);
+        dout = (float)sqrt((double)d2);
+        const int64_t slot = a.cv.inv[iout];
+        const float* P = a.cv.soa;
+        const double a3[3] = {(double)ax, (double)ay, (double)az}, b3[3] = {(double)bx, (double)by, (double)bz};
+        double ee = 0.0, dot = 0.0;
+        for (int k = 0; k < 3; ++k) {
+            const double ek = b3[k] - a3[k], uk = (double)P[k * a.cv.npad + slot] - a3[k];
+            ee += ek * ek;
+            dot += uk * ek;
+        }
+        sout = (float)(ee > 0.0 ? fmin(fmax(dot / ee, 0.0), 1.0) : 0.0);
+    }
+    if (a.d) a.d[e] = dout;
+    if (a.idx) a.idx[e] = iout;
+    if (a.s) a.s[e] = sout;
+}
+
+extern "C" int tohip_clearance_edges(const void* packed, int64_t n_points, const float* a, const float* b, int64_t n_edges, float radius,
+                                     float* d, int32_t* idx, float* s, void* stream) {
+    if (!packed || !a || !b || n_points <= 0 || n_points > INT32_MAX || n_edges <= 0 || n_edges > (int64_t)INT32_MAX ||
+        !clearance_args_ok(radius, 0.f))
+        return TOHIP_EINVAL;
+    ClrEdgeArgs g;
+    g.cv = cloud_view(packed, n_points);
+    g.a = a; g.b = b; g.E = n_edges; g.r = radius;
+    g.d = d; g.idx = idx; g.s = s;
+    k_clearance_edge<<<(unsigned)((n_edges + TO_EDGE_WAVES - 1) / TO_EDGE_WAVES), TO_EDGE_WAVES * 64, 0, (hipStream_t)stream>>>(g);
+    TO_HIP_CHECK_LAUNCH();
+    return TOHIP_OK;
+}

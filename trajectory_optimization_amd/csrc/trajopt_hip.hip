@@ -11,6 +11,7 @@
 #include "optim_kernels.hip"
 #include "team_kernels.hip"
 #include "views_kernels.hip"
+#include "tour_kernels.hip"
 #include "covmap_kernels.hip"
 #include "loss_kernels.hip"
 #include "ingest_kernels.hip"

@@ -919,6 +919,103 @@ def clearance_segments(cloud, poses, radius, weight=0.0, n_traj=1, grad=None, wa
     return (d, idx, s, value) if want_value else (d, idx, s)
 
 
+def clearance_edges(cloud, a, b, radius):
+    """tohip_clearance_edges: the nearest cloud point within `radius` of each of the E unrelated segments a[e] -> b[e] (two (E,3)
+    tensors on the cloud's device) -> (d (E,) f32, +inf when none; idx (E,) int32 caller rows, -1 when none; s (E,) f32) — the bits
+    clearance_segments gives for the same two ends.  One wave per edge, one launch."""
+    _require_cuda(a, "a")
+    _require_cuda(b, "b")
+    a = a.detach().to(torch.float32).contiguous()
+    b = b.detach().to(torch.float32).contiguous()
+    if a.dim() != 2 or a.shape[1] != 3 or a.shape[0] == 0 or b.shape != a.shape:
+        raise ValueError(f"a and b must both be (E,3) with E > 0, got {tuple(a.shape)} and {tuple(b.shape)}")
+    r = check_tour_radius(radius)
+    E, dev = a.shape[0], a.device
+    d = torch.empty(E, dtype=torch.float32, device=dev)
+    idx = torch.empty(E, dtype=torch.int32, device=dev)
+    s = torch.empty(E, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().tohip_clearance_edges(cloud.blob.data_ptr(), cloud.n, ptr(a), ptr(b), E, r, ptr(d), ptr(idx), ptr(s), stream_ptr()),
+              "tohip_clearance_edges")
+    return d, idx, s
+
+
+TOUR_MAX_NODES = 256   # TOHIP_TOUR_MAX_NODES
+TOUR_UNIT = 2.0 ** -20   # metres per unit of a tour's integer lengths
+
+
+def check_tour_radius(radius):
+    """A clearance radius that is given: a finite number > 0 (ValueError otherwise)."""
+    try:
+        r = float(radius)
+    except (TypeError, ValueError):
+        r = float("nan")
+    if not (np.isfinite(r) and r > 0.0):
+        raise ValueError(f"clearance_radius must be a finite number > 0, got {radius!r}")
+    return r
+
+
+def check_tour(poses, quats=None, clearance_radius=None, closed=False, max_moves=None):
+    """The arguments of a tour: poses (n,3) a floating tensor with 2 <= n <= TOUR_MAX_NODES, quats None or (n,4), clearance_radius
+    None or a finite number > 0, max_moves None (4 n) or an integer >= 0 -> (n, radius or None, max_moves); ValueError otherwise."""
+    if not torch.is_tensor(poses) or not poses.is_floating_point() or poses.dim() != 2 or poses.shape[1] != 3:
+        raise ValueError(f"poses must be a floating-point tensor of shape (n,3), got "
+                         f"{tuple(poses.shape) if torch.is_tensor(poses) else type(poses).__name__}")
+    n = poses.shape[0]
+    if n < 2:
+        raise ValueError(f"poses must hold n >= 2 nodes (the start and at least one view), got {n}")
+    if n > TOUR_MAX_NODES:
+        raise ValueError(f"poses must hold at most {TOUR_MAX_NODES} nodes, got n = {n}")
+    if quats is not None and (not torch.is_tensor(quats) or not quats.is_floating_point() or tuple(quats.shape) != (n, 4)):
+        raise ValueError(f"quats must be None or a floating-point tensor of shape ({n},4), got "
+                         f"{tuple(quats.shape) if torch.is_tensor(quats) else type(quats).__name__}")
+    r = check_tour_radius(clearance_radius) if clearance_radius is not None else None
+    if not isinstance(closed, (bool, np.bool_)):
+        raise ValueError(f"closed must be True or False, got {closed!r}")
+    if max_moves is None:
+        max_moves = 4 * n
+    elif isinstance(max_moves, bool) or not isinstance(max_moves, (int, np.integer)) or max_moves < 0:
+        raise ValueError(f"max_moves must be None or an integer >= 0, got {max_moves!r}")
+    return n, r, int(max_moves)
+
+
+def tour_layout(n):
+    """Byte offsets of a tour buffer's sections (include/trajopt_hip.h, tohip_tour_bytes): every section aligned to 256 bytes."""
+    up = lambda v: (v + 255) // 256 * 256
+    out, o = {"header": 0}, 256
+    for name, nbytes in (("order", 4 * n), ("unreachable", n), ("D", 8 * n * n), ("nxt", 4 * n * n)):
+        out[name] = o
+        o += up(nbytes)
+    out["total"] = o
+    return out
+
+
+def tour_edge_ends(n, device):
+    """(i, j): the ends of the n (n - 1) / 2 edges in the order of their indices (the upper triangle, row-major)."""
+    ij = torch.triu_indices(n, n, offset=1, device=device)
+    return ij[0], ij[1]
+
+
+def tour_plan(nodes, edge_idx=None, closed=False, max_moves=None):
+    """tohip_tour_plan over nodes (n,3) f32 on the device and the edge stage's idx (n (n - 1) / 2 int32) or None -> the tour buffer
+    (uint8, tour_layout(n)) on the device; launches only."""
+    _require_cuda(nodes, "nodes")
+    n = nodes.shape[0]
+    L = _lib.lib()
+    nbytes = L.tohip_tour_bytes(n)
+    if nbytes == 0 or tuple(nodes.shape) != (n, 3) or nodes.dtype != torch.float32 or not nodes.is_contiguous():
+        raise ValueError(f"nodes must be a contiguous (n,3) float32 tensor with 2 <= n <= {TOUR_MAX_NODES}, got {tuple(nodes.shape)}")
+    if edge_idx is not None and not (edge_idx.dtype == torch.int32 and edge_idx.is_contiguous() and edge_idx.numel() == n * (n - 1) // 2
+                                     and edge_idx.device == nodes.device):
+        raise ValueError(f"edge_idx must be {n * (n - 1) // 2} contiguous int32 on the nodes' device")
+    assert nbytes == tour_layout(n)["total"]
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=nodes.device)
+    with torch.cuda.device(nodes.device):
+        check(L.tohip_tour_plan(ptr(nodes), n, ptr(edge_idx), int(bool(closed)), int(4 * n if max_moves is None else max_moves), ptr(buf),
+                                nbytes, stream_ptr()), "tohip_tour_plan")
+    return buf
+
+
 def clearance_terms(n_wps, n_traj, mode, device):
     """The float64 buffer the clearance query of `mode` fills for n_traj trajectories of n_wps waypoints: the per-waypoint terms lead
     it in either mode (what the step tails, the regularisers' kernel and the team calls read)."""

@@ -102,3 +102,107 @@ def with_duplicate_rows(base, dup, seed):
     order = np.random.default_rng(seed).permutation(len(src))
     src = src[order]
     return base[src].astype(np.float32), src
+
+
+# ---- tools.plan_tour restated in numpy: what tour_kernels.hip must give, element for element ------------------------
+TOUR_INF = 1 << 62
+TOUR_MAX_LEN = 1 << 40
+
+
+def tour_edge_lengths(P):
+    """w (n,n) int64: llrint(|P_i - P_j| 2^20) in f64, the differences taken lower index minus higher; -1 where an end is not finite
+    or the length exceeds 2^40."""
+    P = np.asarray(P, dtype=np.float32)
+    n = len(P)
+    lo, hi = np.minimum.outer(np.arange(n), np.arange(n)), np.maximum.outer(np.arange(n), np.arange(n))
+    fin = np.isfinite(P).all(axis=1)
+    Pd = np.where(fin[:, None], P, 0).astype(np.float64)
+    d = Pd[lo] - Pd[hi]
+    L = np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]) * 1048576.0
+    w = np.rint(np.minimum(L, float(1 << 42))).astype(np.int64)
+    w[(w > TOUR_MAX_LEN) | ~fin[lo] | ~fin[hi]] = -1
+    return w
+
+
+def tour_two_opt_changes(D, t, closed):
+    """(m,m) int64: entry (i, j), 1 <= i < j <= m - 1, is what reversing t[i..j] adds to the length; 0 elsewhere."""
+    m = len(t)
+    out = np.zeros((m, m), dtype=np.int64)
+    if m < 3:
+        return out
+    t = np.asarray(t)
+    tn = np.append(t, t[0])
+    i, j = np.triu_indices(m, 1)
+    keep = i >= 1
+    i, j = i[keep], j[keep]
+    has_next = np.full(len(i), True) if closed else j + 1 < m
+    d = D[tn[i - 1], tn[j]] - D[tn[i - 1], tn[i]]
+    d = d + np.where(has_next, D[tn[i], tn[j + 1]] - D[tn[j], tn[j + 1]], 0)
+    out[i, j] = d
+    return out
+
+
+def tour_plan(P, blocked=None, closed=False, max_moves=None):
+    """The whole definition: P (n,3) f32 nodes (node 0 the start), blocked (n,n) bool or None (the pairs whose segment query found a
+    point; symmetric) -> dict(order, m, unreachable, length_fixed, nn_length_fixed, moves, converged, D, nxt, w, walk).  Floyd-Warshall
+    is vectorised per k and 2-opt per move, all in int64."""
+    P = np.asarray(P, dtype=np.float32)
+    n = len(P)
+    max_moves = 4 * n if max_moves is None else int(max_moves)
+    w = tour_edge_lengths(P)
+    opened = w >= 0
+    if blocked is not None:
+        opened &= ~np.asarray(blocked, dtype=bool)
+    np.fill_diagonal(opened, False)
+    D = np.where(opened, w, TOUR_INF).astype(np.int64)
+    np.fill_diagonal(D, 0)
+    nxt = np.where(opened, np.arange(n)[None, :], -1).astype(np.int32)
+    for k in range(n):
+        a, b = D[:, k:k + 1], D[k:k + 1, :]
+        s = a + b   # (below 2^63: both terms are at most 2^62)
+        better = (a < TOUR_INF) & (b < TOUR_INF) & (s < D)
+        D = np.where(better, s, D)
+        nxt = np.where(better, nxt[:, k:k + 1], nxt)
+    reach = D[0] < TOUR_INF
+    m = int(reach.sum())
+    t, left = [0], reach.copy()
+    left[0] = False
+    nn = 0
+    while len(t) < m:
+        row = np.where(left, D[t[-1]], np.iinfo(np.int64).max)
+        j = int(np.argmin(row))   # the first minimum: ties to the lowest j
+        nn += int(row[j])
+        t.append(j)
+        left[j] = False
+    if closed and m > 1:
+        nn += int(D[t[-1], 0])
+    length, moves = nn, 0
+    while True:
+        ch = tour_two_opt_changes(D, t, closed)
+        best = int(ch.min())
+        if best >= 0:
+            converged = True
+            break
+        if moves >= max_moves:
+            converged = False
+            break
+        i, j = np.unravel_index(int(np.argmin(ch)), ch.shape)   # row-major first minimum: lowest i, then lowest j
+        t[i:j + 1] = t[i:j + 1][::-1]
+        length += best
+        moves += 1
+    order = np.full(n, -1, dtype=np.int32)
+    order[:m] = t
+    return dict(order=order, m=m, unreachable=~reach, length_fixed=length, nn_length_fixed=nn, moves=moves, converged=converged, D=D,
+                nxt=nxt, w=w, walk=tour_walk(t, nxt, closed))
+
+
+def tour_walk(order, nxt, closed):
+    """The order with the pass-through nodes inserted: u, nxt[u][v], ..., v for consecutive u, v (and back to node 0 when closed)."""
+    stops = [int(v) for v in order] + ([int(order[0])] if closed and len(order) > 1 else [])
+    walk = [stops[0]]
+    for v in stops[1:]:
+        u = walk[-1]
+        while u != v:
+            u = int(nxt[u][v])
+            walk.append(u)
+    return walk

@@ -341,3 +341,126 @@ def select_views(model_or_cloud, cand_poses, cand_quats, k, prior_log_odds=None,
     return ViewSelection(order=sel, gain_fixed=gfix, gains=gfix.to(torch.float64) / float(2 ** shift) / cloud.n, poses=ps[idx], quats=qs[idx],
                          rewards=rewards, mean_reward=float(scalars[0]), coverage_log_odds=coverage, nnz=int(h[0]), absent=absent.cpu(),
                          log_odds=S)
+
+
+def _clearance_cloud(points_or_cloud_or_model, what):
+    """The packed cloud behind a clearance query's first argument: a ModelTraj (its cloud), an ops.PackedCloud (sorted or not) or
+    (N,3) points (packed here) — checked, nothing launched: -> (cloud or None, points or None)."""
+    c = points_or_cloud_or_model
+    if hasattr(c, "_cloud") and hasattr(c, "_shard"):
+        if c._shard.kind == "points" or c._shard.world_size > 1 or c._shard.collective:
+            raise ValueError(f"{what}: a sharded model (WaypointShard / PointShard) is not supported")
+        c = c._cloud
+    if isinstance(c, ops.PackedCloud):
+        return c, None
+    if not torch.is_tensor(c) or c.dim() != 2 or c.shape[1] != 3 or c.shape[0] == 0:
+        raise ValueError(f"{what}: points must be an (N,3) tensor with N > 0, a PackedCloud or a ModelTraj, got "
+                         f"{tuple(c.shape) if torch.is_tensor(c) else type(c).__name__}")
+    return None, c
+
+
+def edge_clearance(points_or_cloud_or_model, a, b, radius):
+    """How far each straight segment a[e] -> b[e] is from the cloud: (d, idx, s) on the device, (E,) each — trajectory_clearance's
+    segment query (segments=True) for E unrelated segments: d f32 the distance to the nearest point within `radius` (+inf when
+    none), idx int32 that point's row in the caller's order (-1 when none, or an end that is not finite), s f32 where along the
+    segment its closest point lies.  The same bits as the query over the two-waypoint path a[e], b[e]."""
+    cloud, pts = _clearance_cloud(points_or_cloud_or_model, "edge_clearance")
+    a, b = torch.as_tensor(a, dtype=torch.float32), torch.as_tensor(b, dtype=torch.float32)
+    if a.dim() != 2 or a.shape[1] != 3 or a.shape[0] == 0 or b.shape != a.shape:
+        raise ValueError(f"edge_clearance: a and b must both be (E,3) with E > 0, got {tuple(a.shape)} and {tuple(b.shape)}")
+    r = ops.check_tour_radius(radius)
+    if cloud is None:
+        cloud = ops.PackedCloud(pts.to(torch.float32))
+    return ops.clearance_edges(cloud, a.to(cloud.device), b.to(cloud.device), r)
+
+
+class Tour:
+    """What plan_tour returns.  order (m,) int64 on the host: the reachable nodes in visiting order, order[0] == 0; unreachable (n,)
+    bool; walk: the list of node indices actually travelled — the order with the nodes a leg passes through inserted (and the way
+    back to node 0 when closed); poses / quats: the walk's rows on the device (a pass-through node keeps its own quaternion; quats is
+    None when none were given), ready for ModelTraj.sharing_cloud_of; length / nn_length: the walk's length and the nearest-neighbour
+    start's, metres in f64 from the integer sums length_fixed / nn_length_fixed (units of 2^-20 m); moves, converged: the 2-opt
+    moves made and whether no improving move is left; blocked (n,n) bool on the host: the pairs whose straight leg comes within the
+    clearance radius of the cloud; edge_distance (n,n) f32 on the device: that leg's distance to the cloud, +inf where it keeps the
+    radius (and on the diagonal); D (n,n) int64 / nxt (n,n) int32 on the host: the shortest open route between every two nodes and
+    its first step."""
+    __slots__ = ("order", "unreachable", "walk", "poses", "quats", "length", "nn_length", "length_fixed", "nn_length_fixed", "moves",
+                 "converged", "blocked", "edge_distance", "D", "nxt")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def tour_edge_stage(cloud, n_edges):
+    """Which of the two edge stages answers n_edges segments over `cloud` sooner — the same bits either way.  'segments': one 16-wave
+    block per edge (tohip_clearance_segments over two-waypoint paths), about 25 ns per edge whatever the cloud; 'edges': one wave per
+    edge (tohip_clearance_edges), 4 to 13 ns per edge behind a floor of one wave's walk over all tile spheres, 64 at a time.  Measured
+    crossings (tools/time_tour.py --sweep): about 1 100 edges on the bundled cloud (159 tiles), about 5 600 at 1 M
+    points (4 096 tiles)."""
+    return "edges" if n_edges >= 1024 + 64 * -(-cloud.npad // 16384) else "segments"
+
+
+def tour_edge_query(cloud, nodes, radius, stage=None):
+    """(d, idx, s) of every edge i < j of `nodes` (n,3) in edge-index order (the upper triangle, row-major) through one of the two
+    edge stages (stage=None: tour_edge_stage's choice)."""
+    i, j = ops.tour_edge_ends(nodes.shape[0], nodes.device)
+    a, b = nodes[i], nodes[j]
+    if (stage or tour_edge_stage(cloud, a.shape[0])) == "edges":
+        return ops.clearance_edges(cloud, a, b, radius)
+    return ops.clearance_segments(cloud, torch.stack([a, b], dim=1).reshape(-1, 3), radius, n_traj=a.shape[0])
+
+
+def plan_tour(points_or_cloud_or_model, poses, quats=None, clearance_radius=None, closed=False, max_moves=None):
+    """A short visiting order through view poses whose every straight leg keeps clearance_radius from the cloud.
+    poses (n,3), 2 <= n <= 256: row 0 is where the tour starts (the robot), the others are the views (select_views' sel.poses);
+    quats (n,4) or None.  Every pair of nodes is put to the swept clearance query (edge_clearance); the pairs it finds nothing near
+    are the open legs.  Shortest open routes between all nodes (Floyd-Warshall), a nearest-neighbour order from node 0 over them and
+    best-improvement 2-opt (at most max_moves moves, default 4 n; 0: the nearest-neighbour order) run on the device in integer
+    arithmetic — lengths in units of 2^-20 m — so every run gives the same tour.  Where the direct leg is blocked the walk passes
+    through other nodes; nodes no open route reaches are reported in `unreachable` and left out.  closed=True: the tour returns to
+    node 0.  clearance_radius=None: no query, every leg is open.
+    points_or_cloud_or_model: (N,3) points on the device, an ops.PackedCloud (sorted or not) or a ModelTraj (its cloud).
+    -> Tour.  Launches only, then one copy to the host."""
+    cloud, pts = _clearance_cloud(points_or_cloud_or_model, "plan_tour")
+    n, r, max_moves = ops.check_tour(poses, quats, clearance_radius, closed, max_moves)
+    if cloud is None:
+        if not pts.is_cuda:
+            raise ValueError(f"plan_tour: points must live on a HIP device, got {pts.device}")
+        if r is not None:
+            cloud = ops.PackedCloud(pts.to(torch.float32))
+    dev = cloud.device if cloud is not None else pts.device
+    nodes = poses.detach().to(device=dev, dtype=torch.float32).contiguous()
+    qs = quats.detach().to(device=dev, dtype=torch.float32).contiguous() if quats is not None else None
+    E = n * (n - 1) // 2
+    i, j = ops.tour_edge_ends(n, dev)
+    dist = torch.full((n, n), float("inf"), dtype=torch.float32, device=dev)
+    if r is not None:
+        d, idx, _ = tour_edge_query(cloud, nodes, r)
+        dist[i, j] = d
+        dist[j, i] = d
+    else:
+        idx = None
+    buf = ops.tour_plan(nodes, idx, closed, max_moves)
+    # the one synchronisation: the tour buffer and the edges' answers in one copy
+    tail = idx.view(torch.uint8) if idx is not None else buf[:0]
+    h = torch.cat([buf, tail]).cpu()
+    lay = ops.tour_layout(n)
+    hdr = h[:64].view(torch.int64)
+    m = int(hdr[0])
+    order = h[lay["order"]:lay["order"] + 4 * n].view(torch.int32)[:m].to(torch.int64)
+    unreachable = h[lay["unreachable"]:lay["unreachable"] + n] != 0
+    D = h[lay["D"]:lay["D"] + 8 * n * n].view(torch.int64).reshape(n, n).clone()
+    nxt = h[lay["nxt"]:lay["nxt"] + 4 * n * n].view(torch.int32).reshape(n, n).clone()
+    blocked = torch.zeros((n, n), dtype=torch.bool)
+    if idx is not None:
+        hit = h[lay["total"]:lay["total"] + 4 * E].view(torch.int32) != -1
+        ih, jh = i.cpu(), j.cpu()
+        blocked[ih, jh] = hit
+        blocked[jh, ih] = hit
+    from .synth import tour_walk   # (numpy only)
+    walk = tour_walk(order.tolist(), nxt.numpy(), closed)
+    w = torch.as_tensor(walk, dtype=torch.int64, device=dev)
+    return Tour(order=order, unreachable=unreachable, walk=walk, poses=nodes[w], quats=qs[w] if qs is not None else None,
+                length=int(hdr[3]) * ops.TOUR_UNIT, nn_length=int(hdr[4]) * ops.TOUR_UNIT, length_fixed=int(hdr[3]),
+                nn_length_fixed=int(hdr[4]), moves=int(hdr[1]), converged=bool(hdr[2]), blocked=blocked, edge_distance=dist, D=D, nxt=nxt)
