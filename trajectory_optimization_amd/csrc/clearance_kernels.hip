@@ -1,6 +1,18 @@
-// clearance_kernels.hip — the clearance term of a trajectory: a hinge on each waypoint's distance to its nearest cloud point.
+// clearance_kernels.hip — the clearance term of a trajectory: a hinge on the distance from each waypoint ('waypoints' mode), or from
+// each segment between two waypoints ('segments' mode, and the edge stage of tools.plan_tour), to its nearest cloud point.
 //
-// For waypoint position t_w (every waypoint, like the other regularisers):
+// ONE nearest-point search (clr_search) serves the three query kernels.  It is a template on a query GEOMETRY, which says what
+// is measured, and on the number of WAVES that share a query.  The kernels differ in three things only:
+//   1. the geometry      k_clearance: ClrPoint;  k_clearance_seg and k_clearance_edge: ClrSegment
+//   2. waves per query   k_clearance and k_clearance_seg: a block of TO_CLR_WAVES waves per query, folded through LDS (clr_block_min);
+//                        k_clearance_edge: one wave per query, TO_EDGE_WAVES queries to a block, no LDS and no barrier
+//   3. the finish        k_clearance: clr_point_finish;  the other two: clr_seg_finish, to which k_clearance_seg adds the term and
+//                        the gradient parts
+// So "a = b is the point query" and "an edge's (d, idx, s) are the segment query's" hold bit for bit: ClrSegment::d2 with a = b
+// rounds to ClrPoint::d2's bits for every point (u - 0 e = u, and (-v)(-v) = v v), the two segment kernels instantiate the same
+// geometry and call the same finish, and the winner does not depend on how many waves looked for it (below).
+//
+// The point query, for waypoint position t_w (every waypoint, like the other regularisers):
 //   d2_w = min_i fl((dx*dx + dy*dy) + dz*dz), dx = fl(t_w.x - x_i.x) ...  (f32, no contraction), over the rows whose three
 //          coordinates are finite (pads never count); ties go to the lowest caller row; i*_w = that row, or -1 when no point has
 //          d2 < fl(r*r) (and for a waypoint with a non-finite coordinate)
@@ -8,19 +20,154 @@
 //   clearance = weight * sum_w (r - d_w)^2 over the waypoints with i*_w >= 0, the sum in f64 in w order, rounded to f32
 //   d clearance / d t_w = -2 weight (r - d_w) (t_w - x_{i*}) / d_w in f64, rounded to f32; zero when i* = -1 or d_w = 0
 //
-// One block of 16 waves per query over the packed cloud (each wave a sixteenth of the tiles) (tohip_pack_cloud: SoA in Morton order, one bounding sphere per 256 points).  The
-// lanes stride over the tile spheres and keep a tile when |t - c| <= R + rad with a relative and an absolute slack (rad: the
-// search radius, r at first, then the distance of the best point so far); a sphere with a non-finite centre or radius (a tile
-// with a NaN or inf coordinate) is always kept, since its finite points still count.  The wave scans each kept tile's 256 points,
-// 4 per lane, and keeps per lane the smallest 64-bit key (float bits of d2) << 32 | caller row: for d2 >= 0 the unsigned order is
-// the float order, so the wave's minimum is the argmin with its tie rule, whatever order the lanes met the points in.  No
+// The segment query, for consecutive waypoints a = t_w, b = t_{w+1} of ONE trajectory (never across two trajectories laid end to
+// end) or the two ends of an edge, all f32 without contraction:  e = fl(b - a), ee = fl(fl(ex ex + ey ey) + ez ez), inv = fl(1 / ee)
+// (0 when ee is not > 0);  per finite point x: u = fl(x - a), s = fmin(fmax(fl(fl(fl(ux ex + uy ey) + uz ez) inv), 0), 1) (a NaN
+// becomes 0), q = fl(u - fl(s e)), d2 = fl(fl(qx qx + qy qy) + qz qz).  The winner is the argmin of d2 over d2 < fl(r r), ties to the
+// lowest caller row (-1: none, or an endpoint that is not finite).  One thread finishes in f64: d = sqrt((double)d2), s* and the
+// closest point c recomputed in f64 from the f32 coordinates, n = (c - x) / |c - x|, term = (r - d)^2,
+// g_a = -2 weight (r - d)(1 - s*) n, g_b = -2 weight (r - d) s* n (the envelope theorem: s* is a minimiser or sits on its clamp),
+// both zero when |c - x| = 0.  The per-segment parts go to scratch; k_clearance_seg_rows adds them per waypoint.
+//
+// The search, over the packed cloud (tohip_pack_cloud: SoA in Morton order, one bounding sphere per 256 points): wave k of WAVES
+// takes the groups of 64 tile spheres k, k + WAVES, ...  Its lanes stride over a group's spheres and keep a tile unless the distance
+// from the sphere's centre to the query exceeds R + rad with a relative and an absolute slack (rad: the search radius, r at first,
+// then the distance of the wave's best point so far); a sphere with a non-finite centre or radius (a tile with a NaN or inf
+// coordinate) is always kept, since its finite points still count.  The wave scans each kept tile's 256 points, 4 per lane, and
+// keeps per lane the smallest 64-bit key (float bits of d2) << 32 | caller row: for d2 >= 0 the unsigned order is the float order,
+// so the minimum is the argmin with its tie rule, whatever order the lanes met the points in.  The prune only ever drops tiles that
+// hold no point within the current radius, so the minimum is the same for any number of waves and any order of the tiles.  No
 // atomics; the per-query results do not depend on the launch.  (One wave per query walked the 4 096 spheres of a 1 M-point cloud in
-// 64 dependent steps: 40 us for 128 queries on a chip that had 128 waves to run.)
+// 64 dependent steps: 40 us for 128 queries on a chip that had 128 waves to run.  The edge stage asks all pairs of 257 nodes, 32 896
+// queries, far more than the chip has room for at once: there 16 waves to a query buy no latency and cost a block-wide fold each.)
 #include "common.hpp"
 #include "opt_step.hpp"
 
-#define TO_CLR_WAVES 16   // waves per query (one block): each takes every 16th group of 64 tile spheres
+#define TO_CLR_WAVES 16   // waves per query (one block) of k_clearance and k_clearance_seg
+#define TO_EDGE_WAVES 4   // queries per block, one wave each, of k_clearance_edge
 
+// ---- the two geometries: finite(), the exact f32 d2 of a point, and for the prune the plain-f32 distance of a sphere's centre and
+// the query's max |coordinate| -----------------------------------------------------------------------------------------------------
+struct ClrPoint {
+    float tx, ty, tz;
+    __device__ explicit ClrPoint(const float* t) : tx(t[0]), ty(t[1]), tz(t[2]) {}
+    __device__ bool finite() const { return finite3(tx, ty, tz); }
+    __device__ float max_abs() const { return fmaxf(fmaxf(fabsf(tx), fabsf(ty)), fabsf(tz)); }
+    __device__ float d2(float x, float y, float z) const {
+        const float dx = __fsub_rn(tx, x), dy = __fsub_rn(ty, y), dz = __fsub_rn(tz, z);
+        return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+    }
+    __device__ float centre_dist(const float4& b) const {
+        const float dx = tx - b.x, dy = ty - b.y, dz = tz - b.z;
+        return sqrtf(dx * dx + dy * dy + dz * dz);
+    }
+};
+
+struct ClrSegment {
+    float ax, ay, az, bx, by, bz;
+    float ex, ey, ez, inv;   // e = fl(b - a), inv = fl(1 / fl(e.e)) or 0
+    __device__ ClrSegment(const float* a, const float* b) : ax(a[0]), ay(a[1]), az(a[2]), bx(b[0]), by(b[1]), bz(b[2]) {
+        ex = __fsub_rn(bx, ax), ey = __fsub_rn(by, ay), ez = __fsub_rn(bz, az);
+        const float ee = __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez));
+        inv = ee > 0.f ? __fdiv_rn(1.f, ee) : 0.f;
+    }
+    __device__ bool finite() const { return finite3(ax, ay, az) && finite3(bx, by, bz); }
+    __device__ float max_abs() const {
+        return fmaxf(fmaxf(fmaxf(fabsf(ax), fabsf(ay)), fabsf(az)), fmaxf(fmaxf(fabsf(bx), fabsf(by)), fabsf(bz)));
+    }
+    __device__ float d2(float x, float y, float z) const {
+        const float ux = __fsub_rn(x, ax), uy = __fsub_rn(y, ay), uz = __fsub_rn(z, az);
+        const float dot = __fadd_rn(__fadd_rn(__fmul_rn(ux, ex), __fmul_rn(uy, ey)), __fmul_rn(uz, ez));
+        const float t = fminf(fmaxf(__fmul_rn(dot, inv), 0.f), 1.f);   // fmaxf(NaN, 0) = 0
+        const float qx = __fsub_rn(ux, __fmul_rn(t, ex)), qy = __fsub_rn(uy, __fmul_rn(t, ey)), qz = __fsub_rn(uz, __fmul_rn(t, ez));
+        return __fadd_rn(__fadd_rn(__fmul_rn(qx, qx), __fmul_rn(qy, qy)), __fmul_rn(qz, qz));
+    }
+    __device__ float centre_dist(const float4& b) const {   // the same clamp
+        const float ux = b.x - ax, uy = b.y - ay, uz = b.z - az;
+        const float t = fminf(fmaxf((ux * ex + uy * ey + uz * ez) * inv, 0.f), 1.f);
+        const float qx = ux - t * ex, qy = uy - t * ey, qz = uz - t * ez;
+        return sqrtf(qx * qx + qy * qy + qz * qz);
+    }
+};
+
+__device__ __forceinline__ unsigned long long clr_wave_min(unsigned long long v) {
+    for (int s = 32; s > 0; s >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, s), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), s);
+        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+// ---- the search: the smallest key over this wave's share of the tiles, the same in every lane; ~0 when no point has d2 < fl(r r) or
+// the query is not finite.  wave of WAVES: this wave's index among the waves that share the query. ---------------------------------
+template <int WAVES, class Geom>
+__device__ __forceinline__ unsigned long long clr_search(const CloudView& cv, const Geom& g, float r, int wave) {
+    unsigned long long best = ~0ull;
+    if (!g.finite()) return best;
+    const int lane = threadIdx.x & 63;
+    const int64_t npad = cv.npad, n = cv.n;
+    const int ntiles = (int)(npad / 256);
+    const float* X = cv.soa;
+    const float* Y = X + npad;
+    const float* Z = Y + npad;
+    const float r2 = __fmul_rn(r, r), ta = g.max_abs();
+    float rad = r;
+    auto cand = [&](float x, float y, float z, int64_t s, int row) {
+        if (s >= n || row < 0 || !finite3(x, y, z)) return;
+        const float d2 = g.d2(x, y, z);
+        if (d2 < r2) {
+            const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)row;
+            best = key < best ? key : best;
+        }
+    };
+    for (int base = 64 * wave; base < ntiles; base += 64 * WAVES) {
+        const int tile = base + lane;
+        bool keep = false;
+        if (tile < ntiles) {
+            const float4 b = cv.bounds[tile];
+            if (!(finite3(b.x, b.y, b.z) && isfinite(b.w))) {
+                keep = true;
+            } else {
+                const float dc = g.centre_dist(b);
+                const float amax = fmaxf(ta, fmaxf(fmaxf(fabsf(b.x), fabsf(b.y)), fabsf(b.z)));
+                // dropped when |c - query| - R > rad, with room for the rounding of dc, of the sphere and of each point's d2.  Written
+                // as !(>) so that a dc that is not a number (a segment's overflow: inf - inf) keeps the tile.  A point's dc is the
+                // square root of a sum of squares of differences of finite numbers: +inf at most, never NaN, and the bound is never
+                // NaN either (finite terms, or one infinite product), so for the point query this is dc <= bound
+                keep = !(dc > (b.w + rad) * 1.0001f + 1e-5f * amax + 1e-6f);
+            }
+        }
+        unsigned long long kept = __ballot(keep);
+        if (!kept) continue;
+        while (kept) {
+            const int k = __ffsll((long long)kept) - 1;
+            kept &= kept - 1;
+            const int64_t p0 = (int64_t)(base + k) * 256 + 4 * lane;   // base + k < ntiles: only lanes with tile < ntiles vote
+            const float4 x4 = *(const float4*)(X + p0), y4 = *(const float4*)(Y + p0), z4 = *(const float4*)(Z + p0);
+            const int4 i4 = *(const int4*)(cv.perm + p0);
+            cand(x4.x, y4.x, z4.x, p0, i4.x);
+            cand(x4.y, y4.y, z4.y, p0 + 1, i4.y);
+            cand(x4.z, y4.z, z4.z, p0 + 2, i4.z);
+            cand(x4.w, y4.w, z4.w, p0 + 3, i4.w);
+        }
+        best = clr_wave_min(best);   // uniform from here: the search radius shrinks to the best distance so far
+        if (best != ~0ull) rad = sqrtf(__uint_as_float((unsigned)(best >> 32)));
+    }
+    return clr_wave_min(best);
+}
+
+// the block's minimum: the waves' keys in LDS, thread 0 folds them (min is order-free: the same bits whatever the schedule).  True in
+// thread 0 alone, where best becomes the minimum
+__device__ __forceinline__ bool clr_block_min(unsigned long long& best, unsigned long long (&sbest)[TO_CLR_WAVES]) {
+    if ((threadIdx.x & 63) == 0) sbest[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x != 0) return false;
+    for (int k = 0; k < TO_CLR_WAVES; ++k) best = sbest[k] < best ? sbest[k] : best;
+    return true;
+}
+
+// ---- the point query ---------------------------------------------------------------------------------------------------------------
 struct ClrArgs {
     CloudView cv;
     const float* q;        // (nq, 3) query positions
@@ -33,79 +180,8 @@ struct ClrArgs {
     int accumulate;
 };
 
-__device__ __forceinline__ unsigned long long clr_wave_min(unsigned long long v) {
-    for (int s = 32; s > 0; s >>= 1) {
-        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, s), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), s);
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ bool clr_finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
-__global__ void __launch_bounds__(TO_CLR_WAVES * 64) k_clearance(ClrArgs a) {
-    __shared__ unsigned long long sbest[TO_CLR_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t w = blockIdx.x;   // the query
-    const float tx = a.q[3 * w], ty = a.q[3 * w + 1], tz = a.q[3 * w + 2];
-    const float r2 = __fmul_rn(a.r, a.r);
-    unsigned long long best = ~0ull;
-    if (clr_finite3(tx, ty, tz)) {
-        const int64_t npad = a.cv.npad, n = a.cv.n;
-        const int ntiles = (int)(npad / 256);
-        const float* X = a.cv.soa;
-        const float* Y = X + npad;
-        const float* Z = Y + npad;
-        const float ta = fmaxf(fmaxf(fabsf(tx), fabsf(ty)), fabsf(tz));
-        float rad = a.r;
-        auto cand = [&](float x, float y, float z, int64_t s, int row) {
-            if (s >= n || row < 0 || !clr_finite3(x, y, z)) return;
-            const float dx = __fsub_rn(tx, x), dy = __fsub_rn(ty, y), dz = __fsub_rn(tz, z);
-            const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-            if (d2 < r2) {
-                const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)row;
-                best = key < best ? key : best;
-            }
-        };
-        for (int base = 64 * wave; base < ntiles; base += 64 * TO_CLR_WAVES) {
-            const int tile = base + lane;
-            bool keep = false;
-            if (tile < ntiles) {
-                const float4 b = a.cv.bounds[tile];
-                if (!(clr_finite3(b.x, b.y, b.z) && isfinite(b.w))) {
-                    keep = true;
-                } else {
-                    const float dx = tx - b.x, dy = ty - b.y, dz = tz - b.z;
-                    const float dc = sqrtf(dx * dx + dy * dy + dz * dz);
-                    const float amax = fmaxf(ta, fmaxf(fmaxf(fabsf(b.x), fabsf(b.y)), fabsf(b.z)));
-                    // |t - c| - R > rad, with room for the rounding of dc, of the sphere and of each point's d2
-                    keep = dc <= (b.w + rad) * 1.0001f + 1e-5f * amax + 1e-6f;
-                }
-            }
-            unsigned long long kept = __ballot(keep);
-            if (!kept) continue;
-            while (kept) {
-                const int k = __ffsll((long long)kept) - 1;
-                kept &= kept - 1;
-                const int64_t p0 = (int64_t)(base + k) * 256 + 4 * lane;
-                const float4 x4 = *(const float4*)(X + p0), y4 = *(const float4*)(Y + p0), z4 = *(const float4*)(Z + p0);
-                const int4 i4 = *(const int4*)(a.cv.perm + p0);
-                cand(x4.x, y4.x, z4.x, p0, i4.x);
-                cand(x4.y, y4.y, z4.y, p0 + 1, i4.y);
-                cand(x4.z, y4.z, z4.z, p0 + 2, i4.z);
-                cand(x4.w, y4.w, z4.w, p0 + 3, i4.w);
-            }
-            best = clr_wave_min(best);   // uniform from here: the search radius shrinks to the best distance so far
-            if (best != ~0ull) rad = sqrtf(__uint_as_float((unsigned)(best >> 32)));
-        }
-        best = clr_wave_min(best);
-    }
-    // the block's minimum: the waves' keys in LDS, one thread folds them (min is order-free: the same bits whatever the schedule)
-    if (lane == 0) sbest[wave] = best;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    for (int k = 0; k < TO_CLR_WAVES; ++k) best = sbest[k] < best ? sbest[k] : best;
+// (its gradient divides by d = sqrt((double)d2), the segment's by |c - x| recomputed in f64: not the same bits, so not one formula)
+__device__ __forceinline__ void clr_point_finish(const ClrArgs& a, const ClrPoint& t, int64_t w, unsigned long long best) {
     float dout = INFINITY, g[3] = {0.f, 0.f, 0.f};
     int iout = -1;
     double term = 0.0;
@@ -119,7 +195,7 @@ __global__ void __launch_bounds__(TO_CLR_WAVES * 64) k_clearance(ClrArgs a) {
         if (d > 0.0) {
             const int64_t s = a.cv.inv[iout];
             const double c = -2.0 * (double)a.weight * h;
-            const double t3[3] = {(double)tx, (double)ty, (double)tz};
+            const double t3[3] = {(double)t.tx, (double)t.ty, (double)t.tz};
             const float* P = a.cv.soa;
             for (int k = 0; k < 3; ++k) g[k] = (float)(c * (t3[k] - (double)P[k * a.cv.npad + s]) / d);
         }
@@ -131,16 +207,42 @@ __global__ void __launch_bounds__(TO_CLR_WAVES * 64) k_clearance(ClrArgs a) {
         for (int k = 0; k < 3; ++k) a.grad[3 * w + k] = a.accumulate ? a.grad[3 * w + k] + g[k] : g[k];
 }
 
-// ---- the swept term: the same hinge on each SEGMENT's distance to its nearest cloud point ('segments' mode) --------------------
-// For consecutive waypoints a = t_w, b = t_{w+1} of ONE trajectory (never across two trajectories laid end to end), all f32 without
-// contraction:  e = fl(b - a), ee = fl(fl(ex ex + ey ey) + ez ez), inv = fl(1 / ee) (0 when ee is not > 0);  per finite point x:
-// u = fl(x - a), s = fmin(fmax(fl(fl(fl(ux ex + uy ey) + uz ez) inv), 0), 1) (a NaN becomes 0), q = fl(u - fl(s e)),
-// d2 = fl(fl(qx qx + qy qy) + qz qz).  The winner is the argmin of d2 over d2 < fl(r r), ties to the lowest caller row (-1: none, or
-// an endpoint that is not finite); a = b is the point query above, bit for bit.  One thread finishes in f64: d = sqrt((double)d2),
-// s* and the closest point c recomputed in f64 from the f32 coordinates, n = (c - x) / |c - x|, term = (r - d)^2,
-// g_a = -2 weight (r - d)(1 - s*) n, g_b = -2 weight (r - d) s* n (the envelope theorem: s* is a minimiser or sits on its clamp),
-// both zero when |c - x| = 0.  The per-segment parts go to scratch; k_clearance_seg_rows adds them per waypoint.
-// The same block shape as k_clearance; the prune measures the sphere's centre against the segment (same clamp, plain f32).
+__global__ void __launch_bounds__(TO_CLR_WAVES * 64) k_clearance(ClrArgs a) {
+    __shared__ unsigned long long sbest[TO_CLR_WAVES];
+    const int64_t w = blockIdx.x;   // the query
+    const ClrPoint t(a.q + 3 * w);
+    unsigned long long best = clr_search<TO_CLR_WAVES>(a.cv, t, a.r, threadIdx.x >> 6);
+    if (clr_block_min(best, sbest)) clr_point_finish(a, t, w, best);
+}
+
+// ---- the segment queries -----------------------------------------------------------------------------------------------------------
+struct ClrSegHit {
+    int idx;          // caller row of the nearest point, -1 when none is within r
+    double d, s;      // its distance (+inf when none) and where along the segment the closest point c lies (0 = a, 1 = b; 0 when none)
+    double v[3];      // c - x
+};
+
+__device__ __forceinline__ ClrSegHit clr_seg_finish(const CloudView& cv, const ClrSegment& g, unsigned long long best) {
+    ClrSegHit o = {-1, (double)INFINITY, 0.0, {0.0, 0.0, 0.0}};
+    if (best == ~0ull) return o;
+    const float d2 = __uint_as_float((unsigned)(best >> 32));
+    o.idx = (int)(unsigned)(best & 0xffffffffull);
+    o.d = sqrt((double)d2);
+    const int64_t slot = cv.inv[o.idx];
+    const float* P = cv.soa;
+    const double a3[3] = {(double)g.ax, (double)g.ay, (double)g.az}, b3[3] = {(double)g.bx, (double)g.by, (double)g.bz};
+    double e3[3], u3[3], ee = 0.0, dot = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        e3[k] = b3[k] - a3[k];
+        u3[k] = (double)P[k * cv.npad + slot] - a3[k];
+        ee += e3[k] * e3[k];
+        dot += u3[k] * e3[k];
+    }
+    o.s = ee > 0.0 ? fmin(fmax(dot / ee, 0.0), 1.0) : 0.0;
+    for (int k = 0; k < 3; ++k) o.v[k] = o.s * e3[k] - u3[k];
+    return o;
+}
+
 struct ClrSegArgs {
     CloudView cv;
     const float* p;        // (n_traj W, 3) waypoint positions, trajectories end to end
@@ -155,115 +257,55 @@ struct ClrSegArgs {
 
 __global__ void __launch_bounds__(TO_CLR_WAVES * 64) k_clearance_seg(ClrSegArgs a) {
     __shared__ unsigned long long sbest[TO_CLR_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t seg = blockIdx.x;
     const int64_t row = seg / (a.W - 1) * a.W + seg % (a.W - 1);   // the waypoint row of the segment's first end
-    const float ax = a.p[3 * row], ay = a.p[3 * row + 1], az = a.p[3 * row + 2];
-    const float bx = a.p[3 * row + 3], by = a.p[3 * row + 4], bz = a.p[3 * row + 5];
-    const float r2 = __fmul_rn(a.r, a.r);
-    unsigned long long best = ~0ull;
-    if (clr_finite3(ax, ay, az) && clr_finite3(bx, by, bz)) {
-        const int64_t npad = a.cv.npad, n = a.cv.n;
-        const int ntiles = (int)(npad / 256);
-        const float* X = a.cv.soa;
-        const float* Y = X + npad;
-        const float* Z = Y + npad;
-        const float ex = __fsub_rn(bx, ax), ey = __fsub_rn(by, ay), ez = __fsub_rn(bz, az);
-        const float ee = __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez));
-        const float inv = ee > 0.f ? __fdiv_rn(1.f, ee) : 0.f;
-        const float ta = fmaxf(fmaxf(fmaxf(fabsf(ax), fabsf(ay)), fabsf(az)), fmaxf(fmaxf(fabsf(bx), fabsf(by)), fabsf(bz)));
-        float rad = a.r;
-        auto cand = [&](float x, float y, float z, int64_t s, int prow) {
-            if (s >= n || prow < 0 || !clr_finite3(x, y, z)) return;
-            const float ux = __fsub_rn(x, ax), uy = __fsub_rn(y, ay), uz = __fsub_rn(z, az);
-            const float dot = __fadd_rn(__fadd_rn(__fmul_rn(ux, ex), __fmul_rn(uy, ey)), __fmul_rn(uz, ez));
-            const float t = fminf(fmaxf(__fmul_rn(dot, inv), 0.f), 1.f);   // fmaxf(NaN, 0) = 0
-            const float qx = __fsub_rn(ux, __fmul_rn(t, ex)), qy = __fsub_rn(uy, __fmul_rn(t, ey)), qz = __fsub_rn(uz, __fmul_rn(t, ez));
-            const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(qx, qx), __fmul_rn(qy, qy)), __fmul_rn(qz, qz));
-            if (d2 < r2) {
-                const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)prow;
-                best = key < best ? key : best;
-            }
-        };
-        for (int base = 64 * wave; base < ntiles; base += 64 * TO_CLR_WAVES) {
-            const int tile = base + lane;
-            bool keep = false;
-            if (tile < ntiles) {
-                const float4 b = a.cv.bounds[tile];
-                if (!(clr_finite3(b.x, b.y, b.z) && isfinite(b.w))) {
-                    keep = true;
-                } else {
-                    const float ux = b.x - ax, uy = b.y - ay, uz = b.z - az;
-                    const float t = fminf(fmaxf((ux * ex + uy * ey + uz * ez) * inv, 0.f), 1.f);
-                    const float qx = ux - t * ex, qy = uy - t * ey, qz = uz - t * ez;
-                    const float dc = sqrtf(qx * qx + qy * qy + qz * qz);
-                    const float amax = fmaxf(ta, fmaxf(fmaxf(fabsf(b.x), fabsf(b.y)), fabsf(b.z)));
-                    // |c - segment| - R > rad, with room for the rounding of dc, of the sphere and of each point's d2; (a dc that is
-                    // not a number — an overflow — keeps the tile)
-                    keep = !(dc > (b.w + rad) * 1.0001f + 1e-5f * amax + 1e-6f);
-                }
-            }
-            unsigned long long kept = __ballot(keep);
-            if (!kept) continue;
-            while (kept) {
-                const int k = __ffsll((long long)kept) - 1;
-                kept &= kept - 1;
-                const int64_t p0 = (int64_t)(base + k) * 256 + 4 * lane;
-                const float4 x4 = *(const float4*)(X + p0), y4 = *(const float4*)(Y + p0), z4 = *(const float4*)(Z + p0);
-                const int4 i4 = *(const int4*)(a.cv.perm + p0);
-                cand(x4.x, y4.x, z4.x, p0, i4.x);
-                cand(x4.y, y4.y, z4.y, p0 + 1, i4.y);
-                cand(x4.z, y4.z, z4.z, p0 + 2, i4.z);
-                cand(x4.w, y4.w, z4.w, p0 + 3, i4.w);
-            }
-            best = clr_wave_min(best);   // uniform from here: the search radius shrinks to the best distance so far
-            if (best != ~0ull) rad = sqrtf(__uint_as_float((unsigned)(best >> 32)));
-        }
-        best = clr_wave_min(best);
-    }
-    if (lane == 0) sbest[wave] = best;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    for (int k = 0; k < TO_CLR_WAVES; ++k) best = sbest[k] < best ? sbest[k] : best;
-    float dout = INFINITY, sout = 0.f;
-    int iout = -1;
-    double term = 0.0, g[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (best != ~0ull) {
-        const float d2 = __uint_as_float((unsigned)(best >> 32));
-        iout = (int)(unsigned)(best & 0xffffffffull);
-        const double d = sqrt((double)d2);
-        dout = (float)d;
-        const double h = (double)a.r - d;
+    const ClrSegment g(a.p + 3 * row, a.p + 3 * row + 3);
+    unsigned long long best = clr_search<TO_CLR_WAVES>(a.cv, g, a.r, threadIdx.x >> 6);
+    if (!clr_block_min(best, sbest)) return;
+    const ClrSegHit hit = clr_seg_finish(a.cv, g, best);
+    double term = 0.0, part[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (hit.idx >= 0) {
+        const double h = (double)a.r - hit.d;
         term = h * h;
-        const int64_t slot = a.cv.inv[iout];
-        const float* P = a.cv.soa;
-        const double a3[3] = {(double)ax, (double)ay, (double)az}, b3[3] = {(double)bx, (double)by, (double)bz};
-        double e3[3], u3[3], v3[3], ee = 0.0, dot = 0.0, vv = 0.0;
-        for (int k = 0; k < 3; ++k) {
-            e3[k] = b3[k] - a3[k];
-            u3[k] = (double)P[k * a.cv.npad + slot] - a3[k];
-            ee += e3[k] * e3[k];
-            dot += u3[k] * e3[k];
-        }
-        const double t = ee > 0.0 ? fmin(fmax(dot / ee, 0.0), 1.0) : 0.0;
-        sout = (float)t;
-        for (int k = 0; k < 3; ++k) {
-            v3[k] = t * e3[k] - u3[k];   // c - x
-            vv += v3[k] * v3[k];
-        }
+        double vv = 0.0;
+        for (int k = 0; k < 3; ++k) vv += hit.v[k] * hit.v[k];
         if (vv > 0.0) {
             const double c = -2.0 * (double)a.weight * h / sqrt(vv);
             for (int k = 0; k < 3; ++k) {
-                g[k] = c * (1.0 - t) * v3[k];
-                g[3 + k] = c * t * v3[k];
+                part[k] = c * (1.0 - hit.s) * hit.v[k];
+                part[3 + k] = c * hit.s * hit.v[k];
             }
         }
     }
-    if (a.d) a.d[seg] = dout;
-    if (a.idx) a.idx[seg] = iout;
-    if (a.s) a.s[seg] = sout;
+    if (a.d) a.d[seg] = (float)hit.d;
+    if (a.idx) a.idx[seg] = hit.idx;
+    if (a.s) a.s[seg] = (float)hit.s;
     a.term[row] = term;
-    for (int k = 0; k < 6; ++k) a.part[6 * seg + k] = g[k];
+    for (int k = 0; k < 6; ++k) a.part[6 * seg + k] = part[k];
+}
+
+// arbitrary segments, one WAVE each: tohip_clearance_segments with n_wps = 2 would answer them with a block of 16 waves apiece
+struct ClrEdgeArgs {
+    CloudView cv;
+    const float* a;        // (E, 3) first ends
+    const float* b;        // (E, 3) second ends
+    int64_t E;
+    float r;
+    float* d;              // may be NULL: (E) distance, +inf when no point is within r
+    int* idx;              // may be NULL: (E) caller row of the nearest point, -1 when none
+    float* s;              // may be NULL: (E) where along the edge the closest point lies
+};
+
+__global__ void __launch_bounds__(TO_EDGE_WAVES * 64) k_clearance_edge(ClrEdgeArgs a) {
+    const int64_t e = (int64_t)blockIdx.x * TO_EDGE_WAVES + (threadIdx.x >> 6);
+    if (e >= a.E) return;   // (wave-uniform)
+    const ClrSegment g(a.a + 3 * e, a.b + 3 * e);
+    const unsigned long long best = clr_search<1>(a.cv, g, a.r, 0);
+    if ((threadIdx.x & 63) != 0) return;
+    const ClrSegHit hit = clr_seg_finish(a.cv, g, best);
+    if (a.d) a.d[e] = (float)hit.d;
+    if (a.idx) a.idx[e] = hit.idx;
+    if (a.s) a.s[e] = (float)hit.s;
 }
 
 // one thread per waypoint row: gradient row w = (float)(g_b of segment w - 1 + g_a of segment w), added in f64 in that order and
@@ -333,6 +375,16 @@ extern "C" int tohip_clearance(const void* packed, int64_t n_points, const float
 // ---- 'segments' mode: the entry points -------------------------------------------------------------------------------------------
 static inline size_t clearance_seg_part_bytes(int64_t W, int64_t n_traj) { return align_up((size_t)(n_traj * (W - 1)) * 48, 256); }
 
+// tohip_clearance_segments' workspace: terms (n_traj W) f64 | the per-segment parts
+static inline size_t clearance_seg_ws_term_bytes(int64_t W, int64_t n_traj) { return align_up((size_t)(W * n_traj) * 8, 256); }
+static inline size_t clearance_seg_ws_bytes(int64_t W, int64_t n_traj) {
+    return clearance_seg_ws_term_bytes(W, n_traj) + clearance_seg_part_bytes(W, n_traj);
+}
+static inline double* clearance_seg_ws_term(void* ws) { return (double*)ws; }
+static inline double* clearance_seg_ws_part(void* ws, int64_t W, int64_t n_traj) {
+    return (double*)((char*)ws + clearance_seg_ws_term_bytes(W, n_traj));
+}
+
 // the two launches behind every path that carries the swept term: the segment query, then the per-waypoint rows and terms
 static inline int clearance_seg_launch(const void* packed, int64_t n_points, const float* poses, int64_t W, int64_t n_traj, float r,
                                        float weight, float* d, int* idx, float* s, double* term, double* part, float* grad, hipStream_t st) {
@@ -370,8 +422,7 @@ static inline bool clearance_seg_counts_ok(int64_t n_wps, int64_t n_traj) {
 }
 
 extern "C" size_t tohip_clearance_segments_workspace_bytes(int64_t n_wps, int64_t n_traj) {
-    if (!clearance_seg_counts_ok(n_wps, n_traj)) return 0;
-    return align_up((size_t)(n_wps * n_traj) * 8, 256) + clearance_seg_part_bytes(n_wps, n_traj);
+    return clearance_seg_counts_ok(n_wps, n_traj) ? clearance_seg_ws_bytes(n_wps, n_traj) : 0;
 }
 
 extern "C" size_t tohip_traj_clearance_segments_scratch_bytes(int64_t n_wps, int64_t n_traj) {
@@ -386,121 +437,13 @@ extern "C" int tohip_clearance_segments(const void* packed, int64_t n_points, co
         return TOHIP_EINVAL;
     if (workspace_bytes < tohip_clearance_segments_workspace_bytes(n_wps, n_traj)) return TOHIP_ENOSPC;
     hipStream_t st = (hipStream_t)stream;
-    double* term = (double*)workspace;
-    double* part = (double*)((char*)workspace + align_up((size_t)(n_wps * n_traj) * 8, 256));
-    int rc = clearance_seg_launch(packed, n_points, poses, n_wps, n_traj, radius, weight, d, idx, s, term, part, grad, st);
+    double* term = clearance_seg_ws_term(workspace);
+    int rc = clearance_seg_launch(packed, n_points, poses, n_wps, n_traj, radius, weight, d, idx, s, term,
+                                  clearance_seg_ws_part(workspace, n_wps, n_traj), grad, st);
     if (rc != TOHIP_OK || !value) return rc;
     k_clearance_value<<<(unsigned)n_traj, 64, 0, st>>>(term, n_wps, weight, value);
     TO_HIP_CHECK_LAUNCH();
     return TOHIP_OK;
-}
-
-// ---- arbitrary segments, one WAVE each: the edge stage of tools.plan_tour (tour_kernels.hip) -----------------------------------
-// tohip_clearance_segments with n_wps = 2 answers E unrelated segments with E blocks of 16 waves; all pairs of 257 nodes are 32 896 of
-// them, far more than the chip has room for at once, so the 16 waves of a block buy no latency and cost a block-wide fold each.  Here
-// a wave owns an edge (TO_EDGE_WAVES edges to a block, no LDS, no barrier): its lanes stride over ALL the tile spheres with
-// k_clearance_seg's inequality, it scans the kept tiles of each group of 64 four points per lane and shrinks the radius after each
-// group.  The key, the per-point arithmetic and the f64 finish are k_clearance_seg's, so (d, idx, s) are its bits for the same two
-// ends: the prune only ever drops tiles that hold no point within the current radius, whatever the order the tiles are met in.
-#define TO_EDGE_WAVES 4
-
-struct ClrEdgeArgs {
-    CloudView cv;
-    const float* a;        // (E, 3) first ends
-    const float* b;        // (E, 3) second ends
-    int64_t E;
-    float r;
-    float* d;              // may be NULL: (E) distance, +inf when no point is within r
-    int* idx;              // may be NULL: (E) caller row of the nearest point, -1 when none
-    float* s;              // may be NULL: (E) where along the edge the closest point lies
-};
-
-__global__ void __launch_bounds__(TO_EDGE_WAVES * 64) k_clearance_edge(ClrEdgeArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int64_t e = (int64_t)blockIdx.x * TO_EDGE_WAVES + (threadIdx.x >> 6);
-    if (e >= a.E) return;   // (wave-uniform)
-    const float ax = a.a[3 * e], ay = a.a[3 * e + 1], az = a.a[3 * e + 2];
-    const float bx = a.b[3 * e], by = a.b[3 * e + 1], bz = a.b[3 * e + 2];
-    const float r2 = __fmul_rn(a.r, a.r);
-    unsigned long long best = ~0ull;
-    if (clr_finite3(ax, ay, az) && clr_finite3(bx, by, bz)) {
-        const int64_t npad = a.cv.npad, n = a.cv.n;
-        const int ntiles = (int)(npad / 256);
-        const float* X = a.cv.soa;
-        const float* Y = X + npad;
-        const float* Z = Y + npad;
-        const float ex = __fsub_rn(bx, ax), ey = __fsub_rn(by, ay), ez = __fsub_rn(bz, az);
-        const float ee = __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez));
-        const float inv = ee > 0.f ? __fdiv_rn(1.f, ee) : 0.f;
-        const float ta = fmaxf(fmaxf(fmaxf(fabsf(ax), fabsf(ay)), fabsf(az)), fmaxf(fmaxf(fabsf(bx), fabsf(by)), fabsf(bz)));
-        float rad = a.r;
-        auto cand = [&](float x, float y, float z, int64_t s, int prow) {
-            if (s >= n || prow < 0 || !clr_finite3(x, y, z)) return;
-            const float ux = __fsub_rn(x, ax), uy = __fsub_rn(y, ay), uz = __fsub_rn(z, az);
-            const float dot = __fadd_rn(__fadd_rn(__fmul_rn(ux, ex), __fmul_rn(uy, ey)), __fmul_rn(uz, ez));
-            const float t = fminf(fmaxf(__fmul_rn(dot, inv), 0.f), 1.f);   // fmaxf(NaN, 0) = 0
-            const float qx = __fsub_rn(ux, __fmul_rn(t, ex)), qy = __fsub_rn(uy, __fmul_rn(t, ey)), qz = __fsub_rn(uz, __fmul_rn(t, ez));
-            const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(qx, qx), __fmul_rn(qy, qy)), __fmul_rn(qz, qz));
-            if (d2 < r2) {
-                const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)prow;
-                best = key < best ? key : best;
-            }
-        };
-        for (int base = 0; base < ntiles; base += 64) {
-            const int tile = base + lane;
-            bool keep = false;
-            if (tile < ntiles) {
-                const float4 b = a.cv.bounds[tile];
-                if (!(clr_finite3(b.x, b.y, b.z) && isfinite(b.w))) {
-                    keep = true;
-                } else {
-                    const float ux = b.x - ax, uy = b.y - ay, uz = b.z - az;
-                    const float t = fminf(fmaxf((ux * ex + uy * ey + uz * ez) * inv, 0.f), 1.f);
-                    const float qx = ux - t * ex, qy = uy - t * ey, qz = uz - t * ez;
-                    const float dc = sqrtf(qx * qx + qy * qy + qz * qz);
-                    const float amax = fmaxf(ta, fmaxf(fmaxf(fabsf(b.x), fabsf(b.y)), fabsf(b.z)));
-                    keep = !(dc > (b.w + rad) * 1.0001f + 1e-5f * amax + 1e-6f);   // k_clearance_seg's inequality
-                }
-            }
-            unsigned long long kept = __ballot(keep);
-            if (!kept) continue;
-            while (kept) {
-                const int k = __ffsll((long long)kept) - 1;
-                kept &= kept - 1;
-                const int64_t p0 = (int64_t)(base + k) * 256 + 4 * lane;   // base + k < ntiles: only lanes with tile < ntiles vote
-                const float4 x4 = *(const float4*)(X + p0), y4 = *(const float4*)(Y + p0), z4 = *(const float4*)(Z + p0);
-                const int4 i4 = *(const int4*)(a.cv.perm + p0);
-                cand(x4.x, y4.x, z4.x, p0, i4.x);
-                cand(x4.y, y4.y, z4.y, p0 + 1, i4.y);
-                cand(x4.z, y4.z, z4.z, p0 + 2, i4.z);
-                cand(x4.w, y4.w, z4.w, p0 + 3, i4.w);
-            }
-            best = clr_wave_min(best);   // uniform from here: the search radius shrinks to the best distance so far
-            if (best != ~0ull) rad = sqrtf(__uint_as_float((unsigned)(best >> 32)));
-        }
-        best = clr_wave_min(best);
-    }
-    if (lane != 0) return;
-    float dout = INFINITY, sout = 0.f;
-    int iout = -1;
-    if (best != ~0ull) {   // k_clearance_seg's finish, without the term and the gradient
-        const float d2 = __uint_as_float((unsigned)(best >> 32));
-        iout = (int)(unsigned)(best & 0xffffffffull);
-        dout = (float)sqrt((double)d2);
-        const int64_t slot = a.cv.inv[iout];
-        const float* P = a.cv.soa;
-        const double a3[3] = {(double)ax, (double)ay, (double)az}, b3[3] = {(double)bx, (double)by, (double)bz};
-        double ee = 0.0, dot = 0.0;
-        for (int k = 0; k < 3; ++k) {
-            const double ek = b3[k] - a3[k], uk = (double)P[k * a.cv.npad + slot] - a3[k];
-            ee += ek * ek;
-            dot += uk * ek;
-        }
-        sout = (float)(ee > 0.0 ? fmin(fmax(dot / ee, 0.0), 1.0) : 0.0);
-    }
-    if (a.d) a.d[e] = dout;
-    if (a.idx) a.idx[e] = iout;
-    if (a.s) a.s[e] = sout;
 }
 
 extern "C" int tohip_clearance_edges(const void* packed, int64_t n_points, const float* a, const float* b, int64_t n_edges, float radius,

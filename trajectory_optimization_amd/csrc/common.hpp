@@ -140,6 +140,8 @@ static inline CamConsts make_consts(const tohip_camera* c) {
     return k;
 }
 
+__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+
 // ----------------------------------------------------------------------------------------------
 // Transcendentals on the hardware units (v_exp_f32 / v_log_f32 / v_rcp_f32, 1 ulp each).
 

@@ -63,7 +63,7 @@ k_tour_init(const float* __restrict__ P, int n, const int* __restrict__ edge_idx
     } else {
         const int lo = i < j ? i : j, hi = i < j ? j : i;
         const float xl = P[3 * lo], yl = P[3 * lo + 1], zl = P[3 * lo + 2], xh = P[3 * hi], yh = P[3 * hi + 1], zh = P[3 * hi + 2];
-        const bool finite = clr_finite3(xl, yl, zl) && clr_finite3(xh, yh, zh);
+        const bool finite = finite3(xl, yl, zl) && finite3(xh, yh, zh);
         const int e = lo * n - lo * (lo + 1) / 2 + (hi - lo - 1);
         if (finite && (!edge_idx || edge_idx[e] == -1)) {
             const double dx = (double)xl - (double)xh, dy = (double)yl - (double)yh, dz = (double)zl - (double)zh;
@@ -215,7 +215,7 @@ __global__ void __launch_bounds__(1024) k_tour_route(TourRoute a) {
         a.hdr[2] = converged;
         a.hdr[3] = len;
         a.hdr[4] = nn_len;
-        a.hdr[5] = clr_finite3(a.P[0], a.P[1], a.P[2]) ? 0 : 1;
+        a.hdr[5] = finite3(a.P[0], a.P[1], a.P[2]) ? 0 : 1;
     }
 }
 
