@@ -37,7 +37,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_clearance_edges / tohip_tour_bytes / tohip_tour_plan (a collision-checked tour through chosen views): new symbols
+/* (still 15) + tohip_roadmap_knn / tohip_roadmap_routes_bytes / tohip_roadmap_relax / tohip_roadmap_pred / tohip_tour_plan_via (a
+ * free-space roadmap: routes where no straight leg is open): new symbols only.
+ * (still 15) + tohip_clearance_edges / tohip_tour_bytes / tohip_tour_plan (a collision-checked tour through chosen views): new symbols
  * only.
  * (still 15) + tohip_clearance_segments / tohip_clearance_segments_workspace_bytes / tohip_traj_clearance_segments_scratch_bytes and
  * the flag bit TOHIP_TRAJ_CLEARANCE_SEGMENTS (the swept clearance term: the hinge on each segment's distance): new symbols and one
@@ -62,7 +64,7 @@ extern "C" {
 #define TOHIP_OK 0
 #define TOHIP_EINVAL (-1)   /* bad size / null pointer */
 #define TOHIP_ENOSPC (-2)   /* caller-provided workspace or output capacity too small */
-#define TOHIP_ENOTCONV (-3) /* hull construction did not converge within its round limit */
+#define TOHIP_ENOTCONV (-3) /* an iteration did not converge within its limit: the hull's rounds, a roadmap's relaxation sweeps */
 #define TOHIP_ENAN (-4)     /* hull input holds a NaN (a zero-norm point flips to NaN, tools.py:49-52): scipy raises ValueError */
 
 /* Points are processed in tiles of this many; packed clouds are padded to a multiple of it. */
@@ -767,6 +769,45 @@ int tohip_clearance_edges(const void *packed, int64_t n_points, const float *a, 
 size_t tohip_tour_bytes(int64_t n);
 int tohip_tour_plan(const float *nodes, int64_t n, const int32_t *edge_idx, int closed, int64_t max_moves, void *buf, size_t bytes,
                     void *stream);
+
+/* ---- a free-space roadmap (roadmap_kernels.hip) ------------------------------------------------------------------
+ * nodes (n_nodes, 3) f32 on the device, 2 <= n_nodes <= TOHIP_ROADMAP_MAX_NODES, supplied by the caller; 1 <= k <= TOHIP_ROADMAP_MAX_K.
+ * The key of a pair (i, j), i != j: with lo = min(i, j), hi = max(i, j), in f64 without contraction dx = (double)x_lo - (double)x_hi
+ * ..., d2 = (dx dx + dy dy) + dz dz — one value per unordered pair.
+ * tohip_roadmap_knn: nbr (n_nodes, k) int32 = the k candidates j != i with the smallest (d2, j), ties to the lower j, in ascending
+ * order of that key; both ends finite and d2 <= (double)max_edge^2 (max_edge >= 0; +inf: no limit); -1 in the slots no candidate
+ * fills (every slot of a node that is not finite).  len (n_nodes, k) int64 = llrint(sqrt(d2) 2^20), the tour's length (held at 2^42;
+ * a slot above 2^40 is stored and never open), -1 in an empty slot.  One launch, no atomics: the same bits in every run.
+ * The edge stage is tohip_clearance_edges with a = node min(i, j), b = node max(i, j) for the filled slots; open (n_nodes, k) uint8 is
+ * the caller's array: non-zero where the slot is filled, its length fits and that query gave idx == -1.  The graph is undirected:
+ * {i, j} is an edge iff an open slot names it in either list.
+ * tohip_roadmap_relax: src (n_sources) int32 on the device, 1 <= n_sources <= TOHIP_ROADMAP_MAX_SOURCES; D (n_sources, n_nodes) int64.
+ * init != 0: D[s][v] = INF = 2^62, D[s][src[s]] = 0 first.  Then n_sweeps (0 <= n_sweeps <= n_nodes) sweeps over all (source, node,
+ * slot) triples, each relaxing both directions of an open slot with a 64-bit integer atomic minimum.  *changed (one device int32) is
+ * zeroed and then holds the number (from 1) of the call's last sweep that lowered anything: the table is final when
+ * *changed < n_sweeps.  The fixed point — the shortest route lengths over the open edges — does not depend on the order of the
+ * relaxations; the number of sweeps it takes may.  At most n_nodes sweeps are ever needed.  Launches only.
+ * tohip_roadmap_pred (after convergence): pred (n_sources, n_nodes) int32 = the lowest u with {u, v} open and D[s][u] + len == D[s][v];
+ * -1 for the source and for v no route reaches.  Two launches.  Coincident nodes are joined by zero-length edges and may name each
+ * other: a walk back from a goal follows pred until it would re-enter a node and then searches the tight edges (D[u] + len == D[v]).
+ * tohip_roadmap_routes_bytes: the bytes of one buffer that holds [D][pred][changed], every section aligned to 256 bytes (0 for sizes
+ * out of range); the entries take the three pointers, so the caller may also keep them apart.
+ * tohip_tour_plan_via: tohip_tour_plan with a roadmap behind it.  via_D: row i (leading dimension via_ld >= n, in int64) holds the
+ * roadmap's route lengths from tour node i, its first n columns those to the tour nodes (the tour nodes are the roadmap's first n).
+ * The initial leg is w_ij = min(direct, via_D[i][j]) with direct today's value (the integer length of an open straight leg, else
+ * INF); via_flag (n, n) uint8 = 1 iff via_D[i][j] < direct strictly; nxt = j where w_ij < INF.  Everything behind that is
+ * tohip_tour_plan's. */
+#define TOHIP_ROADMAP_MAX_NODES 16384
+#define TOHIP_ROADMAP_MAX_K 32
+#define TOHIP_ROADMAP_MAX_SOURCES 256
+int tohip_roadmap_knn(const float *nodes, int64_t n_nodes, int64_t k, float max_edge, int32_t *nbr, int64_t *len, void *stream);
+size_t tohip_roadmap_routes_bytes(int64_t n_nodes, int64_t n_sources);
+int tohip_roadmap_relax(const int32_t *nbr, const int64_t *len, const uint8_t *open, int64_t n_nodes, int64_t k, const int32_t *src,
+                        int64_t n_sources, int64_t *D, int64_t n_sweeps, int32_t *changed, int init, void *stream);
+int tohip_roadmap_pred(const int32_t *nbr, const int64_t *len, const uint8_t *open, int64_t n_nodes, int64_t k, const int32_t *src,
+                       int64_t n_sources, const int64_t *D, int32_t *pred, void *stream);
+int tohip_tour_plan_via(const float *nodes, int64_t n, const int32_t *edge_idx, const int64_t *via_D, int64_t via_ld, int closed,
+                        int64_t max_moves, void *buf, size_t bytes, uint8_t *via_flag, void *stream);
 
 /* ---- input formats (pointcloud_utils.py, launch/voxels_filtering.launch) --------------------------------
  * PointCloud2 payload -> (N,3) f32 with non-finite rows removed, in message order

@@ -1,0 +1,363 @@
+"""The free-space roadmap on the GPU (tools.build_roadmap / plan_path / plan_tour(via=...), roadmap_kernels.hip): the neighbour stage
+against the numpy restatement of its definition (synth.roadmap_knn_ref), bit for bit and twice in a row; the edge stage against
+edge_clearance asked from the lower index; routes and predecessors against synth.roadmap_routes_ref with `open` injected; a wall with
+a doorway that no straight leg passes and the roadmap does; plan_path; via=None; and the chain select_views -> plan_tour(via=lattice)
+-> ModelTraj(clearance_mode='segments') on the bundled cloud."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from trajectory_optimization_amd import synth
+
+pytestmark = pytest.mark.gpu
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+f32 = np.float32
+INF = synth.TOUR_INF
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available()
+    return torch.device("cuda:0")
+
+
+def knn_nodes(kind, M, seed):
+    rng = np.random.default_rng(seed)
+    if kind == "lattice":   # 5 x 5 x 3: nearly every key ties
+        Q = synth.roadmap_lattice((0, 0, 0), (2, 2, 1), 0.5)
+        assert len(Q) == M == 75
+        return Q
+    Q = (rng.random((M, 3)) * f32([20.0, 20.0, 3.0])).astype(f32)
+    if kind == "twins" and M >= 3:
+        Q[M - 1] = Q[M // 3]
+    if kind == "nan" and M >= 3:
+        Q[M // 2, 1] = np.nan
+    if kind == "inf" and M >= 3:
+        Q[0, 2] = np.inf
+    return Q
+
+
+KNN_CASES = [("random", 2, 1, None), ("random", 3, 4, None), ("nan", 3, 4, None), ("random", 65, 12, None), ("twins", 65, 12, None),
+             ("nan", 65, 12, None), ("lattice", 75, 12, None), ("lattice", 75, 32, None), ("lattice", 75, 7, 0.5), ("random", 300, 32, None),
+             ("inf", 300, 32, 3.0), ("random", 1025, 12, None), ("twins", 1025, 12, 1.25), ("random", 65, 12, 0.0)]
+
+
+@pytest.mark.parametrize("kind,M,k,max_edge", KNN_CASES)
+def test_neighbours_equal_the_restatement(dev, kind, M, k, max_edge):
+    from trajectory_optimization_amd import ops
+    Q = knn_nodes(kind, M, 100 * M + k)
+    want_nbr, want_len = synth.roadmap_knn_ref(Q, k, max_edge)
+    if k > M - 1 or max_edge is not None or kind in ("nan", "inf"):
+        assert (want_nbr == -1).any()   # pads are part of the case
+    if max_edge is not None and max_edge > 0:
+        assert (want_nbr >= 0).any()
+    q = torch.from_numpy(Q).to(dev)
+    for _ in range(2):
+        nbr, length = ops.roadmap_knn(q, k, max_edge)
+        assert nbr.dtype == torch.int32 and length.dtype == torch.int64 and tuple(nbr.shape) == tuple(length.shape) == (M, k)
+        assert torch.equal(nbr.cpu(), torch.from_numpy(want_nbr)) and torch.equal(length.cpu(), torch.from_numpy(want_len))
+
+
+def test_edge_stage_is_the_segment_query_from_the_lower_index(dev):
+    from trajectory_optimization_amd import ops, tools
+    pts = torch.from_numpy(synth.make_cloud(2_000, seed=11)).to(dev)
+    Q = (np.random.default_rng(12).random((400, 3)) * f32([40.0, 40.0, 4.0]) - f32([20.0, 20.0, 2.0])).astype(f32)
+    Q[17] = np.nan
+    r, k = 0.8, 8
+    rm = tools.build_roadmap(pts, torch.from_numpy(Q), r, k=k, max_edge=6.0)
+    nbr, length = synth.roadmap_knn_ref(Q, k, 6.0)
+    assert torch.equal(rm.nbr.cpu(), torch.from_numpy(nbr)) and torch.equal(rm.length_fixed.cpu(), torch.from_numpy(length))
+    i = np.repeat(np.arange(len(Q)), k)
+    j = nbr.reshape(-1)
+    f = j >= 0
+    lo, hi = np.minimum(i, j)[f], np.maximum(i, j)[f]
+    d, idx, _ = tools.edge_clearance(pts, torch.from_numpy(Q[lo]), torch.from_numpy(Q[hi]), r)
+    want = np.zeros(len(i), dtype=bool)
+    want[f] = (idx.cpu().numpy() == -1) & (length.reshape(-1)[f] <= synth.TOUR_MAX_LEN)
+    got = rm.open.cpu().numpy()
+    assert got.dtype == np.bool_ and np.array_equal(got.reshape(-1), want) and want.any() and (~want[f]).any()
+    dist = np.full(len(i), np.inf, dtype=f32)
+    dist[f] = d.cpu().numpy()
+    assert np.array_equal(rm.edge_distance.cpu().numpy().reshape(-1), dist)
+    touched = np.zeros(len(Q), dtype=bool)
+    touched[i[want]] = True
+    touched[j[want]] = True
+    assert np.array_equal(rm.isolated.cpu().numpy(), ~touched) and rm.isolated[17]
+    assert rm.n_open == len({(min(a, b), max(a, b)) for a, b in zip(i[want], j[want])})
+    # both directions of a pair carry the same answer
+    state = {}
+    for a, b, o in zip(np.minimum(i, j)[f], np.maximum(i, j)[f], want[f]):
+        assert state.setdefault((a, b), o) == o
+
+
+def routes_both(dev, Q, k, opened, sources, max_edge=None):
+    """(D, pred, sweeps) of the device at sweeps_per_check = 8, checked against the restatement and against sweeps_per_check = 1."""
+    from trajectory_optimization_amd import ops
+    q = torch.from_numpy(Q).to(dev)
+    nbr, length = ops.roadmap_knn(q, k, max_edge)
+    o = torch.from_numpy(opened).to(dev) & (nbr >= 0)
+    want_D, want_pred = synth.roadmap_routes_ref(nbr.cpu().numpy(), length.cpu().numpy(), o.cpu().numpy(), sources)
+    D, pred, sweeps = ops.roadmap_routes(nbr, length, o, sources, sweeps_per_check=8)
+    assert D.dtype == torch.int64 and pred.dtype == torch.int32 and tuple(D.shape) == tuple(pred.shape) == (len(sources), len(Q))
+    assert torch.equal(D.cpu(), torch.from_numpy(want_D)) and torch.equal(pred.cpu(), torch.from_numpy(want_pred))
+    D1, pred1, sweeps1 = ops.roadmap_routes(nbr, length, o, sources, sweeps_per_check=1)
+    assert torch.equal(D1, D) and torch.equal(pred1, pred)
+    assert 1 <= sweeps <= len(Q) and 1 <= sweeps1 <= len(Q)
+    return want_D, want_pred
+
+
+@pytest.mark.parametrize("closed_share", [0.0, 0.5, 0.9])
+def test_routes_under_random_closures(dev, closed_share):
+    rng = np.random.default_rng(int(closed_share * 10) + 40)
+    M, k = 300, 4
+    Q = (rng.random((M, 3)) * f32([12.0, 12.0, 2.0])).astype(f32)
+    opened = rng.random((M, k)) >= closed_share
+    sources = rng.permutation(M)[:256].tolist()
+    D, pred = routes_both(dev, Q, k, opened, sources)
+    sub = D[:, sources]
+    assert np.array_equal(sub, sub.T) and (np.diag(sub) == 0).all()   # an exact integer sum over an undirected graph
+    assert (D < INF).sum() > 256 and ((D >= INF).any() or closed_share == 0.0)
+    if closed_share == 0.9:
+        assert (D >= INF).any()
+
+
+def test_routes_along_a_chain_of_1025(dev):
+    M = 1025
+    Q = np.zeros((M, 3), dtype=f32)
+    Q[:, 0] = np.arange(M) * 0.25
+    D, pred = routes_both(dev, Q, 2, np.ones((M, 2), dtype=bool), [0])
+    assert np.array_equal(D[0], np.arange(M, dtype=np.int64) * 262144)   # the cumulative sum: 0.25 m = 2^18 units
+    want = np.arange(M) - 1   # at k = 2 the two end nodes also name the node two steps in: a tie, to the lower predecessor
+    want[2], want[M - 1] = 0, M - 3
+    assert np.array_equal(pred[0], want)
+
+
+def test_routes_over_components_and_degenerate_sources(dev):
+    rng = np.random.default_rng(77)
+    A = rng.random((100, 3)) * 8.0
+    B = rng.random((100, 3)) * 8.0 + 100.0
+    Q = np.concatenate([A, B, [[1000.0, 0.0, 0.0]], [[np.nan, 0.0, 0.0]]]).astype(f32)
+    lone, bad = 200, 201
+    opened = np.ones((len(Q), 6), dtype=bool)
+    D, pred = routes_both(dev, Q, 6, opened, [5, lone, bad], max_edge=6.0)
+    assert (D[0, :100] < INF).all() and (D[0, 100:] >= INF).all()   # the other component is not reached
+    for row, s in ((1, lone), (2, bad)):
+        assert D[row, s] == 0 and (np.delete(D[row], s) == INF).all() and (pred[row] == -1).all()
+    D1, _ = routes_both(dev, Q, 6, opened, [150], max_edge=6.0)
+    assert (D1[0, 100:200] < INF).all() and (D1[0, :100] >= INF).all()
+
+
+@pytest.fixture(scope="module")
+def doorway(dev):
+    """The scene, the tour without and with the roadmap, and the restatement of the latter — computed once."""
+    from trajectory_optimization_amd import tools
+    sc = synth.doorway_scene()
+    pts = torch.from_numpy(sc["points"]).to(dev)
+    nodes, r = sc["nodes"], sc["radius"]
+    quats = torch.nn.functional.normalize(torch.from_numpy(np.random.default_rng(3).normal(size=(len(nodes), 4)).astype(f32)), dim=1)
+    plain = tools.plan_tour(pts, torch.from_numpy(nodes), quats, clearance_radius=r)
+    tour = tools.plan_tour(pts, torch.from_numpy(nodes), quats, clearance_radius=r, via=torch.from_numpy(sc["lattice"]))
+    Q = synth.roadmap_join(nodes, sc["lattice"])
+    nbr, length = synth.roadmap_knn_ref(Q, 12)
+    n = len(nodes)
+    D, pred = synth.roadmap_routes_ref(nbr, length, tour.roadmap.open.cpu().numpy(), list(range(n)))
+    ref = synth.tour_plan(nodes, tour.blocked.numpy(), False, None, via_D=D)
+    return dict(sc=sc, pts=pts, quats=quats, plain=plain, tour=tour, Q=Q, nbr=nbr, length=length, D=D, pred=pred, ref=ref, n=n)
+
+
+def test_doorway_scene_is_not_vacuous(doorway):
+    sc, plain, n = doorway["sc"], doorway["plain"], doorway["n"]
+    far = sc["right"] + [sc["enclosed"]]
+    assert plain.blocked[sc["left"]][:, far].all() and plain.blocked[sc["enclosed"], :sc["enclosed"]].all()
+    assert not plain.blocked[sc["left"]][:, sc["left"]].any() and not plain.blocked[sc["right"]][:, sc["right"]].any()
+    want = np.zeros(n, dtype=bool)
+    want[far] = True
+    assert np.array_equal(plain.unreachable.numpy(), want)
+    assert np.array_equal(synth.tour_plan(sc["nodes"], plain.blocked.numpy())["unreachable"], want)
+    assert plain.roadmap is None and plain.via_flag is None and plain.walk_nodes is None
+
+
+def test_doorway_tour_runs_through_the_gap(doorway):
+    from trajectory_optimization_amd import tools
+    sc, t, Q, n = doorway["sc"], doorway["tour"], doorway["Q"], doorway["n"]
+    want = np.zeros(n, dtype=bool)
+    want[sc["enclosed"]] = True
+    assert np.array_equal(t.unreachable.numpy(), want) and sorted(t.order.tolist()) == sc["left"] + sc["right"]
+    assert torch.equal(t.blocked, doorway["plain"].blocked)
+    wn = np.asarray(t.walk_nodes)
+    assert wn[0] == 0 and set(sc["left"] + sc["right"]) <= set(wn.tolist()) and sc["enclosed"] not in wn
+    stops = iter(wn.tolist())
+    assert all(v in stops for v in t.walk)   # the tour nodes' walk, in order, within it
+    lo, hi = np.minimum(wn[:-1], wn[1:]), np.maximum(wn[:-1], wn[1:])
+    assert (lo != hi).all()
+    _, idx, _ = tools.edge_clearance(doorway["pts"], torch.from_numpy(Q[lo]), torch.from_numpy(Q[hi]), sc["radius"])
+    assert bool((idx == -1).all())
+    W = Q[wn]
+    assert np.isfinite(W).all() and ((np.abs(W[:, 0]) <= 0.5) & (np.abs(W[:, 1]) < 0.5)).any()
+    legs = synth.tour_edge_lengths(W)
+    assert t.length_fixed == sum(int(legs[a, a + 1]) for a in range(len(wn) - 1)) and t.length == t.length_fixed * 2.0 ** -20
+    assert torch.equal(t.poses.cpu(), torch.from_numpy(W))
+
+
+def test_doorway_tour_equals_the_restatement(doorway):
+    t, ref, rm, n = doorway["tour"], doorway["ref"], doorway["tour"].roadmap, doorway["n"]
+    assert torch.equal(rm.nbr.cpu(), torch.from_numpy(doorway["nbr"])) and torch.equal(rm.length_fixed.cpu(), torch.from_numpy(doorway["length"]))
+    assert torch.equal(rm.nodes.cpu().isnan(), torch.from_numpy(np.isnan(doorway["Q"]))) and bool(rm.nodes.isnan().any())
+    routes = rm.routes(list(range(n)))
+    assert torch.equal(routes.D.cpu(), torch.from_numpy(doorway["D"])) and torch.equal(routes.pred.cpu(), torch.from_numpy(doorway["pred"]))
+    sub = doorway["D"][:, :n]
+    assert np.array_equal(sub, sub.T)
+    assert np.array_equal(t.via_flag.numpy(), ref["via_flag"]) and ref["via_flag"].any() and not ref["via_flag"].all()
+    assert np.array_equal(t.D.numpy(), ref["D"]) and np.array_equal(t.nxt.numpy(), ref["nxt"])
+    assert t.order.tolist() == ref["order"][:ref["m"]].tolist() and t.walk == ref["walk"]
+    assert np.array_equal(t.unreachable.numpy(), ref["unreachable"])
+    assert (t.length_fixed, t.nn_length_fixed, t.moves, t.converged) == (ref["length_fixed"], ref["nn_length_fixed"], ref["moves"], ref["converged"])
+    want_nodes, lead = [t.walk[0]], [t.walk[0]]
+    for u, v in zip(t.walk, t.walk[1:]):
+        hop = synth.roadmap_walk(doorway["pred"][u], u, v)[1:] if ref["via_flag"][u, v] else [v]
+        want_nodes += hop
+        lead += [x if x < n else v for x in hop]   # a free-space node takes the quaternion of the view its leg leads to
+    assert t.walk_nodes == want_nodes and len(want_nodes) > len(t.walk)
+    assert torch.equal(t.quats.cpu(), doorway["quats"][lead])
+
+
+def test_doorway_tour_buffer_equals_the_restatement(dev, doorway):
+    """The raw buffer of tohip_tour_plan_via, section by section."""
+    from trajectory_optimization_amd import ops, tools
+    sc, ref, n = doorway["sc"], doorway["ref"], doorway["n"]
+    nodes = torch.from_numpy(sc["nodes"]).to(dev)
+    cloud = ops.PackedCloud(doorway["pts"])
+    _, idx, _ = tools.tour_edge_query(cloud, nodes, sc["radius"])
+    buf, flag = ops.tour_plan_via(nodes, idx, torch.from_numpy(doorway["D"]).to(dev))
+    h, lay = buf.cpu(), ops.tour_layout(n)
+    hdr = h[:64].view(torch.int64).tolist()
+    assert hdr[:6] == [ref["m"], ref["moves"], int(ref["converged"]), ref["length_fixed"], ref["nn_length_fixed"], 0]
+    assert h[lay["order"]:lay["order"] + 4 * n].view(torch.int32).tolist() == ref["order"].tolist()
+    assert h[lay["unreachable"]:lay["unreachable"] + n].tolist() == ref["unreachable"].astype(int).tolist()
+    assert np.array_equal(h[lay["D"]:lay["D"] + 8 * n * n].view(torch.int64).numpy().reshape(n, n), ref["D"])
+    assert np.array_equal(h[lay["nxt"]:lay["nxt"] + 4 * n * n].view(torch.int32).numpy().reshape(n, n), ref["nxt"])
+    assert np.array_equal(flag.cpu().numpy(), ref["via_flag"].astype(np.uint8))
+
+
+def test_two_views_at_one_position_behind_the_wall(dev, doorway):
+    """Coincident tour nodes are joined by a zero-length edge and tie each other's predecessors in a circle; the walk still arrives."""
+    from trajectory_optimization_amd import tools
+    sc = doorway["sc"]
+    nodes = np.concatenate([sc["nodes"], sc["nodes"][4:5]])   # node 8 = node 4, across the wall from the start
+    n, r = len(nodes), sc["radius"]
+    t = tools.plan_tour(doorway["pts"], torch.from_numpy(nodes), clearance_radius=r, via=torch.from_numpy(sc["lattice"]))
+    Q = synth.roadmap_join(nodes, sc["lattice"])
+    routes = t.roadmap.routes(list(range(n)))
+    D, pred = routes.D.cpu().numpy(), routes.pred.cpu().numpy()
+    nbr, length = synth.roadmap_knn_ref(Q, 12)
+    want_D, want_pred = synth.roadmap_routes_ref(nbr, length, t.roadmap.open.cpu().numpy(), list(range(n)))
+    assert np.array_equal(D, want_D) and np.array_equal(pred, want_pred)
+    assert pred[0, 4] == 8 and pred[0, 8] == 4 and D[0, 4] == D[0, 8] < INF and D[4, 8] == 0   # the circle is there
+    want = np.zeros(n, dtype=bool)
+    want[sc["enclosed"]] = True
+    assert np.array_equal(t.unreachable.numpy(), want) and sorted(t.order.tolist()) == [0, 1, 2, 3, 4, 5, 6, 8]
+    ref = synth.tour_plan(nodes, t.blocked.numpy(), via_D=want_D)
+    assert t.walk == ref["walk"] and t.length_fixed == ref["length_fixed"] and np.array_equal(t.via_flag.numpy(), ref["via_flag"])
+    wn = np.asarray(t.walk_nodes)
+    assert {4, 8} <= set(wn.tolist()) and wn[0] == 0 and len(wn) > len(t.walk)
+    lo, hi = np.minimum(wn[:-1], wn[1:]), np.maximum(wn[:-1], wn[1:])
+    assert (lo != hi).all()
+    _, idx, _ = tools.edge_clearance(doorway["pts"], torch.from_numpy(Q[lo]), torch.from_numpy(Q[hi]), r)
+    assert bool((idx == -1).all())
+    legs = synth.tour_edge_lengths(Q[wn])
+    assert t.length_fixed == sum(int(legs[a, a + 1]) for a in range(len(wn) - 1))
+    # plan_path with every via row given twice: twins among the free-space nodes, and the length the restatement's table holds
+    via2 = np.concatenate([sc["lattice"], sc["lattice"]])
+    p = tools.plan_path(doorway["pts"], [-2.0, 3.0, 1.0], [2.0, 3.0, 1.0], torch.from_numpy(via2), r)
+    Q2 = synth.roadmap_join(f32([[-2.0, 3.0, 1.0], [2.0, 3.0, 1.0]]), via2)
+    nbr2, length2 = synth.roadmap_knn_ref(Q2, 12)
+    D2, _ = synth.roadmap_routes_ref(nbr2, length2, p.roadmap.open.cpu().numpy(), [0])
+    legs2 = synth.tour_edge_lengths(Q2[p.walk])
+    assert p.length_fixed == int(D2[0, 1]) == sum(int(legs2[a, a + 1]) for a in range(len(p.walk) - 1))
+    assert p.walk[0] == 0 and p.walk[-1] == 1 and len(set(p.walk)) == len(p.walk)
+
+
+def test_plan_path_through_the_doorway(dev, doorway):
+    from trajectory_optimization_amd import tools
+    sc = doorway["sc"]
+    via, r = torch.from_numpy(sc["lattice"]), sc["radius"]
+    start, goal = [-2.0, 3.0, 1.0], [2.0, 3.0, 1.0]
+    p = tools.plan_path(doorway["pts"], start, goal, via, r)
+    Q = synth.roadmap_join(f32([start, goal]), sc["lattice"])
+    assert p.walk[0] == 0 and p.walk[-1] == 1 and len(p.walk) > 4 and torch.equal(p.poses.cpu(), torch.from_numpy(Q[p.walk]))
+    wn = np.asarray(p.walk)
+    lo, hi = np.minimum(wn[:-1], wn[1:]), np.maximum(wn[:-1], wn[1:])
+    _, idx, _ = tools.edge_clearance(doorway["pts"], torch.from_numpy(Q[lo]), torch.from_numpy(Q[hi]), r)
+    assert bool((idx == -1).all())
+    nbr, length = synth.roadmap_knn_ref(Q, 12)
+    D, pred = synth.roadmap_routes_ref(nbr, length, p.roadmap.open.cpu().numpy(), [0])
+    assert p.length_fixed == int(D[0, 1]) < INF and p.length == p.length_fixed * 2.0 ** -20 and p.walk == synth.roadmap_walk(pred[0], 0, 1)
+    legs = synth.tour_edge_lengths(Q[wn])
+    assert p.length_fixed == sum(int(legs[a, a + 1]) for a in range(len(wn) - 1))
+    assert ((np.abs(Q[wn][:, 0]) <= 0.5) & (np.abs(Q[wn][:, 1]) < 0.5)).any()
+    with pytest.raises(ValueError, match="plan_path: no route from start to goal"):
+        tools.plan_path(doorway["pts"], start, sc["nodes"][sc["enclosed"]].tolist(), via, r)
+    assert p.roadmap.route(0, 1)[0] == p.walk and p.roadmap.route(1, 0)[1] == p.length_fixed
+
+
+def test_without_via_plan_tour_is_todays(dev):
+    from trajectory_optimization_amd import ops, tools
+    cloud = torch.from_numpy(synth.make_cloud(3_000, seed=3) + f32([500.0, 0.0, 0.0])).to(dev)
+    th = 2 * np.pi * np.arange(16) / 16
+    ring = np.stack([5 * np.cos(th), 5 * np.sin(th), np.zeros(16)], axis=1).astype(f32)[np.random.default_rng(5).permutation(16)]
+    nodes = torch.from_numpy(ring).to(dev)
+    _, idx, _ = tools.tour_edge_query(ops.PackedCloud(cloud), nodes, 2.0)
+    want = ops.tour_plan(nodes, idx, True, None).cpu()
+    t = tools.plan_tour(cloud, torch.from_numpy(ring), clearance_radius=2.0, closed=True, via=None)
+    lay, n = ops.tour_layout(16), 16
+    hdr = want[:64].view(torch.int64)
+    assert (t.length_fixed, t.nn_length_fixed, t.moves, int(t.converged), len(t.order)) == (int(hdr[3]), int(hdr[4]), int(hdr[1]), int(hdr[2]), int(hdr[0]))
+    assert torch.equal(t.order.to(torch.int32), want[lay["order"]:lay["order"] + 4 * n].view(torch.int32)[:len(t.order)])
+    assert torch.equal(t.D, want[lay["D"]:lay["D"] + 8 * n * n].view(torch.int64).reshape(n, n))
+    assert torch.equal(t.nxt, want[lay["nxt"]:lay["nxt"] + 4 * n * n].view(torch.int32).reshape(n, n))
+    assert torch.equal(t.unreachable.to(torch.uint8), want[lay["unreachable"]:lay["unreachable"] + n])
+    assert t.roadmap is None and t.via_flag is None and t.walk_nodes is None
+    # with a roadmap that adds nothing shorter (the straight legs are all open, the lattice lies 1 m off their plane) the same again
+    via = torch.from_numpy(synth.roadmap_lattice((-5, -5, 1), (5, 5, 1), 2.5))
+    v = tools.plan_tour(cloud, torch.from_numpy(ring), clearance_radius=2.0, closed=True, via=via)
+    assert not v.via_flag.any() and torch.equal(v.D, t.D) and torch.equal(v.nxt, t.nxt) and v.walk == t.walk == v.walk_nodes
+
+
+BUNDLED_RADIUS = 0.008   # the bundled cloud holds the ground the bundled path runs on, 9 mm below its first waypoint
+
+
+def test_selected_views_reached_over_a_lattice_make_a_path_the_swept_term_accepts(dev):
+    from trajectory_optimization_amd import tools
+    from trajectory_optimization_amd.model import ModelTraj
+    d = np.load(os.path.join(REPO, "tests", "golden", "bundled.npz"))
+    pts_np, path = np.ascontiguousarray(d["pts"], dtype=f32), np.ascontiguousarray(d["poses"], dtype=f32)
+    K, iw, ih = tools.load_intrinsics(device=dev)
+    quats = torch.from_numpy(np.tile(f32([1.0, 0.0, 0.0, 0.0]), (len(path), 1)))
+    model = ModelTraj(torch.from_numpy(pts_np), torch.from_numpy(path), quats, K, iw, ih, device=dev)
+    cp, cq = synth.bundled_candidate_grid(pts_np, path)
+    sel = tools.select_views(model, torch.from_numpy(cp), torch.from_numpy(cq), 8)
+    poses = torch.cat([model.poses.data[:1], sel.poses])
+    qs = torch.cat([model.quats.data[:1], sel.quats])
+    r = BUNDLED_RADIUS
+    lo, hi = pts_np.min(axis=0).astype(np.float64), pts_np.max(axis=0).astype(np.float64)
+    z = float(path[:, 2].astype(np.float64).mean())
+    via = torch.from_numpy(synth.roadmap_lattice((lo[0], lo[1], z), (hi[0], hi[1], z + 1.0), 1.0))
+    plain = tools.plan_tour(model, poses, qs, clearance_radius=r)
+    t = tools.plan_tour(model, poses, qs, clearance_radius=r, via=via)
+    assert int(t.unreachable.sum()) <= int(plain.unreachable.sum())
+    assert len(t.walk_nodes) >= len(t.walk) >= len(t.order) >= 3 and t.converged and t.poses.shape[0] == len(t.walk_nodes) == t.quats.shape[0]
+    planned = ModelTraj.sharing_cloud_of(model, t.poses, t.quats, clearance_radius=r, clearance_weight=5.0, clearance_mode="segments")
+    planned(vis_wps_dist=0.0)
+    assert float(planned.loss["clearance"].detach()) == 0.0
+
+
+def test_the_example_runs(dev):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("roadmap_tour_sample", os.path.join(REPO, "examples", "roadmap_tour_sample.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    out = mod.main(["--opt-steps", "3"])
+    assert out["unreachable_with_roadmap"] <= out["unreachable_without"] and out["clearance_planned_start"] == 0.0
+    assert out["n_walk_nodes"] >= out["n_walk"] >= 3 and all(np.isfinite(out[k]) for k in ("planned_length", "reward_before", "reward_after"))

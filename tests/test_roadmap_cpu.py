@@ -1,0 +1,346 @@
+"""CPU checks of the free-space roadmap (no GPU): the five entry points are declared in the header and in _lib's table with matching
+argument counts and without a new ABI version; each entry refuses bad arguments before any launch; every argument the host layer
+does not accept is refused with a ValueError that names it, before any GPU call; the numpy restatements (synth.roadmap_knn_ref,
+roadmap_routes_ref, tour_plan(via_D=...)) give what the definitions dictate on cases small enough to work out by hand; and the doorway
+scene of the GPU test is what it claims to be, by a brute-force segment-to-point distance."""
+import ctypes
+import os
+import re
+import types
+
+import numpy as np
+import pytest
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EINVAL, ENOSPC = -1, -2
+ENTRIES = ("tohip_roadmap_knn", "tohip_roadmap_routes_bytes", "tohip_roadmap_relax", "tohip_roadmap_pred", "tohip_tour_plan_via")
+
+
+def test_header_and_table_declare_the_roadmap_entries():
+    from trajectory_optimization_amd import _lib, ops, synth
+    header = open(os.path.join(REPO, "include", "trajopt_hip.h")).read()
+    assert "#define TOHIP_ABI_VERSION 15" in header and _lib.ABI_VERSION == 15 == _lib.lib().tohip_abi_version()
+    before = header.split("#define TOHIP_ABI_VERSION")[0]
+    for sym in ENTRIES:
+        decl = re.search(r"\b(?:int|size_t)\s+" + sym + r"\(([^;]*)\);", header)
+        assert decl, sym
+        n_args = len([a for a in decl.group(1).split(",") if a.strip()])
+        assert sym in _lib.SIGNATURES and len(_lib.SIGNATURES[sym][1]) == n_args, sym
+        assert hasattr(_lib.lib(), sym)
+        assert sym in before, sym   # the changelog line
+    assert re.search(r"\(still 15\) \+ tohip_roadmap_knn", before)
+    for name, v in (("NODES", 16384), ("K", 32), ("SOURCES", 256)):
+        assert f"#define TOHIP_ROADMAP_MAX_{name} {v}\n" in header
+        assert getattr(ops, f"ROADMAP_MAX_{name}") == v == getattr(synth, f"ROADMAP_MAX_{name}")
+    assert ops.ROADMAP_INF == synth.TOUR_INF and ops.ROADMAP_MAX_LEN == synth.TOUR_MAX_LEN and _lib.ENOTCONV == -3
+    src = open(os.path.join(REPO, "trajectory_optimization_amd", "csrc", "trajopt_hip.hip")).read()
+    assert src.index('#include "tour_kernels.hip"') < src.index('#include "roadmap_kernels.hip"')
+
+
+def test_routes_bytes_is_the_documented_layout():
+    from trajectory_optimization_amd import _lib, ops
+    L = _lib.lib()
+    up = lambda v: (v + 255) // 256 * 256
+    for M, S in ((2, 1), (300, 3), (1025, 256), (16384, 256)):
+        lay = ops.roadmap_routes_layout(M, S)
+        assert L.tohip_roadmap_routes_bytes(M, S) == up(8 * M * S) + up(4 * M * S) + 256 == lay["total"]
+        assert lay["D"] == 0 and lay["pred"] == up(8 * M * S) and lay["changed"] == lay["pred"] + up(4 * M * S)
+    for M, S in ((1, 1), (16385, 1), (0, 1), (-4, 1), (10, 0), (10, 257), (10, -1)):
+        assert L.tohip_roadmap_routes_bytes(M, S) == 0, (M, S)
+
+
+def test_entries_refuse_bad_arguments_without_gpu():
+    from trajectory_optimization_amd import _lib
+    L = _lib.lib()
+    p = ctypes.c_void_p(64)   # a non-null pointer no call may reach: every case below fails its checks first
+
+    names = ("nodes", "n_nodes", "k", "max_edge", "nbr", "len", "stream")
+    base = dict(zip(names, (p, 100, 12, float("inf"), p, p, None)))
+    knn = lambda **kw: L.tohip_roadmap_knn(*[kw.get(k, base[k]) for k in names])
+    for k in ("nodes", "nbr", "len"):
+        assert knn(**{k: None}) == EINVAL, k
+    for M in (1, 0, -1, 16385, 1 << 40):
+        assert knn(n_nodes=M) == EINVAL, M
+    for k in (0, -1, 33, 1 << 33):
+        assert knn(k=k) == EINVAL, k
+    for e in (-1.0, float("nan"), -float("inf")):
+        assert knn(max_edge=e) == EINVAL, e
+
+    names = ("nbr", "len", "open", "n_nodes", "k", "src", "n_sources", "D", "n_sweeps", "changed", "init", "stream")
+    base = dict(zip(names, (p, p, p, 100, 12, p, 3, p, 8, p, 1, None)))
+    relax = lambda **kw: L.tohip_roadmap_relax(*[kw.get(k, base[k]) for k in names])
+    for k in ("nbr", "len", "open", "src", "D", "changed"):
+        assert relax(**{k: None}) == EINVAL, k
+    for kw in (dict(n_nodes=1), dict(n_nodes=16385), dict(k=0), dict(k=33), dict(n_sources=0), dict(n_sources=257), dict(n_sweeps=-1),
+               dict(n_sweeps=101)):
+        assert relax(**kw) == EINVAL, kw
+
+    names = ("nbr", "len", "open", "n_nodes", "k", "src", "n_sources", "D", "pred", "stream")
+    base = dict(zip(names, (p, p, p, 100, 12, p, 3, p, p, None)))
+    pred = lambda **kw: L.tohip_roadmap_pred(*[kw.get(k, base[k]) for k in names])
+    for k in ("nbr", "len", "open", "src", "D", "pred"):
+        assert pred(**{k: None}) == EINVAL, k
+    for kw in (dict(n_nodes=1), dict(n_nodes=16385), dict(k=0), dict(k=33), dict(n_sources=0), dict(n_sources=257)):
+        assert pred(**kw) == EINVAL, kw
+
+    n = 12
+    tb = L.tohip_tour_bytes(n)
+    names = ("nodes", "n", "edge_idx", "via_D", "via_ld", "closed", "max_moves", "buf", "bytes", "via_flag", "stream")
+    base = dict(zip(names, (p, n, None, p, 700, 0, 4 * n, p, tb, p, None)))
+    plan = lambda **kw: L.tohip_tour_plan_via(*[kw.get(k, base[k]) for k in names])
+    for k in ("nodes", "via_D", "buf", "via_flag"):
+        assert plan(**{k: None}) == EINVAL, k
+    assert plan(n=1) == EINVAL and plan(n=257) == EINVAL and plan(via_ld=n - 1) == EINVAL and plan(max_moves=-1) == EINVAL
+    assert plan(bytes=tb - 1) == ENOSPC and plan(edge_idx=p, bytes=0) == ENOSPC
+
+
+class _Shard:
+    def __init__(self, kind="waypoints", world_size=1, collective=False):
+        self.kind, self.world_size, self.collective = kind, world_size, collective
+
+
+def test_host_refusals_come_before_any_gpu_call():
+    from trajectory_optimization_amd import ops
+    from trajectory_optimization_amd.tools import Roadmap, build_roadmap, plan_path, plan_tour
+    Q = torch.zeros(40, 3)
+    assert ops.check_roadmap(Q) == (40, 12, None, float("inf"), None)
+    assert ops.check_roadmap(Q, 3, 0.5, 2, torch.tensor([0, 39]), 1) == (40, 3, 0.5, 2.0, [0, 39])
+    bad = [
+        (dict(nodes=[[0, 0, 0], [1, 1, 1]]), "nodes must be a floating-point tensor"),
+        (dict(nodes=torch.zeros(40, 3, dtype=torch.int32)), "nodes must be a floating-point tensor"),
+        (dict(nodes=torch.zeros(40, 2)), r"nodes must be a floating-point tensor of shape \(M,3\)"),
+        (dict(nodes=torch.zeros(1, 3)), "2 <= M <= 16384 nodes, got M = 1"),
+        (dict(nodes=torch.zeros(16385, 3)), "2 <= M <= 16384 nodes, got M = 16385"),
+        (dict(k=0), r"k must be an integer in 1\.\.32"), (dict(k=33), "k must be an integer"), (dict(k=2.0), "k must be an integer"),
+        (dict(k=True), "k must be an integer"),
+        (dict(clearance_radius=0.0), "clearance_radius must be a finite number > 0"), (dict(clearance_radius=-1.0), "clearance_radius"),
+        (dict(clearance_radius=float("nan")), "clearance_radius"), (dict(clearance_radius=float("inf")), "clearance_radius"),
+        (dict(max_edge=-0.5), "max_edge must be None or a number >= 0"), (dict(max_edge=float("nan")), "max_edge"),
+        (dict(max_edge="far"), "max_edge"),
+        (dict(sources=[]), r"sources must be 1\.\.256 integer node indices"), (dict(sources=list(range(257))), "sources must be"),
+        (dict(sources=[0.5]), "sources must be"), (dict(sources=[[0, 1]]), "sources must be"),
+        (dict(sources=[-1]), r"sources must lie in \[0, 40\)"), (dict(sources=[0, 40]), r"sources must lie in \[0, 40\)"),
+        (dict(sweeps_per_check=0), "sweeps_per_check must be an integer >= 1"), (dict(sweeps_per_check=1.5), "sweeps_per_check"),
+    ]
+    for kw, msg in bad:
+        args = dict(nodes=Q, k=12, clearance_radius=0.5, max_edge=None, sources=[0], sweeps_per_check=8)
+        args.update(kw)
+        with pytest.raises(ValueError, match=msg):
+            ops.check_roadmap(**args)
+    pts, P, via = torch.zeros(50, 3), torch.zeros(6, 3), torch.ones(30, 3)
+    for kw, msg in ((dict(k=0), "k must be an integer"), (dict(max_edge=-1), "max_edge"), (dict(clearance_radius=0), "clearance_radius"),
+                    (dict(clearance_radius=None), "clearance_radius"), (dict(nodes=torch.zeros(1, 3)), "2 <= M"),
+                    (dict(nodes=torch.zeros(5, 4)), r"shape \(M,3\)")):
+        args = dict(nodes=Q, clearance_radius=0.5, k=12, max_edge=None)
+        args.update(kw)
+        with pytest.raises(ValueError, match=msg):
+            build_roadmap(pts, **args)
+    for kw, msg in ((dict(via=None), r"via must be a floating-point tensor of shape \(F,3\)"), (dict(via=torch.zeros(0, 3)), "via must be"),
+                    (dict(via=torch.zeros(4, 2)), "via must be"), (dict(via=torch.zeros(16383, 3)), "at most 16384 nodes, got 2 \\+ 16383"),
+                    (dict(k=40), "k must be an integer"), (dict(max_edge=-2.0), "max_edge"), (dict(clearance_radius=-1), "clearance_radius"),
+                    (dict(clearance_radius=None), "clearance_radius"), (dict(start=[0.0, 1.0]), "start must hold 3 coordinates"),
+                    (dict(goal=[[0.0] * 3] * 2), "goal must hold 3 coordinates")):
+        args = dict(start=[0.0, 0.0, 0.0], goal=[1.0, 0.0, 0.0], via=via, clearance_radius=0.5, k=12, max_edge=None)
+        args.update(kw)
+        with pytest.raises(ValueError, match=msg):
+            plan_path(pts, **args)
+    for kw, msg in ((dict(via=torch.zeros(4, 2)), "via must be"), (dict(via=[[0, 0, 0]]), "via must be"),
+                    (dict(via=torch.zeros(16379, 3)), "at most 16384 nodes, got 6 \\+ 16379"), (dict(via_k=0), "k must be an integer"),
+                    (dict(via_max_edge=-1.0), "max_edge"), (dict(clearance_radius=None), "via needs a clearance_radius"),
+                    (dict(poses=torch.zeros(257, 3)), "at most 256 nodes")):
+        args = dict(poses=P, quats=None, clearance_radius=0.5, via=via, via_k=12, via_max_edge=None)
+        args.update(kw)
+        with pytest.raises(ValueError, match=msg):
+            plan_tour(pts, **args)
+    for shard in (_Shard("points"), _Shard("waypoints", 2, True)):
+        model = types.SimpleNamespace(_cloud=types.SimpleNamespace(n=50), _shard=shard)
+        with pytest.raises(ValueError, match="build_roadmap: a sharded model"):
+            build_roadmap(model, Q, 0.5)
+        with pytest.raises(ValueError, match="plan_path: a sharded model"):
+            plan_path(model, [0, 0, 0], [1, 0, 0], via, 0.5)
+        with pytest.raises(ValueError, match="plan_tour: a sharded model"):
+            plan_tour(model, P, None, 0.5, via=via)
+    # every argument is fine: the last check before the first GPU call
+    with pytest.raises(ValueError, match="build_roadmap: points must live on a HIP device"):
+        build_roadmap(pts, Q, 0.5)
+    with pytest.raises(ValueError, match="plan_path: points must live on a HIP device"):
+        plan_path(pts, [0, 0, 0], [1, 0, 0], via, 0.5)
+    with pytest.raises(ValueError, match="plan_tour: points must live on a HIP device"):
+        plan_tour(pts, P, None, 0.5, via=via)
+    with pytest.raises(ValueError, match=r"build_roadmap: points must be an \(N,3\) tensor"):
+        build_roadmap("cloud.pcd", Q, 0.5)
+    rm = Roadmap(nodes=Q, nbr=torch.zeros((40, 4), dtype=torch.int32))
+    with pytest.raises(ValueError, match=r"sources must lie in \[0, 40\)"):
+        rm.routes([40])
+    with pytest.raises(ValueError, match="dst must be a node index"):
+        rm.route(0, 40)
+    with pytest.raises(RuntimeError, match="nodes must live on a HIP device"):
+        ops.roadmap_knn(Q, 4)
+    with pytest.raises(RuntimeError, match="nbr must live on a HIP device"):
+        ops.roadmap_routes(torch.zeros((40, 4), dtype=torch.int32), torch.zeros((40, 4), dtype=torch.int64), torch.zeros((40, 4), dtype=torch.bool), [0])
+
+
+def test_lattice_ties_go_to_the_lower_index():
+    from trajectory_optimization_amd import synth
+    Q = synth.roadmap_lattice((0, 0, 0), (2, 2, 1), 0.5)   # index = (ix * 5 + iy) * 3 + iz
+    assert Q.shape == (75, 3) and Q.dtype == np.float32 and Q[1].tolist() == [0, 0, 0.5] and Q[3].tolist() == [0, 0.5, 0] and Q[-1].tolist() == [2, 2, 1]
+    nbr, length = synth.roadmap_knn_ref(Q, 8)
+    c = (2 * 5 + 2) * 3 + 1   # the centre: six neighbours at 0.5 m, then twelve at 0.5 sqrt 2 of which the two lowest fit
+    six = sorted([c - 15, c + 15, c - 3, c + 3, c - 1, c + 1])
+    assert nbr[c, :6].tolist() == six and (length[c, :6] == 524288).all()
+    assert nbr[c, 6:].tolist() == [c - 15 - 3, c - 15 - 1] and (length[c, 6:] == 741455).all()
+    assert nbr[0].tolist() == [1, 3, 15, 4, 16, 18, 19, 2]   # the corner: three at 0.5 m, three at 0.5 sqrt 2, 19 at 0.5 sqrt 3, and the lowest of three at 1 m
+    # too few candidates, a limit, twins and a node that is not finite
+    n3, l3 = synth.roadmap_knn_ref(Q[:3], 4)
+    assert n3.tolist() == [[1, 2, -1, -1], [0, 2, -1, -1], [1, 0, -1, -1]] and l3[2].tolist() == [524288, 1048576, -1, -1]
+    n5, _ = synth.roadmap_knn_ref(Q, 8, max_edge=0.5)
+    assert n5[c].tolist() == six + [-1, -1] and n5[0].tolist() == [1, 3, 15] + [-1] * 5
+    T = np.float32([[0, 0, 0], [1, 0, 0], [0, 0, 0], [np.nan, 0, 0], [3, 0, 0]])
+    nt, lt = synth.roadmap_knn_ref(T, 3)
+    assert nt.tolist() == [[2, 1, 4], [0, 2, 4], [0, 1, 4], [-1, -1, -1], [1, 0, 2]] and lt[0].tolist() == [0, 1 << 20, 3 << 20]
+    far = np.float32([[0, 0, 0], [3e7, 0, 0]])   # 3e7 m 2^20 > 2^40: stored, never open
+    nf, lf = synth.roadmap_knn_ref(far, 1)
+    assert nf.tolist() == [[1], [0]] and (lf > synth.TOUR_MAX_LEN).all()
+    assert len(synth.roadmap_edges(nf, lf, np.ones((2, 1), dtype=bool))[0]) == 0
+
+
+def test_routes_on_a_hand_made_graph():
+    from trajectory_optimization_amd import synth
+    INF = synth.TOUR_INF
+    # 0 -1- 1 -1- 2, 0 -3- 2, 2 -2- 3, 1 -3- 3; node 4 alone.  Slots name each pair once or twice, one of them closed in one list only.
+    nbr = np.int32([[1, 2], [0, 2], [3, 1], [1, -1], [-1, -1]])
+    length = np.int64([[1, 3], [1, 1], [2, 1], [3, -1], [-1, -1]])
+    opened = np.array([[1, 1], [0, 1], [1, 0], [1, 0], [0, 0]], dtype=bool)   # 1's slot to 0 is closed, 0's slot to 1 is open: an edge
+    D, pred = synth.roadmap_routes_ref(nbr, length, opened, [0, 3, 4])
+    assert D.tolist() == [[0, 1, 2, 4, INF], [4, 3, 2, 0, INF], [INF, INF, INF, INF, 0]]
+    assert pred.tolist() == [[-1, 0, 1, 1, -1], [1, 2, 3, -1, -1], [-1] * 5]   # 0 -> 3: over 1 (1 + 3) and over 2 (2 + 2) tie: the lower
+    assert synth.roadmap_walk(pred[0], 0, 3) == [0, 1, 3] and synth.roadmap_walk(pred[1], 3, 0) == [3, 2, 1, 0]
+    assert synth.roadmap_walk(pred[0], 0, 4) is None and synth.roadmap_walk(pred[0], 0, 0) == [0]
+    closed = opened.copy()
+    closed[0, 0] = False   # now {0, 1} is closed in both lists
+    D2, pred2 = synth.roadmap_routes_ref(nbr, length, closed, [0])
+    assert D2.tolist() == [[0, 4, 3, 5, INF]] and pred2.tolist() == [[-1, 2, 0, 2, -1]]
+    with pytest.raises(ValueError, match="run in a circle"):
+        synth.roadmap_walk(np.int32([1, 0, 1]), 5, 2)
+
+
+def test_tour_plan_without_via_is_unchanged_and_with_via_takes_the_shorter():
+    from trajectory_optimization_amd import synth
+    INF = synth.TOUR_INF
+    th = 2 * np.pi * np.arange(16) / 16
+    ring = np.stack([5 * np.cos(th), 5 * np.sin(th), np.zeros(16)], axis=1).astype(np.float32)
+    P4 = np.float32([[0, 0, 0], [2, 0, 0], [1, 1, 0], [9, 9, 9]])
+    blocked = np.zeros((4, 4), dtype=bool)
+    blocked[0, 1] = blocked[1, 0] = True
+    blocked[3, :] = blocked[:, 3] = True
+    for P, b, closed in ((ring[np.random.default_rng(2).permutation(16)], None, True), (P4, blocked, False), (P4, blocked, True)):
+        old = synth.tour_plan(P, b, closed)
+        same = synth.tour_plan(P, b, closed, None, via_D=None)
+        none = synth.tour_plan(P, b, closed, via_D=np.full((len(P), len(P)), INF, dtype=np.int64))
+        assert "via_flag" not in old and not none["via_flag"].any()
+        for k in ("order", "unreachable", "D", "nxt", "w"):
+            assert np.array_equal(old[k], same[k]) and np.array_equal(old[k], none[k]), k
+        for k in ("m", "length_fixed", "nn_length_fixed", "moves", "converged", "walk"):
+            assert old[k] == same[k] == none[k], k
+    r = synth.tour_plan(P4, blocked)   # what test_tour_cpu pins: the route through the node in between
+    assert r["order"].tolist() == [0, 2, 1, -1] and r["nxt"][0, 1] == 2 and r["D"][0, 1] == r["w"][0, 2] + r["w"][2, 1]
+    # a roadmap that reaches node 3 and shortens 0 -> 1 below the detour (never below the straight line, but the leg is blocked)
+    via = np.full((4, 6), INF, dtype=np.int64)
+    np.fill_diagonal(via, 0)
+    via[0, 1] = via[1, 0] = int(r["w"][0, 1]) + 5
+    via[2, 3] = via[3, 2] = 20 << 20
+    via[0, 2] = via[2, 0] = int(r["w"][0, 2])   # equal to the open straight leg: not strictly shorter, no flag
+    v = synth.tour_plan(P4, blocked, via_D=via)
+    want = np.zeros((4, 4), dtype=bool)
+    want[0, 1] = want[1, 0] = want[2, 3] = want[3, 2] = True
+    assert np.array_equal(v["via_flag"], want) and not v["unreachable"].any() and v["m"] == 4
+    assert v["D"][0, 1] == r["w"][0, 1] + 5 and v["nxt"][0, 1] == 1 and v["D"][0, 3] == r["w"][0, 2] + (20 << 20) and v["nxt"][0, 3] == 2
+    assert np.array_equal(v["D"], v["D"].T)
+
+
+def segment_point_distance(A, B, P):
+    """The smallest distance from each segment A[e] -> B[e] to the points P, brute force in f64."""
+    A, B, P = A.astype(np.float64), B.astype(np.float64), P.astype(np.float64)
+    out = np.empty(len(A))
+    for s in range(0, len(A), 256):
+        a, e = A[s:s + 256, None, :], (B[s:s + 256] - A[s:s + 256])[:, None, :]
+        ee = (e * e).sum(-1)
+        u = P[None] - a
+        t = np.clip((u * e).sum(-1) / np.where(ee > 0, ee, 1.0), 0.0, 1.0)
+        q = u - t[..., None] * e
+        out[s:s + 256] = np.sqrt((q * q).sum(-1)).min(axis=1)
+    return out
+
+
+def test_doorway_scene_is_what_the_gpu_test_assumes():
+    from trajectory_optimization_amd import synth
+    sc = synth.doorway_scene()
+    P, N, r = sc["points"], sc["nodes"], sc["radius"]
+    wall = P[P[:, 0] == 0]
+    assert len(wall) == (161 - 19) * 61 and np.abs(wall[:, 1]).min() == 0.5 and wall[:, 2].max() == 3.0 and len(P) - len(wall) == 6 * 289
+    assert (np.abs(N[:, 1]) >= 2).all() and (N[sc["left"], 0] < -1.5).all() and (N[sc["right"], 0] > 1.5).all()
+    i, j = np.triu_indices(len(N), 1)
+    d = segment_point_distance(N[i], N[j], P)
+    margin = 0.01   # f32 against f64 is nowhere near it
+    side = np.zeros(len(N), dtype=int)
+    side[sc["right"]] = 1
+    side[sc["enclosed"]] = 2
+    for a, b, dist in zip(i, j, d):
+        if side[a] == side[b]:
+            assert dist > r + margin, (a, b, dist)   # the legs on one side of the wall are open
+        else:
+            assert dist < r - margin, (a, b, dist)   # every leg across the wall, and every leg to the enclosed view, is blocked
+    # the roadmap over [nodes; lattice]: its open edges join the two sides through the gap, and nothing reaches the enclosed view
+    Q = synth.roadmap_join(N, sc["lattice"])
+    assert np.isnan(Q).any(axis=1).sum() == 1 and np.isnan(Q[8 + np.flatnonzero((sc["lattice"] == N[0]).all(axis=1))]).all()
+    nbr, length = synth.roadmap_knn_ref(Q, 12)
+    ii, jj = np.repeat(np.arange(len(Q)), 12), nbr.reshape(-1)
+    pairs = np.unique(np.stack([np.minimum(ii, jj), np.maximum(ii, jj)], axis=1)[jj >= 0], axis=0)
+    near = P[(P[:, 2] > 0.5 - r - 0.1) & (P[:, 2] < 1.5 + r + 0.1)]   # the nodes lie in z in [0.5, 1.5]
+    de = segment_point_distance(Q[pairs[:, 0]], Q[pairs[:, 1]], near)
+    assert (np.abs(de - r) > margin).all()   # no edge is a close call
+    is_open = {(a, b): x > r for (a, b), x in zip(map(tuple, pairs), de)}
+    opened = np.zeros(nbr.shape, dtype=bool)
+    opened.reshape(-1)[jj >= 0] = [is_open[(min(a, b), max(a, b))] for a, b in zip(ii[jj >= 0], jj[jj >= 0])]
+    D, pred = synth.roadmap_routes_ref(nbr, length, opened, list(range(8)))
+    reach = D[:, :8] < synth.TOUR_INF
+    want = np.ones((8, 8), dtype=bool)
+    want[7, :7] = want[:7, 7] = False
+    assert np.array_equal(reach, want) and np.array_equal(D[:, :8], D[:, :8].T)
+    W = Q[synth.roadmap_walk(pred[0], 0, 4)]
+    assert ((np.abs(W[:, 0]) <= 0.5) & (np.abs(W[:, 1]) < 0.5)).any()
+    t = synth.tour_plan(N, np.array([[a != b and (side[a] != side[b]) for b in range(8)] for a in range(8)]), via_D=D)
+    assert t["unreachable"].tolist() == [False] * 7 + [True] and t["via_flag"][0, 4] and not t["via_flag"][0, 1]
+
+
+def test_coincident_nodes_do_not_stop_a_walk():
+    """Two views at one position, reached over the roadmap only: the lowest-predecessor rule points each at the other, and the walk
+    still arrives — over the tight edges, with the length the table holds."""
+    from trajectory_optimization_amd import synth
+    INF = synth.TOUR_INF
+    P = np.float32([[0, 0, 0], [5.25, 0.25, 0], [5.25, 0.25, 0]])
+    Q = synth.roadmap_join(P, synth.roadmap_lattice((0, 0, 0), (6, 1, 0), 0.5))
+    nbr, length = synth.roadmap_knn_ref(Q, 8)
+    opened = nbr >= 0
+    D, pred = synth.roadmap_routes_ref(nbr, length, opened, [0, 1, 2])
+    assert D[1, 2] == 0 == D[2, 1] and D[0, 1] == D[0, 2] < INF
+    assert pred[0, 1] == 2 and pred[0, 2] == 1   # the circle
+    with pytest.raises(ValueError, match="run in a circle"):
+        synth.roadmap_walk(pred[0], 0, 1)
+    edges = synth.roadmap_edges(nbr, length, opened)
+    lens = {(int(a), int(b)): int(c) for a, b, c in zip(*edges)}
+    for dst in (1, 2):
+        w = synth.roadmap_walk(pred[0], 0, dst, tight=lambda: (D[0], edges))
+        assert w[0] == 0 and w[-1] == dst and len(set(w)) == len(w)
+        assert sum(lens[(a, b)] for a, b in zip(w, w[1:])) == D[0, dst]
+        assert w == synth.roadmap_tight_walk(D[0], edges, 0, dst)
+    # where no tie closes a circle the fallback is never asked, and an unreachable node stays None
+    far = synth.roadmap_walk(pred[0], 0, 5, tight=lambda: 1 / 0)
+    assert far[0] == 0 and far[-1] == 5
+    assert synth.roadmap_tight_walk(np.full(len(Q), INF), edges, 0, 5) is None
+    # the tour over it: both twins visited, the direct legs from the start blocked
+    blocked = np.zeros((3, 3), dtype=bool)
+    blocked[0, 1:] = blocked[1:, 0] = True
+    t = synth.tour_plan(P, blocked, via_D=D)
+    assert not t["unreachable"].any() and t["order"].tolist() == [0, 1, 2] and t["via_flag"][0, 1] and not t["via_flag"][1, 2]

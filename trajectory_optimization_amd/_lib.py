@@ -205,6 +205,11 @@ SIGNATURES = {
     "tohip_clearance_edges": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_f, c_vp, c_vp, c_vp, c_vp]),
     "tohip_tour_bytes": (c_sz, [c_i64]),
     "tohip_tour_plan": (ctypes.c_int, [c_vp, c_i64, c_vp, ctypes.c_int, c_i64, c_vp, c_sz, c_vp]),
+    "tohip_roadmap_knn": (ctypes.c_int, [c_vp, c_i64, c_i64, c_f, c_vp, c_vp, c_vp]),
+    "tohip_roadmap_routes_bytes": (c_sz, [c_i64, c_i64]),
+    "tohip_roadmap_relax": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, ctypes.c_int, c_vp]),
+    "tohip_roadmap_pred": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "tohip_tour_plan_via": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, ctypes.c_int, c_i64, c_vp, c_sz, c_vp, c_vp]),
     "tohip_gather_waypoints": (ctypes.c_int, [c_vp, c_vp, c_i64, ctypes.c_int, c_vp, c_vp, c_vp]),
     "tohip_rows_strided": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
     "tohip_adam_step": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_f, c_f, c_f, c_i32, c_vp, c_vp]),
@@ -288,6 +293,7 @@ def lib():
 
 ABI_VERSION = 15  # TOHIP_ABI_VERSION of include/trajopt_hip.h (tests/test_host_cpu.py checks the two agree)
 ENOSPC = -2  # TOHIP_ENOSPC
+ENOTCONV = -3  # TOHIP_ENOTCONV
 ENAN = -4    # TOHIP_ENAN
 
 

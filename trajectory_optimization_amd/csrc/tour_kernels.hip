@@ -50,32 +50,60 @@ inline TourLayout tour_layout(int64_t n) {
     return l;
 }
 
+// the key of a pair: the squared distance in f64 without contraction, differences taken lower index minus higher
+__device__ __forceinline__ double tour_d2(float xl, float yl, float zl, float xh, float yh, float zh) {
+    const double dx = (double)xl - (double)xh, dy = (double)yl - (double)yh, dz = (double)zl - (double)zh;
+    return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+}
+
+// llrint(sqrt(d2) 2^20), held at 2^42 so that llrint stays in range; anything above kTourMaxLen is closed anyway
+__device__ __forceinline__ long long tour_len_fixed(double d2) {
+    const double L = sqrt(d2) * 1048576.0;
+    return L < 4398046511104.0 ? llrint(L) : (1ll << 42);
+}
+
+// the straight leg (i, j), i != j: its integer length when it is open, INF otherwise (the one definition both init kernels share)
+__device__ __forceinline__ long long tour_direct(const float* __restrict__ P, int n, const int* __restrict__ edge_idx, int i, int j) {
+    const int lo = i < j ? i : j, hi = i < j ? j : i;
+    const float xl = P[3 * lo], yl = P[3 * lo + 1], zl = P[3 * lo + 2], xh = P[3 * hi], yh = P[3 * hi + 1], zh = P[3 * hi + 2];
+    const bool finite = finite3(xl, yl, zl) && finite3(xh, yh, zh);
+    const int e = lo * n - lo * (lo + 1) / 2 + (hi - lo - 1);
+    if (finite && (!edge_idx || edge_idx[e] == -1)) {
+        const long long q = tour_len_fixed(tour_d2(xl, yl, zl, xh, yh, zh));
+        if (q <= kTourMaxLen) return q;
+    }
+    return kTourInf;
+}
+
 // one thread per (i, j)
 __global__ void __launch_bounds__(256)
 k_tour_init(const float* __restrict__ P, int n, const int* __restrict__ edge_idx, long long* __restrict__ D, int* __restrict__ nxt) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= n * n) return;
     const int i = c / n, j = c % n;
-    long long w = kTourInf;
-    int nx = -1;
-    if (i == j) {
-        w = 0;
-    } else {
-        const int lo = i < j ? i : j, hi = i < j ? j : i;
-        const float xl = P[3 * lo], yl = P[3 * lo + 1], zl = P[3 * lo + 2], xh = P[3 * hi], yh = P[3 * hi + 1], zh = P[3 * hi + 2];
-        const bool finite = finite3(xl, yl, zl) && finite3(xh, yh, zh);
-        const int e = lo * n - lo * (lo + 1) / 2 + (hi - lo - 1);
-        if (finite && (!edge_idx || edge_idx[e] == -1)) {
-            const double dx = (double)xl - (double)xh, dy = (double)yl - (double)yh, dz = (double)zl - (double)zh;
-            const double L = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz))) * 1048576.0;
-            if (L < 4398046511104.0) {   // 2^42: llrint stays in range; anything above is closed anyway
-                const long long q = llrint(L);
-                if (q <= kTourMaxLen) { w = q; nx = j; }
-            }
-        }
+    const long long w = i == j ? 0 : tour_direct(P, n, edge_idx, i, j);
+    D[c] = w;
+    nxt[c] = (i != j && w < kTourInf) ? j : -1;
+}
+
+// k_tour_init with a roadmap behind it: w_ij = min(direct, via), via = via_D[i][j] (row i: the routes from node i over the roadmap,
+// leading dimension ld); via_flag = 1 where the roadmap's route is strictly shorter than the straight leg (or that leg is closed)
+__global__ void __launch_bounds__(256)
+k_tour_init_via(const float* __restrict__ P, int n, const int* __restrict__ edge_idx, const long long* __restrict__ via_D, long long ld,
+                long long* __restrict__ D, int* __restrict__ nxt, unsigned char* __restrict__ via_flag) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= n * n) return;
+    const int i = c / n, j = c % n;
+    long long w = 0;
+    unsigned char f = 0;
+    if (i != j) {
+        w = tour_direct(P, n, edge_idx, i, j);
+        const long long via = via_D[(long long)i * ld + j];
+        if (via < w) { w = via; f = 1; }
     }
     D[c] = w;
-    nxt[c] = nx;
+    nxt[c] = (i != j && w < kTourInf) ? j : -1;
+    via_flag[c] = f;
 }
 
 // iteration k of Floyd-Warshall, one thread per (i, j): reads row k and column k, which no thread of this sweep writes
@@ -223,8 +251,11 @@ __global__ void __launch_bounds__(1024) k_tour_route(TourRoute a) {
 
 extern "C" size_t tohip_tour_bytes(int64_t n) { return tour_size_ok(n) ? tour_layout(n).total : 0; }
 
-extern "C" int tohip_tour_plan(const float* nodes, int64_t n, const int32_t* edge_idx, int closed, int64_t max_moves, void* buf, size_t bytes,
-                               void* stream) {
+namespace {
+
+// the stages behind both entries: the leg matrix (with or without a roadmap's routes), Floyd-Warshall, the route
+int tour_run(const float* nodes, int64_t n, const int32_t* edge_idx, const long long* via_D, int64_t via_ld, unsigned char* via_flag,
+             int closed, int64_t max_moves, void* buf, size_t bytes, void* stream) {
     if (!nodes || !buf || !tour_size_ok(n) || max_moves < 0) return TOHIP_EINVAL;
     const TourLayout l = tour_layout(n);
     if (bytes < l.total) return TOHIP_ENOSPC;
@@ -234,7 +265,8 @@ extern "C" int tohip_tour_plan(const float* nodes, int64_t n, const int32_t* edg
     int* nxt = (int*)(b + l.off_nxt);
     const int N = (int)n;
     const unsigned blocks = (unsigned)((N * N + 255) / 256);
-    k_tour_init<<<blocks, 256, 0, st>>>(nodes, N, edge_idx, D, nxt);
+    if (via_D) k_tour_init_via<<<blocks, 256, 0, st>>>(nodes, N, edge_idx, via_D, (long long)via_ld, D, nxt, via_flag);
+    else k_tour_init<<<blocks, 256, 0, st>>>(nodes, N, edge_idx, D, nxt);
     TO_HIP_CHECK_LAUNCH();
     for (int k = 0; k < N; ++k) {
         k_tour_fw<<<blocks, 256, 0, st>>>(N, k, D, nxt);
@@ -246,4 +278,17 @@ extern "C" int tohip_tour_plan(const float* nodes, int64_t n, const int32_t* edg
     k_tour_route<<<1, 1024, 0, st>>>(a);
     TO_HIP_CHECK_LAUNCH();
     return TOHIP_OK;
+}
+
+}  // namespace
+
+extern "C" int tohip_tour_plan(const float* nodes, int64_t n, const int32_t* edge_idx, int closed, int64_t max_moves, void* buf, size_t bytes,
+                               void* stream) {
+    return tour_run(nodes, n, edge_idx, nullptr, 0, nullptr, closed, max_moves, buf, bytes, stream);
+}
+
+extern "C" int tohip_tour_plan_via(const float* nodes, int64_t n, const int32_t* edge_idx, const int64_t* via_D, int64_t via_ld, int closed,
+                                   int64_t max_moves, void* buf, size_t bytes, uint8_t* via_flag, void* stream) {
+    if (!via_D || !via_flag || via_ld < n) return TOHIP_EINVAL;
+    return tour_run(nodes, n, edge_idx, (const long long*)via_D, via_ld, via_flag, closed, max_moves, buf, bytes, stream);
 }

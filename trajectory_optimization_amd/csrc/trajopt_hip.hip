@@ -12,6 +12,7 @@
 #include "team_kernels.hip"
 #include "views_kernels.hip"
 #include "tour_kernels.hip"
+#include "roadmap_kernels.hip"
 #include "covmap_kernels.hip"
 #include "loss_kernels.hip"
 #include "ingest_kernels.hip"
@@ -24,7 +25,7 @@ extern "C" const char* tohip_error_string(int code) {
         case TOHIP_OK: return "ok";
         case TOHIP_EINVAL: return "invalid argument (null pointer or bad size)";
         case TOHIP_ENOSPC: return "workspace or output capacity too small";
-        case TOHIP_ENOTCONV: return "convex hull did not converge within the round limit";
+        case TOHIP_ENOTCONV: return "did not converge within its round limit (hull rounds, roadmap sweeps)";
         case TOHIP_ENAN: return "points cannot contain NaN";
         default: return code > 0 ? hipGetErrorString((hipError_t)code) : "unknown error";
     }

@@ -1016,6 +1016,148 @@ def tour_plan(nodes, edge_idx=None, closed=False, max_moves=None):
     return buf
 
 
+ROADMAP_MAX_NODES = 16384   # TOHIP_ROADMAP_MAX_NODES
+ROADMAP_MAX_K = 32          # TOHIP_ROADMAP_MAX_K
+ROADMAP_MAX_SOURCES = 256   # TOHIP_ROADMAP_MAX_SOURCES
+ROADMAP_INF = 1 << 62       # a route length where no route exists
+ROADMAP_MAX_LEN = 1 << 40   # the longest edge that can be open, in units of 2^-20 m
+
+
+def check_roadmap_options(k=12, clearance_radius=None, max_edge=None):
+    """k an integer in 1..ROADMAP_MAX_K, clearance_radius None or a finite number > 0, max_edge None or a number >= 0 (NaN refused)
+    -> (k, radius or None, max_edge as a float, +inf for None); ValueError otherwise."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= ROADMAP_MAX_K:
+        raise ValueError(f"k must be an integer in 1..{ROADMAP_MAX_K}, got {k!r}")
+    r = check_tour_radius(clearance_radius) if clearance_radius is not None else None
+    if max_edge is None:
+        me = float("inf")
+    else:
+        try:
+            me = float(max_edge)
+        except (TypeError, ValueError):
+            me = float("nan")
+        if not me >= 0.0:
+            raise ValueError(f"max_edge must be None or a number >= 0, got {max_edge!r}")
+    return int(k), r, me
+
+
+def check_roadmap(nodes, k=12, clearance_radius=None, max_edge=None, sources=None, sweeps_per_check=8):
+    """The arguments of a roadmap: nodes (M,3) a floating tensor with 2 <= M <= ROADMAP_MAX_NODES, k an integer in 1..ROADMAP_MAX_K,
+    clearance_radius None or a finite number > 0, max_edge None or a number >= 0 (NaN refused), sources None or 1..ROADMAP_MAX_SOURCES
+    integer node indices in [0, M) (a list, an array or a tensor), sweeps_per_check an integer >= 1 -> (M, k, radius or None,
+    max_edge as a float (+inf for None), sources as a list or None); ValueError otherwise.  Nothing is launched."""
+    if not torch.is_tensor(nodes) or not nodes.is_floating_point() or nodes.dim() != 2 or nodes.shape[1] != 3:
+        raise ValueError(f"nodes must be a floating-point tensor of shape (M,3), got "
+                         f"{tuple(nodes.shape) if torch.is_tensor(nodes) else type(nodes).__name__}")
+    M = nodes.shape[0]
+    if M < 2 or M > ROADMAP_MAX_NODES:
+        raise ValueError(f"nodes must hold 2 <= M <= {ROADMAP_MAX_NODES} nodes, got M = {M}")
+    k, r, me = check_roadmap_options(k, clearance_radius, max_edge)
+    if isinstance(sweeps_per_check, bool) or not isinstance(sweeps_per_check, (int, np.integer)) or sweeps_per_check < 1:
+        raise ValueError(f"sweeps_per_check must be an integer >= 1, got {sweeps_per_check!r}")
+    src = None
+    if sources is not None:
+        a = sources.detach().cpu().numpy() if torch.is_tensor(sources) else np.asarray(sources)
+        if a.ndim != 1 or a.size < 1 or a.size > ROADMAP_MAX_SOURCES or a.dtype.kind not in "iu":
+            raise ValueError(f"sources must be 1..{ROADMAP_MAX_SOURCES} integer node indices in one dimension, got "
+                             f"shape {a.shape} of {a.dtype}")
+        if (a < 0).any() or (a >= M).any():
+            raise ValueError(f"sources must lie in [0, {M}), got {a.min()}..{a.max()}")
+        src = [int(v) for v in a]
+    return M, int(k), r, me, src
+
+
+def roadmap_knn(nodes, k=12, max_edge=None):
+    """tohip_roadmap_knn over nodes (M,3) f32 on the device -> (nbr (M,k) int32, length_fixed (M,k) int64): each node's k nearest
+    others by the exact f64 key (d2, j), ties to the lower j, -1 where no candidate fills a slot.  One launch."""
+    M, k, _, me, _ = check_roadmap(nodes, k, None, max_edge)
+    _require_cuda(nodes, "nodes")
+    if nodes.dtype != torch.float32 or not nodes.is_contiguous():
+        raise ValueError("nodes must be a contiguous float32 tensor")
+    nbr = torch.empty((M, k), dtype=torch.int32, device=nodes.device)
+    length = torch.empty((M, k), dtype=torch.int64, device=nodes.device)
+    with torch.cuda.device(nodes.device):
+        check(_lib.lib().tohip_roadmap_knn(ptr(nodes), M, k, me, ptr(nbr), ptr(length), stream_ptr()), "tohip_roadmap_knn")
+    return nbr, length
+
+
+def roadmap_routes_layout(M, S):
+    """Byte offsets of a routes buffer's sections (include/trajopt_hip.h, tohip_roadmap_routes_bytes)."""
+    up = lambda v: (v + 255) // 256 * 256
+    return {"D": 0, "pred": up(8 * M * S), "changed": up(8 * M * S) + up(4 * M * S), "total": up(8 * M * S) + up(4 * M * S) + 256}
+
+
+def roadmap_routes(nbr, length_fixed, open_, sources, sweeps_per_check=8):
+    """Shortest routes from `sources` over the open slots of a roadmap -> (D (S,M) int64, pred (S,M) int32, sweeps).  The batch loop
+    around tohip_roadmap_relax: sweeps_per_check sweeps per call, one 4-byte read-back per batch, until a sweep lowered nothing; then
+    tohip_roadmap_pred.  M sweeps always suffice: a table still moving after them raises the library's 'did not converge' error."""
+    _require_cuda(nbr, "nbr")
+    dev = nbr.device
+    if nbr.dim() != 2 or nbr.dtype != torch.int32 or not nbr.is_contiguous():
+        raise ValueError(f"nbr must be a contiguous (M,k) int32 tensor, got {tuple(nbr.shape)} of {nbr.dtype}")
+    M, k = nbr.shape
+    if not (length_fixed.dtype == torch.int64 and length_fixed.is_contiguous() and tuple(length_fixed.shape) == (M, k)
+            and length_fixed.device == dev):
+        raise ValueError(f"length_fixed must be a contiguous ({M},{k}) int64 tensor on the nodes' device")
+    if open_.dtype == torch.bool:
+        open_ = open_.view(torch.uint8)
+    if not (open_.dtype == torch.uint8 and open_.is_contiguous() and tuple(open_.shape) == (M, k) and open_.device == dev):
+        raise ValueError(f"open must be a contiguous ({M},{k}) bool or uint8 tensor on the nodes' device")
+    if not 1 <= k <= ROADMAP_MAX_K or not 2 <= M <= ROADMAP_MAX_NODES:
+        raise ValueError(f"a roadmap holds 2 <= M <= {ROADMAP_MAX_NODES} nodes and 1 <= k <= {ROADMAP_MAX_K} slots, got ({M},{k})")
+    _, _, _, _, src = check_roadmap(torch.empty((M, 3)), k, None, None, sources, sweeps_per_check)
+    if src is None:
+        raise ValueError("sources must be given")
+    S, per = len(src), int(sweeps_per_check)
+    L = _lib.lib()
+    lay = roadmap_routes_layout(M, S)
+    assert L.tohip_roadmap_routes_bytes(M, S) == lay["total"]
+    buf = torch.empty(lay["total"], dtype=torch.uint8, device=dev)
+    D = buf[:8 * M * S].view(torch.int64).view(S, M)
+    pred = buf[lay["pred"]:lay["pred"] + 4 * M * S].view(torch.int32).view(S, M)
+    changed = buf[lay["changed"]:lay["changed"] + 4].view(torch.int32)
+    src_t = torch.tensor(src, dtype=torch.int32, device=dev)
+    sweeps = 0
+    with torch.cuda.device(dev):
+        while True:
+            if sweeps >= M:
+                check(_lib.ENOTCONV, "roadmap_routes")
+            n = min(per, M - sweeps)
+            check(L.tohip_roadmap_relax(ptr(nbr), ptr(length_fixed), ptr(open_), M, k, ptr(src_t), S, ptr(D), n, ptr(changed),
+                                        int(sweeps == 0), stream_ptr()), "tohip_roadmap_relax")
+            last = int(changed.item())   # the batch's one read-back
+            sweeps += n if last == n else last + 1   # (the sweeps that mattered: up to the first that lowered nothing)
+            if last < n:
+                break
+        check(L.tohip_roadmap_pred(ptr(nbr), ptr(length_fixed), ptr(open_), M, k, ptr(src_t), S, ptr(D), ptr(pred), stream_ptr()),
+              "tohip_roadmap_pred")
+    return D, pred, sweeps
+
+
+def tour_plan_via(nodes, edge_idx, via_D, closed=False, max_moves=None):
+    """tohip_tour_plan_via: tour_plan whose initial legs are min(direct, via_D[i][j]) — via_D (n or more rows, n or more columns)
+    int64 on the device, row i the roadmap's routes from tour node i -> (the tour buffer, via_flag (n,n) uint8); launches only."""
+    _require_cuda(nodes, "nodes")
+    n = nodes.shape[0]
+    L = _lib.lib()
+    nbytes = L.tohip_tour_bytes(n)
+    if nbytes == 0 or tuple(nodes.shape) != (n, 3) or nodes.dtype != torch.float32 or not nodes.is_contiguous():
+        raise ValueError(f"nodes must be a contiguous (n,3) float32 tensor with 2 <= n <= {TOUR_MAX_NODES}, got {tuple(nodes.shape)}")
+    if edge_idx is not None and not (edge_idx.dtype == torch.int32 and edge_idx.is_contiguous() and edge_idx.numel() == n * (n - 1) // 2
+                                     and edge_idx.device == nodes.device):
+        raise ValueError(f"edge_idx must be {n * (n - 1) // 2} contiguous int32 on the nodes' device")
+    if not (torch.is_tensor(via_D) and via_D.dtype == torch.int64 and via_D.dim() == 2 and via_D.shape[0] >= n and via_D.shape[1] >= n
+            and via_D.stride(1) == 1 and via_D.stride(0) >= via_D.shape[1] and via_D.device == nodes.device):
+        raise ValueError(f"via_D must be an int64 tensor of at least ({n},{n}) with unit column stride on the nodes' device")
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=nodes.device)
+    flag = torch.empty((n, n), dtype=torch.uint8, device=nodes.device)
+    with torch.cuda.device(nodes.device):
+        check(L.tohip_tour_plan_via(ptr(nodes), n, ptr(edge_idx), ptr(via_D), via_D.stride(0), int(bool(closed)),
+                                    int(4 * n if max_moves is None else max_moves), ptr(buf), nbytes, ptr(flag), stream_ptr()),
+              "tohip_tour_plan_via")
+    return buf, flag
+
+
 def clearance_terms(n_wps, n_traj, mode, device):
     """The float64 buffer the clearance query of `mode` fills for n_traj trajectories of n_wps waypoints: the per-waypoint terms lead
     it in either mode (what the step tails, the regularisers' kernel and the team calls read)."""

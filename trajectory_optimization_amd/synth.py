@@ -142,10 +142,12 @@ def tour_two_opt_changes(D, t, closed):
     return out
 
 
-def tour_plan(P, blocked=None, closed=False, max_moves=None):
+def tour_plan(P, blocked=None, closed=False, max_moves=None, via_D=None):
     """The whole definition: P (n,3) f32 nodes (node 0 the start), blocked (n,n) bool or None (the pairs whose segment query found a
     point; symmetric) -> dict(order, m, unreachable, length_fixed, nn_length_fixed, moves, converged, D, nxt, w, walk).  Floyd-Warshall
-    is vectorised per k and 2-opt per move, all in int64."""
+    is vectorised per k and 2-opt per move, all in int64.  via_D (n or more rows, n or more columns, int64; None: no roadmap): the
+    roadmap's route lengths between the tour nodes — the initial leg is min(direct, via) and the result gains via_flag (n,n) bool,
+    True where via < direct strictly."""
     P = np.asarray(P, dtype=np.float32)
     n = len(P)
     max_moves = 4 * n if max_moves is None else int(max_moves)
@@ -155,6 +157,14 @@ def tour_plan(P, blocked=None, closed=False, max_moves=None):
         opened &= ~np.asarray(blocked, dtype=bool)
     np.fill_diagonal(opened, False)
     D = np.where(opened, w, TOUR_INF).astype(np.int64)
+    via_flag = None
+    if via_D is not None:
+        via = np.asarray(via_D, dtype=np.int64)[:n, :n]
+        via_flag = via < D
+        np.fill_diagonal(via_flag, False)
+        D = np.where(via_flag, via, D)
+        opened = D < TOUR_INF
+        np.fill_diagonal(opened, False)
     np.fill_diagonal(D, 0)
     nxt = np.where(opened, np.arange(n)[None, :], -1).astype(np.int32)
     for k in range(n):
@@ -192,8 +202,11 @@ def tour_plan(P, blocked=None, closed=False, max_moves=None):
         moves += 1
     order = np.full(n, -1, dtype=np.int32)
     order[:m] = t
-    return dict(order=order, m=m, unreachable=~reach, length_fixed=length, nn_length_fixed=nn, moves=moves, converged=converged, D=D,
-                nxt=nxt, w=w, walk=tour_walk(t, nxt, closed))
+    out = dict(order=order, m=m, unreachable=~reach, length_fixed=length, nn_length_fixed=nn, moves=moves, converged=converged, D=D,
+               nxt=nxt, w=w, walk=tour_walk(t, nxt, closed))
+    if via_flag is not None:
+        out["via_flag"] = via_flag
+    return out
 
 
 def tour_walk(order, nxt, closed):
@@ -206,3 +219,176 @@ def tour_walk(order, nxt, closed):
             u = int(nxt[u][v])
             walk.append(u)
     return walk
+
+
+# ---- the free-space roadmap restated in numpy: what roadmap_kernels.hip must give, element for element ---------------
+ROADMAP_MAX_NODES = 16384
+ROADMAP_MAX_K = 32
+ROADMAP_MAX_SOURCES = 256
+
+
+def roadmap_lattice(lo, hi, spacing):
+    """Free-space node candidates: the lattice lo + spacing (a, b, c) inside the box [lo, hi] (both ends included up to rounding),
+    x the slowest index -> (M,3) f32.  Plain numpy; whether a node or an edge is free is the roadmap's business."""
+    lo, hi = np.asarray(lo, dtype=np.float64).reshape(3), np.asarray(hi, dtype=np.float64).reshape(3)
+    h = float(spacing)
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and np.isfinite(h) and h > 0.0 and (hi >= lo).all()):
+        raise ValueError(f"roadmap_lattice needs finite lo <= hi and a finite spacing > 0, got {lo}, {hi}, {spacing!r}")
+    axes = [lo[a] + h * np.arange(int(np.floor((hi[a] - lo[a]) / h + 1e-9)) + 1) for a in range(3)]
+    g = np.stack(np.meshgrid(*axes, indexing="ij"), axis=-1).reshape(-1, 3)
+    return g.astype(np.float32)
+
+
+def roadmap_knn_ref(Q, k, max_edge=None):
+    """nbr (M,k) int32, length_fixed (M,k) int64: for each node the k others with the smallest (d2, j), ties to the lower j, ascending
+    — d2 in f64 without contraction, the differences taken lower index minus higher; both ends finite; d2 <= (double)(float)max_edge^2
+    when max_edge is given; -1 in both arrays where no candidate fills the slot.  length = rint(min(sqrt(d2) 2^20, 2^42))."""
+    Q = np.asarray(Q, dtype=np.float32)
+    M = len(Q)
+    fin = np.isfinite(Q).all(axis=1)
+    Qd = np.where(fin[:, None], Q, 0).astype(np.float64)
+    idx = np.arange(M)
+    lo, hi = np.minimum.outer(idx, idx), np.maximum.outer(idx, idx)
+    d = Qd[lo] - Qd[hi]
+    d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    ok = fin[:, None] & fin[None, :] & (idx[:, None] != idx[None, :])
+    if max_edge is not None:
+        ok &= d2 <= np.float64(np.float32(max_edge)) ** 2
+    key = np.where(ok, d2, np.inf)
+    order = np.argsort(key, axis=1, kind="stable")[:, :k]   # stable: equal keys keep the ascending j
+    got = np.take_along_axis(ok, order, axis=1)
+    nbr = np.full((M, k), -1, dtype=np.int32)
+    length = np.full((M, k), -1, dtype=np.int64)
+    kk = order.shape[1]
+    L = np.rint(np.minimum(np.sqrt(np.take_along_axis(d2, order, axis=1)) * 1048576.0, float(1 << 42))).astype(np.int64)
+    nbr[:, :kk] = np.where(got, order, -1)
+    length[:, :kk] = np.where(got, L, -1)
+    return nbr, length
+
+
+def roadmap_edges(nbr, length, open_):
+    """The directed relaxations (u, v, L) of a roadmap: both directions of every open slot (a pair named in both lists appears twice in
+    each direction: harmless)."""
+    nbr, length = np.asarray(nbr), np.asarray(length, dtype=np.int64)
+    M = nbr.shape[0]
+    ok = np.asarray(open_).astype(bool) & (nbr >= 0) & (nbr < M) & (length >= 0) & (length <= TOUR_MAX_LEN)
+    i, s = np.nonzero(ok)
+    j = nbr[i, s].astype(np.int64)
+    L = length[i, s]
+    return np.concatenate([i, j]), np.concatenate([j, i]), np.concatenate([L, L])
+
+
+def roadmap_routes_ref(nbr, length, open_, sources):
+    """D (S,M) int64, pred (S,M) int32 over the undirected graph of the open slots: Bellman-Ford sweeps in int64 until nothing moves
+    (the fixed point is the shortest-route table whatever the order), INF = 2^62 where no route exists, D[s][src[s]] = 0; pred[s][v] =
+    the lowest u with {u, v} open and D[s][u] + len == D[s][v], -1 for the source and the unreachable."""
+    M = np.asarray(nbr).shape[0]
+    src = np.asarray(sources, dtype=np.int64).reshape(-1)
+    S = len(src)
+    u, v, L = roadmap_edges(nbr, length, open_)
+    D = np.full((S, M), TOUR_INF, dtype=np.int64)
+    D[np.arange(S), src] = 0
+    pred = np.full((S, M), -1, dtype=np.int32)
+    if len(u) == 0:
+        return D, pred
+    o = np.argsort(v, kind="stable")
+    u, v, L = u[o], v[o], L[o]
+    heads, starts = np.unique(v, return_index=True)
+    for _ in range(M + 1):
+        cand = np.where(D[:, u] < TOUR_INF, D[:, u] + L[None, :], TOUR_INF)
+        best = np.minimum.reduceat(cand, starts, axis=1)
+        new = np.minimum(D[:, heads], best)
+        if (new == D[:, heads]).all():
+            break
+        D[:, heads] = new
+    else:
+        raise RuntimeError("roadmap_routes_ref did not converge")
+    hit = (D[:, u] < TOUR_INF) & (D[:, u] + L[None, :] == D[:, v]) & (v[None, :] != src[:, None])
+    cu = np.where(hit, u[None, :], np.iinfo(np.int64).max)
+    lowest = np.minimum.reduceat(cu, starts, axis=1)
+    pred[:, heads] = np.where(lowest < M, lowest, -1).astype(np.int32)
+    return D, pred
+
+
+def roadmap_tight_walk(D_row, edges, src, dst):
+    """src, ..., dst over tight edges only — (u, v, L) of roadmap_edges with D[u] + L == D[v] — by a depth-first search back from dst
+    that takes the lowest u first and enters no node twice: every edge of a shortest route is tight, so it ends at src whenever
+    D[dst] is finite, zero-length edges between coincident nodes or not.  None when dst is not reached."""
+    src, dst = int(src), int(dst)
+    D_row = np.asarray(D_row, dtype=np.int64)
+    if D_row[dst] >= TOUR_INF:
+        return None
+    u, v, L = edges
+    tight = (D_row[u] < TOUR_INF) & (D_row[u] + L == D_row[v])
+    u, v = u[tight], v[tight]
+    o = np.lexsort((u, v))
+    u, v = u[o], v[o]
+    first, last = np.searchsorted(v, np.arange(len(D_row))), np.searchsorted(v, np.arange(len(D_row)), side="right")
+    parent, stack = {dst: None}, [dst]
+    while stack:
+        x = stack.pop()
+        if x == src:
+            walk = [src]
+            while parent[walk[-1]] is not None:
+                walk.append(parent[walk[-1]])
+            return walk
+        for w in u[first[x]:last[x]][::-1].tolist():   # pushed in descending order: the lowest comes off first
+            if w not in parent:
+                parent[w] = x
+                stack.append(w)
+    return None
+
+
+def roadmap_walk(pred_row, src, dst, tight=None):
+    """src, ..., dst along one source's predecessors, or None when dst is not reached.  Coincident nodes are joined by zero-length
+    edges, and the lowest-predecessor rule can then point two of them at each other: a chain that comes back to a node it has
+    visited is replaced by roadmap_tight_walk over (D_row, edges) = tight() — a route of the same length; without `tight` it
+    raises."""
+    src, dst = int(src), int(dst)
+    walk, seen = [dst], {dst}
+    while walk[-1] != src:
+        p = int(pred_row[walk[-1]])
+        if p < 0:
+            return None
+        if p in seen:
+            if tight is None:
+                raise ValueError("the predecessors run in a circle: coincident nodes joined by zero-length edges")
+            return roadmap_tight_walk(*tight(), src, dst)
+        walk.append(p)
+        seen.add(p)
+    return walk[::-1]
+
+def roadmap_join(head, via):
+    """[head; via] as the planners build it: a via row that coincides with a head row is made non-finite (such a node has no edge,
+    and no zero-length edge ties it to its twin) -> (len(head) + len(via), 3) f32."""
+    head, via = np.asarray(head, dtype=np.float32).reshape(-1, 3), np.array(via, dtype=np.float32).reshape(-1, 3)
+    twin = (via[:, None, :] == head[None, :, :]).all(axis=2).any(axis=1)
+    via[twin] = np.nan
+    return np.concatenate([head, via])
+
+
+def doorway_scene():
+    """A wall with a doorway and a sealed box: dict(points (N,3) f32: the plane x = 0, y in [-4, 4], z in [0, 3] at 0.05 m spacing
+    with a gap at |y| < 0.5, and a closed cubic shell of half side 0.4 m around node 7; radius 0.3; nodes (8,3) f32: the start and
+    three views at x ~ -2, three views at x ~ +2 (all at y >= 2: every straight leg across the wall hits it) and a view inside the
+    shell; left / right / enclosed: those nodes' indices; lattice (663,3) f32: roadmap_lattice at 0.5 m over the box [-3, 3] x
+    [-4, 4] x [0.5, 1.5], which holds nodes inside the gap and no way round the wall's ends)."""
+    g = np.arange(-80, 81) * 0.05
+    z = np.arange(0, 61) * 0.05
+    yy, zz = np.meshgrid(g[np.abs(g) >= 0.5 - 1e-9], z, indexing="ij")
+    wall = np.stack([np.zeros(yy.size), yy.ravel(), zz.ravel()], axis=1)
+    c = np.array([2.25, -2.25, 1.25])
+    t = np.arange(-8, 9) * 0.05
+    a, b = [m.ravel() for m in np.meshgrid(t, t, indexing="ij")]
+    faces = []
+    for axis in range(3):
+        for side in (-0.4, 0.4):
+            f = np.empty((a.size, 3))
+            f[:, axis] = side
+            f[:, (axis + 1) % 3] = a
+            f[:, (axis + 2) % 3] = b
+            faces.append(c + f)
+    nodes = np.float32([[-2.0, 3.0, 1.0], [-2.1, 2.2, 1.2], [-2.2, 3.6, 0.8], [-1.9, 2.7, 1.4],
+                        [2.1, 2.3, 1.1], [1.9, 3.4, 0.9], [2.2, 2.8, 1.3], [2.25, -2.25, 1.25]])
+    return dict(points=np.concatenate([wall] + faces).astype(np.float32), radius=0.3, nodes=nodes, left=[0, 1, 2, 3], right=[4, 5, 6],
+                enclosed=7, lattice=roadmap_lattice((-3.0, -4.0, 0.5), (3.0, 4.0, 1.5), 0.5))

@@ -383,9 +383,13 @@ class Tour:
     moves made and whether no improving move is left; blocked (n,n) bool on the host: the pairs whose straight leg comes within the
     clearance radius of the cloud; edge_distance (n,n) f32 on the device: that leg's distance to the cloud, +inf where it keeps the
     radius (and on the diagonal); D (n,n) int64 / nxt (n,n) int32 on the host: the shortest open route between every two nodes and
-    its first step."""
+    its first step.
+    With via= (a free-space roadmap behind the legs; None otherwise): roadmap: the Roadmap over [poses; via]; via_flag (n,n) bool on
+    the host: the legs that run over the roadmap because that is shorter than the straight leg (or the straight leg is blocked);
+    walk_nodes: the walk as indices into [poses; via], every such leg expanded into the roadmap's nodes — poses / quats then follow
+    walk_nodes (a free-space node takes the quaternion of the view its leg leads to), walk keeps listing tour nodes only."""
     __slots__ = ("order", "unreachable", "walk", "poses", "quats", "length", "nn_length", "length_fixed", "nn_length_fixed", "moves",
-                 "converged", "blocked", "edge_distance", "D", "nxt")
+                 "converged", "blocked", "edge_distance", "D", "nxt", "roadmap", "via_flag", "walk_nodes")
 
     def __init__(self, **kw):
         for k, v in kw.items():
@@ -411,7 +415,8 @@ def tour_edge_query(cloud, nodes, radius, stage=None):
     return ops.clearance_segments(cloud, torch.stack([a, b], dim=1).reshape(-1, 3), radius, n_traj=a.shape[0])
 
 
-def plan_tour(points_or_cloud_or_model, poses, quats=None, clearance_radius=None, closed=False, max_moves=None):
+def plan_tour(points_or_cloud_or_model, poses, quats=None, clearance_radius=None, closed=False, max_moves=None, via=None, via_k=12,
+              via_max_edge=None):
     """A short visiting order through view poses whose every straight leg keeps clearance_radius from the cloud.
     poses (n,3), 2 <= n <= 256: row 0 is where the tour starts (the robot), the others are the views (select_views' sel.poses);
     quats (n,4) or None.  Every pair of nodes is put to the swept clearance query (edge_clearance); the pairs it finds nothing near
@@ -421,9 +426,15 @@ def plan_tour(points_or_cloud_or_model, poses, quats=None, clearance_radius=None
     through other nodes; nodes no open route reaches are reported in `unreachable` and left out.  closed=True: the tour returns to
     node 0.  clearance_radius=None: no query, every leg is open.
     points_or_cloud_or_model: (N,3) points on the device, an ops.PackedCloud (sorted or not) or a ModelTraj (its cloud).
-    -> Tour.  Launches only, then one copy to the host."""
+    via (F,3), optional: free-space nodes (synth.roadmap_lattice, say), n + F <= 16 384; clearance_radius is then required.  A
+    roadmap (build_roadmap, k = via_k, max_edge = via_max_edge) over [poses; via] gives every pair of tour nodes its shortest
+    collision-checked route, and a leg takes it wherever that beats the straight leg: a view behind a wall is reached through the
+    doorway.  A via node that coincides with a pose is left out (its row is made non-finite: the index of every other node stays).
+    -> Tour.  Launches only, then one copy to the host (with via: one read-back per batch of route sweeps before it)."""
     cloud, pts = _clearance_cloud(points_or_cloud_or_model, "plan_tour")
     n, r, max_moves = ops.check_tour(poses, quats, clearance_radius, closed, max_moves)
+    if via is not None:
+        return _plan_tour_via(cloud, pts, poses, quats, n, r, closed, max_moves, via, via_k, via_max_edge)
     if cloud is None:
         if not pts.is_cuda:
             raise ValueError(f"plan_tour: points must live on a HIP device, got {pts.device}")
@@ -463,4 +474,225 @@ def plan_tour(points_or_cloud_or_model, poses, quats=None, clearance_radius=None
     w = torch.as_tensor(walk, dtype=torch.int64, device=dev)
     return Tour(order=order, unreachable=unreachable, walk=walk, poses=nodes[w], quats=qs[w] if qs is not None else None,
                 length=int(hdr[3]) * ops.TOUR_UNIT, nn_length=int(hdr[4]) * ops.TOUR_UNIT, length_fixed=int(hdr[3]),
-                nn_length_fixed=int(hdr[4]), moves=int(hdr[1]), converged=bool(hdr[2]), blocked=blocked, edge_distance=dist, D=D, nxt=nxt)
+                nn_length_fixed=int(hdr[4]), moves=int(hdr[1]), converged=bool(hdr[2]), blocked=blocked, edge_distance=dist, D=D, nxt=nxt,
+                roadmap=None, via_flag=None, walk_nodes=None)
+
+
+class RoadmapRoutes:
+    """What Roadmap.routes returns: sources (the list asked for), D (S,M) int64 and pred (S,M) int32 on the device — the shortest
+    route length from each source to every node over the open edges (2^62 where none exists) and, for each node, the lowest
+    neighbour a shortest route arrives from (-1 for the source and the unreachable) — and sweeps, the relaxation sweeps it took."""
+    __slots__ = ("sources", "D", "pred", "sweeps")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+class Roadmap:
+    """What build_roadmap returns, device tensors unless noted: nodes (M,3) f32; nbr (M,k) int32: each node's k nearest others (-1:
+    none); length_fixed (M,k) int64: those edges' lengths in units of 2^-20 m; open (M,k) bool: the edges that keep the clearance
+    radius; edge_distance (M,k) f32: a blocked edge's distance to the cloud, +inf where open (and in an empty slot); isolated (M,)
+    bool: the nodes no open edge touches; n_open (an int): the open edges, each unordered pair counted once."""
+    __slots__ = ("nodes", "nbr", "length_fixed", "open", "edge_distance", "isolated", "n_open", "_edges")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    def host_edges(self):
+        """(u, v, L) on the host: both directions of every open slot (synth.roadmap_edges), copied once — what a walk falls back
+        on when coincident nodes tie its predecessors in a circle."""
+        if getattr(self, "_edges", None) is None:
+            from .synth import roadmap_edges   # (numpy only)
+            self._edges = roadmap_edges(self.nbr.cpu().numpy(), self.length_fixed.cpu().numpy(), self.open.cpu().numpy())
+        return self._edges
+
+    def walk(self, routes, row, pred_row, dst):
+        """routes.sources[row], ..., dst: along pred_row (that row of routes.pred on the host), or over the tight edges where
+        zero-length edges between coincident nodes close the predecessors into a circle; None when dst is not reached."""
+        from .synth import roadmap_walk   # (numpy only)
+        return roadmap_walk(pred_row, routes.sources[row], dst, tight=lambda: (routes.D[row].cpu().numpy(), self.host_edges()))
+
+    def routes(self, sources, sweeps_per_check=8):
+        """Shortest routes from up to 256 source nodes to every node -> RoadmapRoutes."""
+        _, _, _, _, src = ops.check_roadmap(self.nodes, self.nbr.shape[1], None, None, sources, sweeps_per_check)
+        if src is None:
+            raise ValueError("sources must be given")
+        D, pred, sweeps = ops.roadmap_routes(self.nbr, self.length_fixed, self.open, src, sweeps_per_check)
+        return RoadmapRoutes(sources=src, D=D, pred=pred, sweeps=sweeps)
+
+    def route(self, src, dst):
+        """The shortest open route between two nodes -> (walk: the node indices src, ..., dst; length_fixed; length in metres), or
+        None when there is none.  One routes() call and one copy to the host."""
+        M = self.nodes.shape[0]
+        for name, v in (("src", src), ("dst", dst)):
+            if isinstance(v, bool) or not hasattr(v, "__index__") or not 0 <= v < M:
+                raise ValueError(f"{name} must be a node index in [0, {M}), got {v!r}")
+        r = self.routes([int(src)])
+        h = torch.cat([r.D[0, dst].reshape(1).view(torch.int32), r.pred[0]]).cpu()
+        walk = self.walk(r, 0, h[2:].numpy(), dst)
+        if walk is None:
+            return None
+        fixed = int(h[:2].view(torch.int64))
+        return walk, fixed, fixed * ops.TOUR_UNIT
+
+
+def _device_cloud(cloud, pts, what):
+    """The packed cloud of a _clearance_cloud pair: the points are packed here, which is the first GPU call."""
+    if cloud is None:
+        if not pts.is_cuda:
+            raise ValueError(f"{what}: points must live on a HIP device, got {pts.device}")
+        cloud = ops.PackedCloud(pts.to(torch.float32))
+    return cloud
+
+
+def _build_roadmap(cloud, nodes, r, k, max_edge):
+    """build_roadmap behind its checks: nodes (M,3) f32 contiguous on the cloud's device."""
+    M = nodes.shape[0]
+    nbr, length = ops.roadmap_knn(nodes, k, max_edge)
+    # the edge stage: the filled slots, each asked from the lower index
+    i = torch.arange(M, device=nodes.device, dtype=torch.int64)[:, None].expand(M, k).reshape(-1)
+    slot = torch.nonzero(nbr.reshape(-1) >= 0).reshape(-1)
+    i, j = i[slot], nbr.reshape(-1)[slot].to(torch.int64)
+    lo, hi = torch.minimum(i, j), torch.maximum(i, j)
+    opened = torch.zeros(M * k, dtype=torch.bool, device=nodes.device)
+    dist = torch.full((M * k,), float("inf"), dtype=torch.float32, device=nodes.device)
+    if slot.numel():
+        d, idx, _ = ops.clearance_edges(cloud, nodes[lo], nodes[hi], r)
+        free = (idx == -1) & (length.reshape(-1)[slot] <= ops.ROADMAP_MAX_LEN)
+        opened[slot] = free
+        dist[slot] = d
+        lo, hi = lo[free], hi[free]
+    opened, dist = opened.view(M, k), dist.view(M, k)
+    touched = torch.zeros(M, dtype=torch.bool, device=nodes.device)
+    touched[lo] = True
+    touched[hi] = True
+    pairs = lo * M + hi
+    n_open = int(torch.unique(pairs).numel())
+    return Roadmap(nodes=nodes, nbr=nbr, length_fixed=length, open=opened, edge_distance=dist, isolated=~touched, n_open=n_open,
+                   _edges=None)
+
+
+def build_roadmap(points_or_cloud_or_model, nodes, clearance_radius, k=12, max_edge=None):
+    """A roadmap over caller-supplied free-space nodes: nodes (M,3), 2 <= M <= 16 384 (synth.roadmap_lattice makes a
+    lattice); every node is joined to its k <= 32 nearest others (no further than max_edge when that is given) by the exact f64 key
+    (d2, j), ties to the lower index, and an edge is open when the swept clearance query (edge_clearance, asked from the lower index)
+    finds no cloud point within clearance_radius of it.  The graph is undirected: a pair is an edge when either list names it open.
+    Lengths are integers in units of 2^-20 m, so routes over it are the same bits in every run.  -> Roadmap."""
+    cloud, pts = _clearance_cloud(points_or_cloud_or_model, "build_roadmap")
+    if clearance_radius is None:
+        raise ValueError("clearance_radius must be a finite number > 0, got None")
+    _, k, r, me, _ = ops.check_roadmap(nodes, k, clearance_radius, max_edge)
+    cloud = _device_cloud(cloud, pts, "build_roadmap")
+    q = nodes.detach().to(device=cloud.device, dtype=torch.float32).contiguous()
+    return _build_roadmap(cloud, q, r, k, max_edge)
+
+
+class PlannedPath:
+    """What plan_path returns: poses (L,3) f32 on the device: start, the free-space nodes of the route, goal — every leg keeps the
+    clearance radius; length in metres (f64 from the integer length_fixed, units of 2^-20 m); walk: the route as indices into
+    [start; goal; via]; roadmap: the Roadmap it ran over."""
+    __slots__ = ("poses", "length", "length_fixed", "walk", "roadmap")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def _point3(p, name, device):
+    t = torch.as_tensor(p, dtype=torch.float32).detach()
+    if t.numel() != 3:
+        raise ValueError(f"{name} must hold 3 coordinates, got shape {tuple(t.shape)}")
+    return t.reshape(1, 3).to(device)
+
+
+def _check_via(via, n, what="via"):
+    if not torch.is_tensor(via) or not via.is_floating_point() or via.dim() != 2 or via.shape[1] != 3 or via.shape[0] == 0:
+        raise ValueError(f"{what} must be a floating-point tensor of shape (F,3) with F > 0, got "
+                         f"{tuple(via.shape) if torch.is_tensor(via) else type(via).__name__}")
+    if n + via.shape[0] > ops.ROADMAP_MAX_NODES:
+        raise ValueError(f"{what}: the roadmap holds at most {ops.ROADMAP_MAX_NODES} nodes, got {n} + {via.shape[0]}")
+
+
+def _join_nodes(head, via):
+    """[head; via] with the via rows that coincide with a head row made non-finite: such a node has no edge, and no zero-length
+    edge ties it to its twin."""
+    twin = (via[:, None, :] == head[None, :, :]).all(dim=2).any(dim=1)
+    return torch.cat([head, torch.where(twin[:, None], torch.full_like(via, float("nan")), via)]).contiguous()
+
+
+def plan_path(points_or_cloud_or_model, start, goal, via, clearance_radius, k=12, max_edge=None):
+    """A path from start to goal that keeps clearance_radius from the cloud, over the free-space nodes `via` (F,3): the shortest
+    route of the roadmap over [start; goal; via] (build_roadmap).  -> PlannedPath, whose poses are an initial path for
+    ModelTraj.sharing_cloud_of(..., clearance_mode='segments'); ValueError when no route exists."""
+    cloud, pts = _clearance_cloud(points_or_cloud_or_model, "plan_path")
+    _check_via(via, 2)
+    if clearance_radius is None:
+        raise ValueError("clearance_radius must be a finite number > 0, got None")
+    k, r, _ = ops.check_roadmap_options(k, clearance_radius, max_edge)
+    ends = torch.cat([_point3(start, "start", "cpu"), _point3(goal, "goal", "cpu")])
+    cloud = _device_cloud(cloud, pts, "plan_path")
+    dev = cloud.device
+    nodes = _join_nodes(ends.to(dev), via.detach().to(device=dev, dtype=torch.float32))
+    rm = _build_roadmap(cloud, nodes, r, k, max_edge)
+    got = rm.route(0, 1)
+    if got is None:
+        raise ValueError(f"plan_path: no route from start to goal keeps {r} m from the cloud over these {via.shape[0]} via nodes")
+    walk, fixed, length = got
+    return PlannedPath(poses=nodes[torch.as_tensor(walk, dtype=torch.int64, device=dev)], length=length, length_fixed=fixed, walk=walk,
+                       roadmap=rm)
+
+
+def _plan_tour_via(cloud, pts, poses, quats, n, r, closed, max_moves, via, via_k, via_max_edge):
+    """plan_tour with a roadmap behind its legs (its arguments are checked already)."""
+    _check_via(via, n)
+    if r is None:
+        raise ValueError("plan_tour: via needs a clearance_radius (a finite number > 0), got None")
+    k, _, _ = ops.check_roadmap_options(via_k, r, via_max_edge)
+    cloud = _device_cloud(cloud, pts, "plan_tour")
+    dev = cloud.device
+    nodes = poses.detach().to(device=dev, dtype=torch.float32).contiguous()
+    qs = quats.detach().to(device=dev, dtype=torch.float32).contiguous() if quats is not None else None
+    allnodes = _join_nodes(nodes, via.detach().to(device=dev, dtype=torch.float32))
+    M = allnodes.shape[0]
+    rm = _build_roadmap(cloud, allnodes, r, k, via_max_edge)
+    routes = rm.routes(list(range(n)))
+    E = n * (n - 1) // 2
+    i, j = ops.tour_edge_ends(n, dev)
+    dist = torch.full((n, n), float("inf"), dtype=torch.float32, device=dev)
+    d, idx, _ = tour_edge_query(cloud, nodes, r)
+    dist[i, j] = d
+    dist[j, i] = d
+    buf, flag = ops.tour_plan_via(nodes, idx, routes.D, closed, max_moves)
+    h = torch.cat([buf, idx.view(torch.uint8), routes.pred.reshape(-1).view(torch.uint8), flag.reshape(-1)]).cpu()
+    lay = ops.tour_layout(n)
+    hdr = h[:64].view(torch.int64)
+    m = int(hdr[0])
+    order = h[lay["order"]:lay["order"] + 4 * n].view(torch.int32)[:m].to(torch.int64)
+    unreachable = h[lay["unreachable"]:lay["unreachable"] + n] != 0
+    D = h[lay["D"]:lay["D"] + 8 * n * n].view(torch.int64).reshape(n, n).clone()
+    nxt = h[lay["nxt"]:lay["nxt"] + 4 * n * n].view(torch.int32).reshape(n, n).clone()
+    o = lay["total"]
+    hit = h[o:o + 4 * E].view(torch.int32) != -1
+    blocked = torch.zeros((n, n), dtype=torch.bool)
+    ih, jh = i.cpu(), j.cpu()
+    blocked[ih, jh] = hit
+    blocked[jh, ih] = hit
+    o += 4 * E
+    pred = h[o:o + 4 * n * M].view(torch.int32).reshape(n, M).numpy()
+    o += 4 * n * M
+    via_flag = h[o:o + n * n].reshape(n, n) != 0
+    from .synth import tour_walk   # (numpy only)
+    walk = tour_walk(order.tolist(), nxt.numpy(), closed)
+    walk_nodes, q_of = [walk[0]], [walk[0]]   # q_of: the tour node whose quaternion each walk node takes
+    for u, v in zip(walk, walk[1:]):
+        hop = rm.walk(routes, u, pred[u], v)[1:] if via_flag[u, v] else [v]
+        walk_nodes += hop
+        q_of += [x if x < n else v for x in hop]
+    w = torch.as_tensor(walk_nodes, dtype=torch.int64, device=dev)
+    return Tour(order=order, unreachable=unreachable, walk=walk, poses=allnodes[w],
+                quats=qs[torch.as_tensor(q_of, dtype=torch.int64, device=dev)] if qs is not None else None,
+                length=int(hdr[3]) * ops.TOUR_UNIT, nn_length=int(hdr[4]) * ops.TOUR_UNIT, length_fixed=int(hdr[3]),
+                nn_length_fixed=int(hdr[4]), moves=int(hdr[1]), converged=bool(hdr[2]), blocked=blocked, edge_distance=dist, D=D, nxt=nxt,
+                roadmap=rm, via_flag=via_flag, walk_nodes=walk_nodes)
