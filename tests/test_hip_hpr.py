@@ -190,6 +190,29 @@ def test_hpr_batched_many_small_segments(dev):
     assert idx.numel() == 0 and voff.tolist() == [0, 0, 0] and status.tolist() == [1, 1] and mask.numel() == 0
 
 
+def test_hpr_batched_ten_thousand_segments_walked_eight_to_a_wave(dev):
+    """10 000 viewpoints of 24 points on a sphere of radius 3: round 0 has about four candidates per segment, more than the
+    32 768 from which the host launches k_owner_claim_sub (eight walks to a wave), and the segments are far too small for the
+    sample phase.  Every 97th segment against Qhull on that segment alone; two calls agree bit for bit."""
+    from oracle import oracle
+    from trajectory_optimization_amd import ops
+    rng = np.random.default_rng(17)
+    nseg, per = 10_000, 24
+    v = rng.normal(size=(nseg, per, 3))
+    v *= 3.0 / np.linalg.norm(v, axis=2, keepdims=True)
+    pts = (v + rng.uniform(-8, 8, (nseg, 1, 3))).astype(np.float32)
+    offs = np.arange(nseg + 1) * per
+    cloud = torch.from_numpy(pts.reshape(-1, 3)).to(dev)
+    idx, voff, mask, status = ops.hidden_pts_removal_batched(cloud, offs)
+    idx2, voff2, mask2, status2 = ops.hidden_pts_removal_batched(cloud, offs)
+    assert torch.equal(idx, idx2) and torch.equal(voff, voff2) and torch.equal(mask, mask2) and torch.equal(status, status2)
+    assert voff[0] == 0 and voff[-1] == len(idx)
+    idx, voff, status = idx.cpu().numpy().astype(np.int64), voff.numpy(), status.cpu().numpy()
+    for s in range(0, nseg, 97):
+        assert status[s] == 0, s
+        assert np.array_equal(idx[voff[s]:voff[s + 1]] - offs[s], oracle.hidden_pts_removal(pts[s])[0]), s
+
+
 def test_hull_all_points_on_a_sphere_retries_with_a_larger_face_pool(dev):
     """Every point a hull vertex: the default face pool / face lists run out (TOHIP_ENOSPC) and ops retries with 4x the bytes."""
     from scipy.spatial import ConvexHull

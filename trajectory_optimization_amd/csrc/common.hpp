@@ -370,6 +370,36 @@ __device__ __forceinline__ double block_sum_double(double v, double* lds /* >= o
     return r;
 }
 
+// Ordered compaction, a block of TO_BLOCK threads per 1024-item tile (four trips): count the kept items of every tile, scan the
+// counts (launch_scan_tiles), place the kept items from the tile's offset on, in order.  `keep(i)` is asked once per item by its
+// thread (all threads, so it answers false beyond the end itself); what it loaded for `emit(i, dst)` it leaves in its captures.
+template <class I, class Keep>
+__device__ __forceinline__ void tile_count_kept(I tile0, int* __restrict__ tile_cnt, Keep keep) {
+    __shared__ int wave_cnt[TO_WAVES_PER_BLOCK];
+    int cnt = 0;
+    for (int k = 0; k < 4; ++k) cnt += __popcll(__ballot(keep(tile0 + k * TO_BLOCK + threadIdx.x)));
+    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+}
+template <class I, class Keep, class Emit>
+__device__ __forceinline__ void tile_place_kept(I tile0, int base, Keep keep, Emit emit) {
+    __shared__ int wave_cnt[TO_WAVES_PER_BLOCK];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int k = 0; k < 4; ++k) {
+        const I i = tile0 + k * TO_BLOCK + threadIdx.x;
+        const bool kept = keep(i);
+        const unsigned long long bal = __ballot(kept);
+        if (lane == 0) wave_cnt[wave] = __popcll(bal);
+        __syncthreads();
+        int off = base;
+        for (int w = 0; w < wave; ++w) off += wave_cnt[w];
+        if (kept) emit(i, off + __popcll(bal & ((1ull << lane) - 1ull)));
+        base += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+        __syncthreads();
+    }
+}
+
 // Rotation matrix (row-major R, camera->world) from a quaternion, homogeneous quadratic form.
 __host__ __device__ inline void quat_to_R(const float q[4], float R[9]) {
     const float w = q[0], x = q[1], y = q[2], z = q[3];

@@ -324,12 +324,17 @@ __device__ __forceinline__ int block_alloc(int* counter, int want) {
     return base + before + incl - want;
 }
 
-// segment of expanded index i: the largest s with seg_off[s] <= i
+// Segments are searched in two index spaces: expanded indices (segment s starts at seg_off[s]) and rows of the caller's source
+// array, where no earlier segment has spent a slot on its origin (segment s starts at seg_off[s] - s).
+struct Expanded { static __device__ __forceinline__ int first(const Bufs& b, int s) { return b.seg_off[s]; } };
+struct SourceRows { static __device__ __forceinline__ int first(const Bufs& b, int s) { return b.seg_off[s] - s; } };
+// segment of index i: the largest s with first(s) <= i
+template <class Space = Expanded>
 __device__ __forceinline__ int find_seg(const Bufs& b, int i) {
     int lo = 0, hi = b.nseg;
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
-        if (b.seg_off[mid] <= i) lo = mid; else hi = mid;
+        if (Space::first(b, mid) <= i) lo = mid; else hi = mid;
     }
     return lo;
 }
@@ -337,20 +342,17 @@ __device__ __forceinline__ int find_seg(const Bufs& b, int i) {
 // 127 boundaries: the search runs ONCE per wave on the scalar unit (r06; every lane's own search was seven dependent vector loads per
 // point — most of what k_bbox, k_sort_keys, k_load, k_norm_max_seg and k_flip_seg cost for 128 views).  e0 must be wave-uniform;
 // *end = the first index behind the segment.  The lanes' segment: wave_seg's if e0 + 63 < *end, their own find_seg otherwise.
+template <class Space = Expanded>
 __device__ __forceinline__ int wave_seg(const Bufs& b, int e0, int* end) {
-    const int e = __builtin_amdgcn_readfirstlane(e0);
-    int lo = 0, hi = b.nseg;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (b.seg_off[mid] <= e) lo = mid; else hi = mid;
-    }
-    *end = b.seg_off[lo + 1];
+    const int lo = find_seg<Space>(b, __builtin_amdgcn_readfirstlane(e0));
+    *end = Space::first(b, lo + 1);
     return lo;
 }
+template <class Space = Expanded>
 __device__ __forceinline__ int lane_seg(const Bufs& b, int e0, int e) {
     int end;
-    const int s0 = wave_seg(b, e0, &end);
-    return e0 + 63 < end ? s0 : find_seg(b, e);   // (wave-uniform branch)
+    const int s0 = wave_seg<Space>(b, e0, &end);
+    return e0 + 63 < end ? s0 : find_seg<Space>(b, e);   // (wave-uniform branch)
 }
 
 __device__ __forceinline__ int* ccnt(const Bufs& b, int par, int s) { return b.ctrl + kCtrlInts + (par * kSubLists + s) * kCntStride; }
@@ -412,58 +414,78 @@ __global__ void __launch_bounds__(TO_BLOCK) k_bbox_init(Bufs b) {
     if (i < b.nseg) b.seg_nan[i] = 0;
 }
 
-// Every wave walks ONE contiguous run of points and keeps the running box of the segment it is in in registers; the box
-// goes to memory (six atomics) when the run leaves the segment and at the end — a few thousand atomics in all, where one
-// set per 64 points serialised on the segments' addresses (1.6 ms for 13.6 M points).
-__global__ void __launch_bounds__(TO_BLOCK) k_bbox(Bufs b, const float* __restrict__ pts, int with_origin) {
+// A per-segment reduction over n items laid out segment after segment (k_bbox, k_norm_max_seg).  Every wave walks ONE contiguous
+// run and keeps the running value of the segment it is in in registers; the value goes to memory when the run leaves the segment
+// and at the end — a few thousand atomics in all, where one set per 64 items serialised on the segments' addresses (1.6 ms for
+// the boxes of 13.6 M points).  item = load(i, sg) for an item inside the run (a value-initialised item is neutral); add(item) into
+// the running value; commit(sg): wave-reduce the running value, send it to segment sg, start afresh (all lanes); straddle(sg, item):
+// the 64 items lie on a segment boundary and are settled one by one (sg < 0: no item).
+template <class Space, class Load, class Add, class Commit, class Straddle>
+__device__ __forceinline__ void walk_segment_runs(const Bufs& b, int n, Load load, Add add, Commit commit, Straddle straddle) {
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * TO_WAVES_PER_BLOCK + (threadIdx.x >> 6), nwaves = gridDim.x * TO_WAVES_PER_BLOCK;
-    const int chunk = ((b.m1 + nwaves - 1) / nwaves + 63) / 64 * 64;
+    const int chunk = ((n + nwaves - 1) / nwaves + 63) / 64 * 64;
     const int64_t begin64 = (int64_t)wave * chunk;
-    const int begin = begin64 < b.m1 ? (int)begin64 : b.m1, end = begin64 + chunk < b.m1 ? (int)(begin64 + chunk) : b.m1;
+    const int begin = begin64 < n ? (int)begin64 : n, end = begin64 + chunk < n ? (int)(begin64 + chunk) : n;
     int cur = -1, cur_seg = -1, cur_end = -1;
+    for (int i0 = begin; i0 < end; i0 += 64) {
+        const int i = i0 + lane;
+        int sg = -1;
+        decltype(load(0, 0)) item{};
+        if (i0 >= cur_end) cur_seg = wave_seg<Space>(b, i0, &cur_end);   // (the run has left the segment it was in: wave-uniform)
+        if (i < end) {
+            sg = i0 + 63 < cur_end ? cur_seg : find_seg<Space>(b, i);
+            item = load(i, sg);
+        }
+        const int s0 = __shfl(sg, 0);  // lane 0 is always inside the run
+        if (__all(sg == s0 || sg < 0)) {
+            if (s0 != cur) {
+                if (cur >= 0) commit(cur);
+                cur = s0;
+            }
+            add(item);
+        } else {
+            if (cur >= 0) commit(cur);
+            cur = -1;
+            straddle(sg, item);
+        }
+    }
+    if (cur >= 0) commit(cur);
+}
+
+struct BoxItem { unsigned key[3]; bool ok[3]; };
+__global__ void __launch_bounds__(TO_BLOCK) k_bbox(Bufs b, const float* __restrict__ pts, int with_origin) {
     unsigned lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-    auto flush = [&]() {  // wave-uniform `cur`: called by all lanes
-        if (cur >= 0) {
+    walk_segment_runs<Expanded>(b, b.m1,
+        [&](int e, int sg) {
+            BoxItem it{};
+            float c[3];
+            source_point(b, pts, with_origin, e, sg, &c[0], &c[1], &c[2]);
+            for (int k = 0; k < 3; ++k) {
+                if (c[k] == c[k]) { it.key[k] = fkey(c[k]); it.ok[k] = true; }  // NaN coordinates take no part in the box ...
+                else b.seg_nan[sg] = 1;                                          // ... and void the segment (scipy: "Points cannot contain NaN")
+            }
+            return it;
+        },
+        [&](const BoxItem& it) {
+            for (int k = 0; k < 3; ++k)
+                if (it.ok[k]) { lo[k] = min(lo[k], it.key[k]); hi[k] = max(hi[k], it.key[k]); }
+        },
+        [&](int sg) {
             for (int k = 0; k < 3; ++k) {
                 for (int s = 32; s > 0; s >>= 1) {
                     lo[k] = min(lo[k], (unsigned)__shfl_xor((int)lo[k], s));
                     hi[k] = max(hi[k], (unsigned)__shfl_xor((int)hi[k], s));
                 }
             }
-            if (lane == 0)
-                for (int k = 0; k < 3; ++k) { atomicMin(&b.seg_bbox[6 * cur + k], lo[k]); atomicMax(&b.seg_bbox[6 * cur + 3 + k], hi[k]); }
-        }
-        for (int k = 0; k < 3; ++k) { lo[k] = 0xffffffffu; hi[k] = 0u; }
-    };
-    for (int e0 = begin; e0 < end; e0 += 64) {
-        const int e = e0 + lane;
-        int sg = -1;
-        unsigned key[3] = {0u, 0u, 0u};
-        bool ok[3] = {false, false, false};
-        if (e0 >= cur_end) cur_seg = wave_seg(b, e0, &cur_end);   // (the run has left the segment it was in: wave-uniform)
-        if (e < end) {
-            sg = e0 + 63 < cur_end ? cur_seg : find_seg(b, e);
-            float c[3];
-            source_point(b, pts, with_origin, e, sg, &c[0], &c[1], &c[2]);
-            for (int k = 0; k < 3; ++k) {
-                if (c[k] == c[k]) { key[k] = fkey(c[k]); ok[k] = true; }  // NaN coordinates take no part in the box ...
-                else b.seg_nan[sg] = 1;                                    // ... and void the segment (scipy: "Points cannot contain NaN")
-            }
-        }
-        const int s0 = __shfl(sg, 0);  // lane 0 is always inside the run
-        if (__all(sg == s0 || sg < 0)) {
-            if (s0 != cur) { flush(); cur = s0; }
+            if ((threadIdx.x & 63) == 0)
+                for (int k = 0; k < 3; ++k) { atomicMin(&b.seg_bbox[6 * sg + k], lo[k]); atomicMax(&b.seg_bbox[6 * sg + 3 + k], hi[k]); }
+            for (int k = 0; k < 3; ++k) { lo[k] = 0xffffffffu; hi[k] = 0u; }
+        },
+        [&](int sg, const BoxItem& it) {
             for (int k = 0; k < 3; ++k)
-                if (ok[k]) { lo[k] = min(lo[k], key[k]); hi[k] = max(hi[k], key[k]); }
-        } else {  // the 64 points straddle a segment boundary: settle them one by one
-            flush();
-            cur = -1;
-            for (int k = 0; k < 3; ++k)
-                if (ok[k]) { atomicMin(&b.seg_bbox[6 * sg + k], key[k]); atomicMax(&b.seg_bbox[6 * sg + 3 + k], key[k]); }
-        }
-    }
-    flush();
+                if (it.ok[k]) { atomicMin(&b.seg_bbox[6 * sg + k], it.key[k]); atomicMax(&b.seg_bbox[6 * sg + 3 + k], it.key[k]); }
+        });
 }
 
 // ONE segment (r06): the walk above keeps a wave on one long run so that a segment's six words see few atomics — 512 waves on a
@@ -811,16 +833,59 @@ __global__ void __launch_bounds__(TO_BLOCK) k_assign0(Bufs b) {
 //   kCtrlAccepted    regions accepted this round
 // The tail prepares the NEXT round (per-face reset, next candidate list), so a round has no reset launch of its own.
 
-// The ownership propagation of a round in ONE launch, one WAVE per candidate: breadth first over the region the candidate's
-// apex sees, the frontier in LDS, every (frontier face, edge) pair on its own lane — a level costs one chain of dependent
-// loads (neighbour id -> its owner and plane -> the claim) whatever the frontier's size, where one thread per candidate
-// paid that chain once per face.  A face is claimed unless a better candidate holds it (worse ones are robbed); every claim
-// is logged (LDS, flushed to the block's sub-list of claimed faces with one counter update per candidate).  Which faces end
-// up with a LOSING candidate depends on arrival order, the winners' regions do not: k_accept admits a candidate only if it
-// owns every face its apex sees and borders no better region, so an incomplete walk (frontier or claim budget exhausted, a
-// face stolen later) can only cost that candidate this round; a round that accepts nobody is repeated with k_owner_prop
-// run to convergence.
+// The ownership propagation of a round in ONE launch: every candidate walks, breadth first, the region its apex sees, the
+// frontier in LDS, every (frontier face, edge) pair on its own lane — a level costs one chain of dependent loads (neighbour id ->
+// its owner and plane -> the claim) whatever the frontier's size, where one thread per candidate paid that chain once per face.
+// The RULE of that walk has one text, the device functions below (round_begin, claim_admit, claim_edge, ClaimLog); the two
+// kernels behind them, k_owner_claim and k_owner_claim_sub, are two schedules of it.
 constexpr int kClaimFront = 128, kClaimMax = 4096, kClaimLog = 192;
+
+// candidate o is not accepted this round (fflags bit 1)
+__device__ __forceinline__ void turn_down(const Bufs& b, int o) { atomicAnd(&b.fflags[o], ~2); }
+
+// Block 0's housekeeping at the start of a round, in the launch that gives the verdict (a claim walk; k_accept in the careful path).
+// Nothing has been inserted yet this round: the staged count is the face count; it is published here for the kernels that run
+// while k_new_faces raises the staged one.  The next round's lists start empty.
+__device__ __forceinline__ void round_begin(const Bufs& b, int par) {
+    if (blockIdx.x != 0) return;
+    if (threadIdx.x == 0) { b.ctrl[kCtrlNFaces] = min(b.ctrl[kCtrlNFaces + 8], b.fcap); b.ctrl[kCtrlAccepted] = 0; }
+    if (threadIdx.x < kSubLists) { *ccnt(b, par ^ 1, threadIdx.x) = 0; *ocnt(b, par ^ 1, threadIdx.x) = 0; }
+}
+
+// Does candidate o walk this round?  Asked by groups of W consecutive lanes, a candidate per group (o = kNone: a group that has
+// none to ask about), all lanes of the wave taking part.  Not a candidate without a point outside its face (never seen), not
+// one whose face a better one has taken — and not one whose own face is seen by the apex of a BETTER candidate next door: it has
+// lost before it starts, since that neighbour's walk takes this face at its first level, and not walking keeps its claims off the
+// faces that worse candidates need (it is turned down here).  Hands back the candidate's rank and its apex; the apex's coordinates
+// are requested before the look at the neighbours, not after it: two chains of dependent loads side by side.
+template <int W>
+__device__ __forceinline__ bool claim_admit(const Bufs& b, int o, int lane, unsigned long long* po, double* px, double* py, double* pz) {
+    const int gl = lane % W;
+    bool ok = false, doomed = false;
+    if (o >= 0) {
+        const unsigned long long ax = b.fmax[o];
+        const int n0 = gl < 3 ? b.fn[3 * o + gl] : kNone;   // for the look at the neighbours below: requested with the apex
+        if (ax == 0ull) {
+            if (gl == 0) { b.fowner[o] = kNone; turn_down(b, o); }
+        } else if (__hip_atomic_load(&b.fowner[o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == o) {
+            ok = true;
+            *po = b.fprio[o];
+            const int apex = apex_pos(ax);
+            *px = b.px[apex]; *py = b.py[apex]; *pz = b.pz[apex];
+            if (n0 >= 0 && (b.fflags[n0] & 3) == 3 && b.fprio[n0] < *po) {
+                const unsigned long long an = b.fmax[n0];
+                if (an != 0ull) {
+                    const int pa = apex_pos(an);
+                    doomed = plane_dist(b.frec[o], b.px[pa], b.py[pa], b.pz[pa]) > 0.0;
+                }
+            }
+        }
+    }
+    const unsigned long long gm = W == 64 ? ~0ull : ((1ull << (W & 63)) - 1ull) << (lane - gl);
+    const bool gd = (__ballot(doomed) & gm) != 0ull;   // (the whole wave's ballot; this group's bits)
+    if (ok && gd && gl == 0) turn_down(b, o);
+    return ok && !gd;
+}
 
 // Two regions that share a horizon edge (u, v) can BOTH go in this round when the new faces on it, (u, v, mine) and (v, u, theirs),
 // meet convexly: their apex lies strictly below the plane of my new face (and then mine below theirs).  In the sequential order
@@ -843,79 +908,98 @@ __device__ __forceinline__ bool convex_across(const Bufs& b, int cg, int k, doub
     const double d = nx * tx + ny * ty + nz * tz;
     return d < 0.0 && d * d > (kConvexTol * kConvexTol) * (nx * nx + ny * ny + nz * nz) * (tx * tx + ty * ty + tz * tz);
 }
-// The fast path's walk (r06) also DECIDES who is accepted, so the round needs no k_accept launch.  k_accept's rule —
-// a candidate stays accepted iff it owns every face its apex sees and no better candidate owns a face across its horizon — is
-// settled where ownership changes hands: a walk that meets a face it sees in better hands, or a better owner across its horizon,
-// fails itself; a walk that robs a face, or finds a worse owner across its horizon, fails that one; an incomplete walk fails itself.
-// Every claimed face's three neighbours are looked at AFTER the claim's CAS has returned (the next level of the walk), and claims
-// and looks are atomics at the memory side: of two candidates that take adjacent faces at the same time at least one sees the
-// other, whichever order the CASes land in.  The verdict is what k_accept computed from the final ownership: the accepted bit
-// (fflags bit 1) of the candidates nobody failed.  Block 0 does k_accept's housekeeping.
-__global__ void __launch_bounds__(TO_BLOCK) k_owner_claim(Bufs b, int round, int par) {
-    __shared__ int fr[TO_WAVES_PER_BLOCK][2][kClaimFront];
-    if (b.ctrl[kCtrlError] != 0) return;   // (see round_dead)
-    if (blockIdx.x == 0) {
-        // nothing has been inserted yet this round: the staged count is the face count; it is published here for the
-        // kernels that run while k_new_faces raises the staged one.  The next round's lists start empty.
-        if (threadIdx.x == 0) { b.ctrl[kCtrlNFaces] = min(b.ctrl[kCtrlNFaces + 8], b.fcap); b.ctrl[kCtrlAccepted] = 0; }
-        if (threadIdx.x < kSubLists) { *ccnt(b, par ^ 1, threadIdx.x) = 0; *ocnt(b, par ^ 1, threadIdx.x) = 0; }
+
+// One (face, edge) pair of candidate o's walk: face cg of its frontier, the neighbour n across edge k.  A face the apex sees is
+// claimed unless a better candidate holds it (worse ones are robbed).  Which faces end up with a LOSING candidate depends on arrival
+// order, the winners' regions do not: a candidate is admitted only if it owns every face its apex sees and borders no better region,
+// so an incomplete walk (frontier or claim budget exhausted, a face stolen later) can only cost that candidate this round; a round
+// that accepts nobody is repeated with k_owner_prop run to convergence.
+// The walk also DECIDES who is accepted (r06), so the fast path needs no k_accept launch.  k_accept's rule — a candidate stays
+// accepted iff it owns every face its apex sees and no better candidate owns a face across its horizon — is settled where ownership
+// changes hands: a walk that meets a face it sees in better hands, or a better owner across its horizon, fails itself (fail_me); a
+// walk that robs a face, or finds a worse owner across its horizon, fails that one (fail_other, for the caller to turn down); an
+// incomplete walk fails itself.  Every claimed face's three neighbours are looked at AFTER the claim's CAS has returned (the next level
+// of the walk), and claims and looks are atomics at the memory side: of two candidates that take adjacent faces at the same time at
+// least one sees the other, whichever order the CASes land in.  The verdict is what k_accept computed from the final ownership: the
+// accepted bit (fflags bit 1) of the candidates nobody failed.  po: o's rank; (px, py, pz): its apex.
+struct ClaimEdge {
+    int n = kNone;            // the neighbour
+    bool mine = false;        // claimed just now: goes to the log and the next level's frontier
+    bool fail_me = false;
+    int fail_other = kNone;
+};
+__device__ __forceinline__ ClaimEdge claim_edge(const Bufs& b, int o, unsigned long long po, double px, double py, double pz, int cg, int k) {
+    ClaimEdge r;
+    r.n = b.fn[3 * cg + k];
+    int co = __hip_atomic_load(&b.fowner[r.n], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool sees = plane_dist(b.frec[r.n], px, py, pz) > 0.0;  // loaded alongside the owner, not after it
+    if (co >= b.fcap) co = kNone;   // (never: an owner is a face id)
+    if (sees && !(co == o || (co >= 0 && b.fprio[co] <= po))) {
+        while (true) {
+            const int old = atomicCAS(&b.fowner[r.n], co, o);
+            if (old == co) { r.mine = true; r.fail_other = co; break; }  // two lanes on the same face: the second finds `o` there; a robbed owner has lost
+            co = old;
+            if (co == o) break;
+            if (co >= 0 && b.fprio[co] <= po) { r.fail_me = true; break; }   // a better one was quicker
+        }
+    } else if (sees) {
+        r.fail_me = co != o;                     // a face my apex sees, in better hands
+    } else if (co >= 0 && co != o) {   // across my horizon, in other hands: unless the two fit, the worse one loses
+        if (!b.share_edges || !convex_across(b, cg, k, px, py, pz, co)) {
+            if (b.fprio[co] < po) r.fail_me = true; else r.fail_other = co;
+        }
     }
-    __shared__ int lg[TO_WAVES_PER_BLOCK][kClaimLog];
-    __shared__ int lgc[TO_WAVES_PER_BLOCK][kClaimLog];   // who claimed it
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int sl = blockIdx.x % kSubLists, cap = sub_cap(b);
-    const int* __restrict__ cand = b.cand[par] + (size_t)sl * cap;
-    int* __restrict__ own = b.olist + (size_t)sl * cap;
-    int* __restrict__ ownc = b.oclaim + (size_t)sl * cap;
-    int* own_n = ocnt(b, par, sl);
-    const int ncand = min(*ccnt(b, par, sl), cap);
-    const int wstep = (gridDim.x / kSubLists) * TO_WAVES_PER_BLOCK;
-    int logn = 0;
-    auto flush = [&]() {  // wave-uniform
+    return r;
+}
+
+// Every claim is logged: a wave's claimed faces gather in LDS and go to the block's sub-list of claimed faces with one counter
+// update per flush.  A sub-list that runs full marks the round: k_accept turns everybody down; the build ends (kErrCapacity).
+struct ClaimLog {
+    int *face, *who;            // this wave's two rows in LDS: the face, the candidate that claimed it
+    int *own, *ownc, *own_n;    // the block's sub-list (faces, claimers) and its counter
+    int cap, logn;
+    // all lanes of the wave: bal = __ballot(mine); a lane with `mine` logs (n, o)
+    __device__ __forceinline__ void put(const Bufs& b, unsigned long long bal, bool mine, int n, int o) {
+        const int cnt = __popcll(bal);
+        if (logn + cnt > kClaimLog) flush(b);
+        if (mine) { const int r = logn + __popcll(bal & ((1ull << (threadIdx.x & 63)) - 1ull)); face[r] = n; who[r] = o; }
+        logn += cnt;
+    }
+    __device__ __forceinline__ void flush(const Bufs& b) {  // wave-uniform
         if (logn == 0) return;
+        const int lane = threadIdx.x & 63;
         int base = 0;
         if (lane == 0) base = atomicAdd(own_n, logn);
         base = __shfl(base, 0);
         for (int i = lane; i < logn; i += 64) {
-            if (base + i < cap) { own[base + i] = lg[wid][i]; ownc[base + i] = lgc[wid][i]; }
-            else { b.ctrl[kCtrlOverflow] = 1; b.ctrl[kCtrlError] |= kErrCapacity; }  // k_accept turns everybody down; the build ends
+            if (base + i < cap) { own[base + i] = face[i]; ownc[base + i] = who[i]; }
+            else { b.ctrl[kCtrlOverflow] = 1; b.ctrl[kCtrlError] |= kErrCapacity; }
         }
         logn = 0;
-    };
+    }
+};
+__device__ __forceinline__ ClaimLog claim_log(const Bufs& b, int par) {
+    __shared__ int rows[2][TO_WAVES_PER_BLOCK][kClaimLog];
+    const int wid = threadIdx.x >> 6, sl = blockIdx.x % kSubLists, cap = sub_cap(b);
+    return ClaimLog{rows[0][wid], rows[1][wid], b.olist + (size_t)sl * cap, b.oclaim + (size_t)sl * cap, ocnt(b, par, sl), cap, 0};
+}
+
+// A WAVE per candidate: nested loops over the levels of its walk, a frontier of up to 128 faces per level.
+__global__ void __launch_bounds__(TO_BLOCK) k_owner_claim(Bufs b, int round, int par) {
+    __shared__ int fr[TO_WAVES_PER_BLOCK][2][kClaimFront];
+    if (b.ctrl[kCtrlError] != 0) return;   // (see round_dead)
+    round_begin(b, par);
+    ClaimLog log = claim_log(b, par);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int sl = blockIdx.x % kSubLists, cap = sub_cap(b);
+    const int* __restrict__ cand = b.cand[par] + (size_t)sl * cap;
+    const int ncand = min(*ccnt(b, par, sl), cap);
+    const int wstep = (gridDim.x / kSubLists) * TO_WAVES_PER_BLOCK;
     for (int c = (blockIdx.x / kSubLists) * TO_WAVES_PER_BLOCK + wid; c < ncand; c += wstep) {
         const int o = cand[c];
-        const unsigned long long ax = b.fmax[o];
-        const int n0 = lane < 3 ? b.fn[3 * o + lane] : kNone;   // for the look at the neighbours below: requested with the apex
-        if (ax == 0ull) {  // a candidate without a point outside its face (never seen): not a candidate
-            if (lane == 0) { b.fowner[o] = kNone; atomicAnd(&b.fflags[o], ~2); }
-            continue;
-        }
-        if (__hip_atomic_load(&b.fowner[o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != o) continue;  // taken by a better one
-        const unsigned long long po = b.fprio[o];
-        // the apex's coordinates are requested before the look at the neighbours below, not after it: two chains of dependent
-        // loads side by side
-        const int apex = apex_pos(ax);
-        const double px = b.px[apex], py = b.py[apex], pz = b.pz[apex];
-        {
-            // A candidate whose own face is seen by the apex of a BETTER candidate next door has lost before it starts: that
-            // neighbour's walk takes this face at its first level.  Not walking keeps its claims off the faces that worse
-            // candidates need
-            bool doomed = false;
-            if (n0 >= 0) {
-                const int n = n0;
-                if ((b.fflags[n] & 3) == 3 && b.fprio[n] < po) {
-                    const unsigned long long an = b.fmax[n];
-                    if (an != 0ull) {
-                        const int pa = apex_pos(an);
-                        doomed = plane_dist(b.frec[o], b.px[pa], b.py[pa], b.pz[pa]) > 0.0;
-                    }
-                }
-            }
-            if (__any(doomed)) {
-                if (lane == 0) atomicAnd(&b.fflags[o], ~2);
-                continue;
-            }
-        }
+        unsigned long long po = 0ull;
+        double px = 0.0, py = 0.0, pz = 0.0;
+        if (!claim_admit<64>(b, o, lane, &po, &px, &py, &pz)) continue;
         int cur = 0, ncur = 1, claimed = 0;
         bool failed = false;   // (wave-uniform)
         if (lane == 0) fr[wid][0][0] = o;
@@ -923,40 +1007,14 @@ __global__ void __launch_bounds__(TO_BLOCK) k_owner_claim(Bufs b, int round, int
             int nnext = 0;
             for (int base = 0; base < 3 * ncur; base += 64) {
                 const int t = base + lane;
-                bool mine = false;
-                int n = kNone;
-                bool fail_me = false;
-                int fail_other = kNone;
-                if (t < 3 * ncur) {
-                    const int cg = fr[wid][cur][t / 3];
-                    n = b.fn[3 * cg + t % 3];
-                    int co = __hip_atomic_load(&b.fowner[n], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const bool sees = plane_dist(b.frec[n], px, py, pz) > 0.0;  // loaded alongside the owner, not after it
-                    if (co >= b.fcap) co = kNone;   // (never: an owner is a face id)
-                    if (sees && !(co == o || (co >= 0 && b.fprio[co] <= po))) {
-                        while (true) {
-                            const int old = atomicCAS(&b.fowner[n], co, o);
-                            if (old == co) { mine = true; fail_other = co; break; }  // two lanes on the same face: the second finds `o` there; a robbed owner has lost
-                            co = old;
-                            if (co == o) break;
-                            if (co >= 0 && b.fprio[co] <= po) { fail_me = true; break; }   // a better one was quicker
-                        }
-                    } else if (sees) {
-                        fail_me = co != o;                     // a face my apex sees, in better hands
-                    } else if (co >= 0 && co != o) {   // across my horizon, in other hands: unless the two fit, the worse one loses
-                        if (!b.share_edges || !convex_across(b, cg, t % 3, px, py, pz, co)) {
-                            if (b.fprio[co] < po) fail_me = true; else fail_other = co;
-                        }
-                    }
-                }
-                if (fail_other >= 0) atomicAnd(&b.fflags[fail_other], ~2);
-                failed = failed || __any(fail_me);
-                const unsigned long long bal = __ballot(mine);
+                ClaimEdge e;
+                if (t < 3 * ncur) e = claim_edge(b, o, po, px, py, pz, fr[wid][cur][t / 3], t % 3);
+                if (e.fail_other >= 0) turn_down(b, e.fail_other);
+                failed = failed || __any(e.fail_me);
+                const unsigned long long bal = __ballot(e.mine);
                 const int cnt = __popcll(bal), rank = __popcll(bal & ((1ull << lane) - 1ull));
-                if (logn + cnt > kClaimLog) flush();
-                if (mine) { lg[wid][logn + rank] = n; lgc[wid][logn + rank] = o; }
-                logn += cnt;
-                if (mine && nnext + rank < kClaimFront) fr[wid][cur ^ 1][nnext + rank] = n;  // beyond: the walk stays incomplete (safe)
+                log.put(b, bal, e.mine, e.n, o);
+                if (e.mine && nnext + rank < kClaimFront) fr[wid][cur ^ 1][nnext + rank] = e.n;  // beyond: the walk stays incomplete (safe)
                 nnext += cnt;
             }
             claimed += nnext;
@@ -965,53 +1023,33 @@ __global__ void __launch_bounds__(TO_BLOCK) k_owner_claim(Bufs b, int round, int
             cur ^= 1;
         }
         if (ncur > 0) failed = true;                  // the claim budget ran out with a frontier left
-        if (failed && lane == 0) atomicAnd(&b.fflags[o], ~2);
+        if (failed && lane == 0) turn_down(b, o);
     }
-    flush();
+    log.flush(b);
 }
 
-// The same walk for rounds with TENS OF THOUSANDS of candidates (a batch of views: up to 150 k per round), eight candidates to a
+// The schedule for rounds with TENS OF THOUSANDS of candidates (a batch of views: up to 150 k per round), eight candidates to a
 // wave (r06).  There a wave's walk is a chain of dependent accesses (neighbour -> owner and plane -> CAS, ~4.5 us per candidate) on
 // the 10-20 lanes its region's edges fill, every wave of the chip holds one, and the launch is as long as the 18 candidates a wave
 // walks one after the other (80 us per round for 128 views).  Regions are small in such rounds, so each EIGHTH of a wave takes a
 // candidate of its own: eight (face, edge) pairs per step, a frontier of at most 32 faces per level — a walk that outgrows it is
 // incomplete: the candidate fails itself and comes back in a later round — eight chains in flight per wave (measured: 12.0-12.1 ms
 // for 128 views; sixteen lanes each: 12.3-12.4; a wave each: 13.9-14.0).  The eight walks are independent but move in lock-step
-// through one instruction stream: every ballot is the whole wave's, a group reads its bits of it.  Same claims, same log, same
-// verdict rule as k_owner_claim.
+// through one instruction stream: every ballot is the whole wave's, a group reads its bits of it.
 constexpr int kSubFront = 32;
 __global__ void __launch_bounds__(TO_BLOCK) k_owner_claim_sub(Bufs b, int round, int par) {
     constexpr int SL = 8, NG = 64 / SL;   // lanes per candidate, candidates per wave
     __shared__ int fr[TO_WAVES_PER_BLOCK][NG][2][kSubFront];
-    __shared__ int lg[TO_WAVES_PER_BLOCK][kClaimLog];
-    __shared__ int lgc[TO_WAVES_PER_BLOCK][kClaimLog];
     if (b.ctrl[kCtrlError] != 0) return;   // (see round_dead)
-    if (blockIdx.x == 0) {   // k_accept's housekeeping (see k_owner_claim)
-        if (threadIdx.x == 0) { b.ctrl[kCtrlNFaces] = min(b.ctrl[kCtrlNFaces + 8], b.fcap); b.ctrl[kCtrlAccepted] = 0; }
-        if (threadIdx.x < kSubLists) { *ccnt(b, par ^ 1, threadIdx.x) = 0; *ocnt(b, par ^ 1, threadIdx.x) = 0; }
-    }
+    round_begin(b, par);
+    ClaimLog log = claim_log(b, par);
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, grp = lane / SL, gl = lane % SL;
     const unsigned long long gm = ((1ull << SL) - 1ull) << (SL * grp), below = (1ull << lane) - 1ull;
     const int sl = blockIdx.x % kSubLists, cap = sub_cap(b);
     const int* __restrict__ cand = b.cand[par] + (size_t)sl * cap;
-    int* __restrict__ own = b.olist + (size_t)sl * cap;
-    int* __restrict__ ownc = b.oclaim + (size_t)sl * cap;
-    int* own_n = ocnt(b, par, sl);
     const int ncand = min(*ccnt(b, par, sl), cap);
     const int cstep = (gridDim.x / kSubLists) * TO_WAVES_PER_BLOCK * NG;
     int c = ((blockIdx.x / kSubLists) * TO_WAVES_PER_BLOCK + wid) * NG + grp;   // this group's next candidate
-    int logn = 0;
-    auto flush = [&]() {  // wave-uniform
-        if (logn == 0) return;
-        int base = 0;
-        if (lane == 0) base = atomicAdd(own_n, logn);
-        base = __shfl(base, 0);
-        for (int i = lane; i < logn; i += 64) {
-            if (base + i < cap) { own[base + i] = lg[wid][i]; ownc[base + i] = lgc[wid][i]; }
-            else { b.ctrl[kCtrlOverflow] = 1; b.ctrl[kCtrlError] |= kErrCapacity; }
-        }
-        logn = 0;
-    };
     // a group's walk (the same values in its eight lanes)
     bool active = false, failed = false;
     int o = kNone, cur = 0, ncur = 0, nnext = 0, claimed = 0, base = 0;
@@ -1022,74 +1060,23 @@ __global__ void __launch_bounds__(TO_BLOCK) k_owner_claim_sub(Bufs b, int round,
         const bool fetch = !active && c < ncand;
         if (!__any(active || fetch)) break;
         {
-            int oc = kNone;
-            unsigned long long ax = 0ull;
-            bool ok = false, doomed = false;
-            if (fetch) {
-                oc = cand[c];
-                ax = b.fmax[oc];
-                const int n0 = gl < 3 ? b.fn[3 * oc + gl] : kNone;
-                if (ax == 0ull) {   // (never seen: a candidate without a point outside its face)
-                    if (gl == 0) { b.fowner[oc] = kNone; atomicAnd(&b.fflags[oc], ~2); }
-                } else if (__hip_atomic_load(&b.fowner[oc], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == oc) {
-                    ok = true;
-                    po = b.fprio[oc];
-                    const int apex = apex_pos(ax);
-                    px = b.px[apex]; py = b.py[apex]; pz = b.pz[apex];
-                    if (n0 >= 0 && (b.fflags[n0] & 3) == 3 && b.fprio[n0] < po) {   // a better candidate next door whose apex sees this face
-                        const unsigned long long an = b.fmax[n0];
-                        if (an != 0ull) {
-                            const int pa = apex_pos(an);
-                            doomed = plane_dist(b.frec[oc], b.px[pa], b.py[pa], b.pz[pa]) > 0.0;
-                        }
-                    }
-                }
-                c += cstep;
-            }
-            const bool gd = (__ballot(doomed) & gm) != 0ull;   // (the whole wave's ballot; this group's bits)
-            if (fetch && ok) {
-                if (gd) { if (gl == 0) atomicAnd(&b.fflags[oc], ~2); }
-                else {
-                    o = oc; active = true; failed = false; cur = 0; ncur = 1; nnext = 0; claimed = 0; base = 0;
-                    if (gl == 0) fr[wid][grp][0][0] = o;
-                }
+            const int oc = fetch ? cand[c] : kNone;
+            if (fetch) c += cstep;
+            if (claim_admit<SL>(b, oc, lane, &po, &px, &py, &pz)) {
+                o = oc; active = true; failed = false; cur = 0; ncur = 1; nnext = 0; claimed = 0; base = 0;
+                if (gl == 0) fr[wid][grp][0][0] = o;
             }
         }
         // ---- one step of every walking group: eight (face, edge) pairs of its current level
         const int t = base + gl;
-        bool mine = false, fail_me = false;
-        int n = kNone, fail_other = kNone;
-        if (active && t < 3 * ncur) {
-            const int cg = fr[wid][grp][cur][t / 3];
-            n = b.fn[3 * cg + t % 3];
-            int co = __hip_atomic_load(&b.fowner[n], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const bool sees = plane_dist(b.frec[n], px, py, pz) > 0.0;
-            if (co >= b.fcap) co = kNone;   // (never: an owner is a face id)
-            if (sees && !(co == o || (co >= 0 && b.fprio[co] <= po))) {
-                while (true) {
-                    const int old = atomicCAS(&b.fowner[n], co, o);
-                    if (old == co) { mine = true; fail_other = co; break; }
-                    co = old;
-                    if (co == o) break;
-                    if (co >= 0 && b.fprio[co] <= po) { fail_me = true; break; }
-                }
-            } else if (sees) {
-                fail_me = co != o;
-            } else if (co >= 0 && co != o) {   // (see k_owner_claim)
-                if (!b.share_edges || !convex_across(b, cg, t % 3, px, py, pz, co)) {
-                    if (b.fprio[co] < po) fail_me = true; else fail_other = co;
-                }
-            }
-        }
-        if (fail_other >= 0) atomicAnd(&b.fflags[fail_other], ~2);
-        const unsigned long long bal = __ballot(mine), balf = __ballot(fail_me);
-        const int total = __popcll(bal);
-        if (logn + total > kClaimLog) flush();
-        if (mine) { const int r = logn + __popcll(bal & below); lg[wid][r] = n; lgc[wid][r] = o; }
-        logn += total;
+        ClaimEdge e;
+        if (active && t < 3 * ncur) e = claim_edge(b, o, po, px, py, pz, fr[wid][grp][cur][t / 3], t % 3);
+        if (e.fail_other >= 0) turn_down(b, e.fail_other);
+        const unsigned long long bal = __ballot(e.mine), balf = __ballot(e.fail_me);
+        log.put(b, bal, e.mine, e.n, o);
         if (active) {
             const int cnt = __popcll(bal & gm), rank = __popcll(bal & gm & below);
-            if (mine && nnext + rank < kSubFront) fr[wid][grp][cur ^ 1][nnext + rank] = n;   // beyond: the walk stays incomplete
+            if (e.mine && nnext + rank < kSubFront) fr[wid][grp][cur ^ 1][nnext + rank] = e.n;   // beyond: the walk stays incomplete
             nnext += cnt;
             failed = failed || (balf & gm) != 0ull;
             base += SL;
@@ -1100,13 +1087,13 @@ __global__ void __launch_bounds__(TO_BLOCK) k_owner_claim_sub(Bufs b, int round,
                 cur ^= 1; nnext = 0; base = 0;
                 if (ncur == 0 || claimed >= kClaimMax) {
                     if (ncur > 0) failed = true;
-                    if (failed && gl == 0) atomicAnd(&b.fflags[o], ~2);
+                    if (failed && gl == 0) turn_down(b, o);
                     active = false;
                 }
             }
         }
     }
-    flush();
+    log.flush(b);
 }
 
 // The careful path (after a round that accepted nobody): each live face adopts the best-priority owner among its neighbours
@@ -1150,12 +1137,7 @@ __global__ void __launch_bounds__(TO_BLOCK) k_owned_list(Bufs b, int par) {
 
 __global__ void __launch_bounds__(TO_BLOCK) k_accept(Bufs b, int round, int par) {
     if (b.ctrl[kCtrlError] != 0) return;   // (see round_dead)
-    if (blockIdx.x == 0) {
-        // nothing has been inserted yet this round: the staged count is the face count; it is published here for the
-        // kernels that run while k_new_faces raises the staged one.  The next round's lists start empty.
-        if (threadIdx.x == 0) { b.ctrl[kCtrlNFaces] = min(b.ctrl[kCtrlNFaces + 8], b.fcap); b.ctrl[kCtrlAccepted] = 0; }
-        if (threadIdx.x < kSubLists) { *ccnt(b, par ^ 1, threadIdx.x) = 0; *ocnt(b, par ^ 1, threadIdx.x) = 0; }
-    }
+    round_begin(b, par);
     const bool overflow = b.ctrl[kCtrlOverflow] != 0;  // a claimed face is missing from the lists: nobody can be checked
     const ListWalk w = list_walk(b, par, blockIdx.x, gridDim.x);
     for (int it = 0; it < w.loops; ++it) {
@@ -1874,73 +1856,26 @@ __global__ void __launch_bounds__(TO_BLOCK) k_mark_vertices(Bufs b) {
             }
 }
 
-// ---- compaction of the live-point list (ordered: the Morton locality stays) -----------------------
+// ---- ordered compactions (tile_count_kept | scan | tile_place_kept): the live-point list (the Morton locality stays) ... -----
 __global__ void __launch_bounds__(TO_BLOCK) k_live_count(Bufs b, int nlive, int* __restrict__ tile_cnt) {
-    __shared__ int wave_cnt[TO_WAVES_PER_BLOCK];
-    const int tile0 = blockIdx.x * 1024;
-    int cnt = 0;
-    for (int k = 0; k < 4; ++k) {
-        const int j = tile0 + k * TO_BLOCK + threadIdx.x;
-        cnt += __popcll(__ballot(j < nlive && b.pface[b.live[j]] >= 0));
-    }
-    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    tile_count_kept((int)(blockIdx.x * 1024), tile_cnt, [&](int j) { return j < nlive && b.pface[b.live[j]] >= 0; });
 }
-
 __global__ void __launch_bounds__(TO_BLOCK) k_live_write(Bufs b, int nlive_old, const int* __restrict__ tile_off) {
-    __shared__ int wave_cnt[TO_WAVES_PER_BLOCK];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int tile0 = blockIdx.x * 1024;
-    int base = tile_off[blockIdx.x];
-    for (int k = 0; k < 4; ++k) {
-        const int j = tile0 + k * TO_BLOCK + threadIdx.x;
-        const int i = j < nlive_old ? b.live[j] : 0;
-        const bool keep = j < nlive_old && b.pface[i] >= 0;
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) wave_cnt[wave] = __popcll(bal);
-        __syncthreads();
-        int off = base;
-        for (int w = 0; w < wave; ++w) off += wave_cnt[w];
-        if (keep) b.live2[off + __popcll(bal & ((1ull << lane) - 1ull))] = i;
-        base += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-        __syncthreads();
-    }
+    int i = 0;
+    tile_place_kept((int)(blockIdx.x * 1024), tile_off[blockIdx.x],
+                    [&](int j) { i = j < nlive_old ? b.live[j] : 0; return j < nlive_old && b.pface[i] >= 0; },
+                    [&](int, int dst) { b.live2[dst] = i; });
 }
 
-// ---- ordered compaction of the flagged indices (same scheme as the frustum cull) ----------------
+// ---- ... and the ascending indices of the flagged points --------------------------------------------
 __global__ void __launch_bounds__(TO_BLOCK) k_flag_count(const int* __restrict__ flag, int n, int* __restrict__ tile_cnt) {
-    __shared__ int wave_cnt[TO_WAVES_PER_BLOCK];
-    const int tile0 = blockIdx.x * 1024;
-    int cnt = 0;
-    for (int j = 0; j < 4; ++j) {
-        const int i = tile0 + j * TO_BLOCK + threadIdx.x;
-        cnt += __popcll(__ballot(i < n && flag[i] != 0));
-    }
-    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    tile_count_kept((int)(blockIdx.x * 1024), tile_cnt, [&](int i) { return i < n && flag[i] != 0; });
 }
-
 __global__ void __launch_bounds__(TO_BLOCK)
 k_flag_write(const int* __restrict__ flag, int n, const int* __restrict__ tile_off, int* __restrict__ out, int cap) {
-    __shared__ int wave_cnt[TO_WAVES_PER_BLOCK];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int tile0 = blockIdx.x * 1024;
-    int base = tile_off[blockIdx.x];
-    for (int j = 0; j < 4; ++j) {
-        const int i = tile0 + j * TO_BLOCK + threadIdx.x;
-        const bool keep = i < n && flag[i] != 0;
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) wave_cnt[wave] = __popcll(bal);
-        __syncthreads();
-        int off = base;
-        for (int w = 0; w < wave; ++w) off += wave_cnt[w];
-        const int dst = off + __popcll(bal & ((1ull << lane) - 1ull));
-        if (keep && dst < cap) out[dst] = i;
-        base += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-        __syncthreads();
-    }
+    tile_place_kept((int)(blockIdx.x * 1024), tile_off[blockIdx.x],
+                    [&](int i) { return i < n && flag[i] != 0; },
+                    [&](int i, int dst) { if (dst < cap) out[dst] = i; });
 }
 
 // visible = all hull vertices but the last (tools.py:79); count and 0/1 mask
@@ -1977,6 +1912,102 @@ inline int nblocks(int64_t n, int cap = 2048) {
     int64_t nb = (n + TO_BLOCK - 1) / TO_BLOCK;
     return (int)(nb < 1 ? 1 : (nb > cap ? cap : nb));
 }
+
+// One readback = k_report's record in mapped host memory, the host polling its sequence number.  Two records, so that the host
+// can keep ONE batch of rounds enqueued ahead of the readback it is waiting for and the GPU never idles while the host looks at
+// the counts.  The records are one pair per (thread, device) and live as long as the thread (a build must not pay two pinned
+// allocations) — they are the thread's next build's too, so no build may leave while a report is on its way into them: the
+// destructor drains, whatever build() returns and wherever it returns from.
+class Readback {
+    struct Pinned {
+        int* rec[2] = {nullptr, nullptr};    // host addresses
+        int* drec[2] = {nullptr, nullptr};   // the same records as the device sees them
+        int seq = 0;                         // last sequence number handed out (never reused: a stale record cannot match)
+        bool ok = false;
+        Pinned() {   // mapped, coherent host memory: the GPU's stores land in it without a copy
+            ok = true;
+            for (int i = 0; i < 2 && ok; ++i) {
+                ok = hipHostMalloc((void**)&rec[i], sizeof(int) * kRepInts, hipHostMallocPortable | hipHostMallocMapped) == hipSuccess &&
+                     hipHostGetDevicePointer((void**)&drec[i], rec[i], 0) == hipSuccess;
+                if (ok) for (int k = 0; k < kRepInts; ++k) rec[i][k] = 0;
+            }
+        }
+        ~Pinned() {
+            for (int i = 0; i < 2; ++i)
+                if (rec[i]) (void)hipHostFree(rec[i]);
+        }
+        Pinned(const Pinned&) = delete;
+        Pinned& operator=(const Pinned&) = delete;
+    };
+    Pinned* pin_ = nullptr;
+    hipStream_t st_;
+    const int* h_ = nullptr;             // the record collected last
+    int wslot_ = 0, rslot_ = 0, inflight_ = 0, posted_at_ = 0;
+    int want_seq_[2] = {0, 0}, tag_[2] = {0, 0};
+
+public:
+    explicit Readback(hipStream_t st) : st_(st) {
+        static thread_local std::map<int, std::unique_ptr<Pinned>> pins;
+        int cur_dev = 0;
+        if (hipGetDevice(&cur_dev) != hipSuccess) return;
+        std::unique_ptr<Pinned>& slot = pins[cur_dev];
+        if (!slot) slot.reset(new Pinned());
+        if (slot->ok) { pin_ = slot.get(); h_ = pin_->rec[0]; }
+    }
+    ~Readback() { (void)drain(); }
+    Readback(const Readback&) = delete;
+    Readback& operator=(const Readback&) = delete;
+
+    bool ok() const { return pin_ != nullptr; }
+    int inflight() const { return inflight_; }
+    const int* h() const { return h_; }                               // the scalars of the control block, as collected last
+    int candidates(int par) const { return h_[kRepCand + par]; }      // entries of the candidate list of that parity
+    int posted_at() const { return posted_at_; }                      // the tag the collected report was posted with
+
+    hipError_t post(const Bufs& b, int tag = 0) {  // enqueue the report; collect() waits for it
+        want_seq_[wslot_] = ++pin_->seq;
+        tag_[wslot_] = tag;
+        k_report<<<1, 64, 0, st_>>>(b, pin_->drec[wslot_], want_seq_[wslot_]);
+        const hipError_t er = hipGetLastError();
+        wslot_ ^= 1; ++inflight_;
+        return er;
+    }
+    hipError_t collect() {
+        hipError_t er = hipSuccess;
+        const volatile int* seqp = pin_->rec[rslot_] + kRepSeq;
+        // poll; every so often ask the stream whether it is still working (a fault, or a report that never ran, must not hang the host)
+        for (long spin = 1; __atomic_load_n(seqp, __ATOMIC_ACQUIRE) != want_seq_[rslot_]; ++spin) {
+            if ((spin & 0x3fff) == 0) {
+                const hipError_t q = hipStreamQuery(st_);
+                if (q == hipSuccess) {   // everything enqueued has run: the record is there, or it never will be
+                    if (__atomic_load_n(seqp, __ATOMIC_ACQUIRE) != want_seq_[rslot_]) er = hipErrorUnknown;
+                    break;
+                }
+                if (q != hipErrorNotReady) { er = q; break; }
+            }
+            __builtin_ia32_pause();
+        }
+        h_ = pin_->rec[rslot_];
+        posted_at_ = tag_[rslot_];
+        rslot_ ^= 1; --inflight_;
+        return er;
+    }
+    hipError_t post_and_collect(const Bufs& b) {
+        const hipError_t er = post(b);
+        return er == hipSuccess ? collect() : er;
+    }
+    hipError_t drain() {   // the first error, after every report in flight has been waited for
+        hipError_t er = hipSuccess;
+        while (inflight_ > 0) {
+            const hipError_t ec = collect();
+            if (er == hipSuccess) er = ec;
+        }
+        return er;
+    }
+};
+
+// what a build that stopped on the device's error word returns
+inline int build_error(const int* h) { return (h[kCtrlError] & kErrCapacity) ? TOHIP_ENOSPC : TOHIP_ENOTCONV; }
 
 // Builds the hull of pts (n,3) [+ origin]; leaves vflag set.  Synchronises the stream.
 // b.seg_off must already be on the device (k_single_segment for one hull).
@@ -2052,77 +2083,18 @@ static int build(const Bufs& b_in, const float* pts, int with_origin, int64_t ma
         k_round_tail<<<kSubLists, TO_BLOCK, 0, st>>>(b, 1, 0);  // round 0's candidates: the tetrahedra's faces with points outside
     }
     TO_HIP_CHECK_LAUNCH();
-    // One readback = k_report's record in mapped host memory, the host polling its sequence number: the host keeps ONE batch of
-    // rounds enqueued ahead of the readback it is waiting for, so the GPU never idles while the host looks at the counts.
     // Rounds enqueued after the hull is complete find no candidate and change nothing; the counts only size grids, and every
     // kernel strides over its lists.
-    struct Pinned {
-        int* rec[2] = {nullptr, nullptr};    // host addresses
-        int* drec[2] = {nullptr, nullptr};   // the same records as the device sees them
-        int seq = 0;                         // last sequence number handed out (never reused: a stale record cannot match)
-        bool ok = false;
-        Pinned() {   // mapped, coherent host memory: the GPU's stores land in it without a copy
-            ok = true;
-            for (int i = 0; i < 2 && ok; ++i) {
-                ok = hipHostMalloc((void**)&rec[i], sizeof(int) * kRepInts, hipHostMallocPortable | hipHostMallocMapped) == hipSuccess &&
-                     hipHostGetDevicePointer((void**)&drec[i], rec[i], 0) == hipSuccess;
-                if (ok) for (int k = 0; k < kRepInts; ++k) rec[i][k] = 0;
-            }
-        }
-        ~Pinned() {
-            for (int i = 0; i < 2; ++i)
-                if (rec[i]) (void)hipHostFree(rec[i]);
-        }
-        Pinned(const Pinned&) = delete;
-        Pinned& operator=(const Pinned&) = delete;
-    };
-    // one set per (thread, device): it lives as long as the thread (a build must not pay two pinned allocations)
-    static thread_local std::map<int, std::unique_ptr<Pinned>> pins;
-    int cur_dev = 0;
-    if (hipGetDevice(&cur_dev) != hipSuccess) return TOHIP_EINVAL;
-    std::unique_ptr<Pinned>& pin_slot = pins[cur_dev];
-    if (!pin_slot) pin_slot.reset(new Pinned());
-    Pinned& pin = *pin_slot;
-    if (!pin.ok) return TOHIP_EINVAL;
-    const int* h = pin.rec[0];
-    int wslot = 0, rslot = 0, inflight = 0;
-    int want_seq[2] = {0, 0};
-    auto post_readback = [&]() -> hipError_t {  // enqueue the report; collect() waits for it
-        want_seq[wslot] = ++pin.seq;
-        k_report<<<1, 64, 0, st>>>(b, pin.drec[wslot], want_seq[wslot]);
-        const hipError_t er = hipGetLastError();
-        wslot ^= 1; ++inflight;
-        return er;
-    };
-    auto collect = [&]() -> hipError_t {
-        hipError_t er = hipSuccess;
-        const volatile int* seqp = pin.rec[rslot] + kRepSeq;
-        // poll; every so often ask the stream whether it is still working (a fault, or a report that never ran, must not hang the host)
-        for (long spin = 1; __atomic_load_n(seqp, __ATOMIC_ACQUIRE) != want_seq[rslot]; ++spin) {
-            if ((spin & 0x3fff) == 0) {
-                const hipError_t q = hipStreamQuery(st);
-                if (q == hipSuccess) {   // everything enqueued has run: the record is there, or it never will be
-                    if (__atomic_load_n(seqp, __ATOMIC_ACQUIRE) != want_seq[rslot]) er = hipErrorUnknown;
-                    break;
-                }
-                if (q != hipErrorNotReady) { er = q; break; }
-            }
-            __builtin_ia32_pause();
-        }
-        h = pin.rec[rslot];
-        rslot ^= 1; --inflight;
-        return er;
-    };
-    auto candidates = [&](int par) { return h[kRepCand + par]; };
+    Readback rb(st);   // (drains on every way out of here)
+    if (!rb.ok()) return TOHIP_EINVAL;
     auto cdiv = [](int64_t a, int64_t d) { return (a + d - 1) / d; };
-    e = post_readback();
-    if (e == hipSuccess) e = collect();
+    e = rb.post_and_collect(b);
     if (e != hipSuccess) return (int)e;
-    if (b.nseg == 1 && (h[kCtrlError] & kErrNaN)) return TOHIP_ENAN;
-    if (b.nseg == 1 && (h[kCtrlError] & kErrFlat)) return TOHIP_EINVAL;
-    int nf = h[kCtrlNFaces + 8];
+    if (b.nseg == 1 && (rb.h()[kCtrlError] & kErrNaN)) return TOHIP_ENAN;
+    if (b.nseg == 1 && (rb.h()[kCtrlError] & kErrFlat)) return TOHIP_EINVAL;
+    int nf = rb.h()[kCtrlNFaces + 8];
     const int max_rounds = 100000;
-    int round = 0 /* rounds enqueued */, ncand = candidates(0), live_bound = (b.m1 + b.sub - 1) / b.sub;
+    int round = 0 /* rounds enqueued */, ncand = rb.candidates(0), live_bound = (b.m1 + b.sub - 1) / b.sub;
     constexpr int batch = 3;          // rounds per readback (1 M points: 2.38 / 2.29 / 2.26 / 2.29 / 2.30 / 2.37 ms at 1 / 2 / 3 / 4 / 6 / 8)
     constexpr int compact_every = 2;  // readbacks between two compactions of the live list
     constexpr int sub_claim = 4;      // candidates per wave from which eight walks to a wave take over (k_owner_claim_sub)
@@ -2154,10 +2126,9 @@ static int build(const Bufs& b_in, const float* pts, int with_origin, int64_t ma
                     k_owner_prop<<<nblocks(nf), TO_BLOCK, 0, st>>>(b, round);
                     k_owner_prop<<<nblocks(nf), TO_BLOCK, 0, st>>>(b, round);
                     TO_HIP_CHECK_LAUNCH();
-                    ec = post_readback();
-                    if (ec == hipSuccess) ec = collect();
+                    ec = rb.post_and_collect(b);
                     if (ec != hipSuccess) return (int)ec;
-                    if (!h[kCtrlChanged]) break;
+                    if (!rb.h()[kCtrlChanged]) break;
                 }
                 k_owned_list<<<kSubLists * (int)std::min<int64_t>(16, std::max<int64_t>(1, cdiv(nf, kSubLists * TO_BLOCK))), TO_BLOCK, 0, st>>>(b, par);
                 TO_HIP_CHECK_LAUNCH();
@@ -2172,14 +2143,22 @@ static int build(const Bufs& b_in, const float* pts, int with_origin, int64_t ma
         }
         return TOHIP_OK;
     };
-    int rounds_seen = 0;                 // rounds covered by the last collected readback
-    int round_of[2] = {0, 0};            // rounds enqueued when each in-flight readback was posted
+    int rounds_seen = 0;                 // rounds covered by the last collected readback (a report is posted with `round` as its tag)
     int batches_since_compaction = 0;
     int compaction_pending_until = -1;   // a compaction was enqueued when `round` was this: older readbacks hold the old live count
     bool stalled = false;                // the last collected batch accepted nobody
     int careful_at = -1;                 // `round` right after the careful round was enqueued
     const int ahead = always_careful ? 1 : 2;
-    auto drain = [&](int rc) { while (inflight > 0) (void)collect(); return rc; };
+    // the first nlive entries of the live list without the points that have no conflict face (any more); the new count stays on the device
+    auto compact_live = [&](int nlive) -> hipError_t {
+        const int ntl = (nlive + 1023) / 1024;
+        k_live_count<<<ntl, TO_BLOCK, 0, st>>>(b, nlive, b.tile_cnt);
+        launch_scan_tiles(b.tile_cnt, ntl, b.tile_off, b.ctrl + kCtrlNLive, st);
+        k_live_write<<<ntl, TO_BLOCK, 0, st>>>(b, nlive, b.tile_off);
+        const hipError_t el = hipGetLastError();
+        if (el == hipSuccess) std::swap(b.live, b.live2);
+        return el;
+    };
     // the sample's rounds end when its hulls have a few hundred faces each (faces created ~ 3x faces alive), are complete, or late
     const int64_t switch_faces = (int64_t)192 * b.nseg;
     auto join_all_points = [&]() -> int {
@@ -2195,12 +2174,8 @@ static int build(const Bufs& b_in, const float* pts, int with_origin, int64_t ma
         TO_HIP_CHECK_LAUNCH();
         // the live list: every point that has a conflict face now
         k_live_all<<<nblocks(b.m1), TO_BLOCK, 0, st>>>(b);
-        const int ntl = (b.m1 + 1023) / 1024;
-        k_live_count<<<ntl, TO_BLOCK, 0, st>>>(b, b.m1, b.tile_cnt);
-        launch_scan_tiles(b.tile_cnt, ntl, b.tile_off, b.ctrl + kCtrlNLive, st);
-        k_live_write<<<ntl, TO_BLOCK, 0, st>>>(b, b.m1, b.tile_off);
-        TO_HIP_CHECK_LAUNCH();
-        int* t = b.live; b.live = b.live2; b.live2 = t;
+        ej = compact_live(b.m1);
+        if (ej != hipSuccess) return (int)ej;
         const int par = round & 1;
         ej = hipMemsetAsync(b.ctrl + kCtrlInts + par * kSubLists * kCntStride, 0, sizeof(int) * kSubLists * kCntStride, st);
         if (ej != hipSuccess) return (int)ej;
@@ -2211,92 +2186,79 @@ static int build(const Bufs& b_in, const float* pts, int with_origin, int64_t ma
     };
     while ((ncand > 0 || b.sub > 1) && round < max_rounds) {
         if (b.sub > 1 && (b.serial || nf >= switch_faces || ncand == 0 || round >= 96)) {
-            while (inflight > 0) {  // the rounds in flight belong to the sample
-                e = collect();
-                if (e != hipSuccess) return drain((int)e);
-                if (h[kCtrlError]) return drain((h[kCtrlError] & kErrCapacity) ? TOHIP_ENOSPC : TOHIP_ENOTCONV);
+            while (rb.inflight() > 0) {  // the rounds in flight belong to the sample
+                e = rb.collect();
+                if (e != hipSuccess) return (int)e;
+                if (rb.h()[kCtrlError]) return build_error(rb.h());
             }
-            nf = h[kCtrlNFaces + 8] < b.fcap ? h[kCtrlNFaces + 8] : b.fcap;
+            nf = std::min(rb.h()[kCtrlNFaces + 8], b.fcap);
             const int rc = join_all_points();
             if (rc != TOHIP_OK) return rc;
-            e = post_readback();
-            if (e == hipSuccess) e = collect();
-            if (e != hipSuccess) return drain((int)e);
-            if (h[kCtrlError]) return (h[kCtrlError] & kErrCapacity) ? TOHIP_ENOSPC : TOHIP_ENOTCONV;
-            ncand = candidates(round & 1);
+            e = rb.post_and_collect(b);
+            if (e != hipSuccess) return (int)e;
+            if (rb.h()[kCtrlError]) return build_error(rb.h());
+            ncand = rb.candidates(round & 1);
             stalled = false;
-            live_bound = std::max(1, h[kCtrlNLive]);   // the join compacted the list: this readback holds its length
+            live_bound = std::max(1, rb.h()[kCtrlNLive]);   // the join compacted the list: this readback holds its length
             batches_since_compaction = 0;
             compaction_pending_until = round;
             continue;
         }
         if (!stalled) {
-            while (inflight < ahead) {  // keep one batch ahead of the readback being waited for
+            while (rb.inflight() < ahead) {  // keep one batch ahead of the readback being waited for
                 // few candidates left: the build is about to end, and every round enqueued beyond its end is five launches of
                 // nothing (up to eight such rounds at four per readback: 0.1 ms of a build) -> two per readback from here on
                 // ... and with tens of thousands of candidates (a batch of views) a round is hundreds of microseconds: the host is
                 // ahead anyway, and one round per readback wastes the fewest at the end (128 views: 9.5 ms at 4, 9.0 at 2, 8.9 at 1)
                 const int per = ncand >= 16384 ? 1 : (ncand <= 512 ? 2 : batch);
                 const int rc = enqueue_rounds(always_careful ? 1 : per, always_careful);
-                if (rc != TOHIP_OK) return drain(rc);
-                round_of[wslot] = round;
-                e = post_readback();
-                if (e != hipSuccess) return drain((int)e);
+                if (rc != TOHIP_OK) return rc;
+                e = rb.post(b, round);
+                if (e != hipSuccess) return (int)e;
             }
-        } else if (inflight == 0) {
+        } else if (rb.inflight() == 0) {
             // every enqueued round has reported and the last one accepted nobody: one round with converged ownership
             const int rc = enqueue_rounds(1, true);
-            if (rc != TOHIP_OK) return drain(rc);
-            round_of[wslot] = round;
+            if (rc != TOHIP_OK) return rc;
             careful_at = round;
-            e = post_readback();
-            if (e != hipSuccess) return drain((int)e);
+            e = rb.post(b, round);
+            if (e != hipSuccess) return (int)e;
         }
-        const int posted_at = round_of[rslot];
-        e = collect();
-        if (e != hipSuccess) return drain((int)e);
+        e = rb.collect();
+        if (e != hipSuccess) return (int)e;
+        const int posted_at = rb.posted_at();
         rounds_seen = posted_at;
-        if (h[kCtrlError]) return drain((h[kCtrlError] & kErrCapacity) ? TOHIP_ENOSPC : TOHIP_ENOTCONV);
-        nf = h[kCtrlNFaces + 8] < b.fcap ? h[kCtrlNFaces + 8] : b.fcap;
-        ncand = candidates(posted_at & 1);
+        if (rb.h()[kCtrlError]) return build_error(rb.h());
+        nf = std::min(rb.h()[kCtrlNFaces + 8], b.fcap);
+        ncand = rb.candidates(posted_at & 1);
         if (ncand == 0) {  // no face has a point outside it: the hull is complete (rounds still in flight are no-ops) ...
             if (b.sub > 1) continue;  // ... of the sample: time for the other points
             break;
         }
-        if (h[kCtrlAccepted] <= 0) {
+        if (rb.h()[kCtrlAccepted] <= 0) {
             // converged ownership always admits the best candidate: a careful round without progress = inconsistent predicates
-            if (posted_at == careful_at || always_careful) return drain(TOHIP_ENOTCONV);
+            if (posted_at == careful_at || always_careful) return TOHIP_ENOTCONV;
             stalled = true;   // let what is in flight report, then run a careful round
             continue;
         }
         stalled = false;
-        if (++batches_since_compaction >= compact_every && h[kCtrlNLive] > 4096 && posted_at > compaction_pending_until) {
+        if (++batches_since_compaction >= compact_every && rb.h()[kCtrlNLive] > 4096 && posted_at > compaction_pending_until) {
             // drop the points that have retired inside the hull from the list the point kernels walk
-            const int nlive = h[kCtrlNLive], ntl = (nlive + 1023) / 1024;
-            k_live_count<<<ntl, TO_BLOCK, 0, st>>>(b, nlive, b.tile_cnt);
-            launch_scan_tiles(b.tile_cnt, ntl, b.tile_off, b.ctrl + kCtrlNLive, st);
-            k_live_write<<<ntl, TO_BLOCK, 0, st>>>(b, nlive, b.tile_off);
-            {
-                const hipError_t el = hipGetLastError();   // a report may be in flight into the shared mapped records: drain before leaving
-                if (el != hipSuccess) return drain((int)el);
-            }
-            int* t = b.live; b.live = b.live2; b.live2 = t;
+            const int nlive = rb.h()[kCtrlNLive];
+            e = compact_live(nlive);
+            if (e != hipSuccess) return (int)e;
             batches_since_compaction = 0;
             live_bound = nlive;  // the new count is on the device only; this bounds it
             compaction_pending_until = round;  // readbacks posted up to now still show the count before this compaction
         }
     }
-    if (round >= max_rounds && ncand > 0) return drain(TOHIP_ENOTCONV);
+    if (round >= max_rounds && ncand > 0) return TOHIP_ENOTCONV;
     round = rounds_seen;
     if (rounds_out) *rounds_out = round;
     k_mark_vertices<<<nblocks(nf), TO_BLOCK, 0, st>>>(b);
-    e = hipGetLastError();   // (a report may be in flight into the shared mapped records: drain before leaving)
-    if (e != hipSuccess) return drain((int)e);
-    while (inflight > 0) {  // the mapped records are this thread's next build's too
-        e = collect();
-        if (e != hipSuccess) return (int)e;
-    }
-    return TOHIP_OK;
+    TO_HIP_CHECK_LAUNCH();
+    e = rb.drain();
+    return e == hipSuccess ? TOHIP_OK : (int)e;
 }
 
 // ascending indices of the flagged points -> out (capacity cap), *total on the device
@@ -2312,72 +2274,29 @@ static int compact(const Bufs& b, int* out, int cap, int* total_dev, hipStream_t
 }
 
 // ---- batched hidden-point removal: per-segment flip radius, per-segment "drop the last hull vertex" -------
-__device__ __forceinline__ int find_src_seg(const Bufs& b, int r) {  // segment of source row r (seg_off[s] - s <= r)
-    int lo = 0, hi = b.nseg;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (b.seg_off[mid] - mid <= r) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// (wave_seg for source rows: r0 wave-uniform, *end = the first row behind the segment)
-__device__ __forceinline__ int wave_src_seg(const Bufs& b, int r0, int* end) {
-    const int r = __builtin_amdgcn_readfirstlane(r0);
-    int lo = 0, hi = b.nseg;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (b.seg_off[mid] - mid <= r) lo = mid; else hi = mid;
-    }
-    *end = b.seg_off[lo + 1] - (lo + 1);
-    return lo;
-}
-
 __global__ void __launch_bounds__(TO_BLOCK) k_norm_max_seg(Bufs b, const float* __restrict__ xyz, int n) {
-    // contiguous run per wave, running maximum of the current segment in a register (as k_bbox)
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * TO_WAVES_PER_BLOCK + (threadIdx.x >> 6), nwaves = gridDim.x * TO_WAVES_PER_BLOCK;
-    const int chunk = ((n + nwaves - 1) / nwaves + 63) / 64 * 64;
-    const int64_t begin64 = (int64_t)wave * chunk;
-    const int begin = begin64 < n ? (int)begin64 : n, end = begin64 + chunk < n ? (int)(begin64 + chunk) : n;
-    int cur = -1, m = 0, cur_seg = -1, cur_end = -1;
-    auto flush = [&]() {
-        if (cur >= 0) {
-            for (int s = 32; s > 0; s >>= 1) m = max(m, __shfl_xor(m, s));
-            if (lane == 0) atomicMax(&b.flip_max[cur], m);
-        }
-        m = 0;
-    };
-    for (int i0 = begin; i0 < end; i0 += 64) {
-        const int i = i0 + lane;
-        int sg = -1, v = 0;
-        if (i0 >= cur_end) cur_seg = wave_src_seg(b, i0, &cur_end);   // (wave-uniform)
-        if (i < end) {
-            sg = i0 + 63 < cur_end ? cur_seg : find_src_seg(b, i);
+    int m = 0;   // the running maximum of the wave's current segment
+    walk_segment_runs<SourceRows>(b, n,
+        [&](int i, int) {
             const Row3 p = load_row(xyz, i);
-            v = __float_as_int(flip_norm(p.x, p.y, p.z)) & 0x7fffffff;
-        }
-        const int s0 = __shfl(sg, 0);
-        if (__all(sg == s0 || sg < 0)) {
-            if (s0 != cur) { flush(); cur = s0; }
-            m = max(m, v);
-        } else {
-            flush();
-            cur = -1;
-            if (sg >= 0) atomicMax(&b.flip_max[sg], v);
-        }
-    }
-    flush();
+            return __float_as_int(flip_norm(p.x, p.y, p.z)) & 0x7fffffff;
+        },
+        [&](int v) { m = max(m, v); },
+        [&](int sg) {
+            for (int s = 32; s > 0; s >>= 1) m = max(m, __shfl_xor(m, s));
+            if ((threadIdx.x & 63) == 0) atomicMax(&b.flip_max[sg], m);
+            m = 0;
+        },
+        [&](int sg, int v) { if (sg >= 0) atomicMax(&b.flip_max[sg], v); });
 }
 
 __global__ void __launch_bounds__(TO_BLOCK)
 k_flip_seg(Bufs b, const float* __restrict__ xyz, int n, float scale, float* __restrict__ flipped) {
     const int stride = gridDim.x * TO_BLOCK;
     for (int i = blockIdx.x * TO_BLOCK + threadIdx.x; i - (int)(threadIdx.x & 63) < n; i += stride) {
-        int send;
-        const int i0 = i - (int)(threadIdx.x & 63), s0 = wave_src_seg(b, i0, &send);   // (all lanes of the wave take part)
+        const int sg = lane_seg<SourceRows>(b, i - (int)(threadIdx.x & 63), i);   // (all lanes of the wave take part)
         if (i >= n) continue;
-        const float radius = __int_as_float(b.flip_max[i0 + 63 < send ? s0 : find_src_seg(b, i)]) * scale;  // tools.py:45, per viewpoint
+        const float radius = __int_as_float(b.flip_max[sg]) * scale;  // tools.py:45, per viewpoint
         const Row3 p = load_row(xyz, i);
         const float x = p.x, y = p.y, z = p.z;
         const float nr = flip_norm(x, y, z);

@@ -84,43 +84,15 @@ struct Pc2Mode { int hint; int mode_a; };   // hint: persistent; mode_a: what TH
 __global__ void __launch_bounds__(TO_BLOCK)
 k_pc2_count(const uint8_t* __restrict__ data, int64_t n, int point_step, int xo, int yo, int zo, int datatype, int be,
             int remove_nans, int32_t* __restrict__ tile_count, Pc2Mode* __restrict__ mode, float* __restrict__ out) {
-    __shared__ int wave_cnt[TO_WAVES_PER_BLOCK];
     const int64_t tile0 = (int64_t)blockIdx.x * 1024;
     const bool dense = mode != nullptr && (mode->hint == TO_PC2_HINT_DENSE || !remove_nans);   // (nobody writes the hint during this launch)
     if (mode != nullptr && blockIdx.x == 0 && threadIdx.x == 0) mode->mode_a = dense ? 1 : 0;
-    int cnt = 0;
-    for (int j = 0; j < 4; ++j) {
-        const int64_t i = tile0 + j * TO_BLOCK + threadIdx.x;
+    tile_count_kept(tile0, tile_count, [&](int64_t i) {
         float x, y, z;
         const bool keep = i < n && unpack_point(data, i, point_step, xo, yo, zo, datatype, be, remove_nans, x, y, z);
         if (dense && i < n) { out[3 * i] = x; out[3 * i + 1] = y; out[3 * i + 2] = z; }   // where it belongs if no row before it is dropped
-        cnt += __popcll(__ballot(keep));
-    }
-    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_count[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-}
-
-// one 1024-point tile's kept rows to out[base ..) in message order; all threads of the block
-__device__ __forceinline__ void pc2_write_tile(const uint8_t* __restrict__ data, int64_t n, int point_step, int xo, int yo, int zo, int datatype,
-                                               int be, int remove_nans, int64_t tile0, int base, float* __restrict__ out, int* wave_cnt) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int j = 0; j < 4; ++j) {
-        const int64_t i = tile0 + j * TO_BLOCK + threadIdx.x;
-        float x = 0, y = 0, z = 0;
-        const bool keep = i < n && unpack_point(data, i, point_step, xo, yo, zo, datatype, be, remove_nans, x, y, z);
-        const unsigned long long b = __ballot(keep);
-        if (lane == 0) wave_cnt[wave] = __popcll(b);
-        __syncthreads();
-        int off = base;
-        for (int w = 0; w < wave; ++w) off += wave_cnt[w];
-        if (keep) {
-            const int64_t d = off + __popcll(b & ((1ull << lane) - 1ull));
-            out[3 * d] = x; out[3 * d + 1] = y; out[3 * d + 2] = z;
-        }
-        base += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-        __syncthreads();
-    }
+        return keep;
+    });
 }
 
 // a block per tile.  Adaptive (mode != nullptr): a tile that the count pass has put in place already (no row dropped before or
@@ -131,7 +103,6 @@ __global__ void __launch_bounds__(TO_BLOCK)
 k_pc2_write(const uint8_t* __restrict__ data, int64_t n, int point_step, int xo, int yo, int zo, int datatype, int be,
             int remove_nans, const int32_t* __restrict__ tile_off, const int32_t* __restrict__ tile_count, Pc2Mode* __restrict__ mode,
             const int32_t* __restrict__ total, float* __restrict__ out) {
-    __shared__ int wave_cnt[TO_WAVES_PER_BLOCK];
     const int64_t tile0 = (int64_t)blockIdx.x * 1024;
     const int base = tile_off[blockIdx.x];
     if (mode != nullptr) {
@@ -141,7 +112,10 @@ k_pc2_write(const uint8_t* __restrict__ data, int64_t n, int point_step, int xo,
         const int64_t rows = n - tile0 < 1024 ? n - tile0 : 1024;
         if (placed && base == (int)tile0 && tile_count[blockIdx.x] == (int)rows) return;   // (block-uniform)
     }
-    pc2_write_tile(data, n, point_step, xo, yo, zo, datatype, be, remove_nans, tile0, base, out, wave_cnt);
+    float x = 0, y = 0, z = 0;   // one 1024-point tile's kept rows to out[base ..) in message order
+    tile_place_kept(tile0, base,
+                    [&](int64_t i) { return i < n && unpack_point(data, i, point_step, xo, yo, zo, datatype, be, remove_nans, x, y, z); },
+                    [&](int64_t, int64_t d) { out[3 * d] = x; out[3 * d + 1] = y; out[3 * d + 2] = z; });
 }
 
 extern "C" size_t tohip_ingest_workspace_bytes(int64_t n) {
