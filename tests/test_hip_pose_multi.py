@@ -164,6 +164,50 @@ def test_ops_multi_matches_single_and_oracle(dev, masked):
                 assert np.abs(g).max() <= 1e-20
 
 
+@pytest.mark.parametrize("n", [7, 2049])
+@pytest.mark.parametrize("case", ["sorted", "bits"])
+def test_ops_multi_sorted_cloud_and_bit_rows(dev, n, case):
+    """What the cases above leave to other files: a cloud packed with sort=True (observations and the float mask go through the
+    permutation) and each pose's own occlusion bit row, at B = 3 (a full tile and a short one).  n = 7 is less than one lane's
+    eight points; n = 2049 is one chunk and one point, so the second chunk is nearly all pads."""
+    from oracle import oracle
+    from trajectory_optimization_amd import ops
+    pts = synth.make_cloud(n, seed=n % 97) * np.float32(0.25)   # a 10 x 10 x 1 m slab: most points in view
+    cloud = ops.PackedCloud(torch.from_numpy(pts).to(dev), sort=case == "sorted")
+    cam = ops.Camera(torch.from_numpy(K), IW, IH, 1.0, 5.0, 1e-6)
+    B = 3
+    g = torch.Generator().manual_seed(n)
+    if case == "sorted":
+        masks = (torch.rand(n, generator=g) < 0.7).to(torch.float32).to(dev).expand(B, n)
+        kw = [dict(mask=masks[0].contiguous())] * B
+        kw_multi = kw[0]
+    else:   # random rows with random pad bits
+        rows = torch.randint(-2 ** 31, 2 ** 31 - 1, (B, cloud.npad // 32), generator=g, dtype=torch.int64).to(torch.int32).to(dev)
+        masks = ops.unpack_occlusion_rows(cloud, rows)
+        kw = [dict(occ=rows[b:b + 1]) for b in range(B)]
+        kw_multi = dict(occ=rows)
+    starts = _starts(B, seed=n, centre=(0.0, 0.0, 0.0), spread=0.5)
+    t_np, q_np = np.concatenate([s[0] for s in starts]), np.concatenate([s[1] for s in starts])
+    t, q = torch.from_numpy(t_np).to(dev), torch.from_numpy(q_np).to(dev)
+    obs, sc, tg, qg = ops.pose_forward_backward_multi(cloud, t, q, cam, ops.PoseWorkspace(cloud, B), observations=True, **kw_multi)
+    ws1 = ops.PoseWorkspace(cloud)
+    for b in range(B):
+        o1, s1, tg1, qg1 = ops.pose_forward_backward(cloud, t[b:b + 1].contiguous(), q[b:b + 1].contiguous(), cam, ws1, **kw[b])
+        assert torch.equal(obs[b], o1) and torch.equal(sc[b], s1)
+        assert torch.equal(tg[b:b + 1], tg1) and torch.equal(qg[b:b + 1], qg1)
+        mask_np = masks[b].cpu().numpy()
+        of, lf = oracle.pose_forward(pts, t_np[b], q_np[b], K, IW, IH, mask=mask_np, prec="f64")
+        assert rel_inf(obs[b].cpu().numpy(), of) < 1e-5
+        assert abs(float(sc[b, 1]) - lf) <= 1e-5 * lf
+        tr, qr = oracle.pose_backward(pts, t_np[b], q_np[b], K, IW, IH, lf, mask=mask_np, prec="f64")
+        for gr, r in ((tg[b:b + 1], tr), (qg[b:b + 1], qr)):
+            gr = gr.cpu().numpy()
+            if np.abs(r).max() > 1e-20:
+                assert rel_inf(gr, r) < 1e-5, (b, gr, r)
+            else:
+                assert np.abs(gr).max() <= 1e-20
+
+
 def test_opt_step_writes_observations_only_when_asked(dev):
     import ctypes
     from trajectory_optimization_amd import _lib, ops

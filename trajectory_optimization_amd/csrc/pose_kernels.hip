@@ -57,25 +57,32 @@ __global__ void k_prep_posecam(const float* __restrict__ trans, const float* __r
 #define TO_POSE_NSUM 13                     // sum of the observations + 12 gradient sums
 #define TO_POSE_MAXBLOCKS 1024
 
+// Several poses of one camera over one cloud (optimizer.optimize_poses: many starts; scoring candidate views) run the same pass.
+//
+// Grid nb x T: nb is the pass's grid for this cloud (pose_stream_blocks), T = ceil(B / TILE) tiles of poses.  Block (c0, tile)
+// walks the chunks c0, c0 + nb, ... and evaluates the tile's poses on each chunk while its points sit in registers: the points
+// are read once per tile instead of once per pose.  What a pose adds, and in which order, does not depend on TILE: per pose a
+// lane's sums, the DPP tree and the f64 order over the waves are one text, so the (pose, block) row of partials of a batch is
+// bitwise the row the pose gets alone.  A single call is the pass at TILE = 1 over one pose; a batch runs TILE = TO_POSE_TILE.
+// Each pose carries 1 + 12 packed accumulators (25 VGPRs): TO_POSE_TILE is set from the register report.
+#ifndef TO_POSE_TILE   // (-DTO_POSE_TILE=n: a diagnostic build for comparing tile sizes, tools/time_pose_multi.py)
+#define TO_POSE_TILE 2
+#endif
+
 struct PoseArgs {
     CloudView cv;
-    const float* trans;
-    const float* quat;
+    const float* trans;   // (B,3)
+    const float* quat;    // (B,4)
+    int n_poses;
     EvalK k;
     union {                      // (one slot: the float kernels' arguments stay what they were)
-        const float* mask;       // caller's order, may be NULL
-        const uint32_t* bits;    // OCC: the occlusion bit row (Npad/32 words, bit i = packed point i)
+        const float* mask;       // caller's order, may be NULL: shared by every pose
+        const uint32_t* bits;    // OCC: (B, Npad/32) occlusion bit rows, one per pose (bit i = packed point i)
     };
-    const float* grad_obs;   // caller's order, may be NULL: dL/d observations (general upstream); NULL: unit weights
-    float* obs;              // caller's order (FWD)
-    double* part;            // gridDim.x x 16 doubles
+    const float* grad_obs;   // caller's order, may be NULL: dL/d observations (general upstream) of a single pose; NULL: unit weights
+    float* obs;              // (B,N) caller's order (FWD), may be NULL: nothing written
+    double* part;            // (B, nb, 16): pose b's rows are part[(b nb + block) 16 + j]
 };
-
-// the camera record of the pose in LDS (prep_wayrec: F.normalize, R, the projection rows) — every block builds its own: no launch
-__device__ __forceinline__ void pose_record(const PoseArgs& a, WayRec* srec, WayCold* scold) {
-    if (threadIdx.x == 0) prep_wayrec(0, a.trans, a.quat, 1, nullptr, nullptr, a.k, srec, scold, nullptr, 1);
-    __syncthreads();
-}
 
 // the weights of a lane's eight points from an occlusion bit row: they are one aligned byte of a word (base is a multiple of 8);
 // w = bit ? 1 : 0, pads 0 — the values a float mask of zeros and ones gives, so everything after is the float path's arithmetic
@@ -85,29 +92,42 @@ __device__ __forceinline__ void occ_weights(uint32_t word, int64_t base, int64_t
     for (int i = 0; i < TO_POSE_PTS; ++i) w[i] = (base + i < n && ((byte >> i) & 1u)) ? 1.0f : 0.f;
 }
 
-// OCC: the mask is the bit row a.bits (packed order) instead of a.mask
-template <bool FWD, bool GRAD, bool OCC>
+// FWD: observations are written (where a.obs is given).  OCC: pose b's mask is its own bit row a.bits + b Npad/32 instead of
+// a.mask (the tile's words are read once per chunk, next to the points)
+template <int TILE, bool FWD, bool GRAD, bool OCC>
 __global__ void __launch_bounds__(TO_BLOCK) k_pose_stream(PoseArgs a) {
-    __shared__ WayRec srec;
-    __shared__ WayCold scold;
-    __shared__ float swave[TO_WAVES_PER_BLOCK][16];
-    pose_record(a, &srec, &scold);
-    // the record's first line as scalars: a packed instruction takes one scalar operand
-    WayRec r;
-    {
-        const float* src = reinterpret_cast<const float*>(&srec);
-        float* dst = reinterpret_cast<float*>(&r);
+    static_assert(TILE * 16 <= TO_BLOCK, "one thread per (pose, sum) writes the partial rows");
+    __shared__ WayRec srec[TILE];
+    __shared__ WayCold scold[TILE];
+    __shared__ float swave[TILE][TO_WAVES_PER_BLOCK][16];
+    const int b0 = (int)blockIdx.y * TILE;
+    // poses of this tile: the last may hold fewer (never a tile of one)
+    const int np = TILE == 1 ? 1 : (a.n_poses - b0 < TILE ? a.n_poses - b0 : TILE);
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    // the tile's camera records in LDS, one thread per pose (prep_wayrec: F.normalize, R, the projection rows) — every block
+    // builds its own: no launch
+    if (t < np) prep_wayrec(0, a.trans + 3 * (b0 + t), a.quat + 4 * (b0 + t), 1, nullptr, nullptr, a.k, &srec[t], &scold[t], nullptr, 1);
+    __syncthreads();
+    // every record's first line as scalars (a packed instruction takes one scalar operand); a tile's missing poses copy its last
+    WayRec r[TILE];
+#pragma unroll
+    for (int p = 0; p < TILE; ++p) {
+        const float* src = reinterpret_cast<const float*>(&srec[p < np ? p : np - 1]);
+        float* dst = reinterpret_cast<float*>(&r[p]);
 #pragma unroll
         for (int i = 0; i < 16; ++i) dst[i] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, src[i])));
     }
     const EvalK& k = a.k;
     const bool ident = a.cv.hdr[0] == 0;   // the points keep the caller's order: observations, masks and upstream gradients are read / written in place
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int64_t n = a.cv.n, npad = a.cv.npad;
-    float asum = 0.f;
-    f2 acc[12];
+    float asum[TILE];
+    f2 acc[TILE][12];
 #pragma unroll
-    for (int j = 0; j < 12; ++j) acc[j] = pk_splat(0.f);
+    for (int p = 0; p < TILE; ++p) {
+        asum[p] = 0.f;
+#pragma unroll
+        for (int j = 0; j < 12; ++j) acc[p][j] = pk_splat(0.f);
+    }
     const int64_t nchunks = npad / TO_POSE_CHUNK;
     // two blocks to a CU, each striding over the chunks: the next chunk's points are requested before this one is evaluated
     float nx[TO_POSE_PTS], ny[TO_POSE_PTS], nz[TO_POSE_PTS];
@@ -131,8 +151,10 @@ __global__ void __launch_bounds__(TO_BLOCK) k_pose_stream(PoseArgs a) {
         float w[TO_POSE_PTS];   // what multiplies p in the observation (the occlusion mask), 0 for pads
 #pragma unroll
         for (int i = 0; i < TO_POSE_PTS; ++i) w[i] = base + i < n ? 1.0f : 0.f;
+        uint32_t occw[TILE];   // OCC: each pose's word of this lane's points
         if (OCC) {
-            occ_weights(a.bits[base >> 5], base, n, w);
+#pragma unroll
+            for (int p = 0; p < TILE; ++p) occw[p] = p < np ? a.bits[(int64_t)(b0 + p) * (npad >> 5) + (base >> 5)] : 0u;
         } else if (a.mask != nullptr) {
             if (whole && ((((uintptr_t)a.mask) & 15) == 0)) {
                 const float4 m0 = *reinterpret_cast<const float4*>(a.mask + base), m1 = *reinterpret_cast<const float4*>(a.mask + base + 4);
@@ -143,95 +165,122 @@ __global__ void __launch_bounds__(TO_BLOCK) k_pose_stream(PoseArgs a) {
                     if (base + i < n) w[i] = a.mask[o[i]];
             }
         }
-        float gw[TO_POSE_PTS];   // GRAD: the weight of dp/dy — the mask, times the upstream gradient where one is given
 #pragma unroll
-        for (int i = 0; i < TO_POSE_PTS; ++i) gw[i] = w[i];
-        if (GRAD && a.grad_obs != nullptr) {
+        for (int p = 0; p < TILE; ++p) {
+            if (p >= np) continue;   // uniform: the last tile's missing poses
+            if (OCC) occ_weights(occw[p], base, n, w);
+            float gw[TO_POSE_PTS];   // GRAD: the weight of dp/dy — the mask, times the upstream gradient where one is given
 #pragma unroll
-            for (int i = 0; i < TO_POSE_PTS; ++i) gw[i] = base + i < n ? a.grad_obs[o[i]] * w[i] : 0.f;
-        }
-        float ob[TO_POSE_PTS];
+            for (int i = 0; i < TO_POSE_PTS; ++i) gw[i] = w[i];
+            if (GRAD && TILE == 1 && a.grad_obs != nullptr) {   // (only a single call has one: a batch's pass carries no code for it)
 #pragma unroll
-        for (int i = 0; i < TO_POSE_PTS; i += 2) {
-            VisGrad2 vg;
-            const f2 p = vis_p_pk_grad(r, k, f2{x[i], x[i + 1]}, f2{y[i], y[i + 1]}, f2{z[i], z[i + 1]}, vg);
-            const f2 obs2 = f2{w[i], w[i + 1]} * p;   // model.py:115: mask * observations
-            ob[i] = obs2.x; ob[i + 1] = obs2.y;
-            asum += obs2.x;
-            asum += obs2.y;
-            if (GRAD) {
-                f2 g[3];
-                dvis_dy_pk(r, k, p, vg, g);
-                const f2 wg = f2{gw[i], gw[i + 1]};
-                const f2 w0 = wg * g[0], w1 = wg * g[1], w2 = wg * g[2];
-                acc[0] = acc[0] + w0; acc[1] = acc[1] + w1; acc[2] = acc[2] + w2;
-                acc[3] = pk_fma(vg.y0, w0, acc[3]); acc[4] = pk_fma(vg.y0, w1, acc[4]); acc[5] = pk_fma(vg.y0, w2, acc[5]);
-                acc[6] = pk_fma(vg.y1, w0, acc[6]); acc[7] = pk_fma(vg.y1, w1, acc[7]); acc[8] = pk_fma(vg.y1, w2, acc[8]);
-                acc[9] = pk_fma(vg.y2, w0, acc[9]); acc[10] = pk_fma(vg.y2, w1, acc[10]); acc[11] = pk_fma(vg.y2, w2, acc[11]);
+                for (int i = 0; i < TO_POSE_PTS; ++i) gw[i] = base + i < n ? a.grad_obs[o[i]] * w[i] : 0.f;
             }
-        }
-        if (FWD) {
-            if (whole && ((((uintptr_t)a.obs) & 15) == 0)) {
-                __builtin_nontemporal_store(f4v{ob[0], ob[1], ob[2], ob[3]}, reinterpret_cast<f4v*>(a.obs + base));
-                __builtin_nontemporal_store(f4v{ob[4], ob[5], ob[6], ob[7]}, reinterpret_cast<f4v*>(a.obs + base + 4));
-            } else {
+            float ob[TO_POSE_PTS];
 #pragma unroll
-                for (int i = 0; i < TO_POSE_PTS; ++i)
-                    if (base + i < n) a.obs[o[i]] = ob[i];
+            for (int i = 0; i < TO_POSE_PTS; i += 2) {
+                VisGrad2 vg;
+                const f2 pv = vis_p_pk_grad(r[p], k, f2{x[i], x[i + 1]}, f2{y[i], y[i + 1]}, f2{z[i], z[i + 1]}, vg);
+                const f2 obs2 = f2{w[i], w[i + 1]} * pv;   // model.py:115: mask * observations
+                ob[i] = obs2.x; ob[i + 1] = obs2.y;
+                asum[p] += obs2.x;
+                asum[p] += obs2.y;
+                if (GRAD) {
+                    f2 g[3];
+                    dvis_dy_pk(r[p], k, pv, vg, g);
+                    const f2 wg = f2{gw[i], gw[i + 1]};
+                    const f2 w0 = wg * g[0], w1 = wg * g[1], w2 = wg * g[2];
+                    f2* ac = acc[p];
+                    ac[0] = ac[0] + w0; ac[1] = ac[1] + w1; ac[2] = ac[2] + w2;
+                    ac[3] = pk_fma(vg.y0, w0, ac[3]); ac[4] = pk_fma(vg.y0, w1, ac[4]); ac[5] = pk_fma(vg.y0, w2, ac[5]);
+                    ac[6] = pk_fma(vg.y1, w0, ac[6]); ac[7] = pk_fma(vg.y1, w1, ac[7]); ac[8] = pk_fma(vg.y1, w2, ac[8]);
+                    ac[9] = pk_fma(vg.y2, w0, ac[9]); ac[10] = pk_fma(vg.y2, w1, ac[10]); ac[11] = pk_fma(vg.y2, w2, ac[11]);
+                }
+            }
+            if (FWD && a.obs != nullptr) {   // (only a batch may pass none: the single calls refuse a NULL obs)
+                float* orow = a.obs + (int64_t)(b0 + p) * n;
+                if (whole && ((((uintptr_t)orow) & 15) == 0)) {
+                    __builtin_nontemporal_store(f4v{ob[0], ob[1], ob[2], ob[3]}, reinterpret_cast<f4v*>(orow + base));
+                    __builtin_nontemporal_store(f4v{ob[4], ob[5], ob[6], ob[7]}, reinterpret_cast<f4v*>(orow + base + 4));
+                } else {
+#pragma unroll
+                    for (int i = 0; i < TO_POSE_PTS; ++i)
+                        if (base + i < n) orow[o[i]] = ob[i];
+                }
             }
         }
     }
-    // per wave one DPP tree per sum (valid in lane 63), then the block's four waves in order, in f64
-    float sums[TO_POSE_NSUM];
-    sums[0] = wave_sum63(asum);
-    if (GRAD) {
+    // per pose and wave one DPP tree per sum (valid in lane 63), then the block's four waves in order, in f64
 #pragma unroll
-        for (int j = 0; j < 12; ++j) sums[1 + j] = wave_sum63(acc[j].x + acc[j].y);
-    }
-    if (lane == 63) {
+    for (int p = 0; p < TILE; ++p) {
+        if (p >= np) continue;
+        float sums[TO_POSE_NSUM];
+        sums[0] = wave_sum63(asum[p]);
+        if (GRAD) {
 #pragma unroll
-        for (int j = 0; j < (GRAD ? TO_POSE_NSUM : 1); ++j) swave[wave][j] = sums[j];
+            for (int j = 0; j < 12; ++j) sums[1 + j] = wave_sum63(acc[p][j].x + acc[p][j].y);
+        }
+        if (lane == 63) {
+#pragma unroll
+            for (int j = 0; j < (GRAD ? TO_POSE_NSUM : 1); ++j) swave[p][wave][j] = sums[j];
+        }
     }
     __syncthreads();
-    if (t < (GRAD ? TO_POSE_NSUM : 1)) {
+    const int p = t >> 4, j = t & 15;
+    if (p < np && j < (GRAD ? TO_POSE_NSUM : 1)) {
         double s = 0.0;
 #pragma unroll
-        for (int wv = 0; wv < TO_WAVES_PER_BLOCK; ++wv) s += (double)swave[wv][t];
-        a.part[(int64_t)blockIdx.x * 16 + t] = s;
+        for (int wv = 0; wv < TO_WAVES_PER_BLOCK; ++wv) s += (double)swave[p][wv][j];
+        a.part[((int64_t)(b0 + p) * gridDim.x + blockIdx.x) * 16 + j] = s;
     }
 }
 
 // what follows the pass: the blocks' totals -> scalars (sum, loss), and — GRAD — the gradient sums scaled, rotated into the camera
-// frame and chained to (position, raw quaternion).  One block.
+// frame and chained to (position, raw quaternion).  One block per pose.
 //   coef_mode 0: the sums carry their upstream gradient already (grad_obs)       1: x -loss^2 gout[0] (scalars_in[1] = loss)
 //             2: x -loss^2 gout[0] with the loss of THIS pass (forward + backward in one call; gout NULL: 1)
+// The pointers are pose 0's; the per-pose rows follow (part: nparts rows of 16 per pose, trans / grads / moments 3 or 4 floats,
+// scalars 4, gout 1, loss_log n_steps)
 struct PoseFinish {
-    const double* part;
-    int nparts;
-    const float *trans, *quat;
-    EvalK k;
-    float eps;
-    float* scalars_out;        // may be NULL
-    const float* scalars_in;   // coef_mode 1
-    const float* gout;
-    int coef_mode, grad;
-    float *trans_grad, *quat_grad;
-    // a device-resident optimisation step (optimizer.optimize_pose): Adam on (trans, quat) with the gradient just computed
-    int adam;
-    float *mt, *vt, *mq, *vq;
-    float lr_pose, lr_quat, beta1, beta2, adam_eps;
-    int step;                  // 1-based
-    float* loss_log;           // adam: loss_log[step - 1] = the loss of this step
+    const double* part = nullptr;
+    int nparts = 0;
+    const float *trans = nullptr, *quat = nullptr;
+    EvalK k = {};
+    float eps = 0.f;
+    float* scalars_out = nullptr;        // may be NULL
+    const float* scalars_in = nullptr;   // coef_mode 1 (a single pose)
+    const float* gout = nullptr;
+    int coef_mode = 0, grad = 0;
+    float *trans_grad = nullptr, *quat_grad = nullptr;
+    // a device-resident optimisation step (optimizer.optimize_pose / optimize_poses): Adam on (trans, quat) with the gradient just computed
+    int adam = 0;
+    float *mt = nullptr, *vt = nullptr, *mq = nullptr, *vq = nullptr;
+    float lr_pose = 0.f, lr_quat = 0.f, beta1 = 0.f, beta2 = 0.f, adam_eps = 0.f;
+    int step = 0;                  // 1-based
+    int n_steps = 0;               // adam: a pose's row of loss_log
+    float* loss_log = nullptr;     // adam: loss_log[b n_steps + step - 1] = the loss of this step
 };
 
-// k_pose_finish's body, shared with k_pose_finish_multi (one block per pose there): the order of every f64 add depends only on
-// f.nparts and blockDim.x, so a pose of a batch gets the bits it gets alone
-__device__ __forceinline__ void pose_finish_body(const PoseFinish& f) {
+// the order of every f64 add depends only on f.nparts and blockDim.x, so a pose of a batch gets the bits it gets alone
+__global__ void __launch_bounds__(1024) k_pose_finish(PoseFinish f) {
     __shared__ double stot[16];
     __shared__ double sred[1024 / 16][16];
     __shared__ WayRec srec;
     __shared__ WayCold scold;
     __shared__ float vgrad[12];
+    const int64_t b = blockIdx.x;   // this block's pose: its rows
+    f.part += b * f.nparts * 16;
+    f.trans += 3 * b;
+    f.quat += 4 * b;
+    if (f.scalars_out) f.scalars_out += 4 * b;
+    if (f.gout) f.gout += b;
+    if (f.trans_grad) f.trans_grad += 3 * b;
+    if (f.quat_grad) f.quat_grad += 4 * b;
+    if (f.adam) {
+        f.mt += 3 * b; f.vt += 3 * b;
+        f.mq += 4 * b; f.vq += 4 * b;
+        f.loss_log += b * f.n_steps;
+    }
     const int t = threadIdx.x, col = t & 15, row = t >> 4;
     if (t == 0) prep_wayrec(0, f.trans, f.quat, 1, nullptr, nullptr, f.k, &srec, &scold, nullptr, 1);
     // column `col` of the partials, rows row, row + 16, ... in order; then the sixteen row groups in order (fixed: deterministic)
@@ -278,187 +327,6 @@ __device__ __forceinline__ void pose_finish_body(const PoseFinish& f) {
             for (int i = 0; i < 4; ++i) adam_apply(const_cast<float*>(f.quat), o[3 + i], f.mq, f.vq, i, f.beta1, f.beta2, f.adam_eps, cq);
         }
     }
-}
-
-__global__ void __launch_bounds__(1024) k_pose_finish(PoseFinish f) { pose_finish_body(f); }
-
-// ---------------------------------------------------------------------------------------------
-// Several poses of one camera over one cloud (optimizer.optimize_poses: many starts; scoring candidate views).
-//
-// Grid nb x T: nb is the single-pose pass's grid for this cloud, T = ceil(B / TO_POSE_TILE) tiles of poses.  Block (c0, tile)
-// walks the chunks c0, c0 + nb, ... exactly as k_pose_stream's block c0 does (same eight points per lane, same prefetch) and
-// evaluates the tile's poses on each chunk while its points sit in registers: the points are read once per tile instead of once
-// per pose.  Per pose a lane adds in the single-pose order, then the same DPP tree and the same f64 order over the waves, so the
-// (pose, block) row of partials is bitwise the row k_pose_stream writes for that pose alone.  Each pose carries 1 + 12 packed
-// accumulators (25 VGPRs): TO_POSE_TILE is set from the register report.
-#ifndef TO_POSE_TILE   // (-DTO_POSE_TILE=n: a diagnostic build for comparing tile sizes, tools/time_pose_multi.py)
-#define TO_POSE_TILE 2
-#endif
-
-struct PoseMultiArgs {
-    CloudView cv;
-    const float* trans;   // (B,3)
-    const float* quat;    // (B,4)
-    int n_poses;
-    EvalK k;
-    union {
-        const float* mask;    // caller's order, may be NULL: shared by every pose
-        const uint32_t* bits; // OCC: (B, Npad/32) occlusion bit rows, one per pose (packed order)
-    };
-    float* obs;           // (B,N) caller's order, may be NULL: nothing written
-    double* part;         // (B, nb, 16): pose b's rows are part[(b nb + block) 16 + j]
-};
-
-// OCC: pose b's mask is its own bit row a.bits + b Npad/32 (the tile's words are read once per chunk, next to the points)
-template <bool GRAD, bool OCC>
-__global__ void __launch_bounds__(TO_BLOCK) k_pose_stream_multi(PoseMultiArgs a) {
-    __shared__ WayRec srec[TO_POSE_TILE];
-    __shared__ WayCold scold[TO_POSE_TILE];
-    __shared__ float swave[TO_POSE_TILE][TO_WAVES_PER_BLOCK][16];
-    const int b0 = (int)blockIdx.y * TO_POSE_TILE;
-    const int np = a.n_poses - b0 < TO_POSE_TILE ? a.n_poses - b0 : TO_POSE_TILE;   // poses of this tile (the last may hold fewer)
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    // the tile's camera records, one thread per pose (prep_wayrec as k_pose_stream's pose_record)
-    if (t < np) prep_wayrec(0, a.trans + 3 * (b0 + t), a.quat + 4 * (b0 + t), 1, nullptr, nullptr, a.k, &srec[t], &scold[t], nullptr, 1);
-    __syncthreads();
-    // every record's first line as scalars (a packed instruction takes one scalar operand); a tile's missing poses copy its last
-    WayRec r[TO_POSE_TILE];
-#pragma unroll
-    for (int p = 0; p < TO_POSE_TILE; ++p) {
-        const float* src = reinterpret_cast<const float*>(&srec[p < np ? p : np - 1]);
-        float* dst = reinterpret_cast<float*>(&r[p]);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) dst[i] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, src[i])));
-    }
-    const EvalK& k = a.k;
-    const bool ident = a.cv.hdr[0] == 0;
-    const int64_t n = a.cv.n, npad = a.cv.npad;
-    float asum[TO_POSE_TILE];
-    f2 acc[TO_POSE_TILE][12];
-#pragma unroll
-    for (int p = 0; p < TO_POSE_TILE; ++p) {
-        asum[p] = 0.f;
-#pragma unroll
-        for (int j = 0; j < 12; ++j) acc[p][j] = pk_splat(0.f);
-    }
-    const int64_t nchunks = npad / TO_POSE_CHUNK;
-    float nx[TO_POSE_PTS], ny[TO_POSE_PTS], nz[TO_POSE_PTS];
-    if ((int64_t)blockIdx.x < nchunks) load_points<TO_POSE_PTS>(a.cv.soa, npad, (int64_t)blockIdx.x * TO_POSE_CHUNK + (int64_t)t * TO_POSE_PTS, nx, ny, nz);
-    for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-        const int64_t base = c * TO_POSE_CHUNK + (int64_t)t * TO_POSE_PTS;
-        float x[TO_POSE_PTS], y[TO_POSE_PTS], z[TO_POSE_PTS];
-#pragma unroll
-        for (int i = 0; i < TO_POSE_PTS; ++i) { x[i] = nx[i]; y[i] = ny[i]; z[i] = nz[i]; }
-        if (c + gridDim.x < nchunks) load_points<TO_POSE_PTS>(a.cv.soa, npad, (c + gridDim.x) * TO_POSE_CHUNK + (int64_t)t * TO_POSE_PTS, nx, ny, nz);
-        if (base >= n) continue;   // pads only
-        const bool whole = base + TO_POSE_PTS <= n && ident;
-        int o[TO_POSE_PTS];
-        if (!ident) {
-            const int4 p0 = *reinterpret_cast<const int4*>(a.cv.perm + base), p1 = *reinterpret_cast<const int4*>(a.cv.perm + base + 4);
-            o[0] = p0.x; o[1] = p0.y; o[2] = p0.z; o[3] = p0.w; o[4] = p1.x; o[5] = p1.y; o[6] = p1.z; o[7] = p1.w;
-        } else {
-#pragma unroll
-            for (int i = 0; i < TO_POSE_PTS; ++i) o[i] = (int)(base + i);
-        }
-        float w[TO_POSE_PTS];   // the occlusion mask (shared by the poses), 0 for pads
-#pragma unroll
-        for (int i = 0; i < TO_POSE_PTS; ++i) w[i] = base + i < n ? 1.0f : 0.f;
-        uint32_t occw[TO_POSE_TILE];   // OCC: each pose's word of this lane's points
-        if (OCC) {
-#pragma unroll
-            for (int p = 0; p < TO_POSE_TILE; ++p) occw[p] = p < np ? a.bits[(int64_t)(b0 + p) * (npad >> 5) + (base >> 5)] : 0u;
-        } else if (a.mask != nullptr) {
-            if (whole && ((((uintptr_t)a.mask) & 15) == 0)) {
-                const float4 m0 = *reinterpret_cast<const float4*>(a.mask + base), m1 = *reinterpret_cast<const float4*>(a.mask + base + 4);
-                w[0] = m0.x; w[1] = m0.y; w[2] = m0.z; w[3] = m0.w; w[4] = m1.x; w[5] = m1.y; w[6] = m1.z; w[7] = m1.w;
-            } else {
-#pragma unroll
-                for (int i = 0; i < TO_POSE_PTS; ++i)
-                    if (base + i < n) w[i] = a.mask[o[i]];
-            }
-        }
-#pragma unroll
-        for (int p = 0; p < TO_POSE_TILE; ++p) {
-            if (p >= np) continue;   // uniform: the last tile's missing poses
-            if (OCC) occ_weights(occw[p], base, n, w);
-            float ob[TO_POSE_PTS];
-#pragma unroll
-            for (int i = 0; i < TO_POSE_PTS; i += 2) {
-                VisGrad2 vg;
-                const f2 pv = vis_p_pk_grad(r[p], k, f2{x[i], x[i + 1]}, f2{y[i], y[i + 1]}, f2{z[i], z[i + 1]}, vg);
-                const f2 obs2 = f2{w[i], w[i + 1]} * pv;
-                ob[i] = obs2.x; ob[i + 1] = obs2.y;
-                asum[p] += obs2.x;
-                asum[p] += obs2.y;
-                if (GRAD) {
-                    f2 g[3];
-                    dvis_dy_pk(r[p], k, pv, vg, g);
-                    const f2 wg = f2{w[i], w[i + 1]};
-                    const f2 w0 = wg * g[0], w1 = wg * g[1], w2 = wg * g[2];
-                    f2* ac = acc[p];
-                    ac[0] = ac[0] + w0; ac[1] = ac[1] + w1; ac[2] = ac[2] + w2;
-                    ac[3] = pk_fma(vg.y0, w0, ac[3]); ac[4] = pk_fma(vg.y0, w1, ac[4]); ac[5] = pk_fma(vg.y0, w2, ac[5]);
-                    ac[6] = pk_fma(vg.y1, w0, ac[6]); ac[7] = pk_fma(vg.y1, w1, ac[7]); ac[8] = pk_fma(vg.y1, w2, ac[8]);
-                    ac[9] = pk_fma(vg.y2, w0, ac[9]); ac[10] = pk_fma(vg.y2, w1, ac[10]); ac[11] = pk_fma(vg.y2, w2, ac[11]);
-                }
-            }
-            if (a.obs != nullptr) {
-                float* orow = a.obs + (int64_t)(b0 + p) * n;
-                if (whole && ((((uintptr_t)orow) & 15) == 0)) {
-                    __builtin_nontemporal_store(f4v{ob[0], ob[1], ob[2], ob[3]}, reinterpret_cast<f4v*>(orow + base));
-                    __builtin_nontemporal_store(f4v{ob[4], ob[5], ob[6], ob[7]}, reinterpret_cast<f4v*>(orow + base + 4));
-                } else {
-#pragma unroll
-                    for (int i = 0; i < TO_POSE_PTS; ++i)
-                        if (base + i < n) orow[o[i]] = ob[i];
-                }
-            }
-        }
-    }
-    // per pose and wave one DPP tree per sum (valid in lane 63), then the block's four waves in order, in f64 (k_pose_stream's)
-#pragma unroll
-    for (int p = 0; p < TO_POSE_TILE; ++p) {
-        if (p >= np) continue;
-        float sums[TO_POSE_NSUM];
-        sums[0] = wave_sum63(asum[p]);
-        if (GRAD) {
-#pragma unroll
-            for (int j = 0; j < 12; ++j) sums[1 + j] = wave_sum63(acc[p][j].x + acc[p][j].y);
-        }
-        if (lane == 63) {
-#pragma unroll
-            for (int j = 0; j < (GRAD ? TO_POSE_NSUM : 1); ++j) swave[p][wave][j] = sums[j];
-        }
-    }
-    __syncthreads();
-    const int p = t >> 4, j = t & 15;
-    if (p < np && j < (GRAD ? TO_POSE_NSUM : 1)) {
-        double s = 0.0;
-#pragma unroll
-        for (int wv = 0; wv < TO_WAVES_PER_BLOCK; ++wv) s += (double)swave[p][wv][j];
-        a.part[((int64_t)(b0 + p) * gridDim.x + blockIdx.x) * 16 + j] = s;
-    }
-}
-static_assert(TO_POSE_TILE * 16 <= TO_BLOCK, "one thread per (pose, sum) writes the partial rows");
-
-// k_pose_finish for pose b = blockIdx.x of a batch: f's pointers are pose 0's; the per-pose rows follow (part: f.nparts rows of 16
-// per pose, trans / grads / moments 3 or 4 floats, scalars 4, gout 1, loss_log n_steps)
-__global__ void __launch_bounds__(1024) k_pose_finish_multi(PoseFinish f, int n_steps) {
-    const int64_t b = blockIdx.x;
-    PoseFinish g = f;
-    g.part = f.part + b * f.nparts * 16;
-    g.trans = f.trans + 3 * b;
-    g.quat = f.quat + 4 * b;
-    if (f.scalars_out) g.scalars_out = f.scalars_out + 4 * b;
-    if (f.gout) g.gout = f.gout + b;
-    if (f.trans_grad) g.trans_grad = f.trans_grad + 3 * b;
-    if (f.quat_grad) g.quat_grad = f.quat_grad + 4 * b;
-    if (f.adam) {
-        g.mt = f.mt + 3 * b; g.vt = f.vt + 3 * b;
-        g.mq = f.mq + 4 * b; g.vq = f.vq + 4 * b;
-        g.loss_log = f.loss_log + b * n_steps;
-    }
-    pose_finish_body(g);
 }
 
 __global__ void __launch_bounds__(TO_BLOCK)
@@ -653,7 +521,7 @@ inline int pose_stream_blocks(int64_t npad) {   // (the OCC variants run on the 
         int dev = 0, cus = 256, per = 4;
         hipDeviceProp_t prop;
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_pose_stream<FWD, GRAD, false>, TO_BLOCK, 0) != hipSuccess || per <= 0) per = 2;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_pose_stream<1, FWD, GRAD, false>, TO_BLOCK, 0) != hipSuccess || per <= 0) per = 2;
         if (per > 2) per = 2;   // two blocks to a CU keep the chip's HBM pipes full with the next chunk's loads in flight (12 MB), and
                                 // the finish has a quarter of the partials to add
         const int r = per * cus;
@@ -661,43 +529,6 @@ inline int pose_stream_blocks(int64_t npad) {   // (the OCC variants run on the 
     }();
     const int64_t nchunks = npad / TO_POSE_CHUNK;
     return (int)(nchunks < resident ? nchunks : resident);
-}
-
-struct PoseCall {
-    hipStream_t st;
-    bool occ;   // a.bits holds an occlusion bit row (else a.mask a float mask or NULL)
-    PoseArgs a;
-    PoseFinish f;
-};
-inline int pose_call_init(PoseCall& c, const void* packed, int64_t n, const float* trans, const float* quat, const tohip_camera* cam,
-                          const float* mask, const uint32_t* bits, void* workspace, size_t workspace_bytes, void* stream_) {
-    if (!packed || !trans || !quat || !cam || !workspace || n <= 0 || (mask && bits)) return TOHIP_EINVAL;
-    const PosePlan pl = pose_plan();
-    if (workspace_bytes < pl.total) return TOHIP_ENOSPC;
-    c.st = (hipStream_t)stream_;
-    c.a.cv = cloud_view(packed, n);
-    c.a.trans = trans; c.a.quat = quat; c.a.k = make_evalk(cam); c.occ = bits != nullptr;
-    if (c.occ) c.a.bits = bits;
-    else c.a.mask = mask;
-    c.a.grad_obs = nullptr; c.a.obs = nullptr;
-    c.a.part = (double*)((char*)workspace + pl.off_part);
-    PoseFinish& f = c.f;
-    f.part = c.a.part; f.nparts = 0; f.trans = trans; f.quat = quat; f.k = c.a.k; f.eps = cam->eps;
-    f.scalars_out = nullptr; f.scalars_in = nullptr; f.gout = nullptr; f.coef_mode = 0; f.grad = 0; f.trans_grad = nullptr; f.quat_grad = nullptr;
-    f.adam = 0; f.mt = f.vt = f.mq = f.vq = nullptr; f.lr_pose = f.lr_quat = f.beta1 = f.beta2 = f.adam_eps = 0.f; f.step = 0; f.loss_log = nullptr;
-    return TOHIP_OK;
-}
-template <bool FWD, bool GRAD>
-inline int pose_launch(PoseCall& c) {
-    const int nb = pose_stream_blocks<FWD, GRAD>(c.a.cv.npad);
-    if (c.occ) k_pose_stream<FWD, GRAD, true><<<nb, TO_BLOCK, 0, c.st>>>(c.a);
-    else k_pose_stream<FWD, GRAD, false><<<nb, TO_BLOCK, 0, c.st>>>(c.a);
-    TO_HIP_CHECK_LAUNCH();
-    c.f.nparts = nb;
-    c.f.grad = GRAD ? 1 : 0;
-    k_pose_finish<<<1, nb > 64 ? 1024 : TO_BLOCK, 0, c.st>>>(c.f);
-    TO_HIP_CHECK_LAUNCH();
-    return TOHIP_OK;
 }
 
 // the multi-pose workspace: the (B, nb, 16) partial rows first, nb <= min(chunks, TO_POSE_MAXBLOCKS), then a single-pose
@@ -708,35 +539,48 @@ inline size_t pose_multi_bytes(int64_t n, int64_t n_poses) {
     return align_up((size_t)n_poses * (size_t)rows * 16 * sizeof(double), 256) + pose_plan().total;
 }
 
-// B poses per launch pair: the stream pass on the single-pose grid x tiles, then one finish block per pose
-template <bool GRAD>
-inline int pose_multi_launch(const PoseMultiArgs& a, bool occ, PoseFinish f, int n_steps, hipStream_t st) {
-    const int nb = pose_stream_blocks<true, GRAD>(a.cv.npad);   // the single-pose pass's grid: the same chunks per block
-    const int tiles = (a.n_poses + TO_POSE_TILE - 1) / TO_POSE_TILE;
-    if (occ) k_pose_stream_multi<GRAD, true><<<dim3(nb, tiles), TO_BLOCK, 0, st>>>(a);
-    else k_pose_stream_multi<GRAD, false><<<dim3(nb, tiles), TO_BLOCK, 0, st>>>(a);
-    TO_HIP_CHECK_LAUNCH();
-    f.nparts = nb;
-    f.grad = GRAD ? 1 : 0;
-    k_pose_finish_multi<<<a.n_poses, nb > 64 ? 1024 : TO_BLOCK, 0, st>>>(f, n_steps);   // k_pose_finish's block size rule
-    TO_HIP_CHECK_LAUNCH();
+struct PoseCall {
+    hipStream_t st;
+    bool occ;   // a.bits holds occlusion bit rows (else a.mask a float mask or NULL)
+    PoseArgs a;
+    PoseFinish f;
+};
+// which workspace a call was given: a single-pose one (the partial rows at off_part; one pose) or a many-pose one (the rows first)
+enum class PoseWs { single, batch };
+// mask: floats in the caller's order, may be NULL; bits: occlusion bit rows in packed order instead — which a _bits entry must be
+// given (need_bits)
+inline int pose_call_init(PoseCall& c, const void* packed, int64_t n, const float* trans, const float* quat, int64_t n_poses, PoseWs kind,
+                          const tohip_camera* cam, const float* mask, const uint32_t* bits, bool need_bits, void* workspace,
+                          size_t workspace_bytes, void* stream_) {
+    if (!packed || !trans || !quat || !cam || !workspace || n <= 0 || n_poses <= 0 || (need_bits && !bits) || (mask && bits)) return TOHIP_EINVAL;
+    const bool batch = kind == PoseWs::batch;
+    if (batch && (n > INT32_MAX || n_poses > INT32_MAX || (n_poses + TO_POSE_TILE - 1) / TO_POSE_TILE > 65535)) return TOHIP_EINVAL;   // the grid's y extent
+    const PosePlan pl = pose_plan();
+    if (workspace_bytes < (batch ? pose_multi_bytes(n, n_poses) : pl.total)) return TOHIP_ENOSPC;
+    c.st = (hipStream_t)stream_;
+    c.a.cv = cloud_view(packed, n);
+    c.a.trans = trans; c.a.quat = quat; c.a.n_poses = (int)n_poses; c.a.k = make_evalk(cam); c.occ = bits != nullptr;
+    if (c.occ) c.a.bits = bits;
+    else c.a.mask = mask;
+    c.a.grad_obs = nullptr; c.a.obs = nullptr;
+    c.a.part = (double*)((char*)workspace + (batch ? 0 : pl.off_part));
+    c.f = PoseFinish{};
+    c.f.part = c.a.part; c.f.trans = trans; c.f.quat = quat; c.f.k = c.a.k; c.f.eps = cam->eps;
     return TOHIP_OK;
 }
 
-inline int pose_multi_init(PoseMultiArgs& a, PoseFinish& f, const void* packed, int64_t n, const float* trans, const float* quat,
-                           int64_t n_poses, const tohip_camera* cam, const float* mask, const uint32_t* bits, float* obs, void* workspace,
-                           size_t workspace_bytes) {
-    if (!packed || !trans || !quat || !cam || !workspace || n <= 0 || n_poses <= 0 || n > INT32_MAX || (mask && bits)) return TOHIP_EINVAL;
-    if ((n_poses + TO_POSE_TILE - 1) / TO_POSE_TILE > 65535 || n_poses > INT32_MAX) return TOHIP_EINVAL;   // the grid's y extent
-    if (workspace_bytes < pose_multi_bytes(n, n_poses)) return TOHIP_ENOSPC;
-    a.cv = cloud_view(packed, n);
-    a.trans = trans; a.quat = quat; a.n_poses = (int)n_poses; a.k = make_evalk(cam); a.obs = obs;
-    if (bits) a.bits = bits;
-    else a.mask = mask;
-    a.part = (double*)workspace;
-    f.part = a.part; f.nparts = 0; f.trans = trans; f.quat = quat; f.k = a.k; f.eps = cam->eps;
-    f.scalars_out = nullptr; f.scalars_in = nullptr; f.gout = nullptr; f.coef_mode = 2; f.grad = 0; f.trans_grad = nullptr; f.quat_grad = nullptr;
-    f.adam = 0; f.mt = f.vt = f.mq = f.vq = nullptr; f.lr_pose = f.lr_quat = f.beta1 = f.beta2 = f.adam_eps = 0.f; f.step = 0; f.loss_log = nullptr;
+// the stream pass over tiles of TILE poses, then one finish block per pose
+template <int TILE, bool FWD, bool GRAD>
+inline int pose_launch(PoseCall& c) {
+    const int nb = pose_stream_blocks<FWD, GRAD>(c.a.cv.npad);
+    const dim3 grid(nb, (c.a.n_poses + TILE - 1) / TILE);
+    if (c.occ) k_pose_stream<TILE, FWD, GRAD, true><<<grid, TO_BLOCK, 0, c.st>>>(c.a);
+    else k_pose_stream<TILE, FWD, GRAD, false><<<grid, TO_BLOCK, 0, c.st>>>(c.a);
+    TO_HIP_CHECK_LAUNCH();
+    c.f.nparts = nb;
+    c.f.grad = GRAD ? 1 : 0;
+    k_pose_finish<<<c.a.n_poses, nb > 64 ? 1024 : TO_BLOCK, 0, c.st>>>(c.f);
+    TO_HIP_CHECK_LAUNCH();
     return TOHIP_OK;
 }
 }  // namespace
@@ -747,97 +591,106 @@ extern "C" size_t tohip_pose_workspace_bytes(int64_t n_points) {
 }
 
 namespace {
-// the bodies of the exported calls, with the mask given as floats (caller's order) or as an occlusion bit row (packed order)
+// the bodies of the exported calls
 int pose_forward_impl(const void* packed, int64_t n, const float* trans, const float* quat, const tohip_camera* cam, const float* mask,
-                      const uint32_t* bits, float* obs, float* scalars, void* workspace, size_t workspace_bytes, void* stream_) {
+                      const uint32_t* bits, bool need_bits,
+                      float* obs, float* scalars, void* workspace, size_t workspace_bytes, void* stream_) {
     if (!obs || !scalars) return TOHIP_EINVAL;
     PoseCall c;
-    const int rc = pose_call_init(c, packed, n, trans, quat, cam, mask, bits, workspace, workspace_bytes, stream_);
+    const int rc = pose_call_init(c, packed, n, trans, quat, 1, PoseWs::single, cam, mask, bits, need_bits, workspace, workspace_bytes,
+                                  stream_);
     if (rc != TOHIP_OK) return rc;
     c.a.obs = obs;
     c.f.scalars_out = scalars;
-    return pose_launch<true, false>(c);
+    return pose_launch<1, true, false>(c);
 }
 
 int pose_backward_impl(const void* packed, int64_t n, const float* trans, const float* quat, const tohip_camera* cam, const float* mask,
-                       const uint32_t* bits, const float* grad_obs, const float* scalars, const float* gout, float* trans_grad,
-                       float* quat_grad, void* workspace, size_t workspace_bytes, void* stream_) {
+                       const uint32_t* bits, bool need_bits,
+                       const float* grad_obs, const float* scalars, const float* gout, float* trans_grad, float* quat_grad,
+                       void* workspace, size_t workspace_bytes, void* stream_) {
     if (!trans_grad || !quat_grad || (!grad_obs && (!scalars || !gout))) return TOHIP_EINVAL;
     PoseCall c;
-    const int rc = pose_call_init(c, packed, n, trans, quat, cam, mask, bits, workspace, workspace_bytes, stream_);
+    const int rc = pose_call_init(c, packed, n, trans, quat, 1, PoseWs::single, cam, mask, bits, need_bits, workspace, workspace_bytes,
+                                  stream_);
     if (rc != TOHIP_OK) return rc;
     c.a.grad_obs = grad_obs;
     c.f.coef_mode = grad_obs ? 0 : 1;
     c.f.scalars_in = scalars; c.f.gout = gout;
     c.f.trans_grad = trans_grad; c.f.quat_grad = quat_grad;
-    return pose_launch<false, true>(c);
+    return pose_launch<1, false, true>(c);
 }
 
 int pose_forward_backward_impl(const void* packed, int64_t n, const float* trans, const float* quat, const tohip_camera* cam,
-                               const float* mask, const uint32_t* bits, float* obs, float* scalars, const float* gout, float* trans_grad,
-                               float* quat_grad, void* workspace, size_t workspace_bytes, void* stream_) {
+                               const float* mask, const uint32_t* bits, bool need_bits, float* obs, float* scalars, const float* gout,
+                               float* trans_grad, float* quat_grad,
+                               void* workspace, size_t workspace_bytes, void* stream_) {
     if (!obs || !scalars || !trans_grad || !quat_grad) return TOHIP_EINVAL;
     PoseCall c;
-    const int rc = pose_call_init(c, packed, n, trans, quat, cam, mask, bits, workspace, workspace_bytes, stream_);
+    const int rc = pose_call_init(c, packed, n, trans, quat, 1, PoseWs::single, cam, mask, bits, need_bits, workspace, workspace_bytes,
+                                  stream_);
     if (rc != TOHIP_OK) return rc;
     c.a.obs = obs;
     c.f.scalars_out = scalars;
     c.f.coef_mode = 2; c.f.gout = gout;
     c.f.trans_grad = trans_grad; c.f.quat_grad = quat_grad;
-    return pose_launch<true, true>(c);
+    return pose_launch<1, true, true>(c);
 }
 
 int pose_opt_step_impl(const void* packed, int64_t n, float* trans, float* quat, const tohip_camera* cam, const float* mask,
-                       const uint32_t* bits, float* obs, float* scalars, float* trans_grad, float* quat_grad, float* exp_avg_t,
-                       float* exp_avg_sq_t, float* exp_avg_q, float* exp_avg_sq_q, float lr_pose, float lr_quat, float beta1, float beta2,
-                       float adam_eps, int32_t step, float* loss_log, void* workspace, size_t workspace_bytes, void* stream_) {
+                       const uint32_t* bits, bool need_bits, float* obs,
+                       float* scalars, float* trans_grad, float* quat_grad, float* exp_avg_t, float* exp_avg_sq_t, float* exp_avg_q,
+                       float* exp_avg_sq_q, float lr_pose, float lr_quat, float beta1, float beta2, float adam_eps, int32_t step,
+                       float* loss_log, void* workspace, size_t workspace_bytes, void* stream_) {
     if (!obs || !scalars || !exp_avg_t || !exp_avg_sq_t || !exp_avg_q || !exp_avg_sq_q || !loss_log || step < 1) return TOHIP_EINVAL;
     PoseCall c;
-    const int rc = pose_call_init(c, packed, n, trans, quat, cam, mask, bits, workspace, workspace_bytes, stream_);
+    const int rc = pose_call_init(c, packed, n, trans, quat, 1, PoseWs::single, cam, mask, bits, need_bits, workspace, workspace_bytes,
+                                  stream_);
     if (rc != TOHIP_OK) return rc;
     c.a.obs = obs;
     c.f.scalars_out = scalars;
-    c.f.coef_mode = 2;
     c.f.trans_grad = trans_grad; c.f.quat_grad = quat_grad;
+    c.f.coef_mode = 2;
     c.f.adam = 1; c.f.mt = exp_avg_t; c.f.vt = exp_avg_sq_t; c.f.mq = exp_avg_q; c.f.vq = exp_avg_sq_q;
     c.f.lr_pose = lr_pose; c.f.lr_quat = lr_quat; c.f.beta1 = beta1; c.f.beta2 = beta2; c.f.adam_eps = adam_eps; c.f.step = step; c.f.loss_log = loss_log;
-    return pose_launch<true, true>(c);
+    return pose_launch<1, true, true>(c);
 }
 
 int pose_forward_backward_multi_impl(const void* packed, int64_t n, const float* trans, const float* quat, int64_t n_poses,
-                                     const tohip_camera* cam, const float* mask, const uint32_t* bits, float* obs, float* scalars,
-                                     const float* gout, float* trans_grad, float* quat_grad, void* workspace, size_t workspace_bytes,
-                                     void* stream_) {
+                                     const tohip_camera* cam, const float* mask, const uint32_t* bits, bool need_bits, float* obs,
+                                     float* scalars, const float* gout,
+                                     float* trans_grad, float* quat_grad, void* workspace, size_t workspace_bytes, void* stream_) {
     if (!scalars || (trans_grad == nullptr) != (quat_grad == nullptr)) return TOHIP_EINVAL;
-    PoseMultiArgs a;
-    PoseFinish f;
-    const int rc = pose_multi_init(a, f, packed, n, trans, quat, n_poses, cam, mask, bits, obs, workspace, workspace_bytes);
+    PoseCall c;
+    const int rc = pose_call_init(c, packed, n, trans, quat, n_poses, PoseWs::batch, cam, mask, bits, need_bits, workspace, workspace_bytes,
+                                  stream_);
     if (rc != TOHIP_OK) return rc;
-    f.scalars_out = scalars;
-    if (!trans_grad) return pose_multi_launch<false>(a, bits != nullptr, f, 0, (hipStream_t)stream_);   // scoring: no gradient sums
-    f.gout = gout; f.trans_grad = trans_grad; f.quat_grad = quat_grad;
-    return pose_multi_launch<true>(a, bits != nullptr, f, 0, (hipStream_t)stream_);
+    c.a.obs = obs;
+    c.f.scalars_out = scalars;
+    if (!trans_grad) return pose_launch<TO_POSE_TILE, true, false>(c);   // scoring: no gradient sums
+    c.f.coef_mode = 2; c.f.gout = gout;
+    c.f.trans_grad = trans_grad; c.f.quat_grad = quat_grad;
+    return pose_launch<TO_POSE_TILE, true, true>(c);
 }
 }  // namespace
 
 extern "C" int tohip_pose_forward(const void* packed, int64_t n, const float* trans, const float* quat,
                                   const tohip_camera* cam, const float* mask, float* obs, float* scalars,
                                   void* workspace, size_t workspace_bytes, void* stream_) {
-    return pose_forward_impl(packed, n, trans, quat, cam, mask, nullptr, obs, scalars, workspace, workspace_bytes, stream_);
+    return pose_forward_impl(packed, n, trans, quat, cam, mask, nullptr, false, obs, scalars, workspace, workspace_bytes, stream_);
 }
 
 extern "C" int tohip_pose_forward_bits(const void* packed, int64_t n, const float* trans, const float* quat,
                                        const tohip_camera* cam, const uint32_t* occlusion_bits, float* obs, float* scalars,
                                        void* workspace, size_t workspace_bytes, void* stream_) {
-    if (!occlusion_bits) return TOHIP_EINVAL;
-    return pose_forward_impl(packed, n, trans, quat, cam, nullptr, occlusion_bits, obs, scalars, workspace, workspace_bytes, stream_);
+    return pose_forward_impl(packed, n, trans, quat, cam, nullptr, occlusion_bits, true, obs, scalars, workspace, workspace_bytes, stream_);
 }
 
 extern "C" int tohip_pose_backward(const void* packed, int64_t n, const float* trans, const float* quat,
                                    const tohip_camera* cam, const float* mask, const float* grad_obs,
                                    const float* scalars, const float* gout, float* trans_grad, float* quat_grad,
                                    void* workspace, size_t workspace_bytes, void* stream_) {
-    return pose_backward_impl(packed, n, trans, quat, cam, mask, nullptr, grad_obs, scalars, gout, trans_grad, quat_grad, workspace,
+    return pose_backward_impl(packed, n, trans, quat, cam, mask, nullptr, false, grad_obs, scalars, gout, trans_grad, quat_grad, workspace,
                               workspace_bytes, stream_);
 }
 
@@ -845,15 +698,14 @@ extern "C" int tohip_pose_backward_bits(const void* packed, int64_t n, const flo
                                         const tohip_camera* cam, const uint32_t* occlusion_bits, const float* grad_obs,
                                         const float* scalars, const float* gout, float* trans_grad, float* quat_grad,
                                         void* workspace, size_t workspace_bytes, void* stream_) {
-    if (!occlusion_bits) return TOHIP_EINVAL;
-    return pose_backward_impl(packed, n, trans, quat, cam, nullptr, occlusion_bits, grad_obs, scalars, gout, trans_grad, quat_grad,
+    return pose_backward_impl(packed, n, trans, quat, cam, nullptr, occlusion_bits, true, grad_obs, scalars, gout, trans_grad, quat_grad,
                               workspace, workspace_bytes, stream_);
 }
 
 extern "C" int tohip_pose_forward_backward(const void* packed, int64_t n, const float* trans, const float* quat,
                                            const tohip_camera* cam, const float* mask, float* obs, float* scalars, const float* gout,
                                            float* trans_grad, float* quat_grad, void* workspace, size_t workspace_bytes, void* stream_) {
-    return pose_forward_backward_impl(packed, n, trans, quat, cam, mask, nullptr, obs, scalars, gout, trans_grad, quat_grad, workspace,
+    return pose_forward_backward_impl(packed, n, trans, quat, cam, mask, nullptr, false, obs, scalars, gout, trans_grad, quat_grad, workspace,
                                       workspace_bytes, stream_);
 }
 
@@ -861,8 +713,7 @@ extern "C" int tohip_pose_forward_backward_bits(const void* packed, int64_t n, c
                                                 const tohip_camera* cam, const uint32_t* occlusion_bits, float* obs, float* scalars,
                                                 const float* gout, float* trans_grad, float* quat_grad, void* workspace,
                                                 size_t workspace_bytes, void* stream_) {
-    if (!occlusion_bits) return TOHIP_EINVAL;
-    return pose_forward_backward_impl(packed, n, trans, quat, cam, nullptr, occlusion_bits, obs, scalars, gout, trans_grad, quat_grad,
+    return pose_forward_backward_impl(packed, n, trans, quat, cam, nullptr, occlusion_bits, true, obs, scalars, gout, trans_grad, quat_grad,
                                       workspace, workspace_bytes, stream_);
 }
 
@@ -870,7 +721,7 @@ extern "C" int tohip_pose_opt_step(const void* packed, int64_t n, float* trans, 
                                    float* obs, float* scalars, float* trans_grad, float* quat_grad, float* exp_avg_t, float* exp_avg_sq_t,
                                    float* exp_avg_q, float* exp_avg_sq_q, float lr_pose, float lr_quat, float beta1, float beta2,
                                    float adam_eps, int32_t step, float* loss_log, void* workspace, size_t workspace_bytes, void* stream_) {
-    return pose_opt_step_impl(packed, n, trans, quat, cam, mask, nullptr, obs, scalars, trans_grad, quat_grad, exp_avg_t, exp_avg_sq_t,
+    return pose_opt_step_impl(packed, n, trans, quat, cam, mask, nullptr, false, obs, scalars, trans_grad, quat_grad, exp_avg_t, exp_avg_sq_t,
                               exp_avg_q, exp_avg_sq_q, lr_pose, lr_quat, beta1, beta2, adam_eps, step, loss_log, workspace,
                               workspace_bytes, stream_);
 }
@@ -880,8 +731,7 @@ extern "C" int tohip_pose_opt_step_bits(const void* packed, int64_t n, float* tr
                                         float* exp_avg_t, float* exp_avg_sq_t, float* exp_avg_q, float* exp_avg_sq_q, float lr_pose,
                                         float lr_quat, float beta1, float beta2, float adam_eps, int32_t step, float* loss_log,
                                         void* workspace, size_t workspace_bytes, void* stream_) {
-    if (!occlusion_bits) return TOHIP_EINVAL;
-    return pose_opt_step_impl(packed, n, trans, quat, cam, nullptr, occlusion_bits, obs, scalars, trans_grad, quat_grad, exp_avg_t,
+    return pose_opt_step_impl(packed, n, trans, quat, cam, nullptr, occlusion_bits, true, obs, scalars, trans_grad, quat_grad, exp_avg_t,
                               exp_avg_sq_t, exp_avg_q, exp_avg_sq_q, lr_pose, lr_quat, beta1, beta2, adam_eps, step, loss_log, workspace,
                               workspace_bytes, stream_);
 }
@@ -894,34 +744,34 @@ extern "C" size_t tohip_pose_workspace_bytes_multi(int64_t n_points, int64_t n_p
 extern "C" int tohip_pose_forward_backward_multi(const void* packed, int64_t n, const float* trans, const float* quat, int64_t n_poses,
                                                  const tohip_camera* cam, const float* mask, float* obs, float* scalars, const float* gout,
                                                  float* trans_grad, float* quat_grad, void* workspace, size_t workspace_bytes, void* stream_) {
-    return pose_forward_backward_multi_impl(packed, n, trans, quat, n_poses, cam, mask, nullptr, obs, scalars, gout, trans_grad, quat_grad,
-                                            workspace, workspace_bytes, stream_);
+    return pose_forward_backward_multi_impl(packed, n, trans, quat, n_poses, cam, mask, nullptr, false, obs, scalars, gout, trans_grad,
+                                            quat_grad, workspace, workspace_bytes, stream_);
 }
 
 extern "C" int tohip_pose_forward_backward_multi_bits(const void* packed, int64_t n, const float* trans, const float* quat,
                                                       int64_t n_poses, const tohip_camera* cam, const uint32_t* occlusion_bits, float* obs,
                                                       float* scalars, const float* gout, float* trans_grad, float* quat_grad,
                                                       void* workspace, size_t workspace_bytes, void* stream_) {
-    if (!occlusion_bits) return TOHIP_EINVAL;
-    return pose_forward_backward_multi_impl(packed, n, trans, quat, n_poses, cam, nullptr, occlusion_bits, obs, scalars, gout, trans_grad,
+    return pose_forward_backward_multi_impl(packed, n, trans, quat, n_poses, cam, nullptr, occlusion_bits, true, obs, scalars, gout, trans_grad,
                                             quat_grad, workspace, workspace_bytes, stream_);
 }
 
 extern "C" int tohip_pose_opt_step_multi(const tohip_pose_opt* o, int32_t step, float* obs, void* stream_) {
     if (!o || !o->scalars || !o->exp_avg_t || !o->exp_avg_sq_t || !o->exp_avg_q || !o->exp_avg_sq_q || !o->loss_log || step < 1 ||
-        step > o->n_steps || (o->occlusion_mask && o->occlusion_bits))
+        step > o->n_steps)
         return TOHIP_EINVAL;
-    PoseMultiArgs a;
-    PoseFinish f;
-    const int rc = pose_multi_init(a, f, o->packed, o->n_points, o->trans, o->quat, o->n_poses, &o->cam, o->occlusion_mask, o->occlusion_bits,
-                                   obs, o->workspace, o->workspace_bytes);
+    PoseCall c;
+    const int rc = pose_call_init(c, o->packed, o->n_points, o->trans, o->quat, o->n_poses, PoseWs::batch, &o->cam,
+                                  o->occlusion_mask, o->occlusion_bits, false, o->workspace, o->workspace_bytes, stream_);
     if (rc != TOHIP_OK) return rc;
-    f.scalars_out = o->scalars;
-    f.trans_grad = o->trans_grad; f.quat_grad = o->quat_grad;
-    f.adam = 1; f.mt = o->exp_avg_t; f.vt = o->exp_avg_sq_t; f.mq = o->exp_avg_q; f.vq = o->exp_avg_sq_q;
-    f.lr_pose = o->lr_pose; f.lr_quat = o->lr_quat; f.beta1 = o->beta1; f.beta2 = o->beta2; f.adam_eps = o->adam_eps; f.step = step;
-    f.loss_log = o->loss_log;
-    return pose_multi_launch<true>(a, o->occlusion_bits != nullptr, f, o->n_steps, (hipStream_t)stream_);
+    c.a.obs = obs;
+    c.f.scalars_out = o->scalars;
+    c.f.trans_grad = o->trans_grad; c.f.quat_grad = o->quat_grad;
+    c.f.coef_mode = 2;
+    c.f.adam = 1; c.f.mt = o->exp_avg_t; c.f.vt = o->exp_avg_sq_t; c.f.mq = o->exp_avg_q; c.f.vq = o->exp_avg_sq_q;
+    c.f.lr_pose = o->lr_pose; c.f.lr_quat = o->lr_quat; c.f.beta1 = o->beta1; c.f.beta2 = o->beta2; c.f.adam_eps = o->adam_eps; c.f.step = step;
+    c.f.n_steps = o->n_steps; c.f.loss_log = o->loss_log;
+    return pose_launch<TO_POSE_TILE, true, true>(c);
 }
 
 extern "C" int tohip_to_camera_frame(const float* xyz, int64_t n, const float* quat, const float* trans, int normalize,
