@@ -37,7 +37,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_roadmap_knn / tohip_roadmap_routes_bytes / tohip_roadmap_relax / tohip_roadmap_pred / tohip_tour_plan_via (a
+/* (still 15) + tohip_path_bytes / tohip_path_refine (refine a planned walk: any-angle shortcuts and even waypoint spacing): new symbols
+ * only.
+ * (still 15) + tohip_roadmap_knn / tohip_roadmap_routes_bytes / tohip_roadmap_relax / tohip_roadmap_pred / tohip_tour_plan_via (a
  * free-space roadmap: routes where no straight leg is open): new symbols only.
  * (still 15) + tohip_clearance_edges / tohip_tour_bytes / tohip_tour_plan (a collision-checked tour through chosen views): new symbols
  * only.
@@ -808,6 +810,40 @@ int tohip_roadmap_pred(const int32_t *nbr, const int64_t *len, const uint8_t *op
                        int64_t n_sources, const int64_t *D, int32_t *pred, void *stream);
 int tohip_tour_plan_via(const float *nodes, int64_t n, const int32_t *edge_idx, const int64_t *via_D, int64_t via_ld, int closed,
                         int64_t max_moves, void *buf, size_t bytes, uint8_t *via_flag, void *stream);
+
+/* ---- refine a planned walk into a trajectory (path_kernels.hip) -----------------------------------------------------
+ * nodes (n_nodes, 3) f32 on the device in walking order, 2 <= n_nodes = L <= TOHIP_PATH_MAX_NODES; keep (L) uint8 or NULL: the nodes
+ * the result must pass through (nodes 0 and L - 1 always are); quats (L, 4) f32 or NULL; 1 <= window = W <= L - 1.
+ * A chord is a pair (i, j), i < j, j - i <= W, of length w_ij = llrint(sqrt(d2) 2^20), the tour's length (d2 in f64 without
+ * contraction, the differences lower index minus higher; held at 2^42).  The input leg (i, i + 1) is always open.  A chord with
+ * j >= i + 2 is open iff no kept node lies strictly between i and j, w_ij <= 2^40 and open_band[i][j - i - 1] != 0 — open_band (L, W)
+ * uint8 is the caller's: non-zero where tohip_clearance_edges gave idx == -1 for a = node i, b = node j (column 0, the input legs,
+ * is not read).
+ * Search: D[0] = 0, D[j] = min over open (i, j) of D[i] + w_ij; pred[j] = the lowest i that attains it, pred[0] = -1.  The corners
+ * c_0 = 0 < ... < c_m = L - 1 follow pred back from L - 1: every kept node is a corner, length_fixed = D[L - 1] <= input_length_fixed
+ * = the sum of the input legs, and W = 1 or keep all ones gives the input's nodes.
+ * Rows: H = llrint((double)spacing 2^20), at least 1 and held at 2^42 (spacing = 0: corners only, n_q = 1).  Corner leg q from A =
+ * node c_q to B = node c_q+1, of length w_q, is cut into n_q = max(1, (w_q + H - 1) / H) equal pieces: row (q, t), 0 <= t < n_q, is per
+ * coordinate (float)((double)A + ((double)B - (double)A) ((double)t / (double)n_q)) in f64 without contraction (t = 0: A itself); the
+ * last row is node L - 1; R = 1 + the sum of n_q.  row_node (R) int32 = the input index at a corner row, -1 at an interpolated one.
+ * With quats: for a row between the consecutive kept corners a and b, u = s_row / S_ab with S_ab the summed lengths of the corner legs
+ * from a to b and s_row those before the row's leg plus ((double)w_q (double)t) / (double)n_q (u = 0 when S_ab = 0); q_a, q_b = the
+ * two kept rows' quaternions divided by their f64 norms sqrt(((w w + x x) + y y) + z z), q_b negated when q_a . q_b < 0; the row's
+ * quaternion is (1 - u) q_a + u q_b divided by its norm, rounded to f32.  A kept row's quaternion is its own, normalised; the
+ * quaternions of rows that are not kept are never read.
+ * buf (tohip_path_bytes(L, max_rows) device bytes, caller-owned, 256-byte aligned, 1 <= max_rows <= TOHIP_PATH_MAX_ROWS), every
+ * section aligned to 256 bytes: [header 32 x int64: [0] m [1] R [2] length_fixed [3] input_length_fixed [4] status [5] the number of
+ * open chords with j >= i + 2] [D L int64] [pred L int32] [corner L int32: the first m + 1 count, -1 behind them] [out_poses
+ * max_rows x 3 f32] [out_quats max_rows x 4 f32] [row_node max_rows int32].
+ * status bit 0: a coordinate of nodes, or a kept row's quaternion, is not finite, or that quaternion is zero: only the header is
+ * written, with m = R = 0.  Bit 1: R > max_rows: the header ([1] = the R that is needed), D, pred and corner are written, no row is.
+ * One launch of one block, nothing synchronises; integers after the lengths: the same bits in every run.
+ * tohip_path_bytes: 0 for sizes out of range.  spacing must be finite and >= 0. */
+#define TOHIP_PATH_MAX_NODES 1024
+#define TOHIP_PATH_MAX_ROWS 4096
+size_t tohip_path_bytes(int64_t n_nodes, int64_t max_rows);
+int tohip_path_refine(const float *nodes, const float *quats, const uint8_t *keep, int64_t n_nodes, int64_t window,
+                      const uint8_t *open_band, float spacing, int64_t max_rows, void *buf, size_t bytes, void *stream);
 
 /* ---- input formats (pointcloud_utils.py, launch/voxels_filtering.launch) --------------------------------
  * PointCloud2 payload -> (N,3) f32 with non-finite rows removed, in message order

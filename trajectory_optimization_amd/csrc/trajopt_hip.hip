@@ -13,6 +13,7 @@
 #include "views_kernels.hip"
 #include "tour_kernels.hip"
 #include "roadmap_kernels.hip"
+#include "path_kernels.hip"
 #include "covmap_kernels.hip"
 #include "loss_kernels.hip"
 #include "ingest_kernels.hip"

@@ -1158,6 +1158,90 @@ def tour_plan_via(nodes, edge_idx, via_D, closed=False, max_moves=None):
     return buf, flag
 
 
+PATH_MAX_NODES = 1024   # TOHIP_PATH_MAX_NODES
+PATH_MAX_ROWS = 4096    # TOHIP_PATH_MAX_ROWS
+
+
+def check_path(path, quats=None, keep=None, window=None, spacing=None, max_rows=None):
+    """The arguments of a path refinement: path (L,3) a floating tensor with 2 <= L <= PATH_MAX_NODES, quats None or (L,4) floating,
+    keep None or (L,) bool / uint8, window None (L - 1) or an integer in 1..L-1, spacing None or a finite number > 0, max_rows None
+    (PATH_MAX_ROWS) or an integer in 1..PATH_MAX_ROWS -> (L, window, spacing as a float or None, max_rows); ValueError otherwise.
+    Nothing is launched."""
+    if not torch.is_tensor(path) or not path.is_floating_point() or path.dim() != 2 or path.shape[1] != 3:
+        raise ValueError(f"path must be a floating-point tensor of shape (L,3), got "
+                         f"{tuple(path.shape) if torch.is_tensor(path) else type(path).__name__}")
+    L = path.shape[0]
+    if L < 2 or L > PATH_MAX_NODES:
+        raise ValueError(f"path must hold 2 <= L <= {PATH_MAX_NODES} nodes, got L = {L}")
+    if quats is not None and (not torch.is_tensor(quats) or not quats.is_floating_point() or tuple(quats.shape) != (L, 4)):
+        raise ValueError(f"quats must be None or a floating-point tensor of shape ({L},4), got "
+                         f"{tuple(quats.shape) if torch.is_tensor(quats) else type(quats).__name__}")
+    if keep is not None and (not torch.is_tensor(keep) or keep.dtype not in (torch.bool, torch.uint8) or tuple(keep.shape) != (L,)):
+        raise ValueError(f"keep must be None or a bool / uint8 tensor of shape ({L},), got "
+                         f"{(tuple(keep.shape), keep.dtype) if torch.is_tensor(keep) else type(keep).__name__}")
+    if window is None:
+        window = L - 1
+    elif isinstance(window, bool) or not isinstance(window, (int, np.integer)) or not 1 <= window <= L - 1:
+        raise ValueError(f"window must be None or an integer in 1..{L - 1}, got {window!r}")
+    h = None
+    if spacing is not None:
+        try:
+            h = float(spacing)
+        except (TypeError, ValueError):
+            h = float("nan")
+        with np.errstate(over="ignore"):
+            hf = float(np.float32(h))   # what the library is handed
+        if not (np.isfinite(hf) and hf > 0.0):
+            raise ValueError(f"spacing must be None or a finite number > 0 (as a float32), got {spacing!r}")
+    if max_rows is None:
+        max_rows = PATH_MAX_ROWS
+    elif isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or not 1 <= max_rows <= PATH_MAX_ROWS:
+        raise ValueError(f"max_rows must be None or an integer in 1..{PATH_MAX_ROWS}, got {max_rows!r}")
+    return L, int(window), h, int(max_rows)
+
+
+def path_layout(L, max_rows):
+    """Byte offsets of a refined path's buffer (include/trajopt_hip.h, tohip_path_bytes): every section aligned to 256 bytes."""
+    up = lambda v: (v + 255) // 256 * 256
+    out, o = {"header": 0}, 256
+    for name, nbytes in (("D", 8 * L), ("pred", 4 * L), ("corner", 4 * L), ("out_poses", 12 * max_rows), ("out_quats", 16 * max_rows),
+                         ("row_node", 4 * max_rows)):
+        out[name] = o
+        o += up(nbytes)
+    out["total"] = o
+    return out
+
+
+def path_refine(P, quats, keep, open_band, window=None, spacing=None, max_rows=None):
+    """tohip_path_refine over P (L,3) f32 contiguous on the device, quats (L,4) f32 or None, keep (L,) bool / uint8 or None and
+    open_band (L,W) bool / uint8, all on P's device -> the buffer (uint8, path_layout(L, max_rows)) on the device; one launch.  The
+    header's status word is the caller's to read."""
+    L, W, h, max_rows = check_path(P, quats, keep, window, spacing, max_rows)
+    _require_cuda(P, "P")
+    dev = P.device
+    if P.dtype != torch.float32 or not P.is_contiguous():
+        raise ValueError("P must be a contiguous float32 tensor")
+    if quats is not None and not (quats.dtype == torch.float32 and quats.is_contiguous() and quats.device == dev):
+        raise ValueError("quats must be a contiguous float32 tensor on P's device")
+    if keep is not None:
+        keep = keep.view(torch.uint8) if keep.dtype == torch.bool else keep
+        if not (keep.is_contiguous() and keep.device == dev):
+            raise ValueError("keep must be contiguous on P's device")
+    if torch.is_tensor(open_band) and open_band.dtype == torch.bool:
+        open_band = open_band.view(torch.uint8)
+    if not (torch.is_tensor(open_band) and open_band.dtype == torch.uint8 and open_band.is_contiguous() and tuple(open_band.shape) == (L, W)
+            and open_band.device == dev):
+        raise ValueError(f"open_band must be a contiguous ({L},{W}) bool or uint8 tensor on P's device")
+    lib = _lib.lib()
+    lay = path_layout(L, max_rows)
+    assert lib.tohip_path_bytes(L, max_rows) == lay["total"]
+    buf = torch.empty(lay["total"], dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.tohip_path_refine(ptr(P), ptr(quats), ptr(keep), L, W, ptr(open_band), 0.0 if h is None else h, max_rows, ptr(buf),
+                                    lay["total"], stream_ptr()), "tohip_path_refine")
+    return buf
+
+
 def clearance_terms(n_wps, n_traj, mode, device):
     """The float64 buffer the clearance query of `mode` fills for n_traj trajectories of n_wps waypoints: the per-waypoint terms lead
     it in either mode (what the step tails, the regularisers' kernel and the team calls read)."""

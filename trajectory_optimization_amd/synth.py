@@ -10,6 +10,8 @@ waypoint positions (W,3) f32 and wxyz quaternions (W,4) f32
 (/root/reference/src/trajectory_optimization.py:66-80), intrinsics as returned
 by load_intrinsics (/root/reference/src/tools.py:320-325).
 """
+import math
+
 import numpy as np
 
 # /root/reference/src/tools.py:320-325
@@ -392,3 +394,112 @@ def doorway_scene():
                         [2.1, 2.3, 1.1], [1.9, 3.4, 0.9], [2.2, 2.8, 1.3], [2.25, -2.25, 1.25]])
     return dict(points=np.concatenate([wall] + faces).astype(np.float32), radius=0.3, nodes=nodes, left=[0, 1, 2, 3], right=[4, 5, 6],
                 enclosed=7, lattice=roadmap_lattice((-3.0, -4.0, 0.5), (3.0, 4.0, 1.5), 0.5))
+
+
+# ---- tools.refine_path restated in numpy: what path_kernels.hip must give, element for element ------------------------
+PATH_MAX_NODES = 1024
+PATH_MAX_ROWS = 4096
+
+
+def path_chord_lengths(P):
+    """w (L,L) int64, read at [i, j] with i < j: rint(min(|P_i - P_j| 2^20, 2^42)) in f64, the differences lower index minus higher
+    (the tour's length without its limit: an input leg is open however long it is)."""
+    Pd = np.asarray(P, dtype=np.float32).astype(np.float64)
+    d = Pd[:, None, :] - Pd[None, :, :]
+    L = np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]) * 1048576.0
+    return np.rint(np.minimum(L, float(1 << 42))).astype(np.int64)
+
+
+def path_spacing_fixed(spacing):
+    """H: rint((double)(float)spacing 2^20), at least 1 and held at 2^42; 0 for no spacing."""
+    if spacing is None or float(np.float32(spacing)) == 0.0:
+        return 0
+    return max(1, int(np.rint(min(float(np.float32(spacing)) * 1048576.0, float(1 << 42)))))
+
+
+def _unit_quat(q):
+    w, x, y, z = (float(v) for v in q)
+    n = math.sqrt(((w * w + x * x) + y * y) + z * z)
+    return [w / n, x / n, y / n, z / n]
+
+
+def path_refine_ref(P, keep, open_band, window, spacing, quats=None, max_rows=PATH_MAX_ROWS):
+    """The whole definition: P (L,3) f32 in walking order, keep (L,) or None, open_band (L,W), window W, spacing h or None ->
+    dict(status, m, R, length_fixed, input_length_fixed, n_open, D, pred, corner, corners, row_node, poses, quats): int64 for the
+    search, f64 for rows and quaternions.  With status bit 0 only the header fields are there (m = R = 0); with bit 1 (R > max_rows)
+    row_node / poses / quats are None."""
+    P = np.asarray(P, dtype=np.float32)
+    L, W = len(P), int(window)
+    kept = np.zeros(L, dtype=bool) if keep is None else np.asarray(keep).astype(bool).copy()
+    kept[0] = kept[-1] = True
+    bad = not np.isfinite(P).all()
+    if quats is not None:
+        quats = np.asarray(quats, dtype=np.float32)
+        qk = quats[kept]
+        bad = bad or bool((~np.isfinite(qk).all(axis=1) | (qk == 0).all(axis=1)).any())
+    if bad:
+        return dict(status=1, m=0, R=0, length_fixed=0, input_length_fixed=0, n_open=0)
+    w = path_chord_lengths(P)
+    band = np.asarray(open_band).reshape(L, W) != 0
+    idx = np.arange(L)
+    last = np.maximum.accumulate(np.where(kept, idx, -1))   # the largest kept node <= i
+    nxt = np.minimum.accumulate(np.where(kept, idx, L)[::-1])[::-1]   # the smallest kept node >= i
+    D, pred, n_open = np.zeros(L, dtype=np.int64), np.full(L, -1, dtype=np.int32), 0
+    for j in range(1, L):
+        i = np.arange(max(j - W, last[j - 1]), j)
+        wi = w[i, j]
+        op = (wi <= TOUR_MAX_LEN) & band[i, j - i - 1]
+        n_open += int(op[:-1].sum())
+        op[-1] = True   # the input leg
+        key = np.where(op, D[i] + wi, np.iinfo(np.int64).max)
+        k = int(np.argmin(key))   # the first minimum: the lowest i
+        D[j], pred[j] = key[k], i[k]
+    corners = [L - 1]
+    while corners[-1] != 0:
+        corners.append(int(pred[corners[-1]]))
+    corners = corners[::-1]
+    m = len(corners) - 1
+    corner = np.full(L, -1, dtype=np.int32)
+    corner[:m + 1] = corners
+    H = path_spacing_fixed(spacing)
+    wq = [int(w[a, b]) for a, b in zip(corners, corners[1:])]
+    nq = [max(1, (x + H - 1) // H) if H else 1 for x in wq]
+    R = 1 + sum(nq)
+    out = dict(status=0, m=m, R=R, length_fixed=int(D[-1]), input_length_fixed=int(w[idx[:-1], idx[1:]].sum()), n_open=n_open, D=D,
+               pred=pred, corner=corner, corners=np.asarray(corners, dtype=np.int64), row_node=None, poses=None, quats=None)
+    if R > max_rows:
+        out["status"] = 2
+        return out
+    Pd = P.astype(np.float64)
+    poses, row_node = np.empty((R, 3), dtype=np.float32), np.full(R, -1, dtype=np.int32)
+    qrows = np.empty((R, 4), dtype=np.float32) if quats is not None else None
+    pre = np.concatenate([[0], np.cumsum(wq)]).astype(np.int64)   # the corner legs' lengths before corner q
+    pos = {c: q for q, c in enumerate(corners)}
+    r = 0
+    for q, (a, b) in enumerate(zip(corners, corners[1:])):
+        n = nq[q]
+        f = np.arange(n, dtype=np.float64) / float(n)
+        poses[r:r + n] = (Pd[a] + (Pd[b] - Pd[a]) * f[:, None]).astype(np.float32)
+        poses[r] = P[a]
+        row_node[r] = a
+        if quats is not None:
+            ka, kb = int(last[a]), int(nxt[a + 1])
+            S = float(pre[pos[kb]] - pre[pos[ka]])
+            qa, qb = _unit_quat(quats[ka]), _unit_quat(quats[kb])
+            dot = ((qa[0] * qb[0] + qa[1] * qb[1]) + qa[2] * qb[2]) + qa[3] * qb[3]
+            sg = -1.0 if dot < 0.0 else 1.0
+            for t in range(n):
+                if t == 0 and kept[a]:
+                    qrows[r] = _unit_quat(quats[a])
+                    continue
+                s = float(pre[q] - pre[pos[ka]]) + float(wq[q]) * float(t) / float(n)
+                u = s / S if S > 0.0 else 0.0
+                o = [(1.0 - u) * x + u * (sg * y) for x, y in zip(qa, qb)]
+                nn = math.sqrt(((o[0] * o[0] + o[1] * o[1]) + o[2] * o[2]) + o[3] * o[3])
+                qrows[r + t] = [x / nn for x in o]
+        r += n
+    poses[r], row_node[r] = P[L - 1], L - 1
+    if quats is not None:
+        qrows[r] = _unit_quat(quats[L - 1])
+    out.update(poses=poses, row_node=row_node, quats=qrows)
+    return out

@@ -696,3 +696,91 @@ def _plan_tour_via(cloud, pts, poses, quats, n, r, closed, max_moves, via, via_k
                 length=int(hdr[3]) * ops.TOUR_UNIT, nn_length=int(hdr[4]) * ops.TOUR_UNIT, length_fixed=int(hdr[3]),
                 nn_length_fixed=int(hdr[4]), moves=int(hdr[1]), converged=bool(hdr[2]), blocked=blocked, edge_distance=dist, D=D, nxt=nxt,
                 roadmap=rm, via_flag=via_flag, walk_nodes=walk_nodes)
+
+
+class RefinedPath:
+    """What refine_path returns.  poses (R,3) f32 and quats (R,4) f32 (None when no quaternions came in) on the device, ready for
+    ModelTraj.sharing_cloud_of; row_node (R,) int32 on the host: the input row a corner row came from, -1 at an interpolated row;
+    corners (m + 1,) int64 on the host: the input rows the refined path turns at, 0 first and L - 1 last; length / input_length in
+    metres (f64 from the integer sums length_fixed / input_length_fixed, units of 2^-20 m); leg_blocked (L - 1,) bool on the host:
+    the input legs the swept clearance query finds within the radius (reported, not acted on); n_open: the open chords that skip
+    at least one node; open_band (L,W) uint8 on the device: the chord stage's answers as the search read them."""
+    __slots__ = ("poses", "quats", "row_node", "corners", "length", "length_fixed", "input_length", "input_length_fixed", "leg_blocked",
+                 "n_open", "open_band")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def _path_chord_band(cloud, P, kept, W, r):
+    """open_band (L,W) uint8 on the device: 1 where the swept clearance query finds nothing within r of the chord (i, i + off + 1).
+    Only the admissible slots are asked — no kept node strictly between the ends — gathered on the device."""
+    L, dev = P.shape[0], P.device
+    idx = torch.arange(L, device=dev, dtype=torch.int64)
+    last = torch.cummax(torch.where(kept, idx, torch.full_like(idx, -1)), dim=0).values   # the largest kept node <= i
+    i = idx[:, None].expand(L, W)
+    j = i + torch.arange(1, W + 1, device=dev, dtype=torch.int64)[None, :]
+    ask = j < L
+    ask &= last[(j - 1).clamp(max=L - 1)] <= i
+    slot = torch.nonzero(ask.reshape(-1)).reshape(-1)
+    band = torch.zeros(L * W, dtype=torch.uint8, device=dev)
+    _, hit, _ = ops.clearance_edges(cloud, P[i.reshape(-1)[slot]], P[j.reshape(-1)[slot]], r)   # (the input legs are always asked)
+    band[slot] = (hit == -1).to(torch.uint8)
+    return band.view(L, W)
+
+
+def refine_path(points_or_cloud_or_model, path, quats=None, clearance_radius=None, spacing=None, keep=None, window=None, max_rows=None):
+    """Turn a planned walk into a trajectory: shortcut it under the same clearance radius, so that it runs at any
+    angle instead of along a roadmap's directions, and resample it at `spacing` metres with orientations turning evenly between
+    the views.  path: (L,3) poses with 2 <= L <= 1024, a Tour (its poses, quats and keep = the walk rows that are tour nodes) or a
+    PlannedPath (its poses); quats / keep given here take precedence.  keep (L,) bool: the rows the result must pass through (the
+    first and the last always are); window: the most rows a shortcut may span (default L - 1).  Every pair of rows at most
+    `window` apart with no kept row between them is put to the swept clearance query (edge_clearance); the shortest route over
+    the open chords and the input legs is found on the device in integer arithmetic — lengths in units of 2^-20 m, ties to the
+    lowest predecessor — so every run gives the same path.  Each leg between two corners is then cut into equal pieces no longer
+    than `spacing` (None: corners only); a row's quaternion is the normalised linear blend of the two kept rows around it by arc
+    length.  -> RefinedPath; ValueError when a coordinate (or a kept row's quaternion) is not finite or more than max_rows
+    (default 4 096) rows are needed.  Launches only, then one copy to the host."""
+    cloud, pts = _clearance_cloud(points_or_cloud_or_model, "refine_path")
+    if isinstance(path, Tour):
+        if keep is None:   # (without via every row of the walk is a tour node)
+            n = path.D.shape[0]
+            keep = torch.tensor([v < n for v in (path.walk_nodes if path.walk_nodes is not None else path.walk)], dtype=torch.bool)
+        quats = path.quats if quats is None else quats
+        path = path.poses
+    elif isinstance(path, PlannedPath):
+        path = path.poses
+    L, W, h, max_rows = ops.check_path(path, quats, keep, window, spacing, max_rows)
+    if clearance_radius is None:
+        raise ValueError("clearance_radius must be a finite number > 0, got None")
+    r = ops.check_tour_radius(clearance_radius)
+    cloud = _device_cloud(cloud, pts, "refine_path")
+    dev = cloud.device
+    P = path.detach().to(device=dev, dtype=torch.float32).contiguous()
+    qs = quats.detach().to(device=dev, dtype=torch.float32).contiguous() if quats is not None else None
+    kept = torch.zeros(L, dtype=torch.bool, device=dev) if keep is None else keep.to(dev) != 0
+    kept[0] = kept[L - 1] = True
+    band = _path_chord_band(cloud, P, kept, W, r)
+    buf = ops.path_refine(P, qs, kept, band, W, h, max_rows)
+    lay = ops.path_layout(L, max_rows)
+    # the one synchronisation: the header, the corners, row_node and the input legs' answers in one copy
+    h_ = torch.cat([buf[:256], buf[lay["corner"]:lay["corner"] + 4 * L], buf[lay["row_node"]:lay["row_node"] + 4 * max_rows],
+                    band[:L - 1, 0].contiguous()]).cpu()
+    hdr = h_[:256].view(torch.int64)
+    m, R, status = int(hdr[0]), int(hdr[1]), int(hdr[4])
+    if status & 1:
+        raise ValueError("refine_path: path holds a coordinate that is not finite, or a kept row's quaternion is zero or not finite")
+    if status & 2:
+        raise ValueError(f"refine_path: the refined path needs {R} rows, max_rows = {max_rows}")
+    o = 256
+    corners = h_[o:o + 4 * L].view(torch.int32)[:m + 1].to(torch.int64)
+    o += 4 * L
+    row_node = h_[o:o + 4 * R].view(torch.int32).clone()
+    o += 4 * max_rows
+    leg_blocked = h_[o:o + L - 1] == 0
+    poses = buf[lay["out_poses"]:lay["out_poses"] + 12 * R].view(torch.float32).view(R, 3).clone()
+    out_q = buf[lay["out_quats"]:lay["out_quats"] + 16 * R].view(torch.float32).view(R, 4).clone() if qs is not None else None
+    return RefinedPath(poses=poses, quats=out_q, row_node=row_node, corners=corners, length=int(hdr[2]) * ops.TOUR_UNIT,
+                       length_fixed=int(hdr[2]), input_length=int(hdr[3]) * ops.TOUR_UNIT, input_length_fixed=int(hdr[3]),
+                       leg_blocked=leg_blocked, n_open=int(hdr[5]), open_band=band)
