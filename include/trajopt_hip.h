@@ -37,7 +37,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_path_bytes / tohip_path_refine (refine a planned walk: any-angle shortcuts and even waypoint spacing): new symbols
+/* (still 15) + tohip_view_histogram / tohip_view_headings (propose candidate views: per-position bearing histograms of what is left to
+ * see, and the best headings of each): new symbols only.
+ * (still 15) + tohip_path_bytes / tohip_path_refine (refine a planned walk: any-angle shortcuts and even waypoint spacing): new symbols
  * only.
  * (still 15) + tohip_roadmap_knn / tohip_roadmap_routes_bytes / tohip_roadmap_relax / tohip_roadmap_pred / tohip_tour_plan_via (a
  * free-space roadmap: routes where no straight leg is open): new symbols only.
@@ -844,6 +846,40 @@ int tohip_tour_plan_via(const float *nodes, int64_t n, const int32_t *edge_idx, 
 size_t tohip_path_bytes(int64_t n_nodes, int64_t max_rows);
 int tohip_path_refine(const float *nodes, const float *quats, const uint8_t *keep, int64_t n_nodes, int64_t window,
                       const uint8_t *open_band, float spacing, int64_t max_rows, void *buf, size_t bytes, void *stream);
+
+/* ---- propose candidate views (propose_kernels.hip) --------------------------------------------------------------------
+ * A pre-filter for tohip_views_*: where can a level camera stand, and which way should it look from there?  A heuristic by design: the
+ * gate is on RANGE, not on camera depth, and nothing is occluded.
+ * tohip_view_histogram: positions (n_positions, 3) f32 and open (n_positions) uint8 on the device, 1 <= n_positions <=
+ * TOHIP_VIEW_MAX_POSITIONS; weights (n_points) int32 on the device in the CALLER's row order, each in [0, 32768] (not checked: a value
+ * outside gives unspecified sums), or NULL: every point weighs 1; sectors = S in {8, 16, 32, 64, 128}; table_host: 2 (S/4 - 1) floats on
+ * the HOST, c_k = (float)cos(2 pi k / S) for k = 1 .. S/4 - 1, then s_k = (float)sin(2 pi k / S) likewise, all finite (read before the
+ * call returns; S = 8 has one c and one s); 1e-3 <= min_dist < max_dist and tan_v >= 0 (the tangent of half the vertical field of
+ * view), all finite.
+ * The pair test of position t and point x, f32 without contraction: d = fl(x - t); hh = fl(fl(dx dx) + fl(dy dy)), zz = fl(dz dz),
+ * r2 = fl(hh + zz); range gate fl(min min) <= r2 <= fl(max max); elevation gate zz <= fl(fl(tan_v tan_v) hh); quadrant q and (a, b):
+ * q = 0: dx > 0, dy >= 0 -> (dx, dy); q = 1: dx <= 0, dy > 0 -> (dy, -dx); q = 2: dx < 0, dy <= 0 -> (-dx, -dy); q = 3: dx >= 0, dy < 0
+ * -> (-dy, dx); sector = q S/4 + #{k : fl(b c_k) >= fl(a s_k)} (a point on a boundary belongs to the upper sector).
+ * hist (n_positions, S) int64, overwritten: hist[c][j] = the sum of the weights of the points that pass both gates from position c and
+ * fall into sector j, the bearings [2 pi j / S, 2 pi (j + 1) / S) about +z.  Rows of the cloud with a coordinate that is not finite
+ * never count; a position with such a coordinate or open = 0 gets a row of zeros.  prune != 0 (the product path): a 256-point tile
+ * whose bounding sphere lies wholly outside the shell [min_dist, max_dist] of a position is not tested against it; the exact gates
+ * decide every point of a kept tile, so prune changes no bit (0: every tile, for timing).  Integer sums: the same bits in every run,
+ * for a sorted and an unsorted packed cloud alike.  One memset and one launch.
+ * tohip_view_headings: hist (n_positions, S) int64; 0 <= half_window = hw, 2 hw + 1 <= S; 1 <= n_per <= TOHIP_VIEW_MAX_PER_POSITION;
+ * 0 <= sep <= S; min_score >= 0.  score[c][h] = sum over j = -hw .. hw of hist[c][(h + j) mod S].  n_per rounds: h* = the argmax of
+ * score over the unsuppressed h with score >= max(min_score, 1), ties to the lowest h; none: the remaining slots are heading -1,
+ * score 0; otherwise slot r = (h*, score[h*]) and every h whose circular distance to h* is <= sep is suppressed.
+ * heading (n_positions, n_per) int32, score (n_positions, n_per) int64.  One launch.
+ * Both: every argument check returns before anything is enqueued. */
+#define TOHIP_VIEW_MAX_POSITIONS 65536
+#define TOHIP_VIEW_MAX_SECTORS 128
+#define TOHIP_VIEW_MAX_PER_POSITION 8
+int tohip_view_histogram(const void *packed, int64_t n_points, const float *positions, const uint8_t *open, int64_t n_positions,
+                         const int32_t *weights, int32_t sectors, const float *table_host, float min_dist, float max_dist, float tan_v,
+                         int32_t prune, int64_t *hist, void *stream);
+int tohip_view_headings(const int64_t *hist, int64_t n_positions, int32_t sectors, int32_t half_window, int32_t n_per, int32_t sep,
+                        int64_t min_score, int32_t *heading, int64_t *score, void *stream);
 
 /* ---- input formats (pointcloud_utils.py, launch/voxels_filtering.launch) --------------------------------
  * PointCloud2 payload -> (N,3) f32 with non-finite rows removed, in message order

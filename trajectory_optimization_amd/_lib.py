@@ -212,6 +212,8 @@ SIGNATURES = {
     "tohip_tour_plan_via": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, ctypes.c_int, c_i64, c_vp, c_sz, c_vp, c_vp]),
     "tohip_path_bytes": (c_sz, [c_i64, c_i64]),
     "tohip_path_refine": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_f, c_i64, c_vp, c_sz, c_vp]),
+    "tohip_view_histogram": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i32, ctypes.POINTER(c_f), c_f, c_f, c_f, c_i32, c_vp, c_vp]),
+    "tohip_view_headings": (ctypes.c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp]),
     "tohip_gather_waypoints": (ctypes.c_int, [c_vp, c_vp, c_i64, ctypes.c_int, c_vp, c_vp, c_vp]),
     "tohip_rows_strided": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
     "tohip_adam_step": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_f, c_f, c_f, c_i32, c_vp, c_vp]),

@@ -14,6 +14,7 @@
 #include "tour_kernels.hip"
 #include "roadmap_kernels.hip"
 #include "path_kernels.hip"
+#include "propose_kernels.hip"
 #include "covmap_kernels.hip"
 #include "loss_kernels.hip"
 #include "ingest_kernels.hip"

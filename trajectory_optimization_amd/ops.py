@@ -1242,6 +1242,116 @@ def path_refine(P, quats, keep, open_band, window=None, spacing=None, max_rows=N
     return buf
 
 
+VIEW_MAX_POSITIONS = 65536      # TOHIP_VIEW_MAX_POSITIONS
+VIEW_SECTORS = (8, 16, 32, 64, 128)
+VIEW_MAX_PER_POSITION = 8       # TOHIP_VIEW_MAX_PER_POSITION
+VIEW_MAX_WEIGHT = 32768         # a point's largest weight: 65 536 points of a block x 32 768 < 2^32
+VIEW_MIN_DIST = float(np.float32(1e-3))
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def check_propose(n_points, positions, open=None, weights=None, sectors=32, min_dist=1.0, max_dist=5.0, tan_v=1.0, hw=0, n_per=2, sep=None,
+                  min_score=0):
+    """The arguments of a view proposal over a cloud of n_points: positions (M,3) a floating tensor, 1 <= M <= VIEW_MAX_POSITIONS (a
+    coordinate that is not finite is allowed: that position counts nothing); open None or (M,) bool / uint8; weights None or (n_points,)
+    int32, each in [0, VIEW_MAX_WEIGHT]; sectors one of VIEW_SECTORS; 1e-3 <= min_dist < max_dist and tan_v >= 0, finite as float32;
+    hw an integer >= 0 with 2 hw + 1 <= sectors; n_per an integer in 1..VIEW_MAX_PER_POSITION; sep None (2 hw) or an integer in
+    0..sectors; min_score an integer >= 0 -> (M, sectors, min_dist, max_dist, tan_v, hw, n_per, sep, min_score); ValueError otherwise.
+    Nothing is launched (the weights' range is read where they live)."""
+    if not torch.is_tensor(positions) or not positions.is_floating_point() or positions.dim() != 2 or positions.shape[1] != 3:
+        raise ValueError(f"positions must be a floating-point tensor of shape (M,3), got "
+                         f"{tuple(positions.shape) if torch.is_tensor(positions) else type(positions).__name__}")
+    M = positions.shape[0]
+    if M < 1 or M > VIEW_MAX_POSITIONS:
+        raise ValueError(f"positions must hold 1 <= M <= {VIEW_MAX_POSITIONS} rows, got M = {M}")
+    if open is not None and (not torch.is_tensor(open) or open.dtype not in (torch.bool, torch.uint8) or tuple(open.shape) != (M,)):
+        raise ValueError(f"open must be None or a bool / uint8 tensor of shape ({M},), got "
+                         f"{(tuple(open.shape), open.dtype) if torch.is_tensor(open) else type(open).__name__}")
+    if weights is not None:
+        if not torch.is_tensor(weights) or weights.dtype != torch.int32 or tuple(weights.shape) != (n_points,):
+            raise ValueError(f"weights must be None or an int32 tensor of shape ({n_points},) (one entry per point), got "
+                             f"{(tuple(weights.shape), weights.dtype) if torch.is_tensor(weights) else type(weights).__name__}")
+        if n_points and (int(weights.min()) < 0 or int(weights.max()) > VIEW_MAX_WEIGHT):
+            raise ValueError(f"weights must lie in [0, {VIEW_MAX_WEIGHT}], got {int(weights.min())}..{int(weights.max())}")
+    if not _is_int(sectors) or sectors not in VIEW_SECTORS:
+        raise ValueError(f"sectors must be one of {VIEW_SECTORS}, got {sectors!r}")
+    vals = []
+    for name, v in (("min_dist", min_dist), ("max_dist", max_dist), ("tan_v", tan_v)):
+        try:
+            with np.errstate(over="ignore"):
+                f = float(np.float32(float(v)))   # what the library is handed
+        except (TypeError, ValueError):
+            f = float("nan")
+        if not np.isfinite(f):
+            raise ValueError(f"{name} must be a finite number (as a float32), got {v!r}")
+        vals.append(f)
+    mn, mx, tv = vals
+    if not (mn >= VIEW_MIN_DIST and mn < mx):
+        raise ValueError(f"min_dist and max_dist must satisfy 1e-3 <= min_dist < max_dist, got {min_dist!r} and {max_dist!r}")
+    if not tv >= 0.0:
+        raise ValueError(f"tan_v must be >= 0, got {tan_v!r}")
+    if not _is_int(hw) or hw < 0 or 2 * hw + 1 > sectors:
+        raise ValueError(f"hw must be an integer >= 0 with 2 hw + 1 <= sectors = {sectors}, got {hw!r}")
+    if not _is_int(n_per) or not 1 <= n_per <= VIEW_MAX_PER_POSITION:
+        raise ValueError(f"n_per must be an integer in 1..{VIEW_MAX_PER_POSITION}, got {n_per!r}")
+    if sep is None:
+        sep = 2 * hw
+    elif not _is_int(sep) or not 0 <= sep <= sectors:
+        raise ValueError(f"sep must be None or an integer in 0..{sectors}, got {sep!r}")
+    if not _is_int(min_score) or min_score < 0 or min_score >= 1 << 63:
+        raise ValueError(f"min_score must be an integer >= 0, got {min_score!r}")
+    return M, int(sectors), mn, mx, tv, int(hw), int(n_per), int(sep), int(min_score)
+
+
+def view_histogram(cloud, positions, open=None, weights=None, sectors=32, min_dist=1.0, max_dist=5.0, tan_v=1.0, prune=True):
+    """tohip_view_histogram over a PackedCloud (sorted or not): positions (M,3) f32 contiguous, open (M,) bool / uint8 or None (every
+    position open) and weights (N,) int32 in the CALLER's row order or None (every point weighs 1), all on the cloud's device -> hist
+    (M, sectors) int64: per position and bearing sector the summed weights of the points inside the range shell and the vertical
+    field of view (propose_kernels.hip).  prune=False tests every tile against every position (the same bits; for timing).  One
+    memset and one launch."""
+    M, S, mn, mx, tv, _, _, _, _ = check_propose(cloud.n, positions, open, weights, sectors, min_dist, max_dist, tan_v)
+    _require_cuda(positions, "positions")
+    dev = cloud.device
+    if positions.dtype != torch.float32 or not positions.is_contiguous() or positions.device != dev:
+        raise ValueError("positions must be a contiguous float32 tensor on the cloud's device")
+    if open is None:
+        open = torch.ones(M, dtype=torch.uint8, device=dev)
+    open = open.view(torch.uint8) if open.dtype == torch.bool else open
+    if not (open.is_contiguous() and open.device == dev):
+        raise ValueError("open must be contiguous on the cloud's device")
+    if weights is not None and not (weights.is_contiguous() and weights.device == dev):
+        raise ValueError("weights must be contiguous on the cloud's device")
+    from .synth import propose_tables   # (numpy only)
+    table = np.ascontiguousarray(propose_tables(S)[0].reshape(-1))
+    table_c = (ctypes.c_float * max(1, table.size))(*table.tolist())
+    hist = torch.empty((M, S), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().tohip_view_histogram(ptr(cloud.blob), cloud.n, ptr(positions), ptr(open), M, ptr(weights), S, table_c, mn, mx, tv,
+                                              int(bool(prune)), ptr(hist), stream_ptr()), "tohip_view_histogram")
+    return hist
+
+
+def view_headings(hist, hw=0, n_per=2, sep=None, min_score=0):
+    """tohip_view_headings over hist (M,S) int64 contiguous on the device -> (heading (M,n_per) int32, score (M,n_per) int64): per
+    position the n_per best headings by the circular window sum over |j| <= hw, ties to the lowest heading, each suppressing the
+    headings within sep (default 2 hw: disjoint windows) of it; -1 / 0 where fewer reach max(min_score, 1).  One launch."""
+    if not torch.is_tensor(hist) or hist.dtype != torch.int64 or hist.dim() != 2 or not hist.is_contiguous():
+        raise ValueError(f"hist must be a contiguous (M,S) int64 tensor, got "
+                         f"{(tuple(hist.shape), hist.dtype) if torch.is_tensor(hist) else type(hist).__name__}")
+    M, S = hist.shape
+    _, S, _, _, _, hw, n_per, sep, min_score = check_propose(0, torch.empty((M, 3)), sectors=S, hw=hw, n_per=n_per, sep=sep, min_score=min_score)
+    _require_cuda(hist, "hist")
+    heading = torch.empty((M, n_per), dtype=torch.int32, device=hist.device)
+    score = torch.empty((M, n_per), dtype=torch.int64, device=hist.device)
+    with torch.cuda.device(hist.device):
+        check(_lib.lib().tohip_view_headings(ptr(hist), M, S, hw, n_per, sep, min_score, ptr(heading), ptr(score), stream_ptr()),
+              "tohip_view_headings")
+    return heading, score
+
+
 def clearance_terms(n_wps, n_traj, mode, device):
     """The float64 buffer the clearance query of `mode` fills for n_traj trajectories of n_wps waypoints: the per-waypoint terms lead
     it in either mode (what the step tails, the regularisers' kernel and the team calls read)."""

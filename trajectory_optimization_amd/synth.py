@@ -503,3 +503,93 @@ def path_refine_ref(P, keep, open_band, window, spacing, quats=None, max_rows=PA
         qrows[r] = _unit_quat(quats[L - 1])
     out.update(poses=poses, row_node=row_node, quats=qrows)
     return out
+
+
+# ---- tools.propose_views restated in numpy: what propose_kernels.hip must give, element for element ------------------
+VIEW_MAX_POSITIONS = 65536
+VIEW_SECTORS = (8, 16, 32, 64, 128)
+VIEW_MAX_PER_POSITION = 8
+VIEW_MAX_WEIGHT = 32768
+
+
+def propose_tables(S):
+    """The two host-made tables of a proposal with S sectors -> (bounds (2, S/4 - 1) f32: row 0 c_k = (float)cos(2 pi k / S), row 1
+    s_k = (float)sin(2 pi k / S) for k = 1 .. S/4 - 1, computed in f64; quats (S, 4) f32 wxyz: heading h looks along the centre of
+    sector h, r_z((h + 1/2) 2 pi / S) (x) Q_OPTICAL, candidate_grid's convention)."""
+    if S not in VIEW_SECTORS:
+        raise ValueError(f"sectors must be one of {VIEW_SECTORS}, got {S!r}")
+    ang = 2.0 * np.pi * np.arange(1, S // 4, dtype=np.float64) / S
+    bounds = np.stack([np.cos(ang), np.sin(ang)]).astype(np.float32)
+    mid = (np.arange(S, dtype=np.float64) + 0.5) * (2.0 * np.pi / S)
+    rz = np.stack([np.cos(mid / 2), np.zeros(S), np.zeros(S), np.sin(mid / 2)], axis=1)
+    return bounds, quat_mul(rz, Q_OPTICAL[None, :]).astype(np.float32)
+
+
+def propose_sectors(dx, dy, S, bounds):
+    """The sector of each (dx, dy) f32 pair: q S/4 + the COUNT of boundaries k with fl(b c_k) >= fl(a s_k); -1 where dx = dy = 0 (or
+    a NaN) gives no quadrant.  f32, operation for operation."""
+    dx, dy = np.asarray(dx, dtype=np.float32), np.asarray(dy, dtype=np.float32)
+    c, s = np.asarray(bounds[0], dtype=np.float32), np.asarray(bounds[1], dtype=np.float32)
+    quad = [(dx > 0) & (dy >= 0), (dx <= 0) & (dy > 0), (dx < 0) & (dy <= 0), (dx >= 0) & (dy < 0)]
+    a = np.select(quad, [dx, dy, -dx, -dy], default=np.float32(0)).astype(np.float32)
+    b = np.select(quad, [dy, -dx, -dy, dx], default=np.float32(0)).astype(np.float32)
+    q = np.select(quad, [0, 1, 2, 3], default=-1)
+    with np.errstate(all="ignore"):
+        count = ((b[:, None] * c[None, :]) >= (a[:, None] * s[None, :])).sum(axis=1)
+    return np.where(q >= 0, q * (S // 4) + count, -1).astype(np.int64)
+
+
+def propose_hist_ref(points, positions, open, weights, S, min_dist, max_dist, tan_v):
+    """hist (M, S) int64 of the pair test (propose_kernels.hip's header), in numpy f32 operation for operation: points (N,3),
+    positions (M,3), open (M,) (zero = closed), weights (N,) integers in the points' row order or None (every point weighs 1)."""
+    f32 = np.float32
+    P, T = np.asarray(points, dtype=f32).reshape(-1, 3), np.asarray(positions, dtype=f32).reshape(-1, 3)
+    op = np.asarray(open).reshape(-1) != 0
+    w = np.ones(len(P), dtype=np.int64) if weights is None else np.asarray(weights).astype(np.int64).reshape(-1)
+    bounds, _ = propose_tables(S)
+    fin = np.isfinite(P).all(axis=1)
+    X, Y, Z, w = P[fin, 0], P[fin, 1], P[fin, 2], w[fin]
+    mn, mx, tv = f32(min_dist), f32(max_dist), f32(tan_v)
+    hist = np.zeros((len(T), S), dtype=np.int64)
+    with np.errstate(all="ignore"):
+        min2, max2, tv2 = mn * mn, mx * mx, tv * tv
+        for c in range(len(T)):
+            t = T[c]
+            if not op[c] or not np.isfinite(t).all():
+                continue
+            dx, dy, dz = X - t[0], Y - t[1], Z - t[2]
+            hh, zz = dx * dx + dy * dy, dz * dz
+            r2 = hh + zz
+            g = (r2 >= min2) & (r2 <= max2) & (zz <= tv2 * hh)
+            sec = propose_sectors(dx[g], dy[g], S, bounds)
+            ok = sec >= 0
+            # (float64 weights in bincount: the sums are integers below 2^53, so they are exact)
+            hist[c] = np.bincount(sec[ok], weights=w[g][ok].astype(np.float64), minlength=S).astype(np.int64)
+    return hist
+
+
+def propose_headings_ref(hist, hw, n_per, sep=None, min_score=0):
+    """(heading (M, n_per) int32, score (M, n_per) int64) of hist (M, S) int64: circular window sums over |j| <= hw, then n_per
+    rounds of the argmax over the unsuppressed headings with score >= max(min_score, 1), ties to the lowest h, suppressing every h
+    within sep (circular; default 2 hw) of the winner; -1 / 0 in the slots no round fills."""
+    hist = np.asarray(hist, dtype=np.int64)
+    M, S = hist.shape
+    sep = 2 * hw if sep is None else sep
+    win = np.zeros_like(hist)
+    for j in range(-hw, hw + 1):
+        win += np.roll(hist, -j, axis=1)   # win[h] += hist[(h + j) mod S]
+    heading = np.full((M, n_per), -1, dtype=np.int32)
+    score = np.zeros((M, n_per), dtype=np.int64)
+    thr = max(int(min_score), 1)
+    hs = np.arange(S)
+    for c in range(M):
+        free = win[c] >= thr
+        for r in range(n_per):
+            if not free.any():
+                break
+            best = int(win[c][free].max())
+            h = int(np.flatnonzero(free & (win[c] == best))[0])
+            heading[c, r], score[c, r] = h, best
+            d = np.abs(hs - h)
+            free &= np.minimum(d, S - d) > sep
+    return heading, score

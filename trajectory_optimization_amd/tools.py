@@ -4,6 +4,7 @@ per-camera hard-visibility pipeline of /root/reference/src/pc_processor.py:158-1
 
 All index sets are bit-exact with the reference's CPU path (tests/test_hip_hard.py).  No CPU fallback.
 """
+import math
 import types
 
 import torch
@@ -784,3 +785,115 @@ def refine_path(points_or_cloud_or_model, path, quats=None, clearance_radius=Non
     return RefinedPath(poses=poses, quats=out_q, row_node=row_node, corners=corners, length=int(hdr[2]) * ops.TOUR_UNIT,
                        length_fixed=int(hdr[2]), input_length=int(hdr[3]) * ops.TOUR_UNIT, input_length_fixed=int(hdr[3]),
                        leg_blocked=leg_blocked, n_open=int(hdr[5]), open_band=band)
+
+
+class ViewProposals:
+    """What propose_views returns, ranked by what is left to see.  poses (V,3) f32 and quats (V,4) f32 wxyz on the device — they feed
+    select_views(..., prop.poses, prop.quats, k) as they are; score (V,) int64: the summed weights inside the proposal's window
+    of sectors; position_index (V,) int64 and heading (V,) int32: the position row and the sector the view looks along; all in rank
+    order: score descending, then position, then heading.  hist (M,S) int64, open (M,) bool and weights (N,) int32 or None (no
+    prior: every point weighs 1) are what the ranking was computed from, on the device; sectors, hw, tan_v, min_dist, max_dist: the
+    settings behind them."""
+    __slots__ = ("poses", "quats", "score", "position_index", "heading", "hist", "open", "weights", "sectors", "hw", "tan_v", "min_dist",
+                 "max_dist")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    @property
+    def n_views(self):
+        return int(self.score.shape[0])
+
+
+def _propose_camera(m, prior_log_odds, given):
+    """propose_views' camera and prior: a ModelTraj brings its own (the keywords must stay None), points need K, img_width, img_height
+    -> (prior or None, min_dist, max_dist, K as nine host floats, img_width, img_height)."""
+    names = ("min_dist", "max_dist", "K", "img_width", "img_height")
+    if hasattr(m, "_cloud") and hasattr(m, "_shard"):
+        extra = [k for k in names if given[k] is not None]
+        if extra:
+            raise ValueError(f"propose_views: {extra} belong to the call with points; a ModelTraj brings its own camera and distances")
+        prior = m.prior_log_odds if prior_log_odds is None else prior_log_odds
+        return prior, m.pc_clip_limits[0], m.pc_clip_limits[1], [float(v) for v in m._cam.c.K], m.img_width, m.img_height
+    missing = [k for k in ("K", "img_width", "img_height") if given[k] is None]
+    if missing:
+        raise ValueError(f"propose_views: with points or a PackedCloud the camera is needed: {missing} missing")
+    K = torch.as_tensor(given["K"], dtype=torch.float32).detach().cpu().reshape(-1).tolist()
+    if len(K) != 9:
+        raise ValueError(f"propose_views: K must hold 3 x 3 intrinsics, got {len(K)} values")
+    return (prior_log_odds, 1.0 if given["min_dist"] is None else given["min_dist"], 5.0 if given["max_dist"] is None else given["max_dist"],
+            K, given["img_width"], given["img_height"])
+
+
+def propose_views(points_or_cloud_or_model, positions, n_per_position=2, sectors=32, prior_log_odds=None, clearance_radius=None,
+                  max_views=None, min_score=0, min_dist=None, max_dist=None, K=None, img_width=None, img_height=None):
+    """Candidate views for select_views, ranked by what is left to see: where can a level camera stand among
+    `positions` (M,3) — a lattice from synth.roadmap_lattice, say — and which way should it look from there?
+
+    A position is open when its coordinates are finite and, with clearance_radius, trajectory_clearance finds no cloud point nearer
+    than it.  From every open position one pass over the cloud sorts the points whose RANGE lies in [min_dist, max_dist] and whose
+    elevation lies inside the vertical field of view, tan_v = (img_height / 2) / fy, into `sectors` bearing sectors about +z, each
+    point weighing rint(32768 (1 - sigmoid(prior))) — what the prior has not covered yet; without a prior every point weighs 1.
+    prior_log_odds: (N,) log-odds or an ops.CoverageMap (looked up over the cloud).  A heading's score is the sum over the sectors the
+    horizontal field of view spans, hw = floor(atan((img_width / 2) / fx) / (2 pi / sectors)) on either side; each position
+    proposes its n_per_position <= 8 best headings with disjoint windows and a score >= max(min_score, 1).  The view at heading h
+    looks along the centre of sector h: r_z((h + 1/2) 2 pi / sectors) (x) Q_OPTICAL, synth.candidate_grid's convention.
+
+    This is a pre-filter and a heuristic by design: the gate is on range, not on camera depth, nothing is occluded, there is no
+    rig and no soft mask.  select_views does the exact scoring on the few hundred views that come out.  Everything is integer
+    after the f32 gates, so every run gives the same ranking: by (score descending, position, heading), cut to max_views.
+
+    First argument: a ModelTraj (its cloud, camera, distances and prior; prior_log_odds overrides the prior), (N,3) points or an
+    ops.PackedCloud (sorted or not) with K, img_width, img_height[, min_dist = 1, max_dist = 5].  -> ViewProposals."""
+    m = points_or_cloud_or_model
+    cloud, pts = _clearance_cloud(m, "propose_views")
+    given = dict(min_dist=min_dist, max_dist=max_dist, K=K, img_width=img_width, img_height=img_height)
+    prior, mn, mx, Kh, iw, ih = _propose_camera(m, prior_log_odds, given)
+    try:
+        iw, ih, fx, fy = float(iw), float(ih), float(Kh[0]), float(Kh[4])
+    except (TypeError, ValueError):
+        iw = ih = fx = fy = float("nan")
+    if not all(math.isfinite(v) and v > 0.0 for v in (iw, ih, fx, fy)):
+        raise ValueError(f"propose_views: img_width, img_height and the focal lengths K[0][0], K[1][1] must be finite numbers > 0, got "
+                         f"{img_width!r}, {img_height!r}, {Kh[0]!r}, {Kh[4]!r}")
+    if sectors not in ops.VIEW_SECTORS:
+        raise ValueError(f"sectors must be one of {ops.VIEW_SECTORS}, got {sectors!r}")
+    hw = int(math.floor(math.atan((iw / 2.0) / fx) / (2.0 * math.pi / sectors)))
+    tan_v = (ih / 2.0) / fy
+    n = cloud.n if cloud is not None else pts.shape[0]
+    M, S, mn, mx, tan_v, hw, n_per, sep, min_score = ops.check_propose(n, positions, None, None, sectors, mn, mx, tan_v, hw, n_per_position,
+                                                                       None, min_score)
+    if max_views is not None and (isinstance(max_views, bool) or not isinstance(max_views, int) or max_views < 1):
+        raise ValueError(f"max_views must be None or an integer >= 1, got {max_views!r}")
+    r = ops.check_tour_radius(clearance_radius) if clearance_radius is not None else None
+    if prior is not None and not isinstance(prior, ops.CoverageMap):
+        ops.check_prior(prior, n)
+    cloud = _device_cloud(cloud, pts, "propose_views")
+    dev = cloud.device
+    P = positions.detach().to(device=dev, dtype=torch.float32).contiguous()
+    weights = None
+    if prior is not None:
+        prior = ops.check_prior(ops.resolve_prior(prior, cloud), n, dev)
+        weights = torch.round(32768.0 * (1.0 - torch.sigmoid(prior))).to(torch.int32)   # f32; round = rint (half to even)
+    is_open = torch.isfinite(P).all(dim=1)
+    if r is not None:
+        d, _ = trajectory_clearance(cloud, P, r)
+        is_open &= d >= r
+    hist = ops.view_histogram(cloud, P, is_open, weights, S, mn, mx, tan_v)
+    heading, score = ops.view_headings(hist, hw, n_per, sep, min_score)
+    # the ranking: one unique int64 key per proposal, so no tie is left to the sort — the rank of the score among the distinct
+    # scores (descending), then the position, then the heading
+    slot = torch.nonzero(heading.reshape(-1) >= 0).reshape(-1)
+    h, s = heading.reshape(-1)[slot].to(torch.int64), score.reshape(-1)[slot]
+    p = slot // n_per
+    distinct, rank = torch.unique(s, sorted=True, return_inverse=True)
+    key = ((distinct.numel() - 1 - rank) * ops.VIEW_MAX_POSITIONS + p) * 128 + h
+    order = torch.sort(key).indices
+    if max_views is not None:
+        order = order[:max_views]
+    h, s, p = h[order], s[order], p[order]
+    from .synth import propose_tables   # (numpy only)
+    qtable = torch.from_numpy(propose_tables(S)[1]).to(dev)
+    return ViewProposals(poses=P[p], quats=qtable[h], score=s, position_index=p, heading=h.to(torch.int32), hist=hist, open=is_open,
+                         weights=weights, sectors=S, hw=hw, tan_v=tan_v, min_dist=mn, max_dist=mx)
