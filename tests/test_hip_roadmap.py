@@ -241,6 +241,28 @@ def test_doorway_tour_buffer_equals_the_restatement(dev, doorway):
     assert np.array_equal(flag.cpu().numpy(), ref["via_flag"].astype(np.uint8))
 
 
+def test_a_tie_with_the_straight_leg_is_not_flagged(dev):
+    """tohip_tour_plan_via at n = 3: a route one unit shorter than its straight leg is taken and flagged, a route as long as its
+    straight leg is not (the kernel's via < w is strict); the buffer and the flags against the restatement."""
+    from test_roadmap_cpu import via_tie_case
+    from trajectory_optimization_amd import ops
+    P, via_D, w = via_tie_case()
+    n = 3
+    nodes = torch.from_numpy(P).to(dev)
+    for closed in (False, True):
+        ref = synth.tour_plan(P, None, closed, via_D=via_D)
+        # the case is not vacuous, by the restatement's own account: one flagged leg and one tie
+        assert ref["via_flag"].sum() == 2 and ref["via_flag"][0, 2] and via_D[0, 1] == w[0, 1] and not ref["via_flag"][0, 1]
+        buf, flag = ops.tour_plan_via(nodes, None, torch.from_numpy(via_D).to(dev), closed)
+        h, lay = buf.cpu(), ops.tour_layout(n)
+        hdr = h[:64].view(torch.int64).tolist()
+        assert hdr[:6] == [ref["m"], ref["moves"], int(ref["converged"]), ref["length_fixed"], ref["nn_length_fixed"], 0]
+        assert h[lay["order"]:lay["order"] + 4 * n].view(torch.int32).tolist() == ref["order"].tolist()
+        assert np.array_equal(h[lay["D"]:lay["D"] + 8 * n * n].view(torch.int64).numpy().reshape(n, n), ref["D"])
+        assert np.array_equal(h[lay["nxt"]:lay["nxt"] + 4 * n * n].view(torch.int32).numpy().reshape(n, n), ref["nxt"])
+        assert np.array_equal(flag.cpu().numpy(), ref["via_flag"].astype(np.uint8))
+
+
 def test_two_views_at_one_position_behind_the_wall(dev, doorway):
     """Coincident tour nodes are joined by a zero-length edge and tie each other's predecessors in a circle; the walk still arrives."""
     from trajectory_optimization_amd import tools

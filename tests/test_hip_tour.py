@@ -164,16 +164,21 @@ def read_tour(buf, n):
                 nxt=h[lay["nxt"]:lay["nxt"] + 4 * n * n].view(torch.int32).numpy().reshape(n, n))
 
 
-@pytest.mark.parametrize("max_moves", [0, 1, None])
-@pytest.mark.parametrize("closed", [False, True])
-@pytest.mark.parametrize("n", [2, 3, 12, 64, 256])
-def test_tour_equals_the_restatement(dev, n, closed, max_moves):
+def check_tour_entry(dev, n, closed, max_moves, via):
+    """One entry's buffer against the restatement.  via: through ops.tour_plan_via with routes that beat no leg — all 2^62, in a
+    table wider than n — so the legs, and with them the whole buffer, are those of ops.tour_plan, and no flag is set."""
     from trajectory_optimization_amd import ops
     P, _, edge_idx = tour_case(n)
     want = tour_ref(n, closed, max_moves)
     nodes, idx = torch.from_numpy(P).to(dev), torch.from_numpy(edge_idx).to(dev)
+    via_D = torch.full((n, n + 3), synth.TOUR_INF, dtype=torch.int64, device=dev) if via else None
     for run in range(2):
-        got = read_tour(ops.tour_plan(nodes, idx, closed, max_moves), n)
+        if via:
+            buf, flag = ops.tour_plan_via(nodes, idx, via_D, closed, max_moves)
+            assert flag.dtype == torch.uint8 and tuple(flag.shape) == (n, n) and not bool(flag.any())
+        else:
+            buf = ops.tour_plan(nodes, idx, closed, max_moves)
+        got = read_tour(buf, n)
         for k in ("m", "moves", "converged", "length_fixed", "nn_length_fixed"):
             assert got[k] == want[k], (k, run)
         for k in ("order", "unreachable", "D", "nxt"):
@@ -184,6 +189,22 @@ def test_tour_equals_the_restatement(dev, n, closed, max_moves):
     if n == 256 and max_moves is None:   # the case is not a trivial one
         assert want["moves"] > 1 and want["converged"] and want["unreachable"].sum() >= 1 and want["m"] > 200
         assert (want["D"][want["D"] < synth.TOUR_INF] > np.where(want["w"] >= 0, want["w"], 0)[want["D"] < synth.TOUR_INF]).any()
+
+
+@pytest.mark.parametrize("max_moves", [0, 1, None])
+@pytest.mark.parametrize("closed", [False, True])
+@pytest.mark.parametrize("n", [2, 3, 12, 64, 256])
+def test_tour_equals_the_restatement(dev, n, closed, max_moves):
+    check_tour_entry(dev, n, closed, max_moves, via=False)
+
+
+@pytest.mark.parametrize("max_moves", [0, 1, None])
+@pytest.mark.parametrize("closed", [False, True])
+@pytest.mark.parametrize("n", [2, 3, 12, 64, 256])
+def test_tour_via_entry_equals_the_restatement(dev, n, closed, max_moves):
+    """Both entries launch one init kernel: the second one's null-free arguments and its leading dimension, against the CPU
+    restatement (not against the other entry, which would compare the kernel with itself)."""
+    check_tour_entry(dev, n, closed, max_moves, via=True)
 
 
 def walled_scene():

@@ -95,6 +95,34 @@ def test_entries_refuse_bad_arguments_without_gpu():
     assert plan(bytes=tb - 1) == ENOSPC and plan(edge_idx=p, bytes=0) == ENOSPC
 
 
+def via_tie_case():
+    """Three nodes and a table of routes that beats exactly one straight leg, (0, 2) by one unit, and ties another, (0, 1): min(direct,
+    via) is strict, so only the first is flagged -> (P, via_D (3,5) int64: wider than n, w: the straight legs' lengths)."""
+    from trajectory_optimization_amd import synth
+    P = np.float32([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 2.0, 0.0]])
+    w = synth.tour_edge_lengths(P)
+    via_D = np.full((3, 5), synth.TOUR_INF, dtype=np.int64)
+    via_D[0, 1] = via_D[1, 0] = w[0, 1]
+    via_D[0, 2] = via_D[2, 0] = w[0, 2] - 1
+    return P, via_D, w
+
+
+def test_via_tie_case_flags_one_leg_and_ties_another():
+    from trajectory_optimization_amd import synth
+    P, via_D, w = via_tie_case()
+    assert w[0, 1] == 1 << 20 and w[0, 2] == 2 << 20 and w[1, 2] > 0
+    ref = synth.tour_plan(P, None, via_D=via_D)
+    want = np.zeros((3, 3), dtype=bool)
+    want[0, 2] = want[2, 0] = True
+    assert np.array_equal(ref["via_flag"], want)                      # one flagged leg, both directions
+    assert via_D[0, 1] == w[0, 1] == ref["D"][0, 1] and not ref["via_flag"][0, 1]   # the tie: not flagged
+    assert ref["D"][0, 2] == w[0, 2] - 1 and ref["D"][1, 2] == w[1, 2] and ref["m"] == 3
+    # with the straight legs (0, 1) and (0, 2) blocked the tie is no tie any more: both are flagged
+    blocked = np.zeros((3, 3), dtype=bool)
+    blocked[0, 1] = blocked[1, 0] = blocked[0, 2] = blocked[2, 0] = True
+    assert synth.tour_plan(P, blocked, via_D=via_D)["via_flag"].sum() == 4
+
+
 class _Shard:
     def __init__(self, kind="waypoints", world_size=1, collective=False):
         self.kind, self.world_size, self.collective = kind, world_size, collective

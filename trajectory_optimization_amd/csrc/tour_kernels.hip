@@ -6,7 +6,7 @@
 //
 //   k_tour_init    w_ij = llrint(sqrt((dx dx + dy dy) + dz dz) 2^20) in f64 without contraction (dx = (double)x_lo - (double)x_hi, lo < hi:
 //                  one value per pair); closed when w > 2^40.  D = w on open edges, 0 on the diagonal, INF = 2^62 elsewhere; nxt = j
-//                  on open edges, -1 elsewhere.
+//                  on open edges, -1 elsewhere.  With a roadmap's routes (tohip_tour_plan_via): w = min(w, via_D[i][j]), flagged.
 //   k_tour_fw      one launch per k, ascending, one thread per (i, j): D[i][k] + D[k][j] < D[i][j] strictly, both terms below INF ->
 //                  D[i][j] = the sum, nxt[i][j] = nxt[i][k].  D[k][k] = 0, so row k and column k do not change during iteration k
 //                  (D[i][k] + 0 < D[i][k] never holds): the threads of a sweep read only what none of them writes, and the parallel
@@ -62,7 +62,7 @@ __device__ __forceinline__ long long tour_len_fixed(double d2) {
     return L < 4398046511104.0 ? llrint(L) : (1ll << 42);
 }
 
-// the straight leg (i, j), i != j: its integer length when it is open, INF otherwise (the one definition both init kernels share)
+// the straight leg (i, j), i != j: its integer length when it is open, INF otherwise
 __device__ __forceinline__ long long tour_direct(const float* __restrict__ P, int n, const int* __restrict__ edge_idx, int i, int j) {
     const int lo = i < j ? i : j, hi = i < j ? j : i;
     const float xl = P[3 * lo], yl = P[3 * lo + 1], zl = P[3 * lo + 2], xh = P[3 * hi], yh = P[3 * hi + 1], zh = P[3 * hi + 2];
@@ -75,22 +75,12 @@ __device__ __forceinline__ long long tour_direct(const float* __restrict__ P, in
     return kTourInf;
 }
 
-// one thread per (i, j)
+// one thread per (i, j).  With a roadmap behind the legs (via_D, or null): w_ij = min(direct, via), via = via_D[i][j] (row i: the routes
+// from node i over the roadmap, leading dimension ld); via_flag (or null) = 1 where the roadmap's route is strictly shorter than the
+// straight leg (or that leg is closed).  Both branches are on kernel arguments: uniform over the grid
 __global__ void __launch_bounds__(256)
-k_tour_init(const float* __restrict__ P, int n, const int* __restrict__ edge_idx, long long* __restrict__ D, int* __restrict__ nxt) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= n * n) return;
-    const int i = c / n, j = c % n;
-    const long long w = i == j ? 0 : tour_direct(P, n, edge_idx, i, j);
-    D[c] = w;
-    nxt[c] = (i != j && w < kTourInf) ? j : -1;
-}
-
-// k_tour_init with a roadmap behind it: w_ij = min(direct, via), via = via_D[i][j] (row i: the routes from node i over the roadmap,
-// leading dimension ld); via_flag = 1 where the roadmap's route is strictly shorter than the straight leg (or that leg is closed)
-__global__ void __launch_bounds__(256)
-k_tour_init_via(const float* __restrict__ P, int n, const int* __restrict__ edge_idx, const long long* __restrict__ via_D, long long ld,
-                long long* __restrict__ D, int* __restrict__ nxt, unsigned char* __restrict__ via_flag) {
+k_tour_init(const float* __restrict__ P, int n, const int* __restrict__ edge_idx, const long long* __restrict__ via_D, long long ld,
+            long long* __restrict__ D, int* __restrict__ nxt, unsigned char* __restrict__ via_flag) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= n * n) return;
     const int i = c / n, j = c % n;
@@ -98,12 +88,14 @@ k_tour_init_via(const float* __restrict__ P, int n, const int* __restrict__ edge
     unsigned char f = 0;
     if (i != j) {
         w = tour_direct(P, n, edge_idx, i, j);
-        const long long via = via_D[(long long)i * ld + j];
-        if (via < w) { w = via; f = 1; }
+        if (via_D) {
+            const long long via = via_D[(long long)i * ld + j];
+            if (via < w) { w = via; f = 1; }
+        }
     }
     D[c] = w;
     nxt[c] = (i != j && w < kTourInf) ? j : -1;
-    via_flag[c] = f;
+    if (via_flag) via_flag[c] = f;
 }
 
 // iteration k of Floyd-Warshall, one thread per (i, j): reads row k and column k, which no thread of this sweep writes
@@ -265,8 +257,7 @@ int tour_run(const float* nodes, int64_t n, const int32_t* edge_idx, const long 
     int* nxt = (int*)(b + l.off_nxt);
     const int N = (int)n;
     const unsigned blocks = (unsigned)((N * N + 255) / 256);
-    if (via_D) k_tour_init_via<<<blocks, 256, 0, st>>>(nodes, N, edge_idx, via_D, (long long)via_ld, D, nxt, via_flag);
-    else k_tour_init<<<blocks, 256, 0, st>>>(nodes, N, edge_idx, D, nxt);
+    k_tour_init<<<blocks, 256, 0, st>>>(nodes, N, edge_idx, via_D, (long long)via_ld, D, nxt, via_flag);
     TO_HIP_CHECK_LAUNCH();
     for (int k = 0; k < N; ++k) {
         k_tour_fw<<<blocks, 256, 0, st>>>(N, k, D, nxt);

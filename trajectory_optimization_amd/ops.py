@@ -23,6 +23,46 @@ def _require_cuda(t, what):
         raise RuntimeError(f"{what} must live on a HIP device (got {t.device}); the visibility path has no CPU fallback")
 
 
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _float_or_nan(v, cast=float):
+    """float(cast(v)), or NaN where v cannot be one (cast=np.float32: rounded as the library is handed it)."""
+    try:
+        return float(cast(v))
+    except (TypeError, ValueError):
+        return float("nan")
+
+
+def _check_float_rows(t, name, wording, cols, rows=None, empty=True):
+    """t must be a floating tensor of shape (rows, cols) — any number of rows for None, none at all only with `empty` — otherwise
+    ValueError '<name> must be <wording>, got <its shape, or its type>'."""
+    if (not torch.is_tensor(t) or not t.is_floating_point() or t.dim() != 2 or t.shape[1] != cols or (rows is not None and t.shape[0] != rows)
+            or not (empty or t.shape[0])):
+        raise ValueError(f"{name} must be {wording}, got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+
+
+def _sections(header_bytes, sections):
+    """Byte offsets of a buffer's sections, each rounded up to 256 bytes, behind a header of header_bytes ("header": 0; none for 0)
+    -> {name: offset, ..., "total": bytes}.  sections: ((name, nbytes), ...)."""
+    out, o = ({"header": 0} if header_bytes else {}), header_bytes
+    for name, nbytes in sections:
+        out[name] = o
+        o += (nbytes + 255) // 256 * 256
+    out["total"] = o
+    return out
+
+
+def _model_cloud(m, what):
+    """m's packed cloud where m is a ModelTraj (ValueError for a sharded one); anything else is handed back as it is."""
+    if hasattr(m, "_cloud") and hasattr(m, "_shard"):
+        if m._shard.kind == "points" or m._shard.world_size > 1 or m._shard.collective:
+            raise ValueError(f"{what}: a sharded model (WaypointShard / PointShard) is not supported")
+        return m._cloud
+    return m
+
+
 class PackedCloud:
     """The cloud in the kernels' layout (x|y|z, padded); built once per CLOUD (it is constant over an optimisation run:
     /root/reference/src/model.py:80,174) and shared by every model over it — the reference builds a model per message pair over the
@@ -480,20 +520,14 @@ def check_covmap(origin, resolution, clamp_max=None, capacity=None):
         o = np.zeros(0, dtype=np.float32)
     if o.shape != (3,) or not np.isfinite(o).all():
         raise ValueError(f"origin must be 3 finite numbers, got {origin!r}")
-    try:
-        r = float(np.float32(resolution))
-    except (TypeError, ValueError):
-        r = float("nan")
+    r = _float_or_nan(resolution, np.float32)
     if not (np.isfinite(r) and r > 0.0):
         raise ValueError(f"resolution must be a finite number > 0, got {resolution!r}")
-    try:
-        c = float("inf") if clamp_max is None else float(np.float32(clamp_max))
-    except (TypeError, ValueError):
-        c = float("nan")
+    c = float("inf") if clamp_max is None else _float_or_nan(clamp_max, np.float32)
     if not c >= 0.0:
         raise ValueError(f"clamp_max must be a number >= 0 or None, got {clamp_max!r}")
     if capacity is not None:
-        if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not 1 <= capacity <= 1 << 32:
+        if not _is_int(capacity) or not 1 <= capacity <= 1 << 32:
             raise ValueError(f"capacity must be None or an integer in [1, 2^32], got {capacity!r}")
         capacity = max(COVMAP_MIN_CAPACITY, 1 << (int(capacity) - 1).bit_length())
     return o, r, c, capacity
@@ -502,11 +536,7 @@ def check_covmap(origin, resolution, clamp_max=None, capacity=None):
 def covmap_points(points_or_cloud, device, what="CoverageMap"):
     """The rows a coverage map keys: (N,3) points, a PackedCloud (its caller-order points) or a ModelTraj (its cloud's) -> (N,3) f32
     contiguous on `device`; ValueError for a sharded model, another shape or another device."""
-    m = points_or_cloud
-    if hasattr(m, "_cloud") and hasattr(m, "_shard"):   # a ModelTraj
-        if m._shard.kind == "points" or m._shard.world_size > 1 or m._shard.collective:
-            raise ValueError(f"{what}: a sharded model (WaypointShard / PointShard) is not supported")
-        m = m._cloud
+    m = _model_cloud(points_or_cloud, what)
     if isinstance(m, PackedCloud):
         m = m.points
     if not torch.is_tensor(m) or not m.is_floating_point() or m.dim() != 2 or m.shape[1] != 3:
@@ -710,30 +740,21 @@ def check_views(cand_poses, cand_quats, k, min_gain=0.0, chunk=None):
         raise ValueError(f"cand_poses holds {M} candidates, cand_quats {cand_quats.shape[0]}")
     if M > VIEWS_MAX_CANDIDATES:
         raise ValueError(f"at most {VIEWS_MAX_CANDIDATES} candidate views, got {M}")
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+    if not _is_int(k) or k < 1:
         raise ValueError(f"k must be an integer >= 1, got {k!r}")
-    try:
-        g = float(min_gain)
-    except (TypeError, ValueError):
-        g = float("nan")
+    g = _float_or_nan(min_gain)
     if not (np.isfinite(g) and g >= 0.0):
         raise ValueError(f"min_gain must be a finite number >= 0, got {min_gain!r}")
-    if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or not 1 <= chunk <= VIEWS_MAX_CHUNK):
+    if chunk is not None and (not _is_int(chunk) or not 1 <= chunk <= VIEWS_MAX_CHUNK):
         raise ValueError(f"chunk must be None or an integer in [1, {VIEWS_MAX_CHUNK}], got {chunk!r}")
     return M, min(int(k), M), g
 
 
 def views_layout(npad, n_candidates, nnz_capacity):
     """Byte offsets of a view set's sections (include/trajopt_hip.h, tohip_views_bytes): every section aligned to 256 bytes."""
-    up = lambda v: (v + 255) // 256 * 256
     M, nseg = n_candidates, (npad + 8191) // 8192
-    out, o = {"header": 0}, 256
-    for name, nbytes in (("offsets", 8 * (M + 1)), ("absent", 4 * M), ("gain", 8 * M), ("chosen", 4 * M),
-                         ("segments", 4 * VIEWS_MAX_CHUNK * nseg), ("idx", 4 * nnz_capacity), ("val", 4 * nnz_capacity)):
-        out[name] = o
-        o += up(nbytes)
-    out["total"] = o
-    return out
+    return _sections(256, (("offsets", 8 * (M + 1)), ("absent", 4 * M), ("gain", 8 * M), ("chosen", 4 * M),
+                           ("segments", 4 * VIEWS_MAX_CHUNK * nseg), ("idx", 4 * nnz_capacity), ("val", 4 * nnz_capacity)))
 
 
 class ViewSet:
@@ -946,10 +967,7 @@ TOUR_UNIT = 2.0 ** -20   # metres per unit of a tour's integer lengths
 
 def check_tour_radius(radius):
     """A clearance radius that is given: a finite number > 0 (ValueError otherwise)."""
-    try:
-        r = float(radius)
-    except (TypeError, ValueError):
-        r = float("nan")
+    r = _float_or_nan(radius)
     if not (np.isfinite(r) and r > 0.0):
         raise ValueError(f"clearance_radius must be a finite number > 0, got {radius!r}")
     return r
@@ -958,36 +976,27 @@ def check_tour_radius(radius):
 def check_tour(poses, quats=None, clearance_radius=None, closed=False, max_moves=None):
     """The arguments of a tour: poses (n,3) a floating tensor with 2 <= n <= TOUR_MAX_NODES, quats None or (n,4), clearance_radius
     None or a finite number > 0, max_moves None (4 n) or an integer >= 0 -> (n, radius or None, max_moves); ValueError otherwise."""
-    if not torch.is_tensor(poses) or not poses.is_floating_point() or poses.dim() != 2 or poses.shape[1] != 3:
-        raise ValueError(f"poses must be a floating-point tensor of shape (n,3), got "
-                         f"{tuple(poses.shape) if torch.is_tensor(poses) else type(poses).__name__}")
+    _check_float_rows(poses, "poses", "a floating-point tensor of shape (n,3)", 3)
     n = poses.shape[0]
     if n < 2:
         raise ValueError(f"poses must hold n >= 2 nodes (the start and at least one view), got {n}")
     if n > TOUR_MAX_NODES:
         raise ValueError(f"poses must hold at most {TOUR_MAX_NODES} nodes, got n = {n}")
-    if quats is not None and (not torch.is_tensor(quats) or not quats.is_floating_point() or tuple(quats.shape) != (n, 4)):
-        raise ValueError(f"quats must be None or a floating-point tensor of shape ({n},4), got "
-                         f"{tuple(quats.shape) if torch.is_tensor(quats) else type(quats).__name__}")
+    if quats is not None:
+        _check_float_rows(quats, "quats", f"None or a floating-point tensor of shape ({n},4)", 4, n)
     r = check_tour_radius(clearance_radius) if clearance_radius is not None else None
     if not isinstance(closed, (bool, np.bool_)):
         raise ValueError(f"closed must be True or False, got {closed!r}")
     if max_moves is None:
         max_moves = 4 * n
-    elif isinstance(max_moves, bool) or not isinstance(max_moves, (int, np.integer)) or max_moves < 0:
+    elif not _is_int(max_moves) or max_moves < 0:
         raise ValueError(f"max_moves must be None or an integer >= 0, got {max_moves!r}")
     return n, r, int(max_moves)
 
 
 def tour_layout(n):
     """Byte offsets of a tour buffer's sections (include/trajopt_hip.h, tohip_tour_bytes): every section aligned to 256 bytes."""
-    up = lambda v: (v + 255) // 256 * 256
-    out, o = {"header": 0}, 256
-    for name, nbytes in (("order", 4 * n), ("unreachable", n), ("D", 8 * n * n), ("nxt", 4 * n * n)):
-        out[name] = o
-        o += up(nbytes)
-    out["total"] = o
-    return out
+    return _sections(256, (("order", 4 * n), ("unreachable", n), ("D", 8 * n * n), ("nxt", 4 * n * n)))
 
 
 def tour_edge_ends(n, device):
@@ -996,9 +1005,9 @@ def tour_edge_ends(n, device):
     return ij[0], ij[1]
 
 
-def tour_plan(nodes, edge_idx=None, closed=False, max_moves=None):
-    """tohip_tour_plan over nodes (n,3) f32 on the device and the edge stage's idx (n (n - 1) / 2 int32) or None -> the tour buffer
-    (uint8, tour_layout(n)) on the device; launches only."""
+def _tour_plan(nodes, edge_idx, closed, max_moves, via, via_D=None):
+    """tour_plan (via=False) and tour_plan_via (via=True) behind their signatures: the checks, the buffer, the launch -> (buf, via_flag
+    or None)."""
     _require_cuda(nodes, "nodes")
     n = nodes.shape[0]
     L = _lib.lib()
@@ -1008,12 +1017,26 @@ def tour_plan(nodes, edge_idx=None, closed=False, max_moves=None):
     if edge_idx is not None and not (edge_idx.dtype == torch.int32 and edge_idx.is_contiguous() and edge_idx.numel() == n * (n - 1) // 2
                                      and edge_idx.device == nodes.device):
         raise ValueError(f"edge_idx must be {n * (n - 1) // 2} contiguous int32 on the nodes' device")
+    if via and not (torch.is_tensor(via_D) and via_D.dtype == torch.int64 and via_D.dim() == 2 and via_D.shape[0] >= n and via_D.shape[1] >= n
+                    and via_D.stride(1) == 1 and via_D.stride(0) >= via_D.shape[1] and via_D.device == nodes.device):
+        raise ValueError(f"via_D must be an int64 tensor of at least ({n},{n}) with unit column stride on the nodes' device")
     assert nbytes == tour_layout(n)["total"]
     buf = torch.empty(nbytes, dtype=torch.uint8, device=nodes.device)
+    closed, max_moves = int(bool(closed)), int(4 * n if max_moves is None else max_moves)
     with torch.cuda.device(nodes.device):
-        check(L.tohip_tour_plan(ptr(nodes), n, ptr(edge_idx), int(bool(closed)), int(4 * n if max_moves is None else max_moves), ptr(buf),
-                                nbytes, stream_ptr()), "tohip_tour_plan")
-    return buf
+        if not via:
+            check(L.tohip_tour_plan(ptr(nodes), n, ptr(edge_idx), closed, max_moves, ptr(buf), nbytes, stream_ptr()), "tohip_tour_plan")
+            return buf, None
+        flag = torch.empty((n, n), dtype=torch.uint8, device=nodes.device)
+        check(L.tohip_tour_plan_via(ptr(nodes), n, ptr(edge_idx), ptr(via_D), via_D.stride(0), closed, max_moves, ptr(buf), nbytes, ptr(flag),
+                                    stream_ptr()), "tohip_tour_plan_via")
+    return buf, flag
+
+
+def tour_plan(nodes, edge_idx=None, closed=False, max_moves=None):
+    """tohip_tour_plan over nodes (n,3) f32 on the device and the edge stage's idx (n (n - 1) / 2 int32) or None -> the tour buffer
+    (uint8, tour_layout(n)) on the device; launches only."""
+    return _tour_plan(nodes, edge_idx, closed, max_moves, False)[0]
 
 
 ROADMAP_MAX_NODES = 16384   # TOHIP_ROADMAP_MAX_NODES
@@ -1026,18 +1049,12 @@ ROADMAP_MAX_LEN = 1 << 40   # the longest edge that can be open, in units of 2^-
 def check_roadmap_options(k=12, clearance_radius=None, max_edge=None):
     """k an integer in 1..ROADMAP_MAX_K, clearance_radius None or a finite number > 0, max_edge None or a number >= 0 (NaN refused)
     -> (k, radius or None, max_edge as a float, +inf for None); ValueError otherwise."""
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= ROADMAP_MAX_K:
+    if not _is_int(k) or not 1 <= k <= ROADMAP_MAX_K:
         raise ValueError(f"k must be an integer in 1..{ROADMAP_MAX_K}, got {k!r}")
     r = check_tour_radius(clearance_radius) if clearance_radius is not None else None
-    if max_edge is None:
-        me = float("inf")
-    else:
-        try:
-            me = float(max_edge)
-        except (TypeError, ValueError):
-            me = float("nan")
-        if not me >= 0.0:
-            raise ValueError(f"max_edge must be None or a number >= 0, got {max_edge!r}")
+    me = float("inf") if max_edge is None else _float_or_nan(max_edge)
+    if not me >= 0.0:
+        raise ValueError(f"max_edge must be None or a number >= 0, got {max_edge!r}")
     return int(k), r, me
 
 
@@ -1046,14 +1063,12 @@ def check_roadmap(nodes, k=12, clearance_radius=None, max_edge=None, sources=Non
     clearance_radius None or a finite number > 0, max_edge None or a number >= 0 (NaN refused), sources None or 1..ROADMAP_MAX_SOURCES
     integer node indices in [0, M) (a list, an array or a tensor), sweeps_per_check an integer >= 1 -> (M, k, radius or None,
     max_edge as a float (+inf for None), sources as a list or None); ValueError otherwise.  Nothing is launched."""
-    if not torch.is_tensor(nodes) or not nodes.is_floating_point() or nodes.dim() != 2 or nodes.shape[1] != 3:
-        raise ValueError(f"nodes must be a floating-point tensor of shape (M,3), got "
-                         f"{tuple(nodes.shape) if torch.is_tensor(nodes) else type(nodes).__name__}")
+    _check_float_rows(nodes, "nodes", "a floating-point tensor of shape (M,3)", 3)
     M = nodes.shape[0]
     if M < 2 or M > ROADMAP_MAX_NODES:
         raise ValueError(f"nodes must hold 2 <= M <= {ROADMAP_MAX_NODES} nodes, got M = {M}")
     k, r, me = check_roadmap_options(k, clearance_radius, max_edge)
-    if isinstance(sweeps_per_check, bool) or not isinstance(sweeps_per_check, (int, np.integer)) or sweeps_per_check < 1:
+    if not _is_int(sweeps_per_check) or sweeps_per_check < 1:
         raise ValueError(f"sweeps_per_check must be an integer >= 1, got {sweeps_per_check!r}")
     src = None
     if sources is not None:
@@ -1083,8 +1098,7 @@ def roadmap_knn(nodes, k=12, max_edge=None):
 
 def roadmap_routes_layout(M, S):
     """Byte offsets of a routes buffer's sections (include/trajopt_hip.h, tohip_roadmap_routes_bytes)."""
-    up = lambda v: (v + 255) // 256 * 256
-    return {"D": 0, "pred": up(8 * M * S), "changed": up(8 * M * S) + up(4 * M * S), "total": up(8 * M * S) + up(4 * M * S) + 256}
+    return _sections(0, (("D", 8 * M * S), ("pred", 4 * M * S), ("changed", 256)))
 
 
 def roadmap_routes(nbr, length_fixed, open_, sources, sweeps_per_check=8):
@@ -1137,25 +1151,7 @@ def roadmap_routes(nbr, length_fixed, open_, sources, sweeps_per_check=8):
 def tour_plan_via(nodes, edge_idx, via_D, closed=False, max_moves=None):
     """tohip_tour_plan_via: tour_plan whose initial legs are min(direct, via_D[i][j]) — via_D (n or more rows, n or more columns)
     int64 on the device, row i the roadmap's routes from tour node i -> (the tour buffer, via_flag (n,n) uint8); launches only."""
-    _require_cuda(nodes, "nodes")
-    n = nodes.shape[0]
-    L = _lib.lib()
-    nbytes = L.tohip_tour_bytes(n)
-    if nbytes == 0 or tuple(nodes.shape) != (n, 3) or nodes.dtype != torch.float32 or not nodes.is_contiguous():
-        raise ValueError(f"nodes must be a contiguous (n,3) float32 tensor with 2 <= n <= {TOUR_MAX_NODES}, got {tuple(nodes.shape)}")
-    if edge_idx is not None and not (edge_idx.dtype == torch.int32 and edge_idx.is_contiguous() and edge_idx.numel() == n * (n - 1) // 2
-                                     and edge_idx.device == nodes.device):
-        raise ValueError(f"edge_idx must be {n * (n - 1) // 2} contiguous int32 on the nodes' device")
-    if not (torch.is_tensor(via_D) and via_D.dtype == torch.int64 and via_D.dim() == 2 and via_D.shape[0] >= n and via_D.shape[1] >= n
-            and via_D.stride(1) == 1 and via_D.stride(0) >= via_D.shape[1] and via_D.device == nodes.device):
-        raise ValueError(f"via_D must be an int64 tensor of at least ({n},{n}) with unit column stride on the nodes' device")
-    buf = torch.empty(nbytes, dtype=torch.uint8, device=nodes.device)
-    flag = torch.empty((n, n), dtype=torch.uint8, device=nodes.device)
-    with torch.cuda.device(nodes.device):
-        check(L.tohip_tour_plan_via(ptr(nodes), n, ptr(edge_idx), ptr(via_D), via_D.stride(0), int(bool(closed)),
-                                    int(4 * n if max_moves is None else max_moves), ptr(buf), nbytes, ptr(flag), stream_ptr()),
-              "tohip_tour_plan_via")
-    return buf, flag
+    return _tour_plan(nodes, edge_idx, closed, max_moves, True, via_D)
 
 
 PATH_MAX_NODES = 1024   # TOHIP_PATH_MAX_NODES
@@ -1167,49 +1163,37 @@ def check_path(path, quats=None, keep=None, window=None, spacing=None, max_rows=
     keep None or (L,) bool / uint8, window None (L - 1) or an integer in 1..L-1, spacing None or a finite number > 0, max_rows None
     (PATH_MAX_ROWS) or an integer in 1..PATH_MAX_ROWS -> (L, window, spacing as a float or None, max_rows); ValueError otherwise.
     Nothing is launched."""
-    if not torch.is_tensor(path) or not path.is_floating_point() or path.dim() != 2 or path.shape[1] != 3:
-        raise ValueError(f"path must be a floating-point tensor of shape (L,3), got "
-                         f"{tuple(path.shape) if torch.is_tensor(path) else type(path).__name__}")
+    _check_float_rows(path, "path", "a floating-point tensor of shape (L,3)", 3)
     L = path.shape[0]
     if L < 2 or L > PATH_MAX_NODES:
         raise ValueError(f"path must hold 2 <= L <= {PATH_MAX_NODES} nodes, got L = {L}")
-    if quats is not None and (not torch.is_tensor(quats) or not quats.is_floating_point() or tuple(quats.shape) != (L, 4)):
-        raise ValueError(f"quats must be None or a floating-point tensor of shape ({L},4), got "
-                         f"{tuple(quats.shape) if torch.is_tensor(quats) else type(quats).__name__}")
+    if quats is not None:
+        _check_float_rows(quats, "quats", f"None or a floating-point tensor of shape ({L},4)", 4, L)
     if keep is not None and (not torch.is_tensor(keep) or keep.dtype not in (torch.bool, torch.uint8) or tuple(keep.shape) != (L,)):
         raise ValueError(f"keep must be None or a bool / uint8 tensor of shape ({L},), got "
                          f"{(tuple(keep.shape), keep.dtype) if torch.is_tensor(keep) else type(keep).__name__}")
     if window is None:
         window = L - 1
-    elif isinstance(window, bool) or not isinstance(window, (int, np.integer)) or not 1 <= window <= L - 1:
+    elif not _is_int(window) or not 1 <= window <= L - 1:
         raise ValueError(f"window must be None or an integer in 1..{L - 1}, got {window!r}")
     h = None
     if spacing is not None:
-        try:
-            h = float(spacing)
-        except (TypeError, ValueError):
-            h = float("nan")
+        h = _float_or_nan(spacing)
         with np.errstate(over="ignore"):
             hf = float(np.float32(h))   # what the library is handed
         if not (np.isfinite(hf) and hf > 0.0):
             raise ValueError(f"spacing must be None or a finite number > 0 (as a float32), got {spacing!r}")
     if max_rows is None:
         max_rows = PATH_MAX_ROWS
-    elif isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or not 1 <= max_rows <= PATH_MAX_ROWS:
+    elif not _is_int(max_rows) or not 1 <= max_rows <= PATH_MAX_ROWS:
         raise ValueError(f"max_rows must be None or an integer in 1..{PATH_MAX_ROWS}, got {max_rows!r}")
     return L, int(window), h, int(max_rows)
 
 
 def path_layout(L, max_rows):
     """Byte offsets of a refined path's buffer (include/trajopt_hip.h, tohip_path_bytes): every section aligned to 256 bytes."""
-    up = lambda v: (v + 255) // 256 * 256
-    out, o = {"header": 0}, 256
-    for name, nbytes in (("D", 8 * L), ("pred", 4 * L), ("corner", 4 * L), ("out_poses", 12 * max_rows), ("out_quats", 16 * max_rows),
-                         ("row_node", 4 * max_rows)):
-        out[name] = o
-        o += up(nbytes)
-    out["total"] = o
-    return out
+    return _sections(256, (("D", 8 * L), ("pred", 4 * L), ("corner", 4 * L), ("out_poses", 12 * max_rows), ("out_quats", 16 * max_rows),
+                           ("row_node", 4 * max_rows)))
 
 
 def path_refine(P, quats, keep, open_band, window=None, spacing=None, max_rows=None):
@@ -1249,10 +1233,6 @@ VIEW_MAX_WEIGHT = 32768         # a point's largest weight: 65 536 points of a b
 VIEW_MIN_DIST = float(np.float32(1e-3))
 
 
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
-
-
 def check_propose(n_points, positions, open=None, weights=None, sectors=32, min_dist=1.0, max_dist=5.0, tan_v=1.0, hw=0, n_per=2, sep=None,
                   min_score=0):
     """The arguments of a view proposal over a cloud of n_points: positions (M,3) a floating tensor, 1 <= M <= VIEW_MAX_POSITIONS (a
@@ -1261,9 +1241,7 @@ def check_propose(n_points, positions, open=None, weights=None, sectors=32, min_
     hw an integer >= 0 with 2 hw + 1 <= sectors; n_per an integer in 1..VIEW_MAX_PER_POSITION; sep None (2 hw) or an integer in
     0..sectors; min_score an integer >= 0 -> (M, sectors, min_dist, max_dist, tan_v, hw, n_per, sep, min_score); ValueError otherwise.
     Nothing is launched (the weights' range is read where they live)."""
-    if not torch.is_tensor(positions) or not positions.is_floating_point() or positions.dim() != 2 or positions.shape[1] != 3:
-        raise ValueError(f"positions must be a floating-point tensor of shape (M,3), got "
-                         f"{tuple(positions.shape) if torch.is_tensor(positions) else type(positions).__name__}")
+    _check_float_rows(positions, "positions", "a floating-point tensor of shape (M,3)", 3)
     M = positions.shape[0]
     if M < 1 or M > VIEW_MAX_POSITIONS:
         raise ValueError(f"positions must hold 1 <= M <= {VIEW_MAX_POSITIONS} rows, got M = {M}")
@@ -1280,11 +1258,8 @@ def check_propose(n_points, positions, open=None, weights=None, sectors=32, min_
         raise ValueError(f"sectors must be one of {VIEW_SECTORS}, got {sectors!r}")
     vals = []
     for name, v in (("min_dist", min_dist), ("max_dist", max_dist), ("tan_v", tan_v)):
-        try:
-            with np.errstate(over="ignore"):
-                f = float(np.float32(float(v)))   # what the library is handed
-        except (TypeError, ValueError):
-            f = float("nan")
+        with np.errstate(over="ignore"):
+            f = float(np.float32(_float_or_nan(v)))   # what the library is handed
         if not np.isfinite(f):
             raise ValueError(f"{name} must be a finite number (as a float32), got {v!r}")
         vals.append(f)

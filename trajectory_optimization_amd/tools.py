@@ -220,7 +220,16 @@ def coverage_map(origin=(0.0, 0.0, 0.0), resolution=0.1, clamp_max=None, capacit
     return ops.CoverageMap(origin, resolution, clamp_max=clamp_max, capacity=capacity, device=device)
 
 
-class ViewSelection:
+class _Result:
+    """What the result classes share: the keyword constructor; each names its fields in its own __slots__."""
+    __slots__ = ()
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+class ViewSelection(_Result):
     """What select_views returns: order (n_selected,) int64 and gains (n_selected,) f64 on the host (gain j = what view order[j] added
     to the mean reward when it was chosen), poses / quats (the chosen rows in selection order), rewards (N,) and mean_reward of the
     chosen views together (with the prior), coverage_log_odds (N,) in the caller's order (prior + the chosen views' log-odds: the next
@@ -228,10 +237,6 @@ class ViewSelection:
     gain_fixed (n_selected,) int64 (the integer sums behind `gains`) and log_odds (npad,) the chosen views' summed log-odds in the
     packed order."""
     __slots__ = ("order", "gains", "gain_fixed", "poses", "quats", "rewards", "mean_reward", "coverage_log_odds", "nnz", "absent", "log_odds")
-
-    def __init__(self, **kw):
-        for k, v in kw.items():
-            setattr(self, k, v)
 
     @property
     def n_selected(self):
@@ -242,9 +247,7 @@ def _views_setup(model_or_cloud, prior_log_odds, occlusion, kw):
     """select_views' first argument resolved -> dict(cloud, cam, rig, flags, prior, occlusion, limits); cloud / prior may still be
     what the caller gave (points / a tensor): they are packed after every check has passed."""
     m = model_or_cloud
-    if hasattr(m, "_cloud") and hasattr(m, "_shard"):   # a ModelTraj: its own settings, nothing to override
-        if m._shard.kind == "points" or m._shard.world_size > 1 or m._shard.collective:
-            raise ValueError("select_views: a sharded model (WaypointShard / PointShard) is not supported")
+    if ops._model_cloud(m, "select_views") is not m:   # a ModelTraj: its own settings, nothing to override
         if kw:
             raise ValueError(f"select_views: {sorted(kw)} belong to the call with points; a ModelTraj brings its own camera and rig")
         if occlusion is not None and occlusion != m._occlusion:
@@ -347,11 +350,7 @@ def select_views(model_or_cloud, cand_poses, cand_quats, k, prior_log_odds=None,
 def _clearance_cloud(points_or_cloud_or_model, what):
     """The packed cloud behind a clearance query's first argument: a ModelTraj (its cloud), an ops.PackedCloud (sorted or not) or
     (N,3) points (packed here) — checked, nothing launched: -> (cloud or None, points or None)."""
-    c = points_or_cloud_or_model
-    if hasattr(c, "_cloud") and hasattr(c, "_shard"):
-        if c._shard.kind == "points" or c._shard.world_size > 1 or c._shard.collective:
-            raise ValueError(f"{what}: a sharded model (WaypointShard / PointShard) is not supported")
-        c = c._cloud
+    c = ops._model_cloud(points_or_cloud_or_model, what)
     if isinstance(c, ops.PackedCloud):
         return c, None
     if not torch.is_tensor(c) or c.dim() != 2 or c.shape[1] != 3 or c.shape[0] == 0:
@@ -375,7 +374,7 @@ def edge_clearance(points_or_cloud_or_model, a, b, radius):
     return ops.clearance_edges(cloud, a.to(cloud.device), b.to(cloud.device), r)
 
 
-class Tour:
+class Tour(_Result):
     """What plan_tour returns.  order (m,) int64 on the host: the reachable nodes in visiting order, order[0] == 0; unreachable (n,)
     bool; walk: the list of node indices actually travelled — the order with the nodes a leg passes through inserted (and the way
     back to node 0 when closed); poses / quats: the walk's rows on the device (a pass-through node keeps its own quaternion; quats is
@@ -391,10 +390,6 @@ class Tour:
     walk_nodes (a free-space node takes the quaternion of the view its leg leads to), walk keeps listing tour nodes only."""
     __slots__ = ("order", "unreachable", "walk", "poses", "quats", "length", "nn_length", "length_fixed", "nn_length_fixed", "moves",
                  "converged", "blocked", "edge_distance", "D", "nxt", "roadmap", "via_flag", "walk_nodes")
-
-    def __init__(self, **kw):
-        for k, v in kw.items():
-            setattr(self, k, v)
 
 
 def tour_edge_stage(cloud, n_edges):
@@ -435,71 +430,91 @@ def plan_tour(points_or_cloud_or_model, poses, quats=None, clearance_radius=None
     cloud, pts = _clearance_cloud(points_or_cloud_or_model, "plan_tour")
     n, r, max_moves = ops.check_tour(poses, quats, clearance_radius, closed, max_moves)
     if via is not None:
-        return _plan_tour_via(cloud, pts, poses, quats, n, r, closed, max_moves, via, via_k, via_max_edge)
-    if cloud is None:
-        if not pts.is_cuda:
-            raise ValueError(f"plan_tour: points must live on a HIP device, got {pts.device}")
-        if r is not None:
-            cloud = ops.PackedCloud(pts.to(torch.float32))
+        _check_via(via, n)
+        if r is None:
+            raise ValueError("plan_tour: via needs a clearance_radius (a finite number > 0), got None")
+        k, _, _ = ops.check_roadmap_options(via_k, r, via_max_edge)
+    cloud = _device_cloud(cloud, pts, "plan_tour", pack=r is not None)
     dev = cloud.device if cloud is not None else pts.device
-    nodes = poses.detach().to(device=dev, dtype=torch.float32).contiguous()
+    nodes = allnodes = poses.detach().to(device=dev, dtype=torch.float32).contiguous()
     qs = quats.detach().to(device=dev, dtype=torch.float32).contiguous() if quats is not None else None
-    E = n * (n - 1) // 2
-    i, j = ops.tour_edge_ends(n, dev)
-    dist = torch.full((n, n), float("inf"), dtype=torch.float32, device=dev)
-    if r is not None:
-        d, idx, _ = tour_edge_query(cloud, nodes, r)
-        dist[i, j] = d
-        dist[j, i] = d
+    rm = None
+    if via is not None:   # the roadmap over [poses; via] and the routes from every tour node
+        allnodes = _join_nodes(nodes, via.detach().to(device=dev, dtype=torch.float32))
+        rm = _build_roadmap(cloud, allnodes, r, k, via_max_edge)
+        routes = rm.routes(list(range(n)))
+    E, M = n * (n - 1) // 2, allnodes.shape[0]
+    d, idx, _ = tour_edge_query(cloud, nodes, r) if r is not None else (None, None, None)
+    dist = _symmetric(n, ops.tour_edge_ends(n, dev), d, float("inf"), torch.float32)
+    tail = [idx.view(torch.uint8)] if idx is not None else []
+    if rm is None:
+        buf = ops.tour_plan(nodes, idx, closed, max_moves)
     else:
-        idx = None
-    buf = ops.tour_plan(nodes, idx, closed, max_moves)
-    # the one synchronisation: the tour buffer and the edges' answers in one copy
-    tail = idx.view(torch.uint8) if idx is not None else buf[:0]
-    h = torch.cat([buf, tail]).cpu()
+        buf, flag = ops.tour_plan_via(nodes, idx, routes.D, closed, max_moves)
+        tail += [routes.pred.reshape(-1).view(torch.uint8), flag.reshape(-1)]
+    # the one synchronisation: the tour buffer, the edges' answers and (with via) the routes' predecessors and the flags in one copy
+    h = torch.cat([buf] + tail).cpu()
+    hdr, order, unreachable, D, nxt = _unpack_tour(h, n)
+    o = ops.tour_layout(n)["total"]
+    hit = h[o:o + 4 * E].view(torch.int32) != -1 if idx is not None else None
+    blocked = _symmetric(n, ops.tour_edge_ends(n, "cpu"), hit, False, torch.bool)
+    from .synth import tour_walk   # (numpy only)
+    walk = tour_walk(order.tolist(), nxt.numpy(), closed)
+    via_flag, walk_nodes, q_of = None, None, walk   # q_of: the tour node whose quaternion each row of the walk takes
+    if rm is not None:   # every leg that runs over the roadmap expanded into its nodes
+        o += 4 * E
+        pred = h[o:o + 4 * n * M].view(torch.int32).reshape(n, M).numpy()
+        o += 4 * n * M
+        via_flag = h[o:o + n * n].reshape(n, n) != 0
+        walk_nodes, q_of = [walk[0]], [walk[0]]
+        for u, v in zip(walk, walk[1:]):
+            hop = rm.walk(routes, u, pred[u], v)[1:] if via_flag[u, v] else [v]
+            walk_nodes += hop
+            q_of += [x if x < n else v for x in hop]
+    w = torch.as_tensor(walk if walk_nodes is None else walk_nodes, dtype=torch.int64, device=dev)
+    return Tour(order=order, unreachable=unreachable, walk=walk, poses=allnodes[w],
+                quats=qs[torch.as_tensor(q_of, dtype=torch.int64, device=dev)] if qs is not None else None,
+                length=int(hdr[3]) * ops.TOUR_UNIT, nn_length=int(hdr[4]) * ops.TOUR_UNIT, length_fixed=int(hdr[3]),
+                nn_length_fixed=int(hdr[4]), moves=int(hdr[1]), converged=bool(hdr[2]), blocked=blocked, edge_distance=dist, D=D, nxt=nxt,
+                roadmap=rm, via_flag=via_flag, walk_nodes=walk_nodes)
+
+
+def _symmetric(n, ends, values, fill, dtype):
+    """The symmetric (n,n) matrix of per-edge values: values[e] at (i[e], j[e]) and (j[e], i[e]) for ends = (i, j), `fill` elsewhere
+    (and everywhere for values None), on the ends' device."""
+    i, j = ends
+    out = torch.full((n, n), fill, dtype=dtype, device=i.device)
+    if values is not None:
+        out[i, j] = values
+        out[j, i] = values
+    return out
+
+
+def _unpack_tour(h, n):
+    """A host copy h of a tour buffer (ops.tour_layout(n); anything may follow it) -> (hdr: the first 8 int64 of the header, order (m,)
+    int64, unreachable (n,) bool, D (n,n) int64, nxt (n,n) int32)."""
     lay = ops.tour_layout(n)
     hdr = h[:64].view(torch.int64)
-    m = int(hdr[0])
-    order = h[lay["order"]:lay["order"] + 4 * n].view(torch.int32)[:m].to(torch.int64)
+    order = h[lay["order"]:lay["order"] + 4 * n].view(torch.int32)[:int(hdr[0])].to(torch.int64)
     unreachable = h[lay["unreachable"]:lay["unreachable"] + n] != 0
     D = h[lay["D"]:lay["D"] + 8 * n * n].view(torch.int64).reshape(n, n).clone()
     nxt = h[lay["nxt"]:lay["nxt"] + 4 * n * n].view(torch.int32).reshape(n, n).clone()
-    blocked = torch.zeros((n, n), dtype=torch.bool)
-    if idx is not None:
-        hit = h[lay["total"]:lay["total"] + 4 * E].view(torch.int32) != -1
-        ih, jh = i.cpu(), j.cpu()
-        blocked[ih, jh] = hit
-        blocked[jh, ih] = hit
-    from .synth import tour_walk   # (numpy only)
-    walk = tour_walk(order.tolist(), nxt.numpy(), closed)
-    w = torch.as_tensor(walk, dtype=torch.int64, device=dev)
-    return Tour(order=order, unreachable=unreachable, walk=walk, poses=nodes[w], quats=qs[w] if qs is not None else None,
-                length=int(hdr[3]) * ops.TOUR_UNIT, nn_length=int(hdr[4]) * ops.TOUR_UNIT, length_fixed=int(hdr[3]),
-                nn_length_fixed=int(hdr[4]), moves=int(hdr[1]), converged=bool(hdr[2]), blocked=blocked, edge_distance=dist, D=D, nxt=nxt,
-                roadmap=None, via_flag=None, walk_nodes=None)
+    return hdr, order, unreachable, D, nxt
 
 
-class RoadmapRoutes:
+class RoadmapRoutes(_Result):
     """What Roadmap.routes returns: sources (the list asked for), D (S,M) int64 and pred (S,M) int32 on the device — the shortest
     route length from each source to every node over the open edges (2^62 where none exists) and, for each node, the lowest
     neighbour a shortest route arrives from (-1 for the source and the unreachable) — and sweeps, the relaxation sweeps it took."""
     __slots__ = ("sources", "D", "pred", "sweeps")
 
-    def __init__(self, **kw):
-        for k, v in kw.items():
-            setattr(self, k, v)
 
-
-class Roadmap:
+class Roadmap(_Result):
     """What build_roadmap returns, device tensors unless noted: nodes (M,3) f32; nbr (M,k) int32: each node's k nearest others (-1:
     none); length_fixed (M,k) int64: those edges' lengths in units of 2^-20 m; open (M,k) bool: the edges that keep the clearance
     radius; edge_distance (M,k) f32: a blocked edge's distance to the cloud, +inf where open (and in an empty slot); isolated (M,)
     bool: the nodes no open edge touches; n_open (an int): the open edges, each unordered pair counted once."""
     __slots__ = ("nodes", "nbr", "length_fixed", "open", "edge_distance", "isolated", "n_open", "_edges")
-
-    def __init__(self, **kw):
-        for k, v in kw.items():
-            setattr(self, k, v)
 
     def host_edges(self):
         """(u, v, L) on the host: both directions of every open slot (synth.roadmap_edges), copied once — what a walk falls back
@@ -539,12 +554,14 @@ class Roadmap:
         return walk, fixed, fixed * ops.TOUR_UNIT
 
 
-def _device_cloud(cloud, pts, what):
-    """The packed cloud of a _clearance_cloud pair: the points are packed here, which is the first GPU call."""
+def _device_cloud(cloud, pts, what, pack=True):
+    """The packed cloud of a _clearance_cloud pair: the points are packed here, which is the first GPU call (pack=False: only
+    checked to be on the device, and None comes back for them)."""
     if cloud is None:
         if not pts.is_cuda:
             raise ValueError(f"{what}: points must live on a HIP device, got {pts.device}")
-        cloud = ops.PackedCloud(pts.to(torch.float32))
+        if pack:
+            cloud = ops.PackedCloud(pts.to(torch.float32))
     return cloud
 
 
@@ -583,22 +600,18 @@ def build_roadmap(points_or_cloud_or_model, nodes, clearance_radius, k=12, max_e
     Lengths are integers in units of 2^-20 m, so routes over it are the same bits in every run.  -> Roadmap."""
     cloud, pts = _clearance_cloud(points_or_cloud_or_model, "build_roadmap")
     if clearance_radius is None:
-        raise ValueError("clearance_radius must be a finite number > 0, got None")
+        ops.check_tour_radius(clearance_radius)   # (raises: a roadmap needs one)
     _, k, r, me, _ = ops.check_roadmap(nodes, k, clearance_radius, max_edge)
     cloud = _device_cloud(cloud, pts, "build_roadmap")
     q = nodes.detach().to(device=cloud.device, dtype=torch.float32).contiguous()
     return _build_roadmap(cloud, q, r, k, max_edge)
 
 
-class PlannedPath:
+class PlannedPath(_Result):
     """What plan_path returns: poses (L,3) f32 on the device: start, the free-space nodes of the route, goal — every leg keeps the
     clearance radius; length in metres (f64 from the integer length_fixed, units of 2^-20 m); walk: the route as indices into
     [start; goal; via]; roadmap: the Roadmap it ran over."""
     __slots__ = ("poses", "length", "length_fixed", "walk", "roadmap")
-
-    def __init__(self, **kw):
-        for k, v in kw.items():
-            setattr(self, k, v)
 
 
 def _point3(p, name, device):
@@ -609,9 +622,7 @@ def _point3(p, name, device):
 
 
 def _check_via(via, n, what="via"):
-    if not torch.is_tensor(via) or not via.is_floating_point() or via.dim() != 2 or via.shape[1] != 3 or via.shape[0] == 0:
-        raise ValueError(f"{what} must be a floating-point tensor of shape (F,3) with F > 0, got "
-                         f"{tuple(via.shape) if torch.is_tensor(via) else type(via).__name__}")
+    ops._check_float_rows(via, what, "a floating-point tensor of shape (F,3) with F > 0", 3, empty=False)
     if n + via.shape[0] > ops.ROADMAP_MAX_NODES:
         raise ValueError(f"{what}: the roadmap holds at most {ops.ROADMAP_MAX_NODES} nodes, got {n} + {via.shape[0]}")
 
@@ -630,7 +641,7 @@ def plan_path(points_or_cloud_or_model, start, goal, via, clearance_radius, k=12
     cloud, pts = _clearance_cloud(points_or_cloud_or_model, "plan_path")
     _check_via(via, 2)
     if clearance_radius is None:
-        raise ValueError("clearance_radius must be a finite number > 0, got None")
+        ops.check_tour_radius(clearance_radius)   # (raises: a path needs one)
     k, r, _ = ops.check_roadmap_options(k, clearance_radius, max_edge)
     ends = torch.cat([_point3(start, "start", "cpu"), _point3(goal, "goal", "cpu")])
     cloud = _device_cloud(cloud, pts, "plan_path")
@@ -645,61 +656,7 @@ def plan_path(points_or_cloud_or_model, start, goal, via, clearance_radius, k=12
                        roadmap=rm)
 
 
-def _plan_tour_via(cloud, pts, poses, quats, n, r, closed, max_moves, via, via_k, via_max_edge):
-    """plan_tour with a roadmap behind its legs (its arguments are checked already)."""
-    _check_via(via, n)
-    if r is None:
-        raise ValueError("plan_tour: via needs a clearance_radius (a finite number > 0), got None")
-    k, _, _ = ops.check_roadmap_options(via_k, r, via_max_edge)
-    cloud = _device_cloud(cloud, pts, "plan_tour")
-    dev = cloud.device
-    nodes = poses.detach().to(device=dev, dtype=torch.float32).contiguous()
-    qs = quats.detach().to(device=dev, dtype=torch.float32).contiguous() if quats is not None else None
-    allnodes = _join_nodes(nodes, via.detach().to(device=dev, dtype=torch.float32))
-    M = allnodes.shape[0]
-    rm = _build_roadmap(cloud, allnodes, r, k, via_max_edge)
-    routes = rm.routes(list(range(n)))
-    E = n * (n - 1) // 2
-    i, j = ops.tour_edge_ends(n, dev)
-    dist = torch.full((n, n), float("inf"), dtype=torch.float32, device=dev)
-    d, idx, _ = tour_edge_query(cloud, nodes, r)
-    dist[i, j] = d
-    dist[j, i] = d
-    buf, flag = ops.tour_plan_via(nodes, idx, routes.D, closed, max_moves)
-    h = torch.cat([buf, idx.view(torch.uint8), routes.pred.reshape(-1).view(torch.uint8), flag.reshape(-1)]).cpu()
-    lay = ops.tour_layout(n)
-    hdr = h[:64].view(torch.int64)
-    m = int(hdr[0])
-    order = h[lay["order"]:lay["order"] + 4 * n].view(torch.int32)[:m].to(torch.int64)
-    unreachable = h[lay["unreachable"]:lay["unreachable"] + n] != 0
-    D = h[lay["D"]:lay["D"] + 8 * n * n].view(torch.int64).reshape(n, n).clone()
-    nxt = h[lay["nxt"]:lay["nxt"] + 4 * n * n].view(torch.int32).reshape(n, n).clone()
-    o = lay["total"]
-    hit = h[o:o + 4 * E].view(torch.int32) != -1
-    blocked = torch.zeros((n, n), dtype=torch.bool)
-    ih, jh = i.cpu(), j.cpu()
-    blocked[ih, jh] = hit
-    blocked[jh, ih] = hit
-    o += 4 * E
-    pred = h[o:o + 4 * n * M].view(torch.int32).reshape(n, M).numpy()
-    o += 4 * n * M
-    via_flag = h[o:o + n * n].reshape(n, n) != 0
-    from .synth import tour_walk   # (numpy only)
-    walk = tour_walk(order.tolist(), nxt.numpy(), closed)
-    walk_nodes, q_of = [walk[0]], [walk[0]]   # q_of: the tour node whose quaternion each walk node takes
-    for u, v in zip(walk, walk[1:]):
-        hop = rm.walk(routes, u, pred[u], v)[1:] if via_flag[u, v] else [v]
-        walk_nodes += hop
-        q_of += [x if x < n else v for x in hop]
-    w = torch.as_tensor(walk_nodes, dtype=torch.int64, device=dev)
-    return Tour(order=order, unreachable=unreachable, walk=walk, poses=allnodes[w],
-                quats=qs[torch.as_tensor(q_of, dtype=torch.int64, device=dev)] if qs is not None else None,
-                length=int(hdr[3]) * ops.TOUR_UNIT, nn_length=int(hdr[4]) * ops.TOUR_UNIT, length_fixed=int(hdr[3]),
-                nn_length_fixed=int(hdr[4]), moves=int(hdr[1]), converged=bool(hdr[2]), blocked=blocked, edge_distance=dist, D=D, nxt=nxt,
-                roadmap=rm, via_flag=via_flag, walk_nodes=walk_nodes)
-
-
-class RefinedPath:
+class RefinedPath(_Result):
     """What refine_path returns.  poses (R,3) f32 and quats (R,4) f32 (None when no quaternions came in) on the device, ready for
     ModelTraj.sharing_cloud_of; row_node (R,) int32 on the host: the input row a corner row came from, -1 at an interpolated row;
     corners (m + 1,) int64 on the host: the input rows the refined path turns at, 0 first and L - 1 last; length / input_length in
@@ -708,10 +665,6 @@ class RefinedPath:
     at least one node; open_band (L,W) uint8 on the device: the chord stage's answers as the search read them."""
     __slots__ = ("poses", "quats", "row_node", "corners", "length", "length_fixed", "input_length", "input_length_fixed", "leg_blocked",
                  "n_open", "open_band")
-
-    def __init__(self, **kw):
-        for k, v in kw.items():
-            setattr(self, k, v)
 
 
 def _path_chord_band(cloud, P, kept, W, r):
@@ -753,8 +706,6 @@ def refine_path(points_or_cloud_or_model, path, quats=None, clearance_radius=Non
     elif isinstance(path, PlannedPath):
         path = path.poses
     L, W, h, max_rows = ops.check_path(path, quats, keep, window, spacing, max_rows)
-    if clearance_radius is None:
-        raise ValueError("clearance_radius must be a finite number > 0, got None")
     r = ops.check_tour_radius(clearance_radius)
     cloud = _device_cloud(cloud, pts, "refine_path")
     dev = cloud.device
@@ -787,7 +738,7 @@ def refine_path(points_or_cloud_or_model, path, quats=None, clearance_radius=Non
                        leg_blocked=leg_blocked, n_open=int(hdr[5]), open_band=band)
 
 
-class ViewProposals:
+class ViewProposals(_Result):
     """What propose_views returns, ranked by what is left to see.  poses (V,3) f32 and quats (V,4) f32 wxyz on the device — they feed
     select_views(..., prop.poses, prop.quats, k) as they are; score (V,) int64: the summed weights inside the proposal's window
     of sectors; position_index (V,) int64 and heading (V,) int32: the position row and the sector the view looks along; all in rank
@@ -796,10 +747,6 @@ class ViewProposals:
     settings behind them."""
     __slots__ = ("poses", "quats", "score", "position_index", "heading", "hist", "open", "weights", "sectors", "hw", "tan_v", "min_dist",
                  "max_dist")
-
-    def __init__(self, **kw):
-        for k, v in kw.items():
-            setattr(self, k, v)
 
     @property
     def n_views(self):
@@ -850,10 +797,7 @@ def propose_views(points_or_cloud_or_model, positions, n_per_position=2, sectors
     cloud, pts = _clearance_cloud(m, "propose_views")
     given = dict(min_dist=min_dist, max_dist=max_dist, K=K, img_width=img_width, img_height=img_height)
     prior, mn, mx, Kh, iw, ih = _propose_camera(m, prior_log_odds, given)
-    try:
-        iw, ih, fx, fy = float(iw), float(ih), float(Kh[0]), float(Kh[4])
-    except (TypeError, ValueError):
-        iw = ih = fx = fy = float("nan")
+    iw, ih, fx, fy = (ops._float_or_nan(v) for v in (iw, ih, Kh[0], Kh[4]))
     if not all(math.isfinite(v) and v > 0.0 for v in (iw, ih, fx, fy)):
         raise ValueError(f"propose_views: img_width, img_height and the focal lengths K[0][0], K[1][1] must be finite numbers > 0, got "
                          f"{img_width!r}, {img_height!r}, {Kh[0]!r}, {Kh[4]!r}")
