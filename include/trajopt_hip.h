@@ -37,7 +37,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_view_histogram / tohip_view_headings (propose candidate views: per-position bearing histograms of what is left to
+/* (still 15) + tohip_occ_bytes / tohip_occ_init / tohip_occ_insert / tohip_occ_lookup / tohip_los_segments / tohip_los_rows (an
+ * occupancy bit grid and exact line-of-sight walks: the 'voxel' occlusion rows): new symbols only.
+ * (still 15) + tohip_view_histogram / tohip_view_headings (propose candidate views: per-position bearing histograms of what is left to
  * see, and the best headings of each): new symbols only.
  * (still 15) + tohip_path_bytes / tohip_path_refine (refine a planned walk: any-angle shortcuts and even waypoint spacing): new symbols
  * only.
@@ -1073,6 +1075,53 @@ int tohip_covmap_rehash(void *map, size_t map_bytes, int64_t capacity, const voi
 int tohip_covmap_export(void *map, size_t map_bytes, int64_t capacity, int64_t out_capacity, int64_t *keys, float *values,
                         float *centres, void *stream);
 int tohip_covmap_read_header(const void *map, int64_t *words_host, float *geometry_host, void *stream);
+
+/* ---- occupancy bit grid and exact line-of-sight walks ("Voxel line of sight") -------
+ * A dense grid of one bit per voxel, filled from any number of clouds, and an integer voxel traversal through it: "is B visible
+ * from A", and a third kind of occlusion bit row beside the hull's and the z-buffer's.
+ *
+ * Geometry (tohip_occ_geom, a HOST struct handed to every call; the library keeps no state): origin and resolution r > 0 finite,
+ * dims each in [1, 2048] with nx ny nz <= 2^31.  Buffer: tohip_occ_bytes(nx, ny, nz) device bytes (0 for bad dims), caller-owned,
+ * 8-byte aligned: a 256-byte header, then one 32-bit word per brick of 4 x 4 x 2 voxels.  Nothing public depends on the layout.
+ *
+ * Coordinate of a position, per axis: g = (p - origin) / r in f32 (correctly rounded: numpy.float32 gives the same value); IN RANGE
+ * iff g is finite and -2048 <= g < 4096 (the grid and an apron in which everything is free); q = (int) floorf(g * 256), the unit
+ * 1/256 voxel; voxel = q >> 8.
+ * tohip_occ_init: every voxel free.  tohip_occ_insert: each row of points (n, 3) f32 on the device whose coordinates are in range
+ * and whose voxel lies inside dims sets that voxel's bit (32-bit integer atomic OR); every other row is skipped and counted.  Bits
+ * are never cleared.  skipped_host (HOST, may be NULL): the number of skipped rows of this call — the call then synchronises.
+ * tohip_occ_lookup: ijk (m, 3) int32 voxel indices -> out (m) uint8, 0 outside dims.
+ *
+ * The walk from A to B (fixed-point triples, in range): D = B - A, s = sign D, m = |D|, v0 = A >> 8, e = B >> 8; per axis the
+ * distance to the next face n = (v+1) 256 - A for s > 0, A - v 256 for s < 0 (0 on a face: that step comes first).  It takes
+ * sum |e - v0| steps, each along the axis — among those with v_a != e_a — with the smallest n_a / m_a, compared exactly as
+ * n_a m_b < n_b m_a, ties to the lowest axis; then v_a += s_a and n_a += 256.  It visits v0 ... e.  A visited voxel is tested iff
+ * cheb(v, v0) >= start_skip and cheb(v, e) > end_skip; the ray is blocked iff a tested voxel inside dims is occupied.  Skips are
+ * in [0, 8192].
+ * tohip_los_segments: a, b (n_rays, 3) f32 world points on the device -> out (n_rays) uint8: 1 clear, 0 blocked, 2 an endpoint out
+ * of range.  tohip_los_rows: rows (n_wps, npad/32) int32 in the layout of tohip_occlusion_rows — bit i = packed position i of
+ * `packed` (tohip_pack_cloud), 1 iff tohip_cull_waypoints(normalize = 1) with this camera and these limits keeps the point for
+ * waypoint w (the same device functions: the same bit) and the ray from poses[w] to the point is not blocked; a ray with an
+ * endpoint out of range counts as clear; pad bits 0.  One launch, nothing read back.  1 <= n_wps <= 65535.  prune != 0 skips the
+ * 256-point tiles whose bounding sphere cannot pass the depth gate (never changes a bit).
+ * stats (DEVICE uint64 x 2, may be NULL, zero-filled by the caller): += rays walked, += voxels visited.
+ * Every argument check returns before anything is enqueued. */
+typedef struct tohip_occ_geom {
+    float origin[3];
+    float resolution;
+    int32_t dims[3];
+} tohip_occ_geom;
+size_t tohip_occ_bytes(int32_t nx, int32_t ny, int32_t nz);
+int tohip_occ_init(void *grid, size_t grid_bytes, const tohip_occ_geom *geom, void *stream);
+int tohip_occ_insert(void *grid, size_t grid_bytes, const tohip_occ_geom *geom, const float *points, int64_t n_points,
+                     int64_t *skipped_host, void *stream);
+int tohip_occ_lookup(const void *grid, size_t grid_bytes, const tohip_occ_geom *geom, const int32_t *ijk, int64_t m, uint8_t *out,
+                     void *stream);
+int tohip_los_segments(const void *grid, size_t grid_bytes, const tohip_occ_geom *geom, const float *a, const float *b, int64_t n_rays,
+                       int32_t start_skip, int32_t end_skip, uint8_t *out, uint64_t *stats, void *stream);
+int tohip_los_rows(const void *grid, size_t grid_bytes, const tohip_occ_geom *geom, const void *packed, int64_t n_points,
+                   const float *poses, const float *quats, int64_t n_wps, const tohip_camera *cam, float min_dist, float max_dist,
+                   int32_t start_skip, int32_t end_skip, int32_t prune, int32_t *rows, uint64_t *stats, void *stream);
 
 /* ---- optional per-kernel timing (bench.py's roofline leg) -----------------------------------------
  * When enabled, every launch of the big kernels is bracketed by hipEventRecord on its own stream.

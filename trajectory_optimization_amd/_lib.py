@@ -68,6 +68,11 @@ class AdamGroup(ctypes.Structure):
                 ("beta2", c_f), ("eps", c_f), ("step", c_i32)]
 
 
+class OccGeom(ctypes.Structure):
+    """struct tohip_occ_geom (include/trajopt_hip.h)."""
+    _fields_ = [("origin", c_f * 3), ("resolution", c_f), ("dims", c_i32 * 3)]
+
+
 ADAM_MAX_GROUPS = 8  # TOHIP_ADAM_MAX_GROUPS
 
 # name -> (restype, argtypes); every symbol include/trajopt_hip.h declares
@@ -196,6 +201,13 @@ SIGNATURES = {
     "tohip_covmap_rehash": (ctypes.c_int, [c_vp, c_sz, c_i64, c_vp, c_sz, c_i64, ctypes.POINTER(c_i64), c_vp]),
     "tohip_covmap_export": (ctypes.c_int, [c_vp, c_sz, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "tohip_covmap_read_header": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_f), c_vp]),
+    "tohip_occ_bytes": (c_sz, [c_i32, c_i32, c_i32]),
+    "tohip_occ_init": (ctypes.c_int, [c_vp, c_sz, ctypes.POINTER(OccGeom), c_vp]),
+    "tohip_occ_insert": (ctypes.c_int, [c_vp, c_sz, ctypes.POINTER(OccGeom), c_vp, c_i64, ctypes.POINTER(c_i64), c_vp]),
+    "tohip_occ_lookup": (ctypes.c_int, [c_vp, c_sz, ctypes.POINTER(OccGeom), c_vp, c_i64, c_vp, c_vp]),
+    "tohip_los_segments": (ctypes.c_int, [c_vp, c_sz, ctypes.POINTER(OccGeom), c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "tohip_los_rows": (ctypes.c_int, [c_vp, c_sz, ctypes.POINTER(OccGeom), c_vp, c_i64, c_vp, c_vp, c_i64, ctypes.POINTER(Camera), c_f, c_f,
+                                       c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "tohip_clearance_workspace_bytes": (c_sz, [c_i64]),
     "tohip_clearance": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_f, c_f, c_vp, c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_sz, c_vp]),
     "tohip_traj_clearance_scratch_bytes": (c_sz, [c_i64, c_i64]),

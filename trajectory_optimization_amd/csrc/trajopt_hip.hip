@@ -16,6 +16,7 @@
 #include "path_kernels.hip"
 #include "propose_kernels.hip"
 #include "covmap_kernels.hip"
+#include "occupancy_kernels.hip"
 #include "loss_kernels.hip"
 #include "ingest_kernels.hip"
 #include "render_kernels.hip"

@@ -611,6 +611,17 @@ def _adopt_cloud(points, cloud, device, sort, model_cls):
     return cloud, cloud.points
 
 
+def _occlusion_grid(occlusion, grid, voxel, cloud):
+    """The occupancy grid of a model with occlusion='voxel': `grid` (an ops.OccupancyGrid on the cloud's device: the map so far, walls
+    of earlier clouds included) or, for None, one built here from the cloud's own points at resolution `voxel`.  None for every other
+    method, which takes no grid."""
+    if occlusion != "voxel":
+        if grid is not None:
+            raise ValueError(f"occlusion_grid needs occlusion='voxel', got occlusion={occlusion!r}")
+        return None
+    return ops.OccupancyGrid.from_points(cloud, resolution=voxel) if grid is None else ops.check_occlusion_grid(grid, cloud)
+
+
 class ModelPose(nn.Module):
     """Single camera pose optimisation model (/root/reference/src/model.py:65-127).
 
@@ -620,6 +631,8 @@ class ModelPose(nn.Module):
     /root/reference/src/pc_processor.py:158-187; observations[n] = dist_mask * fov_mask * bit[n].  The row carries no gradient and is
     rebuilt on every `occlusion_refresh_every`-th forward (ModelTraj's policy).  forward(hpr=True) keeps the reference's world-frame
     HPR from the world origin (model.py:112-115) and cannot be combined with `occlusion`.
+    `occlusion='voxel'` walks an occupancy grid from the camera to each kept point instead (ops.OccupancyGrid: `occlusion_grid=`, the
+    map so far, or a grid of the model's own points at `occlusion_voxel` metres, built on construction).
     """
 
     def __init__(self,
@@ -630,7 +643,7 @@ class ModelPose(nn.Module):
                  img_width, img_height,
                  min_dist=1.0, max_dist=5.0,
                  device=torch.device('cuda:0'), *, cloud=None, fast_adam=False, occlusion=None, occlusion_limits=(1.0, 15.0),
-                 occlusion_refresh_every=1):
+                 occlusion_refresh_every=1, occlusion_grid=None, occlusion_voxel=0.1):
         super().__init__()
         assert trans0.size() == torch.Size([1, 3])
         assert q0.size() == torch.Size([1, 4])
@@ -663,9 +676,8 @@ class ModelPose(nn.Module):
         self._cam = ops.Camera(self.K, self.img_width, self.img_height, min_dist, max_dist, self.eps)
         self._ws = ops.PoseWorkspace(self._cloud)
         self._occlusion_mask, self._occlusion_key = None, None
-        if occlusion not in (None, "hpr", "zbuffer"):
-            raise ValueError("occlusion must be None, 'hpr' or 'zbuffer'")
-        self._occlusion, self._occlusion_limits = occlusion, occlusion_limits
+        self._occlusion, self._occlusion_limits = ops.check_occlusion(occlusion), occlusion_limits
+        self._occlusion_grid, self._occlusion_voxel = _occlusion_grid(occlusion, occlusion_grid, occlusion_voxel, self._cloud), occlusion_voxel
         # The pose's occlusion row is piecewise constant in the pose and carries no gradient; building it (a hard cull and a convex
         # hull, or a z-buffer) costs many plain steps.  Rebuilt on the first forward and on every occlusion_refresh_every-th one after
         # (k = 1: every forward), reused in between; refresh_occlusion() forces a rebuild at the next forward.
@@ -690,6 +702,9 @@ class ModelPose(nn.Module):
         kw.setdefault("occlusion", other._occlusion)
         kw.setdefault("occlusion_limits", other._occlusion_limits)
         kw.setdefault("occlusion_refresh_every", other.occlusion_refresh_every)
+        if kw["occlusion"] == "voxel":   # (the same grid object, not one more built from the same points)
+            kw.setdefault("occlusion_grid", other._occlusion_grid)
+            kw.setdefault("occlusion_voxel", other._occlusion_voxel)
         return cls(other._cloud, trans0, q0, other.K, other.img_width, other.img_height, **kw)
 
     def refresh_occlusion(self):
@@ -719,7 +734,7 @@ class ModelPose(nn.Module):
     def _build_occlusion_rows(self, trans, quat):
         """(B, npad/32) occlusion bit rows of B poses of this camera over this cloud, in one batched pass (B = 1 for the model's own)."""
         return ops.occlusion_bits(self._cloud, self.points, trans, quat, self._cam, self._occlusion_limits[0], self._occlusion_limits[1],
-                                  self._occlusion)
+                                  self._occlusion, grid=self._occlusion_grid)
 
     def _hpr_mask(self):
         """HPR of the WORLD-frame cloud seen from the world origin (model.py:114): pose independent, so it is computed once per
@@ -782,7 +797,9 @@ class ModelTraj(nn.Module):
     `occlusion='hpr'|'zbuffer'` makes the reward occlusion-aware per waypoint — the reference's TODO
     (/root/reference/src/tools.py:61-62, /root/reference/src/model.py:210): each waypoint's camera-frame cloud goes
     through the hard pipeline of /root/reference/src/pc_processor.py:171-178 (frustum cull with `occlusion_limits`,
-    then HPR from the camera centre) and the points it hides get p = 0 for that waypoint;
+    then HPR from the camera centre) and the points it hides get p = 0 for that waypoint; `occlusion='voxel'` keeps the cull and
+    walks an occupancy grid from the camera to each kept point instead (ops.OccupancyGrid: `occlusion_grid=`, the map so far — walls
+    of earlier clouds included — or a grid of the model's own points at `occlusion_voxel` metres, built on construction);
     `prior_log_odds=` an (N,) tensor of what is already known of the map (OctoMap's accumulated log-odds, >= 0, in the caller's point
     order): rewards become sigmoid(lo_sum + prior) — see the prior_log_odds property and coverage_log_odds().  An ops.CoverageMap is
     accepted in its place: the prior is its lookup over this cloud (commit_coverage folds a plan back into it).
@@ -799,7 +816,8 @@ class ModelTraj(nn.Module):
                  device=torch.device('cuda'),
                  *, rig=None, shard=None, dense=False, occlusion=None, occlusion_limits=(1.0, 15.0), occlusion_refresh_every=1,
                  occlusion_refresh_tol=None, occlusion_check_every=5, n_points_global=None, cloud=None, fast_adam=False,
-                 clearance_radius=None, clearance_weight=0.0, prior_log_odds=None, clearance_mode='waypoints'):
+                 clearance_radius=None, clearance_weight=0.0, prior_log_odds=None, clearance_mode='waypoints', occlusion_grid=None,
+                 occlusion_voxel=0.1):
         super().__init__()
         # the clearance term (clearance_kernels.hip): weight x sum over ALL waypoints of (r - d)^2, d = the distance to the nearest
         # cloud point within r — it keeps the path off the cloud; weight 0 (the default): off, the reference's criterion as it is.
@@ -867,9 +885,8 @@ class ModelTraj(nn.Module):
         self._rig = ops.CameraRig(rig[0], rig[1], self.device) if rig is not None else None
         self._shard = shard if shard is not None else _NoShard()
         self._flags = ops.DENSE if dense else 0  # dense: evaluate every pair (results are bitwise the same)
-        if occlusion not in (None, "hpr", "zbuffer"):
-            raise ValueError("occlusion must be None, 'hpr' or 'zbuffer'")
-        self._occlusion, self._occlusion_limits = occlusion, occlusion_limits
+        self._occlusion, self._occlusion_limits = ops.check_occlusion(occlusion), occlusion_limits
+        self._occlusion_grid, self._occlusion_voxel = _occlusion_grid(occlusion, occlusion_grid, occlusion_voxel, self._cloud), occlusion_voxel
         self._prior = None   # ops.LogOddsPrior (the property below)
         self.prior_log_odds = prior_log_odds
         # The occlusion masks are piecewise constant in the poses (a point is hidden from a waypoint or it is not) and carry no
@@ -995,6 +1012,9 @@ class ModelTraj(nn.Module):
         kw.setdefault("device", other.device)
         kw.setdefault("min_dist", other.pc_clip_limits[0])
         kw.setdefault("max_dist", other.pc_clip_limits[1])
+        if kw.get("occlusion") == "voxel" and other._occlusion_grid is not None:   # (the same grid object, not one more of the same points)
+            kw.setdefault("occlusion_grid", other._occlusion_grid)
+            kw.setdefault("occlusion_voxel", other._occlusion_voxel)
         return cls(other._cloud, wps_poses, wps_quats, other.K, other.img_width, other.img_height, **kw)
 
     @property
@@ -1084,7 +1104,7 @@ class ModelTraj(nn.Module):
             vt = (ps[:, None, :] + torch.einsum("wij,cj->wci", R, lc)).reshape(-1, 3)
             ps, qs = vt.contiguous(), vq.contiguous()
         return ops.occlusion_bits(self._cloud, self.points, ps, qs, self._cam, self._occlusion_limits[0],
-                                  self._occlusion_limits[1], self._occlusion)
+                                  self._occlusion_limits[1], self._occlusion, grid=self._occlusion_grid)
 
     def _needs_split_step(self, prior=True):
         """Whether the visibility step goes through the separate calls (ops.WaypointShardStep / PointShardStep) instead of the

@@ -703,6 +703,192 @@ class CoverageMap:
         return list(w), list(g)
 
 
+OCC_MAX_DIM = 2048        # voxels per axis of an occupancy grid
+OCC_MAX_VOXELS = 1 << 31
+LOS_MAX_SKIP = 8192
+OCCLUSION_METHODS = (None, "hpr", "zbuffer", "voxel")
+
+
+def check_occlusion(occlusion):
+    """The models' and select_views' occlusion= value: None, 'hpr', 'zbuffer' or 'voxel'; ValueError otherwise."""
+    if occlusion not in OCCLUSION_METHODS:
+        raise ValueError(f"occlusion must be None, 'hpr' or 'zbuffer', or 'voxel', got {occlusion!r}")
+    return occlusion
+
+
+def check_los_skip(skip):
+    """skip = (start_skip, end_skip): two integers in [0, LOS_MAX_SKIP] -> (int, int); ValueError otherwise."""
+    try:
+        s = tuple(skip)
+    except TypeError:
+        s = ()
+    if len(s) != 2 or not all(_is_int(v) and 0 <= v <= LOS_MAX_SKIP for v in s):
+        raise ValueError(f"skip must be two integers (start_skip, end_skip) in [0, {LOS_MAX_SKIP}], got {skip!r}")
+    return int(s[0]), int(s[1])
+
+
+def check_los(origin, resolution, dims, skip=(1, 1), a=None, b=None):
+    """An occupancy grid's settings and a segment query's arguments, by name: origin 3 finite numbers, resolution a finite number > 0,
+    dims three integers in [1, OCC_MAX_DIM] with at most 2^31 voxels, skip two integers in [0, LOS_MAX_SKIP], a and b (given
+    together) floating tensors of one shape (R,3) on one device -> (origin (3,) float32 array, resolution as a float32-exact float,
+    dims (nx, ny, nz), skip); ValueError otherwise.  Needs no GPU."""
+    o, r, _, _ = check_covmap(origin, resolution)
+    try:
+        d = tuple(dims)
+    except TypeError:
+        d = ()
+    if len(d) != 3 or not all(_is_int(v) and 1 <= v <= OCC_MAX_DIM for v in d):
+        raise ValueError(f"dims must be three integers in [1, {OCC_MAX_DIM}], got {dims!r}")
+    d = tuple(int(v) for v in d)
+    if d[0] * d[1] * d[2] > OCC_MAX_VOXELS:
+        raise ValueError(f"dims must hold at most 2^31 voxels, got {d} = {d[0] * d[1] * d[2]}")
+    skip = check_los_skip(skip)
+    if (a is None) != (b is None):
+        raise ValueError("a and b must be given together")
+    if a is not None:
+        _check_float_rows(a, "a", "an (R,3) floating-point tensor", 3)
+        _check_float_rows(b, "b", f"an (R,3) floating-point tensor with a's {a.shape[0]} rows", 3, rows=a.shape[0])
+        if a.device != b.device:
+            raise ValueError(f"a and b must live on one device, got {a.device} and {b.device}")
+    return o, r, d, skip
+
+
+def occupancy_extent(lo, hi, resolution, margin):
+    """from_points' geometry from a cloud's f64 bounds -> (origin (3,) f32, dims): origin = r floor(lo / r) - margin r computed in
+    f64 and cast to f32, dims = the voxels from there to hi plus the margin; ValueError names an extent the grid cannot hold."""
+    r = _float_or_nan(resolution, np.float32)
+    if not (np.isfinite(r) and r > 0.0):
+        raise ValueError(f"resolution must be a finite number > 0, got {resolution!r}")
+    if not _is_int(margin) or not 0 <= margin <= OCC_MAX_DIM:
+        raise ValueError(f"margin must be an integer in [0, {OCC_MAX_DIM}], got {margin!r}")
+    lo, hi = np.asarray(lo, dtype=np.float64).reshape(-1), np.asarray(hi, dtype=np.float64).reshape(-1)
+    if lo.shape != (3,) or hi.shape != (3,) or not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise ValueError("OccupancyGrid.from_points: the points have no finite bounding box")
+    origin = (r * np.floor(lo / r) - margin * r).astype(np.float32)
+    # (+ 2: the f32 origin and the f32 division may move a point on the far face by a voxel)
+    ext = np.floor((hi - origin.astype(np.float64)) / r) + 2 + margin
+    if (ext > OCC_MAX_DIM).any():
+        raise ValueError(f"OccupancyGrid.from_points: an extent of {tuple(int(v) for v in ext)} voxels exceeds {OCC_MAX_DIM} per axis; "
+                         "use a coarser resolution")
+    dims = tuple(int(max(v, 1)) for v in ext)
+    if dims[0] * dims[1] * dims[2] > OCC_MAX_VOXELS:
+        raise ValueError(f"OccupancyGrid.from_points: {dims} holds more than 2^31 voxels; use a coarser resolution")
+    return origin, dims
+
+
+class OccupancyGrid:
+    """A dense occupancy bit grid on the device (occupancy_kernels.hip), filled from any number of clouds: voxel
+    (i, j, k) is origin + [i, i+1) x [j, j+1) x [k, k+1) resolution, the index floor((x - origin) / resolution) in float32.  Around
+    the grid lies an apron (indices -2048 .. 4095 per axis) in which everything is free; a position beyond it is out of range.
+    Bits are only ever set: two inserts equal one insert of both clouds, in any row order."""
+
+    def __init__(self, origin=(0.0, 0.0, 0.0), resolution=0.1, dims=(64, 64, 64), device="cuda"):
+        self.origin, self.resolution, self.dims, _ = check_los(origin, resolution, dims)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"an OccupancyGrid lives on a HIP device (got {self.device}); there is no CPU fallback")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        L = _lib.lib()
+        self.geom = _lib.OccGeom((ctypes.c_float * 3)(*self.origin.tolist()), self.resolution, (ctypes.c_int32 * 3)(*self.dims))
+        nbytes = L.tohip_occ_bytes(*self.dims)
+        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.skipped = 0   # rows skipped over every insert so far
+        with torch.cuda.device(self.device):
+            check(L.tohip_occ_init(*self._sizes(), stream_ptr()), "tohip_occ_init")
+
+    @classmethod
+    def from_points(cls, points_or_cloud, resolution=0.1, margin=2):
+        """The grid around a cloud — (N,3) points, a PackedCloud or a ModelTraj — with `margin` free voxels on every side, the cloud
+        inserted.  The origin is r floor(min / r) - margin r in f64, cast to f32.  One host read of the bounds."""
+        m = _model_cloud(points_or_cloud, "OccupancyGrid.from_points")
+        pts = m.points if isinstance(m, PackedCloud) else m
+        if not torch.is_tensor(pts) or not pts.is_floating_point() or pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] == 0:
+            raise ValueError("OccupancyGrid.from_points: points must be an (N,3) floating-point tensor with N > 0, a PackedCloud or a "
+                             f"ModelTraj, got {tuple(pts.shape) if torch.is_tensor(pts) else type(pts).__name__}")
+        _require_cuda(pts, "points")
+        p = pts.detach()
+        fin = torch.where(torch.isfinite(p), p, torch.full_like(p, float("nan")))
+        big = torch.finfo(p.dtype).max
+        lo = torch.nan_to_num(fin, nan=big).amin(dim=0).double().cpu().numpy()
+        hi = torch.nan_to_num(fin, nan=-big).amax(dim=0).double().cpu().numpy()
+        if (lo > hi).any():
+            raise ValueError("OccupancyGrid.from_points: the points have no finite bounding box")
+        origin, dims = occupancy_extent(lo, hi, resolution, margin)
+        g = cls(origin, resolution, dims, device=pts.device)
+        g.insert(pts)
+        return g
+
+    def _sizes(self):
+        return ptr(self.buf), self.buf.numel(), ctypes.byref(self.geom)
+
+    def insert(self, points_or_cloud):
+        """Set the voxel of every row; -> the number of rows skipped (a coordinate out of range or not finite, or a voxel outside
+        dims).  One synchronisation (that count)."""
+        pts = covmap_points(points_or_cloud, self.device, "OccupancyGrid.insert")
+        skipped = ctypes.c_int64(0)
+        with torch.cuda.device(self.device):
+            check(_lib.lib().tohip_occ_insert(*self._sizes(), ptr(pts), pts.shape[0], ctypes.byref(skipped), stream_ptr()), "tohip_occ_insert")
+        self.skipped += int(skipped.value)
+        return int(skipped.value)
+
+    def lookup(self, ijk):
+        """(M,3) integer voxel indices -> (M,) uint8, 1 = occupied, 0 outside dims."""
+        if not torch.is_tensor(ijk) or ijk.is_floating_point() or ijk.dtype == torch.bool or ijk.dim() != 2 or ijk.shape[1] != 3:
+            raise ValueError(f"ijk must be an (M,3) integer tensor, got {tuple(ijk.shape) if torch.is_tensor(ijk) else type(ijk).__name__}")
+        q = ijk.to(device=self.device, dtype=torch.int32).contiguous()
+        out = torch.empty(q.shape[0], dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            check(_lib.lib().tohip_occ_lookup(*self._sizes(), ptr(q), q.shape[0], ptr(out), stream_ptr()), "tohip_occ_lookup")
+        return out
+
+    def dense(self):
+        """The grid as a bool (nx, ny, nz) tensor, through lookup: for tests and small grids."""
+        nx, ny, nz = self.dims
+        ijk = torch.stack(torch.meshgrid(torch.arange(nx), torch.arange(ny), torch.arange(nz), indexing="ij"), dim=-1).reshape(-1, 3)
+        return self.lookup(ijk.to(self.device)).view(nx, ny, nz).bool()
+
+    def line_of_sight(self, a, b, skip=(1, 1), stats=None):
+        """(R,) uint8 for the segments a[i] -> b[i] of world points: 1 clear, 0 blocked, 2 an endpoint out of range.  stats: a
+        zero-filled (2,) int64 device tensor that receives (rays walked, voxels visited), or None."""
+        _, _, _, (ss, es) = check_los(self.origin, self.resolution, self.dims, skip, a, b)
+        a, b = covmap_points(a, self.device, "line_of_sight"), covmap_points(b, self.device, "line_of_sight")
+        out = torch.empty(a.shape[0], dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            check(_lib.lib().tohip_los_segments(*self._sizes(), ptr(a), ptr(b), a.shape[0], ss, es, ptr(out), ptr(stats), stream_ptr()),
+                  "tohip_los_segments")
+        return out
+
+
+def check_occlusion_grid(grid, cloud):
+    """occlusion_bits(method='voxel')'s grid: an OccupancyGrid on the cloud's device; ValueError otherwise."""
+    if not isinstance(grid, OccupancyGrid):
+        raise ValueError(f"method='voxel' needs grid= an OccupancyGrid, got {type(grid).__name__}")
+    if grid.device != cloud.device:
+        raise ValueError(f"the grid lives on {grid.device}, the cloud on {cloud.device}")
+    return grid
+
+
+def los_rows(cloud, poses, quats, cam, min_dist, max_dist, grid, skip=(1, 1), prune=True, rows=None, stats=None):
+    """The 'voxel' occlusion bit rows (tohip_los_rows): (W, npad/32) int32, bit i = packed position i, 1 iff cull_waypoints keeps the
+    point for waypoint w and the ray from poses[w] to it is not blocked in `grid`.  One launch per 65 535 waypoints, nothing read
+    back.  prune=False tests every point (the same bits)."""
+    check_occlusion_grid(grid, cloud)
+    ss, es = check_los_skip(skip)
+    dev, W = cloud.device, poses.shape[0]
+    p = poses.detach().to(device=dev, dtype=torch.float32).contiguous()
+    q = quats.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if rows is None:
+        rows = torch.empty((W, cloud.npad // 32), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    for w0 in range(0, W, 65535):
+        w1 = min(W, w0 + 65535)
+        with torch.cuda.device(dev):
+            check(L.tohip_los_rows(*grid._sizes(), ptr(cloud.blob), cloud.n, ptr(p[w0:w1]), ptr(q[w0:w1]), w1 - w0, cam.ref(), float(min_dist),
+                                   float(max_dist), ss, es, int(bool(prune)), ptr(rows[w0:w1]), ptr(stats), stream_ptr()), "tohip_los_rows")
+    return rows
+
+
 def team_loss(poses, poses0, n_members, smoothness_weight, traj_length_weight, eps, scalars, clearance_weight=0.0, clr_terms=None):
     """tohip_team_loss: criterion's terms of every member (poses / poses0: the members' (B W, 3) rows end to end) behind the team's
     `scalars` -> (member_terms (B, 8): [0] vis [1] l2 [2] length [3] smooth [5] clearance; total (1): the team total; reg (B W, 3): the
@@ -1493,11 +1679,15 @@ HPR_BATCH_POINTS = 32_000_000  # points per batched hull pass (workspace ~0.12 K
 OCCLUSION_CULL_BYTES = 4 << 30  # budget for the cull stage's worst-case buffers (16 B per point and waypoint): waypoints are chunked
 
 
-def occlusion_bits(cloud, points, poses, quats, cam, min_dist, max_dist, method="hpr"):
+def occlusion_bits(cloud, points, poses, quats, cam, min_dist, max_dist, method="hpr", grid=None, skip=(1, 1)):
     """(W, npad/32) int32 occlusion bit rows for the given waypoints: the hard per-camera pipeline of
     /root/reference/src/pc_processor.py:158-187 (exact transform -> hard frustum cull -> HPR from the camera
     centre, or the z-buffer splat for method="zbuffer") turned into the bit layout the kernels read.
-    The waypoints go through in chunks sized by OCCLUSION_CULL_BYTES (the cull stage sizes its outputs for the worst case)."""
+    The waypoints go through in chunks sized by OCCLUSION_CULL_BYTES (the cull stage sizes its outputs for the worst case).
+    method="voxel": the same cull, then a line-of-sight walk from the camera to each kept point through `grid` (an OccupancyGrid;
+    `skip`: see los_rows) — the cloud's own packed points, one launch, no host synchronisation."""
+    if method == "voxel":
+        return los_rows(cloud, poses, quats, cam, min_dist, max_dist, grid, skip)
     dev = cloud.device
     W = poses.shape[0]
     rows = torch.empty((W, cloud.npad // 32), dtype=torch.int32, device=dev)

@@ -476,6 +476,8 @@ def optimize_poses(models, n_opt_steps=100, lr_pose=0.1, lr_quat=0.1, hpr=False,
         if (m._occlusion != m0._occlusion or tuple(m._occlusion_limits) != tuple(m0._occlusion_limits) or
                 m.occlusion_refresh_every != m0.occlusion_refresh_every):
             raise ValueError("optimize_poses: the models must share occlusion, occlusion_limits and occlusion_refresh_every")
+        if m._occlusion_grid is not m0._occlusion_grid:
+            raise ValueError("optimize_poses: the models must share one occlusion_grid (ModelPose.sharing_cloud_of hands it on)")
         # what the kernels read is the packed cloud: the same object, or one of equal size over equal rows (the shapes are compared
         # first — a model on a slice of the same tensor shares its data pointer)
         c, c0 = m._cloud, m0._cloud

@@ -593,3 +593,89 @@ def propose_headings_ref(hist, hw, n_per, sep=None, min_score=0):
             d = np.abs(hs - h)
             free &= np.minimum(d, S - d) > sep
     return heading, score
+
+
+# ---- the occupancy grid and the line-of-sight walk restated in numpy: what occupancy_kernels.hip must give, bit for bit --
+OCC_MAX_DIM = 2048
+OCC_MAX_VOXELS = 1 << 31
+LOS_MAX_SKIP = 8192
+
+
+def occ_fixed(points, origin, resolution):
+    """Fixed-point grid coordinates of world points -> (q (N,3) int64 in 1/256 voxel, ok (N,) bool): per axis g = fl(fl(p - origin) /
+    r) in f32, in range iff -2048 <= g < 4096 (false for NaN and inf), q = floor(g * 256) (exact); q = 0 on an axis out of range."""
+    f32 = np.float32
+    P = np.asarray(points, dtype=f32).reshape(-1, 3)
+    o, r = np.asarray(origin, dtype=f32).reshape(3), f32(resolution)
+    with np.errstate(all="ignore"):
+        g = ((P - o[None, :]).astype(f32) / r).astype(f32)
+        ok = (g >= f32(-2048)) & (g < f32(4096))
+        q = np.floor(np.where(ok, g, f32(0)) * f32(256)).astype(np.int64)
+    return q, ok.all(axis=1)
+
+
+def occupancy_ref(points, origin, resolution, dims, occ=None):
+    """insert(points) -> (occ (nx,ny,nz) bool, skipped): a row in range whose voxel q >> 8 lies inside dims sets that voxel; every
+    other row is counted.  occ: the grid so far (not modified) or None for an empty one."""
+    dims = tuple(int(d) for d in dims)
+    out = np.zeros(dims, dtype=bool) if occ is None else np.array(occ, dtype=bool)
+    q, ok = occ_fixed(points, origin, resolution)
+    v = q >> 8
+    inside = ok & ((v >= 0) & (v < np.asarray(dims)[None, :])).all(axis=1)
+    out[v[inside, 0], v[inside, 1], v[inside, 2]] = True
+    return out, int((~inside).sum())
+
+
+def los_fixed(A, B, occ, skip=(1, 1), trace=False):
+    """The walk from A to B, (R,3) integer fixed-point triples (both in range), through occ (nx,ny,nz) bool -> blocked (R,) bool.
+    v = A >> 8, e = B >> 8, n = the distance to the next face ((v+1) 256 - A going up, A - v 256 going down); sum |e - v| steps, each
+    along the axis — among those with v_a != e_a — of the smallest n_a / m_a (n_a m_b < n_b m_a in int64, ties to the lowest axis);
+    a visited voxel is tested iff cheb(v, v0) >= skip[0] and cheb(v, e) > skip[1]; blocked iff a tested voxel inside dims is
+    occupied.  Vectorised over the rays still walking.  trace: every ray walks to its end and (blocked, visited) is returned,
+    visited[r] the list of ray r's voxels v0 .. e."""
+    A, B = np.asarray(A, dtype=np.int64).reshape(-1, 3), np.asarray(B, dtype=np.int64).reshape(-1, 3)
+    occ = np.asarray(occ, dtype=bool)
+    dims = np.asarray(occ.shape, dtype=np.int64)
+    ss, es = int(skip[0]), int(skip[1])
+    R = len(A)
+    D = B - A
+    s, m = np.sign(D), np.abs(D)
+    v0, e = A >> 8, B >> 8
+    v = v0.copy()
+    n = np.where(s > 0, (v + 1) * 256 - A, A - v * 256)
+    blocked = np.zeros(R, dtype=bool)
+    visited = [[] for _ in range(R)] if trace else None
+    idx = np.arange(R)
+    while len(idx):
+        vi = v[idx]
+        if trace:
+            for k, r in enumerate(idx):
+                visited[r].append(tuple(int(c) for c in vi[k]))
+        tested = (np.abs(vi - v0[idx]).max(axis=1) >= ss) & (np.abs(vi - e[idx]).max(axis=1) > es)
+        t = tested & ((vi >= 0) & (vi < dims[None, :])).all(axis=1)
+        hit = np.zeros(len(idx), dtype=bool)
+        hit[t] = occ[vi[t, 0], vi[t, 1], vi[t, 2]]
+        blocked[idx[hit]] = True
+        idx = idx[(trace | ~hit) & (vi != e[idx]).any(axis=1)]
+        if not len(idx):
+            break
+        act, ni, mi = v[idx] != e[idx], n[idx], m[idx]
+        best = np.full(len(idx), -1, dtype=np.int64)
+        nb, mb = np.zeros(len(idx), dtype=np.int64), np.ones(len(idx), dtype=np.int64)
+        for a in range(3):
+            take = act[:, a] & ((best < 0) | (ni[:, a] * mb < nb * mi[:, a]))
+            best = np.where(take, a, best)
+            nb, mb = np.where(take, ni[:, a], nb), np.where(take, mi[:, a], mb)
+        v[idx, best] += s[idx, best]
+        n[idx, best] += 256
+    return (blocked, visited) if trace else blocked
+
+
+def los_ref(a, b, origin, resolution, occ, skip=(1, 1)):
+    """line_of_sight(a, b) of world points (R,3) -> (R,) uint8: 1 clear, 0 blocked, 2 an endpoint out of range."""
+    qa, oka = occ_fixed(a, origin, resolution)
+    qb, okb = occ_fixed(b, origin, resolution)
+    ok = oka & okb
+    out = np.full(len(qa), 2, dtype=np.uint8)
+    out[ok] = 1 - los_fixed(qa[ok], qb[ok], occ, skip).astype(np.uint8)
+    return out

@@ -220,6 +220,31 @@ def coverage_map(origin=(0.0, 0.0, 0.0), resolution=0.1, clamp_max=None, capacit
     return ops.CoverageMap(origin, resolution, clamp_max=clamp_max, capacity=capacity, device=device)
 
 
+def occupancy_grid(points_or_cloud=None, resolution=0.1, margin=2, origin=None, dims=None, device=torch.device('cuda')):
+    """An ops.OccupancyGrid: the dense occupancy bit grid the 'voxel' occlusion method and line_of_sight walk.  With
+    points — (N,3) on the device, a PackedCloud or a ModelTraj — the grid around them with `margin` free voxels on every side, the
+    points inserted; with origin and dims instead, an empty grid of that box.  grid.insert(more_points) adds any later cloud: a wall
+    scanned two messages ago keeps occluding."""
+    if points_or_cloud is not None:
+        if origin is not None or dims is not None:
+            raise ValueError("occupancy_grid: give points (the box is theirs) or origin and dims, not both")
+        return ops.OccupancyGrid.from_points(points_or_cloud, resolution=resolution, margin=margin)
+    if origin is None or dims is None:
+        raise ValueError("occupancy_grid: without points both origin and dims are needed")
+    return ops.OccupancyGrid(origin, resolution, dims, device=device)
+
+
+def line_of_sight(grid, a, b, skip=(1, 1)):
+    """Is b[i] visible from a[i]?  a, b (R,3) world points on the grid's device -> (R,) uint8: 1 clear, 0 blocked, 2 when an endpoint
+    lies beyond the grid's apron (or is not finite).  An exact integer voxel walk (ops.OccupancyGrid): the same bits in every run.
+    skip = (start_skip, end_skip): voxels within start_skip - 1 (Chebyshev) of a's voxel and within end_skip of b's are not tested
+    — the default leaves out a's own voxel and the 3 x 3 x 3 block around b, so a surface point is not hidden by its own patch; a wall
+    seen at a grazing angle still hides its far parts."""
+    if not isinstance(grid, ops.OccupancyGrid):
+        raise ValueError(f"line_of_sight: grid must be an ops.OccupancyGrid, got {type(grid).__name__}")
+    return grid.line_of_sight(a, b, skip)
+
+
 class _Result:
     """What the result classes share: the keyword constructor; each names its fields in its own __slots__."""
     __slots__ = ()
@@ -243,20 +268,26 @@ class ViewSelection(_Result):
         return int(self.order.shape[0])
 
 
-def _views_setup(model_or_cloud, prior_log_odds, occlusion, kw):
-    """select_views' first argument resolved -> dict(cloud, cam, rig, flags, prior, occlusion, limits); cloud / prior may still be
-    what the caller gave (points / a tensor): they are packed after every check has passed."""
+def _views_setup(model_or_cloud, prior_log_odds, occlusion, kw, occlusion_grid=None, occlusion_voxel=0.1):
+    """select_views' first argument resolved -> dict(cloud, cam, rig, flags, prior, occlusion, limits, grid, voxel); cloud / prior
+    may still be what the caller gave (points / a tensor): they are packed after every check has passed (and, for
+    occlusion='voxel' without a grid, the grid built from the packed cloud's points)."""
     m = model_or_cloud
     if ops._model_cloud(m, "select_views") is not m:   # a ModelTraj: its own settings, nothing to override
         if kw:
             raise ValueError(f"select_views: {sorted(kw)} belong to the call with points; a ModelTraj brings its own camera and rig")
         if occlusion is not None and occlusion != m._occlusion:
             raise ValueError(f"select_views: occlusion={occlusion!r} given, the model has {m._occlusion!r}")
+        own_grid = getattr(m, "_occlusion_grid", None)
+        if occlusion_grid is not None and occlusion_grid is not own_grid:
+            raise ValueError("select_views: occlusion_grid given, the model brings its own (occlusion_grid= of its constructor)")
         prior = m._prior if prior_log_odds is None else ops.resolve_prior(prior_log_odds, m._cloud)
         return dict(cloud=m._cloud, cam=m._cam, rig=m._rig, flags=m._flags, prior=prior, occlusion=m._occlusion,
-                    limits=m._occlusion_limits)
-    if occlusion not in (None, "hpr", "zbuffer"):
-        raise ValueError("occlusion must be None, 'hpr' or 'zbuffer'")
+                    limits=m._occlusion_limits, grid=own_grid, voxel=getattr(m, "_occlusion_voxel", 0.1))
+    ops.check_occlusion(occlusion)
+    if occlusion_grid is not None and (occlusion != "voxel" or not isinstance(occlusion_grid, ops.OccupancyGrid)):
+        raise ValueError(f"select_views: occlusion_grid must be an ops.OccupancyGrid and needs occlusion='voxel', got "
+                         f"{type(occlusion_grid).__name__} with occlusion={occlusion!r}")
     allowed = {"intrins", "img_width", "img_height", "min_dist", "max_dist", "rig", "dense", "occlusion_limits"}
     if set(kw) - allowed:
         raise ValueError(f"select_views: unknown keyword(s) {sorted(set(kw) - allowed)}")
@@ -277,11 +308,11 @@ def _views_setup(model_or_cloud, prior_log_odds, occlusion, kw):
         ops.check_prior(prior_log_odds, n)
     cam = ops.Camera(kw["intrins"], kw["img_width"], kw["img_height"], kw.get("min_dist", 1.0), kw.get("max_dist", 5.0))
     return dict(cloud=m, cam=cam, rig=kw.get("rig"), flags=ops.DENSE if kw.get("dense") else 0, prior=prior_log_odds, occlusion=occlusion,
-                limits=kw.get("occlusion_limits", (1.0, 15.0)))
+                limits=kw.get("occlusion_limits", (1.0, 15.0)), grid=occlusion_grid, voxel=occlusion_voxel)
 
 
 def select_views(model_or_cloud, cand_poses, cand_quats, k, prior_log_odds=None, min_gain=0.0, occlusion=None, clamp_max=None, chunk=None,
-                 **camera):
+                 occlusion_grid=None, occlusion_voxel=0.1, **camera):
     """Greedy view selection: out of the M candidate views cand_poses (M,3) / cand_quats (M,4) wxyz, choose up to k
     that together cover the most, against what prior_log_odds (N,) — or an ops.CoverageMap, looked up over the cloud — already holds.  Round after round the view that adds the most to
     the mean reward sigmoid(S + prior) is chosen (S: the log-odds of the views chosen so far; ties go to the lowest index) until k
@@ -291,11 +322,12 @@ def select_views(model_or_cloud, cand_poses, cand_quats, k, prior_log_odds=None,
     model_or_cloud: a ModelTraj — its cloud, camera, rig, dense mode, prior and occlusion setting score the candidates exactly as
     that model rewards them (prior_log_odds overrides its prior) — or (N,3) points / an ops.PackedCloud with the keywords intrins,
     img_width, img_height[, min_dist, max_dist, rig=(quats, trans), dense, occlusion_limits] as the models take them.
-    occlusion='hpr'|'zbuffer': every candidate's occlusion rows are built chunk by chunk (ops.occlusion_bits).  clamp_max: OctoMap's
+    occlusion='hpr'|'zbuffer'|'voxel': every candidate's occlusion rows are built chunk by chunk (ops.occlusion_bits); 'voxel' walks
+    occlusion_grid (an ops.OccupancyGrid: the map so far), or a grid of the cloud's own points at occlusion_voxel metres.  clamp_max: OctoMap's
     upper clamping threshold for coverage_log_odds.  chunk: candidates per forward (None: ops.ViewSet's default).
     -> ViewSelection.  One host synchronisation at the end (the hull pass's own with occlusion; one more run when the candidates'
     rows outgrow the first capacity guess, 1 % of M x N)."""
-    cfg = _views_setup(model_or_cloud, prior_log_odds, occlusion, camera)
+    cfg = _views_setup(model_or_cloud, prior_log_odds, occlusion, camera, occlusion_grid, occlusion_voxel)
     M, k, min_gain = ops.check_views(cand_poses, cand_quats, k, min_gain, chunk)
     if clamp_max is not None and not float(clamp_max) >= 0.0:
         raise ValueError(f"clamp_max must be a number >= 0 or None, got {clamp_max!r}")
@@ -313,9 +345,10 @@ def select_views(model_or_cloud, cand_poses, cand_quats, k, prior_log_odds=None,
     qs = cand_quats.detach().to(device=dev, dtype=torch.float32).contiguous()
     occ_of = None
     if cfg["occlusion"] is not None:
-        from .model import ModelTraj   # (model imports this module)
+        from .model import ModelTraj, _occlusion_grid   # (model imports this module)
+        cfg["grid"] = _occlusion_grid(cfg["occlusion"], cfg["grid"], cfg["voxel"], cloud)
         shim = types.SimpleNamespace(_rig=rig, _cloud=cloud, points=cloud.points, _cam=cfg["cam"], _occlusion_limits=cfg["limits"],
-                                     _occlusion=cfg["occlusion"])
+                                     _occlusion=cfg["occlusion"], _occlusion_grid=cfg["grid"])
         occ_of = lambda p, q: ModelTraj._build_occlusion_rows(shim, p, q)
     capacity = None
     for attempt in range(2):
