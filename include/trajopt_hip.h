@@ -37,7 +37,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_occ_bytes / tohip_occ_init / tohip_occ_insert / tohip_occ_lookup / tohip_los_segments / tohip_los_rows (an
+/* (still 15) + tohip_occ_carve / tohip_occ_state / tohip_occ_frontier / tohip_occ_export_workspace_bytes / tohip_occ_count /
+ * tohip_occ_export (free-space carving, the three-state map, frontiers and the ordered listing of a grid): new symbols only.
+ * (still 15) + tohip_occ_bytes / tohip_occ_init / tohip_occ_insert / tohip_occ_lookup / tohip_los_segments / tohip_los_rows (an
  * occupancy bit grid and exact line-of-sight walks: the 'voxel' occlusion rows): new symbols only.
  * (still 15) + tohip_view_histogram / tohip_view_headings (propose candidate views: per-position bearing histograms of what is left to
  * see, and the best headings of each): new symbols only.
@@ -1122,6 +1124,43 @@ int tohip_los_segments(const void *grid, size_t grid_bytes, const tohip_occ_geom
 int tohip_los_rows(const void *grid, size_t grid_bytes, const tohip_occ_geom *geom, const void *packed, int64_t n_points,
                    const float *poses, const float *quats, int64_t n_wps, const tohip_camera *cam, float min_dist, float max_dist,
                    int32_t start_skip, int32_t end_skip, int32_t prune, int32_t *rows, uint64_t *stats, void *stream);
+
+/* ---- free space and frontiers ("Free space and frontiers") ---------------------------
+ * The FREE PLANE is a second occupancy grid of the same geometry (same buffer size, same layout, every call above works on it) whose
+ * set bit means "a ray passed through".  State of a voxel inside dims: 2 (occupied) if the occupied bit is set, otherwise 1 (free) if
+ * the free bit is set, otherwise 0 (unknown).  State of a position: its voxel's; 3 where a coordinate is out of range or the voxel
+ * lies outside dims.
+ *
+ * tohip_occ_carve: ray i runs from origins + origin_stride * i (origin_stride 0: one origin for all rays; 3: a row per ray) to
+ * points + 3 i, all f32 on the device.  A ray with an endpoint out of range is skipped and counted (skipped_host, HOST, may be NULL:
+ * the call then synchronises).  A, B: the fixed-point triples, D = B - A, L = floor(sqrt(D . D)) exactly.  max_range_fixed = R in
+ * 1/256 voxel, 0 <= R <= 6144 * 256, 0 = none.  With R > 0 and L > R the ray is TRUNCATED: per axis B' = A + sign(D) floor(|D| R /
+ * L), and it is not a hit; otherwise B' = B and it is a hit.  The walk A -> B' is the one above (same steps, same tie order); every
+ * visited voxel inside dims gets its free bit, except the last voxel of a hit.  Bits are only ever set (32-bit integer atomic OR,
+ * issued only where a brick's word lacks one of the gathered bits): any split and order of the rays gives the same plane.  The
+ * occupied grid is not an argument.  flags (DEVICE uint8 x n_rays, may be NULL): 0 hit, 1 truncated, 2 skipped.  stats (DEVICE
+ * uint64 x 3, may be NULL, zero-filled by the caller): += rays walked, += voxels visited (v_0 ... v_T of each), += atomics issued.
+ * tohip_occ_state: positions (m, 3) f32 -> out (m) uint8.
+ * tohip_occ_frontier: frontier (a third buffer of the same size, not one of the two) receives the mask of the voxels inside dims
+ * whose state is 1 and of whose six face neighbours INSIDE DIMS at least min_unknown (1 .. 6) have state 0; its header and pad bits 0.
+ * tohip_occ_count / tohip_occ_export: the set bits of any grid in ascending (word, bit) order — brick order.  count writes the
+ * blocks' offsets into workspace (tohip_occ_export_workspace_bytes device bytes, 8-byte aligned; 0 for bad dims) and the total to
+ * total_host (HOST, may be NULL; the one synchronisation).  export, handed that workspace and total, writes ijk (total, 3) int32 and
+ * centres (total, 3) f32, centre = fl(origin + fl(fl(i + 0.5) r)) per axis; capacity (rows of the outputs) < total: TOHIP_ENOSPC and
+ * nothing is written; no row at or beyond capacity is ever written.
+ * Every argument check returns before anything is enqueued. */
+int tohip_occ_carve(void *free_grid, size_t grid_bytes, const tohip_occ_geom *geom, const float *origins, int64_t origin_stride,
+                    const float *points, int64_t n_rays, int64_t max_range_fixed, uint8_t *flags, uint64_t *stats, int64_t *skipped_host,
+                    void *stream);
+int tohip_occ_state(const void *occupied, const void *free_grid, size_t grid_bytes, const tohip_occ_geom *geom, const float *positions,
+                    int64_t m, uint8_t *out, void *stream);
+int tohip_occ_frontier(const void *occupied, const void *free_grid, void *frontier, size_t grid_bytes, const tohip_occ_geom *geom,
+                       int32_t min_unknown, void *stream);
+size_t tohip_occ_export_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int tohip_occ_count(const void *grid, size_t grid_bytes, const tohip_occ_geom *geom, void *workspace, size_t workspace_bytes,
+                    int64_t *total_host, void *stream);
+int tohip_occ_export(const void *grid, size_t grid_bytes, const tohip_occ_geom *geom, const void *workspace, size_t workspace_bytes,
+                     int64_t total, int64_t capacity, int32_t *ijk, float *centres, void *stream);
 
 /* ---- optional per-kernel timing (bench.py's roofline leg) -----------------------------------------
  * When enabled, every launch of the big kernels is bracketed by hipEventRecord on its own stream.

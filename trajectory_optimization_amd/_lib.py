@@ -208,6 +208,13 @@ SIGNATURES = {
     "tohip_los_segments": (ctypes.c_int, [c_vp, c_sz, ctypes.POINTER(OccGeom), c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "tohip_los_rows": (ctypes.c_int, [c_vp, c_sz, ctypes.POINTER(OccGeom), c_vp, c_i64, c_vp, c_vp, c_i64, ctypes.POINTER(Camera), c_f, c_f,
                                        c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "tohip_occ_carve": (ctypes.c_int, [c_vp, c_sz, ctypes.POINTER(OccGeom), c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, ctypes.POINTER(c_i64),
+                                        c_vp]),
+    "tohip_occ_state": (ctypes.c_int, [c_vp, c_vp, c_sz, ctypes.POINTER(OccGeom), c_vp, c_i64, c_vp, c_vp]),
+    "tohip_occ_frontier": (ctypes.c_int, [c_vp, c_vp, c_vp, c_sz, ctypes.POINTER(OccGeom), c_i32, c_vp]),
+    "tohip_occ_export_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
+    "tohip_occ_count": (ctypes.c_int, [c_vp, c_sz, ctypes.POINTER(OccGeom), c_vp, c_sz, ctypes.POINTER(c_i64), c_vp]),
+    "tohip_occ_export": (ctypes.c_int, [c_vp, c_sz, ctypes.POINTER(OccGeom), c_vp, c_sz, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "tohip_clearance_workspace_bytes": (c_sz, [c_i64]),
     "tohip_clearance": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_f, c_f, c_vp, c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_sz, c_vp]),
     "tohip_traj_clearance_scratch_bytes": (c_sz, [c_i64, c_i64]),

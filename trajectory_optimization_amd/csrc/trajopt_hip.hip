@@ -17,6 +17,7 @@
 #include "propose_kernels.hip"
 #include "covmap_kernels.hip"
 #include "occupancy_kernels.hip"
+#include "frontier_kernels.hip"
 #include "loss_kernels.hip"
 #include "ingest_kernels.hip"
 #include "render_kernels.hip"

@@ -859,6 +859,175 @@ class OccupancyGrid:
                   "tohip_los_segments")
         return out
 
+    def empty_like(self):
+        """An empty grid of this one's origin, resolution, dims and device: a free plane or a mask for it."""
+        return OccupancyGrid(self.origin, self.resolution, self.dims, device=self.device)
+
+    def carve(self, origins, points, max_range=None, stats=None, flags=None):
+        """Treat this grid as a FREE PLANE (a set bit: "a ray passed through") and set the bit of every voxel the rays origins[i] ->
+        points[i] cross, walked exactly as line_of_sight walks (tohip_occ_carve).  origins: (3,) / (1,3) for one origin
+        shared by all rays, or (N,3).  A ray longer than max_range metres (None: no limit) is truncated to that length and carves all
+        of it; any other ray is a hit and leaves its last voxel — the measured one — alone.  -> the number of rays skipped (an
+        endpoint out of range or not finite); one synchronisation (that count).  stats: a zero-filled (3,) int64 device tensor that
+        receives (rays walked, voxels visited, atomics issued); flags: an (N,) uint8 device tensor that receives 0 hit / 1 truncated
+        / 2 skipped per ray.  Bits are only ever set: any split and order of the rays gives the same plane."""
+        R = check_carve(origins, points, max_range, self.resolution)
+        pts = covmap_points(points, self.device, "OccupancyGrid.carve")
+        org = origins if torch.is_tensor(origins) else torch.as_tensor(np.asarray(origins, dtype=np.float32), device=self.device)
+        org = covmap_points(org.reshape(-1, 3), self.device, "OccupancyGrid.carve")
+        if flags is not None and (not torch.is_tensor(flags) or flags.dtype != torch.uint8 or flags.shape != (pts.shape[0],)
+                                  or flags.device != self.device or not flags.is_contiguous()):
+            raise ValueError(f"flags must be a contiguous ({pts.shape[0]},) uint8 tensor on {self.device}")
+        skipped = ctypes.c_int64(0)
+        with torch.cuda.device(self.device):
+            check(_lib.lib().tohip_occ_carve(*self._sizes(), ptr(org), 0 if org.shape[0] == 1 else 3, ptr(pts), pts.shape[0], R, ptr(flags),
+                                             ptr(stats), ctypes.byref(skipped), stream_ptr()), "tohip_occ_carve")
+        return int(skipped.value)
+
+    def _count(self):
+        """-> (the number of set bits, the workspace holding the blocks' offsets for export); the one synchronisation."""
+        L = _lib.lib()
+        ws = torch.empty(L.tohip_occ_export_workspace_bytes(*self.dims), dtype=torch.uint8, device=self.device)
+        total = ctypes.c_int64(0)
+        with torch.cuda.device(self.device):
+            check(L.tohip_occ_count(*self._sizes(), ptr(ws), ws.numel(), ctypes.byref(total), stream_ptr()), "tohip_occ_count")
+        return int(total.value), ws
+
+    def count(self):
+        """The number of set bits; synchronises."""
+        return self._count()[0]
+
+    def export(self):
+        """The set bits listed -> (ijk (F,3) int32, centres (F,3) f32) on the device in ascending (word, bit) order — brick order, what
+        a kernel gives without a sort; centre = origin + (i + 0.5) resolution per axis in f32.  One synchronisation (F)."""
+        total, ws = self._count()
+        ijk = torch.empty((total, 3), dtype=torch.int32, device=self.device)
+        centres = torch.empty((total, 3), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(_lib.lib().tohip_occ_export(*self._sizes(), ptr(ws), ws.numel(), total, total, ptr(ijk), ptr(centres), stream_ptr()),
+                  "tohip_occ_export")
+        return ijk, centres
+
+
+CARVE_MAX_RANGE = 6144 * 256   # of max_range in 1/256 voxel: the span of a grid and its apron
+
+
+def check_carve(origins, points, max_range=None, resolution=0.1):
+    """carve's arguments, by name: points an (N,3) floating tensor; origins a (3,) or (1,3) floating tensor or 3 numbers (one origin
+    for all rays) or an (N,3) floating tensor on points' device; max_range None or a finite number of metres whose fixed-point form
+    R = floor(float64(max_range) / float64(f32 resolution) * 256) lies in [1, 6144 * 256] -> R (0 for None); ValueError otherwise.
+    Needs no GPU."""
+    _check_float_rows(points, "points", "an (N,3) floating-point tensor", 3)
+    n = points.shape[0]
+    o = origins
+    if not torch.is_tensor(o):
+        try:
+            o = torch.from_numpy(np.asarray(o, dtype=np.float32))
+        except (TypeError, ValueError):
+            o = None
+    if o is None or not o.is_floating_point() or tuple(o.shape) not in ((3,), (1, 3), (n, 3)):
+        raise ValueError("origins must be a (3,) or (1,3) floating-point tensor (one origin for all rays) or an (N,3) one with points' "
+                         f"{n} rows, got {tuple(o.shape) if o is not None else type(origins).__name__}")
+    if torch.is_tensor(origins) and origins.device != points.device:
+        raise ValueError(f"origins and points must live on one device, got {origins.device} and {points.device}")
+    if max_range is None:
+        return 0
+    m, r = _float_or_nan(max_range), float(np.float32(resolution))
+    R = int(np.floor(m / r * 256.0)) if np.isfinite(m) and _is_real(max_range) else -1
+    if not 1 <= R <= CARVE_MAX_RANGE:
+        raise ValueError(f"max_range must be None or a finite number of metres between resolution / 256 and 6144 voxels ({6144 * r:g} m), "
+                         f"got {max_range!r}")
+    return R
+
+
+def _is_real(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+
+
+class Frontier:
+    """What SpaceMap.frontier returns: ijk (F,3) int32 voxel indices and points (F,3) f32 (their centres) on the device in brick
+    order, grid (the mask as an OccupancyGrid: lookup, dense, export work on it) and n = F."""
+    __slots__ = ("ijk", "points", "grid")
+
+    def __init__(self, ijk, points, grid):
+        self.ijk, self.points, self.grid = ijk, points, grid
+
+    @property
+    def n(self):
+        return int(self.ijk.shape[0])
+
+
+def check_space_planes(occupied, free):
+    """A SpaceMap's two planes: OccupancyGrids of one origin, resolution, dims and device, not the same grid; ValueError names what
+    differs."""
+    for name, g in (("occupied", occupied), ("free", free)):
+        if not isinstance(g, OccupancyGrid):
+            raise ValueError(f"SpaceMap: {name} must be an ops.OccupancyGrid, got {type(g).__name__}")
+    if free is occupied:
+        raise ValueError("SpaceMap: free must not be the occupied grid itself")
+    if not np.array_equal(occupied.origin, free.origin):
+        raise ValueError(f"SpaceMap: the planes' origins differ ({tuple(map(float, occupied.origin))} and {tuple(map(float, free.origin))})")
+    if occupied.resolution != free.resolution:
+        raise ValueError(f"SpaceMap: the planes' resolutions differ ({occupied.resolution} and {free.resolution})")
+    if occupied.dims != free.dims:
+        raise ValueError(f"SpaceMap: the planes' dims differ ({occupied.dims} and {free.dims})")
+    if occupied.device != free.device:
+        raise ValueError(f"SpaceMap: the planes live on {occupied.device} and {free.device}")
+
+
+def check_min_unknown(min_unknown):
+    if not _is_int(min_unknown) or not 1 <= min_unknown <= 6:
+        raise ValueError(f"min_unknown must be an integer in [1, 6], got {min_unknown!r}")
+    return int(min_unknown)
+
+
+class SpaceMap:
+    """The three-state map ("Free space and frontiers"): the caller's occupied grid — shared, not copied — and a free
+    plane of the same geometry.  A voxel is occupied (2) where the occupied bit is set, else free (1) where a ray passed through, else
+    unknown (0).  Bits are never cleared: the map has no moving obstacles; free space leaks through a wall sampled more sparsely
+    than the voxel; the box's own boundary is not a frontier."""
+
+    def __init__(self, occupied, free=None):
+        if free is None:
+            if not isinstance(occupied, OccupancyGrid):
+                raise ValueError(f"SpaceMap: occupied must be an ops.OccupancyGrid, got {type(occupied).__name__}")
+            free = occupied.empty_like()
+        check_space_planes(occupied, free)
+        self.occupied, self.free = occupied, free
+        self.device = occupied.device
+
+    def integrate(self, origin, points, max_range=None):
+        """One scan: the rays origin -> points[i] carve the free plane, and the rows become occupied — except those beyond max_range:
+        a truncated ray's far point is a direction, not a return, and is carved up to max_range but not inserted.  Which rows those
+        are is carve's own integer rule, read from its per-ray flags (one carve launch, then one insert of the other rows).
+        -> the number of rays skipped (an endpoint out of range)."""
+        check_carve(origin, points, max_range, self.free.resolution)
+        pts = covmap_points(points, self.device, "SpaceMap.integrate")
+        flags = torch.empty(pts.shape[0], dtype=torch.uint8, device=self.device)
+        skipped = self.free.carve(origin, pts, max_range, flags=flags)
+        self.occupied.insert(pts if max_range is None else pts[flags != 1])
+        return skipped
+
+    def state(self, positions):
+        """(M,3) world positions -> (M,) uint8: 2 occupied, 1 free, 0 unknown, 3 beyond the apron, not finite or outside dims."""
+        pos = covmap_points(positions, self.device, "SpaceMap.state")
+        out = torch.empty(pos.shape[0], dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            check(_lib.lib().tohip_occ_state(ptr(self.occupied.buf), *self.free._sizes(), ptr(pos), pos.shape[0], ptr(out), stream_ptr()),
+                  "tohip_occ_state")
+        return out
+
+    def frontier(self, min_unknown=1):
+        """The free voxels with at least min_unknown (1 .. 6) unknown face neighbours inside dims -> Frontier (ijk, points, grid, n).
+        One synchronisation (n)."""
+        k = check_min_unknown(min_unknown)
+        mask = self.free.empty_like()
+        with torch.cuda.device(self.device):
+            check(_lib.lib().tohip_occ_frontier(ptr(self.occupied.buf), ptr(self.free.buf), *mask._sizes(), k, stream_ptr()),
+                  "tohip_occ_frontier")
+        ijk, centres = mask.export()
+        return Frontier(ijk, centres, mask)
+
 
 def check_occlusion_grid(grid, cloud):
     """occlusion_bits(method='voxel')'s grid: an OccupancyGrid on the cloud's device; ValueError otherwise."""

@@ -679,3 +679,154 @@ def los_ref(a, b, origin, resolution, occ, skip=(1, 1)):
     out = np.full(len(qa), 2, dtype=np.uint8)
     out[ok] = 1 - los_fixed(qa[ok], qb[ok], occ, skip).astype(np.uint8)
     return out
+
+
+# ---- free-space carving, the three-state map, frontiers and the ordered listing restated in numpy ("Free space and
+# frontiers"): what frontier_kernels.hip must give, bit for bit.  int64 throughout. --------------------------------------------------
+CARVE_MAX_RANGE = 6144 * 256
+
+
+def carve_clip(A, B, R):
+    """The truncation rule on fixed-point triples (N,3) int64 -> (B' (N,3), hit (N,) bool): L = isqrt(D . D); with R > 0 and L > R,
+    B' = A + sign(D) floor(|D| R / L) per axis and the ray is no hit; otherwise B' = B and it is."""
+    A, B = np.asarray(A, dtype=np.int64).reshape(-1, 3), np.asarray(B, dtype=np.int64).reshape(-1, 3)
+    D = B - A
+    L = np.array([math.isqrt(int(d)) for d in (D * D).sum(axis=1)], dtype=np.int64)
+    R = int(R)
+    cut = (L > R) if R > 0 else np.zeros(len(A), dtype=bool)
+    Bc = A + np.sign(D) * (np.abs(D) * R // np.maximum(L, 1)[:, None])
+    return np.where(cut[:, None], Bc, B), ~cut
+
+
+def carve_fixed(A, B, hit, free):
+    """Walk A -> B (fixed-point triples, in range) exactly as los_fixed does and set free[v] for every visited voxel inside dims,
+    except the last voxel of a ray with hit[i]; free (nx,ny,nz) bool is modified in place.  -> the number of voxels visited (v_0 ...
+    v_T of every ray).  Vectorised over the rays still walking; tests/test_frontier_cpu.py checks it against los_fixed(trace=True)."""
+    A, B = np.asarray(A, dtype=np.int64).reshape(-1, 3), np.asarray(B, dtype=np.int64).reshape(-1, 3)
+    hit = np.asarray(hit, dtype=bool).reshape(-1)
+    dims = np.asarray(free.shape, dtype=np.int64)
+    D = B - A
+    s, m = np.sign(D), np.abs(D)
+    e = B >> 8
+    v = A >> 8
+    n = np.where(s > 0, (v + 1) * 256 - A, A - v * 256)
+    idx = np.arange(len(A))
+    visits = 0
+    while len(idx):
+        vi = v[idx]
+        visits += len(idx)
+        last = (vi == e[idx]).all(axis=1)
+        mark = ~(last & hit[idx]) & ((vi >= 0) & (vi < dims[None, :])).all(axis=1)
+        free[vi[mark, 0], vi[mark, 1], vi[mark, 2]] = True
+        idx = idx[~last]
+        if not len(idx):
+            break
+        act, ni, mi = v[idx] != e[idx], n[idx], m[idx]
+        best = np.full(len(idx), -1, dtype=np.int64)
+        nb, mb = np.zeros(len(idx), dtype=np.int64), np.ones(len(idx), dtype=np.int64)
+        for a in range(3):
+            take = act[:, a] & ((best < 0) | (ni[:, a] * mb < nb * mi[:, a]))
+            best = np.where(take, a, best)
+            nb, mb = np.where(take, ni[:, a], nb), np.where(take, mi[:, a], mb)
+        v[idx, best] += s[idx, best]
+        n[idx, best] += 256
+    return visits
+
+
+def carve_range(max_range, resolution):
+    """max_range in metres -> R in 1/256 voxel: floor(float64(max_range) / float64(f32 resolution) * 256); None -> 0 (no limit)."""
+    if max_range is None:
+        return 0
+    return int(math.floor(float(max_range) / float(np.float32(resolution)) * 256.0))
+
+
+def carve_ref(origins, points, origin, resolution, dims, max_range=None, free=None, R=None):
+    """carve(origins, points, max_range) -> (free (nx,ny,nz) bool, skipped, flags (N,) uint8: 0 hit, 1 truncated, 2 skipped,
+    visits).  origins: (3,) / (1,3) shared or (N,3).  free: the plane so far (not modified) or None.  R: the fixed-point range
+    itself instead of max_range."""
+    dims = tuple(int(d) for d in dims)
+    out = np.zeros(dims, dtype=bool) if free is None else np.array(free, dtype=bool)
+    P = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+    O = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    if len(O) == 1:
+        O = np.broadcast_to(O, P.shape)
+    qa, oka = occ_fixed(O, origin, resolution)
+    qb, okb = occ_fixed(P, origin, resolution)
+    ok = oka & okb
+    R = carve_range(max_range, resolution) if R is None else int(R)
+    flags = np.full(len(P), 2, dtype=np.uint8)
+    Bc, hit = carve_clip(qa[ok], qb[ok], R)
+    flags[ok] = np.where(hit, 0, 1)
+    visits = carve_fixed(qa[ok], Bc, hit, out)
+    return out, int((~ok).sum()), flags, visits
+
+
+def state_ref(positions, origin, resolution, occ, free):
+    """(M,3) world positions -> (M,) uint8: 2 occupied, 1 free, 0 unknown, 3 out of range or outside dims."""
+    occ, free = np.asarray(occ, dtype=bool), np.asarray(free, dtype=bool)
+    q, ok = occ_fixed(positions, origin, resolution)
+    v = q >> 8
+    inside = ok & ((v >= 0) & (v < np.asarray(occ.shape)[None, :])).all(axis=1)
+    out = np.full(len(q), 3, dtype=np.uint8)
+    vi = v[inside]
+    out[inside] = np.where(occ[vi[:, 0], vi[:, 1], vi[:, 2]], 2, free[vi[:, 0], vi[:, 1], vi[:, 2]].astype(np.uint8))
+    return out
+
+
+def frontier_ref(occ, free, min_unknown=1):
+    """The frontier mask (nx,ny,nz) bool: state 1 and at least min_unknown of the six face neighbours inside dims in state 0."""
+    occ, free = np.asarray(occ, dtype=bool), np.asarray(free, dtype=bool)
+    unknown = ~occ & ~free
+    cnt = np.zeros(occ.shape, dtype=np.int64)
+    for ax in range(3):
+        lo, hi = [slice(None)] * 3, [slice(None)] * 3
+        lo[ax], hi[ax] = slice(0, -1), slice(1, None)
+        cnt[tuple(lo)] += unknown[tuple(hi)]
+        cnt[tuple(hi)] += unknown[tuple(lo)]
+    return free & ~occ & (cnt >= int(min_unknown))
+
+
+def occ_export_ref(grid, origin, resolution):
+    """export() of a grid (nx,ny,nz) bool -> (ijk (F,3) int32, centres (F,3) f32) in ascending (word, bit) order: word = ((z >> 1)
+    nby + (y >> 2)) nbx + (x >> 2), bit = x & 3 | (y & 3) << 2 | (z & 1) << 4; centre = fl(origin + fl(fl(i + 0.5) r)) in f32."""
+    g = np.asarray(grid, dtype=bool)
+    nbx, nby = (g.shape[0] + 3) // 4, (g.shape[1] + 3) // 4
+    ijk = np.argwhere(g).astype(np.int64)
+    x, y, z = ijk[:, 0], ijk[:, 1], ijk[:, 2]
+    key = ((((z >> 1) * nby + (y >> 2)) * nbx + (x >> 2)) << 5) | (x & 3) | ((y & 3) << 2) | ((z & 1) << 4)
+    ijk = ijk[np.argsort(key, kind="stable")]
+    f32 = np.float32
+    o, r = np.asarray(origin, dtype=f32).reshape(3), f32(resolution)
+    centres = (o[None, :] + ((ijk.astype(f32) + f32(0.5)) * r).astype(f32)).astype(f32)
+    return ijk.astype(np.int32), centres
+
+
+def box_room(doorway=False, step=0.02):
+    """A scanned room for the exploration tests and the sample: the six faces of the box [0, 2] x [0, 2] x [0, 1] sampled every `step`
+    metres, face after face (edges and corners appear once per face) -> (N,3) f32; doorway: the wall x = 2 is left open for y in
+    (0.75, 1.25), z in (0.01, 0.75)."""
+    s, z = np.arange(int(round(2.0 / step)) + 1) * step, np.arange(int(round(1.0 / step)) + 1) * step
+    faces = []
+    for x in (0.0, 2.0):
+        Y, Z = np.meshgrid(s, z, indexing="ij")
+        faces.append(np.stack([np.full(Y.size, x), Y.ravel(), Z.ravel()], axis=1))
+    for y in (0.0, 2.0):
+        X, Z = np.meshgrid(s, z, indexing="ij")
+        faces.append(np.stack([X.ravel(), np.full(X.size, y), Z.ravel()], axis=1))
+    for h in (0.0, 1.0):
+        X, Y = np.meshgrid(s, s, indexing="ij")
+        faces.append(np.stack([X.ravel(), Y.ravel(), np.full(X.size, h)], axis=1))
+    P = np.concatenate(faces)
+    if doorway:
+        P = P[~((P[:, 0] == 2.0) & (P[:, 1] > 0.75) & (P[:, 1] < 1.25) & (P[:, 2] > 0.01) & (P[:, 2] < 0.75))]
+    return P.astype(np.float32)
+
+
+def doorway_beams(origin, far=6.0):
+    """No-return beams through box_room's doorway, as a scanner reports them: far points `far` metres out along 9 x 7 directions
+    from origin through the opening -> (63,3) f32."""
+    o = np.asarray(origin, dtype=np.float64).reshape(3)
+    T = np.array([[2.0, y, z] for y in np.linspace(0.8, 1.2, 9) for z in np.linspace(0.1, 0.7, 7)])
+    d = T - o
+    d /= np.linalg.norm(d, axis=1)[:, None]
+    return (o + far * d).astype(np.float32)

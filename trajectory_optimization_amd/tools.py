@@ -245,6 +245,30 @@ def line_of_sight(grid, a, b, skip=(1, 1)):
     return grid.line_of_sight(a, b, skip)
 
 
+def space_map(grid, free=None):
+    """An ops.SpaceMap over an occupancy grid: the grid stays the caller's — what it holds is occupied — and a free
+    plane is added.  space.integrate(origin, points, max_range) takes a scan: its rows become occupied and its rays carve free space;
+    what neither has touched stays unknown."""
+    return ops.SpaceMap(grid, free)
+
+
+def frontier_points(space, min_unknown=1):
+    """The centres (F,3) f32 of the frontier voxels — free, with at least min_unknown unknown face neighbours: where the map ends.  A
+    cloud every planning call accepts: propose_views(frontier_points(space), ...), select_views(..., occlusion='voxel',
+    occlusion_grid=space.occupied)."""
+    if not isinstance(space, ops.SpaceMap):
+        raise ValueError(f"frontier_points: space must be an ops.SpaceMap, got {type(space).__name__}")
+    return space.frontier(min_unknown).points
+
+
+def known_free(space, positions):
+    """(M,3) positions -> (M,) bool: the voxel is known to be free (a ray passed through it and nothing was measured in it).  The
+    filter for roadmap_lattice nodes and propose_views positions: a node in a never-scanned room does not pass."""
+    if not isinstance(space, ops.SpaceMap):
+        raise ValueError(f"known_free: space must be an ops.SpaceMap, got {type(space).__name__}")
+    return space.state(positions) == 1
+
+
 class _Result:
     """What the result classes share: the keyword constructor; each names its fields in its own __slots__."""
     __slots__ = ()
