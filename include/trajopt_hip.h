@@ -37,7 +37,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_occ_carve / tohip_occ_state / tohip_occ_frontier / tohip_occ_export_workspace_bytes / tohip_occ_count /
+/* (still 15) + tohip_field_bytes / tohip_field_workspace_bytes / tohip_field_build / tohip_field_positions / tohip_field_segments /
+ * tohip_field_nodes (a conservative clearance field over the occupancy grid): new symbols only.
+ * (still 15) + tohip_occ_carve / tohip_occ_state / tohip_occ_frontier / tohip_occ_export_workspace_bytes / tohip_occ_count /
  * tohip_occ_export (free-space carving, the three-state map, frontiers and the ordered listing of a grid): new symbols only.
  * (still 15) + tohip_occ_bytes / tohip_occ_init / tohip_occ_insert / tohip_occ_lookup / tohip_los_segments / tohip_los_rows (an
  * occupancy bit grid and exact line-of-sight walks: the 'voxel' occlusion rows): new symbols only.
@@ -1161,6 +1163,37 @@ int tohip_occ_count(const void *grid, size_t grid_bytes, const tohip_occ_geom *g
                     int64_t *total_host, void *stream);
 int tohip_occ_export(const void *grid, size_t grid_bytes, const tohip_occ_geom *geom, const void *workspace, size_t workspace_bytes,
                      int64_t total, int64_t capacity, int32_t *ijk, float *centres, void *stream);
+
+/* ---- the clearance field ("Clearance field") ------------------------------------------
+ * A FIELD has an occupancy grid's geometry and holds one uint16 per voxel inside dims, dense, x fastest (index (z ny + y) nx + x):
+ * tohip_field_bytes(nx, ny, nz) = 2 nx ny nz device bytes (0 for bad dims), caller-owned; tohip_field_workspace_bytes is the same.
+ * Obstacles: the voxels inside dims whose occupied bit is set and, where free_or_null is a free plane, also those of state 0
+ * (neither bit: unknown); nothing outside dims.  Metric: gap2(v, u) = sum over the axes of max(|v_a - u_a| - 1, 0)^2, the squared
+ * gap between the two voxel cubes in voxels — an exact integer, and any point of the closed cube of v is at least sqrt(gap2) r from
+ * any point of the cube of u.  field[v] = min over the obstacles u of gap2(v, u) where that is <= D^2 (1 <= D <= 254), else 65535.
+ * tohip_field_build: three launches (x, y, z), field and workspace ping-pong, the result lies in field; the planes are only read.
+ * tohip_field_positions: positions (m, 3) f32 -> d2 (m) int32 — the voxel's value, 65535 in range but outside dims, -1 out of range
+ * — and / or dist (m) f32 metres fl(fl(sqrt(d2)) r), +inf for 65535, NaN for -1; either output may be NULL, not both.
+ * tohip_field_segments: legs a[e] -> b[e], (n_legs, 3) f32 world points, walked as tohip_los_segments walks (same steps, same tie
+ * order, v_0 ... v_T) with no skip rule and no early exit: d2[e] int32 = the minimum of the field over the visited voxels inside
+ * dims (65535: none inside dims, or all hold 65535; -1: an endpoint out of range), vox[e] int32 = the linear index of the first
+ * visited voxel that attains it (-1 with 65535 or -1).  With edge_d / edge_idx (both or neither; d2 and vox may then be NULL) the
+ * answer also comes in tohip_clearance_edges' shape for need2 in [0, 65535]: an open leg (d2 >= need2) +inf / -1, a blocked one
+ * metres / vox, a leg with an endpoint out of range 0 / -2.
+ * tohip_field_nodes: nodes (an occupancy grid buffer of grid_bytes, none of the inputs) receives the mask of the voxels inside dims
+ * with field >= need2, every index i satisfying i % stride == stride / 2 (1 <= stride <= 2048) and — where the two planes of a map
+ * are given (both or neither) — state 1; its header and pad bits 0.  tohip_occ_count / tohip_occ_export list it.
+ * Every argument check returns before anything is enqueued; nothing synchronises with the host. */
+size_t tohip_field_bytes(int32_t nx, int32_t ny, int32_t nz);
+size_t tohip_field_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int tohip_field_build(const void *occupied, const void *free_or_null, size_t grid_bytes, const tohip_occ_geom *geom, int32_t D,
+                      void *field, size_t field_bytes, void *workspace, size_t workspace_bytes, void *stream);
+int tohip_field_positions(const void *field, size_t field_bytes, const tohip_occ_geom *geom, const float *positions, int64_t m,
+                          int32_t *d2, float *dist, void *stream);
+int tohip_field_segments(const void *field, size_t field_bytes, const tohip_occ_geom *geom, const float *a, const float *b,
+                         int64_t n_legs, int32_t *d2, int32_t *vox, int32_t need2, float *edge_d, int32_t *edge_idx, void *stream);
+int tohip_field_nodes(const void *field, size_t field_bytes, const void *occupied_or_null, const void *free_or_null, void *nodes,
+                      size_t grid_bytes, const tohip_occ_geom *geom, int32_t need2, int32_t stride, void *stream);
 
 /* ---- optional per-kernel timing (bench.py's roofline leg) -----------------------------------------
  * When enabled, every launch of the big kernels is bracketed by hipEventRecord on its own stream.

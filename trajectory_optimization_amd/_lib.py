@@ -215,6 +215,12 @@ SIGNATURES = {
     "tohip_occ_export_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "tohip_occ_count": (ctypes.c_int, [c_vp, c_sz, ctypes.POINTER(OccGeom), c_vp, c_sz, ctypes.POINTER(c_i64), c_vp]),
     "tohip_occ_export": (ctypes.c_int, [c_vp, c_sz, ctypes.POINTER(OccGeom), c_vp, c_sz, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "tohip_field_bytes": (c_sz, [c_i32, c_i32, c_i32]),
+    "tohip_field_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
+    "tohip_field_build": (ctypes.c_int, [c_vp, c_vp, c_sz, ctypes.POINTER(OccGeom), c_i32, c_vp, c_sz, c_vp, c_sz, c_vp]),
+    "tohip_field_positions": (ctypes.c_int, [c_vp, c_sz, ctypes.POINTER(OccGeom), c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "tohip_field_segments": (ctypes.c_int, [c_vp, c_sz, ctypes.POINTER(OccGeom), c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "tohip_field_nodes": (ctypes.c_int, [c_vp, c_sz, c_vp, c_vp, c_vp, c_sz, ctypes.POINTER(OccGeom), c_i32, c_i32, c_vp]),
     "tohip_clearance_workspace_bytes": (c_sz, [c_i64]),
     "tohip_clearance": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_f, c_f, c_vp, c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_sz, c_vp]),
     "tohip_traj_clearance_scratch_bytes": (c_sz, [c_i64, c_i64]),

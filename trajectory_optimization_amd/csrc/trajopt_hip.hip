@@ -18,6 +18,7 @@
 #include "covmap_kernels.hip"
 #include "occupancy_kernels.hip"
 #include "frontier_kernels.hip"
+#include "field_kernels.hip"
 #include "loss_kernels.hip"
 #include "ingest_kernels.hip"
 #include "render_kernels.hip"

@@ -1029,6 +1029,176 @@ class SpaceMap:
         return Frontier(ijk, centres, mask)
 
 
+FIELD_MAX_D = 254          # the largest truncation distance in voxels: D^2 < 65535, the sentinel
+FIELD_SENTINEL = 65535     # "no obstacle within D voxels"
+FIELD_UNKNOWN = ("free", "obstacle")
+
+
+def field_need2(radius, resolution):
+    """The squared gap in voxels that certifies `radius` metres at this resolution: ceil((float64(radius) / float64(f32 resolution) +
+    1/64)^2), computed on the host ("Clearance field"; synth.field_need2 restates it)."""
+    return int(np.ceil((float(radius) / float(np.float32(resolution)) + 1.0 / 64.0) ** 2))
+
+
+def check_field(grid_or_space, max_dist=None, unknown="free", D=None, radius=None, stride=1, space=None):
+    """A clearance field's settings and a query's, by name; needs no GPU.  grid_or_space: an OccupancyGrid or a SpaceMap (its occupied
+    grid; its free plane is read only with unknown='obstacle', which needs a SpaceMap).  max_dist: a finite number of metres whose D
+    = ceil(float64(max_dist) / float64(f32 resolution)) lies in [1, 254] — or D itself, an integer in that range, instead.  radius
+    (None: not asked): a finite number > 0 whose need2 = field_need2(radius) is at most D^2 — a larger one this field cannot certify,
+    and the error names the largest it can.  stride: an integer >= 1.  space (None: no filter): a SpaceMap of the grid's origin,
+    resolution, dims and device.  -> (occupied grid, free plane or None, D, need2 or None); ValueError otherwise."""
+    if isinstance(grid_or_space, SpaceMap):
+        occupied, free = grid_or_space.occupied, grid_or_space.free
+    elif isinstance(grid_or_space, OccupancyGrid):
+        occupied, free = grid_or_space, None
+    else:
+        raise ValueError(f"ClearanceField: the map must be an ops.OccupancyGrid or an ops.SpaceMap, got {type(grid_or_space).__name__}")
+    if unknown not in FIELD_UNKNOWN:
+        raise ValueError(f"unknown must be 'free' or 'obstacle', got {unknown!r}")
+    if unknown == "obstacle" and free is None:
+        raise ValueError("unknown='obstacle' needs an ops.SpaceMap (the free plane tells unknown from free), got an OccupancyGrid")
+    r = occupied.resolution
+    if D is None:
+        m = _float_or_nan(max_dist) if _is_real(max_dist) else float("nan")
+        D = int(np.ceil(m / r)) if np.isfinite(m) and m > 0.0 and m / r <= FIELD_MAX_D + 1 else 0
+        if not 1 <= D <= FIELD_MAX_D:
+            raise ValueError(f"max_dist must be a finite number of metres > 0 and at most {FIELD_MAX_D} voxels ({FIELD_MAX_D * r:g} m at this "
+                             f"resolution), got {max_dist!r}")
+    elif not _is_int(D) or not 1 <= D <= FIELD_MAX_D:
+        raise ValueError(f"D must be an integer number of voxels in [1, {FIELD_MAX_D}], got {D!r}")
+    D = int(D)
+    need2 = None
+    if radius is not None:
+        need2 = field_need2(check_tour_radius(radius), r)
+        if need2 > D * D:
+            raise ValueError(f"clearance_radius {radius!r} needs a squared gap of {need2} voxels, this field is truncated at D = {D} "
+                             f"({D * D}): the largest radius it can certify is {(D - 1.0 / 64.0) * r:g} m; build it with a larger max_dist")
+    if not _is_int(stride) or stride < 1:
+        raise ValueError(f"stride must be an integer >= 1, got {stride!r}")
+    if space is not None:
+        if not isinstance(space, SpaceMap):
+            raise ValueError(f"space must be an ops.SpaceMap or None, got {type(space).__name__}")
+        for what, a, b in (("origin", tuple(map(float, space.occupied.origin)), tuple(map(float, occupied.origin))),
+                           ("resolution", space.occupied.resolution, r), ("dims", space.occupied.dims, occupied.dims),
+                           ("device", space.occupied.device, occupied.device)):
+            if a != b:
+                raise ValueError(f"space: its {what} differs from the field's ({a} and {b})")
+    return occupied, (free if unknown == "obstacle" else None), D, need2
+
+
+class FreeNodes(Frontier):
+    """What ClearanceField.free_nodes returns: ijk (F,3) int32 and points (F,3) f32 (the voxel centres) on the device in brick order,
+    grid (the node plane as an OccupancyGrid) and n = F — a Frontier's fields."""
+    __slots__ = ()
+
+
+class ClearanceField:
+    """A conservative clearance field over an occupancy grid (field_kernels.hip, DESIGN.md 10 "Clearance field"): per voxel inside dims
+    the squared gap, in voxels, to the nearest obstacle voxel — gap2(v, u) = sum over the axes of max(|v_a - u_a| - 1, 0)^2, the
+    distance between the voxel cubes, never more than the true one — truncated at D voxels (65535 beyond).  Integers only: the same
+    bits in every run.  It holds the buffers, the geometry, D and the obstacle rule, and reads the map's planes again on rebuild()."""
+
+    def __init__(self, grid_or_space, max_dist=None, unknown="free", D=None):
+        self.occupied, self.free, self.D, _ = check_field(grid_or_space, max_dist, unknown, D=D)
+        self.unknown = unknown
+        g = self.occupied
+        self.origin, self.resolution, self.dims, self.device, self.geom = g.origin, g.resolution, g.dims, g.device, g.geom
+        L = _lib.lib()
+        self.buf = torch.empty(L.tohip_field_bytes(*self.dims), dtype=torch.uint8, device=self.device)
+        self._ws = torch.empty(L.tohip_field_workspace_bytes(*self.dims), dtype=torch.uint8, device=self.device)
+        self.rebuild()
+
+    @classmethod
+    def build(cls, grid_or_space, max_dist, unknown="free"):
+        """The field of an OccupancyGrid or a SpaceMap, truncated at ceil(max_dist / resolution) voxels.  unknown='free': only
+        occupied voxels are obstacles; 'obstacle' (a SpaceMap): the voxels no ray has passed through are too."""
+        return cls(grid_or_space, max_dist, unknown)
+
+    def _sizes(self):
+        return ptr(self.buf), self.buf.numel(), ctypes.byref(self.geom)
+
+    def rebuild(self):
+        """Recompute the whole field from the same planes — after more inserts or carves — into the same buffers: three launches,
+        nothing read back.  -> self."""
+        with torch.cuda.device(self.device):
+            check(_lib.lib().tohip_field_build(ptr(self.occupied.buf), ptr(self.free.buf) if self.free is not None else None,
+                                               self.occupied.buf.numel(), ctypes.byref(self.geom), self.D, ptr(self.buf), self.buf.numel(),
+                                               ptr(self._ws), self._ws.numel(), stream_ptr()), "tohip_field_build")
+        return self
+
+    def dense(self):
+        """The field as an (nx, ny, nz) int32 tensor (a copy): for tests and small grids."""
+        nx, ny, nz = self.dims
+        return self.buf.view(torch.int16).view(nz, ny, nx).to(torch.int32).bitwise_and(0xFFFF).permute(2, 1, 0).contiguous()
+
+    def _positions(self, p, want_d2, want_dist):
+        pos = covmap_points(p, self.device, "ClearanceField")
+        d2 = torch.empty(pos.shape[0], dtype=torch.int32, device=self.device) if want_d2 else None
+        dist = torch.empty(pos.shape[0], dtype=torch.float32, device=self.device) if want_dist else None
+        with torch.cuda.device(self.device):
+            check(_lib.lib().tohip_field_positions(*self._sizes(), ptr(pos), pos.shape[0], ptr(d2), ptr(dist), stream_ptr()),
+                  "tohip_field_positions")
+        return d2, dist
+
+    def lookup_positions(self, p):
+        """(M,3) world positions -> (M,) int32: the squared gap of the position's voxel, 65535 where no obstacle lies within D voxels
+        or the position is in range but outside dims, -1 out of range (beyond the apron, or not finite)."""
+        return self._positions(p, True, False)[0]
+
+    def distance(self, p):
+        """(M,3) world positions -> (M,) f32 metres: sqrt(squared gap) resolution, a lower bound on the distance from anywhere in the
+        position's voxel to anything in an obstacle voxel; +inf for 65535, NaN out of range."""
+        return self._positions(p, False, True)[1]
+
+    def _legs(self, a, b):
+        check_los(self.origin, self.resolution, self.dims, (0, 0), a, b)
+        return covmap_points(a, self.device, "ClearanceField"), covmap_points(b, self.device, "ClearanceField")
+
+    def segments(self, a, b):
+        """The legs a[e] -> b[e], two (E,3) tensors of world points -> (d2 (E,) int32, vox (E,) int32): the smallest squared gap over
+        the voxels the leg crosses — line_of_sight's exact walk, every voxel of it — and the linear index (k ny + j) nx + i of the
+        first crossed voxel that holds it.  65535 / -1: no obstacle within D voxels of the leg; -1 / -1: an endpoint out of range."""
+        a, b = self._legs(a, b)
+        d2 = torch.empty(a.shape[0], dtype=torch.int32, device=self.device)
+        vox = torch.empty(a.shape[0], dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(_lib.lib().tohip_field_segments(*self._sizes(), ptr(a), ptr(b), a.shape[0], ptr(d2), ptr(vox), 0, None, None, stream_ptr()),
+                  "tohip_field_segments")
+        return d2, vox
+
+    def need2(self, radius):
+        """The squared gap that certifies `radius` metres (field_need2); ValueError where it exceeds D^2, naming the largest radius
+        this field can certify.  A leg is open iff its d2 >= need2."""
+        return check_field(self.occupied, D=self.D, radius=radius)[3]
+
+    def edges(self, a, b, radius):
+        """The legs a[e] -> b[e] in the shape clearance_edges answers: (d (E,) f32, idx (E,) int32, s (E,) f32).  A leg the field
+        certifies — every point of it at least `radius` from every obstacle voxel — is open: d +inf, idx -1.  Any other is blocked: d
+        the gap in metres and idx the voxel's linear index; a leg with an endpoint out of range is never certified: d 0, idx -2.
+        s is zeros.  One launch."""
+        need2 = self.need2(radius)
+        a, b = self._legs(a, b)
+        d = torch.empty(a.shape[0], dtype=torch.float32, device=self.device)
+        idx = torch.empty(a.shape[0], dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(_lib.lib().tohip_field_segments(*self._sizes(), ptr(a), ptr(b), a.shape[0], None, None, need2, ptr(d), ptr(idx),
+                                                  stream_ptr()), "tohip_field_segments")
+        return d, idx, torch.zeros(a.shape[0], dtype=torch.float32, device=self.device)
+
+    def free_nodes(self, radius, stride=1, space=None):
+        """Free-space nodes from the map itself: the voxels whose whole cube keeps `radius` from every obstacle voxel (field >= need2),
+        one in stride^3 (every index = stride // 2 modulo stride) and — with a SpaceMap of this geometry — known to be free.
+        -> FreeNodes (ijk, points = the centres, grid, n) in brick order.  One synchronisation (n)."""
+        _, _, _, need2 = check_field(self.occupied, D=self.D, radius=check_tour_radius(radius), stride=stride, space=space)
+        plane = self.occupied.empty_like()
+        occ, fre = (ptr(space.occupied.buf), ptr(space.free.buf)) if space is not None else (None, None)
+        with torch.cuda.device(self.device):
+            check(_lib.lib().tohip_field_nodes(ptr(self.buf), self.buf.numel(), occ, fre, *plane._sizes(), need2, int(stride), stream_ptr()),
+                  "tohip_field_nodes")
+        ijk, centres = plane.export()
+        return FreeNodes(ijk, centres, plane)
+
+
 def check_occlusion_grid(grid, cloud):
     """occlusion_bits(method='voxel')'s grid: an OccupancyGrid on the cloud's device; ValueError otherwise."""
     if not isinstance(grid, OccupancyGrid):

@@ -830,3 +830,206 @@ def doorway_beams(origin, far=6.0):
     d = T - o
     d /= np.linalg.norm(d, axis=1)[:, None]
     return (o + far * d).astype(np.float32)
+
+
+# ---- the clearance field restated in numpy ("Clearance field"): what field_kernels.hip must give, bit for bit.  int64
+# throughout. ------------------------------------------------------------------------------------------------------------------------
+FIELD_SENTINEL = 65535
+FIELD_MAX_D = 254
+FIELD_UNKNOWN = ("free", "obstacle")
+
+
+def field_obstacles(occ, free=None, unknown="free"):
+    """The obstacle mask (nx,ny,nz) bool: the occupied voxels and, with unknown='obstacle', also those of state 0 (neither bit)."""
+    occ = np.asarray(occ, dtype=bool)
+    if unknown not in FIELD_UNKNOWN:
+        raise ValueError(f"unknown must be 'free' or 'obstacle', got {unknown!r}")
+    if unknown == "free":
+        return occ.copy()
+    if free is None:
+        raise ValueError("unknown='obstacle' needs the free plane")
+    return occ | ~np.asarray(free, dtype=bool)
+
+
+def _field_axis_cost(k, metric):
+    k = abs(int(k))
+    return (max(k - 1, 0) if metric == "gap" else k) ** 2
+
+
+def field_ref(occ, free=None, D=8, unknown="free", metric="gap"):
+    """The field (nx,ny,nz) int64 by three windowed passes of truncated min-plus — x, then y, then z; per-axis cost max(|k| - 1, 0)^2
+    (metric='centre': k^2, the squared distance between voxel centres, for the cross-check against scipy); window +-(D + 1); values
+    above D^2 dropped after each pass -> min over the obstacles of gap2 where that is <= D^2, else 65535."""
+    D = int(D)
+    if not 1 <= D <= FIELD_MAX_D:
+        raise ValueError(f"D must be an integer in [1, {FIELD_MAX_D}], got {D}")
+    big = np.int64(1) << 40
+    f = np.where(field_obstacles(occ, free, unknown), np.int64(0), big)
+    for ax in range(3):
+        n = f.shape[ax]
+        out = f.copy()   # (offset 0 costs 0)
+        for k in range(1, min(D + 1, n - 1) + 1):
+            c = _field_axis_cost(k, metric)
+            if c > D * D:
+                break
+            lo, hi = [slice(None)] * 3, [slice(None)] * 3
+            lo[ax], hi[ax] = slice(0, n - k), slice(k, n)
+            lo, hi = tuple(lo), tuple(hi)
+            out[lo] = np.minimum(out[lo], f[hi] + c)
+            out[hi] = np.minimum(out[hi], f[lo] + c)
+        f = np.where(out <= D * D, out, big)
+    return np.where(f <= D * D, f, FIELD_SENTINEL).astype(np.int64)
+
+
+def field_brute(occ, free=None, D=8, unknown="free", metric="gap"):
+    """The field by its definition: the minimum of gap2(v, u) over all obstacles u, for small grids (memory: voxels x obstacles)."""
+    D = int(D)
+    obs = field_obstacles(occ, free, unknown)
+    V = np.argwhere(np.ones(obs.shape, dtype=bool)).astype(np.int64)
+    U = np.argwhere(obs).astype(np.int64)
+    out = np.full(len(V), FIELD_SENTINEL, dtype=np.int64)
+    if len(U):
+        for lo in range(0, len(V), 1024):
+            d = np.abs(V[lo:lo + 1024, None, :] - U[None, :, :])
+            if metric == "gap":
+                d = np.maximum(d - 1, 0)
+            g2 = (d * d).sum(axis=2).min(axis=1)
+            out[lo:lo + 1024] = np.where(g2 <= D * D, g2, FIELD_SENTINEL)
+    return out.reshape(obs.shape)
+
+
+def field_max_dist_voxels(max_dist, resolution):
+    """max_dist in metres -> D in voxels: ceil(float64(max_dist) / float64(f32 resolution)) (not range-checked)."""
+    return int(math.ceil(float(max_dist) / float(np.float32(resolution))))
+
+
+def field_need2(radius, resolution):
+    """The squared gap, in voxels, that certifies `radius` metres: ceil((float64(radius) / float64(f32 resolution) + 1/64)^2).  The
+    1/64 voxel covers the 1/256-voxel quantisation of a leg's endpoints (at most sqrt(3)/256 voxel off the true segment) and the f32
+    rounding of the fixed-point coordinates."""
+    return int(math.ceil((float(radius) / float(np.float32(resolution)) + 1.0 / 64.0) ** 2))
+
+
+def field_positions_ref(positions, origin, resolution, field):
+    """(M,3) world positions -> (M,) int32: the voxel's value, 65535 in range but outside dims, -1 out of range."""
+    field = np.asarray(field)
+    q, ok = occ_fixed(positions, origin, resolution)
+    v = q >> 8
+    inside = ok & ((v >= 0) & (v < np.asarray(field.shape)[None, :])).all(axis=1)
+    out = np.where(ok, FIELD_SENTINEL, -1).astype(np.int32)
+    out[inside] = field[v[inside, 0], v[inside, 1], v[inside, 2]]
+    return out
+
+
+def field_segments_ref(a, b, origin, resolution, field):
+    """The segment query (E,3), (E,3) world points -> (d2 (E,) int32, vox (E,) int32), on top of los_fixed(trace=True): the minimum of
+    the field over the visited voxels v_0 ... v_T inside dims (65535: none inside, or all hold 65535; -1: an endpoint out of range)
+    and the linear index (k ny + j) nx + i of the first visited voxel that attains it (-1 with 65535 or -1)."""
+    field = np.asarray(field)
+    nx, ny, nz = field.shape
+    qa, oka = occ_fixed(a, origin, resolution)
+    qb, okb = occ_fixed(b, origin, resolution)
+    ok = oka & okb
+    d2, vox = np.full(len(qa), -1, dtype=np.int32), np.full(len(qa), -1, dtype=np.int32)
+    rows = np.nonzero(ok)[0]
+    if len(rows):
+        _, visited = los_fixed(qa[ok], qb[ok], np.zeros(field.shape, dtype=bool), (0, 0), trace=True)
+        for e, vs in zip(rows, visited):
+            best, arg = FIELD_SENTINEL, -1
+            for (i, j, k) in vs:
+                if 0 <= i < nx and 0 <= j < ny and 0 <= k < nz and field[i, j, k] < best:
+                    best, arg = int(field[i, j, k]), (k * ny + j) * nx + i
+            d2[e], vox[e] = best, arg
+    return d2, vox
+
+
+def field_metres(d2, resolution):
+    """d2 (any shape) -> f32 metres: fl(fl(sqrt((float) d2)) r); +inf for 65535, NaN for -1."""
+    d2 = np.asarray(d2, dtype=np.int64)
+    with np.errstate(invalid="ignore"):
+        m = (np.sqrt(np.maximum(d2, 0).astype(np.float32)).astype(np.float32) * np.float32(resolution)).astype(np.float32)
+    m = np.where(d2 == FIELD_SENTINEL, np.float32(np.inf), m)
+    return np.where(d2 < 0, np.float32(np.nan), m).astype(np.float32)
+
+
+def field_edges_ref(d2, vox, need2, resolution):
+    """ClearanceField.edges from a segment query's answer -> (d f32, idx int32): an open leg (d2 >= need2) +inf / -1, a blocked one
+    metres / vox, a leg with an endpoint out of range 0 / -2."""
+    d2, vox = np.asarray(d2, dtype=np.int64), np.asarray(vox, dtype=np.int64)
+    open_ = d2 >= int(need2)
+    d = np.where(d2 < 0, np.float32(0), np.where(open_, np.float32(np.inf), field_metres(d2, resolution))).astype(np.float32)
+    idx = np.where(d2 < 0, -2, np.where(open_, -1, vox)).astype(np.int32)
+    return d, idx
+
+
+def field_nodes_ref(field, need2, stride=1, state=None):
+    """The node mask (nx,ny,nz) bool: field >= need2, every index i with i % stride == stride // 2 and, where state (nx,ny,nz) is
+    given, state == 1 (free)."""
+    field = np.asarray(field)
+    stride = int(stride)
+    m = field >= int(need2)
+    for ax, n in enumerate(field.shape):
+        sel = (np.arange(n) % stride) == stride // 2
+        shape = [1, 1, 1]
+        shape[ax] = n
+        m = m & sel.reshape(shape)
+    if state is not None:
+        m = m & (np.asarray(state) == 1)
+    return m
+
+
+FIELD_ROOM = dict(origin=(-0.5, -0.5, -0.5), resolution=0.1, dims=(40, 30, 20))   # box_room and 1.5 m beyond its doorway
+
+
+def field_room_legs(n=2000, seed=11):
+    """Seeded random legs for the field's guarantee over box_room(doorway=True): both ends uniform in [0.05, 2.95] x [0.05, 1.95] x
+    [0.05, 0.95], every other leg no longer than 0.5 m per axis (short legs are the ones a planner asks) -> (a, b) (n,3) f32."""
+    rng = np.random.default_rng(seed)
+    lo, hi = np.array([0.05, 0.05, 0.05]), np.array([2.95, 1.95, 0.95])
+    a = rng.uniform(lo, hi, (n, 3))
+    b = rng.uniform(lo, hi, (n, 3))
+    short = np.clip(a + rng.uniform(-0.5, 0.5, (n, 3)), lo, hi)
+    b[::2] = short[::2]
+    return a.astype(np.float32), b.astype(np.float32)
+
+
+def segment_point_distance(a, b, P, chunk=64):
+    """min over the rows of P of the f64 distance from the point to the segment a[e] -> b[e] -> (E,) f64."""
+    a, b, P = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64), np.asarray(P, dtype=np.float64)
+    out = np.empty(len(a))
+    for lo in range(0, len(a), chunk):
+        A, D = a[lo:lo + chunk, None, :], (b[lo:lo + chunk] - a[lo:lo + chunk])[:, None, :]
+        dd = (D * D).sum(axis=2)
+        t = np.clip(((P[None] - A) * D).sum(axis=2) / np.where(dd > 0, dd, 1.0), 0.0, 1.0)
+        out[lo:lo + chunk] = np.sqrt((((A + t[..., None] * D) - P[None]) ** 2).sum(axis=2).min(axis=1))
+    return out
+
+
+def doorway_outside_scan(origin, n=24000, far=6.0):
+    """A second message for box_room(doorway=True), taken from `origin` outside the wall x = 2 (origin[0] > 2): n beams on a Fibonacci
+    sphere; a beam that meets the wall x = 2 (y in [0, 2], z in [0, 1], not the opening) returns that point, every other beam —
+    into the open, or through the doorway — reports a far point `far` metres out, as a scanner does without a return -> (n,3) f32."""
+    o = np.asarray(origin, dtype=np.float64).reshape(3)
+    k = np.arange(n) + 0.5
+    z = 1.0 - 2.0 * k / n
+    phi = k * (np.pi * (3.0 - np.sqrt(5.0)))
+    rad = np.sqrt(1.0 - z * z)
+    d = np.stack([rad * np.cos(phi), rad * np.sin(phi), z], axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = np.where(d[:, 0] < 0, (2.0 - o[0]) / d[:, 0], np.inf)
+    hit = o + np.where(np.isfinite(t), t, 0.0)[:, None] * d
+    wall = np.isfinite(t) & (hit[:, 1] >= 0) & (hit[:, 1] <= 2) & (hit[:, 2] >= 0) & (hit[:, 2] <= 1)
+    wall &= ~((hit[:, 1] > 0.75) & (hit[:, 1] < 1.25) & (hit[:, 2] > 0.01) & (hit[:, 2] < 0.75))
+    hit[:, 0] = 2.0
+    return np.where(wall[:, None], hit, o + far * d).astype(np.float32)
+
+
+FIELD_DOORWAY = dict(origin=(-0.5, -0.5, -0.5), resolution=0.05, dims=(80, 60, 40))
+
+
+def doorway_messages():
+    """box_room(doorway=True) scanned as two messages -> [(scanner (3,) f32, rows (N,3) f32, max_range or None), ...]: the room from
+    inside — the cone through the opening has no return and stays unknown — then doorway_outside_scan from 0.4 m beyond the door with
+    a range of 1.4 m, which carves that cone and a ball of free space outside.  Beyond that ball nothing is known."""
+    s1, s2 = np.float32([1.03, 0.97, 0.52]), np.float32([2.4, 1.0, 0.5])
+    return [(s1, box_room(doorway=True), None), (s2, doorway_outside_scan(s2), 1.4)]

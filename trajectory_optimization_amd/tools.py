@@ -269,6 +269,25 @@ def known_free(space, positions):
     return space.state(positions) == 1
 
 
+def clearance_field(grid_or_space, max_dist, unknown='free'):
+    """An ops.ClearanceField over an occupancy grid or a space map ("Clearance field"): per voxel a conservative
+    distance to the nearest obstacle voxel, up to max_dist metres, in integers — so every collision check can ask the MAP, which
+    outlives a message, instead of the current cloud.  unknown='free': only occupied voxels are obstacles; 'obstacle' (needs a
+    SpaceMap): so is every voxel no ray has passed through, and a leg through a never-scanned room is blocked.  edge_clearance,
+    build_roadmap, plan_path, plan_tour and refine_path take the field where they take a cloud; field.rebuild() follows later
+    inserts and carves."""
+    return ops.ClearanceField.build(grid_or_space, max_dist, unknown)
+
+
+def free_nodes(field, radius, stride=1, space=None):
+    """Free-space nodes from the map itself instead of a hand-chosen lattice: the voxels of `field` that keep `radius` from every
+    obstacle, one in stride^3, and with space= (an ops.SpaceMap) only those known to be free -> ops.FreeNodes; its .points (F,3) are
+    the via nodes of build_roadmap / plan_path / plan_tour and the positions of propose_views."""
+    if not isinstance(field, ops.ClearanceField):
+        raise ValueError(f"free_nodes: field must be an ops.ClearanceField, got {type(field).__name__}")
+    return field.free_nodes(radius, stride, space)
+
+
 class _Result:
     """What the result classes share: the keyword constructor; each names its fields in its own __slots__."""
     __slots__ = ()
@@ -404,11 +423,12 @@ def select_views(model_or_cloud, cand_poses, cand_quats, k, prior_log_odds=None,
                          log_odds=S)
 
 
-def _clearance_cloud(points_or_cloud_or_model, what):
+def _clearance_cloud(points_or_cloud_or_model, what, field=False):
     """The packed cloud behind a clearance query's first argument: a ModelTraj (its cloud), an ops.PackedCloud (sorted or not) or
-    (N,3) points (packed here) — checked, nothing launched: -> (cloud or None, points or None)."""
+    (N,3) points (packed here) — checked, nothing launched: -> (cloud or None, points or None).  field=True: an ops.ClearanceField
+    is accepted too and comes back in the cloud's place (leg_query asks it)."""
     c = ops._model_cloud(points_or_cloud_or_model, what)
-    if isinstance(c, ops.PackedCloud):
+    if isinstance(c, ops.PackedCloud) or (field and isinstance(c, ops.ClearanceField)):
         return c, None
     if not torch.is_tensor(c) or c.dim() != 2 or c.shape[1] != 3 or c.shape[0] == 0:
         raise ValueError(f"{what}: points must be an (N,3) tensor with N > 0, a PackedCloud or a ModelTraj, got "
@@ -416,19 +436,33 @@ def _clearance_cloud(points_or_cloud_or_model, what):
     return None, c
 
 
+def leg_query(cloud_or_field, a, b, radius, stage="edges"):
+    """(d, idx, s) of the legs a[e] -> b[e], (E,3) f32 contiguous on the source's device — the one query behind edge_clearance,
+    build_roadmap, plan_path, plan_tour and refine_path.  A PackedCloud: the swept clearance query through one of its two stages
+    ('edges': tohip_clearance_edges; 'segments': tohip_clearance_segments over two-waypoint paths — the same bits).  An
+    ops.ClearanceField: field.edges (idx -1 iff the field certifies the leg)."""
+    if isinstance(cloud_or_field, ops.ClearanceField):
+        return cloud_or_field.edges(a, b, radius)
+    if stage == "edges":
+        return ops.clearance_edges(cloud_or_field, a, b, radius)
+    return ops.clearance_segments(cloud_or_field, torch.stack([a, b], dim=1).reshape(-1, 3), radius, n_traj=a.shape[0])
+
+
 def edge_clearance(points_or_cloud_or_model, a, b, radius):
     """How far each straight segment a[e] -> b[e] is from the cloud: (d, idx, s) on the device, (E,) each — trajectory_clearance's
     segment query (segments=True) for E unrelated segments: d f32 the distance to the nearest point within `radius` (+inf when
     none), idx int32 that point's row in the caller's order (-1 when none, or an end that is not finite), s f32 where along the
-    segment its closest point lies.  The same bits as the query over the two-waypoint path a[e], b[e]."""
-    cloud, pts = _clearance_cloud(points_or_cloud_or_model, "edge_clearance")
+    segment its closest point lies.  The same bits as the query over the two-waypoint path a[e], b[e].
+    With an ops.ClearanceField in the cloud's place the map answers (ClearanceField.edges): idx -1 iff the field certifies that the
+    leg keeps `radius` from every obstacle voxel, else d the gap in metres and idx the voxel's linear index (-2: out of range)."""
+    cloud, pts = _clearance_cloud(points_or_cloud_or_model, "edge_clearance", field=True)
     a, b = torch.as_tensor(a, dtype=torch.float32), torch.as_tensor(b, dtype=torch.float32)
     if a.dim() != 2 or a.shape[1] != 3 or a.shape[0] == 0 or b.shape != a.shape:
         raise ValueError(f"edge_clearance: a and b must both be (E,3) with E > 0, got {tuple(a.shape)} and {tuple(b.shape)}")
     r = ops.check_tour_radius(radius)
     if cloud is None:
         cloud = ops.PackedCloud(pts.to(torch.float32))
-    return ops.clearance_edges(cloud, a.to(cloud.device), b.to(cloud.device), r)
+    return leg_query(cloud, a.to(cloud.device), b.to(cloud.device), r)
 
 
 class Tour(_Result):
@@ -463,9 +497,9 @@ def tour_edge_query(cloud, nodes, radius, stage=None):
     edge stages (stage=None: tour_edge_stage's choice)."""
     i, j = ops.tour_edge_ends(nodes.shape[0], nodes.device)
     a, b = nodes[i], nodes[j]
-    if (stage or tour_edge_stage(cloud, a.shape[0])) == "edges":
-        return ops.clearance_edges(cloud, a, b, radius)
-    return ops.clearance_segments(cloud, torch.stack([a, b], dim=1).reshape(-1, 3), radius, n_traj=a.shape[0])
+    if isinstance(cloud, ops.ClearanceField):
+        return leg_query(cloud, a.contiguous(), b.contiguous(), radius)
+    return leg_query(cloud, a, b, radius, stage or tour_edge_stage(cloud, a.shape[0]))
 
 
 def plan_tour(points_or_cloud_or_model, poses, quats=None, clearance_radius=None, closed=False, max_moves=None, via=None, via_k=12,
@@ -484,14 +518,14 @@ def plan_tour(points_or_cloud_or_model, poses, quats=None, clearance_radius=None
     collision-checked route, and a leg takes it wherever that beats the straight leg: a view behind a wall is reached through the
     doorway.  A via node that coincides with a pose is left out (its row is made non-finite: the index of every other node stays).
     -> Tour.  Launches only, then one copy to the host (with via: one read-back per batch of route sweeps before it)."""
-    cloud, pts = _clearance_cloud(points_or_cloud_or_model, "plan_tour")
+    cloud, pts = _clearance_cloud(points_or_cloud_or_model, "plan_tour", field=True)
     n, r, max_moves = ops.check_tour(poses, quats, clearance_radius, closed, max_moves)
     if via is not None:
         _check_via(via, n)
         if r is None:
             raise ValueError("plan_tour: via needs a clearance_radius (a finite number > 0), got None")
         k, _, _ = ops.check_roadmap_options(via_k, r, via_max_edge)
-    cloud = _device_cloud(cloud, pts, "plan_tour", pack=r is not None)
+    cloud = _device_cloud(cloud, pts, "plan_tour", pack=r is not None, radius=r)
     dev = cloud.device if cloud is not None else pts.device
     nodes = allnodes = poses.detach().to(device=dev, dtype=torch.float32).contiguous()
     qs = quats.detach().to(device=dev, dtype=torch.float32).contiguous() if quats is not None else None
@@ -611,9 +645,12 @@ class Roadmap(_Result):
         return walk, fixed, fixed * ops.TOUR_UNIT
 
 
-def _device_cloud(cloud, pts, what, pack=True):
+def _device_cloud(cloud, pts, what, pack=True, radius=None):
     """The packed cloud of a _clearance_cloud pair: the points are packed here, which is the first GPU call (pack=False: only
-    checked to be on the device, and None comes back for them)."""
+    checked to be on the device, and None comes back for them).  A ClearanceField comes back as it is, once it can certify `radius`
+    (ValueError otherwise, before anything is launched)."""
+    if isinstance(cloud, ops.ClearanceField) and radius is not None:
+        cloud.need2(radius)
     if cloud is None:
         if not pts.is_cuda:
             raise ValueError(f"{what}: points must live on a HIP device, got {pts.device}")
@@ -634,7 +671,7 @@ def _build_roadmap(cloud, nodes, r, k, max_edge):
     opened = torch.zeros(M * k, dtype=torch.bool, device=nodes.device)
     dist = torch.full((M * k,), float("inf"), dtype=torch.float32, device=nodes.device)
     if slot.numel():
-        d, idx, _ = ops.clearance_edges(cloud, nodes[lo], nodes[hi], r)
+        d, idx, _ = leg_query(cloud, nodes[lo], nodes[hi], r)
         free = (idx == -1) & (length.reshape(-1)[slot] <= ops.ROADMAP_MAX_LEN)
         opened[slot] = free
         dist[slot] = d
@@ -655,11 +692,11 @@ def build_roadmap(points_or_cloud_or_model, nodes, clearance_radius, k=12, max_e
     (d2, j), ties to the lower index, and an edge is open when the swept clearance query (edge_clearance, asked from the lower index)
     finds no cloud point within clearance_radius of it.  The graph is undirected: a pair is an edge when either list names it open.
     Lengths are integers in units of 2^-20 m, so routes over it are the same bits in every run.  -> Roadmap."""
-    cloud, pts = _clearance_cloud(points_or_cloud_or_model, "build_roadmap")
+    cloud, pts = _clearance_cloud(points_or_cloud_or_model, "build_roadmap", field=True)
     if clearance_radius is None:
         ops.check_tour_radius(clearance_radius)   # (raises: a roadmap needs one)
     _, k, r, me, _ = ops.check_roadmap(nodes, k, clearance_radius, max_edge)
-    cloud = _device_cloud(cloud, pts, "build_roadmap")
+    cloud = _device_cloud(cloud, pts, "build_roadmap", radius=r)
     q = nodes.detach().to(device=cloud.device, dtype=torch.float32).contiguous()
     return _build_roadmap(cloud, q, r, k, max_edge)
 
@@ -695,13 +732,13 @@ def plan_path(points_or_cloud_or_model, start, goal, via, clearance_radius, k=12
     """A path from start to goal that keeps clearance_radius from the cloud, over the free-space nodes `via` (F,3): the shortest
     route of the roadmap over [start; goal; via] (build_roadmap).  -> PlannedPath, whose poses are an initial path for
     ModelTraj.sharing_cloud_of(..., clearance_mode='segments'); ValueError when no route exists."""
-    cloud, pts = _clearance_cloud(points_or_cloud_or_model, "plan_path")
+    cloud, pts = _clearance_cloud(points_or_cloud_or_model, "plan_path", field=True)
     _check_via(via, 2)
     if clearance_radius is None:
         ops.check_tour_radius(clearance_radius)   # (raises: a path needs one)
     k, r, _ = ops.check_roadmap_options(k, clearance_radius, max_edge)
     ends = torch.cat([_point3(start, "start", "cpu"), _point3(goal, "goal", "cpu")])
-    cloud = _device_cloud(cloud, pts, "plan_path")
+    cloud = _device_cloud(cloud, pts, "plan_path", radius=r)
     dev = cloud.device
     nodes = _join_nodes(ends.to(dev), via.detach().to(device=dev, dtype=torch.float32))
     rm = _build_roadmap(cloud, nodes, r, k, max_edge)
@@ -736,7 +773,7 @@ def _path_chord_band(cloud, P, kept, W, r):
     ask &= last[(j - 1).clamp(max=L - 1)] <= i
     slot = torch.nonzero(ask.reshape(-1)).reshape(-1)
     band = torch.zeros(L * W, dtype=torch.uint8, device=dev)
-    _, hit, _ = ops.clearance_edges(cloud, P[i.reshape(-1)[slot]], P[j.reshape(-1)[slot]], r)   # (the input legs are always asked)
+    _, hit, _ = leg_query(cloud, P[i.reshape(-1)[slot]], P[j.reshape(-1)[slot]], r)   # (the input legs are always asked)
     band[slot] = (hit == -1).to(torch.uint8)
     return band.view(L, W)
 
@@ -753,7 +790,7 @@ def refine_path(points_or_cloud_or_model, path, quats=None, clearance_radius=Non
     than `spacing` (None: corners only); a row's quaternion is the normalised linear blend of the two kept rows around it by arc
     length.  -> RefinedPath; ValueError when a coordinate (or a kept row's quaternion) is not finite or more than max_rows
     (default 4 096) rows are needed.  Launches only, then one copy to the host."""
-    cloud, pts = _clearance_cloud(points_or_cloud_or_model, "refine_path")
+    cloud, pts = _clearance_cloud(points_or_cloud_or_model, "refine_path", field=True)
     if isinstance(path, Tour):
         if keep is None:   # (without via every row of the walk is a tour node)
             n = path.D.shape[0]
@@ -764,7 +801,7 @@ def refine_path(points_or_cloud_or_model, path, quats=None, clearance_radius=Non
         path = path.poses
     L, W, h, max_rows = ops.check_path(path, quats, keep, window, spacing, max_rows)
     r = ops.check_tour_radius(clearance_radius)
-    cloud = _device_cloud(cloud, pts, "refine_path")
+    cloud = _device_cloud(cloud, pts, "refine_path", radius=r)
     dev = cloud.device
     P = path.detach().to(device=dev, dtype=torch.float32).contiguous()
     qs = quats.detach().to(device=dev, dtype=torch.float32).contiguous() if quats is not None else None
