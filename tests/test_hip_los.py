@@ -176,6 +176,32 @@ def test_segments_through_an_empty_and_a_full_grid(dev):
     assert int(stats[0]) == int(in_range.sum()) and int(stats[1]) > int(stats[0])
 
 
+@pytest.mark.parametrize("E", [1, 65, 5000])
+def test_line_of_sight_and_carve_count_one_walk(dev, E):
+    """The rays of tests/walk_cases.py through an empty (37, 5, 20) grid, given to line_of_sight(skip=(0, 0)) and to carve
+    on a fresh free plane: both run the one walk, so they walk the same rays, and carve — which counts v_0 ... v_T where line of sight
+    stops before v_T — visits exactly one voxel per ray more.  Both counters equal what synth counts on the CPU; rays out of range
+    count in neither."""
+    from walk_cases import WALK_DIMS, WALK_R, walk_case
+    from trajectory_optimization_amd import ops
+    A, B, ok, traces, free_ref, carve_visits = walk_case(E)[:6]
+    los_visits = sum(len(t) - 1 for t in traces)
+    a, b = _t(A, dev), _t(B, dev)
+    g = ops.OccupancyGrid((0, 0, 0), WALK_R, WALK_DIMS, device=dev)
+    free = g.empty_like()
+    los_stats, carve_stats = torch.zeros(2, dtype=torch.int64, device=dev), torch.zeros(3, dtype=torch.int64, device=dev)
+    got = g.line_of_sight(a, b, skip=(0, 0), stats=los_stats)
+    skipped = free.carve(a, b, max_range=None, stats=carve_stats)
+    los_rays, los_seen = (int(v) for v in los_stats)
+    carve_rays, carve_seen = int(carve_stats[0]), int(carve_stats[1])
+    print(f"E {E}: rays {los_rays} / {carve_rays} (in range {int(ok.sum())}), visits los {los_seen} (synth {los_visits}) carve {carve_seen} (synth {carve_visits})")
+    assert los_rays == carve_rays == int(ok.sum()) and skipped == int((~ok).sum())
+    assert carve_seen == los_seen + los_rays
+    assert los_seen == los_visits and carve_seen == carve_visits
+    assert torch.equal(got.cpu(), torch.from_numpy(np.where(ok, 1, 2).astype(np.uint8)))
+    assert torch.equal(free.dense().cpu(), torch.from_numpy(free_ref))
+
+
 def test_a_wall_hides_what_lies_behind_it(dev):
     from trajectory_optimization_amd import ops
     occ = np.zeros(DIMS, bool)

@@ -301,3 +301,41 @@ def test_the_walk_finds_every_voxel_dense_f64_sampling_finds():
     assert not (sampled & ~blocked).any(), np.flatnonzero(sampled & ~blocked)[:10]
     assert 0.2 < blocked.mean() < 0.98   # (the case is neither empty nor saturated)
     print(f"walk blocked {int(blocked.sum())}, sampling blocked {int(sampled.sum())}; walk-only share {float((blocked & ~sampled).mean()):.4%}")
+
+
+# ---- one walk behind line of sight and the carve -----------------------------------------------------------------------------------
+
+from walk_cases import WALK_DIMS, walk_case  # noqa: E402
+
+
+def test_the_trace_of_los_fixed_is_what_carve_fixed_marks():
+    """5 000 rays through the (37, 5, 20) grid — axis rays, a == b, ends in the apron: every sequence los_fixed traces has 1 + sum |e -
+    v| voxels, starts at v_0 and ends at e; carve_fixed marks exactly the traced voxels inside dims (all but the last of each ray when
+    every ray is a hit) and counts every one of them; the first 65 rays also one by one."""
+    from trajectory_optimization_amd import synth
+    A, B, ok, traces, free, carve_visits, qa, qb = walk_case(5000)
+    assert ok.sum() == 4996 and len(traces) == 4996
+    v0, e = qa >> 8, qb >> 8
+    dims = np.array(WALK_DIMS)
+    assert ((v0 < 0) | (v0 >= dims)).any(axis=1).sum() > 500 and ((e < 0) | (e >= dims)).any(axis=1).sum() > 200   # ends in the apron
+    assert (v0[0] == e[0]).all() and [int((v0[i] != e[i]).sum()) for i in range(1, 5)] == [1, 1, 1, 1]               # a == b, the axis rays
+    for i, t in enumerate(traces):
+        assert len(t) == 1 + int(np.abs(e[i] - v0[i]).sum()) and t[0] == tuple(v0[i]) and t[-1] == tuple(e[i]), i
+    assert carve_visits == sum(len(t) for t in traces)
+
+    def plane(seqs):
+        p = np.zeros(WALK_DIMS, dtype=bool)
+        for t in seqs:
+            for v in t:
+                if all(0 <= c < d for c, d in zip(v, WALK_DIMS)):
+                    p[v] = True
+        return p
+
+    assert np.array_equal(free, plane(t[:-1] for t in traces)) and free.any() and not free.all()   # carve_ref: every ray a hit
+    miss = np.zeros(WALK_DIMS, dtype=bool)
+    assert synth.carve_fixed(qa, qb, np.zeros(len(qa), dtype=bool), miss) == carve_visits
+    assert np.array_equal(miss, plane(traces))
+    for i in range(65):
+        one = np.zeros(WALK_DIMS, dtype=bool)
+        assert synth.carve_fixed(qa[i:i + 1], qb[i:i + 1], [False], one) == len(traces[i])
+        assert np.array_equal(one, plane([traces[i]])), i

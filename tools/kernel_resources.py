@@ -31,7 +31,8 @@ def main():
         elif cur:
             rows[cur][m.group(1).split(" [")[0]] = m.group(2)
     for name, r in rows.items():
-        short = subprocess.run(["c++filt", name], stdout=subprocess.PIPE, text=True).stdout.strip().split("(")[0]
+        full = subprocess.run(["c++filt", name], stdout=subprocess.PIPE, text=True).stdout.strip()
+        short = full.replace("(anonymous namespace)::", "").split("(")[0]
         if want and not any(w in short for w in want):
             continue
         g = lambda k: str(r.get(k))  # noqa: E731

@@ -1,6 +1,6 @@
 // field_kernels.hip — a conservative clearance field over the occupancy grid ("Clearance field"), for gfx950.  Included
-// right after frontier_kernels.hip: the geometry, the fixed-point coordinates, the brick layout, the brick mask and the walk's axis
-// set-up are those files'.
+// right after frontier_kernels.hip: the geometry, the fixed-point coordinates, the brick layout, the brick mask and the walk
+// (occ_walk) are those files'.
 //
 // The FIELD has the grid's geometry and one uint16 per voxel inside dims, dense, x fastest: index (z ny + y) nx + x.  Obstacles: the
 // occupied voxels inside dims and, with a free plane, also the voxels of state 0 (neither bit).  Metric: the gap between voxel cubes,
@@ -19,9 +19,8 @@
 //                    truncated passes give the exact truncated minimum.
 //   k_field_positions  (M,3) f32 positions -> int32: the voxel's value, 65535 in range but outside dims, -1 out of range; optionally
 //                    metres, fl(fl(sqrt(d2)) r), +inf for 65535, NaN for -1.
-//   edt_walk         los_walk's steps — the same axis set-up, the same step block, the loop shape of carve_walk: the test at the top,
-//                    then the voxel, then the step, v_T behind the loop — with no skip rule and no early exit: the minimum of the
-//                    field over v_0 ... v_T inside dims and the first voxel that attains it stay in registers.
+//   edt_walk         occ_walk with stop_at = 0 and a visitor that never stops it, v_T behind the walk: the minimum of the field over
+//                    v_0 ... v_T inside dims and the first voxel that attains it stay in registers.
 //   k_field_segments one lane per leg in a grid-stride loop, as k_los_segments: d2 / vox, and optionally the (d, idx) a clearance
 //                    edge query gives for need2.
 //   k_field_nodes    one lane per brick word: the voxels inside dims with field >= need2, every index = stride / 2 modulo stride and,
@@ -33,13 +32,15 @@ namespace {
 constexpr int kFieldSentinel = 65535;
 constexpr int kFieldMaxD = 254;
 
-inline size_t field_voxels(const OccGeom& g) { return (size_t)g.nx * (size_t)g.ny * (size_t)g.nz; }
+inline size_t field_voxels(int64_t nx, int64_t ny, int64_t nz) { return (size_t)nx * (size_t)ny * (size_t)nz; }
+inline size_t field_voxels(const OccGeom& g) { return field_voxels(g.nx, g.ny, g.nz); }
+inline bool field_fits(size_t bytes, const OccGeom& g) { return bytes >= field_voxels(g) * sizeof(uint16_t); }
 
 // the geometry (occ_check's rules) and the field buffer's size
 inline int field_check(const void* field, size_t bytes, const tohip_occ_geom* geom, OccGeom& g) {
     const int rc = occ_check(field, ~(size_t)0, geom, g);
     if (rc != TOHIP_OK) return rc;
-    return bytes < field_voxels(g) * sizeof(uint16_t) ? TOHIP_ENOSPC : TOHIP_OK;
+    return field_fits(bytes, g) ? TOHIP_OK : TOHIP_ENOSPC;
 }
 
 __device__ __forceinline__ long long field_index(const OccGeom& g, int x, int y, int z) { return ((long long)z * g.ny + y) * g.nx + x; }
@@ -114,48 +115,33 @@ k_field_positions(const uint16_t* __restrict__ field, OccGeom g, const float* __
                   float* __restrict__ dist_out) {
     const long long stride = (long long)gridDim.x * TO_BLOCK;
     for (long long i = (long long)blockIdx.x * TO_BLOCK + threadIdx.x; i < m; i += stride) {
-        int qx, qy, qz;
-        const bool ok = occ_fixed(g, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], qx, qy, qz);
-        const int x = qx >> 8, y = qy >> 8, z = qz >> 8;
-        int d2 = -1;
-        if (ok) d2 = occ_inside(g, x, y, z) ? (int)field[field_index(g, x, y, z)] : kFieldSentinel;
+        int x, y, z, d2 = -1;
+        const OccPlace at = occ_locate(g, pos + 3 * i, x, y, z);
+        if (at != kOccOutOfRange) d2 = at == kOccInside ? (int)field[field_index(g, x, y, z)] : kFieldSentinel;
         if (d2_out) d2_out[i] = d2;
         if (dist_out) dist_out[i] = field_metres(d2, g.r);
     }
 }
 
-// voxel (x, y, z) joins the running minimum: a strict < keeps the first voxel, in walk order, that attains it
-__device__ __forceinline__ void edt_visit(const uint16_t* __restrict__ field, const OccGeom& g, int x, int y, int z, int& best, int& arg) {
-    if (!occ_inside(g, x, y, z)) return;
-    const long long at = field_index(g, x, y, z);
+// the voxel the walk stands on joins the running minimum: a strict < keeps the first voxel, in walk order, that attains it.  A visitor
+// that never stops the walk.
+__device__ __forceinline__ bool edt_visit(const uint16_t* __restrict__ field, const OccGeom& g, const OccWalk& k, int& best, int& arg) {
+    if (!occ_inside(g, k.X.v, k.Y.v, k.Z.v)) return false;
+    const long long at = field_index(g, k.X.v, k.Y.v, k.Z.v);
     const int v = field[at];
     if (v < best) { best = v; arg = (int)at; }
+    return false;
 }
 
 // A -> B in fixed point (both in range): the minimum of the field over v0 ... v_T inside dims and where it is first attained
-// (65535, -1: no visited voxel inside dims holds a value).  The loop has los_walk's shape — the test at the top, then the voxel, then
-// the step block — and v_T is handled behind it, as in carve_walk.
+// (65535, -1: no visited voxel inside dims holds a value)
 __device__ __forceinline__ void edt_walk(const uint16_t* __restrict__ field, const OccGeom& g, int ax, int ay, int az, int bx, int by, int bz,
                                          int& best, int& arg) {
-    long long n0, n1, n2;
-    LosAxis X = los_axis(ax, bx, n0), Y = los_axis(ay, by, n1), Z = los_axis(az, bz, n2);
-    long long c01 = n0 * Y.m - n1 * X.m, c02 = n0 * Z.m - n2 * X.m, c12 = n1 * Z.m - n2 * Y.m;
-    const long long sx = 256 * X.m, sy = 256 * Y.m, sz = 256 * Z.m;
+    OccWalk k = occ_walk_begin(ax, ay, az, bx, by, bz);
     best = kFieldSentinel;
     arg = -1;
-    for (;;) {
-        if ((X.rem | Y.rem | Z.rem) == 0) break;
-        edt_visit(field, g, X.v, Y.v, Z.v, best, arg);
-        const bool a0 = X.rem > 0, a1 = Y.rem > 0, a2 = Z.rem > 0;
-        if (a0 && (!a1 || c01 <= 0) && (!a2 || c02 <= 0)) {
-            X.v += X.s; --X.rem; c01 += sy; c02 += sz;
-        } else if (a1 && (!a2 || c12 <= 0)) {
-            Y.v += Y.s; --Y.rem; c01 -= sx; c12 += sz;
-        } else {
-            Z.v += Z.s; --Z.rem; c02 -= sx; c12 -= sy;
-        }
-    }
-    edt_visit(field, g, X.v, Y.v, Z.v, best, arg);
+    occ_walk(k, 0, [&](const OccWalk& at) { return edt_visit(field, g, at, best, arg); });
+    edt_visit(field, g, k, best, arg);
 }
 
 // d2 / vox (either may be null) and, with edge_d and edge_idx, the answer in a clearance edge query's shape for need2: an open leg
@@ -166,7 +152,7 @@ k_field_segments(const uint16_t* __restrict__ field, OccGeom g, const float* __r
     const long long stride = (long long)gridDim.x * TO_BLOCK;
     for (long long i = (long long)blockIdx.x * TO_BLOCK + threadIdx.x; i < n_legs; i += stride) {
         int ax, ay, az, bx, by, bz;
-        const bool ok = occ_fixed(g, a[3 * i], a[3 * i + 1], a[3 * i + 2], ax, ay, az) & occ_fixed(g, b[3 * i], b[3 * i + 1], b[3 * i + 2], bx, by, bz);
+        const bool ok = occ_fixed_leg(g, a + 3 * i, b + 3 * i, ax, ay, az, bx, by, bz);
         int d2 = -1, vox = -1;
         if (ok) edt_walk(field, g, ax, ay, az, bx, by, bz, d2, vox);
         if (d2_out) d2_out[i] = d2;
@@ -184,7 +170,8 @@ k_field_nodes(const uint16_t* __restrict__ field, const unsigned* __restrict__ o
               OccGeom g, long long n_words, int need2, int stride) {
     const long long w = (long long)blockIdx.x * TO_BLOCK + threadIdx.x;
     if (w >= n_words) return;
-    const int bx = (int)(w % g.nbx), by = (int)((w / g.nbx) % g.nby), bz = (int)(w / ((long long)g.nbx * g.nby));
+    int bx, by, bz;
+    occ_brick(g, w, bx, by, bz);
     unsigned cand = occ_brick_mask(g, bx, by, bz);
     if (occ) cand &= fre[w] & ~occ[w];   // state 1
     const int phase = stride >> 1;
@@ -192,19 +179,18 @@ k_field_nodes(const uint16_t* __restrict__ field, const unsigned* __restrict__ o
     while (cand != 0u) {
         const int bit = __ffs(cand) - 1;
         cand &= cand - 1u;
-        const int x = 4 * bx + (bit & 3), y = 4 * by + ((bit >> 2) & 3), z = 2 * bz + (bit >> 4);
+        int x, y, z;
+        occ_voxel(bx, by, bz, bit, x, y, z);
         if (x % stride != phase || y % stride != phase || z % stride != phase) continue;
         if ((int)field[field_index(g, x, y, z)] >= need2) word |= 1u << bit;
     }
     out[w] = word;
 }
 
-inline bool field_count_ok(int64_t n) { return n >= 0 && n <= (int64_t)1 << 40; }
-
 }  // namespace
 
 extern "C" size_t tohip_field_bytes(int32_t nx, int32_t ny, int32_t nz) {
-    return occ_dims_ok(nx, ny, nz) ? (size_t)nx * (size_t)ny * (size_t)nz * sizeof(uint16_t) : 0;
+    return occ_dims_ok(nx, ny, nz) ? field_voxels(nx, ny, nz) * sizeof(uint16_t) : 0;
 }
 
 extern "C" size_t tohip_field_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) { return tohip_field_bytes(nx, ny, nz); }
@@ -217,8 +203,7 @@ extern "C" int tohip_field_build(const void* occupied, const void* free_or_null,
     if (!field || !workspace || field == workspace || D < 1 || D > kFieldMaxD) return TOHIP_EINVAL;
     if (field == occupied || workspace == occupied || (free_or_null && (free_or_null == occupied || free_or_null == field || free_or_null == workspace)))
         return TOHIP_EINVAL;
-    const size_t need = field_voxels(g) * sizeof(uint16_t);
-    if (field_bytes < need || workspace_bytes < need) return TOHIP_ENOSPC;
+    if (!field_fits(field_bytes, g) || !field_fits(workspace_bytes, g)) return TOHIP_ENOSPC;
     hipStream_t st = (hipStream_t)stream_;
     const long long n = (long long)field_voxels(g);
     const int blocks = occ_grid_blocks(n);
@@ -238,7 +223,7 @@ extern "C" int tohip_field_positions(const void* field, size_t field_bytes, cons
     OccGeom g;
     const int rc = field_check(field, field_bytes, geom, g);
     if (rc != TOHIP_OK) return rc;
-    if (!field_count_ok(m) || (m > 0 && (!positions || (!d2 && !dist)))) return TOHIP_EINVAL;
+    if (!occ_count_ok(m) || (m > 0 && (!positions || (!d2 && !dist)))) return TOHIP_EINVAL;
     if (m == 0) return TOHIP_OK;
     k_field_positions<<<occ_grid_blocks(m), TO_BLOCK, 0, (hipStream_t)stream_>>>((const uint16_t*)field, g, positions, m, d2, dist);
     TO_HIP_CHECK_LAUNCH();
@@ -250,7 +235,7 @@ extern "C" int tohip_field_segments(const void* field, size_t field_bytes, const
     OccGeom g;
     const int rc = field_check(field, field_bytes, geom, g);
     if (rc != TOHIP_OK) return rc;
-    if (!field_count_ok(n_legs) || (n_legs > 0 && (!a || !b))) return TOHIP_EINVAL;
+    if (!occ_count_ok(n_legs) || (n_legs > 0 && (!a || !b))) return TOHIP_EINVAL;
     if ((edge_d == nullptr) != (edge_idx == nullptr) || (edge_d && (need2 < 0 || need2 > kFieldSentinel))) return TOHIP_EINVAL;
     if (n_legs > 0 && !edge_d && (!d2 || !vox)) return TOHIP_EINVAL;
     if (n_legs == 0) return TOHIP_OK;
@@ -268,14 +253,12 @@ extern "C" int tohip_field_nodes(const void* field, size_t field_bytes, const vo
     if (!field || (occupied_or_null == nullptr) != (free_or_null == nullptr) || nodes == occupied_or_null || nodes == free_or_null ||
         nodes == field || need2 < 0 || need2 > kFieldSentinel || stride < 1 || stride > kOccMaxDim)
         return TOHIP_EINVAL;
-    if (field_bytes < field_voxels(g) * sizeof(uint16_t)) return TOHIP_ENOSPC;
+    if (!field_fits(field_bytes, g)) return TOHIP_ENOSPC;
     hipStream_t st = (hipStream_t)stream_;
-    const hipError_t e = hipMemsetAsync(nodes, 0, kOccHdr, st);
-    if (e != hipSuccess) return (int)e;
-    const int64_t nw = (int64_t)occ_words(g.nx, g.ny, g.nz);
-    k_field_nodes<<<(unsigned)occ_list_blocks(g), TO_BLOCK, 0, st>>>((const uint16_t*)field, occupied_or_null ? occ_data(occupied_or_null) : nullptr,
-                                                                     free_or_null ? occ_data(free_or_null) : nullptr, occ_data(nodes), g, nw,
-                                                                     need2, stride);
+    const OccMaskLaunch m = occ_mask_begin(nodes, g, st);
+    if (m.rc != TOHIP_OK) return m.rc;
+    k_field_nodes<<<m.blocks, TO_BLOCK, 0, st>>>((const uint16_t*)field, occupied_or_null ? occ_data(occupied_or_null) : nullptr,
+                                                 free_or_null ? occ_data(free_or_null) : nullptr, occ_data(nodes), g, m.n_words, need2, stride);
     TO_HIP_CHECK_LAUNCH();
     return TOHIP_OK;
 }

@@ -1,18 +1,18 @@
 // frontier_kernels.hip — free-space carving, the three-state map, frontier extraction and the ordered listing of a grid's set bits
 // ("Free space and frontiers"), for gfx950.  Included right after occupancy_kernels.hip: the geometry, the fixed-point
-// coordinates, the brick layout and the walk's axis set-up are that file's.
+// coordinates, the brick layout and the walk (occ_walk) are that file's.
 //
 // The FREE PLANE is a second occupancy grid of the same geometry whose set bit means "a ray passed through".  State of a voxel
 // inside dims: 2 occupied (the occupied bit wins), else 1 free, else 0 unknown; 3 for a position out of range or outside dims.
 //
 //   k_occ_carve      one lane per ray a -> b in a grid-stride loop.  An endpoint out of range: skipped and counted.  D = B - A,
 //                    L = isqrt(D.D) (a double sqrt and a +-1 fix-up: D.D < 2^43 is exact in a double); with R > 0 and L > R the ray
-//                    is TRUNCATED to B' = A + sign(D) floor(|D| R / L) per axis (products < 2^42) and is not a hit.  The walk A ->
-//                    B' is los_walk's — the same axis set-up, the same step block — and every visited voxel inside dims gets its
-//                    free bit, except the last one of a hit.  The bits of consecutive steps that fall into one brick are gathered
-//                    in a register and flushed when the walk leaves the word: a plain load first, and the 32-bit atomic OR only
-//                    where the word lacks one of the bits.  Bits are only ever set, so a stale cached word can only cause a
-//                    redundant atomic, never a missed bit; re-carving mapped space costs loads alone.
+//                    is TRUNCATED to B' = A + sign(D) floor(|D| R / L) per axis (products < 2^42) and is not a hit.  A -> B' is
+//                    walked by occ_walk with stop_at = 0, and every visited voxel inside dims gets its free bit: v_0 .. v_T-1 from
+//                    the visitor, v_T behind the walk, except for a hit.  The bits of consecutive steps that fall into one brick
+//                    are gathered in a register and flushed when the walk leaves the word: a plain load first, and the 32-bit atomic
+//                    OR only where the word lacks one of the bits.  Bits are only ever set, so a stale cached word can only cause
+//                    a redundant atomic, never a missed bit; re-carving mapped space costs loads alone.
 //   k_occ_state      (M,3) f32 positions -> uint8 state.
 //   k_occ_frontier   one lane per brick word: the word of both planes and of the six neighbouring bricks; free & ~occ and unknown =
 //                    ~free & ~occ & (inside dims) as 32-bit masks; the six neighbour masks by shifts of 1, 4 and 16 under the edge
@@ -57,38 +57,25 @@ __device__ __forceinline__ void carve_flush(unsigned* words, int cur, unsigned b
     }
 }
 
-// voxel (x, y, z) joins the gathered bits; leaving the word flushes it
-__device__ __forceinline__ void carve_mark(unsigned* words, const OccGeom& g, int x, int y, int z, int& cur, unsigned& bits, unsigned& atomics) {
-    if (!occ_inside(g, x, y, z)) return;
+// the voxel the walk stands on joins the gathered bits; leaving the word flushes it.  A visitor that never stops the walk.
+__device__ __forceinline__ bool carve_mark(unsigned* words, const OccGeom& g, const OccWalk& at, int& cur, unsigned& bits, unsigned& atomics) {
+    const int x = at.X.v, y = at.Y.v, z = at.Z.v;
+    if (!occ_inside(g, x, y, z)) return false;
     const int w = occ_word(g, x, y, z);
     if (w != cur) { carve_flush(words, cur, bits, atomics); cur = w; bits = 0u; }
     bits |= 1u << occ_bit(x, y, z);
+    return false;
 }
 
-// A -> B in fixed point (both in range): v0 ... v_T get their free bit where they lie inside dims, v_T only when !hit.  The loop has
-// los_walk's shape — the test at the top, then the voxel, then the step block — and v_T is handled behind it.
+// A -> B in fixed point (both in range): v0 ... v_T get their free bit where they lie inside dims, v_T only when !hit
 __device__ __forceinline__ void carve_walk(unsigned* words, const OccGeom& g, int ax, int ay, int az, int bx, int by, int bz, bool hit,
                                            unsigned& visits, unsigned& atomics) {
-    long long n0, n1, n2;
-    LosAxis X = los_axis(ax, bx, n0), Y = los_axis(ay, by, n1), Z = los_axis(az, bz, n2);
-    long long c01 = n0 * Y.m - n1 * X.m, c02 = n0 * Z.m - n2 * X.m, c12 = n1 * Z.m - n2 * Y.m;
-    const long long sx = 256 * X.m, sy = 256 * Y.m, sz = 256 * Z.m;
+    OccWalk k = occ_walk_begin(ax, ay, az, bx, by, bz);
     int cur = -1;
     unsigned bits = 0;
-    visits += 1u + (unsigned)(X.rem + Y.rem + Z.rem);   // v0 ... v_T
-    for (;;) {
-        if ((X.rem | Y.rem | Z.rem) == 0) break;
-        carve_mark(words, g, X.v, Y.v, Z.v, cur, bits, atomics);
-        const bool a0 = X.rem > 0, a1 = Y.rem > 0, a2 = Z.rem > 0;
-        if (a0 && (!a1 || c01 <= 0) && (!a2 || c02 <= 0)) {
-            X.v += X.s; --X.rem; c01 += sy; c02 += sz;
-        } else if (a1 && (!a2 || c12 <= 0)) {
-            Y.v += Y.s; --Y.rem; c01 -= sx; c12 += sz;
-        } else {
-            Z.v += Z.s; --Z.rem; c02 -= sx; c12 -= sy;
-        }
-    }
-    if (!hit) carve_mark(words, g, X.v, Y.v, Z.v, cur, bits, atomics);
+    visits += 1u + (unsigned)(k.X.rem + k.Y.rem + k.Z.rem);   // v0 ... v_T
+    occ_walk(k, 0, [&](const OccWalk& at) { return carve_mark(words, g, at, cur, bits, atomics); });
+    if (!hit) carve_mark(words, g, k, cur, bits, atomics);
     carve_flush(words, cur, bits, atomics);
 }
 
@@ -100,7 +87,7 @@ k_occ_carve(unsigned long long* __restrict__ hdr, unsigned* words, OccGeom g, co
     for (long long i = (long long)blockIdx.x * TO_BLOCK + threadIdx.x; i < n; i += stride) {
         const float* o = origins + (long long)origin_stride * i;
         int ax, ay, az, bx, by, bz;
-        const bool ok = occ_fixed(g, o[0], o[1], o[2], ax, ay, az) & occ_fixed(g, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], bx, by, bz);
+        const bool ok = occ_fixed_leg(g, o, pts + 3 * i, ax, ay, az, bx, by, bz);
         int flag = 2;
         if (ok) {
             const bool hit = carve_clip(ax, ay, az, bx, by, bz, R);
@@ -124,11 +111,8 @@ k_occ_state(const unsigned* __restrict__ occ, const unsigned* __restrict__ fre, 
             uint8_t* __restrict__ out) {
     const long long stride = (long long)gridDim.x * TO_BLOCK;
     for (long long i = (long long)blockIdx.x * TO_BLOCK + threadIdx.x; i < m; i += stride) {
-        int qx, qy, qz;
-        const bool ok = occ_fixed(g, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], qx, qy, qz);
-        const int x = qx >> 8, y = qy >> 8, z = qz >> 8;
-        int s = 3;
-        if (ok && occ_inside(g, x, y, z)) {
+        int x, y, z, s = 3;
+        if (occ_locate(g, pos + 3 * i, x, y, z) == kOccInside) {
             const int w = occ_word(g, x, y, z), b = occ_bit(x, y, z);
             s = ((occ[w] >> b) & 1u) ? 2 : (int)((fre[w] >> b) & 1u);
         }
@@ -179,7 +163,8 @@ __device__ __forceinline__ unsigned occ_frontier_word(unsigned cand, unsigned u,
 // the frontier word of brick word w < n_words: the two planes' words of the brick and of its six neighbours
 __device__ __forceinline__ unsigned occ_frontier_at(const unsigned* __restrict__ occ, const unsigned* __restrict__ fre, const OccGeom& g, int nbz,
                                                     long long w, int min_unknown) {
-    const int bx = (int)(w % g.nbx), by = (int)((w / g.nbx) % g.nby), bz = (int)(w / ((long long)g.nbx * g.nby));
+    int bx, by, bz;
+    occ_brick(g, w, bx, by, bz);
     const long long sy = g.nbx, sz = (long long)g.nbx * g.nby;
     const unsigned o = occ[w], f = fre[w], in = occ_brick_mask(g, bx, by, bz);
     const unsigned cand = f & ~o & in, u = ~f & ~o & in;
@@ -206,9 +191,7 @@ __device__ __forceinline__ unsigned occ_listed_bits(const unsigned* __restrict__
                                                     int& bx, int& by, int& bz) {
     bx = by = bz = 0;
     if (w >= n_words) return 0u;
-    bx = (int)(w % g.nbx);
-    by = (int)((w / g.nbx) % g.nby);
-    bz = (int)(w / ((long long)g.nbx * g.nby));
+    occ_brick(g, w, bx, by, bz);
     return words[w] & occ_brick_mask(g, bx, by, bz);
 }
 
@@ -273,7 +256,8 @@ k_occ_scatter(const unsigned* __restrict__ words, OccGeom g, long long n_words, 
         const int b = __ffs(bits) - 1;
         bits &= bits - 1u;
         if (at >= capacity) return;   // (offsets of another grid: nothing is written past the outputs)
-        const int x = 4 * bx + (b & 3), y = 4 * by + ((b >> 2) & 3), z = 2 * bz + (b >> 4);
+        int x, y, z;
+        occ_voxel(bx, by, bz, b, x, y, z);
         ijk[3 * at] = x;
         ijk[3 * at + 1] = y;
         ijk[3 * at + 2] = z;
@@ -286,6 +270,13 @@ k_occ_scatter(const unsigned* __restrict__ words, OccGeom g, long long n_words, 
 
 inline int64_t occ_list_blocks(const OccGeom& g) { return ((int64_t)occ_words(g.nx, g.ny, g.nz) + TO_BLOCK - 1) / TO_BLOCK; }
 
+// an output mask plane begins: its header is cleared (rc), and a kernel with one lane per word is sized
+struct OccMaskLaunch { int rc; unsigned blocks; long long n_words; };
+inline OccMaskLaunch occ_mask_begin(void* plane, const OccGeom& g, hipStream_t st) {
+    const hipError_t e = hipMemsetAsync(plane, 0, kOccHdr, st);
+    return {e == hipSuccess ? TOHIP_OK : (int)e, (unsigned)occ_list_blocks(g), (long long)occ_words(g.nx, g.ny, g.nz)};
+}
+
 }  // namespace
 
 extern "C" int tohip_occ_carve(void* free_grid, size_t grid_bytes, const tohip_occ_geom* geom, const float* origins, int64_t origin_stride,
@@ -294,10 +285,10 @@ extern "C" int tohip_occ_carve(void* free_grid, size_t grid_bytes, const tohip_o
     OccGeom g;
     const int rc = occ_check(free_grid, grid_bytes, geom, g);
     if (rc != TOHIP_OK) return rc;
-    if (n_rays < 0 || n_rays > (int64_t)1 << 40 || (n_rays > 0 && (!origins || !points))) return TOHIP_EINVAL;
+    if (!occ_count_ok(n_rays) || (n_rays > 0 && (!origins || !points))) return TOHIP_EINVAL;
     if ((origin_stride != 0 && origin_stride != 3) || max_range_fixed < 0 || max_range_fixed > kCarveMaxRange) return TOHIP_EINVAL;
     hipStream_t st = (hipStream_t)stream_;
-    hipError_t e = hipMemsetAsync(free_grid, 0, sizeof(unsigned long long), st);
+    const hipError_t e = hipMemsetAsync(free_grid, 0, sizeof(unsigned long long), st);
     if (e != hipSuccess) return (int)e;
     if (n_rays > 0) {
         k_occ_carve<<<occ_grid_blocks(n_rays), TO_BLOCK, 0, st>>>((unsigned long long*)free_grid, occ_data(free_grid), g, origins,
@@ -305,10 +296,7 @@ extern "C" int tohip_occ_carve(void* free_grid, size_t grid_bytes, const tohip_o
                                                                   (unsigned long long*)stats);
         TO_HIP_CHECK_LAUNCH();
     }
-    if (!skipped_host) return TOHIP_OK;
-    e = hipMemcpyAsync(skipped_host, free_grid, sizeof(int64_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return e == hipSuccess ? TOHIP_OK : (int)e;
+    return occ_read_back(skipped_host, free_grid, st);
 }
 
 extern "C" int tohip_occ_state(const void* occupied, const void* free_grid, size_t grid_bytes, const tohip_occ_geom* geom,
@@ -316,7 +304,7 @@ extern "C" int tohip_occ_state(const void* occupied, const void* free_grid, size
     OccGeom g;
     const int rc = occ_check(occupied, grid_bytes, geom, g);
     if (rc != TOHIP_OK) return rc;
-    if (!free_grid || m < 0 || m > (int64_t)1 << 40 || (m > 0 && (!positions || !out))) return TOHIP_EINVAL;
+    if (!free_grid || !occ_count_ok(m) || (m > 0 && (!positions || !out))) return TOHIP_EINVAL;
     if (m == 0) return TOHIP_OK;
     k_occ_state<<<occ_grid_blocks(m), TO_BLOCK, 0, (hipStream_t)stream_>>>(occ_data(occupied), occ_data(free_grid), g, positions, m, out);
     TO_HIP_CHECK_LAUNCH();
@@ -330,11 +318,10 @@ extern "C" int tohip_occ_frontier(const void* occupied, const void* free_grid, v
     if (rc != TOHIP_OK) return rc;
     if (!occupied || !free_grid || frontier == occupied || frontier == free_grid || min_unknown < 1 || min_unknown > 6) return TOHIP_EINVAL;
     hipStream_t st = (hipStream_t)stream_;
-    const hipError_t e = hipMemsetAsync(frontier, 0, kOccHdr, st);
-    if (e != hipSuccess) return (int)e;
-    const int64_t nw = (int64_t)occ_words(g.nx, g.ny, g.nz);
-    k_occ_frontier<<<(unsigned)occ_list_blocks(g), TO_BLOCK, 0, st>>>(occ_data(occupied), occ_data(free_grid), occ_data(frontier), g,
-                                                                      (g.nz + 1) / 2, nw, min_unknown);
+    const OccMaskLaunch m = occ_mask_begin(frontier, g, st);
+    if (m.rc != TOHIP_OK) return m.rc;
+    k_occ_frontier<<<m.blocks, TO_BLOCK, 0, st>>>(occ_data(occupied), occ_data(free_grid), occ_data(frontier), g, (g.nz + 1) / 2, m.n_words,
+                                                  min_unknown);
     TO_HIP_CHECK_LAUNCH();
     return TOHIP_OK;
 }
@@ -358,10 +345,7 @@ extern "C" int tohip_occ_count(const void* grid, size_t grid_bytes, const tohip_
     TO_HIP_CHECK_LAUNCH();
     k_occ_scan<<<1, TO_BLOCK, 0, st>>>(counts, nb);
     TO_HIP_CHECK_LAUNCH();
-    if (!total_host) return TOHIP_OK;
-    hipError_t e = hipMemcpyAsync(total_host, counts + nb, sizeof(int64_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return e == hipSuccess ? TOHIP_OK : (int)e;
+    return occ_read_back(total_host, counts + nb, st);
 }
 
 extern "C" int tohip_occ_export(const void* grid, size_t grid_bytes, const tohip_occ_geom* geom, const void* workspace,

@@ -10,14 +10,16 @@
 //   k_occ_insert     a row in range whose voxel lies inside dims: one 32-bit atomic OR; every other row is counted (per wave, one
 //                    add per wave).  Bits are never cleared: two inserts = one insert of the concatenation, in any order.
 //   k_occ_lookup     (M,3) int32 voxel indices -> uint8 (outside dims: 0).
-//   los_walk         A -> B in fixed point: D = B - A, s = sign D, m = |D|, v = A >> 8, e = B >> 8; per axis the distance to the next
-//                    face n = (v+1)*256 - A (s > 0) or A - v*256 (s < 0, may be 0); sum |e - v| steps, each along the axis — among
-//                    those with v_a != e_a — of the smallest n_a / m_a, compared as n_a m_b < n_b m_a in integers, ties to the
-//                    lowest axis; then v_a += s_a, n_a += 256.  The three cross terms n_a m_b - n_b m_a (up to 2^42: 64-bit) are
-//                    kept incrementally — a step adds 256 m to two of them — so the loop has no multiply.
-//                    A visited voxel is TESTED iff cheb(v, v0) >= start_skip and cheb(v, e) > end_skip; the ray is blocked iff a
-//                    tested voxel inside dims is occupied.  cheb(v, e) only falls along the walk: the loop ends where it reaches
-//                    end_skip.  The last word loaded stays in a register.
+//   occ_walk         the one walk of the map layer, A -> B in fixed point: D = B - A, s = sign D, m = |D|, v = A >> 8, e = B >> 8; per
+//                    axis the distance to the next face n = (v+1)*256 - A (s > 0) or A - v*256 (s < 0, may be 0); sum |e - v| steps,
+//                    each along the axis — among those with v_a != e_a — of the smallest n_a / m_a, compared as n_a m_b < n_b m_a in
+//                    integers, ties to the lowest axis; then v_a += s_a, n_a += 256.  The three cross terms n_a m_b - n_b m_a (up to
+//                    2^42: 64-bit) are kept incrementally — a step adds 256 m to two of them — so the loop has no multiply.
+//                    occ_walk(state, stop_at, visit) calls visit at every voxel with cheb(v, e) > stop_at, in walk order, then steps;
+//                    the state is left where the walk ended.  What happens at a voxel is the visitor's: line of sight here, the
+//                    carve in frontier_kernels.hip, the field's minimum in field_kernels.hip.
+//   los_walk         the visitor of line of sight, stop_at = end_skip: a visited voxel is TESTED iff cheb(v, v0) >= start_skip; the
+//                    ray is blocked iff a tested voxel inside dims is occupied.  The last word loaded stays in a register.
 //   k_los_segments   one lane per ray (a, b in world f32): 1 clear, 0 blocked, 2 an endpoint out of range.
 //   k_los_rows       the occlusion refresh in one launch, grid (runs of 8 packed 256-point tiles) x (waypoints): per point the exact
 //                    transform and frustum_pred — the device functions tohip_cull_waypoints runs, hence its bits — the kept points of
@@ -84,6 +86,28 @@ __device__ __forceinline__ bool occ_inside(const OccGeom& g, int x, int y, int z
 // word and bit of a voxel inside dims (at most 2^28 words)
 __device__ __forceinline__ int occ_word(const OccGeom& g, int x, int y, int z) { return ((z >> 1) * g.nby + (y >> 2)) * g.nbx + (x >> 2); }
 __device__ __forceinline__ int occ_bit(int x, int y, int z) { return (x & 3) | ((y & 3) << 2) | ((z & 1) << 4); }
+// ... and back: the brick of word w, the voxel of a brick's bit
+__device__ __forceinline__ void occ_brick(const OccGeom& g, long long w, int& bx, int& by, int& bz) {
+    bx = (int)(w % g.nbx), by = (int)((w / g.nbx) % g.nby), bz = (int)(w / ((long long)g.nbx * g.nby));
+}
+__device__ __forceinline__ void occ_voxel(int bx, int by, int bz, int bit, int& x, int& y, int& z) {
+    x = 4 * bx + (bit & 3), y = 4 * by + ((bit >> 2) & 3), z = 2 * bz + (bit >> 4);
+}
+
+// where the world point p[0 .. 2] lies, and its voxel (that of fixed point 0 on an axis out of range)
+enum OccPlace { kOccOutOfRange, kOccOutsideDims, kOccInside };
+__device__ __forceinline__ OccPlace occ_locate(const OccGeom& g, const float* __restrict__ p, int& x, int& y, int& z) {
+    int qx, qy, qz;
+    const bool ok = occ_fixed(g, p[0], p[1], p[2], qx, qy, qz);
+    x = qx >> 8, y = qy >> 8, z = qz >> 8;
+    return !ok ? kOccOutOfRange : (occ_inside(g, x, y, z) ? kOccInside : kOccOutsideDims);
+}
+
+// both ends of a leg a -> b in fixed point; false = an endpoint out of range
+__device__ __forceinline__ bool occ_fixed_leg(const OccGeom& g, const float* __restrict__ a, const float* __restrict__ b, int& ax, int& ay, int& az,
+                                              int& bx, int& by, int& bz) {
+    return occ_fixed(g, a[0], a[1], a[2], ax, ay, az) & occ_fixed(g, b[0], b[1], b[2], bx, by, bz);
+}
 
 // sum over the wave, added once per wave (every lane of the wave calls this)
 __device__ __forceinline__ void occ_count(unsigned long long* word, long long c) {
@@ -96,10 +120,8 @@ k_occ_insert(unsigned long long* __restrict__ hdr, unsigned* __restrict__ words,
     const long long stride = (long long)gridDim.x * TO_BLOCK;
     long long skipped = 0;
     for (long long i = (long long)blockIdx.x * TO_BLOCK + threadIdx.x; i < n; i += stride) {
-        int qx, qy, qz;
-        const bool ok = occ_fixed(g, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], qx, qy, qz);
-        const int x = qx >> 8, y = qy >> 8, z = qz >> 8;
-        if (ok && occ_inside(g, x, y, z))
+        int x, y, z;
+        if (occ_locate(g, pts + 3 * i, x, y, z) == kOccInside)
             __hip_atomic_fetch_or(words + occ_word(g, x, y, z), 1u << occ_bit(x, y, z), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else
             ++skipped;
@@ -134,34 +156,54 @@ __device__ __forceinline__ LosAxis los_axis(int a, int b, long long& n) {
     return x;
 }
 
+struct OccWalk {
+    LosAxis X, Y, Z;
+    long long c01, c02, c12, sx, sy, sz;   // the cross terms n_a m_b - n_b m_a and their increments 256 m
+};
+
+__device__ __forceinline__ OccWalk occ_walk_begin(int ax, int ay, int az, int bx, int by, int bz) {
+    OccWalk k;
+    long long n0, n1, n2;
+    k.X = los_axis(ax, bx, n0), k.Y = los_axis(ay, by, n1), k.Z = los_axis(az, bz, n2);
+    k.c01 = n0 * k.Y.m - n1 * k.X.m, k.c02 = n0 * k.Z.m - n2 * k.X.m, k.c12 = n1 * k.Z.m - n2 * k.Y.m;
+    k.sx = 256 * k.X.m, k.sy = 256 * k.Y.m, k.sz = 256 * k.Z.m;
+    return k;
+}
+
+// visit(k) at every voxel whose Chebyshev distance to the end voxel exceeds stop_at, in walk order, then the step; true = the visitor
+// stopped the walk.  k is left at the voxel where the walk ended.  (The distance only falls along the walk.)
+template <class Visit>
+__device__ __forceinline__ bool occ_walk(OccWalk& k, int stop_at, Visit&& visit) {
+    LosAxis &X = k.X, &Y = k.Y, &Z = k.Z;
+    for (;;) {
+        if (max(X.rem, max(Y.rem, Z.rem)) <= stop_at) return false;
+        if (visit(k)) return true;
+        // (some axis is active)
+        const bool a0 = X.rem > 0, a1 = Y.rem > 0, a2 = Z.rem > 0;
+        if (a0 && (!a1 || k.c01 <= 0) && (!a2 || k.c02 <= 0)) {
+            X.v += X.s; --X.rem; ++X.taken; k.c01 += k.sy; k.c02 += k.sz;
+        } else if (a1 && (!a2 || k.c12 <= 0)) {
+            Y.v += Y.s; --Y.rem; ++Y.taken; k.c01 -= k.sx; k.c12 += k.sz;
+        } else {
+            Z.v += Z.s; --Z.rem; ++Z.taken; k.c02 -= k.sx; k.c12 -= k.sy;
+        }
+    }
+}
+
 // 1 = clear, 0 = blocked; visits: the voxels the walk looked at (for the statistics)
 __device__ __forceinline__ int los_walk(const unsigned* __restrict__ words, const OccGeom& g, int ax, int ay, int az, int bx, int by, int bz,
                                         int start_skip, int end_skip, unsigned& visits) {
-    long long n0, n1, n2;
-    LosAxis X = los_axis(ax, bx, n0), Y = los_axis(ay, by, n1), Z = los_axis(az, bz, n2);
-    long long c01 = n0 * Y.m - n1 * X.m, c02 = n0 * Z.m - n2 * X.m, c12 = n1 * Z.m - n2 * Y.m;
-    const long long sx = 256 * X.m, sy = 256 * Y.m, sz = 256 * Z.m;
+    OccWalk k = occ_walk_begin(ax, ay, az, bx, by, bz);
     int cur = -1;
     unsigned word = 0;
-    for (;;) {
-        const int to_end = max(X.rem, max(Y.rem, Z.rem));
-        if (to_end <= end_skip) return 1;   // (it only falls from here on: nothing further is tested)
+    return !occ_walk(k, end_skip, [&](const OccWalk& at) {
+        const int x = at.X.v, y = at.Y.v, z = at.Z.v;
         ++visits;
-        if (max(X.taken, max(Y.taken, Z.taken)) >= start_skip && occ_inside(g, X.v, Y.v, Z.v)) {
-            const int w = occ_word(g, X.v, Y.v, Z.v);
-            if (w != cur) { word = words[w]; cur = w; }
-            if ((word >> occ_bit(X.v, Y.v, Z.v)) & 1u) return 0;
-        }
-        // (to_end > 0: some axis is active)
-        const bool a0 = X.rem > 0, a1 = Y.rem > 0, a2 = Z.rem > 0;
-        if (a0 && (!a1 || c01 <= 0) && (!a2 || c02 <= 0)) {
-            X.v += X.s; --X.rem; ++X.taken; c01 += sy; c02 += sz;
-        } else if (a1 && (!a2 || c12 <= 0)) {
-            Y.v += Y.s; --Y.rem; ++Y.taken; c01 -= sx; c12 += sz;
-        } else {
-            Z.v += Z.s; --Z.rem; ++Z.taken; c02 -= sx; c12 -= sy;
-        }
-    }
+        if (max(at.X.taken, max(at.Y.taken, at.Z.taken)) < start_skip || !occ_inside(g, x, y, z)) return false;
+        const int w = occ_word(g, x, y, z);
+        if (w != cur) { word = words[w]; cur = w; }
+        return (bool)((word >> occ_bit(x, y, z)) & 1u);
+    });
 }
 
 __global__ void __launch_bounds__(TO_BLOCK)
@@ -171,7 +213,7 @@ k_los_segments(const unsigned* __restrict__ words, OccGeom g, const float* __res
     long long rays = 0, visits = 0;
     for (long long i = (long long)blockIdx.x * TO_BLOCK + threadIdx.x; i < n_rays; i += stride) {
         int ax, ay, az, bx, by, bz;
-        const bool ok = occ_fixed(g, a[3 * i], a[3 * i + 1], a[3 * i + 2], ax, ay, az) & occ_fixed(g, b[3 * i], b[3 * i + 1], b[3 * i + 2], bx, by, bz);
+        const bool ok = occ_fixed_leg(g, a + 3 * i, b + 3 * i, ax, ay, az, bx, by, bz);
         int r = 2;
         if (ok) {
             unsigned v = 0;
@@ -272,6 +314,17 @@ __global__ void __launch_bounds__(TO_BLOCK) k_los_rows(LosRowsArgs a) {
     if (a.stats) { occ_count(a.stats, rays); occ_count(a.stats + 1, visits); }
 }
 
+// the row count of a query
+inline bool occ_count_ok(int64_t n) { return n >= 0 && n <= (int64_t)1 << 40; }
+
+// one int64 of device memory -> *host (null: not asked, nothing is read back); synchronises
+inline int occ_read_back(int64_t* host, const void* dev, hipStream_t st) {
+    if (!host) return TOHIP_OK;
+    hipError_t e = hipMemcpyAsync(host, dev, sizeof(int64_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    return e == hipSuccess ? TOHIP_OK : (int)e;
+}
+
 inline bool los_skips_ok(int start_skip, int end_skip) { return start_skip >= 0 && end_skip >= 0 && start_skip <= 8192 && end_skip <= 8192; }
 
 }  // namespace
@@ -293,18 +346,15 @@ extern "C" int tohip_occ_insert(void* grid, size_t grid_bytes, const tohip_occ_g
     OccGeom g;
     const int rc = occ_check(grid, grid_bytes, geom, g);
     if (rc != TOHIP_OK) return rc;
-    if (n < 0 || n > (int64_t)1 << 40 || (n > 0 && !points)) return TOHIP_EINVAL;
+    if (!occ_count_ok(n) || (n > 0 && !points)) return TOHIP_EINVAL;
     hipStream_t st = (hipStream_t)stream_;
-    hipError_t e = hipMemsetAsync(grid, 0, sizeof(unsigned long long), st);
+    const hipError_t e = hipMemsetAsync(grid, 0, sizeof(unsigned long long), st);
     if (e != hipSuccess) return (int)e;
     if (n > 0) {
         k_occ_insert<<<occ_grid_blocks(n), TO_BLOCK, 0, st>>>((unsigned long long*)grid, occ_data(grid), g, points, n);
         TO_HIP_CHECK_LAUNCH();
     }
-    if (!skipped_host) return TOHIP_OK;
-    e = hipMemcpyAsync(skipped_host, grid, sizeof(int64_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return e == hipSuccess ? TOHIP_OK : (int)e;
+    return occ_read_back(skipped_host, grid, st);
 }
 
 extern "C" int tohip_occ_lookup(const void* grid, size_t grid_bytes, const tohip_occ_geom* geom, const int32_t* ijk, int64_t m, uint8_t* out,
@@ -312,7 +362,7 @@ extern "C" int tohip_occ_lookup(const void* grid, size_t grid_bytes, const tohip
     OccGeom g;
     const int rc = occ_check(grid, grid_bytes, geom, g);
     if (rc != TOHIP_OK) return rc;
-    if (m < 0 || m > (int64_t)1 << 40 || (m > 0 && (!ijk || !out))) return TOHIP_EINVAL;
+    if (!occ_count_ok(m) || (m > 0 && (!ijk || !out))) return TOHIP_EINVAL;
     if (m == 0) return TOHIP_OK;
     k_occ_lookup<<<occ_grid_blocks(m), TO_BLOCK, 0, (hipStream_t)stream_>>>(occ_data(grid), g, ijk, m, out);
     TO_HIP_CHECK_LAUNCH();
@@ -324,7 +374,7 @@ extern "C" int tohip_los_segments(const void* grid, size_t grid_bytes, const toh
     OccGeom g;
     const int rc = occ_check(grid, grid_bytes, geom, g);
     if (rc != TOHIP_OK) return rc;
-    if (n_rays < 0 || n_rays > (int64_t)1 << 40 || (n_rays > 0 && (!a || !b || !out)) || !los_skips_ok(start_skip, end_skip)) return TOHIP_EINVAL;
+    if (!occ_count_ok(n_rays) || (n_rays > 0 && (!a || !b || !out)) || !los_skips_ok(start_skip, end_skip)) return TOHIP_EINVAL;
     if (n_rays == 0) return TOHIP_OK;
     k_los_segments<<<occ_grid_blocks(n_rays), TO_BLOCK, 0, (hipStream_t)stream_>>>(occ_data(grid), g, a, b, n_rays, start_skip, end_skip, out,
                                                                                   (unsigned long long*)stats);

@@ -776,6 +776,12 @@ def occupancy_extent(lo, hi, resolution, margin):
     return origin, dims
 
 
+def _map_call(device, name, *args):
+    """One call of the map layer's C entry `name` on `device`: the arguments, then the current stream; a failure raises by name."""
+    with torch.cuda.device(device):
+        check(getattr(_lib.lib(), name)(*args, stream_ptr()), name)
+
+
 class OccupancyGrid:
     """A dense occupancy bit grid on the device (occupancy_kernels.hip), filled from any number of clouds: voxel
     (i, j, k) is origin + [i, i+1) x [j, j+1) x [k, k+1) resolution, the index floor((x - origin) / resolution) in float32.  Around
@@ -794,8 +800,7 @@ class OccupancyGrid:
         nbytes = L.tohip_occ_bytes(*self.dims)
         self.buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self.skipped = 0   # rows skipped over every insert so far
-        with torch.cuda.device(self.device):
-            check(L.tohip_occ_init(*self._sizes(), stream_ptr()), "tohip_occ_init")
+        _map_call(self.device, "tohip_occ_init", *self._sizes())
 
     @classmethod
     def from_points(cls, points_or_cloud, resolution=0.1, margin=2):
@@ -827,8 +832,7 @@ class OccupancyGrid:
         dims).  One synchronisation (that count)."""
         pts = covmap_points(points_or_cloud, self.device, "OccupancyGrid.insert")
         skipped = ctypes.c_int64(0)
-        with torch.cuda.device(self.device):
-            check(_lib.lib().tohip_occ_insert(*self._sizes(), ptr(pts), pts.shape[0], ctypes.byref(skipped), stream_ptr()), "tohip_occ_insert")
+        _map_call(self.device, "tohip_occ_insert", *self._sizes(), ptr(pts), pts.shape[0], ctypes.byref(skipped))
         self.skipped += int(skipped.value)
         return int(skipped.value)
 
@@ -838,8 +842,7 @@ class OccupancyGrid:
             raise ValueError(f"ijk must be an (M,3) integer tensor, got {tuple(ijk.shape) if torch.is_tensor(ijk) else type(ijk).__name__}")
         q = ijk.to(device=self.device, dtype=torch.int32).contiguous()
         out = torch.empty(q.shape[0], dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            check(_lib.lib().tohip_occ_lookup(*self._sizes(), ptr(q), q.shape[0], ptr(out), stream_ptr()), "tohip_occ_lookup")
+        _map_call(self.device, "tohip_occ_lookup", *self._sizes(), ptr(q), q.shape[0], ptr(out))
         return out
 
     def dense(self):
@@ -854,9 +857,7 @@ class OccupancyGrid:
         _, _, _, (ss, es) = check_los(self.origin, self.resolution, self.dims, skip, a, b)
         a, b = covmap_points(a, self.device, "line_of_sight"), covmap_points(b, self.device, "line_of_sight")
         out = torch.empty(a.shape[0], dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            check(_lib.lib().tohip_los_segments(*self._sizes(), ptr(a), ptr(b), a.shape[0], ss, es, ptr(out), ptr(stats), stream_ptr()),
-                  "tohip_los_segments")
+        _map_call(self.device, "tohip_los_segments", *self._sizes(), ptr(a), ptr(b), a.shape[0], ss, es, ptr(out), ptr(stats))
         return out
 
     def empty_like(self):
@@ -879,18 +880,15 @@ class OccupancyGrid:
                                   or flags.device != self.device or not flags.is_contiguous()):
             raise ValueError(f"flags must be a contiguous ({pts.shape[0]},) uint8 tensor on {self.device}")
         skipped = ctypes.c_int64(0)
-        with torch.cuda.device(self.device):
-            check(_lib.lib().tohip_occ_carve(*self._sizes(), ptr(org), 0 if org.shape[0] == 1 else 3, ptr(pts), pts.shape[0], R, ptr(flags),
-                                             ptr(stats), ctypes.byref(skipped), stream_ptr()), "tohip_occ_carve")
+        _map_call(self.device, "tohip_occ_carve", *self._sizes(), ptr(org), 0 if org.shape[0] == 1 else 3, ptr(pts), pts.shape[0], R, ptr(flags),
+                  ptr(stats), ctypes.byref(skipped))
         return int(skipped.value)
 
     def _count(self):
         """-> (the number of set bits, the workspace holding the blocks' offsets for export); the one synchronisation."""
-        L = _lib.lib()
-        ws = torch.empty(L.tohip_occ_export_workspace_bytes(*self.dims), dtype=torch.uint8, device=self.device)
+        ws = torch.empty(_lib.lib().tohip_occ_export_workspace_bytes(*self.dims), dtype=torch.uint8, device=self.device)
         total = ctypes.c_int64(0)
-        with torch.cuda.device(self.device):
-            check(L.tohip_occ_count(*self._sizes(), ptr(ws), ws.numel(), ctypes.byref(total), stream_ptr()), "tohip_occ_count")
+        _map_call(self.device, "tohip_occ_count", *self._sizes(), ptr(ws), ws.numel(), ctypes.byref(total))
         return int(total.value), ws
 
     def count(self):
@@ -903,9 +901,7 @@ class OccupancyGrid:
         total, ws = self._count()
         ijk = torch.empty((total, 3), dtype=torch.int32, device=self.device)
         centres = torch.empty((total, 3), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(_lib.lib().tohip_occ_export(*self._sizes(), ptr(ws), ws.numel(), total, total, ptr(ijk), ptr(centres), stream_ptr()),
-                  "tohip_occ_export")
+        _map_call(self.device, "tohip_occ_export", *self._sizes(), ptr(ws), ws.numel(), total, total, ptr(ijk), ptr(centres))
         return ijk, centres
 
 
@@ -957,6 +953,23 @@ class Frontier:
         return int(self.ijk.shape[0])
 
 
+def _grid_difference(a, b):
+    """Two OccupancyGrids' geometry compared -> None where origin, resolution, dims and device agree, else (what, a's, b's) of the first
+    of these that differs."""
+    for what, x, y in (("origin", tuple(map(float, a.origin)), tuple(map(float, b.origin))), ("resolution", a.resolution, b.resolution),
+                       ("dims", a.dims, b.dims), ("device", a.device, b.device)):
+        if x != y:
+            return what, x, y
+    return None
+
+
+def _listed_plane(cls, like, name, head, tail):
+    """An empty plane of `like`'s geometry, filled by the C entry `name` (head, the plane, tail) and listed -> cls(ijk, centres, plane)."""
+    plane = like.empty_like()
+    _map_call(like.device, name, *head, *plane._sizes(), *tail)
+    return cls(*plane.export(), plane)
+
+
 def check_space_planes(occupied, free):
     """A SpaceMap's two planes: OccupancyGrids of one origin, resolution, dims and device, not the same grid; ValueError names what
     differs."""
@@ -965,14 +978,11 @@ def check_space_planes(occupied, free):
             raise ValueError(f"SpaceMap: {name} must be an ops.OccupancyGrid, got {type(g).__name__}")
     if free is occupied:
         raise ValueError("SpaceMap: free must not be the occupied grid itself")
-    if not np.array_equal(occupied.origin, free.origin):
-        raise ValueError(f"SpaceMap: the planes' origins differ ({tuple(map(float, occupied.origin))} and {tuple(map(float, free.origin))})")
-    if occupied.resolution != free.resolution:
-        raise ValueError(f"SpaceMap: the planes' resolutions differ ({occupied.resolution} and {free.resolution})")
-    if occupied.dims != free.dims:
-        raise ValueError(f"SpaceMap: the planes' dims differ ({occupied.dims} and {free.dims})")
-    if occupied.device != free.device:
-        raise ValueError(f"SpaceMap: the planes live on {occupied.device} and {free.device}")
+    diff = _grid_difference(occupied, free)
+    if diff:
+        texts = {"origin": "the planes' origins differ ({} and {})", "resolution": "the planes' resolutions differ ({} and {})",
+                 "dims": "the planes' dims differ ({} and {})", "device": "the planes live on {} and {}"}
+        raise ValueError("SpaceMap: " + texts[diff[0]].format(*diff[1:]))
 
 
 def check_min_unknown(min_unknown):
@@ -1012,21 +1022,14 @@ class SpaceMap:
         """(M,3) world positions -> (M,) uint8: 2 occupied, 1 free, 0 unknown, 3 beyond the apron, not finite or outside dims."""
         pos = covmap_points(positions, self.device, "SpaceMap.state")
         out = torch.empty(pos.shape[0], dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            check(_lib.lib().tohip_occ_state(ptr(self.occupied.buf), *self.free._sizes(), ptr(pos), pos.shape[0], ptr(out), stream_ptr()),
-                  "tohip_occ_state")
+        _map_call(self.device, "tohip_occ_state", ptr(self.occupied.buf), *self.free._sizes(), ptr(pos), pos.shape[0], ptr(out))
         return out
 
     def frontier(self, min_unknown=1):
         """The free voxels with at least min_unknown (1 .. 6) unknown face neighbours inside dims -> Frontier (ijk, points, grid, n).
         One synchronisation (n)."""
         k = check_min_unknown(min_unknown)
-        mask = self.free.empty_like()
-        with torch.cuda.device(self.device):
-            check(_lib.lib().tohip_occ_frontier(ptr(self.occupied.buf), ptr(self.free.buf), *mask._sizes(), k, stream_ptr()),
-                  "tohip_occ_frontier")
-        ijk, centres = mask.export()
-        return Frontier(ijk, centres, mask)
+        return _listed_plane(Frontier, self.free, "tohip_occ_frontier", (ptr(self.occupied.buf), ptr(self.free.buf)), (k,))
 
 
 FIELD_MAX_D = 254          # the largest truncation distance in voxels: D^2 < 65535, the sentinel
@@ -1078,11 +1081,9 @@ def check_field(grid_or_space, max_dist=None, unknown="free", D=None, radius=Non
     if space is not None:
         if not isinstance(space, SpaceMap):
             raise ValueError(f"space must be an ops.SpaceMap or None, got {type(space).__name__}")
-        for what, a, b in (("origin", tuple(map(float, space.occupied.origin)), tuple(map(float, occupied.origin))),
-                           ("resolution", space.occupied.resolution, r), ("dims", space.occupied.dims, occupied.dims),
-                           ("device", space.occupied.device, occupied.device)):
-            if a != b:
-                raise ValueError(f"space: its {what} differs from the field's ({a} and {b})")
+        diff = _grid_difference(space.occupied, occupied)
+        if diff:
+            raise ValueError("space: its {} differs from the field's ({} and {})".format(*diff))
     return occupied, (free if unknown == "obstacle" else None), D, need2
 
 
@@ -1120,10 +1121,8 @@ class ClearanceField:
     def rebuild(self):
         """Recompute the whole field from the same planes — after more inserts or carves — into the same buffers: three launches,
         nothing read back.  -> self."""
-        with torch.cuda.device(self.device):
-            check(_lib.lib().tohip_field_build(ptr(self.occupied.buf), ptr(self.free.buf) if self.free is not None else None,
-                                               self.occupied.buf.numel(), ctypes.byref(self.geom), self.D, ptr(self.buf), self.buf.numel(),
-                                               ptr(self._ws), self._ws.numel(), stream_ptr()), "tohip_field_build")
+        _map_call(self.device, "tohip_field_build", ptr(self.occupied.buf), ptr(self.free.buf) if self.free is not None else None,
+                  self.occupied.buf.numel(), ctypes.byref(self.geom), self.D, ptr(self.buf), self.buf.numel(), ptr(self._ws), self._ws.numel())
         return self
 
     def dense(self):
@@ -1135,9 +1134,7 @@ class ClearanceField:
         pos = covmap_points(p, self.device, "ClearanceField")
         d2 = torch.empty(pos.shape[0], dtype=torch.int32, device=self.device) if want_d2 else None
         dist = torch.empty(pos.shape[0], dtype=torch.float32, device=self.device) if want_dist else None
-        with torch.cuda.device(self.device):
-            check(_lib.lib().tohip_field_positions(*self._sizes(), ptr(pos), pos.shape[0], ptr(d2), ptr(dist), stream_ptr()),
-                  "tohip_field_positions")
+        _map_call(self.device, "tohip_field_positions", *self._sizes(), ptr(pos), pos.shape[0], ptr(d2), ptr(dist))
         return d2, dist
 
     def lookup_positions(self, p):
@@ -1150,21 +1147,22 @@ class ClearanceField:
         position's voxel to anything in an obstacle voxel; +inf for 65535, NaN out of range."""
         return self._positions(p, False, True)[1]
 
-    def _legs(self, a, b):
+    def _segments(self, a, b, need2=None):
+        """One launch of tohip_field_segments over the legs a[e] -> b[e] -> (d2, vox), two (E,) int32 — or, with need2, the edge answer
+        (d (E,) f32, idx (E,) int32)."""
         check_los(self.origin, self.resolution, self.dims, (0, 0), a, b)
-        return covmap_points(a, self.device, "ClearanceField"), covmap_points(b, self.device, "ClearanceField")
+        a, b = covmap_points(a, self.device, "ClearanceField"), covmap_points(b, self.device, "ClearanceField")
+        x = torch.empty(a.shape[0], dtype=torch.int32 if need2 is None else torch.float32, device=self.device)
+        y = torch.empty(a.shape[0], dtype=torch.int32, device=self.device)
+        outs = (ptr(x), ptr(y), 0, None, None) if need2 is None else (None, None, need2, ptr(x), ptr(y))
+        _map_call(self.device, "tohip_field_segments", *self._sizes(), ptr(a), ptr(b), a.shape[0], *outs)
+        return x, y
 
     def segments(self, a, b):
         """The legs a[e] -> b[e], two (E,3) tensors of world points -> (d2 (E,) int32, vox (E,) int32): the smallest squared gap over
         the voxels the leg crosses — line_of_sight's exact walk, every voxel of it — and the linear index (k ny + j) nx + i of the
         first crossed voxel that holds it.  65535 / -1: no obstacle within D voxels of the leg; -1 / -1: an endpoint out of range."""
-        a, b = self._legs(a, b)
-        d2 = torch.empty(a.shape[0], dtype=torch.int32, device=self.device)
-        vox = torch.empty(a.shape[0], dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(_lib.lib().tohip_field_segments(*self._sizes(), ptr(a), ptr(b), a.shape[0], ptr(d2), ptr(vox), 0, None, None, stream_ptr()),
-                  "tohip_field_segments")
-        return d2, vox
+        return self._segments(a, b)
 
     def need2(self, radius):
         """The squared gap that certifies `radius` metres (field_need2); ValueError where it exceeds D^2, naming the largest radius
@@ -1176,27 +1174,16 @@ class ClearanceField:
         certifies — every point of it at least `radius` from every obstacle voxel — is open: d +inf, idx -1.  Any other is blocked: d
         the gap in metres and idx the voxel's linear index; a leg with an endpoint out of range is never certified: d 0, idx -2.
         s is zeros.  One launch."""
-        need2 = self.need2(radius)
-        a, b = self._legs(a, b)
-        d = torch.empty(a.shape[0], dtype=torch.float32, device=self.device)
-        idx = torch.empty(a.shape[0], dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(_lib.lib().tohip_field_segments(*self._sizes(), ptr(a), ptr(b), a.shape[0], None, None, need2, ptr(d), ptr(idx),
-                                                  stream_ptr()), "tohip_field_segments")
-        return d, idx, torch.zeros(a.shape[0], dtype=torch.float32, device=self.device)
+        d, idx = self._segments(a, b, self.need2(radius))
+        return d, idx, torch.zeros(d.shape[0], dtype=torch.float32, device=self.device)
 
     def free_nodes(self, radius, stride=1, space=None):
         """Free-space nodes from the map itself: the voxels whose whole cube keeps `radius` from every obstacle voxel (field >= need2),
         one in stride^3 (every index = stride // 2 modulo stride) and — with a SpaceMap of this geometry — known to be free.
         -> FreeNodes (ijk, points = the centres, grid, n) in brick order.  One synchronisation (n)."""
         _, _, _, need2 = check_field(self.occupied, D=self.D, radius=check_tour_radius(radius), stride=stride, space=space)
-        plane = self.occupied.empty_like()
         occ, fre = (ptr(space.occupied.buf), ptr(space.free.buf)) if space is not None else (None, None)
-        with torch.cuda.device(self.device):
-            check(_lib.lib().tohip_field_nodes(ptr(self.buf), self.buf.numel(), occ, fre, *plane._sizes(), need2, int(stride), stream_ptr()),
-                  "tohip_field_nodes")
-        ijk, centres = plane.export()
-        return FreeNodes(ijk, centres, plane)
+        return _listed_plane(FreeNodes, self.occupied, "tohip_field_nodes", (ptr(self.buf), self.buf.numel(), occ, fre), (need2, int(stride)))
 
 
 def check_occlusion_grid(grid, cloud):
@@ -1219,12 +1206,10 @@ def los_rows(cloud, poses, quats, cam, min_dist, max_dist, grid, skip=(1, 1), pr
     q = quats.detach().to(device=dev, dtype=torch.float32).contiguous()
     if rows is None:
         rows = torch.empty((W, cloud.npad // 32), dtype=torch.int32, device=dev)
-    L = _lib.lib()
     for w0 in range(0, W, 65535):
         w1 = min(W, w0 + 65535)
-        with torch.cuda.device(dev):
-            check(L.tohip_los_rows(*grid._sizes(), ptr(cloud.blob), cloud.n, ptr(p[w0:w1]), ptr(q[w0:w1]), w1 - w0, cam.ref(), float(min_dist),
-                                   float(max_dist), ss, es, int(bool(prune)), ptr(rows[w0:w1]), ptr(stats), stream_ptr()), "tohip_los_rows")
+        _map_call(dev, "tohip_los_rows", *grid._sizes(), ptr(cloud.blob), cloud.n, ptr(p[w0:w1]), ptr(q[w0:w1]), w1 - w0, cam.ref(),
+                  float(min_dist), float(max_dist), ss, es, int(bool(prune)), ptr(rows[w0:w1]), ptr(stats))
     return rows
 
 

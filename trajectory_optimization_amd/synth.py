@@ -626,37 +626,25 @@ def occupancy_ref(points, origin, resolution, dims, occ=None):
     return out, int((~inside).sum())
 
 
-def los_fixed(A, B, occ, skip=(1, 1), trace=False):
-    """The walk from A to B, (R,3) integer fixed-point triples (both in range), through occ (nx,ny,nz) bool -> blocked (R,) bool.
-    v = A >> 8, e = B >> 8, n = the distance to the next face ((v+1) 256 - A going up, A - v 256 going down); sum |e - v| steps, each
-    along the axis — among those with v_a != e_a — of the smallest n_a / m_a (n_a m_b < n_b m_a in int64, ties to the lowest axis);
-    a visited voxel is tested iff cheb(v, v0) >= skip[0] and cheb(v, e) > skip[1]; blocked iff a tested voxel inside dims is
-    occupied.  Vectorised over the rays still walking.  trace: every ray walks to its end and (blocked, visited) is returned,
-    visited[r] the list of ray r's voxels v0 .. e."""
+def walk_fixed(A, B, visit):
+    """The walk from A to B, (R,3) integer fixed-point triples (both in range), vectorised over the rays still walking — the one
+    restatement of the kernels' step block.  v = A >> 8, e = B >> 8, n = the distance to the next face ((v+1) 256 - A going up, A - v
+    256 going down); sum |e - v| steps, each along the axis — among those with v_a != e_a — of the smallest n_a / m_a (n_a m_b < n_b
+    m_a in int64, ties to the lowest axis).  At every round visit(idx, vi, last) gets the rays still walking, their voxels and which
+    of them stand on their end voxel; it returns the rays that walk on as a bool array, or None for all.  A ray on its end voxel
+    stops whatever visit says."""
     A, B = np.asarray(A, dtype=np.int64).reshape(-1, 3), np.asarray(B, dtype=np.int64).reshape(-1, 3)
-    occ = np.asarray(occ, dtype=bool)
-    dims = np.asarray(occ.shape, dtype=np.int64)
-    ss, es = int(skip[0]), int(skip[1])
-    R = len(A)
     D = B - A
     s, m = np.sign(D), np.abs(D)
-    v0, e = A >> 8, B >> 8
-    v = v0.copy()
+    e = B >> 8
+    v = A >> 8
     n = np.where(s > 0, (v + 1) * 256 - A, A - v * 256)
-    blocked = np.zeros(R, dtype=bool)
-    visited = [[] for _ in range(R)] if trace else None
-    idx = np.arange(R)
+    idx = np.arange(len(A))
     while len(idx):
         vi = v[idx]
-        if trace:
-            for k, r in enumerate(idx):
-                visited[r].append(tuple(int(c) for c in vi[k]))
-        tested = (np.abs(vi - v0[idx]).max(axis=1) >= ss) & (np.abs(vi - e[idx]).max(axis=1) > es)
-        t = tested & ((vi >= 0) & (vi < dims[None, :])).all(axis=1)
-        hit = np.zeros(len(idx), dtype=bool)
-        hit[t] = occ[vi[t, 0], vi[t, 1], vi[t, 2]]
-        blocked[idx[hit]] = True
-        idx = idx[(trace | ~hit) & (vi != e[idx]).any(axis=1)]
+        last = (vi == e[idx]).all(axis=1)
+        go = visit(idx, vi, last)
+        idx = idx[~last if go is None else go & ~last]
         if not len(idx):
             break
         act, ni, mi = v[idx] != e[idx], n[idx], m[idx]
@@ -668,6 +656,32 @@ def los_fixed(A, B, occ, skip=(1, 1), trace=False):
             nb, mb = np.where(take, ni[:, a], nb), np.where(take, mi[:, a], mb)
         v[idx, best] += s[idx, best]
         n[idx, best] += 256
+
+
+def los_fixed(A, B, occ, skip=(1, 1), trace=False):
+    """walk_fixed from A to B through occ (nx,ny,nz) bool -> blocked (R,) bool: a visited voxel is tested iff cheb(v, v0) >= skip[0]
+    and cheb(v, e) > skip[1]; blocked iff a tested voxel inside dims is occupied, and the ray stops there.  trace: every ray walks to
+    its end and (blocked, visited) is returned, visited[r] the list of ray r's voxels v0 .. e."""
+    A, B = np.asarray(A, dtype=np.int64).reshape(-1, 3), np.asarray(B, dtype=np.int64).reshape(-1, 3)
+    occ = np.asarray(occ, dtype=bool)
+    dims = np.asarray(occ.shape, dtype=np.int64)
+    ss, es = int(skip[0]), int(skip[1])
+    v0, e = A >> 8, B >> 8
+    blocked = np.zeros(len(A), dtype=bool)
+    visited = [[] for _ in range(len(A))] if trace else None
+
+    def visit(idx, vi, last):
+        if trace:
+            for k, r in enumerate(idx):
+                visited[r].append(tuple(int(c) for c in vi[k]))
+        tested = (np.abs(vi - v0[idx]).max(axis=1) >= ss) & (np.abs(vi - e[idx]).max(axis=1) > es)
+        t = tested & ((vi >= 0) & (vi < dims[None, :])).all(axis=1)
+        hit = np.zeros(len(idx), dtype=bool)
+        hit[t] = occ[vi[t, 0], vi[t, 1], vi[t, 2]]
+        blocked[idx[hit]] = True
+        return None if trace else ~hit
+
+    walk_fixed(A, B, visit)
     return (blocked, visited) if trace else blocked
 
 
@@ -699,38 +713,20 @@ def carve_clip(A, B, R):
 
 
 def carve_fixed(A, B, hit, free):
-    """Walk A -> B (fixed-point triples, in range) exactly as los_fixed does and set free[v] for every visited voxel inside dims,
-    except the last voxel of a ray with hit[i]; free (nx,ny,nz) bool is modified in place.  -> the number of voxels visited (v_0 ...
-    v_T of every ray).  Vectorised over the rays still walking; tests/test_frontier_cpu.py checks it against los_fixed(trace=True)."""
-    A, B = np.asarray(A, dtype=np.int64).reshape(-1, 3), np.asarray(B, dtype=np.int64).reshape(-1, 3)
+    """walk_fixed from A to B (fixed-point triples, in range), setting free[v] for every visited voxel inside dims except the last
+    voxel of a ray with hit[i]; free (nx,ny,nz) bool is modified in place.  -> the number of voxels visited (v_0 ... v_T of every
+    ray).  tests/test_frontier_cpu.py checks it against los_fixed(trace=True)."""
     hit = np.asarray(hit, dtype=bool).reshape(-1)
     dims = np.asarray(free.shape, dtype=np.int64)
-    D = B - A
-    s, m = np.sign(D), np.abs(D)
-    e = B >> 8
-    v = A >> 8
-    n = np.where(s > 0, (v + 1) * 256 - A, A - v * 256)
-    idx = np.arange(len(A))
-    visits = 0
-    while len(idx):
-        vi = v[idx]
-        visits += len(idx)
-        last = (vi == e[idx]).all(axis=1)
+    visits = [0]
+
+    def visit(idx, vi, last):
+        visits[0] += len(idx)
         mark = ~(last & hit[idx]) & ((vi >= 0) & (vi < dims[None, :])).all(axis=1)
         free[vi[mark, 0], vi[mark, 1], vi[mark, 2]] = True
-        idx = idx[~last]
-        if not len(idx):
-            break
-        act, ni, mi = v[idx] != e[idx], n[idx], m[idx]
-        best = np.full(len(idx), -1, dtype=np.int64)
-        nb, mb = np.zeros(len(idx), dtype=np.int64), np.ones(len(idx), dtype=np.int64)
-        for a in range(3):
-            take = act[:, a] & ((best < 0) | (ni[:, a] * mb < nb * mi[:, a]))
-            best = np.where(take, a, best)
-            nb, mb = np.where(take, ni[:, a], nb), np.where(take, mi[:, a], mb)
-        v[idx, best] += s[idx, best]
-        n[idx, best] += 256
-    return visits
+
+    walk_fixed(A, B, visit)
+    return visits[0]
 
 
 def carve_range(max_range, resolution):
