@@ -8,7 +8,11 @@
  * reference would add.
  *
  * Conventions
- *   - every pointer is a DEVICE pointer unless its name ends in _host;
+ *   - every pointer is a DEVICE pointer unless its name ends in _host.  The suffix is load-bearing: the Python binding
+ *     (trajectory_optimization_amd/_lib.py) is read from this file, and it types a parameter named *_host as a pointer to its
+ *     pointee (or to the struct it names) and every other pointer as an opaque address — a new HOST pointer must be named *_host,
+ *     and every declaration here must be one that reader knows (fixed-width scalars, int, size_t, float, double, pointers to them,
+ *     the structs below);
  *   - the caller allocates every input, output and workspace buffer, and no DEVICE memory is ever allocated or freed by the
  *     library.  Nothing a call computes is kept for a later call.  The two things the library does keep, both HOST-side
  *     scratch that never changes a result:
@@ -60,6 +64,8 @@ extern "C" {
  * (still 15) + tohip_team_step_tail / tohip_team_loss / tohip_team_member_gains / tohip_team_state_bytes /
  * tohip_team_member_gains_bytes (team coverage): new symbols only — no struct and no existing signature changes, so a caller built
  * against the earlier header of 15 works unchanged and the number stays.
+ * (still 15) + tohip_traj_prior_bytes / tohip_traj_prior_build / tohip_traj_reward_prior / tohip_traj_reward_backward_prior /
+ * tohip_traj_backward_prior / tohip_traj_coverage (a per-point log-odds prior): new symbols only.
  * 15: + tohip_clearance / tohip_clearance_workspace_bytes / tohip_traj_clearance_scratch_bytes / tohip_traj_step_tail_clearance /
  * tohip_traj_regularizers_clearance (the clearance term); tohip_traj_loss and tohip_traj_opt gain clearance_radius,
  * clearance_weight, clearance_scratch(_bytes) at their ends (zero = off).
@@ -350,9 +356,10 @@ typedef struct tohip_traj_loss {
     size_t scratch_bytes;
     float *reg_terms;        /* NULL, or (3, W, 3) floats: the gradients of l2, length and smooth separately (callers that
                                 differentiate a single entry of model.loss) */
-    /* the clearance term (tohip_clearance); clearance_weight = 0: off (model() is then exactly the four-term criterion).  On:
-       model() launches the query first (five launches), loss_terms[5] = clearance and total includes it; loss.backward() adds
-       gout x its gradient rows to the regularisers' before the visibility rows: vis + gout (regularisers + clearance) */
+    /* ABI 15, appended after every earlier field: the clearance term (tohip_clearance); clearance_weight = 0: off (model() is then
+       exactly the four-term criterion).  On: model() launches the query first (five launches), loss_terms[5] = clearance and total
+       includes it; loss.backward() adds gout x its gradient rows to the regularisers' before the visibility rows:
+       vis + gout (regularisers + clearance) */
     float clearance_radius;
     float clearance_weight;
     void *clearance_scratch;  /* tohip_traj_clearance_scratch_bytes(W, 1): its gradient rows (W,3) f32 at offset 0, then the terms
@@ -418,10 +425,10 @@ typedef struct tohip_traj_opt {
     size_t workspace_bytes;
     void *scratch;             /* tohip_traj_opt_scratch_bytes(n_wps, n_traj) */
     size_t scratch_bytes;
-    /* the clearance term (tohip_clearance) of every trajectory; clearance_weight = 0: off — the step's launches, grids and outputs
-       are then exactly those without these fields.  On: a SIXTH launch, first, queries every waypoint (n_traj W waves); the sparse
-       launch's prologue blocks sum the terms, the finish epilogue's full gradient is vis + (regularisers + clearance) and the loss
-       log row gets [5] = clearance (total includes it) */
+    /* ABI 15, appended after every earlier field: the clearance term (tohip_clearance) of every trajectory; clearance_weight = 0:
+       off — the step's launches, grids and outputs are then exactly those without these fields.  On: a SIXTH launch, first, queries
+       every waypoint (n_traj W waves); the sparse launch's prologue blocks sum the terms, the finish epilogue's full gradient is
+       vis + (regularisers + clearance) and the loss log row gets [5] = clearance (total includes it) */
     float clearance_radius;
     float clearance_weight;
     void *clearance_scratch;   /* tohip_traj_clearance_scratch_bytes(n_wps, n_traj) (TOHIP_TRAJ_CLEARANCE_SEGMENTS:
@@ -525,9 +532,9 @@ typedef struct tohip_pose_opt {
     float *loss_log;           /* (B, n_steps): loss_log[b n_steps + step - 1] = pose b's loss of this step (before the update) */
     void *workspace;           /* tohip_pose_workspace_bytes_multi(n_points, n_poses) */
     size_t workspace_bytes;
-    const uint32_t *occlusion_bits;   /* (B, Npad/32) or NULL: each pose's own occlusion bit row (tohip_pose_forward_backward_multi_bits);
-                                         giving occlusion_mask too is an error (TOHIP_EINVAL).  A refresh may replace the pointer between
-                                         steps. */
+    const uint32_t *occlusion_bits;   /* ABI 14, appended after every earlier field.  (B, Npad/32) or NULL: each pose's own occlusion
+                                         bit row (tohip_pose_forward_backward_multi_bits); giving occlusion_mask too is an error
+                                         (TOHIP_EINVAL).  A refresh may replace the pointer between steps. */
 } tohip_pose_opt;
 /* step = 1, 2, ... n_steps, in order.  observations (B,N) or NULL: pass it on the step that should leave them (the last).
  * Two launches; nothing synchronises. */

@@ -1,11 +1,10 @@
 """CPU checks of the clearance term's C ABI (no GPU): the new struct fields come after every existing one, and tohip_clearance
 refuses null or bad arguments before any launch."""
 import ctypes
-import os
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_cases import check_abi_entries
 
 
 def _prefix_layout(struct, upto):
@@ -40,10 +39,10 @@ def test_new_fields_come_last(name):
 
 def test_header_declares_the_clearance_abi():
     from trajectory_optimization_amd import _lib
-    header = open(os.path.join(REPO, "include", "trajopt_hip.h")).read()
-    assert "#define TOHIP_ABI_VERSION 15" in header and _lib.ABI_VERSION == 15
-    for sym in ("tohip_clearance", "tohip_clearance_workspace_bytes", "tohip_traj_clearance_scratch_bytes", "tohip_traj_regularizers_clearance",
-                "tohip_traj_step_tail_clearance"):
+    entries = ("tohip_clearance", "tohip_clearance_workspace_bytes", "tohip_traj_clearance_scratch_bytes", "tohip_traj_regularizers_clearance",
+               "tohip_traj_step_tail_clearance")
+    header, _ = check_abi_entries(entries)
+    for sym in entries:
         assert sym + "(" in header and sym in _lib.SIGNATURES
     for struct in ("tohip_traj_loss", "tohip_traj_opt"):
         body = header[header.index(f"typedef struct {struct} {{"):]

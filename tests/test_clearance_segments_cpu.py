@@ -1,22 +1,21 @@
 """CPU checks of the swept clearance term's C ABI and host settings (no GPU): new symbols and one flag bit under ABI 15, the sizes,
 tohip_clearance_segments refusing bad arguments before any launch, and ModelTraj's clearance_mode."""
 import ctypes
-import os
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_cases import ABI, check_abi_entries
+
 NEW = ("tohip_clearance_segments", "tohip_clearance_segments_workspace_bytes", "tohip_traj_clearance_segments_scratch_bytes")
 
 
 def test_header_declares_the_segments_abi():
     from trajectory_optimization_amd import _lib, ops
-    header = open(os.path.join(REPO, "include", "trajopt_hip.h")).read()
-    assert "#define TOHIP_ABI_VERSION 15" in header and _lib.ABI_VERSION == 15
+    header, _ = check_abi_entries(NEW)
     for sym in NEW:
         assert sym + "(" in header and sym in _lib.SIGNATURES
     assert "#define TOHIP_TRAJ_CLEARANCE_SEGMENTS 4" in header and ops.CLEARANCE_SEGMENTS == 4
-    still = [line for line in header.splitlines() if "(still 15)" in line]
+    still = [line for line in header.splitlines() if f"(still {ABI})" in line]
     assert any("tohip_clearance_segments" in line for line in still)
     for struct in ("tohip_traj_loss", "tohip_traj_opt"):
         body = header[header.index(f"typedef struct {struct} {{"):]

@@ -4,11 +4,12 @@ field_segments_ref / field_need2 / field_nodes_ref, what the kernels are compare
 other, on hand cases, against f64 point-segment distances in a scanned room and — for the centre metric — against scipy."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
+
+from abi_cases import check_abi_entries
 
 from trajectory_optimization_amd import synth
 
@@ -20,16 +21,8 @@ SMALL = ((5, 6, 3), (1, 1, 1), (12, 9, 7), (16, 16, 8))
 
 
 def test_header_and_table_declare_the_new_entries_at_abi_15():
-    from trajectory_optimization_amd import _lib
-    header = open(os.path.join(REPO, "include", "trajopt_hip.h")).read()
-    assert "#define TOHIP_ABI_VERSION 15" in header and _lib.ABI_VERSION == 15 == _lib.lib().tohip_abi_version()
-    for sym in ENTRIES:
-        decl = re.search(r"\b(?:int|size_t)\s+" + sym + r"\(([^;]*)\);", header)
-        assert decl, sym
-        n_args = len([a for a in decl.group(1).split(",") if a.strip()])
-        assert sym in _lib.SIGNATURES and len(_lib.SIGNATURES[sym][1]) == n_args, sym
-        assert hasattr(_lib.lib(), sym)
-    assert "tohip_field_build" in header.split("#define TOHIP_ABI_VERSION")[0]
+    header, before = check_abi_entries(ENTRIES)
+    assert "tohip_field_build" in before
     src = open(os.path.join(REPO, "trajectory_optimization_amd", "csrc", "trajopt_hip.hip")).read()
     assert '#include "frontier_kernels.hip"\n#include "field_kernels.hip"' in src
 

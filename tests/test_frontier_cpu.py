@@ -5,11 +5,12 @@ for bit) are checked on hand cases, against los_fixed's trace, and on a scanned 
 import ctypes
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
+
+from abi_cases import check_abi_entries
 
 from trajectory_optimization_amd import synth
 
@@ -22,16 +23,8 @@ SCANNER = np.float32([1.03, 0.97, 0.52])
 
 
 def test_header_and_table_declare_the_new_entries_at_abi_15():
-    from trajectory_optimization_amd import _lib
-    header = open(os.path.join(REPO, "include", "trajopt_hip.h")).read()
-    assert "#define TOHIP_ABI_VERSION 15" in header and _lib.ABI_VERSION == 15 == _lib.lib().tohip_abi_version()
-    for sym in ENTRIES:
-        decl = re.search(r"\b(?:int|size_t)\s+" + sym + r"\(([^;]*)\);", header)
-        assert decl, sym
-        n_args = len([a for a in decl.group(1).split(",") if a.strip()])
-        assert sym in _lib.SIGNATURES and len(_lib.SIGNATURES[sym][1]) == n_args, sym
-        assert hasattr(_lib.lib(), sym)
-    assert "tohip_occ_carve" in header.split("#define TOHIP_ABI_VERSION")[0]
+    header, before = check_abi_entries(ENTRIES)
+    assert "tohip_occ_carve" in before
     src = open(os.path.join(REPO, "trajectory_optimization_amd", "csrc", "trajopt_hip.hip")).read()
     assert '#include "occupancy_kernels.hip"\n#include "frontier_kernels.hip"' in src
 

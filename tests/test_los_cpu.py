@@ -4,11 +4,12 @@ restatement of the walk (synth.los_fixed / los_ref, what the kernels are compare
 independent dense f64 sampling of the segments and against hand-made cases."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
+
+from abi_cases import check_abi_entries
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, ENOSPC = -1, -2
@@ -18,15 +19,8 @@ OLD_MESSAGE = "occlusion must be None, 'hpr' or 'zbuffer'"
 
 def test_header_and_table_declare_the_six_entries():
     from trajectory_optimization_amd import _lib
-    header = open(os.path.join(REPO, "include", "trajopt_hip.h")).read()
-    assert "#define TOHIP_ABI_VERSION 15" in header and _lib.ABI_VERSION == 15 == _lib.lib().tohip_abi_version()
-    for sym in ENTRIES:
-        decl = re.search(r"\b(?:int|size_t)\s+" + sym + r"\(([^;]*)\);", header)
-        assert decl, sym
-        n_args = len([a for a in decl.group(1).split(",") if a.strip()])
-        assert sym in _lib.SIGNATURES and len(_lib.SIGNATURES[sym][1]) == n_args, sym
-        assert hasattr(_lib.lib(), sym)
-    assert "tohip_los_rows" in header.split("#define TOHIP_ABI_VERSION")[0]
+    header, before = check_abi_entries(ENTRIES)
+    assert "tohip_los_rows" in before
     src = open(os.path.join(REPO, "trajectory_optimization_amd", "csrc", "trajopt_hip.hip")).read()
     assert '#include "occupancy_kernels.hip"' in src
     assert ctypes.sizeof(_lib.OccGeom) == 28   # struct tohip_occ_geom: 3 f32, f32, 3 int32

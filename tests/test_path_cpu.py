@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+from abi_cases import ABI, check_abi_entries
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, ENOSPC = -1, -2
 ENTRIES = ("tohip_path_bytes", "tohip_path_refine")
@@ -20,18 +22,9 @@ ONE = 1 << 20   # a metre in the integer lengths' unit
 
 
 def test_header_and_table_declare_the_path_entries():
-    from trajectory_optimization_amd import _lib, ops, synth
-    header = open(os.path.join(REPO, "include", "trajopt_hip.h")).read()
-    assert "#define TOHIP_ABI_VERSION 15" in header and _lib.ABI_VERSION == 15 == _lib.lib().tohip_abi_version()
-    before = header.split("#define TOHIP_ABI_VERSION")[0]
-    for sym in ENTRIES:
-        decl = re.search(r"\b(?:int|size_t)\s+" + sym + r"\(([^;]*)\);", header)
-        assert decl, sym
-        n_args = len([a for a in decl.group(1).split(",") if a.strip()])
-        assert sym in _lib.SIGNATURES and len(_lib.SIGNATURES[sym][1]) == n_args, sym
-        assert hasattr(_lib.lib(), sym)
-        assert sym in before, sym   # the changelog line
-    assert re.search(r"\(still 15\) \+ tohip_path_bytes", before)
+    from trajectory_optimization_amd import ops, synth
+    header, before = check_abi_entries(ENTRIES)
+    assert re.search(rf"\(still {ABI}\) \+ tohip_path_bytes", before)
     for name, v in (("NODES", 1024), ("ROWS", 4096)):
         assert f"#define TOHIP_PATH_MAX_{name} {v}\n" in header
         assert getattr(ops, f"PATH_MAX_{name}") == v == getattr(synth, f"PATH_MAX_{name}")

@@ -1,11 +1,8 @@
 """CPU-side checks of the per-pose occlusion rows' C ABI (no GPU): tohip_pose_opt as the C compiler lays it out is what _lib.PoseOpt
 declares, and the bit-row twins are exported.  (The argument errors are checked with real buffers in test_hip_pose_occlusion.py.)"""
 import ctypes
-import os
-import shutil
-import subprocess
 
-from conftest import REPO
+from abi_cases import c_layouts
 
 
 _FIELDS = ("packed", "n_points", "n_poses", "n_steps", "cam", "occlusion_mask", "trans", "quat", "lr_pose", "lr_quat", "beta1", "beta2",
@@ -14,21 +11,13 @@ _FIELDS = ("packed", "n_points", "n_poses", "n_steps", "cam", "occlusion_mask", 
 
 
 def test_pose_opt_layout_matches_the_c_compiler(tmp_path):
+    """(Every struct of the header, by the same compile: tests/test_bindings_cpu.py.)"""
     from trajectory_optimization_amd import _lib
-    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang") or "/opt/rocm/llvm/bin/clang"   # (the library's toolchain)
-    src = tmp_path / "layout.c"
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "trajopt_hip.h"', "int main(void) {",
-             '    printf("sizeof %zu\\n", sizeof(tohip_pose_opt));']
-    lines += [f'    printf("{f} %zu\\n", offsetof(tohip_pose_opt, {f}));' for f in _FIELDS]
-    lines += ["    return 0;", "}"]
-    src.write_text("\n".join(lines) + "\n")
-    exe = tmp_path / "layout"
-    subprocess.check_call([cc, "-std=c99", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)])
-    got = dict(line.split() for line in subprocess.check_output([str(exe)], text=True).splitlines())
-    assert int(got["sizeof"]) == ctypes.sizeof(_lib.PoseOpt)
+    got = c_layouts({"tohip_pose_opt": _FIELDS}, tmp_path)["tohip_pose_opt"]
+    assert got["sizeof"] == ctypes.sizeof(_lib.PoseOpt)
     assert [name for name, _ in _lib.PoseOpt._fields_] == list(_FIELDS)
     for f in _FIELDS:
-        assert int(got[f]) == getattr(_lib.PoseOpt, f).offset, f
+        assert got[f] == getattr(_lib.PoseOpt, f).offset, f
     assert _lib.PoseOpt._fields_[-1][0] == "occlusion_bits"   # appended: every earlier offset is ABI 13's
 
 

@@ -2,12 +2,12 @@
 version, the prior buffer's size follows its layout, every entry refuses null or bad arguments before any launch, and
 ops.check_prior refuses what is not a finite, non-negative prior of one entry per point."""
 import ctypes
-import os
 
 import pytest
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_cases import check_abi_entries
+
 EINVAL, ENOSPC = -1, -2
 NEW = ("tohip_traj_prior_bytes", "tohip_traj_prior_build", "tohip_traj_reward_prior", "tohip_traj_reward_backward_prior",
        "tohip_traj_backward_prior", "tohip_traj_coverage")
@@ -15,11 +15,9 @@ NEW = ("tohip_traj_prior_bytes", "tohip_traj_prior_build", "tohip_traj_reward_pr
 
 def test_header_declares_the_prior_entries():
     from trajectory_optimization_amd import _lib
-    header = open(os.path.join(REPO, "include", "trajopt_hip.h")).read()
-    assert "#define TOHIP_ABI_VERSION 15" in header and _lib.ABI_VERSION == 15 == _lib.lib().tohip_abi_version()
+    header, _ = check_abi_entries(NEW)
     for sym in NEW:
         assert sym + "(" in header and sym in _lib.SIGNATURES
-        assert hasattr(_lib.lib(), sym)
     # the _prior variants are the existing argument lists plus the prior buffer before the stream
     for old, new in (("tohip_traj_reward", "tohip_traj_reward_prior"), ("tohip_traj_reward_backward", "tohip_traj_reward_backward_prior"),
                      ("tohip_traj_backward", "tohip_traj_backward_prior")):

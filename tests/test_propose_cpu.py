@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+from abi_cases import ABI, check_abi_entries
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL = -1
 ENTRIES = ("tohip_view_histogram", "tohip_view_headings")
@@ -20,18 +22,9 @@ f32 = np.float32
 
 
 def test_header_and_table_declare_the_view_entries():
-    from trajectory_optimization_amd import _lib, ops, synth
-    header = open(os.path.join(REPO, "include", "trajopt_hip.h")).read()
-    assert "#define TOHIP_ABI_VERSION 15" in header and _lib.ABI_VERSION == 15 == _lib.lib().tohip_abi_version()
-    before = header.split("#define TOHIP_ABI_VERSION")[0]
-    for sym in ENTRIES:
-        decl = re.search(r"\bint\s+" + sym + r"\(([^;]*)\);", header)
-        assert decl, sym
-        n_args = len([a for a in decl.group(1).split(",") if a.strip()])
-        assert sym in _lib.SIGNATURES and len(_lib.SIGNATURES[sym][1]) == n_args, sym
-        assert hasattr(_lib.lib(), sym)
-        assert sym in before, sym   # the changelog line
-    assert re.search(r"\(still 15\) \+ tohip_view_histogram", before)
+    from trajectory_optimization_amd import ops, synth
+    header, before = check_abi_entries(ENTRIES)
+    assert re.search(rf"\(still {ABI}\) \+ tohip_view_histogram", before)
     for name, v in (("POSITIONS", 65536), ("PER_POSITION", 8)):
         assert f"#define TOHIP_VIEW_MAX_{name} {v}\n" in header
         assert getattr(ops, f"VIEW_MAX_{name}") == v == getattr(synth, f"VIEW_MAX_{name}")

@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+from abi_cases import ABI, check_abi_entries
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, ENOSPC = -1, -2
 ENTRIES = ("tohip_roadmap_knn", "tohip_roadmap_routes_bytes", "tohip_roadmap_relax", "tohip_roadmap_pred", "tohip_tour_plan_via")
@@ -19,17 +21,8 @@ ENTRIES = ("tohip_roadmap_knn", "tohip_roadmap_routes_bytes", "tohip_roadmap_rel
 
 def test_header_and_table_declare_the_roadmap_entries():
     from trajectory_optimization_amd import _lib, ops, synth
-    header = open(os.path.join(REPO, "include", "trajopt_hip.h")).read()
-    assert "#define TOHIP_ABI_VERSION 15" in header and _lib.ABI_VERSION == 15 == _lib.lib().tohip_abi_version()
-    before = header.split("#define TOHIP_ABI_VERSION")[0]
-    for sym in ENTRIES:
-        decl = re.search(r"\b(?:int|size_t)\s+" + sym + r"\(([^;]*)\);", header)
-        assert decl, sym
-        n_args = len([a for a in decl.group(1).split(",") if a.strip()])
-        assert sym in _lib.SIGNATURES and len(_lib.SIGNATURES[sym][1]) == n_args, sym
-        assert hasattr(_lib.lib(), sym)
-        assert sym in before, sym   # the changelog line
-    assert re.search(r"\(still 15\) \+ tohip_roadmap_knn", before)
+    header, before = check_abi_entries(ENTRIES)
+    assert re.search(rf"\(still {ABI}\) \+ tohip_roadmap_knn", before)
     for name, v in (("NODES", 16384), ("K", 32), ("SOURCES", 256)):
         assert f"#define TOHIP_ROADMAP_MAX_{name} {v}\n" in header
         assert getattr(ops, f"ROADMAP_MAX_{name}") == v == getattr(synth, f"ROADMAP_MAX_{name}")

@@ -2,35 +2,22 @@
 counts and without a new ABI version; each entry refuses bad arguments before any launch; every team the host layer does not support
 is refused with a ValueError that names why, before any GPU call; optimize_team with nothing to run returns an empty result."""
 import ctypes
-import os
-import re
 import types
 
 import pytest
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_cases import ABI, check_abi_entries
+
 EINVAL, ENOSPC = -1, -2
 ENTRIES = ("tohip_team_step_tail", "tohip_team_loss", "tohip_team_member_gains")
 SIZES = ("tohip_team_state_bytes", "tohip_team_member_gains_bytes")
 
 
-def _header():
-    return open(os.path.join(REPO, "include", "trajopt_hip.h")).read()
-
-
 def test_header_and_table_declare_the_team_entries():
-    from trajectory_optimization_amd import _lib
-    header = _header()
-    assert "#define TOHIP_ABI_VERSION 15" in header and _lib.ABI_VERSION == 15 == _lib.lib().tohip_abi_version()
-    for sym in ENTRIES + SIZES:
-        decl = re.search(r"\b(?:int|size_t)\s+" + sym + r"\(([^;]*)\);", header)
-        assert decl, sym
-        n_args = len([a for a in decl.group(1).split(",") if a.strip()])
-        assert sym in _lib.SIGNATURES and len(_lib.SIGNATURES[sym][1]) == n_args, sym
-        assert hasattr(_lib.lib(), sym)
+    header, before = check_abi_entries(ENTRIES + SIZES)
     # the history comment says why the number stays
-    assert "(still 15)" in header and "tohip_team_step_tail" in header.split("#define TOHIP_ABI_VERSION")[0]
+    assert f"(still {ABI})" in header and "tohip_team_step_tail" in before
 
 
 def test_sizes():

@@ -4,12 +4,13 @@ before any launch; every argument the host layer does not accept is refused with
 the numpy restatement of the definition (synth.tour_plan) gives the orders geometry dictates."""
 import ctypes
 import os
-import re
 import types
 
 import numpy as np
 import pytest
 import torch
+
+from abi_cases import check_abi_entries
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, ENOSPC = -1, -2
@@ -17,16 +18,9 @@ ENTRIES = ("tohip_clearance_edges", "tohip_tour_bytes", "tohip_tour_plan")
 
 
 def test_header_and_table_declare_the_tour_entries():
-    from trajectory_optimization_amd import _lib, ops
-    header = open(os.path.join(REPO, "include", "trajopt_hip.h")).read()
-    assert "#define TOHIP_ABI_VERSION 15" in header and _lib.ABI_VERSION == 15 == _lib.lib().tohip_abi_version()
-    for sym in ENTRIES:
-        decl = re.search(r"\b(?:int|size_t)\s+" + sym + r"\(([^;]*)\);", header)
-        assert decl, sym
-        n_args = len([a for a in decl.group(1).split(",") if a.strip()])
-        assert sym in _lib.SIGNATURES and len(_lib.SIGNATURES[sym][1]) == n_args, sym
-        assert hasattr(_lib.lib(), sym)
-    assert "tohip_tour_plan" in header.split("#define TOHIP_ABI_VERSION")[0]
+    from trajectory_optimization_amd import ops
+    header, before = check_abi_entries(ENTRIES)
+    assert "tohip_tour_plan" in before
     assert f"#define TOHIP_TOUR_MAX_NODES {ops.TOUR_MAX_NODES}\n" in header
     src = open(os.path.join(REPO, "trajectory_optimization_amd", "csrc", "trajopt_hip.hip")).read()
     assert '#include "tour_kernels.hip"' in src

@@ -4,33 +4,23 @@ before any launch; every argument the host layer does not accept is refused with
 GPU call; the candidate grid is the documented recipe."""
 import ctypes
 import os
-import re
 import types
 
 import numpy as np
 import pytest
 import torch
 
+from abi_cases import ABI, check_abi_entries
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, ENOSPC = -1, -2
 ENTRIES = ("tohip_views_bytes", "tohip_views_append", "tohip_views_select", "tohip_views_row")
 
 
-def _header():
-    return open(os.path.join(REPO, "include", "trajopt_hip.h")).read()
-
-
 def test_header_and_table_declare_the_views_entries():
-    from trajectory_optimization_amd import _lib, ops
-    header = _header()
-    assert "#define TOHIP_ABI_VERSION 15" in header and _lib.ABI_VERSION == 15 == _lib.lib().tohip_abi_version()
-    for sym in ENTRIES:
-        decl = re.search(r"\b(?:int|size_t)\s+" + sym + r"\(([^;]*)\);", header)
-        assert decl, sym
-        n_args = len([a for a in decl.group(1).split(",") if a.strip()])
-        assert sym in _lib.SIGNATURES and len(_lib.SIGNATURES[sym][1]) == n_args, sym
-        assert hasattr(_lib.lib(), sym)
-    assert "(still 15)" in header and "tohip_views_select" in header.split("#define TOHIP_ABI_VERSION")[0]
+    from trajectory_optimization_amd import ops
+    header, before = check_abi_entries(ENTRIES)
+    assert f"(still {ABI})" in header and "tohip_views_select" in before
     assert f"#define TOHIP_VIEWS_MAX_CHUNK {ops.VIEWS_MAX_CHUNK}\n" in header
     assert f"#define TOHIP_VIEWS_MAX_CANDIDATES {ops.VIEWS_MAX_CANDIDATES}\n" in header
     src = open(os.path.join(REPO, "trajectory_optimization_amd", "csrc", "trajopt_hip.hip")).read()

@@ -1338,7 +1338,7 @@ class TeamTraj(nn.Module):
         log-odds row per member, one pass over those rows (tohip_team_member_gains).  A member that sees nothing at all (far from the
         cloud: its row is NaN, as the reference's rewards are for such a waypoint) counts as absent: gain 0 and count 0 exactly, and
         the others' gains are those of the team without it.  At most 16 members."""
-        if self.B > 16:   # TOHIP_TEAM_MAX_GAINS: the pass keeps one accumulator pair per member in registers
+        if self.B > _lib.CONSTANTS["TOHIP_TEAM_MAX_GAINS"]:   # the pass keeps one accumulator pair per member in registers
             raise ValueError(f"TeamTraj.member_gains: at most 16 members ({self.B} given)")
         m0 = self.models[0]
         ps, qs = self._evaluated(self._step(vis_wps_dist))

@@ -142,7 +142,7 @@ class TrajWorkspace:
         self.generation = 0
 
 
-DENSE = 1  # TOHIP_TRAJ_DENSE
+DENSE = _lib.CONSTANTS["TOHIP_TRAJ_DENSE"]
 
 
 def _rig_ref(rig):
@@ -439,7 +439,7 @@ def check_clearance(radius, weight):
 
 
 CLEARANCE_MODES = ("waypoints", "segments")
-CLEARANCE_SEGMENTS = 4   # TOHIP_TRAJ_CLEARANCE_SEGMENTS: the flag bit of tohip_traj_loss / tohip_traj_opt
+CLEARANCE_SEGMENTS = _lib.CONSTANTS["TOHIP_TRAJ_CLEARANCE_SEGMENTS"]   # the flag bit of tohip_traj_loss / tohip_traj_opt
 
 
 def check_clearance_mode(mode):
@@ -499,7 +499,7 @@ def traj_coverage(cloud, lo_sum, prior=None, clamp_max=None):
     return out
 
 
-COVMAP_MODES = {"max": 0, "add": 1}   # TOHIP_COVMAP_MAX / TOHIP_COVMAP_ADD
+COVMAP_MODES = {"max": _lib.CONSTANTS["TOHIP_COVMAP_MAX"], "add": _lib.CONSTANTS["TOHIP_COVMAP_ADD"]}
 COVMAP_MIN_CAPACITY = 16
 COVMAP_INDEX_LIMIT = 1 << 20          # voxel indices lie in [-2^20, 2^20) per axis
 
@@ -1228,8 +1228,8 @@ def team_loss(poses, poses0, n_members, smoothness_weight, traj_length_weight, e
     return terms, total, reg
 
 
-VIEWS_MAX_CHUNK = 256          # TOHIP_VIEWS_MAX_CHUNK
-VIEWS_MAX_CANDIDATES = 65536   # TOHIP_VIEWS_MAX_CANDIDATES
+VIEWS_MAX_CHUNK = _lib.CONSTANTS["TOHIP_VIEWS_MAX_CHUNK"]
+VIEWS_MAX_CANDIDATES = _lib.CONSTANTS["TOHIP_VIEWS_MAX_CANDIDATES"]
 VIEWS_CHUNK_BYTES = 1 << 30    # the dense (chunk, npad) f32 rows a ViewSet compacts at a time: 256 candidates at 1 M points
 
 
@@ -1471,7 +1471,7 @@ def clearance_edges(cloud, a, b, radius):
     return d, idx, s
 
 
-TOUR_MAX_NODES = 256   # TOHIP_TOUR_MAX_NODES
+TOUR_MAX_NODES = _lib.CONSTANTS["TOHIP_TOUR_MAX_NODES"]
 TOUR_UNIT = 2.0 ** -20   # metres per unit of a tour's integer lengths
 
 
@@ -1549,9 +1549,9 @@ def tour_plan(nodes, edge_idx=None, closed=False, max_moves=None):
     return _tour_plan(nodes, edge_idx, closed, max_moves, False)[0]
 
 
-ROADMAP_MAX_NODES = 16384   # TOHIP_ROADMAP_MAX_NODES
-ROADMAP_MAX_K = 32          # TOHIP_ROADMAP_MAX_K
-ROADMAP_MAX_SOURCES = 256   # TOHIP_ROADMAP_MAX_SOURCES
+ROADMAP_MAX_NODES = _lib.CONSTANTS["TOHIP_ROADMAP_MAX_NODES"]
+ROADMAP_MAX_K = _lib.CONSTANTS["TOHIP_ROADMAP_MAX_K"]
+ROADMAP_MAX_SOURCES = _lib.CONSTANTS["TOHIP_ROADMAP_MAX_SOURCES"]
 ROADMAP_INF = 1 << 62       # a route length where no route exists
 ROADMAP_MAX_LEN = 1 << 40   # the longest edge that can be open, in units of 2^-20 m
 
@@ -1664,8 +1664,8 @@ def tour_plan_via(nodes, edge_idx, via_D, closed=False, max_moves=None):
     return _tour_plan(nodes, edge_idx, closed, max_moves, True, via_D)
 
 
-PATH_MAX_NODES = 1024   # TOHIP_PATH_MAX_NODES
-PATH_MAX_ROWS = 4096    # TOHIP_PATH_MAX_ROWS
+PATH_MAX_NODES = _lib.CONSTANTS["TOHIP_PATH_MAX_NODES"]
+PATH_MAX_ROWS = _lib.CONSTANTS["TOHIP_PATH_MAX_ROWS"]
 
 
 def check_path(path, quats=None, keep=None, window=None, spacing=None, max_rows=None):
@@ -1736,9 +1736,9 @@ def path_refine(P, quats, keep, open_band, window=None, spacing=None, max_rows=N
     return buf
 
 
-VIEW_MAX_POSITIONS = 65536      # TOHIP_VIEW_MAX_POSITIONS
+VIEW_MAX_POSITIONS = _lib.CONSTANTS["TOHIP_VIEW_MAX_POSITIONS"]
 VIEW_SECTORS = (8, 16, 32, 64, 128)
-VIEW_MAX_PER_POSITION = 8       # TOHIP_VIEW_MAX_PER_POSITION
+VIEW_MAX_PER_POSITION = _lib.CONSTANTS["TOHIP_VIEW_MAX_PER_POSITION"]
 VIEW_MAX_WEIGHT = 32768         # a point's largest weight: 65 536 points of a block x 32 768 < 2^32
 VIEW_MIN_DIST = float(np.float32(1e-3))
 
@@ -2244,9 +2244,9 @@ def spherical_flip(points, param=2):
     n = pts.shape[0]
     out = torch.empty_like(pts)
     rad = torch.empty(1, dtype=torch.float32, device=pts.device)
-    ws = torch.empty(8192, dtype=torch.uint8, device=pts.device)   # TOHIP_FLIP_WORKSPACE_BYTES
+    ws = torch.empty(_lib.CONSTANTS["TOHIP_FLIP_WORKSPACE_BYTES"], dtype=torch.uint8, device=pts.device)
     with torch.cuda.device(pts.device):
-        check(_lib.lib().tohip_spherical_flip(ptr(pts), n, float(param), ptr(out), ptr(rad), ptr(ws), 8192, stream_ptr()),
+        check(_lib.lib().tohip_spherical_flip(ptr(pts), n, float(param), ptr(out), ptr(rad), ptr(ws), ws.numel(), stream_ptr()),
               "tohip_spherical_flip")
     return out, rad
 

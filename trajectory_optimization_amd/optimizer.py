@@ -16,7 +16,7 @@ from . import _lib, ops
 from ._lib import check, ptr, stream_ptr
 
 
-LAST_OUTPUTS = 2   # TOHIP_TRAJ_OPT_LAST_OUTPUTS
+LAST_OUTPUTS = _lib.CONSTANTS["TOHIP_TRAJ_OPT_LAST_OUTPUTS"]
 
 
 class TrajOptResult:
