@@ -786,8 +786,14 @@ def occ_export_ref(grid, origin, resolution):
     """export() of a grid (nx,ny,nz) bool -> (ijk (F,3) int32, centres (F,3) f32) in ascending (word, bit) order: word = ((z >> 1)
     nby + (y >> 2)) nbx + (x >> 2), bit = x & 3 | (y & 3) << 2 | (z & 1) << 4; centre = fl(origin + fl(fl(i + 0.5) r)) in f32."""
     g = np.asarray(grid, dtype=bool)
-    nbx, nby = (g.shape[0] + 3) // 4, (g.shape[1] + 3) // 4
-    ijk = np.argwhere(g).astype(np.int64)
+    return occ_export_sparse(np.argwhere(g), g.shape, origin, resolution)
+
+
+def occ_export_sparse(ijk, dims, origin, resolution):
+    """occ_export_ref of the grid of `dims` whose set voxels are the rows of ijk (M,3) — distinct and inside dims — without the dense
+    grid: the rows sorted by the same (word, bit) key, and their centres.  For grids too large to hold as a bool array."""
+    nbx, nby = (int(dims[0]) + 3) // 4, (int(dims[1]) + 3) // 4
+    ijk = np.asarray(ijk, dtype=np.int64).reshape(-1, 3)
     x, y, z = ijk[:, 0], ijk[:, 1], ijk[:, 2]
     key = ((((z >> 1) * nby + (y >> 2)) * nbx + (x >> 2)) << 5) | (x & 3) | ((y & 3) << 2) | ((z & 1) << 4)
     ijk = ijk[np.argsort(key, kind="stable")]
@@ -918,24 +924,29 @@ def field_positions_ref(positions, origin, resolution, field):
 
 
 def field_segments_ref(a, b, origin, resolution, field):
-    """The segment query (E,3), (E,3) world points -> (d2 (E,) int32, vox (E,) int32), on top of los_fixed(trace=True): the minimum of
-    the field over the visited voxels v_0 ... v_T inside dims (65535: none inside, or all hold 65535; -1: an endpoint out of range)
-    and the linear index (k ny + j) nx + i of the first visited voxel that attains it (-1 with 65535 or -1)."""
+    """The segment query (E,3), (E,3) world points -> (d2 (E,) int32, vox (E,) int32), on top of walk_fixed: the minimum of the field
+    over the visited voxels v_0 ... v_T inside dims (65535: none inside, or all hold 65535; -1: an endpoint out of range) and the
+    linear index (k ny + j) nx + i of the first visited voxel that attains it (-1 with 65535 or -1).  Vectorised over the legs: a
+    visitor that keeps a strictly smaller value, so the first voxel in walk order wins (tests/test_map_at_size_cpu.py restates it
+    voxel by voxel over los_fixed's trace)."""
     field = np.asarray(field)
     nx, ny, nz = field.shape
+    dims = np.asarray(field.shape, dtype=np.int64)
     qa, oka = occ_fixed(a, origin, resolution)
     qb, okb = occ_fixed(b, origin, resolution)
     ok = oka & okb
+    best, arg = np.full(int(ok.sum()), FIELD_SENTINEL, dtype=np.int64), np.full(int(ok.sum()), -1, dtype=np.int64)
+
+    def visit(idx, vi, last):
+        inside = ((vi >= 0) & (vi < dims[None, :])).all(axis=1)
+        r, v = idx[inside], vi[inside]
+        val = field[v[:, 0], v[:, 1], v[:, 2]].astype(np.int64)
+        less = val < best[r]
+        best[r[less]], arg[r[less]] = val[less], ((v[:, 2] * ny + v[:, 1]) * nx + v[:, 0])[less]
+
+    walk_fixed(qa[ok], qb[ok], visit)
     d2, vox = np.full(len(qa), -1, dtype=np.int32), np.full(len(qa), -1, dtype=np.int32)
-    rows = np.nonzero(ok)[0]
-    if len(rows):
-        _, visited = los_fixed(qa[ok], qb[ok], np.zeros(field.shape, dtype=bool), (0, 0), trace=True)
-        for e, vs in zip(rows, visited):
-            best, arg = FIELD_SENTINEL, -1
-            for (i, j, k) in vs:
-                if 0 <= i < nx and 0 <= j < ny and 0 <= k < nz and field[i, j, k] < best:
-                    best, arg = int(field[i, j, k]), (k * ny + j) * nx + i
-            d2[e], vox[e] = best, arg
+    d2[ok], vox[ok] = best, arg
     return d2, vox
 
 
