@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_field_bytes / tohip_field_workspace_bytes / tohip_field_build / tohip_field_positions / tohip_field_segments /
+/* (still 15) + tohip_evid_bytes / tohip_evid_init / tohip_evid_fold / tohip_evid_positions (a hit/miss evidence map: integer log-odds
+ * per voxel, the occupied and free planes derived from it): new symbols only.
+ * (still 15) + tohip_field_bytes / tohip_field_workspace_bytes / tohip_field_build / tohip_field_positions / tohip_field_segments /
  * tohip_field_nodes (a conservative clearance field over the occupancy grid): new symbols only.
  * (still 15) + tohip_occ_carve / tohip_occ_state / tohip_occ_frontier / tohip_occ_export_workspace_bytes / tohip_occ_count /
  * tohip_occ_export (free-space carving, the three-state map, frontiers and the ordered listing of a grid): new symbols only.
@@ -1201,6 +1203,38 @@ int tohip_field_segments(const void *field, size_t field_bytes, const tohip_occ_
                          int64_t n_legs, int32_t *d2, int32_t *vox, int32_t need2, float *edge_d, int32_t *edge_idx, void *stream);
 int tohip_field_nodes(const void *field, size_t field_bytes, const void *occupied_or_null, const void *free_or_null, void *nodes,
                       size_t grid_bytes, const tohip_occ_geom *geom, int32_t need2, int32_t stride, void *stream);
+
+/* ---- the evidence map ("Evidence map") ------------------------------------------------
+ * An EVIDENCE buffer has an occupancy grid's geometry (origin, resolution, dims, brick layout: word w = ((z>>1) nby + (y>>2)) nbx +
+ * (x>>2), bit b = x&3 | (y&3)<<2 | (z&1)<<4) and holds one signed 8-bit log-odds value per voxel IN BRICK ORDER: byte 32 w + b after
+ * a 256-byte header (zero), so the 32 voxels of a brick word are 32 consecutive, 32-byte-aligned bytes.  tohip_evid_bytes(nx, ny, nz)
+ * = 256 + 32 words device bytes (0 for bad dims), caller-owned, 16-byte aligned.  The value -128 means NEVER OBSERVED; pad voxels
+ * (outside dims) hold -128 for ever.  State of a voxel with value L: unknown iff L == -128, otherwise occupied iff L > threshold,
+ * otherwise free.  Parameters, all integers: hit and miss in [1, 127], -127 <= lmin <= threshold < lmax <= 127.
+ *
+ * tohip_evid_init: every voxel -128.
+ * tohip_evid_fold: one scan.  hit_plane H and pass_plane M are occupancy grid buffers of the geometry (grid_bytes each; what
+ * tohip_occ_insert and tohip_occ_carve fill).  For every voxel inside dims, base = (L == -128 ? 0 : L); where the H bit is set L <-
+ * min(base + hit, lmax); otherwise, where the M bit is set, L <- max(base - miss, lmin); otherwise L is unchanged: a hit wins within a
+ * scan, and a voxel is updated at most once per scan however many rays cross it.  Bits of H and M outside dims are ignored.  A brick
+ * whose H and M words are both zero is not touched at all.  For every other brick the word of occupied_out receives exactly the bits
+ * L > threshold and the word of free_out exactly the bits L != -128 and L <= threshold (pad bits 0), stored by the lane that owns the
+ * word: handed the two planes of the previous fold over this buffer (empty planes for a fresh buffer), they hold exactly those bits
+ * everywhere after every fold.  clear_scan != 0: every word of H and M that was not zero is zeroed — scratch planes are empty again
+ * without an init launch; 0: H and M are only read.  counts (DEVICE uint64 x 4, may be NULL, zero-filled by the caller): += voxels
+ * updated, += voxels newly known (they left -128), += occupied bits that appeared, += occupied bits that vanished.  Within a scan
+ * nothing depends on a row order or a launch shape: the inputs are bit planes.  The five buffers must be five different ones.
+ * tohip_evid_positions: positions (m, 3) f32 -> values (m) int8: the voxel's value, -128 also for a position out of range or outside
+ * dims — and / or state (m) uint8: 0 unknown, 1 free, 2 occupied (L > threshold, -127 <= threshold <= 126), 3 out of range or
+ * outside dims, tohip_occ_state's codes; either output may be NULL, not both.
+ * Every argument check returns before anything is enqueued; nothing synchronises with the host. */
+size_t tohip_evid_bytes(int32_t nx, int32_t ny, int32_t nz);
+int tohip_evid_init(void *evid, size_t evid_bytes, const tohip_occ_geom *geom, void *stream);
+int tohip_evid_fold(void *evid, size_t evid_bytes, void *hit_plane, void *pass_plane, void *occupied_out, void *free_out,
+                    size_t grid_bytes, const tohip_occ_geom *geom, int32_t hit, int32_t miss, int32_t lmin, int32_t lmax,
+                    int32_t threshold, int32_t clear_scan, uint64_t *counts, void *stream);
+int tohip_evid_positions(const void *evid, size_t evid_bytes, const tohip_occ_geom *geom, int32_t threshold, const float *positions,
+                         int64_t m, int8_t *values, uint8_t *state, void *stream);
 
 /* ---- optional per-kernel timing (bench.py's roofline leg) -----------------------------------------
  * When enabled, every launch of the big kernels is bracketed by hipEventRecord on its own stream.

@@ -19,6 +19,7 @@
 #include "occupancy_kernels.hip"
 #include "frontier_kernels.hip"
 #include "field_kernels.hip"
+#include "evidence_kernels.hip"
 #include "loss_kernels.hip"
 #include "ingest_kernels.hip"
 #include "render_kernels.hip"

@@ -994,8 +994,9 @@ def check_min_unknown(min_unknown):
 class SpaceMap:
     """The three-state map ("Free space and frontiers"): the caller's occupied grid — shared, not copied — and a free
     plane of the same geometry.  A voxel is occupied (2) where the occupied bit is set, else free (1) where a ray passed through, else
-    unknown (0).  Bits are never cleared: the map has no moving obstacles; free space leaks through a wall sampled more sparsely
-    than the voxel; the box's own boundary is not a frontier."""
+    unknown (0).  Bits are never cleared: this map has no moving obstacles (EvidenceMap, below, is the map that takes a voxel back
+    and hands out the same planes); free space leaks through a wall sampled more sparsely than the voxel; the box's own boundary is
+    not a frontier."""
 
     def __init__(self, occupied, free=None):
         if free is None:
@@ -1184,6 +1185,163 @@ class ClearanceField:
         _, _, _, need2 = check_field(self.occupied, D=self.D, radius=check_tour_radius(radius), stride=stride, space=space)
         occ, fre = (ptr(space.occupied.buf), ptr(space.free.buf)) if space is not None else (None, None)
         return _listed_plane(FreeNodes, self.occupied, "tohip_field_nodes", (ptr(self.buf), self.buf.numel(), occ, fre), (need2, int(stride)))
+
+
+EVID_UNKNOWN = -128        # an evidence value: never observed
+EVID_DEFAULTS = dict(hit=17, miss=8, lmin=-40, lmax=70, threshold=0)
+
+
+def check_evidence(origin, resolution, dims, hit=17, miss=8, lmin=-40, lmax=70, threshold=0, hit_plane=None, pass_plane=None, like=None,
+                   own=()):
+    """An evidence map's settings and a fold's planes, by name; needs no GPU.  origin, resolution, dims: an occupancy grid's
+    (check_los).  hit and miss: integers in [1, 127]; lmin, lmax, threshold: integers with -127 <= lmin <= threshold < lmax <= 127.
+    hit_plane and pass_plane (given together): two different ops.OccupancyGrids of the origin, resolution, dims and device of `like`
+    (the map's occupied grid), neither of them one of `own` (the map's own planes).  -> (origin (3,) float32 array, resolution,
+    dims, (hit, miss, lmin, lmax, threshold)); ValueError otherwise."""
+    o, r, d, _ = check_los(origin, resolution, dims)
+    for name, v in (("hit", hit), ("miss", miss)):
+        if not _is_int(v) or not 1 <= v <= 127:
+            raise ValueError(f"{name} must be an integer in [1, 127], got {v!r}")
+    for name, v in (("lmin", lmin), ("lmax", lmax), ("threshold", threshold)):
+        if not _is_int(v):
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    if not -127 <= lmin <= threshold < lmax <= 127:
+        raise ValueError(f"the clamps must satisfy -127 <= lmin <= threshold < lmax <= 127, got lmin = {lmin}, threshold = {threshold}, "
+                         f"lmax = {lmax}")
+    if (hit_plane is None) != (pass_plane is None):
+        raise ValueError("hit_plane and pass_plane must be given together")
+    if hit_plane is not None:
+        for name, g in (("hit_plane", hit_plane), ("pass_plane", pass_plane)):
+            if not isinstance(g, OccupancyGrid):
+                raise ValueError(f"{name} must be an ops.OccupancyGrid, got {type(g).__name__}")
+            if any(g is mine for mine in own):
+                raise ValueError(f"{name} must not be one of the map's own planes")
+            diff = _grid_difference(g, like) if like is not None else None
+            if diff:
+                raise ValueError("{}: its {} differs from the map's ({} and {})".format(name, *diff))
+        if pass_plane is hit_plane:
+            raise ValueError("pass_plane must not be the hit plane itself")
+    return o, r, d, (int(hit), int(miss), int(lmin), int(lmax), int(threshold))
+
+
+class EvidenceMap:
+    """A hit/miss evidence map (evidence_kernels.hip, DESIGN.md 10 "Evidence map"): one signed 8-bit log-odds value per voxel of an
+    occupancy grid's geometry, -128 = never observed, updated once per scan — + hit (up to lmax) where a return fell, otherwise - miss
+    (down to lmin) where a ray passed — and the two planes derived from it: `occupied` (value > threshold) and `free` (observed and
+    value <= threshold), ordinary OccupancyGrids that stay the same objects for the map's life, and `space`, a SpaceMap over them.
+    line_of_sight, frontier, ClearanceField.build / rebuild, free_nodes and occlusion_grid= read them as they read any grid: a map
+    that forgets what moved away.  Integers only: the same bytes in every run.  There is no decay without observation."""
+
+    def __init__(self, origin=(0.0, 0.0, 0.0), resolution=0.1, dims=(64, 64, 64), hit=17, miss=8, lmin=-40, lmax=70, threshold=0, device="cuda"):
+        _, _, _, self.params = check_evidence(origin, resolution, dims, hit, miss, lmin, lmax, threshold)
+        self.occupied = OccupancyGrid(origin, resolution, dims, device=device)
+        self.free = self.occupied.empty_like()
+        self.space = SpaceMap(self.occupied, self.free)
+        self._scan = SpaceMap(self.occupied.empty_like(), self.occupied.empty_like())   # one scan's hit and pass planes, empty between scans
+        g = self.occupied
+        self.origin, self.resolution, self.dims, self.device, self.geom = g.origin, g.resolution, g.dims, g.device, g.geom
+        self.buf = torch.empty(_lib.lib().tohip_evid_bytes(*self.dims), dtype=torch.uint8, device=self.device)
+        self._counts = torch.zeros(4, dtype=torch.int64, device=self.device)
+        _map_call(self.device, "tohip_evid_init", *self._sizes())
+
+    @classmethod
+    def like(cls, grid, **params):
+        """An empty map of an OccupancyGrid's origin, resolution, dims and device (the grid's bits are not read)."""
+        if not isinstance(grid, OccupancyGrid):
+            raise ValueError(f"EvidenceMap.like: grid must be an ops.OccupancyGrid, got {type(grid).__name__}")
+        return cls(grid.origin, grid.resolution, grid.dims, device=grid.device, **params)
+
+    @classmethod
+    def from_space(cls, space, **params):
+        """A map seeded from a SpaceMap, as settled as the clamps allow: its occupied voxels get lmax, its free ones lmin, the rest
+        stay unknown (one fold of space.occupied / space.free with steps that reach the clamps, into an empty map; the SpaceMap is
+        only read).  A later change of mind costs what the clamps say."""
+        if not isinstance(space, SpaceMap):
+            raise ValueError(f"EvidenceMap.from_space: space must be an ops.SpaceMap, got {type(space).__name__}")
+        m = cls.like(space.occupied, **params)
+        m._fold(space.occupied, space.free, False, steps=(127, 127))
+        return m
+
+    def _sizes(self):
+        return ptr(self.buf), self.buf.numel(), ctypes.byref(self.geom)
+
+    @property
+    def threshold(self):
+        return self.params[4]
+
+    def _fold(self, hit_plane, pass_plane, clear, steps=None):
+        hit, miss, lmin, lmax, threshold = self.params
+        if steps is not None:
+            hit, miss = steps
+        self._counts.zero_()
+        _map_call(self.device, "tohip_evid_fold", ptr(self.buf), self.buf.numel(), ptr(hit_plane.buf), ptr(pass_plane.buf), ptr(self.occupied.buf),
+                  ptr(self.free.buf), self.occupied.buf.numel(), ctypes.byref(self.geom), hit, miss, lmin, lmax, threshold, int(bool(clear)),
+                  ptr(self._counts))
+
+    def fold(self, hit_plane, pass_plane, clear=False):
+        """One scan given as planes of the caller's own: hit_plane (a set bit: a return fell in the voxel) and pass_plane (a ray
+        passed through), two OccupancyGrids of the map's geometry.  A hit wins; a voxel moves once however many rays crossed it.
+        clear=True empties both planes behind the fold (only the words that held a bit are written).  One launch, nothing read
+        back; last_counts() tells what changed."""
+        check_evidence(self.origin, self.resolution, self.dims, *self.params, hit_plane=hit_plane, pass_plane=pass_plane, like=self.occupied,
+                       own=(self.occupied, self.free))
+        self._fold(hit_plane, pass_plane, clear)
+
+    def integrate(self, origin, points, max_range=None):
+        """One scan: SpaceMap.integrate of the rays origin -> points[i] on the map's own two scratch planes — the carve, its per-ray
+        flags, the insert of the rows whose ray was not truncated — then one fold, which also empties the scratch planes.
+        -> the number of rays skipped (an endpoint out of range); that count is the one synchronisation."""
+        skipped = self._scan.integrate(origin, points, max_range)
+        self._fold(self._scan.occupied, self._scan.free, True)
+        return skipped
+
+    def last_counts(self):
+        """What the last fold changed -> (voxels updated, voxels newly known, occupied voxels that appeared, occupied voxels that
+        vanished); synchronises.  A clearance field over the map needs a rebuild() when either of the last two is not zero."""
+        return tuple(int(v) for v in self._counts.cpu().tolist())
+
+    def log_odds(self, positions):
+        """(M,3) world positions -> (values (M,) int8, state (M,) uint8): the voxel's value, -128 where it was never observed and
+        where the position lies outside dims, beyond the apron or is not finite; state 0 unknown, 1 free, 2 occupied, 3 outside —
+        SpaceMap.state's codes."""
+        pos = covmap_points(positions, self.device, "EvidenceMap.log_odds")
+        values = torch.empty(pos.shape[0], dtype=torch.int8, device=self.device)
+        state = torch.empty(pos.shape[0], dtype=torch.uint8, device=self.device)
+        _map_call(self.device, "tohip_evid_positions", *self._sizes(), self.threshold, ptr(pos), pos.shape[0], ptr(values), ptr(state))
+        return values, state
+
+    def _bricks(self):
+        nx, ny, nz = self.dims
+        return (nx + 3) // 4, (ny + 3) // 4, (nz + 1) // 2
+
+    def dense(self):
+        """The values as an (nx, ny, nz) int8 tensor (a copy, out of brick order): for tests and small grids."""
+        nx, ny, nz = self.dims
+        nbx, nby, nbz = self._bricks()
+        v = self.buf[256:].view(torch.int8).view(nbz, nby, nbx, 2, 4, 4).permute(2, 5, 1, 4, 0, 3).reshape(4 * nbx, 4 * nby, 2 * nbz)
+        return v[:nx, :ny, :nz].contiguous()
+
+    def load(self, values):
+        """Replace the map's content by `values`, an (nx, ny, nz) integer tensor as dense() gives it — each -128 or in [lmin, lmax] —
+        and derive both planes from it: for tests, small grids and a map saved earlier.  Plain tensor copies, no kernel of the
+        library; the scratch planes and last_counts() are left as they are.  -> self."""
+        _, _, lmin, lmax, threshold = self.params
+        if (not torch.is_tensor(values) or values.is_floating_point() or values.dtype == torch.bool or tuple(values.shape) != tuple(self.dims)):
+            raise ValueError(f"values must be an integer tensor of shape {tuple(self.dims)}, got "
+                             f"{tuple(values.shape) if torch.is_tensor(values) else type(values).__name__}")
+        v = values.to(device=self.device, dtype=torch.int64)
+        if not bool(((v == EVID_UNKNOWN) | ((v >= lmin) & (v <= lmax))).all()):
+            raise ValueError(f"values must each be -128 or lie in [lmin, lmax] = [{lmin}, {lmax}]")
+        nx, ny, nz = self.dims
+        nbx, nby, nbz = self._bricks()
+        full = torch.full((4 * nbx, 4 * nby, 2 * nbz), EVID_UNKNOWN, dtype=torch.int64, device=self.device)
+        full[:nx, :ny, :nz] = v
+        bricks = full.view(nbx, 4, nby, 4, nbz, 2).permute(4, 2, 0, 5, 3, 1).reshape(-1, 4, 8)   # (word, byte of the plane word, bit)
+        self.buf[256:] = bricks.reshape(-1).to(torch.int8).view(torch.uint8)
+        weights = (1 << torch.arange(8, device=self.device, dtype=torch.int64))
+        for plane, bits in ((self.occupied, bricks > threshold), (self.free, (bricks != EVID_UNKNOWN) & (bricks <= threshold))):
+            plane.buf[256:] = (bits.to(torch.int64) * weights).sum(dim=2).to(torch.uint8).reshape(-1)
+        return self
 
 
 def check_occlusion_grid(grid, cloud):

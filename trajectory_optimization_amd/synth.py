@@ -1040,3 +1040,99 @@ def doorway_messages():
     a range of 1.4 m, which carves that cone and a ball of free space outside.  Beyond that ball nothing is known."""
     s1, s2 = np.float32([1.03, 0.97, 0.52]), np.float32([2.4, 1.0, 0.5])
     return [(s1, box_room(doorway=True), None), (s2, doorway_outside_scan(s2), 1.4)]
+
+
+# ---- the evidence map restated in numpy (DESIGN.md 10, "Evidence map"): what evidence_kernels.hip must give, bit for bit.  int64
+# throughout, dense (nx,ny,nz) arrays. --------------------------------------------------------------------------------------------------
+EVID_UNKNOWN = -128
+EVID_HEADER = 256
+EVID_DEFAULTS = dict(hit=17, miss=8, lmin=-40, lmax=70, threshold=0)
+EVID_SCENE = dict(origin=(-0.2, -0.2, -0.2), resolution=0.1, dims=(24, 24, 14), scanner=(0.5, 1.0, 0.5), step=0.04,
+                  pillar=((1.0, 0.8, 0.0), (1.3, 1.2, 0.7)), leg=((0.5, 1.0, 0.35), (1.8, 1.0, 0.35)))
+
+
+def evidence_params(params=None):
+    """{hit, miss, lmin, lmax, threshold} (missing keys: EVID_DEFAULTS; None: all defaults) -> the five integers in that order."""
+    p = dict(EVID_DEFAULTS, **(params or {}))
+    return tuple(int(p[k]) for k in ("hit", "miss", "lmin", "lmax", "threshold"))
+
+
+def evidence_fold_ref(L, H, M, params=None):
+    """One scan folded into the values L (nx,ny,nz) integers (-128: never observed; not modified) -> (L' int64, counts (4,) int64).  H,
+    M: the scan's hit and pass planes (nx,ny,nz) bool.  base = (L == -128 ? 0 : L); with the H bit L' = min(base + hit, lmax);
+    otherwise with the M bit L' = max(base - miss, lmin); otherwise L' = L.  counts: voxels updated, voxels newly known (they left
+    -128), occupied (L > threshold) voxels that appeared, occupied voxels that vanished."""
+    hit, miss, lmin, lmax, thr = evidence_params(params)
+    L = np.asarray(L, dtype=np.int64)
+    H, M = np.asarray(H, dtype=bool), np.asarray(M, dtype=bool)
+    base = np.where(L == EVID_UNKNOWN, 0, L)
+    out = np.where(H, np.minimum(base + hit, lmax), np.where(M, np.maximum(base - miss, lmin), L))
+    touched = H | M
+    counts = np.array([touched.sum(), (touched & (L == EVID_UNKNOWN)).sum(), ((out > thr) & ~(L > thr)).sum(), ((L > thr) & ~(out > thr)).sum()],
+                      dtype=np.int64)
+    return out, counts
+
+
+def evidence_planes_ref(L, threshold=0):
+    """The derived planes of the values L -> (occupied, free) (nx,ny,nz) bool: L > threshold; L != -128 and L <= threshold."""
+    L = np.asarray(L, dtype=np.int64)
+    return L > int(threshold), (L != EVID_UNKNOWN) & (L <= int(threshold))
+
+
+def _evidence_bricks(dims):
+    nx, ny, nz = (int(d) for d in dims)
+    return (nx + 3) // 4, (ny + 3) // 4, (nz + 1) // 2
+
+
+def evidence_brick_order(L):
+    """The byte image of the evidence buffer holding the values L (nx,ny,nz) -> (256 + 32 words,) uint8: a zero header, then the int8
+    value of voxel (x, y, z) at byte 32 w + b, w = ((z >> 1) nby + (y >> 2)) nbx + (x >> 2), b = x & 3 | (y & 3) << 2 | (z & 1) << 4;
+    the pad voxels (outside dims) hold -128."""
+    L = np.asarray(L, dtype=np.int64)
+    nx, ny, nz = L.shape
+    nbx, nby, nbz = _evidence_bricks(L.shape)
+    pad = np.full((4 * nbx, 4 * nby, 2 * nbz), EVID_UNKNOWN, dtype=np.int64)
+    pad[:nx, :ny, :nz] = L
+    # (bx, x&3, by, y&3, bz, z&1) -> (bz, by, bx, z&1, y&3, x&3): the last three are the bit, most significant first
+    img = pad.reshape(nbx, 4, nby, 4, nbz, 2).transpose(4, 2, 0, 5, 3, 1).reshape(-1)
+    return np.concatenate([np.zeros(EVID_HEADER, dtype=np.uint8), img.astype(np.int8).view(np.uint8)])
+
+
+def evidence_from_brick_order(image, dims):
+    """The inverse of evidence_brick_order -> (values (nx,ny,nz) int64, pads: the values of the pad voxels, int64)."""
+    nx, ny, nz = (int(d) for d in dims)
+    nbx, nby, nbz = _evidence_bricks(dims)
+    v = np.asarray(image, dtype=np.uint8)[EVID_HEADER:].view(np.int8).astype(np.int64)
+    full = v.reshape(nbz, nby, nbx, 2, 4, 4).transpose(2, 5, 1, 4, 0, 3).reshape(4 * nbx, 4 * nby, 2 * nbz)
+    inside = np.zeros(full.shape, dtype=bool)
+    inside[:nx, :ny, :nz] = True
+    return full[:nx, :ny, :nz].copy(), full[~inside]
+
+
+def evidence_scan_ref(L, scanner, points, origin, resolution, dims, params=None, max_range=None):
+    """EvidenceMap.integrate restated -> (L', counts, skipped, H, M): the pass plane M is carve_ref of the scan into an empty plane, the
+    hit plane H is occupancy_ref of the rows whose ray was not truncated (flags != 1) into an empty grid, then one evidence_fold_ref.
+    skipped: the rays carve skipped."""
+    P = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+    M, skipped, flags, _ = carve_ref(scanner, P, origin, resolution, dims, max_range=max_range)
+    H, _ = occupancy_ref(P if max_range is None else P[flags != 1], origin, resolution, dims)
+    out, counts = evidence_fold_ref(L, H, M, params)
+    return out, counts, skipped, H, M
+
+
+def pillar_scan(room, origin, lo, hi):
+    """The scan `room` (N,3) taken from `origin` with the axis-aligned box [lo, hi] in the way -> (N,3) f32: a ray origin -> room[i]
+    that enters the box (the slab method in f64; the origin lies outside it) returns its entry point instead."""
+    o = np.asarray(origin, dtype=np.float64).reshape(3)
+    P = np.asarray(room, dtype=np.float64).reshape(-1, 3)
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    d = P - o
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t0, t1 = (lo - o) / d, (hi - o) / d
+    par = d == 0   # a ray parallel to a slab: inside it for every t, or never
+    inside = (o >= lo) & (o <= hi)
+    near = np.where(par, np.where(inside, -np.inf, np.inf), np.minimum(t0, t1))
+    far = np.where(par, np.where(inside, np.inf, -np.inf), np.maximum(t0, t1))
+    t_in, t_out = near.max(axis=1), far.min(axis=1)
+    meets = (t_in <= t_out) & (t_in > 0.0) & (t_in < 1.0)
+    return np.where(meets[:, None], o + np.where(meets, t_in, 0.0)[:, None] * d, P).astype(np.float32)

@@ -288,6 +288,21 @@ def free_nodes(field, radius, stride=1, space=None):
     return field.free_nodes(radius, stride, space)
 
 
+def evidence_map(grid_or_points, resolution=0.1, **params):
+    """An ops.EvidenceMap ("Evidence map"): per voxel an integer log-odds value that every scan moves — up where a
+    return fell, down where a ray passed — and the occupied and free planes derived from it, so a person who walked through the
+    first scan, a door that was shut or one spurious return leave the map again after a few contradicting scans.  From an
+    ops.OccupancyGrid: an empty map of its box; from an ops.SpaceMap: seeded with what it holds (occupied at lmax, free at lmin);
+    from points — (N,3) on the device, a PackedCloud or a ModelTraj — an empty map of the box around them at `resolution`.
+    params: hit, miss, lmin, lmax, threshold (integers; ops.check_evidence).  m.integrate(origin, points, max_range) takes a scan;
+    m.occupied, m.free and m.space go wherever an OccupancyGrid or a SpaceMap goes."""
+    if isinstance(grid_or_points, ops.SpaceMap):
+        return ops.EvidenceMap.from_space(grid_or_points, **params)
+    if isinstance(grid_or_points, ops.OccupancyGrid):
+        return ops.EvidenceMap.like(grid_or_points, **params)
+    return ops.EvidenceMap.like(ops.OccupancyGrid.from_points(grid_or_points, resolution=resolution), **params)
+
+
 class _Result:
     """What the result classes share: the keyword constructor; each names its fields in its own __slots__."""
     __slots__ = ()
