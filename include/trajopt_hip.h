@@ -41,7 +41,10 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_evid_bytes / tohip_evid_init / tohip_evid_fold / tohip_evid_positions (a hit/miss evidence map: integer log-odds
+/* (still 15) + tohip_clearance_map / tohip_clearance_map_segments and the flag bit TOHIP_TRAJ_CLEARANCE_PREFILLED (the clearance term
+ * asked of the map: the obstacles are an occupancy grid's voxels): new symbols and one flag bit that was refused before — no struct
+ * and no existing signature changes.
+ * (still 15) + tohip_evid_bytes / tohip_evid_init / tohip_evid_fold / tohip_evid_positions (a hit/miss evidence map: integer log-odds
  * per voxel, the occupied and free planes derived from it): new symbols only.
  * (still 15) + tohip_field_bytes / tohip_field_workspace_bytes / tohip_field_build / tohip_field_positions / tohip_field_segments /
  * tohip_field_nodes (a conservative clearance field over the occupancy grid): new symbols only.
@@ -152,6 +155,13 @@ size_t tohip_traj_workspace_bytes(int64_t n_points, int64_t n_virtual);
  * query's do, and clearance_scratch is then tohip_traj_clearance_segments_scratch_bytes.  Without the bit, or with weight 0, every
  * launch is the one without it. */
 #define TOHIP_TRAJ_CLEARANCE_SEGMENTS 4
+/* tohip_traj_loss.flags and tohip_traj_opt.flags only: with clearance_weight > 0 the caller has ALREADY written clearance_scratch's
+ * gradient rows and terms for the current poses, on the same stream, and the step launches no clearance query of its own — how a
+ * plan carries a term whose obstacles its struct cannot name (the map's voxels: tohip_clearance_map / _map_segments, below).  With
+ * or without TOHIP_TRAJ_CLEARANCE_SEGMENTS, which then only sizes the scratch.  The scratch then holds the caller's data while the
+ * step reads and writes its other buffers, so it must be a buffer of its own: a clearance_scratch that is any other device pointer of
+ * the struct is TOHIP_EINVAL.  With weight 0 the bit does nothing. */
+#define TOHIP_TRAJ_CLEARANCE_PREFILLED 8
 
 /* Forward over the W evaluated waypoints (caller has applied wps_step, model.py:214-217):
  * to_camera_frame -> get_dist_mask * get_fov_mask -> per-waypoint (p-min)/max -> clip -> log-odds,
@@ -401,7 +411,7 @@ typedef struct tohip_traj_opt {
     int64_t n_points;
     int64_t n_wps;             /* W: waypoints of ONE trajectory */
     int32_t wps_step;          /* every wps_step-th waypoint is evaluated for visibility */
-    int32_t flags;             /* TOHIP_TRAJ_DENSE, TOHIP_TRAJ_OPT_LAST_OUTPUTS, TOHIP_TRAJ_CLEARANCE_SEGMENTS or 0 */
+    int32_t flags;             /* TOHIP_TRAJ_DENSE, TOHIP_TRAJ_OPT_LAST_OUTPUTS, TOHIP_TRAJ_CLEARANCE_SEGMENTS, TOHIP_TRAJ_CLEARANCE_PREFILLED or 0 */
     int32_t n_traj;            /* trajectories laid end to end: rows b * W .. b * W + W - 1 of every per-waypoint array */
     int32_t n_steps;           /* rows of the logs below */
     const int32_t *traj_offsets; /* n_traj + 1 device int32: b * ceil(W / wps_step) (NULL when n_traj == 1) */
@@ -1235,6 +1245,29 @@ int tohip_evid_fold(void *evid, size_t evid_bytes, void *hit_plane, void *pass_p
                     int32_t threshold, int32_t clear_scan, uint64_t *counts, void *stream);
 int tohip_evid_positions(const void *evid, size_t evid_bytes, const tohip_occ_geom *geom, int32_t threshold, const float *positions,
                          int64_t m, int8_t *values, uint8_t *state, void *stream);
+
+/* ---- clearance from the map (clearance_map_kernels.hip, DESIGN.md §10, "Clearance from the map") -------
+ * tohip_clearance and tohip_clearance_segments with the voxels of an occupancy grid as the obstacles.  occupied: a grid buffer of
+ * grid_bytes; free_or_null: NULL, or the free plane of the same geometry (not `occupied` itself).  An OBSTACLE is a voxel inside
+ * dims whose occupied bit is set and, with a free plane, also one of state 0 (neither bit: unknown) — tohip_field_build's rule.  An
+ * obstacle IS the point at its centre, fl(origin_a + fl(fl((float)i_a + 0.5f) resolution)) per axis, tohip_occ_export's bits.  d2,
+ * the hinge, the term, s and the gradients are the two definitions above applied to those points; ties go to the lowest linear
+ * index (z ny + y) nx + x, and idx is that index (-1: no obstacle has d2 < fl(r r), or a query coordinate is not finite).  So over
+ * the obstacle centres C in ascending linear index both calls equal tohip_clearance / tohip_clearance_segments over a packed cloud
+ * of C bit for bit, idx through C's index.  A query outside dims, in the apron or beyond it, is an ordinary query.  radius > 0,
+ * finite, and at most 64 voxels (radius / resolution <= 64: TOHIP_EINVAL beyond); weight >= 0, finite.  The workspaces are
+ * tohip_clearance_workspace_bytes(n_queries) and tohip_clearance_segments_workspace_bytes(n_wps, n_traj), with the same contents
+ * after the call.  To fill a plan's clearance_scratch (TOHIP_TRAJ_CLEARANCE_PREFILLED) pass grad = clearance_scratch and workspace =
+ * clearance_scratch + align256(12 n_traj n_wps), workspace_bytes = the scratch's bytes less that offset: the rows and the terms
+ * (and the per-segment parts) land where the step reads them.  One block of 16 waves per query scans only the bricks within the
+ * radius of the waypoint or segment; no atomics: the results do not depend on the launch.  Every argument check returns before
+ * anything is enqueued; nothing synchronises with the host. */
+int tohip_clearance_map(const void *occupied, const void *free_or_null, size_t grid_bytes, const tohip_occ_geom *geom,
+                        const float *queries, int64_t n_queries, float radius, float weight, float *d, int32_t *idx, float *value,
+                        float *grad, int accumulate, void *workspace, size_t workspace_bytes, void *stream);
+int tohip_clearance_map_segments(const void *occupied, const void *free_or_null, size_t grid_bytes, const tohip_occ_geom *geom,
+                                 const float *poses, int64_t n_wps, int64_t n_traj, float radius, float weight, float *d, int32_t *idx,
+                                 float *s, float *value, float *grad, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- optional per-kernel timing (bench.py's roofline leg) -----------------------------------------
  * When enabled, every launch of the big kernels is bracketed by hipEventRecord on its own stream.

@@ -7,7 +7,9 @@
 //   2. waves per query   k_clearance and k_clearance_seg: a block of TO_CLR_WAVES waves per query, folded through LDS (clr_block_min);
 //                        k_clearance_edge: one wave per query, TO_EDGE_WAVES queries to a block, no LDS and no barrier
 //   3. the finish        k_clearance: clr_point_finish;  the other two: clr_seg_finish, to which k_clearance_seg adds the term and
-//                        the gradient parts
+//                        the gradient parts (clr_seg_write).  A finish takes the winner's three f32 coordinates, read here from the
+//                        packed cloud (clr_cloud_point): the kernels whose obstacles are a map's voxels (clearance_map_kernels.hip)
+//                        hand it a voxel centre and share everything from there on
 // So "a = b is the point query" and "an edge's (d, idx, s) are the segment query's" hold bit for bit: ClrSegment::d2 with a = b
 // rounds to ClrPoint::d2's bits for every point (u - 0 e = u, and (-v)(-v) = v v), the two segment kernels instantiate the same
 // geometry and call the same finish, and the winner does not depend on how many waves looked for it (below).
@@ -40,6 +42,8 @@
 // atomics; the per-query results do not depend on the launch.  (One wave per query walked the 4 096 spheres of a 1 M-point cloud in
 // 64 dependent steps: 40 us for 128 queries on a chip that had 128 waves to run.  The edge stage asks all pairs of 257 nodes, 32 896
 // queries, far more than the chip has room for at once: there 16 waves to a query buy no latency and cost a block-wide fold each.)
+#include <initializer_list>
+
 #include "common.hpp"
 #include "opt_step.hpp"
 
@@ -168,8 +172,8 @@ __device__ __forceinline__ bool clr_block_min(unsigned long long& best, unsigned
 }
 
 // ---- the point query ---------------------------------------------------------------------------------------------------------------
-struct ClrArgs {
-    CloudView cv;
+struct ClrQuery {          // what the point query asks and writes, whatever its obstacles are (the cloud here; the map's voxels:
+                           // clearance_map_kernels.hip)
     const float* q;        // (nq, 3) query positions
     int64_t nq;
     float r, weight;
@@ -179,9 +183,21 @@ struct ClrArgs {
     float* grad;           // may be NULL: (nq, 3) gradient rows, overwritten or (accumulate) added to
     int accumulate;
 };
+struct ClrArgs : ClrQuery {
+    CloudView cv;
+};
 
+// the winner's three f32 coordinates as the cloud holds them (zeros when there is none)
+__device__ __forceinline__ void clr_cloud_point(const CloudView& cv, unsigned long long best, float (&x)[3]) {
+    x[0] = x[1] = x[2] = 0.f;
+    if (best == ~0ull) return;
+    const int64_t s = cv.inv[(int)(unsigned)(best & 0xffffffffull)];
+    for (int k = 0; k < 3; ++k) x[k] = cv.soa[k * cv.npad + s];
+}
+
+// x: the winner's coordinates (not read when best = ~0)
 // (its gradient divides by d = sqrt((double)d2), the segment's by |c - x| recomputed in f64: not the same bits, so not one formula)
-__device__ __forceinline__ void clr_point_finish(const ClrArgs& a, const ClrPoint& t, int64_t w, unsigned long long best) {
+__device__ __forceinline__ void clr_point_finish(const ClrQuery& a, const ClrPoint& t, int64_t w, unsigned long long best, const float (&x)[3]) {
     float dout = INFINITY, g[3] = {0.f, 0.f, 0.f};
     int iout = -1;
     double term = 0.0;
@@ -193,11 +209,9 @@ __device__ __forceinline__ void clr_point_finish(const ClrArgs& a, const ClrPoin
         const double h = (double)a.r - d;
         term = h * h;
         if (d > 0.0) {
-            const int64_t s = a.cv.inv[iout];
             const double c = -2.0 * (double)a.weight * h;
             const double t3[3] = {(double)t.tx, (double)t.ty, (double)t.tz};
-            const float* P = a.cv.soa;
-            for (int k = 0; k < 3; ++k) g[k] = (float)(c * (t3[k] - (double)P[k * a.cv.npad + s]) / d);
+            for (int k = 0; k < 3; ++k) g[k] = (float)(c * (t3[k] - (double)x[k]) / d);
         }
     }
     if (a.d) a.d[w] = dout;
@@ -212,7 +226,10 @@ __global__ void __launch_bounds__(TO_CLR_WAVES * 64) k_clearance(ClrArgs a) {
     const int64_t w = blockIdx.x;   // the query
     const ClrPoint t(a.q + 3 * w);
     unsigned long long best = clr_search<TO_CLR_WAVES>(a.cv, t, a.r, threadIdx.x >> 6);
-    if (clr_block_min(best, sbest)) clr_point_finish(a, t, w, best);
+    if (!clr_block_min(best, sbest)) return;
+    float x[3];
+    clr_cloud_point(a.cv, best, x);
+    clr_point_finish(a, t, w, best, x);
 }
 
 // ---- the segment queries -----------------------------------------------------------------------------------------------------------
@@ -222,19 +239,18 @@ struct ClrSegHit {
     double v[3];      // c - x
 };
 
-__device__ __forceinline__ ClrSegHit clr_seg_finish(const CloudView& cv, const ClrSegment& g, unsigned long long best) {
+// x: the winner's coordinates (not read when best = ~0)
+__device__ __forceinline__ ClrSegHit clr_seg_finish(const ClrSegment& g, unsigned long long best, const float (&x)[3]) {
     ClrSegHit o = {-1, (double)INFINITY, 0.0, {0.0, 0.0, 0.0}};
     if (best == ~0ull) return o;
     const float d2 = __uint_as_float((unsigned)(best >> 32));
     o.idx = (int)(unsigned)(best & 0xffffffffull);
     o.d = sqrt((double)d2);
-    const int64_t slot = cv.inv[o.idx];
-    const float* P = cv.soa;
     const double a3[3] = {(double)g.ax, (double)g.ay, (double)g.az}, b3[3] = {(double)g.bx, (double)g.by, (double)g.bz};
     double e3[3], u3[3], ee = 0.0, dot = 0.0;
     for (int k = 0; k < 3; ++k) {
         e3[k] = b3[k] - a3[k];
-        u3[k] = (double)P[k * cv.npad + slot] - a3[k];
+        u3[k] = (double)x[k] - a3[k];
         ee += e3[k] * e3[k];
         dot += u3[k] * e3[k];
     }
@@ -243,8 +259,7 @@ __device__ __forceinline__ ClrSegHit clr_seg_finish(const CloudView& cv, const C
     return o;
 }
 
-struct ClrSegArgs {
-    CloudView cv;
+struct ClrSegQuery {       // what the segment query asks and writes, whatever its obstacles are
     const float* p;        // (n_traj W, 3) waypoint positions, trajectories end to end
     int W;                 // waypoints of one trajectory (>= 2): segment blockIdx.x = (b, w), b = blockIdx.x / (W - 1)
     float r, weight;
@@ -255,14 +270,17 @@ struct ClrSegArgs {
     double* part;          // (n_traj (W - 1), 6) g_a, g_b of every segment in f64
 };
 
-__global__ void __launch_bounds__(TO_CLR_WAVES * 64) k_clearance_seg(ClrSegArgs a) {
-    __shared__ unsigned long long sbest[TO_CLR_WAVES];
-    const int64_t seg = blockIdx.x;
-    const int64_t row = seg / (a.W - 1) * a.W + seg % (a.W - 1);   // the waypoint row of the segment's first end
-    const ClrSegment g(a.p + 3 * row, a.p + 3 * row + 3);
-    unsigned long long best = clr_search<TO_CLR_WAVES>(a.cv, g, a.r, threadIdx.x >> 6);
-    if (!clr_block_min(best, sbest)) return;
-    const ClrSegHit hit = clr_seg_finish(a.cv, g, best);
+struct ClrSegArgs : ClrSegQuery {
+    CloudView cv;
+};
+
+// the waypoint row of segment seg's first end
+__device__ __forceinline__ int64_t clr_seg_row(int64_t seg, int W) { return seg / (W - 1) * W + seg % (W - 1); }
+
+// one thread: the segment's outputs, its term and its gradient parts from the block's winner
+__device__ __forceinline__ void clr_seg_write(const ClrSegQuery& a, const ClrSegment& g, int64_t seg, int64_t row, unsigned long long best,
+                                              const float (&x)[3]) {
+    const ClrSegHit hit = clr_seg_finish(g, best, x);
     double term = 0.0, part[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (hit.idx >= 0) {
         const double h = (double)a.r - hit.d;
@@ -284,6 +302,18 @@ __global__ void __launch_bounds__(TO_CLR_WAVES * 64) k_clearance_seg(ClrSegArgs 
     for (int k = 0; k < 6; ++k) a.part[6 * seg + k] = part[k];
 }
 
+__global__ void __launch_bounds__(TO_CLR_WAVES * 64) k_clearance_seg(ClrSegArgs a) {
+    __shared__ unsigned long long sbest[TO_CLR_WAVES];
+    const int64_t seg = blockIdx.x;
+    const int64_t row = clr_seg_row(seg, a.W);
+    const ClrSegment g(a.p + 3 * row, a.p + 3 * row + 3);
+    unsigned long long best = clr_search<TO_CLR_WAVES>(a.cv, g, a.r, threadIdx.x >> 6);
+    if (!clr_block_min(best, sbest)) return;
+    float x[3];
+    clr_cloud_point(a.cv, best, x);
+    clr_seg_write(a, g, seg, row, best, x);
+}
+
 // arbitrary segments, one WAVE each: tohip_clearance_segments with n_wps = 2 would answer them with a block of 16 waves apiece
 struct ClrEdgeArgs {
     CloudView cv;
@@ -302,7 +332,9 @@ __global__ void __launch_bounds__(TO_EDGE_WAVES * 64) k_clearance_edge(ClrEdgeAr
     const ClrSegment g(a.a + 3 * e, a.b + 3 * e);
     const unsigned long long best = clr_search<1>(a.cv, g, a.r, 0);
     if ((threadIdx.x & 63) != 0) return;
-    const ClrSegHit hit = clr_seg_finish(a.cv, g, best);
+    float x[3];
+    clr_cloud_point(a.cv, best, x);
+    const ClrSegHit hit = clr_seg_finish(g, best, x);
     if (a.d) a.d[e] = (float)hit.d;
     if (a.idx) a.idx[e] = hit.idx;
     if (a.s) a.s[e] = (float)hit.s;
@@ -330,6 +362,14 @@ __global__ void k_clearance_value(const double* __restrict__ term, int64_t n_seg
 }
 
 static inline bool clearance_args_ok(float r, float weight) { return std::isfinite(r) && r > 0.f && std::isfinite(weight) && weight >= 0.f; }
+
+// TOHIP_TRAJ_CLEARANCE_PREFILLED: the scratch holds the caller's rows and terms while the step reads and writes its other buffers, so
+// it must be a buffer of its own — none of `others`, the plan's other device buffers
+static inline bool clearance_prefilled_ok(const void* scratch, std::initializer_list<const void*> others) {
+    for (const void* o : others)
+        if (o == scratch) return false;
+    return true;
+}
 
 // the query kernel for the paths that carry the term (tohip_clearance, the one-call step, the one-call model, the step tail)
 static inline int clearance_launch(const void* packed, int64_t n_points, const float* q, int64_t nq, float r, float weight, float* d,

@@ -54,6 +54,9 @@ inline bool loss_plan_ok(const tohip_traj_loss* p, LossLayout* l, int* C) {
                                                                                                                   : clearance_scratch_bytes(p->n_wps)) ||
                                        p->n_points > INT32_MAX))
         return false;
+    if (p->clearance_weight != 0.f && (p->flags & TOHIP_TRAJ_CLEARANCE_PREFILLED) &&
+        !clearance_prefilled_ok(p->clearance_scratch, {p->packed, p->poses0, p->workspace, p->scratch, p->reg_terms}))
+        return false;
     *C = (p->rig.n_cams > 0 && p->rig.rig_quats) ? p->rig.n_cams : 1;
     *l = loss_layout(p->n_points, p->n_wps, p->wps_step, *C);
     return true;
@@ -105,15 +108,16 @@ extern "C" int tohip_traj_loss_forward(const tohip_traj_loss* p, const float* po
     const tohip_rig* rig = C > 1 || p->rig.rig_quats ? &p->rig : nullptr;
     // probe (+ the regularisers' block), pass 1, k_traj_sparse<FUSED>, the pair sums with unit upstream gradient (+ the scalars' block)
     TrajStep s;
-    int rc = traj_step_init(s, p->packed, p->n_points, l.n_eval, 1, nullptr, &p->cam, rig, p->flags & 0xff & ~TOHIP_TRAJ_CLEARANCE_SEGMENTS, nullptr, p->workspace, p->workspace_bytes, st, true);
+    int rc = traj_step_init(s, p->packed, p->n_points, l.n_eval, 1, nullptr, &p->cam, rig, p->flags & 0xff & ~(TOHIP_TRAJ_CLEARANCE_SEGMENTS | TOHIP_TRAJ_CLEARANCE_PREFILLED), nullptr, p->workspace, p->workspace_bytes, st, true);
     if (rc != TOHIP_OK) return rc;
     s.wp_stride = p->wps_step;   // every wps_step-th waypoint is evaluated (model.py:215-217): the probe reads them in place
     loss_opt(s.opt, p, l);
     s.opt.poses = const_cast<float*>(poses);
     s.opt.loss_log = loss_terms;
     s.opt_scalars = scal;
-    if (s.opt.clr) {   // one launch more, first: the clearance query of every waypoint — or, TOHIP_TRAJ_CLEARANCE_SEGMENTS, of every
-                       // segment and its per-waypoint combine (the prologue block sums its terms)
+    if (s.opt.clr && !(p->flags & TOHIP_TRAJ_CLEARANCE_PREFILLED)) {
+        // one launch more, first: the clearance query of every waypoint — or, TOHIP_TRAJ_CLEARANCE_SEGMENTS, of every segment and its
+        // per-waypoint combine (the prologue block sums its terms); PREFILLED: the caller's launches have written them
         rc = clearance_scratch_launch(p->packed, p->n_points, poses, p->n_wps, 1, p->clearance_radius, p->clearance_weight,
                                       (p->flags & TOHIP_TRAJ_CLEARANCE_SEGMENTS) != 0, p->clearance_scratch, st);
         if (rc != TOHIP_OK) return rc;
@@ -132,7 +136,7 @@ extern "C" int tohip_traj_loss_backward(const tohip_traj_loss* p, const float* g
     float* qge = (float*)(sc + l.off_qge);
     const tohip_rig* rig = C > 1 || p->rig.rig_quats ? &p->rig : nullptr;
     TrajStep s;
-    int rc = traj_step_init(s, p->packed, p->n_points, l.n_eval, 1, nullptr, &p->cam, rig, p->flags & 0xff & ~TOHIP_TRAJ_CLEARANCE_SEGMENTS, nullptr, p->workspace, p->workspace_bytes, st, false);
+    int rc = traj_step_init(s, p->packed, p->n_points, l.n_eval, 1, nullptr, &p->cam, rig, p->flags & 0xff & ~(TOHIP_TRAJ_CLEARANCE_SEGMENTS | TOHIP_TRAJ_CLEARANCE_PREFILLED), nullptr, p->workspace, p->workspace_bytes, st, false);
     if (rc != TOHIP_OK) return rc;
     loss_opt(s.opt, p, l);
     s.opt.pg = poses_grad; s.opt.qg = quats_grad; s.opt.gout = gout;
@@ -149,7 +153,7 @@ extern "C" int tohip_traj_loss_refresh(const tohip_traj_loss* p, void* stream_) 
     if (p->scratch_bytes < l.total) return TOHIP_ENOSPC;
     const tohip_rig* rig = C > 1 || p->rig.rig_quats ? &p->rig : nullptr;
     TrajStep s;
-    int rc = traj_step_init(s, p->packed, p->n_points, l.n_eval, 1, nullptr, &p->cam, rig, p->flags & 0xff & ~TOHIP_TRAJ_CLEARANCE_SEGMENTS, nullptr, p->workspace, p->workspace_bytes, stream_, false);
+    int rc = traj_step_init(s, p->packed, p->n_points, l.n_eval, 1, nullptr, &p->cam, rig, p->flags & 0xff & ~(TOHIP_TRAJ_CLEARANCE_SEGMENTS | TOHIP_TRAJ_CLEARANCE_PREFILLED), nullptr, p->workspace, p->workspace_bytes, stream_, false);
     if (rc != TOHIP_OK) return rc;
     return launch_pairs(s, sparse_args(s, (float*)((char*)p->scratch + l.off_lo)));
 }

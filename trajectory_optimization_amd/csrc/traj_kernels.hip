@@ -2501,13 +2501,18 @@ extern "C" int tohip_traj_opt_step(const tohip_traj_opt* o, int32_t step_index, 
     if (!o || !o->packed || !o->poses || !o->quats || !o->poses0 || !o->exp_avg_p || !o->exp_avg_sq_p || !o->exp_avg_q || !o->exp_avg_sq_q ||
         !o->poses_grad || !o->quats_grad || !o->lo_sum || !o->minmax || !o->rewards || !o->scalars || !o->loss_log || !o->state_log ||
         !o->workspace || !o->scratch || o->n_points <= 0 || o->n_wps < 3 || o->wps_step < 1 || o->n_traj < 1 || step_index < 0 ||
-        step_index >= o->n_steps || (o->n_traj > 1 && !o->traj_offsets) || (o->flags & ~(TOHIP_TRAJ_DENSE | TOHIP_TRAJ_OPT_LAST_OUTPUTS | TOHIP_TRAJ_CLEARANCE_SEGMENTS)) != 0)
+        step_index >= o->n_steps || (o->n_traj > 1 && !o->traj_offsets) || (o->flags & ~(TOHIP_TRAJ_DENSE | TOHIP_TRAJ_OPT_LAST_OUTPUTS | TOHIP_TRAJ_CLEARANCE_SEGMENTS | TOHIP_TRAJ_CLEARANCE_PREFILLED)) != 0)
         return TOHIP_EINVAL;
     const int64_t W = o->n_wps, B = o->n_traj, n_eval = (W + o->wps_step - 1) / o->wps_step;
     const OptLayout l = opt_layout(W, B);
     if (o->scratch_bytes < l.total) return TOHIP_ENOSPC;
     const bool clr = o->clearance_weight != 0.f;   // zero-initialised: the step without the clearance term
     if (clr && (!clearance_args_ok(o->clearance_radius, o->clearance_weight) || !o->clearance_scratch || o->n_points > INT32_MAX))
+        return TOHIP_EINVAL;
+    if (clr && (o->flags & TOHIP_TRAJ_CLEARANCE_PREFILLED) &&
+        !clearance_prefilled_ok(o->clearance_scratch, {o->packed, o->poses, o->quats, o->poses0, o->exp_avg_p, o->exp_avg_sq_p, o->exp_avg_q,
+                                                       o->exp_avg_sq_q, o->poses_grad, o->quats_grad, o->lo_sum, o->minmax, o->rewards, o->scalars,
+                                                       o->loss_log, o->state_log, o->workspace, o->scratch}))
         return TOHIP_EINVAL;
     const bool clr_seg = clr && (o->flags & TOHIP_TRAJ_CLEARANCE_SEGMENTS) != 0;   // the swept term: the segment query in place of the point query
     if (clr && o->clearance_scratch_bytes < (clr_seg ? clearance_seg_scratch_bytes(W, B) : clearance_scratch_bytes(W * B))) return TOHIP_ENOSPC;
@@ -2542,9 +2547,11 @@ extern "C" int tohip_traj_opt_step(const tohip_traj_opt* o, int32_t step_index, 
         a.clr = clearance_scratch_grad(o->clearance_scratch);
         a.clr_term = clearance_scratch_term(o->clearance_scratch, W * B);
         a.clr_w = o->clearance_weight;
-        rc = clearance_scratch_launch(o->packed, o->n_points, o->poses, W, B, o->clearance_radius, o->clearance_weight, clr_seg,
-                                      o->clearance_scratch, s.st);
-        if (rc != TOHIP_OK) return rc;
+        if (!(o->flags & TOHIP_TRAJ_CLEARANCE_PREFILLED)) {   // (PREFILLED: the caller's launches have written the rows and terms)
+            rc = clearance_scratch_launch(o->packed, o->n_points, o->poses, W, B, o->clearance_radius, o->clearance_weight, clr_seg,
+                                          o->clearance_scratch, s.st);
+            if (rc != TOHIP_OK) return rc;
+        }
     }
     rc = traj_fused_forward(s, o->poses, o->quats, o->lo_sum, o->minmax, o->rewards);
     if (rc != TOHIP_OK) return rc;

@@ -260,10 +260,10 @@ class _Clearance(torch.autograd.Function):
     def forward(ctx, poses, model):
         rows = torch.empty((poses.shape[0], 3), dtype=torch.float32, device=poses.device)
         if model.clearance_mode == "segments":
-            value = ops.clearance_segments(model._cloud, poses.detach(), model.clearance_radius, model.clearance_weight, grad=rows,
+            value = ops.clearance_segments(model._clearance_source, poses.detach(), model.clearance_radius, model.clearance_weight, grad=rows,
                                            want_value=True)[3].reshape(())
         else:
-            _, _, value = ops.clearance(model._cloud, poses.detach(), model.clearance_radius, model.clearance_weight, grad=rows,
+            _, _, value = ops.clearance(model._clearance_source, poses.detach(), model.clearance_radius, model.clearance_weight, grad=rows,
                                         want_value=True)
         ctx.save_for_backward(rows)
         return value
@@ -337,7 +337,7 @@ class _TrajLoss(torch.autograd.Function):
         if model._clearance_on:   # every rank: all W waypoints, the whole cloud
             clr_rows = torch.empty((W, 3), dtype=torch.float32, device=p_all.device)
             clr_terms = ops.clearance_terms(W, 1, model.clearance_mode, p_all.device)
-            ops.clearance_rows(model._cloud, p_all, model.clearance_radius, model.clearance_weight, model.clearance_mode, 1, clr_rows, clr_terms)
+            ops.clearance_rows(model._clearance_source, p_all, model.clearance_radius, model.clearance_weight, model.clearance_mode, 1, clr_rows, clr_terms)
         terms, reg_sum, reg_terms = _regularizers(model, p_all, scalars, clr_terms)
         ctx.step, ctx.step_w, ctx.W = st, step_w, W
         ctx.set_materialize_grads(False)
@@ -400,7 +400,7 @@ class _LossPlan:
         c.workspace, c.workspace_bytes = self.ws.buf.data_ptr(), self.ws.bytes
         c.scratch, c.scratch_bytes = self.scratch.data_ptr(), nbytes
         c.reg_terms = self.reg_terms.data_ptr()
-        self.clr_rows = None
+        self.clr_rows = self.clr_fill = None
         if model._clearance_on:   # the clearance term: its gradient rows (W,3) lead the plan's clearance scratch
             if model.clearance_mode == "segments":   # the swept term: the flag bit and the larger scratch (rows and terms where they were)
                 c.flags |= ops.CLEARANCE_SEGMENTS
@@ -411,6 +411,9 @@ class _LossPlan:
             self.clr_rows = self.clr_scratch[:12 * W].view(torch.float32).view(W, 3)
             c.clearance_radius, c.clearance_weight = float(model.clearance_radius), float(model.clearance_weight)
             c.clearance_scratch, c.clearance_scratch_bytes = self.clr_scratch.data_ptr(), cb
+            if model._clr_map is not None:   # the map's term: forward() fills the scratch itself, the library launches no query
+                c.flags |= ops.CLEARANCE_PREFILLED
+                self.clr_fill = ops.clearance_scratch_views(self.clr_scratch, W)
         self.c, self.ref = c, ctypes.byref(c)
         self.model = model
         self.fwd, self.bwd, self.refresh = L.tohip_traj_loss_forward, L.tohip_traj_loss_backward, L.tohip_traj_loss_refresh
@@ -423,6 +426,9 @@ class _LossPlan:
     def forward(self, poses, quats, rewards, terms):
         self.ws.generation += 1
         self.sums_stale = False
+        if self.clr_fill is not None:   # the map as it is now: its rows and terms for these poses, on the stream of the call below
+            m = self.model
+            ops.clearance_rows(m._clr_map, poses, m.clearance_radius, m.clearance_weight, m.clearance_mode, 1, *self.clr_fill)
         rc = _lib.on_device(self.dev_index, self.fwd, self.ref, poses.data_ptr(), quats.data_ptr(), rewards.data_ptr(), terms.data_ptr())
         if rc:
             check(rc, "tohip_traj_loss_forward")
@@ -803,6 +809,8 @@ class ModelTraj(nn.Module):
     `prior_log_odds=` an (N,) tensor of what is already known of the map (OctoMap's accumulated log-odds, >= 0, in the caller's point
     order): rewards become sigmoid(lo_sum + prior) — see the prior_log_odds property and coverage_log_odds().  An ops.CoverageMap is
     accepted in its place: the prior is its lookup over this cloud (commit_coverage folds a plan back into it).
+    `clearance_map=` an ops.OccupancyGrid, SpaceMap or EvidenceMap: the clearance term keeps the path off the map's occupied voxels
+    (`clearance_unknown='obstacle'`: and its never-seen ones) instead of off `points`; the map is read as it is at every step.
     """
 
     def __init__(self,
@@ -817,7 +825,7 @@ class ModelTraj(nn.Module):
                  *, rig=None, shard=None, dense=False, occlusion=None, occlusion_limits=(1.0, 15.0), occlusion_refresh_every=1,
                  occlusion_refresh_tol=None, occlusion_check_every=5, n_points_global=None, cloud=None, fast_adam=False,
                  clearance_radius=None, clearance_weight=0.0, prior_log_odds=None, clearance_mode='waypoints', occlusion_grid=None,
-                 occlusion_voxel=0.1):
+                 occlusion_voxel=0.1, clearance_map=None, clearance_unknown='free'):
         super().__init__()
         # the clearance term (clearance_kernels.hip): weight x sum over ALL waypoints of (r - d)^2, d = the distance to the nearest
         # cloud point within r — it keeps the path off the cloud; weight 0 (the default): off, the reference's criterion as it is.
@@ -827,6 +835,10 @@ class ModelTraj(nn.Module):
         self._clr = (None, 0.0)
         self._clr_mode = "waypoints"
         self.set_clearance(clearance_radius, clearance_weight, clearance_mode)
+        # clearance_map= an ops.OccupancyGrid, SpaceMap or EvidenceMap: the term's obstacles are the map's voxels (their centres), read
+        # at every step as the map is then, instead of this model's cloud; clearance_unknown='obstacle': never-seen voxels repel too
+        self._clr_map = None
+        self.set_clearance_map(clearance_map, clearance_unknown)
         assert wps_poses.dim() == wps_quats.dim()
         assert wps_poses.size()[1] == 3
         assert wps_quats.size()[1] == 4
@@ -927,6 +939,21 @@ class ModelTraj(nn.Module):
             raise ValueError("the clearance term needs the whole cloud on every rank: not available with PointShard")
         self._clr, self._clr_mode = (r if w > 0.0 else radius, w), mode
 
+    def set_clearance_map(self, map, unknown='free'):
+        """The map whose voxels the clearance term keeps the path off (an ops.OccupancyGrid, SpaceMap or EvidenceMap; unknown 'free'
+        or 'obstacle': ops.MapObstacles' rule, ValueError otherwise), or None: the model's own cloud again.  The model keeps the map
+        object and reads its buffers at every step: an insert or an integrate between two steps is seen by the next one."""
+        self._clr_map = ops.MapObstacles(map, unknown) if map is not None else None
+
+    @property
+    def clearance_map(self):
+        return self._clr_map.map if self._clr_map is not None else None
+
+    @property
+    def _clearance_source(self):
+        """What the clearance queries search: the map's obstacles when there is a clearance_map, the packed cloud otherwise."""
+        return self._clr_map if self._clr_map is not None else self._cloud
+
     @property
     def clearance_mode(self):
         return self._clr_mode
@@ -1015,6 +1042,9 @@ class ModelTraj(nn.Module):
         if kw.get("occlusion") == "voxel" and other._occlusion_grid is not None:   # (the same grid object, not one more of the same points)
             kw.setdefault("occlusion_grid", other._occlusion_grid)
             kw.setdefault("occlusion_voxel", other._occlusion_voxel)
+        if other._clr_map is not None and "clearance_map" not in kw:   # (the same map objects: what a batched or a team run demands)
+            kw["clearance_map"] = other._clr_map.map
+            kw.setdefault("clearance_unknown", other._clr_map.unknown)
         return cls(other._cloud, wps_poses, wps_quats, other.K, other.img_width, other.img_height, **kw)
 
     @property
@@ -1140,7 +1170,7 @@ class ModelTraj(nn.Module):
         """The library-side description of this model for the one-call forward / backward (rebuilt when something it froze
         has changed: the weights of criterion, the mode, the initial trajectory, the number of waypoints)."""
         key = (step_w, float(self.smoothness_weight), float(self.traj_length_weight), self._flags, self.poses0.data_ptr(),
-               self.poses.shape[0], self._clearance_on, self.clearance_radius, self.clearance_weight, self.clearance_mode)
+               self.poses.shape[0], self._clearance_on, self.clearance_radius, self.clearance_weight, self.clearance_mode, self._clr_map)
         if self._plan_key != key:
             self._plan_obj, self._plan_key = _LossPlan(self, step_w), key
         return self._plan_obj
@@ -1242,7 +1272,7 @@ class _TeamLoss(torch.autograd.Function):
         if m0._clearance_on:
             clr_rows = torch.empty((B * W, 3), dtype=torch.float32, device=p_all.device)
             clr_terms = ops.clearance_terms(W, B, m0.clearance_mode, p_all.device)
-            ops.clearance_rows(m0._cloud, p_all, m0.clearance_radius, m0.clearance_weight, m0.clearance_mode, B, clr_rows, clr_terms)
+            ops.clearance_rows(m0._clearance_source, p_all, m0.clearance_radius, m0.clearance_weight, m0.clearance_mode, B, clr_rows, clr_terms)
         terms, total, reg = ops.team_loss(p_all, team._poses0, B, m0.smoothness_weight, m0.traj_length_weight, m0.eps, scalars,
                                           m0.clearance_weight, clr_terms)
         ctx.team, ctx.step, ctx.gen, ctx.step_w, ctx.W, ctx.n_eval, ctx.has_clr = team, st, st.ws.generation, step_w, W, n_eval, clr_rows is not None

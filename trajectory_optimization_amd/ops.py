@@ -1553,10 +1553,53 @@ def team_member_gains(cloud, lo_members, prior=None):
     return gain, h[1 + B:1 + 2 * B].clone()
 
 
+CLEARANCE_MAP_MAX_VOXELS = 64   # of radius / resolution: a waypoint's window is at most 131^3 voxels
+CLEARANCE_PREFILLED = _lib.CONSTANTS["TOHIP_TRAJ_CLEARANCE_PREFILLED"]
+
+
+class MapObstacles:
+    """The clearance term's obstacles taken from a map (clearance_map_kernels.hip, DESIGN.md 10 "Clearance from the map"): accepted
+    by clearance, clearance_segments and clearance_rows where they take a PackedCloud.  map: an OccupancyGrid, a SpaceMap or an
+    EvidenceMap; unknown 'free': the occupied voxels are the obstacles; 'obstacle' (a SpaceMap or an EvidenceMap: the free plane
+    tells unknown from free): the never-seen voxels as well — check_field's rule, ValueError otherwise.  Holds the map's two planes
+    — the objects, not copies: every query reads the buffers as they are then — and idx is a voxel's linear index (z ny + y) nx + x."""
+    __slots__ = ("map", "unknown", "occupied", "free")
+
+    def __init__(self, map, unknown="free"):
+        if not isinstance(map, (OccupancyGrid, SpaceMap, EvidenceMap)):
+            raise ValueError(f"clearance_map must be an ops.OccupancyGrid, an ops.SpaceMap or an ops.EvidenceMap, got {type(map).__name__}")
+        self.map, self.unknown = map, unknown
+        self.occupied, self.free, _, _ = check_field(map.space if isinstance(map, EvidenceMap) else map, D=1, unknown=unknown)
+
+    def same_as(self, other):
+        """The same map objects read under the same rule (what a batched or a team run demands of its members)."""
+        return (isinstance(other, MapObstacles) and other.occupied is self.occupied and other.free is self.free and
+                other.unknown == self.unknown)
+
+    def check_radius(self, radius):
+        voxels = float(np.float32(radius)) / float(np.float32(self.occupied.resolution))
+        if not voxels <= CLEARANCE_MAP_MAX_VOXELS:
+            raise ValueError(f"clearance_radius {radius!r} is {voxels:g} voxels of this map; the map query takes at most "
+                             f"{CLEARANCE_MAP_MAX_VOXELS} ({CLEARANCE_MAP_MAX_VOXELS * self.occupied.resolution:g} m at this resolution)")
+
+
+def _clearance_source(source, radius, device):
+    """What names a clearance query's obstacles to the C ABI -> (the entry points' infix, their leading arguments): a PackedCloud's
+    blob and size, or a MapObstacles' planes and geometry (its radius cap and its device are checked here)."""
+    if not isinstance(source, MapObstacles):
+        return "", (source.blob.data_ptr(), source.n)
+    source.check_radius(radius)
+    g = source.occupied
+    if g.device != device:
+        raise ValueError(f"the clearance map lives on {g.device}, the positions on {device}")
+    return "_map", (ptr(g.buf), ptr(source.free.buf) if source.free is not None else None, g.buf.numel(), ctypes.byref(g.geom))
+
+
 def clearance(cloud, positions, radius, weight=0.0, grad=None, accumulate=False, want_value=False, terms=None):
     """tohip_clearance: each position's nearest cloud point within `radius` -> (d (n,) f32, +inf when none; idx (n,) int32 caller rows,
     -1 when none[, value: 0-d f32 = weight x sum (radius - d)^2]).  grad (n, 3) f32, optional: the term's gradient rows, overwritten
-    (accumulate=False) or added to.  terms (optional): a float64 tensor of n entries that receives the per-position (radius - d)^2."""
+    (accumulate=False) or added to.  terms (optional): a float64 tensor of n entries that receives the per-position (radius - d)^2.
+    cloud: a PackedCloud, or a MapObstacles (tohip_clearance_map: the nearest obstacle voxel's centre, idx its linear index)."""
     _require_cuda(positions, "positions")
     q = positions.detach().to(torch.float32).contiguous()
     if q.dim() != 2 or q.shape[1] != 3 or q.shape[0] == 0:
@@ -1572,9 +1615,11 @@ def clearance(cloud, positions, radius, weight=0.0, grad=None, accumulate=False,
         terms = torch.empty(wsb // 8, dtype=torch.float64, device=dev)
     if grad is not None and not (grad.is_contiguous() and grad.dtype == torch.float32 and tuple(grad.shape) == (n, 3)):
         raise ValueError("grad must be a contiguous (n,3) float32 tensor")
+    infix, source = _clearance_source(cloud, r, dev)
+    name = f"tohip_clearance{infix}"
     with torch.cuda.device(dev):
-        check(L.tohip_clearance(cloud.blob.data_ptr(), cloud.n, ptr(q), n, r, w, ptr(d), ptr(idx), ptr(value), ptr(grad),
-                                int(bool(accumulate)), ptr(terms), terms.numel() * 8, stream_ptr()), "tohip_clearance")
+        check(getattr(L, name)(*source, ptr(q), n, r, w, ptr(d), ptr(idx), ptr(value), ptr(grad), int(bool(accumulate)), ptr(terms),
+                               terms.numel() * 8, stream_ptr()), name)
     return (d, idx, value) if want_value else (d, idx)
 
 
@@ -1602,9 +1647,11 @@ def clearance_segments(cloud, poses, radius, weight=0.0, n_traj=1, grad=None, wa
         terms = clearance_terms(W, B, "segments", dev)
     if grad is not None and not (grad.is_contiguous() and grad.dtype == torch.float32 and tuple(grad.shape) == (n, 3)):
         raise ValueError("grad must be a contiguous (n_traj W, 3) float32 tensor")
+    infix, source = _clearance_source(cloud, r, dev)
+    name = f"tohip_clearance{infix}_segments"
     with torch.cuda.device(dev):
-        check(L.tohip_clearance_segments(cloud.blob.data_ptr(), cloud.n, ptr(q), W, B, r, w, ptr(d), ptr(idx), ptr(s), ptr(value), ptr(grad),
-                                         ptr(terms), terms.numel() * 8, stream_ptr()), "tohip_clearance_segments")
+        check(getattr(L, name)(*source, ptr(q), W, B, r, w, ptr(d), ptr(idx), ptr(s), ptr(value), ptr(grad), ptr(terms), terms.numel() * 8,
+                               stream_ptr()), name)
     return (d, idx, s, value) if want_value else (d, idx, s)
 
 
@@ -2006,11 +2053,19 @@ def clearance_terms(n_wps, n_traj, mode, device):
 
 def clearance_rows(cloud, poses, radius, weight, mode, n_traj, grad, terms):
     """The clearance term of `mode` for n_traj trajectories laid end to end: its per-waypoint gradient rows into `grad` and terms into
-    `terms` (clearance_terms) — one launch for 'waypoints', two for 'segments'."""
+    `terms` (clearance_terms) — one launch for 'waypoints', two for 'segments'.  cloud: a PackedCloud or a MapObstacles."""
     if mode == "segments":
         clearance_segments(cloud, poses, radius, weight, n_traj=n_traj, grad=grad, terms=terms)
     else:
         clearance(cloud, poses, radius, weight, grad=grad, terms=terms)
+
+
+def clearance_scratch_views(scratch, n_rows):
+    """The two parts of a plan's clearance scratch (tohip_traj_clearance[_segments]_scratch_bytes, a uint8 tensor) as clearance_rows
+    takes them -> (grad (n_rows, 3) f32 at offset 0, terms: the float64 rest from the 256-aligned end of the rows — the
+    per-waypoint terms, then in 'segments' mode the per-segment parts): a caller that fills them sets CLEARANCE_PREFILLED."""
+    off = (12 * n_rows + 255) // 256 * 256
+    return scratch[:12 * n_rows].view(torch.float32).view(n_rows, 3), scratch[off:].view(torch.float64)
 
 
 def traj_step_stats(cloud, ws):

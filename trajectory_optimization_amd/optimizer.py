@@ -89,6 +89,11 @@ class _OptRun:
             self.clr_scratch = torch.empty(cb, dtype=torch.uint8, device=dev)
             c.clearance_radius, c.clearance_weight = float(m0.clearance_radius), float(m0.clearance_weight)
             c.clearance_scratch, c.clearance_scratch_bytes = self.clr_scratch.data_ptr(), cb
+        self.clr_fill = None
+        if self.clearance and m0._clr_map is not None:   # the map's term: every step fills the scratch first, the library launches no query
+            c.flags |= ops.CLEARANCE_PREFILLED
+            self.clr_fill = (m0._clr_map, self.poses, m0.clearance_radius, m0.clearance_weight, m0.clearance_mode, B,
+                             *ops.clearance_scratch_views(self.clr_scratch, B * W))
         self.c, self.ref, self.fn = c, ctypes.byref(c), L.tohip_traj_opt_step
 
     def run(self, n):
@@ -101,6 +106,8 @@ class _OptRun:
 
     def _steps(self, n, stream):
         for i in range(n):
+            if self.clr_fill is not None:
+                ops.clearance_rows(*self.clr_fill)
             rc = self.fn(self.ref, i, stream)
             if rc:
                 check(rc, "tohip_traj_opt_step")
@@ -158,7 +165,7 @@ class _TailRun:
     def __init__(self, models, st, n_opt_steps, lr_pose, lr_quat, rewards_th, smoothness_th, vis_wps_dist, betas, adam_eps, what):
         L = _lib.lib()
         m0 = models[0]
-        self.models, self.B, self.dev, self.n, self.cloud = models, len(models), m0.device, int(n_opt_steps), m0._cloud
+        self.models, self.B, self.dev, self.n, self.clr_source = models, len(models), m0.device, int(n_opt_steps), m0._clearance_source
         B, n, dev = self.B, self.n, self.dev
         W = self.W = m0.poses.shape[0]
         step_w = self.step_w = m0._wps_step(vis_wps_dist)
@@ -201,7 +208,7 @@ class _TailRun:
                                                          ptr(self.src[0]), ptr(self.src[1]), stream_ptr()), "tohip_gather_waypoints_multi")
                 vis_step(*self.src, self.stride)
                 if self.clr:
-                    ops.clearance_rows(self.cloud, self.poses, m0.clearance_radius, m0.clearance_weight, m0.clearance_mode, self.B,
+                    ops.clearance_rows(self.clr_source, self.poses, m0.clearance_radius, m0.clearance_weight, m0.clearance_mode, self.B,
                                        self.clr_rows, self.clr_terms)
                 check(tail(i), what)
 
@@ -275,6 +282,9 @@ def _check_same_setup(models, vis_wps_dist, what):
                 (m0._clearance_on and (m.clearance_radius != m0.clearance_radius or m.clearance_weight != m0.clearance_weight or
                                        m.clearance_mode != m0.clearance_mode))):
             raise ValueError(f"{what}: the models must share the camera, rig, mode, weights and clearance settings")
+        if m0._clearance_on and ((m._clr_map is None) != (m0._clr_map is None) or (m0._clr_map is not None and not m0._clr_map.same_as(m._clr_map))):
+            raise ValueError(f"{what}: the models must share the clearance settings: one clearance_map (the same map objects) and the "
+                             "same clearance_unknown")
         if m is not m0 and (m.device != m0.device or float(m.eps) != float(m0.eps)):
             raise ValueError(f"{what}: the models must live on one device and share eps")
         if m is not m0 and rig is not None and (m._rig.n_cams != rig.n_cams or not torch.equal(m._rig.q, rig.q) or not torch.equal(m._rig.t, rig.t)):

@@ -177,21 +177,28 @@ def xy_yaw_gradient(poses_grad, quats, quats_grad):
     return torch.cat([gp[..., :2], (gq * dq).sum(-1, keepdim=True)], dim=-1)
 
 
-def trajectory_clearance(points_or_packed_cloud, poses, radius, segments=False):
+def trajectory_clearance(points_or_packed_cloud, poses, radius, segments=False, unknown='free'):
     """How far each waypoint is from the cloud: (d, idx) on the device — d (W,) f32 the distance to the nearest point within
     `radius` (+inf when none), idx (W,) int32 that point's row in the caller's order (-1 when none; ties go to the lowest row).
     segments=True: how far each of the W - 1 straight segments between consecutive waypoints is from it: (d, idx, s), s (W-1,) f32
     where along the segment its closest point lies (0 = the segment's first waypoint, 1 = its second).
     The queries behind ModelTraj's clearance term (clearance_kernels.hip); `points_or_packed_cloud`: (N,3) points on the device, an
-    ops.PackedCloud (sorted or not) or a ModelTraj (its cloud)."""
+    ops.PackedCloud (sorted or not) or a ModelTraj (its cloud) — or a MAP, an ops.OccupancyGrid, SpaceMap or EvidenceMap: how far each
+    waypoint (segment) is from the centre of the nearest occupied voxel — with unknown='obstacle' (not a bare grid) of the nearest
+    occupied or never-seen one — and idx that voxel's linear index (z ny + y) nx + x (clearance_map_kernels.hip)."""
     cloud = points_or_packed_cloud
-    if hasattr(cloud, "_cloud") and isinstance(cloud._cloud, ops.PackedCloud):
-        cloud = cloud._cloud
-    if not isinstance(cloud, ops.PackedCloud):
-        cloud = ops.PackedCloud(torch.as_tensor(cloud, dtype=torch.float32))
+    if isinstance(cloud, (ops.OccupancyGrid, ops.SpaceMap, ops.EvidenceMap)):
+        cloud = ops.MapObstacles(cloud, unknown)
+        device = cloud.occupied.device
+    else:
+        if hasattr(cloud, "_cloud") and isinstance(cloud._cloud, ops.PackedCloud):
+            cloud = cloud._cloud
+        if not isinstance(cloud, ops.PackedCloud):
+            cloud = ops.PackedCloud(torch.as_tensor(cloud, dtype=torch.float32))
+        device = cloud.device
     poses = torch.as_tensor(poses, dtype=torch.float32)
-    if poses.device != cloud.device:
-        poses = poses.to(cloud.device)
+    if poses.device != device:
+        poses = poses.to(device)
     return ops.clearance_segments(cloud, poses, radius) if segments else ops.clearance(cloud, poses, radius)
 
 
