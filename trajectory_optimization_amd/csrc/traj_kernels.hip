@@ -48,6 +48,7 @@
 // The forward leaves its state (records, extrema, flags) in the workspace; the backward reads it there: the workspace
 // must not be touched between tohip_traj_forward and tohip_traj_backward of the same step.
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <type_traits>
 
@@ -497,13 +498,19 @@ __device__ __forceinline__ void mark_candidate(unsigned long long* __restrict__ 
 }
 
 // DENSE: persistent blocks, as many as the chip holds at once (host: occupancy x CUs).  A lane owns EIGHT consecutive points
-// (four independent packed evaluation chains per waypoint: a SIMD holds only ~5 of these waves, which issue in age order, so the
+// (four independent packed evaluation chains per waypoint: a SIMD holds only ~6 of these waves, which issue in age order, so the
 // instruction-level parallelism has to come from inside the wave), a wave two 256-point slots, a block 2048 points.  The
 // (point block, waypoint) pairs are one flat range cut into gridDim.x equal pieces: a block's piece is a run of consecutive
 // waypoints of one point block (seldom two), so every block does the same number of evaluations to within one waypoint, loads
 // its points once (twice), and all blocks end together: no dispatch order, no tail.  A lane's (min, max) stores of consecutive
 // waypoints are adjacent in `part`.
 #define TO_PD 8
+// Upper bounds on the SGPR count of the plain and of the occlusion build: the host's residency rule needs the count
+// (dense_per_cu) and the runtime cannot tell it.  Up to 96 the scalar register file admits seven blocks per CU, up to 112 six.
+// tests/test_dense_resources_cpu.py compiles the file and holds both builds to these bounds.  Compiling the kernel for seven
+// waves per SIMD (71 VGPRs, 94 SGPRs, the same loop) or for six was measured and bought nothing: DESIGN.md §4.
+#define TO_DENSE_SGPRS 112
+#define TO_DENSE_OCC_SGPRS 112
 template <bool OCC>
 __global__ void __launch_bounds__(TO_BLOCK)
 k_traj_pass1_dense(CloudView cv, const WayRec* __restrict__ rec, int V, int nblk, EvalK k, float2* __restrict__ part,
@@ -522,8 +529,10 @@ k_traj_pass1_dense(CloudView cv, const WayRec* __restrict__ rec, int V, int nblk
     const int64_t u_end = total * (blockIdx.x + 1) / gridDim.x;
     // The SIMD arbiter serves its waves oldest first, so equal pieces do not end together: the old waves race ahead, retire, and
     // the last wave of a SIMD finishes alone at ~70 % of the issue rate.  Priority outranks age: a wave steps its priority down
-    // as it completes quarters of its piece, so whoever is behind is served first and all waves stay within a quarter of each other.
-    const int64_t q1 = u + (u_end - u) / 4, q2 = u + (u_end - u) / 2, q3 = u + 3 * (u_end - u) / 4;
+    // at 3/4, 7/8 and 15/16 of its piece, so whoever is behind is served first.  Who is ahead matters only at the end — while all
+    // waves are resident the SIMD issues at the same rate whichever it serves — and there the waves are within a sixteenth of a
+    // piece of each other (stamps: the blocks of an XCD end within 7 us instead of the 19 us of steps at the quarters).
+    const int64_t len = u_end - u, q1 = u + 3 * len / 4, q2 = u + 7 * len / 8, q3 = u + 15 * len / 16;
     __builtin_amdgcn_s_setprio(3);
     while (u < u_end) {
         const int pb = (int)(u / V);
@@ -2040,25 +2049,37 @@ inline TrajPlan make_plan(int64_t n, int64_t V, int64_t W, int64_t n_traj = 1) {
     return p;
 }
 
+// 256-thread blocks of the dense pass 1 a CU admits:the occupancy API's answer, at most 8, and at most what the scalar register file holds — the API
+// does not count that one and answers a block too many from 82 SGPRs on (MI355X_MICROARCH.md "Residency").  `sgprs` is the
+// build's declared bound (TO_DENSE_SGPRS / TO_DENSE_OCC_SGPRS): the runtime does not know the count.  The rule must never
+// over-count: a block that is not resident from the start would run alone at the end.
+inline int dense_per_cu(int api, int sgprs) {
+    const int by_sgpr = 800 / ((sgprs + 15) / 16 * 16 + 16);
+    const int k = std::min(std::min(api, 8), by_sgpr);
+    return k < 1 ? 1 : k;
+}
 // dense pass 1: as many persistent blocks as are resident at once (never more than one per (point block, waypoint) pair)
 inline int dense_blocks(int nblk, int V, bool occ) {
-    static int per_cu[2] = {0, 0}, cus = 0;
-    if (cus == 0) {
-        int dev = 0;
+    // CU count and occupancy belong to a device: one packed entry per device (cus << 8 | plain per CU << 4 | occlusion per CU),
+    // 0 = not asked yet; a device beyond the table is asked every time
+    constexpr int kDev = 64;
+    static std::atomic<int> cache[kDev];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
+    int e = (dev >= 0 && dev < kDev) ? cache[dev].load(std::memory_order_relaxed) : 0;
+    if (e == 0) {
+        int cus = 0;
         hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
+        if (dev >= 0 && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
         if (cus <= 0) cus = 256;
         int a = 0, b = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_traj_pass1_dense<false>, TO_BLOCK, 0) != hipSuccess || a <= 0) a = 4;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_traj_pass1_dense<true>, TO_BLOCK, 0) != hipSuccess || b <= 0) b = 4;
-        // the API answers one block per CU too many at this kernel's SGPR count (82-96; measured: 6 resident where it says 7,
-        // MI355X_MICROARCH.md "Residency"); a block that is not resident from the start would run alone at the end
-        per_cu[0] = (a > 8 ? 8 : a) - 1;
-        per_cu[1] = (b > 8 ? 8 : b) - 1;
-        if (per_cu[0] < 1) per_cu[0] = 1;
-        if (per_cu[1] < 1) per_cu[1] = 1;
+        e = cus << 8 | dense_per_cu(a, TO_DENSE_SGPRS) << 4 | dense_per_cu(b, TO_DENSE_OCC_SGPRS);
+        if (dev >= 0 && dev < kDev) cache[dev].store(e, std::memory_order_relaxed);
     }
-    int64_t nb = (int64_t)per_cu[occ ? 1 : 0] * cus;
+    const int cus = e >> 8, per_cu = occ ? (e & 15) : (e >> 4 & 15);
+    int64_t nb = (int64_t)per_cu * cus;
     const int64_t total = (int64_t)nblk * V;
     if (nb > total) nb = total;
     return (int)nb;
