@@ -202,11 +202,16 @@ def spherical_flip(points, param=2):
     return out, rad.value
 
 
-def occlusion_masks(points, poses, quats, K, img_w, img_h, min_dist=1.0, max_dist=15.0, param=2):
+def occlusion_masks(points, poses, quats, K, img_w, img_h, min_dist=1.0, max_dist=15.0, param=2, method="hpr"):
     """Per-waypoint occlusion masks (W,N) f32 by the reference's hard per-camera pipeline
     (/root/reference/src/pc_processor.py:158-187): to_camera_frame (normalised quaternion, model.py:50-57) ->
     get_cam_frustum_pts -> hidden_pts_removal of the kept points seen from the camera centre.  A point inside the
-    hard frustum that HPR hides gets 0; everything else 1 (the soft weights of the model already fade it out)."""
+    hard frustum that HPR hides gets 0; everything else 1 (the soft weights of the model already fade it out).
+    method="zbuffer": the same cull, then render_oracle.render_points of the kept camera-frame points (radius 0.03, znear = min_dist,
+    zfar = max_dist, the image of img_h x img_w pixels): a kept point that owns no pixel gets 0.  A pose with fewer than 4 kept
+    points keeps its ones under either method (include/trajopt_hip.h: min_points)."""
+    if method not in ("hpr", "zbuffer"):
+        raise ValueError(f"method must be 'hpr' or 'zbuffer', got {method!r}")
     pts = _f32(points)
     W, N = len(poses), pts.shape[0]
     occ = np.ones((W, N), np.float32)
@@ -215,7 +220,12 @@ def occlusion_masks(points, poses, quats, K, img_w, img_h, min_dist=1.0, max_dis
         d, f = frustum_masks(np.ascontiguousarray(cam.T), K, img_w, img_h, min_dist, max_dist)
         kept = np.flatnonzero(d & f)
         if len(kept) >= 4:
-            vis, _ = hidden_pts_removal(cam[kept], param)
+            if method == "zbuffer":
+                from oracle import render_oracle
+                _, owner = render_oracle.render_points(cam[kept], K, int(img_h), int(img_w), znear=min_dist, zfar=max_dist)
+                vis = np.unique(owner[owner >= 0])
+            else:
+                vis, _ = hidden_pts_removal(cam[kept], param)
             hidden = np.ones(len(kept), bool)
             hidden[vis] = False
             occ[w, kept[hidden]] = 0.0

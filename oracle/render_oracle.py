@@ -10,11 +10,17 @@ def render_points(verts, K, height, width, radius=0.03, znear=1.0, zfar=10.0, ba
     H, W = int(height), int(width)
     zbuf = np.full((H, W), np.inf, np.float32)
     owner = np.full((H, W), -1, np.int64)
-    for i, (X, Y, Z) in enumerate(v):
-        if not (Z >= znear and Z <= zfar):
-            continue
-        u, w_ = fx * X / Z + cx, fy * Y / Z + cy
+    # the rows inside the depth range with finite X and Y, in index order: a row outside it (a NaN depth included) splats nothing, and
+    # neither does one whose projection is not finite (the kernels' `u + rho >= 0 && u - rho <= width` is false for it)
+    with np.errstate(invalid="ignore"):
+        live = (v[:, 2] >= np.float32(znear)) & (v[:, 2] <= np.float32(zfar)) & np.isfinite(v[:, 0]) & np.isfinite(v[:, 1])
+    for i in np.flatnonzero(live):
+        X, Y, Z = v[i]
+        with np.errstate(over="ignore"):
+            u, w_ = fx * X / Z + cx, fy * Y / Z + cy
         rho = fx * np.float32(radius) / Z
+        if not (np.isfinite(u) and np.isfinite(w_)):   # (fx X overflowed)
+            continue
         j0, j1 = max(0, int(np.floor(u - rho - np.float32(0.5)))), min(W - 1, int(np.ceil(u + rho - np.float32(0.5))))
         i0, i1 = max(0, int(np.floor(w_ - rho - np.float32(0.5)))), min(H - 1, int(np.ceil(w_ + rho - np.float32(0.5))))
         if j1 < j0 or i1 < i0:
@@ -27,10 +33,11 @@ def render_points(verts, K, height, width, radius=0.03, znear=1.0, zfar=10.0, ba
         win = inside & ((Z < zb) | ((Z == zb) & (i < ow)))
         zb[win] = Z
         ow[win] = i
-    lo, hi = v.min(), v.max()
     img = np.full((H, W, 3), background, np.float32)
     hit = owner >= 0
-    img[hit] = (v[owner[hit]] - lo) / (hi - lo)
+    if hit.any():   # (an empty cloud has no minimum)
+        lo, hi = v.min(), v.max()
+        img[hit] = (v[owner[hit]] - lo) / (hi - lo)
     return img, owner
 
 

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from conftest import rel_inf
+from hard_size_cases import occ_row_ref as _occ_row_ref   # (the header's statement of a bit row, shared with tests/test_hip_hard_at_size.py)
 from trajectory_optimization_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -186,16 +187,6 @@ def test_inverse_permutation(dev, sort):
 
 
 # ---- 3. one waypoint's occlusion bit row -------------------------------------------------------------------------------------
-
-def _occ_row_ref(n, npad, inv, kept, vis_pos):
-    """The header's statement: all ones; clear each kept point's bit; set the visible kept points' bits again; pads := bit n-1."""
-    b = np.ones(npad, np.uint32)
-    b[inv[kept]] = 0
-    b[inv[kept[vis_pos]]] = 1
-    b[n:] = b[n - 1]
-    words = (b.reshape(-1, 32) << np.arange(32, dtype=np.uint32)).sum(axis=1, dtype=np.uint64).astype(np.uint32)
-    return words.view(np.int32)
-
 
 @pytest.mark.parametrize("sort", [True, False])
 def test_occlusion_row(dev, sort):

@@ -268,8 +268,9 @@ def test_device_early_stop_rule(dev):
 @pytest.mark.parametrize("method", ["hpr", "zbuffer"])
 def test_occlusion_aware_traj_model(dev, method):
     """ModelTraj(occlusion=...) multiplies each waypoint's p by a per-waypoint occlusion mask built by
-    the hard pipeline of pc_processor.py (frustum cull -> HPR from the camera centre).  'hpr': masks, rewards and
-    gradients vs the oracle running the same pipeline on the host; 'zbuffer': consistency with its own mask."""
+    the hard pipeline of pc_processor.py (frustum cull -> HPR from the camera centre, or the z-buffer splat).  Either method: masks,
+    rewards and gradients vs the oracle running the same pipeline on the host (oracle.occlusion_masks; 'zbuffer' through the numpy
+    restatement of the splat, oracle/render_oracle.py)."""
     from oracle import oracle
     from trajectory_optimization_amd.model import ModelTraj
     from trajectory_optimization_amd import ops
@@ -285,10 +286,9 @@ def test_occlusion_aware_traj_model(dev, method):
     bits = ((rows.view(np.uint32)[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1).reshape(rows.shape[0], -1)[:, :m._cloud.n]
     occ = np.zeros((rows.shape[0], m._cloud.n), np.float32)
     occ[:, perm] = bits
-    if method == "hpr":
-        ref_occ = oracle.occlusion_masks(pts, poses, quats, K, IW, IH, 1.0, 15.0)
-        assert np.array_equal(occ, ref_occ)            # bit-exact hidden sets per waypoint
-        assert 0 < (ref_occ == 0).sum() < ref_occ.size
+    ref_occ = oracle.occlusion_masks(pts, poses, quats, K, IW, IH, 1.0, 15.0, method=method)
+    assert np.array_equal(occ, ref_occ)            # bit-exact hidden sets per waypoint
+    assert 0 < (ref_occ == 0).sum() < ref_occ.size
     f = oracle.traj_forward(pts, poses, quats, K, IW, IH, prec="f64", occ=occ)
     pg, qg = oracle.traj_backward(pts, poses, quats, K, IW, IH, f, prec="f64")
     np.testing.assert_allclose(m.rewards.detach().cpu().numpy(), f["rewards"], rtol=2e-5, atol=2e-6)
