@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_clearance_map / tohip_clearance_map_segments and the flag bit TOHIP_TRAJ_CLEARANCE_PREFILLED (the clearance term
+/* (still 15) + tohip_occ_unknown / tohip_view_volume / tohip_view_volume_pick (the unknown volume a view would reveal, and the greedy
+ * choice of views by it): new symbols only.
+ * (still 15) + tohip_clearance_map / tohip_clearance_map_segments and the flag bit TOHIP_TRAJ_CLEARANCE_PREFILLED (the clearance term
  * asked of the map: the obstacles are an occupancy grid's voxels): new symbols and one flag bit that was refused before — no struct
  * and no existing signature changes.
  * (still 15) + tohip_evid_bytes / tohip_evid_init / tohip_evid_fold / tohip_evid_positions (a hit/miss evidence map: integer log-odds
@@ -1268,6 +1270,49 @@ int tohip_clearance_map(const void *occupied, const void *free_or_null, size_t g
 int tohip_clearance_map_segments(const void *occupied, const void *free_or_null, size_t grid_bytes, const tohip_occ_geom *geom,
                                  const float *poses, int64_t n_wps, int64_t n_traj, float radius, float weight, float *d, int32_t *idx,
                                  float *s, float *value, float *grad, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- the unknown volume a view would reveal (volume_kernels.hip, DESIGN.md §10, "Unknown volume") -------
+ * How much unknown space would a camera see from here?  occupied and free_grid are the two planes of a map (one geometry, grid_bytes
+ * each); claimed and mark, where given, are two more grids of that geometry.
+ *
+ * tohip_occ_unknown: out (a third buffer, not one of the two) receives the mask of the voxels inside dims of state 0 (neither bit);
+ * its header and pad bits 0.  tohip_occ_count / tohip_occ_export list it.
+ *
+ * tohip_view_volume: view w is the pose poses + 3 w, quats + 4 w (wxyz, normalised as tohip_los_rows does, normalize = 1).  A voxel v
+ * inside dims is REVEALED by view w iff (1) its state is 0 and, where claimed is given, its bit there is 0; (2) its centre c =
+ * fl(origin + fl(fl(i + 0.5) r)) per axis — tohip_occ_export's bits — is kept by tohip_cull_waypoints(normalize = 1) with this camera
+ * and these limits (the same device functions: the same bit); (3) tohip_los_segments(occupied, poses[w] -> c, start_skip 1, end_skip 0)
+ * gives 1: only occupied voxels block, the camera's own voxel and v itself are not tested, unknown voxels on the way do not block, and
+ * a view whose position is out of range reveals nothing.  gains[w] (DEVICE int64 x n_views, overwritten) = the number of revealed
+ * voxels: an exact integer, the same in every run.  mark (may be NULL): the revealed voxels of every view scored get their bit there
+ * (32-bit integer atomic OR, issued only where a brick's word lacks one of the gathered bits); bits are only ever set.  mark ==
+ * claimed (claim what is counted, in one launch) is allowed only where the call scores ONE view — each word is then read and written by
+ * one lane — and is TOHIP_EINVAL otherwise.  1 <= n_views <= 65535.
+ * view_index (DEVICE int32, may be NULL): the call scores the one view whose number is stored there when the kernel runs — a number
+ * another kernel wrote, tohip_view_volume_pick's order + j — out of the n_views rows: gains[*view_index] receives its count, every
+ * other entry 0; a number outside [0, n_views) scores nothing.
+ * window != 0: per view only the bricks of a box are enumerated that holds every voxel the cull can keep — the camera and the far
+ * ends of the four corner rays of the pixel rectangle widened by a pixel, padded by two voxels, clipped to dims, computed on the
+ * device — and inside it a brick whose bounding sphere cannot pass the depth gate is not tested.  The window never changes a count
+ * or a bit; 0 enumerates every brick.  (It needs K = (fx s cx; 0 fy cy; 0 0 1) with fx, fy > 0: with any other K every brick is
+ * enumerated.)
+ * stop (DEVICE int32, may be NULL): the launch does nothing — gains all 0, mark untouched — where the word is not 0 when it runs.
+ * stats (DEVICE uint64 x 3, may be NULL, zero-filled by the caller): += centres tested, += rays walked, += voxels visited.
+ *
+ * tohip_view_volume_pick: round `round` (>= 0) of a greedy selection over gains (n_views int64).  Among the candidates c with
+ * taken[c] == 0 (DEVICE int32 x n_views) the largest gain wins, ties to the lowest index.  Where that gain is >= min_gain (>= 1):
+ * order[round] = c (int32), picked_gain[round] = the gain (int64), taken[c] = 1.  Otherwise — also where no candidate is left —
+ * *stop = 1 and nothing else is written.  Where *stop is not 0 when the launch runs it does nothing.  So k rounds of (tohip_view_volume
+ * with claimed = R, tohip_view_volume_pick, tohip_view_volume with claimed = mark = R and view_index = order + round), all with one
+ * stop word, choose up to k views greedily with nothing read back; the caller pre-fills order with -1.
+ * Every argument check returns before anything is enqueued; nothing synchronises with the host. */
+int tohip_occ_unknown(const void *occupied, const void *free_grid, void *out, size_t grid_bytes, const tohip_occ_geom *geom, void *stream);
+int tohip_view_volume(const void *occupied, const void *free_grid, const void *claimed, void *mark, size_t grid_bytes,
+                      const tohip_occ_geom *geom, const float *poses, const float *quats, int64_t n_views, const int32_t *view_index,
+                      const tohip_camera *cam, float min_dist, float max_dist, int32_t window, int64_t *gains, const int32_t *stop,
+                      uint64_t *stats, void *stream);
+int tohip_view_volume_pick(const int64_t *gains, int32_t *taken, int64_t n_views, int64_t min_gain, int32_t round, int32_t *order,
+                           int64_t *picked_gain, int32_t *stop, void *stream);
 
 /* ---- optional per-kernel timing (bench.py's roofline leg) -----------------------------------------
  * When enabled, every launch of the big kernels is bracketed by hipEventRecord on its own stream.

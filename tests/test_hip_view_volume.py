@@ -1,0 +1,393 @@
+"""The unknown volume a view reveals and the greedy selection by it, on the GPU.  Every comparison is exact (torch.equal or integer
+equality).  The oracle of a view is the composition of calls that are pinned elsewhere: space.unknown().export() gives the centres,
+ops.cull_waypoints(normalize=True) the kept rows, tools.line_of_sight(space.occupied, t, centre, skip=(1, 0)) == 1 is counted."""
+import ctypes
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from trajectory_optimization_amd import synth
+
+pytestmark = pytest.mark.gpu
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+K, IW, IH = synth.K_INTRINS, synth.IMG_WIDTH, synth.IMG_HEIGHT
+ORIGIN, RES = (0.0, 0.0, 0.0), 0.125
+GRIDS = [(1, 1, 1), (5, 6, 3), (37, 5, 20), (64, 64, 32)]   # (37, 5, 20): no multiple of the 4 x 4 x 2 brick on any axis
+PLANES = ["random", "untouched", "full"]
+WHOLE, SHELL, USUAL = (0.01, 50.0), (2.0, 2.2), (0.5, 5.0)   # limits: the whole grid (the window is clipped on every side), a thin depth shell
+SCENE = dict(origin=(-0.5, -0.5, -0.5), resolution=0.125, dims=(28, 24, 16))
+SCANNER = np.float32([1.03, 0.97, 0.52])
+CAMERA = dict(intrins=torch.from_numpy(K), img_width=IW, img_height=IH)
+Q_PLUS_X = synth.Q_OPTICAL.astype(np.float32)                                              # the camera looks along +x
+Q_MINUS_X = synth.quat_mul(np.array([0.0, 0.0, 0.0, 1.0]), synth.Q_OPTICAL).astype(np.float32)   # ... along -x
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available()
+    return torch.device("cuda:0")
+
+
+def _t(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def _grid_of(bits, origin, r, dev):
+    """An OccupancyGrid holding exactly the voxels of `bits` (their centres inserted)."""
+    from trajectory_optimization_amd import ops
+    g = ops.OccupancyGrid(origin, r, bits.shape, device=dev)
+    _, centres = synth.occ_export_ref(bits, origin, r)
+    if len(centres):
+        assert g.insert(_t(centres, dev)) == 0
+    return g
+
+
+def _planes(kind, dims, seed=0):
+    """(occ, free) bool arrays: random at 10 % occupied / 30 % free, an untouched map, or a full occupied plane."""
+    rng = np.random.default_rng(seed + dims[0])
+    if kind == "random":
+        return rng.random(dims) < 0.10, rng.random(dims) < 0.30
+    return np.full(dims, kind == "full"), np.zeros(dims, bool)
+
+
+def _space(kind, dims, dev, origin=ORIGIN, seed=0):
+    from trajectory_optimization_amd import ops
+    occ, free = _planes(kind, dims, seed)
+    return ops.SpaceMap(_grid_of(occ, origin, RES, dev), _grid_of(free, origin, RES, dev)), occ, free
+
+
+def _views(dims, M, seed=1):
+    """M views of a grid at ORIGIN / RES: [0] from the apron in front of the face x = 0 looking along +x at the grid's middle, [1] a
+    position exactly on voxel faces inside dims, [2] out of range, [3] 24 voxels out in the apron looking in, the rest uniform over
+    the box and a rim around it with random orientations whose quaternions are not unit."""
+    rng = np.random.default_rng(seed + 7 * dims[1])
+    ext = np.asarray(dims, dtype=np.float64) * RES
+    P = rng.random((max(M, 4), 3)) * ext * 1.6 - 0.3 * ext
+    Q = rng.standard_normal((max(M, 4), 4)) * (0.5 + rng.random((max(M, 4), 1)))
+    P[0], Q[0] = [-0.5, ext[1] / 2, ext[2] / 2], synth.Q_OPTICAL
+    P[1] = np.minimum(np.floor(np.asarray(dims) / 2), np.asarray(dims) - 1) * RES
+    P[2] = [600.0, 0.1, 0.1]
+    P[3], Q[3] = [-3.0, ext[1] / 2, ext[2] / 2], synth.Q_OPTICAL
+    return P[:M].astype(np.float32), Q[:M].astype(np.float32)
+
+
+def _cam(limits):
+    from trajectory_optimization_amd import ops
+    return ops.Camera(K, IW, IH, *limits)
+
+
+def _oracle(space, P, Q, limits, dev):
+    """The composition -> (revealed masks (M, nx,ny,nz) bool on the device, kept counts list, unknown count)."""
+    from trajectory_optimization_amd import ops, tools
+    ijk, centres = space.unknown().export()
+    M = len(P)
+    masks = torch.zeros((M,) + tuple(space.occupied.dims), dtype=torch.bool, device=dev)
+    if not len(ijk):
+        return masks, [0] * M, 0
+    p, q = _t(P, dev), _t(Q, dev)
+    kept_idx, _, counts, _ = ops.cull_waypoints(centres, p, q, _cam(limits), limits[0], limits[1], normalize=True)
+    for w in range(M):
+        rows = kept_idx[w, :counts[w]].long()
+        c = centres[rows]
+        see = tools.line_of_sight(space.occupied, p[w].expand_as(c).contiguous(), c, skip=(1, 0)) == 1
+        v = ijk[rows][see].long()
+        masks[w, v[:, 0], v[:, 1], v[:, 2]] = True
+    return masks, counts, len(ijk)
+
+
+def _count(masks):
+    return masks.reshape(len(masks), -1).sum(dim=1)
+
+
+# --------------------------------------------------------------------------------------------------------- the unknown plane
+
+@pytest.mark.parametrize("dims", GRIDS, ids=str)
+def test_unknown_equals_the_restatement_and_pads_are_zero(dev, dims):
+    space, occ, free = _space("random", dims, dev)
+    u = space.unknown()
+    want = synth.unknown_ref(occ, free)
+    assert torch.equal(u.dense().cpu(), torch.from_numpy(want)) and u.count() == int(want.sum())
+    ijk, centres = u.export()
+    ref_ijk, ref_c = synth.occ_export_ref(want, ORIGIN, RES)
+    assert torch.equal(ijk.cpu(), torch.from_numpy(ref_ijk)) and torch.equal(centres.cpu(), torch.from_numpy(ref_c))
+    # pad bits: every set bit of the buffer is one of the listed voxels
+    words = u.buf[256:].view(torch.int32)
+    pop = sum(int(((words >> b) & 1).sum()) for b in range(32))
+    assert pop == int(want.sum()) and not bool(u.buf[:256].any())
+
+
+# --------------------------------------------------------------------------------------------------------- gains against the composition
+
+@pytest.mark.parametrize("M", [1, 3, 70])
+@pytest.mark.parametrize("kind", PLANES)
+@pytest.mark.parametrize("dims", GRIDS, ids=str)
+def test_gains_equal_the_composition(dev, dims, kind, M):
+    from trajectory_optimization_amd import ops
+    space, occ, free = _space(kind, dims, dev)
+    P, Q = _views(dims, M)
+    p, q = _t(P, dev), _t(Q, dev)
+    before = space.occupied.buf.clone(), space.free.buf.clone()
+    in_range = synth.occ_fixed(P, ORIGIN, RES)[1]
+    rng = np.random.default_rng(5)
+    claimed_bits = rng.random(dims) < 0.5
+    claimed = _grid_of(claimed_bits, ORIGIN, RES, dev)
+    for limits in ((WHOLE, SHELL, USUAL) if M <= 3 else (USUAL,)):
+        masks, kept, n_unknown = _oracle(space, P, Q, limits, dev)
+        want = _count(masks)
+        cam = _cam(limits)
+        stats = torch.zeros(3, dtype=torch.int64, device=dev)
+        mark = space.free.empty_like()
+        got = ops.view_volume(space, p, q, cam, *limits, mark=mark, stats=stats)
+        print(dims, kind, M, limits, "gains", got.tolist()[:8], "kept", kept[:8], "stats", stats.tolist())
+        assert got.dtype == torch.int64 and torch.equal(got, want), (limits, got.tolist(), want.tolist())
+        assert torch.equal(mark.dense(), masks.any(dim=0))                   # the mark plane: the union of the views' masks
+        assert mark.count() == int(masks.any(dim=0).sum())                   # (and no pad bit)
+        assert int(stats[1]) == sum(k for k, ok in zip(kept, in_range) if ok)   # rays walked = the oracle's kept rows
+        if M >= 3:
+            assert int(got[2]) == 0 and not in_range[2]                       # a camera out of range reveals nothing
+        if kind == "untouched":   # nothing blocks: every kept centre is revealed (fully unknown, fully kept bricks fill the queue)
+            assert got.tolist() == [k if ok else 0 for k, ok in zip(kept, in_range)]
+        if kind == "full":
+            assert n_unknown == 0 and not bool(got.any()) and stats.tolist() == [0, 0, 0]
+        # window off: every brick enumerated, every unknown centre tested — identical gains, identical mark planes
+        stats_all = torch.zeros(3, dtype=torch.int64, device=dev)
+        mark_all = space.free.empty_like()
+        got_all = ops.view_volume(space, p, q, cam, *limits, mark=mark_all, window=False, stats=stats_all)
+        assert torch.equal(got_all, got) and torch.equal(mark_all.buf, mark.buf)
+        assert stats_all.tolist()[0] == n_unknown * int(in_range.sum()) and stats_all.tolist()[1:] == stats.tolist()[1:]
+        assert int(stats[0]) <= int(stats_all[0])
+        # the same call twice: the same tensors
+        again = ops.view_volume(space, p, q, cam, *limits, mark=mark)
+        assert torch.equal(again, got) and torch.equal(mark.buf, mark_all.buf)
+        # a claimed plane: each gain drops by exactly the claimed revealed voxels
+        cl = torch.from_numpy(claimed_bits).to(dev)
+        got_cl = ops.view_volume(space, p, q, cam, *limits, claimed=claimed)
+        assert torch.equal(got_cl, _count(masks & ~cl[None])) and torch.equal(got - got_cl, _count(masks & cl[None]))
+    if kind != "full" and dims != (1, 1, 1):
+        assert int(ops.view_volume(space, p, q, _cam(WHOLE), *WHOLE)[0]) > 0   # (the first view does look at the grid)
+    assert torch.equal(space.occupied.buf, before[0]) and torch.equal(space.free.buf, before[1])
+
+
+def test_single_voxel_grid_is_seen_or_not(dev):
+    from trajectory_optimization_amd import ops
+    space, _, _ = _space("untouched", (1, 1, 1), dev)
+    p = _t(np.float32([[-0.5, 0.0625, 0.0625], [-0.5, 0.0625, 0.0625]]), dev)
+    q = _t(np.stack([Q_PLUS_X, Q_MINUS_X]), dev)
+    assert ops.view_volume(space, p, q, _cam(WHOLE), *WHOLE).tolist() == [1, 0]
+    assert ops.view_volume(space, p, q, _cam(SHELL), *SHELL).tolist() == [0, 0]   # at depth 0.5625, outside the shell
+
+
+def test_smallest_case_against_the_numpy_restatement(dev):
+    """synth.los_ref's walk (through view_volume_ref) on (5, 6, 3), the cull's verdict taken from cull_waypoints."""
+    from trajectory_optimization_amd import ops
+    dims = (5, 6, 3)
+    space, occ, free = _space("random", dims, dev)
+    P, Q = _views(dims, 12)
+    cam = _cam(WHOLE)
+    got = ops.view_volume(space, _t(P, dev), _t(Q, dev), cam, *WHOLE).tolist()
+    ii = np.stack(np.meshgrid(*[np.arange(d) for d in dims], indexing="ij"), axis=-1).reshape(-1, 3)
+    centres = synth.voxel_centres(dims, ORIGIN, RES).reshape(-1, 3)
+    kept_idx, _, counts, _ = ops.cull_waypoints(_t(centres, dev), _t(P, dev), _t(Q, dev), cam, *WHOLE, normalize=True)
+    for w in range(len(P)):
+        kept = np.zeros(dims, bool)
+        rows = ii[kept_idx[w, :counts[w]].cpu().numpy()]
+        kept[rows[:, 0], rows[:, 1], rows[:, 2]] = True
+        gain, rev = synth.view_volume_ref(kept, P[w], ORIGIN, RES, occ, free)
+        assert got[w] == gain, w
+        one = ops.view_volume(space, _t(P[w:w + 1], dev), _t(Q[w:w + 1], dev), cam, *WHOLE, mark=(m := space.free.empty_like()))
+        assert int(one[0]) == gain and torch.equal(m.dense().cpu(), torch.from_numpy(rev))
+    assert sum(got) > 0
+    # the same walk through los_ref itself, for one view
+    unk = np.argwhere(synth.unknown_ref(occ, free) & kept)
+    c = synth.voxel_centres(dims, ORIGIN, RES)[unk[:, 0], unk[:, 1], unk[:, 2]]
+    assert int((synth.los_ref(np.broadcast_to(P[w], c.shape), c, ORIGIN, RES, occ, (1, 0)) == 1).sum()) == got[w]
+
+
+def test_mark_is_claimed_only_for_one_view(dev):
+    from trajectory_optimization_amd import _lib, ops
+    from trajectory_optimization_amd._lib import ptr
+    dims = (37, 5, 20)
+    space, _, _ = _space("random", dims, dev)
+    P, Q = _views(dims, 3)
+    p, q = _t(P, dev), _t(Q, dev)
+    cam = _cam(WHOLE)
+    plane = space.free.empty_like()
+    with pytest.raises(ValueError, match="mark may be the claimed plane itself only for one view"):
+        ops.view_volume(space, p, q, cam, *WHOLE, claimed=plane, mark=plane)
+    gains = torch.zeros(3, dtype=torch.int64, device=dev)
+    rc = _lib.lib().tohip_view_volume(ptr(space.occupied.buf), ptr(space.free.buf), ptr(plane.buf), ptr(plane.buf), plane.buf.numel(),
+                                      ctypes.byref(space.occupied.geom), ptr(p), ptr(q), 3, None, cam.ref(), 0.01, 50.0, 1, ptr(gains), None, None, None)
+    assert rc == -1 and plane.count() == 0
+    # one view: it claims what it counts, and a second launch finds nothing left
+    first = ops.view_volume(space, p[:1], q[:1], cam, *WHOLE, claimed=plane, mark=plane)
+    assert int(first[0]) > 0 and plane.count() == int(first[0])
+    assert int(ops.view_volume(space, p[:1], q[:1], cam, *WHOLE, claimed=plane, mark=plane)[0]) == 0 and plane.count() == int(first[0])
+
+
+def test_translation_leaves_every_gain_unchanged(dev):
+    """Inputs on the 2^-8 m lattice at r = 2^-3, T = (8192, -8192, 4096): every translated coordinate is representable and every
+    difference keeps its bits, so the gains and the mark planes must be identical; only the window's box differs."""
+    from trajectory_optimization_amd import ops
+    dims, T = (37, 5, 20), np.float64([8192.0, -8192.0, 4096.0])
+    P, Q = _views(dims, 24)
+    P = (np.round(P.astype(np.float64) * 256) / 256)
+    P[2] = [0.25, 0.25, 0.25]   # (the out-of-range view stays out of the translated run's way: in range in both)
+    results = []
+    for shift in (np.zeros(3), T):
+        space, _, _ = _space("random", dims, dev, origin=tuple(shift))
+        mark = space.free.empty_like()
+        g = ops.view_volume(space, _t((P + shift).astype(np.float32), dev), _t(Q, dev), _cam(USUAL), *USUAL, mark=mark)
+        g2 = ops.view_volume(space, _t((P + shift).astype(np.float32), dev), _t(Q, dev), _cam(USUAL), *USUAL, window=False)
+        assert torch.equal(g, g2)
+        results.append((g, mark.buf[256:].clone()))
+    assert ((P + T).astype(np.float32).astype(np.float64) == P + T).all()
+    assert torch.equal(results[0][0], results[1][0]) and torch.equal(results[0][1], results[1][1])
+    assert int(results[0][0].sum()) > 0
+
+
+# --------------------------------------------------------------------------------------------------------- the room
+
+@pytest.fixture(scope="module")
+def rooms(dev):
+    """The exploration sample's grid and scanner: the closed room and the doorway room, each one scan."""
+    from trajectory_optimization_amd.tools import occupancy_grid, space_map
+    out = {}
+    for doorway in (False, True):
+        space = space_map(occupancy_grid(origin=SCENE["origin"], dims=SCENE["dims"], resolution=SCENE["resolution"], device=dev))
+        assert space.integrate(_t(SCANNER, dev), _t(synth.box_room(doorway=doorway), dev)) == 0
+        out[doorway] = space
+    return out
+
+
+def test_closed_room_reveals_nothing_from_free_space(dev, rooms):
+    from trajectory_optimization_amd import tools
+    space = rooms[False]
+    assert space.frontier().n == 0 and space.unknown().count() > 0
+    P, Q = synth.candidate_grid(np.linspace(0.2, 1.8, 6), np.linspace(0.2, 1.8, 6), 0.5, 4)
+    free = tools.known_free(space, _t(P, dev))
+    assert int(free.sum()) >= 36
+    for limits in (WHOLE, USUAL):
+        g = tools.view_volume(space, _t(P, dev)[free], _t(Q, dev)[free], min_dist=limits[0], max_dist=limits[1], **CAMERA)
+        assert g.shape == (int(free.sum()),) and not bool(g.any())
+
+
+def test_doorway_room_looking_away_and_at_the_door(dev, rooms):
+    from trajectory_optimization_amd import tools
+    space = rooms[True]
+    p = _t(np.stack([SCANNER, SCANNER]), dev)
+    q = _t(np.stack([Q_MINUS_X, Q_PLUS_X]), dev)
+    for limits in (WHOLE, USUAL):
+        g = tools.view_volume(space, p, q, min_dist=limits[0], max_dist=limits[1], **CAMERA)
+        masks, _, _ = _oracle(space, np.stack([SCANNER, SCANNER]), np.stack([Q_MINUS_X, Q_PLUS_X]), limits, dev)
+        print("doorway", limits, g.tolist())
+        assert int(g[0]) == 0 and int(g[1]) > 0 and torch.equal(g, _count(masks))
+
+
+def test_beams_lower_the_gain_by_the_newly_free_voxels(dev):
+    from trajectory_optimization_amd import tools
+    from trajectory_optimization_amd.tools import occupancy_grid, space_map
+    space = space_map(occupancy_grid(origin=SCENE["origin"], dims=SCENE["dims"], resolution=SCENE["resolution"], device=dev))
+    space.integrate(_t(SCANNER, dev), _t(synth.box_room(doorway=True), dev))
+    p, q = _t(SCANNER[None], dev), _t(Q_PLUS_X[None], dev)
+    before = int(tools.view_volume(space, p, q, min_dist=0.5, max_dist=5.0, **CAMERA)[0])
+    masks, _, _ = _oracle(space, SCANNER[None], Q_PLUS_X[None], USUAL, dev)
+    free0, occ0 = space.free.dense(), space.occupied.dense()
+    space.integrate(_t(SCANNER, dev), _t(synth.doorway_beams(SCANNER), dev), 1.5)
+    assert torch.equal(space.occupied.dense(), occ0)   # a truncated beam is no return
+    newly_free = space.free.dense() & ~free0
+    after = int(tools.view_volume(space, p, q, min_dist=0.5, max_dist=5.0, **CAMERA)[0])
+    lost = int((newly_free & masks[0]).sum())
+    assert lost > 0 and after == before - lost
+
+
+# --------------------------------------------------------------------------------------------------------- selection
+
+def _candidates():
+    return synth.candidate_grid([0.6, 1.0, 1.4], [0.8, 1.0], 0.5, 2)   # M = 12; every second one looks towards the doorway
+
+
+@pytest.fixture(scope="module")
+def candidate_sets(dev, rooms):
+    P, Q = _candidates()
+    masks, _, _ = _oracle(rooms[True], P, Q, USUAL, dev)
+    return P, Q, masks
+
+
+@pytest.mark.parametrize("k", [1, 3, 12])
+def test_selection_equals_the_restatement(dev, rooms, candidate_sets, k):
+    from trajectory_optimization_amd import tools
+    space = rooms[True]
+    P, Q, masks = candidate_sets
+    assert len(P) == 12
+    rng = np.random.default_rng(3)
+    for claimed_bits in (None, rng.random(SCENE["dims"]) < 0.3):
+        claimed = None if claimed_bits is None else _grid_of(claimed_bits, SCENE["origin"], SCENE["resolution"], dev)
+        kept = None if claimed is None else claimed.buf.clone()
+        order, gains, mask = synth.volume_select_ref(masks.cpu().numpy(), k, 1, claimed_bits)
+        sel = tools.select_views_volume(space, _t(P, dev), _t(Q, dev), k, claimed=claimed, min_dist=0.5, max_dist=5.0, **CAMERA)
+        print("selection", k, claimed is not None, sel.order.tolist(), sel.gains.tolist())
+        assert sel.order.dtype == torch.int64 and sel.gains.dtype == torch.int64
+        assert sel.order.tolist() == order and sel.gains.tolist() == gains and sel.n_selected == len(order) >= 1
+        assert torch.equal(sel.revealed.dense().cpu(), torch.from_numpy(mask))
+        n_claimed = 0 if claimed is None else claimed.count()
+        assert sel.total == sum(gains) == sel.revealed.count() - n_claimed
+        assert torch.equal(sel.poses.cpu(), torch.from_numpy(P[order])) and torch.equal(sel.quats.cpu(), torch.from_numpy(Q[order]))
+        if claimed is not None:
+            assert torch.equal(claimed.buf, kept)   # the caller's plane is not modified
+        assert all(g >= 1 for g in gains) and gains == sorted(gains, reverse=True)   # (submodular: marginal gains only fall)
+
+
+def test_selection_ties_duplicates_min_gain_and_a_team(dev, rooms, candidate_sets):
+    from trajectory_optimization_amd import tools
+    space = rooms[True]
+    P, Q, masks = candidate_sets
+    cam = dict(min_dist=0.5, max_dist=5.0, **CAMERA)
+    best = int(torch.argmax(_count(masks)))
+    # the best candidate twice, in front: the lower index wins the tie, and the twin is never chosen with a positive gain
+    P2, Q2 = np.concatenate([P[[best, best]], P]), np.concatenate([Q[[best, best]], Q])
+    sel = tools.select_views_volume(space, _t(P2, dev), _t(Q2, dev), 14, **cam)
+    order = sel.order.tolist()
+    assert order[0] == 0 and 1 not in order and 2 + best not in order and len(set(order)) == len(order)
+    assert int(sel.gains[0]) == int(_count(masks)[best])
+    # min_gain above the best gain: an empty selection and an untouched claimed plane
+    claimed = _grid_of(np.random.default_rng(4).random(SCENE["dims"]) < 0.2, SCENE["origin"], SCENE["resolution"], dev)
+    kept = claimed.buf.clone()
+    none = tools.select_views_volume(space, _t(P, dev), _t(Q, dev), 3, min_gain=int(_count(masks).max()) + 1, claimed=claimed, **cam)
+    assert none.n_selected == 0 and none.order.tolist() == [] and none.gains.tolist() == [] and none.total == 0
+    assert torch.equal(claimed.buf, kept) and torch.equal(none.revealed.buf[256:], kept[256:])
+    # min_gain exactly the best gain: that view and no other
+    one = tools.select_views_volume(space, _t(P, dev), _t(Q, dev), 3, min_gain=int(_count(masks).max()), **cam)
+    assert one.order.tolist() == [best]
+    # a team: the second call is given the first's revealed plane and never re-counts a voxel
+    a = tools.select_views_volume(space, _t(P, dev), _t(Q, dev), 2, **cam)
+    b = tools.select_views_volume(space, _t(P, dev), _t(Q, dev), 2, claimed=a.revealed, **cam)
+    both = tools.select_views_volume(space, _t(P, dev), _t(Q, dev), 4, **cam)
+    assert a.order.tolist() + b.order.tolist() == both.order.tolist() and a.gains.tolist() + b.gains.tolist() == both.gains.tolist()
+    assert b.total == b.revealed.count() - a.revealed.count() and torch.equal(b.revealed.buf, both.revealed.buf)
+    assert not (set(a.order.tolist()) & set(b.order.tolist()))
+
+
+def test_evidence_map_gives_what_its_space_gives(dev):
+    from trajectory_optimization_amd import tools
+    em = tools.evidence_map(tools.occupancy_grid(origin=SCENE["origin"], dims=SCENE["dims"], resolution=SCENE["resolution"], device=dev))
+    em.integrate(_t(SCANNER, dev), _t(synth.box_room(doorway=True), dev))
+    P, Q = _candidates()
+    cam = dict(min_dist=0.5, max_dist=5.0, **CAMERA)
+    g = tools.view_volume(em, _t(P, dev), _t(Q, dev), **cam)
+    masks, _, _ = _oracle(em.space, P, Q, USUAL, dev)
+    assert torch.equal(g, tools.view_volume(em.space, _t(P, dev), _t(Q, dev), **cam)) and torch.equal(g, _count(masks)) and bool(g.any())
+    a = tools.select_views_volume(em, _t(P, dev), _t(Q, dev), 3, **cam)
+    b = tools.select_views_volume(em.space, _t(P, dev), _t(Q, dev), 3, **cam)
+    assert a.order.tolist() == b.order.tolist() and a.gains.tolist() == b.gains.tolist() and torch.equal(a.revealed.buf, b.revealed.buf)
+
+
+def test_the_example_runs(dev, capsys):
+    spec = importlib.util.spec_from_file_location("volume_exploration_sample", os.path.join(REPO, "examples", "volume_exploration_sample.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    out = mod.main(["-k", "3"])
+    assert len(out["order"]) >= 1 and out["total"] == sum(out["gains"]) > 0 and out["total"] <= out["n_unknown"]
+    assert "adds" in capsys.readouterr().out

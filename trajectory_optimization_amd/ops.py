@@ -1032,6 +1032,108 @@ class SpaceMap:
         k = check_min_unknown(min_unknown)
         return _listed_plane(Frontier, self.free, "tohip_occ_frontier", (ptr(self.occupied.buf), ptr(self.free.buf)), (k,))
 
+    def unknown(self):
+        """The unknown voxels — inside dims, neither occupied nor free — as a new OccupancyGrid of this geometry (pad bits 0):
+        unknown().export() lists them and their centres, unknown().count() is the unexplored volume in voxels."""
+        plane = self.free.empty_like()
+        _map_call(self.device, "tohip_occ_unknown", ptr(self.occupied.buf), ptr(self.free.buf), *plane._sizes())
+        return plane
+
+
+VIEW_VOLUME_MAX_VIEWS = 65535   # views per launch (the grid's second dimension); view_volume chunks by it
+
+
+def check_view_volume(space, poses, quats, k=None, min_gain=1, claimed=None, mark=None):
+    """The arguments of view_volume / view_volume_select, by name: space an ops.SpaceMap; poses (M,3) and quats (M,4) floating
+    tensors with the same M >= 1 (with k given: M <= 65 535), finite; k None or an integer >= 1; min_gain an integer >= 1; claimed and mark None or
+    ops.OccupancyGrids of the map's origin, resolution, dims and device, neither of them one of the map's planes; mark may be claimed
+    itself only with M == 1 -> (M, k clipped to M or None, min_gain); ValueError otherwise.  Needs no GPU."""
+    if not isinstance(space, SpaceMap):
+        raise ValueError(f"space must be an ops.SpaceMap (or an ops.EvidenceMap's .space), got {type(space).__name__}")
+    for name, t, w in (("poses", poses, 3), ("quats", quats, 4)):
+        if not torch.is_tensor(t) or not t.is_floating_point():
+            raise ValueError(f"{name} must be a floating-point tensor, got {type(t).__name__}{'' if not torch.is_tensor(t) else ' of ' + str(t.dtype)}")
+        if t.dim() != 2 or t.shape[1] != w or t.shape[0] == 0:
+            raise ValueError(f"{name} must have shape (M,{w}) with M >= 1, got {tuple(t.shape)}")
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError(f"{name} must be finite (NaN or inf found)")
+    M = poses.shape[0]
+    if quats.shape[0] != M:
+        raise ValueError(f"poses holds {M} views, quats {quats.shape[0]}")
+    if k is not None and (not _is_int(k) or k < 1):
+        raise ValueError(f"k must be an integer >= 1, got {k!r}")
+    if k is not None and M > VIEW_VOLUME_MAX_VIEWS:
+        raise ValueError(f"poses holds {M} candidates, a selection (k given) takes at most {VIEW_VOLUME_MAX_VIEWS}")
+    if not _is_int(min_gain) or min_gain < 1:
+        raise ValueError(f"min_gain must be an integer >= 1 (a number of voxels), got {min_gain!r}")
+    for name, g in (("claimed", claimed), ("mark", mark)):
+        if g is None:
+            continue
+        if not isinstance(g, OccupancyGrid):
+            raise ValueError(f"{name} must be an ops.OccupancyGrid or None, got {type(g).__name__}")
+        if g is space.occupied or g is space.free:
+            raise ValueError(f"{name} must not be one of the map's own planes")
+        diff = _grid_difference(space.occupied, g)
+        if diff:
+            raise ValueError(f"{name}: its {diff[0]} differs from the map's ({diff[2]} and {diff[1]})")
+    if mark is not None and mark is claimed and M > 1:
+        raise ValueError(f"mark may be the claimed plane itself only for one view, got {M} views (two views' lanes would race on one word)")
+    return M, (None if k is None else min(int(k), M)), int(min_gain)
+
+
+def _view_rows(space, poses, quats):
+    p = poses.detach().to(device=space.device, dtype=torch.float32).contiguous()
+    q = quats.detach().to(device=space.device, dtype=torch.float32).contiguous()
+    return p, q
+
+
+def _view_volume_call(space, p, q, n, view_index, cam, min_dist, max_dist, claimed, mark, window, gains, stop, stats):
+    _map_call(space.device, "tohip_view_volume", ptr(space.occupied.buf), ptr(space.free.buf), ptr(claimed.buf if claimed is not None else None),
+              ptr(mark.buf if mark is not None else None), space.occupied.buf.numel(), ctypes.byref(space.occupied.geom), ptr(p), ptr(q), n,
+              ptr(view_index), cam.ref(), float(min_dist), float(max_dist), int(bool(window)), ptr(gains), ptr(stop), ptr(stats))
+
+
+def view_volume(space, poses, quats, cam, min_dist, max_dist, claimed=None, mark=None, window=True, stats=None):
+    """The unknown volume each view would reveal (tohip_view_volume, DESIGN.md 10 "Unknown volume"): (M,) int64 on the device, entry
+    w = the number of voxels of `space` in state 0 — and not set in `claimed` — whose centre cull_waypoints keeps for pose w with this
+    camera and these limits and which line_of_sight(space.occupied, poses[w], centre, skip=(1, 0)) sees.  mark: an OccupancyGrid of
+    the map's geometry that receives the revealed voxels of all M views (bits are only set).  window=False enumerates every brick (the
+    same counts).  stats: a zero-filled (3,) int64 device tensor that receives (centres tested, rays walked, voxels visited).  One
+    launch per 65 535 views, nothing read back."""
+    M, _, _ = check_view_volume(space, poses, quats, claimed=claimed, mark=mark)
+    p, q = _view_rows(space, poses, quats)
+    gains = torch.empty(M, dtype=torch.int64, device=space.device)
+    for w0 in range(0, M, VIEW_VOLUME_MAX_VIEWS):
+        w1 = min(M, w0 + VIEW_VOLUME_MAX_VIEWS)
+        _view_volume_call(space, p[w0:w1], q[w0:w1], w1 - w0, None, cam, min_dist, max_dist, claimed, mark, window, gains[w0:w1], None, stats)
+    return gains
+
+
+def view_volume_select(space, poses, quats, cam, min_dist, max_dist, k, min_gain=1, claimed=None, window=True):
+    """Greedy selection by revealed volume, on the device: k rounds of (score every candidate against the plane of what is claimed so
+    far, pick the largest gain — the lowest index on ties, stop where it is below min_gain — and set the winner's revealed voxels in
+    that plane), 3 k launches and nothing read back; at most 65 535 candidates (one launch scores them all).  -> (order (k,) int32,
+    -1 from the round that stopped; gains (k,) int64, the marginal gains; revealed: a new OccupancyGrid, the caller's `claimed` (not
+    modified) plus what the chosen views reveal), all on the device."""
+    M, k, min_gain = check_view_volume(space, poses, quats, k, min_gain, claimed)
+    p, q = _view_rows(space, poses, quats)
+    dev = space.device
+    revealed = space.free.empty_like()
+    if claimed is not None:
+        revealed.buf.copy_(claimed.buf)
+    scores = torch.empty(M, dtype=torch.int64, device=dev)
+    scratch = torch.empty(M, dtype=torch.int64, device=dev)
+    taken = torch.zeros(M, dtype=torch.int32, device=dev)
+    stop = torch.zeros(1, dtype=torch.int32, device=dev)
+    order = torch.full((k,), -1, dtype=torch.int32, device=dev)
+    picked = torch.zeros(k, dtype=torch.int64, device=dev)
+    for j in range(k):
+        _view_volume_call(space, p, q, M, None, cam, min_dist, max_dist, revealed, None, window, scores, stop, None)
+        _map_call(dev, "tohip_view_volume_pick", ptr(scores), ptr(taken), M, min_gain, j, ptr(order), ptr(picked), ptr(stop))
+        # the mark step: the winner's number stays on the device, and one view may claim what it counts
+        _view_volume_call(space, p, q, M, order[j:j + 1], cam, min_dist, max_dist, revealed, revealed, window, scratch, stop, None)
+    return order, picked, revealed
+
 
 FIELD_MAX_D = 254          # the largest truncation distance in voxels: D^2 < 65535, the sentinel
 FIELD_SENTINEL = 65535     # "no obstacle within D voxels"

@@ -803,6 +803,65 @@ def occ_export_sparse(ijk, dims, origin, resolution):
     return ijk.astype(np.int32), centres
 
 
+# ---- the unknown volume a view reveals and the greedy choice by it restated in numpy ("Unknown volume"): what
+# volume_kernels.hip must give, bit for bit.  int64 throughout. -------------------------------------------------------------------------
+def unknown_ref(occ, free):
+    """SpaceMap.unknown() -> (nx,ny,nz) bool: the voxels of state 0, neither occupied nor free."""
+    return ~np.asarray(occ, dtype=bool) & ~np.asarray(free, dtype=bool)
+
+
+def voxel_centres(dims, origin, resolution):
+    """The centre of every voxel of a grid -> (nx,ny,nz,3) f32: fl(origin + fl(fl(i + 0.5) r)) per axis, export()'s rule."""
+    f32 = np.float32
+    o, r = np.asarray(origin, dtype=f32).reshape(3), f32(resolution)
+    ax = [(o[a] + ((np.arange(int(dims[a])).astype(f32) + f32(0.5)) * r).astype(f32)).astype(f32) for a in range(3)]
+    return np.stack(np.meshgrid(*ax, indexing="ij"), axis=-1).astype(f32)
+
+
+def view_volume_ref(kept, t, origin, resolution, occ, free, claimed=None):
+    """The voxels one view reveals -> (gain, revealed (nx,ny,nz) bool).  kept: (nx,ny,nz) bool, the cull's verdict on every voxel's
+    centre — an input, so the f32 cull is not re-derived here.  A voxel is revealed iff its state is 0, it is not set in claimed,
+    kept holds it and los_fixed from the camera position t to its centre with skip (1, 0) finds no occupied voxel: the camera's own
+    voxel and the target are not tested, unknown voxels do not block.  A position t out of range, or a centre out of range,
+    reveals nothing."""
+    occ, free = np.asarray(occ, dtype=bool), np.asarray(free, dtype=bool)
+    cand = unknown_ref(occ, free) & np.asarray(kept, dtype=bool)
+    if claimed is not None:
+        cand &= ~np.asarray(claimed, dtype=bool)
+    revealed = np.zeros(occ.shape, dtype=bool)
+    qa, oka = occ_fixed(np.asarray(t, dtype=np.float32).reshape(1, 3), origin, resolution)
+    ijk = np.argwhere(cand)
+    if not oka[0] or not len(ijk):
+        return 0, revealed
+    c = voxel_centres(occ.shape, origin, resolution)[ijk[:, 0], ijk[:, 1], ijk[:, 2]]
+    qb, okb = occ_fixed(c, origin, resolution)
+    clear = np.zeros(len(ijk), dtype=bool)
+    clear[okb] = ~los_fixed(np.broadcast_to(qa, qb[okb].shape), qb[okb], occ, (1, 0))
+    ijk = ijk[clear]
+    revealed[ijk[:, 0], ijk[:, 1], ijk[:, 2]] = True
+    return int(clear.sum()), revealed
+
+
+def volume_select_ref(revealed_sets, k, min_gain=1, claimed=None):
+    """The greedy selection over per-view revealed masks (M, nx,ny,nz) bool, each computed WITHOUT a claimed plane -> (order list,
+    gains list, revealed mask).  Round after round the view not yet taken with the most voxels outside the claimed mask wins, the
+    lowest index on ties; below min_gain the selection stops; otherwise its voxels join the mask.  (A voxel's line of sight does not
+    depend on the claimed plane, so masking afterwards equals scoring against it.)"""
+    sets = np.asarray(revealed_sets, dtype=bool)
+    mask = np.zeros(sets.shape[1:], dtype=bool) if claimed is None else np.array(claimed, dtype=bool)
+    taken, order, gains = np.zeros(len(sets), dtype=bool), [], []
+    for _ in range(min(int(k), len(sets))):
+        g = np.array([-1 if taken[i] else int((sets[i] & ~mask).sum()) for i in range(len(sets))], dtype=np.int64)
+        best = int(np.argmax(g))   # (the first of equal gains)
+        if g[best] < int(min_gain):
+            break
+        taken[best] = True
+        order.append(best)
+        gains.append(int(g[best]))
+        mask |= sets[best]
+    return order, gains, mask
+
+
 def box_room(doorway=False, step=0.02):
     """A scanned room for the exploration tests and the sample: the six faces of the box [0, 2] x [0, 2] x [0, 1] sampled every `step`
     metres, face after face (edges and corners appear once per face) -> (N,3) f32; doorway: the wall x = 2 is left open for y in

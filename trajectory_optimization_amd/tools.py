@@ -445,6 +445,67 @@ def select_views(model_or_cloud, cand_poses, cand_quats, k, prior_log_odds=None,
                          log_odds=S)
 
 
+class VolumeSelection(_Result):
+    """What select_views_volume returns: order (n_selected,) int64 and gains (n_selected,) int64 on the host (gain j = the unknown
+    voxels view order[j] added when it was chosen: a marginal gain), poses / quats (the chosen rows in selection order, on the
+    device), revealed (an ops.OccupancyGrid: the caller's `claimed` plus every voxel the chosen views reveal — the next round's or the
+    next robot's `claimed`) and total = sum(gains), the popcount the selection added to it."""
+    __slots__ = ("order", "gains", "poses", "quats", "revealed", "total")
+
+    @property
+    def n_selected(self):
+        return int(self.order.shape[0])
+
+
+def _volume_setup(what, space_or_evidence_map, camera):
+    """view_volume's and select_views_volume's map and camera keywords -> (ops.SpaceMap, ops.Camera, min_dist, max_dist)."""
+    space = space_or_evidence_map.space if isinstance(space_or_evidence_map, ops.EvidenceMap) else space_or_evidence_map
+    if not isinstance(space, ops.SpaceMap):
+        raise ValueError(f"{what}: the map must be an ops.SpaceMap or an ops.EvidenceMap, got {type(space_or_evidence_map).__name__}")
+    allowed = {"intrins", "img_width", "img_height", "min_dist", "max_dist"}
+    if set(camera) - allowed:
+        raise ValueError(f"{what}: unknown keyword(s) {sorted(set(camera) - allowed)}")
+    missing = [k for k in ("intrins", "img_width", "img_height") if k not in camera]
+    if missing:
+        raise ValueError(f"{what}: the camera is needed: {missing} missing")
+    mn, mx = camera.get("min_dist", 1.0), camera.get("max_dist", 5.0)
+    return space, ops.Camera(camera["intrins"], camera["img_width"], camera["img_height"], mn, mx), mn, mx
+
+
+def view_volume(space_or_evidence_map, poses, quats, claimed=None, **camera):
+    """How much unknown space would a camera see from here?  (M,) int64 on the device: per view poses[w] (M,3) / quats[w] (M,4) wxyz
+    the number of UNKNOWN voxels of the map — neither occupied nor free, and not set in `claimed` (an ops.OccupancyGrid of the map's
+    geometry, or None) — whose centre lies inside the camera frustum and the depth limits and is in line of sight of the camera
+    through the occupied voxels ("Unknown volume").  Unknown voxels do not block: the rule is optimistic.  Keywords:
+    intrins, img_width, img_height[, min_dist = 1, max_dist = 5], as select_views takes them with points.  An ops.EvidenceMap is
+    used through its .space.  Exact integers: the same counts in every run."""
+    space, cam, mn, mx = _volume_setup("view_volume", space_or_evidence_map, camera)
+    return ops.view_volume(space, poses, quats, cam, mn, mx, claimed=claimed)
+
+
+def select_views_volume(space_or_evidence_map, cand_poses, cand_quats, k, min_gain=1, claimed=None, **camera):
+    """Greedy next-best-view selection by revealed volume ("Unknown volume"): out of the M candidates cand_poses (M,3) /
+    cand_quats (M,4) wxyz, M <= 65 535 — propose_views' prop.poses, prop.quats go in as they are — choose up to k that together
+    reveal the most unknown voxels of the map.  Round after round every candidate not yet taken is scored by view_volume against the voxels claimed
+    so far, the largest gain wins (ties go to the lowest index), and the winner's voxels are claimed; selection stops after k views,
+    when none is left, or when the best gain is below min_gain (an integer number of voxels >= 1).  claimed: an ops.OccupancyGrid of
+    the map's geometry holding what earlier rounds or other robots will already see (not modified), or None.
+
+    The objective is the coverage of a set — the number of distinct voxels revealed — which is monotone submodular: the greedy
+    choice is within (1 - 1/e) of the best set of that size.  Everything runs on the device, 3 k launches and one host
+    synchronisation at the end.  Keywords: the camera, as view_volume takes it.  -> VolumeSelection."""
+    space, cam, mn, mx = _volume_setup("select_views_volume", space_or_evidence_map, camera)
+    order, gains, revealed = ops.view_volume_select(space, cand_poses, cand_quats, cam, mn, mx, k, min_gain, claimed)
+    h = torch.cat([order.long(), gains]).cpu()   # the one synchronisation
+    kk = order.shape[0]
+    n = int((h[:kk] >= 0).sum())
+    sel, g = h[:n].clone(), h[kk:kk + n].clone()
+    idx = sel.to(space.device)
+    ps = cand_poses.detach().to(device=space.device, dtype=torch.float32)
+    qs = cand_quats.detach().to(device=space.device, dtype=torch.float32)
+    return VolumeSelection(order=sel, gains=g, poses=ps[idx], quats=qs[idx], revealed=revealed, total=int(g.sum()))
+
+
 def _clearance_cloud(points_or_cloud_or_model, what, field=False):
     """The packed cloud behind a clearance query's first argument: a ModelTraj (its cloud), an ops.PackedCloud (sorted or not) or
     (N,3) points (packed here) — checked, nothing launched: -> (cloud or None, points or None).  field=True: an ops.ClearanceField
