@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_occ_unknown / tohip_view_volume / tohip_view_volume_pick (the unknown volume a view would reveal, and the greedy
+/* (still 15) + tohip_cast_segments / tohip_depth_scan (where a ray through the map stops: first hits of segments and the depth image a
+ * sensor at a pose would return): new symbols only.
+ * (still 15) + tohip_occ_unknown / tohip_view_volume / tohip_view_volume_pick (the unknown volume a view would reveal, and the greedy
  * choice of views by it): new symbols only.
  * (still 15) + tohip_clearance_map / tohip_clearance_map_segments and the flag bit TOHIP_TRAJ_CLEARANCE_PREFILLED (the clearance term
  * asked of the map: the obstacles are an occupancy grid's voxels): new symbols and one flag bit that was refused before — no struct
@@ -1313,6 +1315,48 @@ int tohip_view_volume(const void *occupied, const void *free_grid, const void *c
                       uint64_t *stats, void *stream);
 int tohip_view_volume_pick(const int64_t *gains, int32_t *taken, int64_t n_views, int64_t min_gain, int32_t round, int32_t *order,
                            int64_t *picked_gain, int32_t *stop, void *stream);
+
+/* ---- ray casts and depth scans (raycast_kernels.hip, DESIGN.md §10, "Ray casts and depth scans") -------
+ * Where does this ray stop?  Both entries walk exactly as tohip_los_segments walks (same steps, same tie rule, same tests).
+ *
+ * The CAST of a segment A -> B (the fixed-point forms of a and b, both in range) with (start_skip, end_skip): the HIT is the first
+ * visited voxel that tohip_los_segments would call occupied — cheb(v, v0) >= start_skip and cheb(v, e) > end_skip, inside dims, bit
+ * set; with end_skip = 0 the end voxel itself is never tested.  Its ENTRY PARAMETER is the crossing parameter n_a / m_a of the last
+ * step the walk took before it stood on the hit (n the distance to the face in 1/256 voxel before the step adds 256, m = |B - A| on
+ * that axis), the exact rational 0/1 when no step was taken; it equals the maximum over the axes with k_a > 0 steps taken of
+ * (n_a0 + 256 (k_a - 1)) / m_a, compared by integer cross-multiplication.  lam = fl(f32(num) / f32(den)): num and den are exact in
+ * f32 and the division is correctly rounded, so equal rationals give equal bits.
+ *
+ * tohip_cast_segments: a, b (n_rays, 3) f32 world points on the device -> voxel (n_rays) int32: the hit's linear index i + nx (j + ny
+ * k), -1 clear, -2 an endpoint out of range; lam (n_rays) f32: the hit's entry parameter, 1.0 clear, NaN out of range.  voxel == -1
+ * iff tohip_los_segments gives 1 and voxel == -2 iff it gives 2, with the same skips (each in [0, 8192]).  stats (DEVICE uint64 x 2,
+ * may be NULL, zero-filled by the caller): += rays walked, += voxels visited.
+ *
+ * tohip_depth_scan: view w is the pose poses + 3 w, quats + 4 w (wxyz, normalised as tohip_los_rows does, normalize = 1).  cam: K =
+ * (fx 0 cx; 0 fy cy; 0 0 1) with fx, fy > 0, everything finite, W = img_width and H = img_height integral values in [1, 8192]; 1 <=
+ * n_views <= 65535 and n_views H W < 2^31; 0 <= min_dist < max_dist, both finite; TOHIP_EINVAL otherwise (cam's own min_dist,
+ * max_dist and eps are not read).  Pixel (x, y) is column x of row y; all arithmetic is f32, every operation rounded, no fma:
+ * dc = (fl(fl(x - cx) / fx), fl(fl(y - cy) / fy), 1); the far point in the camera frame Fc = (fl(dc.x D), fl(dc.y D), D) with D =
+ * max_dist (the range is a z-depth, as in the cull); in the world B = fl(rot(q, Fc) + t) per axis, rot being tohip_to_camera_frame's two
+ * Hamilton products with the roles of q and its conjugate exchanged and the same order of terms.  The ray is the cast t -> B with skips
+ * (1, 0): the camera's own voxel and B's voxel are not tested.  depth = fl(lam D).  Outputs, each indexed [w][y][x]:
+ *   voxel (int32)  the hit's linear index, -1 no hit, -2 skipped;
+ *   depth (f32)    fl(lam D) of a hit, +inf without one, NaN skipped;
+ *   flags (uint8)  0 a return; 1 no return within D; 2 skipped (t or B out of range); 3 a hit nearer than the sensor's minimum,
+ *                  !(depth > min_dist): the ray is blocked and reports no point (voxel and depth still name what blocked it);
+ *   points (f32 x 3, may be NULL)  flag 0: the hit voxel's centre fl(origin + fl(fl(i + 0.5) r)), tohip_occ_export's bits; flag 1:
+ *                  B; flags 2 and 3: NaN.
+ * hit_plane and pass_plane (each may be NULL): grids of the scanned grid's geometry (grid_bytes each), neither the scanned grid nor
+ * each other (TOHIP_EINVAL).  hit_plane gets the bit of every flag-0 hit voxel; pass_plane the bit of every voxel inside dims that a
+ * ray of flag 0 or 1 visited before its hit — the camera's voxel and every tested, clear voxel; never the hit voxel, never B's voxel.
+ * A flag-3 ray marks nothing.  Bits are only ever set (32-bit integer atomic OR, issued only where a word lacks a bit).
+ * stats (DEVICE uint64 x 3, may be NULL, zero-filled by the caller): += rays walked, += voxels visited, += plane atomics issued.
+ * Every argument check returns before anything is enqueued; nothing synchronises with the host. */
+int tohip_cast_segments(const void *grid, size_t grid_bytes, const tohip_occ_geom *geom, const float *a, const float *b, int64_t n_rays,
+                        int32_t start_skip, int32_t end_skip, int32_t *voxel, float *lam, uint64_t *stats, void *stream);
+int tohip_depth_scan(const void *grid, size_t grid_bytes, const tohip_occ_geom *geom, const float *poses, const float *quats,
+                     int64_t n_views, const tohip_camera *cam, float min_dist, float max_dist, void *hit_plane, void *pass_plane,
+                     int32_t *voxel, float *depth, uint8_t *flags, float *points, uint64_t *stats, void *stream);
 
 /* ---- optional per-kernel timing (bench.py's roofline leg) -----------------------------------------
  * When enabled, every launch of the big kernels is bracketed by hipEventRecord on its own stream.

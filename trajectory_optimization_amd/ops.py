@@ -860,6 +860,19 @@ class OccupancyGrid:
         _map_call(self.device, "tohip_los_segments", *self._sizes(), ptr(a), ptr(b), a.shape[0], ss, es, ptr(out), ptr(stats))
         return out
 
+    def cast(self, a, b, skip=(1, 0), stats=None):
+        """Where does the segment a[i] -> b[i] stop?  -> (voxel (R,) int32, lam (R,) f32) (tohip_cast_segments, DESIGN.md 10 "Ray
+        casts and depth scans"): the first voxel line_of_sight(a, b, skip) would call occupied as its linear index i + nx (j + ny k),
+        -1 where the segment is clear, -2 where an endpoint is out of range; lam the parameter in [0, 1] at which the segment
+        enters that voxel, 1 where clear, NaN where out of range.  With the default skip the end voxel itself is never tested.
+        stats: a zero-filled (2,) int64 device tensor that receives (rays walked, voxels visited), or None."""
+        _, _, _, (ss, es) = check_los(self.origin, self.resolution, self.dims, skip, a, b)
+        a, b = covmap_points(a, self.device, "cast"), covmap_points(b, self.device, "cast")
+        voxel = torch.empty(a.shape[0], dtype=torch.int32, device=self.device)
+        lam = torch.empty(a.shape[0], dtype=torch.float32, device=self.device)
+        _map_call(self.device, "tohip_cast_segments", *self._sizes(), ptr(a), ptr(b), a.shape[0], ss, es, ptr(voxel), ptr(lam), ptr(stats))
+        return voxel, lam
+
     def empty_like(self):
         """An empty grid of this one's origin, resolution, dims and device: a free plane or a mask for it."""
         return OccupancyGrid(self.origin, self.resolution, self.dims, device=self.device)
@@ -1133,6 +1146,92 @@ def view_volume_select(space, poses, quats, cam, min_dist, max_dist, k, min_gain
         # the mark step: the winner's number stays on the device, and one view may claim what it counts
         _view_volume_call(space, p, q, M, order[j:j + 1], cam, min_dist, max_dist, revealed, revealed, window, scratch, stop, None)
     return order, picked, revealed
+
+
+SCAN_MAX_SIDE = 8192    # pixels per side of a depth scan's image
+SCAN_MAX_VIEWS = 65535  # views per launch (the grid's second dimension)
+
+
+def check_depth_scan(grid, poses, quats, intrins, img_width, img_height, min_dist, max_dist, hit_plane=None, pass_plane=None):
+    """depth_scan's arguments, by name: grid an ops.OccupancyGrid; poses (V,3) and quats (V,4) floating tensors with the same V in
+    [1, 65 535], finite; intrins 9 finite numbers (fx 0 cx; 0 fy cy; 0 0 1) with fx, fy > 0; img_width and img_height integral
+    numbers in [1, 8192] with V H W < 2^31; 0 <= min_dist < max_dist, both finite; hit_plane and pass_plane None or
+    ops.OccupancyGrids of the grid's origin, resolution, dims and device, neither the grid itself nor each other
+    -> (V, W, H); ValueError otherwise.  Needs no GPU."""
+    if not isinstance(grid, OccupancyGrid):
+        raise ValueError(f"grid must be an ops.OccupancyGrid, got {type(grid).__name__}")
+    for name, t, w in (("poses", poses, 3), ("quats", quats, 4)):
+        if not torch.is_tensor(t) or not t.is_floating_point():
+            raise ValueError(f"{name} must be a floating-point tensor, got {type(t).__name__}{'' if not torch.is_tensor(t) else ' of ' + str(t.dtype)}")
+        if t.dim() != 2 or t.shape[1] != w or t.shape[0] == 0:
+            raise ValueError(f"{name} must have shape (V,{w}) with V >= 1, got {tuple(t.shape)}")
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError(f"{name} must be finite (NaN or inf found)")
+    V = poses.shape[0]
+    if quats.shape[0] != V:
+        raise ValueError(f"poses holds {V} views, quats {quats.shape[0]}")
+    if V > SCAN_MAX_VIEWS:
+        raise ValueError(f"poses holds {V} views, a scan takes at most {SCAN_MAX_VIEWS}")
+    try:
+        K = np.asarray(torch.as_tensor(intrins, dtype=torch.float32).detach().cpu().numpy(), dtype=np.float32).reshape(-1)
+    except (TypeError, ValueError, RuntimeError):
+        K = np.zeros(0, dtype=np.float32)
+    if K.shape != (9,) or not np.isfinite(K).all():
+        raise ValueError(f"intrins must be 9 finite numbers (a 3 x 3 matrix), got {intrins!r}")
+    if not (K[0] > 0 and K[4] > 0):
+        raise ValueError(f"intrins must have fx > 0 and fy > 0, got fx = {K[0]:g}, fy = {K[4]:g}")
+    if K[1] != 0 or K[3] != 0 or K[6] != 0 or K[7] != 0 or K[8] != 1:
+        raise ValueError(f"intrins must be (fx 0 cx; 0 fy cy; 0 0 1): no skew and K[2][2] = 1, got {K.tolist()}")
+    sides = []
+    for name, v in (("img_width", img_width), ("img_height", img_height)):
+        f = _float_or_nan(v, np.float32) if _is_real(v) else float("nan")
+        if not (1 <= f <= SCAN_MAX_SIDE) or f != np.floor(f):
+            raise ValueError(f"{name} must be an integral number in [1, {SCAN_MAX_SIDE}], got {v!r}")
+        sides.append(int(f))
+    W, H = sides
+    if V * H * W >= 1 << 31:
+        raise ValueError(f"img_width x img_height x views must stay below 2^31 pixels, got {W} x {H} x {V}")
+    mn = _float_or_nan(min_dist, np.float32) if _is_real(min_dist) else float("nan")
+    mx = _float_or_nan(max_dist, np.float32) if _is_real(max_dist) else float("nan")
+    if not (np.isfinite(mn) and mn >= 0):
+        raise ValueError(f"min_dist must be a finite number >= 0, got {min_dist!r}")
+    if not (np.isfinite(mx) and mx > mn):
+        raise ValueError(f"max_dist must be a finite number > min_dist = {mn:g}, got {max_dist!r}")
+    for name, g in (("hit_plane", hit_plane), ("pass_plane", pass_plane)):
+        if g is None:
+            continue
+        if not isinstance(g, OccupancyGrid):
+            raise ValueError(f"{name} must be an ops.OccupancyGrid or None, got {type(g).__name__}")
+        if g is grid:
+            raise ValueError(f"{name} must not be the scanned grid itself")
+        diff = _grid_difference(grid, g)
+        if diff:
+            raise ValueError(f"{name}: its {diff[0]} differs from the scanned grid's ({diff[2]} and {diff[1]})")
+    if hit_plane is not None and pass_plane is hit_plane:
+        raise ValueError("pass_plane must not be the hit plane itself")
+    return V, W, H
+
+
+def depth_scan(grid, poses, quats, cam, min_dist, max_dist, hit_plane=None, pass_plane=None, points=False, stats=None):
+    """The depth image a sensor at each pose would return from `grid` (tohip_depth_scan, DESIGN.md 10 "Ray casts and depth scans")
+    -> (voxel (V,H,W) int32, depth (V,H,W) f32, flags (V,H,W) uint8, points (V,H,W,3) f32 or None), on the device.  Per pixel the
+    ray from the pose through the pixel to z-depth max_dist is cast with skip (1, 0): flags 0 a return (voxel: its linear index,
+    depth = lam max_dist, points: the voxel's centre), 1 no return (voxel -1, depth +inf, points: the ray's far point), 2 skipped
+    (the pose or the far point out of range: -2, NaN, NaN), 3 a hit nearer than min_dist (voxel and depth name it, points NaN).
+    cam: an ops.Camera (its K and image size).  hit_plane / pass_plane: OccupancyGrids of the grid's geometry that receive the
+    flag-0 hit voxels and the voxels the rays of flag 0 and 1 passed (bits are only set).  stats: a zero-filled (3,) int64 device
+    tensor that receives (rays walked, voxels visited, plane atomics issued).  One launch, nothing read back."""
+    V, W, H = check_depth_scan(grid, poses, quats, list(cam.c.K), cam.c.img_width, cam.c.img_height, min_dist, max_dist, hit_plane, pass_plane)
+    p, q = _view_rows(grid, poses, quats)
+    dev = grid.device
+    voxel = torch.empty((V, H, W), dtype=torch.int32, device=dev)
+    depth = torch.empty((V, H, W), dtype=torch.float32, device=dev)
+    flags = torch.empty((V, H, W), dtype=torch.uint8, device=dev)
+    pts = torch.empty((V, H, W, 3), dtype=torch.float32, device=dev) if points else None
+    _map_call(dev, "tohip_depth_scan", *grid._sizes(), ptr(p), ptr(q), V, cam.ref(), float(min_dist), float(max_dist),
+              ptr(hit_plane.buf if hit_plane is not None else None), ptr(pass_plane.buf if pass_plane is not None else None), ptr(voxel),
+              ptr(depth), ptr(flags), ptr(pts), ptr(stats))
+    return voxel, depth, flags, pts
 
 
 FIELD_MAX_D = 254          # the largest truncation distance in voxels: D^2 < 65535, the sentinel

@@ -862,6 +862,181 @@ def volume_select_ref(revealed_sets, k, min_gain=1, claimed=None):
     return order, gains, mask
 
 
+# ---- ray casts and depth scans restated in numpy ("Ray casts and depth scans"): what raycast_kernels.hip must give, bit
+# for bit.  Visitors of walk_fixed in int64; the f32 ray arithmetic operation by operation. ------------------------------------------
+SCAN_MAX_SIDE = 8192
+SCAN_MAX_VIEWS = 65535
+
+
+def cast_fixed(A, B, occ, skip=(1, 0), marks=None, plane=None):
+    """The cast of A -> B, (R,3) fixed-point triples (both in range), through occ (nx,ny,nz) bool: walk_fixed, stopped at the HIT,
+    the first visited voxel that los_fixed would call occupied (cheb(v, v0) >= skip[0], cheb(v, e) > skip[1], inside dims, set).
+    -> dict(hit (R,) bool, voxel (R,3) int64 the hit voxel, steps (R,3) int64 the steps taken per axis when the walk stood on it, last
+    (R,) int64 the axis of the last of them (-1: none), visits (R,) int64 the voxels looked at: those with cheb(v, e) > skip[1] up to
+    and including the hit).  marks (R,) int64 with plane (nx,ny,nz) bool: instead of casting, the first marks[i] looked-at voxels of
+    ray i that lie inside dims are set in plane (the walk in front of a known hit), and nothing is tested."""
+    A, B = np.asarray(A, dtype=np.int64).reshape(-1, 3), np.asarray(B, dtype=np.int64).reshape(-1, 3)
+    occ = np.asarray(occ, dtype=bool)
+    dims = np.asarray(occ.shape, dtype=np.int64)
+    ss, es = int(skip[0]), int(skip[1])
+    R = len(A)
+    v0, e = A >> 8, B >> 8
+    out = dict(hit=np.zeros(R, dtype=bool), voxel=np.zeros((R, 3), dtype=np.int64), steps=np.zeros((R, 3), dtype=np.int64),
+               last=np.full(R, -1, dtype=np.int64), visits=np.zeros(R, dtype=np.int64))
+    prev, axis = v0.copy(), np.full(R, -1, dtype=np.int64)
+    left = None if marks is None else np.array(marks, dtype=np.int64)
+
+    def visit(idx, vi, last):
+        moved = vi != prev[idx]
+        axis[idx] = np.where(moved.any(axis=1), moved.argmax(axis=1), axis[idx])
+        prev[idx] = vi
+        seen = np.abs(vi - e[idx]).max(axis=1) > es
+        inside = ((vi >= 0) & (vi < dims[None, :])).all(axis=1)
+        if left is not None:
+            seen &= left[idx] > 0
+            left[idx[seen]] -= 1
+            m = seen & inside
+            plane[vi[m, 0], vi[m, 1], vi[m, 2]] = True
+            return seen
+        out["visits"][idx[seen]] += 1
+        t = seen & (np.abs(vi - v0[idx]).max(axis=1) >= ss) & inside
+        hit = np.zeros(len(idx), dtype=bool)
+        hit[t] = occ[vi[t, 0], vi[t, 1], vi[t, 2]]
+        r = idx[hit]
+        out["hit"][r], out["voxel"][r], out["steps"][r], out["last"][r] = True, vi[hit], np.abs(vi[hit] - v0[r]), axis[r]
+        return seen & ~hit   # (the distance to e only falls: a voxel not looked at ends the walk)
+
+    walk_fixed(A, B, visit)
+    return out
+
+
+def cast_entry(A, B, steps, last=None):
+    """The entry parameter of the voxel reached from A (towards B) by steps (R,3) per axis -> (num, den) int64, the exact rational:
+    with last (R,) — the axis of the last step, -1 for none — the crossing parameter n / m of that step, n = n0 + 256 (k - 1) the
+    distance to the face before the step added 256; without it the maximum over the axes with k > 0 of (n0_a + 256 (k_a - 1)) / m_a
+    by integer cross-multiplication, the lowest axis kept on ties (equal rationals: the same f32 quotient).  0/1 with no step."""
+    A, B = np.asarray(A, dtype=np.int64).reshape(-1, 3), np.asarray(B, dtype=np.int64).reshape(-1, 3)
+    k = np.asarray(steps, dtype=np.int64).reshape(-1, 3)
+    D = B - A
+    s, m = np.sign(D), np.abs(D)
+    v = A >> 8
+    n = np.where(s > 0, (v + 1) * 256 - A, A - v * 256) + 256 * (k - 1)
+    num, den = np.zeros(len(A), dtype=np.int64), np.ones(len(A), dtype=np.int64)
+    if last is not None:
+        last = np.asarray(last, dtype=np.int64).reshape(-1)
+        has, a = last >= 0, np.maximum(last, 0)
+        rows = np.arange(len(A))
+        return np.where(has, n[rows, a], num), np.where(has, m[rows, a], den)
+    for a in range(3):
+        take = (k[:, a] > 0) & (n[:, a] * den > num * m[:, a])
+        num, den = np.where(take, n[:, a], num), np.where(take, m[:, a], den)
+    return num, den
+
+
+def cast_lam(num, den):
+    """lam = fl(f32(num) / f32(den)): both are exact in f32 (< 2^24) and the division is correctly rounded."""
+    return (np.asarray(num).astype(np.float32) / np.asarray(den).astype(np.float32)).astype(np.float32)
+
+
+def cast_ref(a, b, origin, resolution, occ, skip=(1, 0)):
+    """OccupancyGrid.cast(a, b, skip) of world points (R,3) -> (voxel (R,) int32: i + nx (j + ny k) of the hit, -1 clear, -2 an
+    endpoint out of range; lam (R,) f32: the entry parameter, 1 clear, NaN out of range; visits: the voxels looked at)."""
+    occ = np.asarray(occ, dtype=bool)
+    qa, oka = occ_fixed(a, origin, resolution)
+    qb, okb = occ_fixed(b, origin, resolution)
+    ok = oka & okb
+    voxel, lam = np.full(len(qa), -2, dtype=np.int32), np.full(len(qa), np.nan, dtype=np.float32)
+    c = cast_fixed(qa[ok], qb[ok], occ, skip)
+    num, den = cast_entry(qa[ok], qb[ok], c["steps"])
+    v = c["voxel"]
+    voxel[ok] = np.where(c["hit"], v[:, 0] + occ.shape[0] * (v[:, 1] + occ.shape[1] * v[:, 2]), -1)
+    lam[ok] = np.where(c["hit"], cast_lam(num, den), np.float32(1))
+    return voxel, lam, int(c["visits"].sum())
+
+
+def exact_pose_ref(quats):
+    """exact_pose(normalize = 1) of quaternions (V,4) wxyz in f32, operation by operation: ss = ((w w + x x) + y y) + z z, n =
+    max(sqrt(ss), 1e-12), q / n."""
+    f32 = np.float32
+    q = np.asarray(quats, dtype=f32).reshape(-1, 4)
+    with np.errstate(all="ignore"):
+        ss = (q[:, 0] * q[:, 0]).astype(f32)
+        for a in (1, 2, 3):
+            ss = (ss + (q[:, a] * q[:, a]).astype(f32)).astype(f32)
+        nn = np.sqrt(ss).astype(f32)
+        nn = np.where(nn < f32(1e-12), f32(1e-12), nn).astype(f32)
+        return (q / nn[:, None]).astype(f32)
+
+
+def scan_rays_ref(poses, quats, K, img_width, img_height, max_dist):
+    """The far point of every pixel's ray -> (V, H, W, 3) f32, every operation rounded in f32 and none fused: dc = ((x - cx) / fx,
+    (y - cy) / fy, 1), Fc = (dc.x D, dc.y D, D), B = rot(q, Fc) + t with q = exact_pose_ref(quats) and rot = q (0, Fc) conj(q) as two
+    Hamilton products in exact_to_cam's order of terms."""
+    f32 = np.float32
+    K = np.asarray(K, dtype=f32).reshape(9)
+    W, H, D = int(img_width), int(img_height), f32(max_dist)
+    t = np.asarray(poses, dtype=f32).reshape(-1, 3)
+    q = exact_pose_ref(quats)
+    with np.errstate(all="ignore"):
+        dx = ((np.arange(W).astype(f32) - K[2]).astype(f32) / K[0]).astype(f32)
+        dy = ((np.arange(H).astype(f32) - K[5]).astype(f32) / K[4]).astype(f32)
+        shape = (len(t), H, W)
+        bx = np.broadcast_to((dx * D).astype(f32)[None, None, :], shape)
+        by = np.broadcast_to((dy * D).astype(f32)[None, :, None], shape)
+        bz = np.broadcast_to(D, shape)
+        bw = np.zeros(shape, dtype=f32)
+        aw, ax, ay, az = (q[:, i][:, None, None] for i in range(4))
+        cw, cx, cy, cz = aw, -ax, -ay, -az
+        ow = aw * bw - ax * bx - ay * by - az * bz
+        ox = aw * bx + ax * bw + ay * bz - az * by
+        oy = aw * by - ax * bz + ay * bw + az * bx
+        oz = aw * bz + ax * by - ay * bx + az * bw
+        r = [ow * cx + ox * cw + oy * cz - oz * cy, ow * cy - ox * cz + oy * cw + oz * cx, ow * cz + ox * cy - oy * cx + oz * cw]
+        out = np.stack([r[a] + t[:, a][:, None, None] for a in range(3)], axis=-1)
+    assert out.dtype == f32
+    return out
+
+
+def depth_scan_ref(poses, quats, K, img_width, img_height, min_dist, max_dist, origin, resolution, occ):
+    """depth_scan of the grid occ (nx,ny,nz) bool -> dict(voxel (V,H,W) int32, depth (V,H,W) f32, flags (V,H,W) uint8, points
+    (V,H,W,3) f32, far (V,H,W,3) f32, hit_plane and pass_plane (nx,ny,nz) bool, rays, visits): per pixel the cast t -> B with skip
+    (1, 0); flags 0 a return, 1 none within max_dist, 2 skipped (t or B out of range), 3 a hit with !(depth > min_dist); depth =
+    fl(lam D), +inf for flag 1, NaN for flag 2; points: the hit voxel's centre (flag 0), B (flag 1), NaN otherwise.  hit_plane: the
+    flag-0 hit voxels; pass_plane: the voxels inside dims that a ray of flag 0 or 1 looked at before its hit."""
+    f32 = np.float32
+    occ = np.asarray(occ, dtype=bool)
+    nx, ny, _ = occ.shape
+    far = scan_rays_ref(poses, quats, K, img_width, img_height, max_dist)
+    V, H, W, _ = far.shape
+    t = np.asarray(poses, dtype=f32).reshape(-1, 3)
+    qa, oka = occ_fixed(np.repeat(t, H * W, axis=0), origin, resolution)
+    qb, okb = occ_fixed(far.reshape(-1, 3), origin, resolution)
+    ok = oka & okb
+    n = len(qa)
+    voxel, depth = np.full(n, -2, dtype=np.int32), np.full(n, np.nan, dtype=f32)
+    flags, points = np.full(n, 2, dtype=np.uint8), np.full((n, 3), np.nan, dtype=f32)
+    A, B = qa[ok], qb[ok]
+    c = cast_fixed(A, B, occ, (1, 0))
+    num, den = cast_entry(A, B, c["steps"])
+    hit, v = c["hit"], c["voxel"]
+    dep = (cast_lam(num, den) * f32(max_dist)).astype(f32)
+    fl = np.where(hit, np.where(dep > f32(min_dist), 0, 3), 1).astype(np.uint8)
+    voxel[ok] = np.where(hit, v[:, 0] + nx * (v[:, 1] + ny * v[:, 2]), -1)
+    depth[ok] = np.where(hit, dep, f32(np.inf))
+    flags[ok] = fl
+    o, r = np.asarray(origin, dtype=f32).reshape(3), f32(resolution)
+    centre = (o[None, :] + ((v.astype(f32) + f32(0.5)) * r).astype(f32)).astype(f32)
+    p = np.full((len(A), 3), np.nan, dtype=f32)
+    p[fl == 0], p[fl == 1] = centre[fl == 0], far.reshape(-1, 3)[ok][fl == 1]
+    points[ok] = p
+    hit_plane, pass_plane = np.zeros(occ.shape, dtype=bool), np.zeros(occ.shape, dtype=bool)
+    h = v[fl == 0]
+    hit_plane[h[:, 0], h[:, 1], h[:, 2]] = True
+    cast_fixed(A, B, occ, (1, 0), marks=np.where(fl == 3, 0, c["visits"] - hit), plane=pass_plane)
+    return dict(voxel=voxel.reshape(V, H, W), depth=depth.reshape(V, H, W), flags=flags.reshape(V, H, W), points=points.reshape(V, H, W, 3),
+                far=far, hit_plane=hit_plane, pass_plane=pass_plane, rays=int(ok.sum()), visits=int(c["visits"].sum()))
+
+
 def box_room(doorway=False, step=0.02):
     """A scanned room for the exploration tests and the sample: the six faces of the box [0, 2] x [0, 2] x [0, 1] sampled every `step`
     metres, face after face (edges and corners appear once per face) -> (N,3) f32; doorway: the wall x = 2 is left open for y in

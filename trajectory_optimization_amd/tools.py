@@ -7,6 +7,7 @@ All index sets are bit-exact with the reference's CPU path (tests/test_hip_hard.
 import math
 import types
 
+import numpy as np
 import torch
 
 from . import ops
@@ -504,6 +505,140 @@ def select_views_volume(space_or_evidence_map, cand_poses, cand_quats, k, min_ga
     ps = cand_poses.detach().to(device=space.device, dtype=torch.float32)
     qs = cand_quats.detach().to(device=space.device, dtype=torch.float32)
     return VolumeSelection(order=sel, gains=g, poses=ps[idx], quats=qs[idx], revealed=revealed, total=int(g.sum()))
+
+
+class RayHits(_Result):
+    """What cast_rays returns, on the device: voxel (R,) int32 (the hit's linear index i + nx (j + ny k), -1 clear, -2 an endpoint
+    out of range), ijk (R,3) int32 (the hit voxel, (-1, -1, -1) without one), lam (R,) f32 (where along a -> b the ray enters it, 1
+    clear, NaN out of range) and points (R,3) f32 (the hit voxel's centre by export()'s rule, b where clear, NaN out of range)."""
+    __slots__ = ("voxel", "ijk", "lam", "points")
+
+
+def _scanned_grid(what, grid_or_map):
+    """The occupancy grid a cast walks: an ops.OccupancyGrid, or the occupied plane of an ops.SpaceMap / ops.EvidenceMap."""
+    g = grid_or_map.occupied if isinstance(grid_or_map, (ops.SpaceMap, ops.EvidenceMap)) else grid_or_map
+    if not isinstance(g, ops.OccupancyGrid):
+        raise ValueError(f"{what}: the map must be an ops.OccupancyGrid, an ops.SpaceMap or an ops.EvidenceMap, got {type(grid_or_map).__name__}")
+    return g
+
+
+def _voxel_rows(grid, voxel):
+    """Linear voxel indices (any shape; negative: no voxel) -> (ijk (..., 3) int32, -1 where there is none; centres (..., 3) f32 by
+    export()'s rule fl(origin + fl(fl(i + 0.5) r)), NaN where there is none)."""
+    nx, ny, _ = grid.dims
+    has = (voxel >= 0).unsqueeze(-1)
+    v = voxel.clamp(min=0)
+    ijk = torch.stack([v % nx, (v // nx) % ny, v // (nx * ny)], dim=-1)
+    o = torch.from_numpy(np.asarray(grid.origin, dtype=np.float32)).to(voxel.device)
+    r = torch.tensor(grid.resolution, dtype=torch.float32, device=voxel.device)
+    centres = o + (ijk.to(torch.float32) + 0.5) * r
+    return torch.where(has, ijk, torch.full_like(ijk, -1)), torch.where(has, centres, torch.full_like(centres, float("nan")))
+
+
+def cast_rays(grid_or_map, a, b, skip=(1, 0)):
+    """Where does each segment a[i] -> b[i] stop in the map?  a, b (R,3) world points on the map's device -> RayHits (DESIGN.md 10,
+    "Ray casts and depth scans").  The walk and the tests are line_of_sight's: a ray is clear here exactly where line_of_sight(a, b,
+    skip) says 1.  With the default skip (1, 0) a's own voxel and b's voxel are not tested.  grid_or_map: an ops.OccupancyGrid, or
+    an ops.SpaceMap / ops.EvidenceMap (its occupied plane).  Hits are reported at voxel granularity."""
+    grid = _scanned_grid("cast_rays", grid_or_map)
+    voxel, lam = grid.cast(a, b, skip)
+    ijk, centres = _voxel_rows(grid, voxel)
+    far = b.detach().to(device=grid.device, dtype=torch.float32)
+    points = torch.where((voxel == -1).unsqueeze(-1), far, centres)
+    return RayHits(voxel=voxel, ijk=ijk, lam=lam, points=points)
+
+
+class DepthScan(_Result):
+    """What depth_scan returns, on the device, each image indexed [view][row][column]: depth (V,H,W) f32 (the z-depth at which the
+    ray enters the hit voxel, +inf without a return, NaN where skipped), voxel (V,H,W) int32 (the hit's linear index, -1, -2),
+    flags (V,H,W) uint8 (0 a return, 1 no return within max_dist, 2 skipped: the pose or the far point out of range, 3 blocked
+    nearer than min_dist), points (V,H,W,3) f32 or None (flag 0: the hit voxel's centre, flag 1: the far point, else NaN), grid (the
+    scanned ops.OccupancyGrid).  far and visible() are computed when asked for."""
+    __slots__ = ("depth", "voxel", "flags", "points", "grid", "_rays", "_far")
+
+    @property
+    def far(self):
+        """(V,H,W,3) f32: every pixel's far point B at z-depth max_dist, with the kernel's own operations in its order (the pixel
+        directions and the normalised quaternions come from the host, V x 4 and W + H numbers: one synchronisation)."""
+        if self._far is None:
+            poses, quats, K, D = self._rays
+            f32 = np.float32
+            V, H, W = self.depth.shape
+            dev = self.depth.device
+            q = quats.detach().cpu().numpy().astype(f32)
+            ss = q[:, 0] * q[:, 0]
+            for a in (1, 2, 3):
+                ss = ss + q[:, a] * q[:, a]
+            nn = np.maximum(np.sqrt(ss), f32(1e-12)).astype(f32)
+            q = torch.from_numpy((q / nn[:, None]).astype(f32)).to(dev)
+            bx = torch.from_numpy((((np.arange(W).astype(f32) - K[2]) / K[0]).astype(f32) * D).astype(f32)).to(dev).view(1, 1, W)
+            by = torch.from_numpy((((np.arange(H).astype(f32) - K[5]) / K[4]).astype(f32) * D).astype(f32)).to(dev).view(1, H, 1)
+            bz = torch.full((1, 1, 1), float(D), dtype=torch.float32, device=dev)
+            bw = torch.zeros((1, 1, 1), dtype=torch.float32, device=dev)
+            aw, ax, ay, az = (q[:, i].view(V, 1, 1) for i in range(4))
+            cw, cx, cy, cz = aw, -ax, -ay, -az
+            ow = aw * bw - ax * bx - ay * by - az * bz
+            ox = aw * bx + ax * bw + ay * bz - az * by
+            oy = aw * by - ax * bz + ay * bw + az * bx
+            oz = aw * bz + ax * by - ay * bx + az * bw
+            r = (ow * cx + ox * cw + oy * cz - oz * cy, ow * cy - ox * cz + oy * cw + oz * cx, ow * cz + ox * cy - oy * cx + oz * cw)
+            t = poses.detach().to(device=dev, dtype=torch.float32)
+            self._far = torch.stack([(r[a] + t[:, a].view(V, 1, 1)).expand(V, H, W) for a in range(3)], dim=-1).contiguous()
+        return self._far
+
+    def visible(self):
+        """The visible surface of the map as a cloud -> (ijk (F,3) int32, centres (F,3) f32): the hit voxels of the flag-0 pixels,
+        each once, in brick order — a hit plane of the scan's own, listed by export().  The cloud to give ModelTraj, propose_views or
+        select_views as "points".  One synchronisation (F)."""
+        g = self.grid
+        plane = g.empty_like()
+        v = torch.unique(self.voxel[self.flags == 0].long())
+        nx, ny, _ = g.dims
+        x, y, z = v % nx, (v // nx) % ny, v // (nx * ny)
+        nbx, nby = (nx + 3) // 4, (ny + 3) // 4
+        word = ((z >> 1) * nby + (y >> 2)) * nbx + (x >> 2)
+        bit = (x & 3) | ((y & 3) << 2) | ((z & 1) << 4)
+        # distinct voxels are distinct bits: per byte of the plane their sum is their OR
+        acc = torch.zeros(plane.buf.numel() - 256, dtype=torch.int32, device=g.device)
+        acc.index_add_(0, word * 4 + (bit >> 3), (1 << (bit & 7)).to(torch.int32))
+        plane.buf[256:] = acc.to(torch.uint8)
+        return plane.export()
+
+
+def depth_scan(grid_or_map, poses, quats, into=None, points=False, **camera):
+    """What would a depth sensor at these poses return?  Per view poses[w] (V,3) / quats[w] (V,4) wxyz and per pixel, the ray through
+    the pixel is cast through the map's occupied voxels up to z-depth max_dist ("Ray casts and depth scans")
+    -> DepthScan.  grid_or_map: an ops.OccupancyGrid, or an ops.SpaceMap / ops.EvidenceMap (its occupied plane): a ground-truth grid
+    makes this a simulated sensor, the robot's own map the measurement it expects.  Keywords: intrins, img_width, img_height[,
+    min_dist = 1, max_dist = 5], as view_volume takes them; intrins must be (fx 0 cx; 0 fy cy; 0 0 1).
+
+    into: a DIFFERENT map of the scanned grid's geometry that receives the scan — an ops.SpaceMap has its occupied plane marked with
+    the hit voxels and its free plane with the voxels the rays passed, directly by the kernel; an ops.EvidenceMap has its scratch
+    planes marked and then takes one fold: one call is one scan, however many views.  points=True also returns the per-pixel
+    points.  Hits are reported at voxel granularity (voxel centres); there is no beam divergence and no noise."""
+    grid = _scanned_grid("depth_scan", grid_or_map)
+    allowed = {"intrins", "img_width", "img_height", "min_dist", "max_dist"}
+    if set(camera) - allowed:
+        raise ValueError(f"depth_scan: unknown keyword(s) {sorted(set(camera) - allowed)}")
+    missing = [k for k in ("intrins", "img_width", "img_height") if k not in camera]
+    if missing:
+        raise ValueError(f"depth_scan: the camera is needed: {missing} missing")
+    mn, mx = camera.get("min_dist", 1.0), camera.get("max_dist", 5.0)
+    hit = free = None
+    if into is not None:
+        if not isinstance(into, (ops.SpaceMap, ops.EvidenceMap)):
+            raise ValueError(f"depth_scan: into must be an ops.SpaceMap or an ops.EvidenceMap, got {type(into).__name__}")
+        target = into._scan if isinstance(into, ops.EvidenceMap) else into
+        hit, free = target.occupied, target.free
+        if into is grid_or_map or any(p is grid for p in (into.occupied, into.free, hit, free)):
+            raise ValueError("depth_scan: into must be a different map from the one that is scanned")
+    ops.check_depth_scan(grid, poses, quats, camera["intrins"], camera["img_width"], camera["img_height"], mn, mx, hit, free)
+    cam = ops.Camera(camera["intrins"], camera["img_width"], camera["img_height"], mn, mx)
+    voxel, depth, flags, pts = ops.depth_scan(grid, poses, quats, cam, mn, mx, hit, free, points)
+    if isinstance(into, ops.EvidenceMap):
+        into._fold(hit, free, True)
+    K = np.asarray(list(cam.c.K), dtype=np.float32)
+    return DepthScan(depth=depth, voxel=voxel, flags=flags, points=pts, grid=grid, _rays=(poses, quats, K, np.float32(mx)), _far=None)
 
 
 def _clearance_cloud(points_or_cloud_or_model, what, field=False):
