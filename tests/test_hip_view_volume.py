@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from scan_size_cases import composition_oracle as _oracle   # (the composition, shared with tests/test_hip_scan_at_size.py)
+
 from trajectory_optimization_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -77,25 +79,6 @@ def _views(dims, M, seed=1):
 def _cam(limits):
     from trajectory_optimization_amd import ops
     return ops.Camera(K, IW, IH, *limits)
-
-
-def _oracle(space, P, Q, limits, dev):
-    """The composition -> (revealed masks (M, nx,ny,nz) bool on the device, kept counts list, unknown count)."""
-    from trajectory_optimization_amd import ops, tools
-    ijk, centres = space.unknown().export()
-    M = len(P)
-    masks = torch.zeros((M,) + tuple(space.occupied.dims), dtype=torch.bool, device=dev)
-    if not len(ijk):
-        return masks, [0] * M, 0
-    p, q = _t(P, dev), _t(Q, dev)
-    kept_idx, _, counts, _ = ops.cull_waypoints(centres, p, q, _cam(limits), limits[0], limits[1], normalize=True)
-    for w in range(M):
-        rows = kept_idx[w, :counts[w]].long()
-        c = centres[rows]
-        see = tools.line_of_sight(space.occupied, p[w].expand_as(c).contiguous(), c, skip=(1, 0)) == 1
-        v = ijk[rows][see].long()
-        masks[w, v[:, 0], v[:, 1], v[:, 2]] = True
-    return masks, counts, len(ijk)
 
 
 def _count(masks):
