@@ -41,7 +41,10 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_cast_segments / tohip_depth_scan (where a ray through the map stops: first hits of segments and the depth image a
+/* (still 15) + tohip_travel_bytes / tohip_travel_workspace_bytes / tohip_travel_build / tohip_travel_positions / tohip_travel_paths /
+ * tohip_view_volume_pick_travel (a travel field: reachable space and path cost over the clearance field, and a view pick that prices
+ * the trip): new symbols only.
+ * (still 15) + tohip_cast_segments / tohip_depth_scan (where a ray through the map stops: first hits of segments and the depth image a
  * sensor at a pose would return): new symbols only.
  * (still 15) + tohip_occ_unknown / tohip_view_volume / tohip_view_volume_pick (the unknown volume a view would reveal, and the greedy
  * choice of views by it): new symbols only.
@@ -1357,6 +1360,51 @@ int tohip_cast_segments(const void *grid, size_t grid_bytes, const tohip_occ_geo
 int tohip_depth_scan(const void *grid, size_t grid_bytes, const tohip_occ_geom *geom, const float *poses, const float *quats,
                      int64_t n_views, const tohip_camera *cam, float min_dist, float max_dist, void *hit_plane, void *pass_plane,
                      int32_t *voxel, float *depth, uint8_t *flags, float *points, uint64_t *stats, void *stream);
+
+/* ---- the travel field (travel_kernels.hip, DESIGN.md §10, "Travel field") ------------------------------
+ * Can the robot get there, and how far is it?  A one-to-all shortest-path field over the voxels a clearance field certifies.
+ *
+ * TRAVERSABLE set T: the voxels inside dims with field >= need2 (1 <= need2 <= 65535; the sentinel counts) and — where the two planes
+ * of a map are given (both or neither, grid_bytes each) — of state 1: tohip_field_nodes' mask at stride 1.  A MOVE goes from v to a
+ * voxel u at Chebyshev distance 1 (26 neighbours) and is allowed iff every voxel w with min(v, u) <= w <= max(v, u) per axis (2, 4 or
+ * 8 voxels) is in T: no corner is cut, and the straight leg between the two centres stays inside certified cubes.  Weights, in 1/64
+ * voxel edge: 64 (face), 91 (edge), 111 (corner).  sources (n_sources >= 1 rows of 3 f32 on the device): a source is SEEDED at cost 0
+ * iff its position is in range, its voxel lies inside dims and in T; any other is ignored — no snapping — and seeded (DEVICE uint8 x
+ * n_sources, may be NULL) tells which.  cost[v] = the length of the shortest allowed path from any seeded source to v where that is
+ * <= limit (0 <= limit <= 2^31 - 1: no sum overflows 32 bits), else 0xFFFFFFFF; every stored value is the exact untruncated distance.
+ * Layout: one uint32 per voxel inside dims, dense, x fastest, index (z ny + y) nx + x: tohip_travel_bytes(nx, ny, nz) = 4 nx ny nz
+ * device bytes (0 for bad dims), caller-owned.  The answer is the unique fixed point of cost[s] = 0, cost[v] = min over the allowed u
+ * of cost[u] + w(u, v): it does not depend on the order of the relaxation — the same bits in every run.
+ *
+ * tohip_travel_build: fills cost and relaxes it over a worklist of 8 x 8 x 8-voxel tiles in workspace
+ * (tohip_travel_workspace_bytes device bytes, 256-byte aligned), two launches per round.  It enqueues rounds_per_check rounds (1 ..
+ * 65536), SYNCHRONISES to read one word back — "did the last round have a tile to work on" — and repeats until it had none; rounds
+ * after convergence do nothing.  *rounds_host (HOST, may be NULL): the rounds that had work.  cost, workspace and the inputs must all
+ * differ.
+ * tohip_travel_positions: positions (m, 3) f32 -> cost_out (m) int64: the voxel's cost, -1 unreachable, -2 out of range or outside
+ * dims — and / or dist (m) f32 metres fl(fl((float) cost (1/64)) r), +inf for -1, NaN for -2; either may be NULL, not both.
+ * tohip_travel_paths: goal e (n_goals rows of 3 f32) -> rows + 3 max_rows e: the voxel centres fl(origin + fl(fl(i + 0.5) r)) from the
+ * goal's voxel to a source, and counts[e] (int64) their number; 0 for a goal that is unreachable, out of range or outside dims;
+ * -needed where the path has more than max_rows rows (the first max_rows are written).  PATH RULE: the predecessor of a reachable
+ * voxel v with cost[v] > 0 is the allowed neighbour u with cost[u] + w(u, v) == cost[v], the lowest move number (dz + 1) 9 + (dy + 1)
+ * 3 + (dx + 1) on ties; one exists in every built field.  field, the planes and need2 are the build's.  One launch.
+ * tohip_view_volume_pick_travel: tohip_view_volume_pick with a cost row (int64 x n_views: tohip_travel_positions' codes) and a weight
+ * 0 <= m < 2^31.  The candidates are those with taken == 0, gain >= min_gain and cost >= 0; gain 2^20 - m cost (int64) decides, ties
+ * to the lowest index; picked_gain[round] = the winner's gain.  *stop = 1 where no candidate is left.
+ * Every argument check returns before anything is enqueued. */
+size_t tohip_travel_bytes(int32_t nx, int32_t ny, int32_t nz);
+size_t tohip_travel_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int tohip_travel_build(const void *field, size_t field_bytes, const void *occupied_or_null, const void *free_or_null, size_t grid_bytes,
+                       const tohip_occ_geom *geom, int32_t need2, const float *sources, int64_t n_sources, int64_t limit,
+                       int32_t rounds_per_check, void *cost, size_t cost_bytes, void *workspace, size_t workspace_bytes, uint8_t *seeded,
+                       int64_t *rounds_host, void *stream);
+int tohip_travel_positions(const void *cost, size_t cost_bytes, const tohip_occ_geom *geom, const float *positions, int64_t m,
+                           int64_t *cost_out, float *dist, void *stream);
+int tohip_travel_paths(const void *cost, size_t cost_bytes, const void *field, size_t field_bytes, const void *occupied_or_null,
+                       const void *free_or_null, size_t grid_bytes, const tohip_occ_geom *geom, int32_t need2, const float *goals,
+                       int64_t n_goals, int64_t max_rows, float *rows, int64_t *counts, void *stream);
+int tohip_view_volume_pick_travel(const int64_t *gains, const int64_t *cost, int64_t weight, int32_t *taken, int64_t n_views,
+                                  int64_t min_gain, int32_t round, int32_t *order, int64_t *picked_gain, int32_t *stop, void *stream);
 
 /* ---- optional per-kernel timing (bench.py's roofline leg) -----------------------------------------
  * When enabled, every launch of the big kernels is bracketed by hipEventRecord on its own stream.

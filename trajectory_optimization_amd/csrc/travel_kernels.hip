@@ -1,0 +1,466 @@
+// travel_kernels.hip — a travel field over the clearance field ("Travel field"), for gfx950.  Included after
+// field_kernels.hip (behind evidence_kernels.hip): the geometry, occ_locate, the brick layout and field_index are that file's and
+// frontier_kernels.hip's.
+//
+// The TRAVERSABLE set T: the voxels inside dims with field >= need2 and, with a map's two planes, state 1 — tohip_field_nodes' mask
+// at stride 1.  A MOVE goes from v to one of its 26 neighbours u and is allowed iff every voxel of the box spanned by v and u (2, 4
+// or 8 voxels) is in T: no corner is cut.  Weights in 1/64 voxel edge: 64 (face), 91 (edge), 111 (corner).  cost[v] (uint32, one
+// word per voxel inside dims, x fastest) = the length of the shortest allowed path from a seeded source, 0xFFFFFFFF where there is
+// none of length <= limit (limit < 2^31: no sum overflows).  The answer is the unique fixed point of cost[s] = 0, cost[v] = min
+// over the allowed u of cost[u] + w: it does not depend on the order of the relaxation, so every schedule below gives the same bits.
+//
+//   k_travel_fill     every word of cost <- the sentinel (grid-stride, 64-bit index).
+//   k_travel_seed     one lane per source: a position in range whose voxel lies inside dims and in T gets cost 0, seeded[i] = 1 and
+//                     its tile's bit in bitmap 0; any other source is ignored, seeded[i] = 0.
+//   k_travel_compact  one lane per word of the round's bitmap: the set bits become entries of the tile list (an integer atomic add
+//                     per word reserves their places; the order of the list is of no consequence), the word is cleared.
+//   k_travel_relax    one block per listed tile of 8 x 8 x 8 voxels (a block strides over the list), two voxels per lane.  The
+//                     tile and a one-voxel halo of costs (10^3 words) and of T (10^3 bytes) go to LDS, each voxel's 26-bit mask of
+//                     allowed moves is derived once, and the block relaxes in place in LDS until a whole sweep changes nothing
+//                     (__syncthreads_or): a word has one writer, values only fall and every value ever stored is the length of a
+//                     real path, so a read that races with a write sees an upper bound either way.  Only the tile's own voxels
+//                     that fell are written back; for each of the 26 neighbouring tiles the block sets that tile's bit in the NEXT
+//                     round's bitmap iff it lowered a voxel of the layer that touches it.  A halo word read while its owner
+//                     writes it is old or new — both upper bounds — and the owner's lowering re-activates the reader.
+//   k_travel_positions (M,3) f32 positions -> int64 cost (-1 unreachable, -2 out of range or outside dims) and / or f32 metres.
+//   k_travel_paths    one wave per goal: lanes 0 .. 26 (13 idle) each test one move against the path rule — allowed, and cost[u] +
+//                     w == cost[v] — and a ballot names the lowest; rows are the voxel centres from the goal to its source.
+//   k_view_volume_pick_travel   k_view_volume_pick with a cost row: gain 2^20 - m cost decides, among the reachable candidates.
+//
+// Every kernel ends on its own: no block waits for another.  No float atomics, no process-wide state; every argument check returns
+// before anything is enqueued.
+namespace {
+
+constexpr unsigned kTravelSentinel = 0xFFFFFFFFu;
+constexpr unsigned kTravelInf = 0xFFFFFF00u;          // "no path" inside LDS: + 111 does not wrap, and exceeds every limit
+constexpr long long kTravelMaxLimit = 0x7fffffffll;
+constexpr int kTravelTile = 8;                        // voxels per tile edge
+constexpr int kTravelHalo = kTravelTile + 2;
+constexpr int kTravelHaloN = kTravelHalo * kTravelHalo * kTravelHalo;
+constexpr int kTravelRelaxBlocks = 4096;              // blocks of a relax launch: they stride over the list
+constexpr size_t kTravelHdr = 256;                    // [0] u64 status = rounds with work << 32 | tiles of the last round;
+                                                      // [2], [3] u32 the two rounds' list counts; [4] u32 rounds with work
+constexpr int kTravelMaxRoundsPerCheck = 65536;
+
+struct TravelTiles { long long ntx, nty, ntz, n, words; };
+inline TravelTiles travel_tiles(int64_t nx, int64_t ny, int64_t nz) {
+    TravelTiles t;
+    t.ntx = (nx + kTravelTile - 1) / kTravelTile, t.nty = (ny + kTravelTile - 1) / kTravelTile, t.ntz = (nz + kTravelTile - 1) / kTravelTile;
+    t.n = t.ntx * t.nty * t.ntz;
+    t.words = (t.n + 31) / 32;
+    return t;
+}
+inline size_t travel_align(size_t b) { return (b + 255) & ~(size_t)255; }
+inline size_t travel_bitmap_bytes(const TravelTiles& t) { return travel_align((size_t)t.words * 4); }
+
+// what decides T, in one argument
+struct TravelSet {
+    const uint16_t* field;
+    const unsigned* occ;   // both planes or neither
+    const unsigned* fre;
+    OccGeom g;
+    int need2;
+};
+
+__device__ __forceinline__ bool travel_in_set(const TravelSet& s, int x, int y, int z) {
+    if (!occ_inside(s.g, x, y, z)) return false;
+    if ((int)s.field[field_index(s.g, x, y, z)] < s.need2) return false;
+    if (s.occ) {
+        const int w = occ_word(s.g, x, y, z), b = occ_bit(x, y, z);
+        if (!(((s.fre[w] & ~s.occ[w]) >> b) & 1u)) return false;   // state 1
+    }
+    return true;
+}
+
+// move m = (dz + 1) 9 + (dy + 1) 3 + (dx + 1), m != 13
+__device__ __forceinline__ constexpr int travel_dx(int m) { return m % 3 - 1; }
+__device__ __forceinline__ constexpr int travel_dy(int m) { return (m / 3) % 3 - 1; }
+__device__ __forceinline__ constexpr int travel_dz(int m) { return m / 9 - 1; }
+__device__ __forceinline__ constexpr unsigned travel_weight(int m) {
+    const int k = (travel_dx(m) != 0) + (travel_dy(m) != 0) + (travel_dz(m) != 0);
+    return k == 1 ? 64u : (k == 2 ? 91u : 111u);
+}
+// the bits of a 27-voxel neighbourhood mask (bit = the move's number, 13 the voxel itself) that move m needs: its box
+__device__ __forceinline__ constexpr unsigned travel_box(int m) {
+    unsigned need = 0u;
+    for (int i = 0; i < 8; ++i) {
+        const int ex = (i & 1) ? travel_dx(m) : 0, ey = (i & 2) ? travel_dy(m) : 0, ez = (i & 4) ? travel_dz(m) : 0;
+        need |= 1u << ((ez + 1) * 9 + (ey + 1) * 3 + (ex + 1));
+    }
+    return need;
+}
+
+__device__ __forceinline__ float travel_centre(float o, int i, float r) { return __fadd_rn(o, __fmul_rn((float)i + 0.5f, r)); }
+
+__global__ void __launch_bounds__(TO_BLOCK) k_travel_fill(unsigned* __restrict__ cost, long long n_vox) {
+    const long long stride = (long long)gridDim.x * TO_BLOCK;
+    for (long long i = (long long)blockIdx.x * TO_BLOCK + threadIdx.x; i < n_vox; i += stride) cost[i] = kTravelSentinel;
+}
+
+__global__ void __launch_bounds__(TO_BLOCK)
+k_travel_seed(TravelSet s, const float* __restrict__ src, long long n_src, unsigned* __restrict__ cost, unsigned* __restrict__ bitmap,
+              long long ntx, long long nty, uint8_t* __restrict__ seeded) {
+    const long long stride = (long long)gridDim.x * TO_BLOCK;
+    for (long long i = (long long)blockIdx.x * TO_BLOCK + threadIdx.x; i < n_src; i += stride) {
+        int x, y, z;
+        const bool ok = occ_locate(s.g, src + 3 * i, x, y, z) == kOccInside && travel_in_set(s, x, y, z);
+        if (ok) {
+            cost[field_index(s.g, x, y, z)] = 0u;   // (two sources in one voxel store the same word)
+            const long long t = ((long long)(z >> 3) * nty + (y >> 3)) * ntx + (x >> 3);
+            __hip_atomic_fetch_or(bitmap + (t >> 5), 1u << (t & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (seeded) seeded[i] = ok ? 1 : 0;
+    }
+}
+
+// the set bits of the round's bitmap -> list[0 .. *count), the bitmap cleared.  *count is zero when the launch begins.
+__global__ void __launch_bounds__(TO_BLOCK)
+k_travel_compact(unsigned* __restrict__ bitmap, long long words, int* __restrict__ list, unsigned* __restrict__ count) {
+    const long long w = (long long)blockIdx.x * TO_BLOCK + threadIdx.x;
+    if (w >= words) return;
+    unsigned bits = bitmap[w];
+    if (bits == 0u) return;
+    bitmap[w] = 0u;
+    unsigned at = __hip_atomic_fetch_add(count, (unsigned)__popc(bits), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    while (bits != 0u) {
+        const int b = __ffs(bits) - 1;
+        bits &= bits - 1u;
+        list[at++] = (int)(w * 32 + b);   // (at most 2^22 tiles)
+    }
+}
+
+__global__ void __launch_bounds__(TO_BLOCK)
+k_travel_relax(TravelSet s, unsigned* cost, unsigned limit, const int* __restrict__ list, unsigned* __restrict__ hdr32, int parity,
+               unsigned* __restrict__ next, int ntx, int nty, int ntz) {
+    __shared__ unsigned s_cost[kTravelHaloN];
+    __shared__ unsigned char s_in[kTravelHaloN];
+    __shared__ unsigned s_touch;
+    const unsigned count = hdr32[2 + parity];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        // the bookkeeping of the round: the other round's count starts from zero, and the status word the host reads
+        hdr32[2 + (parity ^ 1)] = 0u;
+        const unsigned rounds = hdr32[4] + (count != 0u ? 1u : 0u);
+        hdr32[4] = rounds;
+        hdr32[0] = count;
+        hdr32[1] = rounds;
+    }
+    const OccGeom& g = s.g;
+    for (unsigned item = blockIdx.x; item < count; item += gridDim.x) {
+        const int t = list[item];
+        const int tx = t % ntx, ty = (t / ntx) % nty, tz = t / (ntx * nty);
+        const int x0 = tx * kTravelTile - 1, y0 = ty * kTravelTile - 1, z0 = tz * kTravelTile - 1;   // the halo's corner
+        if (threadIdx.x == 0) s_touch = 0u;
+        for (int i = threadIdx.x; i < kTravelHaloN; i += TO_BLOCK) {
+            const int x = x0 + i % kTravelHalo, y = y0 + (i / kTravelHalo) % kTravelHalo, z = z0 + i / (kTravelHalo * kTravelHalo);
+            const bool in = travel_in_set(s, x, y, z);
+            unsigned c = kTravelInf;
+            if (in) {
+                c = cost[field_index(g, x, y, z)];
+                if (c > limit) c = kTravelInf;   // (the sentinel)
+            }
+            s_cost[i] = c;
+            s_in[i] = in ? 1 : 0;
+        }
+        __syncthreads();
+        // this lane's two voxels: their place in the halo block, the moves they may make, the value they came with
+        int at[2];
+        unsigned allowed[2], first[2], mine[2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int l = threadIdx.x + k * TO_BLOCK;
+            at[k] = (((l >> 6) + 1) * kTravelHalo + ((l >> 3) & 7) + 1) * kTravelHalo + (l & 7) + 1;
+            unsigned around = 0u;
+#pragma unroll
+            for (int m = 0; m < 27; ++m)
+                around |= (unsigned)s_in[at[k] + (travel_dz(m) * kTravelHalo + travel_dy(m)) * kTravelHalo + travel_dx(m)] << m;
+            unsigned ok = 0u;
+            if ((around >> 13) & 1u) {
+#pragma unroll
+                for (int m = 0; m < 27; ++m)
+                    if (m != 13 && (around & travel_box(m)) == travel_box(m)) ok |= 1u << m;
+            }
+            allowed[k] = ok;
+            first[k] = mine[k] = s_cost[at[k]];
+        }
+        bool changed;
+        do {
+            changed = false;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                if (allowed[k] == 0u) continue;
+                unsigned best = mine[k];
+#pragma unroll
+                for (int m = 0; m < 27; ++m) {
+                    if (m == 13) continue;
+                    const unsigned c = s_cost[at[k] + (travel_dz(m) * kTravelHalo + travel_dy(m)) * kTravelHalo + travel_dx(m)] + travel_weight(m);
+                    if (((allowed[k] >> m) & 1u) && c < best) best = c;
+                }
+                if (best < mine[k] && best <= limit) {
+                    mine[k] = best;
+                    s_cost[at[k]] = best;
+                    changed = true;
+                }
+            }
+        } while (__syncthreads_or(changed));
+        // what fell goes back, and names the neighbouring tiles whose halo it lies in
+        unsigned touch = 0u;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            if (mine[k] >= first[k]) continue;
+            const int l = threadIdx.x + k * TO_BLOCK;
+            const int lx = l & 7, ly = (l >> 3) & 7, lz = l >> 6;
+            cost[field_index(g, x0 + 1 + lx, y0 + 1 + ly, z0 + 1 + lz)] = mine[k];   // (in T: inside dims)
+            const int ax = lx == 0 ? -1 : (lx == 7 ? 1 : 0), ay = ly == 0 ? -1 : (ly == 7 ? 1 : 0), az = lz == 0 ? -1 : (lz == 7 ? 1 : 0);
+#pragma unroll
+            for (int i = 1; i < 8; ++i) {
+                const int ex = (i & 1) ? ax : 0, ey = (i & 2) ? ay : 0, ez = (i & 4) ? az : 0;
+                if (((i & 1) && ax == 0) || ((i & 2) && ay == 0) || ((i & 4) && az == 0)) continue;
+                touch |= 1u << ((ez + 1) * 9 + (ey + 1) * 3 + (ex + 1));
+            }
+        }
+        for (int sh = 32; sh > 0; sh >>= 1) touch |= __shfl_xor(touch, sh);
+        if ((threadIdx.x & 63) == 0 && touch != 0u) atomicOr(&s_touch, touch);
+        __syncthreads();
+        if (threadIdx.x < 27 && threadIdx.x != 13 && ((s_touch >> threadIdx.x) & 1u)) {
+            const int ux = tx + travel_dx(threadIdx.x), uy = ty + travel_dy(threadIdx.x), uz = tz + travel_dz(threadIdx.x);
+            if ((unsigned)ux < (unsigned)ntx && (unsigned)uy < (unsigned)nty && (unsigned)uz < (unsigned)ntz) {
+                const int u = (uz * nty + uy) * ntx + ux;
+                __hip_atomic_fetch_or(next + (u >> 5), 1u << (u & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        __syncthreads();   // (s_touch and the halo block are the next item's)
+    }
+}
+
+// metres of a cost: fl(fl((float) cost (1/64)) r); +inf unreachable, NaN for -2
+__device__ __forceinline__ float travel_metres(long long c, float r) {
+    if (c == -2) return __builtin_nanf("");
+    if (c < 0) return __builtin_inff();
+    return __fmul_rn(__fmul_rn((float)c, 0.015625f), r);
+}
+
+__global__ void __launch_bounds__(TO_BLOCK)
+k_travel_positions(const unsigned* __restrict__ cost, OccGeom g, const float* __restrict__ pos, long long m, long long* __restrict__ cost_out,
+                   float* __restrict__ dist_out) {
+    const long long stride = (long long)gridDim.x * TO_BLOCK;
+    for (long long i = (long long)blockIdx.x * TO_BLOCK + threadIdx.x; i < m; i += stride) {
+        int x, y, z;
+        long long c = -2;
+        if (occ_locate(g, pos + 3 * i, x, y, z) == kOccInside) {
+            const unsigned v = cost[field_index(g, x, y, z)];
+            c = v == kTravelSentinel ? -1 : (long long)v;
+        }
+        if (cost_out) cost_out[i] = c;
+        if (dist_out) dist_out[i] = travel_metres(c, g.r);
+    }
+}
+
+// one wave per goal; rows (n_goals, max_rows, 3): the voxel centres goal -> source; counts: rows, 0 unreachable (or the goal out of
+// range or outside dims), -needed where the path does not fit
+__global__ void __launch_bounds__(TO_BLOCK)
+k_travel_paths(TravelSet s, const unsigned* __restrict__ cost, const float* __restrict__ goals, long long n_goals, long long max_rows,
+               float* __restrict__ rows, long long* __restrict__ counts) {
+    const int lane = threadIdx.x & 63;
+    const long long goal = (long long)blockIdx.x * (TO_BLOCK / 64) + (threadIdx.x >> 6);
+    if (goal >= n_goals) return;   // (a whole wave)
+    const OccGeom& g = s.g;
+    int x, y, z;
+    long long n = 0;
+    if (occ_locate(g, goals + 3 * goal, x, y, z) == kOccInside) {
+        unsigned here = cost[field_index(g, x, y, z)];
+        if (here != kTravelSentinel) {
+            float* out = rows + goal * max_rows * 3;
+            const int dx = lane < 27 ? travel_dx(lane) : 0, dy = lane < 27 ? travel_dy(lane) : 0, dz = lane < 27 ? travel_dz(lane) : 0;
+            const unsigned w = lane < 27 ? travel_weight(lane) : 0u;
+            for (;;) {
+                if (lane == 0 && n < max_rows) {
+                    out[3 * n] = travel_centre(g.ox, x, g.r);
+                    out[3 * n + 1] = travel_centre(g.oy, y, g.r);
+                    out[3 * n + 2] = travel_centre(g.oz, z, g.r);
+                }
+                ++n;
+                if (here == 0u) break;   // a source
+                bool take = false;
+                unsigned there = 0u;
+                if (lane < 27 && lane != 13 && occ_inside(g, x + dx, y + dy, z + dz)) {
+                    there = cost[field_index(g, x + dx, y + dy, z + dz)];
+                    if (there != kTravelSentinel && there + w == here) {
+                        take = true;
+                        for (int i = 1; i < 8 && take; ++i) {   // the box of the move (its far corner holds a cost: it is in T)
+                            if (((i & 1) && dx == 0) || ((i & 2) && dy == 0) || ((i & 4) && dz == 0)) continue;
+                            take = travel_in_set(s, x + ((i & 1) ? dx : 0), y + ((i & 2) ? dy : 0), z + ((i & 4) ? dz : 0));
+                        }
+                    }
+                }
+                const unsigned long long votes = __ballot(take);
+                if (votes == 0ull) { n = 0; break; }   // (not a built field: no predecessor)
+                const int m = __ffsll((long long)votes) - 1;
+                x += travel_dx(m), y += travel_dy(m), z += travel_dz(m);
+                here = __shfl(there, m);
+            }
+        }
+    }
+    if (lane == 0) counts[goal] = n > max_rows ? -n : n;
+}
+
+// round `round` of a greedy selection that prices the trip: gain 2^20 - m cost decides among the candidates not taken with gain >=
+// min_gain and cost >= 0; the lowest index on ties
+__global__ void __launch_bounds__(TO_BLOCK)
+k_view_volume_pick_travel(const long long* __restrict__ gains, const long long* __restrict__ cost, long long weight, int* __restrict__ taken,
+                          long long n, long long min_gain, int round, int* __restrict__ order, long long* __restrict__ picked_gain,
+                          int* __restrict__ stop) {
+    __shared__ long long s_score[TO_BLOCK];
+    __shared__ long long s_idx[TO_BLOCK];
+    if (*stop != 0) return;   // (uniform)
+    long long best = 0, at = -1;
+    for (long long i = threadIdx.x; i < n; i += TO_BLOCK) {   // (ascending: the first of equal scores stays)
+        if (taken[i] || gains[i] < min_gain || cost[i] < 0) continue;
+        const long long sc = gains[i] * (1ll << 20) - weight * cost[i];
+        if (at < 0 || sc > best) { best = sc; at = i; }
+    }
+    s_score[threadIdx.x] = best;
+    s_idx[threadIdx.x] = at;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < TO_BLOCK; ++k) {
+            if (s_idx[k] < 0) continue;
+            if (at < 0 || s_score[k] > best || (s_score[k] == best && s_idx[k] < at)) { best = s_score[k]; at = s_idx[k]; }
+        }
+        if (at < 0) {
+            *stop = 1;
+        } else {
+            order[round] = (int)at;
+            picked_gain[round] = gains[at];
+            taken[at] = 1;
+        }
+    }
+}
+
+inline size_t travel_cost_bytes(const OccGeom& g) { return field_voxels(g) * sizeof(uint32_t); }
+
+// the field, the planes and the geometry of a call -> its TravelSet (argument checks only)
+inline int travel_set(const void* field, size_t field_bytes, const void* occupied_or_null, const void* free_or_null, size_t grid_bytes,
+                      const tohip_occ_geom* geom, int32_t need2, TravelSet& s) {
+    OccGeom g;
+    int rc = field_check(field, field_bytes, geom, g);
+    if (rc != TOHIP_OK) return rc;
+    if ((occupied_or_null == nullptr) != (free_or_null == nullptr) || need2 < 1 || need2 > kFieldSentinel) return TOHIP_EINVAL;
+    if (occupied_or_null) {
+        if (occupied_or_null == free_or_null) return TOHIP_EINVAL;
+        rc = occ_check(occupied_or_null, grid_bytes, geom, g);
+        if (rc != TOHIP_OK) return rc;
+    }
+    s.field = (const uint16_t*)field;
+    s.occ = occupied_or_null ? occ_data(occupied_or_null) : nullptr;
+    s.fre = free_or_null ? occ_data(free_or_null) : nullptr;
+    s.g = g;
+    s.need2 = need2;
+    return TOHIP_OK;
+}
+
+}  // namespace
+
+extern "C" size_t tohip_travel_bytes(int32_t nx, int32_t ny, int32_t nz) {
+    return occ_dims_ok(nx, ny, nz) ? field_voxels(nx, ny, nz) * sizeof(uint32_t) : 0;
+}
+
+extern "C" size_t tohip_travel_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) {
+    if (!occ_dims_ok(nx, ny, nz)) return 0;
+    const TravelTiles t = travel_tiles(nx, ny, nz);
+    return kTravelHdr + 2 * travel_bitmap_bytes(t) + travel_align((size_t)t.n * sizeof(int32_t));
+}
+
+extern "C" int tohip_travel_build(const void* field, size_t field_bytes, const void* occupied_or_null, const void* free_or_null,
+                                  size_t grid_bytes, const tohip_occ_geom* geom, int32_t need2, const float* sources, int64_t n_sources,
+                                  int64_t limit, int32_t rounds_per_check, void* cost, size_t cost_bytes, void* workspace,
+                                  size_t workspace_bytes, uint8_t* seeded, int64_t* rounds_host, void* stream_) {
+    TravelSet s;
+    const int rc = travel_set(field, field_bytes, occupied_or_null, free_or_null, grid_bytes, geom, need2, s);
+    if (rc != TOHIP_OK) return rc;
+    if (!sources || n_sources < 1 || !occ_count_ok(n_sources) || limit < 0 || limit > kTravelMaxLimit || rounds_per_check < 1 ||
+        rounds_per_check > kTravelMaxRoundsPerCheck || !cost || !workspace)
+        return TOHIP_EINVAL;
+    const void* ins[3] = {field, occupied_or_null, free_or_null};
+    for (const void* p : ins)
+        if (p && (p == cost || p == workspace)) return TOHIP_EINVAL;
+    if (cost == workspace) return TOHIP_EINVAL;
+    if (cost_bytes < travel_cost_bytes(s.g) || workspace_bytes < tohip_travel_workspace_bytes(s.g.nx, s.g.ny, s.g.nz)) return TOHIP_ENOSPC;
+    hipStream_t st = (hipStream_t)stream_;
+    const TravelTiles t = travel_tiles(s.g.nx, s.g.ny, s.g.nz);
+    const size_t bm = travel_bitmap_bytes(t);
+    unsigned* hdr32 = (unsigned*)workspace;
+    unsigned* bitmap[2] = {(unsigned*)((char*)workspace + kTravelHdr), (unsigned*)((char*)workspace + kTravelHdr + bm)};
+    int* list = (int*)((char*)workspace + kTravelHdr + 2 * bm);
+    unsigned* c = (unsigned*)cost;
+    hipError_t e = hipMemsetAsync(workspace, 0, kTravelHdr + 2 * bm, st);
+    if (e != hipSuccess) return (int)e;
+    const long long n_vox = (long long)field_voxels(s.g);
+    k_travel_fill<<<occ_grid_blocks(n_vox), TO_BLOCK, 0, st>>>(c, n_vox);
+    TO_HIP_CHECK_LAUNCH();
+    k_travel_seed<<<occ_grid_blocks(n_sources), TO_BLOCK, 0, st>>>(s, sources, n_sources, c, bitmap[0], t.ntx, t.nty, seeded);
+    TO_HIP_CHECK_LAUNCH();
+    const unsigned compact_blocks = (unsigned)((t.words + TO_BLOCK - 1) / TO_BLOCK);
+    const unsigned relax_blocks = (unsigned)(t.n < kTravelRelaxBlocks ? t.n : kTravelRelaxBlocks);
+    int parity = 0;
+    for (;;) {
+        for (int r = 0; r < rounds_per_check; ++r, parity ^= 1) {
+            k_travel_compact<<<compact_blocks, TO_BLOCK, 0, st>>>(bitmap[parity], t.words, list, hdr32 + 2 + parity);
+            TO_HIP_CHECK_LAUNCH();
+            k_travel_relax<<<relax_blocks, TO_BLOCK, 0, st>>>(s, c, (unsigned)limit, list, hdr32, parity, bitmap[parity ^ 1], (int)t.ntx,
+                                                              (int)t.nty, (int)t.ntz);
+            TO_HIP_CHECK_LAUNCH();
+        }
+        // one word back: the tiles the last round worked on (none: nothing was activated after it) and the rounds that had work
+        int64_t status = 0;
+        const int back = occ_read_back(&status, workspace, st);
+        if (back != TOHIP_OK) return back;
+        if ((uint32_t)status == 0u) {
+            if (rounds_host) *rounds_host = status >> 32;
+            return TOHIP_OK;
+        }
+    }
+}
+
+extern "C" int tohip_travel_positions(const void* cost, size_t cost_bytes, const tohip_occ_geom* geom, const float* positions, int64_t m,
+                                      int64_t* cost_out, float* dist, void* stream_) {
+    OccGeom g;
+    const int rc = occ_check(cost, ~(size_t)0, geom, g);
+    if (rc != TOHIP_OK) return rc;
+    if (cost_bytes < travel_cost_bytes(g)) return TOHIP_ENOSPC;
+    if (!occ_count_ok(m) || (m > 0 && (!positions || (!cost_out && !dist)))) return TOHIP_EINVAL;
+    if (m == 0) return TOHIP_OK;
+    k_travel_positions<<<occ_grid_blocks(m), TO_BLOCK, 0, (hipStream_t)stream_>>>((const unsigned*)cost, g, positions, m, (long long*)cost_out,
+                                                                                 dist);
+    TO_HIP_CHECK_LAUNCH();
+    return TOHIP_OK;
+}
+
+extern "C" int tohip_travel_paths(const void* cost, size_t cost_bytes, const void* field, size_t field_bytes, const void* occupied_or_null,
+                                  const void* free_or_null, size_t grid_bytes, const tohip_occ_geom* geom, int32_t need2, const float* goals,
+                                  int64_t n_goals, int64_t max_rows, float* rows, int64_t* counts, void* stream_) {
+    TravelSet s;
+    const int rc = travel_set(field, field_bytes, occupied_or_null, free_or_null, grid_bytes, geom, need2, s);
+    if (rc != TOHIP_OK) return rc;
+    if (!cost || n_goals < 0 || n_goals > (int64_t)1 << 30 || max_rows < 1 || max_rows > (int64_t)1 << 31 ||
+        (n_goals > 0 && (!goals || !rows || !counts)))
+        return TOHIP_EINVAL;
+    if (cost_bytes < travel_cost_bytes(s.g)) return TOHIP_ENOSPC;
+    if (n_goals == 0) return TOHIP_OK;
+    const unsigned blocks = (unsigned)((n_goals + TO_BLOCK / 64 - 1) / (TO_BLOCK / 64));
+    k_travel_paths<<<blocks, TO_BLOCK, 0, (hipStream_t)stream_>>>(s, (const unsigned*)cost, goals, n_goals, max_rows, rows, (long long*)counts);
+    TO_HIP_CHECK_LAUNCH();
+    return TOHIP_OK;
+}
+
+extern "C" int tohip_view_volume_pick_travel(const int64_t* gains, const int64_t* cost, int64_t weight, int32_t* taken, int64_t n_views,
+                                             int64_t min_gain, int32_t round, int32_t* order, int64_t* picked_gain, int32_t* stop,
+                                             void* stream_) {
+    if (!gains || !cost || !taken || !order || !picked_gain || !stop || n_views < 1 || n_views > (int64_t)0x7fffffff || min_gain < 1 ||
+        round < 0 || weight < 0 || weight > kTravelMaxLimit)
+        return TOHIP_EINVAL;
+    k_view_volume_pick_travel<<<1, TO_BLOCK, 0, (hipStream_t)stream_>>>((const long long*)gains, (const long long*)cost, (long long)weight, taken,
+                                                                        (long long)n_views, (long long)min_gain, round, order,
+                                                                        (long long*)picked_gain, stop);
+    TO_HIP_CHECK_LAUNCH();
+    return TOHIP_OK;
+}

@@ -1122,13 +1122,25 @@ def view_volume(space, poses, quats, cam, min_dist, max_dist, claimed=None, mark
     return gains
 
 
-def view_volume_select(space, poses, quats, cam, min_dist, max_dist, k, min_gain=1, claimed=None, window=True):
+def view_volume_select(space, poses, quats, cam, min_dist, max_dist, k, min_gain=1, claimed=None, window=True, travel_cost=None,
+                       travel_m=0):
     """Greedy selection by revealed volume, on the device: k rounds of (score every candidate against the plane of what is claimed so
     far, pick the largest gain — the lowest index on ties, stop where it is below min_gain — and set the winner's revealed voxels in
     that plane), 3 k launches and nothing read back; at most 65 535 candidates (one launch scores them all).  -> (order (k,) int32,
     -1 from the round that stopped; gains (k,) int64, the marginal gains; revealed: a new OccupancyGrid, the caller's `claimed` (not
-    modified) plus what the chosen views reveal), all on the device."""
+    modified) plus what the chosen views reveal), all on the device.
+
+    travel_cost (None: today's launches): an (M,) int64 device row of TravelField.cost codes, one per candidate, and travel_m an
+    integer in [0, 2^31): the pick becomes tohip_view_volume_pick_travel — only candidates with cost >= 0 and gain >= min_gain can win,
+    and gain 2^20 - travel_m cost decides."""
     M, k, min_gain = check_view_volume(space, poses, quats, k, min_gain, claimed)
+    if travel_cost is not None:
+        if not torch.is_tensor(travel_cost) or travel_cost.dtype != torch.int64 or tuple(travel_cost.shape) != (M,):
+            raise ValueError(f"travel_cost must be an ({M},) int64 tensor, got "
+                             f"{(tuple(travel_cost.shape), travel_cost.dtype) if torch.is_tensor(travel_cost) else type(travel_cost).__name__}")
+        if not _is_int(travel_m) or not 0 <= travel_m <= TRAVEL_MAX_LIMIT:
+            raise ValueError(f"travel_m must be an integer in [0, 2^31), got {travel_m!r}")
+        travel_cost = travel_cost.to(space.device).contiguous()
     p, q = _view_rows(space, poses, quats)
     dev = space.device
     revealed = space.free.empty_like()
@@ -1142,7 +1154,11 @@ def view_volume_select(space, poses, quats, cam, min_dist, max_dist, k, min_gain
     picked = torch.zeros(k, dtype=torch.int64, device=dev)
     for j in range(k):
         _view_volume_call(space, p, q, M, None, cam, min_dist, max_dist, revealed, None, window, scores, stop, None)
-        _map_call(dev, "tohip_view_volume_pick", ptr(scores), ptr(taken), M, min_gain, j, ptr(order), ptr(picked), ptr(stop))
+        if travel_cost is None:
+            _map_call(dev, "tohip_view_volume_pick", ptr(scores), ptr(taken), M, min_gain, j, ptr(order), ptr(picked), ptr(stop))
+        else:
+            _map_call(dev, "tohip_view_volume_pick_travel", ptr(scores), ptr(travel_cost), int(travel_m), ptr(taken), M, min_gain, j, ptr(order),
+                      ptr(picked), ptr(stop))
         # the mark step: the winner's number stays on the device, and one view may claim what it counts
         _view_volume_call(space, p, q, M, order[j:j + 1], cam, min_dist, max_dist, revealed, revealed, window, scratch, stop, None)
     return order, picked, revealed
@@ -1386,6 +1402,139 @@ class ClearanceField:
         _, _, _, need2 = check_field(self.occupied, D=self.D, radius=check_tour_radius(radius), stride=stride, space=space)
         occ, fre = (ptr(space.occupied.buf), ptr(space.free.buf)) if space is not None else (None, None)
         return _listed_plane(FreeNodes, self.occupied, "tohip_field_nodes", (ptr(self.buf), self.buf.numel(), occ, fre), (need2, int(stride)))
+
+
+TRAVEL_SENTINEL = 0xFFFFFFFF          # a travel field's "unreachable"
+TRAVEL_MAX_LIMIT = (1 << 31) - 1      # the largest cost a travel field stores, in 1/64 voxel edge
+TRAVEL_MAX_ROUNDS_PER_CHECK = 65536
+TRAVEL_MAX_ROWS = 1 << 20             # rows of one path that paths() sizes for without being told
+
+
+def travel_limit(max_dist, resolution):
+    """max_dist in metres (None: none) -> the largest cost kept, min(floor(float64(max_dist) / float64(f32 resolution) 64), 2^31 - 1)
+    (synth.travel_limit restates it)."""
+    if max_dist is None:
+        return TRAVEL_MAX_LIMIT
+    return int(min(np.floor(float(max_dist) / float(np.float32(resolution)) * 64.0), TRAVEL_MAX_LIMIT))
+
+
+def _check_rows3(t, name, empty=False):
+    if not torch.is_tensor(t) or not t.is_floating_point():
+        raise ValueError(f"{name} must be a floating-point tensor, got {type(t).__name__}{'' if not torch.is_tensor(t) else ' of ' + str(t.dtype)}")
+    if t.dim() == 1 and t.shape[0] == 3:
+        t = t.reshape(1, 3)
+    if t.dim() != 2 or t.shape[1] != 3 or (t.shape[0] == 0 and not empty):
+        raise ValueError(f"{name} must have shape ({'M' if empty else 'S'},3){'' if empty else ' with S >= 1'} (or (3,)), got {tuple(t.shape)}")
+    return t
+
+
+def check_travel(field, radius, sources, space=None, max_dist=None, rounds_per_check=16):
+    """A travel field's arguments, by name; needs no GPU.  field: an ops.ClearanceField; radius: a finite number > 0 whose need2 =
+    field_need2(radius) is at most the field's D^2 (check_field's rule and error); sources: a floating-point (S,3) tensor, S >= 1, or
+    (3,) — rows that are not finite are allowed: they are ignored and reported; space: None or an ops.SpaceMap of the field's origin,
+    resolution, dims and device; max_dist: None or a finite number of metres >= 0; rounds_per_check: an integer in [1, 65536].
+    -> (need2, limit, S); ValueError otherwise."""
+    if not isinstance(field, ClearanceField):
+        raise ValueError(f"TravelField: field must be an ops.ClearanceField, got {type(field).__name__}")
+    _, _, _, need2 = check_field(field.occupied, D=field.D, radius=check_tour_radius(radius), space=space)
+    src = _check_rows3(sources, "sources")
+    if max_dist is not None:
+        m = _float_or_nan(max_dist) if _is_real(max_dist) else float("nan")
+        if not np.isfinite(m) or m < 0.0:
+            raise ValueError(f"max_dist must be None or a finite number of metres >= 0, got {max_dist!r}")
+    if not _is_int(rounds_per_check) or not 1 <= rounds_per_check <= TRAVEL_MAX_ROUNDS_PER_CHECK:
+        raise ValueError(f"rounds_per_check must be an integer in [1, {TRAVEL_MAX_ROUNDS_PER_CHECK}], got {rounds_per_check!r}")
+    return need2, travel_limit(max_dist, field.resolution), src.shape[0]
+
+
+class TravelField:
+    """A travel field over a clearance field (travel_kernels.hip, DESIGN.md 10 "Travel field"): per voxel inside dims the length, in
+    1/64 voxel edge, of the shortest 26-connected path from any of the sources through the voxels the field certifies for `radius`
+    (and, with space=, that are known to be free), no corner cut — a navigation function from the robot's position.  Exact
+    integers: the same bits in every run.  It holds the cost buffer and the worklist's workspace and reads the field (and the map's
+    planes) again on rebuild().  seeded: (S,) uint8 on the device, 0 for a source that was ignored (not finite, out of range, outside
+    dims or not traversable — there is no snapping); rounds: the worklist rounds the last build needed; limit: the largest cost
+    kept."""
+
+    def __init__(self, field, radius, sources, space=None, max_dist=None, rounds_per_check=16):
+        self.need2, self.limit, _ = check_travel(field, radius, sources, space, max_dist, rounds_per_check)
+        self.field, self.radius, self.space, self.max_dist, self.rounds_per_check = field, float(radius), space, max_dist, int(rounds_per_check)
+        self.origin, self.resolution, self.dims, self.device, self.geom = field.origin, field.resolution, field.dims, field.device, field.geom
+        L = _lib.lib()
+        self.buf = torch.empty(L.tohip_travel_bytes(*self.dims), dtype=torch.uint8, device=self.device)
+        self._ws = torch.empty(L.tohip_travel_workspace_bytes(*self.dims), dtype=torch.uint8, device=self.device)
+        self.sources = self.seeded = None
+        self.rounds = 0
+        self.rebuild(sources)
+
+    def _set(self):
+        """The arguments that name T: the field, the map's planes (or none), the planes' size, the geometry, need2."""
+        occ, fre = (ptr(self.space.occupied.buf), ptr(self.space.free.buf)) if self.space is not None else (None, None)
+        return (ptr(self.field.buf), self.field.buf.numel(), occ, fre, self.field.occupied.buf.numel(), ctypes.byref(self.geom), self.need2)
+
+    def rebuild(self, sources=None):
+        """Recompute the whole field into the same buffers — after field.rebuild(), or from new sources (None: the last ones) when
+        the robot has moved.  One synchronisation per rounds_per_check rounds.  -> self."""
+        if sources is not None:
+            check_travel(self.field, self.radius, sources, self.space, self.max_dist, self.rounds_per_check)
+            self.sources = _check_rows3(sources, "sources").detach().to(device=self.device, dtype=torch.float32).contiguous()
+        S = self.sources.shape[0]
+        self.seeded = torch.empty(S, dtype=torch.uint8, device=self.device)
+        rounds = ctypes.c_int64(0)
+        _map_call(self.device, "tohip_travel_build", *self._set(), ptr(self.sources), S, self.limit, self.rounds_per_check, ptr(self.buf),
+                  self.buf.numel(), ptr(self._ws), self._ws.numel(), ptr(self.seeded), ctypes.byref(rounds))
+        self.rounds = int(rounds.value)
+        return self
+
+    def dense(self):
+        """The field as an (nx, ny, nz) int64 tensor (a copy), -1 where unreachable: for tests and small grids."""
+        nx, ny, nz = self.dims
+        c = self.buf.view(torch.int32).view(nz, ny, nx).to(torch.int64).bitwise_and(0xFFFFFFFF)
+        return torch.where(c == TRAVEL_SENTINEL, torch.full_like(c, -1), c).permute(2, 1, 0).contiguous()
+
+    def _positions(self, p, want_cost, want_dist):
+        pos = covmap_points(p, self.device, "TravelField")
+        cost = torch.empty(pos.shape[0], dtype=torch.int64, device=self.device) if want_cost else None
+        dist = torch.empty(pos.shape[0], dtype=torch.float32, device=self.device) if want_dist else None
+        _map_call(self.device, "tohip_travel_positions", ptr(self.buf), self.buf.numel(), ctypes.byref(self.geom), ptr(pos), pos.shape[0],
+                  ptr(cost), ptr(dist))
+        return cost, dist
+
+    def cost(self, positions):
+        """(M,3) world positions -> (M,) int64: the cost of the position's voxel in 1/64 voxel edge, -1 unreachable, -2 out of range
+        (beyond the apron, or not finite) or outside dims."""
+        return self._positions(positions, True, False)[0]
+
+    def distance(self, positions):
+        """(M,3) world positions -> (M,) f32 metres travelled: cost / 64 resolution; +inf unreachable, NaN where cost() gives -2."""
+        return self._positions(positions, False, True)[1]
+
+    def reachable(self, positions):
+        """(M,3) world positions -> (M,) bool: a path from a source to the position's voxel exists (within max_dist)."""
+        return self.cost(positions) >= 0
+
+    def paths(self, goals, max_rows=None):
+        """One path per goal position -> a list of (L,3) f32 device tensors, the voxel centres from the source to the goal's voxel
+        (L = 0: unreachable, out of range or outside dims); every leg joins two 26-neighbours and is one field.edges(a, b, radius)
+        calls open.  max_rows (None: sized from the goals' costs) bounds the rows per path: ValueError names the goal and the rows
+        it needs where a path does not fit.  One launch, one synchronisation."""
+        g = covmap_points(_check_rows3(goals, "goals", empty=True), self.device, "TravelField.paths")
+        G = g.shape[0]
+        if G == 0:
+            return []
+        if max_rows is None:
+            # a path of cost c has at most c / 64 moves
+            max_rows = min(max(int(self.cost(g).max().item()), 0) // 64 + 1, TRAVEL_MAX_ROWS)
+        if not _is_int(max_rows) or max_rows < 1:
+            raise ValueError(f"max_rows must be an integer >= 1 or None, got {max_rows!r}")
+        rows = torch.empty((G, int(max_rows), 3), dtype=torch.float32, device=self.device)
+        counts = torch.empty(G, dtype=torch.int64, device=self.device)
+        _map_call(self.device, "tohip_travel_paths", ptr(self.buf), self.buf.numel(), *self._set(), ptr(g), G, int(max_rows), ptr(rows), ptr(counts))
+        n = counts.cpu().tolist()
+        for e, k in enumerate(n):
+            if k < 0:
+                raise ValueError(f"paths: goal {e} needs {-k} rows, max_rows is {int(max_rows)}")
+        return [rows[e, :k].flip(0) for e, k in enumerate(n)]   # source -> goal
 
 
 EVID_UNKNOWN = -128        # an evidence value: never observed

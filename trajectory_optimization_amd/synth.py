@@ -1276,6 +1276,160 @@ def doorway_messages():
     return [(s1, box_room(doorway=True), None), (s2, doorway_outside_scan(s2), 1.4)]
 
 
+# ---- the travel field restated in numpy ("Travel field"): what travel_kernels.hip must give, bit for bit.  int64
+# throughout, dense (nx,ny,nz) arrays, -1 = unreachable. ---------------------------------------------------------------------------
+TRAVEL_WEIGHTS = (64, 91, 111)          # face, edge, corner moves, in 1/64 voxel edge: round(64 sqrt(k))
+TRAVEL_MAX_LIMIT = (1 << 31) - 1
+TRAVEL_MOVES = tuple((m % 3 - 1, (m // 3) % 3 - 1, m // 9 - 1) for m in range(27))   # move m = (dz+1) 9 + (dy+1) 3 + (dx+1) -> (dx, dy, dz)
+
+
+def travel_limit(max_dist, resolution):
+    """max_dist in metres (None: no truncation) -> the largest cost kept: min(floor(float64(max_dist) / float64(f32 resolution) 64),
+    2^31 - 1)."""
+    if max_dist is None:
+        return TRAVEL_MAX_LIMIT
+    return int(min(math.floor(float(max_dist) / float(np.float32(resolution)) * 64.0), TRAVEL_MAX_LIMIT))
+
+
+def travel_traversable_ref(field, need2, state=None):
+    """The traversable set T (nx,ny,nz) bool: field >= need2 and, where state is given, state == 1 — field_nodes_ref at stride 1."""
+    return field_nodes_ref(field, need2, 1, state)
+
+
+def _travel_shift(a, d, fill):
+    """out[v] = a[v + d] where v + d lies inside, else fill."""
+    out = np.full_like(a, fill)
+    src, dst = [], []
+    for n, k in zip(a.shape, d):
+        src.append(slice(max(k, 0), n + min(k, 0)))
+        dst.append(slice(max(-k, 0), n + min(-k, 0)))
+    out[tuple(dst)] = a[tuple(src)]
+    return out
+
+
+def travel_allowed_ref(T):
+    """{move m: (nx,ny,nz) bool} for the 26 moves: the move from v is allowed iff every voxel of the box spanned by v and v + d is in
+    T (2, 4 or 8 voxels) — no corner is cut."""
+    T = np.asarray(T, dtype=bool)
+    out = {}
+    for m, (dx, dy, dz) in enumerate(TRAVEL_MOVES):
+        if m == 13:
+            continue
+        ok = T.copy()
+        for ex in {0, dx}:
+            for ey in {0, dy}:
+                for ez in {0, dz}:
+                    ok &= _travel_shift(T, (ex, ey, ez), False)
+        out[m] = ok
+    return out
+
+
+def travel_seeds_ref(sources, origin, resolution, T):
+    """(S,3) source positions -> (seeded (S,) uint8, voxels (S,3) int64): seeded iff the position is in range, its voxel lies
+    inside dims and in T; there is no snapping."""
+    T = np.asarray(T, dtype=bool)
+    q, ok = occ_fixed(sources, origin, resolution)
+    v = q >> 8
+    inside = ok & ((v >= 0) & (v < np.asarray(T.shape)[None, :])).all(axis=1)
+    seeded = np.zeros(len(v), dtype=np.uint8)
+    seeded[inside] = T[v[inside, 0], v[inside, 1], v[inside, 2]]
+    return seeded, v
+
+
+def travel_ref(T, seeds, limit=TRAVEL_MAX_LIMIT):
+    """The travel field (nx,ny,nz) int64 by Bellman-Ford: cost 0 at the voxels `seeds` (K,3) that lie in T, then sweeps of 26 shifted
+    minima under the move masks until nothing changes; a value above limit is never stored (a prefix of a shortest path is shorter:
+    what is stored is the untruncated distance).  -1 = unreachable."""
+    T = np.asarray(T, dtype=bool)
+    big = np.int64(1) << 40
+    cost = np.full(T.shape, big, dtype=np.int64)
+    for x, y, z in np.asarray(seeds, dtype=np.int64).reshape(-1, 3):
+        if 0 <= x < T.shape[0] and 0 <= y < T.shape[1] and 0 <= z < T.shape[2] and T[x, y, z]:
+            cost[x, y, z] = 0
+    allowed = travel_allowed_ref(T)
+    weights = {m: TRAVEL_WEIGHTS[sum(1 for k in d if k) - 1] for m, d in enumerate(TRAVEL_MOVES) if m != 13}
+    while True:
+        before = cost.copy()
+        for m, ok in allowed.items():
+            cand = _travel_shift(cost, TRAVEL_MOVES[m], big) + weights[m]
+            cost = np.where(ok & (cand <= limit) & (cand < cost), cand, cost)
+        if np.array_equal(cost, before):
+            break
+    return np.where(cost <= limit, cost, -1).astype(np.int64)
+
+
+def travel_metres(cost, resolution):
+    """cost codes (any shape) -> f32 metres: fl(fl((float) cost / 64) r); +inf for -1, NaN for -2."""
+    c = np.asarray(cost, dtype=np.int64)
+    m = ((np.maximum(c, 0).astype(np.float32) * np.float32(1.0 / 64.0)).astype(np.float32) * np.float32(resolution)).astype(np.float32)
+    m = np.where(c == -1, np.float32(np.inf), m)
+    return np.where(c == -2, np.float32(np.nan), m).astype(np.float32)
+
+
+def travel_positions_ref(positions, origin, resolution, cost):
+    """(M,3) world positions -> (M,) int64: the voxel's cost, -1 unreachable, -2 out of range or outside dims."""
+    cost = np.asarray(cost, dtype=np.int64)
+    q, ok = occ_fixed(positions, origin, resolution)
+    v = q >> 8
+    inside = ok & ((v >= 0) & (v < np.asarray(cost.shape)[None, :])).all(axis=1)
+    out = np.full(len(v), -2, dtype=np.int64)
+    out[inside] = cost[v[inside, 0], v[inside, 1], v[inside, 2]]
+    return out
+
+
+def travel_paths_ref(goals, origin, resolution, cost, T):
+    """One path per goal position, by the path rule -> a list of (L,3) f32 arrays of voxel centres from the goal's voxel to its
+    source (L = 0: the goal is unreachable, out of range or outside dims): the predecessor of v is the allowed neighbour u with
+    cost[u] + w == cost[v], the lowest move number on ties."""
+    cost, T = np.asarray(cost, dtype=np.int64), np.asarray(T, dtype=bool)
+    f32 = np.float32
+    o, r = np.asarray(origin, dtype=f32).reshape(3), f32(resolution)
+    codes = travel_positions_ref(goals, origin, resolution, cost)
+    q, _ = occ_fixed(goals, origin, resolution)
+    inside = lambda p: all(0 <= p[a] < T.shape[a] for a in range(3))   # noqa: E731
+    out = []
+    for e, code in enumerate(codes):
+        rows = []
+        if code >= 0:
+            v = tuple(int(k) for k in q[e] >> 8)
+            while True:
+                rows.append((o + ((np.asarray(v, dtype=f32) + f32(0.5)).astype(f32) * r).astype(f32)).astype(f32))
+                if cost[v] == 0:
+                    break
+                for m, d in enumerate(TRAVEL_MOVES):
+                    u = (v[0] + d[0], v[1] + d[1], v[2] + d[2])
+                    if m == 13 or not inside(u) or cost[u] < 0:
+                        continue
+                    w = TRAVEL_WEIGHTS[sum(1 for k in d if k) - 1]
+                    box = [(v[0] + ex, v[1] + ey, v[2] + ez) for ex in {0, d[0]} for ey in {0, d[1]} for ez in {0, d[2]}]
+                    if cost[u] + w == cost[v] and all(T[b] for b in box):
+                        v = u
+                        break
+                else:
+                    raise AssertionError(f"no predecessor at {v}: not a travel field")
+        out.append(np.asarray(rows, dtype=f32).reshape(-1, 3))
+    return out
+
+
+def travel_weight_fixed(travel_weight, resolution):
+    """select_views_volume's travel_weight (revealed voxels per metre travelled) -> the pick's integer m = round(travel_weight r 2^20 /
+    64): gain 2^20 - m cost is then gain - travel_weight metres, in units of 2^-20 voxel."""
+    return int(round(float(travel_weight) * float(np.float32(resolution)) * (1 << 20) / 64.0))
+
+
+def view_pick_travel_ref(gains, taken, cost, m, min_gain=1):
+    """One round of the pick that prices the trip -> the winner's index or -1 (stop): among the candidates with taken == 0, gain >=
+    min_gain and cost >= 0 the largest gain 2^20 - m cost (Python integers), the lowest index on ties."""
+    best, at = None, -1
+    for i, (g, t, c) in enumerate(zip(np.asarray(gains).tolist(), np.asarray(taken).tolist(), np.asarray(cost).tolist())):
+        if t or g < min_gain or c < 0:
+            continue
+        score = g * (1 << 20) - int(m) * c
+        if best is None or score > best:
+            best, at = score, i
+    return at
+
+
 # ---- the evidence map restated in numpy (DESIGN.md 10, "Evidence map"): what evidence_kernels.hip must give, bit for bit.  int64
 # throughout, dense (nx,ny,nz) arrays. --------------------------------------------------------------------------------------------------
 EVID_UNKNOWN = -128

@@ -296,6 +296,19 @@ def free_nodes(field, radius, stride=1, space=None):
     return field.free_nodes(radius, stride, space)
 
 
+def travel_field(field, start, radius, space=None, max_dist=None):
+    """Can the robot get there, and how far is it?  An ops.TravelField ("Travel field"): from `start` — (3,) or (S,3)
+    positions, the robot's — the length of the shortest path to every voxel of the map, through voxels whose whole cube the clearance
+    field certifies for `radius` metres and, with space= (an ops.SpaceMap), that are known to be free; 26-connected, no corner cut.
+    tf.reachable(positions), tf.distance(positions) (metres), tf.cost(positions) and tf.paths(goals) ask it; travel_path(tf, goal)
+    gives one path; select_views_volume(..., travel=tf, travel_weight=w) prices the trip to each candidate.  max_dist (metres)
+    truncates the field.  A start that is not traversable is ignored (tf.seeded): nothing is then reachable.  tf.rebuild(start)
+    follows field.rebuild() or a robot that has moved."""
+    if not isinstance(field, ops.ClearanceField):
+        raise ValueError(f"travel_field: field must be an ops.ClearanceField, got {type(field).__name__}")
+    return ops.TravelField(field, radius, start, space=space, max_dist=max_dist)
+
+
 def evidence_map(grid_or_points, resolution=0.1, **params):
     """An ops.EvidenceMap ("Evidence map"): per voxel an integer log-odds value that every scan moves — up where a
     return fell, down where a ray passed — and the occupied and free planes derived from it, so a person who walked through the
@@ -450,8 +463,9 @@ class VolumeSelection(_Result):
     """What select_views_volume returns: order (n_selected,) int64 and gains (n_selected,) int64 on the host (gain j = the unknown
     voxels view order[j] added when it was chosen: a marginal gain), poses / quats (the chosen rows in selection order, on the
     device), revealed (an ops.OccupancyGrid: the caller's `claimed` plus every voxel the chosen views reveal — the next round's or the
-    next robot's `claimed`) and total = sum(gains), the popcount the selection added to it."""
-    __slots__ = ("order", "gains", "poses", "quats", "revealed", "total")
+    next robot's `claimed`) and total = sum(gains), the popcount the selection added to it.  travel: (n_selected,) f32 on the device,
+    the metres from the travel field's sources to each chosen view — None where the selection was made without a travel field."""
+    __slots__ = ("order", "gains", "poses", "quats", "revealed", "total", "travel")
 
     @property
     def n_selected(self):
@@ -484,7 +498,8 @@ def view_volume(space_or_evidence_map, poses, quats, claimed=None, **camera):
     return ops.view_volume(space, poses, quats, cam, mn, mx, claimed=claimed)
 
 
-def select_views_volume(space_or_evidence_map, cand_poses, cand_quats, k, min_gain=1, claimed=None, **camera):
+def select_views_volume(space_or_evidence_map, cand_poses, cand_quats, k, min_gain=1, claimed=None, travel=None, travel_weight=0.0,
+                        **camera):
     """Greedy next-best-view selection by revealed volume ("Unknown volume"): out of the M candidates cand_poses (M,3) /
     cand_quats (M,4) wxyz, M <= 65 535 — propose_views' prop.poses, prop.quats go in as they are — choose up to k that together
     reveal the most unknown voxels of the map.  Round after round every candidate not yet taken is scored by view_volume against the voxels claimed
@@ -494,9 +509,29 @@ def select_views_volume(space_or_evidence_map, cand_poses, cand_quats, k, min_ga
 
     The objective is the coverage of a set — the number of distinct voxels revealed — which is monotone submodular: the greedy
     choice is within (1 - 1/e) of the best set of that size.  Everything runs on the device, 3 k launches and one host
-    synchronisation at the end.  Keywords: the camera, as view_volume takes it.  -> VolumeSelection."""
+    synchronisation at the end.  Keywords: the camera, as view_volume takes it.  -> VolumeSelection.
+
+    travel (an ops.TravelField of the map's geometry, travel_field's result; None: none) prices the trip: a candidate whose position
+    the robot cannot reach is never chosen, and every round's winner maximises gain - travel_weight x metres travelled
+    (travel_weight >= 0, in revealed voxels per metre; 0: reachability alone).  The stop rule stays the gain's."""
     space, cam, mn, mx = _volume_setup("select_views_volume", space_or_evidence_map, camera)
-    order, gains, revealed = ops.view_volume_select(space, cand_poses, cand_quats, cam, mn, mx, k, min_gain, claimed)
+    cost, m = None, 0
+    if travel is not None:
+        if not isinstance(travel, ops.TravelField):
+            raise ValueError(f"select_views_volume: travel must be an ops.TravelField or None, got {type(travel).__name__}")
+        w = float(travel_weight) if isinstance(travel_weight, (int, float)) and not isinstance(travel_weight, bool) else float("nan")
+        if not (w >= 0.0) or w == float("inf"):
+            raise ValueError(f"select_views_volume: travel_weight must be a finite number >= 0, got {travel_weight!r}")
+        m = int(round(w * float(travel.resolution) * (1 << 20) / 64.0))
+        if m >= 1 << 31:
+            raise ValueError(f"select_views_volume: travel_weight {travel_weight!r} is too large at this resolution (its fixed-point form "
+                             f"{m} must stay below 2^31)")
+        ops.check_view_volume(space, cand_poses, cand_quats, k, min_gain, claimed)
+        cost = travel.cost(cand_poses.detach().to(device=space.device, dtype=torch.float32).contiguous())
+    elif travel_weight != 0.0:
+        raise ValueError("select_views_volume: travel_weight needs travel= (an ops.TravelField)")
+    order, gains, revealed = ops.view_volume_select(space, cand_poses, cand_quats, cam, mn, mx, k, min_gain, claimed, travel_cost=cost,
+                                                    travel_m=m)
     h = torch.cat([order.long(), gains]).cpu()   # the one synchronisation
     kk = order.shape[0]
     n = int((h[:kk] >= 0).sum())
@@ -504,7 +539,8 @@ def select_views_volume(space_or_evidence_map, cand_poses, cand_quats, k, min_ga
     idx = sel.to(space.device)
     ps = cand_poses.detach().to(device=space.device, dtype=torch.float32)
     qs = cand_quats.detach().to(device=space.device, dtype=torch.float32)
-    return VolumeSelection(order=sel, gains=g, poses=ps[idx], quats=qs[idx], revealed=revealed, total=int(g.sum()))
+    return VolumeSelection(order=sel, gains=g, poses=ps[idx], quats=qs[idx], revealed=revealed, total=int(g.sum()),
+                           travel=travel.distance(ps[idx].contiguous()) if travel is not None else None)
 
 
 class RayHits(_Result):
@@ -966,6 +1002,24 @@ def plan_path(points_or_cloud_or_model, start, goal, via, clearance_radius, k=12
     walk, fixed, length = got
     return PlannedPath(poses=nodes[torch.as_tensor(walk, dtype=torch.int64, device=dev)], length=length, length_fixed=fixed, walk=walk,
                        roadmap=rm)
+
+
+class TravelPath(_Result):
+    """What travel_path returns: poses (L,3) f32 on the device, the voxel centres from the travel field's source to the goal's voxel
+    (L = 0 where it is not reachable) — they go as they are into refine_path(field, path.poses, clearance_radius=radius), which
+    shortcuts the 26-connected staircase; length: metres along the field's metric (inf where not reachable); cost: the integer
+    behind it, in 1/64 voxel edge (-1 unreachable, -2 out of range or outside dims); reachable: bool."""
+    __slots__ = ("poses", "length", "cost", "reachable")
+
+
+def travel_path(tf, goal):
+    """The shortest path of the travel field `tf` (travel_field's result) to `goal` (3,) -> TravelPath.  One synchronisation."""
+    if not isinstance(tf, ops.TravelField):
+        raise ValueError(f"travel_path: tf must be an ops.TravelField, got {type(tf).__name__}")
+    g = _point3(goal, "goal", tf.device).reshape(1, 3)
+    cost = int(tf.cost(g).item())
+    poses = tf.paths(g)[0] if cost >= 0 else torch.empty((0, 3), dtype=torch.float32, device=tf.device)
+    return TravelPath(poses=poses, length=float(tf.distance(g).item()), cost=cost, reachable=cost >= 0)
 
 
 class RefinedPath(_Result):
