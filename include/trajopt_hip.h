@@ -41,7 +41,10 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_travel_bytes / tohip_travel_workspace_bytes / tohip_travel_build / tohip_travel_positions / tohip_travel_paths /
+/* (still 15) + tohip_components_bytes / tohip_components_workspace_bytes / tohip_components_build / tohip_components_stats /
+ * tohip_components_min / tohip_components_positions (connected components of a bit plane: a label volume, per-component size, sums,
+ * box, and the minimum of a value volume over each component): new symbols only.
+ * (still 15) + tohip_travel_bytes / tohip_travel_workspace_bytes / tohip_travel_build / tohip_travel_positions / tohip_travel_paths /
  * tohip_view_volume_pick_travel (a travel field: reachable space and path cost over the clearance field, and a view pick that prices
  * the trip): new symbols only.
  * (still 15) + tohip_cast_segments / tohip_depth_scan (where a ray through the map stops: first hits of segments and the depth image a
@@ -1405,6 +1408,44 @@ int tohip_travel_paths(const void *cost, size_t cost_bytes, const void *field, s
                        int64_t n_goals, int64_t max_rows, float *rows, int64_t *counts, void *stream);
 int tohip_view_volume_pick_travel(const int64_t *gains, const int64_t *cost, int64_t weight, int32_t *taken, int64_t n_views,
                                   int64_t min_gain, int32_t round, int32_t *order, int64_t *picked_gain, int32_t *stop, void *stream);
+
+/* ---- connected components (components_kernels.hip, DESIGN.md §10, "Connected components") ----------------
+ * Which voxels belong together?  plane: any bit plane of the occupancy layout (grid_bytes; header and pad bits 0, as every producer
+ * here leaves them).  Two set voxels inside dims are ADJACENT iff they differ by at most 1 on every axis and by 1 (connectivity 6),
+ * <= 2 (18) or <= 3 (26) axes; there is no corner-cut rule.  A component's ROOT is its lowest linear index v = (z ny + y) nx + x; ids
+ * are 0 .. C - 1 in ascending order of the root.  labels: one uint32 per voxel inside dims, dense, x fastest —
+ * tohip_components_bytes(nx, ny, nz) = 4 nx ny nz device bytes (0 for bad dims), caller-owned, 4-byte aligned: after the build every
+ * set voxel holds its component's id, every clear voxel 0xFFFFFFFF.  The result is a function of the plane and the connectivity
+ * alone — the unique fixed point of label[v] = min(v, label[u] over the adjacent u), ranked: the same bits in every run.
+ *
+ * tohip_components_build: writes label[v] = v and relaxes it over a worklist of 8 x 8 x 8-voxel tiles in workspace
+ * (tohip_components_workspace_bytes device bytes, 256-byte aligned), two launches per round; it enqueues rounds_per_check rounds
+ * (1 .. 1000), SYNCHRONISES to read one word back and repeats until a round had no tile to work on (*rounds_host, HOST, may be NULL:
+ * the rounds that had work).  Then the roots are counted and C is read back into *n_components_host (HOST, required).  C <=
+ * roots_capacity: roots[0 .. C) (DEVICE int32) receives the roots in ascending order and the labels become ids.  C > roots_capacity:
+ * TOHIP_ENOSPC with C reported, roots untouched and the labels left as root indices; the caller sizes roots beforehand — C never
+ * exceeds the plane's set bits (tohip_occ_count) — or builds again.  roots may be NULL with roots_capacity 0.  Bad connectivity,
+ * dims or rounds_per_check, a misaligned or aliased buffer: TOHIP_EINVAL; a short one: TOHIP_ENOSPC.
+ * tohip_components_stats: one pass over labels (built: ids) -> per component sizes (n_components) int64, sums (n_components, 3)
+ * int64 of i, j, k, bbox (n_components, 2, 3) int32 minimum and maximum per axis; integer atomics.  A word that is not an id below
+ * n_components counts for nothing.  The centroid of a component is origin + (sum / size + 0.5) resolution.
+ * tohip_components_min: values (values_bytes >= 4 nx ny nz, uint32 per voxel in labels' layout, 0xFFFFFFFF = none: a travel field's
+ * cost) -> min_value (n_components) int64, the smallest value over the component's voxels, and min_voxel (n_components) int32, the
+ * lowest linear index that attains it; -1 / -1 where every voxel holds 0xFFFFFFFF.  Integer atomic minima, two passes.
+ * tohip_components_positions: positions (m, 3) f32 -> out (m) int64: the voxel's id, -1 clear, -2 out of range or outside dims
+ * (tohip_travel_positions' convention and coordinate rule).
+ * Every argument check returns before anything is enqueued. */
+size_t tohip_components_bytes(int32_t nx, int32_t ny, int32_t nz);
+size_t tohip_components_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int tohip_components_build(const void *plane, size_t grid_bytes, const tohip_occ_geom *geom, int32_t connectivity, void *labels,
+                           size_t labels_bytes, void *workspace, size_t workspace_bytes, int32_t rounds_per_check, int32_t *roots,
+                           int64_t roots_capacity, int64_t *n_components_host, int64_t *rounds_host, void *stream);
+int tohip_components_stats(const void *labels, size_t labels_bytes, const tohip_occ_geom *geom, int64_t n_components, int64_t *sizes,
+                           int64_t *sums, int32_t *bbox, void *stream);
+int tohip_components_min(const void *labels, size_t labels_bytes, const tohip_occ_geom *geom, const void *values, size_t values_bytes,
+                         int64_t n_components, int64_t *min_value, int32_t *min_voxel, void *stream);
+int tohip_components_positions(const void *labels, size_t labels_bytes, const tohip_occ_geom *geom, const float *positions, int64_t m,
+                               int64_t *out, void *stream);
 
 /* ---- optional per-kernel timing (bench.py's roofline leg) -----------------------------------------
  * When enabled, every launch of the big kernels is bracketed by hipEventRecord on its own stream.

@@ -21,6 +21,7 @@
 #include "field_kernels.hip"
 #include "evidence_kernels.hip"
 #include "travel_kernels.hip"
+#include "components_kernels.hip"
 #include "volume_kernels.hip"
 #include "raycast_kernels.hip"
 #include "clearance_map_kernels.hip"

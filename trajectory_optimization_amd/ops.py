@@ -1537,6 +1537,114 @@ class TravelField:
         return [rows[e, :k].flip(0) for e, k in enumerate(n)]   # source -> goal
 
 
+COMPONENT_CONNECTIVITIES = (6, 18, 26)
+COMPONENT_SENTINEL = 0xFFFFFFFF       # a label volume's "clear voxel"
+COMPONENT_MAX_ROUNDS_PER_CHECK = 1000
+
+
+def check_components(grid, connectivity=26, rounds_per_check=16, values=None):
+    """A component labelling's arguments, by name; needs no GPU.  grid: an ops.OccupancyGrid — any bit plane of that layout: an
+    occupied grid, a free plane, Frontier.grid, SpaceMap.unknown(), EvidenceMap.occupied / .free, FreeNodes.grid; connectivity: 6, 18
+    or 26; rounds_per_check: an integer in [1, 1000]; values (min_over's argument, None: not asked): an ops.TravelField of the grid's
+    origin, resolution, dims and device, or a uint32-as-int32 / uint8 device tensor holding 4 nx ny nz bytes (one uint32 per voxel, x
+    fastest, 0xFFFFFFFF = none).  -> (connectivity, rounds_per_check); ValueError otherwise."""
+    if not isinstance(grid, OccupancyGrid):
+        raise ValueError(f"Components: grid must be an ops.OccupancyGrid, got {type(grid).__name__}")
+    if not _is_int(connectivity) or connectivity not in COMPONENT_CONNECTIVITIES:
+        raise ValueError(f"connectivity must be 6, 18 or 26, got {connectivity!r}")
+    if not _is_int(rounds_per_check) or not 1 <= rounds_per_check <= COMPONENT_MAX_ROUNDS_PER_CHECK:
+        raise ValueError(f"rounds_per_check must be an integer in [1, {COMPONENT_MAX_ROUNDS_PER_CHECK}], got {rounds_per_check!r}")
+    if values is not None:
+        if isinstance(values, TravelField):
+            diff = _grid_difference(grid, values)
+            if diff:
+                raise ValueError(f"values: the travel field's {diff[0]} differs from the grid's ({diff[2]} and {diff[1]})")
+        else:
+            nbytes = 4 * grid.dims[0] * grid.dims[1] * grid.dims[2]
+            if not torch.is_tensor(values) or values.dtype not in (torch.int32, torch.uint8) or not values.is_contiguous() or \
+                    values.numel() * values.element_size() != nbytes:
+                raise ValueError(f"values must be an ops.TravelField or a contiguous int32 / uint8 tensor of {nbytes} bytes (one uint32 per "
+                                 f"voxel), got {(tuple(values.shape), values.dtype) if torch.is_tensor(values) else type(values).__name__}")
+            if values.device != grid.device:
+                raise ValueError(f"values must live on the grid's device {grid.device}, got {values.device}")
+    return int(connectivity), int(rounds_per_check)
+
+
+class Components:
+    """The connected components of a bit plane (components_kernels.hip, DESIGN.md 10 "Connected components"): two set voxels belong
+    together iff a chain of adjacent set voxels joins them — adjacent: differing by at most 1 on every axis and on 1 (connectivity
+    6), <= 2 (18) or <= 3 (26) axes; no corner-cut rule.  A component's root is its lowest linear index v = (k ny + j) nx + i, ids are
+    0 .. n - 1 in ascending order of the root: a function of the plane and the connectivity alone, the same bits in every run.
+
+    n: the number of components; labels: (nx ny nz,) int32 on the device holding uint32 bits, x fastest — the id of a set voxel,
+    0xFFFFFFFF (-1 as int32) for a clear one; roots (n,) int32; sizes (n,) int64; sums (n,3) int64 of i, j, k; bbox (n,2,3) int32,
+    minimum and maximum per axis; centroids (n,3) f32 = origin + (sum / size + 0.5) resolution, computed in float64 from the f32
+    origin and resolution, then cast; rounds: the worklist rounds the last build needed.  roots is sized from a count of the plane's
+    set bits (no component count exceeds it), so the build runs once: two synchronisations more than the worklist's own (that count,
+    and n).  It reads the plane again on rebuild()."""
+
+    def __init__(self, grid, connectivity=26, rounds_per_check=16):
+        self.connectivity, self.rounds_per_check = check_components(grid, connectivity, rounds_per_check)
+        self.grid = grid
+        self.origin, self.resolution, self.dims, self.device, self.geom = grid.origin, grid.resolution, grid.dims, grid.device, grid.geom
+        L = _lib.lib()
+        self._buf = torch.empty(L.tohip_components_bytes(*self.dims), dtype=torch.uint8, device=self.device)
+        self._ws = torch.empty(L.tohip_components_workspace_bytes(*self.dims), dtype=torch.uint8, device=self.device)
+        self.labels = self._buf.view(torch.int32)
+        self._roots = None
+        self.n = self.rounds = 0
+        self.rebuild()
+
+    def _labels(self):
+        return ptr(self._buf), self._buf.numel(), ctypes.byref(self.geom)
+
+    def rebuild(self):
+        """Label the plane again into the same buffers — after the grid has changed.  -> self."""
+        dev = self.device
+        capacity = self.grid.count()   # n never exceeds the set bits
+        if self._roots is None or self._roots.numel() < capacity:
+            self._roots = torch.empty(capacity, dtype=torch.int32, device=dev)
+        n, rounds = ctypes.c_int64(0), ctypes.c_int64(0)
+        _map_call(dev, "tohip_components_build", *self.grid._sizes(), self.connectivity, ptr(self._buf), self._buf.numel(), ptr(self._ws),
+                  self._ws.numel(), self.rounds_per_check, ptr(self._roots), self._roots.numel(), ctypes.byref(n), ctypes.byref(rounds))
+        self.n, self.rounds = int(n.value), int(rounds.value)
+        C = self.n
+        self.roots = self._roots[:C]
+        self.sizes = torch.empty(C, dtype=torch.int64, device=dev)
+        self.sums = torch.empty((C, 3), dtype=torch.int64, device=dev)
+        self.bbox = torch.empty((C, 2, 3), dtype=torch.int32, device=dev)
+        _map_call(dev, "tohip_components_stats", *self._labels(), C, ptr(self.sizes), ptr(self.sums), ptr(self.bbox))
+        o = torch.from_numpy(np.asarray(self.origin, dtype=np.float32).astype(np.float64)).to(dev).reshape(1, 3)
+        r = float(np.float32(self.resolution))
+        self.centroids = (o + (self.sums.double() / self.sizes.double()[:, None] + 0.5) * r).float()
+        return self
+
+    def dense(self):
+        """The ids as an (nx, ny, nz) int64 tensor (a copy), -1 where the voxel is clear: for tests and small grids."""
+        nx, ny, nz = self.dims
+        return self.labels.view(nz, ny, nx).to(torch.int64).permute(2, 1, 0).contiguous()
+
+    def at(self, positions):
+        """(M,3) world positions -> (M,) int64: the id of the position's voxel, -1 where it is clear, -2 out of range (beyond the
+        apron, or not finite) or outside dims."""
+        pos = covmap_points(positions, self.device, "Components.at")
+        out = torch.empty(pos.shape[0], dtype=torch.int64, device=self.device)
+        _map_call(self.device, "tohip_components_positions", *self._labels(), ptr(pos), pos.shape[0], ptr(out))
+        return out
+
+    def min_over(self, values):
+        """The minimum of a value volume over each component -> (value (n,) int64, voxel (n,) int32): the smallest word over the
+        component's voxels that is not 0xFFFFFFFF and the lowest linear index that attains it, -1 / -1 where there is none.  values: an
+        ops.TravelField (its cost: how far is the nearest voxel of each component, and which is it) or a tensor of one uint32 per
+        voxel in the labels' layout."""
+        check_components(self.grid, self.connectivity, self.rounds_per_check, values)
+        buf = values.buf if isinstance(values, TravelField) else values
+        value = torch.empty(self.n, dtype=torch.int64, device=self.device)
+        voxel = torch.empty(self.n, dtype=torch.int32, device=self.device)
+        _map_call(self.device, "tohip_components_min", *self._labels(), ptr(buf), buf.numel() * buf.element_size(), self.n, ptr(value), ptr(voxel))
+        return value, voxel
+
+
 EVID_UNKNOWN = -128        # an evidence value: never observed
 EVID_DEFAULTS = dict(hit=17, miss=8, lmin=-40, lmax=70, threshold=0)
 

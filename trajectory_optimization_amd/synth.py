@@ -1430,6 +1430,110 @@ def view_pick_travel_ref(gains, taken, cost, m, min_gain=1):
     return at
 
 
+# ---- connected components restated in numpy ("Connected components"): what components_kernels.hip must give, bit for
+# bit.  Dense (nx,ny,nz) arrays, the linear index of voxel (x, y, z) is v = (z ny + y) nx + x, -1 = a clear voxel. ----------------------
+COMPONENT_CONNECTIVITIES = (6, 18, 26)
+
+
+def components_offsets(connectivity):
+    """The neighbour offsets (dx, dy, dz) of a connectivity: those that differ on 1 (6), <= 2 (18) or <= 3 (26) axes."""
+    if connectivity not in COMPONENT_CONNECTIVITIES:
+        raise ValueError(f"connectivity must be 6, 18 or 26, got {connectivity!r}")
+    most = {6: 1, 18: 2, 26: 3}[connectivity]
+    return [d for m, d in enumerate(TRAVEL_MOVES) if m != 13 and sum(1 for k in d if k) <= most]
+
+
+def components_ref(plane, connectivity=26):
+    """Connected components of a bool plane (nx,ny,nz) -> (ids (nx,ny,nz) int64, -1 where clear; roots (C,) int64 ascending): every
+    set voxel starts with its own linear index; rounds of shifted minima over the connectivity's offsets, each followed by pointer
+    jumping (a label is the index of a voxel of the same component, whose label is no larger), until nothing changes.  The root of a
+    component is its lowest linear index, the id its root's rank."""
+    plane = np.asarray(plane, dtype=bool)
+    nx, ny, nz = plane.shape
+    big = np.int64(1) << 40
+    x, y, z = np.meshgrid(np.arange(nx), np.arange(ny), np.arange(nz), indexing="ij")
+    lin = ((z * ny + y) * nx + x).astype(np.int64)
+    lab = np.where(plane, lin, big)
+    offsets = components_offsets(connectivity)
+    order = lin[plane]                         # a set voxel's linear index, in the dense array's own order
+    flat = np.full(nx * ny * nz, big, dtype=np.int64)
+    while True:
+        before = lab
+        for d in offsets:
+            lab = np.where(plane, np.minimum(lab, _travel_shift(lab, d, big)), big)
+        while True:                            # label <- the label of the voxel it names
+            flat[order] = lab[plane]
+            nxt = flat[lab[plane]]
+            if np.array_equal(nxt, lab[plane]):
+                break
+            lab[plane] = nxt
+        if np.array_equal(lab, before):
+            break
+    roots = np.unique(lab[plane])
+    ids = np.full(plane.shape, -1, dtype=np.int64)
+    ids[plane] = np.searchsorted(roots, lab[plane])
+    return ids, roots.astype(np.int64)
+
+
+def components_stats_ref(ids, origin, resolution):
+    """Per component of an id volume (nx,ny,nz), -1 clear -> dict(sizes (C,) int64, sums (C,3) int64 of i, j, k, bbox (C,2,3) int32
+    minimum and maximum per axis, centroids (C,3) f32 = fl(origin + (sum / size + 0.5) r) computed in float64 from the f32 origin and
+    resolution, then cast)."""
+    ids = np.asarray(ids, dtype=np.int64)
+    C = int(ids.max()) + 1 if ids.size and ids.max() >= 0 else 0
+    ijk = np.argwhere(ids >= 0).astype(np.int64)
+    of = ids[ids >= 0]
+    sizes = np.zeros(C, dtype=np.int64)
+    sums = np.zeros((C, 3), dtype=np.int64)
+    bbox = np.empty((C, 2, 3), dtype=np.int32)
+    bbox[:, 0], bbox[:, 1] = np.iinfo(np.int32).max, -1
+    np.add.at(sizes, of, 1)
+    np.add.at(sums, of, ijk)
+    np.minimum.at(bbox[:, 0], of, ijk.astype(np.int32))
+    np.maximum.at(bbox[:, 1], of, ijk.astype(np.int32))
+    o = np.asarray(origin, dtype=np.float32).astype(np.float64).reshape(1, 3)
+    r = float(np.float32(resolution))
+    centroids = (o + (sums.astype(np.float64) / np.maximum(sizes, 1)[:, None].astype(np.float64) + 0.5) * r).astype(np.float32)
+    return dict(sizes=sizes, sums=sums, bbox=bbox, centroids=centroids)
+
+
+def components_min_ref(ids, values, sentinel=0xFFFFFFFF):
+    """Per component the smallest entry of values (nx,ny,nz) that is not the sentinel, and the lowest linear index v = (z ny + y) nx +
+    x among the voxels that attain it -> (value (C,) int64, voxel (C,) int64); -1 / -1 where every voxel holds the sentinel."""
+    ids, values = np.asarray(ids, dtype=np.int64), np.asarray(values, dtype=np.int64)
+    nx, ny, nz = ids.shape
+    C = int(ids.max()) + 1 if ids.size and ids.max() >= 0 else 0
+    big = np.int64(1) << 40
+    value = np.full(C, big, dtype=np.int64)
+    voxel = np.full(C, big, dtype=np.int64)
+    ok = (ids >= 0) & (values != sentinel)
+    ijk = np.argwhere(ok)
+    lin = (ijk[:, 2] * ny + ijk[:, 1]) * nx + ijk[:, 0]
+    of, val = ids[ok], values[ok]
+    np.minimum.at(value, of, val)
+    hit = val == value[of]
+    np.minimum.at(voxel, of[hit], lin[hit])
+    none = value == big
+    return np.where(none, -1, value), np.where(none, -1, voxel)
+
+
+def components_positions_ref(positions, origin, resolution, ids):
+    """(M,3) world positions -> (M,) int64: the voxel's id, -1 clear, -2 out of range or outside dims."""
+    return travel_positions_ref(positions, origin, resolution, ids)
+
+
+def frontier_clusters_ref(sizes, cost=None, min_size=1):
+    """The rows of frontier_clusters -> the component ids in row order (K,) int64: the components with size >= min_size; with cost
+    (C,) int64 (-1 unreachable) the reachable ones first, by ascending cost, then descending size, then ascending id; without it by
+    descending size, then ascending id."""
+    sizes = [int(s) for s in np.asarray(sizes).tolist()]
+    keep = [i for i, s in enumerate(sizes) if s >= min_size]
+    if cost is None:
+        return np.asarray(sorted(keep, key=lambda i: (-sizes[i], i)), dtype=np.int64)
+    cost = [int(c) for c in np.asarray(cost).tolist()]
+    return np.asarray(sorted(keep, key=lambda i: (cost[i] < 0, max(cost[i], 0), -sizes[i], i)), dtype=np.int64)
+
+
 # ---- the evidence map restated in numpy (DESIGN.md 10, "Evidence map"): what evidence_kernels.hip must give, bit for bit.  int64
 # throughout, dense (nx,ny,nz) arrays. --------------------------------------------------------------------------------------------------
 EVID_UNKNOWN = -128

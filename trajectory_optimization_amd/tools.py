@@ -309,6 +309,17 @@ def travel_field(field, start, radius, space=None, max_dist=None):
     return ops.TravelField(field, radius, start, space=space, max_dist=max_dist)
 
 
+def label_components(grid_or_plane, connectivity=26):
+    """Which voxels belong together?  An ops.Components ("Connected components") of a bit plane: an ops.OccupancyGrid
+    (an occupied grid, a free plane, space.unknown(), an evidence map's .occupied / .free) or anything that carries one as .grid
+    (space.frontier(), field.free_nodes()).  connectivity 6, 18 or 26.  comp.n, comp.sizes, comp.centroids, comp.bbox describe the
+    components, comp.at(positions) names the one a position lies in, comp.min_over(travel_field) the nearest voxel of each."""
+    grid = grid_or_plane.grid if isinstance(grid_or_plane, ops.Frontier) else grid_or_plane
+    if not isinstance(grid, ops.OccupancyGrid):
+        raise ValueError(f"label_components: the plane must be an ops.OccupancyGrid or carry one as .grid, got {type(grid_or_plane).__name__}")
+    return ops.Components(grid, connectivity)
+
+
 def evidence_map(grid_or_points, resolution=0.1, **params):
     """An ops.EvidenceMap ("Evidence map"): per voxel an integer log-odds value that every scan moves — up where a
     return fell, down where a ray passed — and the occupied and free planes derived from it, so a person who walked through the
@@ -1020,6 +1031,66 @@ def travel_path(tf, goal):
     cost = int(tf.cost(g).item())
     poses = tf.paths(g)[0] if cost >= 0 else torch.empty((0, 3), dtype=torch.float32, device=tf.device)
     return TravelPath(poses=poses, length=float(tf.distance(g).item()), cost=cost, reachable=cost >= 0)
+
+
+class FrontierClusters(_Result):
+    """What frontier_clusters returns, one row per cluster kept, all on the device: ids (K,) int64 (the component's id in
+    .components), sizes (K,) int64 voxels, centroids (K,3) f32, bbox (K,2,3) int32, cost (K,) f64 metres along the travel field's
+    metric to the cluster's nearest voxel (inf: unreachable, or no travel field), approach (K,3) f32 the centre of that voxel (NaN
+    where unreachable), reachable (K,) bool; frontier: the ops.Frontier clustered; components: the ops.Components of its plane."""
+    __slots__ = ("ids", "sizes", "centroids", "bbox", "cost", "approach", "reachable", "frontier", "components")
+
+    @property
+    def n(self):
+        return int(self.ids.shape[0])
+
+
+def frontier_clusters(space_or_evidence_map, min_unknown=1, min_size=1, connectivity=26, travel=None):
+    """The openings of the map ("Connected components"): the frontier voxels — free, with at least min_unknown unknown
+    face neighbours — grouped into connected clusters, those smaller than min_size voxels dropped: a stray ray through a gap makes a
+    one-voxel frontier, a doorway into an unscanned hall a large one.  -> FrontierClusters.
+
+    travel (an ops.TravelField of the map's geometry; None: none) prices each cluster by its nearest voxel: rows are ordered
+    reachable first, by ascending cost, then descending size, then ascending id — row 0 is the nearest reachable opening, and
+    approach[reachable] goes unchanged into travel_path(travel, goal), propose_views(..., positions=...) and select_views_volume as
+    candidate positions.  Without travel the rows go by descending size, then ascending id.  The order is made on the device by
+    stable integer sorts.
+
+    The cost is taken over the cluster's own voxels, so it needs a travel field in which frontier voxels are traversable: the
+    pairing clearance_field(space, ..., unknown='free') with travel_field(..., space=space).  With unknown='obstacle' every frontier
+    voxel touches an obstacle, none is traversable and every cluster reports unreachable."""
+    space = space_or_evidence_map.space if isinstance(space_or_evidence_map, ops.EvidenceMap) else space_or_evidence_map
+    if not isinstance(space, ops.SpaceMap):
+        raise ValueError(f"frontier_clusters: the map must be an ops.SpaceMap or an ops.EvidenceMap, got {type(space_or_evidence_map).__name__}")
+    if not ops._is_int(min_size) or min_size < 1:
+        raise ValueError(f"frontier_clusters: min_size must be an integer >= 1, got {min_size!r}")
+    if travel is not None and not isinstance(travel, ops.TravelField):
+        raise ValueError(f"frontier_clusters: travel must be an ops.TravelField or None, got {type(travel).__name__}")
+    ops.check_components(space.free, connectivity, values=travel)
+    front = space.frontier(min_unknown)
+    comp = ops.Components(front.grid, connectivity)
+    dev = space.device
+    ids = torch.nonzero(comp.sizes >= int(min_size)).reshape(-1)             # ascending id
+    ids = ids[torch.sort(comp.sizes[ids], stable=True, descending=True)[1]]  # ... then descending size
+    K = ids.shape[0]
+    if travel is None:
+        value = torch.full((K,), -1, dtype=torch.int64, device=dev)
+        voxel = torch.full((K,), -1, dtype=torch.int64, device=dev)
+    else:
+        value, voxel = comp.min_over(travel)
+        key = torch.where(value < 0, torch.full_like(value, torch.iinfo(torch.int64).max), value)
+        ids = ids[torch.sort(key[ids], stable=True)[1]]                      # ... then ascending cost, the unreachable last
+        value, voxel = value[ids], voxel[ids].long()
+    reachable = value >= 0
+    nx, ny, _ = comp.dims
+    v = voxel.clamp(min=0)
+    ijk = torch.stack([v % nx, (v // nx) % ny, v // (nx * ny)], dim=1)
+    o = torch.from_numpy(np.asarray(comp.origin, dtype=np.float32)).to(dev)
+    approach = o + (ijk.float() + 0.5) * float(np.float32(comp.resolution))  # a voxel's centre as the map computes it, in f32
+    approach = torch.where(reachable[:, None], approach, torch.full_like(approach, float("nan")))
+    cost = torch.where(reachable, value.double() / 64.0 * float(np.float32(comp.resolution)), torch.full((K,), float("inf"), dtype=torch.float64, device=dev))
+    return FrontierClusters(ids=ids, sizes=comp.sizes[ids], centroids=comp.centroids[ids], bbox=comp.bbox[ids], cost=cost, approach=approach,
+                            reachable=reachable, frontier=front, components=comp)
 
 
 class RefinedPath(_Result):
