@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_components_bytes / tohip_components_workspace_bytes / tohip_components_build / tohip_components_stats /
+/* (still 15) + tohip_occ_transfer / tohip_evid_transfer (re-framing and merging maps: voxel content moved from one box into another at
+ * an integer voxel shift, written or combined): new symbols only.
+ * (still 15) + tohip_components_bytes / tohip_components_workspace_bytes / tohip_components_build / tohip_components_stats /
  * tohip_components_min / tohip_components_positions (connected components of a bit plane: a label volume, per-component size, sums,
  * box, and the minimum of a value volume over each component): new symbols only.
  * (still 15) + tohip_travel_bytes / tohip_travel_workspace_bytes / tohip_travel_build / tohip_travel_positions / tohip_travel_paths /
@@ -1255,6 +1257,37 @@ int tohip_evid_fold(void *evid, size_t evid_bytes, void *hit_plane, void *pass_p
                     int32_t threshold, int32_t clear_scan, uint64_t *counts, void *stream);
 int tohip_evid_positions(const void *evid, size_t evid_bytes, const tohip_occ_geom *geom, int32_t threshold, const float *positions,
                          int64_t m, int8_t *values, uint8_t *state, void *stream);
+
+/* ---- re-framing and merging maps (reframe_kernels.hip, DESIGN.md §10, "Re-framing and merging maps") ----
+ * Voxel content moved from one box into another.  src and dst are two DIFFERENT buffers, each with its own geometry (its own dims);
+ * (sx, sy, sz) is an integer voxel shift, each component in [-4096, 4096].  For every voxel v inside dst's dims the SOURCE VALUE is
+ * that of src voxel v + s where that lies inside src's dims, otherwise EMPTY: bit 0 of a plane, -128 of an evidence buffer.  origin
+ * and resolution of the two geometries are checked as everywhere (finite, r > 0) and not interpreted: the caller computes the shift.
+ * Pad bits of dst stay 0, pad bytes stay -128, headers stay as tohip_occ_init / tohip_evid_init leave them.  src is only read; its
+ * pads must be as the layer leaves them (0, -128).
+ *
+ * tohip_occ_transfer: two occupancy grid buffers.  mode 0 (COPY): every dst bit becomes the source bit.  mode 1 (OR): dst |= source.
+ * counts (DEVICE uint64 x 1, may be NULL, zero-filled by the caller): += the bits set in dst afterwards that were not set before; for
+ * COPY, whose dst is not read: += the bits set afterwards.  One lane owns one dst word: no atomic touches the plane.
+ * tohip_evid_transfer: two evidence buffers, and the two derived planes of dst (grid_bytes each, dst's geometry).  With S the source
+ * value and D the dst value, mode 0 (COPY): D <- S.  mode 1 (ADD, independent evidence): S == -128 leaves D alone, otherwise D <-
+ * clamp((D == -128 ? 0 : D) + S, lmin, lmax).  mode 2 (CONFIDENT): D <- the larger of D and S under the total order with key (|L|, L)
+ * and -128 below everything — the stronger belief wins, at equal strength the positive (occupied) one; S outside [lmin, lmax] is
+ * clamped first.  CONFIDENT is a lattice join: commutative, associative, idempotent — any merge order and any repetition gives the
+ * same bytes.  ADD is commutative, and a map merged twice counts twice.  -127 <= lmin <= threshold < lmax <= 127.  For every dst
+ * brick the call writes — every brick in COPY; in ADD and CONFIDENT those with a source value other than -128 inside dst's dims — the
+ * words of occupied_out and free_out are rewritten from the new values exactly as tohip_evid_fold derives them (L > threshold; L !=
+ * -128 and L <= threshold; pad bits 0): handed the planes that were exact before the call, they are exact everywhere after it.
+ * counts (DEVICE uint64 x 4, may be NULL, zero-filled by the caller), tohip_evid_fold's: += values that changed, += voxels newly known,
+ * += occupied bits that appeared, += occupied bits that vanished; COPY does not read dst and counts against an empty one (values
+ * known afterwards, twice; occupied bits afterwards; 0).  src, dst, occupied_out, free_out and counts must be five different buffers.
+ * Both: an argument error is TOHIP_EINVAL, a buffer too small for its geometry TOHIP_ENOSPC; every argument check returns before
+ * anything is enqueued; nothing synchronises with the host; integers only — the same bytes in every run and for every launch shape. */
+int tohip_occ_transfer(const void *src, size_t src_bytes, const tohip_occ_geom *src_geom, void *dst, size_t dst_bytes,
+                       const tohip_occ_geom *dst_geom, int32_t sx, int32_t sy, int32_t sz, int32_t mode, uint64_t *counts, void *stream);
+int tohip_evid_transfer(const void *src, size_t src_bytes, const tohip_occ_geom *src_geom, void *dst, size_t dst_bytes,
+                        const tohip_occ_geom *dst_geom, void *occupied_out, void *free_out, size_t grid_bytes, int32_t sx, int32_t sy,
+                        int32_t sz, int32_t mode, int32_t lmin, int32_t lmax, int32_t threshold, uint64_t *counts, void *stream);
 
 /* ---- clearance from the map (clearance_map_kernels.hip, DESIGN.md §10, "Clearance from the map") -------
  * tohip_clearance and tohip_clearance_segments with the voxels of an occupancy grid as the obstacles.  occupied: a grid buffer of

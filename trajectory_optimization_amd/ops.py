@@ -877,6 +877,30 @@ class OccupancyGrid:
         """An empty grid of this one's origin, resolution, dims and device: a free plane or a mask for it."""
         return OccupancyGrid(self.origin, self.resolution, self.dims, device=self.device)
 
+    def reframed(self, shift=None, dims=None, centre=None):
+        """This grid's content in another box of the same lattice -> a NEW grid (tohip_occ_transfer, DESIGN.md 10 "Re-framing and
+        merging maps"); this one is untouched, and whatever holds it (a SpaceMap, a ClearanceField, ModelTraj(clearance_map=)) keeps
+        it: such consumers are re-pointed or built anew after a re-frame.  Give exactly one of shift — three integers: new voxel v is
+        old voxel v + shift, the new origin float32(float64(origin) + shift * float64(resolution)) — or centre, a world position
+        whose voxel (the f32 index rule) becomes voxel dims // 2.  dims: the new box's (default: this one's).  What leaves the box is
+        dropped, what enters it is empty.  The content moves by the voxel shift, not by re-inserting points.  One launch, nothing
+        read back; `skipped` carries over."""
+        s, d, origin = check_reframe(self, shift, dims, centre)
+        out = OccupancyGrid(origin, self.resolution, d, device=self.device)
+        _map_call(self.device, "tohip_occ_transfer", *self._sizes(), *out._sizes(), *s, XFER_MODES["copy"], None)
+        out.skipped = self.skipped
+        return out
+
+    def merge(self, other, counts=None):
+        """OR another grid of the same lattice into this one over the overlap of the two boxes, in place -> self; `other` is only
+        read.  counts: a zero-filled (1,) int64 device tensor that receives += the bits that were not set before, or None.  One
+        launch, nothing read back."""
+        s, overlap = check_merge(self, other)
+        _check_counts(counts, 1, self.device)
+        if overlap:
+            _map_call(self.device, "tohip_occ_transfer", *other._sizes(), *self._sizes(), *s, XFER_MODES["or"], ptr(counts))
+        return self
+
     def carve(self, origins, points, max_range=None, stats=None, flags=None):
         """Treat this grid as a FREE PLANE (a set bit: "a ray passed through") and set the bit of every voxel the rays origins[i] ->
         points[i] cross, walked exactly as line_of_sight walks (tohip_occ_carve).  origins: (3,) / (1,3) for one origin
@@ -1031,6 +1055,18 @@ class SpaceMap:
         skipped = self.free.carve(origin, pts, max_range, flags=flags)
         self.occupied.insert(pts if max_range is None else pts[flags != 1])
         return skipped
+
+    def reframed(self, shift=None, dims=None, centre=None):
+        """Both planes re-framed (OccupancyGrid.reframed) -> a NEW SpaceMap over two new grids; this map and its planes are untouched."""
+        s, d, _ = check_reframe(self, shift, dims, centre)
+        return SpaceMap(self.occupied.reframed(shift=s, dims=d), self.free.reframed(shift=s, dims=d))
+
+    def merge(self, other):
+        """OR both planes of another SpaceMap of the same lattice into this one's over the overlap, in place -> self."""
+        check_merge(self, other)
+        self.occupied.merge(other.occupied)
+        self.free.merge(other.free)
+        return self
 
     def state(self, positions):
         """(M,3) world positions -> (M,) uint8: 2 occupied, 1 free, 0 unknown, 3 beyond the apron, not finite or outside dims."""
@@ -1753,6 +1789,39 @@ class EvidenceMap:
         self._fold(self._scan.occupied, self._scan.free, True)
         return skipped
 
+    def _transfer(self, src, shift, mode, counts):
+        _, _, lmin, lmax, threshold = self.params
+        _map_call(self.device, "tohip_evid_transfer", *src._sizes(), *self._sizes(), ptr(self.occupied.buf), ptr(self.free.buf),
+                  self.occupied.buf.numel(), *shift, XFER_MODES[mode], lmin, lmax, threshold, ptr(counts))
+
+    def reframed(self, shift=None, dims=None, centre=None):
+        """This map's values in another box of the same lattice -> a NEW EvidenceMap of the same parameters (tohip_evid_transfer,
+        DESIGN.md 10 "Re-framing and merging maps"): a new buffer, both planes derived from it, empty scratch planes; shift, dims
+        and centre as OccupancyGrid.reframed takes them.  This map is untouched, and consumers that hold it or its planes keep
+        them: they are re-pointed or built anew.  One launch, nothing read back; the new map's last_counts() tells what it holds
+        (known voxels, twice; occupied voxels; 0)."""
+        s, d, origin = check_reframe(self, shift, dims, centre)
+        hit, miss, lmin, lmax, threshold = self.params
+        out = EvidenceMap(origin, self.resolution, d, hit, miss, lmin, lmax, threshold, device=self.device)
+        out._transfer(self, s, "copy", out._counts)
+        return out
+
+    def merge(self, other, mode="confident", counts=None):
+        """Fuse another EvidenceMap of the same lattice into this one over the overlap of the two boxes, in place -> self; `other` is
+        only read, both planes stay exact.  mode 'confident': per voxel the stronger belief wins (the larger |L|; at equal strength
+        the positive, occupied one), the other's values clamped to this map's [lmin, lmax] first — a lattice join: commutative,
+        associative and idempotent, so any merge order and any repetition give the same bytes.  mode 'add': independent evidence,
+        clamp(L + L_other, lmin, lmax) where the other has observed the voxel — commutative, but a map merged twice is counted
+        twice.  counts: a zero-filled (4,) int64 device tensor that receives += (values changed, voxels newly known, occupied
+        voxels that appeared, that vanished), or None: last_counts() reports them.  One launch, nothing read back."""
+        s, overlap = check_merge(self, other, mode)
+        _check_counts(counts, 4, self.device)
+        if counts is None:
+            counts = self._counts.zero_()
+        if overlap:
+            self._transfer(other, s, mode, counts)
+        return self
+
     def last_counts(self):
         """What the last fold changed -> (voxels updated, voxels newly known, occupied voxels that appeared, occupied voxels that
         vanished); synchronises.  A clearance field over the map needs a rebuild() when either of the last two is not zero."""
@@ -1800,6 +1869,119 @@ class EvidenceMap:
         for plane, bits in ((self.occupied, bricks > threshold), (self.free, (bricks != EVID_UNKNOWN) & (bricks <= threshold))):
             plane.buf[256:] = (bits.to(torch.int64) * weights).sum(dim=2).to(torch.uint8).reshape(-1)
         return self
+
+
+XFER_MAX_SHIFT = 4096      # of a voxel shift per axis (tohip_occ_transfer / tohip_evid_transfer)
+XFER_MODES = {"copy": 0, "or": 1, "add": 1, "confident": 2}
+LATTICE_TOLERANCE = 1.0 / 256.0   # the layer's fixed-point unit, in voxels
+
+
+def _map_frame(m, name):
+    """The object that carries a map's origin, resolution, dims and device: the map itself, or a SpaceMap's occupied plane."""
+    if isinstance(m, SpaceMap):
+        return m.occupied
+    if isinstance(m, (OccupancyGrid, EvidenceMap)):
+        return m
+    raise ValueError(f"{name} must be an ops.OccupancyGrid, SpaceMap or EvidenceMap, got {type(m).__name__}")
+
+
+def _check_counts(counts, n, device):
+    if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.int64 or tuple(counts.shape) != (n,)
+                               or counts.device != device or not counts.is_contiguous()):
+        raise ValueError(f"counts must be None or a contiguous ({n},) int64 tensor on {device}")
+
+
+def lattice_offset(a, b):
+    """Two maps' frames on one lattice -> the integer voxel offset (kx, ky, kz) of b's origin from a's: b's voxel v is a's voxel v +
+    k.  One lattice iff the f32 resolutions are equal and per axis (float64(o_b) - float64(o_a)) / float64(r) lies within 1/256 of
+    an integer (the layer's fixed-point unit); ValueError names the axis and both origins otherwise.  Needs no GPU."""
+    fa, fb = _map_frame(a, "a"), _map_frame(b, "b")
+    ra, rb = np.float32(fa.resolution), np.float32(fb.resolution)
+    if ra != rb:
+        raise ValueError(f"the maps are not on one lattice: their resolutions differ ({float(ra)!r} and {float(rb)!r})")
+    oa, ob = np.asarray(fa.origin, dtype=np.float64), np.asarray(fb.origin, dtype=np.float64)
+    d = (ob - oa) / float(ra)
+    k = np.rint(d)
+    for axis in range(3):
+        if not abs(d[axis] - k[axis]) <= LATTICE_TOLERANCE:
+            raise ValueError(f"the maps are not on one lattice: along {'xyz'[axis]} the origins {tuple(oa.tolist())} and {tuple(ob.tolist())} "
+                             f"lie {d[axis]:.6g} voxels apart, not within 1/256 of an integer")
+    return tuple(int(v) for v in k)
+
+
+def reframed_origin(origin, resolution, shift):
+    """The origin of a box moved by `shift` voxels: float32(float64(origin) + shift * float64(f32 resolution)), the way
+    occupancy_extent forms origins."""
+    o = np.asarray(origin, dtype=np.float32).astype(np.float64)
+    return (o + np.asarray(shift, dtype=np.float64) * float(np.float32(resolution))).astype(np.float32)
+
+
+def position_voxel(frame, position, name="position"):
+    """The voxel of a world position in a map's frame by the f32 index rule (g = (p - origin) / r in f32, in range iff -2048 <= g <
+    4096, voxel = floor(g * 256) >> 8) -> (i, j, k), which may lie outside dims; ValueError for a position that is not three finite
+    numbers or lies beyond the apron."""
+    try:
+        p = np.asarray(position.detach().cpu() if torch.is_tensor(position) else position, dtype=np.float32).reshape(-1)
+    except (TypeError, ValueError):
+        p = np.zeros(0, dtype=np.float32)
+    if p.shape != (3,) or not np.isfinite(p).all():
+        raise ValueError(f"{name} must be three finite numbers, got {position!r}")
+    with np.errstate(all="ignore"):
+        g = ((p - np.asarray(frame.origin, dtype=np.float32)).astype(np.float32) / np.float32(frame.resolution)).astype(np.float32)
+    if not ((g >= np.float32(-2048)) & (g < np.float32(4096))).all():
+        raise ValueError(f"{name} {tuple(p.tolist())} lies beyond the map's apron (voxel indices -2048 .. 4095)")
+    return tuple(int(v) >> 8 for v in np.floor(g * np.float32(256)).astype(np.int64))
+
+
+def check_reframe(map, shift=None, dims=None, centre=None):
+    """reframed's arguments, by name; needs no GPU.  map: an OccupancyGrid, SpaceMap or EvidenceMap.  Exactly one of shift — three
+    integers in [-4096, 4096]: new voxel v is old voxel v + shift — and centre — a world position, three finite numbers within the
+    apron, whose voxel becomes voxel dims // 2 of the new box.  dims: the new box's (check_los's rule), default the map's own.
+    -> (shift, dims, the new origin as a (3,) float32 array); ValueError otherwise."""
+    f = _map_frame(map, "map")
+    d = f.dims if dims is None else check_los(f.origin, f.resolution, dims)[2]
+    if (shift is None) == (centre is None):
+        raise ValueError("give exactly one of shift and centre")
+    if centre is not None:
+        s = tuple(c - n // 2 for c, n in zip(position_voxel(f, centre, "centre"), d))
+    else:
+        try:
+            s = tuple(shift)
+        except TypeError:
+            s = ()
+        if len(s) != 3 or not all(_is_int(v) for v in s):
+            raise ValueError(f"shift must be three integers, got {shift!r}")
+        s = tuple(int(v) for v in s)
+    if not all(-XFER_MAX_SHIFT <= v <= XFER_MAX_SHIFT for v in s):
+        raise ValueError(f"the shift must lie in [-{XFER_MAX_SHIFT}, {XFER_MAX_SHIFT}] voxels per axis, got {s}")
+    origin = reframed_origin(f.origin, f.resolution, s)
+    if not np.isfinite(origin).all():
+        raise ValueError(f"the re-framed origin {tuple(origin.tolist())} is not finite")
+    return s, d, origin
+
+
+def check_merge(a, b, mode=None):
+    """merge's arguments, by name; needs no GPU.  a (written) and b (read): two different maps of one kind — OccupancyGrid, SpaceMap or
+    EvidenceMap — on one device and one lattice (lattice_offset); mode: None for planes, 'confident' or 'add' for evidence.
+    -> (shift, overlap): a's voxel v takes b's voxel v + shift; overlap False where the two boxes share no voxel (nothing to do)."""
+    fa = _map_frame(a, "a")
+    _map_frame(b, "other")
+    if type(a) is not type(b):
+        raise ValueError(f"a {type(a).__name__} merges with its own kind, got {type(b).__name__}")
+    if a is b:
+        raise ValueError("a map cannot be merged into itself")
+    fb = _map_frame(b, "other")
+    if fa.device != fb.device:
+        raise ValueError(f"the maps must live on one device, got {fa.device} and {fb.device}")
+    if isinstance(a, EvidenceMap):
+        if mode not in ("confident", "add"):
+            raise ValueError(f"mode must be 'confident' or 'add', got {mode!r}")
+    elif mode is not None:
+        raise ValueError(f"mode applies to evidence maps only, got {mode!r} for a {type(a).__name__}")
+    k = lattice_offset(a, b)
+    s = tuple(-v for v in k)   # a's voxel v is b's voxel v - k
+    overlap = all(-na < v < nb for v, na, nb in zip(s, fa.dims, fb.dims))   # some v in [0, na) with v + s in [0, nb)
+    return s, overlap
 
 
 def check_occlusion_grid(grid, cloud):

@@ -1612,6 +1612,61 @@ def evidence_scan_ref(L, scanner, points, origin, resolution, dims, params=None,
     return out, counts, skipped, H, M
 
 
+# ---- re-framing and merging maps restated in numpy ("Re-framing and merging maps"): what reframe_kernels.hip must give,
+# bit for bit.  Slices of dense (nx,ny,nz) arrays. -----------------------------------------------------------------------------------
+def shifted_window(src, dst_dims, shift, empty):
+    """The source values of a destination box -> an array of shape dst_dims: voxel v holds src[v + shift] where v + shift lies inside
+    src's shape, `empty` elsewhere."""
+    src = np.asarray(src)
+    out = np.full(tuple(int(d) for d in dst_dims), empty, dtype=src.dtype)
+    to, frm = [], []
+    for nd, ns, s in zip(out.shape, src.shape, (int(v) for v in shift)):
+        lo, hi = max(0, -s), min(nd, ns - s)   # 0 <= v < nd and 0 <= v + s < ns
+        if hi <= lo:
+            return out
+        to.append(slice(lo, hi))
+        frm.append(slice(lo + s, hi + s))
+    out[tuple(to)] = src[tuple(frm)]
+    return out
+
+
+def occ_transfer_ref(bits, dst_bits, shift, mode):
+    """tohip_occ_transfer restated -> (new (dst's shape) bool, count).  bits: the source plane, dst_bits: the destination before (not
+    modified; only its shape matters to 'copy'), shift: three integers — destination voxel v takes source voxel v + shift.  mode
+    'copy': new = the source bits, count = the bits set afterwards; 'or': new = dst | source, count = the bits that were not set."""
+    dst = np.asarray(dst_bits, dtype=bool)
+    S = shifted_window(np.asarray(bits, dtype=bool), dst.shape, shift, False)
+    if mode == "copy":
+        return S, int(S.sum())
+    if mode != "or":
+        raise ValueError(f"mode must be 'copy' or 'or', got {mode!r}")
+    return dst | S, int((S & ~dst).sum())
+
+
+def evidence_transfer_ref(L_src, L_dst, shift, mode, params=None):
+    """tohip_evid_transfer restated -> (L' (dst's shape) int64, counts (4,) int64).  S = the source values (-128 outside the source), D
+    = L_dst (not modified).  'copy': L' = S, counted against an empty destination.  'add': S == -128 leaves D, else clamp((D == -128 ?
+    0 : D) + S, lmin, lmax).  'confident': the larger of D and clamp(S) under the key (|L|, L), -128 below everything.  counts: values
+    that changed, voxels newly known, occupied (L > threshold) voxels that appeared, that vanished."""
+    _, _, lmin, lmax, thr = evidence_params(params)
+    D = np.asarray(L_dst, dtype=np.int64)
+    S = shifted_window(np.asarray(L_src, dtype=np.int64), D.shape, shift, EVID_UNKNOWN)
+    known = S != EVID_UNKNOWN
+    if mode == "copy":
+        D, out = np.full(D.shape, EVID_UNKNOWN, dtype=np.int64), S
+    elif mode == "add":
+        out = np.where(known, np.clip(np.where(D == EVID_UNKNOWN, 0, D) + S, lmin, lmax), D)
+    elif mode == "confident":
+        C = np.where(known, np.clip(S, lmin, lmax), EVID_UNKNOWN)
+        key = lambda L: np.where(L == EVID_UNKNOWN, -1, 2 * np.abs(L) + (L > 0))   # noqa: E731
+        out = np.where(key(C) > key(D), C, D)
+    else:
+        raise ValueError(f"mode must be 'copy', 'add' or 'confident', got {mode!r}")
+    counts = np.array([(out != D).sum(), ((D == EVID_UNKNOWN) & (out != EVID_UNKNOWN)).sum(), ((out > thr) & ~(D > thr)).sum(),
+                       ((D > thr) & ~(out > thr)).sum()], dtype=np.int64)
+    return out, counts
+
+
 def pillar_scan(room, origin, lo, hi):
     """The scan `room` (N,3) taken from `origin` with the axis-aligned box [lo, hi] in the way -> (N,3) f32: a ray origin -> room[i]
     that enters the box (the slab method in f64; the origin lies outside it) returns its entry point instead."""

@@ -335,6 +335,72 @@ def evidence_map(grid_or_points, resolution=0.1, **params):
     return ops.EvidenceMap.like(ops.OccupancyGrid.from_points(grid_or_points, resolution=resolution), **params)
 
 
+MERGE_MAX_DIM = 2048        # of a merged map's box per axis
+MERGE_MAX_VOXELS = 1 << 31
+
+
+def reframe_map(map, shift=None, dims=None, centre=None):
+    """A map's content in another box of its lattice -> a NEW map of the same kind ("Re-framing and merging maps"): an
+    ops.OccupancyGrid, ops.SpaceMap or ops.EvidenceMap (values, both planes, the parameters).  Give exactly one of shift — three
+    integers: new voxel v is old voxel v + shift — or centre, a world position whose voxel becomes the new box's middle voxel dims //
+    2; dims: the new box's (default: the old one's): grow, crop or move.  What leaves the box is dropped, what enters it is empty
+    (unknown).  The old map is untouched; a ClearanceField, TravelField, Components or ModelTraj(clearance_map=) built over it keeps
+    it and is built anew over the new one.  No rotation, no resampling: the move is a whole number of voxels."""
+    ops.check_reframe(map, shift, dims, centre)
+    return map.reframed(shift=shift, dims=dims, centre=centre)
+
+
+def follow_map(map, position, margin):
+    """Keep a map's box around a moving robot: -> `map` itself while position's voxel lies at least `margin` voxels from every side
+    of the box — host arithmetic only, nothing is launched — otherwise map.reframed(centre=position), a new map of the same dims with
+    that voxel in the middle.  margin: an integer, or three (one per axis: a sensor's range along the axes the robot travels, little
+    along the others), each >= 0 and satisfied by the middle voxel itself (margin <= (n - 1) // 2).  A frontier needs unknown space
+    inside the box, so the margin should exceed the sensor's range.  Call it every step: `m = follow_map(m, p, margin)`."""
+    f = ops._map_frame(map, "map")
+    limits = tuple((n - 1) // 2 for n in f.dims)
+    try:
+        ms = (margin,) * 3 if ops._is_int(margin) else tuple(margin)
+    except TypeError:
+        ms = ()
+    if len(ms) != 3 or not all(ops._is_int(m) and 0 <= m <= lim for m, lim in zip(ms, limits)):
+        raise ValueError(f"margin must be an integer or three integers, each in [0, (n - 1) // 2] of its axis — at most {limits} for dims "
+                         f"{tuple(f.dims)} — got {margin!r}")
+    v = ops.position_voxel(f, position)
+    if all(m <= c <= n - 1 - m for c, n, m in zip(v, f.dims, ms)):
+        return map
+    return map.reframed(centre=position)
+
+
+def merge_maps(maps, mode=None):
+    """Fuse a team's maps into one -> a NEW map over the union of their boxes; the inputs are only read.  maps: two or more
+    ops.OccupancyGrids, ops.SpaceMaps or ops.EvidenceMaps (one kind) on one device and one lattice — equal resolutions, origins a
+    whole number of voxels apart (ops.lattice_offset; ValueError names the axis otherwise).  The first map is re-framed into the
+    union box — which keeps its parameters — and the others are merged into it: planes by OR; evidence by mode 'confident' (the
+    default: per voxel the stronger belief wins; any order and any repetition give the same map) or 'add' (independent evidence
+    summed and clamped; a map given twice counts twice).  ValueError if the union exceeds 2048 voxels on an axis or 2^31 voxels."""
+    maps = list(maps)
+    if len(maps) < 2:
+        raise ValueError(f"merge_maps: at least two maps are needed, got {len(maps)}")
+    first = maps[0]
+    evidence = isinstance(first, ops.EvidenceMap)
+    mode = ("confident" if mode is None else mode) if evidence else mode
+    offsets = [(0, 0, 0)]
+    for m in maps[1:]:
+        if m is not first:   # (the first map again: merged into the new map like any other)
+            ops.check_merge(first, m, mode)
+        offsets.append(ops.lattice_offset(first, m))
+    frames = [ops._map_frame(m, "map") for m in maps]
+    lo = tuple(min(o[a] for o in offsets) for a in range(3))
+    hi = tuple(max(o[a] + f.dims[a] for o, f in zip(offsets, frames)) for a in range(3))
+    dims = tuple(h - l for l, h in zip(lo, hi))
+    if max(dims) > MERGE_MAX_DIM or dims[0] * dims[1] * dims[2] > MERGE_MAX_VOXELS:
+        raise ValueError(f"merge_maps: the union box of {dims} voxels exceeds {MERGE_MAX_DIM} per axis or 2^31 voxels")
+    out = first.reframed(shift=lo, dims=dims)
+    for m in maps[1:]:
+        out.merge(m, mode) if evidence else out.merge(m)
+    return out
+
+
 class _Result:
     """What the result classes share: the keyword constructor; each names its fields in its own __slots__."""
     __slots__ = ()
