@@ -41,7 +41,10 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_occ_transfer / tohip_evid_transfer (re-framing and merging maps: voxel content moved from one box into another at
+/* (still 15) + tohip_travel_batch_bytes / tohip_travel_batch_workspace_bytes / tohip_travel_build_batch / tohip_travel_positions_batch /
+ * tohip_travel_paths_batch / tohip_assign_greedy and TOHIP_TRAVEL_MAX_FIELDS (many travel fields built in the same worklist rounds, their
+ * lookups and paths in one launch each, and a deterministic greedy assignment of rows to columns): new symbols only.
+ * (still 15) + tohip_occ_transfer / tohip_evid_transfer (re-framing and merging maps: voxel content moved from one box into another at
  * an integer voxel shift, written or combined): new symbols only.
  * (still 15) + tohip_components_bytes / tohip_components_workspace_bytes / tohip_components_build / tohip_components_stats /
  * tohip_components_min / tohip_components_positions (connected components of a bit plane: a label volume, per-component size, sums,
@@ -1441,6 +1444,44 @@ int tohip_travel_paths(const void *cost, size_t cost_bytes, const void *field, s
                        int64_t n_goals, int64_t max_rows, float *rows, int64_t *counts, void *stream);
 int tohip_view_volume_pick_travel(const int64_t *gains, const int64_t *cost, int64_t weight, int32_t *taken, int64_t n_views,
                                   int64_t min_gain, int32_t round, int32_t *order, int64_t *picked_gain, int32_t *stop, void *stream);
+
+/* ---- travel fields in batches (travel_kernels.hip, DESIGN.md §10, "Travel fields in batches") --------------
+ * Many-to-all: n_fields (1 .. TOHIP_TRAVEL_MAX_FIELDS) travel fields over ONE traversable set T, built in the same worklist rounds.
+ * T, the move rule, the weights, limit and the sentinel are tohip_travel_build's.  cost holds the fields one after the other, each
+ * in the single field's layout: field b starts at word b nx ny nz (64-bit indices), tohip_travel_batch_bytes = n_fields 4 nx ny nz
+ * (0 for bad dims or a bad n_fields).  source_field (DEVICE int32 x n_sources): source i seeds field source_field[i]; it is seeded
+ * iff 0 <= source_field[i] < n_fields and tohip_travel_build's seeding rule holds, else it is ignored and seeded[i] = 0.  A field
+ * may have several sources or none (it stays all sentinel).  Field b is bit for bit what tohip_travel_build writes from the sources
+ * that name b: each field is the same unique fixed point, and fields share no cost word.
+ * One worklist: a work item is (field, tile), packed b n_tiles + t in the bitmaps and the list — n_fields n_tiles must fit 31 bits
+ * (TOHIP_EINVAL; tohip_travel_batch_workspace_bytes is 0 then).  A round is two launches for all fields together, one status word
+ * comes back per rounds_per_check rounds, *rounds_host = the rounds that had work.  A cost_bytes or workspace_bytes too small is
+ * TOHIP_EINVAL.
+ * tohip_travel_positions_batch: cost_out (n_fields, m) int64 and / or dist (n_fields, m) f32: row b is tohip_travel_positions on
+ * field b.  One launch.
+ * tohip_travel_paths_batch: tohip_travel_paths with goal_field (DEVICE int32 x n_goals), the field goal e is walked in; one out of
+ * [0, n_fields) gives counts[e] = 0.  One launch.
+ * tohip_assign_greedy: cost (n_rows, ld >= n_cols) int64 on the device, 1 <= n_rows <= 64, 1 <= n_cols <= 4096, min_cost >= 0.  A pair
+ * (r, c) is a candidate iff cost[r][c] >= min_cost (negative entries: none).  Starting with nothing assigned, the candidate with the
+ * smallest key (cost, r, c) among those whose row is unassigned and whose column is unclaimed is assigned, until none is left.
+ * col_of_row (n_rows) and row_of_col (n_cols): int32, -1 where nothing was assigned.  One launch of one block, integers only.
+ * Every argument check returns before anything is enqueued. */
+#define TOHIP_TRAVEL_MAX_FIELDS 256
+size_t tohip_travel_batch_bytes(int32_t nx, int32_t ny, int32_t nz, int32_t n_fields);
+size_t tohip_travel_batch_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, int32_t n_fields);
+int tohip_travel_build_batch(const void *field, size_t field_bytes, const void *occupied_or_null, const void *free_or_null,
+                             size_t grid_bytes, const tohip_occ_geom *geom, int32_t need2, const float *sources,
+                             const int32_t *source_field, int64_t n_sources, int32_t n_fields, int64_t limit, int32_t rounds_per_check,
+                             void *cost, size_t cost_bytes, void *workspace, size_t workspace_bytes, uint8_t *seeded,
+                             int64_t *rounds_host, void *stream);
+int tohip_travel_positions_batch(const void *cost, size_t cost_bytes, const tohip_occ_geom *geom, int32_t n_fields,
+                                 const float *positions, int64_t m, int64_t *cost_out, float *dist, void *stream);
+int tohip_travel_paths_batch(const void *cost, size_t cost_bytes, const void *field, size_t field_bytes, const void *occupied_or_null,
+                             const void *free_or_null, size_t grid_bytes, const tohip_occ_geom *geom, int32_t need2, int32_t n_fields,
+                             const float *goals, const int32_t *goal_field, int64_t n_goals, int64_t max_rows, float *rows,
+                             int64_t *counts, void *stream);
+int tohip_assign_greedy(const int64_t *cost, int32_t n_rows, int32_t n_cols, int64_t ld, int64_t min_cost, int32_t *col_of_row,
+                        int32_t *row_of_col, void *stream);
 
 /* ---- connected components (components_kernels.hip, DESIGN.md §10, "Connected components") ----------------
  * Which voxels belong together?  plane: any bit plane of the occupancy layout (grid_bytes; header and pad bits 0, as every producer

@@ -11,7 +11,8 @@
 //
 //   k_travel_fill     every word of cost <- the sentinel (grid-stride, 64-bit index).
 //   k_travel_seed     one lane per source: a position in range whose voxel lies inside dims and in T gets cost 0, seeded[i] = 1 and
-//                     its tile's bit in bitmap 0; any other source is ignored, seeded[i] = 0.
+//                     the bit in bitmap 0 of its tile and of every neighbouring tile whose halo it lies in; any other source is
+//                     ignored, seeded[i] = 0.
 //   k_travel_compact  one lane per word of the round's bitmap: the set bits become entries of the tile list (an integer atomic add
 //                     per word reserves their places; the order of the list is of no consequence), the word is cleared.
 //   k_travel_relax    one block per listed tile of 8 x 8 x 8 voxels (a block strides over the list), two voxels per lane.  The
@@ -26,6 +27,12 @@
 //   k_travel_paths    one wave per goal: lanes 0 .. 26 (13 idle) each test one move against the path rule — allowed, and cost[u] +
 //                     w == cost[v] — and a ballot names the lowest; rows are the voxel centres from the goal to its source.
 //   k_view_volume_pick_travel   k_view_volume_pick with a cost row: gain 2^20 - m cost decides, among the reachable candidates.
+//   k_assign_greedy   one block: rows (robots) take columns (openings) in ascending order of the key (cost, row, column).
+//
+// FIELDS IN BATCHES ("Travel fields in batches"): n_fields cost volumes one after the other (field b starts at word b
+// nx ny nz), one T, one worklist.  A work item is (field, tile) packed as b n_tiles + t — a bit of the bitmaps, an entry of the list —
+// and the kernels above are the batch's: the single build is their n_fields = 1 (b = 0 everywhere, the same words in the same order).
+// Fields share no cost word, so the fixed-point argument holds field by field.
 //
 // Every kernel ends on its own: no block waits for another.  No float atomics, no process-wide state; every argument check returns
 // before anything is enqueued.
@@ -39,8 +46,11 @@ constexpr int kTravelHalo = kTravelTile + 2;
 constexpr int kTravelHaloN = kTravelHalo * kTravelHalo * kTravelHalo;
 constexpr int kTravelRelaxBlocks = 4096;              // blocks of a relax launch: they stride over the list
 constexpr size_t kTravelHdr = 256;                    // [0] u64 status = rounds with work << 32 | tiles of the last round;
-                                                      // [2], [3] u32 the two rounds' list counts; [4] u32 rounds with work
+                                                      // [2], [3] u32 the two rounds' list counts; [4] u32 rounds with work;
+                                                      // [5] u32 the most items of one round; [6] u64 the items of all rounds
+                                                      // (what tools/time_travel_batch.py reads: items per round)
 constexpr int kTravelMaxRoundsPerCheck = 65536;
+constexpr long long kTravelMaxItems = 0x7fffffffll;   // (field, tile) items of a batch: a list entry is an int
 
 struct TravelTiles { long long ntx, nty, ntz, n, words; };
 inline TravelTiles travel_tiles(int64_t nx, int64_t ny, int64_t nz) {
@@ -51,7 +61,7 @@ inline TravelTiles travel_tiles(int64_t nx, int64_t ny, int64_t nz) {
     return t;
 }
 inline size_t travel_align(size_t b) { return (b + 255) & ~(size_t)255; }
-inline size_t travel_bitmap_bytes(const TravelTiles& t) { return travel_align((size_t)t.words * 4); }
+inline size_t travel_bitmap_bytes(const TravelTiles& t, int n_fields = 1) { return travel_align((size_t)t.words * 4 * (size_t)n_fields); }
 
 // what decides T, in one argument
 struct TravelSet {
@@ -98,16 +108,29 @@ __global__ void __launch_bounds__(TO_BLOCK) k_travel_fill(unsigned* __restrict__
 }
 
 __global__ void __launch_bounds__(TO_BLOCK)
-k_travel_seed(TravelSet s, const float* __restrict__ src, long long n_src, unsigned* __restrict__ cost, unsigned* __restrict__ bitmap,
-              long long ntx, long long nty, uint8_t* __restrict__ seeded) {
+k_travel_seed(TravelSet s, const float* __restrict__ src, const int* __restrict__ src_field, int n_fields, long long n_src,
+              unsigned* __restrict__ cost, long long n_vox, unsigned* __restrict__ bitmap, long long ntx, long long nty, long long n_tiles,
+              uint8_t* __restrict__ seeded) {
     const long long stride = (long long)gridDim.x * TO_BLOCK;
     for (long long i = (long long)blockIdx.x * TO_BLOCK + threadIdx.x; i < n_src; i += stride) {
         int x, y, z;
-        const bool ok = occ_locate(s.g, src + 3 * i, x, y, z) == kOccInside && travel_in_set(s, x, y, z);
+        const int b = src_field ? src_field[i] : 0;   // (no row of fields: the single build, field 0)
+        const bool ok = b >= 0 && b < n_fields && occ_locate(s.g, src + 3 * i, x, y, z) == kOccInside && travel_in_set(s, x, y, z);
         if (ok) {
-            cost[field_index(s.g, x, y, z)] = 0u;   // (two sources in one voxel store the same word)
-            const long long t = ((long long)(z >> 3) * nty + (y >> 3)) * ntx + (x >> 3);
-            __hip_atomic_fetch_or(bitmap + (t >> 5), 1u << (t & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            cost[b * n_vox + field_index(s.g, x, y, z)] = 0u;   // (two sources in one voxel store the same word)
+            // its tile, and every neighbouring tile whose halo it lies in: a seed in a border layer whose neighbours inside its own
+            // tile are all closed lowers nothing there, so the relaxation of its own tile alone would never wake the tile next door
+            const long long ntz = n_tiles / (ntx * nty);
+            const int tx = x >> 3, ty = y >> 3, tz = z >> 3;
+            const int ax = (x & 7) == 0 ? -1 : ((x & 7) == 7 ? 1 : 0), ay = (y & 7) == 0 ? -1 : ((y & 7) == 7 ? 1 : 0),
+                      az = (z & 7) == 0 ? -1 : ((z & 7) == 7 ? 1 : 0);
+            for (int k = 0; k < 8; ++k) {
+                if (((k & 1) && ax == 0) || ((k & 2) && ay == 0) || ((k & 4) && az == 0)) continue;
+                const int ux = tx + ((k & 1) ? ax : 0), uy = ty + ((k & 2) ? ay : 0), uz = tz + ((k & 4) ? az : 0);
+                if ((unsigned)ux >= (unsigned)ntx || (unsigned)uy >= (unsigned)nty || (unsigned)uz >= (unsigned)ntz) continue;
+                const long long t = b * n_tiles + ((long long)uz * nty + uy) * ntx + ux;
+                __hip_atomic_fetch_or(bitmap + (t >> 5), 1u << (t & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
         }
         if (seeded) seeded[i] = ok ? 1 : 0;
     }
@@ -125,13 +148,13 @@ k_travel_compact(unsigned* __restrict__ bitmap, long long words, int* __restrict
     while (bits != 0u) {
         const int b = __ffs(bits) - 1;
         bits &= bits - 1u;
-        list[at++] = (int)(w * 32 + b);   // (at most 2^22 tiles)
+        list[at++] = (int)(w * 32 + b);   // (at most 2^31 - 1 items)
     }
 }
 
 __global__ void __launch_bounds__(TO_BLOCK)
-k_travel_relax(TravelSet s, unsigned* cost, unsigned limit, const int* __restrict__ list, unsigned* __restrict__ hdr32, int parity,
-               unsigned* __restrict__ next, int ntx, int nty, int ntz) {
+k_travel_relax(TravelSet s, unsigned* cost_all, long long n_vox, unsigned limit, const int* __restrict__ list, unsigned* __restrict__ hdr32,
+               int parity, unsigned* __restrict__ next_all, int ntx, int nty, int ntz, int n_tiles) {
     __shared__ unsigned s_cost[kTravelHaloN];
     __shared__ unsigned char s_in[kTravelHaloN];
     __shared__ unsigned s_touch;
@@ -143,10 +166,15 @@ k_travel_relax(TravelSet s, unsigned* cost, unsigned limit, const int* __restric
         hdr32[4] = rounds;
         hdr32[0] = count;
         hdr32[1] = rounds;
+        if (count > hdr32[5]) hdr32[5] = count;
+        *(unsigned long long*)(hdr32 + 6) += count;
     }
     const OccGeom& g = s.g;
     for (unsigned item = blockIdx.x; item < count; item += gridDim.x) {
-        const int t = list[item];
+        const int e = list[item];
+        const int fb = e / n_tiles, t = e - fb * n_tiles;   // the item's field and tile
+        unsigned* cost = cost_all + fb * n_vox;
+        const long long next_at = (long long)fb * n_tiles;
         const int tx = t % ntx, ty = (t / ntx) % nty, tz = t / (ntx * nty);
         const int x0 = tx * kTravelTile - 1, y0 = ty * kTravelTile - 1, z0 = tz * kTravelTile - 1;   // the halo's corner
         if (threadIdx.x == 0) s_touch = 0u;
@@ -224,8 +252,8 @@ k_travel_relax(TravelSet s, unsigned* cost, unsigned limit, const int* __restric
         if (threadIdx.x < 27 && threadIdx.x != 13 && ((s_touch >> threadIdx.x) & 1u)) {
             const int ux = tx + travel_dx(threadIdx.x), uy = ty + travel_dy(threadIdx.x), uz = tz + travel_dz(threadIdx.x);
             if ((unsigned)ux < (unsigned)ntx && (unsigned)uy < (unsigned)nty && (unsigned)uz < (unsigned)ntz) {
-                const int u = (uz * nty + uy) * ntx + ux;
-                __hip_atomic_fetch_or(next + (u >> 5), 1u << (u & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const long long u = next_at + (uz * nty + uy) * ntx + ux;
+                __hip_atomic_fetch_or(next_all + (u >> 5), 1u << (u & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
         __syncthreads();   // (s_touch and the halo block are the next item's)
@@ -240,14 +268,16 @@ __device__ __forceinline__ float travel_metres(long long c, float r) {
 }
 
 __global__ void __launch_bounds__(TO_BLOCK)
-k_travel_positions(const unsigned* __restrict__ cost, OccGeom g, const float* __restrict__ pos, long long m, long long* __restrict__ cost_out,
-                   float* __restrict__ dist_out) {
+k_travel_positions(const unsigned* __restrict__ cost, long long n_vox, OccGeom g, const float* __restrict__ pos, long long m, long long total,
+                   long long* __restrict__ cost_out, float* __restrict__ dist_out) {
+    // total = n_fields m: row b of the outputs is field b's answer
     const long long stride = (long long)gridDim.x * TO_BLOCK;
-    for (long long i = (long long)blockIdx.x * TO_BLOCK + threadIdx.x; i < m; i += stride) {
+    for (long long i = (long long)blockIdx.x * TO_BLOCK + threadIdx.x; i < total; i += stride) {
         int x, y, z;
         long long c = -2;
-        if (occ_locate(g, pos + 3 * i, x, y, z) == kOccInside) {
-            const unsigned v = cost[field_index(g, x, y, z)];
+        const long long b = i / m;
+        if (occ_locate(g, pos + 3 * (i - b * m), x, y, z) == kOccInside) {
+            const unsigned v = cost[b * n_vox + field_index(g, x, y, z)];
             c = v == kTravelSentinel ? -1 : (long long)v;
         }
         if (cost_out) cost_out[i] = c;
@@ -258,15 +288,18 @@ k_travel_positions(const unsigned* __restrict__ cost, OccGeom g, const float* __
 // one wave per goal; rows (n_goals, max_rows, 3): the voxel centres goal -> source; counts: rows, 0 unreachable (or the goal out of
 // range or outside dims), -needed where the path does not fit
 __global__ void __launch_bounds__(TO_BLOCK)
-k_travel_paths(TravelSet s, const unsigned* __restrict__ cost, const float* __restrict__ goals, long long n_goals, long long max_rows,
-               float* __restrict__ rows, long long* __restrict__ counts) {
+k_travel_paths(TravelSet s, const unsigned* __restrict__ cost_all, long long n_vox, const float* __restrict__ goals,
+               const int* __restrict__ goal_field, int n_fields, long long n_goals, long long max_rows, float* __restrict__ rows,
+               long long* __restrict__ counts) {
     const int lane = threadIdx.x & 63;
     const long long goal = (long long)blockIdx.x * (TO_BLOCK / 64) + (threadIdx.x >> 6);
     if (goal >= n_goals) return;   // (a whole wave)
     const OccGeom& g = s.g;
     int x, y, z;
     long long n = 0;
-    if (occ_locate(g, goals + 3 * goal, x, y, z) == kOccInside) {
+    const int fb = goal_field ? goal_field[goal] : 0;   // the field the goal is walked in (no row of fields: field 0)
+    const unsigned* cost = cost_all + (fb >= 0 && fb < n_fields ? fb : 0) * n_vox;
+    if (fb >= 0 && fb < n_fields && occ_locate(g, goals + 3 * goal, x, y, z) == kOccInside) {
         unsigned here = cost[field_index(g, x, y, z)];
         if (here != kTravelSentinel) {
             float* out = rows + goal * max_rows * 3;
@@ -336,7 +369,76 @@ k_view_volume_pick_travel(const long long* __restrict__ gains, const long long* 
     }
 }
 
+constexpr int kAssignMaxRows = 64;
+constexpr int kAssignMaxCols = 4096;
+
+// the smaller of two (cost, index) keys, across a wave; cost < 0: none
+__device__ __forceinline__ void assign_wave_min(long long& c, int& at) {
+    for (int sh = 32; sh > 0; sh >>= 1) {
+        const long long oc = __shfl_xor(c, sh);
+        const int oat = __shfl_xor(at, sh);
+        if (oc >= 0 && (c < 0 || oc < c || (oc == c && oat < at))) { c = oc; at = oat; }
+    }
+}
+
+// greedy assignment in one block: every open row keeps its best unclaimed column (the smallest (cost, column)); the smallest
+// (cost, row) among those is the smallest (cost, row, column) of all candidates and is assigned; only the rows whose best column
+// was just claimed look again.  Integers only: the same answer in every run.
+__global__ void __launch_bounds__(TO_BLOCK)
+k_assign_greedy(const long long* __restrict__ cost, int n_rows, int n_cols, long long ld, long long min_cost, int* __restrict__ col_of_row,
+                int* __restrict__ row_of_col) {
+    __shared__ unsigned char s_claimed[kAssignMaxCols];
+    __shared__ long long s_best[kAssignMaxRows];
+    __shared__ int s_col[kAssignMaxRows];
+    __shared__ unsigned char s_look[kAssignMaxRows];   // 1: the row must look for its best column (again)
+    __shared__ unsigned char s_open[kAssignMaxRows];   // 1: the row is unassigned and may still have a candidate
+    __shared__ int s_win;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int c = threadIdx.x; c < n_cols; c += TO_BLOCK) { s_claimed[c] = 0; row_of_col[c] = -1; }
+    for (int r = threadIdx.x; r < n_rows; r += TO_BLOCK) { s_look[r] = 1; s_open[r] = 1; col_of_row[r] = -1; }
+    __syncthreads();
+    for (;;) {
+        for (int r = wave; r < n_rows; r += TO_BLOCK / 64) {   // (uniform per wave)
+            if (!s_open[r] || !s_look[r]) continue;
+            long long best = -1;
+            int at = -1;
+            for (int c = lane; c < n_cols; c += 64) {   // (ascending: the first of equal costs stays)
+                const long long v = cost[r * ld + c];
+                if (v >= min_cost && !s_claimed[c] && (best < 0 || v < best)) { best = v; at = c; }
+            }
+            assign_wave_min(best, at);
+            if (lane == 0) {
+                s_best[r] = best;
+                s_col[r] = at;
+                s_look[r] = 0;
+                if (best < 0) s_open[r] = 0;   // no candidate now: none later, columns are only ever claimed
+            }
+        }
+        __syncthreads();
+        if (wave == 0) {
+            long long best = lane < n_rows && s_open[lane] ? s_best[lane] : -1;
+            int at = lane;
+            assign_wave_min(best, at);
+            if (lane == 0) s_win = best < 0 ? -1 : at;
+        }
+        __syncthreads();
+        const int win = s_win;
+        if (win < 0) return;   // (uniform)
+        const int col = s_col[win];
+        __syncthreads();       // (everyone has read the winner before it changes)
+        if (threadIdx.x == 0) {
+            col_of_row[win] = col;
+            row_of_col[col] = win;
+            s_claimed[col] = 1;
+            s_open[win] = 0;
+        }
+        if (threadIdx.x < n_rows && threadIdx.x != win && s_open[threadIdx.x] && s_col[threadIdx.x] == col) s_look[threadIdx.x] = 1;
+        __syncthreads();
+    }
+}
+
 inline size_t travel_cost_bytes(const OccGeom& g) { return field_voxels(g) * sizeof(uint32_t); }
+inline bool travel_fields_ok(int64_t n_fields) { return n_fields >= 1 && n_fields <= TOHIP_TRAVEL_MAX_FIELDS; }
 
 // the field, the planes and the geometry of a call -> its TravelSet (argument checks only)
 inline int travel_set(const void* field, size_t field_bytes, const void* occupied_or_null, const void* free_or_null, size_t grid_bytes,
@@ -364,30 +466,19 @@ extern "C" size_t tohip_travel_bytes(int32_t nx, int32_t ny, int32_t nz) {
     return occ_dims_ok(nx, ny, nz) ? field_voxels(nx, ny, nz) * sizeof(uint32_t) : 0;
 }
 
-extern "C" size_t tohip_travel_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) {
-    if (!occ_dims_ok(nx, ny, nz)) return 0;
+namespace {
+
+inline size_t travel_workspace_bytes(int64_t nx, int64_t ny, int64_t nz, int n_fields) {
     const TravelTiles t = travel_tiles(nx, ny, nz);
-    return kTravelHdr + 2 * travel_bitmap_bytes(t) + travel_align((size_t)t.n * sizeof(int32_t));
+    return kTravelHdr + 2 * travel_bitmap_bytes(t, n_fields) + travel_align((size_t)t.n * (size_t)n_fields * sizeof(int32_t));
 }
 
-extern "C" int tohip_travel_build(const void* field, size_t field_bytes, const void* occupied_or_null, const void* free_or_null,
-                                  size_t grid_bytes, const tohip_occ_geom* geom, int32_t need2, const float* sources, int64_t n_sources,
-                                  int64_t limit, int32_t rounds_per_check, void* cost, size_t cost_bytes, void* workspace,
-                                  size_t workspace_bytes, uint8_t* seeded, int64_t* rounds_host, void* stream_) {
-    TravelSet s;
-    const int rc = travel_set(field, field_bytes, occupied_or_null, free_or_null, grid_bytes, geom, need2, s);
-    if (rc != TOHIP_OK) return rc;
-    if (!sources || n_sources < 1 || !occ_count_ok(n_sources) || limit < 0 || limit > kTravelMaxLimit || rounds_per_check < 1 ||
-        rounds_per_check > kTravelMaxRoundsPerCheck || !cost || !workspace)
-        return TOHIP_EINVAL;
-    const void* ins[3] = {field, occupied_or_null, free_or_null};
-    for (const void* p : ins)
-        if (p && (p == cost || p == workspace)) return TOHIP_EINVAL;
-    if (cost == workspace) return TOHIP_EINVAL;
-    if (cost_bytes < travel_cost_bytes(s.g) || workspace_bytes < tohip_travel_workspace_bytes(s.g.nx, s.g.ny, s.g.nz)) return TOHIP_ENOSPC;
-    hipStream_t st = (hipStream_t)stream_;
+// the build of n_fields fields in the same rounds; source_field null: every source seeds field 0 (the single build)
+int travel_build(const TravelSet& s, const float* sources, const int32_t* source_field, int64_t n_sources, int n_fields, int64_t limit,
+                 int32_t rounds_per_check, void* cost, void* workspace, uint8_t* seeded, int64_t* rounds_host, hipStream_t st) {
     const TravelTiles t = travel_tiles(s.g.nx, s.g.ny, s.g.nz);
-    const size_t bm = travel_bitmap_bytes(t);
+    const size_t bm = travel_bitmap_bytes(t, n_fields);
+    const long long items = t.n * n_fields, words = (items + 31) / 32;
     unsigned* hdr32 = (unsigned*)workspace;
     unsigned* bitmap[2] = {(unsigned*)((char*)workspace + kTravelHdr), (unsigned*)((char*)workspace + kTravelHdr + bm)};
     int* list = (int*)((char*)workspace + kTravelHdr + 2 * bm);
@@ -395,22 +486,23 @@ extern "C" int tohip_travel_build(const void* field, size_t field_bytes, const v
     hipError_t e = hipMemsetAsync(workspace, 0, kTravelHdr + 2 * bm, st);
     if (e != hipSuccess) return (int)e;
     const long long n_vox = (long long)field_voxels(s.g);
-    k_travel_fill<<<occ_grid_blocks(n_vox), TO_BLOCK, 0, st>>>(c, n_vox);
+    k_travel_fill<<<occ_grid_blocks(n_vox * n_fields), TO_BLOCK, 0, st>>>(c, n_vox * n_fields);
     TO_HIP_CHECK_LAUNCH();
-    k_travel_seed<<<occ_grid_blocks(n_sources), TO_BLOCK, 0, st>>>(s, sources, n_sources, c, bitmap[0], t.ntx, t.nty, seeded);
+    k_travel_seed<<<occ_grid_blocks(n_sources), TO_BLOCK, 0, st>>>(s, sources, source_field, n_fields, n_sources, c, n_vox, bitmap[0], t.ntx,
+                                                                  t.nty, t.n, seeded);
     TO_HIP_CHECK_LAUNCH();
-    const unsigned compact_blocks = (unsigned)((t.words + TO_BLOCK - 1) / TO_BLOCK);
-    const unsigned relax_blocks = (unsigned)(t.n < kTravelRelaxBlocks ? t.n : kTravelRelaxBlocks);
+    const unsigned compact_blocks = (unsigned)((words + TO_BLOCK - 1) / TO_BLOCK);
+    const unsigned relax_blocks = (unsigned)(items < kTravelRelaxBlocks ? items : kTravelRelaxBlocks);
     int parity = 0;
     for (;;) {
         for (int r = 0; r < rounds_per_check; ++r, parity ^= 1) {
-            k_travel_compact<<<compact_blocks, TO_BLOCK, 0, st>>>(bitmap[parity], t.words, list, hdr32 + 2 + parity);
+            k_travel_compact<<<compact_blocks, TO_BLOCK, 0, st>>>(bitmap[parity], words, list, hdr32 + 2 + parity);
             TO_HIP_CHECK_LAUNCH();
-            k_travel_relax<<<relax_blocks, TO_BLOCK, 0, st>>>(s, c, (unsigned)limit, list, hdr32, parity, bitmap[parity ^ 1], (int)t.ntx,
-                                                              (int)t.nty, (int)t.ntz);
+            k_travel_relax<<<relax_blocks, TO_BLOCK, 0, st>>>(s, c, n_vox, (unsigned)limit, list, hdr32, parity, bitmap[parity ^ 1], (int)t.ntx,
+                                                              (int)t.nty, (int)t.ntz, (int)t.n);
             TO_HIP_CHECK_LAUNCH();
         }
-        // one word back: the tiles the last round worked on (none: nothing was activated after it) and the rounds that had work
+        // one word back: the items the last round worked on (none: nothing was activated after it) and the rounds that had work
         int64_t status = 0;
         const int back = occ_read_back(&status, workspace, st);
         if (back != TOHIP_OK) return back;
@@ -421,33 +513,134 @@ extern "C" int tohip_travel_build(const void* field, size_t field_bytes, const v
     }
 }
 
-extern "C" int tohip_travel_positions(const void* cost, size_t cost_bytes, const tohip_occ_geom* geom, const float* positions, int64_t m,
-                                      int64_t* cost_out, float* dist, void* stream_) {
+// what the single and the batched build ask of their arguments alike (T is checked before)
+inline int travel_build_check(const void* field, const void* occupied_or_null, const void* free_or_null, const float* sources, int64_t n_sources,
+                              int64_t limit, int32_t rounds_per_check, const void* cost, const void* workspace) {
+    if (!sources || n_sources < 1 || !occ_count_ok(n_sources) || limit < 0 || limit > kTravelMaxLimit || rounds_per_check < 1 ||
+        rounds_per_check > kTravelMaxRoundsPerCheck || !cost || !workspace)
+        return TOHIP_EINVAL;
+    const void* ins[3] = {field, occupied_or_null, free_or_null};
+    for (const void* p : ins)
+        if (p && (p == cost || p == workspace)) return TOHIP_EINVAL;
+    if (cost == workspace) return TOHIP_EINVAL;
+    return TOHIP_OK;
+}
+
+}  // namespace
+
+extern "C" size_t tohip_travel_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) {
+    return occ_dims_ok(nx, ny, nz) ? travel_workspace_bytes(nx, ny, nz, 1) : 0;
+}
+
+extern "C" size_t tohip_travel_batch_bytes(int32_t nx, int32_t ny, int32_t nz, int32_t n_fields) {
+    return occ_dims_ok(nx, ny, nz) && travel_fields_ok(n_fields) ? field_voxels(nx, ny, nz) * sizeof(uint32_t) * (size_t)n_fields : 0;
+}
+
+extern "C" size_t tohip_travel_batch_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, int32_t n_fields) {
+    if (!occ_dims_ok(nx, ny, nz) || !travel_fields_ok(n_fields) || travel_tiles(nx, ny, nz).n * n_fields > kTravelMaxItems) return 0;
+    return travel_workspace_bytes(nx, ny, nz, n_fields);
+}
+
+extern "C" int tohip_travel_build(const void* field, size_t field_bytes, const void* occupied_or_null, const void* free_or_null,
+                                  size_t grid_bytes, const tohip_occ_geom* geom, int32_t need2, const float* sources, int64_t n_sources,
+                                  int64_t limit, int32_t rounds_per_check, void* cost, size_t cost_bytes, void* workspace,
+                                  size_t workspace_bytes, uint8_t* seeded, int64_t* rounds_host, void* stream_) {
+    TravelSet s;
+    int rc = travel_set(field, field_bytes, occupied_or_null, free_or_null, grid_bytes, geom, need2, s);
+    if (rc != TOHIP_OK) return rc;
+    rc = travel_build_check(field, occupied_or_null, free_or_null, sources, n_sources, limit, rounds_per_check, cost, workspace);
+    if (rc != TOHIP_OK) return rc;
+    if (cost_bytes < travel_cost_bytes(s.g) || workspace_bytes < travel_workspace_bytes(s.g.nx, s.g.ny, s.g.nz, 1)) return TOHIP_ENOSPC;
+    return travel_build(s, sources, nullptr, n_sources, 1, limit, rounds_per_check, cost, workspace, seeded, rounds_host, (hipStream_t)stream_);
+}
+
+extern "C" int tohip_travel_build_batch(const void* field, size_t field_bytes, const void* occupied_or_null, const void* free_or_null,
+                                        size_t grid_bytes, const tohip_occ_geom* geom, int32_t need2, const float* sources,
+                                        const int32_t* source_field, int64_t n_sources, int32_t n_fields, int64_t limit,
+                                        int32_t rounds_per_check, void* cost, size_t cost_bytes, void* workspace, size_t workspace_bytes,
+                                        uint8_t* seeded, int64_t* rounds_host, void* stream_) {
+    TravelSet s;
+    int rc = travel_set(field, field_bytes, occupied_or_null, free_or_null, grid_bytes, geom, need2, s);
+    if (rc != TOHIP_OK) return rc;
+    rc = travel_build_check(field, occupied_or_null, free_or_null, sources, n_sources, limit, rounds_per_check, cost, workspace);
+    if (rc != TOHIP_OK) return rc;
+    if (!source_field || !travel_fields_ok(n_fields) || travel_tiles(s.g.nx, s.g.ny, s.g.nz).n * n_fields > kTravelMaxItems) return TOHIP_EINVAL;
+    if (cost_bytes < travel_cost_bytes(s.g) * (size_t)n_fields || workspace_bytes < travel_workspace_bytes(s.g.nx, s.g.ny, s.g.nz, n_fields))
+        return TOHIP_EINVAL;
+    return travel_build(s, sources, source_field, n_sources, n_fields, limit, rounds_per_check, cost, workspace, seeded, rounds_host,
+                        (hipStream_t)stream_);
+}
+
+namespace {
+
+int travel_positions(const void* cost, size_t cost_bytes, const tohip_occ_geom* geom, int64_t n_fields, const float* positions, int64_t m,
+                     int64_t* cost_out, float* dist, void* stream_) {
     OccGeom g;
     const int rc = occ_check(cost, ~(size_t)0, geom, g);
     if (rc != TOHIP_OK) return rc;
-    if (cost_bytes < travel_cost_bytes(g)) return TOHIP_ENOSPC;
-    if (!occ_count_ok(m) || (m > 0 && (!positions || (!cost_out && !dist)))) return TOHIP_EINVAL;
+    if (!travel_fields_ok(n_fields)) return TOHIP_EINVAL;
+    if (cost_bytes < travel_cost_bytes(g) * (size_t)n_fields) return TOHIP_ENOSPC;
+    if (!occ_count_ok(m) || !occ_count_ok(m * n_fields) || (m > 0 && (!positions || (!cost_out && !dist)))) return TOHIP_EINVAL;
     if (m == 0) return TOHIP_OK;
-    k_travel_positions<<<occ_grid_blocks(m), TO_BLOCK, 0, (hipStream_t)stream_>>>((const unsigned*)cost, g, positions, m, (long long*)cost_out,
-                                                                                 dist);
+    k_travel_positions<<<occ_grid_blocks(m * n_fields), TO_BLOCK, 0, (hipStream_t)stream_>>>(
+        (const unsigned*)cost, (long long)field_voxels(g), g, positions, m, m * n_fields, (long long*)cost_out, dist);
     TO_HIP_CHECK_LAUNCH();
     return TOHIP_OK;
+}
+
+int travel_paths(const void* cost, size_t cost_bytes, const void* field, size_t field_bytes, const void* occupied_or_null,
+                 const void* free_or_null, size_t grid_bytes, const tohip_occ_geom* geom, int32_t need2, int64_t n_fields, const float* goals,
+                 const int32_t* goal_field, int64_t n_goals, int64_t max_rows, float* rows, int64_t* counts, void* stream_) {
+    TravelSet s;
+    const int rc = travel_set(field, field_bytes, occupied_or_null, free_or_null, grid_bytes, geom, need2, s);
+    if (rc != TOHIP_OK) return rc;
+    if (!cost || !travel_fields_ok(n_fields) || n_goals < 0 || n_goals > (int64_t)1 << 30 || max_rows < 1 || max_rows > (int64_t)1 << 31 ||
+        (n_goals > 0 && (!goals || !rows || !counts)))
+        return TOHIP_EINVAL;
+    if (cost_bytes < travel_cost_bytes(s.g) * (size_t)n_fields) return TOHIP_ENOSPC;
+    if (n_goals == 0) return TOHIP_OK;
+    const unsigned blocks = (unsigned)((n_goals + TO_BLOCK / 64 - 1) / (TO_BLOCK / 64));
+    k_travel_paths<<<blocks, TO_BLOCK, 0, (hipStream_t)stream_>>>(s, (const unsigned*)cost, (long long)field_voxels(s.g), goals, goal_field,
+                                                                  (int)n_fields, n_goals, max_rows, rows, (long long*)counts);
+    TO_HIP_CHECK_LAUNCH();
+    return TOHIP_OK;
+}
+
+}  // namespace
+
+extern "C" int tohip_travel_positions(const void* cost, size_t cost_bytes, const tohip_occ_geom* geom, const float* positions, int64_t m,
+                                      int64_t* cost_out, float* dist, void* stream_) {
+    return travel_positions(cost, cost_bytes, geom, 1, positions, m, cost_out, dist, stream_);
+}
+
+extern "C" int tohip_travel_positions_batch(const void* cost, size_t cost_bytes, const tohip_occ_geom* geom, int32_t n_fields,
+                                            const float* positions, int64_t m, int64_t* cost_out, float* dist, void* stream_) {
+    return travel_positions(cost, cost_bytes, geom, n_fields, positions, m, cost_out, dist, stream_);
 }
 
 extern "C" int tohip_travel_paths(const void* cost, size_t cost_bytes, const void* field, size_t field_bytes, const void* occupied_or_null,
                                   const void* free_or_null, size_t grid_bytes, const tohip_occ_geom* geom, int32_t need2, const float* goals,
                                   int64_t n_goals, int64_t max_rows, float* rows, int64_t* counts, void* stream_) {
-    TravelSet s;
-    const int rc = travel_set(field, field_bytes, occupied_or_null, free_or_null, grid_bytes, geom, need2, s);
-    if (rc != TOHIP_OK) return rc;
-    if (!cost || n_goals < 0 || n_goals > (int64_t)1 << 30 || max_rows < 1 || max_rows > (int64_t)1 << 31 ||
-        (n_goals > 0 && (!goals || !rows || !counts)))
+    return travel_paths(cost, cost_bytes, field, field_bytes, occupied_or_null, free_or_null, grid_bytes, geom, need2, 1, goals, nullptr,
+                        n_goals, max_rows, rows, counts, stream_);
+}
+
+extern "C" int tohip_travel_paths_batch(const void* cost, size_t cost_bytes, const void* field, size_t field_bytes,
+                                        const void* occupied_or_null, const void* free_or_null, size_t grid_bytes, const tohip_occ_geom* geom,
+                                        int32_t need2, int32_t n_fields, const float* goals, const int32_t* goal_field, int64_t n_goals,
+                                        int64_t max_rows, float* rows, int64_t* counts, void* stream_) {
+    if (n_goals > 0 && !goal_field) return TOHIP_EINVAL;
+    return travel_paths(cost, cost_bytes, field, field_bytes, occupied_or_null, free_or_null, grid_bytes, geom, need2, n_fields, goals,
+                        goal_field, n_goals, max_rows, rows, counts, stream_);
+}
+
+extern "C" int tohip_assign_greedy(const int64_t* cost, int32_t n_rows, int32_t n_cols, int64_t ld, int64_t min_cost, int32_t* col_of_row,
+                                   int32_t* row_of_col, void* stream_) {
+    if (!cost || !col_of_row || !row_of_col || n_rows < 1 || n_rows > kAssignMaxRows || n_cols < 1 || n_cols > kAssignMaxCols ||
+        ld < n_cols || ld > (int64_t)1 << 40 || min_cost < 0)
         return TOHIP_EINVAL;
-    if (cost_bytes < travel_cost_bytes(s.g)) return TOHIP_ENOSPC;
-    if (n_goals == 0) return TOHIP_OK;
-    const unsigned blocks = (unsigned)((n_goals + TO_BLOCK / 64 - 1) / (TO_BLOCK / 64));
-    k_travel_paths<<<blocks, TO_BLOCK, 0, (hipStream_t)stream_>>>(s, (const unsigned*)cost, goals, n_goals, max_rows, rows, (long long*)counts);
+    k_assign_greedy<<<1, TO_BLOCK, 0, (hipStream_t)stream_>>>((const long long*)cost, n_rows, n_cols, (long long)ld, (long long)min_cost,
+                                                             col_of_row, row_of_col);
     TO_HIP_CHECK_LAUNCH();
     return TOHIP_OK;
 }

@@ -1494,14 +1494,27 @@ class TravelField:
 
     def __init__(self, field, radius, sources, space=None, max_dist=None, rounds_per_check=16):
         self.need2, self.limit, _ = check_travel(field, radius, sources, space, max_dist, rounds_per_check)
-        self.field, self.radius, self.space, self.max_dist, self.rounds_per_check = field, float(radius), space, max_dist, int(rounds_per_check)
-        self.origin, self.resolution, self.dims, self.device, self.geom = field.origin, field.resolution, field.dims, field.device, field.geom
-        L = _lib.lib()
-        self.buf = torch.empty(L.tohip_travel_bytes(*self.dims), dtype=torch.uint8, device=self.device)
-        self._ws = torch.empty(L.tohip_travel_workspace_bytes(*self.dims), dtype=torch.uint8, device=self.device)
+        self._settings(field, radius, space, max_dist, rounds_per_check)
+        self.buf = torch.empty(_lib.lib().tohip_travel_bytes(*self.dims), dtype=torch.uint8, device=self.device)
+        self._ws = None
         self.sources = self.seeded = None
         self.rounds = 0
         self.rebuild(sources)
+
+    def _settings(self, field, radius, space, max_dist, rounds_per_check):
+        self.field, self.radius, self.space, self.max_dist, self.rounds_per_check = field, float(radius), space, max_dist, int(rounds_per_check)
+        self.origin, self.resolution, self.dims, self.device, self.geom = field.origin, field.resolution, field.dims, field.device, field.geom
+
+    @classmethod
+    def over(cls, buf, fields, sources, seeded):
+        """An ops.TravelField over storage that exists: buf, one field's bytes (a slice of `fields`' buffer, an ops.TravelFields — no
+        copy, no build), with the batch's settings, the sources that named the field and their seeded flags.  Its own rebuild() runs
+        the single build into the slice."""
+        self = cls.__new__(cls)
+        self.need2, self.limit = fields.need2, fields.limit
+        self._settings(fields.field, fields.radius, fields.space, fields.max_dist, fields.rounds_per_check)
+        self.buf, self._ws, self.sources, self.seeded, self.rounds = buf, None, sources, seeded, fields.rounds
+        return self
 
     def _set(self):
         """The arguments that name T: the field, the map's planes (or none), the planes' size, the geometry, need2."""
@@ -1515,6 +1528,10 @@ class TravelField:
             check_travel(self.field, self.radius, sources, self.space, self.max_dist, self.rounds_per_check)
             self.sources = _check_rows3(sources, "sources").detach().to(device=self.device, dtype=torch.float32).contiguous()
         S = self.sources.shape[0]
+        if S == 0:
+            raise ValueError("rebuild: this field of a batch had no source; give sources")
+        if self._ws is None:   # (a field over a batch's slice needs none until it rebuilds alone)
+            self._ws = torch.empty(_lib.lib().tohip_travel_workspace_bytes(*self.dims), dtype=torch.uint8, device=self.device)
         self.seeded = torch.empty(S, dtype=torch.uint8, device=self.device)
         rounds = ctypes.c_int64(0)
         _map_call(self.device, "tohip_travel_build", *self._set(), ptr(self.sources), S, self.limit, self.rounds_per_check, ptr(self.buf),
@@ -1566,6 +1583,144 @@ class TravelField:
         rows = torch.empty((G, int(max_rows), 3), dtype=torch.float32, device=self.device)
         counts = torch.empty(G, dtype=torch.int64, device=self.device)
         _map_call(self.device, "tohip_travel_paths", ptr(self.buf), self.buf.numel(), *self._set(), ptr(g), G, int(max_rows), ptr(rows), ptr(counts))
+        n = counts.cpu().tolist()
+        for e, k in enumerate(n):
+            if k < 0:
+                raise ValueError(f"paths: goal {e} needs {-k} rows, max_rows is {int(max_rows)}")
+        return [rows[e, :k].flip(0) for e, k in enumerate(n)]   # source -> goal
+
+
+TRAVEL_MAX_FIELDS = _lib.CONSTANTS["TOHIP_TRAVEL_MAX_FIELDS"]
+TRAVEL_MAX_ITEMS = (1 << 31) - 1      # (field, tile) items of a batch: n_fields times the 8 x 8 x 8-voxel tiles
+
+
+def travel_tiles(dims):
+    """The 8 x 8 x 8-voxel tiles of a grid of `dims`."""
+    return int(np.prod([-(-int(d) // 8) for d in dims]))
+
+
+def check_travel_batch(field, radius, sources, source_field=None, n_fields=None, space=None, max_dist=None, rounds_per_check=16, dims=None):
+    """A batch of travel fields' arguments, by name; needs no GPU.  check_travel's rules, and: source_field: None (one field per
+    source) or an integer tensor of shape (S,) — a row outside [0, n_fields) is allowed: its source is ignored and reported;
+    n_fields: None (S without source_field, else the largest row + 1, at least 1) or an integer in [1, 256]; n_fields times the
+    grid's tiles must fit 31 bits (dims: the grid's, None: the field's).  -> (need2, limit, S, n_fields); ValueError otherwise."""
+    need2, limit, S = check_travel(field, radius, sources, space, max_dist, rounds_per_check)
+    if source_field is not None:
+        if not torch.is_tensor(source_field) or source_field.is_floating_point() or source_field.dtype == torch.bool or \
+                tuple(source_field.shape) != (S,):
+            raise ValueError(f"source_field must be an integer tensor of shape ({S},), got "
+                             f"{(tuple(source_field.shape), source_field.dtype) if torch.is_tensor(source_field) else type(source_field).__name__}")
+    if n_fields is None:
+        n_fields = S if source_field is None else max(int(source_field.max().item()) + 1, 1)
+    if not _is_int(n_fields) or not 1 <= n_fields <= TRAVEL_MAX_FIELDS:
+        raise ValueError(f"n_fields must be an integer in [1, {TRAVEL_MAX_FIELDS}], got {n_fields!r}")
+    tiles = travel_tiles(field.dims if dims is None else dims)
+    if n_fields * tiles > TRAVEL_MAX_ITEMS:
+        raise ValueError(f"n_fields {n_fields} times the grid's {tiles} tiles of 8 x 8 x 8 voxels must fit 31 bits (a list entry packs "
+                         f"field and tile), got {n_fields * tiles}")
+    return need2, limit, S, int(n_fields)
+
+
+class TravelFields:
+    """B travel fields over one clearance field, built in the same worklist rounds (travel_kernels.hip, DESIGN.md 10 "Travel fields
+    in batches"): field b is bit for bit the ops.TravelField of the sources that name b.  sources (S,3); source_field (S,) integers,
+    the field each source seeds (None: one field per source, field i from source i) — a row outside [0, n_fields) is ignored and
+    reported in seeded; n_fields: B (None: S, or the largest source_field + 1); one space, max_dist and limit for all fields.  It
+    holds B cost volumes one after the other (4 B nx ny nz bytes) and the worklist's workspace.  n_fields, seeded (S,) uint8 on the
+    device, rounds, limit as TravelField's.  fields[b] is an ops.TravelField over field b's slice: no copy, no build."""
+
+    def __init__(self, field, radius, sources, source_field=None, n_fields=None, space=None, max_dist=None, rounds_per_check=16):
+        self.need2, self.limit, _, self.n_fields = check_travel_batch(field, radius, sources, source_field, n_fields, space, max_dist,
+                                                                      rounds_per_check)
+        TravelField._settings(self, field, radius, space, max_dist, rounds_per_check)
+        L = _lib.lib()
+        self.buf = torch.empty(L.tohip_travel_batch_bytes(*self.dims, self.n_fields), dtype=torch.uint8, device=self.device)
+        self._ws = torch.empty(L.tohip_travel_batch_workspace_bytes(*self.dims, self.n_fields), dtype=torch.uint8, device=self.device)
+        self.sources = self.source_field = self.seeded = None
+        self.rounds = 0
+        self.rebuild(sources, source_field)
+
+    _set = TravelField._set
+
+    def __len__(self):
+        return self.n_fields
+
+    def rebuild(self, sources=None, source_field=None):
+        """Recompute every field into the same buffers — after field.rebuild(), or from new sources (None: the last ones; with new
+        sources, source_field None means field i from source i again).  The number of fields stays.  -> self."""
+        if sources is not None:
+            _, _, S, _ = check_travel_batch(self.field, self.radius, sources, source_field, self.n_fields, self.space, self.max_dist,
+                                            self.rounds_per_check)
+            self.sources = _check_rows3(sources, "sources").detach().to(device=self.device, dtype=torch.float32).contiguous()
+            self.source_field = (torch.arange(S, device=self.device) if source_field is None else source_field.detach().to(self.device)) \
+                .clamp(-1, self.n_fields).to(torch.int32).contiguous()   # (any row out of range stays out of range)
+        elif source_field is not None:
+            raise ValueError("rebuild: source_field needs sources")
+        S = self.sources.shape[0]
+        self.seeded = torch.empty(S, dtype=torch.uint8, device=self.device)
+        rounds = ctypes.c_int64(0)
+        _map_call(self.device, "tohip_travel_build_batch", *self._set(), ptr(self.sources), ptr(self.source_field), S, self.n_fields, self.limit,
+                  self.rounds_per_check, ptr(self.buf), self.buf.numel(), ptr(self._ws), self._ws.numel(), ptr(self.seeded),
+                  ctypes.byref(rounds))
+        self.rounds = int(rounds.value)
+        return self
+
+    def __getitem__(self, b):
+        if not _is_int(b) or not -self.n_fields <= b < self.n_fields:
+            raise IndexError(f"field {b!r} of {self.n_fields}")
+        b = int(b) % self.n_fields
+        n = self.buf.numel() // self.n_fields
+        mine = self.source_field == b
+        return TravelField.over(self.buf[b * n:(b + 1) * n], self, self.sources[mine], self.seeded[mine])
+
+    def dense(self):
+        """The fields as a (B, nx, ny, nz) int64 tensor (a copy), -1 where unreachable: for tests and small grids."""
+        nx, ny, nz = self.dims
+        c = self.buf.view(torch.int32).view(self.n_fields, nz, ny, nx).to(torch.int64).bitwise_and(0xFFFFFFFF)
+        return torch.where(c == TRAVEL_SENTINEL, torch.full_like(c, -1), c).permute(0, 3, 2, 1).contiguous()
+
+    def _positions(self, p, want_cost, want_dist):
+        pos = covmap_points(p, self.device, "TravelFields")
+        shape = (self.n_fields, pos.shape[0])
+        cost = torch.empty(shape, dtype=torch.int64, device=self.device) if want_cost else None
+        dist = torch.empty(shape, dtype=torch.float32, device=self.device) if want_dist else None
+        _map_call(self.device, "tohip_travel_positions_batch", ptr(self.buf), self.buf.numel(), ctypes.byref(self.geom), self.n_fields, ptr(pos),
+                  pos.shape[0], ptr(cost), ptr(dist))
+        return cost, dist
+
+    def cost(self, positions):
+        """(M,3) world positions -> (B,M) int64: row b is TravelField.cost in field b.  One launch."""
+        return self._positions(positions, True, False)[0]
+
+    def distance(self, positions):
+        """(M,3) world positions -> (B,M) f32 metres: row b is TravelField.distance in field b.  One launch."""
+        return self._positions(positions, False, True)[1]
+
+    def reachable(self, positions):
+        """(M,3) world positions -> (B,M) bool."""
+        return self.cost(positions) >= 0
+
+    def paths(self, goals, goal_field, max_rows=None):
+        """One path per goal, walked in field goal_field[e] -> a list of (L,3) f32 device tensors, source -> goal, as
+        TravelField.paths gives them; L = 0 also where goal_field[e] is outside [0, B).  One launch, one synchronisation."""
+        g = covmap_points(_check_rows3(goals, "goals", empty=True), self.device, "TravelFields.paths")
+        G = g.shape[0]
+        gf = torch.as_tensor(goal_field, device=self.device)
+        if tuple(gf.shape) != (G,) or (G > 0 and (gf.is_floating_point() or gf.dtype == torch.bool)):
+            raise ValueError(f"goal_field must be ({G},) integers, got {tuple(gf.shape)} of {gf.dtype}")
+        if G == 0:
+            return []
+        gf = gf.clamp(-1, self.n_fields).to(torch.int32).contiguous()
+        if max_rows is None:
+            # a path of cost c has at most c / 64 moves
+            mine = self.cost(g).gather(0, gf.long().clamp(0, self.n_fields - 1)[None, :])
+            max_rows = min(max(int(mine.max().item()), 0) // 64 + 1, TRAVEL_MAX_ROWS)
+        if not _is_int(max_rows) or max_rows < 1:
+            raise ValueError(f"max_rows must be an integer >= 1 or None, got {max_rows!r}")
+        rows = torch.empty((G, int(max_rows), 3), dtype=torch.float32, device=self.device)
+        counts = torch.empty(G, dtype=torch.int64, device=self.device)
+        _map_call(self.device, "tohip_travel_paths_batch", ptr(self.buf), self.buf.numel(), *self._set(), self.n_fields, ptr(g), ptr(gf), G,
+                  int(max_rows), ptr(rows), ptr(counts))
         n = counts.cpu().tolist()
         for e, k in enumerate(n):
             if k < 0:

@@ -1430,6 +1430,59 @@ def view_pick_travel_ref(gains, taken, cost, m, min_gain=1):
     return at
 
 
+TRAVEL_MAX_FIELDS = 256
+
+
+def travel_batch_ref(T, seeds_per_field, limit=TRAVEL_MAX_LIMIT):
+    """B travel fields over one T -> (B,nx,ny,nz) int64: field b is travel_ref from seeds_per_field[b] (a (K,3) list of voxels, K >=
+    0) — a loop over the single field, which is the batch's whole definition."""
+    T = np.asarray(T, dtype=bool)
+    return np.stack([travel_ref(T, np.asarray(s, dtype=np.int64).reshape(-1, 3), limit) for s in seeds_per_field]).reshape((-1,) + T.shape)
+
+
+def travel_matrix_ref(positions, origin, resolution, T, limit=TRAVEL_MAX_LIMIT):
+    """The map-distance matrix of (M,3) positions -> (cost (M,M) int64, seeded (M,) uint8): cost[i][j] is the cost, in the field
+    seeded at position i alone, of position j's voxel (travel_positions_ref's codes: -1 unreachable — a whole row where i is not
+    seeded — and -2 in the columns out of range or outside dims)."""
+    seeded, vox = travel_seeds_ref(positions, origin, resolution, T)
+    fields = travel_batch_ref(T, [vox[i:i + 1] if seeded[i] else [] for i in range(len(vox))], limit)
+    cost = np.stack([travel_positions_ref(positions, origin, resolution, f) for f in fields]) if len(vox) else np.zeros((0, 0), dtype=np.int64)
+    return cost.astype(np.int64), seeded
+
+
+def assign_greedy_ref(cost, min_cost=0):
+    """The greedy assignment of rows to columns -> (col_of_row (R,) int32, row_of_col (C,) int32), -1 where nothing was assigned: the
+    candidates are the pairs with cost[r][c] >= min_cost (>= 0: negative entries mean none); the smallest (cost, r, c) whose row is
+    unassigned and whose column is unclaimed is assigned, until none is left."""
+    cost = np.asarray(cost, dtype=np.int64)
+    R, C = cost.shape
+    col_of_row, row_of_col = np.full(R, -1, dtype=np.int32), np.full(C, -1, dtype=np.int32)
+    while True:
+        best = None
+        for r in range(R):
+            if col_of_row[r] >= 0:
+                continue
+            for c in range(C):
+                if row_of_col[c] < 0 and cost[r, c] >= min_cost and (best is None or (int(cost[r, c]), r, c) < best):
+                    best = (int(cost[r, c]), r, c)
+        if best is None:
+            return col_of_row, row_of_col
+        col_of_row[best[1]], row_of_col[best[2]] = best[2], best[1]
+
+
+def assign_min_cost_fixed(min_cost, resolution):
+    """assign_frontiers' min_cost in metres -> the integer bound in 1/64 voxel edge: ceil(float64(min_cost) / float64(f32 r) 64)."""
+    return int(math.ceil(float(min_cost) / float(np.float32(resolution)) * 64.0))
+
+
+def tour_travel_units(cost, resolution):
+    """Travel costs (1/64 voxel edge; any shape) -> the tour's unit, 2^-20 m: round_half_even(float64(cost) (float64(f32 r) 2^14)) —
+    one correctly rounded f64 product (the scale by 2^14 is exact); the codes -1 and -2 become TOUR_INF."""
+    c = np.asarray(cost, dtype=np.int64)
+    scale = float(np.float32(resolution)) * 16384.0
+    return np.where(c < 0, np.int64(TOUR_INF), np.rint(np.maximum(c, 0).astype(np.float64) * scale).astype(np.int64))
+
+
 # ---- connected components restated in numpy (DESIGN.md 10, "Connected components"): what components_kernels.hip must give, bit for
 # bit.  Dense (nx,ny,nz) arrays, the linear index of voxel (x, y, z) is v = (z ny + y) nx + x, -1 = a clear voxel. ----------------------
 COMPONENT_CONNECTIVITIES = (6, 18, 26)

@@ -809,7 +809,9 @@ class Tour(_Result):
     With via= (a free-space roadmap behind the legs; None otherwise): roadmap: the Roadmap over [poses; via]; via_flag (n,n) bool on
     the host: the legs that run over the roadmap because that is shorter than the straight leg (or the straight leg is blocked);
     walk_nodes: the walk as indices into [poses; via], every such leg expanded into the roadmap's nodes — poses / quats then follow
-    walk_nodes (a free-space node takes the quaternion of the view its leg leads to), walk keeps listing tour nodes only."""
+    walk_nodes (a free-space node takes the quaternion of the view its leg leads to), walk keeps listing tour nodes only.
+    With travel=True: via_flag marks the legs that run over the map's travel field, poses / quats hold those legs expanded into the
+    route's voxel centres (they take the quaternion of the view they lead to); roadmap and walk_nodes stay None."""
     __slots__ = ("order", "unreachable", "walk", "poses", "quats", "length", "nn_length", "length_fixed", "nn_length_fixed", "moves",
                  "converged", "blocked", "edge_distance", "D", "nxt", "roadmap", "via_flag", "walk_nodes")
 
@@ -834,7 +836,7 @@ def tour_edge_query(cloud, nodes, radius, stage=None):
 
 
 def plan_tour(points_or_cloud_or_model, poses, quats=None, clearance_radius=None, closed=False, max_moves=None, via=None, via_k=12,
-              via_max_edge=None):
+              via_max_edge=None, travel=False, space=None):
     """A short visiting order through view poses whose every straight leg keeps clearance_radius from the cloud.
     poses (n,3), 2 <= n <= 256: row 0 is where the tour starts (the robot), the others are the views (select_views' sel.poses);
     quats (n,4) or None.  Every pair of nodes is put to the swept clearance query (edge_clearance); the pairs it finds nothing near
@@ -848,7 +850,27 @@ def plan_tour(points_or_cloud_or_model, poses, quats=None, clearance_radius=None
     roadmap (build_roadmap, k = via_k, max_edge = via_max_edge) over [poses; via] gives every pair of tour nodes its shortest
     collision-checked route, and a leg takes it wherever that beats the straight leg: a view behind a wall is reached through the
     doorway.  A via node that coincides with a pose is left out (its row is made non-finite: the index of every other node stays).
-    -> Tour.  Launches only, then one copy to the host (with via: one read-back per batch of route sweeps before it)."""
+    travel=True (the first argument must then be an ops.ClearanceField, clearance_radius is required and via= must be None): the
+    map itself stands behind the legs.  travel_matrix over the n tour nodes (space=: an ops.SpaceMap, known-free voxels only) gives
+    every pair its route length along the travel field's metric, converted to the tour's unit (synth.tour_travel_units) and handed
+    to the same planner as via_D; a leg takes the map route wherever that beats the open straight leg (via_flag).  Such a leg u ->
+    v is walked as pose u, the voxel centres of fields.paths(pose v, field u), pose v; the first and the last hop stay inside the
+    end voxels' certified cubes, every other hop joins two 26-neighbours, so every hop is a leg field.edges calls open, and the rows
+    go into refine_path(field, ...) as any tour's do.  A path's rows take the quaternion of the view they lead to; walk_nodes and
+    roadmap stay None.  No lattice, no node limit: the map of any size is the roadmap.
+    -> Tour.  Launches only, then one copy to the host (with via: one read-back per batch of route sweeps before it; with travel:
+    the build's read-backs before it and one for the paths after it)."""
+    if not isinstance(travel, (bool, np.bool_)):
+        raise ValueError(f"plan_tour: travel must be True or False, got {travel!r}")
+    if travel:
+        if not isinstance(points_or_cloud_or_model, ops.ClearanceField):
+            raise ValueError(f"plan_tour: travel=True needs an ops.ClearanceField as the first argument, got {type(points_or_cloud_or_model).__name__}")
+        if via is not None:
+            raise ValueError("plan_tour: travel=True and via= exclude each other (the map is the roadmap)")
+        if clearance_radius is None:
+            raise ValueError("plan_tour: travel=True needs a clearance_radius (a finite number > 0), got None")
+    elif space is not None:
+        raise ValueError("plan_tour: space= needs travel=True")
     cloud, pts = _clearance_cloud(points_or_cloud_or_model, "plan_tour", field=True)
     n, r, max_moves = ops.check_tour(poses, quats, clearance_radius, closed, max_moves)
     if via is not None:
@@ -869,7 +891,14 @@ def plan_tour(points_or_cloud_or_model, poses, quats=None, clearance_radius=None
     d, idx, _ = tour_edge_query(cloud, nodes, r) if r is not None else (None, None, None)
     dist = _symmetric(n, ops.tour_edge_ends(n, dev), d, float("inf"), torch.float32)
     tail = [idx.view(torch.uint8)] if idx is not None else []
-    if rm is None:
+    tm = None
+    if travel:   # the map's route lengths between the tour nodes, in the tour's unit
+        tm = travel_matrix(cloud, nodes, r, space=space)
+        scale = float(np.float32(cloud.resolution)) * 16384.0   # (synth.tour_travel_units: one rounded f64 product, half to even)
+        via_D = torch.where(tm.cost < 0, torch.full_like(tm.cost, ops.ROADMAP_INF), torch.round(tm.cost.clamp(min=0).double() * scale).long())
+        buf, flag = ops.tour_plan_via(nodes, idx, via_D.contiguous(), closed, max_moves)
+        tail += [flag.reshape(-1)]
+    elif rm is None:
         buf = ops.tour_plan(nodes, idx, closed, max_moves)
     else:
         buf, flag = ops.tour_plan_via(nodes, idx, routes.D, closed, max_moves)
@@ -894,7 +923,21 @@ def plan_tour(points_or_cloud_or_model, poses, quats=None, clearance_radius=None
             walk_nodes += hop
             q_of += [x if x < n else v for x in hop]
     w = torch.as_tensor(walk if walk_nodes is None else walk_nodes, dtype=torch.int64, device=dev)
-    return Tour(order=order, unreachable=unreachable, walk=walk, poses=allnodes[w],
+    walk_poses = allnodes[w]
+    if tm is not None:   # every leg that runs over the map expanded into its voxel centres
+        via_flag = h[o + 4 * E:o + 4 * E + n * n].reshape(n, n) != 0
+        legs = [(u, v) for u, v in zip(walk, walk[1:]) if via_flag[u, v]]
+        paths = iter(tm.fields.paths(nodes[[v for _, v in legs]], torch.as_tensor([u for u, _ in legs], dtype=torch.int32))) if legs else None
+        rows, q_of = [nodes[walk[0]][None]], [walk[0]]
+        for u, v in zip(walk, walk[1:]):
+            if via_flag[u, v]:
+                hop = next(paths)
+                rows.append(hop)
+                q_of += [v] * hop.shape[0]
+            rows.append(nodes[v][None])
+            q_of.append(v)
+        walk_poses = torch.cat(rows)
+    return Tour(order=order, unreachable=unreachable, walk=walk, poses=walk_poses,
                 quats=qs[torch.as_tensor(q_of, dtype=torch.int64, device=dev)] if qs is not None else None,
                 length=int(hdr[3]) * ops.TOUR_UNIT, nn_length=int(hdr[4]) * ops.TOUR_UNIT, length_fixed=int(hdr[3]),
                 nn_length_fixed=int(hdr[4]), moves=int(hdr[1]), converged=bool(hdr[2]), blocked=blocked, edge_distance=dist, D=D, nxt=nxt,
@@ -1079,6 +1122,101 @@ def plan_path(points_or_cloud_or_model, start, goal, via, clearance_radius, k=12
     walk, fixed, length = got
     return PlannedPath(poses=nodes[torch.as_tensor(walk, dtype=torch.int64, device=dev)], length=length, length_fixed=fixed, walk=walk,
                        roadmap=rm)
+
+
+def travel_fields(field, starts, radius, space=None, max_dist=None):
+    """One travel field per start, all built in the same worklist rounds: an ops.TravelFields ("Travel fields in
+    batches") over `starts` (S,3), S <= 256 — a team's robots, a tour's views.  fields[b] is the ops.TravelField of start b (no
+    copy), fields.cost(positions) / .distance / .reachable answer (S,M) at once, fields.paths(goals, goal_field) walks each goal in
+    the field it names.  Field b is bit for bit travel_field(field, starts[b], ...)."""
+    if not isinstance(field, ops.ClearanceField):
+        raise ValueError(f"travel_fields: field must be an ops.ClearanceField, got {type(field).__name__}")
+    return ops.TravelFields(field, radius, ops._check_rows3(starts, "starts"), space=space, max_dist=max_dist)
+
+
+class TravelMatrix(_Result):
+    """What travel_matrix returns: cost (M,M) int64 on the device, cost[i][j] the cost in 1/64 voxel edge, in the field seeded at
+    position i, of position j's voxel (-1: unreachable — a whole row where i was not seeded — and -2 in the columns out of range or
+    outside dims); distance (M,M) f32 metres (+inf / NaN); seeded (M,) uint8; fields: the ops.TravelFields behind it."""
+    __slots__ = ("cost", "distance", "seeded", "fields")
+
+
+def travel_matrix(field, positions, radius, space=None, max_dist=None):
+    """The map distance between every two of `positions` (M,3), M <= 256: what the robot must travel, not the straight line.
+    -> TravelMatrix.  One batched build, one lookup launch.  Symmetric wherever both rows are seeded: an allowed move is allowed
+    both ways at the same weight."""
+    fields = travel_fields(field, positions, radius, space, max_dist)
+    cost, distance = fields._positions(fields.sources, True, True)
+    return TravelMatrix(cost=cost, distance=distance, seeded=fields.seeded, fields=fields)
+
+
+class FrontierAssignment(_Result):
+    """What assign_frontiers returns, all on the device.  clusters: frontier_clusters(...) without travel (K rows: descending size,
+    then ascending id); cost_fixed (R,K) int64: robot r's cost, in 1/64 voxel edge, to cluster k's nearest voxel (-1 unreachable);
+    cost (R,K) f64 metres (inf); approach (R,K,3) f32 that voxel's centre (NaN where unreachable); goal (R,) int64: the row of
+    clusters robot r is sent to, -1 for none; goal_position (R,3) f32 = approach[r, goal[r]] (NaN) and goal_cost (R,) f64 metres
+    (inf); robot_of_cluster (K,) int64, -1 where the cluster went to nobody."""
+    __slots__ = ("clusters", "cost_fixed", "cost", "approach", "goal", "goal_position", "goal_cost", "robot_of_cluster")
+
+
+ASSIGN_MAX_ROBOTS = 64
+ASSIGN_MAX_CLUSTERS = 4096
+
+
+def assign_frontiers(space_or_evidence_map, fields, min_unknown=1, min_size=1, connectivity=26, min_cost=0.0):
+    """Which robot goes to which opening ("Travel fields in batches").  fields: an ops.TravelFields of the map's
+    geometry with one field per robot, R <= 64.  Every frontier cluster (frontier_clusters: min_unknown, min_size, connectivity; at
+    most 4096 of them) is priced from every robot by its nearest voxel — Components.min_over on fields[r], R launches with no read-
+    back between them — and tohip_assign_greedy hands them out: among the pairs (robot, cluster) with a cost >= min_cost (metres;
+    just above 0 keeps a robot from being sent to the opening it stands in) the cheapest goes first, ties to the lower robot, then
+    the lower cluster row, and no robot or cluster is taken twice.  Greedy, not optimal; cluster size plays no part.  The same
+    answer in every run.  -> FrontierAssignment."""
+    if not isinstance(fields, ops.TravelFields):
+        raise ValueError(f"assign_frontiers: fields must be an ops.TravelFields, got {type(fields).__name__}")
+    R = fields.n_fields
+    if R > ASSIGN_MAX_ROBOTS:
+        raise ValueError(f"assign_frontiers: fields must hold at most {ASSIGN_MAX_ROBOTS} fields (one per robot), got {R}")
+    m = ops._float_or_nan(min_cost) if ops._is_real(min_cost) else float("nan")
+    if not np.isfinite(m) or m < 0.0:
+        raise ValueError(f"assign_frontiers: min_cost must be a finite number of metres >= 0, got {min_cost!r}")
+    clusters = frontier_clusters(space_or_evidence_map, min_unknown, min_size, connectivity)
+    comp, dev = clusters.components, clusters.ids.device
+    diff = ops._grid_difference(comp.grid, fields)
+    if diff:
+        raise ValueError(f"assign_frontiers: the travel fields' {diff[0]} differs from the map's ({diff[2]} and {diff[1]})")
+    K = clusters.n
+    if K > ASSIGN_MAX_CLUSTERS:
+        raise ValueError(f"assign_frontiers: {K} clusters, at most {ASSIGN_MAX_CLUSTERS} can be assigned; raise min_size (now {min_size})")
+    from .synth import assign_min_cost_fixed   # (numpy only)
+    priced = [comp.min_over(fields[b]) for b in range(R)]
+    cost_fixed = torch.stack([v[clusters.ids] for v, _ in priced]).contiguous() if K else torch.empty((R, 0), dtype=torch.int64, device=dev)
+    voxel = torch.stack([x[clusters.ids].long() for _, x in priced]) if K else torch.empty((R, 0), dtype=torch.int64, device=dev)
+    reachable = cost_fixed >= 0
+    nx, ny, _ = comp.dims
+    v = voxel.clamp(min=0)
+    ijk = torch.stack([v % nx, (v // nx) % ny, v // (nx * ny)], dim=-1)
+    o = torch.from_numpy(np.asarray(comp.origin, dtype=np.float32)).to(dev)
+    r32 = float(np.float32(comp.resolution))
+    approach = o + (ijk.float() + 0.5) * r32   # a voxel's centre as the map computes it, in f32
+    approach = torch.where(reachable[..., None], approach, torch.full_like(approach, float("nan")))
+    cost = torch.where(reachable, cost_fixed.double() / 64.0 * r32, torch.full_like(cost_fixed, float("inf"), dtype=torch.float64))
+    col_of_row = torch.full((R,), -1, dtype=torch.int32, device=dev)
+    row_of_col = torch.full((K,), -1, dtype=torch.int32, device=dev)
+    if K:
+        ops._map_call(dev, "tohip_assign_greedy", ops.ptr(cost_fixed), R, K, K, assign_min_cost_fixed(m, comp.resolution), ops.ptr(col_of_row),
+                      ops.ptr(row_of_col))
+    goal = col_of_row.long()
+    has = goal >= 0
+    pick = goal.clamp(min=0)
+    if K:
+        rows = torch.arange(R, device=dev)
+        goal_position = torch.where(has[:, None], approach[rows, pick], torch.full((R, 3), float("nan"), device=dev))
+        goal_cost = torch.where(has, cost[rows, pick], torch.full((R,), float("inf"), dtype=torch.float64, device=dev))
+    else:
+        goal_position = torch.full((R, 3), float("nan"), device=dev)
+        goal_cost = torch.full((R,), float("inf"), dtype=torch.float64, device=dev)
+    return FrontierAssignment(clusters=clusters, cost_fixed=cost_fixed, cost=cost, approach=approach, goal=goal, goal_position=goal_position,
+                              goal_cost=goal_cost, robot_of_cluster=row_of_col.long())
 
 
 class TravelPath(_Result):
