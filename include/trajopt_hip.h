@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_travel_batch_bytes / tohip_travel_batch_workspace_bytes / tohip_travel_build_batch / tohip_travel_positions_batch /
+/* (still 15) + tohip_ground_build / tohip_ground_snap (the ground layer: where a robot that drives can stand, what is an obstacle for it
+ * and the slab its centre rides in, as planes the field and travel entry points take unchanged): new symbols only.
+ * (still 15) + tohip_travel_batch_bytes / tohip_travel_batch_workspace_bytes / tohip_travel_build_batch / tohip_travel_positions_batch /
  * tohip_travel_paths_batch / tohip_assign_greedy and TOHIP_TRAVEL_MAX_FIELDS (many travel fields built in the same worklist rounds, their
  * lookups and paths in one launch each, and a deterministic greedy assignment of rows to columns): new symbols only.
  * (still 15) + tohip_occ_transfer / tohip_evid_transfer (re-framing and merging maps: voxel content moved from one box into another at
@@ -1520,6 +1522,32 @@ int tohip_components_min(const void *labels, size_t labels_bytes, const tohip_oc
                          int64_t n_components, int64_t *min_value, int32_t *min_voxel, void *stream);
 int tohip_components_positions(const void *labels, size_t labels_bytes, const tohip_occ_geom *geom, const float *positions, int64_t m,
                                int64_t *out, void *stream);
+
+/* ---- the ground layer ("Ground layer") ------------------------------------------------
+ * For a robot that drives on the map's floor: headroom H voxels (1 .. 64) and step s voxels (0 .. 4, s + 1 <= H).  A voxel is CLEAR
+ * iff it is not occupied and — with unknown_obstacle = 1, which needs the free plane — known free; a voxel outside dims is clear with
+ * unknown_obstacle = 0 and not clear with 1.  All planes are occupancy grid buffers of grid_bytes and one geometry.
+ * tohip_ground_build writes four planes (none of them an input or one another; headers and pad bits 0):
+ *   support    occupied, and the voxels at z + 1 .. z + H clear.
+ *   ground     the support voxels all eight of whose lateral neighbour columns lie inside dims and hold (a) a support voxel at a
+ *              level in [z - s, z + s] or (b) an occupied voxel at a level in [z + 1, z + H] (a wall: its own obstacle).  Ledge and pit
+ *              rims, risers higher than s, the rim of unseen floor and the outermost ring of the grid are not ground.
+ *   obstacles  the occupied voxels that are not FLOOR — floor: the occupied voxels whose contiguous occupied run upwards ends in a
+ *              ground voxel — and, with unknown_obstacle = 1, every voxel inside dims that is neither occupied nor free.
+ *   drive      the voxels that are not occupied with a ground voxel 1 .. s + 1 levels below: the standing voxel and the s above it.
+ * tohip_field_build over (obstacles, NULL) and the travel entry points with the planes (obstacles, drive) as (occupied, free) then give
+ * the places a ball whose centre rides in the drive slab can be.  Three launches, integers only, no atomics, nothing read back.
+ * tohip_ground_snap: positions (m, 3) f32 -> standing (m, 3) f32 and drop (m) int32.  From the position's voxel (x, y, z) — the
+ * coordinate rule of tohip_occ_insert — the first k in 0 .. max_drop (0 <= max_drop <= 2048) with drive at (x, y, z - k) and ground
+ * at (x, y, z - k - 1): standing is that voxel's centre fl(origin + fl(fl(i + 0.5) r)), tohip_travel_paths' rule, and drop is k.
+ * drop -1: there is none; -2: out of range or outside dims; standing is NaN for both.
+ * flags is reserved and must be 0.  Bad flags, H, s, unknown_obstacle or max_drop, a missing, misaligned or aliased plane:
+ * TOHIP_EINVAL; a short grid_bytes: TOHIP_ENOSPC.  Every argument check returns before anything is enqueued. */
+int tohip_ground_build(const void *occupied, const void *free_or_null, size_t grid_bytes, const tohip_occ_geom *geom, int32_t headroom,
+                       int32_t step, int32_t unknown_obstacle, void *support, void *ground, void *obstacles, void *drive, void *stream,
+                       uint32_t flags);
+int tohip_ground_snap(const void *ground, const void *drive, size_t grid_bytes, const tohip_occ_geom *geom, const float *positions,
+                      int64_t m, int32_t max_drop, float *standing, int32_t *drop, void *stream, uint32_t flags);
 
 /* ---- optional per-kernel timing (bench.py's roofline leg) -----------------------------------------
  * When enabled, every launch of the big kernels is bracketed by hipEventRecord on its own stream.

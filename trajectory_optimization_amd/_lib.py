@@ -24,7 +24,9 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "trajopt_hip.h")
 
 c_vp = ctypes.c_void_p
 
-_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
+# (a uint32_t scalar — a reserved flags word — travels as the 32-bit integer it shares a register with: ctypes checks no range, and
+# the scalar types a parameter can have stay these six)
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
             "float": ctypes.c_float, "double": ctypes.c_double}
 _POINTEES = set(_SCALARS) | {"void", "int8_t", "uint8_t", "uint32_t", "uint64_t"}   # what a pointer may point to
 _DECLARATOR = re.compile(r"(?:const\s+)?(.+?)\s*(\**)\s*\b(\w+)\s*(?:\[(\d+)\])?")

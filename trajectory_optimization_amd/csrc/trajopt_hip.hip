@@ -23,6 +23,7 @@
 #include "reframe_kernels.hip"
 #include "travel_kernels.hip"
 #include "components_kernels.hip"
+#include "ground_kernels.hip"
 #include "volume_kernels.hip"
 #include "raycast_kernels.hip"
 #include "clearance_map_kernels.hip"

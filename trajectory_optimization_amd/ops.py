@@ -2026,6 +2026,93 @@ class EvidenceMap:
         return self
 
 
+GROUND_MAX_HEADROOM = 64   # voxels
+GROUND_MAX_STEP = 4        # voxels
+GROUND_MAX_DROP = 2048     # voxels a snap may look down
+
+
+def check_ground(map, headroom, step=1, unknown="free", H=None, max_drop=None):
+    """A ground layer's settings and a snap's, by name; needs no GPU.  map: an OccupancyGrid, a SpaceMap or an EvidenceMap (its planes);
+    headroom: a finite number of metres > 0 whose H = ceil(float64(headroom) / float64(f32 resolution)) lies in [1, 64] — or H itself,
+    an integer in that range, instead; step: an integer number of voxels in [0, 4] with step + 1 <= H; unknown: 'free' or 'obstacle'
+    (which needs a map with a free plane); max_drop (None: not asked): an integer number of voxels in [0, 2048].
+    -> (occupied grid, free plane or None, H, step); ValueError otherwise."""
+    if not isinstance(map, (OccupancyGrid, SpaceMap, EvidenceMap)):
+        raise ValueError(f"GroundLayer: the map must be an ops.OccupancyGrid, an ops.SpaceMap or an ops.EvidenceMap, got {type(map).__name__}")
+    occupied, free = (map, None) if isinstance(map, OccupancyGrid) else (map.occupied, map.free)
+    if unknown not in FIELD_UNKNOWN:
+        raise ValueError(f"unknown must be 'free' or 'obstacle', got {unknown!r}")
+    if unknown == "obstacle" and free is None:
+        raise ValueError("unknown='obstacle' needs an ops.SpaceMap or an ops.EvidenceMap (the free plane tells unknown from free), got an OccupancyGrid")
+    r = occupied.resolution
+    if H is None:
+        m = _float_or_nan(headroom) if _is_real(headroom) else float("nan")
+        H = int(np.ceil(m / r)) if np.isfinite(m) and m > 0.0 and m / r <= GROUND_MAX_HEADROOM + 1 else 0
+        if not 1 <= H <= GROUND_MAX_HEADROOM:
+            raise ValueError(f"headroom must be a finite number of metres > 0 and at most {GROUND_MAX_HEADROOM} voxels "
+                             f"({GROUND_MAX_HEADROOM * r:g} m at this resolution), got {headroom!r}")
+    elif not _is_int(H) or not 1 <= H <= GROUND_MAX_HEADROOM:
+        raise ValueError(f"H must be an integer number of voxels in [1, {GROUND_MAX_HEADROOM}], got {H!r}")
+    H = int(H)
+    if not _is_int(step) or not 0 <= step <= GROUND_MAX_STEP:
+        raise ValueError(f"step must be an integer number of voxels in [0, {GROUND_MAX_STEP}], got {step!r}")
+    if step + 1 > H:
+        raise ValueError(f"step {int(step)} needs a headroom of at least {int(step) + 1} voxels (the slab over a step must be clear), got H = {H}")
+    if max_drop is not None and (not _is_int(max_drop) or not 0 <= max_drop <= GROUND_MAX_DROP):
+        raise ValueError(f"max_drop must be an integer number of voxels in [0, {GROUND_MAX_DROP}], got {max_drop!r}")
+    return occupied, (free if unknown == "obstacle" else None), H, int(step)
+
+
+class GroundLayer:
+    """The ground layer of a map (ground_kernels.hip, DESIGN.md 10 "Ground layer"): for a robot that DRIVES — headroom metres tall,
+    climbing steps of `step` voxels — the planes that tell where it can stand and what is an obstacle for it.  support: occupied
+    voxels with H clear voxels above; ground: the support voxels whose eight neighbour columns continue the surface within +-step
+    levels or are walls; obstacles: what is occupied and not floor (the ground and what is stacked solid under it) — with
+    unknown='obstacle' the unknown voxels too; drive: the standing voxel over every ground voxel and the `step` voxels above it.
+    All four are ordinary OccupancyGrids of the map's geometry; space = SpaceMap(obstacles, drive) and field(max_dist), a
+    ClearanceField over obstacles, go wherever a space and a field go: a TravelField over them covers exactly the places the robot's
+    centre can be.  Integers only: the same bits in every run.  rebuild() follows the map."""
+
+    def __init__(self, map, headroom=None, step=1, unknown="free", H=None):
+        self.occupied, self.free, self.H, self.step = check_ground(map, headroom, step, unknown, H=H)
+        self.map, self.unknown = map, unknown
+        g = self.occupied
+        self.origin, self.resolution, self.dims, self.device, self.geom = g.origin, g.resolution, g.dims, g.device, g.geom
+        self.support, self.ground, self.obstacles, self.drive = (g.empty_like() for _ in range(4))
+        self.space = SpaceMap(self.obstacles, self.drive)
+        self.rebuild()
+
+    def rebuild(self):
+        """Recompute the four planes from the map as it is now — after more inserts, carves or folds — into the same buffers: three
+        launches, nothing read back; fields and travel fields over the layer then rebuild as over any map.  -> self."""
+        with torch.cuda.device(self.device):
+            check(_lib.lib().tohip_ground_build(ptr(self.occupied.buf), ptr(self.free.buf) if self.free is not None else None,
+                                                self.occupied.buf.numel(), ctypes.byref(self.geom), self.H, self.step,
+                                                1 if self.free is not None else 0, ptr(self.support.buf), ptr(self.ground.buf),
+                                                ptr(self.obstacles.buf), ptr(self.drive.buf), stream_ptr(), 0), "tohip_ground_build")
+        return self
+
+    def field(self, max_dist=None, D=None):
+        """A ClearanceField over the layer's obstacles, truncated at max_dist metres (or D voxels): the floor the robot rolls on is
+        no obstacle in it.  A new field each call; field.rebuild() follows layer.rebuild()."""
+        return ClearanceField(self.obstacles, max_dist, D=D)
+
+    def snap(self, positions, max_drop):
+        """(M,3) world positions -> (standing (M,3) f32, drop (M,) int32): the centre of the standing voxel — a drive voxel right
+        above a ground voxel — at or at most max_drop voxels below each position's voxel, and how many voxels below.  drop -1: none;
+        -2: out of range (beyond the apron, or not finite) or outside dims; standing is NaN for both.  What turns a sensor-height
+        pose into a travel source and a row of a path in the slab into a wheel position.  One launch."""
+        check_ground(self.occupied, None, self.step, H=self.H, max_drop=max_drop)
+        pos = covmap_points(_check_rows3(positions, "positions", empty=True), self.device, "GroundLayer.snap")
+        standing = torch.empty((pos.shape[0], 3), dtype=torch.float32, device=self.device)
+        drop = torch.empty(pos.shape[0], dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(_lib.lib().tohip_ground_snap(ptr(self.ground.buf), ptr(self.drive.buf), self.ground.buf.numel(), ctypes.byref(self.geom),
+                                               ptr(pos), pos.shape[0], int(max_drop), ptr(standing), ptr(drop), stream_ptr(), 0),
+                  "tohip_ground_snap")
+        return standing, drop
+
+
 XFER_MAX_SHIFT = 4096      # of a voxel shift per axis (tohip_occ_transfer / tohip_evid_transfer)
 XFER_MODES = {"copy": 0, "or": 1, "add": 1, "confident": 2}
 LATTICE_TOLERANCE = 1.0 / 256.0   # the layer's fixed-point unit, in voxels

@@ -1736,3 +1736,110 @@ def pillar_scan(room, origin, lo, hi):
     t_in, t_out = near.max(axis=1), far.min(axis=1)
     meets = (t_in <= t_out) & (t_in > 0.0) & (t_in < 1.0)
     return np.where(meets[:, None], o + np.where(meets, t_in, 0.0)[:, None] * d, P).astype(np.float32)
+
+
+# ---- the ground layer ("Ground layer") -------------------------------------------------------------------------------
+GROUND_MAX_HEADROOM = 64
+GROUND_MAX_STEP = 4
+GROUND_MAX_DROP = 2048
+GROUND_UNKNOWN = FIELD_UNKNOWN
+
+
+def ground_headroom_voxels(headroom, resolution):
+    """headroom in metres -> H in voxels: ceil(float64(headroom) / float64(f32 resolution)), field_max_dist_voxels' rule."""
+    return field_max_dist_voxels(headroom, resolution)
+
+
+def _ground_up(a, k, fill):
+    """out[x, y, z] = a[x, y, z + k] where z + k lies inside, else fill."""
+    out = np.full_like(a, fill)
+    n = a.shape[2]
+    if abs(k) < n:
+        out[:, :, max(-k, 0):n + min(-k, 0)] = a[:, :, max(k, 0):n + min(k, 0)]
+    return out
+
+
+def ground_ref(occ, free=None, headroom=4, step=1, unknown="free"):
+    """The ground layer of a map -> {support, ground, floor, obstacles, drive}, five (nx,ny,nz) bool arrays, from the five rules.
+    clear: not occupied (and, with unknown='obstacle', known free; outside dims clear under 'free' only).  support: occupied with H
+    clear voxels above.  ground: a support voxel whose eight lateral neighbour columns lie inside dims and hold either a support
+    voxel within +-step levels or an occupied voxel in the H levels above (a wall).  floor: the ground voxels and what is stacked
+    solid under them.  obstacles: occupied and not floor (and, with 'obstacle', every unknown voxel).  drive: the non-occupied
+    voxels with a ground voxel 1 .. step + 1 levels below."""
+    occ = np.asarray(occ, dtype=bool)
+    H, s = int(headroom), int(step)
+    if unknown not in GROUND_UNKNOWN:
+        raise ValueError(f"unknown must be 'free' or 'obstacle', got {unknown!r}")
+    if unknown == "obstacle" and free is None:
+        raise ValueError("unknown='obstacle' needs the free plane")
+    if not 1 <= H <= GROUND_MAX_HEADROOM or not 0 <= s <= GROUND_MAX_STEP or s + 1 > H:
+        raise ValueError(f"headroom must lie in [1, {GROUND_MAX_HEADROOM}] and step in [0, min({GROUND_MAX_STEP}, headroom - 1)], got {H}, {s}")
+    known = unknown == "obstacle"
+    clear = ~occ & np.asarray(free, dtype=bool) if known else ~occ
+    support = occ.copy()
+    for k in range(1, H + 1):
+        support &= _ground_up(clear, k, not known)
+    near = np.zeros_like(occ)    # a support voxel of this column within +-step levels
+    for k in range(-s, s + 1):
+        near |= _ground_up(support, k, False)
+    wall = np.zeros_like(occ)    # an occupied voxel of this column in the H levels above
+    for k in range(1, H + 1):
+        wall |= _ground_up(occ, k, False)
+    fine = near | wall
+    ground = support.copy()
+    for dx in (-1, 0, 1):
+        for dy in (-1, 0, 1):
+            if dx or dy:
+                ground &= _travel_shift(fine, (dx, dy, 0), False)
+    floor = np.zeros_like(occ)
+    for z in range(occ.shape[2] - 1, -1, -1):
+        above = floor[:, :, z + 1] if z + 1 < occ.shape[2] else False
+        floor[:, :, z] = occ[:, :, z] & (ground[:, :, z] | above)
+    obstacles = occ & ~floor
+    if known:
+        obstacles |= ~occ & ~np.asarray(free, dtype=bool)
+    drive = np.zeros_like(occ)
+    for k in range(1, s + 2):
+        drive |= _ground_up(ground, -k, False)
+    drive &= ~occ
+    return {"support": support, "ground": ground, "floor": floor, "obstacles": obstacles, "drive": drive}
+
+
+def ground_snap_ref(positions, origin, resolution, ground, drive, max_drop):
+    """(M,3) positions -> (standing (M,3) f32, drop (M,) int32): from the position's voxel (x, y, z) down, the first k in 0 .. max_drop
+    with drive[x, y, z - k] and ground[x, y, z - k - 1]; standing is that voxel's centre fl(origin + fl(fl(i + 0.5) r)), drop is k.
+    -1: no such voxel; -2: out of range or outside dims; standing is NaN for both."""
+    ground, drive = np.asarray(ground, dtype=bool), np.asarray(drive, dtype=bool)
+    f32 = np.float32
+    o, r = np.asarray(origin, dtype=f32).reshape(3), f32(resolution)
+    q, ok = occ_fixed(positions, origin, resolution)
+    v = q >> 8
+    inside = ok & ((v >= 0) & (v < np.asarray(ground.shape)[None, :])).all(axis=1)
+    standing = np.full((len(v), 3), np.nan, dtype=f32)
+    drop = np.where(inside, -1, -2).astype(np.int32)
+    for i in np.flatnonzero(inside):
+        x, y, z = (int(c) for c in v[i])
+        for k in range(0, int(max_drop) + 1):
+            zz = z - k
+            if zz < 1:
+                break
+            if drive[x, y, zz] and ground[x, y, zz - 1]:
+                at = np.asarray((x, y, zz), dtype=f32)
+                standing[i] = (o + ((at + f32(0.5)).astype(f32) * r).astype(f32)).astype(f32)
+                drop[i] = k
+                break
+    return standing, drop
+
+
+def ground_pack(bits):
+    """A dense (nx,ny,nz) bool array -> the brick words (uint32, x fastest over the bricks) an occupancy plane holds after its
+    header: a word is 4 x 4 x 2 voxels, bit x&3 | (y&3)<<2 | (z&1)<<4; pad bits 0."""
+    bits = np.asarray(bits, dtype=bool)
+    nx, ny, nz = bits.shape
+    nbx, nby, nbz = (nx + 3) // 4, (ny + 3) // 4, (nz + 1) // 2
+    pad = np.zeros((4 * nbx, 4 * nby, 2 * nbz), dtype=np.uint32)
+    pad[:nx, :ny, :nz] = bits
+    b = pad.reshape(nbx, 4, nby, 4, nbz, 2)
+    sh = (np.arange(4)[:, None, None] + 4 * np.arange(4)[None, :, None] + 16 * np.arange(2)[None, None, :]).astype(np.uint32)
+    words = (b << sh[None, :, None, :, None, :]).sum(axis=(1, 3, 5), dtype=np.uint64).astype(np.uint32)   # (nbx, nby, nbz)
+    return np.ascontiguousarray(words.transpose(2, 1, 0)).reshape(-1)

@@ -309,6 +309,36 @@ def travel_field(field, start, radius, space=None, max_dist=None):
     return ops.TravelField(field, radius, start, space=space, max_dist=max_dist)
 
 
+def ground_layer(map, headroom, step=1, unknown='free'):
+    """For a robot that drives: an ops.GroundLayer ("Ground layer") over an ops.OccupancyGrid, ops.SpaceMap or
+    ops.EvidenceMap.  headroom: the robot's height in metres; step: the riser it climbs, in voxels (0 .. 4); unknown='obstacle'
+    (needs a free plane): unseen space neither carries nor lets pass.  layer.ground is where it can stand, layer.obstacles what it
+    must keep its radius from — the floor it rolls on is not among them — and layer.drive the slab its centre rides in.
+    layer.field(max_dist) and layer.space go wherever a clearance field and a space map go: travel_field(s), travel_matrix,
+    travel_path, free_nodes, plan_path, plan_tour(travel=True), refine_path, assign_frontiers, frontier_clusters(travel=),
+    select_views_volume(travel=).  layer.rebuild() follows the map."""
+    return ops.GroundLayer(map, headroom, step, unknown)
+
+
+def ground_travel(layer, start, radius, max_dist=None, max_drop=None, field=None):
+    """Can the robot DRIVE there, and how far is it?  The ops.TravelField of a ground layer: over layer.field(...) and layer.space,
+    from `start` — (3,) or (S,3) poses at any height above the floor, a sensor's for instance — snapped to the standing voxel at or
+    at most max_drop voxels below (None: the layer's headroom H; a start with nothing to stand on is ignored, tf.seeded).  radius:
+    the robot's, in metres; max_dist (metres) truncates the travel field; field: a ClearanceField from layer.field(...) to reuse
+    (None: one is built, truncated one voxel beyond what `radius` needs).  Every voxel with a cost is a place the robot's centre can
+    be: over ramps and steps of at most layer.step voxels, never across a ledge or a pit, under a table only where it fits.
+    tf.sources holds the snapped starts; layer.snap(path, max_drop) brings a path's rows down to the wheels."""
+    if not isinstance(layer, ops.GroundLayer):
+        raise ValueError(f"ground_travel: layer must be an ops.GroundLayer, got {type(layer).__name__}")
+    if field is None:
+        need = int(np.ceil(np.sqrt(ops.field_need2(ops.check_tour_radius(radius), layer.resolution))))
+        field = layer.field(D=min(need + 1, ops.FIELD_MAX_D))
+    elif not isinstance(field, ops.ClearanceField) or field.occupied is not layer.obstacles:
+        raise ValueError("ground_travel: field must be an ops.ClearanceField from layer.field(...)")
+    standing, _ = layer.snap(ops._check_rows3(start, "start"), layer.H if max_drop is None else max_drop)
+    return ops.TravelField(field, radius, standing, space=layer.space, max_dist=max_dist)
+
+
 def label_components(grid_or_plane, connectivity=26):
     """Which voxels belong together?  An ops.Components ("Connected components") of a bit plane: an ops.OccupancyGrid
     (an occupied grid, a free plane, space.unknown(), an evidence map's .occupied / .free) or anything that carries one as .grid
