@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_ground_build / tohip_ground_snap (the ground layer: where a robot that drives can stand, what is an obstacle for it
+/* (still 15) + tohip_scan_prepare / tohip_scan_score / tohip_scan_correlate / tohip_scan_best (scan-to-map registration: a scan scored
+ * against the evidence map at every pose of a search window, and the best of them): new symbols only.
+ * (still 15) + tohip_ground_build / tohip_ground_snap (the ground layer: where a robot that drives can stand, what is an obstacle for it
  * and the slab its centre rides in, as planes the field and travel entry points take unchanged): new symbols only.
  * (still 15) + tohip_travel_batch_bytes / tohip_travel_batch_workspace_bytes / tohip_travel_build_batch / tohip_travel_positions_batch /
  * tohip_travel_paths_batch / tohip_assign_greedy and TOHIP_TRAVEL_MAX_FIELDS (many travel fields built in the same worklist rounds, their
@@ -1548,6 +1550,37 @@ int tohip_ground_build(const void *occupied, const void *free_or_null, size_t gr
                        uint32_t flags);
 int tohip_ground_snap(const void *ground, const void *drive, size_t grid_bytes, const tohip_occ_geom *geom, const float *positions,
                       int64_t m, int32_t max_drop, float *standing, int32_t *drop, void *stream, uint32_t flags);
+
+/* ---- scan matching ("Scan matching") --------------------------------------------------
+ * Score a scan — points (n, 3) f32 in the SENSOR frame, 1 <= n <= 2^22 — against an evidence map at candidate poses.  A pose is 12
+ * f32: R row-major (9), then t (3).  The world coordinate of point p is, per axis a, fl(fl(fl(fl(R_a0 p_x) + fl(R_a1 p_y)) +
+ * fl(R_a2 p_z)) + t_a), and its voxel follows the coordinate rule of tohip_occ_insert.  A point out of range on any axis (NaN, inf)
+ * is skipped and not counted in `used`; a point in the apron takes part.  The VALUE of a voxel, with floor_value in [-127, 0] (-127:
+ * no floor) and unknown_value in [-127, 0]: max(L, floor_value) inside dims where L != -128; unknown_value where the voxel was never
+ * observed or lies outside dims.  The score of a candidate (pose, integer voxel shift s) is the sum over the points not skipped of
+ * the value of voxel(p) + s: an int32, the same in every run.
+ * tohip_scan_prepare: evidence bytes -> the score table, a buffer of tohip_evid_bytes in brick order: header 256 zero bytes, byte =
+ *   128 + value (pad voxels 128 + unknown_value).  table and evid: 16-byte aligned, different.
+ * tohip_scan_score: b explicit candidates (1 <= b <= 2^22) — poses (b, 12) f32 and shifts_or_null (b, 3) int32, any values: a shifted voxel
+ *   that does not fit 32 bits is outside dims — read from the
+ *   evidence bytes themselves -> score, used (points in range), inside (shifted voxel inside dims), known (inside and L != -128), each
+ *   (b) int32; zeroed here on the stream.
+ * tohip_scan_correlate: k poses (1 <= k <= 256) x the window |dx| <= wx, |dy| <= wy, |dz| <= wz (0 <= wx, wy <= 16, 0 <= wz <= 4),
+ *   S = (2wx+1)(2wy+1)(2wz+1), k S <= 2^22, from the TABLE (prepared with the same unknown_value) -> scores[k][dz+wz][dy+wy][dx+wx]
+ *   int32 (scores_bytes >= 4 k S) and used (k) int32; zeroed here on the stream.
+ * tohip_scan_best: the maximum of the key (score, then smaller dx^2+dy^2+dz^2, then lower flat index) over the k S scores -> best,
+ *   int32[8] on the device: flat index, k, dx, dy, dz, score, ties (the candidates whose score equals the best), 0.
+ * flags is reserved and must be 0.  A bad window, k, b, n, floor_value, unknown_value or flags, a null, misaligned or aliased buffer:
+ * TOHIP_EINVAL; a short buffer: TOHIP_ENOSPC.  Every argument check returns before anything is enqueued.  Nothing is read back. */
+int tohip_scan_prepare(const void *evid, size_t evid_bytes, const tohip_occ_geom *geom, int32_t floor_value, int32_t unknown_value,
+                       void *table, size_t table_bytes, void *stream, uint32_t flags);
+int tohip_scan_score(const void *evid, size_t evid_bytes, const tohip_occ_geom *geom, int32_t floor_value, int32_t unknown_value,
+                     const float *points, int64_t n, const float *poses, const int32_t *shifts_or_null, int64_t b, int32_t *score,
+                     int32_t *used, int32_t *inside, int32_t *known, void *stream, uint32_t flags);
+int tohip_scan_correlate(const void *table, size_t table_bytes, const tohip_occ_geom *geom, int32_t unknown_value, const float *points,
+                         int64_t n, const float *poses, int64_t k, int32_t wx, int32_t wy, int32_t wz, int32_t *scores,
+                         size_t scores_bytes, int32_t *used, void *stream, uint32_t flags);
+int tohip_scan_best(const int32_t *scores, int64_t k, int32_t wx, int32_t wy, int32_t wz, int32_t *best, void *stream, uint32_t flags);
 
 /* ---- optional per-kernel timing (bench.py's roofline leg) -----------------------------------------
  * When enabled, every launch of the big kernels is bracketed by hipEventRecord on its own stream.

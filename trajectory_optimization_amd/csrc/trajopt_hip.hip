@@ -20,6 +20,7 @@
 #include "frontier_kernels.hip"
 #include "field_kernels.hip"
 #include "evidence_kernels.hip"
+#include "scanmatch_kernels.hip"
 #include "reframe_kernels.hip"
 #include "travel_kernels.hip"
 #include "components_kernels.hip"

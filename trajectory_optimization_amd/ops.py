@@ -2113,6 +2113,181 @@ class GroundLayer:
         return standing, drop
 
 
+SCAN_MAX_WINDOW = (16, 16, 4)     # voxels a search window reaches per axis
+SCAN_MAX_ROTATIONS = 256
+SCAN_MAX_POINTS = 1 << 22
+SCAN_MAX_CANDIDATES = 1 << 22     # K S of a window search, B of explicit candidates
+
+
+def _host_rows(v, cols, name, rows=None):
+    """Host numbers -> a finite (rows, cols) float64 array: a list, a numpy array or a tensor (a device tensor is read back);
+    a single row may come flat."""
+    if torch.is_tensor(v):
+        v = v.detach().cpu().numpy()
+    try:
+        a = np.asarray(v, dtype=np.float64)
+    except (TypeError, ValueError):
+        a = None
+    if a is not None and a.ndim == 1 and a.shape[0] == cols:
+        a = a.reshape(1, cols)
+    if a is None or a.ndim != 2 or a.shape[1] != cols or a.shape[0] == 0 or (rows is not None and a.shape[0] != rows) or not np.isfinite(a).all():
+        raise ValueError(f"{name} must be ({'B' if rows is None else rows},{cols}) finite numbers on the host, got "
+                         f"{tuple(a.shape) if a is not None else type(v).__name__}")
+    return a
+
+
+def scan_rotations(quats, name="rotations"):
+    """(K,4) quaternions wxyz on the host -> (K,3,3) f32: each normalised in f64, the matrix of p -> q p conj(q) in f64 — depth_scan's
+    convention — rounded once to f32 (synth.scan_rotation)."""
+    q = _host_rows(quats, 4, name)
+    n = np.sqrt((q * q).sum(axis=1))
+    if not (n > 0.0).all():
+        raise ValueError(f"{name}: a quaternion of length 0")
+    w, x, y, z = (q / n[:, None]).T
+    R = np.stack([1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y),
+                  2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x),
+                  2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)], axis=1)
+    return R.astype(np.float32).reshape(-1, 3, 3)
+
+
+def check_scan_match(map, floor=None, unknown_value=0, window=None, n_rotations=None):
+    """A scan matcher's settings and a search's, by name; needs no GPU.  map: an ops.EvidenceMap (a SpaceMap goes through
+    EvidenceMap.from_space); floor: None (no floor) or an integer in [-127, 0]; unknown_value: an integer in [-127, 0]; window (None:
+    not asked): three integers (wx, wy, wz), 0 <= wx, wy <= 16, 0 <= wz <= 4; n_rotations (None: not asked): an integer K in [1, 256]
+    with K (2wx+1)(2wy+1)(2wz+1) <= 2^22.  -> (floor as the library takes it, unknown_value, window or None); ValueError otherwise."""
+    if not isinstance(map, EvidenceMap):
+        raise ValueError(f"ScanMatcher: the map must be an ops.EvidenceMap (EvidenceMap.from_space takes a SpaceMap), got {type(map).__name__}")
+    if floor is not None and (not _is_int(floor) or not -127 <= floor <= 0):
+        raise ValueError(f"floor must be None or an integer in [-127, 0], got {floor!r}")
+    if not _is_int(unknown_value) or not -127 <= unknown_value <= 0:
+        raise ValueError(f"unknown_value must be an integer in [-127, 0], got {unknown_value!r}")
+    if window is not None:
+        try:
+            w = tuple(window)
+        except TypeError:
+            w = ()
+        if len(w) != 3 or not all(_is_int(c) and 0 <= c <= m for c, m in zip(w, SCAN_MAX_WINDOW)):
+            raise ValueError(f"window must be three integers (wx, wy, wz) with 0 <= wx, wy <= 16 and 0 <= wz <= 4, got {window!r}")
+        window = tuple(int(c) for c in w)
+    if n_rotations is not None:
+        S = (2 * window[0] + 1) * (2 * window[1] + 1) * (2 * window[2] + 1) if window is not None else 1
+        if not _is_int(n_rotations) or not 1 <= n_rotations <= SCAN_MAX_ROTATIONS or n_rotations * S > SCAN_MAX_CANDIDATES:
+            raise ValueError(f"the rotations must number 1 .. {SCAN_MAX_ROTATIONS} with K (2wx+1)(2wy+1)(2wz+1) <= 2^22, got K = {n_rotations!r}"
+                             f"{'' if window is None else ' and a window of ' + str(S) + ' shifts'}")
+    return (-127 if floor is None else int(floor)), int(unknown_value), window
+
+
+class ScanMatcher:
+    """Scan-to-map registration on an evidence map (scanmatch_kernels.hip, DESIGN.md 10 "Scan matching"): a scan of sensor-frame points
+    is scored against the map's log-odds at candidate poses — the sum over the points of the value of the voxel each falls in, max(L,
+    floor) where the voxel was observed and unknown_value elsewhere — and correlate() scores every pose of a window of integer voxel
+    shifts around a prior, for a list of rotations, in one launch.  The matcher holds the SCORE TABLE, a second copy of the map's
+    bytes with floor and unknown_value applied: refresh() re-prepares it after the map took another scan.  Integers only: the same
+    scores in every run.  Points: (N,3) floating point on the map's device, 1 <= N <= 2^22; poses and quaternions: host numbers."""
+
+    def __init__(self, map, floor=None, unknown_value=0):
+        self.floor, self.unknown_value, _ = check_scan_match(map, floor, unknown_value)
+        self.map = map
+        self.origin, self.resolution, self.dims, self.device, self.geom = map.origin, map.resolution, map.dims, map.device, map.geom
+        self.table = torch.empty(map.buf.numel(), dtype=torch.uint8, device=self.device)
+        self.refresh()
+
+    def _call(self, name, *args):
+        with torch.cuda.device(self.device):
+            check(getattr(_lib.lib(), name)(*args, stream_ptr(), 0), name)
+
+    def refresh(self):
+        """Prepare the table from the map as it is now: one launch, nothing read back.  -> self."""
+        self._call("tohip_scan_prepare", *self.map._sizes(), self.floor, self.unknown_value, ptr(self.table), self.table.numel())
+        return self
+
+    def _points(self, points, what):
+        pts = covmap_points(points, self.device, what)
+        if not 1 <= pts.shape[0] <= SCAN_MAX_POINTS:
+            raise ValueError(f"{what}: the scan must hold 1 .. 2^22 points, got {pts.shape[0]}")
+        return pts
+
+    def poses(self, poses, quats):
+        """Host poses (B,3) (or one (3,) for all) and quaternions (B,4) -> the (B,12) f32 device tensor the kernels take: R row-major
+        from scan_rotations, then t rounded to f32.  The copy to the device comes from pageable host memory: it waits for the current
+        stream.  A caller that must not wait builds the tensor once and hands it to correlate / score as poses12=."""
+        R = scan_rotations(quats, "quats")
+        t = _host_rows(poses, 3, "poses")
+        if t.shape[0] == 1 and R.shape[0] > 1:
+            t = np.repeat(t, R.shape[0], axis=0)
+        if t.shape[0] != R.shape[0]:
+            raise ValueError(f"poses and quats must have as many rows, got {t.shape[0]} and {R.shape[0]}")
+        rows = np.concatenate([R.reshape(-1, 9), t.astype(np.float32)], axis=1)
+        return torch.from_numpy(np.ascontiguousarray(rows)).to(self.device)
+
+    def _poses12(self, poses12, what):
+        if (not torch.is_tensor(poses12) or poses12.dtype != torch.float32 or poses12.dim() != 2 or poses12.shape[1] != 12 or poses12.shape[0] == 0
+                or poses12.device != self.device or not poses12.is_contiguous()):
+            raise ValueError(f"{what}: poses12 must be a contiguous (B,12) float32 tensor on {self.device} (ScanMatcher.poses), got "
+                             f"{(tuple(poses12.shape), poses12.dtype, str(poses12.device)) if torch.is_tensor(poses12) else type(poses12).__name__}")
+        return poses12
+
+    def correlate(self, points, pose, rotations, window, poses12=None):
+        """Every pose of a search window: pose (3,), the prior translation; rotations (K,4) quaternions, the caller's list; window (wx,
+        wy, wz) in voxels.  -> (scores (K, 2wz+1, 2wy+1, 2wx+1) int32, used (K,) int32) on the device: scores[k][dz+wz][dy+wy][dx+wx]
+        is the score of rotation k with every point's voxel moved by (dx, dy, dz); used[k] the points in range under rotation k.  The
+        table is read, not the map: refresh() after an integrate.  poses12: the (K,12) device tensor of poses() instead of pose and
+        rotations, which are then not looked at.  Two clears and one launch, nothing read back; without poses12 the poses' copy to the
+        device waits for the current stream first (poses())."""
+        pts = self._points(points, "ScanMatcher.correlate")
+        if poses12 is None:
+            poses12 = self.poses(_host_rows(pose, 3, "pose", rows=1), rotations)
+        else:
+            poses12 = self._poses12(poses12, "ScanMatcher.correlate")
+        K = poses12.shape[0]
+        _, _, (wx, wy, wz) = check_scan_match(self.map, None, self.unknown_value, window, K)
+        scores = torch.empty((K, 2 * wz + 1, 2 * wy + 1, 2 * wx + 1), dtype=torch.int32, device=self.device)
+        used = torch.empty(K, dtype=torch.int32, device=self.device)
+        self._call("tohip_scan_correlate", ptr(self.table), self.table.numel(), ctypes.byref(self.geom), self.unknown_value, ptr(pts),
+                   pts.shape[0], ptr(poses12), K, wx, wy, wz, ptr(scores), scores.numel() * 4, ptr(used))
+        return scores, used
+
+    def score(self, points, poses, quats, shifts=None, poses12=None):
+        """B explicit candidates, straight from the map's bytes (no table): poses (B,3) and quats (B,4) on the host, shifts None or
+        (B,3) integers, voxels added to every point's voxel (a device int32 tensor is taken as it is).  -> (score, used, inside,
+        known), each (B,) int32 on the device: the score; the points in range; those whose shifted voxel lies inside dims; those that
+        met an observed voxel there.  What a particle filter weighs its particles by.  poses12: the (B,12) device tensor of poses()
+        instead of poses and quats.  Four clears and one launch, nothing read back; without poses12, and with shifts from the host,
+        the copies to the device wait for the current stream first (poses())."""
+        pts = self._points(points, "ScanMatcher.score")
+        if poses12 is None:
+            poses12 = self.poses(poses, quats)
+        else:
+            poses12 = self._poses12(poses12, "ScanMatcher.score")
+        B = poses12.shape[0]
+        if not 1 <= B <= SCAN_MAX_CANDIDATES:
+            raise ValueError(f"ScanMatcher.score: 1 .. 2^22 candidates, got {B}")
+        if shifts is not None:
+            if not torch.is_tensor(shifts):
+                shifts = torch.from_numpy(np.ascontiguousarray(np.asarray(shifts, dtype=np.int64).astype(np.int32)))
+            if shifts.is_floating_point() or tuple(shifts.shape) != (B, 3):
+                raise ValueError(f"shifts must be ({B},3) integers, got {tuple(shifts.shape)} of {shifts.dtype}")
+            shifts = shifts.to(device=self.device, dtype=torch.int32).contiguous()
+        out = torch.empty((4, B), dtype=torch.int32, device=self.device)
+        self._call("tohip_scan_score", *self.map._sizes(), self.floor, self.unknown_value, ptr(pts), pts.shape[0], ptr(poses12),
+                   ptr(shifts), B, ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]))
+        return out[0], out[1], out[2], out[3]
+
+    def best(self, scores):
+        """The best candidate of correlate's scores -> int32[8] on the device: flat index, k, dx, dy, dz, score, ties, 0 — the maximum
+        of the key (score, then smaller dx^2 + dy^2 + dz^2, then lower flat index); ties: the candidates whose score equals the best.
+        One launch of one block, nothing read back."""
+        if (not torch.is_tensor(scores) or scores.dtype != torch.int32 or scores.dim() != 4 or not scores.is_contiguous()
+                or scores.device != self.device or any(n % 2 == 0 for n in scores.shape[1:])):
+            raise ValueError("scores must be the contiguous (K, 2wz+1, 2wy+1, 2wx+1) int32 tensor correlate returned")
+        K, nzw, nyw, nxw = scores.shape
+        window = (nxw // 2, nyw // 2, nzw // 2)
+        check_scan_match(self.map, None, self.unknown_value, window, K)
+        best = torch.empty(8, dtype=torch.int32, device=self.device)
+        self._call("tohip_scan_best", ptr(scores), K, *window, ptr(best))
+        return best
+
+
 XFER_MAX_SHIFT = 4096      # of a voxel shift per axis (tohip_occ_transfer / tohip_evid_transfer)
 XFER_MODES = {"copy": 0, "or": 1, "add": 1, "confident": 2}
 LATTICE_TOLERANCE = 1.0 / 256.0   # the layer's fixed-point unit, in voxels

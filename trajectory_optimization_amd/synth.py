@@ -1843,3 +1843,118 @@ def ground_pack(bits):
     sh = (np.arange(4)[:, None, None] + 4 * np.arange(4)[None, :, None] + 16 * np.arange(2)[None, None, :]).astype(np.uint32)
     words = (b << sh[None, :, None, :, None, :]).sum(axis=(1, 3, 5), dtype=np.uint64).astype(np.uint32)   # (nbx, nby, nbz)
     return np.ascontiguousarray(words.transpose(2, 1, 0)).reshape(-1)
+
+
+# ---- scan matching restated in numpy ("Scan matching"): what scanmatch_kernels.hip must give, bit for bit -----------
+SCAN_MAX_WINDOW = (16, 16, 4)
+SCAN_MAX_ROTATIONS = 256
+SCAN_MAX_POINTS = 1 << 22
+SCAN_MAX_CANDIDATES = 1 << 22
+
+
+def scan_rotation(quat):
+    """A quaternion (4,) wxyz -> R (3,3) f32: normalised in f64, the rotation matrix of p -> q p conj(q) in f64, rounded once."""
+    q = np.asarray(quat, dtype=np.float64).reshape(4)
+    w, x, y, z = q / np.sqrt((q * q).sum())
+    R = np.array([[1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y)],
+                  [2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x)],
+                  [2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)]], dtype=np.float64)
+    return R.astype(np.float32)
+
+
+def scan_voxels_ref(points, R, t, origin, resolution):
+    """Sensor-frame points (N,3) under the pose (R (3,3), t (3,)) -> (voxel (N,3) int64, ok (N,) bool): per axis a the world coordinate
+    fl(fl(fl(fl(R_a0 p_x) + fl(R_a1 p_y)) + fl(R_a2 p_z)) + t_a) in f32, then occ_fixed's rule and q >> 8.  ok: in range on every axis
+    (false for NaN and inf): the points that take part."""
+    f32 = np.float32
+    P = np.asarray(points, dtype=f32).reshape(-1, 3)
+    R, t = np.asarray(R, dtype=f32).reshape(3, 3), np.asarray(t, dtype=f32).reshape(3)
+    with np.errstate(all="ignore"):
+        cols = []
+        for a in range(3):
+            s = ((R[a, 0] * P[:, 0]).astype(f32) + (R[a, 1] * P[:, 1]).astype(f32)).astype(f32)
+            s = (s + (R[a, 2] * P[:, 2]).astype(f32)).astype(f32)
+            cols.append((s + t[a]).astype(f32))
+        W = np.stack(cols, axis=1)
+    q, ok = occ_fixed(W, origin, resolution)
+    return q >> 8, ok
+
+
+def scan_values_ref(L, floor=None, unknown_value=0):
+    """The value volume of the log-odds L (nx,ny,nz): max(L, floor) where L != -128 (floor None or -127: no floor), unknown_value where
+    it is -128 -> int64."""
+    L = np.asarray(L, dtype=np.int64)
+    fl = -127 if floor is None else int(floor)
+    if not -127 <= fl <= 0 or not -127 <= int(unknown_value) <= 0:
+        raise ValueError(f"floor and unknown_value must lie in [-127, 0], got {floor!r}, {unknown_value!r}")
+    return np.where(L == EVID_UNKNOWN, int(unknown_value), np.maximum(L, fl))
+
+
+def scan_table_ref(L, floor=None, unknown_value=0):
+    """The score table of the values L -> the byte image (256 + 32 words,) uint8: a zero header, then 128 + value per voxel in brick
+    order, 128 + unknown_value in the pad voxels."""
+    L = np.asarray(L, dtype=np.int64)
+    img = evidence_brick_order(L)   # (pads -128)
+    vals = scan_values_ref(img[EVID_HEADER:].view(np.int8).astype(np.int64), floor, unknown_value)
+    return np.concatenate([np.zeros(EVID_HEADER, dtype=np.uint8), (vals + 128).astype(np.uint8)])
+
+
+def scan_score_ref(L, origin, resolution, points, R, t, shift=(0, 0, 0), floor=None, unknown_value=0):
+    """One candidate, point by point -> (score, used, inside, known): used = the points in range; inside = those whose voxel + shift
+    lies inside dims; known = those with L != -128 there; score = the sum over the used points of the value of voxel + shift
+    (unknown_value outside dims)."""
+    L = np.asarray(L, dtype=np.int64)
+    V = scan_values_ref(L, floor, unknown_value)
+    v, ok = scan_voxels_ref(points, R, t, origin, resolution)
+    v = v[ok] + np.asarray(shift, dtype=np.int64).reshape(1, 3)
+    ins = ((v >= 0) & (v < np.asarray(L.shape)[None, :])).all(axis=1)
+    vi = v[ins]
+    known = L[vi[:, 0], vi[:, 1], vi[:, 2]] != EVID_UNKNOWN
+    score = int(V[vi[:, 0], vi[:, 1], vi[:, 2]].sum()) + int(unknown_value) * int((~ins).sum())
+    return score, int(ok.sum()), int(ins.sum()), int(known.sum())
+
+
+def scan_correlate_ref(L, origin, resolution, points, Rs, t, window, floor=None, unknown_value=0, chunk=2048):
+    """Every candidate of a search window -> (scores (K, 2wz+1, 2wy+1, 2wx+1) int32, used (K,) int32): rotations Rs (K,3,3), one
+    translation t, shifts |dx| <= wx, |dy| <= wy, |dz| <= wz.  The value volume is padded with unknown_value by twice the window; a
+    point whose base voxel lies farther than the window from dims sees unknown_value at every shift; the others read their window
+    of the padded volume."""
+    L = np.asarray(L, dtype=np.int64)
+    w = np.asarray([int(c) for c in window], dtype=np.int64)
+    if (w < 0).any() or (w > np.asarray(SCAN_MAX_WINDOW)).any():
+        raise ValueError(f"window must lie in [0, {SCAN_MAX_WINDOW}] per axis, got {tuple(window)!r}")
+    Rs = np.asarray(Rs, dtype=np.float32).reshape(-1, 3, 3)
+    dims = np.asarray(L.shape, dtype=np.int64)
+    V = scan_values_ref(L, floor, unknown_value)
+    pad = np.full(tuple(dims + 4 * w), int(unknown_value), dtype=np.int64)
+    pad[2 * w[0]:2 * w[0] + dims[0], 2 * w[1]:2 * w[1] + dims[1], 2 * w[2]:2 * w[2] + dims[2]] = V
+    views = np.lib.stride_tricks.sliding_window_view(pad, tuple(2 * w + 1))   # [x0, y0, z0, i, j, k] = pad[x0 + i, y0 + j, z0 + k]
+    scores = np.zeros((len(Rs),) + tuple(2 * w[::-1] + 1), dtype=np.int64)
+    used = np.zeros(len(Rs), dtype=np.int32)
+    for k, R in enumerate(Rs):
+        v, ok = scan_voxels_ref(points, R, t, origin, resolution)
+        v = v[ok]
+        used[k] = len(v)
+        near = ((v >= -w) & (v < dims + w)).all(axis=1)
+        acc = np.full(tuple(2 * w + 1), int(unknown_value) * int((~near).sum()), dtype=np.int64)
+        b = v[near] + w   # the window's first voxel v - w in the padded volume: v - w + 2 w
+        for i in range(0, len(b), chunk):
+            c = b[i:i + chunk]
+            acc += views[c[:, 0], c[:, 1], c[:, 2]].sum(axis=0)
+        scores[k] = acc.transpose(2, 1, 0)
+    return scores.astype(np.int32), used
+
+
+def scan_best_ref(scores):
+    """The best candidate of scores (K, nzw, nyw, nxw) -> int32[8]: flat index, k, dx, dy, dz, score, ties, 0 under the key (score,
+    then smaller dx^2 + dy^2 + dz^2, then lower flat index); ties counts the candidates whose score equals the best."""
+    s = np.asarray(scores, dtype=np.int64)
+    K, nzw, nyw, nxw = s.shape
+    dz, dy, dx = np.meshgrid(np.arange(nzw) - nzw // 2, np.arange(nyw) - nyw // 2, np.arange(nxw) - nxw // 2, indexing="ij")
+    d2 = np.broadcast_to(dx * dx + dy * dy + dz * dz, s.shape).reshape(-1)
+    flat = s.reshape(-1)
+    top = flat.max()
+    cand = np.flatnonzero(flat == top)
+    i = int(cand[np.argmin(d2[cand])])   # (argmin: the first of equals, the lower index)
+    return np.array([i, i // (nzw * nyw * nxw), dx.reshape(-1)[i % dx.size], dy.reshape(-1)[i % dx.size], dz.reshape(-1)[i % dx.size], top,
+                     len(cand), 0], dtype=np.int32)

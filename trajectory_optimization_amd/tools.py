@@ -339,6 +339,115 @@ def ground_travel(layer, start, radius, max_dist=None, max_drop=None, field=None
     return ops.TravelField(field, radius, standing, space=layer.space, max_dist=max_dist)
 
 
+def yaw_candidates(quat, half_range, n):
+    """n headings about the world's z axis, centred on `quat` (wxyz) -> (n,4) float64 on the host: n odd, the yaw offsets evenly spaced
+    over [-half_range, +half_range] radians (0 for n = 1), each composed in f64 as yaw(a) * quat.  The middle row is `quat` itself,
+    normalised: its offset is exactly 0."""
+    q = ops._host_rows(quat, 4, "quat", rows=1)[0]
+    if not ops._is_int(n) or n < 1 or n % 2 == 0 or n > ops.SCAN_MAX_ROTATIONS:
+        raise ValueError(f"yaw_candidates: n must be an odd integer in [1, {ops.SCAN_MAX_ROTATIONS}], got {n!r}")
+    h = ops._float_or_nan(half_range)
+    if not (np.isfinite(h) and 0.0 <= h <= math.pi):
+        raise ValueError(f"yaw_candidates: half_range must be a finite angle in [0, pi] radians, got {half_range!r}")
+    q = q / np.sqrt((q * q).sum())
+    m = n // 2
+    w, x, y, z = q
+    out = np.tile(q, (n, 1))
+    for i in range(n):
+        if i != m:
+            c, s = math.cos(0.5 * h * (i - m) / m), math.sin(0.5 * h * (i - m) / m)
+            out[i] = (c * w - s * z, c * x - s * y, c * y + s * x, c * z + s * w)   # (c, 0, 0, s) * q
+    return out
+
+
+def scan_refine(volume, at):
+    """The sub-voxel offset (dx, dy, dz) of one rotation's window volume (2wz+1, 2wy+1, 2wx+1) around its best cell at = (dzi, dyi,
+    dxi) -> (3,) float64 in voxels: per axis the vertex 0.5 (s- - s+) / (s+ - 2 s0 + s-) of the parabola through the best score and
+    its two neighbours along that axis, only where both neighbours lie inside the window and the second difference is negative,
+    clamped to +-0.5 voxel; 0 otherwise.  Host arithmetic in f64."""
+    v = np.asarray(volume, dtype=np.float64)
+    at = tuple(int(c) for c in at)
+    out = np.zeros(3, dtype=np.float64)
+    for axis in range(3):       # of the volume: 0 is z, 1 is y, 2 is x
+        i = at[axis]
+        if i < 1 or i > v.shape[axis] - 2:
+            continue
+        lo, hi = list(at), list(at)
+        lo[axis], hi[axis] = i - 1, i + 1
+        s0, sm, sp = v[at], v[tuple(lo)], v[tuple(hi)]
+        dd = sp - 2.0 * s0 + sm
+        if dd < 0.0:
+            out[2 - axis] = min(0.5, max(-0.5, 0.5 * (sm - sp) / dd))
+    return out
+
+
+def _scan_matcher(what, map_or_matcher, floor, unknown_value):
+    if isinstance(map_or_matcher, ops.ScanMatcher):
+        if floor is not None or not (ops._is_int(unknown_value) and unknown_value == 0):
+            raise ValueError(f"{what}: floor and unknown_value belong to the ScanMatcher that was given (floor {map_or_matcher.floor}, "
+                             f"unknown_value {map_or_matcher.unknown_value}); leave them at their defaults, got {floor!r} and {unknown_value!r}")
+        return map_or_matcher
+    if isinstance(map_or_matcher, ops.SpaceMap):
+        raise ValueError(f"{what}: a SpaceMap holds no log-odds: give ops.EvidenceMap.from_space(space)")
+    return ops.ScanMatcher(map_or_matcher, floor, unknown_value)
+
+
+def match_scan(map_or_matcher, points, pose, quat, window=(8, 8, 2), yaw=None, rotations=None, floor=None, unknown_value=0, refine=True):
+    """Where was the sensor when it took this scan?  Correlative scan matching on an ops.EvidenceMap ("Scan matching"):
+    `points` (N,3), the scan in the SENSOR frame, is scored against the map at the prior `pose` (3,) / `quat` (4,) wxyz moved by every
+    integer voxel shift of `window` = (wx, wy, wz) and turned to every candidate rotation, and the best is returned -> ScanMatch.
+    The rotations are the caller's list: yaw=(half_range_rad, n) asks for yaw_candidates(quat, half_range, n); rotations=(K,4)
+    gives the list itself; neither: the prior's rotation alone.  map_or_matcher: the map — floor and unknown_value then shape the
+    score: max(L, floor) where observed, unknown_value elsewhere — or an ops.ScanMatcher to reuse over several scans of one map
+    (refresh() it after an integrate; floor and unknown_value are then the matcher's and must be left at their defaults).  refine: fit a parabola per axis through the best score and its neighbours for a sub-voxel
+    translation, pose_refined.  Translation is found to one voxel (or to the parabola), rotation to the list's spacing; there is no
+    covariance.  One read-back: the best candidate's eight integers and its counters (and, with refine, its rotation's window);
+    before it one copy of the K poses to the device, which waits for the current stream."""
+    matcher = _scan_matcher("match_scan", map_or_matcher, floor, unknown_value)
+    prior = ops._host_rows(quat, 4, "quat", rows=1)
+    if yaw is not None and rotations is not None:
+        raise ValueError("match_scan: give yaw or rotations, not both")
+    if yaw is not None:
+        try:
+            half_range, n = yaw
+        except (TypeError, ValueError):
+            raise ValueError(f"match_scan: yaw must be (half_range_rad, n), got {yaw!r}") from None
+        quats = yaw_candidates(prior, half_range, n)
+    else:
+        quats = ops._host_rows(prior if rotations is None else rotations, 4, "rotations")
+    t = ops._host_rows(pose, 3, "pose", rows=1)
+    poses12 = matcher.poses(t, quats)
+    scores, used = matcher.correlate(points, t, quats, window, poses12=poses12)
+    best = matcher.best(scores)
+    k = best[1:2].long()
+    counters = matcher.score(points, None, None, shifts=best[2:5].reshape(1, 3), poses12=poses12.index_select(0, k))
+    parts = [best, torch.cat(counters), used.index_select(0, k)]
+    if refine:
+        parts.append(scores.index_select(0, k).reshape(-1))
+    host = torch.cat(parts).cpu().numpy()   # the one read-back
+    flat, kk, dx, dy, dz, score, ties = (int(v) for v in host[:7])
+    if int(host[8]) != score:
+        raise RuntimeError(f"match_scan: the window's best score {score} and the winner's own {int(host[8])} differ: the matcher's table is "
+                           "stale — refresh() it after the map took a scan")
+    r = np.float32(matcher.resolution)
+    shift = np.asarray((dx, dy, dz), dtype=np.float32)
+    found = (t[0].astype(np.float32) + (shift * r).astype(np.float32)).astype(np.float32)
+    refined = found.astype(np.float64)
+    if refine:
+        volume = host[13:].reshape(scores.shape[1:])
+        w = tuple(n // 2 for n in scores.shape[1:])
+        refined = refined + scan_refine(volume, (dz + w[0], dy + w[1], dx + w[2])) * float(r)
+    return ScanMatch(pose=found, quat=quats[kk].copy(), shift=(dx, dy, dz), rotation=kk, score=score, used=int(host[12]), known=int(host[11]),
+                     ties=ties, scores=scores, pose_refined=refined)
+
+
+def score_scans(map_or_matcher, points, poses, quats, shifts=None, floor=None, unknown_value=0):
+    """How well does the scan fit the map at each of these poses?  B explicit candidates — poses (B,3), quats (B,4) wxyz, shifts None
+    or (B,3) voxels — -> (score, used, inside, known), each (B,) int32 on the device (ops.ScanMatcher.score): the weights a particle
+    filter needs, read from the map's bytes themselves.  One launch, nothing read back."""
+    return _scan_matcher("score_scans", map_or_matcher, floor, unknown_value).score(points, poses, quats, shifts)
+
+
 def label_components(grid_or_plane, connectivity=26):
     """Which voxels belong together?  An ops.Components ("Connected components") of a bit plane: an ops.OccupancyGrid
     (an occupied grid, a free plane, space.unknown(), an evidence map's .occupied / .free) or anything that carries one as .grid
@@ -438,6 +547,22 @@ class _Result:
     def __init__(self, **kw):
         for k, v in kw.items():
             setattr(self, k, v)
+
+
+class ScanMatch(_Result):
+    """What match_scan returns: pose (3,) f32 — fl(prior + fl(shift r)) per axis — and quat (4,) f64, the winning candidate; shift (dx,
+    dy, dz) in voxels and rotation, its row of the list; score; used (the points in range under that rotation), known (those that met
+    an observed voxel), ties (the candidates that share the best score: 1 for a unique answer); scores (K, 2wz+1, 2wy+1, 2wx+1) int32
+    on the device; pose_refined (3,) f64, the pose moved by the parabola's sub-voxel offset (equal to pose with refine=False);
+    world(points) takes sensor-frame points to the world at the matched pose."""
+    __slots__ = ("pose", "quat", "shift", "rotation", "score", "used", "known", "ties", "scores", "pose_refined")
+
+    def world(self, points, refined=False):
+        """(N,3) sensor-frame points on a device -> (N,3) f32 world points at the matched (or refined) pose: torch ops, rounded as torch
+        rounds them — the scores' own arithmetic is not promised."""
+        R = torch.from_numpy(ops.scan_rotations(self.quat, "quat")[0]).to(points.device)
+        t = torch.as_tensor(np.asarray(self.pose_refined if refined else self.pose, dtype=np.float32), device=points.device)
+        return points.to(torch.float32) @ R.T + t
 
 
 class ViewSelection(_Result):
