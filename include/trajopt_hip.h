@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_scan_prepare / tohip_scan_score / tohip_scan_correlate / tohip_scan_best (scan-to-map registration: a scan scored
+/* (still 15) + tohip_reloc_levels / tohip_reloc_bounds / tohip_reloc_workspace_bytes / tohip_reloc_search (relocalisation: exact
+ * branch-and-bound scan matching over wide windows, on sliding-maximum copies of the score table): new symbols only.
+ * (still 15) + tohip_scan_prepare / tohip_scan_score / tohip_scan_correlate / tohip_scan_best (scan-to-map registration: a scan scored
  * against the evidence map at every pose of a search window, and the best of them): new symbols only.
  * (still 15) + tohip_ground_build / tohip_ground_snap (the ground layer: where a robot that drives can stand, what is an obstacle for it
  * and the slab its centre rides in, as planes the field and travel entry points take unchanged): new symbols only.
@@ -1581,6 +1583,47 @@ int tohip_scan_correlate(const void *table, size_t table_bytes, const tohip_occ_
                          int64_t n, const float *poses, int64_t k, int32_t wx, int32_t wy, int32_t wz, int32_t *scores,
                          size_t scores_bytes, int32_t *used, void *stream, uint32_t flags);
 int tohip_scan_best(const int32_t *scores, int64_t k, int32_t wx, int32_t wy, int32_t wz, int32_t *best, void *stream, uint32_t flags);
+
+/* ---- relocalisation (scansearch_kernels.hip, DESIGN.md §10, "Relocalisation") -------------------------
+ * The best candidate of a WIDE window — |dx| <= wx, |dy| <= wy (0 <= wx, wy <= 2048), |dz| <= wz (0 <= wz <= 4), k rotations (1 <= k
+ * <= 256) — by branch and bound, equal to the exhaustive search's under scan matching's key, bit for bit.  Poses, points, values and
+ * the score of a candidate are scan matching's; table is tohip_scan_prepare's.  With u = 128 + unknown_value:
+ * LEVEL TABLES: T_0 is the table; T_h (1 <= h <= 6) has its size, header and brick order, and for a voxel inside dims T_h(x, y, z) =
+ *   max over 0 <= i, j < 2^h of T_0'(x + i, y + j, z), T_0' being T_0 continued by u outside dims; pad voxels hold u.
+ * LOOKUP: with b = 2^h - 1, B_h(x, y, z) = u where z is outside [0, nz) or x outside [-b, nx) or y outside [-b, ny); otherwise
+ *   T_h(max(x, 0), max(y, 0), z), replaced by max(that, u) where x < 0 or y < 0.
+ * NODE: four int32 (k, sx, sy, sz) at a level h: rotation k, dz = sz, dx in [sx, sx + 2^h) and dy in [sy, sy + 2^h), cut to the
+ *   window.  Its BOUND: the sum over the points in range under rotation k of B_h(voxel_k(p) + (sx, sy, sz)), less 128 x their number
+ *   — an int32, at level 0 the candidate's score.
+ * tohip_reloc_levels: table -> levels, h tables of tohip_evid_bytes each, T_1 first (16-byte aligned, not overlapping the table;
+ *   levels_bytes >= h x that size).  h launches.
+ * tohip_reloc_bounds: m explicit nodes (m, 4) int32 (1 <= m <= 2^22, 16-byte aligned, any order, any shifts) of one level (0 .. 6),
+ *   `table` being THAT level's table -> bounds (m) int32 and used (k) int32, the points in range under each rotation; a node whose k
+ *   is outside [0, k) gets INT32_MIN.  workspace: tohip_reloc_workspace_bytes(m), 16-byte aligned, contents undefined before and after.
+ * tohip_reloc_workspace_bytes(capacity): what a search with that capacity (1 .. 2^24 nodes a level), or bounds of that many nodes,
+ *   needs; 0 for a capacity out of range.
+ * tohip_reloc_search: the whole search, h levels (0 <= h <= 6; levels_or_null may be NULL for h = 0), enqueued at once.  The top
+ *   level holds every node with sx in {-wx, -wx + 2^h, ...} <= wx, sy likewise, every sz and every rotation; per level h .. 1 the node
+ *   with the largest bound (then the lowest (k, sz, sy, sx)) is followed greedily to a leaf, the incumbent becomes max(incumbent, the
+ *   leaf's score), every node whose bound is below the incumbent is dropped and the others are replaced by their up to four children
+ *   (sx, sy) + {0, 2^(h-1)}^2 that start inside the window.  -> record, 18 int64 on the device: the flat index ((k (2wz+1) + dz+wz)
+ *   (2wy+1) + dy+wy) (2wx+1) + dx+wx of the winner, k, dx, dy, dz, score, ties, status, incumbent (INT32_MIN for h = 0), evaluated
+ *   (all bounds computed, descents included), h, then nodes[0 .. h], the nodes of each level before the drop; the rest 0.  A level
+ *   that would hold more than `capacity` nodes stops the search: status = count << 3 | (level + 1), flat index -1, nodes[level] =
+ *   count, and nothing is written past a buffer; status 0 otherwise.  The order of a node list in memory is not defined; the record is
+ *   the same in every run.
+ * flags is reserved and must be 0.  A bad window, k, h, level, n, m, capacity, unknown_value or flags, a null, misaligned or aliased
+ * buffer: TOHIP_EINVAL; a short buffer: TOHIP_ENOSPC.  Every argument check returns before anything is enqueued.  Nothing is read back. */
+int tohip_reloc_levels(const void *table, size_t table_bytes, const tohip_occ_geom *geom, int32_t unknown_value, int32_t h, void *levels,
+                       size_t levels_bytes, void *stream, uint32_t flags);
+int tohip_reloc_bounds(const void *table, size_t table_bytes, const tohip_occ_geom *geom, int32_t unknown_value, int32_t level,
+                       const float *points, int64_t n, const float *poses, int64_t k, const int32_t *nodes, int64_t m, int32_t *bounds,
+                       int32_t *used, void *workspace, size_t workspace_bytes, void *stream, uint32_t flags);
+size_t tohip_reloc_workspace_bytes(int64_t capacity);
+int tohip_reloc_search(const void *table, size_t table_bytes, const void *levels_or_null, size_t levels_bytes, const tohip_occ_geom *geom,
+                       int32_t unknown_value, int32_t h, const float *points, int64_t n, const float *poses, int64_t k, int32_t wx,
+                       int32_t wy, int32_t wz, int64_t capacity, int64_t *record, void *workspace, size_t workspace_bytes, void *stream,
+                       uint32_t flags);
 
 /* ---- optional per-kernel timing (bench.py's roofline leg) -----------------------------------------
  * When enabled, every launch of the big kernels is bracketed by hipEventRecord on its own stream.

@@ -2197,7 +2197,9 @@ class ScanMatcher:
             check(getattr(_lib.lib(), name)(*args, stream_ptr(), 0), name)
 
     def refresh(self):
-        """Prepare the table from the map as it is now: one launch, nothing read back.  -> self."""
+        """Prepare the table from the map as it is now: one launch, nothing read back; the level tables of levels() are dropped.
+        -> self."""
+        self._levels = None
         self._call("tohip_scan_prepare", *self.map._sizes(), self.floor, self.unknown_value, ptr(self.table), self.table.numel())
         return self
 
@@ -2286,6 +2288,128 @@ class ScanMatcher:
         best = torch.empty(8, dtype=torch.int32, device=self.device)
         self._call("tohip_scan_best", ptr(scores), K, *window, ptr(best))
         return best
+
+    # ---- relocalisation: exact branch and bound over wide windows (scansearch_kernels.hip, DESIGN.md 10 "Relocalisation")
+
+    def levels(self, H):
+        """The level tables T_1 .. T_H of the score table -> an (H, table bytes) uint8 tensor, row h - 1 the sliding maximum of the
+        table over 2^h x 2^h voxels in x and y (check_scan_search: 0 <= H <= 6; H = 0: no rows).  Built once — H launches — and kept;
+        refresh() drops them, a larger H builds them anew.  H + 1 copies of the table in all: 7.3 MB each for a 405 x 405 x 45 room."""
+        check_scan_search(self.map, levels=H)
+        if self._levels is None or self._levels.shape[0] < H:
+            lv = torch.empty((H, self.table.numel()), dtype=torch.uint8, device=self.device)
+            if H > 0:
+                self._call("tohip_reloc_levels", ptr(self.table), self.table.numel(), ctypes.byref(self.geom), self.unknown_value, H, ptr(lv),
+                           lv.numel())
+            self._levels = lv
+        return self._levels[:H]
+
+    def _workspace(self, capacity):
+        return torch.empty(_lib.lib().tohip_reloc_workspace_bytes(capacity), dtype=torch.uint8, device=self.device)
+
+    def bound(self, points, nodes, level, pose=None, rotations=None, poses12=None):
+        """The bounds of explicit nodes of one level: nodes (M,4) integers (k, sx, sy, sz), any order, 1 <= M <= 2^22 (a device int32
+        tensor is taken as it is); pose and rotations, or poses12, as correlate takes them.  -> (bounds (M,) int32, used (K,) int32) on
+        the device: bounds[i] = the sum over the points in range under rotation k of B_level(voxel + (sx, sy, sz)) - 128 used[k], an
+        upper bound of the score of every candidate (k, dx in [sx, sx + 2^level), dy in [sy, sy + 2^level), dz = sz) and at level 0
+        the score itself; INT32_MIN for a k outside [0, K).  Nothing read back."""
+        pts = self._points(points, "ScanMatcher.bound")
+        _, level, _, _ = check_scan_search(self.map, levels=level)
+        if poses12 is None:
+            poses12 = self.poses(_host_rows(pose, 3, "pose", rows=1), rotations)
+        else:
+            poses12 = self._poses12(poses12, "ScanMatcher.bound")
+        K = poses12.shape[0]
+        check_scan_search(self.map, n_rotations=K)
+        if not torch.is_tensor(nodes):
+            nodes = torch.from_numpy(np.ascontiguousarray(np.asarray(nodes, dtype=np.int64).astype(np.int32)))
+        if nodes.is_floating_point() or nodes.dim() != 2 or nodes.shape[1] != 4 or not 1 <= nodes.shape[0] <= SCAN_MAX_CANDIDATES:
+            raise ValueError(f"nodes must be (M,4) integers (k, sx, sy, sz) with 1 <= M <= 2^22, got {tuple(nodes.shape)} of {nodes.dtype}")
+        nodes = nodes.to(device=self.device, dtype=torch.int32).contiguous()
+        M = nodes.shape[0]
+        table = self.table if level == 0 else self.levels(level)[level - 1]
+        bounds = torch.empty(M, dtype=torch.int32, device=self.device)
+        used = torch.empty(K, dtype=torch.int32, device=self.device)
+        work = self._workspace(M)
+        self._call("tohip_reloc_bounds", ptr(table), table.numel(), ctypes.byref(self.geom), self.unknown_value, level, ptr(pts), pts.shape[0],
+                   ptr(poses12), K, ptr(nodes), M, ptr(bounds), ptr(used), ptr(work), work.numel())
+        return bounds, used
+
+    def search(self, points, pose, rotations, window, levels=None, capacity=1 << 22, poses12=None):
+        """The best candidate of a WIDE window, exactly: window (wx, wy, wz) with 0 <= wx, wy <= 2048, 0 <= wz <= 4, K <= 256
+        rotations; levels H in [0, 6] (None: scan_search_levels(window)).  Branch and bound over the level tables: equal to best(
+        correlate(...)) where correlate's window reaches, bit for bit.  -> the record, (18,) int64 on the device: flat index ((k
+        (2wz+1) + dz+wz)(2wy+1) + dy+wy)(2wx+1) + dx+wx, k, dx, dy, dz, score, ties, status, incumbent, evaluated, H, nodes[0 .. H].
+        A level of more than `capacity` nodes stops the search: status = count << 3 | (level + 1) and flat index -1 (scan_search_status
+        names it).  About 5 H + 4 launches, enqueued at once; nothing read back."""
+        pts = self._points(points, "ScanMatcher.search")
+        if poses12 is None:
+            poses12 = self.poses(_host_rows(pose, 3, "pose", rows=1), rotations)
+        else:
+            poses12 = self._poses12(poses12, "ScanMatcher.search")
+        K = poses12.shape[0]
+        (wx, wy, wz), H, capacity, _ = check_scan_search(self.map, window, levels, capacity, K)
+        lv = self.levels(H)
+        record = torch.empty(SCAN_SEARCH_RECORD, dtype=torch.int64, device=self.device)
+        work = self._workspace(capacity)
+        self._call("tohip_reloc_search", ptr(self.table), self.table.numel(), ptr(lv) if H > 0 else ptr(None), lv.numel(), ctypes.byref(self.geom),
+                   self.unknown_value, H, ptr(pts), pts.shape[0], ptr(poses12), K, wx, wy, wz, capacity, ptr(record), ptr(work), work.numel())
+        return record
+
+
+SCAN_SEARCH_MAX_WINDOW = (2048, 2048, 4)
+SCAN_SEARCH_MAX_LEVELS = 6
+SCAN_SEARCH_MAX_CAPACITY = 1 << 24
+SCAN_SEARCH_RECORD = 18
+
+
+def scan_search_levels(window):
+    """The default number of levels of a search: the smallest H <= 6 with ceil((2wx+1) / 2^H) ceil((2wy+1) / 2^H) <= 256."""
+    wx, wy = int(window[0]), int(window[1])
+    for H in range(SCAN_SEARCH_MAX_LEVELS + 1):
+        if -(-(2 * wx + 1) // (1 << H)) * -(-(2 * wy + 1) // (1 << H)) <= 256:
+            return H
+    return SCAN_SEARCH_MAX_LEVELS
+
+
+def scan_search_window(voxel, dims):
+    """The window centred on the prior's voxel, clamped into dims, that reaches every voxel of dims: wx = max(i_x, nx - 1 - i_x), wy
+    likewise, wz = 0."""
+    i = [min(max(int(v), 0), int(d) - 1) for v, d in zip(voxel, dims)]
+    return (max(i[0], int(dims[0]) - 1 - i[0]), max(i[1], int(dims[1]) - 1 - i[1]), 0)
+
+
+def scan_search_status(status):
+    """A record's status word -> None where the search ran to its end, else (level, count): the level that would have held `count`
+    nodes, more than the capacity."""
+    status = int(status)
+    return None if status == 0 else ((status & 7) - 1, status >> 3)
+
+
+def check_scan_search(map, window=None, levels=None, capacity=None, n_rotations=None):
+    """A wide-window search's settings, by name; needs no GPU.  map: an ops.EvidenceMap; window (None: not asked): three integers (wx,
+    wy, wz), 0 <= wx, wy <= 2048, 0 <= wz <= 4; levels: None (with a window: scan_search_levels(window)) or an integer in [0, 6];
+    capacity (None: not asked): an integer in [1, 2^24], the nodes a level may hold; n_rotations (None: not asked): an integer in
+    [1, 256].  -> (window, levels, capacity, n_rotations); ValueError otherwise."""
+    if not isinstance(map, EvidenceMap):
+        raise ValueError(f"ScanMatcher: the map must be an ops.EvidenceMap (EvidenceMap.from_space takes a SpaceMap), got {type(map).__name__}")
+    if window is not None:
+        try:
+            w = tuple(window)
+        except TypeError:
+            w = ()
+        if len(w) != 3 or not all(_is_int(c) and 0 <= c <= m for c, m in zip(w, SCAN_SEARCH_MAX_WINDOW)):
+            raise ValueError(f"window must be three integers (wx, wy, wz) with 0 <= wx, wy <= 2048 and 0 <= wz <= 4, got {window!r}")
+        window = tuple(int(c) for c in w)
+    if levels is None:
+        levels = scan_search_levels(window) if window is not None else None
+    elif not _is_int(levels) or not 0 <= levels <= SCAN_SEARCH_MAX_LEVELS:
+        raise ValueError(f"levels must be None or an integer in [0, {SCAN_SEARCH_MAX_LEVELS}], got {levels!r}")
+    if capacity is not None and (not _is_int(capacity) or not 1 <= capacity <= SCAN_SEARCH_MAX_CAPACITY):
+        raise ValueError(f"capacity must be an integer in [1, 2^24] nodes a level, got {capacity!r}")
+    if n_rotations is not None and (not _is_int(n_rotations) or not 1 <= n_rotations <= SCAN_MAX_ROTATIONS):
+        raise ValueError(f"the rotations must number 1 .. {SCAN_MAX_ROTATIONS}, got K = {n_rotations!r}")
+    return window, (None if levels is None else int(levels)), (None if capacity is None else int(capacity)), n_rotations
 
 
 XFER_MAX_SHIFT = 4096      # of a voxel shift per axis (tohip_occ_transfer / tohip_evid_transfer)

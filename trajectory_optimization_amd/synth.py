@@ -1958,3 +1958,213 @@ def scan_best_ref(scores):
     i = int(cand[np.argmin(d2[cand])])   # (argmin: the first of equals, the lower index)
     return np.array([i, i // (nzw * nyw * nxw), dx.reshape(-1)[i % dx.size], dy.reshape(-1)[i % dx.size], dz.reshape(-1)[i % dx.size], top,
                      len(cand), 0], dtype=np.int32)
+
+
+# ---- relocalisation restated in numpy ("Relocalisation"): what scansearch_kernels.hip must give, bit for bit ----------
+RELOC_MAX_LEVELS = 6
+RELOC_MAX_WINDOW = (2048, 2048, 4)
+RELOC_MAX_CAPACITY = 1 << 24
+RELOC_RECORD = 11 + RELOC_MAX_LEVELS + 1   # int64 words: flat, k, dx, dy, dz, score, ties, status, incumbent, evaluated, H, nodes[0 .. 6]
+RELOC_NO_INCUMBENT = -(1 << 31)            # the incumbent before the first descent (all there is with H = 0)
+
+
+def scan_levels_ref(L, H, floor=None, unknown_value=0):
+    """The level tables of the log-odds L (nx,ny,nz) as dense volumes -> [T_0, ..., T_H], each (nx,ny,nz) int64 of bytes: T_0 = 128 +
+    value; T_h(x, y, z) = max over 0 <= i, j < 2^h of T_0'(x + i, y + j, z), T_0' being T_0 continued by 128 + unknown_value outside
+    dims — built as the four-way maximum of T_{h-1} at stride 2^(h-1)."""
+    if not 0 <= int(H) <= RELOC_MAX_LEVELS:
+        raise ValueError(f"levels must lie in [0, {RELOC_MAX_LEVELS}], got {H!r}")
+    T = [scan_values_ref(L, floor, unknown_value) + 128]
+    nx, ny, nz = T[0].shape
+    u = 128 + int(unknown_value)
+    for h in range(1, int(H) + 1):
+        s = 1 << (h - 1)
+        pad = np.full((nx + s, ny + s, nz), u, dtype=np.int64)
+        pad[:nx, :ny] = T[-1]
+        T.append(np.maximum(np.maximum(pad[:nx, :ny], pad[s:, :ny]), np.maximum(pad[:nx, s:], pad[s:, s:])))
+    return T
+
+
+def scan_level_bytes_ref(T, unknown_value=0):
+    """The byte image of one level table T (nx,ny,nz) of bytes -> (256 + 32 words,) uint8: a zero header, then brick order with 128 +
+    unknown_value in the pad voxels."""
+    T = np.asarray(T, dtype=np.int64)
+    nx, ny, nz = T.shape
+    nbx, nby, nbz = _evidence_bricks(T.shape)
+    pad = np.full((4 * nbx, 4 * nby, 2 * nbz), 128 + int(unknown_value), dtype=np.int64)
+    pad[:nx, :ny, :nz] = T
+    img = pad.reshape(nbx, 4, nby, 4, nbz, 2).transpose(4, 2, 0, 5, 3, 1).reshape(-1)
+    return np.concatenate([np.zeros(EVID_HEADER, dtype=np.uint8), img.astype(np.uint8)])
+
+
+def scan_lookup_ref(Th, h, u, X, Y, Z):
+    """B_h at integer arrays X, Y, Z (any shape): u where Z is outside [0, nz) or X outside [-(2^h - 1), nx) or Y outside [-(2^h - 1),
+    ny); otherwise Th[max(X, 0), max(Y, 0), Z], raised to u where X < 0 or Y < 0."""
+    nx, ny, nz = Th.shape
+    b = (1 << h) - 1
+    ins = (Z >= 0) & (Z < nz) & (X >= -b) & (X < nx) & (Y >= -b) & (Y < ny)
+    c = Th[np.clip(X, 0, nx - 1), np.clip(Y, 0, ny - 1), np.clip(Z, 0, nz - 1)]
+    c = np.where((X < 0) | (Y < 0), np.maximum(c, u), c)
+    return np.where(ins, c, u)
+
+
+def _reloc_bounds(Th, h, u, voxels, nodes, cells=1 << 22):
+    """The bounds of nodes (M,4) int64 (k, sx, sy, sz) at level h; voxels[k]: the (n_k,3) voxels in range under rotation k.  A node whose
+    k names no rotation gets RELOC_NO_INCUMBENT."""
+    nodes = np.asarray(nodes, dtype=np.int64).reshape(-1, 4)
+    out = np.full(len(nodes), RELOC_NO_INCUMBENT, dtype=np.int64)
+    for k in np.unique(nodes[:, 0]):
+        if not 0 <= k < len(voxels):
+            continue
+        rows = np.flatnonzero(nodes[:, 0] == k)
+        v = voxels[k]
+        if len(v) == 0:
+            out[rows] = 0
+            continue
+        step = max(1, cells // len(v))
+        for i in range(0, len(rows), step):
+            r = rows[i:i + step]
+            s = nodes[r, 1:]
+            vals = scan_lookup_ref(Th, h, u, v[None, :, 0] + s[:, None, 0], v[None, :, 1] + s[:, None, 1], v[None, :, 2] + s[:, None, 2])
+            out[r] = vals.sum(axis=1) - 128 * len(v)
+    return out
+
+
+def _reloc_voxels(points, Rs, t, origin, resolution):
+    Rs = np.asarray(Rs, dtype=np.float32).reshape(-1, 3, 3)
+    vox = []
+    for R in Rs:
+        v, ok = scan_voxels_ref(points, R, t, origin, resolution)
+        vox.append(v[ok])
+    return vox
+
+
+def scan_bound_ref(L, origin, resolution, points, Rs, t, nodes, level, floor=None, unknown_value=0):
+    """Explicit nodes (M,4) integers (k, sx, sy, sz) of one level -> (bounds (M,) int32, used (K,) int32): the bound of a node is the sum
+    over the points in range under rotation k of B_level(voxel_k(p) + (sx, sy, sz)), less 128 x their number."""
+    T = scan_levels_ref(L, level, floor, unknown_value)[int(level)]
+    vox = _reloc_voxels(points, Rs, t, origin, resolution)
+    b = _reloc_bounds(T, int(level), 128 + int(unknown_value), vox, nodes)
+    return b.astype(np.int32), np.asarray([len(v) for v in vox], dtype=np.int32)
+
+
+def _reloc_order(nodes, bounds):
+    """The index of the best node: the largest bound, then the lowest (k, sz, sy, sx)."""
+    top = np.flatnonzero(bounds == bounds.max())
+    n = nodes[top]
+    return int(top[np.lexsort((n[:, 1], n[:, 2], n[:, 3], n[:, 0]))[0]])
+
+
+def _reloc_children(nodes, half, wx, wy):
+    kids = []
+    for j in range(4):
+        c = nodes.copy()
+        c[:, 1] += (j & 1) * half
+        c[:, 2] += (j >> 1) * half
+        kids.append(c[(c[:, 1] <= wx) & (c[:, 2] <= wy)])
+    return np.concatenate(kids, axis=0)
+
+
+def scan_search_ref(L, origin, resolution, points, Rs, t, window, levels, floor=None, unknown_value=0, capacity=1 << 22):
+    """The branch-and-bound search as DESIGN.md 10 "Relocalisation" defines it -> the record, (18,) int64: flat index, k, dx, dy, dz,
+    score, ties, status, incumbent, evaluated, H, nodes[0 .. H] (the rest 0).  The top level holds every node with sx in {-wx, -wx +
+    2^H, ...} <= wx, sy likewise, every sz and every rotation; for h = H .. 1: the node with the largest bound (then the lowest (k, sz,
+    sy, sx)) is followed greedily to a leaf, the incumbent becomes max(incumbent, the leaf's score), every node whose bound is below
+    the incumbent is dropped, the rest are replaced by their children; at level 0 the maximum of the key (score, smaller |s|^2, lower
+    flat index) and the number of survivors with the best score.  A level of more than `capacity` nodes stops the search: status =
+    count << 3 | (level + 1), flat index -1, nodes[level] = count."""
+    wx, wy, wz = (int(c) for c in window)
+    H = int(levels)
+    if not (0 <= wx <= RELOC_MAX_WINDOW[0] and 0 <= wy <= RELOC_MAX_WINDOW[1] and 0 <= wz <= RELOC_MAX_WINDOW[2]):
+        raise ValueError(f"window must lie in [0, {RELOC_MAX_WINDOW}] per axis, got {tuple(window)!r}")
+    T = scan_levels_ref(L, H, floor, unknown_value)
+    u = 128 + int(unknown_value)
+    vox = _reloc_voxels(points, Rs, t, origin, resolution)
+    K = len(vox)
+    rec = np.zeros(RELOC_RECORD, dtype=np.int64)
+    rec[8], rec[10] = RELOC_NO_INCUMBENT, H
+    step = 1 << H
+    k, sz, sy, sx = np.meshgrid(np.arange(K), np.arange(-wz, wz + 1), np.arange(-wy, wy + 1, step), np.arange(-wx, wx + 1, step), indexing="ij")
+    nodes = np.stack([k.reshape(-1), sx.reshape(-1), sy.reshape(-1), sz.reshape(-1)], axis=1).astype(np.int64)
+
+    def overflow(level, count):
+        rec[0], rec[7], rec[11 + level] = -1, (count << 3) | (level + 1), count
+        return rec
+
+    if len(nodes) > capacity:
+        return overflow(H, len(nodes))
+    bounds = _reloc_bounds(T[H], H, u, vox, nodes)
+    rec[9] = len(nodes)
+    for h in range(H, 0, -1):
+        rec[11 + h] = len(nodes)
+        at = nodes[_reloc_order(nodes, bounds)][None, :]
+        for lev in range(h - 1, -1, -1):
+            kids = _reloc_children(at, 1 << lev, wx, wy)
+            kb = _reloc_bounds(T[lev], lev, u, vox, kids)
+            rec[9] += len(kids)
+            i = _reloc_order(kids, kb)
+            at, leaf = kids[i][None, :], int(kb[i])
+        rec[8] = max(int(rec[8]), leaf)
+        nodes = _reloc_children(nodes[bounds >= rec[8]], 1 << (h - 1), wx, wy)
+        if len(nodes) > capacity:
+            return overflow(h - 1, len(nodes))
+        bounds = _reloc_bounds(T[h - 1], h - 1, u, vox, nodes)
+        rec[9] += len(nodes)
+    rec[11] = len(nodes)
+    nxw, nyw, nzw = 2 * wx + 1, 2 * wy + 1, 2 * wz + 1
+    top = np.flatnonzero(bounds == bounds.max())
+    n = nodes[top]
+    flat = ((n[:, 0] * nzw + n[:, 3] + wz) * nyw + n[:, 2] + wy) * nxw + n[:, 1] + wx
+    d2 = (n[:, 1:] ** 2).sum(axis=1)
+    i = np.lexsort((flat, d2))[0]
+    rec[:8] = (flat[i], n[i, 0], n[i, 1], n[i, 2], n[i, 3], bounds.max(), len(top), 0)
+    return rec
+
+
+def scan_exhaustive_ref(L, origin, resolution, points, Rs, t, window, floor=None, unknown_value=0):
+    """The exhaustive answer over a window of any size -> (7,) int64: flat index, k, dx, dy, dz, score, ties under scan matching's key.
+    Per rotation the points in range are grouped by voxel, and each distinct voxel adds its count times the slice of the value volume
+    its window covers (unknown_value outside dims) to the window's scores."""
+    wx, wy, wz = (int(c) for c in window)
+    V = scan_values_ref(L, floor, unknown_value)
+    nx, ny, nz = V.shape
+    un = int(unknown_value)
+    vox = _reloc_voxels(points, Rs, t, origin, resolution)
+    scores = np.zeros((len(vox), 2 * wz + 1, 2 * wy + 1, 2 * wx + 1), dtype=np.int64)
+    for k, v in enumerate(vox):
+        acc = np.full((2 * wx + 1, 2 * wy + 1, 2 * wz + 1), un * len(v), dtype=np.int64)
+        if len(v):
+            uniq, cnt = np.unique(v, axis=0, return_counts=True)
+            for (x, y, z), c in zip(uniq, cnt):
+                lo = np.maximum([x - wx, y - wy, z - wz], 0)
+                hi = np.minimum([x + wx + 1, y + wy + 1, z + wz + 1], [nx, ny, nz])
+                if (lo >= hi).any():
+                    continue
+                a = lo - np.asarray([x - wx, y - wy, z - wz])
+                e = a + (hi - lo)
+                acc[a[0]:e[0], a[1]:e[1], a[2]:e[2]] += int(c) * (V[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]] - un)
+        scores[k] = acc.transpose(2, 1, 0)
+    flat = scores.reshape(-1)
+    top = np.flatnonzero(flat == flat.max())
+    S = scores[0].size
+    s = top % S
+    dz, rem = s // ((2 * wy + 1) * (2 * wx + 1)) - wz, s % ((2 * wy + 1) * (2 * wx + 1))
+    dy, dx = rem // (2 * wx + 1) - wy, rem % (2 * wx + 1) - wx
+    i = np.lexsort((top, dx * dx + dy * dy + dz * dz))[0]
+    return np.asarray([top[i], top[i] // S, dx[i], dy[i], dz[i], flat.max(), len(top)], dtype=np.int64)
+
+
+def reloc_default_levels(window):
+    """The smallest H <= 6 with ceil((2wx+1) / 2^H) ceil((2wy+1) / 2^H) <= 256 (6 where none is)."""
+    wx, wy = int(window[0]), int(window[1])
+    for H in range(RELOC_MAX_LEVELS + 1):
+        if -(-(2 * wx + 1) // (1 << H)) * -(-(2 * wy + 1) // (1 << H)) <= 256:
+            return H
+    return RELOC_MAX_LEVELS
+
+
+def reloc_full_window(voxel, dims):
+    """The window centred on the prior's voxel (clamped into dims) that reaches every voxel of dims: wx = max(i_x, nx - 1 - i_x), wy
+    likewise, wz = 0."""
+    i = [min(max(int(v), 0), int(d) - 1) for v, d in zip(voxel, dims)]
+    return (max(i[0], int(dims[0]) - 1 - i[0]), max(i[1], int(dims[1]) - 1 - i[1]), 0)

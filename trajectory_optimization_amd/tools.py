@@ -441,6 +441,71 @@ def match_scan(map_or_matcher, points, pose, quat, window=(8, 8, 2), yaw=None, r
                      ties=ties, scores=scores, pose_refined=refined)
 
 
+def relocalise_scan(map_or_matcher, points, pose, quat, window=None, yaw=None, rotations=None, levels=None, floor=None, unknown_value=0,
+                    refine=True, capacity=1 << 22):
+    """Where in this map am I?  match_scan's question over a WIDE window ("Relocalisation"): the exact best candidate of
+    |dx| <= wx, |dy| <= wy (up to 2048 voxels each), |dz| <= wz <= 4 and the caller's rotations, found by branch and bound over
+    sliding-maximum copies of the score table instead of scoring every candidate — the same winner, tie rule and `ties` as the
+    exhaustive search, bit for bit.  window=None: centred on the prior, reaching every voxel of dims in x and y (wz = 0).  levels: None
+    (the smallest H <= 6 that leaves at most 256 top-level blocks a rotation and z shift) or H in [0, 6].  yaw, rotations, floor,
+    unknown_value, refine and map_or_matcher as match_scan takes them.  -> ScanMatch with, beyond match_scan's fields, levels,
+    nodes (the nodes of each level 0 .. H before the drop), evaluated (all bounds computed), candidates (K S) and incumbent; scores
+    is the (3,3,3) int32 score neighbourhood [dz][dy][dx] of the winner, which the parabola is fitted through.  A level of more
+    than `capacity` nodes raises RuntimeError.  On a map with little structure nothing is pruned and the search costs more than
+    scoring every candidate.  WHEN TO CALL WHICH (measured, DESIGN.md 10 "Relocalisation": a 405 x 405 x 45 room, 100 k points, 41 headings): at
+    window (10, 10, 2) this search and match_scan cost the same, 3.1 against 3.2 ms; at (64, 64, 1) it takes 3.3 ms where scoring
+    every candidate takes 475 ms.  So inside match_scan's reach (16, 16, 4) match_scan remains the right call — it also returns the
+    whole score volume — and every window beyond it is this function's.  One read-back; before it one
+    copy of the K poses to the device, which waits for the current stream."""
+    matcher = _scan_matcher("relocalise_scan", map_or_matcher, floor, unknown_value)
+    prior = ops._host_rows(quat, 4, "quat", rows=1)
+    if yaw is not None and rotations is not None:
+        raise ValueError("relocalise_scan: give yaw or rotations, not both")
+    if yaw is not None:
+        try:
+            half_range, n = yaw
+        except (TypeError, ValueError):
+            raise ValueError(f"relocalise_scan: yaw must be (half_range_rad, n), got {yaw!r}") from None
+        quats = yaw_candidates(prior, half_range, n)
+    else:
+        quats = ops._host_rows(prior if rotations is None else rotations, 4, "rotations")
+    t = ops._host_rows(pose, 3, "pose", rows=1)
+    if window is None:
+        g = (t[0].astype(np.float32) - np.asarray(matcher.origin, dtype=np.float32)) / np.float32(matcher.resolution)   # (the map's rule, in f32)
+        voxel = np.floor(np.clip(g, -2048.0, 4095.0)).astype(np.int64)
+        window = ops.scan_search_window(voxel, matcher.dims)
+    poses12 = matcher.poses(t, quats)
+    record = matcher.search(points, t, quats, window, levels=levels, capacity=capacity, poses12=poses12)
+    k = record[1:2].clamp(0, len(quats) - 1)
+    shift = record[2:5].to(torch.int32)
+    counters = matcher.score(points, None, None, shifts=shift.reshape(1, 3), poses12=poses12.index_select(0, k))
+    i = torch.arange(27, dtype=torch.int32, device=matcher.device)   # the winner's 3 x 3 x 3 neighbourhood, built on the device
+    offs = torch.stack([torch.zeros_like(i), i % 3 - 1, torch.div(i, 3, rounding_mode="floor") % 3 - 1, torch.div(i, 9, rounding_mode="floor") - 1], dim=1)
+    nodes = torch.cat([k.to(torch.int32), shift]).reshape(1, 4) + offs
+    around, used = matcher.bound(points, nodes, 0, poses12=poses12)
+    host = torch.cat([record, torch.cat(counters).long(), used.index_select(0, k).long(), around.long()]).cpu().numpy()   # the one read-back
+    rec = host[:ops.SCAN_SEARCH_RECORD]
+    H = int(rec[10])
+    wx, wy, wz = (int(c) for c in window)
+    stopped = ops.scan_search_status(rec[7])
+    if stopped is not None:
+        raise RuntimeError(f"relocalise_scan: level {stopped[0]} of the search would hold {stopped[1]} nodes, more than the capacity of "
+                           f"{capacity}: give a narrower window, more levels (levels={H} now), fewer rotations or a larger capacity")
+    flat, kk, dx, dy, dz, score, ties = (int(v) for v in rec[:7])
+    if int(host[ops.SCAN_SEARCH_RECORD]) != score:
+        raise RuntimeError(f"relocalise_scan: the search's best score {score} and the winner's own {int(host[ops.SCAN_SEARCH_RECORD])} differ: "
+                           "the matcher's table is stale — refresh() it after the map took a scan")
+    r = np.float32(matcher.resolution)
+    found = (t[0].astype(np.float32) + (np.asarray((dx, dy, dz), dtype=np.float32) * r).astype(np.float32)).astype(np.float32)
+    refined = found.astype(np.float64)
+    if refine:
+        refined = refined + scan_refine(host[-27:].reshape(3, 3, 3), (1, 1, 1)) * float(r)
+    return ScanMatch(pose=found, quat=quats[kk].copy(), shift=(dx, dy, dz), rotation=kk, score=score, used=int(host[ops.SCAN_SEARCH_RECORD + 4]),
+                     known=int(host[ops.SCAN_SEARCH_RECORD + 3]), ties=ties, scores=around.reshape(3, 3, 3), pose_refined=refined, levels=H,
+                     nodes=tuple(int(v) for v in rec[11:12 + H]), evaluated=int(rec[9]), candidates=len(quats) * (2 * wx + 1) * (2 * wy + 1) * (2 * wz + 1),
+                     incumbent=int(rec[8]))
+
+
 def score_scans(map_or_matcher, points, poses, quats, shifts=None, floor=None, unknown_value=0):
     """How well does the scan fit the map at each of these poses?  B explicit candidates — poses (B,3), quats (B,4) wxyz, shifts None
     or (B,3) voxels — -> (score, used, inside, known), each (B,) int32 on the device (ops.ScanMatcher.score): the weights a particle
@@ -554,8 +619,11 @@ class ScanMatch(_Result):
     dy, dz) in voxels and rotation, its row of the list; score; used (the points in range under that rotation), known (those that met
     an observed voxel), ties (the candidates that share the best score: 1 for a unique answer); scores (K, 2wz+1, 2wy+1, 2wx+1) int32
     on the device; pose_refined (3,) f64, the pose moved by the parabola's sub-voxel offset (equal to pose with refine=False);
-    world(points) takes sensor-frame points to the world at the matched pose."""
-    __slots__ = ("pose", "quat", "shift", "rotation", "score", "used", "known", "ties", "scores", "pose_refined")
+    world(points) takes sensor-frame points to the world at the matched pose.  From relocalise_scan: scores is the (3,3,3) score
+    neighbourhood [dz][dy][dx] of the winner, and levels (H), nodes (the nodes of each level 0 .. H before the drop), evaluated (all
+    bounds computed), candidates (K S, what an exhaustive search would score) and incumbent are set as well."""
+    __slots__ = ("pose", "quat", "shift", "rotation", "score", "used", "known", "ties", "scores", "pose_refined", "levels", "nodes", "evaluated",
+                 "candidates", "incumbent")
 
     def world(self, points, refined=False):
         """(N,3) sensor-frame points on a device -> (N,3) f32 world points at the matched (or refined) pose: torch ops, rounded as torch
