@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_reloc_levels / tohip_reloc_bounds / tohip_reloc_workspace_bytes / tohip_reloc_search (relocalisation: exact
+/* (still 15) + tohip_scanreg_normal / tohip_scanreg_step and TOHIP_SCANREG_RECORD / TOHIP_SCANREG_STATE (fine scan registration: integer
+ * normal equations of a scan on the trilinear score table, and a damped Gauss-Newton step per pose): new symbols only.
+ * (still 15) + tohip_reloc_levels / tohip_reloc_bounds / tohip_reloc_workspace_bytes / tohip_reloc_search (relocalisation: exact
  * branch-and-bound scan matching over wide windows, on sliding-maximum copies of the score table): new symbols only.
  * (still 15) + tohip_scan_prepare / tohip_scan_score / tohip_scan_correlate / tohip_scan_best (scan-to-map registration: a scan scored
  * against the evidence map at every pose of a search window, and the best of them): new symbols only.
@@ -1624,6 +1626,42 @@ int tohip_reloc_search(const void *table, size_t table_bytes, const void *levels
                        int32_t unknown_value, int32_t h, const float *points, int64_t n, const float *poses, int64_t k, int32_t wx,
                        int32_t wy, int32_t wz, int64_t capacity, int64_t *record, void *workspace, size_t workspace_bytes, void *stream,
                        uint32_t flags);
+
+/* ---- scan registration (scanreg_kernels.hip, DESIGN.md §10, "Scan registration") ----------------------
+ * Sub-voxel refinement of B poses (1 <= b <= 256) of one scan by damped Gauss-Newton steps on the trilinear interpolation of the
+ * score table.  Poses, points, the transform rule, the skip rule and the table are scan matching's.  All per-point terms are integers
+ * on the map's 1/256-voxel fixed point q = the coordinate rule of tohip_occ_insert:
+ *   c = q - 128, base voxel c >> 8, fraction f = c & 255, weights 256 - f and f per axis; V[i][j][k] the table byte of the base voxel
+ *   + (i, j, k), 128 + unknown_value outside dims;  M24 = sum V wx wy wz;  Gx16 = sum_jk wy wz (V[1][j][k] - V[0][j][k]), Gy16 and Gz16
+ *   alike;  e = (255 2^24 - M24 + 2^11) >> 12;  g = (G16 + 2^7) >> 8;  a = (q - q_t + 32) >> 6 with q_t the fixed point of the pose's
+ *   own translation;  j = (a x g + 2^11) >> 12;  row J = (g, j): translation in 1/256 byte per voxel, rotation about the sensor's
+ *   position in the WORLD frame in 4 byte per radian, e in 1/4096 byte (the residual 255 - M).
+ * RECORD of a pose, TOHIP_SCANREG_RECORD int64: [0:21] the upper triangle of sum J J^T, row-major; [21:27] sum J e; [27] sum e^2; [28]
+ *   used, the points not skipped; [29] inside, those whose eight corners all lie inside dims; [30:32] 0.  Every sum stays below 2^62
+ *   for n <= 2^22.  A pose whose translation is out of range has an all-zero record.
+ * STATE of a pose, TOHIP_SCANREG_STATE 8-byte words, f64 unless named int64: [0:3] t in metres; [3:7] q wxyz, UNNORMALISED; [7] lambda;
+ *   [8:14] the last step (voxels x3, radians x3); [14] status int64 (0 running, 1 converged, 2 stalled, 3 degenerate, 4 empty: every
+ *   value but 0 is frozen); [15] iterations int64; [16] accepted steps int64; [17:20] trial t; [20:24] trial q; [24:56] the record at
+ *   [0:7], int64; [56:64] 0.  The caller writes the start: t, q, trial = them, lambda (2^-10), the rest 0, and `poses` = the trial's 12 f32.
+ * tohip_scanreg_normal: records (b, 32) int64 of the poses (b, 12) f32, zeroed here on the stream, then one launch.  state_or_null: the
+ *   blocks of a pose whose status is not 0 return at once (its record stays 0).  8-byte aligned records and state.
+ * tohip_scanreg_step: one step per pose from the records at the trial poses: a frozen pose is left alone; used = 0: empty; the trial
+ *   is accepted iff it is the first iteration or (used equals the current used and sum e^2 is smaller): current <- trial, from the
+ *   second iteration on lambda <- max(lambda / 8, 2^-30), and converged if the accepted step was within tol_t voxels and tol_r radians
+ *   on every axis; rejected: lambda <- 8 lambda, stalled if that exceeds 2^30.  Then A = S H S, rhs = S b / 4096, S = diag(1/256 x3,
+ *   4 x3), over the degrees of freedom of dof_mask (bit i of x y z roll pitch yaw; 1 .. 63), A_ii += lambda A_ii, LDL^T without
+ *   pivoting (a pivot <= 0 or not finite: degenerate), trial t = t + resolution delta_t, trial q = (1, delta_theta / 2) (x) q, and
+ *   poses[12 b ..] = the f32 roundings of R (from the unnormalised q, s = 2 / q.q) and the trial t.  f64 add, multiply, divide and
+ *   compare in one fixed order: the same bits in every run.  One launch.
+ * flags is reserved and must be 0.  A bad n, b, unknown_value, resolution, dof_mask, tolerance or flags, a null, misaligned or aliased
+ * buffer: TOHIP_EINVAL; a short table: TOHIP_ENOSPC.  Every argument check returns before anything is enqueued.  Nothing is read back. */
+#define TOHIP_SCANREG_RECORD 32
+#define TOHIP_SCANREG_STATE 64
+int tohip_scanreg_normal(const void *table, size_t table_bytes, const tohip_occ_geom *geom, int32_t unknown_value, const float *points,
+                         int64_t n, const float *poses, int64_t b, const int64_t *state_or_null, int64_t *records, void *stream,
+                         uint32_t flags);
+int tohip_scanreg_step(const int64_t *records, int64_t *state, int64_t b, float resolution, int32_t dof_mask, double tol_t, double tol_r,
+                       float *poses, void *stream, uint32_t flags);
 
 /* ---- optional per-kernel timing (bench.py's roofline leg) -----------------------------------------
  * When enabled, every launch of the big kernels is bracketed by hipEventRecord on its own stream.

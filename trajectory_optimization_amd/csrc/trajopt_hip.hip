@@ -21,6 +21,7 @@
 #include "field_kernels.hip"
 #include "evidence_kernels.hip"
 #include "scanmatch_kernels.hip"
+#include "scanreg_kernels.hip"
 #include "scansearch_kernels.hip"
 #include "reframe_kernels.hip"
 #include "travel_kernels.hip"

@@ -2356,6 +2356,143 @@ class ScanMatcher:
                    self.unknown_value, H, ptr(pts), pts.shape[0], ptr(poses12), K, wx, wy, wz, capacity, ptr(record), ptr(work), work.numel())
         return record
 
+    # ---- fine registration: damped Gauss-Newton on the trilinear table (scanreg_kernels.hip, DESIGN.md 10 "Scan registration")
+
+    def normal(self, points, poses=None, quats=None, poses12=None, state=None):
+        """The integer normal equations of B poses (1 <= B <= 256) -> records (B, 32) int64 on the device: per pose the upper triangle
+        of H = sum J J^T (21, row-major), sum J e (6), sum e^2, used, inside (all eight corners inside dims), 0, 0 — J and e of each
+        point by the definitions of DESIGN.md 10 "Scan registration", on the trilinear interpolation of the TABLE (refresh() after
+        an integrate).  A pose whose translation is out of range has an all-zero record.  poses (B,3) and quats (B,4) on the host, or
+        poses12, the (B,12) device tensor of poses().  state: a register() state; the poses it has frozen are not evaluated (their
+        records stay zero).  One clear and one launch, nothing read back."""
+        pts = self._points(points, "ScanMatcher.normal")
+        poses12 = self.poses(poses, quats) if poses12 is None else self._poses12(poses12, "ScanMatcher.normal")
+        B = poses12.shape[0]
+        check_scan_register(self.map, n_poses=B)
+        if state is not None:
+            state = self._state(state, B, "ScanMatcher.normal")
+        records = torch.empty((B, SCAN_REGISTER_RECORD), dtype=torch.int64, device=self.device)
+        self._call("tohip_scanreg_normal", ptr(self.table), self.table.numel(), ctypes.byref(self.geom), self.unknown_value, ptr(pts),
+                   pts.shape[0], ptr(poses12), B, ptr(state), ptr(records))
+        return records
+
+    def _state(self, state, B, what):
+        if (not torch.is_tensor(state) or state.dtype != torch.int64 or tuple(state.shape) != (B, SCAN_REGISTER_STATE) or state.device != self.device
+                or not state.is_contiguous()):
+            raise ValueError(f"{what}: state must be a contiguous ({B},{SCAN_REGISTER_STATE}) int64 tensor on {self.device} (scan_register_start), got "
+                             f"{(tuple(state.shape), state.dtype, str(state.device)) if torch.is_tensor(state) else type(state).__name__}")
+        return state
+
+    def step(self, records, state, poses12, dof="xyzrpw", tol_t=None, tol_r=None):
+        """One Gauss-Newton step of every pose, in place: records (B,32) int64 at the trial poses, state (B,64) int64 and poses12
+        (B,12) f32, which receives the next trial poses.  What register() calls after each normal(); one launch, nothing read back."""
+        B = state.shape[0] if torch.is_tensor(state) and state.dim() == 2 else 0
+        _, mask, tol_t, tol_r = check_scan_register(self.map, None, dof, tol_t, tol_r, B)
+        state, poses12 = self._state(state, B, "ScanMatcher.step"), self._poses12(poses12, "ScanMatcher.step")
+        if (not torch.is_tensor(records) or records.dtype != torch.int64 or tuple(records.shape) != (B, SCAN_REGISTER_RECORD)
+                or records.device != self.device or not records.is_contiguous() or poses12.shape[0] != B):
+            raise ValueError(f"ScanMatcher.step: records must be the contiguous ({B},{SCAN_REGISTER_RECORD}) int64 tensor normal() returned and "
+                             f"poses12 ({B},12)")
+        self._call("tohip_scanreg_step", ptr(records), ptr(state), B, float(np.float32(self.resolution)), mask, tol_t, tol_r, ptr(poses12))
+        return state
+
+    def register(self, points, poses=None, quats=None, iterations=30, dof="xyzrpw", tol_t=None, tol_r=None, state=None, poses12=None):
+        """Refine B poses (1 <= B <= 256) of one scan: `iterations` (1 .. 256) rounds of normal() and step() — Levenberg-Marquardt on
+        the integer normal equations, each pose with its own lambda, frozen once it has converged, stalled, met a degenerate system
+        or lost every point.  -> the device state (B, 64) int64 (f64 words by their bits; scan_register_fields names them).  dof: a
+        string over 'x y z r p w' (translation, roll, pitch, yaw about the world's axes) or a 6-bit mask; tol_t in voxels (None:
+        1/256), tol_r in radians (None: 1e-4).  The start: poses (B,3) and quats (B,4) on the host — one copy to the device, which
+        waits for the current stream — or state and poses12, the device tensors of scan_register_start (they are not modified).  Every
+        pose of a batch is bitwise its own single run.  The table is read, not the map: refresh() after an integrate.  Per iteration
+        one clear and two launches, all enqueued at once; nothing is read back."""
+        pts = self._points(points, "ScanMatcher.register")
+        if state is None:
+            R = scan_rotations(quats, "quats")
+            t = _host_rows(poses, 3, "poses")
+            if t.shape[0] == 1 and R.shape[0] > 1:
+                t = np.repeat(t, R.shape[0], axis=0)
+            if t.shape[0] != R.shape[0]:
+                raise ValueError(f"poses and quats must have as many rows, got {t.shape[0]} and {R.shape[0]}")
+            iterations, mask, tol_t, tol_r = check_scan_register(self.map, iterations, dof, tol_t, tol_r, t.shape[0])
+            st, p12 = scan_register_start(t, _host_rows(quats, 4, "quats"))
+            state, poses12 = torch.from_numpy(st).to(self.device), torch.from_numpy(p12).to(self.device)
+        else:
+            B = state.shape[0] if torch.is_tensor(state) and state.dim() == 2 else 0
+            iterations, mask, tol_t, tol_r = check_scan_register(self.map, iterations, dof, tol_t, tol_r, B)
+            state = self._state(state, B, "ScanMatcher.register").clone()
+            poses12 = self._poses12(poses12, "ScanMatcher.register").clone()
+            if poses12.shape[0] != B:
+                raise ValueError(f"ScanMatcher.register: state and poses12 must have as many rows, got {B} and {poses12.shape[0]}")
+        B = state.shape[0]
+        records = torch.empty((B, SCAN_REGISTER_RECORD), dtype=torch.int64, device=self.device)
+        r = float(np.float32(self.resolution))
+        for _ in range(iterations):
+            self._call("tohip_scanreg_normal", ptr(self.table), self.table.numel(), ctypes.byref(self.geom), self.unknown_value, ptr(pts),
+                       pts.shape[0], ptr(poses12), B, ptr(state), ptr(records))
+            self._call("tohip_scanreg_step", ptr(records), ptr(state), B, r, mask, tol_t, tol_r, ptr(poses12))
+        return state
+
+
+SCAN_REGISTER_RECORD = _lib.CONSTANTS["TOHIP_SCANREG_RECORD"]   # int64 words of a pose's record
+SCAN_REGISTER_STATE = _lib.CONSTANTS["TOHIP_SCANREG_STATE"]     # 8-byte words of a pose's state
+SCAN_REGISTER_MAX_ITERATIONS = 256
+SCAN_REGISTER_LAMBDA0 = 2.0 ** -10
+SCAN_REGISTER_TOL_T, SCAN_REGISTER_TOL_R = 1.0 / 256.0, 1.0e-4   # voxels, radians
+SCAN_REGISTER_STATUS = ("RUNNING", "CONVERGED", "STALLED", "DEGENERATE", "EMPTY")
+SCAN_REGISTER_DOF = "xyzrpw"
+# the state's words: t (3), q (4), lambda, the last step (6), status, iterations, accepted, trial t (3), trial q (4), the record (32)
+SCAN_REGISTER_FIELDS = dict(t=0, q=3, lam=7, delta=8, status=14, iterations=15, accepted=16, trial_t=17, trial_q=20, record=24)
+
+
+def scan_dof_mask(dof):
+    """A string over 'x y z r p w' (each at most once, one at least) or a mask in [1, 63] -> the 6-bit mask: bit i frees degree of
+    freedom i of (x, y, z, roll, pitch, yaw)."""
+    if isinstance(dof, str):
+        if not dof or len(set(dof)) != len(dof) or any(c not in SCAN_REGISTER_DOF for c in dof):
+            raise ValueError(f"dof must name each of 'x y z r p w' at most once and one at least, got {dof!r}")
+        return sum(1 << SCAN_REGISTER_DOF.index(c) for c in dof)
+    if _is_int(dof) and 1 <= dof <= 63:
+        return int(dof)
+    raise ValueError(f"dof must be a string over 'xyzrpw' or a mask in [1, 63], got {dof!r}")
+
+
+def check_scan_register(map, iterations=None, dof="xyzrpw", tol_t=None, tol_r=None, n_poses=None):
+    """A registration's settings, by name; needs no GPU.  map: an ops.EvidenceMap; iterations (None: not asked): an integer in [1,
+    256]; dof: scan_dof_mask's; tol_t (None: 1/256) in voxels and tol_r (None: 1e-4) in radians: finite and >= 0; n_poses (None: not
+    asked): an integer in [1, 256].  -> (iterations, mask, tol_t, tol_r); ValueError otherwise."""
+    if not isinstance(map, EvidenceMap):
+        raise ValueError(f"ScanMatcher: the map must be an ops.EvidenceMap (EvidenceMap.from_space takes a SpaceMap), got {type(map).__name__}")
+    if iterations is not None and (not _is_int(iterations) or not 1 <= iterations <= SCAN_REGISTER_MAX_ITERATIONS):
+        raise ValueError(f"iterations must be an integer in [1, {SCAN_REGISTER_MAX_ITERATIONS}], got {iterations!r}")
+    mask = scan_dof_mask(dof)
+    tols = []
+    for name, v, default in (("tol_t", tol_t, SCAN_REGISTER_TOL_T), ("tol_r", tol_r, SCAN_REGISTER_TOL_R)):
+        f = default if v is None else _float_or_nan(v)
+        if not (np.isfinite(f) and f >= 0.0):
+            raise ValueError(f"{name} must be None or a finite number >= 0, got {v!r}")
+        tols.append(f)
+    if n_poses is not None and (not _is_int(n_poses) or not 1 <= n_poses <= SCAN_MAX_ROTATIONS):
+        raise ValueError(f"the poses must number 1 .. {SCAN_MAX_ROTATIONS}, got {n_poses!r}")
+    return (None if iterations is None else int(iterations)), mask, tols[0], tols[1]
+
+
+def scan_register_start(poses, quats):
+    """The start of a registration on the host: poses (B,3) and quats (B,4) f64 -> (state (B,64) int64, poses12 (B,12) f32): current
+    and trial pose = the start (the quaternion as given, not normalised), lambda = 2^-10, the rest 0; poses12: R of the quaternion with
+    s = 2 / (q . q), in the step kernel's operation order, and t, each rounded once to f32 (synth.scan_register_init_ref)."""
+    t, q = np.asarray(poses, dtype=np.float64).reshape(-1, 3), np.asarray(quats, dtype=np.float64).reshape(-1, 4)
+    F = SCAN_REGISTER_FIELDS
+    st = np.zeros((len(t), SCAN_REGISTER_STATE), dtype=np.float64)
+    st[:, F["t"]:F["t"] + 3] = st[:, F["trial_t"]:F["trial_t"] + 3] = t
+    st[:, F["q"]:F["q"] + 4] = st[:, F["trial_q"]:F["trial_q"] + 4] = q
+    st[:, F["lam"]] = SCAN_REGISTER_LAMBDA0
+    w, x, y, z = q.T
+    s = 2.0 / (((w * w + x * x) + y * y) + z * z)
+    R = np.stack([1.0 - s * (y * y + z * z), s * (x * y - w * z), s * (x * z + w * y),
+                  s * (x * y + w * z), 1.0 - s * (x * x + z * z), s * (y * z - w * x),
+                  s * (x * z - w * y), s * (y * z + w * x), 1.0 - s * (x * x + y * y)], axis=1)
+    return st.view(np.int64), np.ascontiguousarray(np.concatenate([R, t], axis=1).astype(np.float32))
+
 
 SCAN_SEARCH_MAX_WINDOW = (2048, 2048, 4)
 SCAN_SEARCH_MAX_LEVELS = 6

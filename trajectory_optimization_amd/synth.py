@@ -2168,3 +2168,255 @@ def reloc_full_window(voxel, dims):
     likewise, wz = 0."""
     i = [min(max(int(v), 0), int(d) - 1) for v, d in zip(voxel, dims)]
     return (max(i[0], int(dims[0]) - 1 - i[0]), max(i[1], int(dims[1]) - 1 - i[1]), 0)
+
+
+# ---- scan registration restated in numpy and Python floats (DESIGN.md 10, "Scan registration"): what scanreg_kernels.hip must give,
+# ---- bit for bit.  The normal equations are integers; the step is f64 add, multiply, divide and compare in one fixed order.
+SCANREG_RECORD = 32          # int64 words of a pose's record: H's upper triangle (21), J^T e (6), e^2, used, inside, 0, 0
+SCANREG_STATE = 64           # 8-byte words of a pose's state
+SCANREG_STATUS = ("RUNNING", "CONVERGED", "STALLED", "DEGENERATE", "EMPTY")
+SCANREG_MAX_ITERATIONS = 256
+SCANREG_LAMBDA0 = 2.0 ** -10
+SCANREG_LAMBDA_MIN, SCANREG_LAMBDA_MAX = 2.0 ** -30, 2.0 ** 30
+SCANREG_TOL_T, SCANREG_TOL_R = 1.0 / 256.0, 1.0e-4
+# the state's words: f64 unless named an integer
+SR_T, SR_Q, SR_LAMBDA, SR_DELTA, SR_STATUS, SR_ITER, SR_ACCEPTED, SR_TRIAL_T, SR_TRIAL_Q, SR_RECORD = 0, 3, 7, 8, 14, 15, 16, 17, 20, 24
+SCANREG_DOF = "xyzrpw"       # translation x y z, rotation about the world's x (roll), y (pitch), z (yaw)
+
+
+def scan_dof_mask(dof):
+    """A string over `x y z r p w` (each at most once, at least one), or a 6-bit mask in [1, 63] -> the mask: bit i frees degree of
+    freedom i of (x, y, z, roll, pitch, yaw)."""
+    if isinstance(dof, str):
+        if not dof or len(set(dof)) != len(dof) or any(c not in SCANREG_DOF for c in dof):
+            raise ValueError(f"dof must name each of 'x y z r p w' at most once and one at least, got {dof!r}")
+        return sum(1 << SCANREG_DOF.index(c) for c in dof)
+    if isinstance(dof, (int, np.integer)) and not isinstance(dof, bool) and 1 <= int(dof) <= 63:
+        return int(dof)
+    raise ValueError(f"dof must be a string over 'xyzrpw' or a mask in [1, 63], got {dof!r}")
+
+
+def scan_fixed_ref(points, R, t, origin, resolution):
+    """Sensor-frame points (N,3) under the pose (R, t) -> (q (N,3) int64 in 1/256 voxel, ok (N,)): scan_voxels_ref's world coordinate,
+    then occ_fixed."""
+    f32 = np.float32
+    P = np.asarray(points, dtype=f32).reshape(-1, 3)
+    R, t = np.asarray(R, dtype=f32).reshape(3, 3), np.asarray(t, dtype=f32).reshape(3)
+    with np.errstate(all="ignore"):
+        cols = []
+        for a in range(3):
+            s = ((R[a, 0] * P[:, 0]).astype(f32) + (R[a, 1] * P[:, 1]).astype(f32)).astype(f32)
+            s = (s + (R[a, 2] * P[:, 2]).astype(f32)).astype(f32)
+            cols.append((s + t[a]).astype(f32))
+        W = np.stack(cols, axis=1)
+    return occ_fixed(W, origin, resolution)
+
+
+def scan_corners_ref(T, q, unknown_value=0):
+    """Fixed-point positions q (n,3) int64 over the dense table T (nx,ny,nz) of bytes -> (V (2,2,2,n) int64, w [axis] (2,n), all_inside
+    (n,)): the eight table bytes around each position on the lattice of voxel CENTRES, 128 + unknown_value outside dims."""
+    c = q - 128
+    b, f = c >> 8, c & 255
+    w = [np.stack([256 - f[:, k], f[:, k]]) for k in range(3)]
+    dims = np.asarray(T.shape, dtype=np.int64)
+    V = np.empty((2, 2, 2, len(q)), dtype=np.int64)
+    all_in = np.ones(len(q), dtype=bool)
+    for i in range(2):
+        for j in range(2):
+            for k in range(2):
+                v = b + np.asarray((i, j, k), dtype=np.int64)
+                ok = ((v >= 0) & (v < dims)).all(axis=1)
+                vc = np.clip(v, 0, dims - 1)
+                V[i, j, k] = np.where(ok, T[vc[:, 0], vc[:, 1], vc[:, 2]], 128 + int(unknown_value))
+                all_in &= ok
+    return V, w, all_in
+
+
+def scan_rows_ref(T, q, qt, unknown_value=0):
+    """The rows of the normal equations at positions q (n,3) with the pose's own fixed-point translation qt (3,) -> (J (n,6) int64,
+    e (n,) int64, all_inside (n,)), straight from the definitions: M24, G16, e, g, the lever arm a and j = (a x g + 2^11) >> 12."""
+    V, w, all_in = scan_corners_ref(T, q, unknown_value)
+    M24 = sum(V[i, j, k] * w[0][i] * w[1][j] * w[2][k] for i in range(2) for j in range(2) for k in range(2))
+    Gx = sum(w[1][j] * w[2][k] * (V[1, j, k] - V[0, j, k]) for j in range(2) for k in range(2))
+    Gy = sum(w[0][i] * w[2][k] * (V[i, 1, k] - V[i, 0, k]) for i in range(2) for k in range(2))
+    Gz = sum(w[0][i] * w[1][j] * (V[i, j, 1] - V[i, j, 0]) for i in range(2) for j in range(2))
+    e = (255 * (1 << 24) - M24 + (1 << 11)) >> 12
+    g = (np.stack([Gx, Gy, Gz], axis=1) + 128) >> 8
+    a = (q - np.asarray(qt, dtype=np.int64).reshape(1, 3) + 32) >> 6
+    cr = np.stack([a[:, 1] * g[:, 2] - a[:, 2] * g[:, 1], a[:, 2] * g[:, 0] - a[:, 0] * g[:, 2], a[:, 0] * g[:, 1] - a[:, 1] * g[:, 0]], axis=1)
+    return np.concatenate([g, (cr + (1 << 11)) >> 12], axis=1), e, all_in
+
+
+def scan_normal_ref(L, origin, resolution, points, poses12, floor=None, unknown_value=0, chunk=1 << 16):
+    """The records of B poses -> (B, 32) int64: [0:21] the upper triangle of H = sum J J^T, row-major, [21:27] sum J e, [27] sum e^2,
+    [28] used, [29] inside (all eight corners inside dims), [30:32] 0.  poses12 (B,12) f32: R row-major, then t.  A pose whose t is
+    out of range has an all-zero record.  At most 2^22 points: every sum stays below 2^62 and int64 holds it."""
+    P = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+    if not 1 <= len(P) <= SCAN_MAX_POINTS:
+        raise ValueError(f"1 .. 2^22 points, got {len(P)}")
+    poses12 = np.asarray(poses12, dtype=np.float32).reshape(-1, 12)
+    T = scan_values_ref(L, floor, unknown_value) + 128
+    iu = np.triu_indices(6)
+    out = np.zeros((len(poses12), SCANREG_RECORD), dtype=np.int64)
+    for b, pose in enumerate(poses12):
+        qt, t_ok = occ_fixed(pose[9:12], origin, resolution)
+        if not t_ok[0]:
+            continue
+        q, ok = scan_fixed_ref(P, pose[:9], pose[9:12], origin, resolution)
+        q = q[ok]
+        for i in range(0, len(q), chunk):
+            J, e, all_in = scan_rows_ref(T, q[i:i + chunk], qt[0], unknown_value)
+            out[b, :21] += (J[:, iu[0]] * J[:, iu[1]]).sum(axis=0)
+            out[b, 21:27] += (J * e[:, None]).sum(axis=0)
+            out[b, 27] += (e * e).sum()
+            out[b, 29] += int(all_in.sum())
+        out[b, 28] = len(q)
+    return out
+
+
+def scan_pose12_ref(t, q):
+    """The f64 state pose (t (3,) metres, q (4,) wxyz UNNORMALISED) -> the 12 f32 the kernels take: R of q with s = 2 / (q . q), in
+    this operation order, then t; each rounded once."""
+    w, x, y, z = (float(v) for v in q)
+    s = 2.0 / (((w * w + x * x) + y * y) + z * z)
+    R = [1.0 - s * (y * y + z * z), s * (x * y - w * z), s * (x * z + w * y),
+         s * (x * y + w * z), 1.0 - s * (x * x + z * z), s * (y * z - w * x),
+         s * (x * z - w * y), s * (y * z + w * x), 1.0 - s * (x * x + y * y)]
+    return np.asarray(R + [float(v) for v in t], dtype=np.float64).astype(np.float32)
+
+
+def scan_register_init_ref(poses, quats):
+    """B starting poses (B,3) and quaternions (B,4), host numbers -> (state (B,64) int64 — f64 words by their bits —, poses12 (B,12)
+    f32): the current and the trial pose are the start, lambda = 2^-10, everything else 0."""
+    t = np.asarray(poses, dtype=np.float64).reshape(-1, 3)
+    q = np.asarray(quats, dtype=np.float64).reshape(-1, 4)
+    st = np.zeros((len(t), SCANREG_STATE), dtype=np.float64)
+    st[:, SR_T:SR_T + 3] = st[:, SR_TRIAL_T:SR_TRIAL_T + 3] = t
+    st[:, SR_Q:SR_Q + 4] = st[:, SR_TRIAL_Q:SR_TRIAL_Q + 4] = q
+    st[:, SR_LAMBDA] = SCANREG_LAMBDA0
+    return st.view(np.int64), np.stack([scan_pose12_ref(a, b) for a, b in zip(t, q)])
+
+
+def scan_solve_ref(record, lam, mask):
+    """One damped Gauss-Newton solve from a record (32 ints) -> delta (6 floats: voxels, radians) or None where a pivot is <= 0 or not
+    finite.  A = S H S and rhs = S b / 4096 with S = diag(1/256 x3, 4 x3); a locked degree of freedom has its row and column cleared,
+    1 on the diagonal and rhs 0; A_ii += lam A_ii; LDL^T without pivoting, columns left to right, each sum in ascending k."""
+    S = (1.0 / 256.0,) * 3 + (4.0,) * 3
+    A = [[0.0] * 6 for _ in range(6)]
+    rhs = [0.0] * 6
+    n = 0
+    for i in range(6):
+        for j in range(i, 6):
+            free = (mask >> i) & 1 and (mask >> j) & 1
+            v = float(int(record[n])) * S[i] * S[j] if free else (1.0 if i == j else 0.0)
+            A[i][j] = A[j][i] = v
+            n += 1
+        rhs[i] = float(int(record[21 + i])) * S[i] * (1.0 / 4096.0) if (mask >> i) & 1 else 0.0
+    for i in range(6):
+        if (mask >> i) & 1:
+            A[i][i] = A[i][i] + lam * A[i][i]
+    Lm = [[0.0] * 6 for _ in range(6)]
+    d = [0.0] * 6
+    for j in range(6):
+        v = A[j][j]
+        for k in range(j):
+            v = v - Lm[j][k] * (Lm[j][k] * d[k])
+        if not (v > 0.0) or not v < math.inf:
+            return None
+        d[j] = v
+        for i in range(j + 1, 6):
+            u = A[i][j]
+            for k in range(j):
+                u = u - Lm[i][k] * (Lm[j][k] * d[k])
+            Lm[i][j] = u / v
+    y = [0.0] * 6
+    for i in range(6):
+        v = rhs[i]
+        for k in range(i):
+            v = v - Lm[i][k] * y[k]
+        y[i] = v
+    x = [0.0] * 6
+    for i in range(5, -1, -1):
+        v = y[i] / d[i]
+        for k in range(i + 1, 6):
+            v = v - Lm[k][i] * x[k]
+        x[i] = v
+    return x
+
+
+def scan_step_ref(records, state, resolution, dof=63, tol_t=SCANREG_TOL_T, tol_r=SCANREG_TOL_R):
+    """One step of every pose: records (B,32) int64 at the trial poses and state (B,64) int64 -> (the next state, poses12 (B,12) f32 or
+    None rows where a pose wrote none): what k_scan_step does, in Python floats (IEEE binary64, no fused operation)."""
+    mask = scan_dof_mask(dof)
+    r = float(np.float32(resolution))
+    tol_t, tol_r = float(tol_t), float(tol_r)
+    state = np.array(state, dtype=np.int64).reshape(-1, SCANREG_STATE)
+    records = np.asarray(records, dtype=np.int64).reshape(-1, SCANREG_RECORD)
+    F = state.view(np.float64)
+    poses12 = [None] * len(state)
+    for b in range(len(state)):
+        I, D = state[b], F[b]
+        if I[SR_STATUS] != 0:
+            continue
+        first = I[SR_ITER] == 0
+        I[SR_ITER] += 1
+        rec = records[b]
+        if rec[28] == 0:
+            I[SR_STATUS] = 4
+            continue
+        cur = I[SR_RECORD:SR_RECORD + 32]
+        if first or (rec[28] == cur[28] and rec[27] < cur[27]):
+            D[SR_T:SR_T + 3] = D[SR_TRIAL_T:SR_TRIAL_T + 3]
+            D[SR_Q:SR_Q + 4] = D[SR_TRIAL_Q:SR_TRIAL_Q + 4]
+            cur[:] = rec
+            if not first:
+                I[SR_ACCEPTED] += 1
+                lam = float(D[SR_LAMBDA]) / 8.0
+                D[SR_LAMBDA] = lam if lam > SCANREG_LAMBDA_MIN else SCANREG_LAMBDA_MIN
+                d = [float(v) for v in D[SR_DELTA:SR_DELTA + 6]]
+                if all(v <= tol_t and -v <= tol_t for v in d[:3]) and all(v <= tol_r and -v <= tol_r for v in d[3:]):
+                    I[SR_STATUS] = 1
+                    continue
+        else:
+            lam = float(D[SR_LAMBDA]) * 8.0
+            D[SR_LAMBDA] = lam
+            if lam > SCANREG_LAMBDA_MAX:
+                I[SR_STATUS] = 2
+                continue
+        x = scan_solve_ref([int(v) for v in cur], float(D[SR_LAMBDA]), mask)
+        if x is None:
+            I[SR_STATUS] = 3
+            continue
+        D[SR_DELTA:SR_DELTA + 6] = x
+        t = [float(D[SR_T + a]) + r * x[a] for a in range(3)]
+        qw, qx, qy, qz = (float(v) for v in D[SR_Q:SR_Q + 4])
+        hx, hy, hz = 0.5 * x[3], 0.5 * x[4], 0.5 * x[5]
+        q = [((qw - hx * qx) - hy * qy) - hz * qz,
+             ((qx + hx * qw) + hy * qz) - hz * qy,
+             ((qy - hx * qz) + hy * qw) + hz * qx,
+             ((qz + hx * qy) - hy * qx) + hz * qw]
+        D[SR_TRIAL_T:SR_TRIAL_T + 3] = t
+        D[SR_TRIAL_Q:SR_TRIAL_Q + 4] = q
+        poses12[b] = scan_pose12_ref(t, q)
+    return state, poses12
+
+
+def scan_register_ref(L, origin, resolution, points, poses, quats, iterations=30, dof=63, tol_t=SCANREG_TOL_T, tol_r=SCANREG_TOL_R, floor=None,
+                      unknown_value=0):
+    """`iterations` rounds of normal + step from the starting poses -> the state (B,64) int64: what ScanMatcher.register leaves on the
+    device, bit for bit.  A frozen pose's record is not evaluated."""
+    if not 1 <= int(iterations) <= SCANREG_MAX_ITERATIONS:
+        raise ValueError(f"1 .. {SCANREG_MAX_ITERATIONS} iterations, got {iterations!r}")
+    state, poses12 = scan_register_init_ref(poses, quats)
+    for _ in range(int(iterations)):
+        live = np.flatnonzero(state[:, SR_STATUS] == 0)
+        if len(live) == 0:
+            break
+        records = np.zeros((len(state), SCANREG_RECORD), dtype=np.int64)
+        records[live] = scan_normal_ref(L, origin, resolution, points, poses12[live], floor, unknown_value)
+        state, new = scan_step_ref(records, state, resolution, dof, tol_t, tol_r)
+        for b, row in enumerate(new):
+            if row is not None:
+                poses12[b] = row
+    return state
+

@@ -506,6 +506,71 @@ def relocalise_scan(map_or_matcher, points, pose, quat, window=None, yaw=None, r
                      incumbent=int(rec[8]))
 
 
+def scan_registrations(state, resolution, dof="xyzrpw"):
+    """A registration state (B,64) int64 ON THE HOST -> [ScanRegistration] in numpy: the pose, the quaternion normalised once, the
+    cost and counters of the record at the result, the information matrix A = S H S and the covariance sigma^2 A^-1 over the free
+    degrees of freedom, both in metres and radians."""
+    mask = ops.scan_dof_mask(dof)
+    free = np.asarray([(mask >> i) & 1 for i in range(6)], dtype=bool)
+    r = float(np.float32(resolution))
+    state = np.ascontiguousarray(np.asarray(state, dtype=np.int64).reshape(-1, ops.SCAN_REGISTER_STATE))
+    floats = state.view(np.float64)
+    F = ops.SCAN_REGISTER_FIELDS
+    scale = np.asarray([1.0 / (256.0 * r)] * 3 + [4.0] * 3)   # 1/256 byte per voxel -> byte per metre; 4 byte per radian -> byte per radian
+    iu = np.triu_indices(6)
+    out = []
+    for I, D in zip(state, floats):
+        rec = I[F["record"]:F["record"] + ops.SCAN_REGISTER_RECORD]
+        H = np.zeros((6, 6))
+        H[iu] = rec[:21].astype(np.float64)
+        H = H + np.triu(H, 1).T
+        A = H * scale[:, None] * scale[None, :]
+        A[~free] = 0.0
+        A[:, ~free] = 0.0
+        used, n_dof = int(rec[28]), int(free.sum())
+        cost = float(int(rec[27])) / 4096.0 ** 2
+        cov = np.zeros((6, 6))
+        if used > n_dof:
+            sub = A[np.ix_(free, free)]
+            if np.isfinite(sub).all() and np.linalg.matrix_rank(sub) == n_dof:
+                cov[np.ix_(free, free)] = cost / (used - n_dof) * np.linalg.inv(sub)
+        q = D[F["q"]:F["q"] + 4].copy()
+        out.append(ScanRegistration(pose=D[F["t"]:F["t"] + 3].copy(), quat=q / np.sqrt((q * q).sum()), cost=cost,
+                                    rms=math.sqrt(cost / used) if used else 0.0, used=used, inside=int(rec[29]), iterations=int(I[F["iterations"]]),
+                                    accepted=int(I[F["accepted"]]), status=ops.SCAN_REGISTER_STATUS[int(I[F["status"]])], information=A,
+                                    covariance=cov, lam=float(D[F["lam"]])))
+    return out
+
+
+def register_scan(map_or_matcher, points, pose, quat, iterations=30, dof="xyzrpw", tol_t=None, tol_r=None, floor=None, unknown_value=0):
+    """The last link of match -> REGISTER -> integrate ("Scan registration"): refine a pose that match_scan or
+    relocalise_scan found to one voxel and one step of a yaw list into a sub-voxel translation and a continuous rotation, by damped
+    Gauss-Newton steps on the trilinear interpolation of the map's score table.  points (N,3), the scan in the SENSOR frame; pose (3,)
+    and quat (4,) wxyz, or B of each (at most 256): a batch is refined in the same launches, and each pose of it is bitwise its own
+    single run.  dof: the degrees of freedom that move, a string over 'x y z r p w' (roll, pitch, yaw: rotations about the world's x,
+    y, z through the sensor's position) or a 6-bit mask; a planar robot passes 'xyw'.  iterations: 1 .. 256 rounds, each pose frozen
+    as soon as its status leaves RUNNING: CONVERGED (an accepted step within tol_t voxels — None: 1/256 — and tol_r radians — None:
+    1e-4), STALLED (lambda passed 2^30: no step lowers the cost, the usual end at a kink of the field), DEGENERATE (a pivot of the
+    damped system is not positive: a direction the scan does not constrain — lock it with dof) or EMPTY (no point in range).
+    map_or_matcher, floor and unknown_value as match_scan takes them.  -> ScanRegistration for one pose, a list of them for a batch.
+
+    THE COVARIANCE is sigma^2 A^-1 over the free degrees of freedom, A the Gauss-Newton normal matrix at the result and sigma^2 =
+    cost / (used - n_dof): the Gauss-Newton approximation on a piecewise-trilinear field whose residual target is the byte 255.  It
+    tells WHICH DIRECTIONS the scan constrains and how they compare — a corridor's axis comes out orders of magnitude looser than its
+    width, or DEGENERATE — it is not a calibrated uncertainty: the residuals are neither independent nor Gaussian, and the map's own
+    error is not in it.  The basin is about one voxel (that is what match_scan is for); there is no robust loss.
+
+    One copy of the poses to the device, which waits for the current stream, then launches only; one read-back, of the state, at
+    the end."""
+    matcher = _scan_matcher("register_scan", map_or_matcher, floor, unknown_value)
+    q = ops._host_rows(quat, 4, "quat")
+    t = ops._host_rows(pose, 3, "pose")
+    single = t.shape[0] == 1 and q.shape[0] == 1 and np.ndim(pose) <= 1 and np.ndim(quat) <= 1
+    state = matcher.register(points, t, q, iterations=iterations, dof=dof, tol_t=tol_t, tol_r=tol_r)
+    out = scan_registrations(state.cpu().numpy(), matcher.resolution, dof)   # the one read-back
+    return out[0] if single else out
+
+
 def score_scans(map_or_matcher, points, poses, quats, shifts=None, floor=None, unknown_value=0):
     """How well does the scan fit the map at each of these poses?  B explicit candidates — poses (B,3), quats (B,4) wxyz, shifts None
     or (B,3) voxels — -> (score, used, inside, known), each (B,) int32 on the device (ops.ScanMatcher.score): the weights a particle
@@ -630,6 +695,23 @@ class ScanMatch(_Result):
         rounds them — the scores' own arithmetic is not promised."""
         R = torch.from_numpy(ops.scan_rotations(self.quat, "quat")[0]).to(points.device)
         t = torch.as_tensor(np.asarray(self.pose_refined if refined else self.pose, dtype=np.float32), device=points.device)
+        return points.to(torch.float32) @ R.T + t
+
+
+class ScanRegistration(_Result):
+    """What register_scan returns: pose (3,) f64 in metres and quat (4,) f64 wxyz, normalised on the host; cost, the sum of squared
+    residuals 255 - M in byte^2 at the result, and rms = sqrt(cost / used) in bytes; used (the points in range) and inside (those whose
+    eight corners all lie inside dims); iterations run and steps accepted; status, a name of ops.SCAN_REGISTER_STATUS; lam, the last
+    lambda; information (6,6) f64, A = J^T J at the result over (x, y, z in metres; roll, pitch, yaw in radians), and covariance (6,6)
+    f64 = cost / (used - n_dof) A^-1 over the free degrees of freedom — rows and columns of a locked one are zero, and all of it where
+    used <= n_dof or A is singular.  See register_scan for what the covariance is and is not.  world(points) takes sensor-frame points
+    to the world at the registered pose."""
+    __slots__ = ("pose", "quat", "cost", "rms", "used", "inside", "iterations", "accepted", "status", "lam", "information", "covariance")
+
+    def world(self, points):
+        """(N,3) sensor-frame points on a device -> (N,3) f32 world points at the registered pose: torch ops, rounded as torch rounds."""
+        R = torch.from_numpy(ops.scan_rotations(self.quat, "quat")[0]).to(points.device)
+        t = torch.as_tensor(np.asarray(self.pose, dtype=np.float32), device=points.device)
         return points.to(torch.float32) @ R.T + t
 
 
