@@ -41,7 +41,10 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_scanreg_normal / tohip_scanreg_step and TOHIP_SCANREG_RECORD / TOHIP_SCANREG_STATE (fine scan registration: integer
+/* (still 15) + tohip_posegraph_workspace_bytes / tohip_posegraph_layout / tohip_posegraph_start / tohip_posegraph_linearize /
+ * tohip_posegraph_gather / tohip_posegraph_step / tohip_posegraph_optimize / tohip_posegraph_result and the TOHIP_POSEGRAPH_* constants
+ * (pose-graph optimisation: Levenberg-Marquardt over scan poses, each step by block-Jacobi conjugate gradients): new symbols only.
+ * (still 15) + tohip_scanreg_normal / tohip_scanreg_step and TOHIP_SCANREG_RECORD / TOHIP_SCANREG_STATE (fine scan registration: integer
  * normal equations of a scan on the trilinear score table, and a damped Gauss-Newton step per pose): new symbols only.
  * (still 15) + tohip_reloc_levels / tohip_reloc_bounds / tohip_reloc_workspace_bytes / tohip_reloc_search (relocalisation: exact
  * branch-and-bound scan matching over wide windows, on sliding-maximum copies of the score table): new symbols only.
@@ -1662,6 +1665,67 @@ int tohip_scanreg_normal(const void *table, size_t table_bytes, const tohip_occ_
                          uint32_t flags);
 int tohip_scanreg_step(const int64_t *records, int64_t *state, int64_t b, float resolution, int32_t dof_mask, double tol_t, double tol_r,
                        float *poses, void *stream, uint32_t flags);
+
+/* ---- pose-graph optimisation (posegraph_kernels.hip, DESIGN.md §10, "Pose graph") ----------------------
+ * Nodes: n_nodes poses, 7 f64 each (t in metres, q wxyz, NOT required to be unit; R(q) with s = 2 / q.q).  Edges: ab (e, 2) int32, a = -1
+ * an ABSOLUTE edge (node b measured in the world: an edge from the frame t = 0, q = (1, 0, 0, 0)); meas (e, 7) f64, z_t and z_q wxyz;
+ * omega (e, 21) f64, the upper triangle of the symmetric 6 x 6 information matrix over (x, y, z, roll, pitch, yaw), row-major.
+ * Residual: e_t = R_a^T (t_b - t_a) - z_t;  eps = conj(q_a) (x) q_b (x) conj(z_q);  e_r = 2 vec(eps) / w(eps) (no sqrt, no
+ * trigonometry, invariant to the sign and scale of every quaternion; w(eps) = 0 makes the cost non-finite).  s = e^T Omega e; cost =
+ * sum rho(s): rho = s, or with robust_c = c > 0 Geman-McClure c^2 s / (c^2 + s) and the IRLS weight (c^2 / (c^2 + s))^2.  A node moves
+ * by t + dt, q <- (1, dr / 2) (x) q.  free_mask (n_nodes) int32: bit i frees degree of freedom i of a node, 0 fixes it; a locked one has
+ * an identity row and column and a zero right-hand side.  row_ptr (n_nodes + 1) and incident (n_incident) int32: node i's incident
+ * edges incident[row_ptr[i] .. row_ptr[i + 1]), each 2 edge + side (0: the node is a, 1: it is b), in ascending edge index; a and b
+ * of an edge differ.  The caller builds them (synth.pose_graph_incidence); the kernels trust them within the sizes given.
+ * EDGE RECORD, TOHIP_POSEGRAPH_EDGE f64: [0:6] e; [6] s; [7] the weight w; [8] rho; [9] 0; with W = w Omega and the columns of locked
+ *   degrees of freedom of Ja, Jb cleared: [10:31] Ja^T W Ja and [31:52] Jb^T W Jb (upper triangles), [52:88] Ja^T W Jb, [88:94] Ja^T W e,
+ *   [94:100] Jb^T W e.  800 bytes an edge, two buffers of them (current and trial).
+ * WORKSPACE: tohip_posegraph_workspace_bytes(n, e) bytes, 8-byte aligned; tohip_posegraph_layout gives the word offsets of its
+ *   TOHIP_POSEGRAPH_REGIONS regions: the scalars (3 copies of TOHIP_POSEGRAPH_SCALARS words; copy 1 is current between calls: lambda, cost,
+ *   initial cost, status int64 (0 running, 1 converged, 2 stalled, 3 degenerate, 4 non-finite), iterations, accepted, CG iterations in
+ *   total, the current buffer 0 / 1, r.z, its first value, the CG stop flag, whether a trial was ever accepted), poses (8 n), the
+ *   pending step x (6 n), the edge records (2 e 100), the node blocks D (21) and g (6) (2 n 27), L d L^T (21 n), r, z (6 n each), p
+ *   (2 x 6 n), A p (6 n), the partial arrays of the cost, r.z, p.Ap, the small-step and bad-pivot flags, the trial cost with the
+ *   small-step flags' conjunction behind it (2 words), the total.
+ * tohip_posegraph_start: the poses from `nodes`, x = 0, the three copies of the scalars 0 but lambda = 2^-10, the small-step flags 1.
+ *   Every other region stays as it was allocated: each is written before it is read.  One launch.
+ * tohip_posegraph_linearize: the records at the TRIAL poses (current moved by x) into the buffer that is not current, and the cost's
+ *   block partials.  tohip_posegraph_gather: each node's D and g over its incident edges, and the trial cost.  One launch each.
+ * tohip_posegraph_step: k_scan_step's state machine on the trial cost (non-finite: status 4; the first trial, or a strictly lower
+ *   cost: accepted, from the second on lambda <- max(lambda / 8, 2^-30) and converged if the accepted step was within tol_t and tol_r on
+ *   every node; else lambda <- 8 lambda, stalled past 2^30), then (H + lambda diag H) x = -g by conjugate gradients from x = 0,
+ *   preconditioned by the L d L^T of each damped diagonal block (a pivot <= 0 or not finite: status 3): 1 + 2 cg_iterations launches;
+ *   the solve stops at r.z <= cg_tol^2 (r.z)_0 or p.Ap <= 0, after which the remaining launches return at once.
+ * tohip_posegraph_optimize: `iterations` rounds of linearize, gather, step, enqueued at once.  tohip_posegraph_result: out (16 + 7 n +
+ *   2 e) f64: the current scalars, the poses, s and w of every edge at the current poses (0 before any acceptance).
+ * Every sum has one order: the same bits in every run, and synth.pose_graph_*_ref's.  flags is reserved and must be 0.  A
+ * bad size, count, tolerance or flags, a null or misaligned buffer, or a workspace (or out) that shares a byte with an input (or
+ * with the workspace), by address ranges: TOHIP_EINVAL; a short workspace: TOHIP_ENOSPC (tohip_posegraph_workspace_bytes: 0).  Every argument check returns before anything is enqueued.  Nothing is
+ * read back. */
+#define TOHIP_POSEGRAPH_EDGE 100
+#define TOHIP_POSEGRAPH_SCALARS 16
+#define TOHIP_POSEGRAPH_REGIONS 17
+#define TOHIP_POSEGRAPH_MAX_ITERATIONS 256
+#define TOHIP_POSEGRAPH_MAX_CG 4096
+size_t tohip_posegraph_workspace_bytes(int64_t n_nodes, int64_t n_edges, uint32_t flags);
+int tohip_posegraph_layout(int64_t n_nodes, int64_t n_edges, int64_t *offsets_host, uint32_t flags);
+int tohip_posegraph_start(const double *nodes, int64_t n_nodes, int64_t n_edges, void *workspace, size_t workspace_bytes, void *stream,
+                          uint32_t flags);
+int tohip_posegraph_linearize(const int32_t *ab, const double *meas, const double *omega, const int32_t *row_ptr, const int32_t *incident,
+                              const int32_t *free_mask, int64_t n_nodes, int64_t n_edges, int64_t n_incident, double robust_c,
+                              void *workspace, size_t workspace_bytes, void *stream, uint32_t flags);
+int tohip_posegraph_gather(const int32_t *ab, const double *meas, const double *omega, const int32_t *row_ptr, const int32_t *incident,
+                           const int32_t *free_mask, int64_t n_nodes, int64_t n_edges, int64_t n_incident, void *workspace,
+                           size_t workspace_bytes, void *stream, uint32_t flags);
+int tohip_posegraph_step(const int32_t *ab, const double *meas, const double *omega, const int32_t *row_ptr, const int32_t *incident,
+                         const int32_t *free_mask, int64_t n_nodes, int64_t n_edges, int64_t n_incident, int64_t cg_iterations,
+                         double cg_tol, double tol_t, double tol_r, void *workspace, size_t workspace_bytes, void *stream, uint32_t flags);
+int tohip_posegraph_optimize(const int32_t *ab, const double *meas, const double *omega, const int32_t *row_ptr, const int32_t *incident,
+                             const int32_t *free_mask, int64_t n_nodes, int64_t n_edges, int64_t n_incident, int64_t iterations,
+                             int64_t cg_iterations, double cg_tol, double robust_c, double tol_t, double tol_r, void *workspace,
+                             size_t workspace_bytes, void *stream, uint32_t flags);
+int tohip_posegraph_result(int64_t n_nodes, int64_t n_edges, const void *workspace, size_t workspace_bytes, double *out, void *stream,
+                           uint32_t flags);
 
 /* ---- optional per-kernel timing (bench.py's roofline leg) -----------------------------------------
  * When enabled, every launch of the big kernels is bracketed by hipEventRecord on its own stream.

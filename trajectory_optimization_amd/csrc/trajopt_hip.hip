@@ -22,6 +22,7 @@
 #include "evidence_kernels.hip"
 #include "scanmatch_kernels.hip"
 #include "scanreg_kernels.hip"
+#include "posegraph_kernels.hip"
 #include "scansearch_kernels.hip"
 #include "reframe_kernels.hip"
 #include "travel_kernels.hip"

@@ -2494,6 +2494,429 @@ def scan_register_start(poses, quats):
     return st.view(np.int64), np.ascontiguousarray(np.concatenate([R, t], axis=1).astype(np.float32))
 
 
+# ---- pose-graph optimisation: Levenberg-Marquardt over scan poses (posegraph_kernels.hip, DESIGN.md 10 "Pose graph")
+
+POSE_GRAPH_EDGE = _lib.CONSTANTS["TOHIP_POSEGRAPH_EDGE"]          # f64 words of an edge's record
+POSE_GRAPH_SCALARS = _lib.CONSTANTS["TOHIP_POSEGRAPH_SCALARS"]    # words of the optimiser's scalars
+POSE_GRAPH_MAX_ITERATIONS = _lib.CONSTANTS["TOHIP_POSEGRAPH_MAX_ITERATIONS"]
+POSE_GRAPH_MAX_CG = _lib.CONSTANTS["TOHIP_POSEGRAPH_MAX_CG"]
+POSE_GRAPH_MAX_NODES = POSE_GRAPH_MAX_EDGES = 1 << 22
+POSE_GRAPH_STATUS = ("RUNNING", "CONVERGED", "STALLED", "DEGENERATE", "NONFINITE")
+# the workspace's regions in tohip_posegraph_layout's order, and the scalars' words
+POSE_GRAPH_REGIONS = ("scalars", "poses", "x", "edges", "nodes", "ldl", "r", "z", "p", "ap", "cost_partials", "rz_partials", "pap_partials",
+                      "small_flags", "pivot_flags", "trial_cost", "total")
+POSE_GRAPH_FIELDS = dict(lam=0, cost=1, initial_cost=2, status=3, iterations=4, accepted=5, cg_iterations=6, current=7, rz=8, rz0=9, cg_stop=10,
+                         have=11)
+# an edge record's words: e (6), s, w, rho, 0, Ja^T W Ja (21), Jb^T W Jb (21), Ja^T W Jb (36), Ja^T W e (6), Jb^T W e (6)
+POSE_GRAPH_RECORD = dict(e=0, s=6, w=7, rho=8, haa=10, hbb=31, hab=52, ga=88, gb=94)
+assert len(POSE_GRAPH_REGIONS) == _lib.CONSTANTS["TOHIP_POSEGRAPH_REGIONS"]
+_TRIU6 = tuple((i, j) for i in range(6) for j in range(i, 6))
+
+
+def pose_graph_layout(n_nodes, n_edges):
+    """{region: its offset in the workspace, in 8-byte words}, 'total' the workspace's size: tohip_posegraph_layout's answer."""
+    off = (ctypes.c_int64 * len(POSE_GRAPH_REGIONS))()
+    check(_lib.lib().tohip_posegraph_layout(int(n_nodes), int(n_edges), off, 0), "tohip_posegraph_layout")
+    return dict(zip(POSE_GRAPH_REGIONS, (int(v) for v in off)))
+
+
+def pose_graph_incidence(ab, n_nodes):
+    """Edges (E,2), a = -1 an absolute edge -> (row_ptr (n+1,) int32, incident int32): node i's entries incident[row_ptr[i]:row_ptr[i+1]]
+    are 2 edge + side (0: the node is the edge's a, 1: its b) in ascending edge index — the order of every sum over a node's edges."""
+    node = np.asarray(ab, dtype=np.int64).reshape(-1)
+    code = np.arange(len(node), dtype=np.int64)
+    keep = node >= 0
+    node, code = node[keep], code[keep]
+    order = np.argsort(node, kind="stable")
+    row_ptr = np.zeros(int(n_nodes) + 1, dtype=np.int64)
+    np.add.at(row_ptr, node + 1, 1)
+    return np.cumsum(row_ptr).astype(np.int32), code[order].astype(np.int32)
+
+
+def pose_graph_information(information, n_edges, name="information"):
+    """(E,6,6) symmetric matrices, or (E,21) upper triangles row-major (one of either for E edges alike) -> (E,21) f64.  The order is
+    (x, y, z, roll, pitch, yaw), metres and radians.  A non-finite entry, an asymmetric matrix or a negative diagonal entry is
+    refused, by edge."""
+    try:
+        a = np.asarray(information.detach().cpu().numpy() if torch.is_tensor(information) else information, dtype=np.float64)
+    except (TypeError, ValueError):
+        a = np.zeros(0)
+    if a.shape in ((6, 6), (21,)):
+        a = np.broadcast_to(a, (n_edges,) + a.shape)
+    if a.shape == (n_edges, 6, 6):
+        if not np.array_equal(a, a.transpose(0, 2, 1)):
+            k = int(np.flatnonzero((a != a.transpose(0, 2, 1)).any(axis=(1, 2)))[0])
+            raise ValueError(f"{name}: the matrix of edge {k} is not symmetric")
+        a = np.stack([a[:, i, j] for i, j in _TRIU6], axis=1)
+    if a.shape != (n_edges, 21):
+        raise ValueError(f"{name} must be ({n_edges},6,6), ({n_edges},21), or one (6,6) or (21,) for all, got {a.shape}")
+    diag = a[:, [n for n, (i, j) in enumerate(_TRIU6) if i == j]]
+    bad = ~np.isfinite(a).all(axis=1) | (diag < 0.0).any(axis=1)
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"{name}: edge {k} has a non-finite entry or a negative diagonal entry: {a[k].tolist()}")
+    return np.ascontiguousarray(a)
+
+
+def check_pose_graph(n_nodes, ab, fixed=()):
+    """A graph's structure, by name; needs no GPU.  n_nodes in [1, 2^22]; ab (E,2) integers with 1 <= E <= 2^22, b in [0, n), a in [0, n)
+    or -1 (an absolute edge), a != b; fixed: node indices in [0, n).  Every connected component must hold a fixed node or an
+    absolute edge (union-find on the host), otherwise the optimum is not unique and ValueError names a node of the floating
+    component.  -> (ab (E,2) int32, fixed as a sorted int64 array)."""
+    if not _is_int(n_nodes) or not 1 <= n_nodes <= POSE_GRAPH_MAX_NODES:
+        raise ValueError(f"the nodes must number 1 .. 2^22, got {n_nodes!r}")
+    n = int(n_nodes)
+    e = np.asarray(ab)
+    if e.ndim != 2 or e.shape[1] != 2 or e.dtype.kind not in "iu" or not 1 <= e.shape[0] <= POSE_GRAPH_MAX_EDGES:
+        raise ValueError(f"the edges must be an (E,2) integer array with 1 <= E <= 2^22, got {e.shape} {e.dtype}")
+    e = e.astype(np.int64)
+    bad = (e[:, 1] < 0) | (e[:, 1] >= n) | (e[:, 0] < -1) | (e[:, 0] >= n)
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"edge {k} = ({e[k, 0]}, {e[k, 1]}): an index out of range for {n} nodes (a = -1 alone marks an absolute edge)")
+    if (e[:, 0] == e[:, 1]).any():
+        k = int(np.flatnonzero(e[:, 0] == e[:, 1])[0])
+        raise ValueError(f"edge {k} = ({e[k, 0]}, {e[k, 1]}): a and b must differ")
+    f = np.unique(np.asarray(list(fixed) if not isinstance(fixed, np.ndarray) else fixed, dtype=np.int64).reshape(-1))
+    if len(f) and (f[0] < 0 or f[-1] >= n):
+        raise ValueError(f"fixed: node {int(f[0] if f[0] < 0 else f[-1])} out of range for {n} nodes")
+    rel = e[e[:, 0] >= 0]
+    try:                                       # the components: scipy's where it is installed, union-find otherwise; `root` labels them
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components
+        root = connected_components(coo_matrix((np.ones(len(rel), dtype=np.int8), (rel[:, 0], rel[:, 1])), shape=(n, n)), directed=False)[1]
+        root = root.astype(np.int64)
+    except ImportError:
+        parent = np.arange(n, dtype=np.int64)
+
+        def find(i):
+            while parent[i] != i:
+                parent[i] = parent[parent[i]]
+                i = parent[i]
+            return i
+        for a, b in rel:
+            ra, rb = find(a), find(b)
+            if ra != rb:
+                parent[max(ra, rb)] = min(ra, rb)
+        root = np.asarray([find(i) for i in range(n)], dtype=np.int64)
+    anchored = np.zeros(n, dtype=bool)
+    anchored[root[f]] = True
+    anchored[root[e[e[:, 0] < 0, 1]]] = True
+    loose = ~anchored[root]
+    if loose.any():
+        i = int(np.flatnonzero(loose)[0])
+        raise ValueError(f"node {i} belongs to a floating component ({int((root == root[i]).sum())} nodes): it holds no fixed node and no "
+                         "absolute edge, so its poses are not determined")
+    return e.astype(np.int32), f
+
+
+def check_pose_graph_buffers(outputs, inputs):
+    """No output may share a byte with an input or with another output, by address ranges: {name: tensor} each; ValueError names
+    the pair that overlaps."""
+    seen = [(name, t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for name, t in inputs.items()]
+    for name, t in outputs.items():
+        lo, hi = t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
+        for other, a, b in seen:
+            if lo < b and a < hi:
+                raise ValueError(f"the output `{name}` aliases `{other}`: an output may share no byte with an input or with another output")
+        seen.append((name, lo, hi))
+
+
+def check_pose_graph_options(iterations=None, cg_iterations=None, cg_tol=1e-8, robust=None, tol_t=1e-5, tol_r=1e-6, n_nodes=1):
+    """An optimisation's settings, by name; needs no GPU -> (iterations, cg_iterations, cg_tol, robust_c, tol_t, tol_r): iterations
+    (None: not asked) in [1, 256]; cg_iterations None (min(6 n, 1000)) or in [1, 4096]; robust None (-> 0.0, the plain cost) or a finite
+    c > 0; cg_tol, tol_t, tol_r finite and >= 0."""
+    if iterations is not None and (not _is_int(iterations) or not 1 <= iterations <= POSE_GRAPH_MAX_ITERATIONS):
+        raise ValueError(f"iterations must be an integer in [1, {POSE_GRAPH_MAX_ITERATIONS}], got {iterations!r}")
+    if cg_iterations is None:
+        cg_iterations = min(6 * int(n_nodes), 1000)
+    if not _is_int(cg_iterations) or not 1 <= cg_iterations <= POSE_GRAPH_MAX_CG:
+        raise ValueError(f"cg_iterations must be None or an integer in [1, {POSE_GRAPH_MAX_CG}], got {cg_iterations!r}")
+    out = []
+    for name, v in (("cg_tol", cg_tol), ("tol_t", tol_t), ("tol_r", tol_r)):
+        f = _float_or_nan(v)
+        if not (np.isfinite(f) and f >= 0.0):
+            raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
+        out.append(f)
+    c = 0.0 if robust is None else _float_or_nan(robust)
+    if robust is not None and not (np.isfinite(c) and c > 0.0):
+        raise ValueError(f"robust must be None or a finite number > 0, got {robust!r}")
+    return (None if iterations is None else int(iterations)), int(cg_iterations), out[0], c, out[1], out[2]
+
+
+class PoseGraphProblem:
+    """One graph ON THE DEVICE and its workspace: the stages of the optimiser, each enqueued on the current stream with nothing read
+    back.  nodes (N,7) f64 (t, q wxyz), ab (E,2) int32, meas (E,7) f64, omega (E,21) f64, row_ptr (N+1,), incident and free_mask (N,)
+    int32: contiguous tensors of one device, as PoseGraph.upload makes them.  They are read, never written."""
+    NAMES = ("nodes", "ab", "meas", "omega", "row_ptr", "incident", "free_mask")
+
+    def __init__(self, nodes, ab, meas, omega, row_ptr, incident, free_mask):
+        t = dict(zip(self.NAMES, (nodes, ab, meas, omega, row_ptr, incident, free_mask)))
+        n, e = (nodes.shape[0], ab.shape[0]) if torch.is_tensor(nodes) and torch.is_tensor(ab) and nodes.dim() == 2 and ab.dim() == 2 else (0, 0)
+        if not (1 <= n <= POSE_GRAPH_MAX_NODES and 1 <= e <= POSE_GRAPH_MAX_EDGES):
+            raise ValueError(f"PoseGraphProblem: 1 .. 2^22 nodes and edges, got {n} and {e}")
+        want = dict(nodes=((n, 7), torch.float64), ab=((e, 2), torch.int32), meas=((e, 7), torch.float64), omega=((e, 21), torch.float64),
+                    row_ptr=((n + 1,), torch.int32), free_mask=((n,), torch.int32))
+        for name, v in t.items():
+            ok = torch.is_tensor(v) and v.is_contiguous() and v.device == nodes.device
+            if name == "incident":
+                ok = ok and v.dtype == torch.int32 and v.dim() == 1 and e <= v.shape[0] <= 2 * e
+            else:
+                ok = ok and tuple(v.shape) == want[name][0] and v.dtype == want[name][1]
+            if not ok:
+                raise ValueError(f"PoseGraphProblem: {name} must be a contiguous {want.get(name, (('E .. 2E',), torch.int32))} tensor on {nodes.device}, got "
+                                 f"{(tuple(v.shape), v.dtype, str(v.device)) if torch.is_tensor(v) else type(v).__name__}")
+        self.tensors, self.n, self.e, self.device = t, n, e, nodes.device
+        self.off = pose_graph_layout(n, e)
+        assert self.off["total"] * 8 == _lib.lib().tohip_posegraph_workspace_bytes(n, e, 0)
+        self.work = torch.empty(self.off["total"], dtype=torch.float64, device=self.device)
+        check_pose_graph_buffers({"workspace": self.work}, t)
+
+    def _call(self, name, *args):
+        with torch.cuda.device(self.device):
+            check(getattr(_lib.lib(), name)(*args, stream_ptr(), 0), name)
+
+    def _graph(self):
+        t = self.tensors
+        return (ptr(t["ab"]), ptr(t["meas"]), ptr(t["omega"]), ptr(t["row_ptr"]), ptr(t["incident"]), ptr(t["free_mask"]), self.n, self.e,
+                t["incident"].shape[0])
+
+    def _work(self):
+        return ptr(self.work), self.work.numel() * 8
+
+    def start(self):
+        """The current poses = nodes, the pending step 0, lambda = 2^-10 -> self.  One launch."""
+        self._call("tohip_posegraph_start", ptr(self.tensors["nodes"]), self.n, self.e, *self._work())
+        return self
+
+    def linearize(self, robust_c=0.0):
+        """The edge records at the trial poses, into the edge buffer that is not current -> self.  One launch."""
+        self._call("tohip_posegraph_linearize", *self._graph(), float(robust_c), *self._work())
+        return self
+
+    def gather(self):
+        """Each node's diagonal block and gradient from the trial records, and the trial cost -> self.  One launch."""
+        self._call("tohip_posegraph_gather", *self._graph(), *self._work())
+        return self
+
+    def step(self, cg_iterations, cg_tol=1e-8, tol_t=1e-5, tol_r=1e-6):
+        """Accept or reject the trial, adapt lambda, and solve the next damped step -> self.  1 + 2 cg_iterations launches."""
+        self._call("tohip_posegraph_step", *self._graph(), int(cg_iterations), float(cg_tol), float(tol_t), float(tol_r), *self._work())
+        return self
+
+    def optimize(self, iterations, cg_iterations, cg_tol=1e-8, robust_c=0.0, tol_t=1e-5, tol_r=1e-6):
+        """`iterations` rounds of linearize, gather and step, enqueued in one call -> self."""
+        self._call("tohip_posegraph_optimize", *self._graph(), int(iterations), int(cg_iterations), float(cg_tol), float(robust_c), float(tol_t),
+                   float(tol_r), *self._work())
+        return self
+
+    def result(self, out=None):
+        """-> (16 + 7 N + 2 E,) f64 on the device: the scalars (POSE_GRAPH_FIELDS), the current poses, chi^2 and the weight of every
+        edge at them.  out: a tensor to fill; it may be no input and not the workspace."""
+        if out is None:
+            out = torch.empty(POSE_GRAPH_SCALARS + 7 * self.n + 2 * self.e, dtype=torch.float64, device=self.device)
+        elif (not torch.is_tensor(out) or out.dtype != torch.float64 or out.numel() != POSE_GRAPH_SCALARS + 7 * self.n + 2 * self.e
+              or out.device != self.device or not out.is_contiguous()):
+            raise ValueError(f"PoseGraphProblem.result: out must be a contiguous ({POSE_GRAPH_SCALARS + 7 * self.n + 2 * self.e},) float64 tensor on "
+                             f"{self.device}")
+        check_pose_graph_buffers({"out": out}, dict(self.tensors, workspace=self.work))
+        self._call("tohip_posegraph_result", self.n, self.e, *self._work(), ptr(out))
+        return out
+
+    def region(self, name):
+        """A view of one region of the workspace (f64 words; the flags and the integers among the scalars are int64 by their bits)."""
+        i = POSE_GRAPH_REGIONS.index(name)
+        return self.work[self.off[name]:self.off[POSE_GRAPH_REGIONS[i + 1]]]
+
+
+class PoseGraphResult:
+    """What PoseGraph.optimize returns, numpy on the host: poses (N,3) and quats (N,4) wxyz, normalised once on the host; cost and
+    initial_cost, sum rho(s) at the result and at the start; iterations run, steps accepted and cg_iterations in total; status, a name
+    of POSE_GRAPH_STATUS (RUNNING: the iterations ran out); lam, the last lambda; chi2 (E,), s_k = e^T Omega e of every edge at the
+    result, and weights (E,), its IRLS weight (1 without robust=): a wrong closure shows as a large chi2 and a small weight."""
+    __slots__ = ("poses", "quats", "cost", "initial_cost", "iterations", "accepted", "cg_iterations", "status", "lam", "chi2", "weights")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def pose_graph_result(out, n_nodes, n_edges):
+    """The packed result ON THE HOST ((16 + 7 N + 2 E,) f64, PoseGraphProblem.result read back) -> PoseGraphResult."""
+    out = np.ascontiguousarray(np.asarray(out, dtype=np.float64).reshape(-1))
+    S, I, F = out[:POSE_GRAPH_SCALARS], out[:POSE_GRAPH_SCALARS].view(np.int64), POSE_GRAPH_FIELDS
+    nodes = out[POSE_GRAPH_SCALARS:POSE_GRAPH_SCALARS + 7 * n_nodes].reshape(n_nodes, 7)
+    rest = out[POSE_GRAPH_SCALARS + 7 * n_nodes:]
+    q = nodes[:, 3:7]
+    return PoseGraphResult(poses=nodes[:, :3].copy(), quats=q / np.sqrt((q * q).sum(axis=1, keepdims=True)), cost=float(S[F["cost"]]),
+                           initial_cost=float(S[F["initial_cost"]]), iterations=int(I[F["iterations"]]), accepted=int(I[F["accepted"]]),
+                           cg_iterations=int(I[F["cg_iterations"]]), status=POSE_GRAPH_STATUS[int(I[F["status"]])], lam=float(S[F["lam"]]),
+                           chi2=rest[:n_edges].copy(), weights=rest[n_edges:2 * n_edges].copy())
+
+
+def _quat_product(p, q):
+    """The Hamilton product of (…,4) wxyz arrays."""
+    pw, px, py, pz = np.moveaxis(np.asarray(p, dtype=np.float64), -1, 0)
+    qw, qx, qy, qz = np.moveaxis(np.asarray(q, dtype=np.float64), -1, 0)
+    return np.stack([pw * qw - px * qx - py * qy - pz * qz, pw * qx + px * qw + py * qz - pz * qy,
+                     pw * qy - px * qz + py * qw + pz * qx, pw * qz + px * qy - py * qx + pz * qw], axis=-1)
+
+
+class PoseGraph:
+    """A pose graph built on the host and optimised on the device ("Pose graph").  poses (N,3) metres and quats (N,4)
+    wxyz (any length but 0, either sign), the nodes; fixed: the indices of nodes that do not move.  Edges are appended with
+    add_edges, add_absolute and add_registration; their ORDER is part of the definition of every sum, so the same edges in the same
+    order give the same bits, however many calls appended them.  Building needs no GPU; linearize, gradient, cg, residuals and
+    optimize upload the graph (one copy) and run on `device`."""
+
+    def __init__(self, poses, quats, fixed=(), device="cuda"):
+        self.t = _host_rows(poses, 3, "poses")
+        self.q = _host_rows(quats, 4, "quats", rows=self.t.shape[0])
+        if not ((self.q * self.q).sum(axis=1) > 0.0).all():
+            raise ValueError("quats: a quaternion of length 0")
+        if not 1 <= len(self.t) <= POSE_GRAPH_MAX_NODES:
+            raise ValueError(f"the nodes must number 1 .. 2^22, got {len(self.t)}")
+        self.fixed = np.unique(np.asarray(list(fixed), dtype=np.int64).reshape(-1))
+        if len(self.fixed) and (self.fixed[0] < 0 or self.fixed[-1] >= len(self.t)):
+            raise ValueError(f"fixed: node {int(self.fixed[0] if self.fixed[0] < 0 else self.fixed[-1])} out of range for {len(self.t)} nodes")
+        self.device = torch.device(device)
+        self.ab = np.zeros((0, 2), dtype=np.int32)
+        self.meas = np.zeros((0, 7), dtype=np.float64)
+        self.omega = np.zeros((0, 21), dtype=np.float64)
+
+    n_nodes = property(lambda self: len(self.t))
+    n_edges = property(lambda self: len(self.ab))
+
+    def add_edges(self, a, b, t, q, information):
+        """Append E relative edges: a, b (E,) node indices (a = -1: an absolute edge), the measured d_t = R_a^T (t_b - t_a) (E,3) and d_q
+        = conj(q_a) (x) q_b (E,4) wxyz (any length but 0), and the information matrices (pose_graph_information) -> self."""
+        a, b = np.atleast_1d(np.asarray(a)), np.atleast_1d(np.asarray(b))
+        if a.ndim != 1 or a.shape != b.shape or a.dtype.kind not in "iu" or b.dtype.kind not in "iu" or len(a) == 0:
+            raise ValueError(f"a and b must be integer arrays of one length >= 1, got {a.shape} {a.dtype} and {b.shape} {b.dtype}")
+        n, e0 = self.n_nodes, self.n_edges
+        for bad, why in (((a < -1) | (a >= n) | (b < 0) | (b >= n), f"an index out of range for {n} nodes (a = -1 alone marks an absolute edge)"),
+                         (a == b, "a and b must differ")):
+            if bad.any():
+                k = int(np.flatnonzero(bad)[0])
+                raise ValueError(f"edge {e0 + k} = ({int(a[k])}, {int(b[k])}): {why}")
+        zt, zq = _host_rows(t, 3, "t", rows=len(a)), _host_rows(q, 4, "q", rows=len(a))
+        if not ((zq * zq).sum(axis=1) > 0.0).all():
+            raise ValueError("q: a quaternion of length 0")
+        om = pose_graph_information(information, len(a))
+        if e0 + len(a) > POSE_GRAPH_MAX_EDGES:
+            raise ValueError(f"the edges must number at most 2^22, got {e0 + len(a)}")
+        self.ab = np.concatenate([self.ab, np.stack([a, b], axis=1).astype(np.int32)])
+        self.meas = np.concatenate([self.meas, np.concatenate([zt, zq], axis=1)])
+        self.omega = np.concatenate([self.omega, om])
+        return self
+
+    def add_absolute(self, b, t, q, information):
+        """Append absolute edges: node b measured in the world at (t, q): e_t = t_b - t, e_r the Gibbs vector of q_b (x) conj(q) -> self."""
+        b = np.atleast_1d(np.asarray(b))
+        return self.add_edges(np.full(b.shape, -1, dtype=np.int64), b, t, q, information)
+
+    def add_registration(self, b, reg):
+        """Append register_scan's answer for node b as an absolute edge: the measurement reg.pose and reg.quat, the information
+        reg.information / sigma^2 with sigma^2 = reg.cost / (reg.used - n_dof), n_dof the degrees of freedom the registration moved
+        (the non-zero diagonal entries of reg.information) — the inverse of reg.covariance on them, with no change of frame: the edge's
+        parameterisation is the registration's.  A DEGENERATE or EMPTY registration, and one with no residual degrees of freedom or
+        no cost, is refused."""
+        if reg.status in ("DEGENERATE", "EMPTY"):
+            raise ValueError(f"add_registration: the registration of node {b} is {reg.status}: it measured nothing")
+        A = np.asarray(reg.information, dtype=np.float64)
+        n_dof = int((np.diag(A) != 0.0).sum())
+        if not (reg.used > n_dof and reg.cost > 0.0 and np.isfinite(reg.cost)):
+            raise ValueError(f"add_registration: node {b}: sigma^2 = cost / (used - n_dof) needs used > n_dof and a cost > 0, got used = {reg.used}, "
+                             f"n_dof = {n_dof}, cost = {reg.cost}")
+        sigma2 = float(reg.cost) / (int(reg.used) - n_dof)
+        return self.add_absolute([int(b)], reg.pose, reg.quat, A / sigma2)
+
+    def relative(self, a, b):
+        """The relative pose of node b seen from node a at the CURRENT nodes, in an edge's convention -> (d_t (3,), d_q (4,) wxyz,
+        normalised): what add_edges takes as a measurement, so that consecutive registered poses become odometry edges."""
+        qa = self.q[a] / np.sqrt((self.q[a] * self.q[a]).sum())
+        w, x, y, z = qa
+        R = np.asarray([[1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y)],
+                        [2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x)],
+                        [2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)]])
+        dq = _quat_product(qa * np.asarray([1.0, -1.0, -1.0, -1.0]), self.q[b])
+        return R.T @ (self.t[b] - self.t[a]), dq / np.sqrt((dq * dq).sum())
+
+    def check(self):
+        """check_pose_graph on this graph -> self."""
+        check_pose_graph(self.n_nodes, self.ab, self.fixed)
+        return self
+
+    def free_mask(self, dof="xyzrpw"):
+        m = np.full(self.n_nodes, scan_dof_mask(dof), dtype=np.int32)
+        m[self.fixed] = 0
+        return m
+
+    def arrays(self, dof="xyzrpw"):
+        """The seven host arrays a PoseGraphProblem takes, by PoseGraphProblem.NAMES."""
+        self.check()
+        row_ptr, incident = pose_graph_incidence(self.ab, self.n_nodes)
+        return dict(nodes=np.ascontiguousarray(np.concatenate([self.t, self.q], axis=1)), ab=self.ab, meas=self.meas, omega=self.omega, row_ptr=row_ptr,
+                    incident=incident, free_mask=self.free_mask(dof))
+
+    def upload(self, dof="xyzrpw"):
+        """-> PoseGraphProblem: the arrays packed into one host buffer, ONE copy to the device, and views of it."""
+        arrays = self.arrays(dof)
+        at, spans = 0, {}
+        for name, a in arrays.items():
+            spans[name] = (at, a.nbytes)
+            at += -(-a.nbytes // 8) * 8
+        host = np.zeros(at, dtype=np.uint8)
+        for name, a in arrays.items():
+            host[spans[name][0]:spans[name][0] + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+        dev = torch.from_numpy(host).to(self.device)
+        views = {name: dev[spans[name][0]:spans[name][0] + a.nbytes].view(torch.float64 if a.dtype == np.float64 else torch.int32).view(a.shape)
+                 for name, a in arrays.items()}
+        return PoseGraphProblem(**views)
+
+    # ---- the stages, one at a time: each starts from the graph's own nodes and reads its answer back
+
+    def linearize(self, dof="xyzrpw", robust=None):
+        """The edge records (E,100) f64 at the nodes (POSE_GRAPH_RECORD names the words), numpy."""
+        c = check_pose_graph_options(robust=robust)[3]
+        p = self.upload(dof).start().linearize(c)
+        return p.region("edges").view(2, self.n_edges, POSE_GRAPH_EDGE)[1].cpu().numpy()   # (nothing is current yet: the trial buffer is 1)
+
+    def residuals(self):
+        """-> (e (E,6), chi2 (E,)) at the nodes: each edge's residual and e^T Omega e."""
+        rec = self.linearize()
+        return rec[:, :6].copy(), rec[:, POSE_GRAPH_RECORD["s"]].copy()
+
+    def gradient(self, dof="xyzrpw", robust=None):
+        """-> (D (N,21), the upper triangle of each node's diagonal block of H; g (N,6); the cost), numpy, at the nodes."""
+        c = check_pose_graph_options(robust=robust)[3]
+        p = self.upload(dof).start().linearize(c).gather()
+        node = p.region("nodes").view(2, self.n_nodes, 27)[1].cpu().numpy()
+        return node[:, :21].copy(), node[:, 21:].copy(), float(p.region("trial_cost").cpu().numpy()[0])
+
+    def cg(self, cg_iterations=None, cg_tol=1e-8, dof="xyzrpw", robust=None, tol_t=1e-5, tol_r=1e-6):
+        """The first damped solve (lambda = 2^-10) at the nodes -> dict(x (N,6), iterations, status, small): one linearize, gather and
+        step."""
+        _, cg_iterations, cg_tol, c, tol_t, tol_r = check_pose_graph_options(None, cg_iterations, cg_tol, robust, tol_t, tol_r, self.n_nodes)
+        p = self.upload(dof).start().linearize(c).gather().step(cg_iterations, cg_tol, tol_t, tol_r)
+        S = p.region("scalars").cpu().numpy()[POSE_GRAPH_SCALARS:2 * POSE_GRAPH_SCALARS].view(np.int64)
+        return dict(x=p.region("x").view(self.n_nodes, 6).cpu().numpy(), iterations=int(S[POSE_GRAPH_FIELDS["cg_iterations"]]),
+                    status=POSE_GRAPH_STATUS[int(S[POSE_GRAPH_FIELDS["status"]])],
+                    small=bool((p.region("small_flags").cpu().numpy().view(np.int64) != 0).all()))
+
+    def optimize(self, iterations=30, cg_iterations=None, cg_tol=1e-8, dof="xyzrpw", robust=None, tol_t=1e-5, tol_r=1e-6):
+        """Levenberg-Marquardt from the nodes -> PoseGraphResult.  iterations: 1 .. 256 outer iterations, each one linearisation, one
+        gather and one damped solve by block-Jacobi conjugate gradients of at most cg_iterations (None: min(6 N, 1000), a default,
+        not a measurement) steps, stopped at r.z <= cg_tol^2 (r.z)_0.  dof: the degrees of freedom that move, register_scan's
+        ('xyw' for a planar robot).  robust: None, or Geman-McClure's c (in units of sqrt(chi^2)): an edge with s >> c^2 loses its
+        say.  CONVERGED: an accepted step within tol_t metres and tol_r radians on every node.  One upload, launches only, one
+        read-back.  The graph's own nodes are not modified."""
+        iterations, cg_iterations, cg_tol, c, tol_t, tol_r = check_pose_graph_options(iterations, cg_iterations, cg_tol, robust, tol_t, tol_r,
+                                                                                     self.n_nodes)
+        p = self.upload(dof).start().optimize(iterations, cg_iterations, cg_tol, c, tol_t, tol_r)
+        return pose_graph_result(p.result().cpu().numpy(), self.n_nodes, self.n_edges)
+
+
 SCAN_SEARCH_MAX_WINDOW = (2048, 2048, 4)
 SCAN_SEARCH_MAX_LEVELS = 6
 SCAN_SEARCH_MAX_CAPACITY = 1 << 24

@@ -2420,3 +2420,594 @@ def scan_register_ref(L, origin, resolution, points, poses, quats, iterations=30
                 poses12[b] = row
     return state
 
+
+
+# ---- pose-graph optimisation restated in numpy ("Pose graph"): what posegraph_kernels.hip must give, bit for bit.  All
+# ---- of it is f64 add, subtract, multiply, divide and compare, elementwise over the edges or the nodes, in ONE order:
+#   a product of two 6 x 6 blocks, and a block times a vector, sums its six terms in ascending index, left to right, from the first
+#     product (no leading zero);
+#   a node's sums over its incident edges start at 0.0 and add the edges in ascending edge index (pose_graph_incidence);
+#   a sum over the nodes (a dot product: the node's six products left to right first) or over the edges (the cost) is a halving tree
+#     over each block of 256 (v[i] += v[i + m], m = 128, 64 .. 1; the last block padded with 0.0), then the block partials from 0.0 in
+#     ascending block order (pose_graph_tree_sum).
+POSEGRAPH_EDGE = 100         # f64 words of an edge's record
+# the record's words: e (6), s = e^T Omega e, the IRLS weight w, rho(s), 0, then with W = w Omega the upper triangles of Ja^T W Ja and
+# Jb^T W Jb (21 each, row-major), Ja^T W Jb (36, row-major), Ja^T W e and Jb^T W e (6 each)
+PG_E, PG_S, PG_W, PG_RHO, PG_HAA, PG_HBB, PG_HAB, PG_GA, PG_GB = 0, 6, 7, 8, 10, 31, 52, 88, 94
+POSEGRAPH_STATUS = ("RUNNING", "CONVERGED", "STALLED", "DEGENERATE", "NONFINITE")
+POSEGRAPH_LAMBDA0 = 2.0 ** -10
+POSEGRAPH_BLOCK = 256
+POSEGRAPH_MAX_NODES = POSEGRAPH_MAX_EDGES = 1 << 22
+_PG_TRIU = [(i, j) for i in range(6) for j in range(i, 6)]
+
+
+def pose_graph_tree_sum(v):
+    """The one order of a sum over nodes or edges -> a Python float: halving trees over blocks of 256, then the partials ascending."""
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    nb = max(1, -(-len(v) // POSEGRAPH_BLOCK))
+    w = np.zeros(nb * POSEGRAPH_BLOCK, dtype=np.float64)
+    w[:len(v)] = v
+    w = w.reshape(nb, POSEGRAPH_BLOCK)
+    m = POSEGRAPH_BLOCK // 2
+    with np.errstate(all="ignore"):
+        while m >= 1:
+            w[:, :m] = w[:, :m] + w[:, m:2 * m]
+            m //= 2
+        total = 0.0
+        for b in range(nb):
+            total = total + float(w[b, 0])
+    return total
+
+
+def pose_graph_incidence(ab, n):
+    """Edges (E,2) int32, a = -1 an absolute edge -> (row_ptr (n+1,) int32, incident int32): node i's entries are
+    incident[row_ptr[i]:row_ptr[i+1]], each 2 edge + side (side 0: the node is the edge's a, 1: its b), in ascending edge index."""
+    ab = np.asarray(ab, dtype=np.int64).reshape(-1, 2)
+    node = ab.reshape(-1)                                   # entry 2 k + side
+    code = np.arange(len(node), dtype=np.int64)
+    keep = node >= 0
+    node, code = node[keep], code[keep]
+    order = np.argsort(node, kind="stable")                 # (stable: ascending code, so ascending edge, within a node)
+    row_ptr = np.zeros(n + 1, dtype=np.int64)
+    np.add.at(row_ptr, node + 1, 1)
+    return np.cumsum(row_ptr).astype(np.int32), code[order].astype(np.int32)
+
+
+def _pg_qmul(p, q):
+    """The Hamilton product p (x) q of two quaternions given as 4 arrays each, in k_scan_step's operation order."""
+    pw, px, py, pz = p
+    qw, qx, qy, qz = q
+    return (((pw * qw - px * qx) - py * qy) - pz * qz,
+            ((pw * qx + px * qw) + py * qz) - pz * qy,
+            ((pw * qy - px * qz) + py * qw) + pz * qx,
+            ((pw * qz + px * qy) - py * qx) + pz * qw)
+
+
+def _pg_rot(q):
+    """R of an unnormalised quaternion, s = 2 / (q . q): scan_pose12_ref's rule, as 3 x 3 arrays in f64."""
+    w, x, y, z = q
+    s = 2.0 / (((w * w + x * x) + y * y) + z * z)
+    return [[1.0 - s * (y * y + z * z), s * (x * y - w * z), s * (x * z + w * y)],
+            [s * (x * y + w * z), 1.0 - s * (x * x + z * z), s * (y * z - w * x)],
+            [s * (x * z - w * y), s * (y * z + w * x), 1.0 - s * (x * x + y * y)]]
+
+
+def pose_graph_perturb_ref(t, q, x):
+    """Nodes (N,3), (N,4) moved by x (N,6): t + dt and (1, dr / 2) (x) q, k_scan_step's perturbation -> (t, q)."""
+    t, q, x = (np.asarray(v, dtype=np.float64) for v in (t, q, x))
+    with np.errstate(all="ignore"):
+        nq = _pg_qmul((1.0, 0.5 * x[:, 3], 0.5 * x[:, 4], 0.5 * x[:, 5]), (q[:, 0], q[:, 1], q[:, 2], q[:, 3]))
+        return t + x[:, :3], np.stack(nq, axis=1)
+
+
+def _pg_edges(t, q, ab, zt, zq):
+    """-> (e [6], R [3][3] of node a, v [3] = t_b - t_a), arrays over the edges.  An absolute edge (a = -1) is an edge from the world
+    frame, t = 0 and q = (1, 0, 0, 0): then d_t = t_b and d_q = q_b exactly."""
+    t, q = np.asarray(t, dtype=np.float64).reshape(-1, 3), np.asarray(q, dtype=np.float64).reshape(-1, 4)
+    ab = np.asarray(ab, dtype=np.int64).reshape(-1, 2)
+    zt, zq = np.asarray(zt, dtype=np.float64).reshape(-1, 3), np.asarray(zq, dtype=np.float64).reshape(-1, 4)
+    a, b = ab[:, 0], ab[:, 1]
+    world = a < 0
+    ta = np.where(world[:, None], 0.0, t[np.maximum(a, 0)])
+    qa = np.where(world[:, None], np.asarray([1.0, 0.0, 0.0, 0.0]), q[np.maximum(a, 0)])
+    tb, qb = t[b], q[b]
+    R = _pg_rot(qa.T)
+    v = [tb[:, k] - ta[:, k] for k in range(3)]
+    e = [((R[0][i] * v[0] + R[1][i] * v[1]) + R[2][i] * v[2]) - zt[:, i] for i in range(3)]
+    dq = _pg_qmul((qa[:, 0], -qa[:, 1], -qa[:, 2], -qa[:, 3]), qb.T)
+    eps = _pg_qmul(dq, (zq[:, 0], -zq[:, 1], -zq[:, 2], -zq[:, 3]))
+    e += [(2.0 * eps[k]) / eps[0] for k in (1, 2, 3)]
+    return e, R, v
+
+
+def pose_graph_residual_ref(t, q, ab, zt, zq):
+    """The residuals (E,6) of the edges at the nodes (t (N,3), q (N,4) wxyz, not normalised): e_t = R_a^T (t_b - t_a) - z_t and the
+    Gibbs vector e_r = 2 vec(eps) / w(eps) of eps = conj(q_a) (x) q_b (x) conj(z_q).  w(eps) = 0 gives a non-finite entry."""
+    with np.errstate(all="ignore"):
+        return np.stack(_pg_edges(t, q, ab, zt, zq)[0], axis=1)
+
+
+def _pg_jacobians(e, R, v):
+    """The exact first derivatives of e in (dt, dr) of node a and of node b -> (Ja, Jb) as 6 x 6 lists of arrays (a Python 0.0 where
+    the entry is structurally zero).  With G = I - [e_r / 2]x + (e_r / 2)(e_r / 2)^T:
+        Jb = [[R^T, 0], [0, G R^T]],   Ja = [[-R^T, R^T [v]x], [0, -G R^T]]."""
+    h = [0.5 * e[3], 0.5 * e[4], 0.5 * e[5]]
+    G = [[1.0 + h[0] * h[0], h[0] * h[1] + h[2], h[0] * h[2] - h[1]],
+         [h[1] * h[0] - h[2], 1.0 + h[1] * h[1], h[1] * h[2] + h[0]],
+         [h[2] * h[0] + h[1], h[2] * h[1] - h[0], 1.0 + h[2] * h[2]]]
+    GR = [[(G[i][0] * R[j][0] + G[i][1] * R[j][1]) + G[i][2] * R[j][2] for j in range(3)] for i in range(3)]
+    Ja = [[0.0] * 6 for _ in range(6)]
+    Jb = [[0.0] * 6 for _ in range(6)]
+    for i in range(3):
+        for j in range(3):
+            Jb[i][j] = R[j][i]
+            Ja[i][j] = -R[j][i]
+            Jb[3 + i][3 + j] = GR[i][j]
+            Ja[3 + i][3 + j] = -GR[i][j]
+        Ja[i][3] = R[1][i] * v[2] - R[2][i] * v[1]
+        Ja[i][4] = R[2][i] * v[0] - R[0][i] * v[2]
+        Ja[i][5] = R[0][i] * v[1] - R[1][i] * v[0]
+    return Ja, Jb
+
+
+def pose_graph_jacobians_ref(t, q, ab, zt, zq):
+    """-> (Ja (E,6,6), Jb (E,6,6)), unmasked: what pose_graph_linearize_ref multiplies out.  Ja of an absolute edge is the derivative
+    in the world frame's own motion, which nothing uses."""
+    with np.errstate(all="ignore"):
+        e, R, v = _pg_edges(t, q, ab, zt, zq)
+        Ja, Jb = _pg_jacobians(e, R, v)
+    E = len(e[0])
+    full = lambda J: np.stack([np.stack([np.broadcast_to(np.asarray(J[i][j], dtype=np.float64), (E,)) for j in range(6)], axis=1)   # noqa: E731
+                               for i in range(6)], axis=1)
+    return full(Ja), full(Jb)
+
+
+def pose_graph_omega_full(omega):
+    """(E,21) upper triangles, row-major -> (E,6,6) symmetric."""
+    omega = np.asarray(omega, dtype=np.float64).reshape(-1, 21)
+    O = np.zeros((len(omega), 6, 6))
+    for n, (i, j) in enumerate(_PG_TRIU):
+        O[:, i, j] = O[:, j, i] = omega[:, n]
+    return O
+
+
+def pose_graph_free_masks(n, fixed=(), dof=63):
+    """-> (n,) int32: a node's free degrees of freedom, scan_dof_mask(dof), 0 for a fixed node."""
+    m = np.full(n, scan_dof_mask(dof), dtype=np.int32)
+    m[np.asarray(list(fixed), dtype=np.int64)] = 0
+    return m
+
+
+def _pg_dot6(A, x):
+    """sum_k A[k] x[k], ascending k from the first product."""
+    acc = A[0] * x[0]
+    for k in range(1, 6):
+        acc = acc + A[k] * x[k]
+    return acc
+
+
+def pose_graph_linearize_ref(t, q, ab, zt, zq, omega, free_mask, robust=None):
+    """The edge records (E,100) at the nodes: e, s = e^T Omega e (u = Omega e first, each row ascending; then e . u), the weight
+    w (1.0, or (c^2 / (c^2 + s))^2 with robust=c), rho(s) (s, or c^2 s / (c^2 + s)), and with W = w Omega and the columns of Ja and Jb
+    of LOCKED degrees of freedom (free_mask; every one of the world frame's) set to 0.0: M_a = W Ja, M_b = W Jb, u_w = W e, then
+    Ja^T M_a and Jb^T M_b (upper triangles), Ja^T M_b, Ja^T u_w and Jb^T u_w."""
+    ab = np.asarray(ab, dtype=np.int64).reshape(-1, 2)
+    free_mask = np.asarray(free_mask, dtype=np.int64)
+    E = len(ab)
+    rec = np.zeros((E, POSEGRAPH_EDGE), dtype=np.float64)
+    if E == 0:
+        return rec
+    with np.errstate(all="ignore"):
+        e, R, v = _pg_edges(t, q, ab, zt, zq)
+        Ja, Jb = _pg_jacobians(e, R, v)
+        O = pose_graph_omega_full(omega)
+        Om = [[O[:, i, j] for j in range(6)] for i in range(6)]
+        u = [_pg_dot6(Om[i], e) for i in range(6)]
+        s = _pg_dot6(e, u)
+        if robust is None:
+            w, rho = np.ones(E), s
+        else:
+            c2 = float(robust) * float(robust)
+            f = c2 / (c2 + s)
+            w, rho = f * f, (c2 * s) / (c2 + s)
+        ma = np.where(ab[:, 0] >= 0, free_mask[np.maximum(ab[:, 0], 0)], 0)
+        mb = free_mask[ab[:, 1]]
+        zero = np.zeros(E)
+        for J, m in ((Ja, ma), (Jb, mb)):
+            for c in range(6):
+                on = ((m >> c) & 1).astype(bool)
+                for r in range(6):
+                    J[r][c] = np.where(on, J[r][c], zero)
+        W = [[w * Om[i][j] for j in range(6)] for i in range(6)]
+        col = lambda J, j: [J[k][j] for k in range(6)]                                     # noqa: E731
+        Ma = [[_pg_dot6(W[i], col(Ja, j)) for j in range(6)] for i in range(6)]
+        Mb = [[_pg_dot6(W[i], col(Jb, j)) for j in range(6)] for i in range(6)]
+        uw = [_pg_dot6(W[i], e) for i in range(6)]
+        for k in range(6):
+            rec[:, PG_E + k] = e[k]
+            rec[:, PG_GA + k] = _pg_dot6(col(Ja, k), uw)
+            rec[:, PG_GB + k] = _pg_dot6(col(Jb, k), uw)
+        rec[:, PG_S], rec[:, PG_W], rec[:, PG_RHO] = s, w, rho
+        for n, (i, j) in enumerate(_PG_TRIU):
+            rec[:, PG_HAA + n] = _pg_dot6(col(Ja, i), col(Ma, j))
+            rec[:, PG_HBB + n] = _pg_dot6(col(Jb, i), col(Mb, j))
+        for i in range(6):
+            for j in range(6):
+                rec[:, PG_HAB + 6 * i + j] = _pg_dot6(col(Ja, i), col(Mb, j))
+    return rec
+
+
+def pose_graph_gather_ref(rec, ab, n, free_mask):
+    """-> (D (n,21), the upper triangle of each node's diagonal block of H; g (n,6); cost): a node's sums over its incident edges from
+    0.0 in ascending edge index (Ja^T W Ja and Ja^T W e where it is the edge's a, Jb^T W Jb and Jb^T W e where it is its b); then a
+    locked degree of freedom's row and column are 0.0 with 1.0 on the diagonal, and its g is 0.0.  cost: the tree sum of rho."""
+    rec = np.asarray(rec, dtype=np.float64).reshape(-1, POSEGRAPH_EDGE)
+    row_ptr, inc = pose_graph_incidence(ab, n)
+    free_mask = np.asarray(free_mask, dtype=np.int64)
+    D, g = np.zeros((n, 21)), np.zeros((n, 6))
+    deg = np.diff(row_ptr)
+    with np.errstate(all="ignore"):
+        for s in range(int(deg.max()) if n else 0):
+            nodes = np.flatnonzero(deg > s)
+            code = inc[row_ptr[nodes] + s].astype(np.int64)
+            k, side = code >> 1, (code & 1).astype(bool)
+            D[nodes] = D[nodes] + np.where(side[:, None], rec[k, PG_HBB:PG_HBB + 21], rec[k, PG_HAA:PG_HAA + 21])
+            g[nodes] = g[nodes] + np.where(side[:, None], rec[k, PG_GB:PG_GB + 6], rec[k, PG_GA:PG_GA + 6])
+    for m, (i, j) in enumerate(_PG_TRIU):
+        locked = (((free_mask >> i) & 1) == 0) | (((free_mask >> j) & 1) == 0)
+        D[locked, m] = 1.0 if i == j else 0.0
+    for i in range(6):
+        g[((free_mask >> i) & 1) == 0, i] = 0.0
+    return D, g, pose_graph_tree_sum(rec[:, PG_RHO])
+
+
+def pose_graph_factor_ref(D, lam, free_mask):
+    """Each node's damped block, A_ii += lam A_ii on its free degrees of freedom, factored L d L^T in scan_solve_ref's order ->
+    (L (n,6,6) strictly lower, d (n,6), ok (n,) bool: every pivot > 0 and finite)."""
+    D = np.asarray(D, dtype=np.float64).reshape(-1, 21)
+    free_mask = np.asarray(free_mask, dtype=np.int64)
+    n = len(D)
+    A = [[None] * 6 for _ in range(6)]
+    for m, (i, j) in enumerate(_PG_TRIU):
+        A[i][j] = A[j][i] = D[:, m]
+    with np.errstate(all="ignore"):
+        for i in range(6):
+            A[i][i] = np.where((free_mask >> i) & 1, A[i][i] + lam * A[i][i], A[i][i])
+        L, d, ok = np.zeros((n, 6, 6)), np.zeros((n, 6)), np.ones(n, dtype=bool)
+        for j in range(6):
+            v = A[j][j]
+            for k in range(j):
+                v = v - L[:, j, k] * (L[:, j, k] * d[:, k])
+            ok &= (v > 0.0) & (v < math.inf)
+            d[:, j] = v
+            for i in range(j + 1, 6):
+                u = A[i][j]
+                for k in range(j):
+                    u = u - L[:, i, k] * (L[:, j, k] * d[:, k])
+                L[:, i, j] = u / v
+    return L, d, ok
+
+
+def pose_graph_block_solve_ref(L, d, r):
+    """z = (L d L^T)^-1 r per node, scan_solve_ref's forward and back substitution."""
+    n = len(r)
+    y, z = np.zeros((n, 6)), np.zeros((n, 6))
+    with np.errstate(all="ignore"):
+        for i in range(6):
+            v = r[:, i]
+            for k in range(i):
+                v = v - L[:, i, k] * y[:, k]
+            y[:, i] = v
+        for i in range(5, -1, -1):
+            v = y[:, i] / d[:, i]
+            for k in range(i + 1, 6):
+                v = v - L[:, k, i] * z[:, k]
+            z[:, i] = v
+    return z
+
+
+def _pg_node_dot(a, b):
+    """sum over the nodes of a_i . b_i: six products left to right, then the tree."""
+    acc = a[:, 0] * b[:, 0]
+    for k in range(1, 6):
+        acc = acc + a[:, k] * b[:, k]
+    return pose_graph_tree_sum(acc)
+
+
+def pose_graph_matvec_plan(D, rec, ab, lam, free_mask):
+    """-> matvec(p (n,6)) -> (n,6), (H + lam diag H) p by node rows: the node's own damped block first (row r: sum_c A[r][c] p[c],
+    ascending c), then its incident edges in ascending edge index, each adding B p_other (B = Ja^T W Jb where the node is a, its
+    transpose where it is b; the six terms ascending, summed before they are added; an absolute edge has no such block).  What does
+    not depend on p is laid out once."""
+    n = len(D)
+    ab = np.asarray(ab, dtype=np.int64).reshape(-1, 2)
+    free_mask = np.asarray(free_mask, dtype=np.int64)
+    row_ptr, inc = pose_graph_incidence(ab, n)
+    deg = np.diff(row_ptr)
+    A = [[None] * 6 for _ in range(6)]
+    for m, (i, j) in enumerate(_PG_TRIU):
+        A[i][j] = A[j][i] = D[:, m]
+    with np.errstate(all="ignore"):
+        for i in range(6):
+            A[i][i] = np.where((free_mask >> i) & 1, A[i][i] + lam * A[i][i], A[i][i])
+    slots = []
+    for s in range(int(deg.max()) if n else 0):
+        nodes = np.flatnonzero(deg > s)
+        code = inc[row_ptr[nodes] + s].astype(np.int64)
+        k, side = code >> 1, (code & 1).astype(bool)
+        keep = ab[k, 0] >= 0
+        nodes, k, side = nodes[keep], k[keep], side[keep]
+        B = rec[k, PG_HAB:PG_HAB + 36].reshape(-1, 6, 6)
+        rows = [[np.where(side, B[:, c, r], B[:, r, c]) for c in range(6)] for r in range(6)]
+        slots.append((nodes, np.where(side, ab[k, 0], ab[k, 1]), rows))
+
+    def matvec(p):
+        out = np.zeros((n, 6))
+        with np.errstate(all="ignore"):
+            pc = [p[:, c] for c in range(6)]
+            for r in range(6):
+                out[:, r] = _pg_dot6(A[r], pc)
+            for nodes, other, rows in slots:
+                po = [p[other, c] for c in range(6)]
+                for r in range(6):
+                    out[nodes, r] = out[nodes, r] + _pg_dot6(rows[r], po)
+        return out
+    return matvec
+
+
+def pose_graph_matvec_ref(D, rec, ab, lam, free_mask, p):
+    """(H + lam diag H) p -> (n,6): pose_graph_matvec_plan's product, once."""
+    return pose_graph_matvec_plan(D, rec, ab, lam, free_mask)(np.asarray(p, dtype=np.float64))
+
+
+def pose_graph_cg_ref(D, g, rec, ab, lam, free_mask, cg_iterations, cg_tol=1e-8, tol_t=0.0, tol_r=0.0):
+    """One damped solve (H + lam diag H) x = -g by preconditioned conjugate gradients from x = 0, the preconditioner the L d L^T of each
+    damped diagonal block -> dict(x (n,6), iterations, degenerate, small).  r = 0.0 - g, z = M^-1 r, then per iteration: rz = r . z
+    (rz0 the first); stop if rz <= cg_tol^2 rz0; beta = 0.0 the first time, rz / the previous rz after; p = z + beta p (p = 0 before);
+    Ap; pAp = p . Ap; stop, keeping x, unless pAp > 0; alpha = rz / pAp; x = x + alpha p; r = r - alpha Ap; z = M^-1 r.  small: every
+    |x| within tol_t (translation) and tol_r (rotation).  degenerate: a block pivot <= 0 or not finite: nothing is solved."""
+    n = len(D)
+    g = np.asarray(g, dtype=np.float64).reshape(n, 6)
+    L, d, ok = pose_graph_factor_ref(D, lam, free_mask)
+    x = np.zeros((n, 6))
+    out = dict(x=x, iterations=0, degenerate=not bool(ok.all()), small=True)
+    if out["degenerate"]:
+        return out
+    tol2 = float(cg_tol) * float(cg_tol)
+    tol = np.asarray([tol_t] * 3 + [tol_r] * 3, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        r = 0.0 - g
+        z = pose_graph_block_solve_ref(L, d, r)
+        p = np.zeros((n, 6))
+        rz_prev = rz0 = 0.0
+        matvec = pose_graph_matvec_plan(D, rec, ab, lam, free_mask)
+        for k in range(int(cg_iterations)):
+            rz = _pg_node_dot(r, z)
+            if k == 0:
+                rz0, beta = rz, 0.0
+            else:
+                beta = rz / rz_prev
+            if rz <= tol2 * rz0:
+                break
+            rz_prev = rz
+            p = z + beta * p
+            Ap = matvec(p)
+            pAp = _pg_node_dot(p, Ap)
+            if not pAp > 0.0:
+                break
+            alpha = rz / pAp
+            x = x + alpha * p
+            r = r - alpha * Ap
+            z = pose_graph_block_solve_ref(L, d, r)
+            out["iterations"] += 1
+            out["small"] = bool(((x <= tol) & (-x <= tol)).all())
+    out["x"] = x
+    return out
+
+
+def pose_graph_start_ref(t, q):
+    """The optimiser's state at its start, a dict: the current nodes t, q; the pending step x = 0; lam = 2^-10; status RUNNING (0);
+    iterations, accepted, cg_iterations 0; cost and initial_cost 0.0; small True; rec, D, g None until the first acceptance."""
+    t = np.array(t, dtype=np.float64).reshape(-1, 3)
+    q = np.array(q, dtype=np.float64).reshape(-1, 4)
+    return dict(t=t, q=q, x=np.zeros((len(t), 6)), lam=POSEGRAPH_LAMBDA0, status=0, iterations=0, accepted=0, cg_iterations=0, cost=0.0,
+                initial_cost=0.0, small=True, rec=None, D=None, g=None)
+
+
+def pose_graph_step_ref(state, ab, zt, zq, omega, free_mask, cg_iterations, cg_tol=1e-8, robust=None, tol_t=1e-5, tol_r=1e-6):
+    """One outer iteration, in place: linearise at the TRIAL nodes (the current ones moved by x), gather, then k_scan_step's state
+    machine — a non-finite trial cost: NONFINITE; the first trial, or one whose cost is strictly lower: accepted (the trial becomes
+    current; after the first: accepted + 1, lam = max(lam / 8, 2^-30), CONVERGED if the step was small); otherwise lam = 8 lam,
+    STALLED past 2^30 — and the next damped solve by pose_graph_cg_ref (DEGENERATE from it).  A state that is not RUNNING is left."""
+    st = state
+    if st["status"] != 0:
+        return st
+    n = len(st["t"])
+    first = st["iterations"] == 0
+    st["iterations"] += 1
+    tt, tq = pose_graph_perturb_ref(st["t"], st["q"], st["x"])
+    rec = pose_graph_linearize_ref(tt, tq, ab, zt, zq, omega, free_mask, robust)
+    D, g, cost = pose_graph_gather_ref(rec, ab, n, free_mask)
+    if not cost < math.inf:
+        st["status"] = 4
+        return st
+    if first or cost < st["cost"]:
+        st.update(t=tt, q=tq, rec=rec, D=D, g=g, cost=cost)
+        if first:
+            st["initial_cost"] = cost
+        else:
+            st["accepted"] += 1
+            lam = st["lam"] / 8.0
+            st["lam"] = lam if lam > SCANREG_LAMBDA_MIN else SCANREG_LAMBDA_MIN
+            if st["small"]:
+                st["status"] = 1
+                return st
+    else:
+        st["lam"] = st["lam"] * 8.0
+        if st["lam"] > SCANREG_LAMBDA_MAX:
+            st["status"] = 2
+            return st
+    cg = pose_graph_cg_ref(st["D"], st["g"], st["rec"], ab, st["lam"], free_mask, cg_iterations, cg_tol, tol_t, tol_r)
+    st["x"] = cg["x"]                        # (all zero where the solve is degenerate: the kernels clear x before they factor)
+    if cg["degenerate"]:
+        st["status"] = 3
+        return st
+    st["small"] = cg["small"]
+    st["cg_iterations"] += cg["iterations"]
+    return st
+
+
+def pose_graph_default_cg(n):
+    return min(6 * int(n), 1000)
+
+
+def pose_graph_optimize_ref(t, q, ab, zt, zq, omega, fixed=(), iterations=30, cg_iterations=None, cg_tol=1e-8, dof=63, robust=None, tol_t=1e-5,
+                            tol_r=1e-6, snapshots=()):
+    """`iterations` outer iterations from the starting nodes -> the state (pose_graph_start_ref's dict; chi2 = rec[:, 6] and weights =
+    rec[:, 7] at the result).  With snapshots, a tuple of iteration counts: {count: a copy of the state after that many}, the last
+    included, from one run."""
+    import copy
+    t = np.asarray(t, dtype=np.float64).reshape(-1, 3)
+    free_mask = pose_graph_free_masks(len(t), fixed, dof)
+    cg_iterations = pose_graph_default_cg(len(t)) if cg_iterations is None else int(cg_iterations)
+    st = pose_graph_start_ref(t, q)
+    shots = {}
+    for it in range(1, int(iterations) + 1):
+        pose_graph_step_ref(st, ab, zt, zq, omega, free_mask, cg_iterations, cg_tol, robust, tol_t, tol_r)
+        if it in snapshots:
+            shots[it] = copy.deepcopy(st)
+    return shots if snapshots else st
+
+
+def pose_graph_dense_ref(t, q, ab, zt, zq, omega, fixed=(), iterations=30, dof=63, robust=None, tol_t=1e-5, tol_r=1e-6):
+    """The same Levenberg-Marquardt on a dense H, assembled with numpy's matrix products from pose_graph_jacobians_ref and solved with
+    np.linalg.solve: the independent check of the block-sparse path (no fixed order, no conjugate gradients) -> dict(t, q, cost,
+    initial_cost, iterations, accepted, status, lam)."""
+    t = np.array(t, dtype=np.float64).reshape(-1, 3)
+    q = np.array(q, dtype=np.float64).reshape(-1, 4)
+    ab = np.asarray(ab, dtype=np.int64).reshape(-1, 2)
+    n = len(t)
+    free = np.concatenate([[(int(m) >> i) & 1 for i in range(6)] for m in pose_graph_free_masks(n, fixed, dof)]).astype(bool)
+    O = pose_graph_omega_full(omega)
+
+    def evaluate(t, q):
+        e = pose_graph_residual_ref(t, q, ab, zt, zq)
+        Ja, Jb = pose_graph_jacobians_ref(t, q, ab, zt, zq)
+        s = np.einsum("ki,kij,kj->k", e, O, e)
+        if robust is None:
+            w, rho = np.ones(len(s)), s
+        else:
+            c2 = float(robust) ** 2
+            w, rho = (c2 / (c2 + s)) ** 2, c2 * s / (c2 + s)
+        H, g = np.zeros((6 * n, 6 * n)), np.zeros(6 * n)
+        W = w[:, None, None] * O
+        JW = {side: np.einsum("kji,kjl->kil", J, W) for side, J in ((0, Ja), (1, Jb))}             # J^T W per edge
+        for k, (a, b) in enumerate(ab):
+            blocks = [(b, 1, Jb[k])] + ([(a, 0, Ja[k])] if a >= 0 else [])
+            for i, si, _ in blocks:
+                g[6 * i:6 * i + 6] += JW[si][k] @ e[k]
+                for j, _, Jj in blocks:
+                    H[6 * i:6 * i + 6, 6 * j:6 * j + 6] += JW[si][k] @ Jj
+        return float(rho.sum()), H, g
+
+    lam, status, accepted, x = POSEGRAPH_LAMBDA0, 0, 0, np.zeros(6 * n)
+    cost = initial = 0.0
+    H = g = None
+    done = 0
+    for it in range(int(iterations)):
+        done += 1
+        tt, tq = pose_graph_perturb_ref(t, q, x.reshape(n, 6))
+        c, Ht, gt = evaluate(tt, tq)
+        if not np.isfinite(c):
+            status = 4
+            break
+        if it == 0 or c < cost:
+            t, q, cost, H, g = tt, tq, c, Ht, gt
+            if it == 0:
+                initial = c
+            else:
+                accepted += 1
+                lam = max(lam / 8.0, SCANREG_LAMBDA_MIN)
+                xs = np.abs(x.reshape(n, 6))
+                if (xs[:, :3] <= tol_t).all() and (xs[:, 3:] <= tol_r).all():
+                    status = 1
+                    break
+        else:
+            lam *= 8.0
+            if lam > SCANREG_LAMBDA_MAX:
+                status = 2
+                break
+        A = H + lam * np.diag(np.diag(H))
+        x = np.zeros(6 * n)
+        sub = A[np.ix_(free, free)]
+        try:
+            x[free] = np.linalg.solve(sub, -g[free])
+        except np.linalg.LinAlgError:
+            status = 3
+            break
+    return dict(t=t, q=q, cost=cost, initial_cost=initial, iterations=done, accepted=accepted, status=status, lam=lam)
+
+
+def _quat_mul_np(p, q):
+    return np.stack(_pg_qmul(tuple(np.asarray(p, dtype=np.float64).T), tuple(np.asarray(q, dtype=np.float64).T)), axis=-1)
+
+
+def pose_graph_relative_ref(ta, qa, tb, qb):
+    """The relative pose of b seen from a in an edge's convention: (R_a^T (t_b - t_a), conj(q_a) (x) q_b normalised)."""
+    qa, qb = np.asarray(qa, dtype=np.float64), np.asarray(qb, dtype=np.float64)
+    R = np.asarray(_pg_rot(tuple(qa.T)))
+    if R.ndim == 3:
+        R = np.moveaxis(R, -1, 0)
+    d = np.asarray(tb, dtype=np.float64) - np.asarray(ta, dtype=np.float64)
+    dt = np.einsum("...ji,...j->...i", R, d)
+    dq = _quat_mul_np(qa * np.asarray([1.0, -1.0, -1.0, -1.0]), qb)
+    return dt, dq / np.sqrt((dq * dq).sum(axis=-1, keepdims=True))
+
+
+def pose_graph_loop(n, laps=1, sigma_t=0.02, sigma_r=0.01, closures=4, seed=0, radius=5.0):
+    """A ground-truth loop with drifting odometry and closure edges -> dict(truth_t (N,3), truth_q (N,4), t (N,3), q (N,4): the
+    dead-reckoned start; ab (E,2) int32, zt (E,3), zq (E,4), omega (E,21), n_odometry): N = n laps nodes on a circle of `radius` in the
+    plane z = 0, heading along the tangent, with a gentle roll and pitch so that all six degrees of freedom are exercised; N - 1 odometry
+    edges, each the true relative pose with Gaussian noise (sigma_t metres, sigma_r radians per axis) AND a constant bias of sigma_t / 2 in
+    x and sigma_r / 2 in yaw, the drift; `closures` edges of the true relative pose with a fifth of the noise, between node i and node
+    i + n (laps - 1) (the same place on the last lap; with laps = 1 between the start's and the end's neighbourhoods).  Omega is
+    diag(1 / sigma^2) of each edge's own noise.  Node 0 is exact: fix it."""
+    rng = np.random.default_rng(seed)
+    N = int(n) * int(laps)
+    ang = 2.0 * np.pi * np.arange(N) / n
+    truth_t = np.stack([radius * np.cos(ang), radius * np.sin(ang), 0.2 * np.sin(2.0 * ang)], axis=1)
+    yaw, roll, pitch = ang + np.pi / 2.0, 0.05 * np.sin(ang), 0.05 * np.cos(ang)
+    qz = np.stack([np.cos(yaw / 2), 0 * yaw, 0 * yaw, np.sin(yaw / 2)], axis=1)
+    qy = np.stack([np.cos(pitch / 2), 0 * yaw, np.sin(pitch / 2), 0 * yaw], axis=1)
+    qx = np.stack([np.cos(roll / 2), np.sin(roll / 2), 0 * yaw, 0 * yaw], axis=1)
+    truth_q = _quat_mul_np(qz, _quat_mul_np(qy, qx))
+
+    def noisy(a, b, st, sr, bias):
+        dt, dq = pose_graph_relative_ref(truth_t[a], truth_q[a], truth_t[b], truth_q[b])
+        m = len(a)
+        dt = dt + st * rng.standard_normal((m, 3)) + bias * np.asarray([0.5 * st, 0.0, 0.0])
+        h = 0.5 * (sr * rng.standard_normal((m, 3)) + bias * np.asarray([0.0, 0.0, 0.5 * sr]))
+        dq = _quat_mul_np(np.concatenate([np.ones((m, 1)), h], axis=1), dq)
+        om = np.zeros((m, 21))
+        for k, (i, j) in enumerate(_PG_TRIU):
+            if i == j:
+                om[:, k] = 1.0 / (st * st) if i < 3 else 1.0 / (sr * sr)
+        return dt, dq, om
+
+    a = np.arange(N - 1)
+    ot, oq, oo = noisy(a, a + 1, sigma_t, sigma_r, 1.0)
+    if laps > 1:
+        ca = (np.arange(closures) * n) // max(closures, 1) + n // (2 * max(closures, 1))
+        cb = ca + n * (laps - 1)
+    else:
+        ca = np.arange(closures)
+        cb = N - 1 - np.arange(closures)
+    ct, cq, co = noisy(ca, cb, sigma_t / 5.0, sigma_r / 5.0, 0.0)
+    t, q = np.zeros((N, 3)), np.zeros((N, 4))
+    t[0], q[0] = truth_t[0], truth_q[0]
+    for i in range(N - 1):                                   # dead reckoning: t_b = t_a + R_a z_t, q_b = q_a (x) z_q
+        R = np.asarray(_pg_rot(tuple(q[i])))
+        t[i + 1] = t[i] + R @ ot[i]
+        q[i + 1] = _quat_mul_np(q[i], oq[i])
+    return dict(truth_t=truth_t, truth_q=truth_q, t=t, q=q, ab=np.concatenate([np.stack([a, a + 1], axis=1), np.stack([ca, cb], axis=1)]).astype(np.int32),
+                zt=np.concatenate([ot, ct]), zq=np.concatenate([oq, cq]), omega=np.concatenate([oo, co]), n_odometry=N - 1)

@@ -571,6 +571,40 @@ def register_scan(map_or_matcher, points, pose, quat, iterations=30, dof="xyzrpw
     return out[0] if single else out
 
 
+PoseGraph, PoseGraphResult = ops.PoseGraph, ops.PoseGraphResult
+
+
+def optimize_pose_graph(poses, quats, a, b, t, q, information, fixed=(0,), registrations=None, device=torch.device('cuda'), **kw):
+    """The back end behind match -> register -> integrate ("Pose graph"): spread the corrections that loop closures and
+    registrations measure back over a trajectory.  poses (N,3) and quats (N,4) wxyz, the scan poses as they were integrated (any
+    quaternion length, either sign); a, b (E,) node indices, t (E,3) and q (E,4) the measured relative poses R_a^T (t_b - t_a) and
+    conj(q_a) (x) q_b — odometry between consecutive scans (PoseGraph.relative of two registered poses), closures from
+    relocalise_scan — a = -1 for a measurement of node b in the world; information (E,6,6) or (E,21) over (x, y, z, roll, pitch, yaw)
+    in metres and radians, rotations about the edge's own axes through the node's position: for an absolute edge exactly
+    register_scan's parameterisation, so registrations={node: ScanRegistration} appends each with its information / sigma^2 and no
+    change of frame.  fixed: the nodes that do not move (the first by default); every connected component needs a fixed node or an
+    absolute edge, and ValueError names a node of one that floats.  Keywords are PoseGraph.optimize's: iterations=30,
+    cg_iterations=None (min(6 N, 1000)), cg_tol=1e-8, dof='xyzrpw' ('xyw': a planar robot), robust=None or Geman-McClure's c — a
+    relocaliser in a building with two similar corridors WILL close a loop wrongly some day, and with robust= such an edge ends with
+    a weight near 0 and a large chi2 in the result, which is how to find it —, tol_t=1e-5, tol_r=1e-6.  -> PoseGraphResult: poses,
+    quats (normalised), cost, initial_cost, iterations, accepted, cg_iterations, status (CONVERGED, STALLED, DEGENERATE, NONFINITE;
+    RUNNING: the iterations ran out), lam, chi2 (E,) and weights (E,).
+
+    WHAT IT IS NOT.  The solve is block-Jacobi conjugate gradients: it needs on the order of the graph's diameter in iterations, and a
+    long chain with one closure is its worst case.  There are no marginal covariances.  The rotation residual is the Gibbs vector 2
+    tan(theta / 2): it grows faster than the angle beyond about 60 degrees and is undefined at 180.  Geman-McClure needs a sensible
+    start: from a start where the good edges are as wrong as the bad, it keeps whichever it meets.  Edges join poses only: there are
+    no landmarks.  Every sum runs in one stated order: two runs, and the numpy restatement, give the same bits.
+
+    One upload, then launches only; one read-back, of the result, at the end."""
+    g = ops.PoseGraph(poses, quats, fixed=fixed, device=device)
+    if a is not None and len(np.atleast_1d(a)):
+        g.add_edges(a, b, t, q, information)
+    for node, reg in (registrations or {}).items():
+        g.add_registration(node, reg)
+    return g.optimize(**kw)
+
+
 def score_scans(map_or_matcher, points, poses, quats, shifts=None, floor=None, unknown_value=0):
     """How well does the scan fit the map at each of these poses?  B explicit candidates — poses (B,3), quats (B,4) wxyz, shifts None
     or (B,3) voxels — -> (score, used, inside, known), each (B,) int32 on the device (ops.ScanMatcher.score): the weights a particle
