@@ -1739,7 +1739,9 @@ int tohip_profile_read(double *ms_sum_host, int64_t *counts_host);
  * lifetime in shader-clock ticks (s_memtime) and in 100 MHz ticks (s_memrealtime) — at [2*block], then four words per block
  * (start, end, HW_ID, XCC_ID) from [2*grid]; grid = tohip_profile_clock_blocks(n_points, n_virtual, flags, with_occlusion) blocks
  * (6 words each); NULL switches it off.  Their quotient x 100 MHz is the clock
- * the chip actually holds under this kernel (it gives clock back under load).  Never set during a timed pass. */
+ * the chip actually holds under this kernel (it gives clock back under load).  Never set during a timed pass.
+ * The XCC_ID word's low four bits are the XCD (mask with 0xf); bit 8 (0x100) is set by the wide dense kernel (sixteen points per
+ * lane: the one a long dense launch without occlusion bits is routed to) and clear from the narrow one — which kernel ran. */
 int tohip_profile_clock(void *device_buffer);
 int64_t tohip_profile_clock_blocks(int64_t n_points, int64_t n_virtual, int flags, int with_occlusion);
 

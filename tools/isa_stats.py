@@ -3,9 +3,14 @@
 innermost loop.
 
   tools/isa_stats.py [kernel-name-substring ...]          print the mixes
-  tools/isa_stats.py --json profiles/r02_pass1_isa_mix.json
+  tools/isa_stats.py --json profiles/r11_pass1_isa_mix.json
         write the VALU mix of ONE (wave, waypoint) iteration of k_traj_pass1's dense inner loop — what bench.py prices for the
-        VALU-issue roofline (packed f32 / transcendental / other VALU; SALU, s_nop and memory instructions issue on other ports)
+        VALU-issue roofline (packed f32 / transcendental / other VALU; SALU, s_nop and memory instructions issue on other ports).
+        This is the NARROW kernel's loop (8 points per lane, 512 evaluations: what tests/test_host_cpu.py holds the file to)
+  tools/isa_stats.py --json-wide profiles/r11_pass1_wide_isa_mix.json
+        the same count for the wide kernel (k_traj_pass1_dense16: 16 points per lane, 1024 evaluations per iteration), which a
+        long dense launch runs: 1380 issue cycles per 1024 evaluations against 2 x 708, so a roofline priced with the narrow
+        mix reads 2.6 % high for such a launch
 """
 import collections
 import json
@@ -17,7 +22,8 @@ import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(REPO, "trajectory_optimization_amd", "csrc", "trajopt_hip.hip")
-DENSE_PASS1 = "k_traj_pass1_denseILb0E"   # <OCC = false>
+# option -> (mangled-name prefix of the <OCC = false> build, points per lane)
+DENSE_PASS1 = {"--json": ("k_traj_pass1_denseILb0E", 8), "--json-wide": ("k_traj_pass1_dense16ILb0E", 16)}
 TRANS = re.compile(r"v_(exp|log|rcp|rsq|sqrt|sin|cos)_")
 
 
@@ -48,7 +54,7 @@ def kernels(text):
             i += 1
             continue
         name, j, ins, loop, in_loop, by_header, hdr = m.group(1), i + 1, [], [], False, collections.defaultdict(list), None
-        while j < len(text) and "s_endpgm" not in text[j]:
+        while j < len(text) and not text[j].startswith(".Lfunc_end"):   # (a kernel may hold an early s_endpgm before its loops)
             l = text[j].strip()
             j += 1
             mb = re.match(r"^(\.LBB(\w+):|; %bb\.\d+:)", l)
@@ -75,7 +81,7 @@ def hot_loop_ops(text, kernel_prefix, marker="s_load_dwordx16"):
     lists a candidate slot only when the probe's bounds are beaten: a few dozen times per waypoint and launch)."""
     i = next(k for k, l in enumerate(text) if l.startswith(kernel_prefix))
     j = i
-    while "s_endpgm" not in text[j]:
+    while not text[j].startswith(".Lfunc_end"):   # (not the first s_endpgm: a kernel may leave early, before its loops)
         j += 1
     body = text[i:j]
     k = next(n for n, l in enumerate(body) if marker in l)
@@ -159,16 +165,17 @@ def main():
     args = sys.argv[1:]
     text = disassemble()
     ks = kernels(text)
-    if args and args[0] == "--json":
-        name = next(n for n in ks if DENSE_PASS1 in n)
+    if args and args[0] in DENSE_PASS1:
+        prefix, ppl = DENSE_PASS1[args[0]]
+        name = next(n for n in ks if prefix in n)
         # the waypoint loop: the one that loads a waypoint record (s_load_dwordx16), without its cold regions
         body, n_cold = hot_loop_ops(text, name)
         c, cl = classes(body)
-        out = dict(kernel=name, points_per_lane=8, evaluations_per_iteration=512,
+        out = dict(kernel=name, points_per_lane=ppl, evaluations_per_iteration=64 * ppl,
                    packed_f32=cl["packed_f32"], transcendental=cl["transcendental"], other_valu=cl["other_valu"],
                    salu_smem=cl["salu_smem"], vmem=cl["vmem"], cold_instructions_excluded=n_cold, source_hash=source_hash(),
                    note="VALU instructions of one (wave, waypoint) iteration of the dense inner loop (hipcc -O3 --offload-arch=gfx950, "
-                        "ROCm 7.2); a lane owns 8 points = 4 packed pairs; per evaluation: 25 FMA-class operations, 4 transcendentals; "
+                        f"ROCm 7.2); a lane owns {ppl} points = {ppl // 2} packed pairs; per evaluation: 25 FMA-class operations, 4 transcendentals; "
                         "the regions a wave enters only when its slot beats the probe's bounds (atomicMin / atomicMax of the running extrema: a few dozen "
                         "times per waypoint and launch) and the slot-minimum region (entered only for a waypoint whose sample held no exact zero: none "
                         "on the BASELINE workloads) are not counted; 25 FMA-class operations per evaluation since r03",

@@ -586,6 +586,107 @@ k_traj_pass1_dense(CloudView cv, const WayRec* __restrict__ rec, int V, int nblk
     }
 }
 
+// DENSE, wide: the same persistent flat cut, with SIXTEEN consecutive points to a lane — eight independent packed chains per
+// waypoint — built for at least three waves per SIMD (the compiler reaches four, 111 VGPRs, and runs the chains as two groups of
+// four: all eight interleaved do not fit three waves' registers).  A row of 16 lanes is exactly one 256-point
+// slot: the reduction is the in-row one alone (no cross-row step and its s_nop), and the epilogue's fixed part is paid once per
+// 16 points: 1380 issue cycles per 1024 evaluations against 2 x 708 (where the measurements are).
+// A wave holds four slots, a block 4096 points; npad is a multiple of 2048, so the last point block may be half
+// present: the rows beyond npad read point 0 and never store, fold, mark or initialise.  The host routes a launch here when a
+// piece is at least TO_WIDE_MIN_UNITS (point block, waypoint) pairs long (a pair is twice the narrow kernel's: a launch of about
+// one pair per block is latency-bound and keeps the narrow kernel) and there are no occlusion bits (that build was not measured).
+// The block's stamps carry bit 8 in their XCC word (include/trajopt_hip.h, tohip_profile_clock).
+#define TO_PD16 16
+#define TO_XCDS 8
+#define TO_WIDE_SGPRS 112          // declared bound on the SGPR count, as TO_DENSE_SGPRS (tests/test_dense_wide_resources_cpu.py)
+#define TO_WIDE_MIN_UNITS 2
+template <bool OCC>
+__global__ void __launch_bounds__(TO_BLOCK, 3)
+k_traj_pass1_dense16(CloudView cv, const WayRec* __restrict__ rec, int V, int nblk, EvalK k, float2* __restrict__ part,
+                     Extrema* __restrict__ ext, unsigned long long* __restrict__ cbits, int fv_words,
+                     const uint32_t* __restrict__ occ, int64_t occw, OutInit oi, unsigned long long* __restrict__ stamps, int per_cu) {
+    constexpr int P = TO_PD16;
+    const int lane = threadIdx.x & 63;
+    unsigned long long st0 = 0, sr0 = 0;
+    if (stamps != nullptr && threadIdx.x == 0) { st0 = __builtin_amdgcn_s_memtime(); sr0 = __builtin_amdgcn_s_memrealtime(); }
+    f2 eps2 = pk_splat(k.eps), l2e2 = pk_splat(k.l2e_eps), scd2 = pk_splat(k.scd);
+    asm volatile("" : "+v"(eps2), "+v"(l2e2), "+v"(scd2));
+    // Which piece is the block's: the pieces are one pair longer or shorter in a pattern of a short period, the hardware deals
+    // consecutive blocks to the TO_XCDS XCDs in turn and, inside an XCD, to its CUs in turn (observed, not promised) — so with
+    // piece = block whole XCDs get the long pieces (1 M x 128 on 1024 blocks: a CU's four blocks hold 124 pairs on five XCDs and
+    // 120 on three, and the long XCDs end 3 us after the short ones).  With the resident grid (per_cu > 0: per_cu blocks on every
+    // CU) an XCD takes a contiguous eighth of the pieces and a CU per_cu consecutive ones: every CU is within one pair of the
+    // mean.  Any other dealing only moves pieces between blocks: the results do not depend on it.
+    int piece = blockIdx.x;
+    if (per_cu > 0) {
+        const int per_xcd = gridDim.x / TO_XCDS, cus = per_xcd / per_cu, j = blockIdx.x / TO_XCDS;
+        piece = (blockIdx.x % TO_XCDS) * per_xcd + (j % cus) * per_cu + j / cus;
+    }
+    const int64_t total = (int64_t)nblk * V;
+    int64_t u = total * piece / gridDim.x;
+    const int64_t u_end = total * (piece + 1) / gridDim.x;
+    // the narrow kernel's priority steps: without them the blocks of an XCD end 61 us apart instead of 6, with one step at 7/8 21
+    const int64_t len = u_end - u, q1 = u + 3 * len / 4, q2 = u + 7 * len / 8, q3 = u + 15 * len / 16;
+    __builtin_amdgcn_s_setprio(3);
+    while (u < u_end) {
+        const int pb = (int)(u / V);
+        const int v0 = (int)(u - (int64_t)pb * V);
+        const int v1 = (int)min((int64_t)V, v0 + (u_end - u));
+        const int gthread = pb * TO_BLOCK + threadIdx.x;
+        const int64_t base = (int64_t)gthread * P;
+        const bool present = base < cv.npad;   // (the same for the 16 lanes of a row: a slot is present or absent as a whole)
+        const int64_t lbase = present ? base : 0;
+        const int slot = gthread >> 4;   // 16 lanes x 16 points
+        float x[P], y[P], z[P];
+        load_points<P>(cv.soa, cv.npad, lbase, x, y, z);
+        if (v0 == 0 && present) {
+#pragma unroll
+            for (int j = 0; j < P; j += 4) init_outputs(base + j, oi);
+        }
+        float2* prow = part + (int64_t)slot * V;
+        for (int v = v0; v < v1; ++v) {
+            const int64_t uu = u + (v - v0);
+            if (uu == q1) __builtin_amdgcn_s_setprio(2);
+            if (uu == q2) __builtin_amdgcn_s_setprio(1);
+            if (uu == q3) __builtin_amdgcn_s_setprio(0);
+            const WayRec& r = rec[v];
+            float om[P];
+            load_occ<P, OCC>(occ, occw, v, lbase, om);
+            f2 p[P / 2];
+#pragma unroll
+            for (int i = 0; i < P; i += 2)
+                p[i / 2] = vis_p_pk(r, k, f2{x[i], x[i + 1]}, f2{y[i], y[i + 1]}, f2{z[i], z[i + 1]}, eps2, l2e2, scd2) * f2{om[i], om[i + 1]};
+            // (three-operand maxima: eight instructions for sixteen values)
+            const float a0 = fmaxf(fmaxf(p[0].x, p[0].y), p[1].x), a1 = fmaxf(fmaxf(p[1].y, p[2].x), p[2].y),
+                        a2 = fmaxf(fmaxf(p[3].x, p[3].y), p[4].x), a3 = fmaxf(fmaxf(p[4].y, p[5].x), p[5].y),
+                        a4 = fmaxf(fmaxf(p[6].x, p[6].y), p[7].x);
+            const float mx = row_max16_nn(fmaxf(fmaxf(fmaxf(a0, a1), a2), fmaxf(fmaxf(a3, a4), p[7].y)));
+            // the minimum: only while the probe has not exhibited a zero (see the narrow kernel)
+            float mn = 0.f;
+            if (__builtin_bit_cast(int, r.U) != 0) {
+                float m = fminf(p[0].x, p[0].y);
+#pragma unroll
+                for (int i = 1; i < P / 2; ++i) m = fminf(m, fminf(p[i].x, p[i].y));
+                mn = row_min16_nn(m);
+            }
+            if ((lane & 15) == 15 && present) {
+                prow[v] = make_float2(mn, mx);
+                if (fold_extrema(ext, v, mn, mx, r)) mark_candidate(cbits, fv_words, slot, r.seg);
+            }
+        }
+        u += v1 - v0;
+    }
+    if (stamps != nullptr && threadIdx.x == 0) {
+        stamps[2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - st0;
+        stamps[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - sr0;
+        unsigned long long* ext_st = stamps + 2 * (int64_t)gridDim.x + 4 * (int64_t)blockIdx.x;
+        unsigned hw, xcc;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        ext_st[0] = sr0; ext_st[1] = __builtin_amdgcn_s_memrealtime(); ext_st[2] = hw; ext_st[3] = xcc | 0x100u;
+    }
+}
+
 __device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v) {
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
     return ((unsigned long long)hi << 32) | lo;
@@ -600,6 +701,7 @@ __device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v) 
 // pair, were what the kernel's time consisted of.  A pair that is not listed is not written: k_traj_sparse takes (min, max) =
 // (the proven 0, -inf: never flagged) for it from the `live` bit.
 #define TO_CULL_LIST 2048
+#define TO_CULL_PD 8   // points per lane of a unit's half-wave
 struct CullLds {
     unsigned long long cand[TO_PROBE_MAXFW];   // the candidates this block finds
     unsigned long long row[TO_PROBE_MAXFW];    // the waypoint's reachable slots (its row of `live`)
@@ -680,7 +782,7 @@ k_traj_pass1_cull(CloudView cv, const WayRec* __restrict__ rec, int V, EvalK k, 
         return half ? s1 : s0;
     };
     if (wr < nunits) {
-        constexpr int P8 = TO_PD;
+        constexpr int P8 = TO_CULL_PD;
         const f2 eps2 = pk_splat(k.eps), l2e2 = pk_splat(k.l2e_eps), scd2 = pk_splat(k.scd);
         // one unit: the lane's eight points of slot `cur` against the block's waypoint
         auto eval_unit = [&](int u, int cur, const float (&x)[P8], const float (&y)[P8], const float (&z)[P8]) {
@@ -2058,10 +2160,18 @@ inline int dense_per_cu(int api, int sgprs) {
     const int k = std::min(std::min(api, 8), by_sgpr);
     return k < 1 ? 1 : k;
 }
-// dense pass 1: as many persistent blocks as are resident at once (never more than one per (point block, waypoint) pair)
-inline int dense_blocks(int nblk, int V, bool occ) {
-    // CU count and occupancy belong to a device: one packed entry per device (cus << 8 | plain per CU << 4 | occlusion per CU),
-    // 0 = not asked yet; a device beyond the table is asked every time
+// dense pass 1: as many persistent blocks as are resident at once (never more than one per (point block, waypoint) pair), and
+// which of the two kernels runs: the wide one (k_traj_pass1_dense16) without occlusion bits when every piece of its resident grid
+// is at least TO_WIDE_MIN_UNITS of its (point block, waypoint) pairs long, else the narrow one
+struct DenseLaunch {
+    bool wide;
+    int nblk;   // point blocks of the chosen kernel
+    int nb;     // its grid
+    int per_cu; // wide, and the grid is the resident one on whole XCDs: blocks per CU (the kernel deals its pieces by CU); else 0
+};
+inline DenseLaunch dense_blocks(int64_t npad, int V, bool occ) {
+    // CU count and occupancy belong to a device: one packed entry per device (cus << 12 | wide per CU << 8 | plain per CU << 4 |
+    // occlusion per CU), 0 = not asked yet; a device beyond the table is asked every time
     constexpr int kDev = 64;
     static std::atomic<int> cache[kDev];
     int dev = 0;
@@ -2072,17 +2182,23 @@ inline int dense_blocks(int nblk, int V, bool occ) {
         hipDeviceProp_t prop;
         if (dev >= 0 && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
         if (cus <= 0) cus = 256;
-        int a = 0, b = 0;
+        int a = 0, b = 0, w = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_traj_pass1_dense<false>, TO_BLOCK, 0) != hipSuccess || a <= 0) a = 4;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_traj_pass1_dense<true>, TO_BLOCK, 0) != hipSuccess || b <= 0) b = 4;
-        e = cus << 8 | dense_per_cu(a, TO_DENSE_SGPRS) << 4 | dense_per_cu(b, TO_DENSE_OCC_SGPRS);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&w, k_traj_pass1_dense16<false>, TO_BLOCK, 0) != hipSuccess || w <= 0) w = 2;
+        e = cus << 12 | dense_per_cu(w, TO_WIDE_SGPRS) << 8 | dense_per_cu(a, TO_DENSE_SGPRS) << 4 | dense_per_cu(b, TO_DENSE_OCC_SGPRS);
         if (dev >= 0 && dev < kDev) cache[dev].store(e, std::memory_order_relaxed);
     }
-    const int cus = e >> 8, per_cu = occ ? (e & 15) : (e >> 4 & 15);
-    int64_t nb = (int64_t)per_cu * cus;
-    const int64_t total = (int64_t)nblk * V;
-    if (nb > total) nb = total;
-    return (int)nb;
+    const int cus = e >> 12;
+    const int64_t nblk16 = (npad + TO_BLOCK * TO_PD16 - 1) / (TO_BLOCK * TO_PD16), resident16 = (int64_t)(e >> 8 & 15) * cus;
+    DenseLaunch d;
+    d.per_cu = 0;
+    d.wide = !occ && nblk16 * V >= TO_WIDE_MIN_UNITS * resident16;
+    d.nblk = d.wide ? (int)nblk16 : (int)(npad / (TO_BLOCK * TO_PD));
+    const int64_t resident = d.wide ? resident16 : (int64_t)(occ ? (e & 15) : (e >> 4 & 15)) * cus;
+    d.nb = (int)std::min(resident, (int64_t)d.nblk * V);
+    if (d.wide && d.nb == resident && cus % TO_XCDS == 0) d.per_cu = e >> 8 & 15;
+    return d;
 }
 
 inline int rig_cams(const tohip_rig* rig) { return (rig && rig->n_cams > 0 && rig->rig_quats) ? rig->n_cams : 1; }
@@ -2191,10 +2307,10 @@ inline int launch_probe_pass1(const TrajStep& s, const float* poses, const float
             if (occ) k_traj_pass1_cull<true, 4><<<grid, 256, 0, s.st>>>(s.cv, s.rec, V, s.k, s.part, s.ext, s.cbits, s.pl.fv_words, s.live, s.occ, s.occw, oi);
             else k_traj_pass1_cull<false, 4><<<grid, 256, 0, s.st>>>(s.cv, s.rec, V, s.k, s.part, s.ext, s.cbits, s.pl.fv_words, s.live, s.occ, s.occw, oi);
         } else {
-            const int nblk8 = (int)(s.pl.npad / (TO_BLOCK * TO_PD));
-            const int nb = dense_blocks(nblk8, V, occ);
-            if (occ) k_traj_pass1_dense<true><<<nb, TO_BLOCK, 0, s.st>>>(s.cv, s.rec, V, nblk8, s.k, s.part, s.ext, s.cbits, s.pl.fv_words, s.occ, s.occw, oi, clock_stamps());
-            else k_traj_pass1_dense<false><<<nb, TO_BLOCK, 0, s.st>>>(s.cv, s.rec, V, nblk8, s.k, s.part, s.ext, s.cbits, s.pl.fv_words, s.occ, s.occw, oi, clock_stamps());
+            const DenseLaunch d = dense_blocks(s.pl.npad, V, occ);
+            if (d.wide) k_traj_pass1_dense16<false><<<d.nb, TO_BLOCK, 0, s.st>>>(s.cv, s.rec, V, d.nblk, s.k, s.part, s.ext, s.cbits, s.pl.fv_words, s.occ, s.occw, oi, clock_stamps(), d.per_cu);
+            else if (occ) k_traj_pass1_dense<true><<<d.nb, TO_BLOCK, 0, s.st>>>(s.cv, s.rec, V, d.nblk, s.k, s.part, s.ext, s.cbits, s.pl.fv_words, s.occ, s.occw, oi, clock_stamps());
+            else k_traj_pass1_dense<false><<<d.nb, TO_BLOCK, 0, s.st>>>(s.cv, s.rec, V, d.nblk, s.k, s.part, s.ext, s.cbits, s.pl.fv_words, s.occ, s.occw, oi, clock_stamps());
         }
         TO_HIP_CHECK_LAUNCH();
     }
@@ -2819,10 +2935,9 @@ extern "C" int tohip_profile_clock(void* buffer) {
     clock_stamps() = (unsigned long long*)buffer;
     return TOHIP_OK;
 }
-// the dense kernel's grid for this problem (with_occlusion selects the build it is asked about)
+// the grid of the dense kernel that is launched for this problem (with_occlusion selects the build it is asked about)
 extern "C" int64_t tohip_profile_clock_blocks(int64_t n_points, int64_t n_virtual, int flags, int with_occlusion) {
     if (n_points <= 0 || n_virtual <= 0 || !(flags & TOHIP_TRAJ_DENSE)) return 0;   // only the dense kernel stamps
     const TrajPlan pl = make_plan(n_points, n_virtual, n_virtual);
-    const int nblk8 = (int)(pl.npad / (TO_BLOCK * TO_PD));
-    return dense_blocks(nblk8, (int)n_virtual, with_occlusion != 0);
+    return dense_blocks(pl.npad, (int)n_virtual, with_occlusion != 0).nb;
 }
