@@ -162,8 +162,8 @@ def _constant_case():
 
 
 def test_search_prunes_nothing_on_a_constant_map(dev):
-    """198 147 leaves: the lists of the last levels take several grid-stride passes of every kernel, and the bound launch walks more
-    chunks than it has blocks' worth of shares."""
+    """198 147 leaves, none pruned: 777 chunks over three rotations.  Every list kernel still makes one pass (its launch holds
+    524 288 lanes) and the bound launch has 777 items for its 2 048 blocks; tests/test_hip_scan_search_at_size.py goes beyond both."""
     L, pts = _constant_case()
     c = CONSTANT
     _, rec = _search(dev, L, pts, sc.rotations(c["K"]), sc.T, c["window"], c["H"])

@@ -2065,14 +2065,15 @@ def _reloc_children(nodes, half, wx, wy):
     return np.concatenate(kids, axis=0)
 
 
-def scan_search_ref(L, origin, resolution, points, Rs, t, window, levels, floor=None, unknown_value=0, capacity=1 << 22):
+def scan_search_ref(L, origin, resolution, points, Rs, t, window, levels, floor=None, unknown_value=0, capacity=1 << 22, lists=None):
     """The branch-and-bound search as DESIGN.md 10 "Relocalisation" defines it -> the record, (18,) int64: flat index, k, dx, dy, dz,
     score, ties, status, incumbent, evaluated, H, nodes[0 .. H] (the rest 0).  The top level holds every node with sx in {-wx, -wx +
     2^H, ...} <= wx, sy likewise, every sz and every rotation; for h = H .. 1: the node with the largest bound (then the lowest (k, sz,
     sy, sx)) is followed greedily to a leaf, the incumbent becomes max(incumbent, the leaf's score), every node whose bound is below
     the incumbent is dropped, the rest are replaced by their children; at level 0 the maximum of the key (score, smaller |s|^2, lower
     flat index) and the number of survivors with the best score.  A level of more than `capacity` nodes stops the search: status =
-    count << 3 | (level + 1), flat index -1, nodes[level] = count."""
+    count << 3 | (level + 1), flat index -1, nodes[level] = count.  lists: a dict that receives {level: the nodes (m,4) of every list
+    that was bounded}, for tests that ask how a list is made up."""
     wx, wy, wz = (int(c) for c in window)
     H = int(levels)
     if not (0 <= wx <= RELOC_MAX_WINDOW[0] and 0 <= wy <= RELOC_MAX_WINDOW[1] and 0 <= wz <= RELOC_MAX_WINDOW[2]):
@@ -2095,6 +2096,8 @@ def scan_search_ref(L, origin, resolution, points, Rs, t, window, levels, floor=
         return overflow(H, len(nodes))
     bounds = _reloc_bounds(T[H], H, u, vox, nodes)
     rec[9] = len(nodes)
+    if lists is not None:
+        lists[H] = nodes
     for h in range(H, 0, -1):
         rec[11 + h] = len(nodes)
         at = nodes[_reloc_order(nodes, bounds)][None, :]
@@ -2110,6 +2113,8 @@ def scan_search_ref(L, origin, resolution, points, Rs, t, window, levels, floor=
             return overflow(h - 1, len(nodes))
         bounds = _reloc_bounds(T[h - 1], h - 1, u, vox, nodes)
         rec[9] += len(nodes)
+        if lists is not None:
+            lists[h - 1] = nodes
     rec[11] = len(nodes)
     nxw, nyw, nzw = 2 * wx + 1, 2 * wy + 1, 2 * wz + 1
     top = np.flatnonzero(bounds == bounds.max())
