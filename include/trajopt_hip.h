@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_posegraph_workspace_bytes / tohip_posegraph_layout / tohip_posegraph_start / tohip_posegraph_linearize /
+/* (still 15) + tohip_occ_resample / tohip_evid_resample and the TOHIP_RESAMPLE_* constants (resampling maps: voxel content of one box read
+ * in another under a rigid transform and a change of resolution, by an integer affine map the host quantises once): new symbols only.
+ * (still 15) + tohip_posegraph_workspace_bytes / tohip_posegraph_layout / tohip_posegraph_start / tohip_posegraph_linearize /
  * tohip_posegraph_gather / tohip_posegraph_step / tohip_posegraph_optimize / tohip_posegraph_result and the TOHIP_POSEGRAPH_* constants
  * (pose-graph optimisation: Levenberg-Marquardt over scan poses, each step by block-Jacobi conjugate gradients): new symbols only.
  * (still 15) + tohip_scanreg_normal / tohip_scanreg_step and TOHIP_SCANREG_RECORD / TOHIP_SCANREG_STATE (fine scan registration: integer
@@ -1302,6 +1304,43 @@ int tohip_occ_transfer(const void *src, size_t src_bytes, const tohip_occ_geom *
 int tohip_evid_transfer(const void *src, size_t src_bytes, const tohip_occ_geom *src_geom, void *dst, size_t dst_bytes,
                         const tohip_occ_geom *dst_geom, void *occupied_out, void *free_out, size_t grid_bytes, int32_t sx, int32_t sy,
                         int32_t sz, int32_t mode, int32_t lmin, int32_t lmax, int32_t threshold, uint64_t *counts, void *stream);
+
+/* ---- resampling maps (resample_kernels.hip, DESIGN.md §10, "Resampling maps") ----
+ * The transfers above with a rigid transform and a finer or equal resolution between the two boxes.  affine_host: twelve int64 in HOST
+ * memory, read before the call returns — M (3 x 3, row major), then T (3) — in fixed point with frac_bits = TOHIP_RESAMPLE_FRAC_BITS
+ * fraction bits; |M| <= 2^21, |T| <= 2^40.  For every voxel d = (i, j, k) inside dst's dims, in int64,
+ *     u_a = M[a][0] (2 i + 1) + M[a][1] (2 j + 1) + M[a][2] (2 k + 1) + T[a],     n_a = u_a >> frac_bits  (arithmetic: the floor),
+ * u / 2^frac_bits being the source position of d's centre in source voxels (voxel i spans [i, i + 1)) and n its NEAREST source voxel.
+ * Origins and resolutions of the two geometries are checked as everywhere and not interpreted: the caller quantises the transform.
+ * The SOURCE VALUE S of d is, by rule:
+ *   TOHIP_RESAMPLE_NEAREST  the value (bit) of source voxel n; EMPTY (-128, bit 0) where n lies outside src's dims.
+ *   TOHIP_RESAMPLE_COVER    (evidence) over the 3 x 3 x 3 source voxels around n: the largest value above `threshold` if there is
+ *                           one; otherwise -128 if one of the 27 is -128 or lies outside src's dims; otherwise the largest value —
+ *                           the maximum under the key free < unknown < occupied.
+ *   TOHIP_RESAMPLE_ANY      (planes) the OR of the 27 bits;  TOHIP_RESAMPLE_ALL: their AND, a voxel outside src's dims counting 0.
+ * While dst's resolution is not coarser than src's, every point of a dst voxel lies in one of the 27: COVER / ANY lose no occupied
+ * voxel, and COVER / ALL call nothing free that touches a voxel that is not.  NEAREST is unbiased and may open pinholes in a wall one
+ * voxel thick.  S is then written or combined exactly as the transfers do it: tohip_occ_resample with mode COPY (0) / OR (1) and one
+ * count; tohip_evid_resample with mode COPY (0) / ADD (1) / CONFIDENT (2), the two derived planes, the pads, the headers, the rule
+ * that in ADD and CONFIDENT a brick with no S other than -128 inside dst's dims is neither read nor written, and the four counts —
+ * all as documented for tohip_evid_transfer; `threshold` also classifies the source values under COVER.  scratch / scratch_bytes:
+ * room for an implementation with a pre-pass; this one takes COVER's 27 values in place and neither reads nor writes it (NULL, 0 are
+ * fine).  src is only read.  flags is reserved and must be 0.  src, dst, the planes, counts and a scratch that is given must be
+ * different buffers.  A bad rule, mode, frac_bits, affine entry or flags, a null affine_host, an aliased buffer: TOHIP_EINVAL; a
+ * short buffer: TOHIP_ENOSPC.  Every argument check returns before anything is enqueued; nothing synchronises with the host;
+ * integers only, one lane owns a dst word or brick: the same bytes in every run and for every launch shape. */
+#define TOHIP_RESAMPLE_FRAC_BITS 20
+#define TOHIP_RESAMPLE_NEAREST 0
+#define TOHIP_RESAMPLE_COVER 1
+#define TOHIP_RESAMPLE_ANY 1
+#define TOHIP_RESAMPLE_ALL 2
+int tohip_occ_resample(const void *src, size_t src_bytes, const tohip_occ_geom *src_geom, void *dst, size_t dst_bytes,
+                       const tohip_occ_geom *dst_geom, const int64_t *affine_host, int32_t frac_bits, int32_t rule, int32_t mode,
+                       uint64_t *counts, void *stream, uint32_t flags);
+int tohip_evid_resample(const void *src, size_t src_bytes, const tohip_occ_geom *src_geom, void *dst, size_t dst_bytes,
+                        const tohip_occ_geom *dst_geom, void *occupied_out, void *free_out, size_t grid_bytes,
+                        const int64_t *affine_host, int32_t frac_bits, int32_t rule, int32_t mode, int32_t lmin, int32_t lmax,
+                        int32_t threshold, uint64_t *counts, void *scratch, size_t scratch_bytes, void *stream, uint32_t flags);
 
 /* ---- clearance from the map (clearance_map_kernels.hip, DESIGN.md §10, "Clearance from the map") -------
  * tohip_clearance and tohip_clearance_segments with the voxels of an occupancy grid as the obstacles.  occupied: a grid buffer of

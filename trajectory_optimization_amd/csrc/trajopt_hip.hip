@@ -25,6 +25,7 @@
 #include "posegraph_kernels.hip"
 #include "scansearch_kernels.hip"
 #include "reframe_kernels.hip"
+#include "resample_kernels.hip"
 #include "travel_kernels.hip"
 #include "components_kernels.hip"
 #include "ground_kernels.hip"

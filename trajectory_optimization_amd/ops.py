@@ -4,6 +4,7 @@ PyTorch here is plumbing only: device memory, streams and autograd bookkeeping. 
 step of the hot path runs in libtrajopt_hip.so; nothing in this module computes on the CPU and
 nothing falls back to torch ops when the library is missing.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -782,6 +783,12 @@ def _map_call(device, name, *args):
         check(getattr(_lib.lib(), name)(*args, stream_ptr()), name)
 
 
+def _map_call0(device, name, *args):
+    """_map_call for the entries with a reserved flags word behind the stream (0)."""
+    with torch.cuda.device(device):
+        check(getattr(_lib.lib(), name)(*args, stream_ptr(), 0), name)
+
+
 class OccupancyGrid:
     """A dense occupancy bit grid on the device (occupancy_kernels.hip), filled from any number of clouds: voxel
     (i, j, k) is origin + [i, i+1) x [j, j+1) x [k, k+1) resolution, the index floor((x - origin) / resolution) in float32.  Around
@@ -891,13 +898,35 @@ class OccupancyGrid:
         out.skipped = self.skipped
         return out
 
-    def merge(self, other, counts=None):
-        """OR another grid of the same lattice into this one over the overlap of the two boxes, in place -> self; `other` is only
-        read.  counts: a zero-filled (1,) int64 device tensor that receives += the bits that were not set before, or None.  One
-        launch, nothing read back."""
-        s, overlap = check_merge(self, other)
+    def _resample(self, src, affine, rule, mode, counts):
+        keep, a, frac = _affine_arg(affine)
+        _map_call0(self.device, "tohip_occ_resample", *src._sizes(), *self._sizes(), a, frac, RESAMPLE_OCC_RULES[rule], XFER_MODES[mode], ptr(counts))
+
+    def transformed(self, pose, quat, origin=None, resolution=None, dims=None, like=None, rule="nearest", _plane_rule=None):
+        """This grid's content under a rigid transform and, if asked, at a finer resolution -> a NEW grid (tohip_occ_resample, DESIGN.md
+        10 "Resampling maps"); this one is only read.  pose (3,), quat (4,) wxyz: world_new = R(quat) world_old + pose, the pose of
+        this grid's frame in the new one.  The new box: like= a map (its frame), or origin / resolution / dims (check_transform);
+        by default the axis-aligned box around this box's transformed corners, its origin a multiple of the resolution.  rule
+        'nearest': the bit of the voxel that holds the new voxel's centre — unbiased, and a wall one voxel thick may show pinholes;
+        'cover': the OR over the 3 x 3 x 3 voxels around it — no set voxel is lost, walls stay shut and grow by up to a voxel.  One
+        launch, nothing read back; `skipped` carries over."""
+        frame, affine = check_transform(self, pose, quat, origin, resolution, dims, like, rule)
+        out = OccupancyGrid(frame.origin, frame.resolution, frame.dims, device=self.device)
+        out._resample(self, affine, _plane_rule or ("any" if rule == "cover" else "nearest"), "copy", None)
+        out.skipped = self.skipped
+        return out
+
+    def merge(self, other, counts=None, pose=None, quat=None, rule="nearest", _plane_rule=None):
+        """OR another grid into this one over the overlap of the two boxes, in place -> self; `other` is only read.  Without a pose
+        the two share a lattice and the bits move by a voxel shift.  pose (3,), quat (4,) wxyz: the other grid's frame stands at
+        world_self = R(quat) world_other + pose and is resampled (rule 'nearest' or 'cover', as transformed takes it; this grid
+        must not be coarser than the other); an identity pose on this grid's lattice takes the shift path.  counts: a zero-filled
+        (1,) int64 device tensor that receives += the bits that were not set before, or None.  One launch, nothing read back."""
+        s, overlap, affine = check_merge_posed(self, other, None, pose, quat, rule)
         _check_counts(counts, 1, self.device)
-        if overlap:
+        if affine is not None:
+            self._resample(other, affine, _plane_rule or ("any" if rule == "cover" else "nearest"), "or", counts)
+        elif overlap:
             _map_call(self.device, "tohip_occ_transfer", *other._sizes(), *self._sizes(), *s, XFER_MODES["or"], ptr(counts))
         return self
 
@@ -1061,11 +1090,23 @@ class SpaceMap:
         s, d, _ = check_reframe(self, shift, dims, centre)
         return SpaceMap(self.occupied.reframed(shift=s, dims=d), self.free.reframed(shift=s, dims=d))
 
-    def merge(self, other):
-        """OR both planes of another SpaceMap of the same lattice into this one's over the overlap, in place -> self."""
-        check_merge(self, other)
-        self.occupied.merge(other.occupied)
-        self.free.merge(other.free)
+    def transformed(self, pose, quat, origin=None, resolution=None, dims=None, like=None, rule="nearest"):
+        """Both planes under a rigid transform (OccupancyGrid.transformed) -> a NEW SpaceMap over two new grids; this map is only
+        read.  rule 'nearest': both planes take the bit under the new voxel's centre.  rule 'cover', for planning: occupied takes
+        the OR of the 3 x 3 x 3 voxels around it and free their AND (outside the box counts as not free), so no occupied voxel is
+        lost, nothing is called free that touches a voxel that is not, and the two planes stay disjoint."""
+        frame, _ = check_transform(self, pose, quat, origin, resolution, dims, like, rule)
+        cover = rule == "cover"
+        return SpaceMap(self.occupied.transformed(pose, quat, like=frame, rule=rule, _plane_rule="any" if cover else None),
+                        self.free.transformed(pose, quat, like=frame, rule=rule, _plane_rule="all" if cover else None))
+
+    def merge(self, other, pose=None, quat=None, rule="nearest"):
+        """OR both planes of another SpaceMap into this one's over the overlap, in place -> self: of the same lattice, or, with pose
+        and quat (OccupancyGrid.merge), resampled — under rule 'cover' the occupied plane by ANY and the free plane by ALL."""
+        check_merge_posed(self, other, None, pose, quat, rule)
+        cover = rule == "cover"
+        self.occupied.merge(other.occupied, pose=pose, quat=quat, rule=rule, _plane_rule="any" if cover else None)
+        self.free.merge(other.free, pose=pose, quat=quat, rule=rule, _plane_rule="all" if cover else None)
         return self
 
     def state(self, positions):
@@ -1961,19 +2002,44 @@ class EvidenceMap:
         out._transfer(self, s, "copy", out._counts)
         return out
 
-    def merge(self, other, mode="confident", counts=None):
+    def _resample(self, src, affine, rule, mode, counts):
+        _, _, lmin, lmax, threshold = self.params
+        keep, a, frac = _affine_arg(affine)
+        _map_call0(self.device, "tohip_evid_resample", *src._sizes(), *self._sizes(), ptr(self.occupied.buf), ptr(self.free.buf),
+                   self.occupied.buf.numel(), a, frac, RESAMPLE_RULES[rule], XFER_MODES[mode], lmin, lmax, threshold, ptr(counts), None, 0)
+
+    def transformed(self, pose, quat, origin=None, resolution=None, dims=None, like=None, rule="nearest"):
+        """This map's values under a rigid transform and, if asked, at a finer resolution -> a NEW EvidenceMap of the same parameters
+        (tohip_evid_resample, DESIGN.md 10 "Resampling maps"): a new buffer, both planes derived from it, empty scratch planes; this
+        map is only read.  pose, quat and the new box as OccupancyGrid.transformed takes them.  rule 'nearest': the value of the
+        voxel that holds the new voxel's centre — unbiased, the rule for fusing evidence; a wall one voxel thick may show pinholes.
+        rule 'cover', for planning: the maximum over the 3 x 3 x 3 voxels around it under free < unknown < occupied — no occupied
+        voxel is lost and nothing is free unless all it touches was free; walls and the unknown grow by up to a voxel.  One launch,
+        nothing read back; the new map's last_counts() tells what it holds (known voxels, twice; occupied voxels; 0)."""
+        frame, affine = check_transform(self, pose, quat, origin, resolution, dims, like, rule)
+        hit, miss, lmin, lmax, threshold = self.params
+        out = EvidenceMap(frame.origin, frame.resolution, frame.dims, hit, miss, lmin, lmax, threshold, device=self.device)
+        out._resample(self, affine, rule, "copy", out._counts)
+        return out
+
+    def merge(self, other, mode="confident", counts=None, pose=None, quat=None, rule="nearest"):
         """Fuse another EvidenceMap of the same lattice into this one over the overlap of the two boxes, in place -> self; `other` is
         only read, both planes stay exact.  mode 'confident': per voxel the stronger belief wins (the larger |L|; at equal strength
         the positive, occupied one), the other's values clamped to this map's [lmin, lmax] first — a lattice join: commutative,
         associative and idempotent, so any merge order and any repetition give the same bytes.  mode 'add': independent evidence,
         clamp(L + L_other, lmin, lmax) where the other has observed the voxel — commutative, but a map merged twice is counted
         twice.  counts: a zero-filled (4,) int64 device tensor that receives += (values changed, voxels newly known, occupied
-        voxels that appeared, that vanished), or None: last_counts() reports them.  One launch, nothing read back."""
-        s, overlap = check_merge(self, other, mode)
+        voxels that appeared, that vanished), or None: last_counts() reports them.  pose (3,), quat (4,) wxyz: the other map's frame
+        stands at world_self = R(quat) world_other + pose and its values are resampled (rule 'nearest', the unbiased one to fuse
+        evidence with, or 'cover'; transformed says what each gives; this map must not be coarser than the other) before the same
+        combine; an identity pose on this map's lattice takes the shift path.  One launch, nothing read back."""
+        s, overlap, affine = check_merge_posed(self, other, mode, pose, quat, rule)
         _check_counts(counts, 4, self.device)
         if counts is None:
             counts = self._counts.zero_()
-        if overlap:
+        if affine is not None:
+            self._resample(other, affine, rule, mode, counts)
+        elif overlap:
             self._transfer(other, s, mode, counts)
         return self
 
@@ -3083,6 +3149,165 @@ def check_merge(a, b, mode=None):
     s = tuple(-v for v in k)   # a's voxel v is b's voxel v - k
     overlap = all(-na < v < nb for v, na, nb in zip(s, fa.dims, fb.dims))   # some v in [0, na) with v + s in [0, nb)
     return s, overlap
+
+
+MERGE_MAX_DIM = 2048        # of a merged or transformed map's box per axis
+MERGE_MAX_VOXELS = 1 << 31
+RESAMPLE_FRAC_BITS = 20     # fraction bits of the integer affine map (tohip_occ_resample / tohip_evid_resample)
+RESAMPLE_MAX_OFFSET = 1 << 20   # voxels of the source between the two origins
+RESAMPLE_MIN_RATIO = 0.125  # of r_dst / r_src
+RESAMPLE_RULES = {"nearest": 0, "cover": 1}
+RESAMPLE_OCC_RULES = {"nearest": 0, "any": 1, "all": 2}
+
+
+class MapFrame(collections.namedtuple("MapFrame", "origin resolution dims")):
+    """A box of voxels without a buffer — origin (3,), resolution, dims — where only the geometry of a map is needed (resample_affine,
+    transformed_box); every map class carries the same three attributes."""
+    __slots__ = ()
+
+
+def _frame_of(m, name):
+    f = m.occupied if isinstance(m, SpaceMap) else m
+    if not all(hasattr(f, k) for k in ("origin", "resolution", "dims")):
+        raise ValueError(f"{name} must be a map or carry origin, resolution and dims, got {type(m).__name__}")
+    return f
+
+
+def quat_matrix(quat, name="quat"):
+    """One quaternion wxyz on the host -> the (3,3) float64 matrix of p -> q p conj(q), q normalised in f64: scan_rotations' matrix
+    before its rounding to f32."""
+    q = _host_rows(quat, 4, name, rows=1)[0]
+    n = np.sqrt((q * q).sum())
+    if not n > 0.0:
+        raise ValueError(f"{name}: a quaternion of length 0")
+    w, x, y, z = q / n
+    return np.array([[1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y)],
+                     [2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x)],
+                     [2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)]])
+
+
+def resample_affine(src_frame, dst_frame, pose, quat):
+    """The twelve integers the resample entries take ("Resampling maps") -> (12,) int64: M (3 x 3, row major) = rint(A
+    2^19), then T = rint(b 2^20), in f64, with world_dst = R(quat) world_src + pose — the pose of the source map's frame in the
+    destination's, quaternions wxyz as ScanMatch.world reads them — A = (r_d / r_s) R^T and b = (R^T (o_d - pose) - o_s) / r_s: the
+    centre of dst voxel d lies at A (d + 1/2) + b in source voxels.  The frames are maps or MapFrames (f32 origins and resolutions,
+    read as float64).  ValueError where |b| exceeds 2^20 voxels, where r_d > r_s (1 + 1e-6) — coarsening is a reduction, not a
+    resampling — or r_d < r_s / 8.  Needs no GPU."""
+    fs, fd = _frame_of(src_frame, "src_frame"), _frame_of(dst_frame, "dst_frame")
+    rs, rd = float(np.float32(fs.resolution)), float(np.float32(fd.resolution))
+    if not (rs > 0.0 and rd > 0.0 and np.isfinite(rs) and np.isfinite(rd)):
+        raise ValueError(f"the resolutions must be finite and > 0, got {rs!r} and {rd!r}")
+    if rd > rs * (1.0 + 1e-6):
+        raise ValueError(f"the destination's resolution {rd:g} is coarser than the source's {rs:g}: coarsening is a reduction, not a resampling")
+    if rd < rs * RESAMPLE_MIN_RATIO * (1.0 - 1e-6):
+        raise ValueError(f"the destination's resolution {rd:g} is finer than an eighth of the source's {rs:g}")
+    R = quat_matrix(quat)
+    t = _host_rows(pose, 3, "pose", rows=1)[0]
+    o_s = np.asarray(fs.origin, dtype=np.float32).astype(np.float64)
+    o_d = np.asarray(fd.origin, dtype=np.float32).astype(np.float64)
+    A = (rd / rs) * R.T
+    b = (R.T @ (o_d - t) - o_s) / rs
+    if not (np.abs(b) <= RESAMPLE_MAX_OFFSET).all():
+        raise ValueError(f"the destination's origin lies {tuple(b.tolist())} source voxels from the source's: beyond 2^20")
+    return np.concatenate([np.rint(A * float(1 << (RESAMPLE_FRAC_BITS - 1))).reshape(9), np.rint(b * float(1 << RESAMPLE_FRAC_BITS))]).astype(np.int64)
+
+
+def transformed_box(frame, pose, quat, resolution=None, anchor=None):
+    """The axis-aligned box around the eight corners of a map's box taken by world_dst = R(quat) world_src + pose, at `resolution`
+    (default: the map's), on the lattice through `anchor` (default: the world's origin) -> (k, dims): the box starts k voxels (three
+    integers) from the anchor — snapped down, a corner within 1/256 voxel above a lattice plane counting as on it — and holds dims
+    voxels, at least one per axis.  Host arithmetic in f64; needs no GPU."""
+    f = _frame_of(frame, "frame")
+    r_s = float(np.float32(f.resolution))
+    r = r_s if resolution is None else float(np.float32(resolution))
+    if not (np.isfinite(r) and r > 0.0):
+        raise ValueError(f"resolution must be a finite number > 0, got {resolution!r}")
+    R, t = quat_matrix(quat), _host_rows(pose, 3, "pose", rows=1)[0]
+    o = np.asarray(f.origin, dtype=np.float32).astype(np.float64)
+    ext = r_s * np.asarray(f.dims, dtype=np.float64)
+    corners = np.array([[o[0] + cx * ext[0], o[1] + cy * ext[1], o[2] + cz * ext[2]] for cx in (0, 1) for cy in (0, 1) for cz in (0, 1)])
+    w = corners @ R.T + t
+    a = np.zeros(3) if anchor is None else np.asarray(anchor, dtype=np.float32).astype(np.float64)
+    k = np.floor((w.min(axis=0) - a) / r + LATTICE_TOLERANCE)
+    n = np.maximum(np.ceil((w.max(axis=0) - a) / r - k - LATTICE_TOLERANCE), 1.0)
+    if not (np.isfinite(k).all() and np.isfinite(n).all() and (np.abs(k) < 2.0 ** 40).all() and (n < 2.0 ** 40).all()):
+        raise ValueError("the transformed box is not finite")
+    return tuple(int(v) for v in k), tuple(int(v) for v in n)
+
+
+def check_transform(map, pose, quat, origin=None, resolution=None, dims=None, like=None, rule="nearest"):
+    """transformed's arguments, by name; needs no GPU.  map: an OccupancyGrid, SpaceMap or EvidenceMap; pose (3,), quat (4,) wxyz:
+    world_dst = R(quat) world_src + pose; rule 'nearest' or 'cover'.  The new box: like= a map (its origin, resolution and dims; then
+    none of the other three may be given), or origin / resolution / dims, each defaulting — the resolution to the map's, the origin
+    to transformed_box's (a multiple of the resolution), dims to what reaches the far corners of the transformed box from the
+    origin.  Refused beyond MERGE_MAX_DIM per axis or MERGE_MAX_VOXELS.  -> (MapFrame of the new box, the (12,) int64 affine map);
+    ValueError otherwise."""
+    f = _map_frame(map, "map")
+    if rule not in RESAMPLE_RULES:
+        raise ValueError(f"rule must be 'nearest' or 'cover', got {rule!r}")
+    if like is not None:
+        if origin is not None or resolution is not None or dims is not None:
+            raise ValueError("like= brings origin, resolution and dims: give none of them with it")
+        fl = _frame_of(like, "like")
+        origin, resolution, dims = fl.origin, fl.resolution, fl.dims
+    r = f.resolution if resolution is None else resolution
+    k, n = transformed_box(f, pose, quat, r)
+    r64 = float(np.float32(r))
+    if origin is None:
+        origin = (np.asarray(k, dtype=np.float64) * r64).astype(np.float32)
+    elif dims is None:
+        o64 = np.asarray(origin, dtype=np.float32).astype(np.float64).reshape(-1)
+        if o64.shape != (3,) or not np.isfinite(o64).all():
+            raise ValueError(f"origin must be three finite numbers, got {origin!r}")
+        far = np.ceil((np.asarray(k, dtype=np.float64) + np.asarray(n, dtype=np.float64)) - o64 / r64 - LATTICE_TOLERANCE)
+        n = tuple(int(max(v, 1.0)) for v in far)
+    if dims is None:
+        dims = n
+        if max(dims) > MERGE_MAX_DIM or dims[0] * dims[1] * dims[2] > MERGE_MAX_VOXELS:
+            raise ValueError(f"the transformed box of {dims} voxels exceeds {MERGE_MAX_DIM} per axis or 2^31 voxels: give origin= and dims=, "
+                             "or a coarser map")
+    o, r, d, _ = check_los(origin, r, dims)
+    frame = MapFrame(o, r, d)
+    return frame, resample_affine(f, frame, pose, quat)
+
+
+def check_merge_posed(a, b, mode=None, pose=None, quat=None, rule="nearest"):
+    """A merge of b, whose frame stands at (pose, quat) in a's — world_a = R(quat) world_b + pose — into a; needs no GPU.  The kinds,
+    devices and mode as check_merge.  -> (shift, overlap, None) where the pose is the identity (pose 0, quat (w, 0, 0, 0)) and b sits
+    on a's lattice: the integer path, check_merge's answer; otherwise (None, True, the (12,) int64 affine map) for the resample
+    entries, which refuse an `a` coarser than b."""
+    if (pose is None) != (quat is None):
+        raise ValueError("pose and quat must be given together")
+    if rule not in RESAMPLE_RULES:
+        raise ValueError(f"rule must be 'nearest' or 'cover', got {rule!r}")
+    if pose is None:
+        return (*check_merge(a, b, mode), None)
+    t, q = _host_rows(pose, 3, "pose", rows=1)[0], _host_rows(quat, 4, "quat", rows=1)[0]
+    if not t.any() and not q[1:].any() and q[0] != 0.0:
+        try:
+            return (*check_merge(a, b, mode), None)
+        except ValueError as e:
+            if "not on one lattice" not in str(e):
+                raise
+    fa, fb = _map_frame(a, "a"), _map_frame(b, "other")
+    if type(a) is not type(b):
+        raise ValueError(f"a {type(a).__name__} merges with its own kind, got {type(b).__name__}")
+    if a is b:
+        raise ValueError("a map cannot be merged into itself")
+    if fa.device != fb.device:
+        raise ValueError(f"the maps must live on one device, got {fa.device} and {fb.device}")
+    if isinstance(a, EvidenceMap):
+        if mode not in ("confident", "add"):
+            raise ValueError(f"mode must be 'confident' or 'add', got {mode!r}")
+    elif mode is not None:
+        raise ValueError(f"mode applies to evidence maps only, got {mode!r} for a {type(a).__name__}")
+    return None, True, resample_affine(fb, fa, t, q)
+
+
+def _affine_arg(affine):
+    """The (12,) int64 affine map as the resample entries take it: a host array (kept alive by the caller) and frac_bits."""
+    a = np.ascontiguousarray(affine, dtype=np.int64)
+    return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), RESAMPLE_FRAC_BITS
 
 
 def check_occlusion_grid(grid, cloud):

@@ -1696,14 +1696,13 @@ def occ_transfer_ref(bits, dst_bits, shift, mode):
     return dst | S, int((S & ~dst).sum())
 
 
-def evidence_transfer_ref(L_src, L_dst, shift, mode, params=None):
-    """tohip_evid_transfer restated -> (L' (dst's shape) int64, counts (4,) int64).  S = the source values (-128 outside the source), D
-    = L_dst (not modified).  'copy': L' = S, counted against an empty destination.  'add': S == -128 leaves D, else clamp((D == -128 ?
-    0 : D) + S, lmin, lmax).  'confident': the larger of D and clamp(S) under the key (|L|, L), -128 below everything.  counts: values
-    that changed, voxels newly known, occupied (L > threshold) voxels that appeared, that vanished."""
+def evidence_combine_ref(S, L_dst, mode, params=None):
+    """The transfer and resample entries' combine of sampled source values S with the destination's D = L_dst (not modified) -> (L'
+    int64, counts (4,) int64).  'copy': L' = S, counted against an empty destination.  'add': S == -128 leaves D, else clamp((D == -128
+    ? 0 : D) + S, lmin, lmax).  'confident': the larger of D and clamp(S) under the key (|L|, L), -128 below everything.  counts:
+    values that changed, voxels newly known, occupied (L > threshold) voxels that appeared, that vanished."""
     _, _, lmin, lmax, thr = evidence_params(params)
     D = np.asarray(L_dst, dtype=np.int64)
-    S = shifted_window(np.asarray(L_src, dtype=np.int64), D.shape, shift, EVID_UNKNOWN)
     known = S != EVID_UNKNOWN
     if mode == "copy":
         D, out = np.full(D.shape, EVID_UNKNOWN, dtype=np.int64), S
@@ -1718,6 +1717,91 @@ def evidence_transfer_ref(L_src, L_dst, shift, mode, params=None):
     counts = np.array([(out != D).sum(), ((D == EVID_UNKNOWN) & (out != EVID_UNKNOWN)).sum(), ((out > thr) & ~(D > thr)).sum(),
                        ((D > thr) & ~(out > thr)).sum()], dtype=np.int64)
     return out, counts
+
+
+def evidence_transfer_ref(L_src, L_dst, shift, mode, params=None):
+    """tohip_evid_transfer restated -> (L' (dst's shape) int64, counts (4,) int64).  S = the source values (-128 outside the source), D
+    = L_dst (not modified).  'copy': L' = S, counted against an empty destination.  'add': S == -128 leaves D, else clamp((D == -128 ?
+    0 : D) + S, lmin, lmax).  'confident': the larger of D and clamp(S) under the key (|L|, L), -128 below everything.  counts: values
+    that changed, voxels newly known, occupied (L > threshold) voxels that appeared, that vanished."""
+    S = shifted_window(np.asarray(L_src, dtype=np.int64), np.shape(L_dst), shift, EVID_UNKNOWN)
+    return evidence_combine_ref(S, L_dst, mode, params)
+
+
+# ---- resampling maps restated in numpy (DESIGN.md 10, "Resampling maps"): what resample_kernels.hip must give, bit for bit, from the
+# same twelve integers (ops.resample_affine).  Dense (nx,ny,nz) arrays, int64 throughout. ---------------------------------------------
+RESAMPLE_FRAC_BITS = 20
+RESAMPLE_MAX_M, RESAMPLE_MAX_T = 1 << 21, 1 << 40
+RESAMPLE_EVID_RULES = ("nearest", "cover")
+RESAMPLE_OCC_RULES = ("nearest", "any", "all")
+
+
+def resample_nearest(affine, dst_dims):
+    """The twelve integers (M row major, then T) -> n (3, nx, ny, nz) int64, the nearest source voxel of every voxel of dst_dims: u_a =
+    M[a][0] (2 i + 1) + M[a][1] (2 j + 1) + M[a][2] (2 k + 1) + T[a], n_a = u_a >> 20 (numpy's >> of a negative int64 is arithmetic)."""
+    a = np.asarray(affine, dtype=np.int64).reshape(12)
+    if (np.abs(a[:9]) > RESAMPLE_MAX_M).any() or (np.abs(a[9:]) > RESAMPLE_MAX_T).any():
+        raise ValueError("the affine map exceeds |M| <= 2^21, |T| <= 2^40")
+    M, T = a[:9].reshape(3, 3), a[9:]
+    i, j, k = np.ix_(*(2 * np.arange(int(d), dtype=np.int64) + 1 for d in dst_dims))   # (open grids: the sums broadcast)
+    return np.stack([(M[r, 0] * i + M[r, 1] * j + M[r, 2] * k + T[r]) >> RESAMPLE_FRAC_BITS for r in range(3)])
+
+
+def _resample_take(src, n, empty):
+    """src at the voxels n (3, ...) where they lie inside src's shape, `empty` elsewhere."""
+    inside = np.ones(n.shape[1:], dtype=bool)
+    for a in range(3):
+        inside &= (n[a] >= 0) & (n[a] < src.shape[a])
+    c = [np.clip(n[a], 0, src.shape[a] - 1) for a in range(3)]
+    return np.where(inside, src[c[0], c[1], c[2]], empty)
+
+
+_RESAMPLE_TAPS = [np.array((dx, dy, dz), dtype=np.int64).reshape(3, 1, 1, 1) for dz in (-1, 0, 1) for dy in (-1, 0, 1) for dx in (-1, 0, 1)]
+
+
+def evid_sample_ref(L_src, affine, dst_dims, rule="nearest", threshold=0):
+    """The sampled source values S (dst_dims, int64).  'nearest': the value of n, -128 outside the source.  'cover': the maximum over
+    the 27 source voxels around n of the key free < unknown < occupied — 128 + L for L <= threshold, 256 for -128 and outside the
+    source, 640 + L above the threshold — decoded again."""
+    L = np.asarray(L_src, dtype=np.int64)
+    n = resample_nearest(affine, dst_dims)
+    if rule == "nearest":
+        return _resample_take(L, n, EVID_UNKNOWN)
+    if rule != "cover":
+        raise ValueError(f"rule must be 'nearest' or 'cover', got {rule!r}")
+    key = np.where(L == EVID_UNKNOWN, 256, np.where(L > threshold, 640 + L, 128 + L))
+    best = np.zeros(n.shape[1:], dtype=np.int64)
+    for tap in _RESAMPLE_TAPS:
+        best = np.maximum(best, _resample_take(key, n + tap, 256))
+    return np.where(best > 512, best - 640, np.where(best == 256, EVID_UNKNOWN, best - 128))
+
+
+def evid_resample_ref(L_src, L_dst, affine, rule, mode, params=None):
+    """tohip_evid_resample restated -> (L' (dst's shape) int64, counts (4,) int64): evid_sample_ref's S under the parameters'
+    threshold, combined with L_dst (not modified) as the transfer does (evidence_combine_ref)."""
+    S = evid_sample_ref(L_src, affine, np.shape(L_dst), rule, evidence_params(params)[4])
+    return evidence_combine_ref(S, L_dst, mode, params)
+
+
+def occ_resample_ref(bits, dst_bits, affine, rule, mode):
+    """tohip_occ_resample restated -> (new (dst's shape) bool, count).  rule 'nearest': the bit of n; 'any': the OR of the 27 bits
+    around n; 'all': their AND, a voxel outside the source counting 0.  mode 'copy' / 'or' and the count as occ_transfer_ref."""
+    src, dst = np.asarray(bits, dtype=bool), np.asarray(dst_bits, dtype=bool)
+    n = resample_nearest(affine, dst.shape)
+    if rule == "nearest":
+        S = _resample_take(src, n, False)
+    elif rule in ("any", "all"):
+        S = np.full(dst.shape, rule == "all")
+        for tap in _RESAMPLE_TAPS:
+            t = _resample_take(src, n + tap, False)
+            S = (S | t) if rule == "any" else (S & t)
+    else:
+        raise ValueError(f"rule must be 'nearest', 'any' or 'all', got {rule!r}")
+    if mode == "copy":
+        return S, int(S.sum())
+    if mode != "or":
+        raise ValueError(f"mode must be 'copy' or 'or', got {mode!r}")
+    return dst | S, int((S & ~dst).sum())
 
 
 def pillar_scan(room, origin, lo, hi):

@@ -638,8 +638,7 @@ def evidence_map(grid_or_points, resolution=0.1, **params):
     return ops.EvidenceMap.like(ops.OccupancyGrid.from_points(grid_or_points, resolution=resolution), **params)
 
 
-MERGE_MAX_DIM = 2048        # of a merged map's box per axis
-MERGE_MAX_VOXELS = 1 << 31
+MERGE_MAX_DIM, MERGE_MAX_VOXELS = ops.MERGE_MAX_DIM, ops.MERGE_MAX_VOXELS   # of a merged or transformed map's box: per axis, in all
 
 
 def reframe_map(map, shift=None, dims=None, centre=None):
@@ -648,7 +647,8 @@ def reframe_map(map, shift=None, dims=None, centre=None):
     integers: new voxel v is old voxel v + shift — or centre, a world position whose voxel becomes the new box's middle voxel dims //
     2; dims: the new box's (default: the old one's): grow, crop or move.  What leaves the box is dropped, what enters it is empty
     (unknown).  The old map is untouched; a ClearanceField, TravelField, Components or ModelTraj(clearance_map=) built over it keeps
-    it and is built anew over the new one.  No rotation, no resampling: the move is a whole number of voxels."""
+    it and is built anew over the new one.  The move is a whole number of voxels and copies bits and bytes; transform_map is the call
+    that rotates, shifts by a fraction of a voxel or refines the resolution."""
     ops.check_reframe(map, shift, dims, centre)
     return map.reframed(shift=shift, dims=dims, centre=centre)
 
@@ -674,34 +674,89 @@ def follow_map(map, position, margin):
     return map.reframed(centre=position)
 
 
-def merge_maps(maps, mode=None):
+def transform_map(map, pose, quat, origin=None, resolution=None, dims=None, like=None, rule="nearest"):
+    """A map under a rigid transform and, if asked, at a finer resolution -> a NEW map of the same kind and parameters (DESIGN.md 10,
+    "Resampling maps"): an ops.OccupancyGrid, ops.SpaceMap or ops.EvidenceMap; the old one is only read.  pose (3,), quat (4,) wxyz:
+    world_new = R(quat) world_old + pose — the pose of the old map's frame in the new one, what align_maps and register_scan return,
+    or a pose-graph correction.  The new box: like= a map whose frame to take, or origin / resolution / dims; by default the
+    axis-aligned box around the old box's transformed corners at the old resolution, its origin a multiple of it (ValueError beyond
+    2048 voxels an axis or 2^31 voxels).  rule 'nearest': each new voxel takes the old voxel that holds its centre — unbiased, the
+    rule for evidence that will be fused; a wall one voxel thick may show pinholes after a rotation.  rule 'cover', for planning: the
+    maximum over the 3 x 3 x 3 old voxels around it under free < unknown < occupied (planes: OR for occupied, AND for free) — no
+    occupied voxel is lost, nothing is free unless all it touches was free, a ray cannot slip through a wall; walls and the unknown
+    grow by up to a voxel.  Not a coarsening: a resolution coarser than the map's is refused, one finer than an eighth of it too.
+    A ClearanceField, TravelField or Components over the old map is built anew over the new one."""
+    ops.check_transform(map, pose, quat, origin, resolution, dims, like, rule)
+    return map.transformed(pose, quat, origin=origin, resolution=resolution, dims=dims, like=like, rule=rule)
+
+
+def merge_maps(maps, mode=None, poses=None, quats=None, rule="nearest"):
     """Fuse a team's maps into one -> a NEW map over the union of their boxes; the inputs are only read.  maps: two or more
-    ops.OccupancyGrids, ops.SpaceMaps or ops.EvidenceMaps (one kind) on one device and one lattice — equal resolutions, origins a
-    whole number of voxels apart (ops.lattice_offset; ValueError names the axis otherwise).  The first map is re-framed into the
-    union box — which keeps its parameters — and the others are merged into it: planes by OR; evidence by mode 'confident' (the
-    default: per voxel the stronger belief wins; any order and any repetition give the same map) or 'add' (independent evidence
+    ops.OccupancyGrids, ops.SpaceMaps or ops.EvidenceMaps (one kind) on one device.  Without poses they share one lattice — equal
+    resolutions, origins a whole number of voxels apart (ops.lattice_offset; ValueError names the axis otherwise).  poses (n,3) and
+    quats (n,4) wxyz place map i's frame in map 0's — world_0 = R(quats[i]) world_i + poses[i], what align_maps(maps[0], maps[i], ...)
+    returns; row 0 is the identity — and the union is taken over the transformed boxes on map 0's lattice; a map whose pose is the
+    identity and which sits on that lattice moves by a voxel shift, every other one is resampled under `rule` ('nearest', unbiased,
+    or 'cover', conservative: transform_map says what each gives) and must not be finer than map 0.  The first map is re-framed
+    into the union box — which keeps its parameters — and the others are merged into it: planes by OR; evidence by mode 'confident'
+    (the default: per voxel the stronger belief wins; any order and any repetition give the same map) or 'add' (independent evidence
     summed and clamped; a map given twice counts twice).  ValueError if the union exceeds 2048 voxels on an axis or 2^31 voxels."""
     maps = list(maps)
     if len(maps) < 2:
         raise ValueError(f"merge_maps: at least two maps are needed, got {len(maps)}")
+    if (poses is None) != (quats is None):
+        raise ValueError("merge_maps: poses and quats must be given together")
     first = maps[0]
     evidence = isinstance(first, ops.EvidenceMap)
     mode = ("confident" if mode is None else mode) if evidence else mode
-    offsets = [(0, 0, 0)]
-    for m in maps[1:]:
-        if m is not first:   # (the first map again: merged into the new map like any other)
-            ops.check_merge(first, m, mode)
-        offsets.append(ops.lattice_offset(first, m))
     frames = [ops._map_frame(m, "map") for m in maps]
-    lo = tuple(min(o[a] for o in offsets) for a in range(3))
-    hi = tuple(max(o[a] + f.dims[a] for o, f in zip(offsets, frames)) for a in range(3))
+    if poses is None:
+        placed = [(None, None)] * len(maps)
+    else:
+        t, q = ops._host_rows(poses, 3, "poses"), ops._host_rows(quats, 4, "quats")
+        if len(t) != len(maps) or len(q) != len(maps):
+            raise ValueError(f"merge_maps: {len(maps)} maps need as many poses and quats, got {len(t)} and {len(q)}")
+        if t[0].any() or q[0][1:].any() or q[0][0] == 0.0:
+            raise ValueError("merge_maps: the poses place each map in map 0's frame: row 0 must be the identity (pose 0, quat (1, 0, 0, 0))")
+        placed = list(zip(t, q))
+    boxes = [((0, 0, 0), frames[0].dims)]
+    for m, f, (pose, quat) in list(zip(maps, frames, placed))[1:]:
+        affine = None
+        if m is not first:   # (the first map again: merged into the new map like any other)
+            s, _, affine = ops.check_merge_posed(first, m, mode, pose, quat, rule)
+        if affine is None:
+            boxes.append((ops.lattice_offset(first, m), f.dims))
+        else:
+            boxes.append(ops.transformed_box(f, pose, quat, frames[0].resolution, anchor=frames[0].origin))
+    lo = tuple(min(k[a] for k, _ in boxes) for a in range(3))
+    hi = tuple(max(k[a] + n[a] for k, n in boxes) for a in range(3))
     dims = tuple(h - l for l, h in zip(lo, hi))
     if max(dims) > MERGE_MAX_DIM or dims[0] * dims[1] * dims[2] > MERGE_MAX_VOXELS:
         raise ValueError(f"merge_maps: the union box of {dims} voxels exceeds {MERGE_MAX_DIM} per axis or 2^31 voxels")
     out = first.reframed(shift=lo, dims=dims)
-    for m in maps[1:]:
-        out.merge(m, mode) if evidence else out.merge(m)
+    for m, (pose, quat) in list(zip(maps, placed))[1:]:
+        kw = {} if pose is None else dict(pose=pose, quat=quat, rule=rule)
+        out.merge(m, mode, **kw) if evidence else out.merge(m, **kw)
     return out
+
+
+def align_maps(target, source, pose, quat, window=None, yaw=None, iterations=30, dof="xyzrpw"):
+    """Where does one map's frame stand in another's?  -> ScanRegistration whose .pose, .quat satisfy world_target = R(quat)
+    world_source + pose and go straight into merge_maps(poses=, quats=) and transform_map.  Host composition of what exists: the
+    centres of `source`'s occupied voxels (export(), in the source's frame) are the scan; relocalise_scan finds the best integer
+    shift within `window` (None: all of the target's x and y) and heading of yaw=(half_range_rad, n) around the prior (pose, quat),
+    register_scan refines it below a voxel over `dof` in `iterations` rounds.  target: an ops.EvidenceMap or an ops.ScanMatcher over
+    one; source: an ops.OccupancyGrid, SpaceMap or EvidenceMap.  The answer is as good as the two maps' overlap: the matchers' own
+    limits (one voxel and one step of the yaw list before the refinement, a basin of about a voxel for it) apply, and two rooms that
+    look alike align as happily as one room seen twice."""
+    matcher = _scan_matcher("align_maps", target, None, 0)
+    ops._map_frame(source, "source")
+    plane = source if isinstance(source, ops.OccupancyGrid) else source.occupied
+    _, centres = plane.export()
+    if centres.shape[0] == 0:
+        raise ValueError("align_maps: the source map has no occupied voxel")
+    found = relocalise_scan(matcher, centres, pose, quat, window=window, yaw=yaw)
+    return register_scan(matcher, centres, found.pose, found.quat, iterations=iterations, dof=dof)
 
 
 class _Result:
