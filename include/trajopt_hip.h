@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_occ_resample / tohip_evid_resample and the TOHIP_RESAMPLE_* constants (resampling maps: voxel content of one box read
+/* (still 15) + tohip_occ_coarsen / tohip_evid_coarsen and the TOHIP_COARSEN_* constants (coarsening maps: f x f x f voxels of one box reduced
+ * to one voxel of a coarser box under a conservative or an optimistic rule, written or combined as the transfers do): new symbols only.
+ * (still 15) + tohip_occ_resample / tohip_evid_resample and the TOHIP_RESAMPLE_* constants (resampling maps: voxel content of one box read
  * in another under a rigid transform and a change of resolution, by an integer affine map the host quantises once): new symbols only.
  * (still 15) + tohip_posegraph_workspace_bytes / tohip_posegraph_layout / tohip_posegraph_start / tohip_posegraph_linearize /
  * tohip_posegraph_gather / tohip_posegraph_step / tohip_posegraph_optimize / tohip_posegraph_result and the TOHIP_POSEGRAPH_* constants
@@ -1341,6 +1343,43 @@ int tohip_evid_resample(const void *src, size_t src_bytes, const tohip_occ_geom 
                         const tohip_occ_geom *dst_geom, void *occupied_out, void *free_out, size_t grid_bytes,
                         const int64_t *affine_host, int32_t frac_bits, int32_t rule, int32_t mode, int32_t lmin, int32_t lmax,
                         int32_t threshold, uint64_t *counts, void *scratch, size_t scratch_bytes, void *stream, uint32_t flags);
+
+/* ---- coarsening maps (coarsen_kernels.hip, DESIGN.md §10, "Coarsening maps") ----
+ * The transfers above across an integer change of scale: f x f x f source voxels reduced to one dst voxel.  src and dst are two
+ * DIFFERENT buffers, each with its own geometry.  factor f in [2, TOHIP_COARSEN_MAX_FACTOR], the same on all axes; (ox, oy, oz) an
+ * integer offset, each component in [-2^20, 2^20].  The CHILDREN of dst voxel d are the f^3 source voxels f d + o + e, e in [0, f)^3;
+ * a child outside src's dims is EMPTY: -128, bit 0.  Origins and resolutions of the two geometries are checked as everywhere and not
+ * interpreted: the caller computes o and checks r_d = f r_s.  The SOURCE VALUE S of d is, by rule:
+ *   TOHIP_COARSEN_COVER  (evidence) the maximum of the children under the key free < unknown < occupied, TOHIP_RESAMPLE_COVER's: the
+ *                        largest value above `threshold` if there is one; otherwise -128 if a child is -128 or outside; otherwise the
+ *                        largest (least free) value.  Conservative for planning: an occupied child makes d occupied, and d is free
+ *                        only where all f^3 children lie inside src's dims and are free.
+ *   TOHIP_COARSEN_MAX    (evidence) the largest child as a signed byte, -128 only where every child is EMPTY: occupied if any child
+ *                        is, and optimistic about the unknown — for display, occlusion and matching, not for collision checks.
+ *   TOHIP_COARSEN_ANY    (planes) the OR of the child bits;  TOHIP_COARSEN_ALL: their AND, a child outside src's dims counting 0.
+ * veto_or_null (tohip_occ_coarsen, rule ANY only; TOHIP_EINVAL with ALL): a plane of src's geometry and size; with it
+ * S = ANY(src) & ~ANY(veto) — the free plane of a three-state map under MAX, vetoed by its occupied plane.  Both keys are total orders
+ * on the byte, so the maximum is associative and commutative: factor f1 then f2 equals factor f1 f2 once (offset o1 + f1 o2), and any
+ * split of the work gives the same bytes.  S is then written or combined exactly as the transfers do it: tohip_occ_coarsen with mode
+ * COPY (0) / OR (1) and one count; tohip_evid_coarsen with mode COPY (0) / ADD (1) / CONFIDENT (2), the two derived planes, the pads,
+ * the headers, the rule that in ADD and CONFIDENT a brick with no S other than -128 inside dst's dims is neither read nor written,
+ * and the four counts — all as documented for tohip_evid_transfer; `threshold` also classifies the children under COVER.  src and the
+ * veto are only read.  flags is reserved and must be 0.  src, the veto, dst, the planes and counts must be different buffers.  A bad
+ * factor, offset, rule, mode or flags, an aliased buffer: TOHIP_EINVAL; a short buffer: TOHIP_ENOSPC.  Every argument check returns
+ * before anything is enqueued; nothing synchronises with the host; integers only, one lane owns a dst word or brick and no atomic
+ * touches a plane or a value: the same bytes in every run and for every launch shape. */
+#define TOHIP_COARSEN_MAX_FACTOR 8
+#define TOHIP_COARSEN_COVER 0
+#define TOHIP_COARSEN_MAX 1
+#define TOHIP_COARSEN_ANY 0
+#define TOHIP_COARSEN_ALL 1
+int tohip_occ_coarsen(const void *src, size_t src_bytes, const tohip_occ_geom *src_geom, const void *veto_or_null, void *dst,
+                      size_t dst_bytes, const tohip_occ_geom *dst_geom, int32_t factor, int32_t ox, int32_t oy, int32_t oz, int32_t rule,
+                      int32_t mode, uint64_t *counts, void *stream, uint32_t flags);
+int tohip_evid_coarsen(const void *src, size_t src_bytes, const tohip_occ_geom *src_geom, void *dst, size_t dst_bytes,
+                       const tohip_occ_geom *dst_geom, void *occupied_out, void *free_out, size_t grid_bytes, int32_t factor, int32_t ox,
+                       int32_t oy, int32_t oz, int32_t rule, int32_t mode, int32_t lmin, int32_t lmax, int32_t threshold, uint64_t *counts,
+                       void *stream, uint32_t flags);
 
 /* ---- clearance from the map (clearance_map_kernels.hip, DESIGN.md §10, "Clearance from the map") -------
  * tohip_clearance and tohip_clearance_segments with the voxels of an occupancy grid as the obstacles.  occupied: a grid buffer of

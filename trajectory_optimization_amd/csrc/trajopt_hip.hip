@@ -26,6 +26,7 @@
 #include "scansearch_kernels.hip"
 #include "reframe_kernels.hip"
 #include "resample_kernels.hip"
+#include "coarsen_kernels.hip"
 #include "travel_kernels.hip"
 #include "components_kernels.hip"
 #include "ground_kernels.hip"

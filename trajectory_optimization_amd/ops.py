@@ -930,6 +930,33 @@ class OccupancyGrid:
             _map_call(self.device, "tohip_occ_transfer", *other._sizes(), *self._sizes(), *s, XFER_MODES["or"], ptr(counts))
         return self
 
+    def _coarsen(self, src, factor, offset, rule, mode, counts, veto=None):
+        _map_call0(self.device, "tohip_occ_coarsen", *src._sizes(), ptr(veto.buf) if veto is not None else None, *self._sizes(), factor, *offset,
+                   COARSEN_OCC_RULES[rule], XFER_MODES[mode], ptr(counts))
+
+    def coarsened(self, factor=2, rule="any", anchor="origin", origin=None, dims=None, like=None, _veto=None):
+        """This grid at `factor` times its voxel edge -> a NEW grid (tohip_occ_coarsen, DESIGN.md 10 "Coarsening maps"); this one is only
+        read.  factor: an integer in [2, 8]; a coarse voxel's bit is the OR (rule 'any', the default: no set voxel is lost) or the AND
+        (rule 'all': a voxel outside this grid counts 0) of its factor^3 children.  anchor 'origin': the coarse box starts at this
+        grid's origin and holds ceil(n / factor) voxels an axis.  anchor 'world': the coarse lattice's planes lie at multiples of the
+        coarse edge, so coarse grids of any sources on one fine lattice share a lattice and merge as they are.  origin / dims / like:
+        another box (check_coarsen).  One launch, nothing read back; `skipped` carries over."""
+        frame, o, rule = check_coarsen(self, factor, rule, anchor, origin, dims, like)
+        out = OccupancyGrid(frame.origin, frame.resolution, frame.dims, device=self.device)
+        out._coarsen(self, int(factor), o, rule, "copy", None, _veto)
+        out.skipped = self.skipped
+        return out
+
+    def merge_fine(self, fine, rule="any", counts=None):
+        """OR a FINER grid into this one, in place -> self; `fine` is only read.  The factor (2 .. 8) and the offset come from the two
+        frames (check_merge_fine): this grid's resolution is a whole multiple of the other's and the origins lie a whole number of
+        fine voxels apart.  Each of this grid's voxels takes the OR ('any') or AND ('all') of its children.  counts: a zero-filled
+        (1,) int64 device tensor that receives += the bits that were not set before, or None.  One launch, nothing read back."""
+        factor, o, rule = check_merge_fine(self, fine, None, rule)
+        _check_counts(counts, 1, self.device)
+        self._coarsen(fine, factor, o, rule, "or", counts)
+        return self
+
     def carve(self, origins, points, max_range=None, stats=None, flags=None):
         """Treat this grid as a FREE PLANE (a set bit: "a ray passed through") and set the bit of every voxel the rays origins[i] ->
         points[i] cross, walked exactly as line_of_sight walks (tohip_occ_carve).  origins: (3,) / (1,3) for one origin
@@ -1107,6 +1134,29 @@ class SpaceMap:
         cover = rule == "cover"
         self.occupied.merge(other.occupied, pose=pose, quat=quat, rule=rule, _plane_rule="any" if cover else None)
         self.free.merge(other.free, pose=pose, quat=quat, rule=rule, _plane_rule="all" if cover else None)
+        return self
+
+    def coarsened(self, factor=2, rule="cover", anchor="origin", origin=None, dims=None, like=None):
+        """Both planes at `factor` times the voxel edge (OccupancyGrid.coarsened) -> a NEW SpaceMap over two new grids; this map is
+        only read.  rule 'cover', for planning: occupied takes the OR of its children and free their AND (outside the box counts as
+        not free) — no occupied voxel is lost and a coarse voxel is free only where all it holds is free.  rule 'max', for display,
+        occlusion and matching: occupied takes the OR, free the OR of the free children unless one of them is occupied — the unknown
+        is passed over.  The planes stay disjoint under both."""
+        frame, _, rule = check_coarsen(self, factor, rule, anchor, origin, dims, like)
+        occupied = self.occupied.coarsened(factor, "any", like=frame)
+        if rule == "cover":
+            return SpaceMap(occupied, self.free.coarsened(factor, "all", like=frame))
+        return SpaceMap(occupied, self.free.coarsened(factor, "any", like=frame, _veto=self.occupied))
+
+    def merge_fine(self, fine, rule="cover"):
+        """OR both planes of a FINER SpaceMap into this one's, in place -> self: the occupied plane by ANY; the free plane by ALL (rule
+        'cover') or by ANY vetoed by the finer map's occupied plane ('max').  Factor and offset come from the two frames."""
+        factor, o, rule = check_merge_fine(self, fine, None, rule)
+        self.occupied._coarsen(fine.occupied, factor, o, "any", "or", None)
+        if rule == "cover":
+            self.free._coarsen(fine.free, factor, o, "all", "or", None)
+        else:
+            self.free._coarsen(fine.free, factor, o, "any", "or", None, fine.occupied)
         return self
 
     def state(self, positions):
@@ -2041,6 +2091,38 @@ class EvidenceMap:
             self._resample(other, affine, rule, mode, counts)
         elif overlap:
             self._transfer(other, s, mode, counts)
+        return self
+
+    def _coarsen(self, src, factor, offset, rule, mode, counts):
+        _, _, lmin, lmax, threshold = self.params
+        _map_call0(self.device, "tohip_evid_coarsen", *src._sizes(), *self._sizes(), ptr(self.occupied.buf), ptr(self.free.buf),
+                   self.occupied.buf.numel(), factor, *offset, COARSEN_RULES[rule], XFER_MODES[mode], lmin, lmax, threshold, ptr(counts))
+
+    def coarsened(self, factor=2, rule="cover", anchor="origin", origin=None, dims=None, like=None):
+        """This map at `factor` times its voxel edge -> a NEW EvidenceMap of the same parameters (tohip_evid_coarsen, DESIGN.md 10
+        "Coarsening maps"): a new buffer, both planes derived from it, empty scratch planes; this map is only read.  factor: an
+        integer in [2, 8].  rule 'cover', for planning: the maximum of a coarse voxel's factor^3 children under free < unknown <
+        occupied — the strongest occupied value if a child is occupied, else unknown if a child is unknown or lies outside this map,
+        else the least free value: no occupied voxel is lost and nothing is free unless all it holds is free.  rule 'max', for
+        display, occlusion and matching: the largest child as a number, unknown only where every child is — occupied if any child
+        is, and optimistic about the unknown.  anchor, origin, dims, like: the coarse box, as OccupancyGrid.coarsened takes them.
+        One launch, nothing read back; the new map's last_counts() tells what it holds (known voxels, twice; occupied voxels; 0)."""
+        frame, o, rule = check_coarsen(self, factor, rule, anchor, origin, dims, like)
+        hit, miss, lmin, lmax, threshold = self.params
+        out = EvidenceMap(frame.origin, frame.resolution, frame.dims, hit, miss, lmin, lmax, threshold, device=self.device)
+        out._coarsen(self, int(factor), o, rule, "copy", out._counts)
+        return out
+
+    def merge_fine(self, fine, mode="confident", rule="cover", counts=None):
+        """Fuse a FINER EvidenceMap into this one, in place -> self; `fine` is only read, both planes stay exact.  The factor (2 .. 8)
+        and the offset come from the two frames (check_merge_fine).  Each of this map's voxels reduces its children under `rule`
+        (coarsened says what each gives; the threshold is this map's) and the result goes through merge's combine: mode 'confident'
+        or 'add', counts as merge takes them.  One launch, nothing read back."""
+        factor, o, rule = check_merge_fine(self, fine, mode, rule)
+        _check_counts(counts, 4, self.device)
+        if counts is None:
+            counts = self._counts.zero_()
+        self._coarsen(fine, factor, o, rule, mode, counts)
         return self
 
     def last_counts(self):
@@ -3198,7 +3280,8 @@ def resample_affine(src_frame, dst_frame, pose, quat):
     if not (rs > 0.0 and rd > 0.0 and np.isfinite(rs) and np.isfinite(rd)):
         raise ValueError(f"the resolutions must be finite and > 0, got {rs!r} and {rd!r}")
     if rd > rs * (1.0 + 1e-6):
-        raise ValueError(f"the destination's resolution {rd:g} is coarser than the source's {rs:g}: coarsening is a reduction, not a resampling")
+        raise ValueError(f"the destination's resolution {rd:g} is coarser than the source's {rs:g}: coarsening is a reduction, not a resampling "
+                         "(coarsened() / tools.coarsen_map reduce by a whole factor)")
     if rd < rs * RESAMPLE_MIN_RATIO * (1.0 - 1e-6):
         raise ValueError(f"the destination's resolution {rd:g} is finer than an eighth of the source's {rs:g}")
     R = quat_matrix(quat)
@@ -3302,6 +3385,132 @@ def check_merge_posed(a, b, mode=None, pose=None, quat=None, rule="nearest"):
     elif mode is not None:
         raise ValueError(f"mode applies to evidence maps only, got {mode!r} for a {type(a).__name__}")
     return None, True, resample_affine(fb, fa, t, q)
+
+
+COARSEN_MAX_FACTOR = 8      # of tohip_occ_coarsen / tohip_evid_coarsen, the same on all axes
+COARSEN_MAX_OFFSET = 1 << 20   # source voxels between the two origins
+COARSEN_RULES = {"cover": 0, "max": 1}
+COARSEN_OCC_RULES = {"any": 0, "all": 1}
+COARSEN_ANCHORS = ("origin", "world")
+
+
+def _coarsen_factor(factor):
+    if not _is_int(factor) or not 2 <= factor <= COARSEN_MAX_FACTOR:
+        raise ValueError(f"factor must be an integer in [2, {COARSEN_MAX_FACTOR}], got {factor!r}")
+    return int(factor)
+
+
+def _coarsen_rule(map, rule):
+    """The rule by name for the map's kind (None: the kind's default): planes 'any' / 'all', three-state and evidence maps 'cover' / 'max'."""
+    names = COARSEN_OCC_RULES if isinstance(map, OccupancyGrid) else COARSEN_RULES
+    if rule is None:
+        return next(iter(names))
+    if rule not in names:
+        raise ValueError(f"rule must be {' or '.join(repr(n) for n in names)} for a {type(map).__name__}, got {rule!r}")
+    return rule
+
+
+def coarsen_offset(src_frame, dst_frame, factor):
+    """A fine and a coarse frame -> the integer offset (ox, oy, oz) the coarsen entries take ("Coarsening maps"): the
+    children of dst voxel d are the source voxels factor d + o + e, e in [0, factor)^3, so o is the coarse origin's place in source
+    voxels.  The frames are maps or MapFrames (f32 origins and resolutions, read as float64).  ValueError unless factor is an integer
+    in [2, 8], r_d = factor r_s within 1e-6 relative, the origins lie a whole number of source voxels apart within 1/256 voxel
+    (lattice_offset's rule) and at most 2^20 of them.  Needs no GPU."""
+    f = _coarsen_factor(factor)
+    fs, fd = _frame_of(src_frame, "src_frame"), _frame_of(dst_frame, "dst_frame")
+    rs, rd = float(np.float32(fs.resolution)), float(np.float32(fd.resolution))
+    if not (rs > 0.0 and rd > 0.0 and np.isfinite(rs) and np.isfinite(rd)):
+        raise ValueError(f"the resolutions must be finite and > 0, got {rs!r} and {rd!r}")
+    if not abs(rd - f * rs) <= 1e-6 * f * rs:
+        raise ValueError(f"the coarse resolution {rd:g} is not {f} times the fine one {rs:g}")
+    o_s = np.asarray(fs.origin, dtype=np.float32).astype(np.float64)
+    o_d = np.asarray(fd.origin, dtype=np.float32).astype(np.float64)
+    d = (o_d - o_s) / rs
+    k = np.rint(d)
+    for axis in range(3):
+        if not abs(d[axis] - k[axis]) <= LATTICE_TOLERANCE:
+            raise ValueError(f"the coarse box is not on the fine lattice: along {'xyz'[axis]} the origins {tuple(o_s.tolist())} and "
+                             f"{tuple(o_d.tolist())} lie {d[axis]:.6g} fine voxels apart, not within 1/256 of an integer")
+    if not (np.abs(k) <= COARSEN_MAX_OFFSET).all():
+        raise ValueError(f"the coarse origin lies {tuple(k.tolist())} fine voxels from the fine one: beyond 2^20")
+    return tuple(int(v) for v in k)
+
+
+def check_coarsen(map, factor=2, rule=None, anchor="origin", origin=None, dims=None, like=None):
+    """coarsened's arguments, by name; needs no GPU.  map: an OccupancyGrid, SpaceMap or EvidenceMap; factor: an integer in [2, 8];
+    rule: 'any' or 'all' for an OccupancyGrid, 'cover' or 'max' for the other two (None: the first).  The coarse box has resolution
+    float32(factor r) and: like= a map or MapFrame (its origin, resolution and dims; none of the other three with it); or origin=
+    (three finite numbers a whole number of fine voxels from the map's origin) and / or dims=; by default what `anchor` says —
+    'origin': o = 0, the map's origin, dims ceil(n / factor); 'world': the coarse lattice's planes at multiples of factor r, o_a =
+    -(round(origin_a / r) mod factor), refused where the map's origin is not within 1/256 voxel of a multiple of r.  dims defaults to
+    ceil((n - o) / factor), at least 1.  Refused beyond MERGE_MAX_DIM per axis or MERGE_MAX_VOXELS.  -> (MapFrame of the coarse box,
+    the offset (ox, oy, oz), the rule's name); ValueError otherwise."""
+    fr = _map_frame(map, "map")
+    f = _coarsen_factor(factor)
+    rule = _coarsen_rule(map, rule)
+    if anchor not in COARSEN_ANCHORS:
+        raise ValueError(f"anchor must be 'origin' or 'world', got {anchor!r}")
+    rs = float(np.float32(fr.resolution))
+    rd = float(np.float32(f * rs))
+    if like is not None:
+        if origin is not None or dims is not None:
+            raise ValueError("like= brings origin and dims: give neither with it")
+        fl = _frame_of(like, "like")
+        o = coarsen_offset(fr, fl, f)
+        frame = MapFrame(*check_los(fl.origin, fl.resolution, fl.dims)[:3])
+        return frame, o, rule
+    if origin is None:
+        if anchor == "origin":
+            o = (0, 0, 0)
+        else:
+            q = np.asarray(fr.origin, dtype=np.float32).astype(np.float64) / rs
+            k = np.rint(q)
+            if not (np.abs(q - k) <= LATTICE_TOLERANCE).all():
+                raise ValueError(f"anchor='world' needs the map's origin {tuple(fr.origin.tolist())} within 1/256 voxel of a multiple of its "
+                                 f"resolution {rs:g}: it lies at {tuple(q.tolist())} voxels")
+            o = tuple(-(int(v) % f) for v in k)
+        origin = reframed_origin(fr.origin, rs, o)
+    else:
+        try:
+            o32 = np.asarray(origin, dtype=np.float32).reshape(-1)
+        except (TypeError, ValueError):
+            o32 = np.zeros(0, dtype=np.float32)
+        if o32.shape != (3,) or not np.isfinite(o32).all():
+            raise ValueError(f"origin must be three finite numbers, got {origin!r}")
+        o = coarsen_offset(fr, MapFrame(o32, rd, (1, 1, 1)), f)
+        origin = o32
+    if dims is None:
+        dims = tuple(max(-((o_a - n) // f), 1) for n, o_a in zip(fr.dims, o))   # ceil((n - o) / f)
+        if max(dims) > MERGE_MAX_DIM or dims[0] * dims[1] * dims[2] > MERGE_MAX_VOXELS:
+            raise ValueError(f"the coarse box of {dims} voxels exceeds {MERGE_MAX_DIM} per axis or 2^31 voxels: give dims=")
+    og, rg, dg, _ = check_los(origin, rd, dims)
+    return MapFrame(og, rg, dg), o, rule
+
+
+def check_merge_fine(coarse, fine, mode=None, rule=None):
+    """merge_fine's arguments, by name; needs no GPU.  coarse (written) and fine (read): two different maps of one kind on one device,
+    the coarse one's resolution 2 .. 8 times the fine one's (within 1e-6 relative) and the origins a whole number of fine voxels
+    apart (coarsen_offset); mode: None for planes, 'confident' or 'add' for evidence; rule as check_coarsen.
+    -> (factor, offset, the rule's name); ValueError otherwise."""
+    fc, ff = _map_frame(coarse, "coarse"), _map_frame(fine, "fine")
+    if type(coarse) is not type(fine):
+        raise ValueError(f"a {type(coarse).__name__} merges with its own kind, got {type(fine).__name__}")
+    if coarse is fine:
+        raise ValueError("a map cannot be merged into itself")
+    if fc.device != ff.device:
+        raise ValueError(f"the maps must live on one device, got {fc.device} and {ff.device}")
+    if isinstance(coarse, EvidenceMap):
+        if mode not in ("confident", "add"):
+            raise ValueError(f"mode must be 'confident' or 'add', got {mode!r}")
+    elif mode is not None:
+        raise ValueError(f"mode applies to evidence maps only, got {mode!r} for a {type(coarse).__name__}")
+    rule = _coarsen_rule(coarse, rule)
+    ratio = float(np.float32(fc.resolution)) / float(np.float32(ff.resolution))
+    f = int(round(ratio)) if np.isfinite(ratio) else 0
+    if not 2 <= f <= COARSEN_MAX_FACTOR:
+        raise ValueError(f"merge_fine takes a map 2 to {COARSEN_MAX_FACTOR} times finer than this one: the resolutions {fc.resolution:g} and "
+                         f"{ff.resolution:g} stand {ratio:g} to 1")
+    return f, coarsen_offset(ff, fc, f), rule
 
 
 def _affine_arg(affine):

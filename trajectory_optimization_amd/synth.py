@@ -1804,6 +1804,64 @@ def occ_resample_ref(bits, dst_bits, affine, rule, mode):
     return dst | S, int((S & ~dst).sum())
 
 
+# ---- coarsening maps restated in numpy ("Coarsening maps"): what coarsen_kernels.hip must give, bit for bit, from the
+# factor and the integer offset (ops.coarsen_offset).  Dense (nx,ny,nz) arrays, int64 throughout. -------------------------------------
+COARSEN_MAX_FACTOR = 8
+COARSEN_MAX_OFFSET = 1 << 20
+COARSEN_EVID_RULES = ("cover", "max")
+COARSEN_OCC_RULES = ("any", "all")
+
+
+def coarsen_children(src, dst_dims, factor, offset, empty):
+    """The children of every voxel of dst_dims -> (nx, ny, nz, f^3): those of d are src[f d + offset + e], e in [0, f)^3, `empty`
+    where that lies outside src's shape."""
+    f = int(factor)
+    if not 2 <= f <= COARSEN_MAX_FACTOR or any(abs(int(o)) > COARSEN_MAX_OFFSET for o in offset):
+        raise ValueError(f"factor must lie in [2, {COARSEN_MAX_FACTOR}] and the offset within 2^20, got {factor!r} and {tuple(offset)!r}")
+    d = tuple(int(n) for n in dst_dims)
+    win = shifted_window(src, tuple(f * n for n in d), offset, empty)
+    return win.reshape(d[0], f, d[1], f, d[2], f).transpose(0, 2, 4, 1, 3, 5).reshape(*d, f ** 3)
+
+
+def evid_coarsen_sample_ref(L_src, dst_dims, factor, offset, rule="cover", threshold=0):
+    """The source values S (dst_dims, int64) of the coarse voxels.  'cover': the maximum over the f^3 children of evid_sample_ref's key
+    free < unknown < occupied (a child outside the source is unknown), decoded again.  'max': the largest child as a signed byte."""
+    C = coarsen_children(np.asarray(L_src, dtype=np.int64), dst_dims, factor, offset, EVID_UNKNOWN)
+    if rule == "max":
+        return C.max(axis=-1)
+    if rule != "cover":
+        raise ValueError(f"rule must be 'cover' or 'max', got {rule!r}")
+    best = np.where(C == EVID_UNKNOWN, 256, np.where(C > threshold, 640 + C, 128 + C)).max(axis=-1)
+    return np.where(best > 512, best - 640, np.where(best == 256, EVID_UNKNOWN, best - 128))
+
+
+def evid_coarsen_ref(L_src, L_dst, factor, offset, rule, mode, params=None):
+    """tohip_evid_coarsen restated -> (L' (dst's shape) int64, counts (4,) int64): evid_coarsen_sample_ref's S under the parameters'
+    threshold, combined with L_dst (not modified) as the transfer does (evidence_combine_ref)."""
+    S = evid_coarsen_sample_ref(L_src, np.shape(L_dst), factor, offset, rule, evidence_params(params)[4])
+    return evidence_combine_ref(S, L_dst, mode, params)
+
+
+def occ_coarsen_ref(bits, dst_bits, factor, offset, rule, mode, veto=None):
+    """tohip_occ_coarsen restated -> (new (dst's shape) bool, count).  rule 'any': the OR of the f^3 child bits, and with a veto plane
+    (the source's shape; 'any' only) that OR and not the OR of the veto's children; 'all': their AND, a child outside the source
+    counting 0.  mode 'copy' / 'or' and the count as occ_transfer_ref."""
+    src, dst = np.asarray(bits, dtype=bool), np.asarray(dst_bits, dtype=bool)
+    if rule not in COARSEN_OCC_RULES:
+        raise ValueError(f"rule must be 'any' or 'all', got {rule!r}")
+    C = coarsen_children(src, dst.shape, factor, offset, False)
+    S = C.any(axis=-1) if rule == "any" else C.all(axis=-1)
+    if veto is not None:
+        if rule != "any" or np.shape(veto) != src.shape:
+            raise ValueError("a veto plane goes with rule 'any' and has the source's shape")
+        S = S & ~coarsen_children(np.asarray(veto, dtype=bool), dst.shape, factor, offset, False).any(axis=-1)
+    if mode == "copy":
+        return S, int(S.sum())
+    if mode != "or":
+        raise ValueError(f"mode must be 'copy' or 'or', got {mode!r}")
+    return dst | S, int((S & ~dst).sum())
+
+
 def pillar_scan(room, origin, lo, hi):
     """The scan `room` (N,3) taken from `origin` with the axis-aligned box [lo, hi] in the way -> (N,3) f32: a ray origin -> room[i]
     that enters the box (the slab method in f64; the origin lies outside it) returns its entry point instead."""

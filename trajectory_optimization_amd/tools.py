@@ -684,10 +684,39 @@ def transform_map(map, pose, quat, origin=None, resolution=None, dims=None, like
     rule for evidence that will be fused; a wall one voxel thick may show pinholes after a rotation.  rule 'cover', for planning: the
     maximum over the 3 x 3 x 3 old voxels around it under free < unknown < occupied (planes: OR for occupied, AND for free) — no
     occupied voxel is lost, nothing is free unless all it touches was free, a ray cannot slip through a wall; walls and the unknown
-    grow by up to a voxel.  Not a coarsening: a resolution coarser than the map's is refused, one finer than an eighth of it too.
+    grow by up to a voxel.  Not a coarsening: a resolution coarser than the map's is refused (coarsen_map reduces by a whole
+    factor), one finer than an eighth of it too.
     A ClearanceField, TravelField or Components over the old map is built anew over the new one."""
     ops.check_transform(map, pose, quat, origin, resolution, dims, like, rule)
     return map.transformed(pose, quat, origin=origin, resolution=resolution, dims=dims, like=like, rule=rule)
+
+
+def coarsen_map(map, factor=2, rule=None, anchor="origin", origin=None, dims=None, like=None):
+    """A map at `factor` times its voxel edge -> a NEW map of the same kind and parameters ("Coarsening maps"): an
+    ops.OccupancyGrid, ops.SpaceMap or ops.EvidenceMap; the old one is only read.  factor: an integer in [2, 8]; each coarse voxel
+    reduces its factor^3 children.  rule, for a SpaceMap or an EvidenceMap: 'cover' (the default), for planning — occupied if a child
+    is occupied, else unknown if a child is unknown or lies outside the map, else free: no occupied voxel is lost, nothing is free
+    unless all it holds is free, so clearance_field, travel_field and line of sight over the coarse map err on the safe side; or
+    'max', for display, occlusion and matching — the largest child, optimistic about the unknown.  For an OccupancyGrid: 'any' (the
+    default) or 'all'.  anchor 'origin': the coarse box starts at the map's origin; 'world': the coarse lattice's planes lie at
+    multiples of the coarse edge, so coarse maps of any sources on one fine lattice share a lattice and merge_maps takes them as they
+    are.  origin / dims / like: another box on the fine lattice (ops.check_coarsen).  A ClearanceField, TravelField or Components is
+    built anew over the coarse map."""
+    _, _, rule = ops.check_coarsen(map, factor, rule, anchor, origin, dims, like)
+    return map.coarsened(factor, rule=rule, anchor=anchor, origin=origin, dims=dims, like=like)
+
+
+def map_pyramid(map, levels, rule=None):
+    """A map at several scales -> [map, level 1, ..., level `levels`]: each level is the one before it at factor 2 with
+    anchor='origin' (coarsen_map), so level l equals coarsen_map(map, 2 ** l) bit for bit where that factor is allowed — the rules'
+    reductions are associative.  levels: an integer >= 0; rule as coarsen_map (None: the kind's default, 'cover' or 'any')."""
+    ops._map_frame(map, "map")
+    if not ops._is_int(levels) or levels < 0:
+        raise ValueError(f"levels must be an integer >= 0, got {levels!r}")
+    out = [map]
+    for _ in range(int(levels)):
+        out.append(coarsen_map(out[-1], 2, rule=rule))
+    return out
 
 
 def merge_maps(maps, mode=None, poses=None, quats=None, rule="nearest"):
