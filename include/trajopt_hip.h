@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_occ_coarsen / tohip_evid_coarsen and the TOHIP_COARSEN_* constants (coarsening maps: f x f x f voxels of one box reduced
+/* (still 15) + tohip_travel_weights_bytes / tohip_travel_weights_build / tohip_travel_build_weighted / tohip_travel_paths_weighted (weighted
+ * travel fields: a per-voxel cost factor so routes keep off walls and out of the unknown): new symbols only.
+ * (still 15) + tohip_occ_coarsen / tohip_evid_coarsen and the TOHIP_COARSEN_* constants (coarsening maps: f x f x f voxels of one box reduced
  * to one voxel of a coarser box under a conservative or an optimistic rule, written or combined as the transfers do): new symbols only.
  * (still 15) + tohip_occ_resample / tohip_evid_resample and the TOHIP_RESAMPLE_* constants (resampling maps: voxel content of one box read
  * in another under a rigid transform and a change of resolution, by an integer affine map the host quantises once): new symbols only.
@@ -1571,6 +1573,44 @@ int tohip_travel_paths_batch(const void *cost, size_t cost_bytes, const void *fi
                              int64_t *counts, void *stream);
 int tohip_assign_greedy(const int64_t *cost, int32_t n_rows, int32_t n_cols, int64_t ld, int64_t min_cost, int32_t *col_of_row,
                         int32_t *row_of_col, void *stream);
+
+/* ---- weighted travel fields (travel_kernels.hip, DESIGN.md §10, "Weighted travel fields") ------------------
+ * A travel field that minimises WEIGHTED length.  weights: a layer kappa of one uint8 per voxel inside dims, dense, x fastest, the
+ * cost words' index (z ny + y) nx + x: tohip_travel_weights_bytes(nx, ny, nz) = nx ny nz device bytes (0 for bad dims), caller-owned.
+ * 16 <= kappa <= 255; 16 is neutral, 255 costs about 15.9 times as much.  The bytes are the caller's contract: no entry reads them on
+ * the host, and a byte below 16 is a discount the fixed-point argument does not cover.  The move m between v and u, of weight w_m in
+ * {64, 91, 111}, costs
+ *     step(v, u, m) = (w_m (kappa[v] + kappa[u]) + 16) >> 5,
+ * symmetric in v and u, an integer, at least w_m, exactly w_m at kappa = 16 and at most (111 x 510 + 16) >> 5 = 1769.  T, the move
+ * rule (no corner cut; only the move's two endpoints are priced, not the other voxels of its box), the seeds, limit and the sentinel
+ * are tohip_travel_build's; cost is the unique fixed point of cost[s] = 0, cost[v] = min over the allowed u of cost[u] + step — the
+ * same bits in every run.  Because step >= w_m a path's geometric length never exceeds its cost: a limit still bounds the length, and
+ * a path of cost c still has at most c / 64 moves.  At kappa = 16 everywhere every entry below writes tohip_travel_build_batch's and
+ * tohip_travel_paths_batch's bytes.
+ *
+ * tohip_travel_weights_build: out[v] = lut[min(field[v], n_lut - 1)] for every voxel inside dims — field: a clearance field
+ * (tohip_field_build), whose value is the squared gap in voxels; lut: n_lut >= 1 (at most 65536) DEVICE bytes.  With the two planes of
+ * a map (both or neither, grid_bytes each) unknown_add (0 .. 255) is added at the voxels that are neither occupied nor known free, and
+ * the sum saturates at 255.  out: out_bytes >= tohip_travel_weights_bytes (TOHIP_ENOSPC), sharing no byte with the inputs.  One launch.
+ * tohip_travel_build_weighted: tohip_travel_build_batch (n_fields = 1 and source_field all 0: the single field) with the layer, which
+ * all fields share: weights_bytes >= tohip_travel_weights_bytes, and the layer shares no byte with cost or workspace (TOHIP_EINVAL).
+ * tohip_travel_paths_weighted: tohip_travel_paths_batch with the path rule's test cost[u] + step(v, u, m) == cost[v]; the lowest move
+ * number still wins ties.
+ * flags behind the stream is reserved: 0, anything else TOHIP_EINVAL.  Every argument check returns before anything is enqueued. */
+size_t tohip_travel_weights_bytes(int32_t nx, int32_t ny, int32_t nz);
+int tohip_travel_weights_build(const void *field, size_t field_bytes, const void *occupied_or_null, const void *free_or_null,
+                               size_t grid_bytes, const tohip_occ_geom *geom, const uint8_t *lut, int32_t n_lut, int32_t unknown_add,
+                               uint8_t *out, size_t out_bytes, void *stream, uint32_t flags);
+int tohip_travel_build_weighted(const void *field, size_t field_bytes, const void *occupied_or_null, const void *free_or_null,
+                                size_t grid_bytes, const tohip_occ_geom *geom, int32_t need2, const float *sources,
+                                const int32_t *source_field, int64_t n_sources, int32_t n_fields, int64_t limit,
+                                int32_t rounds_per_check, void *cost, size_t cost_bytes, void *workspace, size_t workspace_bytes,
+                                uint8_t *seeded, int64_t *rounds_host, const uint8_t *weights, size_t weights_bytes, void *stream,
+                                uint32_t flags);
+int tohip_travel_paths_weighted(const void *cost, size_t cost_bytes, const void *field, size_t field_bytes, const void *occupied_or_null,
+                                const void *free_or_null, size_t grid_bytes, const tohip_occ_geom *geom, int32_t need2, int32_t n_fields,
+                                const float *goals, const int32_t *goal_field, int64_t n_goals, int64_t max_rows, float *rows,
+                                int64_t *counts, const uint8_t *weights, size_t weights_bytes, void *stream, uint32_t flags);
 
 /* ---- connected components (components_kernels.hip, DESIGN.md §10, "Connected components") ----------------
  * Which voxels belong together?  plane: any bit plane of the occupancy layout (grid_bytes; header and pad bits 0, as every producer

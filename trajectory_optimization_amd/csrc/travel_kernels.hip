@@ -34,12 +34,22 @@
 // and the kernels above are the batch's: the single build is their n_fields = 1 (b = 0 everywhere, the same words in the same order).
 // Fields share no cost word, so the fixed-point argument holds field by field.
 //
+// WEIGHTED FIELDS ("Weighted travel fields"): a layer kappa of one byte per voxel inside dims (dense, x fastest, the
+// cost words' index), 16 <= kappa <= 255, 16 neutral.  The move m between v and u costs step = (w_m (kappa[v] + kappa[u]) + 16) >> 5:
+// symmetric, an integer, >= w_m, exactly w_m at kappa = 16, at most (111 x 510 + 16) >> 5 = 1769.  T, the move rule, the seeds, limit
+// and the sentinel stay; the answer is the same unique fixed point with step in place of w.  k_travel_relax<true> and
+// k_travel_paths<true> are the kernels above with a third halo array (10^3 bytes of kappa) and the step formed per move; <false> is
+// the unweighted kernel, instruction for instruction (the switch is a template parameter).
+//   k_travel_weights  one lane per voxel: kappa[v] = lut[min(field[v], n_lut - 1)], + unknown_add (saturating at 255) where the map's
+//                     two planes are given and v is neither occupied nor known free.
+//
 // Every kernel ends on its own: no block waits for another.  No float atomics, no process-wide state; every argument check returns
 // before anything is enqueued.
 namespace {
 
 constexpr unsigned kTravelSentinel = 0xFFFFFFFFu;
 constexpr unsigned kTravelInf = 0xFFFFFF00u;          // "no path" inside LDS: + 111 does not wrap, and exceeds every limit
+constexpr unsigned kTravelInfWeighted = 0xFFFFF000u;  // the same for a weighted field: + 1769, the largest step, does not wrap
 constexpr long long kTravelMaxLimit = 0x7fffffffll;
 constexpr int kTravelTile = 8;                        // voxels per tile edge
 constexpr int kTravelHalo = kTravelTile + 2;
@@ -100,6 +110,9 @@ __device__ __forceinline__ constexpr unsigned travel_box(int m) {
     return need;
 }
 
+// the weighted cost of a move of weight w between voxels of factors ka and kb (16 = neutral: exactly w)
+__device__ __forceinline__ constexpr unsigned travel_step(unsigned w, unsigned ka, unsigned kb) { return (w * (ka + kb) + 16u) >> 5; }
+
 __device__ __forceinline__ float travel_centre(float o, int i, float r) { return __fadd_rn(o, __fmul_rn((float)i + 0.5f, r)); }
 
 __global__ void __launch_bounds__(TO_BLOCK) k_travel_fill(unsigned* __restrict__ cost, long long n_vox) {
@@ -152,12 +165,20 @@ k_travel_compact(unsigned* __restrict__ bitmap, long long words, int* __restrict
     }
 }
 
+// kWeighted: the moves cost travel_step over the layer kappa (one byte per voxel, the cost words' index); else kappa is not read
+template <bool kWeighted>
 __global__ void __launch_bounds__(TO_BLOCK)
 k_travel_relax(TravelSet s, unsigned* cost_all, long long n_vox, unsigned limit, const int* __restrict__ list, unsigned* __restrict__ hdr32,
-               int parity, unsigned* __restrict__ next_all, int ntx, int nty, int ntz, int n_tiles) {
+               int parity, unsigned* __restrict__ next_all, int ntx, int nty, int ntz, int n_tiles, const uint8_t* __restrict__ kappa) {
     __shared__ unsigned s_cost[kTravelHaloN];
     __shared__ unsigned char s_in[kTravelHaloN];
     __shared__ unsigned s_touch;
+    unsigned char* s_kappa = nullptr;
+    if constexpr (kWeighted) {
+        __shared__ unsigned char s_kappa_halo[kTravelHaloN];
+        s_kappa = s_kappa_halo;
+    }
+    constexpr unsigned kInf = kWeighted ? kTravelInfWeighted : kTravelInf;
     const unsigned count = hdr32[2 + parity];
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         // the bookkeeping of the round: the other round's count starts from zero, and the status word the host reads
@@ -181,18 +202,19 @@ k_travel_relax(TravelSet s, unsigned* cost_all, long long n_vox, unsigned limit,
         for (int i = threadIdx.x; i < kTravelHaloN; i += TO_BLOCK) {
             const int x = x0 + i % kTravelHalo, y = y0 + (i / kTravelHalo) % kTravelHalo, z = z0 + i / (kTravelHalo * kTravelHalo);
             const bool in = travel_in_set(s, x, y, z);
-            unsigned c = kTravelInf;
+            unsigned c = kInf;
             if (in) {
                 c = cost[field_index(g, x, y, z)];
-                if (c > limit) c = kTravelInf;   // (the sentinel)
+                if (c > limit) c = kInf;   // (the sentinel)
             }
             s_cost[i] = c;
             s_in[i] = in ? 1 : 0;
+            if constexpr (kWeighted) s_kappa[i] = in ? kappa[field_index(g, x, y, z)] : 0;   // (outside T: never an endpoint)
         }
         __syncthreads();
         // this lane's two voxels: their place in the halo block, the moves they may make, the value they came with
         int at[2];
-        unsigned allowed[2], first[2], mine[2];
+        unsigned allowed[2], first[2], mine[2], own[2];   // (own: the lane's two factors, weighted fields only)
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const int l = threadIdx.x + k * TO_BLOCK;
@@ -209,6 +231,7 @@ k_travel_relax(TravelSet s, unsigned* cost_all, long long n_vox, unsigned limit,
             }
             allowed[k] = ok;
             first[k] = mine[k] = s_cost[at[k]];
+            if constexpr (kWeighted) own[k] = s_kappa[at[k]];
         }
         bool changed;
         do {
@@ -220,7 +243,10 @@ k_travel_relax(TravelSet s, unsigned* cost_all, long long n_vox, unsigned limit,
 #pragma unroll
                 for (int m = 0; m < 27; ++m) {
                     if (m == 13) continue;
-                    const unsigned c = s_cost[at[k] + (travel_dz(m) * kTravelHalo + travel_dy(m)) * kTravelHalo + travel_dx(m)] + travel_weight(m);
+                    const int nb = at[k] + (travel_dz(m) * kTravelHalo + travel_dy(m)) * kTravelHalo + travel_dx(m);
+                    unsigned c;
+                    if constexpr (kWeighted) c = s_cost[nb] + travel_step(travel_weight(m), own[k], s_kappa[nb]);
+                    else c = s_cost[nb] + travel_weight(m);
                     if (((allowed[k] >> m) & 1u) && c < best) best = c;
                 }
                 if (best < mine[k] && best <= limit) {
@@ -286,11 +312,13 @@ k_travel_positions(const unsigned* __restrict__ cost, long long n_vox, OccGeom g
 }
 
 // one wave per goal; rows (n_goals, max_rows, 3): the voxel centres goal -> source; counts: rows, 0 unreachable (or the goal out of
-// range or outside dims), -needed where the path does not fit
+// range or outside dims), -needed where the path does not fit.  kWeighted: the predecessor test is there + travel_step == here over
+// the layer kappa, which all fields share
+template <bool kWeighted>
 __global__ void __launch_bounds__(TO_BLOCK)
 k_travel_paths(TravelSet s, const unsigned* __restrict__ cost_all, long long n_vox, const float* __restrict__ goals,
                const int* __restrict__ goal_field, int n_fields, long long n_goals, long long max_rows, float* __restrict__ rows,
-               long long* __restrict__ counts) {
+               long long* __restrict__ counts, const uint8_t* __restrict__ kappa) {
     const int lane = threadIdx.x & 63;
     const long long goal = (long long)blockIdx.x * (TO_BLOCK / 64) + (threadIdx.x >> 6);
     if (goal >= n_goals) return;   // (a whole wave)
@@ -317,7 +345,10 @@ k_travel_paths(TravelSet s, const unsigned* __restrict__ cost_all, long long n_v
                 unsigned there = 0u;
                 if (lane < 27 && lane != 13 && occ_inside(g, x + dx, y + dy, z + dz)) {
                     there = cost[field_index(g, x + dx, y + dy, z + dz)];
-                    if (there != kTravelSentinel && there + w == here) {
+                    unsigned step = w;
+                    if constexpr (kWeighted)   // (a neighbour outside T holds the sentinel: its byte decides nothing)
+                        step = travel_step(w, kappa[field_index(g, x, y, z)], kappa[field_index(g, x + dx, y + dy, z + dz)]);
+                    if (there != kTravelSentinel && there + step == here) {
                         take = true;
                         for (int i = 1; i < 8 && take; ++i) {   // the box of the move (its far corner holds a cost: it is in T)
                             if (((i & 1) && dx == 0) || ((i & 2) && dy == 0) || ((i & 4) && dz == 0)) continue;
@@ -334,6 +365,24 @@ k_travel_paths(TravelSet s, const unsigned* __restrict__ cost_all, long long n_v
         }
     }
     if (lane == 0) counts[goal] = n > max_rows ? -n : n;
+}
+
+// a weight layer from a clearance field: kappa[v] = lut[min(field[v], n_lut - 1)]; with the two planes, + unknown_add where v is
+// neither occupied nor known free, saturating at 255.  One lane per voxel inside dims (grid-stride, 64-bit index).
+__global__ void __launch_bounds__(TO_BLOCK)
+k_travel_weights(const uint16_t* __restrict__ field, const unsigned* __restrict__ occ, const unsigned* __restrict__ fre, OccGeom g,
+                 const uint8_t* __restrict__ lut, int n_lut, unsigned unknown_add, uint8_t* __restrict__ out, long long n_vox) {
+    const long long stride = (long long)gridDim.x * TO_BLOCK;
+    for (long long i = (long long)blockIdx.x * TO_BLOCK + threadIdx.x; i < n_vox; i += stride) {
+        const int d2 = (int)field[i];
+        unsigned k = lut[d2 < n_lut ? d2 : n_lut - 1];
+        if (occ) {
+            const int x = (int)(i % g.nx), y = (int)((i / g.nx) % g.ny), z = (int)(i / ((long long)g.nx * g.ny));
+            const int w = occ_word(g, x, y, z), b = occ_bit(x, y, z);
+            if (!(((occ[w] | fre[w]) >> b) & 1u)) k = k + unknown_add > 255u ? 255u : k + unknown_add;   // state 0: unknown
+        }
+        out[i] = (uint8_t)k;
+    }
 }
 
 // round `round` of a greedy selection that prices the trip: gain 2^20 - m cost decides among the candidates not taken with gain >=
@@ -473,9 +522,11 @@ inline size_t travel_workspace_bytes(int64_t nx, int64_t ny, int64_t nz, int n_f
     return kTravelHdr + 2 * travel_bitmap_bytes(t, n_fields) + travel_align((size_t)t.n * (size_t)n_fields * sizeof(int32_t));
 }
 
-// the build of n_fields fields in the same rounds; source_field null: every source seeds field 0 (the single build)
+// the build of n_fields fields in the same rounds; source_field null: every source seeds field 0 (the single build); kappa null: the
+// unweighted field
 int travel_build(const TravelSet& s, const float* sources, const int32_t* source_field, int64_t n_sources, int n_fields, int64_t limit,
-                 int32_t rounds_per_check, void* cost, void* workspace, uint8_t* seeded, int64_t* rounds_host, hipStream_t st) {
+                 int32_t rounds_per_check, void* cost, void* workspace, uint8_t* seeded, int64_t* rounds_host, hipStream_t st,
+                 const uint8_t* kappa = nullptr) {
     const TravelTiles t = travel_tiles(s.g.nx, s.g.ny, s.g.nz);
     const size_t bm = travel_bitmap_bytes(t, n_fields);
     const long long items = t.n * n_fields, words = (items + 31) / 32;
@@ -498,8 +549,12 @@ int travel_build(const TravelSet& s, const float* sources, const int32_t* source
         for (int r = 0; r < rounds_per_check; ++r, parity ^= 1) {
             k_travel_compact<<<compact_blocks, TO_BLOCK, 0, st>>>(bitmap[parity], words, list, hdr32 + 2 + parity);
             TO_HIP_CHECK_LAUNCH();
-            k_travel_relax<<<relax_blocks, TO_BLOCK, 0, st>>>(s, c, n_vox, (unsigned)limit, list, hdr32, parity, bitmap[parity ^ 1], (int)t.ntx,
-                                                              (int)t.nty, (int)t.ntz, (int)t.n);
+            if (kappa)
+                k_travel_relax<true><<<relax_blocks, TO_BLOCK, 0, st>>>(s, c, n_vox, (unsigned)limit, list, hdr32, parity, bitmap[parity ^ 1],
+                                                                        (int)t.ntx, (int)t.nty, (int)t.ntz, (int)t.n, kappa);
+            else
+                k_travel_relax<false><<<relax_blocks, TO_BLOCK, 0, st>>>(s, c, n_vox, (unsigned)limit, list, hdr32, parity, bitmap[parity ^ 1],
+                                                                         (int)t.ntx, (int)t.nty, (int)t.ntz, (int)t.n, nullptr);
             TO_HIP_CHECK_LAUNCH();
         }
         // one word back: the items the last round worked on (none: nothing was activated after it) and the rounds that had work
@@ -590,7 +645,8 @@ int travel_positions(const void* cost, size_t cost_bytes, const tohip_occ_geom* 
 
 int travel_paths(const void* cost, size_t cost_bytes, const void* field, size_t field_bytes, const void* occupied_or_null,
                  const void* free_or_null, size_t grid_bytes, const tohip_occ_geom* geom, int32_t need2, int64_t n_fields, const float* goals,
-                 const int32_t* goal_field, int64_t n_goals, int64_t max_rows, float* rows, int64_t* counts, void* stream_) {
+                 const int32_t* goal_field, int64_t n_goals, int64_t max_rows, float* rows, int64_t* counts, void* stream_,
+                 const uint8_t* kappa = nullptr) {
     TravelSet s;
     const int rc = travel_set(field, field_bytes, occupied_or_null, free_or_null, grid_bytes, geom, need2, s);
     if (rc != TOHIP_OK) return rc;
@@ -600,8 +656,12 @@ int travel_paths(const void* cost, size_t cost_bytes, const void* field, size_t 
     if (cost_bytes < travel_cost_bytes(s.g) * (size_t)n_fields) return TOHIP_ENOSPC;
     if (n_goals == 0) return TOHIP_OK;
     const unsigned blocks = (unsigned)((n_goals + TO_BLOCK / 64 - 1) / (TO_BLOCK / 64));
-    k_travel_paths<<<blocks, TO_BLOCK, 0, (hipStream_t)stream_>>>(s, (const unsigned*)cost, (long long)field_voxels(s.g), goals, goal_field,
-                                                                  (int)n_fields, n_goals, max_rows, rows, (long long*)counts);
+    if (kappa)
+        k_travel_paths<true><<<blocks, TO_BLOCK, 0, (hipStream_t)stream_>>>(s, (const unsigned*)cost, (long long)field_voxels(s.g), goals, goal_field,
+                                                                            (int)n_fields, n_goals, max_rows, rows, (long long*)counts, kappa);
+    else
+        k_travel_paths<false><<<blocks, TO_BLOCK, 0, (hipStream_t)stream_>>>(s, (const unsigned*)cost, (long long)field_voxels(s.g), goals, goal_field,
+                                                                             (int)n_fields, n_goals, max_rows, rows, (long long*)counts, nullptr);
     TO_HIP_CHECK_LAUNCH();
     return TOHIP_OK;
 }
@@ -632,6 +692,81 @@ extern "C" int tohip_travel_paths_batch(const void* cost, size_t cost_bytes, con
     if (n_goals > 0 && !goal_field) return TOHIP_EINVAL;
     return travel_paths(cost, cost_bytes, field, field_bytes, occupied_or_null, free_or_null, grid_bytes, geom, need2, n_fields, goals,
                         goal_field, n_goals, max_rows, rows, counts, stream_);
+}
+
+// ---- weighted fields: the batch's entries with a layer kappa.  The bytes of kappa are the caller's contract (16 .. 255).
+
+namespace {
+
+inline size_t travel_weights_bytes(const OccGeom& g) { return field_voxels(g); }
+
+// [a, a + na) and [b, b + nb) share a byte
+inline bool travel_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+}  // namespace
+
+extern "C" size_t tohip_travel_weights_bytes(int32_t nx, int32_t ny, int32_t nz) {
+    return occ_dims_ok(nx, ny, nz) ? field_voxels(nx, ny, nz) : 0;
+}
+
+extern "C" int tohip_travel_weights_build(const void* field, size_t field_bytes, const void* occupied_or_null, const void* free_or_null,
+                                          size_t grid_bytes, const tohip_occ_geom* geom, const uint8_t* lut, int32_t n_lut,
+                                          int32_t unknown_add, uint8_t* out, size_t out_bytes, void* stream_, uint32_t flags) {
+    if (flags != 0u) return TOHIP_EINVAL;   // (reserved)
+    TravelSet s;
+    const int rc = travel_set(field, field_bytes, occupied_or_null, free_or_null, grid_bytes, geom, 1, s);
+    if (rc != TOHIP_OK) return rc;
+    if (!lut || n_lut < 1 || n_lut > kFieldSentinel + 1 || unknown_add < 0 || unknown_add > 255 || !out) return TOHIP_EINVAL;
+    if (out_bytes < travel_weights_bytes(s.g)) return TOHIP_ENOSPC;
+    const size_t nb = travel_weights_bytes(s.g);
+    if (travel_overlap(out, nb, field, nb * sizeof(uint16_t)) || travel_overlap(out, nb, lut, (size_t)n_lut) ||
+        (occupied_or_null && (travel_overlap(out, nb, occupied_or_null, grid_bytes) || travel_overlap(out, nb, free_or_null, grid_bytes))))
+        return TOHIP_EINVAL;
+    const long long n_vox = (long long)field_voxels(s.g);
+    k_travel_weights<<<occ_grid_blocks(n_vox), TO_BLOCK, 0, (hipStream_t)stream_>>>(s.field, s.occ, s.fre, s.g, lut, n_lut, (unsigned)unknown_add,
+                                                                                   out, n_vox);
+    TO_HIP_CHECK_LAUNCH();
+    return TOHIP_OK;
+}
+
+extern "C" int tohip_travel_build_weighted(const void* field, size_t field_bytes, const void* occupied_or_null, const void* free_or_null,
+                                           size_t grid_bytes, const tohip_occ_geom* geom, int32_t need2, const float* sources,
+                                           const int32_t* source_field, int64_t n_sources, int32_t n_fields, int64_t limit,
+                                           int32_t rounds_per_check, void* cost, size_t cost_bytes, void* workspace, size_t workspace_bytes,
+                                           uint8_t* seeded, int64_t* rounds_host, const uint8_t* weights, size_t weights_bytes, void* stream_,
+                                           uint32_t flags) {
+    if (flags != 0u) return TOHIP_EINVAL;   // (reserved)
+    TravelSet s;
+    int rc = travel_set(field, field_bytes, occupied_or_null, free_or_null, grid_bytes, geom, need2, s);
+    if (rc != TOHIP_OK) return rc;
+    rc = travel_build_check(field, occupied_or_null, free_or_null, sources, n_sources, limit, rounds_per_check, cost, workspace);
+    if (rc != TOHIP_OK) return rc;
+    if (!source_field || !travel_fields_ok(n_fields) || travel_tiles(s.g.nx, s.g.ny, s.g.nz).n * n_fields > kTravelMaxItems) return TOHIP_EINVAL;
+    const size_t cb = travel_cost_bytes(s.g) * (size_t)n_fields, wb = travel_workspace_bytes(s.g.nx, s.g.ny, s.g.nz, n_fields);
+    if (cost_bytes < cb || workspace_bytes < wb) return TOHIP_EINVAL;
+    if (!weights || weights_bytes < travel_weights_bytes(s.g)) return TOHIP_EINVAL;
+    if (travel_overlap(weights, travel_weights_bytes(s.g), cost, cb) || travel_overlap(weights, travel_weights_bytes(s.g), workspace, wb))
+        return TOHIP_EINVAL;
+    return travel_build(s, sources, source_field, n_sources, n_fields, limit, rounds_per_check, cost, workspace, seeded, rounds_host,
+                        (hipStream_t)stream_, weights);
+}
+
+extern "C" int tohip_travel_paths_weighted(const void* cost, size_t cost_bytes, const void* field, size_t field_bytes,
+                                           const void* occupied_or_null, const void* free_or_null, size_t grid_bytes,
+                                           const tohip_occ_geom* geom, int32_t need2, int32_t n_fields, const float* goals,
+                                           const int32_t* goal_field, int64_t n_goals, int64_t max_rows, float* rows, int64_t* counts,
+                                           const uint8_t* weights, size_t weights_bytes, void* stream_, uint32_t flags) {
+    if (flags != 0u) return TOHIP_EINVAL;   // (reserved)
+    if (n_goals > 0 && !goal_field) return TOHIP_EINVAL;
+    OccGeom g;
+    const int rc = field_check(field, field_bytes, geom, g);
+    if (rc != TOHIP_OK) return rc;
+    if (!weights || weights_bytes < travel_weights_bytes(g)) return TOHIP_EINVAL;
+    return travel_paths(cost, cost_bytes, field, field_bytes, occupied_or_null, free_or_null, grid_bytes, geom, need2, n_fields, goals,
+                        goal_field, n_goals, max_rows, rows, counts, stream_, weights);
 }
 
 extern "C" int tohip_assign_greedy(const int64_t* cost, int32_t n_rows, int32_t n_cols, int64_t ld, int64_t min_cost, int32_t* col_of_row,

@@ -1555,12 +1555,133 @@ def _check_rows3(t, name, empty=False):
     return t
 
 
-def check_travel(field, radius, sources, space=None, max_dist=None, rounds_per_check=16):
+TRAVEL_KAPPA_NEUTRAL, TRAVEL_KAPPA_MAX = 16, 255   # a weight layer's factors: 16 is neutral, 255 costs about 15.9 times as much
+
+
+def check_travel_lut(lut, what="lut"):
+    """A weight table, by name; needs no GPU: a 1-D sequence, array or tensor of 1 .. 65536 integers in [16, 255] -> (n,) uint8 numpy;
+    ValueError names the first offender."""
+    a = lut.detach().cpu().numpy() if torch.is_tensor(lut) else np.asarray(lut)
+    if a.ndim != 1 or not 1 <= a.shape[0] <= 65536 or a.dtype.kind not in "iu":
+        raise ValueError(f"{what} must be a 1-D table of 1 .. 65536 integers, got shape {tuple(a.shape)} of {a.dtype}")
+    bad = np.flatnonzero((a < TRAVEL_KAPPA_NEUTRAL) | (a > TRAVEL_KAPPA_MAX))
+    if len(bad):
+        raise ValueError(f"{what}[{int(bad[0])}] = {int(a[bad[0]])} is outside [{TRAVEL_KAPPA_NEUTRAL}, {TRAVEL_KAPPA_MAX}] (16 is neutral; "
+                         "there are no discounts)")
+    return a.astype(np.uint8)
+
+
+def check_travel_unknown_add(unknown_add, space):
+    """unknown_add of a weight layer, by name: an integer in [0, 255], and not 0 only with a space that says what is unknown."""
+    if not _is_int(unknown_add) or not 0 <= unknown_add <= TRAVEL_KAPPA_MAX:
+        raise ValueError(f"unknown_add must be an integer in [0, {TRAVEL_KAPPA_MAX}], got {unknown_add!r}")
+    if unknown_add and space is None:
+        raise ValueError("unknown_add needs space= (an ops.SpaceMap: what is unknown)")
+    return int(unknown_add)
+
+
+def _check_weights_field(field):
+    if not isinstance(field, ClearanceField):
+        raise ValueError(f"TravelWeights: field must be an ops.ClearanceField, got {type(field).__name__}")
+
+
+def check_travel_dense(field, tensor):
+    """A caller's weight layer, by name; needs no GPU for a host tensor's dtype and shape: an integer tensor (nx, ny, nz) of the
+    field's dims on the field's device, every value in [16, 255] — the first offender is named."""
+    _check_weights_field(field)
+    if not torch.is_tensor(tensor) or tensor.is_floating_point() or tensor.is_complex() or tensor.dtype == torch.bool:
+        raise ValueError(f"TravelWeights: the layer must be an integer tensor (dtype), got "
+                         f"{tensor.dtype if torch.is_tensor(tensor) else type(tensor).__name__}")
+    if tuple(tensor.shape) != tuple(field.dims):
+        raise ValueError(f"TravelWeights: the layer must have the field's dims {tuple(field.dims)}, got {tuple(tensor.shape)}")
+    bad = ((tensor < TRAVEL_KAPPA_NEUTRAL) | (tensor > TRAVEL_KAPPA_MAX)).nonzero()
+    if bad.shape[0]:
+        i, j, k = (int(v) for v in bad[0])
+        raise ValueError(f"TravelWeights: kappa[{i}, {j}, {k}] = {int(tensor[i, j, k])} is outside [{TRAVEL_KAPPA_NEUTRAL}, "
+                         f"{TRAVEL_KAPPA_MAX}] (16 is neutral; there are no discounts)")
+    dev = torch.device(field.device)
+    if tensor.device.type != dev.type or (dev.index is not None and tensor.device.index is not None and tensor.device.index != dev.index):
+        raise ValueError(f"TravelWeights: the layer lives on device {tensor.device}, the field on {dev}")
+
+
+class TravelWeights:
+    """A weight layer for travel fields (travel_kernels.hip, DESIGN.md 10 "Weighted travel fields"): one uint8 factor kappa per voxel
+    inside the clearance field's dims, 16 <= kappa <= 255, 16 neutral — the move m between v and u then costs (w_m (kappa[v] +
+    kappa[u]) + 16) >> 5 instead of w_m.  It holds the byte volume (buf, x fastest) and the field's geometry.
+
+    TravelWeights(field, lut=None, space=None, unknown_add=0) gathers kappa[v] = lut[min(field[v], len(lut) - 1)] on the device (the
+    field's value is the squared gap in voxels; lut None: all 16) and, with space=, adds unknown_add at the voxels that are neither
+    occupied nor known free, saturating at 255.  rebuild() re-reads the field (and the planes) after field.rebuild().
+    TravelWeights.from_dense(field, tensor) holds a layer of the caller's own; set_dense(tensor) replaces it in place."""
+
+    def __init__(self, field, lut=None, space=None, unknown_add=0):
+        _check_weights_field(field)
+        check_field(field.occupied, D=field.D, space=space)
+        self.unknown_add = check_travel_unknown_add(unknown_add, space)
+        table = check_travel_lut([TRAVEL_KAPPA_NEUTRAL] if lut is None else lut)
+        self._over(field, space)
+        self.lut = torch.from_numpy(table).to(self.device)
+        self.rebuild()
+
+    def _over(self, field, space):
+        self.field, self.space = field, space
+        self.origin, self.resolution, self.dims, self.device, self.geom = field.origin, field.resolution, field.dims, field.device, field.geom
+        self.buf = torch.empty(_lib.lib().tohip_travel_weights_bytes(*self.dims), dtype=torch.uint8, device=self.device)
+
+    @classmethod
+    def from_dense(cls, field, tensor):
+        """A layer of the caller's own: tensor (nx, ny, nz) on the field's device, uint8 or any integer dtype, every value in [16,
+        255] — the first offender is named.  It is copied."""
+        check_travel_dense(field, tensor)
+        self = cls.__new__(cls)
+        self.unknown_add, self.lut = 0, None
+        self._over(field, None)
+        return self.set_dense(tensor)
+
+    def set_dense(self, tensor):
+        """Replace the layer in place by `tensor` (from_dense's rules): the travel fields over it follow on their next rebuild().
+        -> self."""
+        check_travel_dense(self.field, tensor)
+        self.lut = None
+        self.buf.copy_(tensor.detach().to(torch.uint8).permute(2, 1, 0).reshape(-1))
+        return self
+
+    def rebuild(self):
+        """Gather the layer again from the field (and the space's planes) — after field.rebuild().  One launch.  A layer from
+        from_dense / set_dense has no table and stays as it is.  -> self."""
+        if self.lut is None:
+            return self
+        occ, fre = (ptr(self.space.occupied.buf), ptr(self.space.free.buf)) if self.space is not None else (None, None)
+        _map_call0(self.device, "tohip_travel_weights_build", ptr(self.field.buf), self.field.buf.numel(), occ, fre,
+                   self.field.occupied.buf.numel(), ctypes.byref(self.geom), ptr(self.lut), self.lut.numel(), self.unknown_add, ptr(self.buf),
+                   self.buf.numel())
+        return self
+
+    def dense(self):
+        """The layer as an (nx, ny, nz) uint8 tensor (a copy)."""
+        nx, ny, nz = self.dims
+        return self.buf.view(nz, ny, nx).permute(2, 1, 0).contiguous()
+
+
+def check_travel_weights(field, weights):
+    """weights= of a travel field, by name; needs no GPU: None, or an ops.TravelWeights of the field's origin, resolution, dims and
+    device.  -> weights."""
+    if weights is None:
+        return None
+    if not isinstance(weights, TravelWeights):
+        raise ValueError(f"weights must be an ops.TravelWeights or None, got {type(weights).__name__}")
+    diff = _grid_difference(field, weights)
+    if diff:
+        raise ValueError(f"weights: the layer's {diff[0]} differs from the field's ({diff[2]} and {diff[1]})")
+    return weights
+
+
+def check_travel(field, radius, sources, space=None, max_dist=None, rounds_per_check=16, weights=None):
     """A travel field's arguments, by name; needs no GPU.  field: an ops.ClearanceField; radius: a finite number > 0 whose need2 =
     field_need2(radius) is at most the field's D^2 (check_field's rule and error); sources: a floating-point (S,3) tensor, S >= 1, or
     (3,) — rows that are not finite are allowed: they are ignored and reported; space: None or an ops.SpaceMap of the field's origin,
-    resolution, dims and device; max_dist: None or a finite number of metres >= 0; rounds_per_check: an integer in [1, 65536].
-    -> (need2, limit, S); ValueError otherwise."""
+    resolution, dims and device; max_dist: None or a finite number of metres >= 0; rounds_per_check: an integer in [1, 65536]; weights:
+    None or an ops.TravelWeights of the field's origin, resolution, dims and device.  -> (need2, limit, S); ValueError otherwise."""
     if not isinstance(field, ClearanceField):
         raise ValueError(f"TravelField: field must be an ops.ClearanceField, got {type(field).__name__}")
     _, _, _, need2 = check_field(field.occupied, D=field.D, radius=check_tour_radius(radius), space=space)
@@ -1571,6 +1692,7 @@ def check_travel(field, radius, sources, space=None, max_dist=None, rounds_per_c
             raise ValueError(f"max_dist must be None or a finite number of metres >= 0, got {max_dist!r}")
     if not _is_int(rounds_per_check) or not 1 <= rounds_per_check <= TRAVEL_MAX_ROUNDS_PER_CHECK:
         raise ValueError(f"rounds_per_check must be an integer in [1, {TRAVEL_MAX_ROUNDS_PER_CHECK}], got {rounds_per_check!r}")
+    check_travel_weights(field, weights)
     return need2, travel_limit(max_dist, field.resolution), src.shape[0]
 
 
@@ -1581,19 +1703,22 @@ class TravelField:
     integers: the same bits in every run.  It holds the cost buffer and the worklist's workspace and reads the field (and the map's
     planes) again on rebuild().  seeded: (S,) uint8 on the device, 0 for a source that was ignored (not finite, out of range, outside
     dims or not traversable — there is no snapping); rounds: the worklist rounds the last build needed; limit: the largest cost
-    kept."""
+    kept.  weights (None: geometric length, today's calls): an ops.TravelWeights over the same field — the field then minimises
+    the weighted length (DESIGN.md 10 "Weighted travel fields"), cost, distance and max_dist are in weighted units (never less than
+    the geometric ones), and rebuild() reads the layer again."""
 
-    def __init__(self, field, radius, sources, space=None, max_dist=None, rounds_per_check=16):
-        self.need2, self.limit, _ = check_travel(field, radius, sources, space, max_dist, rounds_per_check)
-        self._settings(field, radius, space, max_dist, rounds_per_check)
+    def __init__(self, field, radius, sources, space=None, max_dist=None, rounds_per_check=16, weights=None):
+        self.need2, self.limit, _ = check_travel(field, radius, sources, space, max_dist, rounds_per_check, weights)
+        self._settings(field, radius, space, max_dist, rounds_per_check, weights)
         self.buf = torch.empty(_lib.lib().tohip_travel_bytes(*self.dims), dtype=torch.uint8, device=self.device)
         self._ws = None
         self.sources = self.seeded = None
         self.rounds = 0
         self.rebuild(sources)
 
-    def _settings(self, field, radius, space, max_dist, rounds_per_check):
+    def _settings(self, field, radius, space, max_dist, rounds_per_check, weights=None):
         self.field, self.radius, self.space, self.max_dist, self.rounds_per_check = field, float(radius), space, max_dist, int(rounds_per_check)
+        self.weights = weights
         self.origin, self.resolution, self.dims, self.device, self.geom = field.origin, field.resolution, field.dims, field.device, field.geom
 
     @classmethod
@@ -1603,7 +1728,7 @@ class TravelField:
         the single build into the slice."""
         self = cls.__new__(cls)
         self.need2, self.limit = fields.need2, fields.limit
-        self._settings(fields.field, fields.radius, fields.space, fields.max_dist, fields.rounds_per_check)
+        self._settings(fields.field, fields.radius, fields.space, fields.max_dist, fields.rounds_per_check, fields.weights)
         self.buf, self._ws, self.sources, self.seeded, self.rounds = buf, None, sources, seeded, fields.rounds
         return self
 
@@ -1612,11 +1737,16 @@ class TravelField:
         occ, fre = (ptr(self.space.occupied.buf), ptr(self.space.free.buf)) if self.space is not None else (None, None)
         return (ptr(self.field.buf), self.field.buf.numel(), occ, fre, self.field.occupied.buf.numel(), ctypes.byref(self.geom), self.need2)
 
+    def _layer(self):
+        """The weighted entries' last arguments: the layer and its size."""
+        w = check_travel_weights(self.field, self.weights)
+        return ptr(w.buf), w.buf.numel()
+
     def rebuild(self, sources=None):
-        """Recompute the whole field into the same buffers — after field.rebuild(), or from new sources (None: the last ones) when
-        the robot has moved.  One synchronisation per rounds_per_check rounds.  -> self."""
+        """Recompute the whole field into the same buffers — after field.rebuild() (and weights.rebuild()), or from new sources
+        (None: the last ones) when the robot has moved.  One synchronisation per rounds_per_check rounds.  -> self."""
         if sources is not None:
-            check_travel(self.field, self.radius, sources, self.space, self.max_dist, self.rounds_per_check)
+            check_travel(self.field, self.radius, sources, self.space, self.max_dist, self.rounds_per_check, self.weights)
             self.sources = _check_rows3(sources, "sources").detach().to(device=self.device, dtype=torch.float32).contiguous()
         S = self.sources.shape[0]
         if S == 0:
@@ -1625,8 +1755,14 @@ class TravelField:
             self._ws = torch.empty(_lib.lib().tohip_travel_workspace_bytes(*self.dims), dtype=torch.uint8, device=self.device)
         self.seeded = torch.empty(S, dtype=torch.uint8, device=self.device)
         rounds = ctypes.c_int64(0)
-        _map_call(self.device, "tohip_travel_build", *self._set(), ptr(self.sources), S, self.limit, self.rounds_per_check, ptr(self.buf),
-                  self.buf.numel(), ptr(self._ws), self._ws.numel(), ptr(self.seeded), ctypes.byref(rounds))
+        if self.weights is None:
+            _map_call(self.device, "tohip_travel_build", *self._set(), ptr(self.sources), S, self.limit, self.rounds_per_check, ptr(self.buf),
+                      self.buf.numel(), ptr(self._ws), self._ws.numel(), ptr(self.seeded), ctypes.byref(rounds))
+        else:   # the batch's weighted entry at n_fields = 1: every source names field 0
+            zeros = torch.zeros(S, dtype=torch.int32, device=self.device)
+            _map_call0(self.device, "tohip_travel_build_weighted", *self._set(), ptr(self.sources), ptr(zeros), S, 1, self.limit,
+                       self.rounds_per_check, ptr(self.buf), self.buf.numel(), ptr(self._ws), self._ws.numel(), ptr(self.seeded),
+                       ctypes.byref(rounds), *self._layer())
         self.rounds = int(rounds.value)
         return self
 
@@ -1661,7 +1797,8 @@ class TravelField:
         """One path per goal position -> a list of (L,3) f32 device tensors, the voxel centres from the source to the goal's voxel
         (L = 0: unreachable, out of range or outside dims); every leg joins two 26-neighbours and is one field.edges(a, b, radius)
         calls open.  max_rows (None: sized from the goals' costs) bounds the rows per path: ValueError names the goal and the rows
-        it needs where a path does not fit.  One launch, one synchronisation."""
+        it needs where a path does not fit.  One launch, one synchronisation.  Over a weighted field the paths are the weighted field's:
+        every step costs at least its length, so the same row bound holds."""
         g = covmap_points(_check_rows3(goals, "goals", empty=True), self.device, "TravelField.paths")
         G = g.shape[0]
         if G == 0:
@@ -1673,7 +1810,13 @@ class TravelField:
             raise ValueError(f"max_rows must be an integer >= 1 or None, got {max_rows!r}")
         rows = torch.empty((G, int(max_rows), 3), dtype=torch.float32, device=self.device)
         counts = torch.empty(G, dtype=torch.int64, device=self.device)
-        _map_call(self.device, "tohip_travel_paths", ptr(self.buf), self.buf.numel(), *self._set(), ptr(g), G, int(max_rows), ptr(rows), ptr(counts))
+        if self.weights is None:
+            _map_call(self.device, "tohip_travel_paths", ptr(self.buf), self.buf.numel(), *self._set(), ptr(g), G, int(max_rows), ptr(rows),
+                      ptr(counts))
+        else:
+            zeros = torch.zeros(G, dtype=torch.int32, device=self.device)
+            _map_call0(self.device, "tohip_travel_paths_weighted", ptr(self.buf), self.buf.numel(), *self._set(), 1, ptr(g), ptr(zeros), G,
+                       int(max_rows), ptr(rows), ptr(counts), *self._layer())
         n = counts.cpu().tolist()
         for e, k in enumerate(n):
             if k < 0:
@@ -1690,12 +1833,14 @@ def travel_tiles(dims):
     return int(np.prod([-(-int(d) // 8) for d in dims]))
 
 
-def check_travel_batch(field, radius, sources, source_field=None, n_fields=None, space=None, max_dist=None, rounds_per_check=16, dims=None):
+def check_travel_batch(field, radius, sources, source_field=None, n_fields=None, space=None, max_dist=None, rounds_per_check=16, dims=None,
+                       weights=None):
     """A batch of travel fields' arguments, by name; needs no GPU.  check_travel's rules, and: source_field: None (one field per
     source) or an integer tensor of shape (S,) — a row outside [0, n_fields) is allowed: its source is ignored and reported;
     n_fields: None (S without source_field, else the largest row + 1, at least 1) or an integer in [1, 256]; n_fields times the
-    grid's tiles must fit 31 bits (dims: the grid's, None: the field's).  -> (need2, limit, S, n_fields); ValueError otherwise."""
-    need2, limit, S = check_travel(field, radius, sources, space, max_dist, rounds_per_check)
+    grid's tiles must fit 31 bits (dims: the grid's, None: the field's); weights: check_travel's, one layer for all fields.
+    -> (need2, limit, S, n_fields); ValueError otherwise."""
+    need2, limit, S = check_travel(field, radius, sources, space, max_dist, rounds_per_check, weights)
     if source_field is not None:
         if not torch.is_tensor(source_field) or source_field.is_floating_point() or source_field.dtype == torch.bool or \
                 tuple(source_field.shape) != (S,):
@@ -1718,12 +1863,13 @@ class TravelFields:
     the field each source seeds (None: one field per source, field i from source i) — a row outside [0, n_fields) is ignored and
     reported in seeded; n_fields: B (None: S, or the largest source_field + 1); one space, max_dist and limit for all fields.  It
     holds B cost volumes one after the other (4 B nx ny nz bytes) and the worklist's workspace.  n_fields, seeded (S,) uint8 on the
-    device, rounds, limit as TravelField's.  fields[b] is an ops.TravelField over field b's slice: no copy, no build."""
+    device, rounds, limit as TravelField's.  fields[b] is an ops.TravelField over field b's slice: no copy, no build.  weights (None:
+    none): one ops.TravelWeights that all fields share, as TravelField's; fields[b] carries it."""
 
-    def __init__(self, field, radius, sources, source_field=None, n_fields=None, space=None, max_dist=None, rounds_per_check=16):
+    def __init__(self, field, radius, sources, source_field=None, n_fields=None, space=None, max_dist=None, rounds_per_check=16, weights=None):
         self.need2, self.limit, _, self.n_fields = check_travel_batch(field, radius, sources, source_field, n_fields, space, max_dist,
-                                                                      rounds_per_check)
-        TravelField._settings(self, field, radius, space, max_dist, rounds_per_check)
+                                                                      rounds_per_check, weights=weights)
+        TravelField._settings(self, field, radius, space, max_dist, rounds_per_check, weights)
         L = _lib.lib()
         self.buf = torch.empty(L.tohip_travel_batch_bytes(*self.dims, self.n_fields), dtype=torch.uint8, device=self.device)
         self._ws = torch.empty(L.tohip_travel_batch_workspace_bytes(*self.dims, self.n_fields), dtype=torch.uint8, device=self.device)
@@ -1732,6 +1878,7 @@ class TravelFields:
         self.rebuild(sources, source_field)
 
     _set = TravelField._set
+    _layer = TravelField._layer
 
     def __len__(self):
         return self.n_fields
@@ -1741,7 +1888,7 @@ class TravelFields:
         sources, source_field None means field i from source i again).  The number of fields stays.  -> self."""
         if sources is not None:
             _, _, S, _ = check_travel_batch(self.field, self.radius, sources, source_field, self.n_fields, self.space, self.max_dist,
-                                            self.rounds_per_check)
+                                            self.rounds_per_check, weights=self.weights)
             self.sources = _check_rows3(sources, "sources").detach().to(device=self.device, dtype=torch.float32).contiguous()
             self.source_field = (torch.arange(S, device=self.device) if source_field is None else source_field.detach().to(self.device)) \
                 .clamp(-1, self.n_fields).to(torch.int32).contiguous()   # (any row out of range stays out of range)
@@ -1750,9 +1897,12 @@ class TravelFields:
         S = self.sources.shape[0]
         self.seeded = torch.empty(S, dtype=torch.uint8, device=self.device)
         rounds = ctypes.c_int64(0)
-        _map_call(self.device, "tohip_travel_build_batch", *self._set(), ptr(self.sources), ptr(self.source_field), S, self.n_fields, self.limit,
-                  self.rounds_per_check, ptr(self.buf), self.buf.numel(), ptr(self._ws), self._ws.numel(), ptr(self.seeded),
-                  ctypes.byref(rounds))
+        args = (*self._set(), ptr(self.sources), ptr(self.source_field), S, self.n_fields, self.limit, self.rounds_per_check, ptr(self.buf),
+                self.buf.numel(), ptr(self._ws), self._ws.numel(), ptr(self.seeded), ctypes.byref(rounds))
+        if self.weights is None:
+            _map_call(self.device, "tohip_travel_build_batch", *args)
+        else:
+            _map_call0(self.device, "tohip_travel_build_weighted", *args, *self._layer())
         self.rounds = int(rounds.value)
         return self
 
@@ -1810,8 +1960,11 @@ class TravelFields:
             raise ValueError(f"max_rows must be an integer >= 1 or None, got {max_rows!r}")
         rows = torch.empty((G, int(max_rows), 3), dtype=torch.float32, device=self.device)
         counts = torch.empty(G, dtype=torch.int64, device=self.device)
-        _map_call(self.device, "tohip_travel_paths_batch", ptr(self.buf), self.buf.numel(), *self._set(), self.n_fields, ptr(g), ptr(gf), G,
-                  int(max_rows), ptr(rows), ptr(counts))
+        args = (ptr(self.buf), self.buf.numel(), *self._set(), self.n_fields, ptr(g), ptr(gf), G, int(max_rows), ptr(rows), ptr(counts))
+        if self.weights is None:
+            _map_call(self.device, "tohip_travel_paths_batch", *args)
+        else:
+            _map_call0(self.device, "tohip_travel_paths_weighted", *args, *self._layer())
         n = counts.cpu().tolist()
         for e, k in enumerate(n):
             if k < 0:
@@ -1917,8 +2070,8 @@ class Components:
     def min_over(self, values):
         """The minimum of a value volume over each component -> (value (n,) int64, voxel (n,) int32): the smallest word over the
         component's voxels that is not 0xFFFFFFFF and the lowest linear index that attains it, -1 / -1 where there is none.  values: an
-        ops.TravelField (its cost: how far is the nearest voxel of each component, and which is it) or a tensor of one uint32 per
-        voxel in the labels' layout."""
+        ops.TravelField (its cost: how far is the nearest voxel of each component, and which is it — the weighted cost where the
+        field has weights) or a tensor of one uint32 per voxel in the labels' layout."""
         check_components(self.grid, self.connectivity, self.rounds_per_check, values)
         buf = values.buf if isinstance(values, TravelField) else values
         value = torch.empty(self.n, dtype=torch.int64, device=self.device)

@@ -1411,6 +1411,96 @@ def travel_paths_ref(goals, origin, resolution, cost, T):
     return out
 
 
+# ---- weighted travel fields ("Weighted travel fields"): a layer kappa (nx,ny,nz) of factors in [16, 255], 16 neutral.
+TRAVEL_KAPPA_NEUTRAL, TRAVEL_KAPPA_MAX = 16, 255
+TRAVEL_MAX_STEP = (111 * 2 * TRAVEL_KAPPA_MAX + 16) >> 5   # 1769
+
+
+def travel_step(w, ka, kb):
+    """The weighted cost of a move of weight w (64, 91 or 111) between voxels of factors ka and kb: (w (ka + kb) + 16) >> 5 —
+    symmetric, an integer, >= w for factors >= 16 and exactly w at 16.  Integers or int64 arrays."""
+    return (w * (ka + kb) + 16) >> 5
+
+
+def travel_weighted_ref(T, seeds, kappa, limit=TRAVEL_MAX_LIMIT):
+    """travel_ref with the layer kappa (nx,ny,nz): the move m from u to v costs travel_step(w_m, kappa[u], kappa[v]).  The same
+    sweeps, the same truncation, -1 = unreachable."""
+    T = np.asarray(T, dtype=bool)
+    kappa = np.asarray(kappa, dtype=np.int64)
+    assert kappa.shape == T.shape and kappa.min(initial=TRAVEL_KAPPA_NEUTRAL) >= TRAVEL_KAPPA_NEUTRAL and \
+        kappa.max(initial=TRAVEL_KAPPA_NEUTRAL) <= TRAVEL_KAPPA_MAX
+    big = np.int64(1) << 40
+    cost = np.full(T.shape, big, dtype=np.int64)
+    for x, y, z in np.asarray(seeds, dtype=np.int64).reshape(-1, 3):
+        if 0 <= x < T.shape[0] and 0 <= y < T.shape[1] and 0 <= z < T.shape[2] and T[x, y, z]:
+            cost[x, y, z] = 0
+    allowed = travel_allowed_ref(T)
+    steps = {m: travel_step(TRAVEL_WEIGHTS[sum(1 for k in d if k) - 1], kappa, _travel_shift(kappa, d, TRAVEL_KAPPA_NEUTRAL))
+             for m, d in enumerate(TRAVEL_MOVES) if m != 13}
+    while True:
+        before = cost.copy()
+        for m, ok in allowed.items():
+            cand = _travel_shift(cost, TRAVEL_MOVES[m], big) + steps[m]
+            cost = np.where(ok & (cand <= limit) & (cand < cost), cand, cost)
+        if np.array_equal(cost, before):
+            break
+    return np.where(cost <= limit, cost, -1).astype(np.int64)
+
+
+def travel_weighted_paths_ref(goals, origin, resolution, cost, T, kappa):
+    """travel_paths_ref under the layer kappa: the predecessor of v is the allowed neighbour u with cost[u] + travel_step(w, kappa[v],
+    kappa[u]) == cost[v], the lowest move number on ties."""
+    cost, T, kappa = np.asarray(cost, dtype=np.int64), np.asarray(T, dtype=bool), np.asarray(kappa, dtype=np.int64)
+    f32 = np.float32
+    o, r = np.asarray(origin, dtype=f32).reshape(3), f32(resolution)
+    codes = travel_positions_ref(goals, origin, resolution, cost)
+    q, _ = occ_fixed(goals, origin, resolution)
+    inside = lambda p: all(0 <= p[a] < T.shape[a] for a in range(3))   # noqa: E731
+    out = []
+    for e, code in enumerate(codes):
+        rows = []
+        if code >= 0:
+            v = tuple(int(k) for k in q[e] >> 8)
+            while True:
+                rows.append((o + ((np.asarray(v, dtype=f32) + f32(0.5)).astype(f32) * r).astype(f32)).astype(f32))
+                if cost[v] == 0:
+                    break
+                for m, d in enumerate(TRAVEL_MOVES):
+                    u = (v[0] + d[0], v[1] + d[1], v[2] + d[2])
+                    if m == 13 or not inside(u) or cost[u] < 0:
+                        continue
+                    step = travel_step(TRAVEL_WEIGHTS[sum(1 for k in d if k) - 1], int(kappa[v]), int(kappa[u]))
+                    box = [(v[0] + ex, v[1] + ey, v[2] + ez) for ex in {0, d[0]} for ey in {0, d[1]} for ez in {0, d[2]}]
+                    if cost[u] + step == cost[v] and all(T[b] for b in box):
+                        v = u
+                        break
+                else:
+                    raise AssertionError(f"no predecessor at {v}: not a weighted travel field")
+        out.append(np.asarray(rows, dtype=f32).reshape(-1, 3))
+    return out
+
+
+def travel_weights_lut(radius, soft_radius, resolution, D, gain=4.0):
+    """The default table of tools.travel_weights -> (D^2 + 1,) uint8, indexed by the clearance field's squared gap d2 in voxels:
+    kappa(d2) = 16 + 16 gain max(0, (soft - g) / (soft - radius))^2 with g = sqrt(d2) f64(f32 resolution), computed in float64, then
+    np.rint and clipped to [16, 255].  Neutral at and beyond soft_radius, steepest at radius."""
+    d2 = np.arange(int(D) * int(D) + 1, dtype=np.float64)
+    g = np.sqrt(d2) * float(np.float32(resolution))
+    t = np.maximum(0.0, (float(soft_radius) - g) / (float(soft_radius) - float(radius)))
+    return np.clip(np.rint(16.0 + 16.0 * float(gain) * t * t), TRAVEL_KAPPA_NEUTRAL, TRAVEL_KAPPA_MAX).astype(np.uint8)
+
+
+def travel_weights_ref(field, lut, state=None, unknown_add=0):
+    """k_travel_weights restated: kappa[v] = lut[min(field[v], len(lut) - 1)] over a clearance field (nx,ny,nz); where `state`
+    (state_ref's codes per voxel: 0 unknown, 1 free, 2 occupied) is given, + unknown_add at the unknown voxels, saturating at 255.
+    -> (nx,ny,nz) uint8."""
+    lut = np.asarray(lut, dtype=np.int64).reshape(-1)
+    k = lut[np.minimum(np.asarray(field, dtype=np.int64), len(lut) - 1)]
+    if state is not None:
+        k = np.where(np.asarray(state) == 0, np.minimum(k + int(unknown_add), TRAVEL_KAPPA_MAX), k)
+    return k.astype(np.uint8)
+
+
 def travel_weight_fixed(travel_weight, resolution):
     """select_views_volume's travel_weight (revealed voxels per metre travelled) -> the pick's integer m = round(travel_weight r 2^20 /
     64): gain 2^20 - m cost is then gain - travel_weight metres, in units of 2^-20 voxel."""

@@ -296,17 +296,44 @@ def free_nodes(field, radius, stride=1, space=None):
     return field.free_nodes(radius, stride, space)
 
 
-def travel_field(field, start, radius, space=None, max_dist=None):
+def travel_field(field, start, radius, space=None, max_dist=None, weights=None):
     """Can the robot get there, and how far is it?  An ops.TravelField ("Travel field"): from `start` — (3,) or (S,3)
     positions, the robot's — the length of the shortest path to every voxel of the map, through voxels whose whole cube the clearance
     field certifies for `radius` metres and, with space= (an ops.SpaceMap), that are known to be free; 26-connected, no corner cut.
     tf.reachable(positions), tf.distance(positions) (metres), tf.cost(positions) and tf.paths(goals) ask it; travel_path(tf, goal)
     gives one path; select_views_volume(..., travel=tf, travel_weight=w) prices the trip to each candidate.  max_dist (metres)
     truncates the field.  A start that is not traversable is ignored (tf.seeded): nothing is then reachable.  tf.rebuild(start)
-    follows field.rebuild() or a robot that has moved."""
+    follows field.rebuild() or a robot that has moved.  weights (an ops.TravelWeights, travel_weights' result; None: geometric
+    length): the field minimises the weighted length instead — routes keep off walls and out of the unknown — and every cost,
+    distance and max_dist is then in weighted units; tf.weights tells a consumer what it holds."""
     if not isinstance(field, ops.ClearanceField):
         raise ValueError(f"travel_field: field must be an ops.ClearanceField, got {type(field).__name__}")
-    return ops.TravelField(field, radius, start, space=space, max_dist=max_dist)
+    return ops.TravelField(field, radius, start, space=space, max_dist=max_dist, weights=weights)
+
+
+def travel_weights(field, radius, soft_radius, gain=4.0, space=None, unknown_add=0, lut=None):
+    """A cost layer so that routes keep off walls: an ops.TravelWeights ("Weighted travel fields") for
+    travel_field(s)(..., weights=).  Each voxel gets a factor kappa in [16, 255] (16: neutral) from the clearance field's gap g
+    around it: kappa = 16 + 16 gain max(0, (soft_radius - g) / (soft_radius - radius))^2, rounded — neutral at and beyond soft_radius,
+    1 + gain times as dear at `radius`, where the traversable set ends.  The table is computed on the host in float64
+    (synth.travel_weights_lut restates it) and gathered on the device in one launch; lut= (1-D integers in [16, 255], indexed by the
+    field's squared gap in voxels, the last entry for everything beyond) replaces it.  space= with unknown_add (0 .. 255) adds that
+    much at every voxel that is neither occupied nor known free, saturating at 255: a dash through the unknown stops costing what
+    a walk through the scanned room costs.  weights.rebuild() follows field.rebuild()."""
+    if not isinstance(field, ops.ClearanceField):
+        raise ValueError(f"travel_weights: field must be an ops.ClearanceField, got {type(field).__name__}")
+    if lut is None:
+        r = ops.check_tour_radius(radius)
+        soft = ops._float_or_nan(soft_radius) if ops._is_real(soft_radius) else float("nan")
+        if not np.isfinite(soft) or soft <= r:
+            raise ValueError(f"travel_weights: soft_radius must be a finite number of metres > radius ({radius!r}), got {soft_radius!r}")
+        gn = ops._float_or_nan(gain) if ops._is_real(gain) else float("nan")
+        if not np.isfinite(gn) or gn < 0.0:
+            raise ValueError(f"travel_weights: gain must be a finite number >= 0, got {gain!r}")
+        d2 = np.arange(field.D * field.D + 1, dtype=np.float64)
+        t = np.maximum(0.0, (soft - np.sqrt(d2) * float(np.float32(field.resolution))) / (soft - r))
+        lut = np.clip(np.rint(16.0 + 16.0 * gn * t * t), ops.TRAVEL_KAPPA_NEUTRAL, ops.TRAVEL_KAPPA_MAX).astype(np.uint8)
+    return ops.TravelWeights(field, lut=lut, space=space, unknown_add=unknown_add)
 
 
 def ground_layer(map, headroom, step=1, unknown='free'):
@@ -320,14 +347,16 @@ def ground_layer(map, headroom, step=1, unknown='free'):
     return ops.GroundLayer(map, headroom, step, unknown)
 
 
-def ground_travel(layer, start, radius, max_dist=None, max_drop=None, field=None):
+def ground_travel(layer, start, radius, max_dist=None, max_drop=None, field=None, weights=None):
     """Can the robot DRIVE there, and how far is it?  The ops.TravelField of a ground layer: over layer.field(...) and layer.space,
     from `start` — (3,) or (S,3) poses at any height above the floor, a sensor's for instance — snapped to the standing voxel at or
     at most max_drop voxels below (None: the layer's headroom H; a start with nothing to stand on is ignored, tf.seeded).  radius:
     the robot's, in metres; max_dist (metres) truncates the travel field; field: a ClearanceField from layer.field(...) to reuse
     (None: one is built, truncated one voxel beyond what `radius` needs).  Every voxel with a cost is a place the robot's centre can
     be: over ramps and steps of at most layer.step voxels, never across a ledge or a pit, under a table only where it fits.
-    tf.sources holds the snapped starts; layer.snap(path, max_drop) brings a path's rows down to the wheels."""
+    tf.sources holds the snapped starts; layer.snap(path, max_drop) brings a path's rows down to the wheels.  weights: an
+    ops.TravelWeights of the layer's geometry (over `field`, or over another layer.field(...)), as travel_field's — a slope penalty, a
+    keep-out zone."""
     if not isinstance(layer, ops.GroundLayer):
         raise ValueError(f"ground_travel: layer must be an ops.GroundLayer, got {type(layer).__name__}")
     if field is None:
@@ -336,7 +365,7 @@ def ground_travel(layer, start, radius, max_dist=None, max_drop=None, field=None
     elif not isinstance(field, ops.ClearanceField) or field.occupied is not layer.obstacles:
         raise ValueError("ground_travel: field must be an ops.ClearanceField from layer.field(...)")
     standing, _ = layer.snap(ops._check_rows3(start, "start"), layer.H if max_drop is None else max_drop)
-    return ops.TravelField(field, radius, standing, space=layer.space, max_dist=max_dist)
+    return ops.TravelField(field, radius, standing, space=layer.space, max_dist=max_dist, weights=weights)
 
 
 def yaw_candidates(quat, half_range, n):
@@ -1013,7 +1042,8 @@ def select_views_volume(space_or_evidence_map, cand_poses, cand_quats, k, min_ga
 
     travel (an ops.TravelField of the map's geometry, travel_field's result; None: none) prices the trip: a candidate whose position
     the robot cannot reach is never chosen, and every round's winner maximises gain - travel_weight x metres travelled
-    (travel_weight >= 0, in revealed voxels per metre; 0: reachability alone).  The stop rule stays the gain's."""
+    (travel_weight >= 0, in revealed voxels per metre; 0: reachability alone).  The stop rule stays the gain's.  With a weighted
+    field (travel_field(..., weights=)) the trip's price is the weighted cost."""
     space, cam, mn, mx = _volume_setup("select_views_volume", space_or_evidence_map, camera)
     cost, m = None, 0
     if travel is not None:
@@ -1259,7 +1289,7 @@ def tour_edge_query(cloud, nodes, radius, stage=None):
 
 
 def plan_tour(points_or_cloud_or_model, poses, quats=None, clearance_radius=None, closed=False, max_moves=None, via=None, via_k=12,
-              via_max_edge=None, travel=False, space=None):
+              via_max_edge=None, travel=False, space=None, weights=None):
     """A short visiting order through view poses whose every straight leg keeps clearance_radius from the cloud.
     poses (n,3), 2 <= n <= 256: row 0 is where the tour starts (the robot), the others are the views (select_views' sel.poses);
     quats (n,4) or None.  Every pair of nodes is put to the swept clearance query (edge_clearance); the pairs it finds nothing near
@@ -1280,7 +1310,8 @@ def plan_tour(points_or_cloud_or_model, poses, quats=None, clearance_radius=None
     v is walked as pose u, the voxel centres of fields.paths(pose v, field u), pose v; the first and the last hop stay inside the
     end voxels' certified cubes, every other hop joins two 26-neighbours, so every hop is a leg field.edges calls open, and the rows
     go into refine_path(field, ...) as any tour's do.  A path's rows take the quaternion of the view they lead to; walk_nodes and
-    roadmap stay None.  No lattice, no node limit: the map of any size is the roadmap.
+    roadmap stay None.  No lattice, no node limit: the map of any size is the roadmap.  weights (an ops.TravelWeights, needs
+    travel=True): the matrix is the weighted one, so a map route is priced by its weighted cost against the straight leg's length.
     -> Tour.  Launches only, then one copy to the host (with via: one read-back per batch of route sweeps before it; with travel:
     the build's read-backs before it and one for the paths after it)."""
     if not isinstance(travel, (bool, np.bool_)):
@@ -1294,6 +1325,8 @@ def plan_tour(points_or_cloud_or_model, poses, quats=None, clearance_radius=None
             raise ValueError("plan_tour: travel=True needs a clearance_radius (a finite number > 0), got None")
     elif space is not None:
         raise ValueError("plan_tour: space= needs travel=True")
+    if weights is not None and not travel:
+        raise ValueError("plan_tour: weights= needs travel=True")
     cloud, pts = _clearance_cloud(points_or_cloud_or_model, "plan_tour", field=True)
     n, r, max_moves = ops.check_tour(poses, quats, clearance_radius, closed, max_moves)
     if via is not None:
@@ -1316,7 +1349,7 @@ def plan_tour(points_or_cloud_or_model, poses, quats=None, clearance_radius=None
     tail = [idx.view(torch.uint8)] if idx is not None else []
     tm = None
     if travel:   # the map's route lengths between the tour nodes, in the tour's unit
-        tm = travel_matrix(cloud, nodes, r, space=space)
+        tm = travel_matrix(cloud, nodes, r, space=space, weights=weights)
         scale = float(np.float32(cloud.resolution)) * 16384.0   # (synth.tour_travel_units: one rounded f64 product, half to even)
         via_D = torch.where(tm.cost < 0, torch.full_like(tm.cost, ops.ROADMAP_INF), torch.round(tm.cost.clamp(min=0).double() * scale).long())
         buf, flag = ops.tour_plan_via(nodes, idx, via_D.contiguous(), closed, max_moves)
@@ -1547,14 +1580,15 @@ def plan_path(points_or_cloud_or_model, start, goal, via, clearance_radius, k=12
                        roadmap=rm)
 
 
-def travel_fields(field, starts, radius, space=None, max_dist=None):
+def travel_fields(field, starts, radius, space=None, max_dist=None, weights=None):
     """One travel field per start, all built in the same worklist rounds: an ops.TravelFields ("Travel fields in
     batches") over `starts` (S,3), S <= 256 — a team's robots, a tour's views.  fields[b] is the ops.TravelField of start b (no
     copy), fields.cost(positions) / .distance / .reachable answer (S,M) at once, fields.paths(goals, goal_field) walks each goal in
-    the field it names.  Field b is bit for bit travel_field(field, starts[b], ...)."""
+    the field it names.  Field b is bit for bit travel_field(field, starts[b], ...).  weights: one ops.TravelWeights for all fields, as
+    travel_field's."""
     if not isinstance(field, ops.ClearanceField):
         raise ValueError(f"travel_fields: field must be an ops.ClearanceField, got {type(field).__name__}")
-    return ops.TravelFields(field, radius, ops._check_rows3(starts, "starts"), space=space, max_dist=max_dist)
+    return ops.TravelFields(field, radius, ops._check_rows3(starts, "starts"), space=space, max_dist=max_dist, weights=weights)
 
 
 class TravelMatrix(_Result):
@@ -1564,11 +1598,12 @@ class TravelMatrix(_Result):
     __slots__ = ("cost", "distance", "seeded", "fields")
 
 
-def travel_matrix(field, positions, radius, space=None, max_dist=None):
+def travel_matrix(field, positions, radius, space=None, max_dist=None, weights=None):
     """The map distance between every two of `positions` (M,3), M <= 256: what the robot must travel, not the straight line.
     -> TravelMatrix.  One batched build, one lookup launch.  Symmetric wherever both rows are seeded: an allowed move is allowed
-    both ways at the same weight."""
-    fields = travel_fields(field, positions, radius, space, max_dist)
+    both ways at the same weight.  weights (travel_field's): the weighted cost of every pair, still symmetric — a step's cost is
+    symmetric in its two voxels."""
+    fields = travel_fields(field, positions, radius, space, max_dist, weights)
     cost, distance = fields._positions(fields.sources, True, True)
     return TravelMatrix(cost=cost, distance=distance, seeded=fields.seeded, fields=fields)
 
@@ -1593,7 +1628,8 @@ def assign_frontiers(space_or_evidence_map, fields, min_unknown=1, min_size=1, c
     back between them — and tohip_assign_greedy hands them out: among the pairs (robot, cluster) with a cost >= min_cost (metres;
     just above 0 keeps a robot from being sent to the opening it stands in) the cheapest goes first, ties to the lower robot, then
     the lower cluster row, and no robot or cluster is taken twice.  Greedy, not optimal; cluster size plays no part.  The same
-    answer in every run.  -> FrontierAssignment."""
+    answer in every run.  Over weighted fields (travel_fields(..., weights=)) the price is the weighted cost.
+    -> FrontierAssignment."""
     if not isinstance(fields, ops.TravelFields):
         raise ValueError(f"assign_frontiers: fields must be an ops.TravelFields, got {type(fields).__name__}")
     R = fields.n_fields
@@ -1646,7 +1682,9 @@ class TravelPath(_Result):
     """What travel_path returns: poses (L,3) f32 on the device, the voxel centres from the travel field's source to the goal's voxel
     (L = 0 where it is not reachable) — they go as they are into refine_path(field, path.poses, clearance_radius=radius), which
     shortcuts the 26-connected staircase; length: metres along the field's metric (inf where not reachable); cost: the integer
-    behind it, in 1/64 voxel edge (-1 unreachable, -2 out of range or outside dims); reachable: bool."""
+    behind it, in 1/64 voxel edge (-1 unreachable, -2 out of range or outside dims); reachable: bool.  Over a weighted field
+    (tf.weights) cost is the weighted cost the field minimises and length the GEOMETRIC metres summed over the rows' moves (64, 91
+    or 111 per move, then the same conversion): never more than cost / 64 resolution, and equal to it at kappa = 16 everywhere."""
     __slots__ = ("poses", "length", "cost", "reachable")
 
 
@@ -1657,7 +1695,12 @@ def travel_path(tf, goal):
     g = _point3(goal, "goal", tf.device).reshape(1, 3)
     cost = int(tf.cost(g).item())
     poses = tf.paths(g)[0] if cost >= 0 else torch.empty((0, 3), dtype=torch.float32, device=tf.device)
-    return TravelPath(poses=poses, length=float(tf.distance(g).item()), cost=cost, reachable=cost >= 0)
+    length = float(tf.distance(g).item())
+    if tf.weights is not None and cost >= 0:   # the geometric length of the rows: the field's unit, unweighted
+        axes = ((poses[1:] - poses[:-1]).abs() > 0.5 * float(tf.resolution)).sum(dim=1)
+        units = int(torch.tensor([0, 64, 91, 111], device=tf.device)[axes].sum().item())
+        length = float(np.float32(np.float32(units) * np.float32(0.015625)) * np.float32(tf.resolution))
+    return TravelPath(poses=poses, length=length, cost=cost, reachable=cost >= 0)
 
 
 class FrontierClusters(_Result):
@@ -1685,7 +1728,8 @@ def frontier_clusters(space_or_evidence_map, min_unknown=1, min_size=1, connecti
 
     The cost is taken over the cluster's own voxels, so it needs a travel field in which frontier voxels are traversable: the
     pairing clearance_field(space, ..., unknown='free') with travel_field(..., space=space).  With unknown='obstacle' every frontier
-    voxel touches an obstacle, none is traversable and every cluster reports unreachable."""
+    voxel touches an obstacle, none is traversable and every cluster reports unreachable.  With a weighted field the cost is the
+    weighted one."""
     space = space_or_evidence_map.space if isinstance(space_or_evidence_map, ops.EvidenceMap) else space_or_evidence_map
     if not isinstance(space, ops.SpaceMap):
         raise ValueError(f"frontier_clusters: the map must be an ops.SpaceMap or an ops.EvidenceMap, got {type(space_or_evidence_map).__name__}")
