@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_travel_weights_bytes / tohip_travel_weights_build / tohip_travel_build_weighted / tohip_travel_paths_weighted (weighted
+/* (still 15) + tohip_evid_weight_plane / tohip_view_information (information gain: a view scored by a weight per voxel that depends on
+ * its evidence byte, summed over the voxels it sees, and the map's remaining information): new symbols only.
+ * (still 15) + tohip_travel_weights_bytes / tohip_travel_weights_build / tohip_travel_build_weighted / tohip_travel_paths_weighted (weighted
  * travel fields: a per-voxel cost factor so routes keep off walls and out of the unknown): new symbols only.
  * (still 15) + tohip_occ_coarsen / tohip_evid_coarsen and the TOHIP_COARSEN_* constants (coarsening maps: f x f x f voxels of one box reduced
  * to one voxel of a coarser box under a conservative or an optimistic rule, written or combined as the transfers do): new symbols only.
@@ -1448,6 +1450,37 @@ int tohip_view_volume(const void *occupied, const void *free_grid, const void *c
                       uint64_t *stats, void *stream);
 int tohip_view_volume_pick(const int64_t *gains, int32_t *taken, int64_t n_views, int64_t min_gain, int32_t round, int32_t *order,
                            int64_t *picked_gain, int32_t *stop, void *stream);
+
+/* ---- information gain (volume_kernels.hip, DESIGN.md §10, "Information gain") -------
+ * How much is left to learn about what a camera would see from here?  evidence is an evidence buffer of the geometry (evid_bytes,
+ * tohip_evid_bytes); table W is 256 unsigned 16-bit weights in DEVICE memory, indexed by the evidence byte read as unsigned, L + 128:
+ * W[0] weighs a voxel never observed.  A voxel v inside dims is a CANDIDATE of the map under W iff W[byte(v)] > 0, whatever its state;
+ * pad voxels are never candidates.
+ *
+ * tohip_evid_weight_plane: plane_out (an occupancy grid buffer of the geometry, grid_bytes, not the evidence buffer) receives the
+ * candidate mask — its header zero as tohip_occ_init leaves it, pad bits 0 — and *total_out (DEVICE int64, may be NULL, zero-filled by
+ * the caller) += the sum of W[byte(v)] over the voxels inside dims: the map's remaining information under W (one 64-bit integer
+ * atomic add per block).  One launch, nothing read back.  Prepared once, the plane serves every tohip_view_information launch until
+ * the evidence or the table changes.
+ *
+ * tohip_view_information: tohip_view_volume's arguments and meaning — view w, claimed, mark, view_index, window, stop, stats,
+ * n_views in [1, 65535], mark == claimed only where ONE view is scored — with `candidates` (tohip_evid_weight_plane's plane for this
+ * evidence and table) standing where the unknown voxels stood.  A candidate whose claimed bit is 0 is INFORMED by view w under
+ * tohip_view_volume's conditions (2) and (3), unchanged: its centre is kept by the cull, and tohip_los_segments(occupied, poses[w] ->
+ * centre, start_skip 1, end_skip 0) gives 1 — the target voxel itself is not tested, so a weakly occupied surface voxel can be
+ * informed; unknown voxels on the way do not block.  gains[w] (DEVICE int64 x n_views, overwritten) = the sum of W[byte(v)] over the
+ * informed voxels: an exact integer, the same in every run.  mark receives the informed voxels.  free_grid is not read; candidates
+ * must be none of occupied, free_grid, mark and evidence.  With W[0] = 1 and every other weight 0 on a map whose planes are the
+ * evidence's, the gains and the mark plane are tohip_view_volume's.  tohip_view_volume_pick and tohip_view_volume_pick_travel choose
+ * among these gains as they are; the travel pick forms gain 2^20 - m cost, so a caller keeps 65535 x voxels x 2^20 below 2^63.
+ * flags is reserved (0).  Every argument check returns before anything is enqueued; nothing synchronises with the host. */
+int tohip_evid_weight_plane(const void *evidence, size_t evid_bytes, const tohip_occ_geom *geom, const uint16_t *table, void *plane_out,
+                            size_t grid_bytes, int64_t *total_out, void *stream, uint32_t flags);
+int tohip_view_information(const void *occupied, const void *free_grid, const void *claimed, void *mark, size_t grid_bytes,
+                           const tohip_occ_geom *geom, const void *evidence, size_t evid_bytes, const uint16_t *table,
+                           const void *candidates, const float *poses, const float *quats, int64_t n_views, const int32_t *view_index,
+                           const tohip_camera *cam, float min_dist, float max_dist, int32_t window, int64_t *gains, const int32_t *stop,
+                           uint64_t *stats, void *stream, uint32_t flags);
 
 /* ---- ray casts and depth scans (raycast_kernels.hip, DESIGN.md §10, "Ray casts and depth scans") -------
  * Where does this ray stop?  Both entries walk exactly as tohip_los_segments walks (same steps, same tie rule, same tests).

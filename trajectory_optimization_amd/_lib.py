@@ -28,7 +28,7 @@ c_vp = ctypes.c_void_p
 # the scalar types a parameter can have stay these six)
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
             "float": ctypes.c_float, "double": ctypes.c_double}
-_POINTEES = set(_SCALARS) | {"void", "int8_t", "uint8_t", "uint32_t", "uint64_t"}   # what a pointer may point to
+_POINTEES = set(_SCALARS) | {"void", "int8_t", "uint8_t", "uint16_t", "uint32_t", "uint64_t"}   # what a pointer may point to
 _DECLARATOR = re.compile(r"(?:const\s+)?(.+?)\s*(\**)\s*\b(\w+)\s*(?:\[(\d+)\])?")
 
 

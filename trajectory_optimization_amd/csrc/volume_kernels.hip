@@ -23,6 +23,20 @@
 //                      window = 0 enumerates every brick and tests every unknown voxel: the same counts.
 //   k_view_volume_pick one block: the largest gain among the candidates not taken, the lowest index on ties.
 //
+//
+// INFORMATION GAIN ("Information gain"): the same kernel scores a view by what is left to learn about the voxels it
+// sees.  A table W of 256 unsigned 16-bit weights is indexed by the evidence byte read as unsigned, L + 128; a voxel inside dims is a
+// CANDIDATE iff W[byte] > 0, whatever its state; it is INFORMED by a view under the cull and the walk above (the target voxel is not
+// tested, so a weakly occupied surface voxel can be informed); gain(view) = the sum of W[byte] over the informed voxels.
+//
+//   k_evid_weight_plane  one lane per brick word: the table staged in LDS (512 B), the lane's 32 bytes as two 16-byte loads, the
+//                        candidate word (pad bits 0) stored; block 0 zeroes the header; with a total, one 64-bit integer atomic add
+//                        per block of the weights of the block's voxels inside dims.
+//   k_view_volume<true>  the weighted instantiation (the switch is a template parameter; the unweighted kernel is the code it was):
+//                        the candidate word comes from the plane, the table is staged in LDS, and pass 2 gathers W[byte at 32 w + b]
+//                        of each queued voxel in front of its walk (one register stays live across the walk, the load hides
+//                        under it) and adds it per survivor instead of 1.
+//
 // Integer counts, integer atomics, no process-wide state, nothing read back: a selection never synchronises with the host.
 namespace {
 
@@ -37,6 +51,50 @@ k_occ_unknown(const unsigned* __restrict__ occ, const unsigned* __restrict__ fre
     int bx, by, bz;
     occ_brick(g, w, bx, by, bz);
     out[w] = ~occ[w] & ~fre[w] & occ_brick_mask(g, bx, by, bz);
+}
+
+// the candidate word of every brick under a weight table, and the map's remaining information
+__global__ void __launch_bounds__(TO_BLOCK)
+k_evid_weight_plane(const uint4* __restrict__ vals, const unsigned short* __restrict__ table, unsigned* __restrict__ hdr, unsigned* __restrict__ out,
+                    OccGeom g, long long n_words, unsigned long long* __restrict__ total) {
+    __shared__ unsigned short s_table[256];
+    __shared__ unsigned long long s_wave[TO_BLOCK / 64];
+    static_assert(TO_BLOCK == 256, "one table entry per lane");
+    s_table[threadIdx.x] = table[threadIdx.x];
+    if (blockIdx.x == 0 && threadIdx.x < (int)(kOccHdr / 4)) hdr[threadIdx.x] = 0u;   // the header as tohip_occ_init leaves it
+    __syncthreads();
+    const long long w = (long long)blockIdx.x * TO_BLOCK + threadIdx.x;
+    unsigned long long sum = 0;
+    if (w < n_words) {
+        int bx, by, bz;
+        evid_brick(g, (unsigned)w, bx, by, bz);
+        const unsigned in = occ_brick_mask(g, bx, by, bz);
+        const uint4 lo = vals[2 * w], hi = vals[2 * w + 1];
+        const unsigned v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        unsigned cand = 0u, lane_sum = 0u;   // (32 weights below 2^16)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const unsigned x = v[k] ^ 0x80808080u;   // the bytes biased to L + 128
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const unsigned wt = ((in >> (4 * k + j)) & 1u) ? (unsigned)s_table[(x >> (8 * j)) & 0xFFu] : 0u;
+                cand |= (wt != 0u ? 1u : 0u) << (4 * k + j);
+                lane_sum += wt;
+            }
+        }
+        out[w] = cand;
+        sum = lane_sum;
+    }
+    if (total) {   // (uniform)
+        for (int sh = 32; sh > 0; sh >>= 1) sum += __shfl_xor(sum, sh);
+        if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = sum;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned long long t = 0;
+            for (int k = 0; k < TO_BLOCK / 64; ++k) t += s_wave[k];
+            if (t != 0) __hip_atomic_fetch_add(total, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
 }
 
 struct ViewVolumeArgs {
@@ -56,6 +114,10 @@ struct ViewVolumeArgs {
     unsigned long long* gains;
     const int* stop;
     unsigned long long* stats;
+    // the weighted instantiation only (behind every earlier field: the unweighted kernel's argument offsets stay)
+    const unsigned* cand;            // the candidate plane's words: stands where ~occ & ~free stood
+    const unsigned char* bytes;      // the evidence values in brick order, byte 32 w + b
+    const unsigned short* table;     // 256 weights, indexed by L + 128
 };
 
 struct VolWindow {
@@ -124,6 +186,9 @@ __device__ __forceinline__ bool vol_brick_reachable(const OccGeom& g, const Exac
     return los_tile_reachable(e, f, b);
 }
 
+// kWeighted: the candidates are the plane's and a survivor adds its weight from the table; else neither the plane, the bytes nor the
+// table is read
+template <bool kWeighted>
 __global__ void __launch_bounds__(TO_BLOCK) k_view_volume(ViewVolumeArgs a) {
     __shared__ unsigned short s_queue[kVolQueue];
     __shared__ unsigned s_mark[kVolSlab];
@@ -142,6 +207,13 @@ __global__ void __launch_bounds__(TO_BLOCK) k_view_volume(ViewVolumeArgs a) {
     const VolWindow win = vol_window(a, e);
     const long long nw = (long long)win.wx * win.wy * win.wz;
     long long revealed = 0, centres = 0, rays = 0, visits = 0;
+    const unsigned short* weight = nullptr;
+    if constexpr (kWeighted) {
+        __shared__ unsigned short s_table[256];
+        static_assert(TO_BLOCK == 256, "one table entry per lane");
+        s_table[threadIdx.x] = a.table[threadIdx.x];   // (visible behind the first barrier of the slab loop)
+        weight = s_table;
+    }
     for (long long first = (long long)blockIdx.x * kVolSlab; first < nw; first += (long long)gridDim.x * kVolSlab) {   // (uniform)
         if (threadIdx.x == 0) s_count = 0;
         s_mark[threadIdx.x] = 0u;
@@ -154,7 +226,9 @@ __global__ void __launch_bounds__(TO_BLOCK) k_view_volume(ViewVolumeArgs a) {
             int bx, by, bz;
             vol_brick(win, li, bx, by, bz);
             w = ((long long)bz * a.g.nby + by) * a.g.nbx + bx;
-            unsigned u = ~a.occ[w] & ~a.fre[w] & occ_brick_mask(a.g, bx, by, bz);
+            unsigned u;
+            if constexpr (kWeighted) u = a.cand[w];   // (pad bits 0: k_evid_weight_plane masked them)
+            else u = ~a.occ[w] & ~a.fre[w] & occ_brick_mask(a.g, bx, by, bz);
             if (a.claimed) u &= ~a.claimed[w];
             if (u != 0u && a.window && !vol_brick_reachable(a.g, e, a.f, bx, by, bz)) u = 0u;
             while (u != 0u) {
@@ -198,12 +272,15 @@ __global__ void __launch_bounds__(TO_BLOCK) k_view_volume(ViewVolumeArgs a) {
             float px, py, pz;
             vol_centre(a.g, x, y, z, px, py, pz);
             if (!occ_fixed(a.g, px, py, pz, tx, ty, tz)) continue;
+            [[maybe_unused]] unsigned wt = 1u;   // the byte is gathered before the walk: its latency hides under it, and only the weight stays live
+            if constexpr (kWeighted) wt = weight[a.bytes[32 * (((long long)bz * a.g.nby + by) * a.g.nbx + bx) + b] ^ 0x80u];
             unsigned v = 0;
             const int clear = los_walk(a.occ, a.g, cx, cy, cz, tx, ty, tz, 1, 0, v);
             ++rays;
             visits += v;
             if (clear) {
-                ++revealed;
+                if constexpr (kWeighted) revealed += wt;
+                else ++revealed;
                 if (a.mark) atomicOr(&s_mark[l], 1u << b);
             }
         }
@@ -283,13 +360,33 @@ extern "C" int tohip_occ_unknown(const void* occupied, const void* free_grid, vo
     return TOHIP_OK;
 }
 
-extern "C" int tohip_view_volume(const void* occupied, const void* free_grid, const void* claimed, void* mark, size_t grid_bytes,
-                                 const tohip_occ_geom* geom, const float* poses, const float* quats, int64_t n_views, const int32_t* view_index,
-                                 const tohip_camera* cam, float min_dist, float max_dist, int32_t window, int64_t* gains, const int32_t* stop,
-                                 uint64_t* stats, void* stream_) {
+namespace {
+
+// what the weighted instantiation reads beyond tohip_view_volume's arguments; all null: the unweighted kernel
+struct ViewWeights {
+    const void* evidence;
+    size_t evid_bytes;
+    const uint16_t* table;
+    const void* candidates;
+};
+
+// tohip_view_volume and tohip_view_information: one set of checks, one launch
+int view_volume_launch(const void* occupied, const void* free_grid, const void* claimed, void* mark, size_t grid_bytes, const tohip_occ_geom* geom,
+                       const ViewWeights* wt, const float* poses, const float* quats, int64_t n_views, const int32_t* view_index,
+                       const tohip_camera* cam, float min_dist, float max_dist, int32_t window, int64_t* gains, const int32_t* stop, uint64_t* stats,
+                       void* stream_) {
     OccGeom g;
     const int rc = occ_check(occupied, grid_bytes, geom, g);
     if (rc != TOHIP_OK) return rc;
+    if (wt) {
+        OccGeom ge;
+        const int re = evid_check(wt->evidence, wt->evid_bytes, geom, ge);
+        if (re != TOHIP_OK) return re;
+        if (!wt->table || ((uintptr_t)wt->table & 1u) != 0 || !wt->candidates) return TOHIP_EINVAL;
+        const void* others[4] = {occupied, free_grid, mark, wt->evidence};   // (free_grid is not read: it is here to be told apart)
+        for (const void* o : others)
+            if (wt->candidates == o) return TOHIP_EINVAL;
+    }
     if (!free_grid || free_grid == occupied || !poses || !quats || !cam || !gains || n_views < 1 || n_views > 65535) return TOHIP_EINVAL;
     if (mark && (mark == occupied || mark == free_grid)) return TOHIP_EINVAL;
     if (mark && mark == claimed && n_views > 1 && !view_index) return TOHIP_EINVAL;   // two views' lanes would race on one word
@@ -315,13 +412,57 @@ extern "C" int tohip_view_volume(const void* occupied, const void* free_grid, co
     a.gains = (unsigned long long*)gains;
     a.stop = stop;
     a.stats = (unsigned long long*)stats;
+    a.cand = wt ? occ_data(wt->candidates) : nullptr;
+    a.bytes = wt ? (const unsigned char*)wt->evidence + kEvidHdr : nullptr;
+    a.table = wt ? wt->table : nullptr;
     const hipError_t e = hipMemsetAsync(gains, 0, sizeof(int64_t) * (size_t)n_views, st);
     if (e != hipSuccess) return (int)e;
     const int64_t slabs = ((int64_t)occ_words(g.nx, g.ny, g.nz) + kVolSlab - 1) / kVolSlab;
     const dim3 grid_dim((unsigned)(slabs < kVolMaxSlabBlocks ? slabs : kVolMaxSlabBlocks), view_index ? 1u : (unsigned)n_views);
-    k_view_volume<<<grid_dim, TO_BLOCK, 0, st>>>(a);
+    if (wt)
+        k_view_volume<true><<<grid_dim, TO_BLOCK, 0, st>>>(a);
+    else
+        k_view_volume<false><<<grid_dim, TO_BLOCK, 0, st>>>(a);
     TO_HIP_CHECK_LAUNCH();
     return TOHIP_OK;
+}
+
+}  // namespace
+
+extern "C" int tohip_view_volume(const void* occupied, const void* free_grid, const void* claimed, void* mark, size_t grid_bytes,
+                                 const tohip_occ_geom* geom, const float* poses, const float* quats, int64_t n_views, const int32_t* view_index,
+                                 const tohip_camera* cam, float min_dist, float max_dist, int32_t window, int64_t* gains, const int32_t* stop,
+                                 uint64_t* stats, void* stream_) {
+    return view_volume_launch(occupied, free_grid, claimed, mark, grid_bytes, geom, nullptr, poses, quats, n_views, view_index, cam, min_dist,
+                              max_dist, window, gains, stop, stats, stream_);
+}
+
+extern "C" int tohip_evid_weight_plane(const void* evidence, size_t evid_bytes, const tohip_occ_geom* geom, const uint16_t* table, void* plane_out,
+                                       size_t grid_bytes, int64_t* total_out, void* stream_, uint32_t flags) {
+    if (flags != 0u) return TOHIP_EINVAL;   // (reserved)
+    OccGeom g;
+    int rc = evid_check(evidence, evid_bytes, geom, g);
+    if (rc != TOHIP_OK) return rc;
+    rc = occ_check(plane_out, grid_bytes, geom, g);
+    if (rc != TOHIP_OK) return rc;
+    if (!table || ((uintptr_t)table & 1u) != 0 || plane_out == evidence || ((uintptr_t)plane_out & 3u) != 0) return TOHIP_EINVAL;
+    const long long n_words = (long long)occ_words(g.nx, g.ny, g.nz);
+    k_evid_weight_plane<<<(unsigned)occ_list_blocks(g), TO_BLOCK, 0, (hipStream_t)stream_>>>(
+        reinterpret_cast<const uint4*>((const char*)evidence + kEvidHdr), table, (unsigned*)plane_out, occ_data(plane_out), g, n_words,
+        (unsigned long long*)total_out);
+    TO_HIP_CHECK_LAUNCH();
+    return TOHIP_OK;
+}
+
+extern "C" int tohip_view_information(const void* occupied, const void* free_grid, const void* claimed, void* mark, size_t grid_bytes,
+                                      const tohip_occ_geom* geom, const void* evidence, size_t evid_bytes, const uint16_t* table,
+                                      const void* candidates, const float* poses, const float* quats, int64_t n_views, const int32_t* view_index,
+                                      const tohip_camera* cam, float min_dist, float max_dist, int32_t window, int64_t* gains, const int32_t* stop,
+                                      uint64_t* stats, void* stream_, uint32_t flags) {
+    if (flags != 0u) return TOHIP_EINVAL;   // (reserved)
+    const ViewWeights wt = {evidence, evid_bytes, table, candidates};
+    return view_volume_launch(occupied, free_grid, claimed, mark, grid_bytes, geom, &wt, poses, quats, n_views, view_index, cam, min_dist, max_dist,
+                              window, gains, stop, stats, stream_);
 }
 
 extern "C" int tohip_view_volume_pick(const int64_t* gains, int32_t* taken, int64_t n_views, int64_t min_gain, int32_t round, int32_t* order,

@@ -1261,14 +1261,28 @@ def view_volume_select(space, poses, quats, cam, min_dist, max_dist, k, min_gain
     integer in [0, 2^31): the pick becomes tohip_view_volume_pick_travel — only candidates with cost >= 0 and gain >= min_gain can win,
     and gain 2^20 - travel_m cost decides."""
     M, k, min_gain = check_view_volume(space, poses, quats, k, min_gain, claimed)
-    if travel_cost is not None:
-        if not torch.is_tensor(travel_cost) or travel_cost.dtype != torch.int64 or tuple(travel_cost.shape) != (M,):
-            raise ValueError(f"travel_cost must be an ({M},) int64 tensor, got "
-                             f"{(tuple(travel_cost.shape), travel_cost.dtype) if torch.is_tensor(travel_cost) else type(travel_cost).__name__}")
-        if not _is_int(travel_m) or not 0 <= travel_m <= TRAVEL_MAX_LIMIT:
-            raise ValueError(f"travel_m must be an integer in [0, 2^31), got {travel_m!r}")
-        travel_cost = travel_cost.to(space.device).contiguous()
+    travel_cost = _check_travel_cost(travel_cost, travel_m, M, space.device)
     p, q = _view_rows(space, poses, quats)
+
+    def score(view_index, claimed, mark, gains, stop):
+        _view_volume_call(space, p, q, M, view_index, cam, min_dist, max_dist, claimed, mark, window, gains, stop, None)
+    return _view_select(space, score, M, k, min_gain, claimed, travel_cost, travel_m)
+
+
+def _check_travel_cost(travel_cost, travel_m, M, device):
+    if travel_cost is None:
+        return None
+    if not torch.is_tensor(travel_cost) or travel_cost.dtype != torch.int64 or tuple(travel_cost.shape) != (M,):
+        raise ValueError(f"travel_cost must be an ({M},) int64 tensor, got "
+                         f"{(tuple(travel_cost.shape), travel_cost.dtype) if torch.is_tensor(travel_cost) else type(travel_cost).__name__}")
+    if not _is_int(travel_m) or not 0 <= travel_m <= TRAVEL_MAX_LIMIT:
+        raise ValueError(f"travel_m must be an integer in [0, 2^31), got {travel_m!r}")
+    return travel_cost.to(device).contiguous()
+
+
+def _view_select(space, score, M, k, min_gain, claimed, travel_cost, travel_m):
+    """The greedy rounds of view_volume_select and view_information_select: score(view_index, claimed, mark, gains, stop) is the
+    scoring launch over the M candidates.  -> (order, picked, revealed)."""
     dev = space.device
     revealed = space.free.empty_like()
     if claimed is not None:
@@ -1280,18 +1294,148 @@ def view_volume_select(space, poses, quats, cam, min_dist, max_dist, k, min_gain
     order = torch.full((k,), -1, dtype=torch.int32, device=dev)
     picked = torch.zeros(k, dtype=torch.int64, device=dev)
     for j in range(k):
-        _view_volume_call(space, p, q, M, None, cam, min_dist, max_dist, revealed, None, window, scores, stop, None)
+        score(None, revealed, None, scores, stop)
         if travel_cost is None:
             _map_call(dev, "tohip_view_volume_pick", ptr(scores), ptr(taken), M, min_gain, j, ptr(order), ptr(picked), ptr(stop))
         else:
             _map_call(dev, "tohip_view_volume_pick_travel", ptr(scores), ptr(travel_cost), int(travel_m), ptr(taken), M, min_gain, j, ptr(order),
                       ptr(picked), ptr(stop))
         # the mark step: the winner's number stays on the device, and one view may claim what it counts
-        _view_volume_call(space, p, q, M, order[j:j + 1], cam, min_dist, max_dist, revealed, revealed, window, scratch, stop, None)
+        score(order[j:j + 1], revealed, revealed, scratch, stop)
     return order, picked, revealed
 
 
-SCAN_MAX_SIDE = 8192    # pixels per side of a depth scan's image
+INFORMATION_MAX_WEIGHT = 65535   # a weight table's entries are unsigned 16-bit
+
+
+def information_table(params, unit=0.05, unknown_bits=1.0, scale=4096):
+    """The default weight table of an evidence map with the settings `params` = (hit, miss, lmin, lmax, threshold) -> (256,) uint16
+    host tensor, indexed by L + 128: the binary entropy, in bits, that observation can still remove from a voxel at value L —
+    H(sigma(unit L)) - H(sigma(unit c)), c the clamp its state moves towards (lmin where L <= threshold, lmax above), never below 0
+    — times scale, rounded; entry 0 (never observed) = round(scale unknown_bits); entries outside [lmin, lmax] are 0.  So a voxel
+    at a clamp weighs 0 and a finished map has information 0.  unit: the log-odds one step of L stands for.  Computed in f64."""
+    _, _, lmin, lmax, threshold = params
+    for name, v in (("unit", unit), ("unknown_bits", unknown_bits), ("scale", scale)):
+        if not _is_real(v) or not np.isfinite(float(v)) or float(v) < 0.0 or (name == "unit" and float(v) == 0.0):
+            raise ValueError(f"information_table: {name} must be a finite number {'> 0' if name == 'unit' else '>= 0'}, got {v!r}")
+
+    def H(L):
+        p = 1.0 / (1.0 + np.exp(-float(unit) * np.asarray(L, dtype=np.float64)))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            h = -(p * np.log2(p) + (1.0 - p) * np.log2(1.0 - p))
+        return np.where((p <= 0.0) | (p >= 1.0), 0.0, h)
+    L = np.arange(int(lmin), int(lmax) + 1)
+    c = np.where(L <= int(threshold), int(lmin), int(lmax))
+    W = np.zeros(256, dtype=np.float64)
+    W[L + 128] = np.round(float(scale) * np.maximum(0.0, H(L) - H(c)))
+    W[0] = np.round(float(scale) * float(unknown_bits))
+    if not W.max() <= INFORMATION_MAX_WEIGHT:
+        raise ValueError(f"information_table: the weights do not fit 16 bits (the largest is {W.max():.0f}): scale = {scale!r}, "
+                         f"unknown_bits = {unknown_bits!r}")
+    return torch.from_numpy(W.astype(np.uint16))
+
+
+def check_information_table(table, device=None):
+    """A weight table, by name: 256 integers in [0, 65535] — a tensor, an array or a sequence of shape (256,), never floating point
+    -> the table as 256 16-bit words on `device` (None: on the host).  A (256,) uint16 or int16 tensor already on `device` is used
+    as it is: the bits are the weights, and nothing is read back.  ValueError otherwise."""
+    if torch.is_tensor(table) and table.dtype in (torch.uint16, torch.int16):
+        if tuple(table.shape) != (256,):
+            raise ValueError(f"table must have shape (256,), got {tuple(table.shape)}")
+        t = table.detach().contiguous().view(torch.int16)
+        return t if device is None or t.device == torch.device(device) else t.to(device)
+    if torch.is_tensor(table):
+        if table.is_floating_point() or table.is_complex() or table.dtype == torch.bool:
+            raise ValueError(f"table must hold integers, got {table.dtype}")
+        a = table.detach().cpu().numpy()
+    else:
+        try:
+            a = np.asarray(table)
+        except Exception:
+            a = None
+        if a is None or a.dtype.kind not in "iu":
+            raise ValueError(f"table must be 256 integers (a tensor or an array of an integer dtype), got {type(table).__name__}"
+                             f"{'' if a is None else ' of ' + str(a.dtype)}")
+    if a.shape != (256,):
+        raise ValueError(f"table must have shape (256,), got {tuple(a.shape)}")
+    if int(a.min()) < 0 or int(a.max()) > INFORMATION_MAX_WEIGHT:
+        raise ValueError(f"table entries must lie in [0, {INFORMATION_MAX_WEIGHT}], got [{int(a.min())}, {int(a.max())}]")
+    t = torch.from_numpy(a.astype(np.uint16).view(np.int16))
+    return t if device is None else t.to(device)
+
+
+def check_view_information(map, poses, quats, table=None, k=None, min_gain=1, claimed=None, mark=None, travel=False):
+    """The arguments of view_information / view_information_select, by name: map an ops.EvidenceMap (a SpaceMap has no evidence
+    bytes); table None (the map's default, information_table) or check_information_table's; poses, quats, k, claimed and mark as
+    check_view_volume takes them; min_gain an integer >= 1, in table units; travel=True: the map must be small enough for the travel
+    pick's gain 2^20 - m cost, 65535 x voxels x 2^20 < 2^63 -> (M, k clipped to M or None, min_gain); ValueError otherwise.
+    Needs no GPU."""
+    if not isinstance(map, EvidenceMap):
+        raise ValueError(f"map must be an ops.EvidenceMap (a SpaceMap has no evidence bytes to weigh), got {type(map).__name__}")
+    if table is not None:
+        check_information_table(table)
+    if not _is_int(min_gain) or min_gain < 1:
+        raise ValueError(f"min_gain must be an integer >= 1 (in the table's units), got {min_gain!r}")
+    n_voxels = int(map.dims[0]) * int(map.dims[1]) * int(map.dims[2])
+    if travel and INFORMATION_MAX_WEIGHT * n_voxels * (1 << 20) >= 1 << 63:
+        raise ValueError(f"travel: a map of {n_voxels} voxels is too large for a selection with travel= (the pick forms gain x 2^20, and "
+                         f"{INFORMATION_MAX_WEIGHT} x {n_voxels} x 2^20 reaches 2^63); select on a window of the map (reframed) or without travel=")
+    return check_view_volume(map.space, poses, quats, k, min_gain, claimed, mark)
+
+
+def _information_plane(map, table, total=None):
+    """(the table on the device, the candidate plane: a new OccupancyGrid) of an EvidenceMap under `table`; one launch.  total: a
+    zero-filled int64 device tensor that receives the map's remaining information, or None."""
+    t = check_information_table(information_table(map.params) if table is None else table, map.device)
+    plane = map.occupied.empty_like()
+    _map_call0(map.device, "tohip_evid_weight_plane", *map._sizes(), ptr(t), ptr(plane.buf), plane.buf.numel(), ptr(total))
+    return t, plane
+
+
+def _view_information_call(map, t, plane, p, q, n, view_index, cam, min_dist, max_dist, claimed, mark, window, gains, stop, stats):
+    _map_call0(map.device, "tohip_view_information", ptr(map.occupied.buf), ptr(map.free.buf), ptr(claimed.buf if claimed is not None else None),
+               ptr(mark.buf if mark is not None else None), map.occupied.buf.numel(), ctypes.byref(map.geom), ptr(map.buf), map.buf.numel(),
+               ptr(t), ptr(plane.buf), ptr(p), ptr(q), n, ptr(view_index), cam.ref(), float(min_dist), float(max_dist), int(bool(window)),
+               ptr(gains), ptr(stop), ptr(stats))
+
+
+def view_information(map, poses, quats, cam, min_dist, max_dist, table=None, claimed=None, mark=None, window=True, stats=None):
+    """The information each view would gain (tohip_view_information, DESIGN.md 10 "Information gain"): (M,) int64 on the device,
+    entry w = the sum of table[L + 128] over the voxels of the EvidenceMap `map` with a positive weight — whatever their state, and
+    not set in `claimed` — whose centre cull_waypoints keeps for pose w with this camera and these limits and which
+    line_of_sight(map.occupied, poses[w], centre, skip=(1, 0)) sees: the target voxel is not tested, so a weakly occupied surface
+    voxel counts.  table: None (information_table of the map's settings) or 256 integers in [0, 65535].  mark, window, stats: as
+    view_volume takes them.  The candidate plane is built once per call (one launch); then one launch per 65 535 views, nothing
+    read back."""
+    M, _, _ = check_view_information(map, poses, quats, table, claimed=claimed, mark=mark)
+    p, q = _view_rows(map.space, poses, quats)
+    t, plane = _information_plane(map, table)
+    gains = torch.empty(M, dtype=torch.int64, device=map.device)
+    for w0 in range(0, M, VIEW_VOLUME_MAX_VIEWS):
+        w1 = min(M, w0 + VIEW_VOLUME_MAX_VIEWS)
+        _view_information_call(map, t, plane, p[w0:w1], q[w0:w1], w1 - w0, None, cam, min_dist, max_dist, claimed, mark, window, gains[w0:w1],
+                               None, stats)
+    return gains
+
+
+def view_information_select(map, poses, quats, cam, min_dist, max_dist, k, table=None, min_gain=1, claimed=None, window=True,
+                            travel_cost=None, travel_m=0):
+    """Greedy selection by information gain, on the device: view_volume_select's rounds with view_information's gains — the
+    candidate plane once, then 3 k launches, nothing read back; at most 65 535 candidates.  min_gain is in the table's units.
+    -> (order (k,) int32, -1 from the round that stopped; gains (k,) int64, the marginal gains; revealed: a new OccupancyGrid, the
+    caller's `claimed` (not modified) plus the voxels the chosen views inform), all on the device.  travel_cost, travel_m: as
+    view_volume_select takes them; refused by name where 65535 x voxels x 2^20 could reach 2^63."""
+    M, k, min_gain = check_view_information(map, poses, quats, table, k, min_gain, claimed, travel=travel_cost is not None)
+    travel_cost = _check_travel_cost(travel_cost, travel_m, M, map.device)
+    p, q = _view_rows(map.space, poses, quats)
+    t, plane = _information_plane(map, table)
+
+    def score(view_index, claimed, mark, gains, stop):
+        _view_information_call(map, t, plane, p, q, M, view_index, cam, min_dist, max_dist, claimed, mark, window, gains, stop, None)
+    return _view_select(map.space, score, M, k, min_gain, claimed, travel_cost, travel_m)
+
+
+SCAN_MAX_SIDE = 8192   # pixels per side of a depth scan's image
 SCAN_MAX_VIEWS = 65535  # views per launch (the grid's second dimension)
 
 
@@ -2292,6 +2436,20 @@ class EvidenceMap:
         state = torch.empty(pos.shape[0], dtype=torch.uint8, device=self.device)
         _map_call(self.device, "tohip_evid_positions", *self._sizes(), self.threshold, ptr(pos), pos.shape[0], ptr(values), ptr(state))
         return values, state
+
+    def uncertain(self, table=None):
+        """The candidates of this map under a weight table (None: information_table of the map's settings) — the voxels inside dims
+        whose weight table[L + 128] is positive, whatever their state — as a new OccupancyGrid of this geometry (pad bits 0):
+        uncertain().export() lists them.  One launch (tohip_evid_weight_plane), nothing read back."""
+        return _information_plane(self, table)[1]
+
+    def information(self, table=None):
+        """What is left to learn in this map -> a 0-d int64 device tensor: the sum of table[L + 128] over the voxels inside dims, in
+        the table's units (the default table: 1/4096 bit); 0 for a map whose every voxel sits at a clamp.  One launch, nothing read
+        back: int(m.information()) is the synchronisation."""
+        total = torch.zeros((), dtype=torch.int64, device=self.device)
+        _information_plane(self, table, total)
+        return total
 
     def _bricks(self):
         nx, ny, nz = self.dims

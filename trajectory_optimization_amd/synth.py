@@ -818,6 +818,23 @@ def voxel_centres(dims, origin, resolution):
     return np.stack(np.meshgrid(*ax, indexing="ij"), axis=-1).astype(f32)
 
 
+def _seen_candidates(cand, t, origin, resolution, occ):
+    """The voxels of the mask cand (nx,ny,nz) bool that the walk from t sees -> (nx,ny,nz) bool: los_fixed from the camera position t
+    to the voxel's centre with skip (1, 0) finds no occupied voxel.  A position t out of range, or a centre out of range, sees nothing."""
+    seen = np.zeros(occ.shape, dtype=bool)
+    qa, oka = occ_fixed(np.asarray(t, dtype=np.float32).reshape(1, 3), origin, resolution)
+    ijk = np.argwhere(cand)
+    if not oka[0] or not len(ijk):
+        return seen
+    c = voxel_centres(occ.shape, origin, resolution)[ijk[:, 0], ijk[:, 1], ijk[:, 2]]
+    qb, okb = occ_fixed(c, origin, resolution)
+    clear = np.zeros(len(ijk), dtype=bool)
+    clear[okb] = ~los_fixed(np.broadcast_to(qa, qb[okb].shape), qb[okb], occ, (1, 0))
+    ijk = ijk[clear]
+    seen[ijk[:, 0], ijk[:, 1], ijk[:, 2]] = True
+    return seen
+
+
 def view_volume_ref(kept, t, origin, resolution, occ, free, claimed=None):
     """The voxels one view reveals -> (gain, revealed (nx,ny,nz) bool).  kept: (nx,ny,nz) bool, the cull's verdict on every voxel's
     centre — an input, so the f32 cull is not re-derived here.  A voxel is revealed iff its state is 0, it is not set in claimed,
@@ -828,18 +845,31 @@ def view_volume_ref(kept, t, origin, resolution, occ, free, claimed=None):
     cand = unknown_ref(occ, free) & np.asarray(kept, dtype=bool)
     if claimed is not None:
         cand &= ~np.asarray(claimed, dtype=bool)
-    revealed = np.zeros(occ.shape, dtype=bool)
-    qa, oka = occ_fixed(np.asarray(t, dtype=np.float32).reshape(1, 3), origin, resolution)
-    ijk = np.argwhere(cand)
-    if not oka[0] or not len(ijk):
-        return 0, revealed
-    c = voxel_centres(occ.shape, origin, resolution)[ijk[:, 0], ijk[:, 1], ijk[:, 2]]
-    qb, okb = occ_fixed(c, origin, resolution)
-    clear = np.zeros(len(ijk), dtype=bool)
-    clear[okb] = ~los_fixed(np.broadcast_to(qa, qb[okb].shape), qb[okb], occ, (1, 0))
-    ijk = ijk[clear]
-    revealed[ijk[:, 0], ijk[:, 1], ijk[:, 2]] = True
-    return int(clear.sum()), revealed
+    revealed = _seen_candidates(cand, t, origin, resolution, occ)
+    return int(revealed.sum()), revealed
+
+
+def information_weights_ref(values_int8, table):
+    """The weight of every voxel -> (nx,ny,nz) int64: table[L + 128], the table (256,) read as unsigned 16-bit."""
+    L = np.asarray(values_int8).astype(np.int64)
+    W = np.asarray(table).astype(np.int64).reshape(256)
+    assert L.min() >= -128 and L.max() <= 127 and W.min() >= 0 and W.max() <= 65535
+    return W[L + 128]
+
+
+def view_information_ref(kept, t, origin, resolution, values_int8, occ, table, claimed=None):
+    """The information one view gains -> (gain, informed (nx,ny,nz) bool).  values_int8: the map's evidence values (nx,ny,nz), -128
+    never observed; table: (256,) weights indexed by L + 128; occ: the occupied plane the walk tests (the map's: L > threshold).  A
+    voxel is a candidate iff its weight is positive, whatever its state; it is informed iff it is not set in claimed, kept holds it
+    and the walk of view_volume_ref sees it — the target voxel is not tested, so an occupied candidate can be informed.  gain = the sum
+    of the informed voxels' weights, int64."""
+    occ = np.asarray(occ, dtype=bool)
+    weights = information_weights_ref(values_int8, table)
+    cand = (weights > 0) & np.asarray(kept, dtype=bool)
+    if claimed is not None:
+        cand &= ~np.asarray(claimed, dtype=bool)
+    informed = _seen_candidates(cand, t, origin, resolution, occ)
+    return int(weights[informed].sum()), informed
 
 
 def volume_select_ref(revealed_sets, k, min_gain=1, claimed=None):
@@ -852,6 +882,25 @@ def volume_select_ref(revealed_sets, k, min_gain=1, claimed=None):
     taken, order, gains = np.zeros(len(sets), dtype=bool), [], []
     for _ in range(min(int(k), len(sets))):
         g = np.array([-1 if taken[i] else int((sets[i] & ~mask).sum()) for i in range(len(sets))], dtype=np.int64)
+        best = int(np.argmax(g))   # (the first of equal gains)
+        if g[best] < int(min_gain):
+            break
+        taken[best] = True
+        order.append(best)
+        gains.append(int(g[best]))
+        mask |= sets[best]
+    return order, gains, mask
+
+
+def information_select_ref(informed_sets, weights, k, min_gain=1, claimed=None):
+    """volume_select_ref with a weight per voxel: the greedy selection over per-view informed masks (M, nx,ny,nz) bool, each computed
+    WITHOUT a claimed plane, and weights (nx,ny,nz) int64 -> (order list, gains list, claimed mask).  A view's gain is the sum of the
+    weights of its voxels outside the mask; the lowest index wins a tie; below min_gain the selection stops."""
+    sets, weights = np.asarray(informed_sets, dtype=bool), np.asarray(weights, dtype=np.int64)
+    mask = np.zeros(sets.shape[1:], dtype=bool) if claimed is None else np.array(claimed, dtype=bool)
+    taken, order, gains = np.zeros(len(sets), dtype=bool), [], []
+    for _ in range(min(int(k), len(sets))):
+        g = np.array([-1 if taken[i] else int(weights[sets[i] & ~mask].sum()) for i in range(len(sets))], dtype=np.int64)
         best = int(np.argmax(g))   # (the first of equal gains)
         if g[best] < int(min_gain):
             break

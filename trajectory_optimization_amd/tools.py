@@ -1047,30 +1047,113 @@ def select_views_volume(space_or_evidence_map, cand_poses, cand_quats, k, min_ga
     space, cam, mn, mx = _volume_setup("select_views_volume", space_or_evidence_map, camera)
     cost, m = None, 0
     if travel is not None:
-        if not isinstance(travel, ops.TravelField):
-            raise ValueError(f"select_views_volume: travel must be an ops.TravelField or None, got {type(travel).__name__}")
-        w = float(travel_weight) if isinstance(travel_weight, (int, float)) and not isinstance(travel_weight, bool) else float("nan")
-        if not (w >= 0.0) or w == float("inf"):
-            raise ValueError(f"select_views_volume: travel_weight must be a finite number >= 0, got {travel_weight!r}")
-        m = int(round(w * float(travel.resolution) * (1 << 20) / 64.0))
-        if m >= 1 << 31:
-            raise ValueError(f"select_views_volume: travel_weight {travel_weight!r} is too large at this resolution (its fixed-point form "
-                             f"{m} must stay below 2^31)")
+        m = _travel_weight_fixed("select_views_volume", travel, travel_weight)
         ops.check_view_volume(space, cand_poses, cand_quats, k, min_gain, claimed)
         cost = travel.cost(cand_poses.detach().to(device=space.device, dtype=torch.float32).contiguous())
     elif travel_weight != 0.0:
         raise ValueError("select_views_volume: travel_weight needs travel= (an ops.TravelField)")
     order, gains, revealed = ops.view_volume_select(space, cand_poses, cand_quats, cam, mn, mx, k, min_gain, claimed, travel_cost=cost,
                                                     travel_m=m)
-    h = torch.cat([order.long(), gains]).cpu()   # the one synchronisation
+    return VolumeSelection(**_selection_fields(space.device, cand_poses, cand_quats, order, gains, revealed, travel))
+
+
+def _travel_weight_fixed(what, travel, travel_weight):
+    """travel= and travel_weight= of a selection -> the weight's fixed-point form m (gain 2^20 - m cost decides)."""
+    if not isinstance(travel, ops.TravelField):
+        raise ValueError(f"{what}: travel must be an ops.TravelField or None, got {type(travel).__name__}")
+    w = float(travel_weight) if isinstance(travel_weight, (int, float)) and not isinstance(travel_weight, bool) else float("nan")
+    if not (w >= 0.0) or w == float("inf"):
+        raise ValueError(f"{what}: travel_weight must be a finite number >= 0, got {travel_weight!r}")
+    m = int(round(w * float(travel.resolution) * (1 << 20) / 64.0))
+    if m >= 1 << 31:
+        raise ValueError(f"{what}: travel_weight {travel_weight!r} is too large at this resolution (its fixed-point form "
+                         f"{m} must stay below 2^31)")
+    return m
+
+
+def _selection_fields(device, cand_poses, cand_quats, order, gains, revealed, travel):
+    """A device selection (order, gains, revealed) -> the fields VolumeSelection and InformationSelection share; the one
+    synchronisation."""
+    h = torch.cat([order.long(), gains]).cpu()
     kk = order.shape[0]
     n = int((h[:kk] >= 0).sum())
     sel, g = h[:n].clone(), h[kk:kk + n].clone()
-    idx = sel.to(space.device)
-    ps = cand_poses.detach().to(device=space.device, dtype=torch.float32)
-    qs = cand_quats.detach().to(device=space.device, dtype=torch.float32)
-    return VolumeSelection(order=sel, gains=g, poses=ps[idx], quats=qs[idx], revealed=revealed, total=int(g.sum()),
-                           travel=travel.distance(ps[idx].contiguous()) if travel is not None else None)
+    idx = sel.to(device)
+    ps = cand_poses.detach().to(device=device, dtype=torch.float32)
+    qs = cand_quats.detach().to(device=device, dtype=torch.float32)
+    return dict(order=sel, gains=g, poses=ps[idx], quats=qs[idx], revealed=revealed, total=int(g.sum()),
+                travel=travel.distance(ps[idx].contiguous()) if travel is not None else None)
+
+
+def information_table(map, unit=0.05, unknown_bits=1.0, scale=4096):
+    """The default weight table of an ops.EvidenceMap -> (256,) uint16 on the host, indexed by the evidence byte read as unsigned,
+    L + 128: the entropy that observation can still remove from a voxel, round(scale max(0, H(sigma(unit L)) - H(sigma(unit c))))
+    with H the binary entropy in bits and c the clamp the voxel's state moves towards (lmin where L <= threshold, lmax above);
+    entry 0, a voxel never observed, weighs round(scale unknown_bits).  A voxel at a clamp weighs 0: a finished map has information
+    0.  unit = 0.05 is the log-odds per step of the map's default hit = 17 / miss = 8 (0.85 / 0.4).  Any (256,) table of the caller's
+    own goes wherever table= goes — "only weakly occupied voxels" is a table that is 0 up to the threshold."""
+    if not isinstance(map, ops.EvidenceMap):
+        raise ValueError(f"information_table: the map must be an ops.EvidenceMap, got {type(map).__name__}")
+    return ops.information_table(map.params, unit, unknown_bits, scale)
+
+
+class InformationSelection(_Result):
+    """What select_views_information returns: VolumeSelection's fields with gains in the table's units — order (n_selected,) int64
+    and gains (n_selected,) int64 on the host (gain j = the weights view order[j] added when it was chosen), poses / quats (the
+    chosen rows in selection order, on the device), revealed (an ops.OccupancyGrid: the caller's `claimed` plus every voxel the chosen
+    views inform — the next robot's `claimed`), total = sum(gains), travel ((n_selected,) f32 metres, or None) — and table, the
+    (256,) weights the selection used, on the host."""
+    __slots__ = ("order", "gains", "poses", "quats", "revealed", "total", "travel", "table")
+
+    @property
+    def n_selected(self):
+        return int(self.order.shape[0])
+
+
+def _information_setup(what, evidence_map, camera, table):
+    """view_information's and select_views_information's map, camera keywords and table -> (ops.Camera, min_dist, max_dist, table)."""
+    if not isinstance(evidence_map, ops.EvidenceMap):
+        raise ValueError(f"{what}: the map must be an ops.EvidenceMap (a SpaceMap has no evidence bytes to weigh), got "
+                         f"{type(evidence_map).__name__}")
+    _, cam, mn, mx = _volume_setup(what, evidence_map, camera)
+    return cam, mn, mx, information_table(evidence_map) if table is None else table
+
+
+def view_information(evidence_map, poses, quats, table=None, claimed=None, **camera):
+    """How much is left to learn about what a camera would see from here?  (M,) int64 on the device: per view poses[w] (M,3) /
+    quats[w] (M,4) wxyz the sum of the weights table[L + 128] of the voxels of the ops.EvidenceMap — of any state, with a positive
+    weight and not set in `claimed` — whose centre lies inside the camera frustum and the depth limits and is in line of sight of
+    the camera through the occupied voxels ("Information gain").  table: None (information_table(evidence_map)) or
+    256 integers in [0, 65535].  A voxel seen once keeps most of its weight, a weakly occupied surface attracts a view, and a
+    voxel at a clamp weighs nothing.  Unknown voxels do not block.  Keywords: the camera, as view_volume takes it.  The map is read
+    when the call is made: an integrate between two calls is seen.  Exact integers: the same gains in every run."""
+    cam, mn, mx, table = _information_setup("view_information", evidence_map, camera, table)
+    return ops.view_information(evidence_map, poses, quats, cam, mn, mx, table=table, claimed=claimed)
+
+
+def select_views_information(evidence_map, cand_poses, cand_quats, k, min_gain=1, table=None, claimed=None, travel=None, travel_weight=0.0,
+                             **camera):
+    """select_views_volume with view_information's objective ("Information gain"): out of the M <= 65 535 candidates
+    choose up to k that together inform the largest weight of the ops.EvidenceMap's voxels.  Round after round every candidate
+    not yet taken is scored against the voxels claimed so far, the largest gain wins (ties go to the lowest index), and the
+    winner's voxels are claimed; selection stops after k views, when none is left, or when the best gain is below min_gain (an
+    integer >= 1 in the table's units).  A weighted coverage: monotone submodular, so greedy is within (1 - 1/e) of the best set.
+    The candidate plane is rebuilt on every call (one launch, then 3 k), one host synchronisation at the end.  travel, travel_weight:
+    as select_views_volume takes them, travel_weight in table units per metre; refused by name on a map so large that
+    65535 x voxels x 2^20 could reach 2^63.  -> InformationSelection."""
+    what = "select_views_information"
+    cam, mn, mx, table = _information_setup(what, evidence_map, camera, table)
+    cost, m = None, 0
+    if travel is not None:
+        m = _travel_weight_fixed(what, travel, travel_weight)
+        ops.check_view_information(evidence_map, cand_poses, cand_quats, table, k, min_gain, claimed, travel=True)
+        cost = travel.cost(cand_poses.detach().to(device=evidence_map.device, dtype=torch.float32).contiguous())
+    elif travel_weight != 0.0:
+        raise ValueError(f"{what}: travel_weight needs travel= (an ops.TravelField)")
+    order, gains, revealed = ops.view_information_select(evidence_map, cand_poses, cand_quats, cam, mn, mx, k, table, min_gain, claimed,
+                                                         travel_cost=cost, travel_m=m)
+    host = ops.check_information_table(table).cpu().view(torch.uint16)
+    return InformationSelection(table=host, **_selection_fields(evidence_map.device, cand_poses, cand_quats, order, gains, revealed, travel))
 
 
 class RayHits(_Result):
