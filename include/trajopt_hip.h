@@ -41,7 +41,10 @@
 extern "C" {
 #endif
 
-/* (still 15) + tohip_evid_weight_plane / tohip_view_information (information gain: a view scored by a weight per voxel that depends on
+/* (still 15) + tohip_mcl_seed_gaussian / tohip_mcl_seed_positions / tohip_mcl_predict / tohip_mcl_poses / tohip_mcl_weigh /
+ * tohip_mcl_weights / tohip_mcl_resample_systematic and the TOHIP_MCL_* constants (a particle filter on the evidence map: pose hypotheses seeded,
+ * moved, weighed by scan matching's score and resampled on the device, in integers): new symbols only.
+ * (still 15) + tohip_evid_weight_plane / tohip_view_information (information gain: a view scored by a weight per voxel that depends on
  * its evidence byte, summed over the voxels it sees, and the map's remaining information): new symbols only.
  * (still 15) + tohip_travel_weights_bytes / tohip_travel_weights_build / tohip_travel_build_weighted / tohip_travel_paths_weighted (weighted
  * travel fields: a per-voxel cost factor so routes keep off walls and out of the unknown): new symbols only.
@@ -1739,6 +1742,68 @@ int tohip_scan_correlate(const void *table, size_t table_bytes, const tohip_occ_
                          int64_t n, const float *poses, int64_t k, int32_t wx, int32_t wy, int32_t wz, int32_t *scores,
                          size_t scores_bytes, int32_t *used, void *stream, uint32_t flags);
 int tohip_scan_best(const int32_t *scores, int64_t k, int32_t wx, int32_t wy, int32_t wz, int32_t *best, void *stream, uint32_t flags);
+
+/* ---- particle filter (particle_kernels.hip, DESIGN.md §10, "Particle filter") -------------------------
+ * Monte Carlo localisation on the evidence map: n pose hypotheses (1 <= n <= 2^20) kept on the device from scan to scan.
+ * state (n, 4) int32, 16-byte aligned: X, Y, Z in 1/256 voxel from the map's origin, clamped to |.| <= 2^24 - 1, and a heading h in
+ *   [0, 16384), 1/16384 turn about world z.  log_weight (n) int64: Q16 log2, <= 0, maximum 0 after tohip_mcl_weights, floor -2^40.
+ * tables: TOHIP_MCL_TABLE_WORDS int32 the caller builds once (f64, rounded once): word 2 h, 2 h + 1 = round(32768 cos), round(32768
+ *   sin) of 2 pi h / 16384; word TOHIP_MCL_GAUSS_WORD + i = round(4096 Phi^-1((i + 0.5) / 1025)), i = 0 .. 1024; word TOHIP_MCL_EXP2_WORD
+ *   + j = round(2^20 2^(-j / 256)), j = 0 .. 255.
+ * Random numbers: Philox4x32-10, key (seed_lo, seed_hi), counter (particle index, 0, step, stream): stream 0 tohip_mcl_seed_gaussian, 1
+ *   tohip_mcl_predict, 2 the resample offset (particle 0), 3 tohip_mcl_seed_positions; the four words serve x, y, z and heading.
+ *   noise(u, sigma_q8), sigma_q8 = round(256 sigma) in [0, 2^24]: i = u >> 22, f = (u >> 6) & 0xFFFF, g = (GAUSS[i] (65536 - f) +
+ *   GAUSS[i + 1] f) >> 16, noise = (g sigma_q8 + 2^19) >> 20 (arithmetic shifts).
+ * tohip_mcl_seed_gaussian: state = clamp(prior_host[a] + noise), heading (prior_host[3] + noise) mod 16384; log_weight = 0.  prior_host
+ *   and sigma_q8_host: 4 int32 on the host, |prior| <= 2^24 - 1 (the heading: |.| <= 2^30).
+ * tohip_mcl_seed_positions: particle i takes row (word0 mod m) of positions (m, 3) f32 world coordinates, 1 <= m < 2^31: the voxel it
+ *   lies in by the coordinate rule of tohip_occ_insert (a row out of range: fixed point 0 on that axis), at 1/256 offsets word1 >> 24,
+ *   (word1 >> 16) & 255, word2 >> 24 with jitter = 1 and at the centre (128) with jitter = 0; heading word3 >> 18; log_weight = 0.
+ * tohip_mcl_predict: delta_host 4 int32 (a body-frame motion, state units, |.| <= 2^24 - 1), n_a = delta_a + noise; (c, s) = TRIG[h];
+ *   X += (c n_x - s n_y + 2^14) >> 15, Y += (s n_x + c n_y + 2^14) >> 15 (64-bit products), Z += n_z, clamped; h = (h + n_h) mod 16384.
+ * tohip_mcl_poses: poses (n, 12) f32, 16-byte aligned, scan matching's pose of each particle: R = Rz(h) A with c32 = f32(c) 2^-15 and A
+ *   the 9 f32 of attitude_host (row-major; NULL: the identity): row 0 fl(fl(c32 A_0j) - fl(s32 A_1j)), row 1 fl(fl(s32 A_0j) + fl(c32
+ *   A_1j)), row 2 A_2j; t_a = fl(fl(f32(X_a) f32(resolution / 256)) + origin_a).
+ * tohip_mcl_weigh: for each particle, scan matching's score, used and known (tohip_scan_score at zero shift, under tohip_mcl_poses'
+ *   pose) of the scan `points` (p, 3) f32, 1 <= p <= 2^22, read from the evidence bytes -> score, used, known, each (n) int32; zeroed
+ *   here on the stream where the points are split over grid rows.
+ * tohip_mcl_weights: log_weight += score beta_q (score_or_null NULL: nothing added), beta_q in [1, 65536]; the maximum subtracted, the
+ *   floor applied; weights (n) int64: d = -log_weight, w = EXP2[(d & 0xFFFF) >> 8] >> (d >> 16) where d >> 16 <= 20, else 0; record,
+ *   TOHIP_MCL_RECORD int64: S1 = sum w, S2 = sum w^2, sum w X, sum w Y, sum w Z, sum w cos, sum w sin (TRIG's integers; the position
+ *   sums are exact while n max|X| < 2^43 and wrap modulo 2^64 beyond), the best index (the lowest i with log_weight 0), its score,
+ *   known and used (0 where the array is NULL), the verdict (1: n_eff < threshold), n_eff's bits (f64(S1) f64(S1) / f64(S2)), the
+ *   maximum subtracted, n, 0.  threshold: finite, >= 0.  workspace: TOHIP_MCL_WORKSPACE_BYTES, 8-byte aligned, contents ignored.
+ * tohip_mcl_resample_systematic: the verdict again from record's S1, S2 and `threshold` (record words 11 and 12 rewritten).  If 1: r = (word0 2^32
+ *   + word1) mod S1, t_j = (j S1 + r) div n, ancestors[j] = the least i with C_i > t_j (C: the inclusive prefix sum of weights, left in
+ *   cumulative (n) uint64), state_out[j] = state[ancestors[j]], log_weight = 0.  If 0: state_out = state, ancestors[j] = j, log_weight
+ *   untouched.  weights and record: tohip_mcl_weights' of the same state.
+ * flags is reserved and must be 0.  A bad n, p, m, sigma, delta, prior, beta_q, threshold, attitude (not finite) or flags, a null,
+ * misaligned or aliased buffer: TOHIP_EINVAL; short tables or workspace: TOHIP_ENOSPC.  Every argument check returns before anything
+ * is enqueued.  Nothing is read back. */
+#define TOHIP_MCL_TABLE_WORDS 34052
+#define TOHIP_MCL_GAUSS_WORD 32768
+#define TOHIP_MCL_EXP2_WORD 33796
+#define TOHIP_MCL_RECORD 16
+#define TOHIP_MCL_WORKSPACE_BYTES 81920
+int tohip_mcl_seed_gaussian(int32_t *state, int64_t *log_weight, int64_t n, const int32_t *tables, size_t tables_bytes,
+                            const int32_t *prior_host, const int32_t *sigma_q8_host, uint32_t seed_lo, uint32_t seed_hi, uint32_t step,
+                            void *stream, uint32_t flags);
+int tohip_mcl_seed_positions(int32_t *state, int64_t *log_weight, int64_t n, const tohip_occ_geom *geom, const float *positions, int64_t m,
+                             int32_t jitter, uint32_t seed_lo, uint32_t seed_hi, uint32_t step, void *stream, uint32_t flags);
+int tohip_mcl_predict(int32_t *state, int64_t n, const int32_t *tables, size_t tables_bytes, const int32_t *delta_host,
+                      const int32_t *sigma_q8_host, uint32_t seed_lo, uint32_t seed_hi, uint32_t step, void *stream, uint32_t flags);
+int tohip_mcl_poses(const int32_t *state, int64_t n, const int32_t *tables, size_t tables_bytes, const tohip_occ_geom *geom,
+                    const float *attitude_host, float *poses, void *stream, uint32_t flags);
+int tohip_mcl_weigh(const void *evid, size_t evid_bytes, const tohip_occ_geom *geom, int32_t floor_value, int32_t unknown_value,
+                    const float *points, int64_t p, const int32_t *state, int64_t n, const int32_t *tables, size_t tables_bytes,
+                    const float *attitude_host, int32_t *score, int32_t *used, int32_t *known, void *stream, uint32_t flags);
+int tohip_mcl_weights(const int32_t *state, int64_t *log_weight, int64_t n, const int32_t *tables, size_t tables_bytes,
+                      const int32_t *score_or_null, const int32_t *used_or_null, const int32_t *known_or_null, int32_t beta_q,
+                      double threshold, int64_t *weights, int64_t *record, void *workspace, size_t workspace_bytes, void *stream,
+                      uint32_t flags);
+int tohip_mcl_resample_systematic(const int32_t *state, int32_t *state_out, int64_t *log_weight, int64_t n, const int64_t *weights, int64_t *record,
+                       double threshold, uint64_t *cumulative, int32_t *ancestors, void *workspace, size_t workspace_bytes,
+                       uint32_t seed_lo, uint32_t seed_hi, uint32_t step, void *stream, uint32_t flags);
 
 /* ---- relocalisation (scansearch_kernels.hip, DESIGN.md §10, "Relocalisation") -------------------------
  * The best candidate of a WIDE window — |dx| <= wx, |dy| <= wy (0 <= wx, wy <= 2048), |dz| <= wz (0 <= wz <= 4), k rotations (1 <= k

@@ -21,6 +21,7 @@
 #include "field_kernels.hip"
 #include "evidence_kernels.hip"
 #include "scanmatch_kernels.hip"
+#include "particle_kernels.hip"
 #include "scanreg_kernels.hip"
 #include "posegraph_kernels.hip"
 #include "scansearch_kernels.hip"

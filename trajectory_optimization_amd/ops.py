@@ -5081,3 +5081,311 @@ def selftest_wave_reduce(mat64xk):
         check(_lib.lib().tohip_selftest_wave_reduce(ptr(mat64xk.contiguous()), k, ptr(s), ptr(mn), ptr(mx), stream_ptr()),
               "tohip_selftest_wave_reduce")
     return s, mn, mx
+
+
+# ---- the particle filter: Monte Carlo localisation on the evidence map (particle_kernels.hip, DESIGN.md 10 "Particle filter") -------
+MCL_MAX_N = 1 << 20
+MCL_TURN = 16384                   # heading units a turn
+MCL_CLAMP = (1 << 24) - 1          # |X|, |Y|, |Z| of a state, 1/256 voxel
+MCL_MAX_SIGMA = 65536.0            # state units: sigma_q8 = round(256 sigma) <= 2^24
+MCL_RECORD = _lib.CONSTANTS["TOHIP_MCL_RECORD"]
+MCL_RECORD_FIELDS = ("s1", "s2", "sum_x", "sum_y", "sum_z", "sum_cos", "sum_sin", "best", "best_score", "best_known", "best_used", "verdict",
+                     "n_eff_bits", "max_log_weight", "n", "zero")
+_MCL_TABLES = {}
+
+
+def particle_tables():
+    """The filter's three tables as the one int32 array the kernels take (TOHIP_MCL_TABLE_WORDS), built once on the host in f64 and
+    rounded once: TRIG[h] = round(32768 cos), round(32768 sin) of 2 pi h / 16384 at words 2 h, 2 h + 1; GAUSS[i] = round(4096
+    Phi^-1((i + 0.5) / 1025)), i = 0 .. 1024, at TOHIP_MCL_GAUSS_WORD; EXP2[j] = round(2^20 2^(-j / 256)), j = 0 .. 255, at
+    TOHIP_MCL_EXP2_WORD (synth.mcl_table_words_ref restates them)."""
+    if "words" not in _MCL_TABLES:
+        from statistics import NormalDist
+        C = _lib.CONSTANTS
+        words = np.zeros(C["TOHIP_MCL_TABLE_WORDS"], dtype=np.int32)
+        a = 2.0 * np.pi * np.arange(MCL_TURN, dtype=np.float64) / MCL_TURN
+        words[0:2 * MCL_TURN:2], words[1:2 * MCL_TURN:2] = np.rint(32768.0 * np.cos(a)), np.rint(32768.0 * np.sin(a))
+        nd = NormalDist()
+        words[C["TOHIP_MCL_GAUSS_WORD"]:C["TOHIP_MCL_GAUSS_WORD"] + 1025] = [round(4096.0 * nd.inv_cdf((i + 0.5) / 1025.0)) for i in range(1025)]
+        words[C["TOHIP_MCL_EXP2_WORD"]:C["TOHIP_MCL_EXP2_WORD"] + 256] = np.rint(2.0 ** 20 * 2.0 ** (-np.arange(256, dtype=np.float64) / 256.0))
+        _MCL_TABLES["words"] = words
+    return _MCL_TABLES["words"]
+
+
+def _mcl_four(v, name, scale):
+    """Four host numbers (x, y, z, heading) -> four f64 in state units: `scale` = (per position unit, per heading unit)."""
+    a = _host_rows(v, 4, name, rows=1)[0]
+    return np.array([a[0] * scale[0], a[1] * scale[0], a[2] * scale[0], a[3] * scale[1]], dtype=np.float64)
+
+
+def check_particles(map_or_matcher, n=1, seed=0, beta_q=256, floor=None, unknown_value=0, sigma=None, delta=None, ratio=None, attitude=None,
+                    units="metric"):
+    """A particle filter's settings and a step's arguments, by name; needs no GPU.  map_or_matcher: an ops.EvidenceMap, or an
+    ops.ScanMatcher (floor and unknown_value are then the matcher's and must be left at their defaults); n: an integer in [1, 2^20];
+    seed: an integer in [0, 2^64); beta_q: an integer in [1, 65536], Q16 halvings of weight per score unit; floor, unknown_value:
+    check_scan_match's.  sigma (None: not asked): four numbers >= 0 (x, y, z, heading), at most 65536 state units each; delta (None:
+    not asked): four numbers, at most 2^24 - 1 state units each in size; units 'metric' (metres and radians) or 'state' (1/256 voxel
+    and 1/16384 turn); ratio (None: not asked): a number in [0, 1]; attitude (None: the identity): nine finite numbers, a (3,3)
+    rotation.  -> dict(map, floor, unknown_value, n, seed, beta_q, sigma_q8, delta, ratio, attitude): sigma_q8 four ints round(256
+    sigma), delta four ints, attitude a (9,) f32 array or None; ValueError otherwise."""
+    if isinstance(map_or_matcher, ScanMatcher):
+        if floor is not None or not (_is_int(unknown_value) and unknown_value == 0):
+            raise ValueError(f"ParticleFilter: floor and unknown_value belong to the ScanMatcher that was given (floor {map_or_matcher.floor}, "
+                             f"unknown_value {map_or_matcher.unknown_value}); leave them at their defaults, got {floor!r} and {unknown_value!r}")
+        map, fl, unk = map_or_matcher.map, map_or_matcher.floor, map_or_matcher.unknown_value
+    else:
+        map = map_or_matcher
+        if not isinstance(map, EvidenceMap):
+            raise ValueError("ParticleFilter: the map must be an ops.EvidenceMap or an ops.ScanMatcher (EvidenceMap.from_space takes a SpaceMap), "
+                             f"got {type(map).__name__}")
+        fl, unk, _ = check_scan_match(map, floor, unknown_value)
+    if not _is_int(n) or not 1 <= n <= MCL_MAX_N:
+        raise ValueError(f"n must be an integer in [1, 2^20] particles, got {n!r}")
+    if not _is_int(seed) or not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+    if not _is_int(beta_q) or not 1 <= beta_q <= 65536:
+        raise ValueError(f"beta_q must be an integer in [1, 65536] (Q16 halvings per score unit), got {beta_q!r}")
+    if units not in ("metric", "state"):
+        raise ValueError(f"units must be 'metric' (metres, radians) or 'state' (1/256 voxel, 1/16384 turn), got {units!r}")
+    scale = (256.0 / float(map.resolution), MCL_TURN / (2.0 * np.pi)) if units == "metric" else (1.0, 1.0)
+    sigma_q8 = None
+    if sigma is not None:
+        s = _mcl_four(sigma, "sigma", scale)
+        if (s < 0.0).any() or (s > MCL_MAX_SIGMA).any():
+            raise ValueError(f"sigma must be four numbers >= 0 (x, y, z, heading) of at most 65536 state units, got {s.tolist()} state units")
+        sigma_q8 = [int(v) for v in np.rint(256.0 * s)]
+    if delta is not None:
+        d = np.rint(_mcl_four(delta, "delta", scale))
+        if (np.abs(d) > MCL_CLAMP).any():
+            raise ValueError(f"delta must be four numbers (x, y, z, heading) of at most 2^24 - 1 state units in size, got {d.tolist()} state units")
+        delta = [int(v) for v in d]
+    if ratio is not None:
+        try:
+            ratio = float(ratio)
+        except (TypeError, ValueError):
+            ratio = float("nan")
+        if not 0.0 <= ratio <= 1.0:
+            raise ValueError(f"ratio must be a number in [0, 1] (resample where n_eff < ratio n), got {ratio!r}")
+    if attitude is not None:
+        try:
+            a = np.asarray(attitude.detach().cpu().numpy() if torch.is_tensor(attitude) else attitude, dtype=np.float64)
+        except (TypeError, ValueError):
+            a = np.zeros(0)
+        if a.shape not in ((3, 3), (9,)) or not np.isfinite(a).all():
+            raise ValueError(f"attitude must be nine finite numbers, a (3,3) rotation, got {a.shape if a.size else type(attitude).__name__}")
+        attitude = a.reshape(9).astype(np.float32)
+    return dict(map=map, floor=fl, unknown_value=unk, n=int(n), seed=int(seed), beta_q=int(beta_q), sigma_q8=sigma_q8, delta=delta, ratio=ratio,
+                attitude=attitude)
+
+
+ParticleEstimate = collections.namedtuple("ParticleEstimate", "pose yaw quat best_pose best_yaw best_index best_score known used n_eff resampled "
+                                                              "state record")
+ParticleEstimate.__doc__ = """ParticleFilter.estimate(): pose (3,) f64, the weighted mean position in the world (origin + resolution
+(sum w X / S1) / 256); yaw, the weighted mean heading in radians (atan2 of sum w sin, sum w cos); quat (4,) wxyz of that heading;
+best_pose, best_yaw, best_index, best_score: the particle with the largest weight (the lowest index among equals) and scan matching's
+score of the last scan there; known, used: of its points, those that met an observed voxel and those in range; n_eff =
+S1^2 / S2; resampled: the last verdict; state (4,) f64, the mean in state units; record: the device record's 16 integers
+(MCL_RECORD_FIELDS)."""
+
+
+class ParticleFilter:
+    """Monte Carlo localisation on an evidence map (particle_kernels.hip, DESIGN.md 10 "Particle filter"): n pose hypotheses carried
+    from scan to scan.  predict() moves them by odometry plus noise, weigh() multiplies each weight by 2^(score beta_q / 65536) with
+    scan matching's score of the scan at the particle's pose, resample() draws a new generation where the weights have collapsed,
+    estimate() reads the answer.  The state lives on the device — .state (n,4) int32: x, y, z in 1/256 voxel from the map's origin
+    and a heading in 1/16384 turn about world z; .log_weight (n,) int64 in 1/65536 halvings — noise comes from Philox4x32-10 keyed by
+    `seed`, and every step is integer arithmetic: the same bits in every run, and synth.mcl_*_ref's bit for bit.  Only estimate()
+    reads anything back.  Roll and pitch are the caller's (`attitude`); the map's bytes are read as they are at each weigh() (no
+    refresh() is needed after an integrate)."""
+
+    def __init__(self, map_or_matcher, n, seed=0, beta_q=256, floor=None, unknown_value=0):
+        c = check_particles(map_or_matcher, n, seed, beta_q, floor, unknown_value)
+        self.map, self.floor, self.unknown_value, self.n, self.seed, self.beta_q = (c[k] for k in ("map", "floor", "unknown_value", "n", "seed",
+                                                                                                    "beta_q"))
+        m = self.map
+        self.origin, self.resolution, self.dims, self.device, self.geom = m.origin, m.resolution, m.dims, m.device, m.geom
+        self.step = 0
+        self.ratio = 0.5
+        dev, n = self.device, self.n
+        self.tables = torch.from_numpy(particle_tables()).to(dev)
+        self._states = [torch.empty((n, 4), dtype=torch.int32, device=dev) for _ in range(2)]
+        self.log_weight = torch.empty(n, dtype=torch.int64, device=dev)
+        self._weights = torch.empty(n, dtype=torch.int64, device=dev)
+        self._cumulative = torch.empty(n, dtype=torch.int64, device=dev)
+        self.ancestors = torch.empty(n, dtype=torch.int32, device=dev)
+        self.record = torch.empty(MCL_RECORD, dtype=torch.int64, device=dev)
+        self.scores = torch.empty((3, n), dtype=torch.int32, device=dev)   # score, used, known of the last weigh()
+        self._workspace = torch.empty(_lib.CONSTANTS["TOHIP_MCL_WORKSPACE_BYTES"], dtype=torch.uint8, device=dev)
+        self._seeded = self._weighed = False
+
+    @property
+    def state(self):
+        return self._states[0]
+
+    def _call(self, fn, *args):
+        with torch.cuda.device(self.device):
+            check(fn(*args, stream_ptr(), 0), fn.__name__)
+
+    def _key(self):
+        return self.seed & 0xFFFFFFFF, self.seed >> 32, self.step
+
+    def _tables(self):
+        return ptr(self.tables), self.tables.numel() * 4
+
+    @staticmethod
+    def _four(v):
+        return (ctypes.c_int32 * 4)(*v)
+
+    def _attitude(self, attitude):
+        a = check_particles(self.map, attitude=attitude)["attitude"]
+        return None if a is None else (ctypes.c_float * 9)(*a.tolist())
+
+    def _need(self, what, seeded=True, weighed=False):
+        if seeded and not self._seeded:
+            raise ValueError(f"ParticleFilter.{what}: seed the filter first (seed_gaussian or seed_positions)")
+        if weighed and not self._weighed:
+            raise ValueError(f"ParticleFilter.{what}: weigh a scan first (weigh)")
+
+    def state_units(self, pose, yaw):
+        """A world position (3,) and a heading in radians -> the four state integers (f64, rounded once)."""
+        p = np.rint(256.0 * (_host_rows(pose, 3, "pose", rows=1)[0] - np.asarray(self.origin, dtype=np.float64)) / float(self.resolution))
+        if (np.abs(p) > MCL_CLAMP).any():
+            raise ValueError(f"pose lies beyond 2^24 - 1 state units of the map's origin: {p.tolist()}")
+        return [int(v) for v in p] + [int(round(MCL_TURN * float(yaw) / (2.0 * np.pi))) % MCL_TURN]
+
+    def seed_gaussian(self, pose, yaw, sigma_xyz, sigma_yaw, units="metric"):
+        """Particles around a prior: pose (3,) in the world and yaw in radians (units='state': four state integers as `pose`, yaw
+        None), sigma_xyz one number or three and sigma_yaw, in metres and radians or in state units.  Every log-weight 0.  One
+        launch, nothing read back.  -> self."""
+        sx = np.broadcast_to(np.asarray(sigma_xyz, dtype=np.float64).reshape(-1), (3,))
+        c = check_particles(self.map, sigma=[sx[0], sx[1], sx[2], sigma_yaw], units=units)
+        if units == "state":
+            prior = [int(v) for v in _host_rows(pose, 4, "pose", rows=1)[0]]
+            if any(abs(v) > MCL_CLAMP for v in prior[:3]):
+                raise ValueError(f"pose lies beyond 2^24 - 1 state units of the map's origin: {prior}")
+            prior[3] %= MCL_TURN
+        else:
+            prior = self.state_units(pose, yaw)
+        self._call(_lib.lib().tohip_mcl_seed_gaussian, ptr(self.state), ptr(self.log_weight), self.n, *self._tables(), self._four(prior),
+                   self._four(c["sigma_q8"]), *self._key())
+        self._seeded, self._weighed = True, False
+        return self
+
+    def seed_positions(self, positions, jitter=True):
+        """A global start: particle i takes row (word0 mod M) of positions (M,3), floating point on the map's device — m.free.export(),
+        a field's free_nodes, known-free voxel centres — lands uniformly inside that row's voxel (jitter=False: at its centre) and
+        takes a uniform heading.  Every log-weight 0.  One launch, nothing read back.  -> self."""
+        if isinstance(positions, tuple) and len(positions) == 2:   # (ijk, centres): what OccupancyGrid.export() returns
+            positions = positions[1]
+        pts = covmap_points(positions, self.device, "ParticleFilter.seed_positions")
+        if not 1 <= pts.shape[0] < 1 << 31:
+            raise ValueError(f"ParticleFilter.seed_positions: 1 .. 2^31 - 1 positions, got {pts.shape[0]}")
+        self._call(_lib.lib().tohip_mcl_seed_positions, ptr(self.state), ptr(self.log_weight), self.n, ctypes.byref(self.geom), ptr(pts), pts.shape[0],
+                   1 if jitter else 0, *self._key())
+        self._seeded, self._weighed = True, False
+        return self
+
+    def predict(self, delta, sigma, units="metric"):
+        """The motion update: delta = (dx, dy, dz, dyaw), the odometry in the BODY frame, and sigma, four standard deviations of the
+        noise each particle adds to it; metres and radians, or state units.  The step counter advances first: every predict draws
+        fresh noise.  One launch, nothing read back.  -> self."""
+        self._need("predict")
+        c = check_particles(self.map, sigma=sigma, delta=delta, units=units)
+        self.step = (self.step + 1) & 0xFFFFFFFF
+        self._call(_lib.lib().tohip_mcl_predict, ptr(self.state), self.n, *self._tables(), self._four(c["delta"]), self._four(c["sigma_q8"]), *self._key())
+        return self
+
+    def poses12(self, attitude=None):
+        """-> (n,12) f32 on the device: scan matching's pose of every particle, R = Rz(heading) A row-major, then t — what
+        ScanMatcher.score and correlate take as poses12=.  attitude: A, a (3,3) rotation (an IMU's roll and pitch); None: the
+        identity.  One launch."""
+        self._need("poses12")
+        out = torch.empty((self.n, 12), dtype=torch.float32, device=self.device)
+        self._call(_lib.lib().tohip_mcl_poses, ptr(self.state), self.n, *self._tables(), ctypes.byref(self.geom), self._attitude(attitude), ptr(out))
+        return out
+
+    def weigh(self, points, attitude=None, ratio=None):
+        """The measurement update with one scan, points (P,3) in the SENSOR frame on the map's device, 1 <= P <= 2^22: every
+        particle's log-weight gains beta_q times scan matching's score of the scan at its pose; then the largest is subtracted, the
+        weights and their sums are formed and the record is written, with the verdict n_eff < ratio n; ratio None: self.ratio, what the
+        last weigh() or resample() was given (0.5 at first), otherwise it becomes self.ratio.  .scores holds (score, used,
+        known) per particle.  At most three clears and four launches, nothing read back.  -> self."""
+        self._need("weigh")
+        if ratio is not None:
+            self.ratio = check_particles(self.map, ratio=ratio)["ratio"]
+        pts = covmap_points(points, self.device, "ParticleFilter.weigh")
+        if not 1 <= pts.shape[0] <= SCAN_MAX_POINTS:
+            raise ValueError(f"ParticleFilter.weigh: the scan must hold 1 .. 2^22 points, got {pts.shape[0]}")
+        sc = self.scores
+        self._call(_lib.lib().tohip_mcl_weigh, *self.map._sizes(), self.floor, self.unknown_value, ptr(pts), pts.shape[0], ptr(self.state), self.n,
+                   *self._tables(), self._attitude(attitude), ptr(sc[0]), ptr(sc[1]), ptr(sc[2]))
+        return self._weights_call(sc)
+
+    def _weights_call(self, sc=None):
+        none = ctypes.c_void_p(0)
+        self._call(_lib.lib().tohip_mcl_weights, ptr(self.state), ptr(self.log_weight), self.n, *self._tables(),
+                   *((ptr(sc[0]), ptr(sc[1]), ptr(sc[2])) if sc is not None else (none, none, none)), self.beta_q, self.ratio * self.n,
+                   ptr(self._weights), ptr(self.record), ptr(self._workspace), self._workspace.numel())
+        self._best_row = self.state.index_select(0, self.record[7:8])   # (a device gather: the state moves on, the record does not)
+        self._weighed = True
+        return self
+
+    def normalise(self, ratio=None):
+        """The weights, their sums and the record from .log_weight as it stands, with no scan: after the caller wrote log-weights
+        of its own; ratio as in weigh().  Three launches.  -> self."""
+        self._need("normalise")
+        if ratio is not None:
+            self.ratio = check_particles(self.map, ratio=ratio)["ratio"]
+        return self._weights_call(None)
+
+    def weights(self):
+        """-> (n,) int64 on the device: the integer weights of the last weigh(), at most 2^20 each (the largest is exactly 2^20)."""
+        self._need("weights", weighed=True)
+        return self._weights
+
+    def resample(self, ratio=0.5):
+        """Systematic resampling, decided on the device: where n_eff = S1^2 / S2 < ratio n, generation j descends from the least i
+        with C_i > (j S1 + r) div n and every log-weight becomes 0; otherwise nothing changes.  .ancestors (n,) int32 names each
+        particle's parent (the identity where nothing changed).  The state is double-buffered: .state is the new tensor.  Four
+        launches, nothing read back.  -> self."""
+        self._need("resample", weighed=True)
+        self.ratio = check_particles(self.map, ratio=ratio)["ratio"]
+        self._call(_lib.lib().tohip_mcl_resample_systematic, ptr(self._states[0]), ptr(self._states[1]), ptr(self.log_weight), self.n, ptr(self._weights),
+                   ptr(self.record), self.ratio * self.n, ptr(self._cumulative), ptr(self.ancestors), ptr(self._workspace),
+                   self._workspace.numel(), *self._key())
+        self._states.reverse()
+        return self
+
+    def estimate(self):
+        """The answer after a weigh(): one read-back — the record and the best particle's row — -> ParticleEstimate.  The means are
+        formed on the host in f64 from the record's integer sums; they describe the weights of the last weigh(), also after a
+        resample() (whose equal weights would say the same up to its sampling)."""
+        self._need("estimate", weighed=True)
+        return _particle_estimate(self, torch.cat([self.record, self._best_row.reshape(-1).to(torch.int64)]).cpu().numpy())
+
+    def spread(self):
+        """-> (std (3,) f64 tensor, metres; circular std of the heading, radians, a 0-d f64 tensor) on the device: the weighted
+        spread of the particles as they are now, by torch ops in f64 from .log_weight and .state.  No bit promise: the reductions'
+        order is torch's."""
+        self._need("spread")
+        w = torch.exp2(self.log_weight.to(torch.float64) / 65536.0)
+        w = w / w.sum()
+        x = self.state[:, :3].to(torch.float64) * (float(self.resolution) / 256.0)
+        mean = (w[:, None] * x).sum(dim=0)
+        std = torch.sqrt((w[:, None] * (x - mean) ** 2).sum(dim=0))
+        a = self.state[:, 3].to(torch.float64) * (2.0 * np.pi / MCL_TURN)
+        R = torch.sqrt((w * torch.cos(a)).sum() ** 2 + (w * torch.sin(a)).sum() ** 2).clamp(1e-300, 1.0)
+        return std, torch.sqrt(-2.0 * torch.log(R))
+
+
+def _particle_estimate(pf, host):
+    rec = dict(zip(MCL_RECORD_FIELDS, (int(v) for v in host[:MCL_RECORD])))
+    row = [int(v) for v in host[MCL_RECORD:MCL_RECORD + 4]]
+    o, r = np.asarray(pf.origin, dtype=np.float64), float(pf.resolution)
+    mean = np.array([rec["sum_x"], rec["sum_y"], rec["sum_z"]], dtype=np.float64) / float(rec["s1"])
+    yaw = float(np.arctan2(float(rec["sum_sin"]), float(rec["sum_cos"])))
+    return ParticleEstimate(pose=o + r * mean / 256.0, yaw=yaw, quat=np.array([np.cos(0.5 * yaw), 0.0, 0.0, np.sin(0.5 * yaw)]),
+                            best_pose=o + r * np.asarray(row[:3], dtype=np.float64) / 256.0, best_yaw=2.0 * np.pi * row[3] / MCL_TURN,
+                            best_index=rec["best"], best_score=rec["best_score"], known=rec["best_known"], used=rec["best_used"],
+                            n_eff=float(rec["s1"]) * float(rec["s1"]) / float(rec["s2"]), resampled=bool(rec["verdict"]),
+                            state=np.append(mean, (yaw % (2.0 * np.pi)) * MCL_TURN / (2.0 * np.pi)), record=np.asarray(host[:MCL_RECORD]))

@@ -3297,3 +3297,285 @@ def pose_graph_loop(n, laps=1, sigma_t=0.02, sigma_r=0.01, closures=4, seed=0, r
         q[i + 1] = _quat_mul_np(q[i], oq[i])
     return dict(truth_t=truth_t, truth_q=truth_q, t=t, q=q, ab=np.concatenate([np.stack([a, a + 1], axis=1), np.stack([ca, cb], axis=1)]).astype(np.int32),
                 zt=np.concatenate([ot, ct]), zq=np.concatenate([oq, cq]), omega=np.concatenate([oo, co]), n_odometry=N - 1)
+
+
+# ---- the particle filter restated in numpy ("Particle filter"): what particle_kernels.hip must give, bit for bit ------
+MCL_MAX_N = 1 << 20
+MCL_CLAMP = (1 << 24) - 1
+MCL_FLOOR = -(1 << 40)
+MCL_MAX_SIGMA_Q8 = 1 << 24
+MCL_TURN = 16384
+MCL_RECORD = 16
+MCL_RECORD_FIELDS = ("s1", "s2", "sum_x", "sum_y", "sum_z", "sum_cos", "sum_sin", "best", "best_score", "best_known", "best_used", "verdict",
+                     "n_eff_bits", "max_log_weight", "n", "zero")
+MCL_GAUSS_WORD, MCL_EXP2_WORD, MCL_TABLE_WORDS = 32768, 33796, 34052
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32_ref(counter, key, rounds=10):
+    """Philox4x32 (Salmon et al. 2011): counter = four 32-bit words, key = two, each a number or an array (broadcast) -> (..., 4)
+    uint32.  Multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and 0xBB67AE85."""
+    c = [np.asarray(v, dtype=np.uint64) & _M32 for v in counter]
+    k = [np.asarray(v, dtype=np.uint64) & _M32 for v in key]
+    c0, c1, c2, c3 = np.broadcast_arrays(*c)
+    k0, k1 = k
+    for _ in range(rounds):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & _M32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & _M32, (k1 + np.uint64(0xBB67AE85)) & _M32
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def _mcl_words(n, step, stream, seed):
+    """The four words of particles 0 .. n - 1 -> (n, 4) int64: key (seed's low and high 32 bits), counter (i, 0, step, stream)."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return philox4x32_ref((np.arange(n), 0, int(step) & 0xFFFFFFFF, stream), (seed & 0xFFFFFFFF, seed >> 32)).astype(np.int64)
+
+
+def _norm_ppf(p):
+    """The standard normal's quantile by bisection on erfc, in f64 (no scipy)."""
+    lo, hi = -9.0, 9.0
+    for _ in range(80):
+        mid = 0.5 * (lo + hi)
+        if 0.5 * math.erfc(-mid / math.sqrt(2.0)) < p:
+            lo = mid
+        else:
+            hi = mid
+    return 0.5 * (lo + hi)
+
+
+def mcl_trig_table():
+    """TRIG (16384, 2) int32: round(32768 cos), round(32768 sin) of 2 pi h / 16384."""
+    a = 2.0 * np.pi * np.arange(MCL_TURN, dtype=np.float64) / MCL_TURN
+    return np.stack([np.rint(32768.0 * np.cos(a)), np.rint(32768.0 * np.sin(a))], axis=1).astype(np.int32)
+
+
+def mcl_gauss_table():
+    """GAUSS (1025,) int32: round(4096 Phi^-1((i + 0.5) / 1025)), a Q12 standard normal at 1025 knots."""
+    return np.array([int(round(4096.0 * _norm_ppf((i + 0.5) / 1025.0))) for i in range(1025)], dtype=np.int32)
+
+
+def mcl_exp2_table():
+    """EXP2 (256,) int32: round(2^20 2^(-j / 256))."""
+    return np.rint(2.0 ** 20 * 2.0 ** (-np.arange(256, dtype=np.float64) / 256.0)).astype(np.int32)
+
+
+_MCL_TABLES = {}
+
+
+def mcl_tables_ref():
+    """-> (TRIG, GAUSS, EXP2), built once."""
+    if not _MCL_TABLES:
+        _MCL_TABLES["t"] = (mcl_trig_table(), mcl_gauss_table(), mcl_exp2_table())
+    return _MCL_TABLES["t"]
+
+
+def mcl_table_words_ref():
+    """The tables as the one int32 buffer the kernels take: TRIG at word 0, GAUSS at 32768, EXP2 at 33796; 34052 words."""
+    trig, gauss, exp2 = mcl_tables_ref()
+    words = np.zeros(MCL_TABLE_WORDS, dtype=np.int32)
+    words[:2 * MCL_TURN] = trig.reshape(-1)
+    words[MCL_GAUSS_WORD:MCL_GAUSS_WORD + 1025] = gauss
+    words[MCL_EXP2_WORD:MCL_EXP2_WORD + 256] = exp2
+    return words
+
+
+def mcl_sigma_q8(sigma):
+    """sigma in state units -> round(256 sigma), an int in [0, 2^24]."""
+    q = np.rint(256.0 * np.asarray(sigma, dtype=np.float64)).astype(np.int64)
+    if (q < 0).any() or (q > MCL_MAX_SIGMA_Q8).any():
+        raise ValueError(f"sigma must lie in [0, 65536] state units, got {sigma!r}")
+    return q
+
+
+def mcl_gauss_ref(u):
+    """32-bit words -> the Q12 standard normal g: i = u >> 22, f = (u >> 6) & 0xFFFF, (GAUSS[i] (65536 - f) + GAUSS[i + 1] f) >> 16."""
+    gauss = mcl_tables_ref()[1].astype(np.int64)
+    u = np.asarray(u, dtype=np.int64)
+    i, f = u >> 22, (u >> 6) & 0xFFFF
+    return (gauss[i] * (65536 - f) + gauss[i + 1] * f) >> 16
+
+
+def mcl_noise_ref(u, sigma_q8):
+    """noise(u, sigma) = (g sigma_q8 + 2^19) >> 20, state units (arithmetic shift)."""
+    return (mcl_gauss_ref(u) * np.asarray(sigma_q8, dtype=np.int64) + (1 << 19)) >> 20
+
+
+def mcl_seed_gaussian_ref(n, prior, sigma_q8, seed=0, step=0):
+    """-> state (n, 4) int32: clamp(prior_a + noise(word_a, sigma_a)) for x, y, z; (prior_h + noise) mod 16384.  Stream 0."""
+    u = _mcl_words(n, step, 0, seed)
+    s = np.asarray(prior, dtype=np.int64).reshape(1, 4) + mcl_noise_ref(u, np.asarray(sigma_q8, dtype=np.int64).reshape(1, 4))
+    s[:, :3] = np.clip(s[:, :3], -MCL_CLAMP, MCL_CLAMP)
+    s[:, 3] %= MCL_TURN
+    return s.astype(np.int32)
+
+
+def mcl_seed_positions_ref(n, positions, origin, resolution, jitter=True, seed=0, step=0):
+    """-> state (n, 4) int32: particle i takes row word0 mod M of the world positions (M, 3): the voxel it lies in (occ_fixed's rule),
+    at 1/256 offsets word1 >> 24, (word1 >> 16) & 255, word2 >> 24 (128 each without jitter); heading word3 >> 18.  Stream 3."""
+    P = np.asarray(positions, dtype=np.float32).reshape(-1, 3)
+    u = _mcl_words(n, step, 3, seed)
+    q, _ = occ_fixed(P[u[:, 0] % P.shape[0]], origin, resolution)
+    j = np.stack([u[:, 1] >> 24, (u[:, 1] >> 16) & 0xFF, u[:, 2] >> 24], axis=1) if jitter else np.full((n, 3), 128, dtype=np.int64)
+    return np.concatenate([(q >> 8) * 256 + j, (u[:, 3] >> 18)[:, None]], axis=1).astype(np.int32)
+
+
+def mcl_predict_ref(state, delta, sigma_q8, seed=0, step=1):
+    """One motion update -> the new state (n, 4) int32.  n_a = delta_a + noise(word_a, sigma_a); (c, s) = TRIG[h]; X += (c n_x - s n_y +
+    2^14) >> 15, Y += (s n_x + c n_y + 2^14) >> 15, Z += n_z, clamped; h = (h + n_h) mod 16384.  Stream 1."""
+    s = np.asarray(state, dtype=np.int64).copy()
+    u = _mcl_words(s.shape[0], step, 1, seed)
+    nz = np.asarray(delta, dtype=np.int64).reshape(1, 4) + mcl_noise_ref(u, np.asarray(sigma_q8, dtype=np.int64).reshape(1, 4))
+    trig = mcl_tables_ref()[0].astype(np.int64)[s[:, 3] % MCL_TURN]
+    c, sn = trig[:, 0], trig[:, 1]
+    s[:, 0] += (c * nz[:, 0] - sn * nz[:, 1] + (1 << 14)) >> 15
+    s[:, 1] += (sn * nz[:, 0] + c * nz[:, 1] + (1 << 14)) >> 15
+    s[:, 2] += nz[:, 2]
+    s[:, :3] = np.clip(s[:, :3], -MCL_CLAMP, MCL_CLAMP)
+    s[:, 3] = (s[:, 3] % MCL_TURN + nz[:, 3]) % MCL_TURN
+    return s.astype(np.int32)
+
+
+def mcl_poses_ref(state, origin, resolution, attitude=None):
+    """-> (n, 12) f32, scan matching's pose of each particle: R = Rz(h) A in f32 — c32 = f32(c) 2^-15; row 0 fl(fl(c32 A_0j) - fl(s32
+    A_1j)), row 1 fl(fl(s32 A_0j) + fl(c32 A_1j)), row 2 A_2j — and t_a = fl(fl(f32(X_a) f32(resolution / 256)) + origin_a)."""
+    f32 = np.float32
+    s = np.asarray(state, dtype=np.int64)
+    A = np.eye(3, dtype=f32) if attitude is None else np.asarray(attitude, dtype=f32).reshape(3, 3)
+    trig = mcl_tables_ref()[0][s[:, 3] % MCL_TURN].astype(f32) * f32(2.0 ** -15)
+    c, sn = trig[:, 0:1], trig[:, 1:2]
+    r0 = ((c * A[0][None, :]).astype(f32) - (sn * A[1][None, :]).astype(f32)).astype(f32)
+    r1 = ((sn * A[0][None, :]).astype(f32) + (c * A[1][None, :]).astype(f32)).astype(f32)
+    r2 = np.broadcast_to(A[2][None, :], r0.shape)
+    r256 = f32(f32(resolution) / f32(256.0))
+    t = ((s[:, :3].astype(f32) * r256).astype(f32) + np.asarray(origin, dtype=f32).reshape(1, 3)).astype(f32)
+    return np.ascontiguousarray(np.concatenate([r0, r1, r2, t], axis=1), dtype=f32)
+
+
+def mcl_weigh_ref(L, origin, resolution, points, state, attitude=None, floor=None, unknown_value=0, chunk=128):
+    """-> (score, used, known), each (n,) int32: scan matching's score, used and known of the scan at every particle's pose (zero
+    shift), by scan_score_ref's rules, `chunk` particles at a time."""
+    f32 = np.float32
+    L = np.asarray(L, dtype=np.int64)
+    V = scan_values_ref(L, floor, unknown_value)
+    P = np.asarray(points, dtype=f32).reshape(-1, 3)
+    T = mcl_poses_ref(state, origin, resolution, attitude)
+    n = T.shape[0]
+    score, used, known = (np.zeros(n, dtype=np.int64) for _ in range(3))
+    dims = np.asarray(L.shape)
+    for a in range(0, n, chunk):
+        Tc = T[a:a + chunk]
+        with np.errstate(all="ignore"):
+            cols = []
+            for ax in range(3):
+                w = ((Tc[:, 3 * ax, None] * P[None, :, 0]).astype(f32) + (Tc[:, 3 * ax + 1, None] * P[None, :, 1]).astype(f32)).astype(f32)
+                w = (w + (Tc[:, 3 * ax + 2, None] * P[None, :, 2]).astype(f32)).astype(f32)
+                cols.append((w + Tc[:, 9 + ax, None]).astype(f32))
+            W = np.stack(cols, axis=2)
+        q, ok = occ_fixed(W.reshape(-1, 3), origin, resolution)
+        v = (q >> 8).reshape(W.shape)
+        ok = ok.reshape(W.shape[:2])
+        ins = ok & ((v >= 0) & (v < dims[None, None, :])).all(axis=2)
+        vc = np.where(ins[:, :, None], v, 0)
+        Lp = L[vc[:, :, 0], vc[:, :, 1], vc[:, :, 2]]
+        kn = ins & (Lp != EVID_UNKNOWN)
+        val = np.where(ins, V[vc[:, :, 0], vc[:, :, 1], vc[:, :, 2]], int(unknown_value))
+        score[a:a + chunk] = np.where(ok, val, 0).sum(axis=1)
+        used[a:a + chunk] = ok.sum(axis=1)
+        known[a:a + chunk] = kn.sum(axis=1)
+    return score.astype(np.int32), used.astype(np.int32), known.astype(np.int32)
+
+
+def mcl_weight_ref(log_weight):
+    """Normalised log-weights (<= 0) -> w int64: d = -log_weight, EXP2[(d & 0xFFFF) >> 8] >> (d >> 16) where d >> 16 <= 20, else 0."""
+    d = -np.asarray(log_weight, dtype=np.int64)
+    q = d >> 16
+    e = mcl_tables_ref()[2].astype(np.int64)[(d & 0xFFFF) >> 8]
+    return np.where(q <= 20, e >> np.minimum(q, 20), 0)
+
+
+def mcl_n_eff(s1, s2):
+    """f64(S1) f64(S1) / f64(S2): one conversion each, one multiply, one divide."""
+    return float(int(s1)) * float(int(s1)) / float(int(s2))
+
+
+def mcl_weights_ref(state, log_weight, score=None, beta_q=256, threshold=0.0, used=None, known=None):
+    """One weight update -> (log_weight (n,) int64, w (n,) int64, record (16,) int64): log_weight += score beta_q (score None: nothing
+    added), the maximum subtracted, the floor -2^40 applied, the weights, and the record MCL_RECORD_FIELDS names.  The integer sums
+    wrap modulo 2^64 as the device's do."""
+    s = np.asarray(state, dtype=np.int64)
+    lw = np.asarray(log_weight, dtype=np.int64).copy()
+    if score is not None:
+        lw = lw + np.asarray(score, dtype=np.int64) * int(beta_q)
+    m = int(lw.max())
+    lw = np.maximum(lw - m, MCL_FLOOR)
+    w = mcl_weight_ref(lw)
+    trig = mcl_tables_ref()[0].astype(np.int64)[s[:, 3] % MCL_TURN]
+    with np.errstate(over="ignore"):
+        sums = [w.sum(), (w * w).sum(), (w * s[:, 0]).sum(), (w * s[:, 1]).sum(), (w * s[:, 2]).sum(), (w * trig[:, 0]).sum(), (w * trig[:, 1]).sum()]
+    best = int(np.flatnonzero(lw == 0)[0])
+    n_eff = mcl_n_eff(sums[0], sums[1])
+    pick = lambda a: 0 if a is None else int(np.asarray(a)[best])   # noqa: E731
+    rec = [int(v) for v in sums] + [best, pick(score), pick(known), pick(used), int(n_eff < float(threshold)),
+                                    int(np.float64(n_eff).view(np.int64)), m, s.shape[0], 0]
+    return lw, w, np.array(rec, dtype=np.int64)
+
+
+def mcl_ancestors_ref(w, r):
+    """The systematic resample -> ancestors (n,) int64: t_j = (j S1 + r) div n, a_j = the least i with C_i > t_j, C the inclusive prefix
+    sum of w; r in [0, S1)."""
+    w = np.asarray(w, dtype=np.uint64)
+    n = w.shape[0]
+    C = np.cumsum(w, dtype=np.uint64)
+    s1 = int(C[-1])
+    if not 0 <= int(r) < s1 or n * s1 + s1 >= 1 << 64:
+        raise ValueError("r must lie in [0, S1) and n S1 fit 64 bits")
+    t = (np.arange(n, dtype=np.uint64) * np.uint64(s1) + np.uint64(int(r))) // np.uint64(n)
+    return np.searchsorted(C, t, side="right").astype(np.int64)
+
+
+def mcl_resample_ref(state, log_weight, w, threshold, seed=0, step=0):
+    """-> (state, log_weight, ancestors (n,) int32, verdict): resample iff n_eff < threshold, with r = (word0 2^32 + word1) mod S1 of the
+    words of counter (0, 0, step, 2); otherwise the state and the log-weights as they are and the identity."""
+    s, lw, w = np.asarray(state, dtype=np.int32), np.asarray(log_weight, dtype=np.int64), np.asarray(w, dtype=np.int64)
+    s1, s2 = int(w.sum()), int((w * w).sum())
+    if not mcl_n_eff(s1, s2) < float(threshold):
+        return s.copy(), lw.copy(), np.arange(s.shape[0], dtype=np.int32), 0
+    u = _mcl_words(1, step, 2, seed)[0]
+    a = mcl_ancestors_ref(w, ((int(u[0]) << 32) + int(u[1])) % s1)
+    return s[a].copy(), np.zeros_like(lw), a.astype(np.int32), 1
+
+
+def mcl_estimate_ref(record, origin, resolution):
+    """The record -> dict: mean position (world, f64: origin + resolution (sum / S1) / 256), mean heading (radians, atan2 of the two
+    sums), n_eff, best index."""
+    rec = dict(zip(MCL_RECORD_FIELDS, (int(v) for v in record)))
+    mean = np.array([rec["sum_x"], rec["sum_y"], rec["sum_z"]], dtype=np.float64) / float(rec["s1"])
+    return dict(state=mean, position=np.asarray(origin, dtype=np.float64) + float(resolution) * mean / 256.0,
+                yaw=math.atan2(float(rec["sum_sin"]), float(rec["sum_cos"])), n_eff=mcl_n_eff(rec["s1"], rec["s2"]), best=rec["best"])
+
+
+def mcl_state_units(pose, yaw, origin, resolution):
+    """A world position (3,) and a heading in radians -> the four state integers: round(256 (p - origin) / resolution), round(16384 yaw
+    / 2 pi) mod 16384, in f64."""
+    p = np.rint(256.0 * (np.asarray(pose, dtype=np.float64).reshape(3) - np.asarray(origin, dtype=np.float64).reshape(3)) / float(resolution))
+    return [int(v) for v in p] + [int(round(MCL_TURN * float(yaw) / (2.0 * math.pi))) % MCL_TURN]
+
+
+def mcl_filter_ref(L, origin, resolution, scans, deltas, sigmas_q8, prior, prior_sigma_q8, n, seed=0, beta_q=256, ratio=0.5, floor=None,
+                   unknown_value=0, attitude=None):
+    """The whole loop restated: seed_gaussian at step 0, then per scan predict (step k + 1) -> weigh -> weights -> resample.  deltas
+    (K, 4) in state units, sigmas_q8 (4,) -> a list of dicts: state and log_weight after the update, record, ancestors, score."""
+    state = mcl_seed_gaussian_ref(n, prior, prior_sigma_q8, seed, 0)
+    lw = np.zeros(n, dtype=np.int64)
+    out = []
+    for k, pts in enumerate(scans):
+        step = k + 1
+        state = mcl_predict_ref(state, deltas[k], sigmas_q8, seed, step)
+        score, used, known = mcl_weigh_ref(L, origin, resolution, pts, state, attitude, floor, unknown_value)
+        lw, w, rec = mcl_weights_ref(state, lw, score, beta_q, ratio * n, used, known)
+        weighed = state
+        state, lw, anc, verdict = mcl_resample_ref(state, lw, w, ratio * n, seed, step)
+        assert verdict == rec[11]
+        out.append(dict(state=state, log_weight=lw, record=rec, ancestors=anc, score=score, weighed_state=weighed, weights=w))
+    return out

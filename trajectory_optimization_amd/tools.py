@@ -2032,3 +2032,41 @@ def propose_views(points_or_cloud_or_model, positions, n_per_position=2, sectors
     qtable = torch.from_numpy(propose_tables(S)[1]).to(dev)
     return ViewProposals(poses=P[p], quats=qtable[h], score=s, position_index=p, heading=h.to(torch.int32), hist=hist, open=is_open,
                          weights=weights, sectors=S, hw=hw, tan_v=tan_v, min_dist=mn, max_dist=mx)
+
+
+def particle_filter(map_or_matcher, n=4096, seed=0, beta_q=256, floor=None, unknown_value=0):
+    """Where is the robot, scan after scan?  An ops.ParticleFilter ("Particle filter") on an ops.EvidenceMap — or on an
+    ops.ScanMatcher, whose floor and unknown_value it takes: n pose hypotheses on the device that predict() moves by odometry,
+    weigh() judges by scan matching's score, resample() renews and estimate() reads.  pf.seed_gaussian(pose, yaw, sigma_xyz,
+    sigma_yaw) starts from a prior, pf.seed_positions(m.free.export()) from everywhere the map knows to be free.  beta_q: how sharply
+    a score unit halves a weight, in 1/65536 (256: a weight halves per 256 score units)."""
+    if isinstance(map_or_matcher, ops.SpaceMap):
+        raise ValueError("particle_filter: a SpaceMap holds no log-odds: give ops.EvidenceMap.from_space(space)")
+    return ops.ParticleFilter(map_or_matcher, n, seed, beta_q, floor, unknown_value)
+
+
+def localise_particles(map_or_matcher, scans, deltas, pose, yaw, sigma_xyz, sigma_yaw, motion_sigma, n=4096, seed=0, beta_q=256, ratio=0.5,
+                       floor=None, unknown_value=0, attitudes=None, units="metric", filter=None):
+    """Track a robot over a sequence: scans, K tensors (P_k,3) in the SENSOR frame, and deltas (K,4), the odometry (dx, dy, dz, dyaw)
+    in the body frame that led to each.  The filter is seeded around (pose, yaw) with (sigma_xyz, sigma_yaw) — or `filter`, an
+    ops.ParticleFilter already seeded, is carried on — and runs predict(delta_k, motion_sigma) -> weigh(scan_k) -> resample(ratio)
+    per scan.  attitudes: None or K (3,3) rotations, the roll and pitch at each scan.  units: of deltas and sigmas, 'metric' or
+    'state'.  -> (estimates, filter): K ops.ParticleEstimate, each of the weights before that step's resample.  One read-back per
+    scan (the estimate); deltas and attitudes are host numbers."""
+    d = ops._host_rows(deltas, 4, "deltas")
+    scans = list(scans)
+    if len(scans) != d.shape[0] or (attitudes is not None and len(attitudes) != len(scans)):
+        raise ValueError(f"localise_particles: as many scans, deltas and attitudes, got {len(scans)}, {d.shape[0]}"
+                         f"{'' if attitudes is None else ', ' + str(len(attitudes))}")
+    pf = filter
+    if pf is None:
+        pf = particle_filter(map_or_matcher, n, seed, beta_q, floor, unknown_value).seed_gaussian(pose, yaw, sigma_xyz, sigma_yaw, units=units)
+    elif not isinstance(pf, ops.ParticleFilter):
+        raise ValueError(f"localise_particles: filter must be an ops.ParticleFilter, got {type(pf).__name__}")
+    estimates = []
+    for k, pts in enumerate(scans):
+        pf.predict(d[k], motion_sigma, units=units)
+        pf.weigh(pts, None if attitudes is None else attitudes[k], ratio=ratio)
+        estimates.append(pf.estimate())
+        pf.resample(ratio)
+    return estimates, pf
